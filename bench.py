@@ -557,6 +557,27 @@ def cpu_baseline(vghf, nrm, tf_path, size, planes, xform, mv, gpu_frame, budget_
             "host_cpus": os.cpu_count(), "parity_max_abs_err_vs_gpu": err}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_PIXELS = 1 << 20
+
+
+def dump_outputs(d, frame, size):
+    """What the timed path hands its caller, from its last timed step: the RGBA float32 frame (on rank 0 the merged one),
+    as d/frame.npy [size, size, 4].  A frame above 64 MB is written as a fixed sample instead: the pixels of a seeded
+    draw (d/frame_sample_pixels.npy, row-major pixel indices as float64) and their RGBA (d/frame_sample.npy)."""
+    torch.cuda.synchronize()
+    os.makedirs(d, exist_ok=True)
+    img = frame.view(size * size, 4).cpu().numpy()
+    if img.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(d, "frame.npy"), img.reshape(size, size, 4))
+        return {"dir": d, "files": ["frame.npy"], "shape": [size, size, 4], "dtype": "float32"}
+    pix = np.sort(np.random.default_rng(0).choice(size * size, DUMP_SAMPLE_PIXELS, replace=False))
+    np.save(os.path.join(d, "frame_sample_pixels.npy"), pix.astype(np.float64))
+    np.save(os.path.join(d, "frame_sample.npy"), img[pix])
+    return {"dir": d, "files": ["frame_sample_pixels.npy", "frame_sample.npy"], "shape": [DUMP_SAMPLE_PIXELS, 4],
+            "dtype": "float32", "sampled_from": [size, size, 4]}
+
+
 def launch_ranks(n):
     """`python bench.py --gpus N` without a launcher: start N ranks of this very command under
     torch.distributed.run (one process per GPU), relay their output and exit with their code.  Runs
@@ -593,7 +614,11 @@ def main():
     ap.add_argument("--no-north-star", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the secondary timings (dense / opaque tables, config 5)")
     ap.add_argument("--north-star-volume", type=int, default=1024)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame the timed steps computed in their last step to DIR/*.npy (float32; rank 0)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(a.gpus))
 
@@ -698,6 +723,7 @@ def main():
     with torch.cuda.stream(work):
         t, kms, kn = timed(r, a.steps, a.warmup, frame, world, cstate)
     kernel, _, alg_bytes = r.last_frame_info()
+    dumped = dump_outputs(a.dump_outputs, frame, size) if a.dump_outputs and rank == 0 else None
     ms = t / a.steps * 1e3
     default_workload = (n, size, planes) == (512, 1024, 512)
     samples = float(size) * size * planes
@@ -735,6 +761,8 @@ def main():
         out["workgroups"] = workgroup_load(r)
         if world == 1 and not a.no_extra and flags_on:
             out["without_brick_flags"] = no_flags_leg(r, work, frame, size, planes, a.steps)
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     failures = int(r.stat("slab_failures"))
     if world > 1:
         # every rank's own figures on the one line: kernel time of its shard, longest workgroup against the mean slot load,
