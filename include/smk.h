@@ -139,10 +139,11 @@ int smk_set_perturb(smk_ctx *ctx, const unsigned char *noise_rgba, int n, const 
  * :2991-3180) under the light's projection (LTWidgetRen::genXForm, LTWidgetRen.cpp:231-291).  Uses the
  * light position, eye, at and xform of smk_set_shading.  buffer_px = gluvv.light.buffsz[0], quality =
  * gluvv.light.gShadowQual or iShadowQual: the light buffer has ceil(quality * buffer_px)^2 texels.
- * Applies to 2-D / 3-D classification with no or R8k shading on an unsharded context, with or without the clip-plane
- * widget's planes (smk_set_clip, smk_set_clip_plane: both passes leave out what lies beyond them, as the reference's
- * clipped slice polygons do); other configurations (1-D table, NV20 combiners, perturbation, a sub-box, depth output,
- * shards) make smk_render fail with the reason.  The blend order follows the light (under when
+ * Applies to 2-D / 3-D classification with no or R8k shading, with or without the clip-plane widget's planes
+ * (smk_set_clip, smk_set_clip_plane: both passes leave out what lies beyond them, as the reference's clipped slice polygons
+ * do); other configurations (1-D table, NV20 combiners, perturbation, a sub-box, depth output) make smk_render fail with
+ * the reason.  A shard (smk_set_shard) renders shadows once it has this frame's light entries (smk_shadow_exports_device,
+ * smk_shadow_entries_device below; without them smk_render fails) and a halo of smk_get_shadow_margin's halo_needed.  The blend order follows the light (under when
  * the slices run away from the eye, over otherwise), smk_set_blend is not consulted.
  * How it is rendered: a light-buffer texel depends on itself alone from slice to slice, so the light pass is
  * ONE march per texel that keeps every slice's buffer (nslices + 1 buffers in device memory), and the eye pass is an
@@ -294,6 +295,34 @@ typedef struct {
 int smk_get_shadowcoef(smk_ctx *ctx, smk_shadowcoef *out);
 /* the light buffer as the last frame with shadows left it: [LB][LB][4] floats to HOST memory (synchronises) */
 int smk_get_light_buffer(smk_ctx *ctx, float *rgba_out, int *lb_out);
+/* the light buffer after slices 1..k (k = 0..nslices; 0 = cleared) of the last frame with shadows rendered with the two
+ * marches: [LB][LB][4] floats to HOST memory (synchronises).  On a shard only the texels whose slice-k sample lies within
+ * the margin of the shard's region hold the unsharded frame's values (they are all its eye pass looks up). */
+int smk_get_light_history(smk_ctx *ctx, int k, float *rgba_out);
+
+/* Shadows on shards ("Shadows on shards").  The reference draws the bricks of a shadowed volume one after
+ * another against one light buffer (R8kVolRen3D.cpp:582-679, volShadow :1651-1868); here every rank marches its own light
+ * samples.  A light-buffer texel's ray crosses the shards' boxes in the light's BSP order, so the buffer rank j reads is
+ * E_j over H_j: H_j = j's own march over the samples within its margin m of its region, E_j = the other ranks' samples
+ * before the ray reaches that, which they send.  Per frame, after the camera, light and tables are set on every rank:
+ *   1. smk_shadow_exports_device on every rank r: X_{r->j} for every rank j, [nranks][LB][LB][4] floats (slot r zero),
+ *      enqueued on `stream` (NULL: the context's stream);
+ *   2. every rank j receives slot j of every rank's exports, in rank order, [nranks][LB][LB][4] floats, and hands them to
+ *      smk_shadow_entries_device (copied on `stream`, consumed by the next smk_render[_device] -- which fails without);
+ *   3. smk_render[_device] on every rank, merged with smk_composite_over_device in smk_shard_order's order.
+ * smk_shadow_exchange_local runs steps 1-2 for contexts of one process (device-to-device copies, peer copies between
+ * devices; it synchronises every rank's stream).  The halo (option "halo", before upload) must be at least
+ * smk_get_shadow_margin's halo_needed = m + 1.  Frames stay within a few ulp of the unsharded frame (the over of the light
+ * buffer is associated differently).  Not provided: a transport of the light exchange over RCCL (smk_exchange_* with an id:
+ * a host moves the exports itself between steps 1 and 2), bench.py legs, and shards with option shadow_march 0 or
+ * shadow_fused (the per-slice and cooperative paths stay single-GPU: smk_render fails). */
+int smk_shadow_exports_device(smk_ctx *ctx, void *d_exports, void *stream);
+int smk_shadow_entries_device(smk_ctx *ctx, const void *d_entries, void *stream);
+int smk_shadow_exchange_local(smk_ctx *const *all, int nranks);
+/* the ranks in the light's BSP order, nearest the light first (smk_shard_order's rule from the light rays' apex) */
+int smk_shard_light_order(smk_ctx *ctx, int *order_out /* nranks */);
+/* margin m (voxels) of this shard's frame with shadows and the halo it needs (m + 1); per frame: it follows the light */
+int smk_get_shadow_margin(smk_ctx *ctx, int *m, int *halo_needed);
 /* Empty-space skipping (option "bricks", no reference counterpart: the reference draws every slice and lets the blend
  * unit discard what the table made transparent, VolumeRenderer.cpp:507-741).  The flags the NEXT frame would use, for
  * checkers: one byte per brick of 8x8x8 cells of this context's stored box, x fastest, 1 = some sample whose cell lies
@@ -326,7 +355,7 @@ int smk_get_brick_flags(smk_ctx *ctx, unsigned char *flags_out, int *nb_out, int
  *   (test hook: the next slice-ring frame reports this status word) */
 int smk_set_option(smk_ctx *ctx, const char *key, int value);
 /* samples of the current frame set-up that lie inside the volume (region and clip planes counted in): the renderers'
- * membership test for every plane of every ray, nothing fetched.  SURVEY 8(d)'s "in-volume sample count", to be read
+ * membership test for every plane of every ray, nothing fetched (with shadows on: the eye pass's half-angle slices).  SURVEY 8(d)'s "in-volume sample count", to be read
  * beside the nominal width x height x planes.  Synchronises. */
 int smk_count_samples(smk_ctx *ctx, double *in_volume);
 /* last frame: which kernel ran (1 gather, 2 slice-ring, 3 the per-slice shadow passes of option shadow_march 0, 4 column-
@@ -340,7 +369,8 @@ int smk_timing_read(smk_ctx *ctx, float *avg_ms, int *nframes);
 /* named counters of the last frame (developer statistics, no reference counterpart):
  * "slab_iters", "slab_active_lanes", "slab_inside_lanes" (lanes that interpolate a sample: not skipped as part of an
  * empty layer), "slab_hit_lanes" (collected when option
- * lockstep has bit 16 set), "slab_status" (these synchronise the device); "slab_failures",
+ * lockstep has bit 16 set), "slab_status" (these synchronise the device); "light_samples" (the light-march samples of
+ * the current frame with shadows this context owns -- all of them on the whole volume; synchronises); "slab_failures",
  * "slab_retries" (host-side counters, no synchronisation). */
 int smk_get_stat(smk_ctx *ctx, const char *name, double *value);
 /* workgroup timeline of the last slice-ring frame (developer tool):

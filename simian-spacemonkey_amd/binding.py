@@ -26,6 +26,8 @@ ABI_SYMBOLS = [
     "smk_exchange_last_error", "smk_exchange_partial", "smk_exchange_acquire", "smk_exchange_rendered", "smk_exchange_frame",
     "smk_exchange_frame_local", "smk_exchange_wait", "smk_exchange_set_order",
     "smk_set_region", "smk_render_slice", "smk_render_slice_device", "smk_count_samples",
+    "smk_get_light_history", "smk_shadow_exports_device", "smk_shadow_entries_device", "smk_shadow_exchange_local",
+    "smk_shard_light_order", "smk_get_shadow_margin",
 ]
 
 # gluvvDataMode order (gluvv.h:221-235)
@@ -135,6 +137,12 @@ def load_library():
     L.smk_set_shadow.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float]
     L.smk_get_shadowcoef.argtypes = [C.c_void_p, P(ShadowCoef)]
     L.smk_get_light_buffer.argtypes = [C.c_void_p, C.c_void_p, P(C.c_int)]
+    L.smk_get_light_history.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.smk_shadow_exports_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.smk_shadow_entries_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.smk_shadow_exchange_local.argtypes = [P(C.c_void_p), C.c_int]
+    L.smk_shard_light_order.argtypes = [C.c_void_p, P(C.c_int)]
+    L.smk_get_shadow_margin.argtypes = [C.c_void_p, P(C.c_int), P(C.c_int)]
     L.smk_get_brick_flags.argtypes = [C.c_void_p, C.c_void_p, P(C.c_int), P(C.c_int)]
     L.smk_render.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.smk_render_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -217,6 +225,7 @@ class Renderer:
         self.ctx = self.L.smk_create(device, C.byref(err))
         if not self.ctx:
             raise SmkError(self.L.smk_last_error(None).decode())
+        self.device = device
         self.size = (0, 0)
         self._keep = []
 
@@ -368,6 +377,33 @@ class Renderer:
         self._ck(self.L.smk_get_light_buffer(self.ctx, out.ctypes.data_as(C.c_void_p), C.byref(lb)))
         return out
 
+    def light_history(self, k):
+        """the light buffer after slices 1..k of the last frame with shadows (two marches): [LB][LB][4] float32"""
+        lb = int(self.shadowcoef().LB)
+        out = np.zeros((lb, lb, 4), np.float32)
+        self._ck(self.L.smk_get_light_history(self.ctx, int(k), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    # -- shadows on shards (smk.h: smk_shadow_exports_device ...)
+    def shadow_exports_device(self, d_exports, stream=None):
+        """phase 1: X_{this->j} for every rank j into [nranks][LB][LB][4] float32 device memory"""
+        self._ck(self.L.smk_shadow_exports_device(self.ctx, d_exports, stream))
+
+    def shadow_entries_device(self, d_entries, stream=None):
+        """X_{r->this} of every rank r, [nranks][LB][LB][4] float32 device memory, for the next frame"""
+        self._ck(self.L.smk_shadow_entries_device(self.ctx, d_entries, stream))
+
+    def shard_light_order(self, nranks):
+        o = (C.c_int * nranks)()
+        self._ck(self.L.smk_shard_light_order(self.ctx, o))
+        return list(o)
+
+    def shadow_margin(self):
+        """(m, halo_needed) of this shard's frame with shadows"""
+        m, h = C.c_int(0), C.c_int(0)
+        self._ck(self.L.smk_get_shadow_margin(self.ctx, C.byref(m), C.byref(h)))
+        return m.value, h.value
+
     def brick_flags(self):
         """(flags [nbz][nby][nbx] uint8, in_use) -- the empty-space flags the next frame would use (smk_get_brick_flags)"""
         nb = (C.c_int * 3)()
@@ -489,6 +525,15 @@ class Renderer:
     def synth_volume_device(self, kind, seed, dims, d_out):
         sx, sy, sz = dims
         self._ck(self.L.smk_synth_volume_device(self.ctx, kind, seed, sx, sy, sz, d_out))
+
+
+def shadow_exchange_local(renderers):
+    """phase 1 and the light exchange of a frame with shadows for shard contexts of this process, in rank order"""
+    arr = (C.c_void_p * len(renderers))(*[r.ctx for r in renderers])
+    rc = renderers[0].L.smk_shadow_exchange_local(arr, len(renderers))
+    if rc != 0:
+        msgs = [r.L.smk_last_error(r.ctx).decode() for r in renderers]
+        raise SmkError(next((m for m in msgs if m), "smk_shadow_exchange_local failed"))
 
 
 def exchange_unique_id():

@@ -190,7 +190,7 @@ extern "C" void smk_destroy(smk_ctx *c) {
   if (c->tf_stream) { (void)hipStreamSynchronize(c->tf_stream); (void)hipStreamDestroy(c->tf_stream); }
   free_brick_set(c->br3);
   smk_cols_free(&c->cols);
-  void *ptrs[] = {c->d_light_hist, c->d_shadow_barrier, c->d_tf_raw, c->d_tlut, c->d_tf_h, c->d_tf3d, c->d_tf3d_occ, c->d_noise, c->d_out, c->d_depth, c->d_light[0], c->d_light[1]};
+  void *ptrs[] = {c->d_light_hist, c->d_shadow_entries, c->d_shadow_exports, c->d_shadow_barrier, c->d_tf_raw, c->d_tlut, c->d_tf_h, c->d_tf3d, c->d_tf3d_occ, c->d_noise, c->d_out, c->d_depth, c->d_light[0], c->d_light[1]};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   if (c->slab.h_status) (void)hipHostFree(c->slab.h_status);
@@ -254,7 +254,8 @@ __global__ void smk_k_pack(const void *src, const unsigned char *grad, int bx, i
   }
 }
 
-static void shard_region(const smk_ctx *c, int g0[3], int g1[3]) {
+// the region of shard `rank` of `nranks`
+static void shard_region_of(const smk_ctx *c, int rank, int g0[3], int g1[3]) {
   for (int a = 0; a < 3; ++a) {
     g0[a] = 0;
     g1[a] = c->N[a];
@@ -262,10 +263,12 @@ static void shard_region(const smk_ctx *c, int g0[3], int g1[3]) {
   int bit = 0;
   for (int n = c->nranks; n > 1; n >>= 1, ++bit) {
     int a = bit % 3, half = c->N[a] / 2;  // bit 0 splits x, bit 1 y, bit 2 z
-    if ((c->rank >> bit) & 1) g0[a] = std::max(g0[a], half);
+    if ((rank >> bit) & 1) g0[a] = std::max(g0[a], half);
     else g1[a] = std::min(g1[a], half);
   }
 }
+
+static void shard_region(const smk_ctx *c, int g0[3], int g1[3]) { shard_region_of(c, c->rank, g0, g1); }
 
 static int upload_impl(smk_ctx *c, const smk_volume_desc *b, int nb, int nelts, smk_dtype dtype, smk_datamode dmode,
                        bool on_device) {
@@ -1125,17 +1128,10 @@ extern "C" int smk_get_tf2d_effective(smk_ctx *c, unsigned char *out, float *rat
   return 0;
 }
 
-extern "C" int smk_shard_order(smk_ctx *c, int *order) {
-  if (!c || !order) return 1;
-  if (!c->have_volume || !c->have_camera) FAIL(c, "smk_shard_order: volume and camera must be set");
-  double inv[16];
-  inverse_affine(inv, c->mv);
-  // eye in voxel index space; per split axis the half holding the eye is in front (BSP order)
+// the shards in BSP order seen from a point (voxel index space): per split axis the half holding the point comes first
+static void bsp_order(const smk_ctx *c, const double pos[3], int *order) {
   int nearbit[3];
-  for (int a = 0; a < 3; ++a) {
-    double e = inv[12 + a] * c->N[a] / c->fsize[a] - 0.5;
-    nearbit[a] = e >= (double)(c->N[a] / 2) - 0.5 ? 1 : 0;
-  }
+  for (int a = 0; a < 3; ++a) nearbit[a] = pos[a] >= (double)(c->N[a] / 2) - 0.5 ? 1 : 0;
   int nbits = 0;
   for (int n = c->nranks; n > 1; n >>= 1) ++nbits;
   std::vector<std::pair<int, int>> keyed;
@@ -1147,6 +1143,30 @@ extern "C" int smk_shard_order(smk_ctx *c, int *order) {
   }
   std::sort(keyed.begin(), keyed.end());
   for (int r = 0; r < c->nranks; ++r) order[r] = keyed[r].second;
+}
+
+extern "C" int smk_shard_order(smk_ctx *c, int *order) {
+  if (!c || !order) return 1;
+  if (!c->have_volume || !c->have_camera) FAIL(c, "smk_shard_order: volume and camera must be set");
+  double inv[16];
+  inverse_affine(inv, c->mv);
+  // eye in voxel index space
+  double e[3];
+  for (int a = 0; a < 3; ++a) e[a] = inv[12 + a] * c->N[a] / c->fsize[a] - 0.5;
+  bsp_order(c, e, order);
+  return 0;
+}
+
+// The light's BSP order: from the apex of the light rays (smk_shadowcoef Lc, voxel index space), the point every light-buffer
+// texel's ray starts from -- a ray crosses the shards' convex boxes in this order (R8kVolRen3D.cpp:582-679 draws the bricks of
+// a shadowed volume one after another against one light buffer)
+extern "C" int smk_shard_light_order(smk_ctx *c, int *order) {
+  if (!c || !order) return 1;
+  if (!c->have_volume || !c->have_camera) FAIL(c, "smk_shard_light_order: volume and camera must be set");
+  smk_shadowcoef sc;
+  if (compute_shadowcoef(c, &sc)) return 1;
+  const double l[3] = {sc.Lc[0], sc.Lc[1], sc.Lc[2]};
+  bsp_order(c, l, order);
   return 0;
 }
 
@@ -1288,6 +1308,9 @@ extern "C" int smk_frame_failed(smk_ctx *c, long long frame_id) {
   return take_status(c, frame_id) ? 1 : 0;
 }
 
+static int shadow_setup(smk_ctx *c, RenderParams &P, smk_shadowcoef &sc, SmkShadowShard *S, int *halo_need);
+static int shadow_light_owned(smk_ctx *c, RenderParams &P, smk_shadowcoef &sc, float olo[3], float ohi[3]);
+
 extern "C" int smk_get_stat(smk_ctx *c, const char *name, double *value) {
   if (!c || !name || !value) return 1;
   HIPCHK(c, hipSetDevice(c->device));
@@ -1305,6 +1328,22 @@ extern "C" int smk_get_stat(smk_ctx *c, const char *name, double *value) {
       *value = v;
       return 0;
     }
+  if (!strcmp(name, "light_samples")) {  // light-march samples of the current frame with shadows this context owns (all of them unsharded)
+    RenderParams P;
+    smk_shadowcoef sc;
+    float olo[3], ohi[3];
+    if (shadow_light_owned(c, P, sc, olo, ohi)) return 1;
+    unsigned long long *d = nullptr, h = 0;
+    HIPCHK(c, hipMalloc((void **)&d, 8));
+    hipError_t e = hipMemsetAsync(d, 0, 8, c->stream);
+    if (e == hipSuccess) e = smk_launch_shadow_count_light(P, sc, olo, ohi, d, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&h, d, 8, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(d);
+    HIPCHK(c, e);
+    *value = (double)h;
+    return 0;
+  }
   if (!strcmp(name, "slab_status")) {  // status word of the latest frame (0 = ok); synchronises
     HIPCHK(c, hipDeviceSynchronize());
     *value = c->slab.h_status ? (((volatile int *)c->slab.h_status)[c->slab.status_slot] & 0xff) : 0;
@@ -1447,6 +1486,9 @@ extern "C" int smk_count_samples(smk_ctx *c, double *in_volume) {
   HIPCHK(c, hipSetDevice(c->device));
   RenderParams P;
   if (build_params(c, P, c->stream)) return 1;
+  // a frame with shadows samples the half-angle slices in its eye box (shadow_setup)
+  smk_shadowcoef sc;
+  if (c->shadow_on && c->tf_mode != 0 && !P.pert_on && !c->region_on && shadow_setup(c, P, sc, nullptr, nullptr)) return 1;
   unsigned long long *d = nullptr, h = 0;
   HIPCHK(c, hipMalloc((void **)&d, 8));
   hipError_t e = hipMemsetAsync(d, 0, 8, c->stream);
@@ -1467,6 +1509,40 @@ extern "C" int smk_last_frame_info(smk_ctx *c, int *kernel, float *ms, double *a
   return 0;
 }
 
+// The box of voxels g0..g1 in voxel coordinates, [g0 - .5, g1 - .5) per axis (closed where top[a]: the volume's upper face),
+// cut by an orthogonal clip plane and the sub-box.  A shard's region; with 0..N the whole volume's box.
+static void region_box(const smk_ctx *c, const int g0[3], const int g1[3], float lo[3], float hi[3], int top[3]) {
+  for (int a = 0; a < 3; ++a) {
+    lo[a] = (float)g0[a] - 0.5f;
+    hi[a] = (float)g1[a] - 0.5f;
+    top[a] = g1[a] == c->N[a];
+  }
+  // orthogonal clip plane (NV20VolRen3D::setupClips, NV20VolRen3D.cpp:251-327): the sliced box ends
+  // at the plane, i.e. the region shrinks along one axis; the new face is an outer (inclusive) one
+  if (c->clip_axis >= 1 && c->clip_axis <= 6) {
+    const int a = (c->clip_axis - 1) / 2;
+    const float fs = c->fsize[a];
+    const float cp = c->clip_vpos[a] > 0.0f ? (c->clip_vpos[a] < fs ? c->clip_vpos[a] : fs) : 0.0f;
+    const float face = (float)((double)cp / (double)fs * (double)c->N[a] - 0.5);
+    if ((c->clip_axis - 1) % 2 == 0) {
+      if (face < hi[a] || (face == hi[a] && !top[a])) { hi[a] = face; top[a] = 1; }
+    } else if (face > lo[a]) {
+      lo[a] = face;
+    }
+  }
+  // sub-box of renderVolume(.., xext, yext, zext) (VolumeRenderer.cpp:428-505): the region shrinks on every axis; the new
+  // upper faces are half-open like a shard's inner ones (a face that coincides with a voxel plane belongs to one side)
+  if (c->region_on)
+    for (int a = 0; a < 3; ++a) {
+      const double fs = c->fsize[a];
+      const double l = c->region_lo[a] > 0 ? (c->region_lo[a] < fs ? c->region_lo[a] : fs) : 0.0;
+      const double h = c->region_hi[a] > 0 ? (c->region_hi[a] < fs ? c->region_hi[a] : fs) : 0.0;
+      const float flo = (float)(l / fs * (double)c->N[a] - 0.5), fhi = (float)(h / fs * (double)c->N[a] - 0.5);
+      if (flo > lo[a]) lo[a] = flo;
+      if (fhi < hi[a]) { hi[a] = fhi; top[a] = 0; }
+    }
+}
+
 static int build_params(smk_ctx *c, RenderParams &P, hipStream_t s) {
   if (!c->have_volume) FAIL(c, "smk_render: no volume uploaded");
   if (!c->have_camera) FAIL(c, "smk_render: no camera set");
@@ -1481,35 +1557,9 @@ static int build_params(smk_ctx *c, RenderParams &P, hipStream_t s) {
     P.N[a] = c->N[a];
     P.O[a] = c->O[a];
     P.D[a] = c->D[a];
-    P.lo[a] = (float)c->g0[a] - 0.5f;
-    P.hi[a] = (float)c->g1[a] - 0.5f;
-    P.top[a] = c->g1[a] == c->N[a];
     P.invN[a] = 1.0f / (float)c->N[a];
   }
-  // orthogonal clip plane (NV20VolRen3D::setupClips, NV20VolRen3D.cpp:251-327): the sliced box ends
-  // at the plane, i.e. the region shrinks along one axis; the new face is an outer (inclusive) one
-  if (c->clip_axis >= 1 && c->clip_axis <= 6) {
-    const int a = (c->clip_axis - 1) / 2;
-    const float fs = c->fsize[a];
-    const float cp = c->clip_vpos[a] > 0.0f ? (c->clip_vpos[a] < fs ? c->clip_vpos[a] : fs) : 0.0f;
-    const float face = (float)((double)cp / (double)fs * (double)c->N[a] - 0.5);
-    if ((c->clip_axis - 1) % 2 == 0) {
-      if (face < P.hi[a] || (face == P.hi[a] && !P.top[a])) { P.hi[a] = face; P.top[a] = 1; }
-    } else if (face > P.lo[a]) {
-      P.lo[a] = face;
-    }
-  }
-  // sub-box of renderVolume(.., xext, yext, zext) (VolumeRenderer.cpp:428-505): the region shrinks on every axis; the new
-  // upper faces are half-open like a shard's inner ones (a face that coincides with a voxel plane belongs to one side)
-  if (c->region_on)
-    for (int a = 0; a < 3; ++a) {
-      const double fs = c->fsize[a];
-      const double l = c->region_lo[a] > 0 ? (c->region_lo[a] < fs ? c->region_lo[a] : fs) : 0.0;
-      const double h = c->region_hi[a] > 0 ? (c->region_hi[a] < fs ? c->region_hi[a] : fs) : 0.0;
-      const float flo = (float)(l / fs * (double)c->N[a] - 0.5), fhi = (float)(h / fs * (double)c->N[a] - 0.5);
-      if (flo > P.lo[a]) P.lo[a] = flo;
-      if (fhi < P.hi[a]) { P.hi[a] = fhi; P.top[a] = 0; }
-    }
+  region_box(c, c->g0, c->g1, P.lo, P.hi, P.top);
   for (int a = 0; a < 3; ++a) P.hin[a] = P.top[a] ? P.hi[a] : nextafterf(P.hi[a], -INFINITY);
   // free clip plane: eye-space plane -> voxel coordinates.  eye = MV * model, model = (p + 1/2)/N * fSize
   // (same operations in the same order as the CPU checker's orc_clip_plane_voxel)
@@ -1667,6 +1717,298 @@ static int shade_kind_of(const smk_ctx *c) {
   return 0;
 }
 
+// Margin m of a shard with shadows ("Shadows on shards"): an eye sample p of slice k looks the light buffer up
+// bilinearly at p's light-buffer position, i.e. the (up to) 4 texels whose centres lie less than one texel from it on each
+// axis; each such texel's slice-k sample lies on slice k's plane near p, off by the texel offset times the Jacobian of the
+// map (buffer position -> point of the plane), here (a, b) -> Lc + lnum G(a, b) / nG(a, b).  Its largest size over a grid
+// of the region's box, in voxels per texel, with half again as much for the curvature between grid points and the float
+// chains, rounded up: the light samples rank j must march itself lie within m voxels of its region.
+static int shadow_margin(const smk_shadowcoef &sc, const int g0[3], const int g1[3]) {
+  double worst = 0.0;
+  const int n = 8;
+  for (int iz = 0; iz <= n; ++iz)
+    for (int iy = 0; iy <= n; ++iy)
+      for (int ix = 0; ix <= n; ++ix) {
+        const int ii[3] = {ix, iy, iz};
+        double p[3];
+        for (int a = 0; a < 3; ++a) p[a] = (double)g0[a] - 0.5 + (double)(g1[a] - g0[a]) * ii[a] / n;
+        const double lw = sc.Wm[0] * p[0] + sc.Wm[1] * p[1] + sc.Wm[2] * p[2] + sc.Wm[3];
+        if (!(fabs(lw) > 1e-30)) return 1 << 20;
+        const double lx = (sc.Xm[0] * p[0] + sc.Xm[1] * p[1] + sc.Xm[2] * p[2] + sc.Xm[3]) / lw * sc.lscale + sc.lbias;
+        const double ly = (sc.Ym[0] * p[0] + sc.Ym[1] * p[1] + sc.Ym[2] * p[2] + sc.Ym[3]) / lw * sc.lscale + sc.lbias;
+        const double a = lx * sc.las + sc.lal, b = ly * sc.las + sc.lal;  // (texel x has a = fma(x + .5, las, lal))
+        double G[3], d[3], gg = 0.0, dg = 0.0;
+        for (int q = 0; q < 3; ++q) {
+          G[q] = a * sc.Gx[q] + b * sc.Gy[q] + sc.Gc[q];
+          d[q] = p[q] - sc.Lc[q];
+          gg += G[q] * G[q];
+          dg += d[q] * G[q];
+        }
+        const double nG = a * sc.nGx + b * sc.nGy + sc.nGc;
+        if (!(gg > 0.0) || !(fabs(nG) > 1e-30)) return 1 << 20;
+        const double w = dg / gg;  // p = Lc + w G
+        for (int q = 0; q < 3; ++q) {
+          const double ja = w * (sc.Gx[q] - G[q] * sc.nGx / nG), jb = w * (sc.Gy[q] - G[q] * sc.nGy / nG);
+          worst = std::max(worst, (double)sc.las * (fabs(ja) + fabs(jb)));
+        }
+      }
+  const double m = ceil(1.5 * worst + 0.5);
+  return m > (double)(1 << 20) || m != m ? 1 << 20 : std::max(1, (int)m);
+}
+
+// A frame with shadows: the half-angle slices (compute_shadowcoef), the eye rays over them in P.sh, and the boxes.  On the
+// whole volume: a light sample lies in the volume's closed box (what an orthogonal clip plane leaves of it), an eye sample in
+// that box widened by SMK_SHADOW_BOX_EPS.  On a shard the outer faces keep that treatment and the inner ones the half-open
+// rule of a shard's region (a sample on the split plane belongs to the upper half), so that every light sample and every eye
+// sample of the unsharded frame belongs to exactly one rank; the light march's bracket and sample set stay the whole volume's
+// (P.sh.llo / lhi).  With S: the phase-1 / phase-2 parameters of the shard (SmkShadowShard), *halo_need = m + 1.
+static int shadow_setup(smk_ctx *c, RenderParams &P, smk_shadowcoef &sc, SmkShadowShard *S, int *halo_need) {
+  if (compute_shadowcoef(c, &sc)) return 1;
+  // the eye rays over the half-angle slices, planes counted from the eye (smk_internal.h SmkShadowRays)
+  SmkShadowRays &h = P.sh;
+  memset(&h, 0, sizeof h);
+  h.on = 1;
+  for (int a = 0; a < 3; ++a) { h.Ec[a] = sc.Ec[a]; h.Dc[a] = sc.Dc[a]; h.Dx[a] = sc.Dx[a]; h.Dy[a] = sc.Dy[a]; }
+  h.nDc = sc.nDc; h.nDx = sc.nDx; h.nDy = sc.nDy;
+  if (sc.front_to_back) { h.numA = fmaf(1.0f, sc.dnum, sc.num0); h.dB = sc.dnum; h.k0 = 1; h.dk = 1; }
+  else { h.numA = fmaf((float)sc.nslices, sc.dnum, sc.num0); h.dB = -sc.dnum; h.k0 = sc.nslices; h.dk = -1; }
+  h.LB = sc.LB;
+  for (int q = 0; q < 4; ++q) { h.Xm[q] = sc.Xm[q]; h.Ym[q] = sc.Ym[q]; h.Wm[q] = sc.Wm[q]; }
+  h.lscale = sc.lscale; h.lbias = sc.lbias;
+  {
+    smk_raycoef &rc = P.rc;
+    memset(&rc, 0, sizeof rc);
+    rc.pxs = sc.pxs; rc.pxl = sc.pxl; rc.pys = sc.pys; rc.pyl = sc.pyl;
+    rc.nplanes = sc.nslices;
+    // (Bc: the central ray's step, which the kernel choice below keys its measurements on)
+    const double nDc = (double)sc.nDc != 0.0 ? (double)sc.nDc : 1.0;
+    for (int a = 0; a < 3; ++a) rc.Bc[a] = (float)((double)h.dB / nDc * (double)sc.Dc[a]);
+  }
+  // The last slice lies ON the volume's far corner -- on a whole face when the half-way vector is a volume axis (a light at
+  // the eye) -- where a sample's coordinate, the end of an fma chain, lands on either side of the face by rounding.  The
+  // reference draws that slice (a polygon clipped against the box keeps its boundary); the eye pass's membership test is
+  // therefore 2^-10 voxels wide of the box (clamp-to-edge fetches: the value at the face).  The CPU checker does the same.
+  // Clip planes (round 3): both passes draw the same clipped slice polygons in the reference (volShadow slices the box
+  // setupClips left; glClipPlane stays enabled), so a light ray's sample must lie in the same box (closed, no slack: its
+  // last slice gets no special treatment in rounds 1-2 either) and on the kept side of the free plane.
+  float wlo[3], whi[3];
+  int wtop[3];
+  const int z0[3] = {0, 0, 0};
+  region_box(c, z0, c->N, wlo, whi, wtop);
+  float olo[3], ohi[3];
+  for (int a = 0; a < 3; ++a) {
+    const bool inner_lo = c->g0[a] > 0 && P.lo[a] == (float)c->g0[a] - 0.5f, inner_hi = !P.top[a];
+    h.llo[a] = wlo[a];
+    h.lhi[a] = whi[a];
+    olo[a] = P.lo[a];
+    ohi[a] = inner_hi ? nextafterf(P.hi[a], -INFINITY) : P.hi[a];
+    if (!inner_lo) P.lo[a] -= SMK_SHADOW_BOX_EPS;
+    if (inner_hi) P.hin[a] = nextafterf(P.hi[a], -INFINITY);
+    else {
+      P.hi[a] += SMK_SHADOW_BOX_EPS;
+      P.hin[a] = P.hi[a];
+      P.top[a] = 1;
+    }
+  }
+  if (!S) return 0;
+  memset(S, 0, sizeof *S);
+  S->nranks = c->nranks;
+  S->rank = c->rank;
+  for (int a = 0; a < 3; ++a) { S->olo[a] = olo[a]; S->ohi[a] = ohi[a]; }
+  int m_own = 0;
+  for (int j = 0; j < c->nranks; ++j) {
+    int g0[3], g1[3];
+    shard_region_of(c, j, g0, g1);
+    const int m = shadow_margin(sc, g0, g1);
+    if (j == c->rank) m_own = m;
+    for (int a = 0; a < 3; ++a) {
+      S->glo[j][a] = (float)((double)g0[a] - 0.5 - m);
+      S->ghi[j][a] = (float)((double)g1[a] - 0.5 + m);
+    }
+  }
+  for (int a = 0; a < 3; ++a) {
+    S->xlo[a] = S->glo[c->rank][a] - 0.25f;
+    S->xhi[a] = S->ghi[c->rank][a] + 0.25f;
+  }
+  const double l[3] = {sc.Lc[0], sc.Lc[1], sc.Lc[2]};
+  bsp_order(c, l, S->order);
+  if (halo_need) *halo_need = m_own + 1;
+  return 0;
+}
+
+// what a frame with shadows cannot be combined with (the same reasons as smk_render's)
+static int shadow_refusals(smk_ctx *c, const RenderParams &P, bool depth) {
+  const int sk = shade_kind_of(c);
+  if (c->tf_mode == 0) FAIL(c, "smk_render: shadows need a 2-D or 3-D transfer function (the 1-D table renderer has no shadow mode)");
+  if (sk == 2) FAIL(c, "smk_render: shadows are implemented for R8k shading or none (NV20 combiners: no shadow mode in NV20VolRen3D)");
+  if (c->nranks > 1 && (!c->opt_shadow_march || (c->opt_lockstep & 256)))
+    FAIL(c, "smk_render: shadows need the whole volume on one GPU with option shadow_march 0 or shadow_fused (the light buffer couples every "
+            "slice of every brick); a shard renders shadows with the two marches only");
+  if (P.pert_on || depth || c->region_on)
+    FAIL(c, "smk_render: shadows cannot be combined with perturbation, a sub-box or depth output");
+  if (c->opt_kernel == 3) FAIL(c, "smk_render: the column-stream kernel has no shadow mode");
+  return 0;
+}
+
+// a shard's halo against the margin of its frame with shadows
+static int shadow_halo_check(smk_ctx *c, int need) {
+  for (int a = 0; a < 3; ++a)
+    if (c->halo < need && c->D[a] < c->N[a])
+      FAIL(c, "smk_render: shadows on a shard need halo >= %d voxels (have %d; margin %d, smk_get_shadow_margin); set option 'halo' before upload",
+           need, c->halo, need - 1);
+  return 0;
+}
+
+float4 *smk_shadow_entries_reserve(smk_ctx *c, int LB) {
+  const size_t n = (size_t)c->nranks * LB * LB;
+  if (n > c->shadow_entries_cap) {
+    if (c->d_shadow_entries) (void)hipFree(c->d_shadow_entries);
+    c->d_shadow_entries = nullptr;
+    c->shadow_entries_cap = 0;
+    if (hipMalloc((void **)&c->d_shadow_entries, n * 16) != hipSuccess) {
+      (void)hipGetLastError();
+      c->d_shadow_entries = nullptr;
+      return nullptr;
+    }
+    c->shadow_entries_cap = n;
+  }
+  c->shadow_entries_fresh = false;
+  return c->d_shadow_entries;
+}
+
+void smk_shadow_entries_commit(smk_ctx *c, const smk_shadowcoef &sc) {
+  c->shadow_entries_sc = sc;
+  c->shadow_entries_fresh = true;
+}
+
+int smk_shadow_shard_setup(smk_ctx *c, RenderParams &P, smk_shadowcoef &sc, SmkShadowShard &S, hipStream_t s) {
+  if (!c->shadow_on) FAIL(c, "smk_shadow_exports_device: shadows are off (smk_set_shadow)");
+  if (build_params(c, P, s)) return 1;
+  if (shadow_refusals(c, P, false)) return 1;
+  int need = 0;
+  if (shadow_setup(c, P, sc, &S, &need)) return 1;
+  if (shadow_halo_check(c, need)) return 1;
+  return 0;
+}
+
+extern "C" int smk_shadow_exports_device(smk_ctx *c, void *d_exports, void *stream) {
+  if (!c) return 1;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!d_exports) FAIL(c, "smk_shadow_exports_device: null output");
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  RenderParams P;
+  smk_shadowcoef sc;
+  SmkShadowShard S;
+  if (smk_shadow_shard_setup(c, P, sc, S, s)) return 1;
+  S.exports = (float4 *)d_exports;
+  hipError_t e = smk_launch_shadow_exports(P, sc, c->dtype, c->tf_mode, S, s);
+  if (e == hipErrorNotSupported) FAIL(c, "smk_shadow_exports_device: no shadow kernel instance for this configuration");
+  HIPCHK(c, e);
+  return 0;
+}
+
+extern "C" int smk_shadow_entries_device(smk_ctx *c, const void *d_entries, void *stream) {
+  if (!c) return 1;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!d_entries) FAIL(c, "smk_shadow_entries_device: null input");
+  if (!c->have_volume || !c->have_camera) FAIL(c, "smk_shadow_entries_device: volume and camera must be set");
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  smk_shadowcoef sc;
+  if (compute_shadowcoef(c, &sc)) return 1;
+  float4 *d = smk_shadow_entries_reserve(c, sc.LB);
+  if (!d) FAIL(c, "smk_shadow_entries_device: device allocation failed");
+  HIPCHK(c, hipMemcpyAsync(d, d_entries, (size_t)c->nranks * sc.LB * sc.LB * 16, hipMemcpyDeviceToDevice, s));
+  smk_shadow_entries_commit(c, sc);
+  return 0;
+}
+
+extern "C" int smk_get_shadow_margin(smk_ctx *c, int *m, int *halo_needed) {
+  if (!c) return 1;
+  if (!c->have_volume || !c->have_camera) FAIL(c, "smk_get_shadow_margin: volume and camera must be set");
+  smk_shadowcoef sc;
+  if (compute_shadowcoef(c, &sc)) return 1;
+  const int mm = shadow_margin(sc, c->g0, c->g1);
+  if (m) *m = mm;
+  if (halo_needed) *halo_needed = mm + 1;
+  return 0;
+}
+
+static int shadow_light_owned(smk_ctx *c, RenderParams &P, smk_shadowcoef &sc, float olo[3], float ohi[3]) {
+  if (!c->shadow_on) FAIL(c, "smk_get_stat: light_samples needs shadows on (smk_set_shadow)");
+  if (build_params(c, P, c->stream)) return 1;
+  SmkShadowShard S;
+  if (shadow_setup(c, P, sc, &S, nullptr)) return 1;
+  for (int a = 0; a < 3; ++a) { olo[a] = S.olo[a]; ohi[a] = S.ohi[a]; }
+  return 0;
+}
+
+// In-process transport of the light exchange: phase 1 on every rank into its own scratch buffer, then slot j of rank r's
+// exports into slot r of rank j's entries (device-to-device; peer copies between devices).  Synchronous: every rank's stream
+// is idle before (the entries of the previous frame are no longer read) and after.
+extern "C" int smk_shadow_exchange_local(smk_ctx *const *all, int nranks) {
+  if (!all || nranks < 1 || nranks > SMK_MAX_RANKS) return 1;
+  for (int r = 0; r < nranks; ++r) {
+    if (!all[r]) return 1;
+    if (all[r]->nranks != nranks || all[r]->rank != r) FAIL(all[r], "smk_shadow_exchange_local: context %d is not shard %d of %d", r, r, nranks);
+  }
+  std::vector<smk_shadowcoef> scs(nranks);
+  for (int r = 0; r < nranks; ++r) {
+    smk_ctx *c = all[r];
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    RenderParams P;
+    SmkShadowShard S;
+    if (smk_shadow_shard_setup(c, P, scs[r], S, c->stream)) return 1;
+    if (r > 0 && memcmp(&scs[r], &scs[0], sizeof scs[0])) FAIL(c, "smk_shadow_exchange_local: the ranks' slice sets differ (camera, light, buffer or volume)");
+    const size_t n = (size_t)nranks * scs[r].LB * scs[r].LB;
+    if (n > c->shadow_exports_cap) {
+      if (c->d_shadow_exports) (void)hipFree(c->d_shadow_exports);
+      c->d_shadow_exports = nullptr;
+      c->shadow_exports_cap = 0;
+      HIPCHK(c, hipMalloc((void **)&c->d_shadow_exports, n * 16));
+      c->shadow_exports_cap = n;
+    }
+    S.exports = c->d_shadow_exports;
+    hipError_t e = smk_launch_shadow_exports(P, scs[r], c->dtype, c->tf_mode, S, c->stream);
+    if (e == hipErrorNotSupported) FAIL(c, "smk_shadow_exchange_local: no shadow kernel instance for this configuration");
+    HIPCHK(c, e);
+  }
+  const size_t nl = (size_t)scs[0].LB * scs[0].LB;
+  std::vector<float4 *> dst(nranks);
+  for (int j = 0; j < nranks; ++j) {
+    HIPCHK(all[j], hipSetDevice(all[j]->device));
+    dst[j] = smk_shadow_entries_reserve(all[j], scs[0].LB);
+    if (!dst[j]) FAIL(all[j], "smk_shadow_exchange_local: device allocation failed");
+  }
+  for (int r = 0; r < nranks; ++r) {
+    smk_ctx *c = all[r];
+    HIPCHK(c, hipSetDevice(c->device));
+    for (int j = 0; j < nranks; ++j) {
+      if (all[j]->device == c->device)
+        HIPCHK(c, hipMemcpyAsync(dst[j] + (size_t)r * nl, c->d_shadow_exports + (size_t)j * nl, nl * 16, hipMemcpyDeviceToDevice, c->stream));
+      else
+        HIPCHK(c, hipMemcpyPeerAsync(dst[j] + (size_t)r * nl, all[j]->device, c->d_shadow_exports + (size_t)j * nl, c->device, nl * 16, c->stream));
+    }
+  }
+  for (int r = 0; r < nranks; ++r) {
+    HIPCHK(all[r], hipSetDevice(all[r]->device));
+    HIPCHK(all[r], hipStreamSynchronize(all[r]->stream));
+  }
+  for (int j = 0; j < nranks; ++j) smk_shadow_entries_commit(all[j], scs[0]);
+  return 0;
+}
+
+extern "C" int smk_get_light_history(smk_ctx *c, int k, float *rgba_out) {
+  if (!c || !rgba_out) return 1;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!c->light_hist_n || !c->d_light_hist) FAIL(c, "smk_get_light_history: the last frame with shadows kept no history (option shadow_march 0?)");
+  if (k < 0 || k >= c->light_hist_n) FAIL(c, "smk_get_light_history: slice %d outside 0..%d", k, c->light_hist_n - 1);
+  HIPCHK(c, hipDeviceSynchronize());
+  HIPCHK(c, hipMemcpy(rgba_out, c->d_light_hist + (size_t)k * c->light_hist_stride, (size_t)c->light_lb * c->light_lb * 16,
+                      hipMemcpyDeviceToHost));
+  return 0;
+}
+
 extern "C" int smk_render_device(smk_ctx *c, void *d_rgba, void *d_depth, void *stream) {
   if (!c) return 1;
   HIPCHK(c, hipSetDevice(c->device));
@@ -1714,48 +2056,23 @@ extern "C" int smk_render_device(smk_ctx *c, void *d_rgba, void *d_depth, void *
     // ---- half-angle slicing (smk_shadow.hip): the light march, then the eye pass as an ordinary frame of the ray-marchers
     // below over the half-angle slices (SmkShadowRays) -- or, option shadow_march 0, a launch per slice
     const int sk = shade_kind_of(c);
-    if (c->tf_mode == 0) FAIL(c, "smk_render: shadows need a 2-D or 3-D transfer function (the 1-D table renderer has no shadow mode)");
-    if (sk == 2) FAIL(c, "smk_render: shadows are implemented for R8k shading or none (NV20 combiners: no shadow mode in NV20VolRen3D)");
-    if (c->nranks > 1) FAIL(c, "smk_render: shadows need the whole volume on one GPU (the light buffer couples every slice of every brick)");
-    if (P.pert_on || d_depth || c->region_on)
-      FAIL(c, "smk_render: shadows cannot be combined with perturbation, a sub-box or depth output");
-    if (c->opt_kernel == 3) FAIL(c, "smk_render: the column-stream kernel has no shadow mode");
+    if (c->nranks > 1 && !c->shadow_entries_fresh && c->tf_mode != 0 && sk != 2)
+      FAIL(c, "smk_render: shadows need the whole volume on one GPU (the light buffer couples every slice of every brick) -- "
+              "or, on a shard, this frame's light entries: smk_shadow_exports_device on every rank, then smk_shadow_entries_device "
+              "(smk_shadow_exchange_local in one process)");
+    const bool entries = c->shadow_entries_fresh;
+    c->shadow_entries_fresh = false;  // (consumed by this frame, whatever becomes of it)
+    if (shadow_refusals(c, P, d_depth != nullptr)) return 1;
     smk_shadowcoef sc;
-    if (compute_shadowcoef(c, &sc)) return 1;
-    // the eye rays over the half-angle slices, planes counted from the eye (smk_internal.h SmkShadowRays)
+    SmkShadowShard S;
+    int halo_need = 0;
+    if (shadow_setup(c, P, sc, c->nranks > 1 ? &S : nullptr, &halo_need)) return 1;
     SmkShadowRays &h = P.sh;
-    memset(&h, 0, sizeof h);
-    h.on = 1;
-    for (int a = 0; a < 3; ++a) { h.Ec[a] = sc.Ec[a]; h.Dc[a] = sc.Dc[a]; h.Dx[a] = sc.Dx[a]; h.Dy[a] = sc.Dy[a]; }
-    h.nDc = sc.nDc; h.nDx = sc.nDx; h.nDy = sc.nDy;
-    if (sc.front_to_back) { h.numA = fmaf(1.0f, sc.dnum, sc.num0); h.dB = sc.dnum; h.k0 = 1; h.dk = 1; }
-    else { h.numA = fmaf((float)sc.nslices, sc.dnum, sc.num0); h.dB = -sc.dnum; h.k0 = sc.nslices; h.dk = -1; }
-    h.LB = sc.LB;
-    for (int q = 0; q < 4; ++q) { h.Xm[q] = sc.Xm[q]; h.Ym[q] = sc.Ym[q]; h.Wm[q] = sc.Wm[q]; }
-    h.lscale = sc.lscale; h.lbias = sc.lbias;
-    {
-      smk_raycoef &rc = P.rc;
-      memset(&rc, 0, sizeof rc);
-      rc.pxs = sc.pxs; rc.pxl = sc.pxl; rc.pys = sc.pys; rc.pyl = sc.pyl;
-      rc.nplanes = sc.nslices;
-      // (Bc: the central ray's step, which the kernel choice below keys its measurements on)
-      const double nDc = (double)sc.nDc != 0.0 ? (double)sc.nDc : 1.0;
-      for (int a = 0; a < 3; ++a) rc.Bc[a] = (float)((double)h.dB / nDc * (double)sc.Dc[a]);
-    }
-    // The last slice lies ON the volume's far corner -- on a whole face when the half-way vector is a volume axis (a light at
-    // the eye) -- where a sample's coordinate, the end of an fma chain, lands on either side of the face by rounding.  The
-    // reference draws that slice (a polygon clipped against the box keeps its boundary); the eye pass's membership test is
-    // therefore 2^-10 voxels wide of the box (clamp-to-edge fetches: the value at the face).  The CPU checker does the same.
-    // Clip planes (round 3): both passes draw the same clipped slice polygons in the reference (volShadow slices the box
-    // setupClips left; glClipPlane stays enabled), so a light ray's sample must lie in the same box (closed, no slack: its
-    // last slice gets no special treatment in rounds 1-2 either) and on the kept side of the free plane.
-    for (int a = 0; a < 3; ++a) {
-      h.llo[a] = P.lo[a];
-      h.lhi[a] = P.hi[a];
-      P.lo[a] -= SMK_SHADOW_BOX_EPS;
-      P.hi[a] += SMK_SHADOW_BOX_EPS;
-      P.hin[a] = P.hi[a];
-      P.top[a] = 1;
+    if (c->nranks > 1) {
+      if (shadow_halo_check(c, halo_need)) return 1;
+      if (!entries || memcmp(&sc, &c->shadow_entries_sc, sizeof sc))
+        FAIL(c, "smk_render: shadows on a shard: the light entries were made for another slice set (camera, light or buffer changed since)");
+      S.entries = c->d_shadow_entries;
     }
     P.blend = SMK_BLEND_FRONT_TO_BACK;  // (a light that faces the viewer: the per-slice form blends back to front, the marchers
                                         //  composite the same samples front to back -- the association of the blend differs)
@@ -1782,14 +2099,21 @@ extern "C" int smk_render_device(smk_ctx *c, void *d_rgba, void *d_depth, void *
       } else c->light_hist_cap = nhist;
     }
     c->light_lb = sc.LB;
+    c->light_hist_n = 0;
+    if (c->nranks > 1 && !march)
+      FAIL(c, "smk_render: shadows on a shard: the light history (%.1f GB) does not fit a quarter of the free device memory",
+           (double)nhist * 16.0 / 1e9);
     if (march) {
       HIPCHK(c, hipEventRecord(c->ev0, s));
       ev0_recorded = true;
-      hipError_t e = smk_launch_shadow_march(P, sc, c->dtype, c->tf_mode, c->d_light_hist, (long long)hstride, s);
+      hipError_t e = c->nranks > 1 ? smk_launch_shadow_march_shard(P, sc, c->dtype, c->tf_mode, c->d_light_hist, (long long)hstride, S, s)
+                                   : smk_launch_shadow_march(P, sc, c->dtype, c->tf_mode, c->d_light_hist, (long long)hstride, s);
       if (e == hipErrorNotSupported) FAIL(c, "smk_render: no shadow kernel instance for this configuration");
       HIPCHK(c, e);
       h.hist = c->d_light_hist;
       h.hstride = (long long)hstride;
+      c->light_hist_n = sc.nslices + 1;
+      c->light_hist_stride = (long long)hstride;
       c->d_light_last = c->d_light_hist + (size_t)sc.nslices * hstride;
       // the history is written once (16 B per texel and slice)
       c->last_alg_bytes += (double)sc.nslices * (16.0 * (double)nl);

@@ -35,6 +35,21 @@ struct SmkShadowRays {
   long long hstride;   // (LB * LB + a pad: buffers a power of two apart would meet in the same memory channels)
 };
 
+// A frame with shadows on one shard of a sort-last split (smk_shadow.hip; DESIGN.md 4b, "Shadows on shards").  A texel's
+// light ray ENTERS grown(j) -- rank j's region widened by its margin m_j -- at its first sample (slices k0..k1 of the whole
+// volume's bracket, in the light's order) inside that box.  Phase 1: rank r marches the samples it owns and keeps, per
+// destination j, the value before the entry into grown(j): X_{r->j}.  Phase 2: rank j composes E_j = the X_{r->j} in the
+// light's BSP order and marches, from E_j, the unsharded samples after the entry that lie in grown(j) + 0.25 voxels.
+struct SmkShadowShard {
+  int nranks, rank;
+  float olo[3], ohi[3];                                 // the light samples this rank owns (closed; an inner upper face one float below the split)
+  float glo[SMK_MAX_RANKS][3], ghi[SMK_MAX_RANKS][3];   // grown(j) for every rank j
+  float xlo[3], xhi[3];                                 // phase 2: grown(rank) + 0.25 voxels (inside region + halo when halo >= m + 1)
+  int order[SMK_MAX_RANKS];                             // the ranks in the light's BSP order, nearest the light first
+  const float4 *entries;                                // phase 2: [nranks][LB][LB] X_{r->rank}, r in rank order
+  float4 *exports;                                      // phase 1: [nranks][LB][LB] X_{rank->j} (slot rank zero)
+};
+
 // Everything a render kernel needs, passed by value as the kernarg (wave-uniform => SGPRs).
 struct RenderParams {
   // ---- volume, packed layout (DESIGN.md "HBM layout")
@@ -284,6 +299,15 @@ struct smk_ctx {
   const float4 *d_light_last = nullptr;     // the light buffer the last frame with shadows left (in d_light[] or the history)
   int opt_shadow_march = 1;                 // option "shadow_march": 1 = two marches (default), 0 = a launch per slice
   unsigned *d_shadow_barrier = nullptr;     // the fused shadow launch's grid-barrier counter
+  int light_hist_n = 0;                     // buffers the last march kept (nslices + 1; 0: none)
+  long long light_hist_stride = 0;          // texels between two of them
+  // shadows on a shard (smk_shadow_entries_device): X_{r->this} of every rank r, for the next frame
+  float4 *d_shadow_entries = nullptr;
+  size_t shadow_entries_cap = 0;            // texels
+  bool shadow_entries_fresh = false;        // set since the last frame with shadows
+  smk_shadowcoef shadow_entries_sc;         // the slice set they were made for
+  float4 *d_shadow_exports = nullptr;       // phase 1's output of smk_shadow_exchange_local
+  size_t shadow_exports_cap = 0;            // texels
 
   // perturbation
   uint32_t *d_noise = nullptr;
@@ -338,6 +362,19 @@ hipError_t smk_launch_shadow(const RenderParams &P, const smk_shadowcoef &sc, in
                              float4 *L0, float4 *L1, unsigned *barrier /* one device word for the fused launch's grid barrier, or null */, hipStream_t s);
 hipError_t smk_launch_shadow_march(const RenderParams &P, const smk_shadowcoef &sc, int dtype, int tf_mode, float4 *hist, long long hstride,
                                    hipStream_t s);
+// shadows on a shard: phase 1 (S.exports) and phase 2 (the march from the composed entries, into hist); the light samples
+// of the box [olo, ohi] (smk_get_stat "light_samples")
+hipError_t smk_launch_shadow_exports(const RenderParams &P, const smk_shadowcoef &sc, int dtype, int tf_mode, const SmkShadowShard &S,
+                                     hipStream_t s);
+hipError_t smk_launch_shadow_march_shard(const RenderParams &P, const smk_shadowcoef &sc, int dtype, int tf_mode, float4 *hist,
+                                         long long hstride, const SmkShadowShard &S, hipStream_t s);
+hipError_t smk_launch_shadow_count_light(const RenderParams &P, const smk_shadowcoef &sc, const float olo[3], const float ohi[3],
+                                         unsigned long long *d_count, hipStream_t s);
+// (smk_api.hip) the frame with shadows a shard context would render now: its slice set and phase-1 parameters; the buffer
+// for X_{r->this} (LB x LB texels per rank), made current for the next frame by smk_shadow_entries_commit
+int smk_shadow_shard_setup(smk_ctx *c, RenderParams &P, smk_shadowcoef &sc, SmkShadowShard &S, hipStream_t s);
+float4 *smk_shadow_entries_reserve(smk_ctx *c, int LB);
+void smk_shadow_entries_commit(smk_ctx *c, const smk_shadowcoef &sc);
 // returns hipErrorNotSupported (and *why) when the frame must use the gather kernel
 hipError_t smk_launch_slab(RenderParams P, int dtype, int tf_mode, int shade_kind, int opt_T, int opt_tile, int forced,
                            const void *vox_native, const void *vox_xmajor, SlabAux *aux, const char **why,

@@ -23,6 +23,10 @@
 
 #include "smk_device.h"
 
+struct SmkBox3 {
+  float lo[3], hi[3];
+};
+
 struct ShadowSlice {
   smk_shadowcoef sc;
   const float4 *Lprev;  // [LB][LB] light buffer after the previous slices
@@ -33,7 +37,19 @@ struct ShadowSlice {
 };
 
 // the 8 corners of voxel coordinate p and the interpolated data channels (same arithmetic as kernel G)
-template <int DT, int TF, bool SHADE>
+// (LOC: a shard's stored box, region + halo from voxel O on: global indices -> stored ones, clamped for memory safety --
+//  the shard's marches stay inside it by construction, smk_api.hip; the whole volume has O = 0, D = N.  x0 at most D - 2:
+//  the u8 pair load reads voxels x0 and x0 + 1 at once)
+__device__ __forceinline__ void shadow_local(const RenderParams &P, int &x0, int &x1, int &y0, int &y1, int &z0, int &z1) {
+  x0 = min(max(x0 - P.O[0], 0), max(P.D[0] - 2, 0));
+  x1 = min(max(x1 - P.O[0], 0), P.D[0] - 1);
+  y0 = min(max(y0 - P.O[1], 0), P.D[1] - 1);
+  y1 = min(max(y1 - P.O[1], 0), P.D[1] - 1);
+  z0 = min(max(z0 - P.O[2], 0), P.D[2] - 1);
+  z1 = min(max(z1 - P.O[2], 0), P.D[2] - 1);
+}
+
+template <int DT, int TF, bool SHADE, bool LOC = false>
 __device__ __forceinline__ void shadow_fetch(const RenderParams &P, float p0, float p1, float p2, float &ch0, float &ch1,
                                              float &ch2, float &ch3, float &n0, float &n1, float &n2) {
   int x0, x1, y0, y1, z0, z1;
@@ -41,6 +57,7 @@ __device__ __forceinline__ void shadow_fetch(const RenderParams &P, float p0, fl
   smk_lin_clamp(p0, P.N[0], x0, x1, fx);
   smk_lin_clamp(p1, P.N[1], y0, y1, fy);
   smk_lin_clamp(p2, P.N[2], z0, z1, fz);
+  if constexpr (LOC) shadow_local(P, x0, x1, y0, y1, z0, z1);
   const int Dx = P.D[0], Dy = P.D[1];
   size_t r00 = ((size_t)z0 * Dy + y0) * Dx, r10 = ((size_t)z0 * Dy + y1) * Dx;
   size_t r01 = ((size_t)z1 * Dy + y0) * Dx, r11 = ((size_t)z1 * Dy + y1) * Dx;
@@ -369,8 +386,12 @@ __device__ __forceinline__ bool shadow_tile_of_block(int bid, int ntiles, int &t
 // lays the 8 slices' samples over the running value in order -- 8 short steps on values passed between lanes, every lane of a
 // texel computing the same running value, lane s keeping it as slice s leaves it -- and stores 8 buffers' worth.  The same
 // operations in the same order per texel as a launch per slice: bit-identical light buffers.
-template <int DT, int TF>
-__global__ __launch_bounds__(256) void smk_k_shadow_light_march(const RenderParams P, const ShadowSlice Q, float4 *hist, long long hstride) {
+// SHARD (phase 2 of a frame with shadows on a shard, SmkShadowShard): the running value starts at E_j, the entries composed
+// in the light's BSP order, and a sample is laid over it only once the texel's ray has entered grown(j) and while it lies in
+// grown(j) + 0.25 voxels; the brick flags and voxels are the shard's stored box.
+template <int DT, int TF, bool SHARD = false>
+__global__ __launch_bounds__(256) void smk_k_shadow_light_march(const RenderParams P, const ShadowSlice Q, float4 *hist, long long hstride,
+                                                                const SmkShadowShard S) {
   const smk_shadowcoef &sc = Q.sc;
   // blocks of 8 x 4 texels (a wave = 8 texels of one row), dealt to the XCDs in contiguous runs
   // (8 waves side by side -- 64 x 1 texels, a block's stores into one buffer one run of memory -- measured slower: 1.25 vs 1.0 ms)
@@ -391,18 +412,35 @@ __global__ __launch_bounds__(256) void smk_k_shadow_light_march(const RenderPara
   shadow_k_range(P, sc.lnum0, sc.ldnum, nG, G, sc.Lc, sc.nslices, k0, k1);
   if (!live) k1 = 0;
   float4 L = make_float4(0.f, 0.f, 0.f, 0.f);
+  if constexpr (SHARD) {
+    // E_j: X_{r->j} over one another in the light's order (each marched from transparent: colour and 1 - alpha are affine
+    // in the value below, so laying X over L is L (1 - X.w) + X)
+    if (live)
+      for (int q = 0; q < S.nranks; ++q) {
+        const float4 X = S.entries[(size_t)S.order[q] * sc.LB * sc.LB + o];
+        const float f = 1.0f - X.w;
+        L = make_float4(__fmaf_rn(f, L.x, X.x), __fmaf_rn(f, L.y, X.y), __fmaf_rn(f, L.z, X.z), __fmaf_rn(f, L.w, X.w));
+      }
+  }
   if (live && sl == 0) hist[o] = L;
   // where this lane's sample of slice k is, and -- requested one turn of the loop ahead, so that the first of the turn's
   // dependent round trips is over when the turn begins -- the flag of its brick (shadow_brick_empty's test)
   float p[3] = {0.f, 0.f, 0.f};
+  bool g = false;  // (SHARD) the sample lies in grown(rank)
   auto place = [&](int k) -> bool {
+    g = false;
     if (!(k >= k0 && k <= k1 && k <= sc.nslices)) return false;
     const float w = __fdiv_rn(__fmaf_rn((float)k, sc.ldnum, sc.lnum0), nG);
     bool in = w > 0.0f && !isinf(w);
+    if constexpr (SHARD) g = in;
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
       p[q] = __fmaf_rn(w, G[q], sc.Lc[q]);
       in = in && p[q] >= P.sh.llo[q] && p[q] <= P.sh.lhi[q];
+      if constexpr (SHARD) {
+        g = g && p[q] >= S.glo[S.rank][q] && p[q] <= S.ghi[S.rank][q];
+        in = in && p[q] >= S.xlo[q] && p[q] <= S.xhi[q];
+      }
     }
     if (in && P.cplane_on) in = __fmaf_rn(p[0], P.cplane[0], __fmaf_rn(p[1], P.cplane[1], __fmaf_rn(p[2], P.cplane[2], P.cplane[3]))) >= 0.0f;
     return in;
@@ -415,6 +453,7 @@ __global__ __launch_bounds__(256) void smk_k_shadow_light_march(const RenderPara
     smk_lin_clamp(p[0], P.N[0], x0, x1, fx);
     smk_lin_clamp(p[1], P.N[1], y0, y1, fy);
     smk_lin_clamp(p[2], P.N[2], z0, z1, fz);
+    if constexpr (SHARD) shadow_local(P, x0, x1, y0, y1, z0, z1);
     return P.bricks[((size_t)(z0 >> SMK_BRICK_LOG2) * P.nbr[1] + (size_t)(y0 >> SMK_BRICK_LOG2)) * P.nbr[0] + (size_t)(x0 >> SMK_BRICK_LOG2)];
   };
   // the slices some texel of this wave can have a sample in: before them every buffer is the cleared one, behind them the
@@ -432,12 +471,22 @@ __global__ __launch_bounds__(256) void smk_k_shadow_light_march(const RenderPara
   // cost are those with samples in flagged bricks, a chain of corner, occupancy and table round trips each; forcing 8 waves
   // per SIMD to overlap more of them spills: 1.0 -> 1.45 ms.)
   int kb = kb_first;
+  bool entered = false;  // (SHARD) this texel's ray has had a sample in grown(rank) in an earlier turn
   for (; kb <= sc.nslices && kb <= khi; kb += 32) {
     float pu[4][3];
     unsigned char fl[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      fl[u] = flag_of(place(kb + 8 * u + sl));
+      if constexpr (!SHARD) {
+        fl[u] = flag_of(place(kb + 8 * u + sl));
+      } else {
+        // entered by slice k: a sample in grown(rank) at this texel's slices <= k (lanes t + 8 s, s <= sl, of the turn)
+        const bool in = place(kb + 8 * u + sl);
+        const unsigned long long mine = (__ballot(g) >> t) & 0x0101010101010101ull;
+        const bool ent = entered || (mine & ((2ull << (8 * sl)) - 1ull)) != 0;
+        entered = entered || mine != 0;
+        fl[u] = flag_of(in && ent);
+      }
       pu[u][0] = p[0]; pu[u][1] = p[1]; pu[u][2] = p[2];
     }
 #pragma unroll
@@ -446,7 +495,7 @@ __global__ __launch_bounds__(256) void smk_k_shadow_light_march(const RenderPara
       float4 col = make_float4(0.f, 0.f, 0.f, 0.f);  // this lane's sample: saturated colour and alpha, alpha 0 = nothing to lay over
       if (fl[u]) {
         float ch0, ch1, ch2, ch3, n0, n1, n2;
-        shadow_fetch<DT, TF, false>(P, pu[u][0], pu[u][1], pu[u][2], ch0, ch1, ch2, ch3, n0, n1, n2);
+        shadow_fetch<DT, TF, false, SHARD>(P, pu[u][0], pu[u][1], pu[u][2], ch0, ch1, ch2, ch3, n0, n1, n2);
         float4 cc;
         if (shadow_maybe_visible<TF>(P, ch0, ch1) && smk_classify<DT, TF>(P, ch0, ch1, ch2, ch3, cc))
           col = make_float4(smk_sat(cc.x), smk_sat(cc.y), smk_sat(cc.z), cc.w);
@@ -474,12 +523,12 @@ __global__ __launch_bounds__(256) void smk_k_shadow_light_march(const RenderPara
     if (live && kb + sl <= sc.nslices) hist[(size_t)(kb + sl) * nl + o] = L;
 }
 
-template <int DT, int TF>
-static hipError_t run_march(const RenderParams &P, ShadowSlice Q, float4 *hist, long long hstride, hipStream_t s) {
+template <int DT, int TF, bool SHARD = false>
+static hipError_t run_march(const RenderParams &P, ShadowSlice Q, float4 *hist, long long hstride, const SmkShadowShard &S, hipStream_t s) {
   const smk_shadowcoef &sc = Q.sc;
   const int tiles = ((sc.LB + 7) / 8) * ((sc.LB + 3) / 4);
   const int lblocks = 8 * ((tiles + 7) / 8);
-  hipLaunchKernelGGL((smk_k_shadow_light_march<DT, TF>), dim3(lblocks), dim3(256), 0, s, P, Q, hist, hstride);
+  hipLaunchKernelGGL((smk_k_shadow_light_march<DT, TF, SHARD>), dim3(lblocks), dim3(256), 0, s, P, Q, hist, hstride, S);
   return hipGetLastError();
 }
 
@@ -490,11 +539,196 @@ hipError_t smk_launch_shadow_march(const RenderParams &P, const smk_shadowcoef &
   ShadowSlice Q;
   memset(&Q, 0, sizeof Q);
   Q.sc = sc;
+  SmkShadowShard S;
+  memset(&S, 0, sizeof S);
 #define CASE(D, T) \
-  if (dtype == D && tf_mode == T) return run_march<D, T>(P, Q, hist, hstride, s);
+  if (dtype == D && tf_mode == T) return run_march<D, T>(P, Q, hist, hstride, S, s);
   CASE(0, 1) CASE(0, 2) CASE(1, 1) CASE(1, 2)
 #undef CASE
   return hipErrorNotSupported;
+}
+
+hipError_t smk_launch_shadow_march_shard(const RenderParams &P, const smk_shadowcoef &sc, int dtype, int tf_mode, float4 *hist,
+                                         long long hstride, const SmkShadowShard &S, hipStream_t s) {
+  ShadowSlice Q;
+  memset(&Q, 0, sizeof Q);
+  Q.sc = sc;
+#define CASE(D, T) \
+  if (dtype == D && tf_mode == T) return run_march<D, T, true>(P, Q, hist, hstride, S, s);
+  CASE(0, 1) CASE(0, 2) CASE(1, 1) CASE(1, 2)
+#undef CASE
+  return hipErrorNotSupported;
+}
+
+// ---- shadows on a shard, phase 1 ("Shadows on shards"): this rank's OWNED samples of every texel's light ray,
+// marched once from transparent as the light march does (same waves of 8 texels x 8 slices, same brick flags, no history),
+// with a snapshot per destination rank j of the running value as it stood just before the ray's first sample in grown(j):
+// X_{rank->j}, all of rank's samples that come before the ray enters grown(j).  Rays that never enter grown(j) give j the
+// whole march (no texel j looks up needs them: harmless).  Slot `rank` stays zero.
+template <int DT, int TF>
+__global__ __launch_bounds__(256) void smk_k_shadow_exports(const RenderParams P, const ShadowSlice Q, const SmkShadowShard S) {
+  const smk_shadowcoef &sc = Q.sc;
+  const int bx = (sc.LB + 7) >> 3, by = (sc.LB + 3) >> 2;
+  int tile;
+  if (!shadow_tile_of_block((int)blockIdx.x, bx * by, tile)) return;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int t = lane & 7, sl = lane >> 3;
+  const int x = (tile % bx) * 8 + t, y = (tile / bx) * 4 + wave;
+  const bool live = x < sc.LB && y < sc.LB;
+  const size_t o = (size_t)y * sc.LB + x, nl = (size_t)sc.LB * sc.LB;
+  const float a = __fmaf_rn((float)x + 0.5f, sc.las, sc.lal), bb = __fmaf_rn((float)y + 0.5f, sc.las, sc.lal);
+  const float nG = __fmaf_rn(a, sc.nGx, __fmaf_rn(bb, sc.nGy, sc.nGc));
+  float G[3];
+#pragma unroll
+  for (int q = 0; q < 3; ++q) G[q] = __fmaf_rn(a, sc.Gx[q], __fmaf_rn(bb, sc.Gy[q], sc.Gc[q]));
+  int k0, k1;
+  shadow_k_range(P, sc.lnum0, sc.ldnum, nG, G, sc.Lc, sc.nslices, k0, k1);
+  if (!live) k1 = 0;
+  // this lane's sample of slice k: owned by this rank? and the grown boxes it lies in (bit j) -- the phase-2 march of rank j
+  // decides "entered" from the same positions with the same test
+  float p[3] = {0.f, 0.f, 0.f};
+  unsigned gm = 0;
+  auto place = [&](int k) -> bool {
+    gm = 0;
+    if (!(k >= k0 && k <= k1 && k <= sc.nslices)) return false;
+    const float w = __fdiv_rn(__fmaf_rn((float)k, sc.ldnum, sc.lnum0), nG);
+    const bool wok = w > 0.0f && !isinf(w);
+    bool in = wok;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      p[q] = __fmaf_rn(w, G[q], sc.Lc[q]);
+      in = in && p[q] >= P.sh.llo[q] && p[q] <= P.sh.lhi[q] && p[q] >= S.olo[q] && p[q] <= S.ohi[q];
+    }
+    if (wok)
+      for (int j = 0; j < S.nranks; ++j)
+        if (p[0] >= S.glo[j][0] && p[0] <= S.ghi[j][0] && p[1] >= S.glo[j][1] && p[1] <= S.ghi[j][1] && p[2] >= S.glo[j][2] &&
+            p[2] <= S.ghi[j][2])
+          gm |= 1u << j;
+    if (in && P.cplane_on) in = __fmaf_rn(p[0], P.cplane[0], __fmaf_rn(p[1], P.cplane[1], __fmaf_rn(p[2], P.cplane[2], P.cplane[3]))) >= 0.0f;
+    return in;
+  };
+  int klo = k1 >= k0 ? k0 : 0x7fffffff, khi = k1 >= k0 ? k1 : -0x7fffffff;
+  for (int off = 32; off > 0; off >>= 1) {
+    klo = min(klo, __shfl_xor(klo, off));
+    khi = max(khi, __shfl_xor(khi, off));
+  }
+  const int kb_first = klo > khi ? sc.nslices + 1 : 1 + ((klo - 1) & ~7);
+  float4 L = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 snap[SMK_MAX_RANKS];
+#pragma unroll
+  for (int j = 0; j < SMK_MAX_RANKS; ++j) snap[j] = L;
+  unsigned entered = 0;  // ranks whose grown box this texel's ray has entered (identical in the texel's 8 lanes)
+  for (int kb = kb_first; kb <= sc.nslices && kb <= khi; kb += 8) {
+    const bool in = place(kb + sl);
+    // per rank j: the turn's slice (0..7, 8 = none) of the texel's first sample in grown(j), 4 bits each
+    unsigned first = 0xffffffffu;
+    for (int j = 0; j < S.nranks; ++j) {
+      const unsigned long long mine = (__ballot((gm >> j) & 1u) >> t) & 0x0101010101010101ull;
+      const unsigned s0 = mine ? (unsigned)(__builtin_ctzll(mine) >> 3) : 8u;
+      first = (first & ~(15u << (4 * j))) | (s0 << (4 * j));
+    }
+    unsigned char fl = 0;
+    if (in) {
+      fl = 1;
+      if (P.bricks != nullptr) {
+        int x0, x1, y0, y1, z0, z1;
+        float fx, fy, fz;
+        smk_lin_clamp(p[0], P.N[0], x0, x1, fx);
+        smk_lin_clamp(p[1], P.N[1], y0, y1, fy);
+        smk_lin_clamp(p[2], P.N[2], z0, z1, fz);
+        shadow_local(P, x0, x1, y0, y1, z0, z1);
+        fl = P.bricks[((size_t)(z0 >> SMK_BRICK_LOG2) * P.nbr[1] + (size_t)(y0 >> SMK_BRICK_LOG2)) * P.nbr[0] + (size_t)(x0 >> SMK_BRICK_LOG2)];
+      }
+    }
+    float4 col = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (fl) {
+      float ch0, ch1, ch2, ch3, n0, n1, n2;
+      shadow_fetch<DT, TF, false, true>(P, p[0], p[1], p[2], ch0, ch1, ch2, ch3, n0, n1, n2);
+      float4 cc;
+      if (shadow_maybe_visible<TF>(P, ch0, ch1) && smk_classify<DT, TF>(P, ch0, ch1, ch2, ch3, cc))
+        col = make_float4(smk_sat(cc.x), smk_sat(cc.y), smk_sat(cc.z), cc.w);
+    }
+    const bool work = __any(col.w != 0.0f);
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+#pragma unroll
+      for (int j = 0; j < SMK_MAX_RANKS; ++j)
+        if (j < S.nranks && !((entered >> j) & 1u) && ((first >> (4 * j)) & 15u) == (unsigned)s) snap[j] = L;
+      if (work) {
+        const int src = t + 8 * s;
+        const float al = __shfl(col.w, src), cx = __shfl(col.x, src), cy = __shfl(col.y, src), cz = __shfl(col.z, src);
+        if (al != 0.0f) {  // (as the light march)
+          L.x = smk_sat(__fmaf_rn(al, cx - L.x, L.x));
+          L.y = smk_sat(__fmaf_rn(al, cy - L.y, L.y));
+          L.z = smk_sat(__fmaf_rn(al, cz - L.z, L.z));
+          L.w = smk_sat(__fmaf_rn(1.0f - al, L.w, al));
+        }
+      }
+    }
+    for (int j = 0; j < S.nranks; ++j)
+      if (((first >> (4 * j)) & 15u) != 8u) entered |= 1u << j;
+  }
+  if (!live || sl != 0) return;
+#pragma unroll
+  for (int j = 0; j < SMK_MAX_RANKS; ++j) {
+    if (j >= S.nranks) break;
+    const float4 v = j == S.rank ? make_float4(0.f, 0.f, 0.f, 0.f) : ((entered >> j) & 1u) ? snap[j] : L;
+    S.exports[(size_t)j * nl + o] = v;
+  }
+}
+
+hipError_t smk_launch_shadow_exports(const RenderParams &P, const smk_shadowcoef &sc, int dtype, int tf_mode, const SmkShadowShard &S,
+                                     hipStream_t s) {
+  ShadowSlice Q;
+  memset(&Q, 0, sizeof Q);
+  Q.sc = sc;
+  const int tiles = ((sc.LB + 7) / 8) * ((sc.LB + 3) / 4);
+  const int lblocks = 8 * ((tiles + 7) / 8);
+#define CASE(D, T)                                                                                    \
+  if (dtype == D && tf_mode == T) {                                                                  \
+    hipLaunchKernelGGL((smk_k_shadow_exports<D, T>), dim3(lblocks), dim3(256), 0, s, P, Q, S);        \
+    return hipGetLastError();                                                                        \
+  }
+  CASE(0, 1) CASE(0, 2) CASE(1, 1) CASE(1, 2)
+#undef CASE
+  return hipErrorNotSupported;
+}
+
+// the light samples of the frame that lie in [olo, ohi] (and in the volume, on the kept side of the clip plane): a thread
+// per texel, the light march's placement and tests (smk_get_stat "light_samples")
+__global__ __launch_bounds__(256) void smk_k_shadow_count_light(const RenderParams P, const smk_shadowcoef sc, SmkBox3 own,
+                                                                unsigned long long *count) {
+  const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
+  unsigned n = 0;
+  if (x < sc.LB && y < sc.LB) {
+    const float a = __fmaf_rn((float)x + 0.5f, sc.las, sc.lal), bb = __fmaf_rn((float)y + 0.5f, sc.las, sc.lal);
+    const float nG = __fmaf_rn(a, sc.nGx, __fmaf_rn(bb, sc.nGy, sc.nGc));
+    float G[3];
+    for (int q = 0; q < 3; ++q) G[q] = __fmaf_rn(a, sc.Gx[q], __fmaf_rn(bb, sc.Gy[q], sc.Gc[q]));
+    int k0, k1;
+    shadow_k_range(P, sc.lnum0, sc.ldnum, nG, G, sc.Lc, sc.nslices, k0, k1);
+    for (int k = k0; k <= k1 && k <= sc.nslices; ++k) {
+      const float w = __fdiv_rn(__fmaf_rn((float)k, sc.ldnum, sc.lnum0), nG);
+      bool in = w > 0.0f && !isinf(w);
+      float p[3];
+      for (int q = 0; q < 3; ++q) {
+        p[q] = __fmaf_rn(w, G[q], sc.Lc[q]);
+        in = in && p[q] >= P.sh.llo[q] && p[q] <= P.sh.lhi[q] && p[q] >= own.lo[q] && p[q] <= own.hi[q];
+      }
+      if (in && P.cplane_on) in = __fmaf_rn(p[0], P.cplane[0], __fmaf_rn(p[1], P.cplane[1], __fmaf_rn(p[2], P.cplane[2], P.cplane[3]))) >= 0.0f;
+      n += in ? 1u : 0u;
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
+  if ((threadIdx.x & 63) == 0 && n) atomicAdd(count, (unsigned long long)n);
+}
+
+hipError_t smk_launch_shadow_count_light(const RenderParams &P, const smk_shadowcoef &sc, const float olo[3], const float ohi[3],
+                                         unsigned long long *d_count, hipStream_t s) {
+  SmkBox3 own;
+  for (int q = 0; q < 3; ++q) { own.lo[q] = olo[q]; own.hi[q] = ohi[q]; }
+  hipLaunchKernelGGL(smk_k_shadow_count_light, dim3((sc.LB + 15) / 16, (sc.LB + 15) / 16), dim3(256), 0, s, P, sc, own, d_count);
+  return hipGetLastError();
 }
 
 template <int DT, int TF, int SH>

@@ -221,3 +221,24 @@ class ExchangePipeline:
             self._exchange(self.pending)
             self.pending = None
         self.x.wait(torch.cuda.current_stream().cuda_stream)
+
+
+def render_shadow_frame_local(renderers):
+    """One frame with shadows on P shard contexts of this process that share one device, ranks in order (smk.h "Shadows on
+    shards"): phase 1 and the light exchange (smk_shadow_exchange_local), every rank's frame, then the HIP "over" of the P
+    layers in smk_shard_order's order.  Returns the merged frame, a [H][W][4] float32 tensor on that device."""
+    from .binding import shadow_exchange_local
+    nranks = len(renderers)
+    w, h = renderers[0].size
+    npix = w * h
+    dev = torch.device("cuda", renderers[0].device)
+    shadow_exchange_local(renderers)
+    layers = torch.zeros((nranks, npix, 4), dtype=torch.float32, device=dev)
+    out = torch.zeros((npix, 4), dtype=torch.float32, device=dev)
+    torch.cuda.synchronize(dev)
+    for r, R in enumerate(renderers):
+        R.render_device(layers[r].data_ptr())
+    torch.cuda.synchronize(dev)
+    renderers[0].composite_over_device(layers.data_ptr(), nranks, renderers[0].shard_order(nranks), npix, out.data_ptr())
+    torch.cuda.synchronize(dev)
+    return out.view(h, w, 4)
