@@ -1175,12 +1175,11 @@ extern "C" int smk_shard_light_order(smk_ctx *c, int *order) {
 extern "C" int smk_set_option(smk_ctx *c, const char *key, int value) {
   if (!c || !key) return 1;
   if (!strcmp(key, "kernel")) c->opt_kernel = value;
-  else if (!strcmp(key, "slab_T")) c->opt_slab_T = value;
+  else if (!strcmp(key, "slab_T")) c->slab.opt_T = value & 0xff;
   else if (!strcmp(key, "inject_slab_status")) c->opt_inject_status = value;
-  else if (!strcmp(key, "slab_fly")) c->opt_slab_fly = value < 0 ? 0 : (value > 63 ? 63 : value);
-  else if (!strcmp(key, "slab_sched")) c->opt_slab_sched = value < 0 ? 0 : (value > 15 ? 15 : value);
-  else if (!strcmp(key, "slab_ns")) c->opt_slab_ns = value < 0 ? 0 : (value > 63 ? 63 : value);
-  else if (!strcmp(key, "tile")) c->opt_tile = value;
+  else if (!strcmp(key, "slab_fly")) c->slab.opt_fly = value < 0 ? 0 : (value > 63 ? 63 : value);
+  else if (!strcmp(key, "slab_ns")) c->slab.opt_ns = value < 0 ? 0 : (value > 63 ? 63 : value);
+  else if (!strcmp(key, "tile")) c->slab.opt_tile = value;
   else if (!strcmp(key, "shadow_march")) c->opt_shadow_march = value ? 1 : 0;  // (0: a launch per slice, the form of rounds 1-2)
   else if (!strcmp(key, "shadow_fused")) c->opt_lockstep = value ? (c->opt_lockstep | 256) : (c->opt_lockstep & ~256);  // (developer: all slices in one cooperative launch)
   else if (!strcmp(key, "slab_split")) c->slab.opt_split = value < 0 ? 0 : (value > 8 ? 8 : value);
@@ -2235,13 +2234,11 @@ extern "C" int smk_render_device(smk_ctx *c, void *d_rgba, void *d_depth, void *
     }
     if (c->opt_lockstep & 16) HIPCHK(c, hipMemsetAsync(c->slab.d_diag, 0, 16 * sizeof(float), s));
     const char *why = nullptr;
-    const int forced = c->opt_kernel == 2;
     c->slab.frame_ev0 = ev0_recorded ? nullptr : c->ev0;
-    const int knobs = c->opt_slab_T | (c->opt_slab_fly << 8) | (c->opt_slab_ns << 16) | (c->opt_slab_sched << 24);
-    hipError_t e = smk_launch_slab(P, c->dtype, c->tf_mode, shade_kind_of(c), knobs, c->opt_tile, forced, c->d_vox, c->d_vox_x, &c->slab, &why, s);
+    hipError_t e = smk_launch_slab(P, c->dtype, c->tf_mode, shade_kind_of(c), c->d_vox, c->d_vox_x, &c->slab, &why, s);
     if (e == hipErrorNotSupported && why && !strcmp(why, "x-major copy unavailable")) {
       if (make_xmajor_copy(c)) return 1;
-      e = smk_launch_slab(P, c->dtype, c->tf_mode, shade_kind_of(c), knobs, c->opt_tile, forced, c->d_vox, c->d_vox_x, &c->slab, &why, s);
+      e = smk_launch_slab(P, c->dtype, c->tf_mode, shade_kind_of(c), c->d_vox, c->d_vox_x, &c->slab, &why, s);
     }
     if (e == hipSuccess) {
       c->last_kernel = 2;

@@ -144,6 +144,9 @@ struct SlabAux {
   void *d_seg = nullptr;
   size_t seg_cap = 0;
   int opt_split = 0;            // option "slab_split": 0 auto, 1 off, 2.. forced
+  // developer options (0 = the planner decides): "tile" (workgroup shape id), "slab_T" (band wait + 1), "slab_fly"
+  // (slices a loader keeps in flight), "slab_ns" (cap on the ring's slots)
+  int opt_tile = 0, opt_T = 0, opt_fly = 0, opt_ns = 0;
   int nsplit_last = 0, nblocks_last = 0;
   std::vector<unsigned char> ksplit_last;  // pieces per tile of the latest launch
   unsigned *d_pticks = nullptr, *h_pticks = nullptr;  // [ntiles][8] durations of the pieces of split tiles (device; pinned copy)
@@ -321,11 +324,8 @@ struct smk_ctx {
   size_t out_cap = 0;
 
   // options / stats
-  int opt_kernel = 0, opt_slab_T = 0, opt_tf_raw = 0, opt_tile = 0;
-  int opt_slab_fly = 0;  // slices a loader keeps in flight (0 = default)
-  int opt_slab_ns = 0;   // cap on the ring's slots (0 = as many as fit)
+  int opt_kernel = 0, opt_tf_raw = 0;
   int opt_bricks = 1;      // brick flags on (0: every slice is streamed and sampled, as before round 2's last step)
-  int opt_slab_sched = 0;  // order of an XCD's tiles: 0 longest first, 1.. coarse weight classes + spatial blocks
   int opt_inject_status = 0;  // (test hook) the next slice-ring frame reports this status word
   int opt_wave_w = 8, opt_blk_w = 2, opt_lockstep = 1;
   SlabAux slab;  // slice-ring kernel side buffers
@@ -375,10 +375,9 @@ hipError_t smk_launch_shadow_count_light(const RenderParams &P, const smk_shadow
 int smk_shadow_shard_setup(smk_ctx *c, RenderParams &P, smk_shadowcoef &sc, SmkShadowShard &S, hipStream_t s);
 float4 *smk_shadow_entries_reserve(smk_ctx *c, int LB);
 void smk_shadow_entries_commit(smk_ctx *c, const smk_shadowcoef &sc);
-// returns hipErrorNotSupported (and *why) when the frame must use the gather kernel
-hipError_t smk_launch_slab(RenderParams P, int dtype, int tf_mode, int shade_kind, int opt_T, int opt_tile, int forced,
-                           const void *vox_native, const void *vox_xmajor, SlabAux *aux, const char **why,
-                           hipStream_t s);
+// plan + launch (smk_slab_plan.hip); returns hipErrorNotSupported (and *why) when the frame must use the gather kernel
+hipError_t smk_launch_slab(RenderParams P, int dtype, int tf_mode, int shade_kind, const void *vox_native, const void *vox_xmajor, SlabAux *aux,
+                           const char **why, hipStream_t s);
 // the column-stream kernel (smk_cols.hip); same convention as smk_launch_slab
 hipError_t smk_launch_cols(RenderParams P, int dtype, int tf_mode, int shade_kind, int knobs, const void *vox_native, ColsAux *aux,
                            int *status_word, const char **why, hipStream_t s);

@@ -37,55 +37,10 @@
 #include <type_traits>
 
 #include "smk_device.h"
+#include "smk_slab.h"
 
-// wave-uniform description of one launch
-struct SlabParams {
-  int perm;                    // 0: S=z (U=x,V=y)  1: S=y (U=x,V=z)  2: S=x (U=y,V=z; x-major copy)
-  int au, av, as;              // model-axis index of U, V, S
-  long long strideV, strideS;  // voxel strides of the layout in use (U stride is 1)
-  int Ou, Ov, Os;              // stored-box origin along U,V,S (global voxel index)
-  int Du, Dv, Ds;              // stored-box dims along U,V,S
-  int wu;                      // 16-byte units per window row that are loaded at most (<= wp)
-  int wv;                      // window rows that are loaded
-  int wp;                      // LDS row pitch in 16-byte units, a multiple of 8: the slot image is flat with this
-                               // pitch, so the (row, column) a DMA lane serves repeats every `per` chunks = `rpg` rows
-  int per, rpg;                // chunks and rows per group: per = wp / gcd(64, wp), rpg = 64 / gcd(64, wp)
-  int groups;                  // row groups per slice = ceil(wv / rpg); chunks = groups * per
-  int mask_need;               // loaders fetch only what each slice needs of the window (big windows)
-  int chunks;                  // DMA wave-instructions per slice = ceil(wv / rows per chunk), uniform
-  int slot_bytes;              // chunks * 1024
-  int nslots;                  // ring size
-  int maxfly;                  // slices a loader keeps in flight ((maxfly-1) * its chunks <= 63)
-  int wstep;                   // a wave steps when slices up to its slowest lane's position + 1 + wstep have landed
-  int pmask;                   // consumers publish progress when (iteration & pmask) == 0
-  int dir;                     // +1: rays advance towards +S, -1: towards -S
-  int tw, th;                  // pixel tile
-  const void *vox;             // layout base (native or x-major)
-  int use_ah;                  // third-axis alpha served from a 1-D LDS table (<= 3 channels)
-  int use_occ;                 // (V,G) occupancy bitmap copied to LDS
-  int fast_tf;                 // alpha-first classification with 8-byte texel loads (no third axis, or use_ah)
-  const unsigned char *bricks;  // brick flags of the stored box (smk_bricks.hip) or null: see "EMPTY LAYERS" in the kernel
-  int bsu, bsv, bss;           // their strides along U, V, S (in bricks)
-  const int2 *order;           // workgroup of each block: {tile | piece << 20 | pieces << 26, cut fractions lo | hi << 8} (work-balanced
-                               // schedule, .x = -1: none), see smk_launch_slab and DEPTH SEGMENTS
-  unsigned *tile_ticks;        // [5][ntiles]: duration of each tile's workgroup in 100 MHz ticks (next frame's weights) |
-                               // slices its loaders streamed | slices of its range (the loaders stop once every ray of
-                               // the tile is saturated: what was NOT streamed is not counted as read, smk_last_frame_info)
-  int ntiles;
-  int *status;                 // host-visible word: status_tag | (1 = protocol time-out, 2 = window bound violated)
-  int status_tag;              // the frame's id << 8: a word written late, into a slot that has been handed on, is told apart by it
-  float *diag;                 // [16] diagnostic counters (lockstep bit 16) or null
-  unsigned *trace;             // [nblocks][8] per-workgroup timeline record (lockstep bit 32, see smk.h) or null
-  float4 *seg_out;             // [maxseg - 1][W * H]: partial frames of the depth segments 1.. of split tiles (DEPTH SEGMENTS), or null
-  unsigned *piece_ticks;       // [ntiles][8]: duration of every piece of a split tile (where the next cuts come from)
-};
-
-#define SLAB_EPS 0.02f
-// cache policy of the LDS-DMA stream ("" = default, " nt" = non-temporal); an experiment knob
-#ifndef SLAB_DMA_POLICY
-#define SLAB_DMA_POLICY ""
-#endif
 #define SLAB_DONE 0x3fffffff
+constexpr int SLAB_POLL_SLEEP = 2;  // s_sleep of a consumer wave between two polls for its next slices
 
 template <int DT>
 struct VoxT;
@@ -141,14 +96,6 @@ __device__ __forceinline__ void slab_read8_nb8(unsigned a, unsigned ap, unsigned
   SLAB_READ8("ds_read_b32", "8");
 }
 #undef SLAB_READ8
-
-// per-slice table entry: where the slice's window sits in the ring and in the volume
-struct SlabEnt {
-  int base;      // LDS byte address of GLOBAL voxel (u=0, v=0) of this slice's slot image:
-                 // corner address = base + v * pitch_bytes + u * voxel_bytes
-  unsigned pack;  // loader: window origin u0 | v0 << 11 (stored-box voxels), (units the slice needs - 1) << 22,
-                  // rows of the window the slice can spare, in sixteenths of wv, << 28
-};
 
 typedef __attribute__((address_space(3))) void *lds_ptr_t;
 typedef __attribute__((address_space(3))) char *lds_cptr_w;
@@ -245,11 +192,8 @@ __device__ __forceinline__ float slab_tex_chan(const SlabTexel4 &x, int k) {
 // (SHD: the frame's planes are the half-angle slices of a frame with shadows -- SmkShadowRays; the eye pass of smk_shadow.hip.
 //  Compile-time: the instances live in smk_slab_shadow.hip, SLAB_PART 2)
 template <int DT, int SH, int PERM, int NW, int NL, bool DIAG, int TF = 1, bool BR = true, bool SHD = false>
-#ifndef SLAB_BIG_WAVES
-#define SLAB_BIG_WAVES 12  // workgroups of more waves than this are "big": one per CU
-#endif
 // (second argument: waves per SIMD the register allocation must allow -- two small workgroups per CU)
-__global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) == 5 || (NW + NL) == 10) ? 5 : ((NW + NL) == 11 ? 3 : ((NW + NL) == 12 && 12 <= SLAB_BIG_WAVES) ? 6 : ((NW + NL) == 14 && 14 <= SLAB_BIG_WAVES) ? 7 : 4)) void smk_k_slab(const RenderParams P, const SlabParams Q) {
+__global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) == 5 || (NW + NL) == 10) ? 5 : ((NW + NL) == 11 ? 3 : (NW + NL) == 12 ? 6 : 4)) void smk_k_slab(const RenderParams P, const SlabParams Q) {
   constexpr int UPV = DT == 0 ? 2 : 1;   // voxels per 16-byte DMA unit
   constexpr int VB = DT == 0 ? 8 : 16;   // bytes per voxel
   // (global_load_lds_dwordx3 does NOT compact: it writes 12 bytes per lane at a 16-byte lane stride
@@ -257,33 +201,20 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
   constexpr int VBL = DT == 0 ? 3 : 4;   // log2
   constexpr int NTH = (NW + NL) * 64;
   // big workgroups (one per CU, 128 VGPRs each): read whole voxels, release ring slots early
-#ifndef SLAB_EARLY
-#define SLAB_EARLY 1  // (re-measured with the loaders in pairs: without the early release 4.56 vs 4.11 ms on the 1024^3 frame)
-#endif
-  constexpr bool BIG = (NW + NL) > SLAB_BIG_WAVES;
-  constexpr bool EARLY = BIG && SLAB_EARLY;
+  // (re-measured with the loaders in pairs: without the early release 4.56 vs 4.11 ms on the 1024^3 frame)
+  constexpr bool BIG = slab_big(NW, NL);
+  constexpr bool EARLY = BIG;
   // ... and their loaders skip the row groups a slice does not need, counting DMA instructions per
   // slice; small workgroups keep every slice the same number of instructions (cheaper bookkeeping:
   // measured 3 % on the 512^3 frame, where the loaders' issue slots are the consumers')
-#ifndef SLAB_SMALL_FIFO
-#define SLAB_SMALL_FIFO 0
-#endif
-  constexpr bool FIFO = BIG || SLAB_SMALL_FIFO;
+  constexpr bool FIFO = BIG;
   // Small workgroups: the loaders take WHOLE slices in turn (loader l streams slices l, l + NL, ...) instead of a share of
   // the row groups of every slice.  A slice costs a loader ~120 scalar instructions before its first DMA (ring check,
   // table entry, 64-bit source address, column masks); with 3 DMA instructions per loader and slice that overhead was the
   // larger part of the loaders' time, and they were busy 90 % of the frame.  Big workgroups keep the split: their ring is
   // too short for NL slices being filled at once.
-#ifndef SLAB_ALT
-#define SLAB_ALT 1
-#endif
-  // Generalised: the loaders form NLG groups; group g streams slices g, g + NLG, ..., and the LPG loaders of a group
-  // share the row groups of such a slice.  Small workgroups: NLG = NL (a loader per slice).  Big ones: SLAB_BIG_NLG
-  // (1 = every loader works on every slice).
-#ifndef SLAB_BIG_NLG
-#define SLAB_BIG_NLG 2
-#endif
-  constexpr int NLG = !SLAB_ALT ? 1 : (BIG ? ((NL % SLAB_BIG_NLG) == 0 ? SLAB_BIG_NLG : 1) : NL);
+  // Generalised: the loaders form NLG groups of LPG loaders each (slab_loader_groups, smk_slab.h).
+  constexpr int NLG = slab_loader_groups(NW, NL);
   constexpr int LPG = NL / NLG;
   constexpr int QSTEP = NLG;
   extern __shared__ __align__(16) unsigned char smem[];
@@ -305,7 +236,7 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
   const int cut_lo = oent.y & 255, cut_hi = (oent.y >> 8) & 255;  // this piece's share of the tile's slice positions, in 255ths
   const bool flags = BR && Q.bricks != nullptr;
   const bool tracing = DIAG && Q.trace != nullptr && (P.lockstep & 32);  // (diagnostic: workgroup timeline)
-  // the workgroup's duration feeds the next frame's schedule (see smk_launch_slab): one scalar
+  // the workgroup's duration feeds the next frame's schedule (see slab_measured_weights in smk_slab_plan.hip): one scalar
   // timestamp at each end and one 4-byte store per tile
   const unsigned trace_t0 = (unsigned)__builtin_amdgcn_s_memrealtime();
   const int ty = tile / P.ntx, tx = tile - ty * P.ntx;
@@ -377,7 +308,6 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
   // -- lo <= p <= hin on every axis, hin = hi itself on a top face, else the float just below
   // it -- form ONE interval of q; the conservative range above brackets it with a few planes of
   // slack, so testing its ends here removes the per-sample test from the marching loop.
-#ifndef SLAB_NO_INTERVAL
   {
     auto inside = [&](int q) -> bool {
       const float qf = (float)q;
@@ -407,7 +337,6 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
     m = mf;  // (no inside sample at all: mf = m1 + 1 > ml, the ray is empty)
     m1 = ml;
   }
-#endif
 
   constexpr int AS = PERM == 0 ? 2 : (PERM == 1 ? 1 : 0);
   constexpr int AU = PERM == 2 ? 1 : 0;
@@ -769,7 +698,7 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
       // (saddr form: no per-chunk VALU; M0 written in the statement that reads it)
       unsigned keep_m0;
 #define SLAB_DMA(src_, dst_, voff_)                                                                                 \
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3" SLAB_DMA_POLICY "\n\ts_mov_b32 m0, %0" \
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0" \
                : "=&s"(keep_m0)                                                                                     \
                : "v"(voff_), "s"(dst_), "s"(src_)                                                                   \
                : "memory")
@@ -788,12 +717,9 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
       // after every group of chunks the loader looks, and publishes each in-flight slice whose last
       // instruction is no longer outstanding.  `cur` = instructions of the slice being issued so far
       // (younger than everything in flight).  The blocking wait stays for when nothing can be issued.
-#ifndef SLAB_EAGER
-#define SLAB_EAGER 1
-#endif
       // (big workgroups only: on the small ones' deep ring a late word costs little, and the look costs
       //  the kernel scalar registers -- 97 spilled SGPRs against 39)
-      constexpr bool EAGER = SLAB_EAGER && BIG;
+      constexpr bool EAGER = BIG;
       auto publish_landed = [&](int cur) {
         if (!EAGER || inflight == 0) return;
         const unsigned st = __builtin_amdgcn_s_getreg((31 << 11) | 7);
@@ -876,10 +802,7 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
             // nothing
           } else if (uv != -1) {
             // (small windows: the whole shape -- the saving would not pay for the partial-group path)
-#ifndef SLAB_LIGHT_FULLROWS
-#define SLAB_LIGHT_FULLROWS 0
-#endif
-            const unsigned need_u = (SLAB_LIGHT_FULLROWS && !FIFO) ? (unsigned)Q.wp : Q.mask_need ? (((unsigned)uv >> 22) & 0x3fu) + 1u : (unsigned)Q.wu;
+            const unsigned need_u = Q.mask_need ? (((unsigned)uv >> 22) & 0x3fu) + 1u : (unsigned)Q.wu;
             const unsigned need_v = Q.mask_need ? (unsigned)Q.wv - ((unsigned)uv >> 28) * (unsigned)((Q.wv + 15) / 16) : (unsigned)Q.wv;
             const int sl = (dir > 0 ? smin + q : smax + 1 - q) - Q.Os;
             const unsigned u0 = (unsigned)uv & 0x7ffu, v0 = ((unsigned)uv >> 11) & 0x7ffu;
@@ -923,9 +846,9 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
                   // (every chunk has a column-0 lane, so no mask is empty)
                   unsigned long long keep_exec;
                   asm volatile("s_mov_b32 %[km], m0\n\ts_mov_b64 %[ke], exec\n\ts_mov_b32 m0, %[dst]\n\t"
-                               "s_mov_b64 exec, %[e0]\n\tglobal_load_lds_dwordx4 %[v0], %[src]" SLAB_DMA_POLICY "\n\ts_add_u32 m0, m0, 0x400\n\t"
-                               "s_mov_b64 exec, %[e1]\n\tglobal_load_lds_dwordx4 %[v1], %[src]" SLAB_DMA_POLICY "\n\ts_add_u32 m0, m0, 0x400\n\t"
-                               "s_mov_b64 exec, %[e2]\n\tglobal_load_lds_dwordx4 %[v2], %[src]" SLAB_DMA_POLICY "\n\t"
+                               "s_mov_b64 exec, %[e0]\n\tglobal_load_lds_dwordx4 %[v0], %[src]\n\ts_add_u32 m0, m0, 0x400\n\t"
+                               "s_mov_b64 exec, %[e1]\n\tglobal_load_lds_dwordx4 %[v1], %[src]\n\ts_add_u32 m0, m0, 0x400\n\t"
+                               "s_mov_b64 exec, %[e2]\n\tglobal_load_lds_dwordx4 %[v2], %[src]\n\t"
                                "s_mov_b64 exec, %[ke]\n\ts_mov_b32 m0, %[km]"
                                : [km] "=&s"(keep_m0), [ke] "=&s"(keep_exec)
                                : [dst] "s"(dst), [src] "s"(src), [e0] "s"(mk[0]), [e1] "s"(mk[1]), [e2] "s"(mk[2]), [v0] "v"(voff[0]),
@@ -934,7 +857,7 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
                 } else if (per == 1) {  // one chunk per group (pitches 8, 16, 32, 64): the same, once
                   unsigned long long keep_exec;
                   asm volatile("s_mov_b32 %[km], m0\n\ts_mov_b64 %[ke], exec\n\ts_mov_b32 m0, %[dst]\n\t"
-                               "s_mov_b64 exec, %[e0]\n\tglobal_load_lds_dwordx4 %[v0], %[src]" SLAB_DMA_POLICY "\n\t"
+                               "s_mov_b64 exec, %[e0]\n\tglobal_load_lds_dwordx4 %[v0], %[src]\n\t"
                                "s_mov_b64 exec, %[ke]\n\ts_mov_b32 m0, %[km]"
                                : [km] "=&s"(keep_m0), [ke] "=&s"(keep_exec)
                                : [dst] "s"(dst), [src] "s"(src), [e0] "s"(mk[0]), [v0] "v"(voff[0])
@@ -958,12 +881,8 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
               src += gstep;
               dst += (unsigned)(gn * per * 1024);
               row0 += (unsigned)(gn * rpg);
-#ifndef SLAB_PUBLISH_PER_GROUP
-#define SLAB_PUBLISH_PER_GROUP 1
-#endif
-              if (SLAB_PUBLISH_PER_GROUP) publish_landed(issued);
+              publish_landed(issued);
             }
-            if (!SLAB_PUBLISH_PER_GROUP) publish_landed(issued);
 #undef SLAB_GROUP
 #undef CM
           } else if (!FIFO) {
@@ -1097,27 +1016,23 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
               }
               // (backing off further for waves whose first slice is many slices away was measured
               //  slower: reaction time matters more than the polls' issue slots)
-#ifndef SLAB_POLL_SLEEP
-#define SLAB_POLL_SLEEP 2
-#endif
               __builtin_amdgcn_s_sleep(SLAB_POLL_SLEEP);
               have = landed_all();
             }
           }
           have = __builtin_amdgcn_readfirstlane(have);
         }
-        // (Measured and dropped: SLAB_REPS samples per lane and turn of the loop, to pay the loop's own
+        // (Measured and dropped: several samples per lane and turn of the loop, to pay the loop's own
         //  cost -- progress word, poll, flow control -- once per two or three samples.  512^3 f32 frame,
-        //  REPS 1 / 2 / 3: 1.89 / 2.02 / 1.97 ms; the scalar instruction count did not move (4.74e8 ->
+        //  1 / 2 / 3 samples: 1.89 / 2.02 / 1.97 ms; the scalar instruction count did not move (4.74e8 ->
         //  4.81e8) and the vector one rose 12 %: lanes whose next slices have not landed sit the extra
-        //  sample out, so the second body mostly runs with few lanes.  Kept as a build knob.)
-#ifndef SLAB_REPS
-#define SLAB_REPS 1
-#endif
+        //  sample out, so the second body mostly runs with few lanes.)
+        // (one sample per turn; the body stays a one-turn loop: as a plain block it changes the register allocation of
+        //  the u8 colour-table instances)
 #pragma unroll
-        for (int rep = 0; rep < (EARLY ? 1 : SLAB_REPS); ++rep) {
+        for (int rep = 0; rep < 1; ++rep) {
         const bool act = pb < SLAB_DONE && pb + 2 <= have;
-        if (count && rep == 0) {
+        if (count) {
           n_lead += (float)(have - pos);
           n_wstep += (float)Q.wstep;
         }
@@ -1145,7 +1060,6 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
         // entry holds its length, see the set-up) -- the first plane whose base slice lies behind the run.  The planes
         // in between fall into empty layers, all of them: positions are monotone in the plane index.
         int m_next = m + 1;
-#ifndef SLAB_NO_JUMP
         if (flags && act && (base_a & 3) == 3) {
           const int ptar = pb + (base_a >> 2);  // first position behind the run
           if (ptar >= npos) m_next = m1 + 1;    // nothing but empty layers to the end of the tile's range
@@ -1162,7 +1076,6 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
             m_next = mj;
           }
         }
-#endif
         if (work) {
           const float mf = (float)m;
           // (no membership test: [m, m1] is exactly the inside interval, see the set-up)
@@ -1496,7 +1409,7 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
 
 // ------------------------------------------------------------------------------- host side
 
-// This file is compiled three times (build time: the instances are most of it): as itself -- host side + the byte-voxel
+// This file is compiled three times (build time: the instances are most of it): as itself -- the merge pass + the byte-voxel
 // instances --, through smk_slab_f32.hip (SLAB_PART 1) -- the float-voxel instances alone -- and through smk_slab_shadow.hip
 // (SLAB_PART 2) -- the instances of the eye pass of frames with shadows.
 #ifndef SLAB_PART
@@ -1529,206 +1442,11 @@ __global__ __launch_bounds__(256) void smk_k_slab_merge(const int2 *list, int tw
     out[o] = C;
   }
 }
-
-// a ray's coefficients on the host, for planning: at a real-valued position (px, py) of the image plane, in double -- the
-// kernels' float chains (smk_ray_AB) round differently by less than the planning's own slack
-static void host_ray_at(const RenderParams &P, double px, double py, double A[3], double B[3]) {
-  const smk_raycoef &rc = P.rc;
-  if (!P.sh.on) {
-    for (int a = 0; a < 3; ++a) {
-      A[a] = px * rc.Ax[a] + py * rc.Ay[a] + rc.Ac[a];
-      B[a] = px * rc.Bx[a] + py * rc.By[a] + rc.Bc[a];
-    }
-    return;
-  }
-  const SmkShadowRays &sh = P.sh;  // frames with shadows: half-angle slices (smk_internal.h)
-  const double nD = px * sh.nDx + py * sh.nDy + sh.nDc, tauA = sh.numA / nD, dtau = sh.dB / nD;
-  for (int a = 0; a < 3; ++a) {
-    const double D = px * sh.Dx[a] + py * sh.Dy[a] + sh.Dc[a];
-    A[a] = sh.Ec[a] + tauA * D;
-    B[a] = dtau * D;
-  }
+hipError_t smk_slab_merge(const int2 *list, int n, int tw, int th, int ntx, int W, int H, const float4 *seg_out, float4 *out, int use_max,
+                          hipStream_t s) {
+  hipLaunchKernelGGL(smk_k_slab_merge, dim3(n), dim3(256), 0, s, list, tw, th, ntx, W, H, seg_out, out, use_max);
+  return hipGetLastError();
 }
-static void host_ray(const RenderParams &P, int i, int j, double A[3], double B[3]) {
-  const smk_raycoef &rc = P.rc;
-  const float px = fmaf((float)i + 0.5f, rc.pxs, rc.pxl), py = fmaf((float)j + 0.5f, rc.pys, rc.pyl);
-  if (P.sh.on) {
-    host_ray_at(P, px, py, A, B);
-    return;
-  }
-  for (int a = 0; a < 3; ++a) {
-    A[a] = fmaf(px, rc.Ax[a], fmaf(py, rc.Ay[a], rc.Ac[a]));
-    B[a] = fmaf(px, rc.Bx[a], fmaf(py, rc.By[a], rc.Bc[a]));
-  }
-}
-
-// ---- S-extent of (a tile's ray bundle between the first and the last sample plane) /\ (the region
-// box), in voxel index coordinates.  The bundle is the pyramid section spanned by the rays through
-// the tile's outer pixel EDGES (half a pixel beyond the corner pixels' centres, so a one-pixel-wide
-// tile is not degenerate); rays are affine in the pixel coordinate, so every ray of the tile lies
-// inside it.  Both bodies are convex: the extrema over the intersection sit on its vertices = the
-// vertices of the box faces clipped by the pyramid's six planes + the pyramid's corners inside the
-// box.  Corner rays alone do not bound this: all four may miss a volume that projects inside the
-// tile, and a ray through a side face enters anywhere between the front and the back face.
-namespace {
-struct SlabVec { double v[3]; };
-
-int slab_clip_polygon(const SlabVec *in, int n, const double pl[4], SlabVec *out) {  // keeps pl.(p,1) >= 0
-  int m = 0;
-  for (int k = 0; k < n; ++k) {
-    const SlabVec &a = in[k], &b = in[(k + 1) % n];
-    const double da = pl[0] * a.v[0] + pl[1] * a.v[1] + pl[2] * a.v[2] + pl[3];
-    const double db = pl[0] * b.v[0] + pl[1] * b.v[1] + pl[2] * b.v[2] + pl[3];
-    if (da >= 0) out[m++] = a;
-    if ((da >= 0) != (db >= 0)) {
-      const double t = da / (da - db);
-      SlabVec c;
-      for (int i = 0; i < 3; ++i) c.v[i] = a.v[i] + t * (b.v[i] - a.v[i]);
-      out[m++] = c;
-    }
-  }
-  return m;
-}
-
-bool slab_bundle_slice_range_exact(const RenderParams &P, double fx0, double fy0, double fx1, double fy1, int as, double *smin,
-                                   double *smax);
-// The common case without clipping: when the four corner rays enter the box through ONE face and leave it through ONE
-// face (inside the sampled plane range), so does every ray between them -- the rays through a face form a convex set --
-// and bundle /\ box is the hexahedron of the four entry and four exit points: its S-extent is theirs.  (A bundle that
-// contains a box edge or vertex, or is cut by the first / last sample plane, goes the exact way below.)
-static bool slab_bundle_slice_range_fast(const RenderParams &P, double fx0, double fy0, double fx1, double fy1, int as, double *smin,
-                                         double *smax) {
-  const smk_raycoef &rc = P.rc;
-  const double fx[4] = {fx0, fx1, fx1, fx0}, fy[4] = {fy0, fy0, fy1, fy1};
-  const double q0 = -0.5, q1 = (double)(rc.nplanes - 1) + 0.5, eps = 1e-3;
-  int fin = -1, fout = -1;
-  double mn = 1e300, mx = -1e300;
-  for (int c = 0; c < 4; ++c) {
-    const double px = fx[c] * (double)rc.pxs + (double)rc.pxl, py = fy[c] * (double)rc.pys + (double)rc.pyl;
-    double A[3], B[3], te = -1e300, tx = 1e300;
-    int ie = -1, ix = -1;
-    host_ray_at(P, px, py, A, B);
-    for (int a = 0; a < 3; ++a) {
-      const double lo = (double)P.lo[a] - eps, hi = (double)P.hi[a] + eps;
-      if (fabs(B[a]) < 1e-12) {
-        if (A[a] < lo || A[a] > hi) return false;
-        continue;
-      }
-      const double t1 = (lo - A[a]) / B[a], t2 = (hi - A[a]) / B[a];
-      const double tn = t1 < t2 ? t1 : t2, tf = t1 < t2 ? t2 : t1;
-      if (tn > te) { te = tn; ie = 2 * a + (t1 < t2 ? 0 : 1); }
-      if (tf < tx) { tx = tf; ix = 2 * a + (t1 < t2 ? 1 : 0); }
-    }
-    if (!(te < tx) || te < q0 || tx > q1 || ie < 0 || ix < 0) return false;
-    if (c == 0) { fin = ie; fout = ix; }
-    else if (ie != fin || ix != fout) return false;
-    const double se = A[as] + te * B[as], sx = A[as] + tx * B[as];
-    mn = std::min(mn, std::min(se, sx));
-    mx = std::max(mx, std::max(se, sx));
-  }
-  *smin = std::max(mn, (double)P.lo[as]);
-  *smax = std::min(mx, (double)P.hi[as]);
-  return true;
-}
-
-bool slab_bundle_slice_range(const RenderParams &P, double fx0, double fy0, double fx1, double fy1, int as, double *smin,
-                             double *smax) {
-  static const int check = getenv("SMK_DEBUG_SCAN") ? atoi(getenv("SMK_DEBUG_SCAN")) : 0;  // (developer: 1 = compare the short way with the exact one, 2 = exact only)
-  if (check != 2 && slab_bundle_slice_range_fast(P, fx0, fy0, fx1, fy1, as, smin, smax)) {
-    if (!check) return true;
-    double a = 0, b = 0;
-    const bool ok = slab_bundle_slice_range_exact(P, fx0, fy0, fx1, fy1, as, &a, &b);
-    if (!ok || fabs(a - *smin) > 5e-3 || fabs(b - *smax) > 5e-3)  // (the exact way pads its clipping planes by 1e-6 of the scene's scale)
-      fprintf(stderr, "[smk] SCAN MISMATCH tile (%g,%g)-(%g,%g): fast [%.9g, %.9g] exact %d [%.9g, %.9g]\n", fx0, fy0, fx1, fy1, *smin, *smax, (int)ok, a, b);
-    return true;
-  }
-  return slab_bundle_slice_range_exact(P, fx0, fy0, fx1, fy1, as, smin, smax);
-}
-
-bool slab_bundle_slice_range_exact(const RenderParams &P, double fx0, double fy0, double fx1, double fy1, int as, double *smin,
-                                   double *smax) {
-  const smk_raycoef &rc = P.rc;
-  const double fx[4] = {fx0, fx1, fx1, fx0}, fy[4] = {fy0, fy0, fy1, fy1};  // cyclic
-  const double q0 = -0.5, q1 = (double)(rc.nplanes - 1) + 0.5;
-  SlabVec F[4][2];
-  double cen[3] = {0, 0, 0}, scale = 1.0;
-  for (int c = 0; c < 4; ++c) {
-    const double px = fx[c] * (double)rc.pxs + (double)rc.pxl, py = fy[c] * (double)rc.pys + (double)rc.pyl;
-    double Ar[3], Br[3];
-    host_ray_at(P, px, py, Ar, Br);
-    for (int a = 0; a < 3; ++a) {
-      const double A = Ar[a], B = Br[a];
-      F[c][0].v[a] = A + q0 * B;
-      F[c][1].v[a] = A + q1 * B;
-      cen[a] += (F[c][0].v[a] + F[c][1].v[a]) / 8.0;
-      scale = std::max(scale, std::max(fabs(F[c][0].v[a]), fabs(F[c][1].v[a])));
-    }
-  }
-  double planes[6][4];
-  int npl = 0;
-  auto add_plane = [&](const SlabVec &a, const SlabVec &b, const SlabVec &c) {
-    double e1[3], e2[3], n[4];
-    for (int i = 0; i < 3; ++i) { e1[i] = b.v[i] - a.v[i]; e2[i] = c.v[i] - a.v[i]; }
-    n[0] = e1[1] * e2[2] - e1[2] * e2[1];
-    n[1] = e1[2] * e2[0] - e1[0] * e2[2];
-    n[2] = e1[0] * e2[1] - e1[1] * e2[0];
-    const double len = sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
-    if (!(len > 1e-12 * scale * scale)) return;  // degenerate: not clipping keeps a superset
-    for (int i = 0; i < 3; ++i) n[i] /= len;
-    n[3] = -(n[0] * a.v[0] + n[1] * a.v[1] + n[2] * a.v[2]);
-    if (n[0] * cen[0] + n[1] * cen[1] + n[2] * cen[2] + n[3] < 0)
-      for (int i = 0; i < 4; ++i) n[i] = -n[i];
-    // every corner of the pyramid stays inside (fp slack, sides that are not exactly planar)
-    double worst = 0;
-    for (int c = 0; c < 4; ++c)
-      for (int e = 0; e < 2; ++e)
-        worst = std::min(worst, n[0] * F[c][e].v[0] + n[1] * F[c][e].v[1] + n[2] * F[c][e].v[2] + n[3]);
-    n[3] += -worst + 1e-6 * scale;
-    for (int i = 0; i < 4; ++i) planes[npl][i] = n[i];
-    ++npl;
-  };
-  for (int c = 0; c < 4; ++c) add_plane(F[c][0], F[c][1], F[(c + 1) & 3][0]);
-  add_plane(F[0][0], F[1][0], F[2][0]);
-  add_plane(F[0][1], F[1][1], F[2][1]);
-
-  const double eps = 1e-3;
-  double lo[3], hi[3];
-  for (int a = 0; a < 3; ++a) { lo[a] = (double)P.lo[a] - eps; hi[a] = (double)P.hi[a] + eps; }
-  double mn = 1e300, mx = -1e300;
-  for (int c = 0; c < 4; ++c)
-    for (int e = 0; e < 2; ++e) {
-      const double *p = F[c][e].v;
-      if (p[0] >= lo[0] && p[0] <= hi[0] && p[1] >= lo[1] && p[1] <= hi[1] && p[2] >= lo[2] && p[2] <= hi[2]) {
-        mn = std::min(mn, p[as]);
-        mx = std::max(mx, p[as]);
-      }
-    }
-  for (int a = 0; a < 3; ++a)
-    for (int side = 0; side < 2; ++side) {
-      const int b = (a + 1) % 3, c = (a + 2) % 3;
-      SlabVec poly[2][24];
-      const double bb[4] = {lo[b], hi[b], hi[b], lo[b]}, cc[4] = {lo[c], lo[c], hi[c], hi[c]};
-      for (int k = 0; k < 4; ++k) {
-        poly[0][k].v[a] = side ? hi[a] : lo[a];
-        poly[0][k].v[b] = bb[k];
-        poly[0][k].v[c] = cc[k];
-      }
-      int n = 4, cur = 0;
-      for (int k = 0; k < npl && n > 0; ++k) {
-        n = slab_clip_polygon(poly[cur], n, planes[k], poly[cur ^ 1]);
-        cur ^= 1;
-      }
-      for (int k = 0; k < n; ++k) {
-        mn = std::min(mn, poly[cur][k].v[as]);
-        mx = std::max(mx, poly[cur][k].v[as]);
-      }
-    }
-  if (!(mn <= mx)) return false;
-  *smin = std::max(mn, (double)P.lo[as]);
-  *smax = std::min(mx, (double)P.hi[as]);
-  return true;
-}
-}  // namespace
 #endif  // SLAB_PART == 0
 
 template <int DT, int SH, int PERM, int NW, int NL, bool DIAG, int TF = 1, bool BR = true, bool SHD = false>
@@ -1746,16 +1464,7 @@ static hipError_t launch_slab(const RenderParams &P, const SlabParams &Q, size_t
   return hipGetLastError();
 }
 
-// plan + launch; returns hipErrorNotSupported when the configuration must use the gather kernel
-
-// ---- instance dispatch, one function per voxel type (one translation unit each)
-hipError_t smk_slab_dispatch_u8(const RenderParams &P, const SlabParams &Q, int tf_mode, int shade_kind, int nw, int nl, bool diag, size_t lds,
-                                int nblocks, const char **why, hipStream_t s);
-hipError_t smk_slab_dispatch_f32(const RenderParams &P, const SlabParams &Q, int tf_mode, int shade_kind, int nw, int nl, bool diag, size_t lds,
-                                 int nblocks, const char **why, hipStream_t s);
-// ... and one for the eye pass of frames with shadows (SHD instances: 2-D / 3-D table, R8k shading or none, both voxel types)
-hipError_t smk_slab_dispatch_shadow(const RenderParams &P, const SlabParams &Q, int dtype, int tf_mode, int shade_kind, int nw, int nl, size_t lds,
-                                    int nblocks, const char **why, hipStream_t s);
+// ---- instance dispatch (declared in smk_slab.h)
 #if SLAB_PART == 2
 hipError_t smk_slab_dispatch_shadow(const RenderParams &P, const SlabParams &Q, int dtype, int tf_mode, int shade_kind, int nw, int nl, size_t lds,
                                     int nblocks, const char **why, hipStream_t s) {
@@ -1814,23 +1523,13 @@ hipError_t smk_slab_dispatch_f32(const RenderParams &P, const SlabParams &Q, int
     if (Q.bricks) return (launch_slab<D, S, R, N, L, false, 1, true>(P, Q, lds, nblocks, s));  \
     return (launch_slab<D, S, R, N, L, false, 1, false>(P, Q, lds, nblocks, s));         \
   }
-  // product tile shapes: 32x16 px with 8+2 waves, 32x24 px with 12+4; the others are experiment knobs (option "tile")
-#ifdef SLAB_ALL_TILES
-#define GO_NW(D, S, R) GO(D, S, R, 4, 1) GO(D, S, R, 6, 2) GO(D, S, R, 8, 1) GO(D, S, R, 8, 2) GO(D, S, R, 8, 4) GO(D, S, R, 9, 2) GO(D, S, R, 12, 2) GO(D, S, R, 12, 4) GO(D, S, R, 8, 8) GO(D, S, R, 10, 6) GO(D, S, R, 10, 2)
-#else
+  // workgroup shapes: 8+2 waves (32x16 px), 10+2 (40x16 or 16x40 px), 12+4 (32x24 px and the shapes of option "tile")
 #define GO_NW(D, S, R) GO(D, S, R, 8, 2) GO(D, S, R, 10, 2) GO(D, S, R, 12, 4)
-#endif
 #define GO_R(D, S) GO_NW(D, S, 0) GO_NW(D, S, 1) GO_NW(D, S, 2)
 #if SLAB_PART == 0
-#ifndef SLAB_FEW_INSTANCES
   GO_R(0, 0) GO_R(0, 1) GO_R(0, 2)
-#endif
-#else
-#ifdef SLAB_FEW_INSTANCES
-  GO_R(1, 1)
 #else
   GO_R(1, 0) GO_R(1, 1) GO_R(1, 2)
-#endif
 #endif
 #undef GO_R
 #undef GO_NW
@@ -1839,881 +1538,3 @@ hipError_t smk_slab_dispatch_f32(const RenderParams &P, const SlabParams &Q, int
   return hipErrorNotSupported;
 }
 #endif  // SLAB_PART != 2
-
-#if SLAB_PART == 0
-hipError_t smk_launch_slab(RenderParams P, int dtype, int tf_mode, int shade_kind, int opt_T, int opt_tile, int forced,
-                           const void *vox_native, const void *vox_xmajor, SlabAux *aux, const char **why,
-                           hipStream_t s) {
-  const int opt_fly = (opt_T >> 8) & 0xff;  // (developer knobs travel packed: slab_T | slab_fly << 8 | slab_ns << 16 | slab_sched << 24)
-  const int opt_ns = (opt_T >> 16) & 0xff;
-  const int opt_sched = (opt_T >> 24) & 0xf;  // (experiment knob: order of an XCD's tiles, see the schedule)
-  const int opt_split = P.depth ? 1 : aux->opt_split;  // DEPTH SEGMENTS: 0 auto (measured long tiles), 1 off, 2.. every tile in that many (a depth output: off -- the merge pass knows colours only)
-  opt_T &= 0xff;
-  *why = nullptr;
-  if (tf_mode < 0 || tf_mode > 2) { *why = "no classification mode"; return hipErrorNotSupported; }
-  if (tf_mode == 0 && (!P.tlut || P.tlut_size < 1)) { *why = "no colour table"; return hipErrorNotSupported; }
-  if (tf_mode == 0) shade_kind = 0;  // (the scalar renderer does not shade, VolumeRenderer.cpp:576-587)
-  if (tf_mode == 2 && (!P.tf3d || P.s3v < 1 || P.s3g < 1 || P.s3h < 1)) { *why = "no 3-D table"; return hipErrorNotSupported; }
-  if (P.pert_on) { *why = "perturbation"; return hipErrorNotSupported; }
-  // (back-to-front frames -- VolumeRenderer.cpp:590 -- are composited FRONT TO BACK here: "over" is associative, the slices
-  //  stream one way; what changes is the association of the blend -- a few ulp per sample, as with depth segments -- and a
-  //  saturated ray may stop.  Option kernel = 1 renders them in the reference's own order.)
-  if (P.N[0] < 2 || P.N[1] < 2 || P.N[2] < 2) { *why = "volume thinner than 2 voxels"; return hipErrorNotSupported; }
-  if (dtype == 1 && !P.n_in_w) { *why = "4-channel f32 voxels"; return hipErrorNotSupported; }
-  if (P.rc.nplanes <= 0) { *why = "no planes"; return hipErrorNotSupported; }
-  if (P.sh.on) {
-    // frames with shadows: the component of a ray along the slice normal is affine in the pixel coordinate; where it keeps
-    // its sign over the viewport's corners no ray runs parallel to the slices (the planning divides by it)
-    double lo_n = 1e300, hi_n = -1e300;
-    for (int c = 0; c < 4; ++c) {
-      const double px = ((c & 1) ? (double)P.W : 0.0) * P.rc.pxs + P.rc.pxl, py = ((c & 2) ? (double)P.H : 0.0) * P.rc.pys + P.rc.pyl;
-      const double nD = px * P.sh.nDx + py * P.sh.nDy + P.sh.nDc;
-      lo_n = std::min(lo_n, nD);
-      hi_n = std::max(hi_n, nD);
-    }
-    if (!(lo_n > 0 || hi_n < 0) || std::min(fabs(lo_n), fabs(hi_n)) < 1e-6 * std::max(fabs(lo_n), fabs(hi_n))) {
-      *why = "half-angle slices parallel to some eye ray";
-      return hipErrorNotSupported;
-    }
-  }
-
-  // principal axis from the central ray
-  double Ac[3], Bc[3];
-  host_ray(P, P.W / 2, P.H / 2, Ac, Bc);
-  int as = 0;
-  for (int a = 1; a < 3; ++a)
-    if (fabs(Bc[a]) > fabs(Bc[as])) as = a;
-  SlabParams Q;
-  memset(&Q, 0, sizeof Q);
-  Q.status = aux->h_status + aux->status_slot;
-  Q.status_tag = aux->status_tag;
-  Q.diag = aux->d_diag;
-  Q.as = as;
-  if (as == 2) { Q.perm = 0; Q.au = 0; Q.av = 1; }
-  else if (as == 1) { Q.perm = 1; Q.au = 0; Q.av = 2; }
-  else { Q.perm = 2; Q.au = 1; Q.av = 2; }
-  if (Q.perm == 2 && !vox_xmajor) { *why = "x-major copy unavailable"; return hipErrorNotSupported; }
-  Q.dir = Bc[as] > 0 ? 1 : -1;
-  Q.Ou = P.O[Q.au]; Q.Ov = P.O[Q.av]; Q.Os = P.O[as];
-  Q.Du = P.D[Q.au]; Q.Dv = P.D[Q.av]; Q.Ds = P.D[as];
-  if (Q.perm == 0) { Q.strideV = P.D[0]; Q.strideS = (long long)P.D[0] * P.D[1]; Q.vox = vox_native; }
-  else if (Q.perm == 1) { Q.strideV = (long long)P.D[0] * P.D[1]; Q.strideS = P.D[0]; Q.vox = vox_native; }
-  else { Q.strideV = P.D[1]; Q.strideS = (long long)P.D[1] * P.D[2]; Q.vox = vox_xmajor; }  // [x][z][y]
-  // (the free clip plane lives in the kernel's set-up: the kept samples of a ray are an interval of planes, see there; as a
-  //  run-time test per sample in the consumers' loop it cost every frame WITHOUT a clip plane 4-5 % at 512^3 -- round 2)
-  // an empty region (a clip plane outside a shard's box): the gather kernel's explicit comparisons
-  // render it as nothing; the median-of-three membership test here needs lo <= hi
-  for (int a = 0; a < 3; ++a)
-    if (!(P.lo[a] <= P.hin[a])) { *why = "region is empty"; return hipErrorNotSupported; }
-  if (Q.Ds > 4096) { *why = "more than 4096 slices"; return hipErrorNotSupported; }
-  // u8 voxels are 8 B: the DMA moves 16-B units, so rows must start and end on even voxels
-  if (dtype == 0 && ((Q.Du & 1) || (Q.strideV & 1) || (Q.strideS & 1))) { *why = "odd U extent for 8-byte voxels"; return hipErrorNotSupported; }
-
-  // workgroup shape: consumer waves are 8x8 pixel sub-tiles; NL loader waves.
-  //   light windows: 32x16 tile, 8+1 waves, two workgroups per CU
-  //   heavy windows (1024^3 f32 at a voxel per pixel): 24x32 tile, 12+4 waves, one per CU; the
-  //   tile is narrow along U so that a window row (tile + drift + pair) fits a 32-unit LDS pitch
-  // (one loader wave moves ~10 B/cycle at best, MI355X_MICROARCH.md 'ldsdma-fill'; a heavy
-  //  stream needs several per CU)
-  struct Cfg { int tw, th, nl; };
-  Cfg cfgs[3] = {{32, 16, 2}, {32, 24, 4}, {32, 24, 4}};
-  int ncfg = 2;
-  if (opt_tile == 1) { cfgs[0] = {16, 16, 1}; ncfg = 1; }
-  else if (opt_tile == 2) { cfgs[0] = {24, 32, 4}; ncfg = 1; }
-  else if (opt_tile == 3) { cfgs[0] = {24, 16, 2}; ncfg = 1; }
-  else if (opt_tile == 4) { cfgs[0] = {32, 24, 4}; ncfg = 1; }
-  else if (opt_tile == 5) { cfgs[0] = {32, 16, 2}; ncfg = 1; }
-  else if (opt_tile == 6) { cfgs[0] = {32, 16, 1}; ncfg = 1; }
-  else if (opt_tile == 7) { cfgs[0] = {16, 32, 2}; ncfg = 1; }
-  else if (opt_tile == 8) { cfgs[0] = {32, 16, 4}; ncfg = 1; }
-  else if (opt_tile == 9) { cfgs[0] = {16, 32, 1}; ncfg = 1; }
-  else if (opt_tile == 10) { cfgs[0] = {24, 32, 2}; ncfg = 1; }
-  else if (opt_tile == 11) { cfgs[0] = {24, 24, 2}; ncfg = 1; }
-  else if (opt_tile == 12) { cfgs[0] = {48, 16, 4}; ncfg = 1; }
-  else if (opt_tile == 13) { cfgs[0] = {16, 48, 4}; ncfg = 1; }
-  else if (opt_tile == 14) { cfgs[0] = {32, 24, 2}; ncfg = 1; }
-  // (round 2: MORE loader waves -- 10+6 on 40x16 / 16x40 px, 8+8 on 32x16 / 16x32 -- on the 1024^3 frame: 5.10 / 7.76 /
-  //  6.30 / 7.21 ms against 4.33 for 12+4 on 32x24: the smaller tiles' extra fringe outweighs the issue slots)
-  else if (opt_tile == 15) { cfgs[0] = {40, 16, 6}; ncfg = 1; }
-  else if (opt_tile == 16) { cfgs[0] = {16, 40, 6}; ncfg = 1; }
-  else if (opt_tile == 17) { cfgs[0] = {32, 16, 8}; ncfg = 1; }
-  else if (opt_tile == 18) { cfgs[0] = {16, 32, 8}; ncfg = 1; }
-  else if (opt_tile == 19) { cfgs[0] = {48, 16, 4}; ncfg = 1; }
-  else if (opt_tile == 22) { cfgs[0] = {16, 48, 2}; ncfg = 1; }
-  else if (opt_tile == 23) { cfgs[0] = {48, 16, 2}; ncfg = 1; }
-  else if (opt_tile == 20) { cfgs[0] = {40, 16, 2}; ncfg = 1; }
-  else if (opt_tile == 21) { cfgs[0] = {16, 40, 2}; ncfg = 1; }
-  const int upv = dtype == 0 ? 2 : 1;
-  // Small-workgroup shape: 10 + 2 waves on 16x40 or 40x16 pixels, or 8 + 2 on 32x16 -- whichever needs the fewest DMA
-  // instructions per ray for THIS view (the window's width is rounded up to whole 128-byte units of LDS pitch, so the
-  // answer depends on the pose: cfg 3's gives 7 / 640, 8 / 640 and 6 / 512 rays, and 1.45 / 1.57 / 1.55 ms).  Two
-  // twelve-wave workgroups fill a CU's 24 wave slots at this kernel's 75-80 VGPRs; two ten-wave ones leave four idle.
-  // A probing pass sizes the candidates' windows (each scan is kept, see below), the real pass plans the winner.
-  static const bool dbg_time = getenv("SMK_DEBUG_TIME") != nullptr;  // (developer: where the host's planning time goes)
-  static double dbg_t[4] = {0, 0, 0, 0};
-  static int dbg_n = 0;
-  auto dbg_now = []() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
-  const double dbg_t0 = dbg_time ? dbg_now() : 0;
-  double dbg_scan = 0;
-  struct DbgExit {
-    bool on; double t0; double *acc; decltype(dbg_now) *now;
-    ~DbgExit() { if (on) *acc += (*now)() - t0; }
-  } dbg_exit{dbg_time, dbg_t0, &dbg_t[2], &dbg_now};
-  // (a tie is won by the shape with the longer window rows, see the probe: same DMA count, rows twice as long; A/B on the cfg 3 frame turned
-  //  25 / 30 / 33 / 36 / 40 degrees, five alternations each: 0.611 / 0.577 / 0.614 / 0.636 / 0.625 ms against the narrow
-  //  shape's 0.606 / 0.614 / 0.627 / 0.654 / 0.641, tools/shape_ab.py)
-  Cfg cand[3] = {{40, 16, 2}, {16, 40, 2}, {32, 16, 2}};
-  const bool choose = opt_tile == 0 && SLAB_BIG_WAVES >= 12;
-  int best = -1, best_wu = 0;
-  double best_score = 1e300;
-  // The choice is kept while the view keeps its principal axis, direction and sizes (re-examined every 64 frames): a
-  // camera that moves every frame must not pay the probe -- nor flip between two shapes of nearly equal score, which
-  // would throw away the measured schedule weights of the tiling each time.  The probe itself scans every fourth tile
-  // row and column plus the borders (its answer only ranks the shapes; the real pass sizes the winner's window fully).
-  struct ShapeKey { int as, dir, W, H, dtype, N[3]; float lo[3], hi[3]; } skey;
-  memset(&skey, 0, sizeof skey);
-  skey.as = as; skey.dir = Q.dir; skey.W = P.W; skey.H = P.H; skey.dtype = dtype;
-  for (int a = 0; a < 3; ++a) { skey.N[a] = P.N[a]; skey.lo[a] = P.lo[a]; skey.hi[a] = P.hi[a]; }
-  const bool shape_known = choose && aux->shape_key.size() == sizeof skey && !memcmp(aux->shape_key.data(), &skey, sizeof skey) &&
-                           aux->shape_choice >= 0 && ++aux->shape_age < 64;
-  if (shape_known) best = aux->shape_choice;
-  for (int pass = (choose && !shape_known) ? 0 : 1; pass < 2; ++pass) {
-  int alt = -1;  // the other twelve-wave shape: tried before the big workgroup where the chosen one turns out not to fit
-  if (pass == 1 && best >= 0) {
-    cfgs[0] = cand[best];
-    // (the probe sizes windows from a sparse scan and can rank a shape by a window it will not get: near a pitch step the
-    //  real window of the narrow tile is half as big again, its ring no longer fits half a CU -- a turning camera then
-    //  rendered 60 frames in a row on the big workgroup, 0.72 ms, where the other small shape takes 0.63)
-    alt = best == 0 ? 1 : 0;
-    cfgs[1] = cand[alt];
-    cfgs[2] = {32, 24, 4};
-    ncfg = 3;
-    if (!shape_known) {
-      aux->shape_key.assign(reinterpret_cast<const unsigned char *>(&skey), reinterpret_cast<const unsigned char *>(&skey) + sizeof skey);
-      aux->shape_choice = best;
-      aux->shape_age = 0;
-    }
-  }
-  const Cfg *list = pass == 0 ? cand : cfgs;
-  const int nlist = pass == 0 ? 3 : ncfg;
-  for (int ci = 0; ci < nlist; ++ci) {
-    const int tw = list[ci].tw, th = list[ci].th, nl = list[ci].nl;
-    const int nw = (tw / 8) * (th / 8);
-    Q.tw = tw; Q.th = th;
-    P.ntx = (P.W + tw - 1) / tw;
-    P.nty = (P.H + th - 1) / th;
-    P.tiles_per_xcd = (P.ntx * P.nty + 7) / 8;
-
-    // every ray must advance along S in the same direction and not too obliquely; window bound:
-    // bundle cross-section extent (corner rays of every tile) at the two S faces + drift over the
-    // two-slice interval a window covers + texel pair + eps
-    double max_eu = 0, max_ev = 0, max_drift_u = 0, max_drift_v = 0;
-    std::vector<int> work((size_t)P.ntx * P.nty, 1);  // slices each tile streams (schedule weight)
-    // The scan of all tiles below is a function of camera, region and tile shape alone; a frame of an unchanged
-    // view reuses the last one (per tile ~0.3 us of double arithmetic: 0.65 ms for the 2048 tiles of a 1024^2
-    // viewport -- hidden behind a 1.9 ms kernel, but not behind the 0.3 ms one of an eighth of the volume)
-    struct ScanKey {
-      smk_raycoef rc;
-      int W, H, tw, th, as, au, av, dir, N[3], top[3];
-      float lo[3], hi[3], hin[3];
-      float sh[18];  // frames with shadows: the eye rays' coefficients (SmkShadowRays), else zeros
-    } key;
-    memset(&key, 0, sizeof key);
-    key.rc = P.rc;
-    if (P.sh.on) {
-      const SmkShadowRays &h = P.sh;
-      const float v[18] = {1.0f, h.Ec[0], h.Ec[1], h.Ec[2], h.Dc[0], h.Dc[1], h.Dc[2], h.Dx[0], h.Dx[1], h.Dx[2], h.Dy[0], h.Dy[1], h.Dy[2],
-                           h.nDc, h.nDx, h.nDy, h.numA, h.dB};
-      memcpy(key.sh, v, sizeof v);
-    }
-    key.W = P.W; key.H = P.H; key.tw = tw; key.th = th; key.as = as; key.au = Q.au; key.av = Q.av; key.dir = Q.dir;
-    for (int a = 0; a < 3; ++a) { key.N[a] = P.N[a]; key.top[a] = P.top[a]; key.lo[a] = P.lo[a]; key.hi[a] = P.hi[a]; key.hin[a] = P.hin[a]; }
-    int slot = -1;
-    for (int k = 0; k < 4; ++k)
-      if (aux->scan[k].key.size() == sizeof key && !memcmp(aux->scan[k].key.data(), &key, sizeof key) && aux->scan[k].work.size() == work.size()) slot = k;
-    const bool scan_hit = slot >= 0;
-    if (!scan_hit) slot = aux->scan_next++ & 3;
-    SlabAux::Scan &scan = aux->scan[slot];
-    const double dbg_s0 = dbg_time ? dbg_now() : 0;
-    if (scan_hit) {
-      max_eu = scan.v[0]; max_ev = scan.v[1]; max_drift_u = scan.v[2]; max_drift_v = scan.v[3];
-      work = scan.work;
-    } else
-    {
-      // The rows of tiles are scanned by a few host threads (a pool the context keeps): ~0.13 us of double arithmetic per
-      // tile is 0.27 ms for the 2048 tiles of a 1024^2 viewport on one thread -- as much as a shard's whole kernel when the
-      // camera moves every frame.  Each thread keeps its own maxima and its own refusal; rows write disjoint tiles.
-      struct Part { double eu = 0, ev = 0, du = 0, dv = 0; const char *why = nullptr; };
-      auto scan_rows = [&](int ty0, int ty1, Part &pt) {
-        for (int tyi = ty0; tyi < ty1; ++tyi)
-          for (int txi = 0; txi < P.ntx; ++txi) {
-            if (pass == 0 && !(((txi & 3) == 0 || txi == P.ntx - 1) && ((tyi & 3) == 0 || tyi == P.nty - 1))) continue;  // (sparse probe)
-            double cA[4][3], cB[4][3];
-            for (int c = 0; c < 4; ++c) {
-              int cx = std::min(txi * tw + ((c & 1) ? tw - 1 : 0), P.W - 1);
-              int cy = std::min(tyi * th + ((c & 2) ? th - 1 : 0), P.H - 1);
-              double *A = cA[c], *B = cB[c];
-              host_ray(P, cx, cy, A, B);
-              if (!(B[as] * Q.dir > 0) || fabs(B[as]) < 1e-12) { pt.why = "rays do not share a marching direction"; return; }
-              double du = fabs(B[Q.au] / B[as]), dv = fabs(B[Q.av] / B[as]);
-              // (3 voxels of drift per slice: close-ups with a wide frustum reach ~2.5 at the frame's edge and still
-              //  run 2-3x faster here than on the gather kernel; the window bound below grows with the drift)
-              if (du > 3.0 || dv > 3.0) { pt.why = "view too oblique for the principal axis"; return; }
-              pt.du = std::max(pt.du, du);
-              pt.dv = std::max(pt.dv, dv);
-            }
-            // the slices this tile can stream: S-extent of its ray bundle inside the region (exact for
-            // the continuous bundle, see slab_bundle_slice_range)
-            double smin_t, smax_t;
-            if (!slab_bundle_slice_range(P, (double)(txi * tw), (double)(tyi * th), (double)std::min(txi * tw + tw, P.W),
-                                         (double)std::min(tyi * th + th, P.H), as, &smin_t, &smax_t))
-              continue;  // the bundle misses the region: nothing to stream
-            work[(size_t)tyi * P.ntx + txi] = 16 + (int)(smax_t - smin_t);
-            // cross-section of the bundle where THIS tile streams: it is linear in s (perspective), so
-            // the two ends of the tile's own slice range bound it.  A sample at s reads slices floor(s)
-            // and floor(s)+1, and the window of slice j covers s in [j-1, j+1] (stretched by half a
-            // slice at the volume faces): 2.5 slices beyond the range.  (Bounding by the volume's S
-            // faces instead costs 25-30 % window area at a voxel per pixel: rays are not inside the
-            // volume where they are widest apart.)
-            const double pad = 2.5 + 1e-2;
-            const double se[2] = {std::max(-0.5, smin_t - pad), std::min((double)P.N[as] - 0.5, smax_t + pad)};
-            for (int f = 0; f < 2; ++f) {
-              double umin = 1e300, umax = -1e300, vmin = 1e300, vmax = -1e300;
-              for (int c = 0; c < 4; ++c) {
-                double mm = (se[f] - cA[c][as]) / cB[c][as];
-                double u = cA[c][Q.au] + cB[c][Q.au] * mm, v = cA[c][Q.av] + cB[c][Q.av] * mm;
-                umin = std::min(umin, u); umax = std::max(umax, u);
-                vmin = std::min(vmin, v); vmax = std::max(vmax, v);
-              }
-              pt.eu = std::max(pt.eu, umax - umin);
-              pt.ev = std::max(pt.ev, vmax - vmin);
-            }
-          }
-      };
-      const int nthreads = (pass == 1 && P.nty >= 16 && P.ntx * P.nty >= 512) ? smk_host_pool_size() : 1;
-      std::vector<Part> parts((size_t)std::max(nthreads, 1));
-      if (nthreads <= 1) {
-        scan_rows(0, P.nty, parts[0]);
-      } else {
-        smk_host_pool_run(nthreads, [&](int k) { scan_rows((int)((long long)P.nty * k / nthreads), (int)((long long)P.nty * (k + 1) / nthreads), parts[(size_t)k]); });
-      }
-      for (const Part &pt : parts) {
-        if (pt.why) { *why = pt.why; return hipErrorNotSupported; }
-        max_eu = std::max(max_eu, pt.eu); max_ev = std::max(max_ev, pt.ev);
-        max_drift_u = std::max(max_drift_u, pt.du); max_drift_v = std::max(max_drift_v, pt.dv);
-      }
-    }
-    if (dbg_time) dbg_scan += dbg_now() - dbg_s0;
-    if (!scan_hit && pass == 1) {  // (a scan that bailed out above returned, a probe is sparse: only complete ones are kept)
-      scan.key.assign(reinterpret_cast<const unsigned char *>(&key), reinterpret_cast<const unsigned char *>(&key) + sizeof key);
-      scan.v[0] = max_eu; scan.v[1] = max_ev; scan.v[2] = max_drift_u; scan.v[3] = max_drift_v;
-      scan.work = work;
-    }
-    // a window spans s in [j-1, j+1] (2 slices of drift; 2.5 at a face; 3 where slice 1 of a
-    // three-slice volume touches both); a coordinate range of extent e touches at most ceil(e) + 2
-    // texels (pair included); eps for the fp32 chains
-    const double span = P.N[as] <= 3 ? 3.0 : 2.5;
-    int Wu = (int)ceil(max_eu + span * max_drift_u + 2 * SLAB_EPS) + 2;
-    int Wv = (int)ceil(max_ev + span * max_drift_v + 2 * SLAB_EPS) + 2;
-    if (dtype == 0) Wu = ((Wu + 1) & ~1) + 2;  // even width, even alignment of the origin
-    Wu = std::min(Wu, Q.Du);
-    Wv = std::min(Wv, Q.Dv);
-    if (Wu < 2 || Wv < 2) { *why = "degenerate window"; return hipErrorNotSupported; }
-    // fixed window shape: wu 16-byte units per row on an LDS pitch of the next multiple of 8 units
-    // (128 B); the slot image is flat, so the (row, column) a DMA lane serves repeats every
-    // per = wp / gcd(64, wp) chunks = rpg = 64 / gcd(64, wp) rows ("group")
-    Q.wu = Wu / upv;
-    Q.wv = Wv;
-    if (Q.wu > 64) { if (ci + 1 < nlist || pass == 0) continue; *why = "window wider than one DMA chunk"; return hipErrorNotSupported; }
-    if (Q.Du > 2047 || Q.Dv > 2047) { *why = "stored box wider than 2047 voxels across the view"; return hipErrorNotSupported; }
-    // The pitch: the next multiple of 8 units -- or, where that gives fewer DMA instructions per slice, the next multiple
-    // of 4 whose period is one the loaders know (per = 1, 3, 5, 7: pitches 12, 20, 28): a 17-unit row on a pitch of 20
-    // (two groups of 16 rows x 5 chunks) instead of 24 (four groups of 8 rows x 3 chunks) is 10 instructions for 12, and a
-    // ring that fits half a CU again.
-    {
-      auto shape = [&](int wp, int &per, int &rpg, int &groups) {
-        int g = 64, r = wp;
-        while (r) { int t = g % r; g = r; r = t; }  // gcd(64, wp)
-        per = wp / g;
-        rpg = 64 / g;
-        groups = (Q.wv + rpg - 1) / rpg;
-      };
-      int wp8 = (Q.wu + 7) & ~7, per8, rpg8, gr8;
-      shape(wp8, per8, rpg8, gr8);
-      Q.wp = wp8; Q.per = per8; Q.rpg = rpg8;
-      const int wp4 = (Q.wu + 3) & ~3;
-      static const bool only8 = getenv("SMK_PITCH8") != nullptr;  // (developer: the pitches of rounds 1-3, multiples of 8)
-      if (wp4 != wp8 && !only8) {
-        int per4, rpg4, gr4;
-        shape(wp4, per4, rpg4, gr4);
-        if (per4 <= 7 && gr4 * per4 < gr8 * per8) { Q.wp = wp4; Q.per = per4; Q.rpg = rpg4; }
-      }
-    }
-    Q.groups = (Q.wv + Q.rpg - 1) / Q.rpg;
-    // small workgroups: a window of whole row groups (its LDS image is that big anyway), see the loader's group loop
-    if ((nw + nl) <= SLAB_BIG_WAVES && Q.groups * Q.rpg <= Q.Dv) Q.wv = Q.groups * Q.rpg;
-    Q.chunks = Q.groups * Q.per;
-    // (a kept shape is probed again the moment its own window changes size -- a narrow tile's window row crosses a pitch
-    //  step of 8 units within a degree or two of a turning camera, its DMA count jumps by half, its ring no longer fits
-    //  half a CU and the frames fall to the big workgroup: 0.72 ms where the other small shape takes 0.63 -- not only
-    //  every 64 frames)
-    if (pass == 1 && choose && best >= 0 && ci == 0) {
-      if (shape_known && aux->shape_chunks != Q.chunks) aux->shape_age = 64;
-      if (!shape_known) aux->shape_chunks = Q.chunks;
-    }
-    if (pass == 0) {  // probing: DMA instructions per ray
-      // (the ten-wave shape leaves four of a CU's wave slots idle: with the brick flags on it measures 0.83 ms on the cfg 3
-      //  frame where the twelve-wave shapes take 0.59-0.61, although it needs the fewest DMA instructions per ray at some
-      //  poses -- a camera turning through such a pose got 0.79 ms frames for 0.63.  It has to win by 40 % now.)
-      const double score = (double)Q.chunks / (nw * 64) * (nw + nl < 12 ? 1.4 : 1.0);
-      // (a tie goes to the shape with the LONGER window rows -- the same DMA count in fewer, longer runs of memory: on the
-      //  cfg 3 frame the wide shape, whose rows lie along the image's x there; a view turned a quarter about its axis has
-      //  them along y)
-      if (score < best_score || (score == best_score && Q.wu > best_wu)) { best_score = score; best = ci; best_wu = Q.wu; }
-      continue;
-    }
-    Q.slot_bytes = Q.chunks * 1024;
-    // per-slice extents (and with them the table-occupancy bitmap) from four chunks per slice up:
-    // re-measured with two slices in flight, 512^3 f32 1.66 -> 1.58 ms, 512^3 u8 1.72 -> 1.68,
-    // 256^3 at 1024^2 1.72 -> 1.55 (the first threshold, 12 chunks, dated from five slices in flight)
-    Q.mask_need = Q.chunks >= 4 ? 1 : 0;
-    // loaders of one slice (see the kernel: NLG groups of LPG loaders)
-    const int nlg = !SLAB_ALT ? 1 : ((nw + nl) > SLAB_BIG_WAVES ? ((nl % SLAB_BIG_NLG) == 0 ? SLAB_BIG_NLG : 1) : nl);
-    const int lpg = nl / nlg;
-    if ((Q.groups + lpg - 1) / lpg * Q.per > 63) { if (ci + 1 < nlist) continue; *why = "window needs more than 63 DMA chunks per loader"; return hipErrorNotSupported; }
-    // light enough for this configuration?  otherwise try the next (heavier-duty) one
-    if (ci + 1 < nlist && (double)Q.chunks * 1024.0 / (nw * 64) > 16.0 * nl) {
-      if (pass == 1 && alt >= 0 && ci == 0) ci = 1;  // (a stream this heavy is too heavy for the other small shape as well: the big one next)
-      continue;
-    }
-
-    Q.use_ah = (tf_mode == 1 && P.third_axis && P.nelts <= 3 && P.sv >= 2 && P.sv <= 2048) ? 1 : 0;
-    if (tf_mode == 1 && (P.sv < 2 || P.sg < 2)) { *why = "transfer function smaller than 2x2"; return hipErrorNotSupported; }
-    const size_t occ_bytes = tf_mode == 1 ? (size_t)P.occ_roww * P.sg * 4 : tf_mode == 2 ? (size_t)P.occ_roww * P.s3g * 4 : 0;
-    Q.fast_tf = (tf_mode == 1 && (!P.third_axis || Q.use_ah)) ? 1 : 0;
-    // (measured: 5.99 -> 5.61 ms on 1024^3, where the texel gathers share the texture path with a
-    //  heavy stream; no gain at 512^3, where the 8 KB are worth more as ring slots)
-    Q.use_occ = ((Q.fast_tf || tf_mode == 2) && Q.mask_need && P.tf_occ && occ_bytes > 0 && occ_bytes <= 8192) ? 1 : 0;
-    {  // brick flags (EMPTY LAYERS in the kernel): model-axis strides -> the kernel's (U, V, S)
-      Q.bricks = (tf_mode == 1 || tf_mode == 2) ? P.bricks : nullptr;
-      const int bst[3] = {1, P.nbr[0], P.nbr[0] * P.nbr[1]};
-      Q.bsu = bst[Q.au];
-      Q.bsv = bst[Q.av];
-      Q.bss = bst[Q.as];
-    }
-    const size_t fixed = (size_t)Q.Ds * sizeof(SlabEnt) + (8 + 32) * 4 + 64 + (Q.use_ah ? (size_t)P.sv * 4 : 0) + (Q.use_occ ? occ_bytes : 0);
-    // ring: as many slots as fit two workgroups per CU (small tiles) or one (big tiles)
-    size_t budget = (nw + nl) > SLAB_BIG_WAVES ? 158 * 1024 : 78 * 1024;
-    if (budget <= fixed) { *why = "slice table does not fit LDS"; return hipErrorNotSupported; }
-    int ns = (int)((budget - fixed) / (size_t)Q.slot_bytes);
-    if (ns > 24) ns = 24;
-    // a wave holds ceil(slices per plane) + 1 slices while it works and the loaders want a few in flight
-    const int band = (int)ceil(fabs(Bc[as])) + 2;
-    if (ns < band + 2 && 158 * 1024 > fixed) {
-      // the ring of a small workgroup does not fit half a CU: one workgroup per CU it is -- then
-      // rather the big tile with 16 waves than this one with 10
-      if (ci + 1 < nlist && budget < 158 * 1024) continue;
-      ns = (int)((158 * 1024 - fixed) / (size_t)Q.slot_bytes);
-      if (ns > band + 4) ns = band + 4;
-    }
-    if (opt_ns >= 3 && ns > opt_ns) ns = opt_ns;  // (experiment knob: cap the ring)
-    if (ns < 3) { if (ci + 1 < nlist) continue; *why = "window does not fit LDS"; return hipErrorNotSupported; }
-    Q.nslots = ns;
-    if (pass == 1 && choose && alt >= 0 && ci == 1) {  // the alternative shape it is: kept from the next frame on
-      aux->shape_choice = alt;
-      aux->shape_chunks = Q.chunks;
-      aux->shape_age = 0;
-    }
-    // (the set-up keeps a 16-byte brick mask per layer of bricks in the ring's memory before the stream starts)
-    if (Q.bricks && (size_t)ns * Q.slot_bytes < ((size_t)((Q.Ds - 1) >> SMK_BRICK_LOG2) + 1) * 16) Q.bricks = nullptr;
-    const int mych = (Q.groups + lpg - 1) / lpg * Q.per;  // most DMA instructions one loader issues per slice
-    // Slices a loader keeps in flight.  TWO: a loader publishes a slice as landed only when it stops
-    // issuing and waits for the oldest one, so a deep issue window delays every consumer that polls
-    // for that slice -- and two slices per loader already cover the memory latency (4 loaders x 2 x
-    // ~7 KiB per CU).  Measured (frames per setting 5/4/3/2/1 on a 5-slot ring): 1024^3 f32 4.27 /
-    // 4.19 / 4.03 / 3.84 / 4.36 ms; 512^3 f32 (12 slots) 1.81 at 12, 1.66 at 2-4, 1.80 at 1; 1024^3 u8
-    // 3.54 -> 2.94 ms.
-    // (small workgroups since their loaders take whole slices in turn: ONE slice in flight per loader -- the other
-    //  loader's is in flight beside it; 1 / 2: cfg 3 1.42-1.44 / 1.45-1.46 ms, other poses and a 256^3 frame -0.3 to -3 %)
-    Q.maxfly = std::max(1, std::min(std::min(ns, 63 / mych + 1), opt_fly > 0 ? opt_fly : (nlg > 1 && (nw + nl) <= SLAB_BIG_WAVES ? 1 : 2)));
-    // a deep ring lets the whole band step together (every lane active); on a short one a wave that
-    // waits for its whole band leaves the loaders nothing to overlap with (measured, 1024^3: 5 slots,
-    // wstep 0 / 1 / 2 -> 5.5 / 5.8 / 6.8 ms)
-    // (re-measured with two slices in flight per loader, 5 slots: wstep 0 / 1 / 2 -> 3.80 / 3.68 / 4.68 ms)
-    Q.wstep = std::max(0, std::min((int)ceil(fabs(Bc[as])), ns - 4));
-    if (opt_T > 0) Q.wstep = std::max(0, std::min(opt_T - 1, ns - 3));  // (experiment knob: slab_T = wstep + 1)
-    // (small workgroups, 10 slots against a band of 4: every other turn 1.87 ms, every turn 1.90, every 4th / 8th 2.0 / 2.2)
-    Q.pmask = ns >= 2 * band ? 1 : 0;
-    const size_t lds = (size_t)ns * Q.slot_bytes + fixed;
-    if (getenv("SMK_DEBUG"))
-      fprintf(stderr, "[smk] slice-ring plan: tile %dx%d, %d+%d waves, window %d units x %d rows (pitch %d units), %d chunks/slice, %d slots of %d B, table+ctl %zu B, LDS %zu B, band %d, wstep %d, pmask %d, maxfly %d\n",
-              tw, th, nw, nl, Q.wu, Q.wv, Q.wp, Q.chunks, ns, Q.slot_bytes, fixed, lds, band, Q.wstep, Q.pmask, Q.maxfly);
-    // ---- schedule.  Blocks are dealt round-robin over the 8 XCDs (block b runs on XCD b % 8, in
-    // order of b), each XCD with its own L2.  Every XCD gets one contiguous run of image tiles
-    // (row-major: neighbours that walk neighbouring voxels share an L2) cut so that all runs
-    // stream about the same number of slices -- tiles at the image border cross less of the
-    // volume than central ones -- and starts its long tiles first (shortest tail).
-    int nblocks = 0;
-    long long ticks_sig_now = 0;
-    int ticks_n_now = 0;
-    {
-      const int nt = P.ntx * P.nty;
-      // measured weights: the previous frame's per-tile workgroup durations, when they are of this
-      // very tiling and marching direction.  (The geometric estimate above -- slices streamed --
-      // misses what consumers cost: on 1024^3 the XCDs holding the image's top and bottom rows ran
-      // 1.6x longer per slice than the central ones and the frame waited for them.)
-      const long long tsig = (((long long)P.ntx * 4096 + P.nty) * 64 + tw) * 64 + th + ((long long)(Q.perm * 2 + (Q.dir > 0)) << 48) +
-                             ((long long)nw << 52) + ((long long)dtype << 56);
-      ++aux->ticks_age;
-      if (aux->ticks_pending && hipEventQuery(aux->ticks_ev) == hipSuccess) {  // a copy has come back
-        // (adopted at once for a new tiling, refined after 4, 8 and 16 frames -- a new order changes
-        //  who runs beside whom and with it the durations -- then every 32 frames: durations of a
-        //  steady view barely move, and every new table is an upload and a host touch of the stream)
-        const bool fresh = aux->ticks_good_sig != aux->ticks_pending_sig;
-        const int due = aux->ticks_adopted < 3 ? (4 << aux->ticks_adopted) : 32;
-        if (fresh || aux->ticks_age >= due) {
-          if (fresh || (int)aux->ticks_good.size() != aux->ticks_pending_n) {
-            aux->ticks_good.assign(aux->h_ticks, aux->h_ticks + aux->ticks_pending_n);
-            aux->ticks_adopted = 0;
-          } else {
-            // damped: half the old weight, half the new measurement.  (Workgroups of a few tens of microseconds -- an
-            // opaque table -- measure mostly who ran beside them: averaged, the schedule oscillated between two plans,
-            // 0.11 and 0.20 ms for the same frame; there the SHORTEST duration seen is the tile's own cost.)
-            unsigned longest_new = 0;
-            for (int t = 0; t < aux->ticks_pending_n; ++t) longest_new = std::max(longest_new, aux->h_ticks[t]);
-            for (int t = 0; t < aux->ticks_pending_n; ++t)
-              aux->ticks_good[t] = longest_new < 10000u ? (aux->h_ticks[t] ? std::min(std::max(aux->ticks_good[t], 1u), aux->h_ticks[t]) : aux->ticks_good[t])
-                                                        : (aux->ticks_good[t] + aux->h_ticks[t] + 1) / 2;
-            ++aux->ticks_adopted;
-          }
-          aux->ticks_good_sig = aux->ticks_pending_sig;
-          aux->ticks_age = 0;
-          // the pieces' own durations, and the cuts they were measured under (DEPTH SEGMENTS: the next cuts come from them)
-          if (aux->h_pticks && (int)aux->cuts_pending.size() == aux->ticks_pending_n * 10) {
-            aux->pticks_good.assign(aux->h_pticks, aux->h_pticks + (size_t)aux->ticks_pending_n * 8);
-            aux->cuts_good = aux->cuts_pending;
-          }
-          aux->recut = true;
-        }
-        aux->ticks_pending = false;
-      }
-      (void)hipGetLastError();
-      if (aux->ticks_good_sig == tsig && (int)aux->ticks_good.size() == nt) {
-        for (int t = 0; t < nt; ++t)
-          if (aux->ticks_good[t] > 0) work[t] = (int)std::min<unsigned>(aux->ticks_good[t], 1u << 30);
-      }
-      if (nt > aux->ticks_cap) {
-        if (aux->ticks_pending) (void)hipEventSynchronize(aux->ticks_ev);
-        aux->ticks_pending = false;
-        if (aux->d_ticks) (void)hipFree(aux->d_ticks);
-        if (aux->h_ticks) (void)hipHostFree(aux->h_ticks);
-        aux->d_ticks = nullptr;
-        aux->h_ticks = nullptr;
-        aux->ticks_cap = 0;
-        if (aux->d_pticks) (void)hipFree(aux->d_pticks);
-        if (aux->h_pticks) (void)hipHostFree(aux->h_pticks);
-        aux->d_pticks = nullptr;
-        aux->h_pticks = nullptr;
-        hipError_t e = hipMalloc((void **)&aux->d_ticks, (size_t)nt * 20);
-        if (e != hipSuccess) return e;
-        e = hipMemset(aux->d_ticks, 0, (size_t)nt * 20);
-        if (e != hipSuccess) return e;
-        e = hipHostMalloc((void **)&aux->h_ticks, (size_t)nt * 4, hipHostMallocDefault);
-        if (e != hipSuccess) return e;
-        e = hipMalloc((void **)&aux->d_pticks, (size_t)nt * 32);
-        if (e != hipSuccess) return e;
-        e = hipMemset(aux->d_pticks, 0, (size_t)nt * 32);
-        if (e != hipSuccess) return e;
-        e = hipHostMalloc((void **)&aux->h_pticks, (size_t)nt * 32, hipHostMallocDefault);
-        if (e != hipSuccess) return e;
-        aux->ticks_cap = nt;
-      }
-      if (!aux->ticks_ev) {
-        hipError_t e = hipEventCreateWithFlags(&aux->ticks_ev, hipEventDisableTiming);
-        if (e != hipSuccess) return e;
-      }
-      Q.tile_ticks = aux->d_ticks;
-      Q.piece_ticks = aux->d_pticks;
-      Q.ntiles = nt;
-      aux->ticks_n_last = nt;
-      ticks_sig_now = tsig;
-      ticks_n_now = nt;
-      const int slots = (nw + nl) | (opt_sched << 8) | (opt_split << 12);  // (part of the cached plan.s key)
-      std::vector<int2> order;
-      // DEPTH SEGMENTS: how many workgroups render each tile.  From MEASURED durations only (the geometric estimate says
-      // nothing about what a tile's samples cost): a tile longer than half the mean load of a workgroup slot is cut so that
-      // no piece is; tiles under 60 us are never cut (a segment costs its own set-up, ~13 us).  Small scenes therefore run
-      // unsplit, bit-identical to the gather kernel; option "slab_split" 1 turns it off, 2.. forces that many everywhere.
-      // cuts[t] = {pieces K, cut_0 = 0, ..., cut_K = 255}: the tile's slice positions in 255ths
-      const bool measured = aux->ticks_good_sig == tsig && (int)aux->ticks_good.size() == nt;
-      if ((int)aux->cuts.size() != nt * 10 || aux->cuts_split != opt_split || aux->cuts_sig != tsig) {
-        aux->cuts.assign((size_t)nt * 10, 0);
-        for (int t = 0; t < nt; ++t) { aux->cuts[(size_t)t * 10] = 1; aux->cuts[(size_t)t * 10 + 2] = 255; }
-        aux->cuts_split = opt_split;
-        aux->cuts_sig = tsig;
-        aux->recut = true;
-      }
-      if (aux->recut) {
-        aux->recut = false;
-        auto equal_cuts = [&](int t, int K) {
-          unsigned char *c = &aux->cuts[(size_t)t * 10];
-          c[0] = (unsigned char)K;
-          for (int k = 0; k <= K; ++k) c[1 + k] = (unsigned char)(255 * k / K);
-        };
-        if (opt_split >= 2) {
-          for (int t = 0; t < nt; ++t) equal_cuts(t, std::min(opt_split, 8));
-        } else if (opt_split == 0 && measured) {
-          long long total = 0;
-          for (int t = 0; t < nt; ++t) total += work[t];
-          const double wg_slots = 256.0 * ((nw + nl) > SLAB_BIG_WAVES ? 1 : 2);
-          // a piece should take about half the mean load of a workgroup slot, never under 60 us (a piece costs its own
-          // set-up, ~13 us); frames whose slots carry under 50 us each -- small scenes -- are not cut at all
-          // ... and only frames whose longest tile stands well above the mean load of a slot: where the slots' summed load is
-          // the bound (cfg 3 on one GPU: longest tile 0.52 ms, mean load 0.49 ms, frame 0.61 ms with every tile cut in two --
-          // 0.62 uncut) pieces only add their set-up; on a shard of 1/8 of that volume (longest 0.24, mean 0.08) they are the gain
-          const double mean_load = (double)total / wg_slots;
-          double longest_tile = 0;
-          for (int t = 0; t < nt; ++t) longest_tile = std::max(longest_tile, (double)work[t]);
-          const double piece = std::max(0.75 * mean_load, 6000.0);  // 100 MHz ticks
-          bool big_frame = mean_load >= 5000.0 && longest_tile > 1.5 * mean_load;
-          if (aux->cuts_engaged && mean_load >= 5000.0 && longest_tile > 1.2 * mean_load) big_frame = true;  // (hysteresis)
-          aux->cuts_engaged = big_frame;
-          const bool have_pieces = (int)aux->pticks_good.size() == nt * 8 && (int)aux->cuts_good.size() == nt * 10;
-          for (int t = 0; t < nt; ++t) {
-            unsigned char *c = &aux->cuts[(size_t)t * 10];
-            int Kw = (big_frame && (double)work[t] > 1.25 * piece) ? (int)std::min(8.0, ceil((double)work[t] / piece)) : 1;
-            if (big_frame && c[0] >= 2 && Kw >= 1 && abs(Kw - (int)c[0]) <= 1 && (double)work[t] > piece) Kw = c[0];  // (a tile keeps its count while the wish is a neighbour of it)
-            if (Kw == 1) { equal_cuts(t, 1); continue; }
-            // the pieces this tile was last measured in: work per 255th of depth, piecewise constant
-            const unsigned char *g = have_pieces ? &aux->cuts_good[(size_t)t * 10] : nullptr;
-            const int Kg = g ? g[0] : 1;
-            if (!g || Kg < 2) {
-              if (c[0] != Kw) equal_cuts(t, Kw);
-              continue;
-            }
-            double d[8], tot = 0, longest = 0;
-            for (int k = 0; k < Kg; ++k) {
-              d[k] = std::max(1.0, (double)aux->pticks_good[(size_t)t * 8 + k] - 1300.0);  // (less the piece's own set-up)
-              tot += d[k];
-              longest = std::max(longest, d[k]);
-            }
-            const bool same = !memcmp(g, c, 10);
-            if (same && Kg == Kw && longest <= 1.3 * tot / Kg) continue;  // balanced enough: keep (no flip-flopping)
-            // new cuts: equal shares of the measured cumulative work
-            unsigned char nc[10] = {(unsigned char)Kw, 0};
-            int k = 0;
-            double acc = 0;  // work before piece k
-            for (int j = 1; j < Kw; ++j) {
-              const double want = tot * j / Kw;
-              while (k < Kg - 1 && acc + d[k] < want) acc += d[k++];
-              const double f = d[k] > 0 ? (want - acc) / d[k] : 0.5;
-              int x = (int)lround(g[1 + k] + f * (g[2 + k] - g[1 + k]));
-              x = std::max(x, (int)nc[j] + 1);
-              x = std::min(x, 255 - (Kw - j));
-              nc[1 + j] = (unsigned char)x;
-            }
-            nc[1 + Kw] = 255;
-            memcpy(c, nc, 10);
-          }
-        } else {
-          for (int t = 0; t < nt; ++t) equal_cuts(t, 1);
-        }
-      }
-      std::vector<unsigned char> ksplit((size_t)nt, 1);
-      for (int t = 0; t < nt; ++t) ksplit[t] = aux->cuts[(size_t)t * 10];
-      // a piece's weight: its own measured duration when it was measured under these very cuts, else an equal share
-      auto piece_weight = [&](int t, int k) -> int {
-        const unsigned char *c = &aux->cuts[(size_t)t * 10];
-        if ((int)aux->pticks_good.size() == nt * 8 && (int)aux->cuts_good.size() == nt * 10 && !memcmp(&aux->cuts_good[(size_t)t * 10], c, 10) &&
-            aux->pticks_good[(size_t)t * 8 + k] > 0)
-          return (int)std::min<unsigned>(aux->pticks_good[(size_t)t * 8 + k], 1u << 30);
-        return work[t] / std::max<int>(c[0], 1);
-      };
-      if (aux->plan_slots == slots && aux->plan_work == work && aux->plan_cuts == aux->cuts && !aux->plan_order.empty()) {
-        order = aux->plan_order;  // same weights, same schedule (planning stays off the per-frame path)
-      } else {
-        long long total = 0;
-        for (int t = 0; t < nt; ++t) total += work[t];
-        // The sequence the runs are cut from: tile rows interleaved top half / bottom half (row 0, row
-        // h, row 1, row h+1, ...), so that every XCD holds TWO bands of neighbouring rows, one nearer
-        // the image border and one nearer its centre.  An XCD runs 32 (or 64) workgroups at a time,
-        // longest first; one band of the image centre is ~130 equally long workgroups -- four full
-        // rounds and three stragglers in a fifth -- while a mixed run ends on short workgroups that
-        // fill the last round.  Bands per XCD 1 / 2 / 3 / 4 / 6: 1024^3 f32 3.65 / 3.51 / 3.58 / 3.60 /
-        // 3.56 ms, 1024^3 u8 3.01 / 2.90 / - / 2.96; 512^3 within noise (1.52-1.60).  More bands mix
-        // better but share less of their windows' overlap in the XCD's L2.
-        std::vector<int> seq;
-        seq.reserve((size_t)nt);
-        {
-          const int F = 2, h = (P.nty + F - 1) / F;
-          for (int r = 0; r < h; ++r)
-            for (int f = 0; f < F; ++f)
-              if (r + f * h < P.nty)
-                for (int c = 0; c < P.ntx; ++c) seq.push_back((r + f * h) * P.ntx + c);
-        }
-        // runs = consecutive tiles of that sequence [cut[x], cut[x+1]): equal accumulated weight
-        int cut[9];
-        {
-          long long acc = 0;
-          int x = 0;
-          cut[0] = 0;
-          for (int t = 0; t < nt; ++t) {
-            const int want = (int)std::min<long long>(7, (acc + work[seq[t]] / 2) * 8 / std::max<long long>(total, 1));
-            while (x < want) cut[++x] = t;
-            acc += work[seq[t]];
-          }
-          while (x < 8) cut[++x] = nt;
-        }
-        // (Measured and dropped: refining the cuts against a simulated list schedule of each XCD -- an
-        //  XCD runs 32 or 64 workgroups at a time, longest first, so with 4-7 workgroups per slot its
-        //  finishing time comes in steps and equal weight can leave three stragglers after the last
-        //  full round.  A local search over the cuts won 2 % on 1024^3 and cost tens of milliseconds
-        //  of host time whenever new weights arrived.)
-        std::vector<std::vector<int>> run(8);
-        size_t longest = 0;
-        const bool dealt = opt_sched == 0;
-        if (dealt) {
-          // DEALT (round 3; the runs above stay as option slab_sched 5): tiles in order of falling weight, each to the XCD
-          // that carries the least so far -- every XCD gets the same mix of long and short workgroups.  The dispatcher hands
-          // blocks out in index order, block b to XCD b % 8, and a block whose XCD has no free slot holds back every block
-          // behind it: the XCDs' lists advance in step, entry k of all eight together.  With a contiguous run of the image
-          // per XCD the lists differ (166-240 tiles, the centre's runs hold more long tiles than an XCD has slots: two of
-          // them must share a slot) and slots stood idle for a mean 10 us per turnover while work was pending elsewhere
-          // (tools/timeline.py).  Dealt: cfg 3 0.609 -> 0.587 ms, the 1024^3 frame 1.176 -> 1.109; with every slice streamed
-          // (equal tiles) no change.
-          // What is dealt is a BLOCK of neighbouring tiles, not a single tile: neighbours
-          // weigh about the same, so they also sit next to each other in their XCD's list and stream the same slices at
-          // about the same time -- the window fringes they share are then fetched once per block and hit in that XCD's L2.
-          // Single tiles scatter every tile's neighbours over the other seven XCDs: HBM-side traffic of the cfg 3 frame
-          // 1.18 -> 1.46 GB (2 x 2 blocks: 1.31), of the north star with every slice streamed 22.4 -> 24.0 GB (4 x 4: 22.2).
-          // Block size: 2 x 2 tiles where the tiles' weights differ (brick flags on: bigger blocks deal the work coarser --
-          // measured 4 x 4: cfg 3 0.595 -> 0.604 ms, the 1024^3 frame 1.110 -> 1.136), 4 x 4 where they are nearly equal
-          // (every slice streamed: 4.035 -> 4.01 ms and the traffic of the contiguous runs, 22.2 GB).
-          std::vector<int> ws;
-          ws.reserve((size_t)nt);
-          for (int t = 0; t < nt; ++t)
-            if (work[t] > 0) ws.push_back(work[t]);
-          std::sort(ws.begin(), ws.end());
-          // "nearly equal": the heavier half of the tiles within 1.25 x of one another (95th percentile against the median;
-          // the tiles along the volume's silhouette are short whatever the table)
-          const bool even = ws.size() >= 16 && (long long)ws[ws.size() * 95 / 100] * 4 <= (long long)ws[ws.size() / 2] * 5;
-          const int SLAB_DEAL_W = even ? 4 : 2, SLAB_DEAL_H = even ? 4 : 2;
-          const int gbx = (P.ntx + SLAB_DEAL_W - 1) / SLAB_DEAL_W, gby = (P.nty + SLAB_DEAL_H - 1) / SLAB_DEAL_H;
-          std::vector<long long> gw((size_t)gbx * gby, 0);
-          for (int t = 0; t < nt; ++t) gw[(size_t)((t / P.ntx) / SLAB_DEAL_H) * gbx + (t % P.ntx) / SLAB_DEAL_W] += work[t];
-          std::vector<int> idx((size_t)gbx * gby);
-          for (int g = 0; g < gbx * gby; ++g) idx[g] = g;
-          std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return gw[a] > gw[b]; });
-          long long load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-          for (int g : idx) {
-            int x = 0;
-            for (int k = 1; k < 8; ++k)
-              if (load[k] < load[x]) x = k;
-            const int gy = g / gbx, gx = g - gy * gbx;
-            for (int dy = 0; dy < SLAB_DEAL_H; ++dy)
-              for (int dx = 0; dx < SLAB_DEAL_W; ++dx) {
-                const int ty = gy * SLAB_DEAL_H + dy, tx = gx * SLAB_DEAL_W + dx;
-                if (ty < P.nty && tx < P.ntx) run[x].push_back(ty * P.ntx + tx);
-              }
-            load[x] += gw[g];
-          }
-        }
-        for (int x = 0; x < 8; ++x) {
-          if (!dealt)
-            for (int t = cut[x]; t < cut[x + 1]; ++t) run[x].push_back(seq[t]);
-          if (opt_sched == 0 || opt_sched == 5) {
-            // (a split tile's pieces weigh a share each: they sort behind the unsplit tiles of their tile's full weight)
-            std::stable_sort(run[x].begin(), run[x].end(), [&](int a, int b) { return work[a] / ksplit[a] > work[b] / ksplit[b]; });
-          } else {
-            // spatially coherent dispatch: tiles that share window fringes should stream the same slices at
-            // the same time on this XCD, so that the fringe is fetched from HBM once and hit in L2 after
-            // that.  Weights only in coarse classes (longest class first), inside a class the tiles of a
-            // band column by column: 32 consecutive workgroups = a compact block of neighbours.
-            int wmax = 1;
-            for (int t : run[x]) wmax = std::max(wmax, work[t]);
-            const int classes = opt_sched == 1 ? 6 : (opt_sched == 3 ? 3 : (opt_sched == 4 ? 12 : 1));
-            const int hrows = (P.nty + 1) / 2;
-            auto key = [&](int t) -> long long {
-              const int ty = t / P.ntx, tx = t - ty * P.ntx;
-              const int cls = classes > 1 ? std::min(classes - 1, (int)((long long)work[t] * classes / ((long long)wmax + 1))) : 0;
-              const int band = ty >= hrows ? 1 : 0;
-              return (((long long)(classes - 1 - cls) * 2 + band) * 4096 + tx) * 4096 + ty;
-            };
-            std::stable_sort(run[x].begin(), run[x].end(), [&](int a, int b) { return key(a) < key(b); });
-          }
-          longest = std::max(longest, run[x].size());
-        }
-        // a run's tiles become its workgroups {tile | piece << 20 | pieces << 26, cuts}, longest first by their own weights
-        longest = 0;
-        std::vector<std::vector<std::pair<int, int2>>> items(8);
-        for (int x = 0; x < 8; ++x) {
-          for (int t : run[x]) {
-            const unsigned char *c = &aux->cuts[(size_t)t * 10];
-            for (int k = 0; k < c[0]; ++k)
-              items[x].push_back({piece_weight(t, k), make_int2(t | (k << 20) | ((int)c[0] << 26), (int)c[1 + k] | ((int)c[2 + k] << 8))});
-          }
-          if (opt_sched == 0 || opt_sched == 5) std::stable_sort(items[x].begin(), items[x].end(), [](const std::pair<int, int2> &a, const std::pair<int, int2> &b) { return a.first > b.first; });
-          longest = std::max(longest, items[x].size());
-        }
-        order.assign(longest * 8, make_int2(-1, 0));
-        for (int x = 0; x < 8; ++x)
-          for (size_t k = 0; k < items[x].size(); ++k) order[k * 8 + x] = items[x][k].second;
-        // ... followed by the list of split tiles for the merge pass (tile | pieces << 20), and their number last
-        int nsplit = 0;
-        for (int t = 0; t < nt; ++t)
-          if (ksplit[t] > 1) { order.push_back(make_int2(t | ((int)ksplit[t] << 20), 0)); ++nsplit; }
-        order.push_back(make_int2(nsplit, 0));
-        aux->plan_work = work;
-        aux->plan_cuts = aux->cuts;
-        aux->plan_order = order;
-        aux->plan_slots = slots;
-      }
-      const int nsplit = order.back().x;
-      nblocks = (int)order.size() - 1 - nsplit;
-      aux->ksplit_last.assign((size_t)nt, 1);
-      for (int k = 0; k < nsplit; ++k) {
-        const int code = order[order.size() - 1 - nsplit + k].x;
-        aux->ksplit_last[code & 0xfffff] = (unsigned char)(code >> 20);
-      }
-      int maxseg = 1;
-      for (int k = 0; k < nsplit; ++k) maxseg = std::max(maxseg, order[(size_t)nblocks + k].x >> 20);
-      aux->nsplit_last = nsplit;
-      aux->nblocks_last = nblocks;
-      if (maxseg > 1) {
-        // (room for the largest piece count at once: growing the buffer when a tile's count rises is a hipFree + hipMalloc,
-        //  ~1 ms in the middle of a session -- 7 partial frames of a 1024^2 viewport are 112 MB of 288 GB)
-        const size_t need = (size_t)(8 - 1) * P.W * P.H * 16;
-        if (need > aux->seg_cap) {
-          if (aux->d_seg) (void)hipFree(aux->d_seg);
-          aux->d_seg = nullptr;
-          aux->seg_cap = 0;
-          hipError_t e = hipMalloc(&aux->d_seg, need);
-          if (e != hipSuccess) return e;
-          aux->seg_cap = need;
-        }
-      }
-      Q.seg_out = (float4 *)aux->d_seg;
-      if (dbg_time) {
-        dbg_t[0] += dbg_scan;
-        dbg_t[1] += dbg_now() - dbg_t0;
-        if (++dbg_n % 60 == 0) {
-          fprintf(stderr, "[smk] planning per frame: scans %.3f ms, all of it up to the launch %.3f ms, whole launcher (previous 60) %.3f ms\n", dbg_t[0] / 60, dbg_t[1] / 60, dbg_t[2] / 60);
-          dbg_t[0] = dbg_t[1] = dbg_t[2] = 0;
-        }
-      }
-      if (aux->frame_ev0) {  // the frame's kernel-time bracket opens here: planning is done
-        hipError_t e = hipEventRecord(aux->frame_ev0, s);
-        if (e != hipSuccess) return e;
-      }
-      auto same_order = [&]() { return aux->order_host.size() == order.size() && (order.empty() || !memcmp(aux->order_host.data(), order.data(), order.size() * sizeof(int2))); };
-      if (!same_order()) {  // unchanged camera: the table on the device is still right
-        if ((int)order.size() > aux->order_cap) {
-          if (aux->d_order) (void)hipFree(aux->d_order);
-          aux->d_order = nullptr;
-          for (int k = 0; k < 4; ++k) {
-            if (aux->order_ev[k]) (void)hipEventSynchronize(aux->order_ev[k]);
-            if (aux->h_order[k]) (void)hipHostFree(aux->h_order[k]);
-            aux->h_order[k] = nullptr;
-          }
-          aux->order_cap = 0;
-          // (with headroom: the table grows by a few entries whenever a tile's piece count rises, and every regrowth is a
-          //  device free + allocation and four pinned ones -- a 1 ms hiccup every few dozen frames on a shard)
-          const size_t cap = order.size() * 2 + 1024;
-          hipError_t e = hipMalloc((void **)&aux->d_order, cap * sizeof(int2));
-          if (e != hipSuccess) return e;
-          for (int k = 0; k < 4; ++k) {
-            e = hipHostMalloc((void **)&aux->h_order[k], cap * sizeof(int2), hipHostMallocDefault);
-            if (e != hipSuccess) return e;
-          }
-          aux->order_cap = (int)cap;
-        }
-        // pinned staging + a copy ON THE LAUNCH STREAM: a copy from pageable memory is not
-        // stream-ordered against the kernel that follows (seen as wrong tiles when several
-        // contexts render at once).  Four staging buffers in turn, each rewritten only after its
-        // own last copy: the host does not wait for the stream unless it is four tables ahead.
-        const int k = aux->order_next;
-        aux->order_next = (k + 1) & 3;
-        if (!aux->order_ev[k]) {
-          hipError_t e = hipEventCreateWithFlags(&aux->order_ev[k], hipEventDisableTiming);
-          if (e != hipSuccess) return e;
-        } else {
-          hipError_t e = hipEventSynchronize(aux->order_ev[k]);
-          if (e != hipSuccess) return e;
-        }
-        memcpy(aux->h_order[k], order.data(), order.size() * sizeof(int2));
-        hipError_t e = hipMemcpyAsync(aux->d_order, aux->h_order[k], order.size() * sizeof(int2), hipMemcpyHostToDevice, s);
-        if (e != hipSuccess) return e;
-        e = hipEventRecord(aux->order_ev[k], s);
-        if (e != hipSuccess) return e;
-        aux->order_host.swap(order);
-      }
-      Q.order = aux->d_order;
-      Q.trace = nullptr;
-      if (P.lockstep & 32) {
-        if (nblocks > aux->trace_cap) {
-          if (aux->d_trace) (void)hipFree(aux->d_trace);
-          aux->d_trace = nullptr;
-          aux->trace_cap = 0;
-          hipError_t e = hipMalloc((void **)&aux->d_trace, (size_t)nblocks * 32);
-          if (e != hipSuccess) return e;
-          aux->trace_cap = nblocks;
-        }
-        hipError_t e = hipMemsetAsync(aux->d_trace, 0, (size_t)nblocks * 32, s);
-        if (e != hipSuccess) return e;
-        aux->trace_n = nblocks;
-        Q.trace = aux->d_trace;
-      }
-    }
-    // developer diagnostics (option lockstep bits 2..64) live in separate instances of the f32 +
-    // R8k kernels only: compiled into the product kernels they cost SGPRs (spills) in every frame
-    const bool diag = (P.lockstep & ~1) != 0 && dtype == 1 && shade_kind == 1;
-    const int nsplit_now = aux->nsplit_last, nblocks_now = aux->nblocks_last;
-    if (nsplit_now > 0) {  // (their tick words are sums over the pieces)
-      hipError_t e = hipMemsetAsync(aux->d_ticks, 0, (size_t)ticks_n_now * 20, s);
-      if (e != hipSuccess) return e;
-    }
-    const int mtw = tw, mth = th;
-    // (the merge pass's first launch costs the host a few milliseconds of code loading, which lands between the frame's
-    //  events: paid here, in a context's first slice-ring frame -- not in the frame auto mode happens to be timing when
-    //  the first tiles are cut.  One block whose entry names tile 0 with ONE piece: it rewrites that tile's pixels with
-    //  themselves, before this frame's kernel writes them.)
-    if (!aux->merge_warm && nblocks_now >= 1) {
-      aux->merge_warm = true;
-      static const int2 one = make_int2(0 | (1 << 20), 0);
-      int2 *d_one = nullptr;
-      if (hipMalloc((void **)&d_one, sizeof one) == hipSuccess) {
-        if (hipMemcpyAsync(d_one, &one, sizeof one, hipMemcpyHostToDevice, s) == hipSuccess)
-          hipLaunchKernelGGL(smk_k_slab_merge, dim3(1), dim3(256), 0, s, (const int2 *)d_one, mtw, mth, P.ntx, P.W, P.H, (const float4 *)P.out, P.out, 0);
-        (void)hipStreamSynchronize(s);
-        (void)hipFree(d_one);
-      }
-      (void)hipGetLastError();
-    }
-    auto after_launch = [&](hipError_t e) -> hipError_t {
-      if (e == hipSuccess && nsplit_now > 0) {
-        hipLaunchKernelGGL(smk_k_slab_merge, dim3(nsplit_now), dim3(256), 0, s, (const int2 *)aux->d_order + nblocks_now, mtw, mth, P.ntx, P.W, P.H,
-                           (const float4 *)aux->d_seg, P.out, P.blend == SMK_BLEND_MAX ? 1 : 0);
-        e = hipGetLastError();
-      }
-      if (e != hipSuccess || aux->ticks_pending) return e;
-      // fetch this frame's per-tile durations (one copy in flight at a time)
-      hipError_t e2 = hipMemcpyAsync(aux->h_ticks, aux->d_ticks, (size_t)ticks_n_now * 4, hipMemcpyDeviceToHost, s);
-      if (e2 == hipSuccess && nsplit_now > 0) e2 = hipMemcpyAsync(aux->h_pticks, aux->d_pticks, (size_t)ticks_n_now * 32, hipMemcpyDeviceToHost, s);
-      if (nsplit_now > 0) aux->cuts_pending = aux->cuts; else aux->cuts_pending.clear();
-      if (e2 == hipSuccess) e2 = hipEventRecord(aux->ticks_ev, s);
-      if (e2 != hipSuccess) return e2;
-      aux->ticks_pending = true;
-      aux->ticks_pending_sig = ticks_sig_now;
-      aux->ticks_pending_n = ticks_n_now;
-      return hipSuccess;
-    };
-    return after_launch(P.sh.on     ? smk_slab_dispatch_shadow(P, Q, dtype, tf_mode, shade_kind, nw, nl, lds, nblocks, why, s)
-                        : dtype == 0 ? smk_slab_dispatch_u8(P, Q, tf_mode, shade_kind, nw, nl, diag, lds, nblocks, why, s)
-                                     : smk_slab_dispatch_f32(P, Q, tf_mode, shade_kind, nw, nl, diag, lds, nblocks, why, s));
-  }
-  }  // pass
-  (void)forced;
-  *why = "no configuration fits";
-  return hipErrorNotSupported;
-}
-#endif  // SLAB_PART == 0
