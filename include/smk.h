@@ -77,6 +77,35 @@ int smk_upload_volume(smk_ctx *ctx, const smk_volume_desc *bricks, int n_bricks,
 int smk_upload_volume_device(smk_ctx *ctx, const smk_volume_desc *bricks, int n_bricks, int nelts,
                              smk_dtype dtype, smk_datamode dmode);
 
+/* ---- time-varying data sets: a ring of time steps resident in device memory (DESIGN.md "Time steps").  The reference
+ * keeps `tstepCache` steps of a series in host memory (MetaVolume::swapTStep / cacheTStep, MetaVolume.cpp:894-958) and
+ * rebuilds its textures when gluvv.volren.timestep moves (R8kVolRen3D.cpp:184-188, keys +/- gluvv.cpp:970-1010).  A step is
+ * what smk_upload_volume makes of a volume (packed voxels, normals, brick summaries; on a shard its region + halo); a switch
+ * copies no voxel.  Time-step ids are >= 0.  smk_upload_volume[_device] drops every cached step and stores its volume as the
+ * current step (id 0 on a new context, else the current id); a context that never calls these renders exactly as before. */
+/* replaces MetaVolume::tstepCache: how many steps stay resident (default 1: the current one).  Shrinking frees the steps that
+ * were written longest ago (never the current one); a capacity whose new steps do not fit in free device memory is refused,
+ * with the bytes per step (an x-major copy, made for views along x, adds as much again as the voxels). */
+int smk_set_timestep_cache(smk_ctx *ctx, int nsteps);
+/* replaces MetaVolume::readAll + cacheTStep (MetaVolume.cpp:894-958): stores one step without changing the current one
+ * (on a context without a volume the first step stored becomes current).  A step cached under that id is overwritten in
+ * place; otherwise the step takes an empty slot, else the slot after the one written last -- never the current step's (with
+ * a capacity of 1 the call is refused).  The bricks as for smk_upload_volume, with the first upload's geometry: sizes,
+ * extents, nelts, dtype, datamode, normals present or not (a mismatch is refused, the field named).  Synchronous. */
+int smk_upload_timestep(smk_ctx *ctx, int timestep, const smk_volume_desc *bricks, int n_bricks, int nelts, smk_dtype dtype,
+                        smk_datamode dmode);
+/* same with DEVICE data/grad pointers, asynchronous on `stream` (a hipStream_t, NULL = the context's stream): the pack and
+ * the brick summaries are enqueued there behind the last frame that read the slot, and the frames that render the step wait
+ * for them on their own streams.  The caller keeps the bricks alive until `stream` has passed the upload. */
+int smk_upload_timestep_device(smk_ctx *ctx, int timestep, const smk_volume_desc *bricks, int n_bricks, int nelts,
+                               smk_dtype dtype, smk_datamode dmode, void *stream);
+/* replaces MetaVolume::swapTStep: the next frame renders that step.  A step that is not cached fails with "not cached"
+ * (swapTStep's return 0): the host uploads it (smk_upload_timestep) and selects it again. */
+int smk_select_timestep(smk_ctx *ctx, int timestep);
+/* introspection: the current step (-1: no volume), the cached ids oldest written first (min(cap, *n) of them; ids_out may
+ * be NULL), their number */
+int smk_get_timesteps(smk_ctx *ctx, int *current, int *ids_out, int cap, int *n);
+
 /* Sort-last sharding (no reference equivalent: the reference draws bricks serially on one GPU,
  * NV20VolRen3D.cpp:190-231).  Must be called BEFORE smk_upload_volume: the context then keeps
  * only its convex sub-box (+1 voxel halo) of the volume.  nranks in {1,2,4,8}: split x, then y,

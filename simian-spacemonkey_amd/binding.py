@@ -28,6 +28,8 @@ ABI_SYMBOLS = [
     "smk_set_region", "smk_render_slice", "smk_render_slice_device", "smk_count_samples",
     "smk_get_light_history", "smk_shadow_exports_device", "smk_shadow_entries_device", "smk_shadow_exchange_local",
     "smk_shard_light_order", "smk_get_shadow_margin",
+    "smk_set_timestep_cache", "smk_upload_timestep", "smk_upload_timestep_device", "smk_select_timestep",
+    "smk_get_timesteps",
 ]
 
 # gluvvDataMode order (gluvv.h:221-235)
@@ -117,6 +119,12 @@ def load_library():
     L.smk_last_error.argtypes = [C.c_void_p]
     for n in ("smk_upload_volume", "smk_upload_volume_device"):
         getattr(L, n).argtypes = [C.c_void_p, P(VolumeDesc), C.c_int, C.c_int, C.c_int, C.c_int]
+    L.smk_set_timestep_cache.argtypes = [C.c_void_p, C.c_int]
+    L.smk_upload_timestep.argtypes = [C.c_void_p, C.c_int, P(VolumeDesc), C.c_int, C.c_int, C.c_int, C.c_int]
+    L.smk_upload_timestep_device.argtypes = [C.c_void_p, C.c_int, P(VolumeDesc), C.c_int, C.c_int, C.c_int, C.c_int,
+                                             C.c_void_p]
+    L.smk_select_timestep.argtypes = [C.c_void_p, C.c_int]
+    L.smk_get_timesteps.argtypes = [C.c_void_p, P(C.c_int), P(C.c_int), C.c_int, P(C.c_int)]
     L.smk_set_shard.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.smk_set_clip.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
     L.smk_set_clip_plane.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double)]
@@ -245,9 +253,9 @@ class Renderer:
             raise SmkError(self.L.smk_last_error(self.ctx).decode())
 
     # -- volume
-    def upload_volume(self, data, grad=None, fsize=None, grid=(1, 1, 1), dmode="VGH"):
-        """data [nz][ny][nx][nelts] u8/f32 (numpy); split into `grid` bricks the way
-        MetaVolume::brick does and handed over brick by brick."""
+    @staticmethod
+    def _host_bricks(data, grad, fsize, grid):
+        """(descs, keep-alive list, nelts, dtype code) of a host volume split into `grid` bricks"""
         data = np.ascontiguousarray(data)
         nz, ny, nx, ne = data.shape
         m = float(max(nx, ny, nz))
@@ -269,10 +277,10 @@ class Renderer:
                 keep.append(g)
                 d.grad = _ptr(g)
         dt = 0 if data.dtype == np.uint8 else 1
-        self._ck(self.L.smk_upload_volume(self.ctx, descs, len(bricks), ne, dt, GDM[dmode]))
+        return descs, keep, ne, dt
 
-    def upload_volume_device(self, dptr, dims, nelts, dtype, grad_dptr=None, fsize=None,
-                             dmode="VGH"):
+    @staticmethod
+    def _device_brick(dptr, dims, grad_dptr, fsize):
         nx, ny, nz = dims
         m = float(max(nx, ny, nz))
         fsize = fsize or (nx / m, ny / m, nz / m)
@@ -281,7 +289,48 @@ class Renderer:
         d.xfSize, d.yfSize, d.zfSize = fsize
         d.data = dptr
         d.grad = grad_dptr
+        return d
+
+    def upload_volume(self, data, grad=None, fsize=None, grid=(1, 1, 1), dmode="VGH"):
+        """data [nz][ny][nx][nelts] u8/f32 (numpy); split into `grid` bricks the way
+        MetaVolume::brick does and handed over brick by brick."""
+        descs, keep, ne, dt = self._host_bricks(data, grad, fsize, grid)
+        self._ck(self.L.smk_upload_volume(self.ctx, descs, len(descs), ne, dt, GDM[dmode]))
+
+    def upload_volume_device(self, dptr, dims, nelts, dtype, grad_dptr=None, fsize=None,
+                             dmode="VGH"):
+        d = self._device_brick(dptr, dims, grad_dptr, fsize)
         self._ck(self.L.smk_upload_volume_device(self.ctx, C.byref(d), 1, nelts, dtype, GDM[dmode]))
+
+    # -- time steps (smk.h: smk_set_timestep_cache ...)
+    def set_timestep_cache(self, nsteps):
+        """how many time steps stay resident in device memory (MetaVolume::tstepCache; default 1)"""
+        self._ck(self.L.smk_set_timestep_cache(self.ctx, int(nsteps)))
+
+    def upload_timestep(self, timestep, data, grad=None, fsize=None, grid=(1, 1, 1), dmode="VGH"):
+        """store one step of a series (as upload_volume) without changing the current step"""
+        descs, keep, ne, dt = self._host_bricks(data, grad, fsize, grid)
+        self._ck(self.L.smk_upload_timestep(self.ctx, int(timestep), descs, len(descs), ne, dt, GDM[dmode]))
+
+    def upload_timestep_device(self, timestep, dptr, dims, nelts, dtype, grad_dptr=None, fsize=None, dmode="VGH",
+                               stream=None):
+        """the same from device memory, enqueued on `stream` (a hipStream_t handle; None = the context's stream): the
+        caller keeps the data alive until the stream has passed the upload"""
+        d = self._device_brick(dptr, dims, grad_dptr, fsize)
+        self._ck(self.L.smk_upload_timestep_device(self.ctx, int(timestep), C.byref(d), 1, nelts, dtype, GDM[dmode],
+                                                   stream))
+
+    def select_timestep(self, timestep):
+        """the next frame renders that step; SmkError "... not cached ..." when it is not resident"""
+        self._ck(self.L.smk_select_timestep(self.ctx, int(timestep)))
+
+    def timesteps(self):
+        """(current step or -1, the cached ids oldest written first)"""
+        cur, n = C.c_int(0), C.c_int(0)
+        self._ck(self.L.smk_get_timesteps(self.ctx, C.byref(cur), None, 0, C.byref(n)))
+        ids = (C.c_int * max(n.value, 1))()
+        self._ck(self.L.smk_get_timesteps(self.ctx, C.byref(cur), ids, n.value, C.byref(n)))
+        return cur.value, list(ids)[:n.value]
 
     def set_shard(self, rank, nranks):
         self._ck(self.L.smk_set_shard(self.ctx, rank, nranks))

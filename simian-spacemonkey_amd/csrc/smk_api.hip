@@ -98,25 +98,6 @@ void smk_host_pool_run(int n, const std::function<void(int)> &f) {
   p->njobs = 0;
 }
 
-#define HIPCHK(ctx, call)                                                              \
-  do {                                                                                 \
-    hipError_t e_ = (call);                                                            \
-    if (e_ != hipSuccess) {                                                            \
-      char b_[512];                                                                    \
-      snprintf(b_, sizeof b_, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-      (ctx)->err = b_;                                                                 \
-      return 1;                                                                        \
-    }                                                                                  \
-  } while (0)
-
-#define FAIL(ctx, ...)                     \
-  do {                                     \
-    char b_[512];                          \
-    snprintf(b_, sizeof b_, __VA_ARGS__);  \
-    (ctx)->err = b_;                       \
-    return 1;                              \
-  } while (0)
-
 // ------------------------------------------------------------------------------- lifecycle
 
 extern "C" smk_ctx *smk_create(int device_ordinal, int *err) {
@@ -161,10 +142,7 @@ static void free_brick_set(BrickSet &B) {
 }
 
 static void free_volume(smk_ctx *c) {
-  if (c->d_vox) (void)hipFree(c->d_vox);
-  if (c->d_nrm) (void)hipFree(c->d_nrm);
-  if (c->d_vox_x) (void)hipFree(c->d_vox_x);
-  if (c->d_brick_mm) (void)hipFree(c->d_brick_mm);
+  smk_free_steps(c);  // (every cached step: the current one's d_vox, d_nrm, d_vox_x, d_brick_mm among them)
   smk_cols_drop_layouts(&c->cols);  // (built from this volume)
   c->d_brick_mm = nullptr;
   c->d_vox_x = nullptr;
@@ -254,37 +232,41 @@ __global__ void smk_k_pack(const void *src, const unsigned char *grad, int bx, i
   }
 }
 
-// the region of shard `rank` of `nranks`
-static void shard_region_of(const smk_ctx *c, int rank, int g0[3], int g1[3]) {
+// the region of shard `rank` of `nranks` of an N[0] x N[1] x N[2] volume
+static void shard_box(const int N[3], int rank, int nranks, int g0[3], int g1[3]) {
   for (int a = 0; a < 3; ++a) {
     g0[a] = 0;
-    g1[a] = c->N[a];
+    g1[a] = N[a];
   }
   int bit = 0;
-  for (int n = c->nranks; n > 1; n >>= 1, ++bit) {
-    int a = bit % 3, half = c->N[a] / 2;  // bit 0 splits x, bit 1 y, bit 2 z
+  for (int n = nranks; n > 1; n >>= 1, ++bit) {
+    int a = bit % 3, half = N[a] / 2;  // bit 0 splits x, bit 1 y, bit 2 z
     if ((rank >> bit) & 1) g0[a] = std::max(g0[a], half);
     else g1[a] = std::min(g1[a], half);
   }
 }
 
+static void shard_region_of(const smk_ctx *c, int rank, int g0[3], int g1[3]) { shard_box(c->N, rank, c->nranks, g0, g1); }
+
 static void shard_region(const smk_ctx *c, int g0[3], int g1[3]) { shard_region_of(c, c->rank, g0, g1); }
 
-static int upload_impl(smk_ctx *c, const smk_volume_desc *b, int nb, int nelts, smk_dtype dtype, smk_datamode dmode,
-                       bool on_device) {
-  if (!c) return 1;
-  HIPCHK(c, hipSetDevice(c->device));
-  if (!b || nb <= 0) FAIL(c, "smk_upload_volume: no bricks");
-  if (nelts < 1 || nelts > 4) FAIL(c, "smk_upload_volume: nelts %d not in 1..4", nelts);
-  if (dtype != SMK_U8 && dtype != SMK_F32) FAIL(c, "smk_upload_volume: bad dtype");
-  // whole-volume dims and extent from the brick list (MetaVolume::brick keeps iPos/fPos)
-  int N[3] = {0, 0, 0};
-  float fs[3] = {0, 0, 0};
+// whole-volume dims and extent from the brick list (MetaVolume::brick keeps iPos/fPos), and the box this context stores
+int smk_volume_geometry(smk_ctx *c, const char *who, const smk_volume_desc *b, int nb, int nelts, smk_dtype dtype,
+                        smk_datamode dmode, SmkVolGeom &g) {
+  if (!b || nb <= 0) FAIL(c, "%s: no bricks", who);
+  if (nelts < 1 || nelts > 4) FAIL(c, "%s: nelts %d not in 1..4", who, nelts);
+  if (dtype != SMK_U8 && dtype != SMK_F32) FAIL(c, "%s: bad dtype", who);
+  g = SmkVolGeom();
+  g.dtype = dtype;
+  g.nelts = nelts;
+  g.dmode = dmode;
+  int *N = g.N;
+  float *fs = g.fs;
   bool any_grad = false, all_grad = true;
   for (int i = 0; i < nb; ++i) {
-    if (!b[i].data) FAIL(c, "smk_upload_volume: brick %d has no data", i);
-    if (b[i].xiSize <= 0 || b[i].yiSize <= 0 || b[i].ziSize <= 0) FAIL(c, "smk_upload_volume: brick %d empty", i);
-    if (b[i].xiPos < 0 || b[i].yiPos < 0 || b[i].ziPos < 0) FAIL(c, "smk_upload_volume: brick %d negative origin", i);
+    if (!b[i].data) FAIL(c, "%s: brick %d has no data", who, i);
+    if (b[i].xiSize <= 0 || b[i].yiSize <= 0 || b[i].ziSize <= 0) FAIL(c, "%s: brick %d empty", who, i);
+    if (b[i].xiPos < 0 || b[i].yiPos < 0 || b[i].ziPos < 0) FAIL(c, "%s: brick %d negative origin", who, i);
     N[0] = std::max(N[0], b[i].xiPos + b[i].xiSize);
     N[1] = std::max(N[1], b[i].yiPos + b[i].yiSize);
     N[2] = std::max(N[2], b[i].ziPos + b[i].ziSize);
@@ -294,66 +276,91 @@ static int upload_impl(smk_ctx *c, const smk_volume_desc *b, int nb, int nelts, 
     any_grad |= b[i].grad != nullptr;
     all_grad &= b[i].grad != nullptr;
   }
-  if (any_grad && !all_grad) FAIL(c, "smk_upload_volume: some bricks have normals and some do not");
+  if (any_grad && !all_grad) FAIL(c, "%s: some bricks have normals and some do not", who);
   size_t vox = 0;
   for (int i = 0; i < nb; ++i) vox += (size_t)b[i].xiSize * b[i].yiSize * b[i].ziSize;
-  if (vox != (size_t)N[0] * N[1] * N[2]) FAIL(c, "smk_upload_volume: bricks do not tile the %dx%dx%d volume", N[0], N[1], N[2]);
-  if (!(fs[0] > 0 && fs[1] > 0 && fs[2] > 0)) FAIL(c, "smk_upload_volume: non-positive extent");
-
-  free_volume(c);
-  c->dtype = dtype;
-  c->nelts = nelts;
-  c->dmode = dmode;
-  for (int a = 0; a < 3; ++a) {
-    c->N[a] = N[a];
-    c->fsize[a] = fs[a];
-  }
+  if (vox != (size_t)N[0] * N[1] * N[2]) FAIL(c, "%s: bricks do not tile the %dx%dx%d volume", who, N[0], N[1], N[2]);
+  if (!(fs[0] > 0 && fs[1] > 0 && fs[2] > 0)) FAIL(c, "%s: non-positive extent", who);
   if (c->nranks > 1)
     for (int a = 0; a < 3; ++a)
-      if (N[a] < 2) FAIL(c, "smk_upload_volume: volume too thin to shard");
-  shard_region(c, c->g0, c->g1);
+      if (N[a] < 2) FAIL(c, "%s: volume too thin to shard", who);
+  g.grad = any_grad;
+  shard_box(N, c->rank, c->nranks, g.g0, g.g1);
   for (int a = 0; a < 3; ++a) {
-    int lo = std::max(c->g0[a] - c->halo, 0), hi = std::min(c->g1[a] + c->halo, N[a]);
-    c->O[a] = lo;
-    c->D[a] = hi - lo;
+    int lo = std::max(g.g0[a] - c->halo, 0), hi = std::min(g.g1[a] + c->halo, N[a]);
+    g.O[a] = lo;
+    g.D[a] = hi - lo;
   }
   // 8-byte voxels travel to LDS in 16-byte units: the slice-ring kernel wants even row lengths
   // along both axes that can be its contiguous one (x, and y in the x-major copy) -- one more halo
   // voxel where the volume has one, else a pad column nobody samples (index N: the texel pair of a
   // clamped coordinate ends at N-1)
-  bool padded = false;
   if (dtype == SMK_U8)
     for (int a = 0; a < 2; ++a)
-      if (c->D[a] & 1) {
-        if (c->O[a] + c->D[a] < N[a]) ++c->D[a];
-        else if (c->O[a] > 0) { --c->O[a]; ++c->D[a]; }
-        else { ++c->D[a]; padded = true; }
+      if (g.D[a] & 1) {
+        if (g.O[a] + g.D[a] < N[a]) ++g.D[a];
+        else if (g.O[a] > 0) { --g.O[a]; ++g.D[a]; }
+        else { ++g.D[a]; g.padded = true; }
       }
-  size_t nst = (size_t)c->D[0] * c->D[1] * c->D[2];
-  size_t vb = dtype == SMK_U8 ? 8 : 16;
-  HIPCHK(c, hipMalloc(&c->d_vox, nst * vb + 16));  // (+16: the gather kernel reads u8 voxels in pairs, smk_load_pair_u8)
-  if (padded) HIPCHK(c, hipMemset(c->d_vox, 0, nst * vb));
-  c->vox_bytes = nst * vb;
-  bool n_in_w = dtype == SMK_F32 && nelts <= 3;
-  if (dtype == SMK_F32 && nelts == 4 && any_grad) HIPCHK(c, hipMalloc((void **)&c->d_nrm, nst * 4));
-  c->have_normals = any_grad;
+  const size_t nst = (size_t)g.D[0] * g.D[1] * g.D[2];
+  g.vox_bytes = nst * (dtype == SMK_U8 ? 8 : 16);
+  g.nrm_bytes = dtype == SMK_F32 && nelts == 4 && any_grad ? nst * 4 : 0;
+  for (int a = 0; a < 3; ++a) g.nbr[a] = (g.D[a] - 1) / (1 << SMK_BRICK_LOG2) + 1;
+  g.mm_bytes = (size_t)g.nbr[0] * g.nbr[1] * g.nbr[2] * sizeof(float4);
+  return 0;
+}
 
-  const size_t esz = dtype == SMK_U8 ? 1 : 4;
+// the context's volume geometry becomes g's (the first upload of a volume or a series)
+void smk_set_geometry(smk_ctx *c, const SmkVolGeom &g) {
+  c->dtype = g.dtype;
+  c->nelts = g.nelts;
+  c->dmode = g.dmode;
+  for (int a = 0; a < 3; ++a) {
+    c->N[a] = g.N[a];
+    c->fsize[a] = g.fs[a];
+    c->g0[a] = g.g0[a];
+    c->g1[a] = g.g1[a];
+    c->O[a] = g.O[a];
+    c->D[a] = g.D[a];
+    c->nbr[a] = g.nbr[a];
+  }
+  c->vox_bytes = g.vox_bytes;
+  c->have_normals = g.grad;
+}
+
+int smk_alloc_step(smk_ctx *c, const SmkVolGeom &g, TimeStep &T) {
+  if (!T.vox) {
+    HIPCHK(c, hipMalloc(&T.vox, g.vox_bytes + 16));  // (+16: the gather kernel reads u8 voxels in pairs, smk_load_pair_u8)
+    if (g.padded) HIPCHK(c, hipMemset(T.vox, 0, g.vox_bytes));
+  }
+  if (g.nrm_bytes && !T.nrm) HIPCHK(c, hipMalloc((void **)&T.nrm, g.nrm_bytes));
+  if (!T.mm) HIPCHK(c, hipMalloc((void **)&T.mm, g.mm_bytes));
+  return 0;
+}
+
+// Packs the bricks into step T's buffers and makes its brick summaries.  s == null: synchronous, host bricks staged in chunks
+// (smk_upload_volume); else everything is enqueued on s, which must then also order the reads of the caller's (device)
+// bricks.  The pad column of a padded box was cleared when the buffer was made, and no brick writes it.
+int smk_pack_step(smk_ctx *c, const char *who, const SmkVolGeom &g, const smk_volume_desc *b, int nb, bool on_device, TimeStep &T,
+                  hipStream_t s) {
+  const int nelts = g.nelts;
+  const size_t esz = g.dtype == SMK_U8 ? 1 : 4;
+  const bool n_in_w = g.dtype == SMK_F32 && nelts <= 3;
   void *d_stage = nullptr;
   unsigned char *d_gstage = nullptr;
   const size_t chunk_budget = (size_t)256 << 20;
   for (int i = 0; i < nb; ++i) {
     const smk_volume_desc &k = b[i];
     // skip bricks that cannot touch this context's stored box
-    if (k.xiPos >= c->O[0] + c->D[0] || k.xiPos + k.xiSize <= c->O[0] || k.yiPos >= c->O[1] + c->D[1] ||
-        k.yiPos + k.yiSize <= c->O[1] || k.ziPos >= c->O[2] + c->D[2] || k.ziPos + k.ziSize <= c->O[2])
+    if (k.xiPos >= g.O[0] + g.D[0] || k.xiPos + k.xiSize <= g.O[0] || k.yiPos >= g.O[1] + g.D[1] ||
+        k.yiPos + k.yiSize <= g.O[1] || k.ziPos >= g.O[2] + g.D[2] || k.ziPos + k.ziSize <= g.O[2])
       continue;
     size_t slice = (size_t)k.xiSize * k.yiSize;
     int zper = on_device ? k.ziSize : (int)std::max<size_t>(1, chunk_budget / (slice * nelts * esz));
     for (int z0 = 0; z0 < k.ziSize; z0 += zper) {
       int cz = std::min(zper, k.ziSize - z0);
       // only the z range that intersects the stored box
-      if (k.ziPos + z0 >= c->O[2] + c->D[2] || k.ziPos + z0 + cz <= c->O[2]) continue;
+      if (k.ziPos + z0 >= g.O[2] + g.D[2] || k.ziPos + z0 + cz <= g.O[2]) continue;
       const void *src;
       const unsigned char *gsrc = nullptr;
       size_t off = (size_t)z0 * slice;
@@ -363,7 +370,7 @@ static int upload_impl(smk_ctx *c, const smk_volume_desc *b, int nb, int nelts, 
       } else {
         if (!d_stage) HIPCHK(c, hipMalloc(&d_stage, std::min(chunk_budget + slice * nelts * esz, (size_t)-1)));
         size_t bytes = (size_t)cz * slice * nelts * esz;
-        if (bytes > chunk_budget + slice * nelts * esz) FAIL(c, "smk_upload_volume: internal staging overflow");
+        if (bytes > chunk_budget + slice * nelts * esz) FAIL(c, "%s: internal staging overflow", who);
         HIPCHK(c, hipMemcpy(d_stage, (const char *)k.data + off * nelts * esz, bytes, hipMemcpyHostToDevice));
         src = d_stage;
         if (k.grad) {
@@ -374,30 +381,45 @@ static int upload_impl(smk_ctx *c, const smk_volume_desc *b, int nb, int nelts, 
       }
       size_t total = (size_t)cz * slice;
       unsigned blocks = (unsigned)((total + 255) / 256);
-      if (dtype == SMK_U8)
-        hipLaunchKernelGGL(smk_k_pack<0>, dim3(blocks), dim3(256), 0, 0, src, gsrc, k.xiSize, k.yiSize, cz, nelts,
-                           k.xiPos, k.yiPos, k.ziPos + z0, c->O[0], c->O[1], c->O[2], c->D[0], c->D[1], c->D[2],
-                           c->d_vox, c->d_nrm, 0);
+      if (g.dtype == SMK_U8)
+        hipLaunchKernelGGL(smk_k_pack<0>, dim3(blocks), dim3(256), 0, s, src, gsrc, k.xiSize, k.yiSize, cz, nelts,
+                           k.xiPos, k.yiPos, k.ziPos + z0, g.O[0], g.O[1], g.O[2], g.D[0], g.D[1], g.D[2],
+                           T.vox, T.nrm, 0);
       else
-        hipLaunchKernelGGL(smk_k_pack<1>, dim3(blocks), dim3(256), 0, 0, src, gsrc, k.xiSize, k.yiSize, cz, nelts,
-                           k.xiPos, k.yiPos, k.ziPos + z0, c->O[0], c->O[1], c->O[2], c->D[0], c->D[1], c->D[2],
-                           c->d_vox, c->d_nrm, n_in_w ? 1 : 0);
+        hipLaunchKernelGGL(smk_k_pack<1>, dim3(blocks), dim3(256), 0, s, src, gsrc, k.xiSize, k.yiSize, cz, nelts,
+                           k.xiPos, k.yiPos, k.ziPos + z0, g.O[0], g.O[1], g.O[2], g.D[0], g.D[1], g.D[2],
+                           T.vox, T.nrm, n_in_w ? 1 : 0);
       HIPCHK(c, hipGetLastError());
-      HIPCHK(c, hipDeviceSynchronize());
+      if (!s) HIPCHK(c, hipDeviceSynchronize());
     }
   }
   if (d_stage) (void)hipFree(d_stage);
   if (d_gstage) (void)hipFree(d_gstage);
   // value ranges of the 8x8x8-cell bricks (smk_bricks.hip): what the brick flags of every later table are made from
-  for (int a = 0; a < 3; ++a) c->nbr[a] = (c->D[a] - 1) / (1 << SMK_BRICK_LOG2) + 1;
-  HIPCHK(c, hipMalloc((void **)&c->d_brick_mm, (size_t)c->nbr[0] * c->nbr[1] * c->nbr[2] * sizeof(float4)));
-  HIPCHK(c, smk_bricks_minmax(c->d_vox, dtype == SMK_U8 ? 0 : 1, c->D, c->nbr, c->d_brick_mm, 0));
-  HIPCHK(c, hipDeviceSynchronize());
-  c->bricks3_dirty = true;
-  c->have_volume = true;
+  HIPCHK(c, smk_bricks_minmax(T.vox, g.dtype == SMK_U8 ? 0 : 1, g.D, g.nbr, T.mm, s));
+  if (!s) HIPCHK(c, hipDeviceSynchronize());
+  T.vox_x_valid = false;
+  return 0;
+}
+
+static int upload_impl(smk_ctx *c, const smk_volume_desc *b, int nb, int nelts, smk_dtype dtype, smk_datamode dmode,
+                       bool on_device) {
+  if (!c) return 1;
+  HIPCHK(c, hipSetDevice(c->device));
+  SmkVolGeom g;
+  if (smk_volume_geometry(c, "smk_upload_volume", b, nb, nelts, dtype, dmode, g)) return 1;
+  // every cached time step goes; the volume is stored as the current step
+  free_volume(c);
+  smk_set_geometry(c, g);
+  c->ts.assign((size_t)c->ts_cap, TimeStep());
+  TimeStep &T = c->ts[0];
+  if (smk_alloc_step(c, g, T)) return 1;
+  T.id = c->ts_cur_id;
+  T.written = ++c->ts_written;
+  if (smk_pack_step(c, "smk_upload_volume", g, b, nb, on_device, T, nullptr)) return 1;
+  smk_use_step(c, 0);
   c->tune_choice.clear();  // a new volume: the kernels' relative speed is measured afresh
   c->tune_sig = 0;
-  c->tf_dirty = true;
   return 0;
 }
 
@@ -947,6 +969,7 @@ static int make_brick_set(smk_ctx *c, BrickSet &B, const uint32_t *occ, int roww
   if (!B.h_count) HIPCHK(c, hipHostMalloc((void **)&B.h_count, 4, hipHostMallocDefault));
   if (!B.counted) HIPCHK(c, hipEventCreateWithFlags(&B.counted, hipEventDisableTiming));
   else HIPCHK(c, hipEventSynchronize(B.counted));  // (the pinned word's previous copy: long done)
+  if (smk_step_wait_ready(c, s)) return 1;  // (the summaries of a step uploaded asynchronously)
   HIPCHK(c, smk_bricks_flags(c->d_brick_mm, c->nbr, occ, roww, sv, sg, B.sat, B.flags, B.d_count, s));
   HIPCHK(c, hipMemcpyAsync(B.h_count, B.d_count, 4, hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipEventRecord(B.counted, s));
@@ -1550,6 +1573,7 @@ static int build_params(smk_ctx *c, RenderParams &P, hipStream_t s) {
   double inv[16];
   compute_raycoef(c, &P.rc, inv);
   if (refresh_tf2d(c, P.rc, s)) return 1;
+  if (smk_step_wait_ready(c, s)) return 1;  // a time step uploaded on another stream: the frame waits for it there
   P.vox = c->d_vox;
   P.nrm = c->d_nrm;
   for (int a = 0; a < 3; ++a) {
@@ -1696,7 +1720,10 @@ __global__ __launch_bounds__(256) void smk_k_xmajor(const V *src, V *dst, int Dx
 
 static int make_xmajor_copy(smk_ctx *c) {
   if (c->d_vox_x) return 0;
-  HIPCHK(c, hipMalloc(&c->d_vox_x, c->vox_bytes));
+  TimeStep &T = c->ts[c->ts_cur];  // (the current step's copy: made once per upload of the step)
+  if (!T.vox_x) HIPCHK(c, hipMalloc(&T.vox_x, c->vox_bytes));
+  c->d_vox_x = T.vox_x;
+  if (smk_step_wait_ready(c, c->stream)) return 1;
   dim3 grid((c->D[0] + 31) / 32, (c->D[1] + 31) / 32, c->D[2]);
   if (c->dtype == SMK_U8)
     hipLaunchKernelGGL(smk_k_xmajor<uint2>, grid, dim3(256), 0, c->stream, (const uint2 *)c->d_vox, (uint2 *)c->d_vox_x,
@@ -1706,6 +1733,7 @@ static int make_xmajor_copy(smk_ctx *c) {
                        (float4 *)c->d_vox_x, c->D[0], c->D[1], c->D[2]);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  T.vox_x_valid = true;
   return 0;
 }
 
@@ -1903,7 +1931,7 @@ extern "C" int smk_shadow_exports_device(smk_ctx *c, void *d_exports, void *stre
   hipError_t e = smk_launch_shadow_exports(P, sc, c->dtype, c->tf_mode, S, s);
   if (e == hipErrorNotSupported) FAIL(c, "smk_shadow_exports_device: no shadow kernel instance for this configuration");
   HIPCHK(c, e);
-  return 0;
+  return smk_step_mark_used(c, s);
 }
 
 extern "C" int smk_shadow_entries_device(smk_ctx *c, const void *d_entries, void *stream) {
@@ -2143,6 +2171,7 @@ extern "C" int smk_render_device(smk_ctx *c, void *d_rgba, void *d_depth, void *
         HIPCHK(c, hipEventRecord(c->tfv[c->tf_cur].used, s));
         c->tfv[c->tf_cur].used_valid = true;
       }
+      if (smk_step_mark_used(c, s)) return 1;
       c->tcount++;
       return 0;
     }
@@ -2276,6 +2305,7 @@ extern "C" int smk_render_device(smk_ctx *c, void *d_rgba, void *d_depth, void *
     HIPCHK(c, hipEventRecord(c->tfv[c->tf_cur].used, s));
     c->tfv[c->tf_cur].used_valid = true;
   }
+  if (smk_step_mark_used(c, s)) return 1;  // (and the time step it rendered)
   c->tcount++;
   return 0;
 }
@@ -2410,10 +2440,11 @@ extern "C" int smk_render_slice_device(smk_ctx *c, const float quad[4][3], float
   Q.alpha = alpha;
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   dim3 grid((c->W + 15) / 16, (c->H + 15) / 16);
+  if (smk_step_wait_ready(c, s)) return 1;
   if (c->dtype == SMK_U8) hipLaunchKernelGGL(smk_k_render_slice<0>, grid, dim3(256), 0, s, P, Q, (float4 *)d_rgba);
   else hipLaunchKernelGGL(smk_k_render_slice<1>, grid, dim3(256), 0, s, P, Q, (float4 *)d_rgba);
   HIPCHK(c, hipGetLastError());
-  return 0;
+  return smk_step_mark_used(c, s);
 }
 
 extern "C" int smk_render_slice(smk_ctx *c, const float quad[4][3], float alpha, float *rgba) {

@@ -17,6 +17,26 @@
 #define SMK_TUNE_SETTLE 6  // auto mode: untimed slice-ring frames before a new configuration's timed trial (smk_api.hip)
 #define SMK_STATUS_RING 8  // frames whose slice-ring status stays readable (smk_frame_failed)
 
+// error handling of the C ABI entries (int returns: 0 ok, 1 error with the message in ctx->err)
+#define HIPCHK(ctx, call)                                                              \
+  do {                                                                                 \
+    hipError_t e_ = (call);                                                            \
+    if (e_ != hipSuccess) {                                                            \
+      char b_[512];                                                                    \
+      snprintf(b_, sizeof b_, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
+      (ctx)->err = b_;                                                                 \
+      return 1;                                                                        \
+    }                                                                                  \
+  } while (0)
+
+#define FAIL(ctx, ...)                     \
+  do {                                     \
+    char b_[512];                          \
+    snprintf(b_, sizeof b_, __VA_ARGS__);  \
+    (ctx)->err = b_;                       \
+    return 1;                              \
+  } while (0)
+
 // Eye rays of a frame with shadows (half-angle slicing, smk_shadow.hip).  The slice planes are not perpendicular to the
 // view axis, so a ray's coefficients are not affine in the pixel coordinate; they are (smk_ray_AB, smk_device.h)
 //   D_a = fma(px, Dx_a, fma(py, Dy_a, Dc_a)),  nD = fma(px, nDx, fma(py, nDy, nDc)),
@@ -147,6 +167,7 @@ struct SlabAux {
   // developer options (0 = the planner decides): "tile" (workgroup shape id), "slab_T" (band wait + 1), "slab_fly"
   // (slices a loader keeps in flight), "slab_ns" (cap on the ring's slots)
   int opt_tile = 0, opt_T = 0, opt_fly = 0, opt_ns = 0;
+  bool ticks_stale = false;     // the copy in flight measured another time step: dropped when it arrives
   int nsplit_last = 0, nblocks_last = 0;
   std::vector<unsigned char> ksplit_last;  // pieces per tile of the latest launch
   unsigned *d_pticks = nullptr, *h_pticks = nullptr;  // [ntiles][8] durations of the pieces of split tiles (device; pinned copy)
@@ -203,6 +224,22 @@ struct BrickSet {
   float fill = -1.f;  // share of the bricks that are flagged; < 0: not known yet
 };
 
+// One cached time step (smk_timesteps.hip; DESIGN.md "Time steps"): what smk_upload_volume makes of a volume.  The buffers
+// of a slot are reused by the step that replaces it (every step has the first upload's geometry).
+struct TimeStep {
+  int id = -1;                      // the host's time-step number; -1: slot empty
+  long long written = 0;            // upload sequence number (the ring hands out the slot after the last one written)
+  void *vox = nullptr;              // packed voxels of the stored box (region + halo)
+  uint32_t *nrm = nullptr;          // separate packed normals (f32 with 4 channels and normals), else null
+  float4 *mm = nullptr;             // brick min/max summaries (smk_bricks.hip)
+  void *vox_x = nullptr;            // x-major copy, made on first use (smk_api.hip make_xmajor_copy)
+  bool vox_x_valid = false;
+  hipEvent_t ready = nullptr;       // end of an asynchronous upload, on the stream it was enqueued on
+  bool ready_pending = false;       // ... recorded and not yet seen complete
+  hipEvent_t used = nullptr;        // the last frame that read the step
+  bool used_valid = false;
+};
+
 struct smk_ctx {
   int device = 0;
   std::string err;
@@ -237,6 +274,12 @@ struct smk_ctx {
   uint32_t *d_nrm = nullptr;
   bool have_normals = false;
   size_t vox_bytes = 0;
+  // time steps: ts[ts_cur] is the step frames render (d_vox, d_nrm, d_brick_mm, d_vox_x point into it).  A context that
+  // never calls the time-step entries holds its volume in ts[0] and records no events (ts_series false)
+  std::vector<TimeStep> ts;
+  int ts_cap = 1, ts_cur = -1, ts_cur_id = 0;
+  long long ts_written = 0;
+  bool ts_series = false;
 
   // sharding
   int rank = 0, nranks = 1;
@@ -378,6 +421,8 @@ void smk_shadow_entries_commit(smk_ctx *c, const smk_shadowcoef &sc);
 // plan + launch (smk_slab_plan.hip); returns hipErrorNotSupported (and *why) when the frame must use the gather kernel
 hipError_t smk_launch_slab(RenderParams P, int dtype, int tf_mode, int shade_kind, const void *vox_native, const void *vox_xmajor, SlabAux *aux,
                            const char **why, hipStream_t s);
+// the measured weights and depth cuts belong to the volume they were measured on: forgotten on a time-step switch
+void smk_slab_forget_measurements(SlabAux *aux);
 // the column-stream kernel (smk_cols.hip); same convention as smk_launch_slab
 hipError_t smk_launch_cols(RenderParams P, int dtype, int tf_mode, int shade_kind, int knobs, const void *vox_native, ColsAux *aux,
                            int *status_word, const char **why, hipStream_t s);
@@ -386,3 +431,27 @@ hipError_t smk_launch_cols(RenderParams P, int dtype, int tf_mode, int shade_kin
 #include <functional>
 int smk_host_pool_size();
 void smk_host_pool_run(int n, const std::function<void(int)> &f);
+
+// the geometry of a volume upload (smk_api.hip): every time step of a series has the first one's
+struct SmkVolGeom {
+  int dtype = 0, nelts = 0, dmode = 0;
+  int N[3] = {0, 0, 0};
+  float fs[3] = {0, 0, 0};
+  int g0[3] = {0, 0, 0}, g1[3] = {0, 0, 0}, O[3] = {0, 0, 0}, D[3] = {0, 0, 0}, nbr[3] = {0, 0, 0};
+  bool grad = false, padded = false;
+  size_t vox_bytes = 0, nrm_bytes = 0, mm_bytes = 0;
+};
+int smk_volume_geometry(smk_ctx *c, const char *who, const smk_volume_desc *b, int nb, int nelts, smk_dtype dtype,
+                        smk_datamode dmode, SmkVolGeom &g);
+void smk_set_geometry(smk_ctx *c, const SmkVolGeom &g);
+int smk_alloc_step(smk_ctx *c, const SmkVolGeom &g, TimeStep &T);
+int smk_pack_step(smk_ctx *c, const char *who, const SmkVolGeom &g, const smk_volume_desc *b, int nb, bool on_device, TimeStep &T,
+                  hipStream_t s);
+// ts[k] becomes the step frames render (its brick flags are made again before the next frame)
+void smk_use_step(smk_ctx *c, int k);
+
+// time steps (smk_timesteps.hip).  The step frames render is current; a frame's stream waits for its upload, and its end is
+// recorded as the step's last reader (an upload that overwrites the slot waits for that)
+int smk_step_wait_ready(smk_ctx *c, hipStream_t s);
+int smk_step_mark_used(smk_ctx *c, hipStream_t s);
+void smk_free_steps(smk_ctx *c);

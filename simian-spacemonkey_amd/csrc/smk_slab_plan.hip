@@ -661,6 +661,9 @@ static const char *slab_choose_shape(RenderParams &P, SlabParams &Q, int dtype, 
 // than the central ones and the frame waited for them.)  Also (re)allocates the buffers the kernel writes them to.
 static hipError_t slab_measured_weights(SlabAux *aux, long long tsig, int nt, std::vector<int> &work, SlabParams &Q) {
   ++aux->ticks_age;
+  if (aux->ticks_pending && aux->ticks_stale && hipEventQuery(aux->ticks_ev) == hipSuccess) {  // (of another time step)
+    aux->ticks_pending = aux->ticks_stale = false;
+  }
   if (aux->ticks_pending && hipEventQuery(aux->ticks_ev) == hipSuccess) {  // a copy has come back
     // (adopted at once for a new tiling, refined after 4, 8 and 16 frames -- a new order changes
     //  who runs beside whom and with it the durations -- then every 32 frames: durations of a
@@ -700,7 +703,7 @@ static hipError_t slab_measured_weights(SlabAux *aux, long long tsig, int nt, st
   }
   if (nt > aux->ticks_cap) {
     if (aux->ticks_pending) (void)hipEventSynchronize(aux->ticks_ev);
-    aux->ticks_pending = false;
+    aux->ticks_pending = aux->ticks_stale = false;
     if (aux->d_ticks) (void)hipFree(aux->d_ticks);
     if (aux->h_ticks) (void)hipHostFree(aux->h_ticks);
     if (aux->d_pticks) (void)hipFree(aux->d_pticks);
@@ -725,6 +728,22 @@ static hipError_t slab_measured_weights(SlabAux *aux, long long tsig, int nt, st
   Q.ntiles = nt;
   aux->ticks_n_last = nt;
   return hipSuccess;
+}
+
+// A time-step switch (smk_timesteps.hip): the durations were measured on another volume, whose empty space is not this
+// one's.  The next frames plan from the geometric estimate again, uncut, exactly as a fresh context's first frame does; the
+// geometry scans and the chosen tile shape (camera and sizes alone) are kept.
+void smk_slab_forget_measurements(SlabAux *aux) {
+  aux->ticks_good.clear();
+  aux->ticks_good_sig = -1;
+  aux->ticks_adopted = 0;
+  aux->ticks_stale = aux->ticks_pending;
+  aux->pticks_good.clear();
+  aux->cuts_good.clear();
+  aux->cuts.clear();
+  aux->cuts_sig = -1;
+  aux->cuts_engaged = false;
+  aux->recut = true;
 }
 
 // ---- depth-segment cuts (aux->cuts)

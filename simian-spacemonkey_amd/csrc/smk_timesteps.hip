@@ -1,0 +1,242 @@
+// smk_timesteps.hip -- the device-resident time-step cache (DESIGN.md "Time steps").
+//
+// The reference keeps a ring of `tstepCache` steps in host memory and swaps a cached one in, or reads it from disk
+// (MetaVolume::swapTStep / cacheTStep, MetaVolume.cpp:894-958); R8kVolRen3D::draw rebuilds its textures when
+// gluvv.volren.timestep moves (R8kVolRen3D.cpp:184-188).  Here the ring lives in HBM: a step is what smk_upload_volume makes
+// of a volume (packed voxels, normals, brick summaries), and a switch points the context at another slot.  No voxel is
+// copied; the brick flags of the table are made again from the new step's summaries before the next frame, the column
+// layout (option "kernel" 3) is rebuilt, and the slice-ring planner forgets the durations it measured on the old step.
+//
+// Ordering (no host synchronisation on the asynchronous path):
+//   - smk_upload_timestep_device enqueues the pack and the brick summaries on the caller's stream and records the slot's
+//     `ready` event there; every stream that reads the step (a frame's, the table refresh's) waits for it;
+//   - every frame records the slot's `used` event on its stream; an upload into the slot waits for it first.
+#include <string.h>
+
+#include <algorithm>
+
+#include "smk_internal.h"
+
+int smk_step_wait_ready(smk_ctx *c, hipStream_t s) {
+  if (c->ts_cur < 0) return 0;
+  TimeStep &T = c->ts[c->ts_cur];
+  if (!T.ready_pending) return 0;
+  if (hipEventQuery(T.ready) == hipSuccess) {
+    T.ready_pending = false;  // (long done: no wait to enqueue from now on)
+    return 0;
+  }
+  (void)hipGetLastError();
+  HIPCHK(c, hipStreamWaitEvent(s, T.ready, 0));
+  return 0;
+}
+
+int smk_step_mark_used(smk_ctx *c, hipStream_t s) {
+  if (!c->ts_series || c->ts_cur < 0) return 0;  // (a context without a series never overwrites its volume in place)
+  TimeStep &T = c->ts[c->ts_cur];
+  if (!T.used) HIPCHK(c, hipEventCreateWithFlags(&T.used, hipEventDisableTiming));
+  HIPCHK(c, hipEventRecord(T.used, s));
+  T.used_valid = true;
+  return 0;
+}
+
+static void free_step(TimeStep &T) {
+  if (T.used_valid) (void)hipEventSynchronize(T.used);
+  if (T.ready_pending) (void)hipEventSynchronize(T.ready);
+  if (T.vox) (void)hipFree(T.vox);
+  if (T.nrm) (void)hipFree(T.nrm);
+  if (T.mm) (void)hipFree(T.mm);
+  if (T.vox_x) (void)hipFree(T.vox_x);
+  if (T.ready) (void)hipEventDestroy(T.ready);
+  if (T.used) (void)hipEventDestroy(T.used);
+  T = TimeStep();
+}
+
+void smk_free_steps(smk_ctx *c) {
+  for (TimeStep &T : c->ts) free_step(T);
+  c->ts.clear();
+  c->ts_cur = -1;
+}
+
+void smk_use_step(smk_ctx *c, int k) {
+  TimeStep &T = c->ts[(size_t)k];
+  c->ts_cur = k;
+  c->ts_cur_id = T.id;
+  c->d_vox = T.vox;
+  c->d_nrm = T.nrm;
+  c->d_brick_mm = T.mm;
+  c->d_vox_x = T.vox_x_valid ? T.vox_x : nullptr;
+  c->bricks3_dirty = true;  // the flags of either table come from this step's summaries
+  c->tf_dirty = true;
+  c->have_volume = true;
+}
+
+// another step (or the current one overwritten): what was derived from the old voxels goes.  The auto mode's measured kernel
+// choice stays: it is a property of the configuration, which every step of a series shares.
+static void switch_step(smk_ctx *c, int k) {
+  smk_use_step(c, k);
+  smk_slab_forget_measurements(&c->slab);
+  bool layouts = false;
+  for (const ColLayout &L : c->cols.lay) layouts |= L.d != nullptr;
+  if (layouts) smk_cols_drop_layouts(&c->cols);  // (rebuilt from the new step by its next frame)
+}
+
+static int find_step(const smk_ctx *c, int id) {
+  for (size_t k = 0; k < c->ts.size(); ++k)
+    if (c->ts[k].id == id) return (int)k;
+  return -1;
+}
+
+static size_t bytes_per_step(const smk_ctx *c) {
+  const size_t nst = (size_t)c->D[0] * c->D[1] * c->D[2];
+  const size_t nrm = c->dtype == SMK_F32 && c->nelts == 4 && c->have_normals ? nst * 4 : 0;
+  return c->vox_bytes + 16 + nrm + (size_t)c->nbr[0] * c->nbr[1] * c->nbr[2] * sizeof(float4);
+}
+
+extern "C" int smk_set_timestep_cache(smk_ctx *c, int nsteps) {
+  if (!c) return 1;
+  if (nsteps < 1) FAIL(c, "smk_set_timestep_cache: capacity %d: the cache holds at least the current step", nsteps);
+  HIPCHK(c, hipSetDevice(c->device));
+  c->ts_series = true;
+  if (!c->have_volume) {
+    c->ts_cap = nsteps;
+    return 0;
+  }
+  int held = 0;
+  for (const TimeStep &T : c->ts) held += T.vox != nullptr;
+  if (nsteps > held) {
+    const size_t per = bytes_per_step(c), need = per * (size_t)(nsteps - held);
+    size_t fr = 0, tot = 0;
+    HIPCHK(c, hipMemGetInfo(&fr, &tot));
+    if (need > fr)
+      FAIL(c, "smk_set_timestep_cache: %d steps do not fit: %zu bytes per step, %zu bytes more needed, %zu free", nsteps, per, need, fr);
+  }
+  // the slots in the order they were written; the current step and the newest others stay, in that order from slot 0
+  std::vector<int> order;
+  for (size_t k = 0; k < c->ts.size(); ++k)
+    if (c->ts[k].id >= 0) order.push_back((int)k);
+  std::sort(order.begin(), order.end(), [&](int a, int b) { return c->ts[(size_t)a].written < c->ts[(size_t)b].written; });
+  std::vector<int> keep;
+  if (c->ts_cur >= 0) keep.push_back(c->ts_cur);
+  for (int i = (int)order.size() - 1; i >= 0 && (int)keep.size() < nsteps; --i)
+    if (order[(size_t)i] != c->ts_cur) keep.push_back(order[(size_t)i]);
+  std::sort(keep.begin(), keep.end(), [&](int a, int b) { return c->ts[(size_t)a].written < c->ts[(size_t)b].written; });
+  std::vector<TimeStep> ring((size_t)nsteps);
+  int cur = -1;
+  for (size_t i = 0; i < keep.size(); ++i) {
+    if (keep[i] == c->ts_cur) cur = (int)i;
+    ring[i] = c->ts[(size_t)keep[i]];
+    c->ts[(size_t)keep[i]] = TimeStep();
+  }
+  for (TimeStep &T : c->ts) free_step(T);  // the evicted steps (after the frames that read them)
+  // (slots that held no step keep no buffers: a later upload makes them)
+  c->ts.swap(ring);
+  c->ts_cap = nsteps;
+  c->ts_cur = cur;
+  return 0;
+}
+
+// the slot a new step takes: an empty one, else the one after the slot written last (cacheTStep's oldTSpos), never the
+// current step's
+static int next_slot(const smk_ctx *c) {
+  for (size_t k = 0; k < c->ts.size(); ++k)
+    if (c->ts[k].id < 0) return (int)k;
+  int last = 0;
+  for (size_t k = 0; k < c->ts.size(); ++k)
+    if (c->ts[k].written > c->ts[(size_t)last].written) last = (int)k;
+  int k = (last + 1) % (int)c->ts.size();
+  if (k == c->ts_cur) k = (k + 1) % (int)c->ts.size();
+  return k;
+}
+
+static int upload_step(smk_ctx *c, const char *who, int id, const smk_volume_desc *b, int nb, int nelts, smk_dtype dtype,
+                       smk_datamode dmode, bool on_device, void *stream) {
+  if (!c) return 1;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (id < 0) FAIL(c, "%s: time step %d: ids are >= 0", who, id);
+  SmkVolGeom g;
+  if (smk_volume_geometry(c, who, b, nb, nelts, dtype, dmode, g)) return 1;
+  c->ts_series = true;
+  if (c->have_volume) {  // every step has the geometry of the first upload
+    if (g.N[0] != c->N[0] || g.N[1] != c->N[1] || g.N[2] != c->N[2])
+      FAIL(c, "%s: time step %d: sizes %dx%dx%d differ from the series' %dx%dx%d", who, id, g.N[0], g.N[1], g.N[2], c->N[0], c->N[1], c->N[2]);
+    if (g.fs[0] != c->fsize[0] || g.fs[1] != c->fsize[1] || g.fs[2] != c->fsize[2])
+      FAIL(c, "%s: time step %d: extents %g x %g x %g differ from the series' %g x %g x %g", who, id, g.fs[0], g.fs[1], g.fs[2],
+           c->fsize[0], c->fsize[1], c->fsize[2]);
+    if (g.nelts != c->nelts) FAIL(c, "%s: time step %d: nelts %d differs from the series' %d", who, id, g.nelts, c->nelts);
+    if (g.dtype != c->dtype) FAIL(c, "%s: time step %d: dtype %d differs from the series' %d", who, id, g.dtype, c->dtype);
+    if (g.dmode != c->dmode) FAIL(c, "%s: time step %d: datamode %d differs from the series' %d", who, id, g.dmode, c->dmode);
+    if (g.grad != c->have_normals)
+      FAIL(c, "%s: time step %d: normals %s, the series' %s", who, id, g.grad ? "present" : "absent", c->have_normals ? "present" : "absent");
+  }
+  int k = c->have_volume ? find_step(c, id) : -1;
+  if (k < 0) {
+    if (!c->have_volume) {  // the first step: it sets the geometry, and is the current one
+      smk_set_geometry(c, g);
+      c->ts.assign((size_t)c->ts_cap, TimeStep());
+      c->ts_cur = -1;
+      c->tune_choice.clear();
+      c->tune_sig = 0;
+    } else if (c->ts.size() == 1)
+      FAIL(c, "%s: time step %d: the cache holds one step, the current one (%d); smk_set_timestep_cache sets more", who, id, c->ts_cur_id);
+    k = next_slot(c);
+  }
+  TimeStep &T = c->ts[(size_t)k];
+  const hipStream_t s = on_device ? (stream ? (hipStream_t)stream : c->stream) : nullptr;
+  // the slot's old contents: the frames that read them, and an upload still writing them, come first
+  if (T.used_valid) {
+    if (s) HIPCHK(c, hipStreamWaitEvent(s, T.used, 0));
+    else HIPCHK(c, hipEventSynchronize(T.used));
+  }
+  if (T.ready_pending) {
+    if (s) HIPCHK(c, hipStreamWaitEvent(s, T.ready, 0));
+    else HIPCHK(c, hipEventSynchronize(T.ready));
+    T.ready_pending = false;
+  }
+  T.id = -1;  // (until it holds the new step)
+  if (smk_alloc_step(c, g, T)) return 1;
+  if (smk_pack_step(c, who, g, b, nb, on_device, T, s)) return 1;
+  T.id = id;
+  T.written = ++c->ts_written;
+  if (s) {
+    if (!T.ready) HIPCHK(c, hipEventCreateWithFlags(&T.ready, hipEventDisableTiming));
+    HIPCHK(c, hipEventRecord(T.ready, s));
+    T.ready_pending = true;
+  }
+  if (c->ts_cur < 0) smk_use_step(c, k);
+  else if (k == c->ts_cur) switch_step(c, k);  // the current step overwritten in place
+  return 0;
+}
+
+extern "C" int smk_upload_timestep(smk_ctx *c, int timestep, const smk_volume_desc *bricks, int n_bricks, int nelts, smk_dtype dtype,
+                                   smk_datamode dmode) {
+  return upload_step(c, "smk_upload_timestep", timestep, bricks, n_bricks, nelts, dtype, dmode, false, nullptr);
+}
+
+extern "C" int smk_upload_timestep_device(smk_ctx *c, int timestep, const smk_volume_desc *bricks, int n_bricks, int nelts,
+                                          smk_dtype dtype, smk_datamode dmode, void *stream) {
+  return upload_step(c, "smk_upload_timestep_device", timestep, bricks, n_bricks, nelts, dtype, dmode, true, stream);
+}
+
+extern "C" int smk_select_timestep(smk_ctx *c, int timestep) {
+  if (!c) return 1;
+  HIPCHK(c, hipSetDevice(c->device));
+  c->ts_series = true;
+  if (!c->have_volume) FAIL(c, "smk_select_timestep: no volume uploaded");
+  const int k = find_step(c, timestep);
+  if (k < 0) FAIL(c, "smk_select_timestep: time step %d is not cached (upload it with smk_upload_timestep)", timestep);
+  if (k != c->ts_cur) switch_step(c, k);
+  return 0;
+}
+
+extern "C" int smk_get_timesteps(smk_ctx *c, int *current, int *ids_out, int cap, int *n) {
+  if (!c) return 1;
+  std::vector<const TimeStep *> held;
+  for (const TimeStep &T : c->ts)
+    if (T.id >= 0) held.push_back(&T);
+  std::sort(held.begin(), held.end(), [](const TimeStep *a, const TimeStep *b) { return a->written < b->written; });
+  if (current) *current = c->have_volume ? c->ts_cur_id : -1;
+  if (n) *n = (int)held.size();
+  if (ids_out)
+    for (int i = 0; i < cap && i < (int)held.size(); ++i) ids_out[i] = held[(size_t)i]->id;
+  return 0;
+}

@@ -29,8 +29,8 @@ HipVolumeRenderer::~HipVolumeRenderer() {
   smk_destroy(ctx);
 }
 
-int HipVolumeRenderer::upload(Volume *v, int n) {
-  if (!ctx) return 1;
+// the bricks of a MetaVolume as the renderer reads them (currentData / currentGrad: the time step swapped in)
+static std::vector<smk_volume_desc> brick_descs(Volume *v, int n) {
   std::vector<smk_volume_desc> d(n);
   for (int i = 0; i < n; ++i) {
     d[i].xiSize = v[i].xiSize; d[i].yiSize = v[i].yiSize; d[i].ziSize = v[i].ziSize;
@@ -40,6 +40,12 @@ int HipVolumeRenderer::upload(Volume *v, int n) {
     d[i].data = v[i].currentData;
     d[i].grad = v[i].currentGrad;
   }
+  return d;
+}
+
+int HipVolumeRenderer::upload(Volume *v, int n) {
+  if (!ctx) return 1;
+  std::vector<smk_volume_desc> d = brick_descs(v, n);
   if (smk_upload_volume(ctx, d.data(), n, m_vol->nelts, SMK_U8, (smk_datamode)gluvv.dmode)) {
     std::cerr << "ERROR: HipVolumeRenderer::createVolume: " << smk_last_error(ctx) << std::endl;
     failed = 1;
@@ -146,8 +152,13 @@ void HipVolumeRenderable::init() {
     return;
   }
   volren = new HipVolumeRenderer(gluvv.mv, 0, device);
+  // a series keeps MetaVolume::tstepCache steps resident (MetaVolume.cpp:894-958): they are uploaded under their time-step
+  // numbers from the first one on; with one step the volume is simply replaced whenever the time step moves
+  tcache = gluvv.mv->tstepCache > 1 ? gluvv.mv->tstepCache : 1;
+  tstep = gluvv.volren.timestep;
   int bad;
-  if (gluvv.mv->numSubVols == 1) bad = volren->createVolume(VolRen3DExt, gluvv.mv->volumes);
+  if (tcache > 1) bad = smk_set_timestep_cache(volren->context(), tcache) || uploadStep(tstep);
+  else if (gluvv.mv->numSubVols == 1) bad = volren->createVolume(VolRen3DExt, gluvv.mv->volumes);
   else bad = volren->createVolume(VolRen3DExt, gluvv.mv->volumes, gluvv.mv->numSubVols);
   if (bad || !volren->ok()) return;  // go stays 0: draw() is a no-op (NV20VolRen3D.cpp:44-65)
   if (gluvv.dmode == GDM_V1 && !gluvv.volren.deptex) {
@@ -177,10 +188,47 @@ void HipVolumeRenderable::createNoiseTex(int sx, int sy, int sz) {
 
 void HipVolumeRenderable::modelview(double mv[16]) { build_modelview(mv); }
 
+int HipVolumeRenderable::uploadStep(int timestep) {
+  smk_ctx *c = volren ? volren->context() : nullptr;
+  if (!c) return 1;
+  std::vector<smk_volume_desc> d = brick_descs(gluvv.mv->volumes, gluvv.mv->numSubVols);
+  if (smk_upload_timestep(c, timestep, d.data(), gluvv.mv->numSubVols, gluvv.mv->nelts, SMK_U8, (smk_datamode)gluvv.dmode)) {
+    std::cerr << "ERROR: HipVolumeRenderable: time step " << timestep << ": " << smk_last_error(c) << std::endl;
+    return 1;
+  }
+  return 0;
+}
+
+// R8kVolRen3D::renderVolume (R8kVolRen3D.cpp:184-188) rebuilds its textures from gluvv.mv when gluvv.volren.timestep moves; the
+// key handler has already swapped that step into the MetaVolume or read it (gluvv.cpp:970-1010).  Here a resident step is
+// selected -- no voxel moves -- and any other is uploaded from gluvv.mv's current data under its number, then selected.
+int HipVolumeRenderable::showTimeStep() {
+  const int t = gluvv.volren.timestep;
+  if (t == tstep) return 0;
+  smk_ctx *c = volren->context();
+  if (tcache == 1) {
+    const int bad = gluvv.mv->numSubVols == 1 ? volren->createVolume(VolRen3DExt, gluvv.mv->volumes)
+                                              : volren->createVolume(VolRen3DExt, gluvv.mv->volumes, gluvv.mv->numSubVols);
+    if (bad) return 1;
+  } else if (smk_select_timestep(c, t)) {  // not cached (swapTStep's return 0)
+    if (uploadStep(t)) return 1;
+    if (smk_select_timestep(c, t)) {
+      std::cerr << "ERROR: HipVolumeRenderable::draw: " << smk_last_error(c) << std::endl;
+      return 1;
+    }
+  }
+  tstep = t;
+  return 0;
+}
+
 void HipVolumeRenderable::draw() {
   if (!go || !volren) return;
   if (gluvv.reblend) return;  // R8kVolRen3D.cpp:177
   if (gluvv.picking) return;  // :179
+  if (showTimeStep()) {
+    go = 0;
+    return;
+  }
   double mv[16];
   build_modelview(mv);
   smk_ctx *c = volren->context();

@@ -76,7 +76,7 @@ class HipVolumeRenderer {
 
 class HipVolumeRenderable final : public gluvvPrimitive {
  public:
-  explicit HipVolumeRenderable(int device = 0) : volren(nullptr), go(0), device(device) {}
+  explicit HipVolumeRenderable(int device = 0) : volren(nullptr), go(0), device(device), tstep(0), tcache(1) {}
   ~HipVolumeRenderable() { delete volren; }  // (gluvvPrimitive's destructor is not virtual, gluvvPrimitive.h:26: delete through this type)
   void init();  // virtual in gluvvPrimitive (gluvvPrimitive.h:29-30)
   void draw();
@@ -88,8 +88,12 @@ class HipVolumeRenderable final : public gluvvPrimitive {
 
  private:
   void createNoiseTex(int sx, int sy, int sz);  // R8kVolRen3D_cpy::createNoiseTex (:2392-2436)
+  int uploadStep(int timestep);                 // gluvv.mv's current data as that time step (smk_upload_timestep)
+  int showTimeStep();                           // R8kVolRen3D::renderVolume's time-step check (R8kVolRen3D.cpp:184-188)
   HipVolumeRenderer *volren;
   int go;
   int device;
+  int tstep;   // the time step the frames show (gluvv.volren.timestep when it was uploaded or selected)
+  int tcache;  // device-resident steps: gluvv.mv->tstepCache, at least 1
   std::vector<unsigned char> noise;  // [sz][sy][sx][4]
 };

@@ -319,6 +319,10 @@ size_t load_trex(const char *filename, int timestep, LoadedVolume *out, std::str
   mv.nelts = 1;
   mv.xiSize = h.isize[0]; mv.yiSize = h.isize[1]; mv.ziSize = h.isize[2];
   mv.xfSize = h.fsize[0]; mv.yfSize = h.fsize[1]; mv.zfSize = h.fsize[2];
+  // the series (MetaVolume::parse, MetaVolume.cpp:294-301, 357-380): its steps, the host-side cache, the step just read
+  mv.tsteps = h.tsteps; mv.tstart = h.tstart; mv.tstop = h.tstop;
+  mv.tstepCache = h.tstep_cache;
+  mv.currentTStep = timestep;
   return total;
 }
 

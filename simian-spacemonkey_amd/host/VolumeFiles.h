@@ -68,8 +68,8 @@ struct LoadedVolume {
   TrexHeader header;
 };
 
-// parse + readAll(timestep): every brick read and quantised, MetaVolume fields filled
-// (MetaVolume.cpp:233-627, 891-899).  Returns total bytes read, 0 on failure.
+// parse + readAll(timestep): every brick read and quantised, MetaVolume fields filled -- the series' tsteps, tstart, tstop and
+// tstepCache among them, currentTStep = timestep (MetaVolume.cpp:233-627, 891-899).  Returns total bytes read, 0 on failure.
 size_t load_trex(const char *filename, int timestep, LoadedVolume *out, std::string *err);
 
 // MetaVolume::writeAll + Volume::writeVol (:963-1000, :99-126): "<prefix>.trex" and one raw
