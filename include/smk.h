@@ -170,10 +170,12 @@ int smk_set_perturb(smk_ctx *ctx, const unsigned char *noise_rgba, int n, const 
  * gluvv.light.gShadowQual or iShadowQual: the light buffer has ceil(quality * buffer_px)^2 texels.
  * Applies to 2-D / 3-D classification with no or R8k shading, with or without the clip-plane widget's planes
  * (smk_set_clip, smk_set_clip_plane: both passes leave out what lies beyond them, as the reference's clipped slice polygons
- * do); other configurations (1-D table, NV20 combiners, perturbation, a sub-box, depth output) make smk_render fail with
+ * do); other configurations (1-D table, NV20 combiners, perturbation, a sub-box) make smk_render fail with
  * the reason.  A shard (smk_set_shard) renders shadows once it has this frame's light entries (smk_shadow_exports_device,
  * smk_shadow_entries_device below; without them smk_render fails) and a halo of smk_get_shadow_margin's halo_needed.  The blend order follows the light (under when
- * the slices run away from the eye, over otherwise), smk_set_blend is not consulted.
+ * the slices run away from the eye, over otherwise), smk_set_blend is not consulted.  depth_out works as without shadows:
+ * the view depth of the nearest sample the eye pass composites along the pixel's half-angle ray (the shadow term scales
+ * colour, never alpha, so it is the unshadowed frame's set of contributing samples, placed on the half-angle slices).
  * How it is rendered: a light-buffer texel depends on itself alone from slice to slice, so the light pass is
  * ONE march per texel that keeps every slice's buffer (nslices + 1 buffers in device memory), and the eye pass is an
  * ordinary frame of the ray-marchers over the half-angle slices that looks each sample's slice up -- two launches instead
@@ -226,6 +228,15 @@ int smk_frame_failed(smk_ctx *ctx, long long frame_id);
  * premultiplied RGBA tiles of npix pixels, DEVICE pointers, layer l at layers + l*npix*4 floats. */
 int smk_composite_over_device(smk_ctx *ctx, const void *d_layers, int nlayers, const int *order,
                               int npix, void *d_out, void *stream);
+/* the same merge with first-hit depth (no reference equivalent: the north star's final reduce of per-brick RGBA + depth
+ * segments).  d_depths: [nlayers][npix] floats, layer l's depth at d_depths + l*npix, each the depth_out of
+ * smk_render_device on that shard (+inf where it has no sample).  d_out gets the RGBA of smk_composite_over_device, bit
+ * for bit; d_depth_out[p] = the minimum of the layers' depths at p (+inf where none is finite).  Every blend mode merges
+ * depth by minimum: a context reports its NEAREST contributing sample (front to back the first composited, back to front
+ * the last, GL_MAX the first), every sample belongs to one shard and all shards place samples on one plane set, so the
+ * minimum over the shards is the unsharded frame's depth, bit for bit.  One pass over the pixels. */
+int smk_composite_over_depth_device(smk_ctx *ctx, const void *d_layers, const void *d_depths, int nlayers,
+                                    const int *order, int npix, void *d_out, void *d_depth_out, void *stream);
 
 /* ---- the sort-last merge in C (no reference equivalent): one object per rank = per
  * context / GPU.  Direct send of the 1/P image tiles (grouped ncclSend/ncclRecv over xGMI), ordered
@@ -262,6 +273,20 @@ int smk_exchange_set_order(smk_exchange *x, int slot, const int *order);
 int smk_exchange_frame(smk_exchange *x, int slot, void *d_frame);
 int smk_exchange_frame_local(smk_exchange *const *all, int nranks, int slot, void *d_frame);
 int smk_exchange_wait(smk_exchange *x, void *stream);
+/* First-hit depth through the exchange (no reference equivalent: the north star's RGBA + depth reduce).
+ * smk_exchange_partial_depth: the [npix] float plane a rank renders slot `slot`'s depth into (smk_render_device's
+ * d_depth, beside smk_exchange_partial(x, slot)).  The first call allocates a depth plane beside each RGBA buffer of both
+ * slots (rendered layer, received tiles, finished tile; +inf in the padding) and returns NULL only if that fails; from then
+ * on the exchange carries depth: the depth pieces travel with the RGBA pieces (inside the same ncclGroupStart/End; the
+ * in-process transport with the same copies and events), the merge takes the minimum of the depths in the same pass as
+ * the ordered over (smk_composite_over_depth_device's rule, every blend mode), and frames go through the _depth entries
+ * below -- smk_exchange_frame[_local] refuse a depth-carrying exchange, the _depth entries one that never enabled depth,
+ * and in-process ranks must all carry depth or none.  d_depth ([npix] floats) is rank 0's only, like d_frame.  The merged
+ * depth equals the unsharded frame's bit for bit.  An exchange that never asks for depth allocates and moves exactly
+ * what it did before: 16 B per pixel; with depth 20. */
+void *smk_exchange_partial_depth(smk_exchange *x, int slot);
+int smk_exchange_frame_depth(smk_exchange *x, int slot, void *d_frame, void *d_depth);
+int smk_exchange_frame_local_depth(smk_exchange *const *all, int nranks, int slot, void *d_frame, void *d_depth);
 
 /* data prep on the GPU (genVGH/main.cpp:56-182, VectorMath.h:874-899,
  * 1133-1148, 1217-1281).  All pointers are DEVICE pointers.

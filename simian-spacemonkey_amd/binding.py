@@ -30,6 +30,7 @@ ABI_SYMBOLS = [
     "smk_shard_light_order", "smk_get_shadow_margin",
     "smk_set_timestep_cache", "smk_upload_timestep", "smk_upload_timestep_device", "smk_select_timestep",
     "smk_get_timesteps",
+    "smk_composite_over_depth_device", "smk_exchange_partial_depth", "smk_exchange_frame_depth", "smk_exchange_frame_local_depth",
 ]
 
 # gluvvDataMode order (gluvv.h:221-235)
@@ -156,6 +157,8 @@ def load_library():
     L.smk_render_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.smk_composite_over_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, P(C.c_int), C.c_int,
                                             C.c_void_p, C.c_void_p]
+    L.smk_composite_over_depth_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, P(C.c_int), C.c_int,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p]
     L.smk_make_vgh_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                       C.c_int, C.c_void_p, C.c_void_p]
     L.smk_normals_vgh_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
@@ -190,6 +193,10 @@ def load_library():
     L.smk_exchange_frame.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     L.smk_exchange_frame_local.argtypes = [P(C.c_void_p), C.c_int, C.c_int, C.c_void_p]
     L.smk_exchange_wait.argtypes = [C.c_void_p, C.c_void_p]
+    L.smk_exchange_partial_depth.restype = C.c_void_p
+    L.smk_exchange_partial_depth.argtypes = [C.c_void_p, C.c_int]
+    L.smk_exchange_frame_depth.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.smk_exchange_frame_local_depth.argtypes = [P(C.c_void_p), C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.smk_timing_reset.argtypes = [C.c_void_p]
     L.smk_timing_read.argtypes = [C.c_void_p, P(C.c_float), P(C.c_int)]
     L.smk_count_samples.argtypes = [C.c_void_p, P(C.c_double)]
@@ -480,6 +487,11 @@ class Renderer:
         self._ck(self.L.smk_composite_over_device(self.ctx, d_layers, nlayers,
                                                   (C.c_int * nlayers)(*order), npix, d_out, stream))
 
+    def composite_over_depth_device(self, d_layers, d_depths, nlayers, order, npix, d_out, d_depth_out, stream=None):
+        """the same merge plus the minimum of the layers' first-hit depths ([nlayers][npix] floats) into d_depth_out"""
+        self._ck(self.L.smk_composite_over_depth_device(self.ctx, d_layers, d_depths, nlayers,
+                                                        (C.c_int * nlayers)(*order), npix, d_out, d_depth_out, stream))
+
     def last_frame_id(self):
         return int(self.L.smk_last_frame_id(self.ctx))
 
@@ -618,6 +630,13 @@ class Exchange:
     def partial(self, slot):
         return self.L.smk_exchange_partial(self.x, slot)
 
+    def partial_depth(self, slot):
+        """the [npix] float plane this rank renders slot `slot`'s depth into; the first call makes the exchange carry depth"""
+        p = self.L.smk_exchange_partial_depth(self.x, slot)
+        if not p:
+            raise SmkError(self.L.smk_exchange_last_error(self.x).decode() or "smk_exchange_partial_depth failed")
+        return p
+
     def acquire(self, slot, render_stream=None):
         self._ck(self.L.smk_exchange_acquire(self.x, slot, render_stream))
 
@@ -631,6 +650,9 @@ class Exchange:
     def frame(self, slot, d_frame):
         self._ck(self.L.smk_exchange_frame(self.x, slot, d_frame))
 
+    def frame_depth(self, slot, d_frame, d_depth):
+        self._ck(self.L.smk_exchange_frame_depth(self.x, slot, d_frame, d_depth))
+
     def wait(self, stream=None):
         self._ck(self.L.smk_exchange_wait(self.x, stream))
 
@@ -643,3 +665,8 @@ class Exchange:
     def frame_local(xs, slot, d_frame):
         arr = (C.c_void_p * len(xs))(*[x.x for x in xs])
         xs[0]._ck(xs[0].L.smk_exchange_frame_local(arr, len(xs), slot, d_frame))
+
+    @staticmethod
+    def frame_local_depth(xs, slot, d_frame, d_depth):
+        arr = (C.c_void_p * len(xs))(*[x.x for x in xs])
+        xs[0]._ck(xs[0].L.smk_exchange_frame_local_depth(arr, len(xs), slot, d_frame, d_depth))

@@ -1864,15 +1864,14 @@ static int shadow_setup(smk_ctx *c, RenderParams &P, smk_shadowcoef &sc, SmkShad
 }
 
 // what a frame with shadows cannot be combined with (the same reasons as smk_render's)
-static int shadow_refusals(smk_ctx *c, const RenderParams &P, bool depth) {
+static int shadow_refusals(smk_ctx *c, const RenderParams &P) {
   const int sk = shade_kind_of(c);
   if (c->tf_mode == 0) FAIL(c, "smk_render: shadows need a 2-D or 3-D transfer function (the 1-D table renderer has no shadow mode)");
   if (sk == 2) FAIL(c, "smk_render: shadows are implemented for R8k shading or none (NV20 combiners: no shadow mode in NV20VolRen3D)");
   if (c->nranks > 1 && (!c->opt_shadow_march || (c->opt_lockstep & 256)))
     FAIL(c, "smk_render: shadows need the whole volume on one GPU with option shadow_march 0 or shadow_fused (the light buffer couples every "
             "slice of every brick); a shard renders shadows with the two marches only");
-  if (P.pert_on || depth || c->region_on)
-    FAIL(c, "smk_render: shadows cannot be combined with perturbation, a sub-box or depth output");
+  if (P.pert_on || c->region_on) FAIL(c, "smk_render: shadows cannot be combined with perturbation or a sub-box");
   if (c->opt_kernel == 3) FAIL(c, "smk_render: the column-stream kernel has no shadow mode");
   return 0;
 }
@@ -1911,7 +1910,7 @@ void smk_shadow_entries_commit(smk_ctx *c, const smk_shadowcoef &sc) {
 int smk_shadow_shard_setup(smk_ctx *c, RenderParams &P, smk_shadowcoef &sc, SmkShadowShard &S, hipStream_t s) {
   if (!c->shadow_on) FAIL(c, "smk_shadow_exports_device: shadows are off (smk_set_shadow)");
   if (build_params(c, P, s)) return 1;
-  if (shadow_refusals(c, P, false)) return 1;
+  if (shadow_refusals(c, P)) return 1;
   int need = 0;
   if (shadow_setup(c, P, sc, &S, &need)) return 1;
   if (shadow_halo_check(c, need)) return 1;
@@ -2089,7 +2088,7 @@ extern "C" int smk_render_device(smk_ctx *c, void *d_rgba, void *d_depth, void *
               "(smk_shadow_exchange_local in one process)");
     const bool entries = c->shadow_entries_fresh;
     c->shadow_entries_fresh = false;  // (consumed by this frame, whatever becomes of it)
-    if (shadow_refusals(c, P, d_depth != nullptr)) return 1;
+    if (shadow_refusals(c, P)) return 1;
     smk_shadowcoef sc;
     SmkShadowShard S;
     int halo_need = 0;
@@ -2158,6 +2157,7 @@ extern "C" int smk_render_device(smk_ctx *c, void *d_rgba, void *d_depth, void *
       HIPCHK(c, hipEventRecord(c->ev0, s));
       HIPCHK(c, hipMemsetAsync(c->d_light[0], 0, nl * 16, s));
       HIPCHK(c, hipMemsetAsync(d_rgba, 0, (size_t)c->W * c->H * 16, s));
+      if (d_depth) HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)d_depth, 0x7f800000, (size_t)c->W * c->H, s));  // (+inf: no sample yet)
       if (!c->d_shadow_barrier) HIPCHK(c, hipMalloc((void **)&c->d_shadow_barrier, 16 * 9 * 4));  // (the common word + one per XCD, a cache line apart)
       hipError_t e = smk_launch_shadow(P, sc, c->dtype, c->tf_mode, sk, c->d_light[0], c->d_light[1], c->d_shadow_barrier, s);
       if (e == hipErrorNotSupported) FAIL(c, "smk_render: no shadow kernel instance for this configuration");
@@ -2475,12 +2475,17 @@ struct OrderArg {
   int o[SMK_MAX_RANKS];
 };
 
-__global__ void smk_k_over(const float4 *layers, int nlayers, OrderArg ord, int npix, float4 *out, int use_max) {
+// DEPTH: the depth layers merge in the same pass, by minimum (a template flag: the RGBA loop is the same code either way)
+template <bool DEPTH>
+__global__ void smk_k_over(const float4 *layers, const float *depths, int nlayers, OrderArg ord, int npix, float4 *out,
+                           float *depth_out, int use_max) {
   int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= npix) return;
   float4 C = make_float4(0.f, 0.f, 0.f, 0.f);
+  float Z = __int_as_float(0x7f800000);
   for (int l = 0; l < nlayers; ++l) {
     float4 s = layers[(size_t)ord.o[l] * npix + p];
+    if (DEPTH) Z = fminf(Z, depths[(size_t)ord.o[l] * npix + p]);
     if (use_max) {  // GL_MAX layers merge by maximum, in any order
       C = make_float4(fmaxf(C.x, s.x), fmaxf(C.y, s.y), fmaxf(C.z, s.z), fmaxf(C.w, s.w));
       continue;
@@ -2492,22 +2497,39 @@ __global__ void smk_k_over(const float4 *layers, int nlayers, OrderArg ord, int 
     C.w = __fmaf_rn(w, s.w, C.w);
   }
   out[p] = C;
+  if (DEPTH) depth_out[p] = Z;
+}
+
+static int composite_over(smk_ctx *c, const char *fn, const void *d_layers, const void *d_depths, int nlayers, const int *order,
+                          int npix, void *d_out, void *d_depth_out, void *stream) {
+  if (!c) return 1;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!d_layers || !d_out || !order) FAIL(c, "%s: null argument", fn);
+  if (nlayers < 1 || nlayers > SMK_MAX_RANKS) FAIL(c, "%s: 1..%d layers", fn, SMK_MAX_RANKS);
+  OrderArg oa;
+  for (int l = 0; l < nlayers; ++l) {
+    if (order[l] < 0 || order[l] >= nlayers) FAIL(c, "%s: order[%d]=%d out of range", fn, l, order[l]);
+    oa.o[l] = order[l];
+  }
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  const int use_max = c->blend == SMK_BLEND_MAX ? 1 : 0;
+  if (d_depths)
+    hipLaunchKernelGGL(smk_k_over<true>, dim3((npix + 255) / 256), dim3(256), 0, s, (const float4 *)d_layers, (const float *)d_depths,
+                       nlayers, oa, npix, (float4 *)d_out, (float *)d_depth_out, use_max);
+  else
+    hipLaunchKernelGGL(smk_k_over<false>, dim3((npix + 255) / 256), dim3(256), 0, s, (const float4 *)d_layers, (const float *)nullptr,
+                       nlayers, oa, npix, (float4 *)d_out, (float *)nullptr, use_max);
+  HIPCHK(c, hipGetLastError());
+  return 0;
 }
 
 extern "C" int smk_composite_over_device(smk_ctx *c, const void *d_layers, int nlayers, const int *order, int npix,
                                          void *d_out, void *stream) {
-  if (!c) return 1;
-  HIPCHK(c, hipSetDevice(c->device));
-  if (!d_layers || !d_out || !order) FAIL(c, "smk_composite_over_device: null argument");
-  if (nlayers < 1 || nlayers > SMK_MAX_RANKS) FAIL(c, "smk_composite_over_device: 1..%d layers", SMK_MAX_RANKS);
-  OrderArg oa;
-  for (int l = 0; l < nlayers; ++l) {
-    if (order[l] < 0 || order[l] >= nlayers) FAIL(c, "smk_composite_over_device: order[%d]=%d out of range", l, order[l]);
-    oa.o[l] = order[l];
-  }
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-  hipLaunchKernelGGL(smk_k_over, dim3((npix + 255) / 256), dim3(256), 0, s, (const float4 *)d_layers, nlayers, oa,
-                     npix, (float4 *)d_out, c->blend == SMK_BLEND_MAX ? 1 : 0);
-  HIPCHK(c, hipGetLastError());
-  return 0;
+  return composite_over(c, "smk_composite_over_device", d_layers, nullptr, nlayers, order, npix, d_out, nullptr, stream);
+}
+
+extern "C" int smk_composite_over_depth_device(smk_ctx *c, const void *d_layers, const void *d_depths, int nlayers, const int *order,
+                                               int npix, void *d_out, void *d_depth_out, void *stream) {
+  if (c && (!d_depths || !d_depth_out)) FAIL(c, "smk_composite_over_depth_device: null depth argument");
+  return composite_over(c, "smk_composite_over_depth_device", d_layers, d_depths, nlayers, order, npix, d_out, d_depth_out, stream);
 }

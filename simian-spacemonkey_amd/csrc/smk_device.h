@@ -349,6 +349,23 @@ __device__ __forceinline__ bool smk_tau_ok(float tauA, float dtau, int m) {
   return t > 0.0f && t < __int_as_float(0x7f800000);
 }
 
+// ---- first-hit depth: the view depth of plane m of a pixel's ray.  Both ray forms are X = e + tau (R0 px + R1 py - n R2)
+// (compute_raycoef, compute_shadowcoef), i.e. the view-space point tau (px, py, -n): its depth is tau * n = tau * znear.
+// View-aligned planes: tau = fma(m, rc.dtau, rc.tau0).  Half-angle slices: tau = fma(m, dtau, tauA) of smk_ray_AB.
+template <bool SHD>
+__device__ __forceinline__ float smk_plane_depth(const RenderParams &P, int m, float tauA, float dtau) {
+  return SHD ? __fmaf_rn((float)m, dtau, tauA) * P.znear : __fmaf_rn((float)m, P.rc.dtau, P.rc.tau0) * P.znear;
+}
+// ... the same from the pixel coordinate, for a kernel that does not keep tauA / dtau live (smk_ray_AB_t's operations: the
+// same bits)
+template <bool SHD>
+__device__ __forceinline__ float smk_plane_depth_px(const RenderParams &P, int m, float px, float py) {
+  if (!SHD) return smk_plane_depth<false>(P, m, 0.0f, 0.0f);
+  const SmkShadowRays &sh = P.sh;
+  const float nD = __fmaf_rn(px, sh.nDx, __fmaf_rn(py, sh.nDy, sh.nDc));
+  return smk_plane_depth<true>(P, m, __fdiv_rn(sh.numA, nD), __fdiv_rn(sh.dB, nD));
+}
+
 // bilinear lookup of a light buffer; texels outside it are 0 (the rest of the pbuffer stays cleared)
 __device__ __forceinline__ void smk_light_lookup(const float4 *L, int LB, float lx, float ly, float out[3]) {
   const float fx0 = floorf(lx - 0.5f), fy0 = floorf(ly - 0.5f);

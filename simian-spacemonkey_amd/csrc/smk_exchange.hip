@@ -85,6 +85,10 @@ struct smk_exchange {
   float4 *partial[2] = {nullptr, nullptr};     // [nranks * tp] this rank's layer, one per frame slot
   float4 *recv[2] = {nullptr, nullptr};        // [nranks][tp] tile `rank` of every rank's layer
   float4 *tile[2] = {nullptr, nullptr};        // [tp] the finished tile
+  // first-hit depth (smk_exchange_partial_depth): a float plane beside each of the three, allocated on the first request;
+  // an exchange that never asks has none and moves RGBA only
+  bool depth = false;
+  float *dpartial[2] = {nullptr, nullptr}, *drecv[2] = {nullptr, nullptr}, *dtile[2] = {nullptr, nullptr};
   hipEvent_t ev_in[2] = {nullptr, nullptr}, ev_sent[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};
   bool used[2] = {false, false};
   // visibility order of the ranks for the frame in each slot, taken when the frame was RENDERED (smk_exchange_rendered): the
@@ -140,6 +144,9 @@ extern "C" void smk_exchange_destroy(smk_exchange *x) {
     if (x->partial[s]) (void)hipFree(x->partial[s]);
     if (x->recv[s]) (void)hipFree(x->recv[s]);
     if (x->tile[s]) (void)hipFree(x->tile[s]);
+    if (x->dpartial[s]) (void)hipFree(x->dpartial[s]);
+    if (x->drecv[s]) (void)hipFree(x->drecv[s]);
+    if (x->dtile[s]) (void)hipFree(x->dtile[s]);
     if (x->ev_in[s]) (void)hipEventDestroy(x->ev_in[s]);
     if (x->ev_sent[s]) (void)hipEventDestroy(x->ev_sent[s]);
     if (x->ev_done[s]) (void)hipEventDestroy(x->ev_done[s]);
@@ -233,6 +240,36 @@ extern "C" int smk_exchange_connect_local(smk_exchange *const *all, int nranks) 
 
 extern "C" void *smk_exchange_partial(smk_exchange *x, int slot) { return x && slot >= 0 && slot < 2 ? x->partial[slot] : nullptr; }
 
+extern "C" void *smk_exchange_partial_depth(smk_exchange *x, int slot) {
+  if (!x || slot < 0 || slot > 1) return nullptr;
+  if (!x->depth) {
+    if (hipSetDevice(x->ctx->device) != hipSuccess) {
+      x->err = x->ctx->err = "smk_exchange_partial_depth: hipSetDevice failed";
+      return nullptr;
+    }
+    const size_t n = (size_t)x->tp * x->nranks;
+    bool ok = true;
+    for (int s = 0; s < 2 && ok; ++s)  // (+inf: the padding after npix is "no sample", as a rank's empty pixels are)
+      ok = hipMalloc((void **)&x->dpartial[s], n * sizeof(float)) == hipSuccess && hipMalloc((void **)&x->drecv[s], n * sizeof(float)) == hipSuccess &&
+           hipMalloc((void **)&x->dtile[s], (size_t)x->tp * sizeof(float)) == hipSuccess &&
+           hipMemsetD32((hipDeviceptr_t)x->dpartial[s], 0x7f800000, n) == hipSuccess &&
+           hipMemsetD32((hipDeviceptr_t)x->drecv[s], 0x7f800000, n) == hipSuccess;
+    if (!ok) {
+      (void)hipGetLastError();
+      for (int s = 0; s < 2; ++s) {
+        if (x->dpartial[s]) (void)hipFree(x->dpartial[s]);
+        if (x->drecv[s]) (void)hipFree(x->drecv[s]);
+        if (x->dtile[s]) (void)hipFree(x->dtile[s]);
+        x->dpartial[s] = x->drecv[s] = x->dtile[s] = nullptr;
+      }
+      x->err = x->ctx->err = "smk_exchange_partial_depth: device allocation failed";
+      return nullptr;
+    }
+    x->depth = true;
+  }
+  return x->dpartial[slot];
+}
+
 // before rendering into partial(slot) again: the frame that used it two frames ago must have been sent
 extern "C" int smk_exchange_acquire(smk_exchange *x, int slot, void *render_stream) {
   if (!x || slot < 0 || slot > 1) return 1;
@@ -274,15 +311,25 @@ static int merge_tile(smk_exchange *x, int slot) {
   int order[SMK_MAX_RANKS];
   if (x->order_valid[slot]) memcpy(order, x->order[slot], sizeof order);
   else if (smk_shard_order(x->ctx, order)) XFAIL(x, "smk_exchange: %s", x->ctx->err.c_str());  // (a frame nobody marked: the current camera)
-  if (smk_composite_over_device(x->ctx, x->recv[slot], x->nranks, order, x->tp, x->tile[slot], x->xs))
+  if (x->depth ? smk_composite_over_depth_device(x->ctx, x->recv[slot], x->drecv[slot], x->nranks, order, x->tp, x->tile[slot], x->dtile[slot], x->xs)
+               : smk_composite_over_device(x->ctx, x->recv[slot], x->nranks, order, x->tp, x->tile[slot], x->xs))
     XFAIL(x, "smk_exchange: %s", x->ctx->err.c_str());
   return 0;
 }
 
-extern "C" int smk_exchange_frame(smk_exchange *x, int slot, void *d_frame) {
+// whether a frame entry fits the exchange: the _depth entries need one that carries depth, the others one that does not
+static int depth_check(smk_exchange *x, const char *fn, bool want) {
+  if (want && !x->depth) XFAIL(x, "%s: this exchange carries no depth (smk_exchange_partial_depth enables it, before the frame is rendered)", fn);
+  if (!want && x->depth) XFAIL(x, "%s: this exchange carries depth (smk_exchange_partial_depth): its frames go through %s_depth", fn, fn);
+  return 0;
+}
+
+static int frame_rccl(smk_exchange *x, int slot, void *d_frame, float *d_depth, const char *fn) {
   if (!x || slot < 0 || slot > 1) return 1;
-  if (x->local && x->nranks > 1) XFAIL(x, "smk_exchange_frame: in-process ranks exchange through smk_exchange_frame_local");
-  if (x->rank == 0 && !d_frame) XFAIL(x, "smk_exchange_frame: rank 0 needs the frame buffer");
+  if (x->local && x->nranks > 1) XFAIL(x, "%s: in-process ranks exchange through smk_exchange_frame_local", fn);
+  if (x->rank == 0 && !d_frame) XFAIL(x, "%s: rank 0 needs the frame buffer", fn);
+  if (x->rank == 0 && x->depth && !d_depth) XFAIL(x, "%s: rank 0 needs the depth buffer", fn);
+  const bool dep = x->depth;
   XHIP(x, hipSetDevice(x->ctx->device));
   const int P = x->nranks, me = x->rank, tp = x->tp;
   XHIP(x, hipStreamWaitEvent(x->xs, x->ev_in[slot], 0));  // (smk_exchange_rendered)
@@ -294,25 +341,36 @@ extern "C" int smk_exchange_frame(smk_exchange *x, int slot, void *d_frame) {
       if (p == me) continue;
       XNCCL(x, r->Send(x->partial[slot] + (size_t)p * tp, (size_t)tp * 4, kNcclFloat, p, x->comm, x->xs));
       XNCCL(x, r->Recv(x->recv[slot] + (size_t)p * tp, (size_t)tp * 4, kNcclFloat, p, x->comm, x->xs));
+      if (dep) {  // (the depth piece in the same group: one round of the links for both)
+        XNCCL(x, r->Send(x->dpartial[slot] + (size_t)p * tp, (size_t)tp, kNcclFloat, p, x->comm, x->xs));
+        XNCCL(x, r->Recv(x->drecv[slot] + (size_t)p * tp, (size_t)tp, kNcclFloat, p, x->comm, x->xs));
+      }
     }
     XNCCL(x, r->GroupEnd());
   }
   XHIP(x, hipMemcpyAsync(x->recv[slot] + (size_t)me * tp, x->partial[slot] + (size_t)me * tp, (size_t)tp * sizeof(float4), hipMemcpyDeviceToDevice, x->xs));
+  if (dep)
+    XHIP(x, hipMemcpyAsync(x->drecv[slot] + (size_t)me * tp, x->dpartial[slot] + (size_t)me * tp, (size_t)tp * sizeof(float), hipMemcpyDeviceToDevice, x->xs));
   XHIP(x, hipEventRecord(x->ev_sent[slot], x->xs));
   x->used[slot] = true;
   // ---- ordered over of the P layers of my tile
   if (merge_tile(x, slot)) return 1;
   // ---- finished tiles to rank 0
-  if (me == 0)
+  if (me == 0) {
     XHIP(x, hipMemcpyAsync((float4 *)d_frame, x->tile[slot], (size_t)x->cnt(0) * sizeof(float4), hipMemcpyDeviceToDevice, x->xs));
+    if (dep) XHIP(x, hipMemcpyAsync(d_depth, x->dtile[slot], (size_t)x->cnt(0) * sizeof(float), hipMemcpyDeviceToDevice, x->xs));
+  }
   if (P > 1) {
     Rccl *r = rccl();
     XNCCL(x, r->GroupStart());
     if (me != 0) {
       if (x->cnt(me) > 0) XNCCL(x, r->Send(x->tile[slot], (size_t)x->cnt(me) * 4, kNcclFloat, 0, x->comm, x->xs));
+      if (dep && x->cnt(me) > 0) XNCCL(x, r->Send(x->dtile[slot], (size_t)x->cnt(me), kNcclFloat, 0, x->comm, x->xs));
     } else {
-      for (int p = 1; p < P; ++p)
+      for (int p = 1; p < P; ++p) {
         if (x->cnt(p) > 0) XNCCL(x, r->Recv((float4 *)d_frame + (size_t)p * tp, (size_t)x->cnt(p) * 4, kNcclFloat, p, x->comm, x->xs));
+        if (dep && x->cnt(p) > 0) XNCCL(x, r->Recv(d_depth + (size_t)p * tp, (size_t)x->cnt(p), kNcclFloat, p, x->comm, x->xs));
+      }
     }
     XNCCL(x, r->GroupEnd());
   }
@@ -320,13 +378,32 @@ extern "C" int smk_exchange_frame(smk_exchange *x, int slot, void *d_frame) {
   return 0;
 }
 
-extern "C" int smk_exchange_frame_local(smk_exchange *const *all, int nranks, int slot, void *d_frame) {
+extern "C" int smk_exchange_frame(smk_exchange *x, int slot, void *d_frame) {
+  if (!x) return 1;
+  if (depth_check(x, "smk_exchange_frame", false)) return 1;
+  return frame_rccl(x, slot, d_frame, nullptr, "smk_exchange_frame");
+}
+
+extern "C" int smk_exchange_frame_depth(smk_exchange *x, int slot, void *d_frame, void *d_depth) {
+  if (!x) return 1;
+  if (depth_check(x, "smk_exchange_frame_depth", true)) return 1;
+  return frame_rccl(x, slot, d_frame, (float *)d_depth, "smk_exchange_frame_depth");
+}
+
+static int frame_local(smk_exchange *const *all, int nranks, int slot, void *d_frame, float *d_depth, bool want_depth, const char *fn) {
   if (!all || nranks < 1 || !all[0] || slot < 0 || slot > 1) return 1;
   smk_exchange *x0 = all[0];
-  if (!d_frame) XFAIL(x0, "smk_exchange_frame_local: no frame buffer");
+  if (!d_frame) XFAIL(x0, "%s: no frame buffer", fn);
+  if (want_depth && !d_depth) XFAIL(x0, "%s: no depth buffer", fn);
   for (int r = 0; r < nranks; ++r)
     if (!all[r] || !all[r]->local || (int)all[r]->peers.size() != nranks || all[r]->peers[r] != all[r])
-      XFAIL(x0, "smk_exchange_frame_local: ranks not connected (smk_exchange_connect_local)");
+      XFAIL(x0, "%s: ranks not connected (smk_exchange_connect_local)", fn);
+  for (int r = 0; r < nranks; ++r)
+    if (all[r]->depth != x0->depth)
+      XFAIL(x0, "%s: rank %d %s depth and rank 0 %s: in-process ranks carry depth all or none (smk_exchange_partial_depth)", fn, r,
+            all[r]->depth ? "carries" : "does not carry", x0->depth ? "does" : "does not");
+  if (depth_check(x0, fn, want_depth)) return 1;
+  const bool dep = want_depth;
   const int tp = x0->tp;
   // ---- every rank puts tile p of its layer into rank p's receive buffer
   for (int r = 0; r < nranks; ++r) {
@@ -344,6 +421,14 @@ extern "C" int smk_exchange_frame_local(smk_exchange *const *all, int nranks, in
         XHIP(x, hipMemcpyAsync(dst, src, (size_t)tp * sizeof(float4), hipMemcpyDeviceToDevice, x->xs));
       else
         XHIP(x, hipMemcpyPeerAsync(dst, y->ctx->device, src, x->ctx->device, (size_t)tp * sizeof(float4), x->xs));
+      if (dep) {
+        float *ddst = y->drecv[slot] + (size_t)r * tp;
+        const float *dsrc = x->dpartial[slot] + (size_t)p * tp;
+        if (y->ctx->device == x->ctx->device)
+          XHIP(x, hipMemcpyAsync(ddst, dsrc, (size_t)tp * sizeof(float), hipMemcpyDeviceToDevice, x->xs));
+        else
+          XHIP(x, hipMemcpyPeerAsync(ddst, y->ctx->device, dsrc, x->ctx->device, (size_t)tp * sizeof(float), x->xs));
+      }
     }
     XHIP(x, hipEventRecord(x->ev_sent[slot], x->xs));
   }
@@ -360,6 +445,13 @@ extern "C" int smk_exchange_frame_local(smk_exchange *const *all, int nranks, in
         XHIP(x, hipMemcpyAsync(dst, x->tile[slot], (size_t)x->cnt(r) * sizeof(float4), hipMemcpyDeviceToDevice, x->xs));
       else
         XHIP(x, hipMemcpyPeerAsync(dst, x0->ctx->device, x->tile[slot], x->ctx->device, (size_t)x->cnt(r) * sizeof(float4), x->xs));
+      if (dep) {
+        float *ddst = d_depth + (size_t)r * tp;
+        if (x->ctx->device == x0->ctx->device)
+          XHIP(x, hipMemcpyAsync(ddst, x->dtile[slot], (size_t)x->cnt(r) * sizeof(float), hipMemcpyDeviceToDevice, x->xs));
+        else
+          XHIP(x, hipMemcpyPeerAsync(ddst, x0->ctx->device, x->dtile[slot], x->ctx->device, (size_t)x->cnt(r) * sizeof(float), x->xs));
+      }
     }
     XHIP(x, hipEventRecord(x->ev_done[slot], x->xs));
     x->used[slot] = true;
@@ -368,6 +460,14 @@ extern "C" int smk_exchange_frame_local(smk_exchange *const *all, int nranks, in
   XHIP(x0, hipSetDevice(x0->ctx->device));
   for (int r = 1; r < nranks; ++r) XHIP(x0, hipStreamWaitEvent(x0->xs, all[r]->ev_done[slot], 0));
   return 0;
+}
+
+extern "C" int smk_exchange_frame_local(smk_exchange *const *all, int nranks, int slot, void *d_frame) {
+  return frame_local(all, nranks, slot, d_frame, nullptr, false, "smk_exchange_frame_local");
+}
+
+extern "C" int smk_exchange_frame_local_depth(smk_exchange *const *all, int nranks, int slot, void *d_frame, void *d_depth) {
+  return frame_local(all, nranks, slot, d_frame, (float *)d_depth, true, "smk_exchange_frame_local_depth");
 }
 
 extern "C" int smk_exchange_wait(smk_exchange *x, void *stream) {

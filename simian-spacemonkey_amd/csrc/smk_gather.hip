@@ -206,7 +206,7 @@ __global__ __launch_bounds__(256) void smk_k_gather(const RenderParams P) {
     if (P.blend == SMK_BLEND_FRONT_TO_BACK) {
       // C += (1-A) src   (GL_ONE_MINUS_DST_ALPHA, GL_ONE)
       float w = 1.0f - C3;
-      if (first == __int_as_float(0x7f800000)) first = __fmaf_rn((float)m, rc.dtau, rc.tau0) * P.znear;
+      if (first == __int_as_float(0x7f800000)) first = smk_plane_depth<SHD>(P, m, tauA, dtau);
       C0 = __fmaf_rn(w, src.x, C0);
       C1 = __fmaf_rn(w, src.y, C1);
       C2 = __fmaf_rn(w, src.z, C2);
@@ -217,14 +217,14 @@ __global__ __launch_bounds__(256) void smk_k_gather(const RenderParams P) {
     } else if (btf) {
       // D = S + (1-S.a) D   (GL_ONE, GL_ONE_MINUS_SRC_ALPHA); the nearest contributing sample is the last one
       float w = 1.0f - src.w;
-      first = __fmaf_rn((float)m, rc.dtau, rc.tau0) * P.znear;
+      first = smk_plane_depth<SHD>(P, m, tauA, dtau);
       C0 = __fmaf_rn(w, C0, src.x);
       C1 = __fmaf_rn(w, C1, src.y);
       C2 = __fmaf_rn(w, C2, src.z);
       C3 = __fmaf_rn(w, C3, src.w);
     } else {
       // D = max(S, D) per component (GL_MAX ignores the blend factors)
-      if (first == __int_as_float(0x7f800000)) first = __fmaf_rn((float)m, rc.dtau, rc.tau0) * P.znear;
+      if (first == __int_as_float(0x7f800000)) first = smk_plane_depth<SHD>(P, m, tauA, dtau);
       C0 = fmaxf(C0, src.x);
       C1 = fmaxf(C1, src.y);
       C2 = fmaxf(C2, src.z);

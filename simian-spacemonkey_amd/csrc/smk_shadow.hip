@@ -169,6 +169,12 @@ __device__ __forceinline__ void shadow_st4(float4 *p, float4 v) {
   __hip_atomic_store(f + 3, v.w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+template <bool COH>
+__device__ __forceinline__ void shadow_st1(float *p, float v) {
+  if (!COH) { *p = v; return; }
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 template <int DT, int TF, int SH, bool COH = false>
 __device__ __forceinline__ void shadow_eye_pixel(const RenderParams &P, const ShadowSlice &Q, int i, int j) {
   const smk_shadowcoef &sc = Q.sc;
@@ -208,6 +214,10 @@ __device__ __forceinline__ void shadow_eye_pixel(const RenderParams &P, const Sh
   shadow_lookup<COH>(Q.Lprev, sc.LB, __fmaf_rn(__fdiv_rn(lxx, lw), sc.lscale, sc.lbias),
                      __fmaf_rn(__fdiv_rn(lyy, lw), sc.lscale, sc.lbias), shadow);
   const float4 src = smk_shade_sample<SH>(P, col, n0, n1, n2, ch1, shadow);
+  // first-hit depth (the marchers' smk_plane_depth): slices running away from the viewer composite under, so the first
+  // sample composited -- the one that finds the alpha still exactly 0 -- is the nearest; slices running towards the viewer
+  // composite over, so every one replaces the depth and the last is the nearest.  (Buffer cleared to +inf by the launcher.)
+  if (P.depth != nullptr && (!sc.front_to_back || C.w == 0.0f)) shadow_st1<COH>(P.depth + o, smk_plane_depth<true>(P, m, tauA, dtau));
   if (sc.front_to_back) {
     const float w = 1.0f - C.w;
     C.x = __fmaf_rn(w, src.x, C.x);

@@ -1302,7 +1302,7 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
             }
             // first-hit depth (the gather kernel's `first`): the first sample that passes classification finds the accumulated
             // alpha still exactly 0, no later one does -- nothing is carried through the loop for it
-            if (P.depth != nullptr && C3 == 0.0f) P.depth[(size_t)j * P.W + i] = __fmaf_rn((float)m, rc.dtau, rc.tau0) * P.znear;
+            if (P.depth != nullptr && C3 == 0.0f) P.depth[(size_t)j * P.W + i] = smk_plane_depth_px<SHD>(P, m, px, py);
             if (P.blend == SMK_BLEND_MAX) {  // GL_MAX (gluvvShadeMIP): no order, no termination
               C0 = fmaxf(C0, src.x);
               C1 = fmaxf(C1, src.y);

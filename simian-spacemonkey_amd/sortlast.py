@@ -8,6 +8,10 @@ with ONE exchange step:
 
     direct-send all-to-all of 1/P image tiles  ->  ordered "over" of P layers  ->  gather
 
+First-hit depth (optional) travels beside the RGBA: a [npix_padded] float plane per rank, its
+pieces sent with the RGBA pieces, merged by minimum (every blend mode: each rank reports its
+nearest contributing sample, so the nearest over the ranks is the unsharded frame's depth).
+
 "over" is associative but not commutative, so this cannot be an all-reduce(sum); the layer
 order is the BSP front-to-back order of the shards for the current eye point.  On MI355X
 `backend="nccl"` is RCCL over xGMI; the all-to-all uses all 7 links of each GPU at once.
@@ -55,31 +59,60 @@ def tile_pixels(npix, nranks):
     return (npix + nranks - 1) // nranks
 
 
-def exchange_and_composite(partial, order, compositor, group=None, recv=None, via_host=False):
-    """partial: [npix_padded, 4] premultiplied RGBA of THIS rank's shard (npix_padded divisible
-    by the world size).  Returns this rank's finished tile [npix_padded/P, 4].  `recv` lets a
-    caller keep one receive buffer per frame slot; `via_host` stages device tensors through host
-    memory for a backend that only moves CPU tensors (gloo rehearsals of the GPU plumbing)."""
-    P = dist.get_world_size(group)
-    n = partial.shape[0]
-    assert n % P == 0
-    # direct send: piece r of my partial image goes to rank r; I receive piece `me` of everyone
+def _all_to_all(partial, recv, group, via_host):
     if via_host and partial.is_cuda:
         send = partial.cpu()
         got = torch.empty_like(send)
         dist.all_to_all_single(got, send, group=group)
-        recv = got.to(partial.device)
-    else:
-        if recv is None:
-            recv = torch.empty_like(partial)
-        dist.all_to_all_single(recv, partial, group=group)
+        return got.to(partial.device)
+    if recv is None:
+        recv = torch.empty_like(partial)
+    dist.all_to_all_single(recv, partial, group=group)
+    return recv
+
+
+def merge_depth(dlayers):
+    """[P, tile] first-hit depths -> [tile]: the minimum over the layers (+inf where none is finite)"""
+    out = dlayers[0]
+    for l in range(1, dlayers.shape[0]):
+        out = torch.minimum(out, dlayers[l])
+    return out
+
+
+def exchange_and_composite(partial, order, compositor, group=None, recv=None, via_host=False, depth=None, recv_depth=None):
+    """partial: [npix_padded, 4] premultiplied RGBA of THIS rank's shard (npix_padded divisible
+    by the world size).  Returns this rank's finished tile [npix_padded/P, 4].  `recv` lets a
+    caller keep one receive buffer per frame slot; `via_host` stages device tensors through host
+    memory for a backend that only moves CPU tensors (gloo rehearsals of the GPU plumbing).
+    depth: [npix_padded] float first-hit depth of this rank's shard (+inf: no sample), or None.
+    With it, its pieces travel with the RGBA pieces (`recv_depth`: the caller's receive buffer)
+    and the result is (tile, tile_depth), tile_depth = the minimum over the ranks' pieces."""
+    P = dist.get_world_size(group)
+    n = partial.shape[0]
+    assert n % P == 0
+    # direct send: piece r of my partial image goes to rank r; I receive piece `me` of everyone
+    recv = _all_to_all(partial, recv, group, via_host)
     layers = recv.view(P, n // P, 4)
-    return compositor(layers, order)
+    if depth is None:
+        return compositor(layers, order)
+    assert depth.shape[0] == n
+    recv_depth = _all_to_all(depth, recv_depth, group, via_host)
+    return compositor(layers, order), merge_depth(recv_depth.view(P, n // P))
 
 
-def gather_frame(tile, dst=0, group=None, via_host=False, into=None):
+def gather_frame(tile, dst=0, group=None, via_host=False, into=None, depth=None, depth_into=None):
     """finished tiles -> full frame on rank dst ([npix_padded,4]); None elsewhere.  `into` (rank dst):
-    a preallocated [P, tile, 4] buffer the tiles are received into (no allocation per frame)."""
+    a preallocated [P, tile, 4] buffer the tiles are received into (no allocation per frame).
+    depth: this rank's finished depth tile [tile] (exchange_and_composite's second result), or
+    None; with it the result is (frame, frame_depth [npix_padded]) on rank dst, (None, None)
+    elsewhere (`depth_into`: a preallocated [P, tile] buffer, as `into`)."""
+    if depth is not None:
+        d = _gather(depth, dst, group, via_host, depth_into)
+        return _gather(tile, dst, group, via_host, into, 4), d
+    return _gather(tile, dst, group, via_host, into, 4)
+
+
+def _gather(tile, dst, group, via_host, into, comps=None):
     P = dist.get_world_size(group)
     me = dist.get_rank(group)
     src = tile.cpu() if via_host and tile.is_cuda else tile
@@ -92,8 +125,9 @@ def gather_frame(tile, dst=0, group=None, via_host=False, into=None):
     dist.gather(src, out, dst=dst, group=group)
     if me != dst:
         return None
+    shape = (-1, comps) if comps else (-1,)
     if into is not None and not (via_host and tile.is_cuda):
-        return into.view(-1, 4)
+        return into.view(*shape)
     return torch.cat(out, 0).to(tile.device)
 
 
@@ -103,15 +137,20 @@ class Pipeline:
     context itself is used by one frame at a time (frame i+1's launch waits for frame i's
     ray-marcher, not for its exchange).  `render(ptr, stream_handle)` ray-marches this rank's
     shard into the [npix_padded,4] buffer at `ptr`; `compositor(layers, order, out, stream_handle)`
-    merges [P, tile, 4] front to back into `out`."""
+    merges [P, tile, 4] front to back into `out`.
+    depth=True: every frame also carries first-hit depth -- render(ptr, stream_handle, depth_ptr)
+    writes the [npix_padded] depth plane beside the layer, frame(out, order, out_depth) delivers the
+    merged depth (the minimum over the ranks) into out_depth ([npix]) on rank 0, and frame_check is
+    called with the depth pointer as a fourth argument."""
 
-    def __init__(self, render, compositor, npix, group=None, slots=2, via_host=False, frame_check=None):
+    def __init__(self, render, compositor, npix, group=None, slots=2, via_host=False, frame_check=None, depth=False):
         """frame_check(token, ptr, stream_handle) -> bool (token = what render() returned), called once a frame's ray-marcher has finished and
         BEFORE its layer is exchanged: True = the frame was invalid and has been rendered again into
         the same buffer (the product passes Renderer.frame_failed + a gather-kernel re-render).  The
         repair is local to the rank, so no rank ever leaves the others waiting in a collective."""
         self.render, self.compositor, self.group, self.via_host = render, compositor, group, via_host
         self.frame_check = frame_check
+        self.depth = depth
         P = dist.get_world_size(group)
         me = dist.get_rank(group)
         tp = tile_pixels(npix, P)
@@ -125,14 +164,20 @@ class Pipeline:
                 "tile": torch.zeros((tp, 4), dtype=torch.float32, device="cuda"),
                 # rank 0: where the finished tiles of a frame are gathered (allocated once)
                 "full": torch.empty((P, tp, 4), dtype=torch.float32, device="cuda") if me == 0 else None})
+            if depth:
+                self.slots[-1].update({
+                    "dpartial": torch.full((tp * P,), float("inf"), dtype=torch.float32, device="cuda"),
+                    "drecv": torch.empty((tp * P,), dtype=torch.float32, device="cuda"),
+                    "dfull": torch.empty((P, tp), dtype=torch.float32, device="cuda") if me == 0 else None})
         self.count = 0
         self.repaired = 0        # frames frame_check had to render again
         self.marched = None      # event: the latest frame's ray-marcher has finished
         self.delivered = None    # event: the latest frame has been copied into the caller's buffer
         self.pending = None      # the frame whose layer has not been exchanged yet
 
-    def frame(self, out, order):
-        """enqueue one frame; on rank 0 `out` ([npix,4]) receives it.  Returns at once.  The frame's
+    def frame(self, out, order, out_depth=None):
+        """enqueue one frame; on rank 0 `out` ([npix,4]) receives it (and `out_depth` ([npix]) its
+        depth, depth=True).  Returns at once.  The frame's
         layer is exchanged when the NEXT frame has been enqueued (or at drain()): its ray-marcher has
         then had a frame's time to run, so looking at its status costs the host no wait to speak of,
         and the exchange still overlaps the next frame's ray-marching."""
@@ -143,10 +188,11 @@ class Pipeline:
         with torch.cuda.stream(s):
             if self.marched is not None:
                 s.wait_event(self.marched)
-            sl["token"] = self.render(sl["partial"].data_ptr(), s.cuda_stream)   # (whatever identifies the frame to frame_check)
+            dargs = (sl["dpartial"].data_ptr(),) if self.depth else ()
+            sl["token"] = self.render(sl["partial"].data_ptr(), s.cuda_stream, *dargs)   # (whatever identifies the frame to frame_check)
             self.marched = torch.cuda.Event()
             self.marched.record(s)
-        sl["marched"], sl["out"], sl["order"] = self.marched, out, order
+        sl["marched"], sl["out"], sl["order"], sl["out_depth"] = self.marched, out, order, out_depth
         prev, self.pending = self.pending, sl
         if prev is not None:
             self._exchange(prev)
@@ -156,18 +202,26 @@ class Pipeline:
         with torch.cuda.stream(s):
             if self.frame_check is not None:
                 sl["marched"].synchronize()
-                if self.frame_check(sl["token"], sl["partial"].data_ptr(), s.cuda_stream):
+                dargs = (sl["dpartial"].data_ptr(),) if self.depth else ()
+                if self.frame_check(sl["token"], sl["partial"].data_ptr(), s.cuda_stream, *dargs):
                     self.repaired += 1
 
             def comp(layers, order_):
                 self.compositor(layers, order_, sl["tile"], s.cuda_stream)
                 return sl["tile"]
-            tile = exchange_and_composite(sl["partial"], sl["order"], comp, self.group, sl["recv"], self.via_host)
-            full = gather_frame(tile, 0, self.group, self.via_host, into=sl["full"])
+            if self.depth:
+                tile, dtile = exchange_and_composite(sl["partial"], sl["order"], comp, self.group, sl["recv"], self.via_host,
+                                                     depth=sl["dpartial"], recv_depth=sl["drecv"])
+                full, dfull = gather_frame(tile, 0, self.group, self.via_host, into=sl["full"], depth=dtile, depth_into=sl["dfull"])
+            else:
+                tile = exchange_and_composite(sl["partial"], sl["order"], comp, self.group, sl["recv"], self.via_host)
+                full, dfull = gather_frame(tile, 0, self.group, self.via_host, into=sl["full"]), None
             if full is not None:
                 if self.delivered is not None:
                     s.wait_event(self.delivered)
                 sl["out"].copy_(full[:self.npix])
+                if dfull is not None and sl["out_depth"] is not None:
+                    sl["out_depth"].copy_(dfull[:self.npix])
                 self.delivered = torch.cuda.Event()
                 self.delivered.record(s)
 
@@ -183,38 +237,48 @@ class Pipeline:
 class ExchangePipeline:
     """Pipeline's contract with the merge behind the C ABI (smk_exchange_*, RCCL transport: grouped
     ncclSend/ncclRecv direct send, ordered over, gather -- csrc/smk_exchange.hip).  Python only
-    sequences the calls; no torch collective is in the data path."""
+    sequences the calls; no torch collective is in the data path.  depth=True: as Pipeline's (the
+    exchange carries depth from construction on: smk_exchange_partial_depth, smk_exchange_frame_depth)."""
 
-    def __init__(self, render, exchange, npix, rank, frame_check=None):
+    def __init__(self, render, exchange, npix, rank, frame_check=None, depth=False):
         self.render, self.x, self.npix, self.rank, self.frame_check = render, exchange, npix, rank, frame_check
+        self.depth = depth
+        if depth:
+            self.x.partial_depth(0)
         self.count = 0
         self.repaired = 0
         self.pending = None
 
-    def frame(self, out, order=None):
+    def _dargs(self, slot):
+        return (self.x.partial_depth(slot),) if self.depth else ()
+
+    def frame(self, out, order=None, out_depth=None):
         slot = self.count & 1
         self.count += 1
         st = torch.cuda.current_stream().cuda_stream
         self.x.acquire(slot, st)
-        token = self.render(self.x.partial(slot), st)
+        token = self.render(self.x.partial(slot), st, *self._dargs(slot))
         self.x.rendered(slot, st)      # (also takes the shards' visibility order under THIS frame's camera)
         if order is not None:
             self.x.set_order(slot, order)
         ev = torch.cuda.Event()
         ev.record()
-        prev, self.pending = self.pending, (slot, token, ev, out)
+        prev, self.pending = self.pending, (slot, token, ev, out, out_depth)
         if prev is not None:
             self._exchange(prev)
 
     def _exchange(self, p):
-        slot, token, ev, out = p
+        slot, token, ev, out, out_depth = p
         if self.frame_check is not None:
             ev.synchronize()
             st = torch.cuda.current_stream().cuda_stream
-            if self.frame_check(token, self.x.partial(slot), st):
+            if self.frame_check(token, self.x.partial(slot), st, *self._dargs(slot)):
                 self.repaired += 1
                 self.x.rendered(slot, st)
-        self.x.frame(slot, out.data_ptr() if self.rank == 0 else None)
+        if self.depth:
+            self.x.frame_depth(slot, out.data_ptr() if self.rank == 0 else None, out_depth.data_ptr() if self.rank == 0 else None)
+        else:
+            self.x.frame(slot, out.data_ptr() if self.rank == 0 else None)
 
     def drain(self):
         if self.pending is not None:
@@ -223,10 +287,11 @@ class ExchangePipeline:
         self.x.wait(torch.cuda.current_stream().cuda_stream)
 
 
-def render_shadow_frame_local(renderers):
+def render_shadow_frame_local(renderers, depth=False):
     """One frame with shadows on P shard contexts of this process that share one device, ranks in order (smk.h "Shadows on
     shards"): phase 1 and the light exchange (smk_shadow_exchange_local), every rank's frame, then the HIP "over" of the P
-    layers in smk_shard_order's order.  Returns the merged frame, a [H][W][4] float32 tensor on that device."""
+    layers in smk_shard_order's order.  Returns the merged frame, a [H][W][4] float32 tensor on that device; depth=True:
+    (frame, depth), depth the [H][W] minimum of the ranks' first-hit depths (smk_composite_over_depth_device)."""
     from .binding import shadow_exchange_local
     nranks = len(renderers)
     w, h = renderers[0].size
@@ -235,10 +300,16 @@ def render_shadow_frame_local(renderers):
     shadow_exchange_local(renderers)
     layers = torch.zeros((nranks, npix, 4), dtype=torch.float32, device=dev)
     out = torch.zeros((npix, 4), dtype=torch.float32, device=dev)
+    dlayers = torch.full((nranks, npix), float("inf"), dtype=torch.float32, device=dev) if depth else None
+    dout = torch.empty((npix,), dtype=torch.float32, device=dev) if depth else None
     torch.cuda.synchronize(dev)
     for r, R in enumerate(renderers):
-        R.render_device(layers[r].data_ptr())
+        R.render_device(layers[r].data_ptr(), dlayers[r].data_ptr() if depth else None)
     torch.cuda.synchronize(dev)
-    renderers[0].composite_over_device(layers.data_ptr(), nranks, renderers[0].shard_order(nranks), npix, out.data_ptr())
+    order = renderers[0].shard_order(nranks)
+    if depth:
+        renderers[0].composite_over_depth_device(layers.data_ptr(), dlayers.data_ptr(), nranks, order, npix, out.data_ptr(), dout.data_ptr())
+    else:
+        renderers[0].composite_over_device(layers.data_ptr(), nranks, order, npix, out.data_ptr())
     torch.cuda.synchronize(dev)
-    return out.view(h, w, 4)
+    return (out.view(h, w, 4), dout.view(h, w)) if depth else out.view(h, w, 4)
