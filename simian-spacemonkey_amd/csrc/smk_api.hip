@@ -1,4 +1,5 @@
-// smk_api.hip -- the C ABI (include/smk.h): context, HBM layout, host-side setup, launches.
+// smk_api.hip -- the C ABI (include/smk.h): context, HBM layout, host-side setup, statistics, slice quads and the sort-last
+// merge.  A frame is smk_frame.hip's; the host side of shadows is smk_shadow_plan.hip's.
 // Product code: no CPU rendering path exists here; without a HIP device every entry fails.
 #include <math.h>
 #include <stdio.h>
@@ -120,8 +121,7 @@ extern "C" smk_ctx *smk_create(int device_ordinal, int *err) {
   }
   smk_ctx *c = new smk_ctx();
   c->device = device_ordinal;
-  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-      false) {
+  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
     g_create_err = "smk_create: stream/event creation failed";
     delete c;
     if (err) *err = 4;
@@ -171,20 +171,7 @@ extern "C" void smk_destroy(smk_ctx *c) {
   void *ptrs[] = {c->d_light_hist, c->d_shadow_entries, c->d_shadow_exports, c->d_shadow_barrier, c->d_tf_raw, c->d_tlut, c->d_tf_h, c->d_tf3d, c->d_tf3d_occ, c->d_noise, c->d_out, c->d_depth, c->d_light[0], c->d_light[1]};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
-  if (c->slab.h_status) (void)hipHostFree(c->slab.h_status);
-  if (c->slab.d_diag) (void)hipFree(c->slab.d_diag);
-  if (c->slab.d_order) (void)hipFree(c->slab.d_order);
-  if (c->slab.d_pticks) (void)hipFree(c->slab.d_pticks);
-  if (c->slab.h_pticks) (void)hipHostFree(c->slab.h_pticks);
-  if (c->slab.d_seg) (void)hipFree(c->slab.d_seg);
-  for (int k = 0; k < 4; ++k) {
-    if (c->slab.h_order[k]) (void)hipHostFree(c->slab.h_order[k]);
-    if (c->slab.order_ev[k]) (void)hipEventDestroy(c->slab.order_ev[k]);
-  }
-  if (c->slab.d_trace) (void)hipFree(c->slab.d_trace);
-  if (c->slab.d_ticks) (void)hipFree(c->slab.d_ticks);
-  if (c->slab.h_ticks) (void)hipHostFree(c->slab.h_ticks);
-  if (c->slab.ticks_ev) (void)hipEventDestroy(c->slab.ticks_ev);
+  smk_slab_free(&c->slab);
   for (hipEvent_t e : c->tev0) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->tev1) (void)hipEventDestroy(e);
   if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -246,9 +233,7 @@ static void shard_box(const int N[3], int rank, int nranks, int g0[3], int g1[3]
   }
 }
 
-static void shard_region_of(const smk_ctx *c, int rank, int g0[3], int g1[3]) { shard_box(c->N, rank, c->nranks, g0, g1); }
-
-static void shard_region(const smk_ctx *c, int g0[3], int g1[3]) { shard_region_of(c, c->rank, g0, g1); }
+void smk_shard_region(const smk_ctx *c, int rank, int g0[3], int g1[3]) { shard_box(c->N, rank, c->nranks, g0, g1); }
 
 // whole-volume dims and extent from the brick list (MetaVolume::brick keeps iPos/fPos), and the box this context stores
 int smk_volume_geometry(smk_ctx *c, const char *who, const smk_volume_desc *b, int nb, int nelts, smk_dtype dtype,
@@ -642,7 +627,7 @@ extern "C" int smk_set_perturb(smk_ctx *c, const unsigned char *noise, int n, co
 // ------------------------------------------------------------------------------- host setup
 
 // VolumeRenderer::inverseMatrix (VolumeRenderer.cpp:1096-1131), affine, double
-static void inverse_affine(double inv[16], const double m[16]) {
+void smk_inverse_affine(double inv[16], const double m[16]) {
   double det = m[0] * m[5] * m[10] - m[0] * m[6] * m[9] - m[1] * m[4] * m[10] + m[1] * m[6] * m[8] +
                m[2] * m[4] * m[9] - m[2] * m[5] * m[8];
   inv[0] = (m[5] * m[10] - m[6] * m[9]) / det;
@@ -668,7 +653,7 @@ static void inverse_affine(double inv[16], const double m[16]) {
 // volume (R8kVolRen3D.cpp:1331-1351); voxel coordinate of plane m (front to back) on the ray
 // through pixel (i,j) is fma(m, B_a, A_a) with A,B affine in the pixel's frustum coordinates.
 static int compute_raycoef(smk_ctx *c, smk_raycoef *o, double inv[16]) {
-  inverse_affine(inv, c->mv);
+  smk_inverse_affine(inv, c->mv);
   const double *M = c->mv;
   double f[3] = {c->fsize[0], c->fsize[1], c->fsize[2]};
   double zmin = 1e300, zmax = -1e300;
@@ -722,179 +707,6 @@ extern "C" int smk_get_raycoef(smk_ctx *c, smk_raycoef *out) {
   if (!c->have_volume || !c->have_camera) FAIL(c, "smk_get_raycoef: volume and camera must be set");
   double inv[16];
   return compute_raycoef(c, out, inv);
-}
-
-static double dot3d(const double a[3], const double b[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
-
-// Half-angle slicing set-up (R8kVolRen3D.cpp:296-326; light transform LTWidgetRen.cpp:231-291; light-buffer
-// coordinates R8kVolRen3D.cpp:1664-1676), everything in double, rounded once: slice planes sn . X = tmin + k dc
-// in model space, eye rays X = e + tau (R0 px + R1 py - n R2), light rays from the apex of the light's
-// projection, and the model -> light-buffer map.  The CPU checker (orc_shadow_setup) does the same steps.
-static int compute_shadowcoef(smk_ctx *c, smk_shadowcoef *o) {
-  memset(o, 0, sizeof *o);
-  const double f[3] = {c->fsize[0], c->fsize[1], c->fsize[2]}, N[3] = {(double)c->N[0], (double)c->N[1], (double)c->N[2]};
-  double vd[3] = {(double)c->at[0] - c->eye[0], (double)c->at[1] - c->eye[1], (double)c->at[2] - c->eye[2]};
-  double ld[3] = {-(double)c->light_pos[0], -(double)c->light_pos[1], -(double)c->light_pos[2]};
-  const double vl = sqrt(dot3d(vd, vd)), d0 = sqrt(dot3d(ld, ld));
-  if (!(vl > 0) || !(d0 > 0)) FAIL(c, "smk_render: shadows need eye != at and a light away from the origin");
-  for (int k = 0; k < 3; ++k) {
-    vd[k] /= vl;
-    ld[k] /= d0;
-  }
-  const double vdl = dot3d(vd, ld);
-  if (vdl <= 0)
-    for (int k = 0; k < 3; ++k) vd[k] = -vd[k];
-  double h[3];
-  for (int k = 0; k < 3; ++k) h[k] = (vd[k] - ld[k]) * .5 + ld[k];
-  o->front_to_back = vdl > 0;
-  double xf[16], xinv[16];
-  for (int i = 0; i < 16; ++i) xf[i] = c->xform[i];
-  inverse_affine(xinv, xf);
-  double sn[3];
-  for (int a = 0; a < 3; ++a) sn[a] = xinv[0 + a] * h[0] + xinv[4 + a] * h[1] + xinv[8 + a] * h[2];
-  const double snl = sqrt(dot3d(sn, sn));
-  if (!(snl > 0)) FAIL(c, "smk_render: shadows: degenerate half-way vector");
-  for (int a = 0; a < 3; ++a) sn[a] /= snl;
-  double tmin = 1e300, tmax = -1e300;
-  for (int i = 0; i < 8; ++i) {
-    const double X[3] = {(i & 1) ? f[0] : 0, (i & 2) ? f[1] : 0, (i & 4) ? f[2] : 0};
-    const double t = dot3d(sn, X);
-    if (t < tmin) tmin = t;
-    if (t > tmax) tmax = t;
-  }
-  double dc;
-  int S;
-  if (c->steps > 0) {
-    S = c->steps;
-    dc = (tmax - tmin) / S;
-  } else {
-    const float disf = c->fsize[0] / ((float)c->N[0] * c->sample_rate);  // R8kVolRen3D.cpp:1330
-    dc = disf;
-    S = (int)((tmax - tmin) / dc);
-  }
-  if (S < 0) S = 0;
-  o->nslices = S;
-  double inv[16];
-  inverse_affine(inv, c->mv);
-  const double n = c->clip[0];
-  const double l = c->frustum[0], r = c->frustum[1], b = c->frustum[2], t = c->frustum[3];
-  o->pxs = (float)((r - l) / c->W);
-  o->pxl = (float)l;
-  o->pys = (float)((t - b) / c->H);
-  o->pyl = (float)b;
-  const double R0[3] = {inv[0], inv[1], inv[2]}, R1[3] = {inv[4], inv[5], inv[6]}, R2[3] = {inv[8], inv[9], inv[10]};
-  const double e[3] = {inv[12], inv[13], inv[14]};
-  for (int a = 0; a < 3; ++a) {
-    const double s = N[a] / f[a];
-    o->Ec[a] = (float)(e[a] * s - 0.5);
-    o->Dx[a] = (float)(R0[a] * s);
-    o->Dy[a] = (float)(R1[a] * s);
-    o->Dc[a] = (float)(-n * R2[a] * s);
-  }
-  o->nDx = (float)dot3d(sn, R0);
-  o->nDy = (float)dot3d(sn, R1);
-  o->nDc = (float)(-n * dot3d(sn, R2));
-  o->num0 = (float)(tmin - dot3d(sn, e));
-  o->dnum = (float)dc;
-  // light view: x' = s.q, y' = u.q, z' = 1 - F.q, w = 1 + z'/d0 for a world point q = xform (X - f/2)
-  const double F[3] = {-ld[0], -ld[1], -ld[2]};
-  double sv[3] = {F[1] * 0 - F[2] * 1, F[2] * 0 - F[0] * 0, F[0] * 1 - F[1] * 0};
-  const double sl = sqrt(dot3d(sv, sv));
-  if (!(sl > 1e-12)) FAIL(c, "smk_render: shadows: a light on the y axis has no light transform (gluLookAt with up = y, LTWidgetRen.cpp:262-276)");
-  for (int k = 0; k < 3; ++k) sv[k] /= sl;
-  const double uv[3] = {sv[1] * F[2] - sv[2] * F[1], sv[2] * F[0] - sv[0] * F[2], sv[0] * F[1] - sv[1] * F[0]};
-  double rowx[4], rowy[4], roww[4];
-  for (int a = 0; a < 3; ++a) {
-    const double col[3] = {xf[4 * a + 0], xf[4 * a + 1], xf[4 * a + 2]};
-    rowx[a] = dot3d(sv, col);
-    rowy[a] = dot3d(uv, col);
-    roww[a] = -dot3d(F, col) / d0;
-  }
-  {
-    const double tcol[3] = {xf[12], xf[13], xf[14]};
-    rowx[3] = dot3d(sv, tcol);
-    rowy[3] = dot3d(uv, tcol);
-    roww[3] = 1.0 + (1.0 - dot3d(F, tcol)) / d0;
-    for (int a = 0; a < 3; ++a) {
-      rowx[3] -= rowx[a] * f[a] * .5;
-      rowy[3] -= rowy[a] * f[a] * .5;
-      roww[3] -= roww[a] * f[a] * .5;
-    }
-  }
-  double cx = rowx[3], cy = rowy[3], cw = roww[3];
-  for (int a = 0; a < 3; ++a) {
-    const double sc = f[a] / N[a];
-    o->Xm[a] = (float)(rowx[a] * sc);
-    o->Ym[a] = (float)(rowy[a] * sc);
-    o->Wm[a] = (float)(roww[a] * sc);
-    cx += rowx[a] * sc * .5;
-    cy += rowy[a] * sc * .5;
-    cw += roww[a] * sc * .5;
-  }
-  o->Xm[3] = (float)cx;
-  o->Ym[3] = (float)cy;
-  o->Wm[3] = (float)cw;
-  const double LBf = (double)c->shadow_q * (double)c->shadow_px;
-  o->LB = (int)ceil(LBf);
-  if (o->LB < 1) FAIL(c, "smk_render: shadows: empty light buffer");
-  o->lscale = (float)(.85 * LBf);
-  o->lbias = (float)(.5 * LBf);
-  o->las = (float)(1.0 / (.85 * LBf));
-  o->lal = (float)(-.5 / .85);
-  double apex[3], gx[3], gy[3], gc[3];
-  for (int a = 0; a < 3; ++a) {
-    apex[a] = xinv[12 + a] + f[a] * .5;
-    gx[a] = gy[a] = gc[a] = 0;
-    for (int k = 0; k < 3; ++k) {
-      apex[a] += xinv[4 * k + a] * F[k] * (1.0 + d0);
-      gx[a] += xinv[4 * k + a] * sv[k];
-      gy[a] += xinv[4 * k + a] * uv[k];
-      gc[a] += xinv[4 * k + a] * F[k] * -d0;
-    }
-  }
-  for (int a = 0; a < 3; ++a) {
-    const double s = N[a] / f[a];
-    o->Lc[a] = (float)(apex[a] * s - 0.5);
-    o->Gx[a] = (float)(gx[a] * s);
-    o->Gy[a] = (float)(gy[a] * s);
-    o->Gc[a] = (float)(gc[a] * s);
-  }
-  o->nGx = (float)dot3d(sn, gx);
-  o->nGy = (float)dot3d(sn, gy);
-  o->nGc = (float)dot3d(sn, gc);
-  o->lnum0 = (float)(tmin - dot3d(sn, apex));
-  o->ldnum = (float)dc;
-  return 0;
-}
-
-extern "C" int smk_set_shadow(smk_ctx *c, int on, int buffer_px, float quality) {
-  if (!c) return 1;
-  if (on && (buffer_px < 1 || buffer_px > 8192 || !(quality > 0.0f) || quality > 1.0f))
-    FAIL(c, "smk_set_shadow: buffer_px in 1..8192 and quality in (0,1] (gluvvui.cpp:156-167 clamps the qualities to [.1,1])");
-  c->shadow_on = on ? 1 : 0;
-  if (on) {
-    c->shadow_px = buffer_px;
-    c->shadow_q = quality;
-  }
-  return 0;
-}
-
-extern "C" int smk_get_shadowcoef(smk_ctx *c, smk_shadowcoef *out) {
-  if (!c || !out) return 1;
-  if (!c->have_volume || !c->have_camera) FAIL(c, "smk_get_shadowcoef: volume and camera must be set");
-  return compute_shadowcoef(c, out);
-}
-
-extern "C" int smk_get_light_buffer(smk_ctx *c, float *rgba_out, int *lb_out) {
-  if (!c) return 1;
-  HIPCHK(c, hipSetDevice(c->device));
-  if (!c->light_lb || !c->d_light_last) FAIL(c, "smk_get_light_buffer: no frame with shadows has been rendered");
-  if (lb_out) *lb_out = c->light_lb;
-  if (rgba_out) {
-    HIPCHK(c, hipDeviceSynchronize());
-    HIPCHK(c, hipMemcpy(rgba_out, c->d_light_last, (size_t)c->light_lb * c->light_lb * 16, hipMemcpyDeviceToHost));
-  }
-  return 0;
 }
 
 static void normalize3(float v[3]) {
@@ -1152,7 +964,7 @@ extern "C" int smk_get_tf2d_effective(smk_ctx *c, unsigned char *out, float *rat
 }
 
 // the shards in BSP order seen from a point (voxel index space): per split axis the half holding the point comes first
-static void bsp_order(const smk_ctx *c, const double pos[3], int *order) {
+void smk_bsp_order(const smk_ctx *c, const double pos[3], int *order) {
   int nearbit[3];
   for (int a = 0; a < 3; ++a) nearbit[a] = pos[a] >= (double)(c->N[a] / 2) - 0.5 ? 1 : 0;
   int nbits = 0;
@@ -1172,28 +984,15 @@ extern "C" int smk_shard_order(smk_ctx *c, int *order) {
   if (!c || !order) return 1;
   if (!c->have_volume || !c->have_camera) FAIL(c, "smk_shard_order: volume and camera must be set");
   double inv[16];
-  inverse_affine(inv, c->mv);
+  smk_inverse_affine(inv, c->mv);
   // eye in voxel index space
   double e[3];
   for (int a = 0; a < 3; ++a) e[a] = inv[12 + a] * c->N[a] / c->fsize[a] - 0.5;
-  bsp_order(c, e, order);
+  smk_bsp_order(c, e, order);
   return 0;
 }
 
-// The light's BSP order: from the apex of the light rays (smk_shadowcoef Lc, voxel index space), the point every light-buffer
-// texel's ray starts from -- a ray crosses the shards' convex boxes in this order (R8kVolRen3D.cpp:582-679 draws the bricks of
-// a shadowed volume one after another against one light buffer)
-extern "C" int smk_shard_light_order(smk_ctx *c, int *order) {
-  if (!c || !order) return 1;
-  if (!c->have_volume || !c->have_camera) FAIL(c, "smk_shard_light_order: volume and camera must be set");
-  smk_shadowcoef sc;
-  if (compute_shadowcoef(c, &sc)) return 1;
-  const double l[3] = {sc.Lc[0], sc.Lc[1], sc.Lc[2]};
-  bsp_order(c, l, order);
-  return 0;
-}
-
-// ------------------------------------------------------------------------------- render
+// ------------------------------------------------------------------------------- options and statistics
 
 extern "C" int smk_set_option(smk_ctx *c, const char *key, int value) {
   if (!c || !key) return 1;
@@ -1240,65 +1039,11 @@ extern "C" int smk_set_option(smk_ctx *c, const char *key, int value) {
   return 0;
 }
 
-extern "C" int smk_timing_reset(smk_ctx *c) {
-  if (!c) return 1;
-  c->tcount = 0;
-  return 0;
-}
-
-// average render-kernel duration over the frames recorded since smk_timing_reset (at most the
-// last SMK_TIMING_RING); synchronises the device
-extern "C" int smk_timing_read(smk_ctx *c, float *avg_ms, int *nframes) {
-  if (!c) return 1;
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipDeviceSynchronize());
-  int n = (int)std::min<long long>(c->tcount, SMK_TIMING_RING);
-  double sum = 0;
-  for (int i = 0; i < n; ++i) {
-    float ms = 0;
-    HIPCHK(c, hipEventElapsedTime(&ms, c->tev0[i], c->tev1[i]));
-    sum += ms;
-  }
-  if (avg_ms) *avg_ms = n ? (float)(sum / n) : 0.f;
-  if (nframes) *nframes = n;
-  return 0;
-}
-
-// Slice-ring kernel error words -> failed frames (the kernel never hangs and never returns a frame
-// built from unloaded data silently).  Every frame has its own word, SMK_STATUS_RING of them in turn.
-// A caller that keeps frames in flight asks per frame (smk_frame_failed, after synchronising with it)
-// and renders a flagged frame again; a flag nobody asked about fails the NEXT render call loudly.
-// The status word of frame `id` (slot id % SMK_STATUS_RING), consumed: 0 = none.  Words carry the id of the frame that wrote
-// them (a slice-ring frame may write late, into a slot that has since been handed to a younger frame): one of ANOTHER frame
-// is counted as that frame's failure and left alone for whoever owns it -- or dropped when that frame is out of the ring.
-static int take_status(smk_ctx *c, long long id) {
-  if (!c->slab.h_status || id <= 0) return 0;
-  volatile int *w = (volatile int *)c->slab.h_status + (int)(id % SMK_STATUS_RING);
-  const int st = *w;
-  if (!st) return 0;
-  const long long tag = (st >> 8) & 0x7fffff;
-  if (tag != (id & 0x7fffff)) {
-    // a late word of an older frame of this slot: nobody can be told about that frame any more
-    if (((id - tag) & 0x7fffff) % SMK_STATUS_RING == 0 && tag != 0) {
-      *w = 0;
-      ++c->slab_failures;
-      ++c->slab_lost;
-    }
-    return 0;
-  }
-  *w = 0;
-  ++c->slab_failures;
-  // not again soon: in auto mode that configuration is the gather kernel's for a while
-  if (c->opt_kernel == 0 && c->last_slab_sig) c->tune_choice[c->last_slab_sig] = {1, c->frame_id + 256};
-  return st & 0xff;
-}
-
-static int build_params(smk_ctx *c, RenderParams &P, hipStream_t s);
 extern "C" int smk_get_brick_flags(smk_ctx *c, unsigned char *flags_out, int *nb_out, int *in_use_out) {
   if (!c || !nb_out) return 1;
   HIPCHK(c, hipSetDevice(c->device));
   RenderParams P;
-  if (build_params(c, P, c->stream)) return 1;
+  if (smk_build_params(c, P, c->stream)) return 1;
   HIPCHK(c, hipDeviceSynchronize());
   for (int a = 0; a < 3; ++a) nb_out[a] = c->nbr[a];
   const BrickSet *B = c->tf_mode == 1 && c->tf_cur >= 0 ? &c->tfv[c->tf_cur].br : c->tf_mode == 2 ? &c->br3 : nullptr;
@@ -1310,28 +1055,28 @@ extern "C" int smk_get_brick_flags(smk_ctx *c, unsigned char *flags_out, int *nb
   return 0;
 }
 
-static const char *status_text(int st) {
-  return st == 1 ? "a streaming kernel reported a producer/consumer time-out" : st == 2 ? "the slice-ring kernel reported a window outside its host bound"
-         : st == 3 ? "the column-stream kernel reported a job whose rays do not fit its lanes or its list" : "the column-stream kernel reported a ray it cannot list";
-}
-
-// frame `id` was flagged and nobody has asked about it: the call fails
-static int check_frame_status(smk_ctx *c, long long id) {
-  const int st = take_status(c, id);
-  if (st) FAIL(c, "%s (status %d, frame %lld); frame invalid", status_text(st), st, id);
+// n words a kernel of the latest frame wrote (ticks, counters), read once the device has finished it; synchronises
+template <class T>
+static int read_back(smk_ctx *c, T *h, const T *d, size_t n) {
+  HIPCHK(c, hipDeviceSynchronize());
+  HIPCHK(c, hipMemcpy(h, d, n * sizeof(T), hipMemcpyDeviceToHost));
   return 0;
 }
 
-extern "C" long long smk_last_frame_id(smk_ctx *c) { return c ? c->frame_id : 0; }
-
-extern "C" int smk_frame_failed(smk_ctx *c, long long frame_id) {
-  if (!c) return 1;
-  if (frame_id <= 0 || frame_id > c->frame_id || frame_id + SMK_STATUS_RING <= c->frame_id) return -1;  // never enqueued, or out of the ring: unknown
-  return take_status(c, frame_id) ? 1 : 0;
+// a 64-bit device counter: zeroed, counted into by launch(d) on the context's stream, copied back; synchronises the stream
+template <class Launch>
+static int count_on_device(smk_ctx *c, Launch launch, double *out) {
+  unsigned long long *d = nullptr, h = 0;
+  HIPCHK(c, hipMalloc((void **)&d, 8));
+  hipError_t e = hipMemsetAsync(d, 0, 8, c->stream);
+  if (e == hipSuccess) e = launch(d);
+  if (e == hipSuccess) e = hipMemcpyAsync(&h, d, 8, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  (void)hipFree(d);
+  HIPCHK(c, e);
+  *out = (double)h;
+  return 0;
 }
-
-static int shadow_setup(smk_ctx *c, RenderParams &P, smk_shadowcoef &sc, SmkShadowShard *S, int *halo_need);
-static int shadow_light_owned(smk_ctx *c, RenderParams &P, smk_shadowcoef &sc, float olo[3], float ohi[3]);
 
 extern "C" int smk_get_stat(smk_ctx *c, const char *name, double *value) {
   if (!c || !name || !value) return 1;
@@ -1343,10 +1088,7 @@ extern "C" int smk_get_stat(smk_ctx *c, const char *name, double *value) {
   for (int k = 0; k < 16; ++k)
     if (!strcmp(name, diag_names[k])) {
       float v = 0.f;
-      if (c->slab.d_diag) {
-        HIPCHK(c, hipDeviceSynchronize());
-        HIPCHK(c, hipMemcpy(&v, c->slab.d_diag + k, 4, hipMemcpyDeviceToHost));
-      }
+      if (c->slab.d_diag && read_back(c, &v, c->slab.d_diag + k, 1)) return 1;
       *value = v;
       return 0;
     }
@@ -1354,17 +1096,8 @@ extern "C" int smk_get_stat(smk_ctx *c, const char *name, double *value) {
     RenderParams P;
     smk_shadowcoef sc;
     float olo[3], ohi[3];
-    if (shadow_light_owned(c, P, sc, olo, ohi)) return 1;
-    unsigned long long *d = nullptr, h = 0;
-    HIPCHK(c, hipMalloc((void **)&d, 8));
-    hipError_t e = hipMemsetAsync(d, 0, 8, c->stream);
-    if (e == hipSuccess) e = smk_launch_shadow_count_light(P, sc, olo, ohi, d, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&h, d, 8, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
-    HIPCHK(c, e);
-    *value = (double)h;
-    return 0;
+    if (smk_shadow_light_owned(c, P, sc, olo, ohi)) return 1;
+    return count_on_device(c, [&](unsigned long long *d) { return smk_launch_shadow_count_light(P, sc, olo, ohi, d, c->stream); }, value);
   }
   if (!strcmp(name, "slab_status")) {  // status word of the latest frame (0 = ok); synchronises
     HIPCHK(c, hipDeviceSynchronize());
@@ -1386,9 +1119,8 @@ extern "C" int smk_get_stat(smk_ctx *c, const char *name, double *value) {
     *value = 1.0;
     const int nt = c->slab.ticks_n_last;
     if (c->last_kernel == 2 && c->slab.d_ticks && nt > 0) {
-      HIPCHK(c, hipDeviceSynchronize());
       std::vector<unsigned> h((size_t)2 * nt);
-      HIPCHK(c, hipMemcpy(h.data(), c->slab.d_ticks + nt, (size_t)2 * nt * 4, hipMemcpyDeviceToHost));
+      if (read_back(c, h.data(), c->slab.d_ticks + nt, h.size())) return 1;
       double st = 0, pl = 0;
       for (int t = 0; t < nt; ++t) {
         st += h[t];
@@ -1403,9 +1135,8 @@ extern "C" int smk_get_stat(smk_ctx *c, const char *name, double *value) {
     *value = 0.0;
     const int nt = c->slab.ticks_n_last;
     if (c->last_kernel == 2 && c->slab.d_ticks && nt > 0) {
-      HIPCHK(c, hipDeviceSynchronize());
       std::vector<unsigned> h((size_t)nt);
-      HIPCHK(c, hipMemcpy(h.data(), c->slab.d_ticks, (size_t)nt * 4, hipMemcpyDeviceToHost));
+      if (read_back(c, h.data(), c->slab.d_ticks, h.size())) return 1;
       double mx = 0, sum = 0;
       for (int t = 0; t < nt; ++t) {
         // (a split tile's word is the sum over its pieces: the longest workgroup is taken as an equal share)
@@ -1424,52 +1155,33 @@ extern "C" int smk_get_stat(smk_ctx *c, const char *name, double *value) {
     if (!strcmp(name, "cols_config")) { *value = c->cols.last; return 0; }
     if (!strcmp(name, "cols_jobs")) { *value = c->cols.njobs_last; return 0; }
     if (!strcmp(name, "cols_stream_bytes")) { *value = c->cols.last_stream_bytes; return 0; }
-    if (!strcmp(name, "cols_setup_ms_sum") || !strcmp(name, "cols_rays")) {
-      const int nj = c->cols.njobs_last;
+    if (!strcmp(name, "cols_job_ms_max") || !strcmp(name, "cols_job_ms_sum") || !strcmp(name, "cols_setup_ms_sum") || !strcmp(name, "cols_rays")) {
+      const int nj = c->cols.njobs_last, part = name[5] == 'j' ? 0 : name[5] == 's' ? 1 : 2;  // d_ticks: [3][nj] job, set-up ticks, rays
       if (c->last_kernel == 4 && c->cols.d_ticks && nj > 0) {
-        HIPCHK(c, hipDeviceSynchronize());
         std::vector<unsigned> h((size_t)nj);
-        HIPCHK(c, hipMemcpy(h.data(), c->cols.d_ticks + (size_t)nj * (name[5] == 's' ? 1 : 2), (size_t)nj * 4, hipMemcpyDeviceToHost));
-        double sum = 0;
-        for (int t = 0; t < nj; ++t) sum += h[t];
-        *value = name[5] == 's' ? sum * 1e-5 : sum;
-      }
-      return 0;
-    }
-    if (!strcmp(name, "cols_job_ms_max") || !strcmp(name, "cols_job_ms_sum")) {
-      const int nj = c->cols.njobs_last;
-      if (c->last_kernel == 4 && c->cols.d_ticks && nj > 0) {
-        HIPCHK(c, hipDeviceSynchronize());
-        std::vector<unsigned> h((size_t)nj);
-        HIPCHK(c, hipMemcpy(h.data(), c->cols.d_ticks, (size_t)nj * 4, hipMemcpyDeviceToHost));
+        if (read_back(c, h.data(), c->cols.d_ticks + (size_t)nj * part, h.size())) return 1;
         double mx = 0, sum = 0;
-        for (int t = 0; t < nj; ++t) {
-          mx = std::max(mx, (double)h[t]);
-          sum += h[t];
+        for (unsigned v : h) {
+          mx = std::max(mx, (double)v);
+          sum += v;
         }
-        *value = (name[12] == 'm' ? mx : sum) * 1e-5;
+        *value = part == 2 ? sum : (name[12] == 'm' ? mx : sum) * 1e-5;  // (100 MHz ticks)
       }
       return 0;
     }
     static const char *cn[8] = {"cols_samples", "cols_visible", "cols_slices", "cols_segments", "cols_iters", "cols_active_lanes", "cols_switch_iters", "cols_switch_lanes"};
     for (int k = 0; k < 8; ++k)
       if (!strcmp(name, cn[k])) {
-        if (c->cols.d_counts && c->cols.want_counts) {
-          HIPCHK(c, hipDeviceSynchronize());
-          unsigned long long v = 0;
-          HIPCHK(c, hipMemcpy(&v, c->cols.d_counts + k, 8, hipMemcpyDeviceToHost));
-          *value = (double)v;
-        }
+        unsigned long long v = 0;
+        if (c->cols.d_counts && c->cols.want_counts && read_back(c, &v, c->cols.d_counts + k, 1)) return 1;
+        *value = (double)v;
         return 0;
       }
     FAIL(c, "smk_get_stat: unknown name '%s'", name);
   }
   if (!strcmp(name, "slab_split_tiles")) { *value = c->slab.nsplit_last; return 0; }
   if (!strcmp(name, "slab_workgroups")) { *value = c->slab.nblocks_last; return 0; }
-  if (!strcmp(name, "slab_retries")) {
-    *value = (double)c->slab_retries;
-    return 0;
-  }
+  if (!strcmp(name, "slab_retries")) { *value = (double)c->slab_retries; return 0; }
   FAIL(c, "smk_get_stat: unknown name '%s'", name);
 }
 
@@ -1481,9 +1193,8 @@ extern "C" int smk_get_trace(smk_ctx *c, unsigned *out, int cap_records, int *nr
     const int nt = c->last_kernel == 2 && c->slab.d_ticks ? c->slab.ticks_n_last : 0;
     *nrecords = nt;
     if (out && nt > 0) {
-      HIPCHK(c, hipDeviceSynchronize());
       std::vector<unsigned> h((size_t)nt * 5);
-      HIPCHK(c, hipMemcpy(h.data(), c->slab.d_ticks, (size_t)nt * 20, hipMemcpyDeviceToHost));
+      if (read_back(c, h.data(), c->slab.d_ticks, h.size())) return 1;
       for (int t = 0; t < std::min(cap_records, nt); ++t) {
         unsigned *r = out + (size_t)t * 8;
         r[0] = h[(size_t)3 * nt + t];
@@ -1496,10 +1207,7 @@ extern "C" int smk_get_trace(smk_ctx *c, unsigned *out, int cap_records, int *nr
     return 0;
   }
   *nrecords = c->slab.d_trace ? c->slab.trace_n : 0;
-  if (out && *nrecords > 0) {
-    HIPCHK(c, hipDeviceSynchronize());
-    HIPCHK(c, hipMemcpy(out, c->slab.d_trace, (size_t)std::min(cap_records, *nrecords) * 32, hipMemcpyDeviceToHost));
-  }
+  if (out && *nrecords > 0 && read_back(c, out, c->slab.d_trace, (size_t)std::min(cap_records, *nrecords) * 8)) return 1;
   return 0;
 }
 
@@ -1507,33 +1215,16 @@ extern "C" int smk_count_samples(smk_ctx *c, double *in_volume) {
   if (!c || !in_volume) return 1;
   HIPCHK(c, hipSetDevice(c->device));
   RenderParams P;
-  if (build_params(c, P, c->stream)) return 1;
-  // a frame with shadows samples the half-angle slices in its eye box (shadow_setup)
+  if (smk_build_params(c, P, c->stream)) return 1;
+  // a frame with shadows samples the half-angle slices in its eye box (smk_shadow_setup)
   smk_shadowcoef sc;
-  if (c->shadow_on && c->tf_mode != 0 && !P.pert_on && !c->region_on && shadow_setup(c, P, sc, nullptr, nullptr)) return 1;
-  unsigned long long *d = nullptr, h = 0;
-  HIPCHK(c, hipMalloc((void **)&d, 8));
-  hipError_t e = hipMemsetAsync(d, 0, 8, c->stream);
-  if (e == hipSuccess) e = smk_launch_count_inside(P, d, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(&h, d, 8, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(d);
-  HIPCHK(c, e);
-  *in_volume = (double)h;
-  return 0;
-}
-
-extern "C" int smk_last_frame_info(smk_ctx *c, int *kernel, float *ms, double *alg_bytes) {
-  if (!c) return 1;
-  if (kernel) *kernel = c->last_kernel;
-  if (ms) *ms = c->last_ms;
-  if (alg_bytes) *alg_bytes = c->last_alg_bytes;
-  return 0;
+  if (c->shadow_on && c->tf_mode != 0 && !P.pert_on && !c->region_on && smk_shadow_setup(c, P, sc, nullptr, nullptr)) return 1;
+  return count_on_device(c, [&](unsigned long long *d) { return smk_launch_count_inside(P, d, c->stream); }, in_volume);
 }
 
 // The box of voxels g0..g1 in voxel coordinates, [g0 - .5, g1 - .5) per axis (closed where top[a]: the volume's upper face),
 // cut by an orthogonal clip plane and the sub-box.  A shard's region; with 0..N the whole volume's box.
-static void region_box(const smk_ctx *c, const int g0[3], const int g1[3], float lo[3], float hi[3], int top[3]) {
+void smk_region_box(const smk_ctx *c, const int g0[3], const int g1[3], float lo[3], float hi[3], int top[3]) {
   for (int a = 0; a < 3; ++a) {
     lo[a] = (float)g0[a] - 0.5f;
     hi[a] = (float)g1[a] - 0.5f;
@@ -1565,7 +1256,7 @@ static void region_box(const smk_ctx *c, const int g0[3], const int g1[3], float
     }
 }
 
-static int build_params(smk_ctx *c, RenderParams &P, hipStream_t s) {
+int smk_build_params(smk_ctx *c, RenderParams &P, hipStream_t s) {
   if (!c->have_volume) FAIL(c, "smk_render: no volume uploaded");
   if (!c->have_camera) FAIL(c, "smk_render: no camera set");
   if (c->tf_mode < 0) FAIL(c, "smk_render: no transfer function set");
@@ -1582,7 +1273,7 @@ static int build_params(smk_ctx *c, RenderParams &P, hipStream_t s) {
     P.D[a] = c->D[a];
     P.invN[a] = 1.0f / (float)c->N[a];
   }
-  region_box(c, c->g0, c->g1, P.lo, P.hi, P.top);
+  smk_region_box(c, c->g0, c->g1, P.lo, P.hi, P.top);
   for (int a = 0; a < 3; ++a) P.hin[a] = P.top[a] ? P.hi[a] : nextafterf(P.hi[a], -INFINITY);
   // free clip plane: eye-space plane -> voxel coordinates.  eye = MV * model, model = (p + 1/2)/N * fSize
   // (same operations in the same order as the CPU checker's orc_clip_plane_voxel)
@@ -1718,7 +1409,7 @@ __global__ __launch_bounds__(256) void smk_k_xmajor(const V *src, V *dst, int Dx
   }
 }
 
-static int make_xmajor_copy(smk_ctx *c) {
+int smk_make_xmajor_copy(smk_ctx *c) {
   if (c->d_vox_x) return 0;
   TimeStep &T = c->ts[c->ts_cur];  // (the current step's copy: made once per upload of the step)
   if (!T.vox_x) HIPCHK(c, hipMalloc(&T.vox_x, c->vox_bytes));
@@ -1737,613 +1428,10 @@ static int make_xmajor_copy(smk_ctx *c) {
   return 0;
 }
 
-static int shade_kind_of(const smk_ctx *c) {
+int smk_shade_kind(const smk_ctx *c) {
   if (c->tf_mode == 0 || !c->have_normals) return 0;
   if (c->shade == SMK_SHADE_R8K_DIFF || c->shade == SMK_SHADE_R8K_DSPEC) return 1;
   if (c->shade == SMK_SHADE_NV20_DIFF || c->shade == SMK_SHADE_NV20_DSPEC) return 2;
-  return 0;
-}
-
-// Margin m of a shard with shadows ("Shadows on shards"): an eye sample p of slice k looks the light buffer up
-// bilinearly at p's light-buffer position, i.e. the (up to) 4 texels whose centres lie less than one texel from it on each
-// axis; each such texel's slice-k sample lies on slice k's plane near p, off by the texel offset times the Jacobian of the
-// map (buffer position -> point of the plane), here (a, b) -> Lc + lnum G(a, b) / nG(a, b).  Its largest size over a grid
-// of the region's box, in voxels per texel, with half again as much for the curvature between grid points and the float
-// chains, rounded up: the light samples rank j must march itself lie within m voxels of its region.
-static int shadow_margin(const smk_shadowcoef &sc, const int g0[3], const int g1[3]) {
-  double worst = 0.0;
-  const int n = 8;
-  for (int iz = 0; iz <= n; ++iz)
-    for (int iy = 0; iy <= n; ++iy)
-      for (int ix = 0; ix <= n; ++ix) {
-        const int ii[3] = {ix, iy, iz};
-        double p[3];
-        for (int a = 0; a < 3; ++a) p[a] = (double)g0[a] - 0.5 + (double)(g1[a] - g0[a]) * ii[a] / n;
-        const double lw = sc.Wm[0] * p[0] + sc.Wm[1] * p[1] + sc.Wm[2] * p[2] + sc.Wm[3];
-        if (!(fabs(lw) > 1e-30)) return 1 << 20;
-        const double lx = (sc.Xm[0] * p[0] + sc.Xm[1] * p[1] + sc.Xm[2] * p[2] + sc.Xm[3]) / lw * sc.lscale + sc.lbias;
-        const double ly = (sc.Ym[0] * p[0] + sc.Ym[1] * p[1] + sc.Ym[2] * p[2] + sc.Ym[3]) / lw * sc.lscale + sc.lbias;
-        const double a = lx * sc.las + sc.lal, b = ly * sc.las + sc.lal;  // (texel x has a = fma(x + .5, las, lal))
-        double G[3], d[3], gg = 0.0, dg = 0.0;
-        for (int q = 0; q < 3; ++q) {
-          G[q] = a * sc.Gx[q] + b * sc.Gy[q] + sc.Gc[q];
-          d[q] = p[q] - sc.Lc[q];
-          gg += G[q] * G[q];
-          dg += d[q] * G[q];
-        }
-        const double nG = a * sc.nGx + b * sc.nGy + sc.nGc;
-        if (!(gg > 0.0) || !(fabs(nG) > 1e-30)) return 1 << 20;
-        const double w = dg / gg;  // p = Lc + w G
-        for (int q = 0; q < 3; ++q) {
-          const double ja = w * (sc.Gx[q] - G[q] * sc.nGx / nG), jb = w * (sc.Gy[q] - G[q] * sc.nGy / nG);
-          worst = std::max(worst, (double)sc.las * (fabs(ja) + fabs(jb)));
-        }
-      }
-  const double m = ceil(1.5 * worst + 0.5);
-  return m > (double)(1 << 20) || m != m ? 1 << 20 : std::max(1, (int)m);
-}
-
-// A frame with shadows: the half-angle slices (compute_shadowcoef), the eye rays over them in P.sh, and the boxes.  On the
-// whole volume: a light sample lies in the volume's closed box (what an orthogonal clip plane leaves of it), an eye sample in
-// that box widened by SMK_SHADOW_BOX_EPS.  On a shard the outer faces keep that treatment and the inner ones the half-open
-// rule of a shard's region (a sample on the split plane belongs to the upper half), so that every light sample and every eye
-// sample of the unsharded frame belongs to exactly one rank; the light march's bracket and sample set stay the whole volume's
-// (P.sh.llo / lhi).  With S: the phase-1 / phase-2 parameters of the shard (SmkShadowShard), *halo_need = m + 1.
-static int shadow_setup(smk_ctx *c, RenderParams &P, smk_shadowcoef &sc, SmkShadowShard *S, int *halo_need) {
-  if (compute_shadowcoef(c, &sc)) return 1;
-  // the eye rays over the half-angle slices, planes counted from the eye (smk_internal.h SmkShadowRays)
-  SmkShadowRays &h = P.sh;
-  memset(&h, 0, sizeof h);
-  h.on = 1;
-  for (int a = 0; a < 3; ++a) { h.Ec[a] = sc.Ec[a]; h.Dc[a] = sc.Dc[a]; h.Dx[a] = sc.Dx[a]; h.Dy[a] = sc.Dy[a]; }
-  h.nDc = sc.nDc; h.nDx = sc.nDx; h.nDy = sc.nDy;
-  if (sc.front_to_back) { h.numA = fmaf(1.0f, sc.dnum, sc.num0); h.dB = sc.dnum; h.k0 = 1; h.dk = 1; }
-  else { h.numA = fmaf((float)sc.nslices, sc.dnum, sc.num0); h.dB = -sc.dnum; h.k0 = sc.nslices; h.dk = -1; }
-  h.LB = sc.LB;
-  for (int q = 0; q < 4; ++q) { h.Xm[q] = sc.Xm[q]; h.Ym[q] = sc.Ym[q]; h.Wm[q] = sc.Wm[q]; }
-  h.lscale = sc.lscale; h.lbias = sc.lbias;
-  {
-    smk_raycoef &rc = P.rc;
-    memset(&rc, 0, sizeof rc);
-    rc.pxs = sc.pxs; rc.pxl = sc.pxl; rc.pys = sc.pys; rc.pyl = sc.pyl;
-    rc.nplanes = sc.nslices;
-    // (Bc: the central ray's step, which the kernel choice below keys its measurements on)
-    const double nDc = (double)sc.nDc != 0.0 ? (double)sc.nDc : 1.0;
-    for (int a = 0; a < 3; ++a) rc.Bc[a] = (float)((double)h.dB / nDc * (double)sc.Dc[a]);
-  }
-  // The last slice lies ON the volume's far corner -- on a whole face when the half-way vector is a volume axis (a light at
-  // the eye) -- where a sample's coordinate, the end of an fma chain, lands on either side of the face by rounding.  The
-  // reference draws that slice (a polygon clipped against the box keeps its boundary); the eye pass's membership test is
-  // therefore 2^-10 voxels wide of the box (clamp-to-edge fetches: the value at the face).  The CPU checker does the same.
-  // Clip planes (round 3): both passes draw the same clipped slice polygons in the reference (volShadow slices the box
-  // setupClips left; glClipPlane stays enabled), so a light ray's sample must lie in the same box (closed, no slack: its
-  // last slice gets no special treatment in rounds 1-2 either) and on the kept side of the free plane.
-  float wlo[3], whi[3];
-  int wtop[3];
-  const int z0[3] = {0, 0, 0};
-  region_box(c, z0, c->N, wlo, whi, wtop);
-  float olo[3], ohi[3];
-  for (int a = 0; a < 3; ++a) {
-    const bool inner_lo = c->g0[a] > 0 && P.lo[a] == (float)c->g0[a] - 0.5f, inner_hi = !P.top[a];
-    h.llo[a] = wlo[a];
-    h.lhi[a] = whi[a];
-    olo[a] = P.lo[a];
-    ohi[a] = inner_hi ? nextafterf(P.hi[a], -INFINITY) : P.hi[a];
-    if (!inner_lo) P.lo[a] -= SMK_SHADOW_BOX_EPS;
-    if (inner_hi) P.hin[a] = nextafterf(P.hi[a], -INFINITY);
-    else {
-      P.hi[a] += SMK_SHADOW_BOX_EPS;
-      P.hin[a] = P.hi[a];
-      P.top[a] = 1;
-    }
-  }
-  if (!S) return 0;
-  memset(S, 0, sizeof *S);
-  S->nranks = c->nranks;
-  S->rank = c->rank;
-  for (int a = 0; a < 3; ++a) { S->olo[a] = olo[a]; S->ohi[a] = ohi[a]; }
-  int m_own = 0;
-  for (int j = 0; j < c->nranks; ++j) {
-    int g0[3], g1[3];
-    shard_region_of(c, j, g0, g1);
-    const int m = shadow_margin(sc, g0, g1);
-    if (j == c->rank) m_own = m;
-    for (int a = 0; a < 3; ++a) {
-      S->glo[j][a] = (float)((double)g0[a] - 0.5 - m);
-      S->ghi[j][a] = (float)((double)g1[a] - 0.5 + m);
-    }
-  }
-  for (int a = 0; a < 3; ++a) {
-    S->xlo[a] = S->glo[c->rank][a] - 0.25f;
-    S->xhi[a] = S->ghi[c->rank][a] + 0.25f;
-  }
-  const double l[3] = {sc.Lc[0], sc.Lc[1], sc.Lc[2]};
-  bsp_order(c, l, S->order);
-  if (halo_need) *halo_need = m_own + 1;
-  return 0;
-}
-
-// what a frame with shadows cannot be combined with (the same reasons as smk_render's)
-static int shadow_refusals(smk_ctx *c, const RenderParams &P) {
-  const int sk = shade_kind_of(c);
-  if (c->tf_mode == 0) FAIL(c, "smk_render: shadows need a 2-D or 3-D transfer function (the 1-D table renderer has no shadow mode)");
-  if (sk == 2) FAIL(c, "smk_render: shadows are implemented for R8k shading or none (NV20 combiners: no shadow mode in NV20VolRen3D)");
-  if (c->nranks > 1 && (!c->opt_shadow_march || (c->opt_lockstep & 256)))
-    FAIL(c, "smk_render: shadows need the whole volume on one GPU with option shadow_march 0 or shadow_fused (the light buffer couples every "
-            "slice of every brick); a shard renders shadows with the two marches only");
-  if (P.pert_on || c->region_on) FAIL(c, "smk_render: shadows cannot be combined with perturbation or a sub-box");
-  if (c->opt_kernel == 3) FAIL(c, "smk_render: the column-stream kernel has no shadow mode");
-  return 0;
-}
-
-// a shard's halo against the margin of its frame with shadows
-static int shadow_halo_check(smk_ctx *c, int need) {
-  for (int a = 0; a < 3; ++a)
-    if (c->halo < need && c->D[a] < c->N[a])
-      FAIL(c, "smk_render: shadows on a shard need halo >= %d voxels (have %d; margin %d, smk_get_shadow_margin); set option 'halo' before upload",
-           need, c->halo, need - 1);
-  return 0;
-}
-
-float4 *smk_shadow_entries_reserve(smk_ctx *c, int LB) {
-  const size_t n = (size_t)c->nranks * LB * LB;
-  if (n > c->shadow_entries_cap) {
-    if (c->d_shadow_entries) (void)hipFree(c->d_shadow_entries);
-    c->d_shadow_entries = nullptr;
-    c->shadow_entries_cap = 0;
-    if (hipMalloc((void **)&c->d_shadow_entries, n * 16) != hipSuccess) {
-      (void)hipGetLastError();
-      c->d_shadow_entries = nullptr;
-      return nullptr;
-    }
-    c->shadow_entries_cap = n;
-  }
-  c->shadow_entries_fresh = false;
-  return c->d_shadow_entries;
-}
-
-void smk_shadow_entries_commit(smk_ctx *c, const smk_shadowcoef &sc) {
-  c->shadow_entries_sc = sc;
-  c->shadow_entries_fresh = true;
-}
-
-int smk_shadow_shard_setup(smk_ctx *c, RenderParams &P, smk_shadowcoef &sc, SmkShadowShard &S, hipStream_t s) {
-  if (!c->shadow_on) FAIL(c, "smk_shadow_exports_device: shadows are off (smk_set_shadow)");
-  if (build_params(c, P, s)) return 1;
-  if (shadow_refusals(c, P)) return 1;
-  int need = 0;
-  if (shadow_setup(c, P, sc, &S, &need)) return 1;
-  if (shadow_halo_check(c, need)) return 1;
-  return 0;
-}
-
-extern "C" int smk_shadow_exports_device(smk_ctx *c, void *d_exports, void *stream) {
-  if (!c) return 1;
-  HIPCHK(c, hipSetDevice(c->device));
-  if (!d_exports) FAIL(c, "smk_shadow_exports_device: null output");
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-  RenderParams P;
-  smk_shadowcoef sc;
-  SmkShadowShard S;
-  if (smk_shadow_shard_setup(c, P, sc, S, s)) return 1;
-  S.exports = (float4 *)d_exports;
-  hipError_t e = smk_launch_shadow_exports(P, sc, c->dtype, c->tf_mode, S, s);
-  if (e == hipErrorNotSupported) FAIL(c, "smk_shadow_exports_device: no shadow kernel instance for this configuration");
-  HIPCHK(c, e);
-  return smk_step_mark_used(c, s);
-}
-
-extern "C" int smk_shadow_entries_device(smk_ctx *c, const void *d_entries, void *stream) {
-  if (!c) return 1;
-  HIPCHK(c, hipSetDevice(c->device));
-  if (!d_entries) FAIL(c, "smk_shadow_entries_device: null input");
-  if (!c->have_volume || !c->have_camera) FAIL(c, "smk_shadow_entries_device: volume and camera must be set");
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-  smk_shadowcoef sc;
-  if (compute_shadowcoef(c, &sc)) return 1;
-  float4 *d = smk_shadow_entries_reserve(c, sc.LB);
-  if (!d) FAIL(c, "smk_shadow_entries_device: device allocation failed");
-  HIPCHK(c, hipMemcpyAsync(d, d_entries, (size_t)c->nranks * sc.LB * sc.LB * 16, hipMemcpyDeviceToDevice, s));
-  smk_shadow_entries_commit(c, sc);
-  return 0;
-}
-
-extern "C" int smk_get_shadow_margin(smk_ctx *c, int *m, int *halo_needed) {
-  if (!c) return 1;
-  if (!c->have_volume || !c->have_camera) FAIL(c, "smk_get_shadow_margin: volume and camera must be set");
-  smk_shadowcoef sc;
-  if (compute_shadowcoef(c, &sc)) return 1;
-  const int mm = shadow_margin(sc, c->g0, c->g1);
-  if (m) *m = mm;
-  if (halo_needed) *halo_needed = mm + 1;
-  return 0;
-}
-
-static int shadow_light_owned(smk_ctx *c, RenderParams &P, smk_shadowcoef &sc, float olo[3], float ohi[3]) {
-  if (!c->shadow_on) FAIL(c, "smk_get_stat: light_samples needs shadows on (smk_set_shadow)");
-  if (build_params(c, P, c->stream)) return 1;
-  SmkShadowShard S;
-  if (shadow_setup(c, P, sc, &S, nullptr)) return 1;
-  for (int a = 0; a < 3; ++a) { olo[a] = S.olo[a]; ohi[a] = S.ohi[a]; }
-  return 0;
-}
-
-// In-process transport of the light exchange: phase 1 on every rank into its own scratch buffer, then slot j of rank r's
-// exports into slot r of rank j's entries (device-to-device; peer copies between devices).  Synchronous: every rank's stream
-// is idle before (the entries of the previous frame are no longer read) and after.
-extern "C" int smk_shadow_exchange_local(smk_ctx *const *all, int nranks) {
-  if (!all || nranks < 1 || nranks > SMK_MAX_RANKS) return 1;
-  for (int r = 0; r < nranks; ++r) {
-    if (!all[r]) return 1;
-    if (all[r]->nranks != nranks || all[r]->rank != r) FAIL(all[r], "smk_shadow_exchange_local: context %d is not shard %d of %d", r, r, nranks);
-  }
-  std::vector<smk_shadowcoef> scs(nranks);
-  for (int r = 0; r < nranks; ++r) {
-    smk_ctx *c = all[r];
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    RenderParams P;
-    SmkShadowShard S;
-    if (smk_shadow_shard_setup(c, P, scs[r], S, c->stream)) return 1;
-    if (r > 0 && memcmp(&scs[r], &scs[0], sizeof scs[0])) FAIL(c, "smk_shadow_exchange_local: the ranks' slice sets differ (camera, light, buffer or volume)");
-    const size_t n = (size_t)nranks * scs[r].LB * scs[r].LB;
-    if (n > c->shadow_exports_cap) {
-      if (c->d_shadow_exports) (void)hipFree(c->d_shadow_exports);
-      c->d_shadow_exports = nullptr;
-      c->shadow_exports_cap = 0;
-      HIPCHK(c, hipMalloc((void **)&c->d_shadow_exports, n * 16));
-      c->shadow_exports_cap = n;
-    }
-    S.exports = c->d_shadow_exports;
-    hipError_t e = smk_launch_shadow_exports(P, scs[r], c->dtype, c->tf_mode, S, c->stream);
-    if (e == hipErrorNotSupported) FAIL(c, "smk_shadow_exchange_local: no shadow kernel instance for this configuration");
-    HIPCHK(c, e);
-  }
-  const size_t nl = (size_t)scs[0].LB * scs[0].LB;
-  std::vector<float4 *> dst(nranks);
-  for (int j = 0; j < nranks; ++j) {
-    HIPCHK(all[j], hipSetDevice(all[j]->device));
-    dst[j] = smk_shadow_entries_reserve(all[j], scs[0].LB);
-    if (!dst[j]) FAIL(all[j], "smk_shadow_exchange_local: device allocation failed");
-  }
-  for (int r = 0; r < nranks; ++r) {
-    smk_ctx *c = all[r];
-    HIPCHK(c, hipSetDevice(c->device));
-    for (int j = 0; j < nranks; ++j) {
-      if (all[j]->device == c->device)
-        HIPCHK(c, hipMemcpyAsync(dst[j] + (size_t)r * nl, c->d_shadow_exports + (size_t)j * nl, nl * 16, hipMemcpyDeviceToDevice, c->stream));
-      else
-        HIPCHK(c, hipMemcpyPeerAsync(dst[j] + (size_t)r * nl, all[j]->device, c->d_shadow_exports + (size_t)j * nl, c->device, nl * 16, c->stream));
-    }
-  }
-  for (int r = 0; r < nranks; ++r) {
-    HIPCHK(all[r], hipSetDevice(all[r]->device));
-    HIPCHK(all[r], hipStreamSynchronize(all[r]->stream));
-  }
-  for (int j = 0; j < nranks; ++j) smk_shadow_entries_commit(all[j], scs[0]);
-  return 0;
-}
-
-extern "C" int smk_get_light_history(smk_ctx *c, int k, float *rgba_out) {
-  if (!c || !rgba_out) return 1;
-  HIPCHK(c, hipSetDevice(c->device));
-  if (!c->light_hist_n || !c->d_light_hist) FAIL(c, "smk_get_light_history: the last frame with shadows kept no history (option shadow_march 0?)");
-  if (k < 0 || k >= c->light_hist_n) FAIL(c, "smk_get_light_history: slice %d outside 0..%d", k, c->light_hist_n - 1);
-  HIPCHK(c, hipDeviceSynchronize());
-  HIPCHK(c, hipMemcpy(rgba_out, c->d_light_hist + (size_t)k * c->light_hist_stride, (size_t)c->light_lb * c->light_lb * 16,
-                      hipMemcpyDeviceToHost));
-  return 0;
-}
-
-extern "C" int smk_render_device(smk_ctx *c, void *d_rgba, void *d_depth, void *stream) {
-  if (!c) return 1;
-  HIPCHK(c, hipSetDevice(c->device));
-  if (!d_rgba) FAIL(c, "smk_render_device: null output");
-  RenderParams P;
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-  if (build_params(c, P, s)) return 1;
-  P.out = (float4 *)d_rgba;
-  P.depth = (float *)d_depth;
-  // algorithmic bytes: every stored voxel once + TF + RGBA f32 frame
-  size_t nst = (size_t)c->D[0] * c->D[1] * c->D[2];
-  double bv = c->dtype == SMK_U8 ? (double)c->nelts : 4.0 * c->nelts;
-  if (shade_kind_of(c)) bv += 3.0;
-  double tfb = c->tf_mode == 0 ? 16.0 * c->tlut_size
-               : c->tf_mode == 1 ? 4.0 * c->sv * c->sg * (P.third_axis ? 2 : 1)
-                                 : 4.0 * c->s3v * c->s3g * c->s3h;
-  c->last_alg_bytes = (double)nst * bv + tfb + 16.0 * c->W * c->H;
-  if (c->tev0.empty()) {
-    c->tev0.resize(SMK_TIMING_RING);
-    c->tev1.resize(SMK_TIMING_RING);
-    for (int i = 0; i < SMK_TIMING_RING; ++i) {
-      HIPCHK(c, hipEventCreate(&c->tev0[i]));
-      HIPCHK(c, hipEventCreate(&c->tev1[i]));
-    }
-  }
-  int slot = (int)(c->tcount % SMK_TIMING_RING);
-  c->ev0 = c->tev0[slot];
-  c->ev1 = c->tev1[slot];
-  // (ev0 is recorded by the launcher right before the kernel: host-side planning between the two
-  //  events would otherwise count as kernel time whenever the stream is idle)
-  // kernel choice: the slice-ring kernel when it applies (2-D / separable classification,
-  // no perturbation, rays sharing one principal axis), the generic gather kernel otherwise
-  c->last_kernel = 1;
-  c->slab_why.clear();
-  // The status word this frame takes over belongs to frame id - SMK_STATUS_RING: flagged, and nobody has asked about it
-  // (smk_frame_failed) while they could -- the call fails.  Younger frames' words are left for their owners: a host that
-  // pipelines frames asks about frame i AFTER enqueuing frame i + 1 (sortlast.Pipeline), and must find the word there.
-  if (check_frame_status(c, c->frame_id + 1 - SMK_STATUS_RING)) return 1;
-  ++c->frame_id;
-  c->slab.status_slot = (int)(c->frame_id % SMK_STATUS_RING);
-  c->slab.status_tag = c->cols.status_tag = (int)((c->frame_id & 0x7fffff) << 8);
-  if (c->slab.h_status) ((volatile int *)c->slab.h_status)[c->slab.status_slot] = 0;
-  bool ev0_recorded = false;  // (frames with shadows open the kernel-time bracket before their light march)
-  if (c->shadow_on) {
-    // ---- half-angle slicing (smk_shadow.hip): the light march, then the eye pass as an ordinary frame of the ray-marchers
-    // below over the half-angle slices (SmkShadowRays) -- or, option shadow_march 0, a launch per slice
-    const int sk = shade_kind_of(c);
-    if (c->nranks > 1 && !c->shadow_entries_fresh && c->tf_mode != 0 && sk != 2)
-      FAIL(c, "smk_render: shadows need the whole volume on one GPU (the light buffer couples every slice of every brick) -- "
-              "or, on a shard, this frame's light entries: smk_shadow_exports_device on every rank, then smk_shadow_entries_device "
-              "(smk_shadow_exchange_local in one process)");
-    const bool entries = c->shadow_entries_fresh;
-    c->shadow_entries_fresh = false;  // (consumed by this frame, whatever becomes of it)
-    if (shadow_refusals(c, P)) return 1;
-    smk_shadowcoef sc;
-    SmkShadowShard S;
-    int halo_need = 0;
-    if (shadow_setup(c, P, sc, c->nranks > 1 ? &S : nullptr, &halo_need)) return 1;
-    SmkShadowRays &h = P.sh;
-    if (c->nranks > 1) {
-      if (shadow_halo_check(c, halo_need)) return 1;
-      if (!entries || memcmp(&sc, &c->shadow_entries_sc, sizeof sc))
-        FAIL(c, "smk_render: shadows on a shard: the light entries were made for another slice set (camera, light or buffer changed since)");
-      S.entries = c->d_shadow_entries;
-    }
-    P.blend = SMK_BLEND_FRONT_TO_BACK;  // (a light that faces the viewer: the per-slice form blends back to front, the marchers
-                                        //  composite the same samples front to back -- the association of the blend differs)
-    const size_t nl = (size_t)sc.LB * sc.LB;
-    // The light march keeps every slice's light buffer: (nslices + 1) buffers.  Where that does not fit (more than a quarter
-    // of the device's free memory, or 32 GB) the frame is a launch per slice, as with the option off.
-    // (buffers 4 KiB + 256 B further apart than their size: 512^2 texels are exactly 4 MiB, and a wave of the light march
-    //  stores to 8 consecutive buffers at once -- a power-of-two stride could put them all into the same memory channels;
-    //  measured: 1.00 ms with the pad, 1.03 without, i.e. the fabric's address hash already spreads them)
-    const size_t hstride = nl + 272;
-    const size_t nhist = hstride * ((size_t)sc.nslices + 1);
-    bool march = c->opt_shadow_march && !(c->opt_lockstep & 256) && sc.nslices > 0;
-    if (march && nhist > c->light_hist_cap) {
-      size_t fr = 0, tot = 0;
-      if (c->d_light_hist) (void)hipFree(c->d_light_hist);
-      c->d_light_hist = nullptr;
-      c->light_hist_cap = 0;
-      c->d_light_last = nullptr;
-      if (hipMemGetInfo(&fr, &tot) != hipSuccess || nhist * 16 > fr / 4 || nhist * 16 > ((size_t)32 << 30) ||
-          hipMalloc((void **)&c->d_light_hist, nhist * 16) != hipSuccess) {
-        (void)hipGetLastError();
-        c->d_light_hist = nullptr;
-        march = false;
-      } else c->light_hist_cap = nhist;
-    }
-    c->light_lb = sc.LB;
-    c->light_hist_n = 0;
-    if (c->nranks > 1 && !march)
-      FAIL(c, "smk_render: shadows on a shard: the light history (%.1f GB) does not fit a quarter of the free device memory",
-           (double)nhist * 16.0 / 1e9);
-    if (march) {
-      HIPCHK(c, hipEventRecord(c->ev0, s));
-      ev0_recorded = true;
-      hipError_t e = c->nranks > 1 ? smk_launch_shadow_march_shard(P, sc, c->dtype, c->tf_mode, c->d_light_hist, (long long)hstride, S, s)
-                                   : smk_launch_shadow_march(P, sc, c->dtype, c->tf_mode, c->d_light_hist, (long long)hstride, s);
-      if (e == hipErrorNotSupported) FAIL(c, "smk_render: no shadow kernel instance for this configuration");
-      HIPCHK(c, e);
-      h.hist = c->d_light_hist;
-      h.hstride = (long long)hstride;
-      c->light_hist_n = sc.nslices + 1;
-      c->light_hist_stride = (long long)hstride;
-      c->d_light_last = c->d_light_hist + (size_t)sc.nslices * hstride;
-      // the history is written once (16 B per texel and slice)
-      c->last_alg_bytes += (double)sc.nslices * (16.0 * (double)nl);
-      // ... and the eye pass is the frame the code below renders
-    } else {
-      if (nl > c->light_cap) {
-        for (int k = 0; k < 2; ++k) {
-          if (c->d_light[k]) (void)hipFree(c->d_light[k]);
-          c->d_light[k] = nullptr;
-          HIPCHK(c, hipMalloc((void **)&c->d_light[k], nl * 16));
-        }
-        c->light_cap = nl;
-        c->d_light_last = nullptr;
-      }
-      HIPCHK(c, hipEventRecord(c->ev0, s));
-      HIPCHK(c, hipMemsetAsync(c->d_light[0], 0, nl * 16, s));
-      HIPCHK(c, hipMemsetAsync(d_rgba, 0, (size_t)c->W * c->H * 16, s));
-      if (d_depth) HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)d_depth, 0x7f800000, (size_t)c->W * c->H, s));  // (+inf: no sample yet)
-      if (!c->d_shadow_barrier) HIPCHK(c, hipMalloc((void **)&c->d_shadow_barrier, 16 * 9 * 4));  // (the common word + one per XCD, a cache line apart)
-      hipError_t e = smk_launch_shadow(P, sc, c->dtype, c->tf_mode, sk, c->d_light[0], c->d_light[1], c->d_shadow_barrier, s);
-      if (e == hipErrorNotSupported) FAIL(c, "smk_render: no shadow kernel instance for this configuration");
-      HIPCHK(c, e);
-      HIPCHK(c, hipEventRecord(c->ev1, s));
-      c->d_light_last = c->d_light[sc.nslices & 1];
-      // per slice the frame buffer (read + write where the slice covers it) and both light buffers move again
-      c->last_alg_bytes += (double)sc.nslices * (32.0 * (double)nl);
-      c->last_kernel = 3;
-      if (c->tf_mode == 1 && c->tf_cur >= 0) {  // this frame read the current table version (refresh_tf2d waits for this before rewriting it)
-        HIPCHK(c, hipEventRecord(c->tfv[c->tf_cur].used, s));
-        c->tfv[c->tf_cur].used_valid = true;
-      }
-      if (smk_step_mark_used(c, s)) return 1;
-      c->tcount++;
-      return 0;
-    }
-  }
-  // ---- auto mode: which kernel for this configuration?
-  bool try_slab = c->opt_kernel != 1;
-  unsigned long long sig = 0;
-  int trial = -1;  // 0 / 1: this frame is the slice-ring / gather trial of a new configuration
-  if (c->opt_kernel == 0) {
-    int as = 0;
-    for (int a = 1; a < 3; ++a)
-      if (fabsf(P.rc.Bc[a]) > fabsf(P.rc.Bc[as])) as = a;
-    const unsigned long long f[] = {(unsigned long long)c->dtype, (unsigned long long)c->nelts, (unsigned long long)c->D[0],
-                                    (unsigned long long)c->D[1], (unsigned long long)c->D[2], (unsigned long long)c->W,
-                                    (unsigned long long)c->H, (unsigned long long)P.rc.nplanes, (unsigned long long)shade_kind_of(c),
-                                    (unsigned long long)P.third_axis, (unsigned long long)(as * 2 + (P.rc.Bc[as] > 0)),
-                                    (unsigned long long)c->sv, (unsigned long long)c->sg, (unsigned long long)(d_depth != nullptr),
-                                    (unsigned long long)P.pert_on, (unsigned long long)c->tf_mode, (unsigned long long)c->s3v,
-                                    (unsigned long long)c->s3g, (unsigned long long)c->s3h, (unsigned long long)c->blend,
-                                    (unsigned long long)P.sh.on};
-    sig = 1469598103934665603ull;
-    for (unsigned long long v : f) sig = (sig ^ v) * 1099511628211ull;
-    auto it = c->tune_choice.find(sig);
-    if (it != c->tune_choice.end() && it->second.expires <= c->frame_id) {  // measured long ago: measure again
-      c->tune_choice.erase(it);
-      it = c->tune_choice.end();
-      c->tune_sig = 0;
-    }
-    if (it != c->tune_choice.end()) {
-      try_slab = it->second.kernel == 2;
-    } else {
-      if (c->tune_sig != sig) {
-        c->tune_sig = sig;
-        c->tune_state = 0;
-      }
-      // Trial frames of a new configuration: SMK_TUNE_SETTLE untimed slice-ring frames -- its schedule and depth cuts come
-      // from the workgroup times of earlier frames, so each waits for the one before it (a one-time stall; without it, and
-      // with a single untimed frame, the timed trial was the first frame with cuts, 1.14 ms on a 1/8 shard that settles at
-      // 0.15, and auto mode kept the 0.69 ms gather kernel for the shard) --, one untimed gather frame, then the timed pair.
-      if (c->tune_state == SMK_TUNE_SETTLE + 3) {  // both timed trials issued: decide once their events have completed
-        float ms_s = 0, ms_g = 0;
-        // (a host that enqueues frames far ahead of the GPU would recycle the trials' event pairs -- the ring holds the
-        //  last 64 frames -- before they complete, and the comparison would then be between two later frames of the
-        //  same kernel: wait for the trials rather than let their slots go)
-        if (c->tcount - c->tune_tcount >= SMK_TIMING_RING - 8) (void)hipEventSynchronize(c->tev1[c->tune_slot[1]]);
-        if (hipEventQuery(c->tev1[c->tune_slot[0]]) == hipSuccess && hipEventQuery(c->tev1[c->tune_slot[1]]) == hipSuccess &&
-            hipEventElapsedTime(&ms_s, c->tev0[c->tune_slot[0]], c->tev1[c->tune_slot[0]]) == hipSuccess &&
-            hipEventElapsedTime(&ms_g, c->tev0[c->tune_slot[1]], c->tev1[c->tune_slot[1]]) == hipSuccess) {
-          c->tune_choice[sig] = {ms_s <= ms_g ? 2 : 1, c->frame_id + 1024};
-          try_slab = ms_s <= ms_g;
-          if (getenv("SMK_DEBUG")) fprintf(stderr, "[smk] auto mode: slice-ring %.3f ms, gather %.3f ms (frame %lld)\n", ms_s, ms_g, c->frame_id);
-        }  // else: keep the slice-ring kernel for this frame and ask again
-        (void)hipGetLastError();
-      } else {
-        trial = c->tune_state;
-        try_slab = trial != SMK_TUNE_SETTLE && trial != SMK_TUNE_SETTLE + 2;
-        if (try_slab && trial > 0) (void)hipStreamSynchronize(s);  // (the previous settle frame's workgroup times are back)
-      }
-    }
-  }
-  if (c->opt_kernel == 3) {
-    // ---- the column-stream kernel, forced (smk_cols.hip)
-    try_slab = false;
-    if (!c->slab.h_status) {
-      HIPCHK(c, hipHostMalloc((void **)&c->slab.h_status, SMK_STATUS_RING * sizeof(int), hipHostMallocMapped));
-      for (int k = 0; k < SMK_STATUS_RING; ++k) c->slab.h_status[k] = 0;
-      HIPCHK(c, hipMalloc((void **)&c->slab.d_diag, 16 * sizeof(float)));
-    }
-    const char *why = nullptr;
-    c->cols.frame_ev0 = c->ev0;
-    hipError_t e = smk_launch_cols(P, c->dtype, c->tf_mode, shade_kind_of(c), c->opt_cols, c->d_vox, &c->cols,
-                                   c->slab.h_status + c->slab.status_slot, &why, s);
-    if (e == hipErrorNotSupported) {
-      c->slab_why = why ? why : "?";
-      FAIL(c, "smk_render: column-stream kernel forced but not applicable: %s", c->slab_why.c_str());
-    }
-    HIPCHK(c, e);
-    c->last_kernel = 4;
-    if (c->opt_inject_status && c->slab.h_status) {
-      ((volatile int *)c->slab.h_status)[c->slab.status_slot] = c->slab.status_tag | c->opt_inject_status;
-      c->opt_inject_status = 0;
-    }
-  }
-  if (try_slab) {
-    if (!c->slab.h_status) {
-      HIPCHK(c, hipHostMalloc((void **)&c->slab.h_status, SMK_STATUS_RING * sizeof(int), hipHostMallocMapped));
-      for (int k = 0; k < SMK_STATUS_RING; ++k) c->slab.h_status[k] = 0;
-      HIPCHK(c, hipMalloc((void **)&c->slab.d_diag, 16 * sizeof(float)));
-    }
-    if (c->opt_lockstep & 16) HIPCHK(c, hipMemsetAsync(c->slab.d_diag, 0, 16 * sizeof(float), s));
-    const char *why = nullptr;
-    c->slab.frame_ev0 = ev0_recorded ? nullptr : c->ev0;
-    hipError_t e = smk_launch_slab(P, c->dtype, c->tf_mode, shade_kind_of(c), c->d_vox, c->d_vox_x, &c->slab, &why, s);
-    if (e == hipErrorNotSupported && why && !strcmp(why, "x-major copy unavailable")) {
-      if (make_xmajor_copy(c)) return 1;
-      e = smk_launch_slab(P, c->dtype, c->tf_mode, shade_kind_of(c), c->d_vox, c->d_vox_x, &c->slab, &why, s);
-    }
-    if (e == hipSuccess) {
-      c->last_kernel = 2;
-      c->last_slab_sig = sig;
-      if (c->opt_inject_status && c->slab.h_status) {  // (test hook: what a failed frame leaves behind)
-        ((volatile int *)c->slab.h_status)[c->slab.status_slot] = c->slab.status_tag | c->opt_inject_status;
-        c->opt_inject_status = 0;
-      }
-    }
-    else if (e == hipErrorNotSupported) {
-      c->slab_why = why ? why : "?";
-      if (c->opt_kernel == 2) FAIL(c, "smk_render: slab kernel forced but not applicable: %s", c->slab_why.c_str());
-      // Not remembered: most reasons depend on the pose (too oblique, window does not fit LDS, ...)
-      // and the signature does not; the next frame is planned afresh (planning runs per frame anyway)
-      // and returns to the slice-ring kernel as soon as the view allows.
-      if (c->opt_kernel == 0) trial = -1;
-    } else
-      HIPCHK(c, e);
-  } else if (c->opt_kernel == 2) {
-    FAIL(c, "smk_render: slab kernel forced but classification mode %d is gather-only", c->tf_mode);
-  }
-  if (c->last_kernel == 1) {
-    if (!ev0_recorded) HIPCHK(c, hipEventRecord(c->ev0, s));
-    HIPCHK(c, smk_launch_gather(P, c->dtype, c->tf_mode, shade_kind_of(c), s));
-  }
-  HIPCHK(c, hipEventRecord(c->ev1, s));
-  if (trial >= 0) {
-    if (trial >= SMK_TUNE_SETTLE + 1) {
-      c->tune_slot[trial - (SMK_TUNE_SETTLE + 1)] = slot;
-      c->tune_tcount = c->tcount;
-    }
-    c->tune_state = trial + 1;
-  }
-  if (c->tf_mode == 1 && c->tf_cur >= 0) {  // this frame read the current table version (refresh_tf2d waits for this before rewriting it)
-    HIPCHK(c, hipEventRecord(c->tfv[c->tf_cur].used, s));
-    c->tfv[c->tf_cur].used_valid = true;
-  }
-  if (smk_step_mark_used(c, s)) return 1;  // (and the time step it rendered)
-  c->tcount++;
-  return 0;
-}
-
-extern "C" int smk_render(smk_ctx *c, float *rgba, float *depth) {
-  if (!c) return 1;
-  HIPCHK(c, hipSetDevice(c->device));
-  if (!rgba) FAIL(c, "smk_render: null output");
-  if (!c->have_camera) FAIL(c, "smk_render: no camera set");
-  size_t npix = (size_t)c->W * c->H;
-  if (npix > c->out_cap) {
-    if (c->d_out) (void)hipFree(c->d_out);
-    if (c->d_depth) (void)hipFree(c->d_depth);
-    c->d_out = nullptr;
-    c->d_depth = nullptr;
-    HIPCHK(c, hipMalloc((void **)&c->d_out, npix * 16));
-    HIPCHK(c, hipMalloc((void **)&c->d_depth, npix * 4));
-    c->out_cap = npix;
-  }
-  if (smk_render_device(c, c->d_out, depth ? c->d_depth : nullptr, c->stream)) return 1;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
-  if (check_frame_status(c, c->frame_id)) {
-    // the synchronous entry still owes its caller this frame: in auto mode it is rendered again, by
-    // the gather kernel (take_status has just retired the slice-ring kernel for this configuration)
-    if (c->opt_kernel != 0) return 1;
-    const std::string first = c->err;
-    ++c->slab_retries;
-    if (smk_render_device(c, c->d_out, depth ? c->d_depth : nullptr, c->stream)) return 1;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->last_kernel != 1 || check_frame_status(c, c->frame_id)) {
-      c->err = first;
-      return 1;
-    }
-    fprintf(stderr, "[smk] %s -- frame rendered again by the gather kernel\n", first.c_str());
-  }
-  HIPCHK(c, hipMemcpy(rgba, c->d_out, npix * 16, hipMemcpyDeviceToHost));
-  if (depth) HIPCHK(c, hipMemcpy(depth, c->d_depth, npix * 4, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -2453,15 +1541,7 @@ extern "C" int smk_render_slice(smk_ctx *c, const float quad[4][3], float alpha,
   if (!rgba) FAIL(c, "smk_render_slice: null frame");
   if (!c->have_camera) FAIL(c, "smk_render_slice: no camera set");
   const size_t npix = (size_t)c->W * c->H;
-  if (npix > c->out_cap) {
-    if (c->d_out) (void)hipFree(c->d_out);
-    if (c->d_depth) (void)hipFree(c->d_depth);
-    c->d_out = nullptr;
-    c->d_depth = nullptr;
-    HIPCHK(c, hipMalloc((void **)&c->d_out, npix * 16));
-    HIPCHK(c, hipMalloc((void **)&c->d_depth, npix * 4));
-    c->out_cap = npix;
-  }
+  if (smk_frame_buffers(c)) return 1;
   HIPCHK(c, hipMemcpy(c->d_out, rgba, npix * 16, hipMemcpyHostToDevice));
   if (smk_render_slice_device(c, quad, alpha, c->d_out, c->stream)) return 1;
   HIPCHK(c, hipStreamSynchronize(c->stream));

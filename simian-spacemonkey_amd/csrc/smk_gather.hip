@@ -89,7 +89,7 @@ __global__ __launch_bounds__(256) void smk_k_gather(const RenderParams P) {
 
     if (P.pert_on) {
       if (TF != 0 && P.bricks_dil != nullptr) {
-        // every brick the displaced fetch can reach from here is flagged empty (smk_api.hip build_params): the sample is
+        // every brick the displaced fetch can reach from here is flagged empty (smk_api.hip smk_build_params): the sample is
         // exactly transparent wherever the noise sends it -- neither the noise nor the voxels are looked at
         int u0, u1, v0, v1, w0, w1;
         float fu, fv, fw;

@@ -13,8 +13,8 @@
 #define SMK_MAX_RANKS 8
 #define SMK_TIMING_RING 64
 #define SMK_BRICK_LOG2 3   // bricks of 8x8x8 cells (smk_bricks.hip)
-#define SMK_SHADOW_BOX_EPS 0.0009765625f  // voxels: frames with shadows test an eye sample against the box widened by this (smk_api.hip)
-#define SMK_TUNE_SETTLE 6  // auto mode: untimed slice-ring frames before a new configuration's timed trial (smk_api.hip)
+#define SMK_SHADOW_BOX_EPS 0.0009765625f  // voxels: frames with shadows test an eye sample against the box widened by this (smk_shadow_plan.hip)
+#define SMK_TUNE_SETTLE 6  // auto mode: untimed slice-ring frames before a new configuration's timed trial (smk_frame.hip)
 #define SMK_STATUS_RING 8  // frames whose slice-ring status stays readable (smk_frame_failed)
 
 // error handling of the C ABI entries (int returns: 0 ok, 1 error with the message in ctx->err)
@@ -413,7 +413,7 @@ hipError_t smk_launch_shadow_march_shard(const RenderParams &P, const smk_shadow
                                          long long hstride, const SmkShadowShard &S, hipStream_t s);
 hipError_t smk_launch_shadow_count_light(const RenderParams &P, const smk_shadowcoef &sc, const float olo[3], const float ohi[3],
                                          unsigned long long *d_count, hipStream_t s);
-// (smk_api.hip) the frame with shadows a shard context would render now: its slice set and phase-1 parameters; the buffer
+// (smk_shadow_plan.hip) the frame with shadows a shard context would render now: its slice set and phase-1 parameters; the buffer
 // for X_{r->this} (LB x LB texels per rank), made current for the next frame by smk_shadow_entries_commit
 int smk_shadow_shard_setup(smk_ctx *c, RenderParams &P, smk_shadowcoef &sc, SmkShadowShard &S, hipStream_t s);
 float4 *smk_shadow_entries_reserve(smk_ctx *c, int LB);
@@ -449,6 +449,25 @@ int smk_pack_step(smk_ctx *c, const char *who, const SmkVolGeom &g, const smk_vo
                   hipStream_t s);
 // ts[k] becomes the step frames render (its brick flags are made again before the next frame)
 void smk_use_step(smk_ctx *c, int k);
+
+// host set-up shared by the C ABI's files (smk_api.hip; hidden: not part of the library's interface)
+#pragma GCC visibility push(hidden)
+int smk_build_params(smk_ctx *c, RenderParams &P, hipStream_t s);  // a frame's RenderParams from the context (no shadows)
+int smk_shade_kind(const smk_ctx *c);  // 0 none, 1 R8k, 2 NV20
+void smk_region_box(const smk_ctx *c, const int g0[3], const int g1[3], float lo[3], float hi[3], int top[3]);
+void smk_shard_region(const smk_ctx *c, int rank, int g0[3], int g1[3]);
+void smk_bsp_order(const smk_ctx *c, const double pos[3], int *order);
+void smk_inverse_affine(double inv[16], const double m[16]);
+int smk_make_xmajor_copy(smk_ctx *c);
+int smk_frame_buffers(smk_ctx *c);  // (smk_frame.hip)
+void smk_slab_free(SlabAux *aux);  // (smk_slab_plan.hip)
+// frames with shadows (smk_shadow_plan.hip): the half-angle slices and boxes of P (S, halo_need: a shard's); the light
+// samples a context owns (smk_get_stat); and a frame's shadow stage -- the light march (*marched), else the whole frame
+// as a launch per slice
+int smk_shadow_setup(smk_ctx *c, RenderParams &P, smk_shadowcoef &sc, SmkShadowShard *S, int *halo_need);
+int smk_shadow_light_owned(smk_ctx *c, RenderParams &P, smk_shadowcoef &sc, float olo[3], float ohi[3]);
+int smk_shadow_frame(smk_ctx *c, RenderParams &P, void *d_rgba, void *d_depth, hipStream_t s, bool *marched);
+#pragma GCC visibility pop
 
 // time steps (smk_timesteps.hip).  The step frames render is current; a frame's stream waits for its upload, and its end is
 // recorded as the step's last reader (an upload that overwrites the slot waits for that)

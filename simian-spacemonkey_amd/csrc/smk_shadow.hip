@@ -38,7 +38,7 @@ struct ShadowSlice {
 
 // the 8 corners of voxel coordinate p and the interpolated data channels (same arithmetic as kernel G)
 // (LOC: a shard's stored box, region + halo from voxel O on: global indices -> stored ones, clamped for memory safety --
-//  the shard's marches stay inside it by construction, smk_api.hip; the whole volume has O = 0, D = N.  x0 at most D - 2:
+//  the shard's marches stay inside it by construction, smk_shadow_plan.hip; the whole volume has O = 0, D = N.  x0 at most D - 2:
 //  the u8 pair load reads voxels x0 and x0 + 1 at once)
 __device__ __forceinline__ void shadow_local(const RenderParams &P, int &x0, int &x1, int &y0, int &y1, int &z0, int &z1) {
   x0 = min(max(x0 - P.O[0], 0), max(P.D[0] - 2, 0));
@@ -191,7 +191,7 @@ __device__ __forceinline__ void shadow_eye_pixel(const RenderParams &P, const Sh
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
     p[a] = __fmaf_rn((float)m, B[a], A[a]);
-    in = in && p[a] >= P.lo[a] && p[a] <= P.hi[a];  // (the box, 2^-10 voxels wide: smk_api.hip)
+    in = in && p[a] >= P.lo[a] && p[a] <= P.hi[a];  // (the box, 2^-10 voxels wide: smk_shadow_plan.hip)
   }
   if (!in) return;
   if (P.cplane_on && !(__fmaf_rn(p[0], P.cplane[0], __fmaf_rn(p[1], P.cplane[1], __fmaf_rn(p[2], P.cplane[2], P.cplane[3]))) >= 0.0f)) return;
@@ -543,7 +543,7 @@ static hipError_t run_march(const RenderParams &P, ShadowSlice Q, float4 *hist, 
 }
 
 // The light march alone: hist = nslices + 1 buffers of [LB][LB] texels, `hstride` texels apart; hist[k] = the light buffer after slices 1..k.  The eye pass is
-// then an ordinary frame of the ray-marchers over the half-angle slices (P.sh, smk_api.hip).
+// then an ordinary frame of the ray-marchers over the half-angle slices (P.sh, smk_shadow_plan.hip).
 hipError_t smk_launch_shadow_march(const RenderParams &P, const smk_shadowcoef &sc, int dtype, int tf_mode, float4 *hist, long long hstride,
                                    hipStream_t s) {
   ShadowSlice Q;

@@ -746,6 +746,18 @@ void smk_slab_forget_measurements(SlabAux *aux) {
   aux->recut = true;
 }
 
+// every buffer and event of the context's slice-ring side (smk_destroy); the status ring and d_diag are made by the frame
+// driver (smk_frame.hip), the rest here
+void smk_slab_free(SlabAux *aux) {
+  for (void *p : {(void *)aux->d_diag, (void *)aux->d_order, (void *)aux->d_pticks, aux->d_seg, (void *)aux->d_trace, (void *)aux->d_ticks})
+    if (p) (void)hipFree(p);
+  for (void *p : {(void *)aux->h_status, (void *)aux->h_pticks, (void *)aux->h_ticks, (void *)aux->h_order[0], (void *)aux->h_order[1],
+                  (void *)aux->h_order[2], (void *)aux->h_order[3]})
+    if (p) (void)hipHostFree(p);
+  for (hipEvent_t e : {aux->order_ev[0], aux->order_ev[1], aux->order_ev[2], aux->order_ev[3], aux->ticks_ev})
+    if (e) (void)hipEventDestroy(e);
+}
+
 // ---- depth-segment cuts (aux->cuts)
 // DEPTH SEGMENTS: how many workgroups render each tile.  From MEASURED durations only (the geometric estimate says
 // nothing about what a tile's samples cost): a tile longer than half the mean load of a workgroup slot is cut so that
