@@ -1005,10 +1005,10 @@ extern "C" int smk_set_option(smk_ctx *c, const char *key, int value) {
   else if (!strcmp(key, "shadow_march")) c->opt_shadow_march = value ? 1 : 0;  // (0: a launch per slice, the form of rounds 1-2)
   else if (!strcmp(key, "shadow_fused")) c->opt_lockstep = value ? (c->opt_lockstep | 256) : (c->opt_lockstep & ~256);  // (developer: all slices in one cooperative launch)
   else if (!strcmp(key, "slab_split")) c->slab.opt_split = value < 0 ? 0 : (value > 8 ? 8 : value);
-  else if (!strcmp(key, "cols_shape")) c->opt_cols = (c->opt_cols & ~0xff) | (value & 0xff);
-  else if (!strcmp(key, "cols_ns")) c->opt_cols = (c->opt_cols & ~0xff00) | ((value & 0xff) << 8);
-  else if (!strcmp(key, "cols_chunk")) c->opt_cols = (c->opt_cols & ~0xfff0000) | ((value & 0xfff) << 16);
-  else if (!strcmp(key, "cols_wstep")) c->opt_cols = (c->opt_cols & 0x0fffffff) | ((value & 7) << 28);
+  else if (!strcmp(key, "cols_shape")) c->cols.opt_shape = value & 0xff;
+  else if (!strcmp(key, "cols_ns")) c->cols.opt_ns = value & 0xff;
+  else if (!strcmp(key, "cols_chunk")) c->cols.opt_chunk = value & 0xfff;
+  else if (!strcmp(key, "cols_wstep")) c->cols.opt_wstep = value & 7;
   else if (!strcmp(key, "cols_counts")) c->cols.want_counts = value ? 1 : 0;
   else if (!strcmp(key, "cols_fill")) { c->cols.opt_fill = value; smk_cols_drop_layouts(&c->cols); }
   else if (!strcmp(key, "cols_take_min")) c->cols.opt_take_min = value;
@@ -1052,14 +1052,6 @@ extern "C" int smk_get_brick_flags(smk_ctx *c, unsigned char *flags_out, int *nb
     if (!B || !B->valid || !B->flags) FAIL(c, "smk_get_brick_flags: no flags for this table (1-D colour table, or option 'bricks' 0)");
     HIPCHK(c, hipMemcpy(flags_out, B->flags, (size_t)c->nbr[0] * c->nbr[1] * c->nbr[2], hipMemcpyDeviceToHost));
   }
-  return 0;
-}
-
-// n words a kernel of the latest frame wrote (ticks, counters), read once the device has finished it; synchronises
-template <class T>
-static int read_back(smk_ctx *c, T *h, const T *d, size_t n) {
-  HIPCHK(c, hipDeviceSynchronize());
-  HIPCHK(c, hipMemcpy(h, d, n * sizeof(T), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -1148,37 +1140,7 @@ extern "C" int smk_get_stat(smk_ctx *c, const char *name, double *value) {
     }
     return 0;
   }
-  // column-stream kernel (smk_cols.hip), latest frame; these synchronise
-  if (!strncmp(name, "cols_", 5)) {
-    *value = 0.0;
-    if (!strcmp(name, "cols_builds")) { *value = c->cols.builds; return 0; }
-    if (!strcmp(name, "cols_config")) { *value = c->cols.last; return 0; }
-    if (!strcmp(name, "cols_jobs")) { *value = c->cols.njobs_last; return 0; }
-    if (!strcmp(name, "cols_stream_bytes")) { *value = c->cols.last_stream_bytes; return 0; }
-    if (!strcmp(name, "cols_job_ms_max") || !strcmp(name, "cols_job_ms_sum") || !strcmp(name, "cols_setup_ms_sum") || !strcmp(name, "cols_rays")) {
-      const int nj = c->cols.njobs_last, part = name[5] == 'j' ? 0 : name[5] == 's' ? 1 : 2;  // d_ticks: [3][nj] job, set-up ticks, rays
-      if (c->last_kernel == 4 && c->cols.d_ticks && nj > 0) {
-        std::vector<unsigned> h((size_t)nj);
-        if (read_back(c, h.data(), c->cols.d_ticks + (size_t)nj * part, h.size())) return 1;
-        double mx = 0, sum = 0;
-        for (unsigned v : h) {
-          mx = std::max(mx, (double)v);
-          sum += v;
-        }
-        *value = part == 2 ? sum : (name[12] == 'm' ? mx : sum) * 1e-5;  // (100 MHz ticks)
-      }
-      return 0;
-    }
-    static const char *cn[8] = {"cols_samples", "cols_visible", "cols_slices", "cols_segments", "cols_iters", "cols_active_lanes", "cols_switch_iters", "cols_switch_lanes"};
-    for (int k = 0; k < 8; ++k)
-      if (!strcmp(name, cn[k])) {
-        unsigned long long v = 0;
-        if (c->cols.d_counts && c->cols.want_counts && read_back(c, &v, c->cols.d_counts + k, 1)) return 1;
-        *value = (double)v;
-        return 0;
-      }
-    FAIL(c, "smk_get_stat: unknown name '%s'", name);
-  }
+  if (!strncmp(name, "cols_", 5)) return smk_cols_stat(c, name, value);  // column-stream kernel (smk_cols_plan.hip)
   if (!strcmp(name, "slab_split_tiles")) { *value = c->slab.nsplit_last; return 0; }
   if (!strcmp(name, "slab_workgroups")) { *value = c->slab.nblocks_last; return 0; }
   if (!strcmp(name, "slab_retries")) { *value = (double)c->slab_retries; return 0; }

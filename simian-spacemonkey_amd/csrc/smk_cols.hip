@@ -31,6 +31,9 @@
 // associative in exact arithmetic; in fp32 the frames agree to a few ulp per segment (tests: <= 2e-5 against the
 // gather kernel, <= 1e-4 against the CPU checker, the project's stated tolerance).  Exact early termination holds
 // inside a segment only.
+//
+// This file holds the kernels (march, resolve, layout build) and the launches of their instances; which frames the kernel
+// takes, the layout, the ring and the jobs are planned on the host in smk_cols_plan.hip.
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
@@ -38,38 +41,8 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "smk_cols.h"
 #include "smk_device.h"
-
-#define COL_DONE 0x3fffffff
-#define COL_MAX_CL 256   // positions per job at most (the per-slice table lives in LDS)
-#define COL_BOX_MARGIN 0.05f
-
-// wave-uniform description of one launch
-struct ColParams {
-  const char *lay;            // layout base: [cv][cu][s][(CH+1)][(CW+1)] voxels, slice images of slice_bytes
-  int CW, CH, ncu, ncv;       // cells per column along U, V; columns
-  int Ou, Ov, Os;             // stored-box origin (global voxel index) along U, V, S
-  int Du, Dv, Ds;             // stored-box dims
-  int slice_bytes;            // (CW+1)(CH+1) voxels, rounded up to 16 bytes
-  int n_ch;                   // DMA wave-instructions per slice = ceil(slice_bytes / 1024)
-  unsigned long long last_mask;  // lanes of the last one
-  int nslots, maxfly, wstep;
-  int take_min, take_wait;    // a wave takes new rays when this many lanes are free, or after this many turns
-  int ring_bytes;             // LDS bytes in front of the tables: the ring, at least the set-up's scratch (the unsorted rays)
-  int CL, nck;                // positions per chunk, chunks
-  int dir;                    // +1: rays advance towards +S
-  float Mx[4], My[4], Mw[4];  // voxel (global coordinates) -> continuous pixel: x = Mx.(X,1) / Mw.(X,1)
-  float4 *layers;             // [nkeys][npix]
-  unsigned long long *masks;  // [npix][mask_words]
-  int nkeys, mask_words;
-  int use_ah, use_occ, fast_tf;
-  int *status;                // host-visible: status_tag | (1 protocol time-out, 3 a job's rays do not fit lanes or list, 5 a ray's plane count
-                              // does not fit its list entry)
-  int status_tag;             // the frame's id << 8
-  unsigned *job_ticks;        // [njobs] duration of each job's workgroup in 100 MHz ticks, or null
-  unsigned long long *counts; // [8] samples taken | visible | slices streamed | segments written | consumer wave-iterations | lanes with a sample to
-                              // take in them | iterations in which some lane changes rays | lanes changing rays (developer statistics)
-};
 
 typedef float c_v4f __attribute__((ext_vector_type(4)));
 typedef unsigned c_v2u __attribute__((ext_vector_type(2)));
@@ -145,8 +118,6 @@ __device__ __forceinline__ ColTexel4 col_tex2d_fetch(const uint32_t *tex, int ss
 __device__ __forceinline__ float col_tex_chan(const ColTexel4 &x, int k) {
   return smk_lerp(smk_lerp(smk_ub(x.a, k), smk_ub(x.b, k), x.fs), smk_lerp(smk_ub(x.c, k), smk_ub(x.d, k), x.fs), x.ft) * SMK_INV255;
 }
-
-#define COL_MAX_RAYS 4096   // rays one job can list (8 bytes each in LDS)
 
 // one ray's marching state (registers)
 struct ColRay {
@@ -896,7 +867,20 @@ __global__ __launch_bounds__(256) void smk_k_cols_build(const V *src, char *dst,
   *reinterpret_cast<V *>(dst + sl_col * (size_t)slice_bytes + ((size_t)cy * iw + cx) * sizeof(V)) = val;
 }
 
-// ------------------------------------------------------------------------------- host side
+
+// ------------------------------------------------------------------------------- launches (the planning: smk_cols_plan.hip)
+
+hipError_t smk_cols_build(const void *vox_native, int dtype, int perm, const int D[3], int CW, int CH, int ncu, int ncv, int slice_bytes,
+                          void *dst, unsigned blocks, hipStream_t s) {
+  auto build = [&](auto kernel, auto *src) {
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, s, src, (char *)dst, D[0], D[1], D[2], CW, CH, ncu, ncv, slice_bytes);
+  };
+  const uint2 *u8 = (const uint2 *)vox_native;
+  const float4 *f32 = (const float4 *)vox_native;
+  if (dtype == 0) { if (perm == 0) build(smk_k_cols_build<uint2, 0>, u8); else if (perm == 1) build(smk_k_cols_build<uint2, 1>, u8); else build(smk_k_cols_build<uint2, 2>, u8); }
+  else { if (perm == 0) build(smk_k_cols_build<float4, 0>, f32); else if (perm == 1) build(smk_k_cols_build<float4, 1>, f32); else build(smk_k_cols_build<float4, 2>, f32); }
+  return hipGetLastError();
+}
 
 template <int DT, int SH, int PERM, int TF, int NW, int NL>
 static hipError_t launch_cols(const RenderParams &P, const ColParams &Q, size_t lds, int njobs, hipStream_t s) {
@@ -905,7 +889,7 @@ static hipError_t launch_cols(const RenderParams &P, const ColParams &Q, size_t 
   int dev = 0;
   (void)hipGetDevice(&dev);
   if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-    hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, COL_LDS_CAP);
     if (e != hipSuccess) return e;
     if (dev >= 0 && dev < 64) attr_set[dev] = true;
   }
@@ -913,10 +897,7 @@ static hipError_t launch_cols(const RenderParams &P, const ColParams &Q, size_t 
   return hipGetLastError();
 }
 
-// workgroup shapes: {consumer waves, loader waves}
-struct ColShape { int nw, nl; };
-static const ColShape kColShapes[] = {{15, 1}, {14, 2}};
-
+// the instances of kColShapes
 template <int DT, int SH, int PERM, int TF>
 static hipError_t dispatch_shape(const RenderParams &P, const ColParams &Q, int shape, size_t lds, int njobs, hipStream_t s) {
   switch (shape) {
@@ -936,312 +917,18 @@ static hipError_t dispatch_perm(const RenderParams &P, const ColParams &Q, int p
   return hipErrorInvalidValue;
 }
 
-static void cols_free_layout(ColLayout &L) {
-  if (L.d) (void)hipFree(L.d);
-  L = ColLayout();
-}
-
-void smk_cols_free(ColsAux *aux) {
-  for (int k = 0; k < 3; ++k) cols_free_layout(aux->lay[k]);
-  if (aux->d_layers) (void)hipFree(aux->d_layers);
-  if (aux->d_masks) (void)hipFree(aux->d_masks);
-  if (aux->d_ticks) (void)hipFree(aux->d_ticks);
-  if (aux->d_counts) (void)hipFree(aux->d_counts);
-  *aux = ColsAux();
-}
-
-void smk_cols_drop_layouts(ColsAux *aux) {
-  for (int k = 0; k < 3; ++k) cols_free_layout(aux->lay[k]);
-}
-
-static void host_ray_cols(const RenderParams &P, double fi, double fj, double A[3], double B[3]) {
-  const smk_raycoef &rc = P.rc;
-  const double px = fi * (double)rc.pxs + (double)rc.pxl, py = fj * (double)rc.pys + (double)rc.pyl;
-  for (int a = 0; a < 3; ++a) {
-    A[a] = px * rc.Ax[a] + py * rc.Ay[a] + rc.Ac[a];
-    B[a] = px * rc.Bx[a] + py * rc.By[a] + rc.Bc[a];
-  }
-}
-
-static bool inv3(const double m[9], double o[9]) {
-  const double det = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
-  if (!(fabs(det) > 1e-300)) return false;
-  const double id = 1.0 / det;
-  o[0] = (m[4] * m[8] - m[5] * m[7]) * id; o[1] = (m[2] * m[7] - m[1] * m[8]) * id; o[2] = (m[1] * m[5] - m[2] * m[4]) * id;
-  o[3] = (m[5] * m[6] - m[3] * m[8]) * id; o[4] = (m[0] * m[8] - m[2] * m[6]) * id; o[5] = (m[2] * m[3] - m[0] * m[5]) * id;
-  o[6] = (m[3] * m[7] - m[4] * m[6]) * id; o[7] = (m[1] * m[6] - m[0] * m[7]) * id; o[8] = (m[0] * m[4] - m[1] * m[3]) * id;
-  return true;
-}
-
-// plan + launch; hipErrorNotSupported (and *why) when the frame must use another kernel
-hipError_t smk_launch_cols(RenderParams P, int dtype, int tf_mode, int shade_kind, int knobs, const void *vox_native, ColsAux *aux,
-                           int *status_word, const char **why, hipStream_t s) {
-  *why = nullptr;
-  const int opt_shape = knobs & 0xff, opt_ns = (knobs >> 8) & 0xff, opt_cl = (knobs >> 16) & 0xfff, opt_wstep = (knobs >> 28) & 0x7;
-  if (tf_mode < 0 || tf_mode > 2) { *why = "no classification mode"; return hipErrorNotSupported; }
-  if (tf_mode == 0 && (!P.tlut || P.tlut_size < 1)) { *why = "no colour table"; return hipErrorNotSupported; }
-  if (tf_mode == 0) shade_kind = 0;
-  if (tf_mode == 1 && (!P.tf_vg || P.sv < 2 || P.sg < 2)) { *why = "transfer function smaller than 2x2"; return hipErrorNotSupported; }
-  if (tf_mode == 2 && (!P.tf3d || P.s3v < 1 || P.s3g < 1 || P.s3h < 1)) { *why = "no 3-D table"; return hipErrorNotSupported; }
-  if (P.pert_on) { *why = "perturbation"; return hipErrorNotSupported; }
-  if (P.blend == SMK_BLEND_BACK_TO_FRONT) { *why = "back-to-front blend (columns stream front to back)"; return hipErrorNotSupported; }
-  if (P.depth) { *why = "first-hit depth requested"; return hipErrorNotSupported; }
-  if (P.cplane_on) { *why = "free clip plane"; return hipErrorNotSupported; }
-  if (dtype == 1 && !P.n_in_w) { *why = "4-channel f32 voxels"; return hipErrorNotSupported; }
-  if (P.rc.nplanes <= 0) { *why = "no planes"; return hipErrorNotSupported; }
-  for (int a = 0; a < 3; ++a) {
-    if (P.D[a] < 2 || P.N[a] < 2) { *why = "volume thinner than 2 voxels"; return hipErrorNotSupported; }
-    if (!(P.lo[a] <= P.hin[a])) { *why = "region is empty"; return hipErrorNotSupported; }
-  }
-  if (P.W > 16384 || P.H > 16384) { *why = "viewport larger than 16384"; return hipErrorNotSupported; }
-
-  // principal axis and marching direction from the central ray; every ray must share them
-  double Ac[3], Bc[3];
-  host_ray_cols(P, P.W * 0.5, P.H * 0.5, Ac, Bc);
-  int as = 0;
-  for (int a = 1; a < 3; ++a)
-    if (fabs(Bc[a]) > fabs(Bc[as])) as = a;
-  const int perm = as == 2 ? 0 : (as == 1 ? 1 : 2);
-  const int au = perm == 2 ? 1 : 0, av = perm == 0 ? 1 : 2;
-  const int dir = Bc[as] > 0 ? 1 : -1;
-  double slope_u = 0, slope_v = 0;
-  for (int c = 0; c < 4; ++c) {
-    double A[3], B[3];
-    host_ray_cols(P, (c & 1) ? P.W : 0.0, (c & 2) ? P.H : 0.0, A, B);
-    if (!(B[as] * dir > 0) || fabs(B[as]) < 1e-12) { *why = "rays do not share a marching direction"; return hipErrorNotSupported; }
-    slope_u = std::max(slope_u, fabs(B[au] / B[as]));
-    slope_v = std::max(slope_v, fabs(B[av] / B[as]));
-  }
-  if (slope_u > 3.0 || slope_v > 3.0) { *why = "view too oblique for the principal axis"; return hipErrorNotSupported; }
-
-  ColParams Q;
-  memset(&Q, 0, sizeof Q);
-  Q.dir = dir;
-  Q.Ou = P.O[au]; Q.Ov = P.O[av]; Q.Os = P.O[as];
-  Q.Du = P.D[au]; Q.Dv = P.D[av]; Q.Ds = P.D[as];
-  // voxel -> continuous pixel.  X + .5 = E' + tau d(px, py) with d = Bc + px Bx + py By (per unit of dtau) and
-  // A = E + tau0/dtau * B: (px, py, 1) tau/dtau = G^-1 (X - E), G = [Bx By Bc]
-  {
-    const smk_raycoef &rc = P.rc;
-    const double G[9] = {rc.Bx[0], rc.By[0], rc.Bc[0], rc.Bx[1], rc.By[1], rc.Bc[1], rc.Bx[2], rc.By[2], rc.Bc[2]};
-    double Gi[9];
-    if (!inv3(G, Gi)) { *why = "degenerate projection"; return hipErrorNotSupported; }
-    const double k = (double)rc.tau0 / (double)rc.dtau;
-    const double E[3] = {rc.Ac[0] - k * rc.Bc[0], rc.Ac[1] - k * rc.Bc[1], rc.Ac[2] - k * rc.Bc[2]};
-    double row[3][4];
-    for (int r = 0; r < 3; ++r) {
-      for (int a = 0; a < 3; ++a) row[r][a] = Gi[3 * r + a];
-      row[r][3] = -(Gi[3 * r] * E[0] + Gi[3 * r + 1] * E[1] + Gi[3 * r + 2] * E[2]);
-    }
-    // the sign of the homogeneous coordinate: positive in front of the eye (tau / dtau has dtau's sign)
-    const double sgn = rc.dtau > 0 ? 1.0 : -1.0;
-    for (int a = 0; a < 4; ++a) {
-      Q.Mx[a] = (float)(sgn * (row[0][a] - (double)rc.pxl * row[2][a]) / (double)rc.pxs);
-      Q.My[a] = (float)(sgn * (row[1][a] - (double)rc.pyl * row[2][a]) / (double)rc.pys);
-      Q.Mw[a] = (float)(sgn * row[2][a]);
-    }
-    // scale so that w ~ 1 at the volume's centre (keeps the kernel's "w > 0" test well away from rounding)
-    const double cx = 0.5 * P.N[0], cy = 0.5 * P.N[1], cz = 0.5 * P.N[2];
-    const double wc = Q.Mw[0] * cx + Q.Mw[1] * cy + Q.Mw[2] * cz + Q.Mw[3];
-    if (!(wc > 0)) { *why = "volume centre behind the eye"; return hipErrorNotSupported; }
-    for (int a = 0; a < 4; ++a) {
-      Q.Mx[a] = (float)(Q.Mx[a] / wc);
-      Q.My[a] = (float)(Q.My[a] / wc);
-      Q.Mw[a] = (float)(Q.Mw[a] / wc);
-    }
-  }
-  // ---- workgroup shape and column size.  Every ray that is inside a column at one slice position wants a lane: cells x
-  // rays per cell (largest where the volume is nearest to the eye) must stay below the consumer lanes.
-  const int vb = dtype == 0 ? 8 : 16;
-  auto project = [&](double u, double v, double sc, double &x, double &y) -> bool {
-    double X[3];
-    X[au] = u; X[av] = v; X[as] = sc;
-    const double w = Q.Mw[0] * X[0] + Q.Mw[1] * X[1] + Q.Mw[2] * X[2] + Q.Mw[3];
-    if (!(w > 1e-9)) return false;
-    x = (Q.Mx[0] * X[0] + Q.Mx[1] * X[1] + Q.Mx[2] * X[2] + Q.Mx[3]) / w;
-    y = (Q.My[0] * X[0] + Q.My[1] * X[1] + Q.My[2] * X[2] + Q.My[3]) / w;
-    return true;
-  };
-  // pixels per (u, v) cell of a slice at the volume's corners and centre
-  double dens = 0, flux = 0;
-  for (int c = 0; c < 9; ++c) {
-    const double u = c == 8 ? 0.5 * P.N[au] : ((c & 1) ? P.N[au] - 0.5 : -0.5), v = c == 8 ? 0.5 * P.N[av] : ((c & 2) ? P.N[av] - 0.5 : -0.5),
-                 sc = c == 8 ? 0.5 * P.N[as] : ((c & 4) ? P.N[as] - 0.5 : -0.5);
-    double x0, y0, x1, y1, x2, y2, x3, y3;
-    if (!project(u, v, sc, x0, y0) || !project(u + 1, v, sc, x1, y1) || !project(u, v + 1, sc, x2, y2) || !project(u, v, sc + 1, x3, y3)) {
-      *why = "volume reaches behind the eye";
-      return hipErrorNotSupported;
-    }
-    dens = std::max(dens, fabs((x1 - x0) * (y2 - y0) - (x2 - x0) * (y1 - y0)));
-    flux = std::max(flux, std::max(fabs(x3 - x0), fabs(y3 - y0)));
-  }
-  (void)flux;
-  if (!(dens > 1e-9)) { *why = "degenerate projection"; return hipErrorNotSupported; }
-  int shape = opt_shape ? opt_shape - 1 : 0;
-  if (shape < 0 || shape >= (int)(sizeof kColShapes / sizeof kColShapes[0])) { *why = "no such workgroup shape"; return hipErrorNotSupported; }
-  const ColShape &S = kColShapes[shape];
-  const int lanes = S.nw * 64;
-  // LDS: ring + ray list + entry positions + slot table + two histograms + control + alpha_H + occupancy bitmap
-  const bool three = P.third_axis && P.tf_h;
-  const int use_ah = (tf_mode == 1 && three && P.nelts <= 3 && P.sv >= 2 && P.sv <= 1024) ? 1 : 0;
-  const int fast_tf = (tf_mode == 1 && (!three || use_ah)) ? 1 : 0;
-  const size_t occ_bytes = tf_mode == 1 ? (size_t)P.occ_roww * P.sg * 4 : tf_mode == 2 ? (size_t)P.occ_roww * P.s3g * 4 : 0;
-  const int use_occ = (P.tf_occ && occ_bytes > 0 && occ_bytes <= 16384 && (fast_tf || tf_mode == 2)) ? 1 : 0;
-  const size_t fixed = (size_t)COL_MAX_RAYS * 9 + (size_t)3 * (COL_MAX_CL + 4) * 4 + 32 * 4 + (use_ah ? (size_t)P.sv * 4 : 0) + (use_occ ? occ_bytes : 0) + 64;
-  const size_t lds_cap = 160 * 1024;
-  const int want_slots = opt_ns ? opt_ns : 6;
-  ColLayout &LY = aux->lay[perm];
-  const int cells_u = Q.Du - 1, cells_v = Q.Dv - 1;
-  const double fill = (aux->opt_fill > 0 ? aux->opt_fill : 92) * 0.01;  // of the lanes, at the densest place (the set-up checks every job exactly and reports, see the kernel)
-  auto fits = [&](int cw, int ch, int slots) -> bool {
-    if ((double)cw * ch * dens > fill * lanes) return false;
-    const size_t sb = (((size_t)(cw + 1) * (ch + 1) * vb) + 15) & ~(size_t)15;
-    if (sb * slots + fixed > lds_cap) return false;
-    if ((sb + 1023) / 1024 * 2 > 63) return false;  // two slices in flight per loader within the vmcnt range
-    return true;
-  };
-  bool reuse = LY.d && LY.Du == Q.Du && LY.Dv == Q.Dv && LY.Ds == Q.Ds && LY.src == vox_native && LY.vb == vb;
-  if (reuse) {
-    // an existing layout is kept while its columns fit the lanes and are not wastefully small for the view
-    reuse = fits(LY.CW, LY.CH, 3) && ((double)LY.CW * LY.CH * dens > 0.45 * lanes || (LY.CW >= cells_u && LY.CH >= cells_v));
-  }
-  if (!reuse) {
-    // columns as balanced divisions of the box: the squarest pair that fits, most cells first (least halo)
-    int bw = 0, bh = 0;
-    double best = 1e300;
-    for (int ncu = 1; ncu <= cells_u; ++ncu) {
-      const int cw = (cells_u + ncu - 1) / ncu;
-      if (cw > 255) continue;
-      if (ncu > 1 && (cells_u + ncu - 2) / (ncu - 1) == cw) continue;  // (same width as with one column fewer)
-      for (int ncv = 1; ncv <= cells_v; ++ncv) {
-        const int ch = (cells_v + ncv - 1) / ncv;
-        if (ch > 255) continue;
-        if (ncv > 1 && (cells_v + ncv - 2) / (ncv - 1) == ch) continue;
-        if (!fits(cw, ch, want_slots)) continue;
-        const double over = (double)ncu * (cw + 1) * (double)ncv * (ch + 1) / ((double)cells_u * cells_v);
-        if (over < best) { best = over; bw = cw; bh = ch; }
-      }
-    }
-    if (!bw) { *why = "no column size fits the lanes (view too close)"; return hipErrorNotSupported; }
-    const int ncu = (cells_u + bw - 1) / bw, ncv = (cells_v + bh - 1) / bh;
-    const size_t sb = (((size_t)(bw + 1) * (bh + 1) * vb) + 15) & ~(size_t)15;
-    const size_t bytes = (size_t)ncu * ncv * Q.Ds * sb;
-    size_t free_b = 0, total_b = 0;
-    (void)hipMemGetInfo(&free_b, &total_b);
-    if (LY.d) cols_free_layout(LY);
-    if (bytes + ((size_t)2 << 30) > free_b + 0) {
-      // make room: the other axes' layouts go first
-      for (int k = 0; k < 3; ++k)
-        if (k != perm) cols_free_layout(aux->lay[k]);
-      (void)hipMemGetInfo(&free_b, &total_b);
-      if (bytes + ((size_t)1 << 30) > free_b) { *why = "no memory for the column layout"; return hipErrorNotSupported; }
-    }
-    void *d = nullptr;
-    if (hipMalloc(&d, bytes + 4096) != hipSuccess) { (void)hipGetLastError(); *why = "no memory for the column layout"; return hipErrorNotSupported; }
-    LY.d = d; LY.bytes = bytes; LY.CW = bw; LY.CH = bh; LY.ncu = ncu; LY.ncv = ncv; LY.Du = Q.Du; LY.Dv = Q.Dv; LY.Ds = Q.Ds;
-    LY.slice_bytes = (int)sb; LY.src = vox_native; LY.vb = vb;
-    const size_t total = (size_t)ncu * ncv * Q.Ds * (size_t)(bw + 1) * (bh + 1);
-    const unsigned blocks = (unsigned)((total + 255) / 256);
-    if (total / 256 > 0x7fffffffull) { *why = "volume too large for the layout builder"; return hipErrorNotSupported; }
-#define BUILD(V, R) hipLaunchKernelGGL((smk_k_cols_build<V, R>), dim3(blocks), dim3(256), 0, s, (const V *)vox_native, (char *)d, P.D[0], P.D[1], P.D[2], bw, bh, ncu, ncv, (int)sb)
-    if (dtype == 0) { if (perm == 0) BUILD(uint2, 0); else if (perm == 1) BUILD(uint2, 1); else BUILD(uint2, 2); }
-    else { if (perm == 0) BUILD(float4, 0); else if (perm == 1) BUILD(float4, 1); else BUILD(float4, 2); }
-#undef BUILD
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    ++aux->builds;
-  }
-  Q.lay = (const char *)LY.d;
-  Q.CW = LY.CW; Q.CH = LY.CH; Q.ncu = LY.ncu; Q.ncv = LY.ncv;
-  Q.slice_bytes = LY.slice_bytes;
-  Q.n_ch = (Q.slice_bytes + 1023) / 1024;
-  {
-    const int last_units = Q.slice_bytes / 16 - 64 * (Q.n_ch - 1);
-    Q.last_mask = last_units >= 64 ? ~0ull : ((1ull << last_units) - 1ull);
-  }
-  int nslots = (int)((lds_cap - fixed) / (size_t)Q.slice_bytes);
-  if (opt_ns) nslots = std::min(nslots, opt_ns);
-  nslots = std::min(nslots, 12);
-  if (nslots < 3) { *why = "column slice does not fit LDS three times"; return hipErrorNotSupported; }
-  Q.nslots = nslots;
-  Q.maxfly = std::max(1, std::min(aux->opt_fly > 0 ? aux->opt_fly : 2, (nslots - 2) / S.nl));
-  while (Q.maxfly > 1 && Q.n_ch * Q.maxfly > 63) --Q.maxfly;  // (the counted vmcnt wait takes an immediate < 64)
-  if (Q.n_ch > 63) { *why = "column slice needs more than 63 DMA instructions"; return hipErrorNotSupported; }
-  Q.wstep = opt_wstep ? opt_wstep - 1 : (nslots >= 7 ? 2 : nslots >= 5 ? 1 : 0);
-  Q.take_min = aux->opt_take_min > 0 ? aux->opt_take_min : 16;
-  Q.take_wait = aux->opt_take_wait > 0 ? aux->opt_take_wait - 1 : 3;
-  const int npos_total = Q.Ds - 1;
-  int clmax = opt_cl ? std::min(opt_cl, COL_MAX_CL) : 128;
-  clmax = std::max(clmax, 4);
-  Q.nck = (npos_total + clmax - 1) / clmax;
-  Q.CL = (npos_total + Q.nck - 1) / Q.nck;
-  Q.nck = (npos_total + Q.CL - 1) / Q.CL;
-  Q.nkeys = Q.ncu + Q.ncv + Q.nck - 2;
-  Q.mask_words = (Q.nkeys + 63) / 64;
-  if (Q.mask_words > 8) { *why = "more than 512 segment keys"; return hipErrorNotSupported; }
-  Q.use_ah = use_ah; Q.use_occ = use_occ; Q.fast_tf = fast_tf;
-  const size_t npix = (size_t)P.W * P.H;
-  const size_t lay_bytes = (size_t)Q.nkeys * npix * 16;
-  if (lay_bytes > aux->layers_cap) {
-    if (aux->d_layers) (void)hipFree(aux->d_layers);
-    aux->d_layers = nullptr; aux->layers_cap = 0;
-    if (hipMalloc(&aux->d_layers, lay_bytes) != hipSuccess) { (void)hipGetLastError(); *why = "no memory for the segment layers"; return hipErrorNotSupported; }
-    aux->layers_cap = lay_bytes;
-  }
-  const size_t mask_bytes = npix * Q.mask_words * 8;
-  if (mask_bytes > aux->masks_cap || aux->masks_dirty) {
-    if (mask_bytes > aux->masks_cap) {
-      if (aux->d_masks) (void)hipFree(aux->d_masks);
-      aux->d_masks = nullptr; aux->masks_cap = 0;
-      if (hipMalloc(&aux->d_masks, mask_bytes) != hipSuccess) { (void)hipGetLastError(); *why = "no memory for the segment masks"; return hipErrorNotSupported; }
-      aux->masks_cap = mask_bytes;
-    }
-    hipError_t e = hipMemsetAsync(aux->d_masks, 0, aux->masks_cap, s);
-    if (e != hipSuccess) return e;
-    aux->masks_dirty = false;
-  }
-  aux->mask_words_last = Q.mask_words;
-  const int njobs = Q.ncu * Q.ncv * Q.nck;
-  if (njobs > aux->ticks_cap) {
-    if (aux->d_ticks) (void)hipFree(aux->d_ticks);
-    aux->d_ticks = nullptr; aux->ticks_cap = 0;
-    if (hipMalloc((void **)&aux->d_ticks, (size_t)njobs * 12) != hipSuccess) { (void)hipGetLastError(); *why = "no memory"; return hipErrorNotSupported; }
-    aux->ticks_cap = njobs;
-  }
-  if (!aux->d_counts) {
-    if (hipMalloc((void **)&aux->d_counts, 8 * 8) != hipSuccess) { (void)hipGetLastError(); *why = "no memory"; return hipErrorNotSupported; }
-  }
-  Q.layers = (float4 *)aux->d_layers;
-  Q.masks = (unsigned long long *)aux->d_masks;
-  Q.status = status_word;
-  Q.status_tag = aux->status_tag;
-  Q.job_ticks = aux->d_ticks;
-  Q.counts = aux->want_counts ? aux->d_counts : nullptr;
-  if (Q.counts) {
-    hipError_t e = hipMemsetAsync(aux->d_counts, 0, 64, s);
-    if (e != hipSuccess) return e;
-  }
-  aux->njobs_last = njobs;
-  aux->last = Q.CW | (Q.CH << 8) | (nslots << 16) | (shape << 24);
-  aux->last_stream_bytes = (double)njobs / Q.nck * ((double)npos_total + Q.nck) * Q.slice_bytes;
-  Q.ring_bytes = (int)std::max((size_t)nslots * Q.slice_bytes, (size_t)COL_MAX_RAYS * 16);  // (set-up scratch: the unsorted rays)
-  const size_t lds = (size_t)Q.ring_bytes + fixed;
-  if (lds > lds_cap) { *why = "column job does not fit LDS"; return hipErrorNotSupported; }
-  if (aux->frame_ev0) {
-    hipError_t e = hipEventRecord(aux->frame_ev0, s);
-    if (e != hipSuccess) return e;
-  }
-  hipError_t e = hipErrorInvalidValue;
+// the modes with an instance: {voxel type, classification mode, shading}
+hipError_t smk_cols_march(const RenderParams &P, const ColParams &Q, int dtype, int tf_mode, int shade_kind, int perm, int shape, size_t lds,
+                          int njobs, hipStream_t s) {
 #define CASE(D, T, SHK) \
-  if (dtype == D && tf_mode == T && shade_kind == SHK) e = dispatch_perm<D, SHK, T>(P, Q, perm, shape, lds, njobs, s);
+  if (dtype == D && tf_mode == T && shade_kind == SHK) return dispatch_perm<D, SHK, T>(P, Q, perm, shape, lds, njobs, s);
   CASE(0, 1, 0) CASE(0, 1, 1) CASE(1, 1, 0) CASE(1, 1, 1) CASE(0, 2, 1) CASE(1, 2, 1) CASE(0, 0, 0)
 #undef CASE
-  if (e == hipErrorInvalidValue) { *why = "no column-stream instance for this mode"; return hipErrorNotSupported; }
-  if (e != hipSuccess) return e;
-  aux->masks_dirty = true;  // (until the resolve pass below has run; it clears what it reads)
-  hipLaunchKernelGGL(smk_k_cols_resolve, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, (const float4 *)aux->d_layers,
-                     (unsigned long long *)aux->d_masks, Q.mask_words, npix, P.out, P.blend == SMK_BLEND_MAX ? 1 : 0);
-  e = hipGetLastError();
-  if (e == hipSuccess) aux->masks_dirty = false;
-  return e;
+  return hipErrorInvalidValue;
+}
+
+hipError_t smk_cols_resolve(const float4 *layers, unsigned long long *masks, int mask_words, size_t npix, float4 *out, int use_max,
+                            hipStream_t s) {
+  hipLaunchKernelGGL(smk_k_cols_resolve, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, layers, masks, mask_words, npix, out, use_max);
+  return hipGetLastError();
 }

@@ -213,12 +213,12 @@ static KernelChoice choose_kernel(smk_ctx *c, const RenderParams &P, bool with_d
   return k;
 }
 
-// the column-stream kernel, forced (smk_cols.hip)
+// the column-stream kernel, forced (smk_cols_plan.hip)
 static int launch_cols(smk_ctx *c, const RenderParams &P, hipStream_t s) {
   if (status_ring_ready(c)) return 1;
   const char *why = nullptr;
   c->cols.frame_ev0 = c->ev0;
-  hipError_t e = smk_launch_cols(P, c->dtype, c->tf_mode, smk_shade_kind(c), c->opt_cols, c->d_vox, &c->cols,
+  hipError_t e = smk_launch_cols(P, c->dtype, c->tf_mode, smk_shade_kind(c), c->d_vox, &c->cols,
                                  c->slab.h_status + c->slab.status_slot, &why, s);
   if (e == hipErrorNotSupported) {
     c->slab_why = why ? why : "?";

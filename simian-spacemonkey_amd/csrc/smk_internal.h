@@ -180,7 +180,7 @@ struct SlabAux {
   int trace_cap = 0, trace_n = 0;
 };
 
-// the column-stream kernel's side buffers (smk_cols.hip), owned by the context
+// the column-stream kernel's side buffers (smk_cols_plan.hip), owned by the context
 struct ColLayout {  // the stored box re-laid out for one principal axis: [cv][cu][s][(CH+1)][(CW+1)] voxels
   void *d = nullptr;
   size_t bytes = 0;
@@ -199,9 +199,12 @@ struct ColsAux {
   int ticks_cap = 0, njobs_last = 0;
   unsigned long long *d_counts = nullptr;  // [8] developer statistics of the latest frame (ColParams::counts)
   int want_counts = 0;
-  int opt_fill = 0, opt_take_min = 0, opt_take_wait = 0, opt_fly = 0;  // developer knobs (smk_set_option cols_fill / cols_take_min / cols_take_wait)
+  // developer knobs (smk_set_option cols_shape, cols_ns, cols_chunk, cols_wstep, cols_fill, cols_take_min, cols_take_wait,
+  // cols_fly; 0 = the planner decides)
+  int opt_shape = 0, opt_ns = 0, opt_chunk = 0, opt_wstep = 0;
+  int opt_fill = 0, opt_take_min = 0, opt_take_wait = 0, opt_fly = 0;
   int builds = 0;               // layouts built so far
-  int last = 0;                 // CW | CH << 8 | nslots << 16 | shape << 24 of the latest launch
+  int cw_last = 0, ch_last = 0, nslots_last = 0, shape_last = 0;  // columns, ring slots and workgroup shape of the latest launch
   double last_stream_bytes = 0; // bytes the loaders of the latest launch had to stream
   hipEvent_t frame_ev0 = nullptr;
   int status_tag = 0;           // the frame's id << 8 (written with a status word)
@@ -372,8 +375,7 @@ struct smk_ctx {
   int opt_inject_status = 0;  // (test hook) the next slice-ring frame reports this status word
   int opt_wave_w = 8, opt_blk_w = 2, opt_lockstep = 1;
   SlabAux slab;  // slice-ring kernel side buffers
-  ColsAux cols;  // column-stream kernel side buffers
-  int opt_cols = 0;  // developer knobs of the column-stream kernel: shape | slots << 8 | chunk << 16 | (wstep + 1) << 28
+  ColsAux cols;  // column-stream kernel side buffers and knobs
   // auto mode (option kernel = 0) picks the ray-marcher by measurement: the first frames of a
   // new configuration run the slice-ring kernel, then the gather kernel (bit-identical frames),
   // and the faster one is kept for that configuration
@@ -423,9 +425,9 @@ hipError_t smk_launch_slab(RenderParams P, int dtype, int tf_mode, int shade_kin
                            const char **why, hipStream_t s);
 // the measured weights and depth cuts belong to the volume they were measured on: forgotten on a time-step switch
 void smk_slab_forget_measurements(SlabAux *aux);
-// the column-stream kernel (smk_cols.hip); same convention as smk_launch_slab
-hipError_t smk_launch_cols(RenderParams P, int dtype, int tf_mode, int shade_kind, int knobs, const void *vox_native, ColsAux *aux,
-                           int *status_word, const char **why, hipStream_t s);
+// the column-stream kernel (smk_cols_plan.hip); same convention as smk_launch_slab
+hipError_t smk_launch_cols(RenderParams P, int dtype, int tf_mode, int shade_kind, const void *vox_native, ColsAux *aux, int *status_word,
+                           const char **why, hipStream_t s);
 
 // a few host threads for the per-frame planning (smk_api.hip): run(n, f) calls f(0) .. f(n - 1), f(0) on the caller
 #include <functional>
@@ -450,6 +452,14 @@ int smk_pack_step(smk_ctx *c, const char *who, const SmkVolGeom &g, const smk_vo
 // ts[k] becomes the step frames render (its brick flags are made again before the next frame)
 void smk_use_step(smk_ctx *c, int k);
 
+// n words a kernel of the latest frame wrote (ticks, counters), read once the device has finished it; synchronises
+template <class T>
+static int read_back(smk_ctx *c, T *h, const T *d, size_t n) {
+  HIPCHK(c, hipDeviceSynchronize());
+  HIPCHK(c, hipMemcpy(h, d, n * sizeof(T), hipMemcpyDeviceToHost));
+  return 0;
+}
+
 // host set-up shared by the C ABI's files (smk_api.hip; hidden: not part of the library's interface)
 #pragma GCC visibility push(hidden)
 int smk_build_params(smk_ctx *c, RenderParams &P, hipStream_t s);  // a frame's RenderParams from the context (no shadows)
@@ -461,6 +471,9 @@ void smk_inverse_affine(double inv[16], const double m[16]);
 int smk_make_xmajor_copy(smk_ctx *c);
 int smk_frame_buffers(smk_ctx *c);  // (smk_frame.hip)
 void smk_slab_free(SlabAux *aux);  // (smk_slab_plan.hip)
+// a ray's coefficients on the host, for planning, at a real-valued position (px, py) of the image plane (smk_slab_plan.hip)
+void host_ray_at(const RenderParams &P, double px, double py, double A[3], double B[3]);
+int smk_cols_stat(smk_ctx *c, const char *name, double *value);  // smk_get_stat "cols_*" (smk_cols_plan.hip)
 // frames with shadows (smk_shadow_plan.hip): the half-angle slices and boxes of P (S, halo_need: a shard's); the light
 // samples a context owns (smk_get_stat); and a frame's shadow stage -- the light march (*marched), else the whole frame
 // as a launch per slice

@@ -18,7 +18,7 @@
 
 // a ray's coefficients on the host, for planning: at a real-valued position (px, py) of the image plane, in double -- the
 // kernels' float chains (smk_ray_AB) round differently by less than the planning's own slack
-static void host_ray_at(const RenderParams &P, double px, double py, double A[3], double B[3]) {
+void host_ray_at(const RenderParams &P, double px, double py, double A[3], double B[3]) {
   const smk_raycoef &rc = P.rc;
   if (!P.sh.on) {
     for (int a = 0; a < 3; ++a) {

@@ -118,3 +118,38 @@ def test_sample_count_equals_the_in_volume_samples(R):
     a, b = _both(R, sc, cols_chunk=8)
     assert np.abs(b - ref).max() <= TOL
     assert R.stat("cols_samples") == want
+
+
+# the planner's refusals that frame inputs and knobs reach, each on a frame that passes every check before it
+_REFUSALS = {
+    "perturbation": "perturbation",
+    "back_to_front": "back-to-front blend (columns stream front to back)",
+    "depth": "first-hit depth requested",
+    "clip_plane": "free clip plane",
+    "cols_shape": "no such workgroup shape",
+    "cols_ns": "column slice does not fit LDS three times",
+}
+
+
+@pytest.mark.parametrize("case", sorted(_REFUSALS))
+def test_forced_kernel_reports_why_it_cannot_run(R, smk, case):
+    sc = make_scene("cfg3", n=32, size=48, steps=48, pose="rot", f32=True, shade=1, pert=case == "perturbation")
+    if case == "clip_plane":
+        sc.clip_plane = (0.0, 0.0, -1.0, -6.0)
+    knobs = {"cols_shape": {"cols_shape": 3}, "cols_ns": {"cols_ns": 2}}.get(case, {})
+    try:
+        push_scene(R, sc)
+        R.set_blend(1 if case == "back_to_front" else 0)
+        for k, v in knobs.items():
+            R.set_option(k, v)
+        R.set_option("kernel", 3)
+        with pytest.raises(smk.SmkError) as e:
+            R.render(depth=case == "depth")
+        assert str(e.value).endswith("not applicable: " + _REFUSALS[case]), str(e.value)
+    finally:
+        for k in knobs:
+            R.set_option(k, 0)
+        R.set_option("kernel", 0)
+        R.set_blend(0)
+        R.set_clip_plane(None)
+        R.set_perturb(None, None, None)
