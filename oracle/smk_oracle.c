@@ -733,7 +733,7 @@ int orc_render_shadow(const orc_volume *v, const orc_classify *tf, const orc_cam
   if (tf->mode == ORC_TF_1D || (sh && sh->mode == ORC_SHADE_NV20)) return 2;
   const int W = cam->width, H = cam->height, LB = sc->LB;
   /* the box both passes sample in: the volume, or what an orthogonal clip plane leaves of it (both passes draw the same
-   * clipped slice polygons, and glClipPlane stays enabled through both); closed */
+   * clipped slice polygons, and glClipPlane stays enabled through both), closed and 2^-10 voxels wide in both passes */
   float blo[3], bhi[3];
   int btop[3];
   region_box(v, blo, bhi, btop);
@@ -813,7 +813,8 @@ int orc_render_shadow(const orc_volume *v, const orc_classify *tf, const orc_cam
         for (int q = 0; q < 3; ++q) {
           const float G = fmaf(a, sc->Gx[q], fmaf(b, sc->Gy[q], sc->Gc[q]));
           p[q] = fmaf(w, G, sc->Lc[q]);
-          if (!(p[q] >= blo[q] && p[q] <= bhi[q])) in = 0;
+          /* (the same 2^-10-voxel-wide box as the eye pass: the slice ON a face is one polygon, drawn in both passes) */
+          if (!(p[q] >= blo[q] - 0.0009765625f && p[q] <= bhi[q] + 0.0009765625f)) in = 0;
         }
         if (!in) continue;
         if (v->cplane_on && !(fmaf(p[0], v->cplane[0], fmaf(p[1], v->cplane[1], fmaf(p[2], v->cplane[2], v->cplane[3]))) >= 0.0f)) continue;

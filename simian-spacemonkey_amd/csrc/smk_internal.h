@@ -13,7 +13,7 @@
 #define SMK_MAX_RANKS 8
 #define SMK_TIMING_RING 64
 #define SMK_BRICK_LOG2 3   // bricks of 8x8x8 cells (smk_bricks.hip)
-#define SMK_SHADOW_BOX_EPS 0.0009765625f  // voxels: frames with shadows test an eye sample against the box widened by this (smk_shadow_plan.hip)
+#define SMK_SHADOW_BOX_EPS 0.0009765625f  // voxels: frames with shadows test eye and light samples against the box widened by this (smk_shadow_plan.hip)
 #define SMK_TUNE_SETTLE 6  // auto mode: untimed slice-ring frames before a new configuration's timed trial (smk_frame.hip)
 #define SMK_STATUS_RING 8  // frames whose slice-ring status stays readable (smk_frame_failed)
 

@@ -266,9 +266,11 @@ int smk_shadow_setup(smk_ctx *c, RenderParams &P, smk_shadowcoef &sc, SmkShadowS
   // the eye) -- where a sample's coordinate, the end of an fma chain, lands on either side of the face by rounding.  The
   // reference draws that slice (a polygon clipped against the box keeps its boundary); the eye pass's membership test is
   // therefore 2^-10 voxels wide of the box (clamp-to-edge fetches: the value at the face).  The CPU checker does the same.
-  // Clip planes (round 3): both passes draw the same clipped slice polygons in the reference (volShadow slices the box
-  // setupClips left; glClipPlane stays enabled), so a light ray's sample must lie in the same box (closed, no slack: its
-  // last slice gets no special treatment in rounds 1-2 either) and on the kept side of the free plane.
+  // The light pass draws the same polygon, so a light ray's sample is tested against the same widened box: with a closed
+  // box the light samples of a face-coincident last slice fell outside by rounding and the slice was missing from the
+  // light buffer alone (tests/test_shadow_witness.py::test_face_coincident_last_slice).  Clip planes: both passes draw
+  // the same clipped slice polygons in the reference (volShadow slices the box setupClips left; glClipPlane stays
+  // enabled), so a light ray's sample must lie in the same box and on the kept side of the free plane.
   float wlo[3], whi[3];
   int wtop[3];
   const int z0[3] = {0, 0, 0};
@@ -276,10 +278,10 @@ int smk_shadow_setup(smk_ctx *c, RenderParams &P, smk_shadowcoef &sc, SmkShadowS
   float olo[3], ohi[3];
   for (int a = 0; a < 3; ++a) {
     const bool inner_lo = c->g0[a] > 0 && P.lo[a] == (float)c->g0[a] - 0.5f, inner_hi = !P.top[a];
-    h.llo[a] = wlo[a];
-    h.lhi[a] = whi[a];
-    olo[a] = P.lo[a];
-    ohi[a] = inner_hi ? nextafterf(P.hi[a], -INFINITY) : P.hi[a];
+    h.llo[a] = wlo[a] - SMK_SHADOW_BOX_EPS;
+    h.lhi[a] = whi[a] + SMK_SHADOW_BOX_EPS;
+    olo[a] = inner_lo ? P.lo[a] : P.lo[a] - SMK_SHADOW_BOX_EPS;
+    ohi[a] = inner_hi ? nextafterf(P.hi[a], -INFINITY) : P.hi[a] + SMK_SHADOW_BOX_EPS;
     if (!inner_lo) P.lo[a] -= SMK_SHADOW_BOX_EPS;
     if (inner_hi) P.hin[a] = nextafterf(P.hi[a], -INFINITY);
     else {
