@@ -200,6 +200,29 @@ int smk_render(smk_ctx *ctx, float *rgba_out, float *depth_out);
  * frames -- and six of them wait for the frame before them on `stream`: a one-time stall per configuration.) */
 int smk_render_device(smk_ctx *ctx, void *d_rgba, void *d_depth, void *stream);
 
+/* ---- the host's opaque geometry in front of, behind and inside the volume.  The reference draws every slice with the
+ * depth test on and depth writes off (R8kVolRen3D.cpp:380 "no depth wright, only depth test", :1447-1448;
+ * NV20VolRen3D.cpp:932-933) under glDepthFunc(GL_LESS) (gluvv.cpp:559), into the frame gluvv's widgets and other primitives
+ * were drawn into: opaque geometry hides the part of the volume behind it.  Here: a sample exists only if its view depth --
+ * the value depth_out reports, tau * znear of smk_get_raycoef / smk_get_shadowcoef -- is LESS than the pixel's scene depth.
+ * scene_depth: [height][width] floats of the whole window, row 0 = bottom (rgba_out's layout; the same full-window buffer
+ * on a shard), of the kind
+ *   SMK_SCENE_VIEW_DEPTH:   the view depth d itself (the units of smk_set_camera's clip);
+ *   SMK_SCENE_WINDOW_DEPTH: what glReadPixels(GL_DEPTH_COMPONENT, GL_FLOAT) returns, z_w in [0, 1]; converted per pixel
+ *                           to d = f n / (f - z_w (f - n)), (n, f) = smk_set_camera's clip, evaluated in DOUBLE precision
+ *                           and rounded once to float (every kernel the same way).  z_w >= 1 (a cleared buffer) means no
+ *                           occluder.
+ * NaN means no occluder (+inf) in both kinds.  The test applies under every blend mode, depth_out, clip planes (both
+ * forms), smk_set_region, perturbation, time steps, bricked uploads and shards.  With shadows only the eye pass is
+ * occluded: the light buffer is the unoccluded frame's (the reference's light pbuffer holds the volume alone).  Option
+ * "kernel" 3 (column-stream) refuses such frames; auto mode never takes it.  smk_render_slice is not affected.
+ * smk_render_occluded copies scene_depth at the call; smk_render_occluded_device reads the DEVICE buffer d_scene_depth on
+ * `stream` (the caller keeps it alive until the stream has passed the frame).  A NULL buffer makes them exactly smk_render /
+ * smk_render_device.  A bad kind fails with the reason.  (INTEGRATION.md "Depth for the GL host".) */
+typedef enum { SMK_SCENE_VIEW_DEPTH = 0, SMK_SCENE_WINDOW_DEPTH = 1 } smk_scene_depth_kind;
+int smk_render_occluded(smk_ctx *ctx, const float *scene_depth, int kind, float *rgba_out, float *depth_out);
+int smk_render_occluded_device(smk_ctx *ctx, const void *d_scene_depth, int kind, void *d_rgba, void *d_depth, void *stream);
+
 /* replaces VolumeRenderer::renderSlice(quad, alpha) (VolumeRenderer.h:114, VolumeRenderer.cpp:748-807): ONE quad (model
  * space, the units of fPos / fSize; drawn as glBegin(GL_QUADS) with the vertices in the order 1, 0, 2, 3) textured with the
  * scalar volume -- GL_INTENSITY8, GL_LINEAR, no colour table (:768), texture coordinates = vertex / fSize -- modulated by

@@ -31,12 +31,15 @@ ABI_SYMBOLS = [
     "smk_set_timestep_cache", "smk_upload_timestep", "smk_upload_timestep_device", "smk_select_timestep",
     "smk_get_timesteps",
     "smk_composite_over_depth_device", "smk_exchange_partial_depth", "smk_exchange_frame_depth", "smk_exchange_frame_local_depth",
+    "smk_render_occluded", "smk_render_occluded_device",
 ]
 
 # gluvvDataMode order (gluvv.h:221-235)
 GDM = {n: i for i, n in enumerate(
     ["V1", "V1G", "V1GH", "V2", "V2G", "V2GH", "V3", "V3G", "V4", "VGH", "VGH_VG", "VGH_V"])}
 SHADE = {"none": 0, "r8k_diff": 1, "r8k": 2, "nv20_diff": 3, "nv20": 4}
+# smk_scene_depth_kind: what a scene depth handed to Renderer.render / render_device holds
+SCENE_VIEW_DEPTH, SCENE_WINDOW_DEPTH = 0, 1
 
 
 class SmkError(RuntimeError):
@@ -155,6 +158,8 @@ def load_library():
     L.smk_get_brick_flags.argtypes = [C.c_void_p, C.c_void_p, P(C.c_int), P(C.c_int)]
     L.smk_render.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.smk_render_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.smk_render_occluded.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.smk_render_occluded_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.smk_composite_over_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, P(C.c_int), C.c_int,
                                             C.c_void_p, C.c_void_p]
     L.smk_composite_over_depth_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, P(C.c_int), C.c_int,
@@ -473,15 +478,27 @@ class Renderer:
         self._ck(self.L.smk_set_option(self.ctx, key.encode(), int(value)))
 
     # -- render
-    def render(self, depth=False):
+    def render(self, depth=False, scene_depth=None, scene_depth_kind=SCENE_VIEW_DEPTH):
+        """one frame to host memory; scene_depth: the host's opaque scene depth, [h][w] floats of the window (row 0 at the
+        bottom) of the kind SCENE_VIEW_DEPTH or SCENE_WINDOW_DEPTH -- a sample exists only in front of it (smk_render_occluded)"""
         w, h = self.size
         out = np.zeros((h, w, 4), np.float32)
         dep = np.zeros((h, w), np.float32) if depth else None
-        self._ck(self.L.smk_render(self.ctx, _ptr(out), _ptr(dep)))
+        if scene_depth is None:
+            self._ck(self.L.smk_render(self.ctx, _ptr(out), _ptr(dep)))
+        else:
+            zs = np.ascontiguousarray(scene_depth, dtype=np.float32)
+            if zs.shape != (h, w):
+                raise ValueError("scene_depth must be [%d][%d] floats, got shape %s" % (h, w, zs.shape))
+            self._ck(self.L.smk_render_occluded(self.ctx, _ptr(zs), int(scene_depth_kind), _ptr(out), _ptr(dep)))
         return (out, dep) if depth else out
 
-    def render_device(self, d_rgba, d_depth=None, stream=None):
-        self._ck(self.L.smk_render_device(self.ctx, d_rgba, d_depth, stream))
+    def render_device(self, d_rgba, d_depth=None, stream=None, d_scene_depth=None, scene_depth_kind=SCENE_VIEW_DEPTH):
+        """d_scene_depth: a DEVICE buffer of [h][w] floats read on `stream` (smk_render_occluded_device), or None"""
+        if d_scene_depth is None:
+            self._ck(self.L.smk_render_device(self.ctx, d_rgba, d_depth, stream))
+        else:
+            self._ck(self.L.smk_render_occluded_device(self.ctx, d_scene_depth, int(scene_depth_kind), d_rgba, d_depth, stream))
 
     def composite_over_device(self, d_layers, nlayers, order, npix, d_out, stream=None):
         self._ck(self.L.smk_composite_over_device(self.ctx, d_layers, nlayers,

@@ -168,7 +168,7 @@ extern "C" void smk_destroy(smk_ctx *c) {
   if (c->tf_stream) { (void)hipStreamSynchronize(c->tf_stream); (void)hipStreamDestroy(c->tf_stream); }
   free_brick_set(c->br3);
   smk_cols_free(&c->cols);
-  void *ptrs[] = {c->d_light_hist, c->d_shadow_entries, c->d_shadow_exports, c->d_shadow_barrier, c->d_tf_raw, c->d_tlut, c->d_tf_h, c->d_tf3d, c->d_tf3d_occ, c->d_noise, c->d_out, c->d_depth, c->d_light[0], c->d_light[1]};
+  void *ptrs[] = {c->d_light_hist, c->d_shadow_entries, c->d_shadow_exports, c->d_shadow_barrier, c->d_tf_raw, c->d_tlut, c->d_tf_h, c->d_tf3d, c->d_tf3d_occ, c->d_noise, c->d_out, c->d_depth, c->d_zscene, c->d_light[0], c->d_light[1]};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   smk_slab_free(&c->slab);

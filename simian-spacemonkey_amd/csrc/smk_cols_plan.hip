@@ -27,6 +27,7 @@ struct ColPlan {
 
 // ---- refusal: frames the kernel does not take, in this order
 static const char *cols_refusal(const RenderParams &P, int dtype, int tf_mode) {
+  if (P.zscene) return "scene depth";  // (smk_render_occluded: the ray-marchers take such frames)
   if (tf_mode < 0 || tf_mode > 2) return "no classification mode";
   if (tf_mode == 0 && (!P.tlut || P.tlut_size < 1)) return "no colour table";
   if (tf_mode == 1 && (!P.tf_vg || P.sv < 2 || P.sg < 2)) return "transfer function smaller than 2x2";

@@ -366,6 +366,29 @@ __device__ __forceinline__ float smk_plane_depth_px(const RenderParams &P, int m
   return smk_plane_depth<true>(P, m, __fdiv_rn(sh.numA, nD), __fdiv_rn(sh.dB, nD));
 }
 
+// ---- the host's opaque scene depth (smk_render_occluded; the reference's depth test, GL_LESS with depth writes off,
+// R8kVolRen3D.cpp:380, 1447-1448, gluvv.cpp:559): the view depth D of pixel o -- a sample exists only where its
+// smk_plane_depth is less than D.  Window depths (glReadPixels) are turned into view depths in double,
+// d = f n / (f - z (f - n)), rounded once to float; z >= 1 (a cleared buffer) and NaN mean no occluder in both kinds.
+__device__ __forceinline__ float smk_scene_depth(const RenderParams &P, size_t o) {
+  const float z = P.zscene[o];
+  if (P.zscene_kind == SMK_SCENE_WINDOW_DEPTH) return z < 1.0f ? (float)(P.zs_fn / (P.zs_f - (double)z * P.zs_fmn)) : __int_as_float(0x7f800000);
+  return z == z ? z : __int_as_float(0x7f800000);
+}
+// The planes of a ray with smk_plane_depth(m) < D.  That depth, fma(m, dtau, tau0) * znear (znear > 0), is monotone in m:
+// the planes form one interval, a prefix (dtau > 0) or a suffix (dtau < 0) of the ray.  Its end is bracketed here with two
+// planes of slack (like the clip plane's fold); the caller tests the ends exactly with smk_plane_depth itself.
+__device__ __forceinline__ void smk_scene_bracket(float D, float tau0, float dtau, float znear, float &tenter, float &texit, bool &empty) {
+  if (fabsf(dtau) > 1e-30f) {
+    // (D = +inf: no bound; D = -inf: an empty ray; clamped so that the caller's float-to-int conversions stay defined)
+    const float tz = fminf(fmaxf((D / znear - tau0) / dtau, -4.0f), 1073741824.0f);
+    if (dtau > 0.0f) texit = fminf(texit, tz + 2.0f);
+    else tenter = fmaxf(tenter, tz - 2.0f);
+  } else if (!(tau0 * znear < D)) {
+    empty = true;
+  }
+}
+
 // bilinear lookup of a light buffer; texels outside it are 0 (the rest of the pbuffer stays cleared)
 __device__ __forceinline__ void smk_light_lookup(const float4 *L, int LB, float lx, float ly, float out[3]) {
   const float fx0 = floorf(lx - 0.5f), fy0 = floorf(ly - 0.5f);

@@ -122,6 +122,7 @@ static int frame_open(smk_ctx *c, RenderParams &P, void *d_rgba, void *d_depth) 
                : c->tf_mode == 1 ? 4.0 * c->sv * c->sg * (P.third_axis ? 2 : 1)
                                  : 4.0 * c->s3v * c->s3g * c->s3h;
   c->last_alg_bytes = (double)nst * bv + tfb + 16.0 * c->W * c->H;
+  if (P.zscene) c->last_alg_bytes += 4.0 * c->W * c->H;  // (the host's scene depth: one float per pixel read)
   if (c->tev0.empty()) {
     c->tev0.resize(SMK_TIMING_RING);
     c->tev1.resize(SMK_TIMING_RING);
@@ -170,7 +171,7 @@ static KernelChoice choose_kernel(smk_ctx *c, const RenderParams &P, bool with_d
                                   (unsigned long long)c->sv, (unsigned long long)c->sg, (unsigned long long)with_depth,
                                   (unsigned long long)P.pert_on, (unsigned long long)c->tf_mode, (unsigned long long)c->s3v,
                                   (unsigned long long)c->s3g, (unsigned long long)c->s3h, (unsigned long long)c->blend,
-                                  (unsigned long long)P.sh.on};
+                                  (unsigned long long)P.sh.on, (unsigned long long)(P.zscene != nullptr)};
   k.sig = 1469598103934665603ull;
   for (unsigned long long v : f) k.sig = (k.sig ^ v) * 1099511628211ull;
   auto it = c->tune_choice.find(k.sig);
@@ -285,13 +286,31 @@ static int frame_close(smk_ctx *c, hipStream_t s, int trial) {
   return 0;
 }
 
-extern "C" int smk_render_device(smk_ctx *c, void *d_rgba, void *d_depth, void *stream) {
+// The kind of a scene depth handed to smk_render_occluded[_device] (checked with or without a buffer)
+static int scene_depth_kind_check(smk_ctx *c, const char *who, int kind) {
+  if (kind != SMK_SCENE_VIEW_DEPTH && kind != SMK_SCENE_WINDOW_DEPTH)
+    FAIL(c, "%s: bad scene depth kind %d (SMK_SCENE_VIEW_DEPTH = 0 or SMK_SCENE_WINDOW_DEPTH = 1)", who, kind);
+  return 0;
+}
+
+// A frame on `stream`; d_zscene: the host's opaque scene depth on the device ([H][W] floats of that kind), or null
+static int render_frame(smk_ctx *c, const char *who, void *d_rgba, void *d_depth, const float *d_zscene, int zkind, void *stream) {
   if (!c) return 1;
   HIPCHK(c, hipSetDevice(c->device));
-  if (!d_rgba) FAIL(c, "smk_render_device: null output");
+  if (!d_rgba) FAIL(c, "%s: null output", who);
   RenderParams P;
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   if (smk_build_params(c, P, s)) return 1;
+  if (d_zscene) {
+    P.zscene = d_zscene;
+    P.zscene_kind = zkind;
+    const double n = c->clip[0], f = c->clip[1];
+    if (zkind == SMK_SCENE_WINDOW_DEPTH && !(f > n))
+      FAIL(c, "%s: window depths need a far plane beyond the near plane (clip = %g, %g)", who, n, f);
+    P.zs_fn = f * n;
+    P.zs_f = f;
+    P.zs_fmn = f - n;
+  }
   if (frame_open(c, P, d_rgba, d_depth)) return 1;
   bool marched = false;  // (a frame with shadows opens the kernel-time bracket before its light march)
   if (c->shadow_on) {
@@ -306,6 +325,16 @@ extern "C" int smk_render_device(smk_ctx *c, void *d_rgba, void *d_depth, void *
     FAIL(c, "smk_render: slab kernel forced but classification mode %d is gather-only", c->tf_mode);
   if (c->last_kernel == 1 && launch_gather(c, P, marched, s)) return 1;
   return frame_close(c, s, k.trial);
+}
+
+extern "C" int smk_render_device(smk_ctx *c, void *d_rgba, void *d_depth, void *stream) {
+  return render_frame(c, "smk_render_device", d_rgba, d_depth, nullptr, 0, stream);
+}
+
+extern "C" int smk_render_occluded_device(smk_ctx *c, const void *d_scene_depth, int kind, void *d_rgba, void *d_depth, void *stream) {
+  if (!c) return 1;
+  if (scene_depth_kind_check(c, "smk_render_occluded_device", kind)) return 1;
+  return render_frame(c, "smk_render_occluded_device", d_rgba, d_depth, (const float *)d_scene_depth, kind, stream);
 }
 
 // the context's own W x H frame and depth buffers (smk_render, smk_render_slice)
@@ -323,14 +352,28 @@ int smk_frame_buffers(smk_ctx *c) {
   return 0;
 }
 
-extern "C" int smk_render(smk_ctx *c, float *rgba, float *depth) {
+// A frame to host memory, rendered again on the gather kernel if the slice-ring kernel flags it; scene_depth: the host's
+// opaque scene depth in HOST memory, or null
+static int render_host(smk_ctx *c, const char *who, float *rgba, float *depth, const float *scene_depth, int zkind) {
   if (!c) return 1;
   HIPCHK(c, hipSetDevice(c->device));
-  if (!rgba) FAIL(c, "smk_render: null output");
-  if (!c->have_camera) FAIL(c, "smk_render: no camera set");
+  if (!rgba) FAIL(c, "%s: null output", who);
+  if (!c->have_camera) FAIL(c, "%s: no camera set", who);
   size_t npix = (size_t)c->W * c->H;
   if (smk_frame_buffers(c)) return 1;
-  if (smk_render_device(c, c->d_out, depth ? c->d_depth : nullptr, c->stream)) return 1;
+  const float *d_zscene = nullptr;
+  if (scene_depth) {  // (staged in the context's buffer: the re-render below reads the same one)
+    if (npix > c->zscene_cap) {
+      if (c->d_zscene) (void)hipFree(c->d_zscene);
+      c->d_zscene = nullptr;
+      c->zscene_cap = 0;
+      HIPCHK(c, hipMalloc((void **)&c->d_zscene, npix * 4));
+      c->zscene_cap = npix;
+    }
+    HIPCHK(c, hipMemcpy(c->d_zscene, scene_depth, npix * 4, hipMemcpyHostToDevice));
+    d_zscene = c->d_zscene;
+  }
+  if (render_frame(c, who, c->d_out, depth ? c->d_depth : nullptr, d_zscene, zkind, c->stream)) return 1;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
   if (check_frame_status(c, c->frame_id)) {
@@ -339,7 +382,7 @@ extern "C" int smk_render(smk_ctx *c, float *rgba, float *depth) {
     if (c->opt_kernel != 0) return 1;
     const std::string first = c->err;
     ++c->slab_retries;
-    if (smk_render_device(c, c->d_out, depth ? c->d_depth : nullptr, c->stream)) return 1;
+    if (render_frame(c, who, c->d_out, depth ? c->d_depth : nullptr, d_zscene, zkind, c->stream)) return 1;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->last_kernel != 1 || check_frame_status(c, c->frame_id)) {
       c->err = first;
@@ -350,4 +393,12 @@ extern "C" int smk_render(smk_ctx *c, float *rgba, float *depth) {
   HIPCHK(c, hipMemcpy(rgba, c->d_out, npix * 16, hipMemcpyDeviceToHost));
   if (depth) HIPCHK(c, hipMemcpy(depth, c->d_depth, npix * 4, hipMemcpyDeviceToHost));
   return 0;
+}
+
+extern "C" int smk_render(smk_ctx *c, float *rgba, float *depth) { return render_host(c, "smk_render", rgba, depth, nullptr, 0); }
+
+extern "C" int smk_render_occluded(smk_ctx *c, const float *scene_depth, int kind, float *rgba, float *depth) {
+  if (!c) return 1;
+  if (scene_depth_kind_check(c, "smk_render_occluded", kind)) return 1;
+  return render_host(c, "smk_render_occluded", rgba, depth, scene_depth, kind);
 }

@@ -11,7 +11,9 @@
 #include "smk_device.h"
 
 // SHD: the frame's planes are the half-angle slices of a frame with shadows (SmkShadowRays): the eye pass of smk_shadow.hip
-template <int DT, int TF, int SH, bool SHD = false>
+// OCC: the frame has the host's opaque scene depth (smk_render_occluded; compile-time: as a run-time test it cost the
+// instances of frames without one up to two VGPRs)
+template <int DT, int TF, int SH, bool SHD = false, bool OCC = false>
 __global__ __launch_bounds__(256) void smk_k_gather(const RenderParams P) {
   int tx, ty;
   if (!smk_tile_of_block(P, blockIdx.x, tx, ty)) return;
@@ -46,9 +48,21 @@ __global__ __launch_bounds__(256) void smk_k_gather(const RenderParams P) {
       empty = true;
     }
   }
+  // the host's opaque scene depth (smk_render_occluded): the planes in front of it, bracketed here and their ends tested
+  // exactly below -- the loop never hears of it
+  float zD = __int_as_float(0x7f800000);
+  if (OCC && live) {
+    zD = smk_scene_depth(P, (size_t)j * P.W + i);
+    smk_scene_bracket(zD, SHD ? tauA : rc.tau0, SHD ? dtau : rc.dtau, P.znear, tenter, texit, empty);
+  }
   int m0 = (int)floorf(fmaxf(tenter, 0.0f));
   int m1 = (int)ceilf(fminf(texit, (float)(rc.nplanes - 1)));
   if (empty || !(tenter <= texit) || !live) m1 = m0 - 1;
+  if (OCC) {
+    // (monotone in m: the planes that pass are one interval, and the bracket leaves a few planes to drop at either end)
+    while (m0 <= m1 && !(smk_plane_depth<SHD>(P, m0, tauA, dtau) < zD)) ++m0;
+    while (m1 >= m0 && !(smk_plane_depth<SHD>(P, m1, tauA, dtau) < zD)) --m1;
+  }
   int mlo = m0, mhi = m1;
   if (P.lockstep) {
     // all 64 rays of the wave visit the same plane in the same iteration: their corner
@@ -270,7 +284,8 @@ hipError_t smk_launch_count_inside(const RenderParams &P, unsigned long long *d_
 template <int DT, int TF, int SH, bool SHD = false>
 static hipError_t launch(const RenderParams &P, hipStream_t s) {
   dim3 grid(8 * P.tiles_per_xcd), block(256);
-  hipLaunchKernelGGL((smk_k_gather<DT, TF, SH, SHD>), grid, block, 0, s, P);
+  if (P.zscene) hipLaunchKernelGGL((smk_k_gather<DT, TF, SH, SHD, true>), grid, block, 0, s, P);
+  else hipLaunchKernelGGL((smk_k_gather<DT, TF, SH, SHD>), grid, block, 0, s, P);
   return hipGetLastError();
 }
 

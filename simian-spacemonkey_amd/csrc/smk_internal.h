@@ -125,6 +125,13 @@ struct RenderParams {
   // ---- tile mapping
   int ntx, nty, tiles_per_xcd;
   int wave_w, blk_w, lockstep;  // gather-kernel tiling knobs (smk_set_option)
+  // ---- the host's opaque scene depth (smk_render_occluded): [H][W] floats of the window, or null.  A sample exists only
+  // where its smk_plane_depth is less than the pixel's smk_scene_depth (smk_device.h); kind = smk_scene_depth_kind, and
+  // for window depths zs_fn = f n, zs_f = f, zs_fmn = f - n of the camera's clip planes.  (Last: the fields above keep
+  // their kernarg offsets, and the kernels without a scene depth their register allocation.)
+  const float *zscene;
+  int zscene_kind;
+  double zs_fn, zs_f, zs_fmn;
 };
 
 // side buffers of the slice-ring kernel, owned by the context
@@ -368,6 +375,9 @@ struct smk_ctx {
   float4 *d_out = nullptr;
   float *d_depth = nullptr;
   size_t out_cap = 0;
+  // smk_render_occluded: the host's scene depth staged for the frame (and its re-render)
+  float *d_zscene = nullptr;
+  size_t zscene_cap = 0;
 
   // options / stats
   int opt_kernel = 0, opt_tf_raw = 0;

@@ -175,7 +175,7 @@ __device__ __forceinline__ void shadow_st1(float *p, float v) {
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <int DT, int TF, int SH, bool COH = false>
+template <int DT, int TF, int SH, bool COH = false, bool OCC = false>
 __device__ __forceinline__ void shadow_eye_pixel(const RenderParams &P, const ShadowSlice &Q, int i, int j) {
   const smk_shadowcoef &sc = Q.sc;
   if (i >= P.W || j >= P.H) return;
@@ -196,6 +196,8 @@ __device__ __forceinline__ void shadow_eye_pixel(const RenderParams &P, const Sh
   if (!in) return;
   if (P.cplane_on && !(__fmaf_rn(p[0], P.cplane[0], __fmaf_rn(p[1], P.cplane[1], __fmaf_rn(p[2], P.cplane[2], P.cplane[3]))) >= 0.0f)) return;
   const size_t o = (size_t)j * P.W + i;
+  // the host's opaque scene depth (smk_render_occluded): the fragment exists in front of it only (the ray-marchers' test)
+  if (OCC && !(smk_plane_depth<true>(P, m, tauA, dtau) < smk_scene_depth(P, o))) return;
   float4 C = shadow_ld4<COH>(P.out + o);
   if (sc.front_to_back && C.w == 1.0f) return;  // exact: every later weight (1-A) is 0
   if (shadow_brick_empty(P, p[0], p[1], p[2])) return;
@@ -269,13 +271,14 @@ __device__ __forceinline__ void shadow_light_texel(const RenderParams &P, const 
   shadow_st4<COH>(Q.Lnext + o, L);
 }
 
-template <int DT, int TF, int SH>
+// (OCC: the frame has the host's opaque scene depth -- smk_render_occluded; its eye fragments are tested against it)
+template <int DT, int TF, int SH, bool OCC = false>
 __global__ __launch_bounds__(256) void smk_k_shadow_slice(const RenderParams P, const ShadowSlice Q) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   // a workgroup = 16x16 pixels, each wave an 8x8 sub-tile (compact footprints in the volume)
   const int lx = (wave & 1) * 8 + (lane & 7), ly = (wave >> 1) * 8 + (lane >> 3);
   if ((int)blockIdx.x < Q.eye_blocks) {
-    shadow_eye_pixel<DT, TF, SH>(P, Q, ((int)blockIdx.x % Q.eye_bx) * 16 + lx, ((int)blockIdx.x / Q.eye_bx) * 16 + ly);
+    shadow_eye_pixel<DT, TF, SH, false, OCC>(P, Q, ((int)blockIdx.x % Q.eye_bx) * 16 + lx, ((int)blockIdx.x / Q.eye_bx) * 16 + ly);
   } else {
     const int b = (int)blockIdx.x - Q.eye_blocks;
     shadow_light_texel<DT, TF>(P, Q, (b % Q.light_bx) * 16 + lx, (b / Q.light_bx) * 16 + ly);
@@ -288,7 +291,7 @@ __global__ __launch_bounds__(256) void smk_k_shadow_slice(const RenderParams P, 
 // slice k + 1.  The same arithmetic per pixel and texel as the per-slice launches: identical frames and light buffers.
 // 512 launches of ~11 us each were the larger part of a frame with shadows (5.7 ms); the barrier is a fence and one
 // atomic round per workgroup.
-template <int DT, int TF, int SH>
+template <int DT, int TF, int SH, bool OCC = false>
 __global__ __launch_bounds__(256) void smk_k_shadow_fused(const RenderParams P, ShadowSlice Q, float4 *L0, float4 *L1, unsigned *barrier) {
   const smk_shadowcoef &sc = Q.sc;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -305,7 +308,7 @@ __global__ __launch_bounds__(256) void smk_k_shadow_fused(const RenderParams P, 
       if (b < nlb) shadow_light_texel<DT, TF, true>(P, Q, (b % Q.light_bx) * 16 + lx, (b / Q.light_bx) * 16 + ly);
       else {
         const int e = b - nlb;
-        shadow_eye_pixel<DT, TF, SH, true>(P, Q, (e % Q.eye_bx) * 16 + lx, (e / Q.eye_bx) * 16 + ly);
+        shadow_eye_pixel<DT, TF, SH, true, OCC>(P, Q, (e % Q.eye_bx) * 16 + lx, (e / Q.eye_bx) * 16 + ly);
       }
     }
     // grid barrier: every wave's device-scope stores have been acknowledged (vmcnt 0) before its workgroup signs in; one
@@ -741,7 +744,7 @@ hipError_t smk_launch_shadow_count_light(const RenderParams &P, const smk_shadow
   return hipGetLastError();
 }
 
-template <int DT, int TF, int SH>
+template <int DT, int TF, int SH, bool OCC>
 static hipError_t run(const RenderParams &P, ShadowSlice Q, float4 *L0, float4 *L1, unsigned *barrier, hipStream_t s) {
   const smk_shadowcoef &sc = Q.sc;
   Q.eye_bx = (P.W + 15) / 16;
@@ -761,7 +764,7 @@ static hipError_t run(const RenderParams &P, ShadowSlice Q, float4 *L0, float4 *
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, dev);
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (coop && cus > 0 && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, smk_k_shadow_fused<DT, TF, SH>, 256, 0) == hipSuccess && per_cu > 0) {
+    if (coop && cus > 0 && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, smk_k_shadow_fused<DT, TF, SH, OCC>, 256, 0) == hipSuccess && per_cu > 0) {
       // (a barrier costs with the number of workgroups that meet at it: four per CU hide the gathers' latency, more only wait)
       static const int wgs_per_cu = getenv("SMK_SHADOW_WGS") ? std::max(1, atoi(getenv("SMK_SHADOW_WGS"))) : 4;  // (developer knob)
       const int grid = std::min(blocks, cus * std::min(per_cu, wgs_per_cu));
@@ -771,7 +774,7 @@ static hipError_t run(const RenderParams &P, ShadowSlice Q, float4 *L0, float4 *
       if (bar && hipMemsetAsync(bar, 0, 16 * 9 * 4, s) != hipSuccess) bar = nullptr;
       void *args[] = {(void *)&Pa, (void *)&Qa, (void *)&L0, (void *)&L1, (void *)&bar};
       if (bar) {
-      const hipError_t e = hipLaunchCooperativeKernel((const void *)smk_k_shadow_fused<DT, TF, SH>, dim3(grid), dim3(256), args, 0, s);
+      const hipError_t e = hipLaunchCooperativeKernel((const void *)smk_k_shadow_fused<DT, TF, SH, OCC>, dim3(grid), dim3(256), args, 0, s);
       if (e == hipSuccess) return hipGetLastError();
       (void)hipGetLastError();  // refused (resources): the per-slice launches below
       }
@@ -782,7 +785,7 @@ static hipError_t run(const RenderParams &P, ShadowSlice Q, float4 *L0, float4 *
     Q.lnum = fmaf((float)k, sc.ldnum, sc.lnum0);
     Q.Lprev = (k & 1) ? L0 : L1;
     Q.Lnext = (k & 1) ? L1 : L0;
-    hipLaunchKernelGGL((smk_k_shadow_slice<DT, TF, SH>), dim3(blocks), dim3(256), 0, s, P, Q);
+    hipLaunchKernelGGL((smk_k_shadow_slice<DT, TF, SH, OCC>), dim3(blocks), dim3(256), 0, s, P, Q);
   }
   return hipGetLastError();
 }
@@ -794,7 +797,8 @@ hipError_t smk_launch_shadow(const RenderParams &P, const smk_shadowcoef &sc, in
   memset(&Q, 0, sizeof Q);
   Q.sc = sc;
 #define CASE(D, T, S) \
-  if (dtype == D && tf_mode == T && shade_kind == S) return run<D, T, S>(P, Q, L0, L1, barrier, s);
+  if (dtype == D && tf_mode == T && shade_kind == S) \
+    return P.zscene ? run<D, T, S, true>(P, Q, L0, L1, barrier, s) : run<D, T, S, false>(P, Q, L0, L1, barrier, s);
   CASE(0, 1, 0) CASE(0, 1, 1) CASE(0, 2, 0) CASE(0, 2, 1)
   CASE(1, 1, 0) CASE(1, 1, 1) CASE(1, 2, 0) CASE(1, 2, 1)
 #undef CASE

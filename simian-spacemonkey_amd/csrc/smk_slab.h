@@ -74,6 +74,12 @@ hipError_t smk_slab_dispatch_f32(const RenderParams &P, const SlabParams &Q, int
 // ... and one for the eye pass of frames with shadows (SHD instances: 2-D / 3-D table, R8k shading or none, both voxel types)
 hipError_t smk_slab_dispatch_shadow(const RenderParams &P, const SlabParams &Q, int dtype, int tf_mode, int shade_kind, int nw, int nl, size_t lds,
                                     int nblocks, const char **why, hipStream_t s);
+// ... and for frames with the host's opaque scene depth (OCC instances, smk_render_occluded): view-aligned planes, and the eye
+// pass of frames with shadows
+hipError_t smk_slab_dispatch_occluded(const RenderParams &P, const SlabParams &Q, int dtype, int tf_mode, int shade_kind, int nw, int nl, size_t lds,
+                                      int nblocks, const char **why, hipStream_t s);
+hipError_t smk_slab_dispatch_occluded_shadow(const RenderParams &P, const SlabParams &Q, int dtype, int tf_mode, int shade_kind, int nw, int nl,
+                                             size_t lds, int nblocks, const char **why, hipStream_t s);
 // DEPTH SEGMENTS: the merge pass over the n split tiles listed at `list` (tile | pieces << 20)
 hipError_t smk_slab_merge(const int2 *list, int n, int tw, int th, int ntx, int W, int H, const float4 *seg_out, float4 *out, int use_max,
                           hipStream_t s);

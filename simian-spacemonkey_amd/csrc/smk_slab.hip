@@ -191,7 +191,10 @@ __device__ __forceinline__ float slab_tex_chan(const SlabTexel4 &x, int k) {
 //  the run-time test alone, three per loop turn, cost them 12 % in scalar registers spilled)
 // (SHD: the frame's planes are the half-angle slices of a frame with shadows -- SmkShadowRays; the eye pass of smk_shadow.hip.
 //  Compile-time: the instances live in smk_slab_shadow.hip, SLAB_PART 2)
-template <int DT, int SH, int PERM, int NW, int NL, bool DIAG, int TF = 1, bool BR = true, bool SHD = false>
+// (OCC: the frame has the host's opaque scene depth, smk_render_occluded -- folded into each ray's plane range in the set-up.
+//  Compile-time as well: as a run-time test it cost the instances of frames without one a VGPR and a few SGPR spills; the
+//  instances live in smk_slab_occ.hip and smk_slab_occ_shadow.hip, SLAB_PART 3 and 4)
+template <int DT, int SH, int PERM, int NW, int NL, bool DIAG, int TF = 1, bool BR = true, bool SHD = false, bool OCC = false>
 // (second argument: waves per SIMD the register allocation must allow -- two small workgroups per CU)
 __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) == 5 || (NW + NL) == 10) ? 5 : ((NW + NL) == 11 ? 3 : (NW + NL) == 12 ? 6 : 4)) void smk_k_slab(const RenderParams P, const SlabParams Q) {
   constexpr int UPV = DT == 0 ? 2 : 1;   // voxels per 16-byte DMA unit
@@ -300,6 +303,13 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
       empty = true;
     }
   }
+  // The host's opaque scene depth (smk_render_occluded): a sample exists where its smk_plane_depth is below the pixel's --
+  // monotone in q as well (smk_scene_bracket), folded the same way and tested exactly at the ends by inside() below.
+  float zD = __int_as_float(0x7f800000);
+  if (OCC && live) {
+    zD = smk_scene_depth(P, (size_t)j * P.W + i);
+    smk_scene_bracket(zD, SHD ? tauA : rc.tau0, SHD ? dtau : rc.dtau, P.znear, tenter, texit, empty);
+  }
   int m = (int)floorf(fmaxf(tenter, 0.0f));
   int m1 = (int)ceilf(fminf(texit, (float)(rc.nplanes - 1)));
   if (empty || !(tenter <= texit)) m1 = m - 1;
@@ -317,6 +327,7 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
       // (the gather kernel's own fma chain for the plane: the same samples pass, bit for bit)
       if (P.cplane_on) in = in && __fmaf_rn(p0, P.cplane[0], __fmaf_rn(p1, P.cplane[1], __fmaf_rn(p2, P.cplane[2], P.cplane[3]))) >= 0.0f;
       if (SHD) in = in && smk_tau_ok(tauA, dtau, q);
+      if constexpr (OCC) in = in && smk_plane_depth<SHD>(P, q, tauA, dtau) < zD;  // (depth_out's chain: the same bits)
       return in;
     };
     int mf = m1 + 1, ml = m - 1;
@@ -1409,9 +1420,10 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
 
 // ------------------------------------------------------------------------------- host side
 
-// This file is compiled three times (build time: the instances are most of it): as itself -- the merge pass + the byte-voxel
-// instances --, through smk_slab_f32.hip (SLAB_PART 1) -- the float-voxel instances alone -- and through smk_slab_shadow.hip
-// (SLAB_PART 2) -- the instances of the eye pass of frames with shadows.
+// This file is compiled five times (build time: the instances are most of it): as itself -- the merge pass + the byte-voxel
+// instances --, through smk_slab_f32.hip (SLAB_PART 1) -- the float-voxel instances alone --, through smk_slab_shadow.hip
+// (SLAB_PART 2) -- the instances of the eye pass of frames with shadows --, and through smk_slab_occ.hip (SLAB_PART 3) and
+// smk_slab_occ_shadow.hip (SLAB_PART 4) -- the instances of frames with the host's scene depth (OCC), without and with shadows.
 #ifndef SLAB_PART
 #define SLAB_PART 0
 #endif
@@ -1449,9 +1461,9 @@ hipError_t smk_slab_merge(const int2 *list, int n, int tw, int th, int ntx, int 
 }
 #endif  // SLAB_PART == 0
 
-template <int DT, int SH, int PERM, int NW, int NL, bool DIAG, int TF = 1, bool BR = true, bool SHD = false>
+template <int DT, int SH, int PERM, int NW, int NL, bool DIAG, int TF = 1, bool BR = true, bool SHD = false, bool OCC = false>
 static hipError_t launch_slab(const RenderParams &P, const SlabParams &Q, size_t lds, int nblocks, hipStream_t s) {
-  auto k = smk_k_slab<DT, SH, PERM, NW, NL, DIAG, TF, BR, SHD>;
+  auto k = smk_k_slab<DT, SH, PERM, NW, NL, DIAG, TF, BR, SHD, OCC>;
   static bool attr_set[64] = {};  // per device: the attribute belongs to the function ON the current device
   int dev = 0;
   (void)hipGetDevice(&dev);
@@ -1465,7 +1477,44 @@ static hipError_t launch_slab(const RenderParams &P, const SlabParams &Q, size_t
 }
 
 // ---- instance dispatch (declared in smk_slab.h)
-#if SLAB_PART == 2
+#if SLAB_PART == 3 || SLAB_PART == 4
+// Frames with the host's scene depth: one instance per shape, shading, axis and table kind -- with the brick-flag code (it
+// is exact with no flags as well: Q.bricks null), and none of the diagnostic ones.
+#if SLAB_PART == 3
+hipError_t smk_slab_dispatch_occluded(const RenderParams &P, const SlabParams &Q, int dtype, int tf_mode, int shade_kind, int nw, int nl, size_t lds,
+                                      int nblocks, const char **why, hipStream_t s) {
+#define GO(D, S, R, N, L)                                                                              \
+  if (dtype == D && shade_kind == S && Q.perm == R && nw == N && nl == L) {                          \
+    if (tf_mode == 2) return (launch_slab<D, S, R, N, L, false, 2, true, false, true>(P, Q, lds, nblocks, s)); \
+    if (tf_mode == 1) return (launch_slab<D, S, R, N, L, false, 1, true, false, true>(P, Q, lds, nblocks, s)); \
+    if constexpr (S == 0) return (launch_slab<D, S, R, N, L, false, 0, false, false, true>(P, Q, lds, nblocks, s)); \
+    *why = "no colour-table instance with this shading";                                               \
+    return hipErrorNotSupported;                                                                     \
+  }
+#define GO_R(D, S) GO_NW(D, S, 0) GO_NW(D, S, 1) GO_NW(D, S, 2)
+#define GO_NW(D, S, R) GO(D, S, R, 8, 2) GO(D, S, R, 10, 2) GO(D, S, R, 12, 4)
+  GO_R(0, 0) GO_R(0, 1) GO_R(0, 2) GO_R(1, 0) GO_R(1, 1) GO_R(1, 2)
+#else
+hipError_t smk_slab_dispatch_occluded_shadow(const RenderParams &P, const SlabParams &Q, int dtype, int tf_mode, int shade_kind, int nw, int nl,
+                                             size_t lds, int nblocks, const char **why, hipStream_t s) {
+#define GO(D, S, R, N, L)                                                                              \
+  if (dtype == D && shade_kind == S && Q.perm == R && nw == N && nl == L) {                          \
+    if (tf_mode == 2) return (launch_slab<D, S, R, N, L, false, 2, true, true, true>(P, Q, lds, nblocks, s)); \
+    if (tf_mode == 1) return (launch_slab<D, S, R, N, L, false, 1, true, true, true>(P, Q, lds, nblocks, s)); \
+    *why = "shadows need a 2-D or 3-D table";                                                        \
+    return hipErrorNotSupported;                                                                     \
+  }
+#define GO_R(D, S) GO_NW(D, S, 0) GO_NW(D, S, 1) GO_NW(D, S, 2)
+#define GO_NW(D, S, R) GO(D, S, R, 8, 2) GO(D, S, R, 10, 2) GO(D, S, R, 12, 4)
+  GO_R(0, 0) GO_R(0, 1) GO_R(1, 0) GO_R(1, 1)
+#endif
+#undef GO_R
+#undef GO_NW
+#undef GO
+  *why = "no scene-depth instance for this configuration";
+  return hipErrorNotSupported;
+}
+#elif SLAB_PART == 2
 hipError_t smk_slab_dispatch_shadow(const RenderParams &P, const SlabParams &Q, int dtype, int tf_mode, int shade_kind, int nw, int nl, size_t lds,
                                     int nblocks, const char **why, hipStream_t s) {
 #define GO(D, S, R, N, L)                                                                                  \
@@ -1537,4 +1586,4 @@ hipError_t smk_slab_dispatch_f32(const RenderParams &P, const SlabParams &Q, int
   *why = "no kernel instance for this tile size";
   return hipErrorNotSupported;
 }
-#endif  // SLAB_PART != 2
+#endif  // SLAB_PART 0 / 1

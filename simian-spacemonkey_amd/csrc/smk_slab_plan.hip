@@ -1054,7 +1054,9 @@ static hipError_t slab_run(const RenderParams &P, const SlabParams &Q, SlabAux *
     }
     (void)hipGetLastError();
   }
-  e = P.sh.on     ? smk_slab_dispatch_shadow(P, Q, dtype, tf_mode, shade_kind, nw, sh.nl, lds, nblocks, why, s)
+  e = P.zscene   ? (P.sh.on ? smk_slab_dispatch_occluded_shadow(P, Q, dtype, tf_mode, shade_kind, nw, sh.nl, lds, nblocks, why, s)
+                             : smk_slab_dispatch_occluded(P, Q, dtype, tf_mode, shade_kind, nw, sh.nl, lds, nblocks, why, s))
+      : P.sh.on    ? smk_slab_dispatch_shadow(P, Q, dtype, tf_mode, shade_kind, nw, sh.nl, lds, nblocks, why, s)
       : dtype == 0 ? smk_slab_dispatch_u8(P, Q, tf_mode, shade_kind, nw, sh.nl, diag, lds, nblocks, why, s)
                    : smk_slab_dispatch_f32(P, Q, tf_mode, shade_kind, nw, sh.nl, diag, lds, nblocks, why, s);
   if (e == hipSuccess && nsplit > 0)

@@ -287,11 +287,13 @@ class ExchangePipeline:
         self.x.wait(torch.cuda.current_stream().cuda_stream)
 
 
-def render_shadow_frame_local(renderers, depth=False):
+def render_shadow_frame_local(renderers, depth=False, scene_depth=None, scene_depth_kind=0):
     """One frame with shadows on P shard contexts of this process that share one device, ranks in order (smk.h "Shadows on
     shards"): phase 1 and the light exchange (smk_shadow_exchange_local), every rank's frame, then the HIP "over" of the P
     layers in smk_shard_order's order.  Returns the merged frame, a [H][W][4] float32 tensor on that device; depth=True:
-    (frame, depth), depth the [H][W] minimum of the ranks' first-hit depths (smk_composite_over_depth_device)."""
+    (frame, depth), depth the [H][W] minimum of the ranks' first-hit depths (smk_composite_over_depth_device).
+    scene_depth: the host's opaque scene depth, [H][W] floats (array or tensor) of kind scene_depth_kind, the same
+    full-window buffer for every rank (smk_render_occluded_device); the light exchange is not affected."""
     from .binding import shadow_exchange_local
     nranks = len(renderers)
     w, h = renderers[0].size
@@ -302,9 +304,15 @@ def render_shadow_frame_local(renderers, depth=False):
     out = torch.zeros((npix, 4), dtype=torch.float32, device=dev)
     dlayers = torch.full((nranks, npix), float("inf"), dtype=torch.float32, device=dev) if depth else None
     dout = torch.empty((npix,), dtype=torch.float32, device=dev) if depth else None
+    zs = None
+    if scene_depth is not None:
+        zs = torch.as_tensor(scene_depth, dtype=torch.float32).to(dev).contiguous()
+        if tuple(zs.shape) != (h, w):
+            raise ValueError("scene_depth must be [%d][%d] floats, got shape %s" % (h, w, tuple(zs.shape)))
     torch.cuda.synchronize(dev)
     for r, R in enumerate(renderers):
-        R.render_device(layers[r].data_ptr(), dlayers[r].data_ptr() if depth else None)
+        R.render_device(layers[r].data_ptr(), dlayers[r].data_ptr() if depth else None,
+                        d_scene_depth=zs.data_ptr() if zs is not None else None, scene_depth_kind=scene_depth_kind)
     torch.cuda.synchronize(dev)
     order = renderers[0].shard_order(nranks)
     if depth:
