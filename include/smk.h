@@ -145,6 +145,43 @@ int smk_set_sampling(smk_ctx *ctx, float sample_rate, int steps, float gamma, in
  * on one side of an axis-aligned plane through vpos (volume space, the units of fPos/fSize).
  * oaxis = VolRenMajorAxis: 1 X+ (x <= vpos.x stays), 2 X-, 3 Y+, 4 Y-, 5 Z+, 6 Z-.  on = 0: off. */
 int smk_set_clip(smk_ctx *ctx, int on, int oaxis, const float vpos[3]);
+/* replaces drawClip + renderSlice of the two live renderers (R8kVolRen3D.cpp:763-891, 893-921; NV20VolRen3D.cpp:329-502,
+ * 506-528): in orthogonal mode they draw the slice of the data that lies on the clip plane, blended with gluvv.clip.alpha,
+ * behind the volume when the plane faces away from the eye and on top of it when it faces the eye.  Drawn only while
+ * smk_set_clip is on (its oaxis is used; free-mode planes draw no slice, R8kVolRen3D.cpp:800, NV20VolRen3D.cpp:363).
+ *   corners = gluvv.clip.corners (CPWidgetRen::set_info, CPWidgetRen.cpp:215-296), volume space (the units of fPos / fSize);
+ *   alpha   = gluvv.clip.alpha;
+ *   dv      = dot(normalize(eye - clip.pos), normalize(clip.dir)), computed by the caller (R8kVolRen3D.cpp:273-281,
+ *             NV20VolRen3D.cpp:124-131).
+ * When: the slice is drawn BEFORE the volume when the case of oaxis holds for dv, AFTER it when it holds for -dv
+ * (R8kVolRen3D.cpp:360-372, 400-424; NV20VolRen3D.cpp:144-148, 173-178): X+ dv < 0, X- dv > 0, Y+ dv > 0, Y- dv < 0, Z+ dv < 0,
+ * Z- dv > 0 (R8kVolRen3D.cpp:826-879; the Y+ sign is the reference's), and -- except for X-, which the reference does not
+ * test (:835) -- only if corner 0's clamped coordinate on that axis lies strictly inside (0, fSize).  dv == 0: neither.
+ * Where: the corners are clamped to the volume box (:810-821), moved by +0.001 (X+, Y+, Z+) or -0.001 (X-, Y-, Z-) along
+ * the axis (:823, 829-831 ...) and drawn as one GL_QUADS quad, triangles (0, 1, 2) and (0, 2, 3), texture coordinates =
+ * the moved vertex / fSize (:906-913), GL_LINEAR, clamp to edge.
+ * Colour: SMK_CLIP_LOOK_NV20 (final combiner, NV20VolRen3D.cpp:390, 426-431): src = (V a, V a, V a, a), V = the value channel,
+ *   a = alpha.  SMK_CLIP_LOOK_R8K (createFragClip, R8kVolRen3D.cpp:3190-3250, textures per data mode :1926-2055): rgb = the
+ *   data texel's first three channels in the third-axis data modes (four-byte texture); the texel with green replaced by
+ *   its alpha otherwise -- (c0, c1, c0) for the two-byte modes V1G, V2, VGH_VG and (0, c0, 0) for the one-byte modes V1,
+ *   VGH_V --, saturated; a = sat(alpha), src = (sat(rgb a), a) (:3223-3245).  u8 voxels decode / 255, f32 voxels are used
+ *   as they are and saturated.
+ * Order, onto the finished volume frame (GL_ONE, GL_ONE_MINUS_SRC_ALPHA, R8kVolRen3D.cpp:364, 404, 416): before pass
+ * frame = volume + (1 - volume.a) src, after pass frame = src + (1 - a) volume.  Under SMK_BLEND_MAX the before pass is
+ * max(volume, src) per component (the slice is in the framebuffer when GL_MAX starts, NV20VolRen3D.cpp:144-163).  With
+ * shadows the before pass is skipped when the light runs along the view (axis[3] = vdl > 0, R8kVolRen3D.cpp:306-324, 360);
+ * the after pass is always drawn; the slice never enters the light buffer.
+ * Depth: the depth test is on, depth writes are off (R8kVolRen3D.cpp:365, 405, 417; NV20VolRen3D.cpp:433-434): under
+ * smk_render_occluded a slice pixel exists only where its view depth is LESS than the scene depth; depth_out is not
+ * changed by the slice (it reports volume samples).  On a shard every rank draws the part of the quad that lies in its own
+ * region, before the exchange; the merged frame is the unsharded one where the pass is the one the geometry calls for
+ * (before: the eye looks at the kept side of the plane; after: at the cut face), because everything beyond the slice, or
+ * in front of it, is then clipped away in every rank; a pass that
+ * contradicts the geometry is composed per rank all the same and merges to something else.  An after pass under
+ * SMK_BLEND_MAX is refused on shards: a maximum cannot merge it.  on = 0, or smk_set_clip off: frames are bit-identical to those without this call
+ * and nothing more is launched.  A bad look and non-finite corners, alpha or dv fail with the reason. */
+typedef enum { SMK_CLIP_LOOK_NV20 = 0, SMK_CLIP_LOOK_R8K = 1 } smk_clip_look;
+int smk_set_clip_slice(smk_ctx *ctx, int on, const float corners[4][3], float alpha, float dv, smk_clip_look look);
 /* replaces the extents of VolumeRenderer::renderVolume(sampleRate, mv, xext, yext, zext) (VolumeRenderer.h:103-108,
  * VolumeRenderer.cpp:333-384, render3DVolumeEXTSV :428-505): only the axis-aligned sub-box lo..hi of the volume is drawn
  * (volume space, the units of fPos / fSize; clamped to the volume as :452-457 do; the reference's `x[1] -= origf[1]` slip,
@@ -215,7 +252,8 @@ int smk_render_device(smk_ctx *ctx, void *d_rgba, void *d_depth, void *stream);
  * NaN means no occluder (+inf) in both kinds.  The test applies under every blend mode, depth_out, clip planes (both
  * forms), smk_set_region, perturbation, time steps, bricked uploads and shards.  With shadows only the eye pass is
  * occluded: the light buffer is the unoccluded frame's (the reference's light pbuffer holds the volume alone).  Option
- * "kernel" 3 (column-stream) refuses such frames; auto mode never takes it.  smk_render_slice is not affected.
+ * "kernel" 3 (column-stream) refuses such frames; auto mode never takes it.  The clip-plane widget's slice
+ * (smk_set_clip_slice) is tested the same way.  smk_render_slice is not affected.
  * smk_render_occluded copies scene_depth at the call; smk_render_occluded_device reads the DEVICE buffer d_scene_depth on
  * `stream` (the caller keeps it alive until the stream has passed the frame).  A NULL buffer makes them exactly smk_render /
  * smk_render_device.  A bad kind fails with the reason.  (INTEGRATION.md "Depth for the GL host".) */
@@ -228,7 +266,9 @@ int smk_render_occluded_device(smk_ctx *ctx, const void *d_scene_depth, int kind
  * scalar volume -- GL_INTENSITY8, GL_LINEAR, no colour table (:768), texture coordinates = vertex / fSize -- modulated by
  * glColor4f(1, 1, 1, alpha) and blended GL_ONE, GL_ONE_MINUS_SRC_ALPHA into the frame:
  *   src = (I, I, I, I * alpha), frame = src + (1 - src.a) * frame,   I = the first data channel in [0, 1].
- * Uses the camera of smk_set_camera.  rgba_inout: [height][width][4] float, read and written. */
+ * Uses the camera of smk_set_camera.  rgba_inout: [height][width][4] float, read and written.  (Not the clip-plane widget's
+ * slice, smk_set_clip_slice: that one is part of the frame -- ordered against the volume, depth-tested, drawn on shards --
+ * and takes its colour from the renderers' data texel, not from GL_INTENSITY8.) */
 int smk_render_slice(smk_ctx *ctx, const float quad[4][3], float alpha, float *rgba_inout);
 int smk_render_slice_device(smk_ctx *ctx, const float quad[4][3], float alpha, void *d_rgba_inout, void *stream);
 
@@ -448,7 +488,8 @@ int smk_timing_read(smk_ctx *ctx, float *avg_ms, int *nframes);
  * empty layer), "slab_hit_lanes" (collected when option
  * lockstep has bit 16 set), "slab_status" (these synchronise the device); "light_samples" (the light-march samples of
  * the current frame with shadows this context owns -- all of them on the whole volume; synchronises); "slab_failures",
- * "slab_retries" (host-side counters, no synchronisation). */
+ * "slab_retries" (host-side counters, no synchronisation); "clip_slice_pass" (which pass of smk_set_clip_slice the last
+ * frame's rule chose: 0 none, 1 before the volume, 2 after it; no synchronisation). */
 int smk_get_stat(smk_ctx *ctx, const char *name, double *value);
 /* workgroup timeline of the last slice-ring frame (developer tool):
  * records of 8 x uint32 {start, end (100 MHz ticks), HW_ID, XCC_ID | tile<<8 | slices<<20, loader 0's

@@ -32,12 +32,15 @@ ABI_SYMBOLS = [
     "smk_get_timesteps",
     "smk_composite_over_depth_device", "smk_exchange_partial_depth", "smk_exchange_frame_depth", "smk_exchange_frame_local_depth",
     "smk_render_occluded", "smk_render_occluded_device",
+    "smk_set_clip_slice",
 ]
 
 # gluvvDataMode order (gluvv.h:221-235)
 GDM = {n: i for i, n in enumerate(
     ["V1", "V1G", "V1GH", "V2", "V2G", "V2GH", "V3", "V3G", "V4", "VGH", "VGH_VG", "VGH_V"])}
 SHADE = {"none": 0, "r8k_diff": 1, "r8k": 2, "nv20_diff": 3, "nv20": 4}
+# smk_clip_look: whose colour the clip-plane widget's data slice takes (Renderer.set_clip_slice)
+CLIP_LOOK = {"nv20": 0, "r8k": 1}
 # smk_scene_depth_kind: what a scene depth handed to Renderer.render / render_device holds
 SCENE_VIEW_DEPTH, SCENE_WINDOW_DEPTH = 0, 1
 
@@ -132,6 +135,7 @@ def load_library():
     L.smk_set_shard.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.smk_set_clip.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
     L.smk_set_clip_plane.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double)]
+    L.smk_set_clip_slice.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_int]
     L.smk_set_region.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.smk_render_slice.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float)]
     L.smk_render_slice_device.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_float, C.c_void_p, C.c_void_p]
@@ -394,6 +398,17 @@ class Renderer:
             self._ck(self.L.smk_set_clip_plane(self.ctx, 0, None))
         else:
             self._ck(self.L.smk_set_clip_plane(self.ctx, 1, (C.c_double * 4)(*[float(v) for v in plane_eye])))
+
+    def set_clip_slice(self, corners, alpha=1.0, dv=0.0, look="r8k"):
+        """the clip-plane widget's data slice (smk_set_clip_slice): corners = gluvv.clip.corners (4 x 3, volume space), alpha =
+        gluvv.clip.alpha, dv = dot(normalize(eye - clip.pos), normalize(clip.dir)), look "r8k" / "nv20"; drawn with the frame
+        while set_clip is on.  corners None switches it off"""
+        if corners is None:
+            self._ck(self.L.smk_set_clip_slice(self.ctx, 0, None, 0.0, 0.0, 0))
+            return
+        q = np.ascontiguousarray(corners, np.float32).reshape(12)
+        self._ck(self.L.smk_set_clip_slice(self.ctx, 1, q.ctypes.data_as(C.POINTER(C.c_float)), float(alpha), float(dv),
+                                           CLIP_LOOK[look] if isinstance(look, str) else int(look)))
 
     def set_region(self, lo=None, hi=None):
         """sub-box of the volume in volume space (renderVolume's x/y/zext); None = off"""

@@ -1144,6 +1144,7 @@ extern "C" int smk_get_stat(smk_ctx *c, const char *name, double *value) {
   if (!strcmp(name, "slab_split_tiles")) { *value = c->slab.nsplit_last; return 0; }
   if (!strcmp(name, "slab_workgroups")) { *value = c->slab.nblocks_last; return 0; }
   if (!strcmp(name, "slab_retries")) { *value = (double)c->slab_retries; return 0; }
+  if (!strcmp(name, "clip_slice_pass")) { *value = c->clip_slice_pass; return 0; }  // (smk_clip_slice.hip)
   FAIL(c, "smk_get_stat: unknown name '%s'", name);
 }
 

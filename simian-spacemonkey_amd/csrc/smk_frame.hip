@@ -1,6 +1,7 @@
 // smk_frame.hip -- a frame: the driver behind smk_render_device / smk_render as a sequence of stages (frame_open, the shadow
-// stage of smk_shadow_plan.hip, the kernel choice, one launch per ray-marcher, frame_close), the auto mode's choice between
-// the slice-ring and the gather kernel, the per-frame status words and the timing ring.
+// stage of smk_shadow_plan.hip, the kernel choice, one launch per ray-marcher, the clip slice of smk_clip_slice.hip,
+// frame_close), the auto mode's choice between the slice-ring and the gather kernel, the per-frame status words and the
+// timing ring.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -315,7 +316,7 @@ static int render_frame(smk_ctx *c, const char *who, void *d_rgba, void *d_depth
   bool marched = false;  // (a frame with shadows opens the kernel-time bracket before its light march)
   if (c->shadow_on) {
     if (smk_shadow_frame(c, P, d_rgba, d_depth, s, &marched)) return 1;
-    if (!marched) return frame_close(c, s, -1);  // (a launch per slice: the whole frame)
+    if (!marched) return smk_clip_slice_stage(c, P, s) ? 1 : frame_close(c, s, -1);  // (a launch per slice: the whole frame)
   }
   KernelChoice k = choose_kernel(c, P, d_depth != nullptr, s);
   if (c->opt_kernel == 3 && launch_cols(c, P, s)) return 1;
@@ -324,6 +325,9 @@ static int render_frame(smk_ctx *c, const char *who, void *d_rgba, void *d_depth
   } else if (c->opt_kernel == 2)
     FAIL(c, "smk_render: slab kernel forced but classification mode %d is gather-only", c->tf_mode);
   if (c->last_kernel == 1 && launch_gather(c, P, marched, s)) return 1;
+  // the clip-plane widget's data slice (smk_clip_slice.hip) composes onto the finished volume frame, whichever ray-marcher
+  // made it, before the frame's completion event (and so before a shard's exchange); nothing is launched unless it is on
+  if (smk_clip_slice_stage(c, P, s)) return 1;
   return frame_close(c, s, k.trial);
 }
 

@@ -274,6 +274,11 @@ struct smk_ctx {
   float clip_vpos[3] = {0, 0, 0};
   int cplane_on = 0;  // free clip plane (glClipPlane), eye space
   double cplane_eye[4] = {0, 0, 0, 0};
+  // the clip-plane widget's data slice (smk_set_clip_slice; smk_clip_slice.hip)
+  int clip_slice_on = 0, clip_slice_look = 0;
+  float clip_slice_corners[4][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+  float clip_slice_alpha = 0, clip_slice_dv = 0;
+  int clip_slice_pass = 0;  // the pass the last frame's rule chose: 0 none, 1 before, 2 after (smk_get_stat "clip_slice_pass")
   void *d_vox = nullptr;
   void *d_vox_x = nullptr;  // x-major copy [x][z][y] for views whose principal axis is x (lazy)
   float4 *d_brick_mm = nullptr;  // per brick of the stored box: range of the first two channels (smk_bricks.hip)
@@ -490,6 +495,10 @@ int smk_cols_stat(smk_ctx *c, const char *name, double *value);  // smk_get_stat
 int smk_shadow_setup(smk_ctx *c, RenderParams &P, smk_shadowcoef &sc, SmkShadowShard *S, int *halo_need);
 int smk_shadow_light_owned(smk_ctx *c, RenderParams &P, smk_shadowcoef &sc, float olo[3], float ohi[3]);
 int smk_shadow_frame(smk_ctx *c, RenderParams &P, void *d_rgba, void *d_depth, hipStream_t s, bool *marched);
+bool smk_shadow_light_along_view(const smk_ctx *c);  // the reference's axis[3] = vdl > 0 (compute_shadowcoef's front_to_back)
+// the clip-plane widget's data slice composed onto the finished volume frame of P, on the frame's stream (smk_clip_slice.hip);
+// launches nothing unless smk_set_clip_slice and the orthogonal clip plane are on
+int smk_clip_slice_stage(smk_ctx *c, const RenderParams &P, hipStream_t s);
 #pragma GCC visibility pop
 
 // time steps (smk_timesteps.hip).  The step frames render is current; a frame's stream waits for its upload, and its end is

@@ -11,6 +11,31 @@
 
 static double dot3d(const double a[3], const double b[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 
+// The unit view direction, the unit light direction (ldir = -light.pos), the light's distance d0 and the dot product vdl, the
+// sign the reference keeps in axis[3] (R8kVolRen3D.cpp:296-324); false where eye == at or the light sits at the origin
+static bool view_and_light(const smk_ctx *c, double vd[3], double ld[3], double *light_dist, double *vdl) {
+  for (int k = 0; k < 3; ++k) {
+    vd[k] = (double)c->at[k] - c->eye[k];
+    ld[k] = -(double)c->light_pos[k];
+  }
+  const double vl = sqrt(dot3d(vd, vd)), d0 = sqrt(dot3d(ld, ld));
+  if (!(vl > 0) || !(d0 > 0)) return false;
+  for (int k = 0; k < 3; ++k) {
+    vd[k] /= vl;
+    ld[k] /= d0;
+  }
+  *light_dist = d0;
+  *vdl = dot3d(vd, ld);
+  return true;
+}
+
+// vdl > 0: the slices run away from the viewer (smk_shadowcoef's front_to_back), for a stage that needs nothing else of
+// the set-up (smk_clip_slice.hip); a degenerate light fails the frame itself, with the reason
+bool smk_shadow_light_along_view(const smk_ctx *c) {
+  double vd[3], ld[3], d0 = 0, vdl = 0;
+  return view_and_light(c, vd, ld, &d0, &vdl) && vdl > 0;
+}
+
 // Half-angle slicing set-up (R8kVolRen3D.cpp:296-326; light transform LTWidgetRen.cpp:231-291; light-buffer
 // coordinates R8kVolRen3D.cpp:1664-1676), everything in double, rounded once: slice planes sn . X = tmin + k dc
 // in model space, eye rays X = e + tau (R0 px + R1 py - n R2), light rays from the apex of the light's
@@ -18,15 +43,8 @@ static double dot3d(const double a[3], const double b[3]) { return a[0] * b[0] +
 static int compute_shadowcoef(smk_ctx *c, smk_shadowcoef *o) {
   memset(o, 0, sizeof *o);
   const double f[3] = {c->fsize[0], c->fsize[1], c->fsize[2]}, N[3] = {(double)c->N[0], (double)c->N[1], (double)c->N[2]};
-  double vd[3] = {(double)c->at[0] - c->eye[0], (double)c->at[1] - c->eye[1], (double)c->at[2] - c->eye[2]};
-  double ld[3] = {-(double)c->light_pos[0], -(double)c->light_pos[1], -(double)c->light_pos[2]};
-  const double vl = sqrt(dot3d(vd, vd)), d0 = sqrt(dot3d(ld, ld));
-  if (!(vl > 0) || !(d0 > 0)) FAIL(c, "smk_render: shadows need eye != at and a light away from the origin");
-  for (int k = 0; k < 3; ++k) {
-    vd[k] /= vl;
-    ld[k] /= d0;
-  }
-  const double vdl = dot3d(vd, ld);
+  double vd[3], ld[3], d0 = 0, vdl = 0;
+  if (!view_and_light(c, vd, ld, &d0, &vdl)) FAIL(c, "smk_render: shadows need eye != at and a light away from the origin");
   if (vdl <= 0)
     for (int k = 0; k < 3; ++k) vd[k] = -vd[k];
   double h[3];

@@ -276,6 +276,25 @@ void HipVolumeRenderable::draw() {
   // Phong of the platform's renderer: register combiners on the GeForce3 targets (NV20VolRen3D.cpp:634-806),
   // the cube-map shader everywhere else (R8kVolRen3D.cpp:2620-2679, 2886-2902; renderer choice gluvv.cpp:141-199)
   const bool nv20 = gluvv.plat == GPNV20 || gluvv.plat == GPNV202D;
+  // the widget's data slice (drawClip, R8kVolRen3D.cpp:360-372, 400-424; NV20VolRen3D.cpp:144-148, 173-178): the corners and
+  // alpha CPWidgetRen::set_info publishes, and dv = dot(normalize(eye - clip.pos), normalize(clip.dir)) as renderVolume
+  // computes it (R8kVolRen3D.cpp:273-281; a widget that has not published a direction yet draws no slice).  Its colour is
+  // the platform's renderer's: the NV20 final combiner, else the R8k clip shader (what gluvv.cpp:169 instantiates).
+  {
+    float vd[3], cd[3], lv = 0, lc = 0;
+    for (int i = 0; i < 3; ++i) {
+      vd[i] = gluvv.env.eye[i] - gluvv.clip.pos[i];
+      cd[i] = gluvv.clip.dir[i];
+      lv += vd[i] * vd[i];
+      lc += cd[i] * cd[i];
+    }
+    lv = sqrtf(lv);
+    lc = sqrtf(lc);
+    const float dv = lv > 0 && lc > 0 ? (vd[0] / lv) * (cd[0] / lc) + (vd[1] / lv) * (cd[1] / lc) + (vd[2] / lv) * (cd[2] / lc) : 0.0f;
+    if (smk_set_clip_slice(c, gluvv.clip.on && gluvv.clip.ortho, gluvv.clip.corners, gluvv.clip.alpha, dv,
+                           nv20 ? SMK_CLIP_LOOK_NV20 : SMK_CLIP_LOOK_R8K))
+      std::cerr << "ERROR: HipVolumeRenderable::draw: " << smk_last_error(c) << std::endl;
+  }
   smk_shade sm = SMK_SHADE_NONE;
   if (gluvv.shade == gluvvShadeDiff) sm = nv20 ? SMK_SHADE_NV20_DIFF : SMK_SHADE_R8K_DIFF;
   if (gluvv.shade == gluvvShadeDSpec) sm = nv20 ? SMK_SHADE_NV20_DSPEC : SMK_SHADE_R8K_DSPEC;

@@ -344,6 +344,8 @@ struct gluvvClip {
   float pos[3];
   float vpos[3];
   float dir[3];
+  float mousepnt[3];
+  float corners[4][3];
 };
 
 struct gluvvPert {
