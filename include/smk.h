@@ -485,7 +485,9 @@ int smk_timing_reset(smk_ctx *ctx);
 int smk_timing_read(smk_ctx *ctx, float *avg_ms, int *nframes);
 /* named counters of the last frame (developer statistics, no reference counterpart):
  * "slab_iters", "slab_active_lanes", "slab_inside_lanes" (lanes that interpolate a sample: not skipped as part of an
- * empty layer), "slab_hit_lanes" (collected when option
+ * empty layer), "slab_hit_lanes", "slab_iters_with_maybe" (turns in which a lane passes the table's occupancy bit),
+ * "slab_visible_kcyc", "slab_texel_wait_kcyc" (cycles of those turns' visible path, and of them waiting for the table
+ * texels) (collected when option
  * lockstep has bit 16 set), "slab_status" (these synchronise the device); "light_samples" (the light-march samples of
  * the current frame with shadows this context owns -- all of them on the whole volume; synchronises); "slab_failures",
  * "slab_retries" (host-side counters, no synchronisation); "clip_slice_pass" (which pass of smk_set_clip_slice the last

@@ -1073,11 +1073,14 @@ static int count_on_device(smk_ctx *c, Launch launch, double *out) {
 extern "C" int smk_get_stat(smk_ctx *c, const char *name, double *value) {
   if (!c || !name || !value) return 1;
   HIPCHK(c, hipSetDevice(c->device));
-  static const char *diag_names[16] = {"slab_iters", "slab_active_lanes", "slab_inside_lanes", "slab_hit_lanes",
+  static const char *diag_names[SMK_SLAB_NDIAG] = {"slab_iters", "slab_active_lanes", "slab_inside_lanes", "slab_hit_lanes",
                                       "slab_loader_issue_kcyc", "slab_loader_wait_kcyc", "slab_loader_blocked_kcyc", "slab_loader_total_kcyc",
                                       "slab_iters_with_hit", "slab_lead_sum", "slab_waits", "slab_wstep_sum", "slab_dead_tail_sum", "slab_waves",
-                                      "slab_iters_sampling", "slab_iters_own_brick"};
-  for (int k = 0; k < 16; ++k)
+                                      "slab_iters_sampling", "slab_iters_own_brick",
+                                      // turns with a lane on the visible path (occupancy bit set), that path's cycles, and those
+                                      // of them spent waiting for the table texels (lockstep bit 512: waited for where issued)
+                                      "slab_iters_with_maybe", "slab_visible_kcyc", "slab_texel_wait_kcyc"};
+  for (int k = 0; k < SMK_SLAB_NDIAG; ++k)
     if (!strcmp(name, diag_names[k])) {
       float v = 0.f;
       if (c->slab.d_diag && read_back(c, &v, c->slab.d_diag + k, 1)) return 1;

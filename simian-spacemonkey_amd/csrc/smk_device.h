@@ -251,11 +251,15 @@ __device__ __forceinline__ bool smk_classify(const RenderParams &P, float ch0, f
 // in: straight colour col (col.w = alpha); out: premultiplied src
 // `shadow`: the light-buffer colour at the sample (half-angle slicing), applied as the R8k eye shader does
 // -- MUL r0, r0, 1 - r5 before the colour is weighted by its opacity (R8kVolRen3D.cpp:2928-2934); null = none
+// The Phong term in two halves, so that a kernel can run the first -- which needs the normal alone -- while the sample's
+// table texels are still on their way (slice-ring kernel, smk_slab.hip), and the second once colour and alpha are known.
+// What the normal contributes: R8k the diffuse and specular factors kd, ks; NV20 |N.L| (kd) and the specular power (ks).
+struct SmkPhong {
+  float kd, ks;
+};
 template <int SH>
-__device__ __forceinline__ float4 smk_shade_sample(const RenderParams &P, float4 col, float n0, float n1, float n2, float g,
-                                                   const float *shadow = nullptr) {
-  float a = col.w;
-  float c[3] = {col.x, col.y, col.z};
+__device__ __forceinline__ SmkPhong smk_shade_geom(const RenderParams &P, float n0, float n1, float n2) {
+  SmkPhong o = {0.f, 0.f};
   if (SH == 1) {
     float w0 = __fmaf_rn(P.R[0], n0, __fmaf_rn(P.R[1], n1, P.R[2] * n2));
     float w1 = __fmaf_rn(P.R[3], n0, __fmaf_rn(P.R[4], n1, P.R[5] * n2));
@@ -267,24 +271,35 @@ __device__ __forceinline__ float4 smk_shade_sample(const RenderParams &P, float4
     w2 *= il;
     float dl = fabsf(__fmaf_rn(P.L[0], w0, __fmaf_rn(P.L[1], w1, P.L[2] * w2)));
     float dh = fabsf(__fmaf_rn(P.Hv[0], w0, __fmaf_rn(P.Hv[1], w1, P.Hv[2] * w2)));
-    float kd = smk_clampf(dl, 0.2f, 1.0f) * P.intens;  // == sat(max(sat(dl), .2))
-    float ks = P.use_spec ? smk_sat(smk_pow30(smk_sat(dh))) * P.intens : 0.0f;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      float shaded = __fmaf_rn(c[k], kd, ks);
-      c[k] = __fmaf_rn(g, shaded - c[k], c[k]);
-    }
+    o.kd = smk_clampf(dl, 0.2f, 1.0f) * P.intens;  // == sat(max(sat(dl), .2))
+    o.ks = P.use_spec ? smk_sat(smk_pow30(smk_sat(dh))) * P.intens : 0.0f;
   } else if (SH == 2) {
     float dl = fabsf(__fmaf_rn(P.L[0], n0, __fmaf_rn(P.L[1], n1, P.L[2] * n2)));
     float dh = __fmaf_rn(P.Hv[0], n0, __fmaf_rn(P.Hv[1], n1, P.Hv[2] * n2));
     float s2 = smk_sat(dh * dh), s4 = s2 * s2, s8 = s4 * s4, s16 = s8 * s8;
-    float spec = P.use_spec ? s16 * P.intens * a : 0.0f;
+    o.kd = dl;
+    o.ks = s16;
+  }
+  return o;
+}
+template <int SH>
+__device__ __forceinline__ float4 smk_shade_apply(const RenderParams &P, float4 col, float g, SmkPhong ph, const float *shadow = nullptr) {
+  float a = col.w;
+  float c[3] = {col.x, col.y, col.z};
+  if (SH == 1) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      float shaded = __fmaf_rn(c[k], ph.kd, ph.ks);
+      c[k] = __fmaf_rn(g, shaded - c[k], c[k]);
+    }
+  } else if (SH == 2) {
+    float spec = P.use_spec ? ph.ks * P.intens * a : 0.0f;
     float ia = P.intens * a, aa = 0.3f * a;
     float4 o;
     float r[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-      float cc = smk_sat(__fmaf_rn(c[k] * smk_sat(dl), ia, c[k] * aa));
+      float cc = smk_sat(__fmaf_rn(c[k] * smk_sat(ph.kd), ia, c[k] * aa));
       r[k] = smk_sat(__fmaf_rn(spec, 1.0f - cc, cc));
     }
     o.x = r[0];
@@ -298,6 +313,11 @@ __device__ __forceinline__ float4 smk_shade_sample(const RenderParams &P, float4
     for (int k = 0; k < 3; ++k) c[k] *= 1.0f - shadow[k];
   }
   return make_float4(smk_sat(c[0] * a), smk_sat(c[1] * a), smk_sat(c[2] * a), a);
+}
+template <int SH>
+__device__ __forceinline__ float4 smk_shade_sample(const RenderParams &P, float4 col, float n0, float n1, float n2, float g,
+                                                   const float *shadow = nullptr) {
+  return smk_shade_apply<SH>(P, col, g, smk_shade_geom<SH>(P, n0, n1, n2), shadow);
 }
 
 __device__ __forceinline__ float smk_nrm(uint32_t a, uint32_t b, uint32_t c, uint32_t d, uint32_t e, uint32_t f,

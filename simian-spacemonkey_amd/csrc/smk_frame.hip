@@ -97,7 +97,7 @@ static int status_ring_ready(smk_ctx *c) {
   if (c->slab.h_status) return 0;
   HIPCHK(c, hipHostMalloc((void **)&c->slab.h_status, SMK_STATUS_RING * sizeof(int), hipHostMallocMapped));
   for (int k = 0; k < SMK_STATUS_RING; ++k) c->slab.h_status[k] = 0;
-  HIPCHK(c, hipMalloc((void **)&c->slab.d_diag, 16 * sizeof(float)));
+  HIPCHK(c, hipMalloc((void **)&c->slab.d_diag, SMK_SLAB_NDIAG * sizeof(float)));
   return 0;
 }
 
@@ -236,7 +236,7 @@ static int launch_cols(smk_ctx *c, const RenderParams &P, hipStream_t s) {
 // gather kernel's (and in auto mode no trial)
 static int launch_slab(smk_ctx *c, const RenderParams &P, KernelChoice &k, bool ev0_recorded, hipStream_t s) {
   if (status_ring_ready(c)) return 1;
-  if (c->opt_lockstep & 16) HIPCHK(c, hipMemsetAsync(c->slab.d_diag, 0, 16 * sizeof(float), s));
+  if (c->opt_lockstep & 16) HIPCHK(c, hipMemsetAsync(c->slab.d_diag, 0, SMK_SLAB_NDIAG * sizeof(float), s));
   const char *why = nullptr;
   c->slab.frame_ev0 = ev0_recorded ? nullptr : c->ev0;
   hipError_t e = smk_launch_slab(P, c->dtype, c->tf_mode, smk_shade_kind(c), c->d_vox, c->d_vox_x, &c->slab, &why, s);

@@ -135,12 +135,13 @@ struct RenderParams {
 };
 
 // side buffers of the slice-ring kernel, owned by the context
+constexpr int SMK_SLAB_NDIAG = 19;  // counters of the slice-ring kernel's diagnostic instance (names: smk_get_stat)
 struct SlabAux {
   int *h_status = nullptr;      // pinned, device-visible: SMK_STATUS_RING error words (0 = ok), one per frame in turn
   int status_slot = 0;          // the word of the frame being launched
   int status_tag = 0;           // ... and that frame's id << 8, which the kernel writes with its status
   hipEvent_t frame_ev0 = nullptr;  // recorded by the launcher right before its first stream operation
-  float *d_diag = nullptr;      // [16] diagnostic counters (option lockstep bit 16)
+  float *d_diag = nullptr;      // [SMK_SLAB_NDIAG] diagnostic counters (option lockstep bit 16)
   int2 *d_order = nullptr;      // workgroup schedule of the current camera
   int2 *h_order[4] = {nullptr, nullptr, nullptr, nullptr};  // pinned staging copies, used in turn
   hipEvent_t order_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // completion of each one's last copy

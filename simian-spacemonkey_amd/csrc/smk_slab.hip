@@ -982,6 +982,11 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
       const bool count = DIAG && (P.lockstep & 48) != 0 && Q.diag != nullptr;
       float n_it = 0.f, n_act = 0.f, n_in = 0.f, n_hit = 0.f, n_anyhit = 0.f, n_lead = 0.f, n_waits = 0.f, n_wstep = 0.f;
       float n_work = 0.f, n_own = 0.f;
+      // (turns in which some lane's occupancy bit is set -- the visible path runs --, the cycles of that path, from the issue
+      //  of the table loads to the blend, and the cycles of them spent waiting for the texels: two time stamps each)
+      float n_anymaybe = 0.f, c_vis = 0.f, c_texwait = 0.f;
+      // (diagnostic: wait for the texels where they are issued, as the kernel did before the normal work moved under them)
+      const bool texwait_at_issue = count && (P.lockstep & 512) != 0;
       int have = 0;  // cached copy of `landed` (monotonic): re-polled only when a lane is blocked on it
       const float inv_bs = 1.0f / B[AS];  // (planes per slice along this ray; the principal axis' B is never 0)
       // table row of the sample's base slice: entry index = bs - Os = psgn*pb + (-psgn*poff - Os)
@@ -1048,7 +1053,8 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
           n_wstep += (float)Q.wstep;
         }
         asm volatile("" ::: "memory");  // slot reads stay behind the poll
-        bool d_hit = false, d_own = false;  // (diagnostic counters only)
+        bool d_hit = false, d_own = false, d_maybe = false;  // (diagnostic counters only)
+        unsigned d_t0 = 0, d_vis = 0, d_wait = 0;
         // ---- part A: where the sample is and its corner addresses; EARLY: the whole corner batch
         float fx = 0.f, fy = 0.f, fz = 0.f;
         unsigned a0 = 0, b0 = 0;
@@ -1230,6 +1236,26 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
 #undef E0
           }
 #undef TRI
+          // what the interpolated normal contributes to the Phong term (smk_shade_geom): the packed normals of the same
+          // corners -- a second batch of LDS reads, or already here (EARLY) --, their interpolation, the two dot products
+          auto phong_geom = [&]() -> SmkPhong {
+            uint32_t nb[8];
+            if constexpr (EARLY) {
+#pragma unroll
+              for (int k = 0; k < 8; ++k) {
+                if constexpr (DT == 1) nb[k] = __float_as_uint(rq[k].w);
+                else nb[k] = rq[k].y;
+              }
+            } else if (DT == 1) slab_read8_nb16(a0, a0 + pitch_b, b0, b0 + pitch_b, nb);
+            else slab_read8_nb8(a0, a0 + pitch_b, b0, b0 + pitch_b, nb);
+#define NB(dx, dy, dz) nb[QI(dx, dy, dz)]
+            float n0 = smk_nrm(NB(0, 0, 0), NB(1, 0, 0), NB(0, 1, 0), NB(1, 1, 0), NB(0, 0, 1), NB(1, 0, 1), NB(0, 1, 1), NB(1, 1, 1), 0, fx, fy, fz);
+            float n1 = smk_nrm(NB(0, 0, 0), NB(1, 0, 0), NB(0, 1, 0), NB(1, 1, 0), NB(0, 0, 1), NB(1, 0, 1), NB(0, 1, 1), NB(1, 1, 1), 1, fx, fy, fz);
+            float n2 = smk_nrm(NB(0, 0, 0), NB(1, 0, 0), NB(0, 1, 0), NB(1, 1, 0), NB(0, 0, 1), NB(1, 0, 1), NB(0, 1, 1), NB(1, 1, 1), 2, fx, fy, fz);
+#undef NB
+            return smk_shade_geom<SH>(P, n0, n1, n2);
+          };
+          SmkPhong ph = {0.f, 0.f};
           float4 col;
           bool hit;
           SlabTexel4 tx4 = {0, 0, 0, 0, 0.f, 0.f};
@@ -1244,8 +1270,28 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
             if (Q.use_occ) maybe = (occ[__mul24(t0, P.occ_roww) + (s0 >> 5)] >> (s0 & 31)) & 1u;
             col.w = 0.0f;
             if (maybe) {
-              // alpha first (all four (V,G) texels are needed for it anyway); colour only on a hit
+              if (count) {
+                d_maybe = true;
+                d_t0 = (unsigned)__builtin_amdgcn_s_memtime();
+              }
               tx4 = slab_tex2d_fetch(P.tf_vg, P.sv, s0, t0, fs, ft);
+              if (texwait_at_issue) {
+                const unsigned t = (unsigned)__builtin_amdgcn_s_memtime();
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                d_wait = (unsigned)__builtin_amdgcn_s_memtime() - t;
+              }
+              // SHADE UNDER THE FETCH.  The four texels come from L2; nothing of the normal's share of the Phong term needs
+              // them -- the second batch of LDS reads, 21 lerps, the rotation, rsqrt, two dot products and the specular power,
+              // the larger half of a visible sample's arithmetic -- so it runs here, behind the issue of the loads and in front
+              // of their first use.  (The asm statement of the LDS batch keeps the loads above it; the wait for them is the
+              // compiler's, in front of the alpha below.)  A sample that then turns out to have alpha 0 paid it for nothing.
+              if constexpr (SH != 0) ph = phong_geom();
+              if (count) {
+                const unsigned t = (unsigned)__builtin_amdgcn_s_memtime();
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                d_wait += (unsigned)__builtin_amdgcn_s_memtime() - t;
+              }
+              // alpha first (all four (V,G) texels are needed for it anyway); colour only on a hit
               col.w = slab_tex_chan(tx4, 3);
               if (Q.use_ah) {  // third-axis alpha (the same products as smk_classify)
                 if (lazy_h) ch2 = tri_h_early();
@@ -1295,21 +1341,9 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
             } else if (SH == 0) {
               src = smk_shade_sample<0>(P, col, 0.f, 0.f, 0.f, 0.f, shp);
             } else {
-              uint32_t nb[8];  // the packed normals of the same corners: second batch, or already here (EARLY)
-              if constexpr (EARLY) {
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                  if constexpr (DT == 1) nb[k] = __float_as_uint(rq[k].w);
-                  else nb[k] = rq[k].y;
-                }
-              } else if (DT == 1) slab_read8_nb16(a0, a0 + pitch_b, b0, b0 + pitch_b, nb);
-              else slab_read8_nb8(a0, a0 + pitch_b, b0, b0 + pitch_b, nb);
-#define NB(dx, dy, dz) nb[QI(dx, dy, dz)]
-              float n0 = smk_nrm(NB(0, 0, 0), NB(1, 0, 0), NB(0, 1, 0), NB(1, 1, 0), NB(0, 0, 1), NB(1, 0, 1), NB(0, 1, 1), NB(1, 1, 1), 0, fx, fy, fz);
-              float n1 = smk_nrm(NB(0, 0, 0), NB(1, 0, 0), NB(0, 1, 0), NB(1, 1, 0), NB(0, 0, 1), NB(1, 0, 1), NB(0, 1, 1), NB(1, 1, 1), 1, fx, fy, fz);
-              float n2 = smk_nrm(NB(0, 0, 0), NB(1, 0, 0), NB(0, 1, 0), NB(1, 1, 0), NB(0, 0, 1), NB(1, 0, 1), NB(0, 1, 1), NB(1, 1, 1), 2, fx, fy, fz);
-#undef NB
-              src = smk_shade_sample<SH>(P, col, n0, n1, n2, ch1, shp);
+              // (the separable table's path has the normal's share already: SHADE UNDER THE FETCH)
+              if (!(TF == 1 && Q.fast_tf)) ph = phong_geom();
+              src = smk_shade_apply<SH>(P, col, ch1, ph, shp);
             }
             // first-hit depth (the gather kernel's `first`): the first sample that passes classification finds the accumulated
             // alpha still exactly 0, no later one does -- nothing is carried through the loop for it
@@ -1330,6 +1364,7 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
               if (C3 == 1.0f) m1 = m;
             }
           }
+          if (count && d_maybe) d_vis = (unsigned)__builtin_amdgcn_s_memtime() - d_t0;
 #undef QI
         }
         if (act) {
@@ -1355,6 +1390,13 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
           n_anyhit += __any(d_hit) ? 1.f : 0.f;
           n_work += __any(work) ? 1.f : 0.f;
           n_own += __any(work && d_own) ? 1.f : 0.f;
+          const unsigned long long mm = __ballot(d_maybe);
+          if (mm) {  // (the stamps are the wave's: any lane that ran the visible path holds them)
+            const int src = __ffsll(mm) - 1;
+            n_anymaybe += 1.f;
+            c_vis += (float)(unsigned)__builtin_amdgcn_readlane((int)d_vis, src);
+            c_texwait += (float)(unsigned)__builtin_amdgcn_readlane((int)d_wait, src);
+          }
         }
         }  // rep
       }
@@ -1374,6 +1416,9 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
         // (how much of the tile's slice range this wave did not need: it finished at position `pos`)
         atomicAdd(&Q.diag[12], (float)max(npos - min(pos, npos), 0) / (float)max(npos, 1));
         atomicAdd(&Q.diag[13], 1.0f);
+        atomicAdd(&Q.diag[16], n_anymaybe);
+        atomicAdd(&Q.diag[17], c_vis * 1e-3f);
+        atomicAdd(&Q.diag[18], c_texwait * 1e-3f);
       }
     }
   }
