@@ -501,7 +501,10 @@ int smk_get_stat(smk_ctx *ctx, const char *name, double *value);
  * leaves its record empty).
  * *nrecords = records available; copies min(cap_records, *nrecords) when out != NULL. */
 int smk_get_trace(smk_ctx *ctx, unsigned *out, int cap_records, int *nrecords);
-/* effective 2-D TF after opacity correction, as uploaded (sg*sv*4 bytes) */
+/* effective 2-D TF after opacity correction (sg*sv*4 bytes) and the rate it was corrected with.  This is a HOST
+ * recomputation: the alpha map of the current rate applied to the host copy of the raw table -- not a read-back of
+ * what the device kernel wrote into the table version the frames fetch from.  The device table, its occupancy bitmap
+ * and the brick flags built on it are checked through frames and flags in tests/test_gpu_tf_correction.py. */
 int smk_get_tf2d_effective(smk_ctx *ctx, unsigned char *out, float *rate_out);
 
 #ifdef __cplusplus

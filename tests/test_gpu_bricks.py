@@ -63,8 +63,10 @@ def test_flags_skip_something_and_the_checker_agrees(R):
 
 
 def test_flags_follow_the_table(R):
-    """a new table (and a new correction rate) brings new flags: first a table that hides everything but a band,
-    then an opaque one, then the first again -- each frame equal to the gather kernel's"""
+    """a new table brings new flags: first a table that hides everything but a band, then an opaque one, then the first
+    again -- each frame equal to the gather kernel's.  (The step count changes too, but push_scene sets tf_raw 1: the
+    tables are taken as already corrected and the rate changes nothing here.  Frames under a rate that moves are
+    test_gpu_tf_correction.py's.)"""
     sc = make_scene("cfg3", n=64, size=96, steps=128, pose="diag", f32=True, shade=1)
     R.set_option("bricks", 1)
     push_scene(R, sc)
@@ -194,33 +196,51 @@ def test_perturbed_fetch(R, kind, weights):
                                            ("tf3d_panes", True, None), ("cfg3", True, (41, 23, 70))])
 def test_flags_equal_the_numpy_restatement(R, kind, f32, dims):
     """the flags themselves, byte for byte, against oracle/bricks.py (value ranges over the voxels a brick's cells touch,
-    the occupancy bitmap of the EFFECTIVE table, the summed-area range test widened by one texel)"""
+    the occupancy bitmap of the EFFECTIVE table, the summed-area range test widened by one texel) -- with the table handed
+    over as already corrected (tf_raw 1), and for the 2-D tables once more handed over raw and corrected on the device,
+    where the expected flags come from the table tests/_tf_correction.py corrected and the read-back has to equal it"""
     import bricks as B      # oracle/bricks.py
+    import _tf_correction as T
     sc = make_scene(kind, n=48, size=64, steps=96, pose="rot", f32=f32, shade=1, dims=dims)
-    R.set_option("bricks", 1)
-    push_scene(R, sc)
-    got, in_use = R.brick_flags()
     vol = sc.data
     if vol.dtype == np.uint8:
         v = vol[..., 0].astype(np.float32) * np.float32(1.0 / 255.0)
         g = vol[..., 1].astype(np.float32) * np.float32(1.0 / 255.0)
     else:
         v, g = vol[..., 0].astype(np.float32), vol[..., 1].astype(np.float32)
+
+    def check(occ):
+        got, in_use = R.brick_flags()
+        want = B.brick_flags(np.ascontiguousarray(v), np.ascontiguousarray(g), occ)
+        assert got.shape == want.shape
+        assert np.array_equal(got, want), "%d of %d flags differ" % ((got != want).sum(), got.size)
+        assert in_use == (want.mean() <= 0.9) or in_use    # (dropped only once the count came back above 90 %)
+
+    R.set_option("bricks", 1)
+    push_scene(R, sc)
     if sc.tf_mode == 2:
-        occ = B.fold_occupancy(sc.tf3d[..., 3])
-    else:
-        eff, _ = R.tf2d_effective(sc.tf_vg.shape[1], sc.tf_vg.shape[0])
-        occ = B.occupancy(eff[..., 3])
-    want = B.brick_flags(np.ascontiguousarray(v), np.ascontiguousarray(g), occ)
-    assert got.shape == want.shape
-    assert np.array_equal(got, want), "%d of %d flags differ" % ((got != want).sum(), got.size)
-    assert in_use == (want.mean() <= 0.9) or in_use    # (dropped only once the count came back above 90 %)
+        check(B.fold_occupancy(sc.tf3d[..., 3]))
+        return
+    eff, _ = R.tf2d_effective(sc.tf_vg.shape[1], sc.tf_vg.shape[0])
+    check(B.occupancy(eff[..., 3]))
+    raw = sc.tf_vg.copy()
+    try:
+        rate = T.push_corrected(R, sc, raw, upload=False)
+        want_eff = T.apply(raw, rate)
+        check(B.occupancy(want_eff[..., 3]))
+        eff, got_rate = R.tf2d_effective(raw.shape[1], raw.shape[0])
+        assert np.float32(got_rate).tobytes() == np.float32(rate).tobytes(), (got_rate, rate)
+        assert np.array_equal(eff, want_eff)
+    finally:
+        R.set_option("tf_raw", 1)
 
 
 def test_a_table_edited_every_frame_without_synchronising(R):
-    """the interactive case: a new table AND a new correction rate every frame, frames enqueued without waiting (the raw
+    """the interactive case: a new table and a new step count every frame, frames enqueued without waiting (the raw
     table, its effective versions, their bitmaps and brick flags all rotate behind stream events); every eighth frame
-    is compared with the gather kernel's, flags off, after the fact"""
+    is compared with the gather kernel's, flags off, after the fact.  (tf_raw is 1 here: the map stays the identity
+    whatever the rate; two different corrections of ONE table go through the versions in
+    test_gpu_tf_correction.py::test_a_turning_camera_without_waiting.)"""
     import torch
     sc = make_scene("cfg3", n=64, size=96, steps=128, pose="rot", f32=True, shade=1)
     R.set_option("bricks", 1)

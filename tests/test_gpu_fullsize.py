@@ -53,11 +53,11 @@ def test_full_size_frames(gpu_renderer_factory, O, n, workload):
         # CPU checker on random rays of the same frame (same effective table, same matrix); the checker
         # works per ray, so the 1024^3 north-star frame costs it memory for the volume (13 GB as f32 on
         # the host) and a few seconds: 600 rays at 512^3, 300 at 1024^3
-        tf_eff, _ = r.tf2d_effective(256, 256)
+        tf_eff, tf_rate = r.tf2d_effective(256, 256)
         sc = O.Scene(vghf.cpu().numpy(), grad=nrm.cpu().numpy())
         del vghf, nrm
         torch.cuda.empty_cache()
-        sc.tf_mode, sc.tf_vg = 1, tf_eff
+        sc.tf_mode = 1
         if workload == "cfg4":
             sc.tf_h, sc.third_axis = np.load(os.path.join(ROOT, "tests", "golden", "tf_h_slider05.npy")), 1
         sc.width = sc.height = size
@@ -66,6 +66,14 @@ def test_full_size_frames(gpu_renderer_factory, O, n, workload):
         sc.mv_override = mv
         sc.shade_mode, sc.use_spec = 1, 1
         sc.frustum = b.FRUSTUM
+        # the checker's table: the raw one bench.py hands over, corrected in numpy with the rate of the CHECKER's ray set-up
+        # (tests/_tf_correction.py); the product's read-back has to agree with both
+        import _tf_correction as T
+        raw = np.load(os.path.join(ROOT, "tests", "golden", "tf_cfg3_levwidget.npy"))
+        rate = T.frame_rate(sc, 1.0, 1)
+        sc.tf_vg = T.apply(raw, rate)
+        assert np.float32(tf_rate).tobytes() == np.float32(rate).tobytes(), (tf_rate, rate)
+        assert np.array_equal(tf_eff, sc.tf_vg)
         rng = np.random.default_rng(7)
         pix = rng.integers(0, size, size=(600 if n == 512 else 300, 2)).astype(np.int32)   # (i, j)
         ref = sc.render_pixels(pix)
