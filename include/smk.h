@@ -261,6 +261,52 @@ typedef enum { SMK_SCENE_VIEW_DEPTH = 0, SMK_SCENE_WINDOW_DEPTH = 1 } smk_scene_
 int smk_render_occluded(smk_ctx *ctx, const float *scene_depth, int kind, float *rgba_out, float *depth_out);
 int smk_render_occluded_device(smk_ctx *ctx, const void *d_scene_depth, int kind, void *d_rgba, void *d_depth, void *stream);
 
+/* ---- display-ready frames (DESIGN.md "Present").  The reference's frame IS the 8-bit GL framebuffer
+ * its slices blend into, with the depth buffer beside it; smk_render hands the host 16 B per pixel of float RGBA in pageable
+ * memory and leaves the depth conversion to it.  These entries deliver what the framebuffer takes: [height][width] RGBA8
+ * (R in byte 0, row 0 = bottom) and, on request, [height][width] float32 window depths, in pinned host memory.
+ *   Colour, q(x) = (uint8) floor(sat(x) * 255 + 0.5), NaN -> 0, fp32, one rounding per operation:
+ *     bg NULL:  every channel c of the premultiplied frame, alpha included, becomes q(c);
+ *     bg[3]:    an opaque background colour in [0, 1] drawn UNDER the frame -- the reference's white quad blended with
+ *               GL_ONE_MINUS_DST_ALPHA, GL_ONE after the renderables (gluvv.cpp:606-623), for any colour --:
+ *               rgb = q(C + (1 - A) * b), a = 255.
+ *   Depth: the first-hit view depth d (depth_out of smk_render) becomes the window depth glReadPixels(GL_DEPTH_COMPONENT)
+ *     would hold, z_w = f (d - n) / ((f - n) d) with (n, f) = smk_set_camera's clip, evaluated in DOUBLE, clamped to [0, 1]
+ *     and rounded once to float: the inverse of SMK_SCENE_WINDOW_DEPTH's conversion.  d = +inf (nothing hit) or NaN gives
+ *     exactly 1 (the cleared depth buffer), d <= n gives 0.  Needs f > n. */
+/* replaces the host's own float -> 8-bit conversion and glDrawPixels(GL_FLOAT)'s, and the "convert on the
+ * host" step of INTEGRATION.md 4: the conversion ALONE, asynchronous on `stream` (NULL: the context's stream), of any frame of
+ * the context's window size in DEVICE memory -- of smk_render_device, merged by smk_composite_over[_depth]_device, an exchange
+ * result on rank 0.  d_rgba: [h][w][4] floats, 16-byte aligned; d_rgba8: [h][w][4] bytes (16-byte aligned buffers are written
+ * with 16-byte stores); d_depth_or_null / d_zwin_or_null: [h][w] floats each, both or neither. */
+int smk_present_device(smk_ctx *ctx, const void *d_rgba, const void *d_depth_or_null, const float *bg_or_null, void *d_rgba8,
+                       void *d_zwin_or_null, void *stream);
+/* replaces gluvvPrimitive::draw() + the framebuffer the host then reads or blits (smk_render + the host's conversion): one
+ * frame, synchronous -- the ray-march (smk_render_occluded's when scene_depth_or_null, HOST memory of kind scene_depth_kind,
+ * is given), the conversion, the copy into pinned host buffers the context owns.  *rgba8 and *zwin (NULL when want_depth is 0;
+ * either argument may be NULL) point INTO those buffers: see the slots below.  A frame the slice-ring kernel flags is handled
+ * as smk_render handles it: in auto mode it is rendered again by the gather kernel before anything is returned, otherwise the
+ * call fails. */
+int smk_render_present(smk_ctx *ctx, const float *bg_or_null, const float *scene_depth_or_null, int scene_depth_kind,
+                       int want_depth, const unsigned char **rgba8, const float **zwin);
+/* the same frame in two calls (no reference equivalent: the reference renders synchronously).  _begin enqueues the ray-march and
+ * the conversion on the context's stream and the copy to the host on a stream of its own behind them, and returns a ticket
+ * (1, 2, ...) at once: frame k's copy runs beside frame k + 1's ray-march.  _end waits for that ticket's copy and returns the
+ * pointers; a flagged frame is treated as by smk_render_present (the second rendering is synchronous and uses the context's
+ * state at _end).  There are TWO slots, taken in turn; each owns everything its frame needs while in flight -- RGBA8 and
+ * window-depth device buffers, their pinned copies, its copy of scene_depth (taken at _begin) -- so:
+ *   - a slot's pointers stay valid and its bytes unchanged until the SECOND _begin after its own (smk_render_present is a
+ *     _begin + _end and counts as one);
+ *   - a third _begin while two tickets are outstanding is refused;
+ *   - smk_set_camera with another window size is refused while a ticket is outstanding;
+ *   - an unknown or already ended ticket is refused;
+ * each with the reason in smk_last_error.  The float frame is the context's own, written and read in stream order.  Pinned
+ * memory is allocated at a slot's first frame, again when the window's pixel count changes, and released by smk_destroy.
+ * smk_last_frame_info reports the frame _end returned; smk_get_stat "present_ms" / "present_bytes" its conversion and copy. */
+int smk_render_present_begin(smk_ctx *ctx, const float *bg_or_null, const float *scene_depth_or_null, int scene_depth_kind,
+                             int want_depth, long long *ticket);
+int smk_render_present_end(smk_ctx *ctx, long long ticket, const unsigned char **rgba8, const float **zwin);
+
 /* replaces VolumeRenderer::renderSlice(quad, alpha) (VolumeRenderer.h:114, VolumeRenderer.cpp:748-807): ONE quad (model
  * space, the units of fPos / fSize; drawn as glBegin(GL_QUADS) with the vertices in the order 1, 0, 2, 3) textured with the
  * scalar volume -- GL_INTENSITY8, GL_LINEAR, no colour table (:768), texture coordinates = vertex / fSize -- modulated by
@@ -491,7 +537,10 @@ int smk_timing_read(smk_ctx *ctx, float *avg_ms, int *nframes);
  * lockstep has bit 16 set), "slab_status" (these synchronise the device); "light_samples" (the light-march samples of
  * the current frame with shadows this context owns -- all of them on the whole volume; synchronises); "slab_failures",
  * "slab_retries" (host-side counters, no synchronisation); "clip_slice_pass" (which pass of smk_set_clip_slice the last
- * frame's rule chose: 0 none, 1 before the volume, 2 after it; no synchronisation). */
+ * frame's rule chose: 0 none, 1 before the volume, 2 after it; no synchronisation); "present_ms" (the HIP-event time of the
+ * conversion kernel of the last frame smk_render_present[_end] returned, or of the last smk_present_device -- then it waits for
+ * that kernel), "present_bytes" (the bytes the last frame smk_render_present[_end] returned copied to the host: 4 per pixel,
+ * 8 with depth). */
 int smk_get_stat(smk_ctx *ctx, const char *name, double *value);
 /* workgroup timeline of the last slice-ring frame (developer tool):
  * records of 8 x uint32 {start, end (100 MHz ticks), HW_ID, XCC_ID | tile<<8 | slices<<20, loader 0's

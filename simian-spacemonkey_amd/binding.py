@@ -33,6 +33,7 @@ ABI_SYMBOLS = [
     "smk_composite_over_depth_device", "smk_exchange_partial_depth", "smk_exchange_frame_depth", "smk_exchange_frame_local_depth",
     "smk_render_occluded", "smk_render_occluded_device",
     "smk_set_clip_slice",
+    "smk_present_device", "smk_render_present", "smk_render_present_begin", "smk_render_present_end",
 ]
 
 # gluvvDataMode order (gluvv.h:221-235)
@@ -164,6 +165,10 @@ def load_library():
     L.smk_render_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.smk_render_occluded.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     L.smk_render_occluded_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.smk_present_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.smk_render_present.argtypes = [C.c_void_p, P(C.c_float), C.c_void_p, C.c_int, C.c_int, P(C.c_void_p), P(C.c_void_p)]
+    L.smk_render_present_begin.argtypes = [C.c_void_p, P(C.c_float), C.c_void_p, C.c_int, C.c_int, P(C.c_longlong)]
+    L.smk_render_present_end.argtypes = [C.c_void_p, C.c_longlong, P(C.c_void_p), P(C.c_void_p)]
     L.smk_composite_over_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, P(C.c_int), C.c_int,
                                             C.c_void_p, C.c_void_p]
     L.smk_composite_over_depth_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, P(C.c_int), C.c_int,
@@ -514,6 +519,62 @@ class Renderer:
             self._ck(self.L.smk_render_device(self.ctx, d_rgba, d_depth, stream))
         else:
             self._ck(self.L.smk_render_occluded_device(self.ctx, d_scene_depth, int(scene_depth_kind), d_rgba, d_depth, stream))
+
+    # -- display-ready frames (smk.h: smk_present_device ...): RGBA8, window depth, pinned host buffers
+    def present_device(self, d_rgba, d_rgba8, bg=None, d_depth=None, d_zwin=None, stream=None):
+        """the conversion alone, asynchronous on `stream`: the float frame d_rgba ([h][w][4], device) becomes RGBA8 in d_rgba8,
+        composed over the opaque colour bg = (r, g, b) when given; d_depth (view depth) becomes the window depth in d_zwin"""
+        self._ck(self.L.smk_present_device(self.ctx, d_rgba, d_depth, _fa(bg, 3) if bg is not None else None, d_rgba8, d_zwin,
+                                           stream))
+
+    def _scene_depth_arg(self, scene_depth):
+        if scene_depth is None:
+            return None
+        h, w = self.size[1], self.size[0]
+        zs = np.ascontiguousarray(scene_depth, dtype=np.float32)
+        if zs.shape != (h, w):
+            raise ValueError("scene_depth must be [%d][%d] floats, got shape %s" % (h, w, zs.shape))
+        return zs
+
+    def _present_views(self, p8, pz, size):
+        """numpy views of a slot's pinned buffers (valid until the second begin after the slot's own)"""
+        w, h = size
+        rgba8 = np.ctypeslib.as_array(C.cast(p8, C.POINTER(C.c_ubyte)), shape=(h, w, 4))
+        zwin = np.ctypeslib.as_array(C.cast(pz, C.POINTER(C.c_float)), shape=(h, w)) if pz.value else None
+        return rgba8, zwin
+
+    def render_present(self, bg=None, depth=False, scene_depth=None, scene_depth_kind=SCENE_VIEW_DEPTH, copy=True):
+        """one frame as the 8-bit framebuffer takes it: [h][w][4] uint8 (over the opaque colour bg when given) and, with depth,
+        the [h][w] float32 window depth.  Returns numpy copies; copy=False returns views of the context's pinned buffers"""
+        zs = self._scene_depth_arg(scene_depth)
+        p8, pz = C.c_void_p(), C.c_void_p()
+        self._ck(self.L.smk_render_present(self.ctx, _fa(bg, 3) if bg is not None else None, _ptr(zs), int(scene_depth_kind),
+                                           int(bool(depth)), C.byref(p8), C.byref(pz)))
+        rgba8, zwin = self._present_views(p8, pz, self.size)
+        if copy:
+            rgba8, zwin = rgba8.copy(), (zwin.copy() if zwin is not None else None)
+        return (rgba8, zwin) if depth else rgba8
+
+    def render_present_begin(self, bg=None, depth=False, scene_depth=None, scene_depth_kind=SCENE_VIEW_DEPTH):
+        """enqueue a frame, its conversion and its copy to the host; returns the ticket for render_present_end.  At most two
+        tickets are outstanding"""
+        zs = self._scene_depth_arg(scene_depth)
+        t = C.c_longlong(0)
+        self._ck(self.L.smk_render_present_begin(self.ctx, _fa(bg, 3) if bg is not None else None, _ptr(zs),
+                                                 int(scene_depth_kind), int(bool(depth)), C.byref(t)))
+        self._present_sizes = getattr(self, "_present_sizes", {})
+        self._present_sizes[t.value] = self.size
+        return t.value
+
+    def render_present_end(self, ticket, copy=False):
+        """wait for that frame: (rgba8, zwin or None), views of the slot's pinned buffers -- unchanged until the second
+        render_present_begin after the frame's own -- or numpy copies with copy=True"""
+        p8, pz = C.c_void_p(), C.c_void_p()
+        self._ck(self.L.smk_render_present_end(self.ctx, int(ticket), C.byref(p8), C.byref(pz)))
+        rgba8, zwin = self._present_views(p8, pz, getattr(self, "_present_sizes", {}).pop(int(ticket), self.size))
+        if copy:
+            rgba8, zwin = rgba8.copy(), (zwin.copy() if zwin is not None else None)
+        return rgba8, zwin
 
     def composite_over_device(self, d_layers, nlayers, order, npix, d_out, stream=None):
         self._ck(self.L.smk_composite_over_device(self.ctx, d_layers, nlayers,

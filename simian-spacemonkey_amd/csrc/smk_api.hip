@@ -168,6 +168,7 @@ extern "C" void smk_destroy(smk_ctx *c) {
   if (c->tf_stream) { (void)hipStreamSynchronize(c->tf_stream); (void)hipStreamDestroy(c->tf_stream); }
   free_brick_set(c->br3);
   smk_cols_free(&c->cols);
+  smk_present_free(c);  // (the slots' device and pinned buffers, the copy stream)
   void *ptrs[] = {c->d_light_hist, c->d_shadow_entries, c->d_shadow_exports, c->d_shadow_barrier, c->d_tf_raw, c->d_tlut, c->d_tf_h, c->d_tf3d, c->d_tf3d_occ, c->d_noise, c->d_out, c->d_depth, c->d_zscene, c->d_light[0], c->d_light[1]};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
@@ -559,6 +560,8 @@ extern "C" int smk_set_camera(smk_ctx *c, const double mv[16], const float fr[4]
   if (w <= 0 || h <= 0) FAIL(c, "smk_set_camera: bad window %dx%d", w, h);
   if (!(clip[0] > 0)) FAIL(c, "smk_set_camera: near plane must be > 0");
   if (!(fr[1] > fr[0]) || !(fr[3] > fr[2])) FAIL(c, "smk_set_camera: degenerate frustum");
+  if ((w != c->W || h != c->H) && smk_present_outstanding(c))  // (a frame in flight owns buffers of the window it was begun with)
+    FAIL(c, "smk_set_camera: the window cannot change from %dx%d to %dx%d while a frame of smk_render_present_begin is outstanding", c->W, c->H, w, h);
   memcpy(c->mv, mv, sizeof c->mv);
   memcpy(c->frustum, fr, sizeof c->frustum);
   memcpy(c->clip, clip, sizeof c->clip);
@@ -1148,6 +1151,10 @@ extern "C" int smk_get_stat(smk_ctx *c, const char *name, double *value) {
   if (!strcmp(name, "slab_workgroups")) { *value = c->slab.nblocks_last; return 0; }
   if (!strcmp(name, "slab_retries")) { *value = (double)c->slab_retries; return 0; }
   if (!strcmp(name, "clip_slice_pass")) { *value = c->clip_slice_pass; return 0; }  // (smk_clip_slice.hip)
+  // the hand-over to the host (smk_present.hip): the present kernel's HIP-event time of the last frame handed over (after
+  // smk_present_device: waits for it), and the bytes that frame's copy to the host moved
+  if (!strcmp(name, "present_ms")) return smk_present_ms(c, value);
+  if (!strcmp(name, "present_bytes")) { *value = c->present_bytes; return 0; }
   FAIL(c, "smk_get_stat: unknown name '%s'", name);
 }
 

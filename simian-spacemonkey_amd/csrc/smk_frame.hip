@@ -341,6 +341,12 @@ extern "C" int smk_render_occluded_device(smk_ctx *c, const void *d_scene_depth,
   return render_frame(c, "smk_render_occluded_device", d_rgba, d_depth, (const float *)d_scene_depth, kind, stream);
 }
 
+int smk_frame_enqueue(smk_ctx *c, const char *who, void *d_rgba, void *d_depth, const float *d_zscene, int zkind, void *stream) {
+  return render_frame(c, who, d_rgba, d_depth, d_zscene, zkind, stream);
+}
+
+int smk_frame_check_status(smk_ctx *c, long long id) { return check_frame_status(c, id); }
+
 // the context's own W x H frame and depth buffers (smk_render, smk_render_slice)
 int smk_frame_buffers(smk_ctx *c) {
   const size_t npix = (size_t)c->W * c->H;

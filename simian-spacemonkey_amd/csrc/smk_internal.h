@@ -251,6 +251,26 @@ struct TimeStep {
   bool used_valid = false;
 };
 
+// One frame on its way to the host (smk_present.hip; DESIGN.md "Present"): everything a frame in flight needs that the
+// context would otherwise share -- its RGBA8 and window-depth device buffers, their pinned host copies, its staged copy of
+// the host's scene depth, its events.  Two of them, used in turn by the tickets of smk_render_present_begin.
+struct PresentSlot {
+  unsigned char *d_rgba8 = nullptr, *h_rgba8 = nullptr;  // [npix][4] bytes: device; pinned
+  float *d_zwin = nullptr, *h_zwin = nullptr;            // [npix] window depths: device; pinned
+  size_t cap = 0;                                        // pixels those four hold
+  float *d_zscene = nullptr;                             // the host's scene depth, copied at `begin`
+  size_t zscene_cap = 0;
+  hipEvent_t pev0 = nullptr, pev1 = nullptr;             // around the present kernel (smk_get_stat "present_ms")
+  hipEvent_t presented = nullptr, copied = nullptr;      // render stream: buffers written; copy stream: they are in host memory
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;               // the frame's pair of the timing ring (not owned)
+  long long ticket = 0, frame_id = 0;
+  bool outstanding = false;                              // begun and not ended
+  bool want_depth = false, has_bg = false, has_scene = false;
+  float bg[3] = {0, 0, 0};
+  int zkind = 0;
+  size_t npix = 0;                                       // the window the frame was begun with
+};
+
 struct smk_ctx {
   int device = 0;
   std::string err;
@@ -385,6 +405,15 @@ struct smk_ctx {
   float *d_zscene = nullptr;
   size_t zscene_cap = 0;
 
+  // frames handed to the host as RGBA8 + window depth (smk_present.hip)
+  PresentSlot present[2];
+  long long present_ticket = 0;            // the last ticket handed out (ticket t lives in slot t & 1)
+  hipStream_t present_stream = nullptr;    // the device-to-host copies, beside the next frame's ray-march
+  hipEvent_t present_ev[2] = {nullptr, nullptr};  // around the kernel of the last smk_present_device
+  bool present_pending = false;            // ... recorded and not read yet
+  float present_ms = 0;                    // smk_get_stat "present_ms"
+  double present_bytes = 0;                // smk_get_stat "present_bytes"
+
   // options / stats
   int opt_kernel = 0, opt_tf_raw = 0;
   int opt_bricks = 1;      // brick flags on (0: every slice is streamed and sampled, as before round 2's last step)
@@ -486,6 +515,14 @@ void smk_bsp_order(const smk_ctx *c, const double pos[3], int *order);
 void smk_inverse_affine(double inv[16], const double m[16]);
 int smk_make_xmajor_copy(smk_ctx *c);
 int smk_frame_buffers(smk_ctx *c);  // (smk_frame.hip)
+// (smk_frame.hip) a frame enqueued on `stream` -- what smk_render[_occluded]_device do, d_zscene a DEVICE buffer or null --, and the
+// status word of frame `id`, consumed: non-zero (with the reason in c->err) when a streaming kernel flagged the frame
+int smk_frame_enqueue(smk_ctx *c, const char *who, void *d_rgba, void *d_depth, const float *d_zscene, int zkind, void *stream);
+int smk_frame_check_status(smk_ctx *c, long long id);
+// (smk_present.hip) frames begun and not ended; smk_get_stat "present_ms"; everything the slots own (smk_destroy)
+bool smk_present_outstanding(const smk_ctx *c);
+int smk_present_ms(smk_ctx *c, double *value);
+void smk_present_free(smk_ctx *c);
 void smk_slab_free(SlabAux *aux);  // (smk_slab_plan.hip)
 // a ray's coefficients on the host, for planning, at a real-valued position (px, py) of the image plane (smk_slab_plan.hip)
 void host_ray_at(const RenderParams &P, double px, double py, double A[3], double B[3]);

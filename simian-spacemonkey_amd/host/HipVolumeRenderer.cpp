@@ -15,7 +15,8 @@ static void build_world_modelview(double mv[16]);
 static void mul(double o[16], const double a[16], const double b[16]);
 static void translate(double m[16], double x, double y, double z);
 
-HipVolumeRenderer::HipVolumeRenderer(MetaVolume *vm, int, int device) : ctx(nullptr), m_vol(vm), tlut(nullptr), failed(0), m_bb(0), m_bbb(0) {
+HipVolumeRenderer::HipVolumeRenderer(MetaVolume *vm, int, int device)
+    : ctx(nullptr), m_vol(vm), tlut(nullptr), pmode(HipPresentFloat), pdepth(0), pticket(0), pW(0), pH(0), fb8(nullptr), zb(nullptr), failed(0), m_bb(0), m_bbb(0) {
   int err = 0;
   ctx = smk_create(device, &err);
   if (!ctx) {
@@ -108,9 +109,83 @@ void HipVolumeRenderer::loadTransferTableRGBA() {
   }
 }
 
+// the frame in flight, waited for: its pinned buffers become framebuffer8() / depthbuffer()
+int HipVolumeRenderer::endTicket() {
+  if (!pticket) return 0;
+  const long long t = pticket;
+  pticket = 0;
+  const unsigned char *p8 = nullptr;
+  const float *pz = nullptr;
+  if (smk_render_present_end(ctx, t, &p8, &pz)) return 1;
+  fb8 = p8;
+  zb = pz;
+  return 0;
+}
+
+void HipVolumeRenderer::present(HipPresentMode mode, int want_depth) {
+  if (!ok()) return;
+  if (endTicket()) {  // (a frame enqueued under the old mode is not lost)
+    std::cerr << "ERROR: HipVolumeRenderer::present: " << smk_last_error(ctx) << std::endl;
+    failed = 1;
+  }
+  pmode = mode;
+  pdepth = want_depth;
+}
+
+void HipVolumeRenderer::flush() {
+  if (!ok()) return;
+  if (endTicket()) {
+    std::cerr << "ERROR: HipVolumeRenderer::flush: " << smk_last_error(ctx) << std::endl;
+    failed = 1;
+  }
+}
+
+// gluvv.env.bgColor as display() reads it (gluvv.cpp:606-623): 0 draws a white quad UNDER the finished frame
+// (GL_ONE_MINUS_DST_ALPHA, GL_ONE), anything else leaves the cleared black
+void HipVolumeRenderer::renderPresent() {
+  static const float white[3] = {1.0f, 1.0f, 1.0f};
+  const float *bg = gluvv.env.bgColor == 0 ? white : nullptr;
+  const size_t npix = (size_t)gluvv.win.width * (size_t)gluvv.win.height;
+  if (pmode == HipPresentSync) {
+    if (endTicket() || smk_render_present(ctx, bg, nullptr, 0, pdepth, &fb8, &zb)) failed = 1;
+    return;
+  }
+  // pipelined: this frame is enqueued BEFORE the one in flight is waited for, so that its ray-march runs beside that copy
+  const long long before = pticket;
+  long long t = 0;
+  if (smk_render_present_begin(ctx, bg, nullptr, 0, pdepth, &t)) {
+    failed = 1;
+    return;
+  }
+  pticket = before;
+  if (before) {
+    if (endTicket()) failed = 1;
+  } else {  // the first frame: nothing has arrived yet
+    blank8.assign(npix * 4, 0);
+    blankz.assign(npix, 1.0f);
+    fb8 = blank8.data();
+    zb = pdepth ? blankz.data() : nullptr;
+  }
+  pticket = t;
+}
+
 void HipVolumeRenderer::renderVolume(float sampleRate, double mv[16]) {
   if (!ok()) return;
   const int W = (int)gluvv.win.width, H = (int)gluvv.win.height;
+  if (pmode != HipPresentFloat) {
+    // (a frame in flight owns buffers of the window it was enqueued with: it is handed over before the window changes)
+    if (pticket && (pW != W || pH != H) && endTicket()) failed = 1;
+    pW = W;
+    pH = H;
+    int rc = failed || smk_set_camera(ctx, mv, gluvv.env.frustum, gluvv.env.clip, W, H);
+    rc = rc || smk_set_sampling(ctx, sampleRate, 0, gluvv.volren.gamma, gluvv.volren.scaleAlphas);
+    if (!rc) renderPresent();
+    if (rc || failed) {
+      std::cerr << "ERROR: HipVolumeRenderer::renderVolume: " << smk_last_error(ctx) << std::endl;
+      failed = 1;
+    }
+    return;
+  }
   fb.assign((size_t)W * H * 4, 0.0f);
   int rc = smk_set_camera(ctx, mv, gluvv.env.frustum, gluvv.env.clip, W, H);
   rc |= smk_set_sampling(ctx, sampleRate, 0, gluvv.volren.gamma, gluvv.volren.scaleAlphas);

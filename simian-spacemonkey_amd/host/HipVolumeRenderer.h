@@ -23,6 +23,14 @@
 
 enum { VolRenUnkown, VolRen2DTexture, VolRen3DTexture, VolRen3DExt };  // VolumeRenderer.h:64-69
 
+// What renderVolume / draw() leave for the host (HipVolumeRenderer::present).  The reference's frame is the 8-bit GL
+// framebuffer with its depth buffer; the two present modes deliver exactly that, in pinned memory (smk.h "display-ready frames").
+enum HipPresentMode {
+  HipPresentFloat = 0,      // framebuffer(): premultiplied float RGBA, one call one frame (the default)
+  HipPresentPipelined = 1,  // framebuffer8() [+ depthbuffer()]: a call enqueues its frame and hands over the one before it
+  HipPresentSync = 2        // framebuffer8() [+ depthbuffer()]: one call one frame
+};
+
 // The renderer's colour map.  TLUT::scaleAlpha (TLUT.cpp:138-154) ends in loadTransferTableRGBA(), a
 // GL colour-table upload, and returns nothing; this subclass reaches TLUT's protected members to do
 // the same opacity correction on the same fields without the GL call and says whether the table
@@ -57,6 +65,22 @@ class HipVolumeRenderer {
   int bboxBrackets() const { return m_bbb; }
   // the frame of the last renderVolume: [height][width][4] premultiplied float RGBA
   const float *framebuffer() const { return fb.data(); }
+  // Display-ready frames.  In a present mode renderVolume fills framebuffer8() -- [height][width] RGBA8, row 0 at the bottom,
+  // for glDrawPixels(w, h, GL_RGBA, GL_UNSIGNED_BYTE, ..) -- and, with depth asked for, depthbuffer() -- [height][width] float
+  // window depths, 1 where the volume left nothing, for GL_DEPTH_COMPONENT / GL_FLOAT -- instead of framebuffer().  The
+  // background follows gluvv.env.bgColor as display() does (gluvv.cpp:606-623): 0 composes the frame over white (alpha 255
+  // everywhere), anything else leaves it premultiplied on transparent black.
+  //   HipPresentPipelined: a call enqueues its frame (ray-march, conversion, copy to pinned memory) and returns the frame
+  //     of the call BEFORE it, whose copy ran beside this one's ray-march: the display lags one frame, as a swap chain does.
+  //     After the first call the buffers hold a cleared frame (zero bytes, depth 1).  flush() hands over the frame in
+  //     flight without enqueuing another (a host that stops animating calls it, or switches to HipPresentSync).
+  //   HipPresentSync: the strict one-call-one-frame behaviour.
+  // The pointers stay valid until the next renderVolume / flush / present call.
+  void present(HipPresentMode mode, int want_depth = 0);
+  HipPresentMode presentMode() const { return pmode; }
+  const unsigned char *framebuffer8() const { return fb8; }
+  const float *depthbuffer() const { return zb; }
+  void flush();
   int ok() const { return ctx != nullptr && !failed; }
   smk_ctx *context() { return ctx; }
   void loadTransferTableRGBA();  // what TLUT::loadTransferTableRGBA did with the GL color table
@@ -69,6 +93,16 @@ class HipVolumeRenderer {
   MetaVolume *m_vol;
   HipTLUT *tlut;
   std::vector<float> fb;
+  void renderPresent();                   // renderVolume's frame in a present mode (camera and sampling already set)
+  int endTicket();                        // the frame in flight becomes framebuffer8() / depthbuffer()
+  HipPresentMode pmode;
+  int pdepth;
+  long long pticket;                      // the frame in flight (0: none)
+  int pW, pH;                             // ... and the window it was enqueued with
+  const unsigned char *fb8;
+  const float *zb;
+  std::vector<unsigned char> blank8;      // what framebuffer8() / depthbuffer() hold before the first frame arrives
+  std::vector<float> blankz;
   int failed;
   int m_bb;
   int m_bbb;
@@ -81,6 +115,13 @@ class HipVolumeRenderable final : public gluvvPrimitive {
   void init();  // virtual in gluvvPrimitive (gluvvPrimitive.h:29-30)
   void draw();
   const float *framebuffer() const { return volren ? volren->framebuffer() : nullptr; }
+  // display-ready frames (HipVolumeRenderer::present): call after init().  draw() then fills framebuffer8() and, with
+  // want_depth, depthbuffer(); in HipPresentPipelined mode draw() enqueues its frame and hands over the one before it, so
+  // after draw() framebuffer8() holds the newest FINISHED frame; HipPresentSync is one draw() one frame.
+  void present(HipPresentMode mode, int want_depth = 0) { if (volren) volren->present(mode, want_depth); }
+  const unsigned char *framebuffer8() const { return volren ? volren->framebuffer8() : nullptr; }
+  const float *depthbuffer() const { return volren ? volren->depthbuffer() : nullptr; }
+  void flush() { if (volren) volren->flush(); }
   int running() const { return go; }
   HipVolumeRenderer *renderer() { return volren; }  // the inner interface (VolumeRenderable keeps it private; a host that
                                                     // draws sub-boxes or slice quads needs it)
