@@ -185,7 +185,8 @@ int smk_set_clip_slice(smk_ctx *ctx, int on, const float corners[4][3], float al
 /* replaces the extents of VolumeRenderer::renderVolume(sampleRate, mv, xext, yext, zext) (VolumeRenderer.h:103-108,
  * VolumeRenderer.cpp:333-384, render3DVolumeEXTSV :428-505): only the axis-aligned sub-box lo..hi of the volume is drawn
  * (volume space, the units of fPos / fSize; clamped to the volume as :452-457 do; the reference's `x[1] -= origf[1]` slip,
- * :459, is not reproduced).  Planes stay the whole volume's.  on = 0: off. */
+ * :459, is not reproduced).  Planes stay the whole volume's.  on = 0: off.  A frame with shadows (smk_set_shadow) takes
+ * the sub-box in both passes, as it takes an orthogonal clip plane's box. */
 int smk_set_region(smk_ctx *ctx, int on, const float lo[3], const float hi[3]);
 /* replaces the clip widget's free mode: glClipPlane(GL_CLIP_PLANE5, {0,0,-1,0}) specified under the
  * modelview wmv * T(clip.pos) * clip.xform (NV20VolRen3D.cpp:346-357; R8kVolRen3D.cpp:780-794).
@@ -195,7 +196,9 @@ int smk_set_region(smk_ctx *ctx, int on, const float lo[3], const float hi[3]);
 int smk_set_clip_plane(smk_ctx *ctx, int on, const double plane_eye[4]);
 /* replaces R8kVolRen3D_cpy::createNoiseTex + gluvv.pert (R8kVolRen3D_cpy.cpp:2392-2480,
  * 1590-1595): n^3 RGBA8 noise (GL_REPEAT), weights/scales of the two live octaves. noise NULL
- * or all weights 0 turns perturbation off. */
+ * or all weights 0 turns perturbation off.  Only the data fetch is displaced: p' = (t + sum_q w_q (noise(t s_q) - .5)) N - .5
+ * for a sample at voxel coordinate p, t = (p + .5) / N; the sample exists, or not, by p itself (box, clip planes, scene
+ * depth), and its first-hit depth is p's.  With shadows: see smk_set_shadow (option "shadow_perturb"). */
 int smk_set_perturb(smk_ctx *ctx, const unsigned char *noise_rgba, int n, const float w[4],
                     const float s[4]);
 /* replaces R8kVolRen3D's shadow mode (gluvv.light.shadow; gluvv.cpp:287-300 buffer size and qualities):
@@ -207,8 +210,21 @@ int smk_set_perturb(smk_ctx *ctx, const unsigned char *noise_rgba, int n, const 
  * gluvv.light.gShadowQual or iShadowQual: the light buffer has ceil(quality * buffer_px)^2 texels.
  * Applies to 2-D / 3-D classification with no or R8k shading, with or without the clip-plane widget's planes
  * (smk_set_clip, smk_set_clip_plane: both passes leave out what lies beyond them, as the reference's clipped slice polygons
- * do); other configurations (1-D table, NV20 combiners, perturbation, a sub-box) make smk_render fail with
- * the reason.  A shard (smk_set_shard) renders shadows once it has this frame's light entries (smk_shadow_exports_device,
+ * do), and with a sub-box (smk_set_region): to both passes the sub-box is what an orthogonal clip plane's box is -- the
+ * eye box and the light box are intersected with it, its faces closed and 2^-10 voxels wide like a clip face, the slice set
+ * stays the whole volume's.
+ * Perturbation (smk_set_perturb) with shadows is what R8kVolRen3D_cpy draws -- volShadow binds the noise texture in both
+ * passes (R8kVolRen3D_cpy.cpp:1566-1601), so the perturbed data drives the light buffer as well as the eye slices -- and
+ * is OPT-IN: option "shadow_perturb" 1.  With the default 0 such a frame fails as it always has ("shadows cannot be combined
+ * with perturbation or a sub-box"): an existing test pins that refusal, and hosts may rely on it; flipping the default,
+ * together with that test, is a later one-line change.  With the option on: in both passes a sample exists, or not, by its
+ * own position on the half-angle slice (the widened box, both clip planes, tau > 0, the scene depth in the eye pass);
+ * nothing about membership, first-hit depth or the position the light buffer is looked up at depends on the noise; only
+ * the data fetch (and, in the eye pass, the normal) is displaced, by the gather kernel's chain (smk_set_perturb above).  The
+ * light-buffer recurrence is unchanged.  The eye pass of such a frame is the gather kernel's (auto mode lands there).
+ * Still refused, with the reason: the 1-D table and NV20 combiners; perturbation or a sub-box with shadows on a shard
+ * (smk_render and smk_shadow_exports_device) and under option shadow_fused; a forced slice-ring kernel ("kernel" 2) on a
+ * perturbed frame; the column-stream kernel ("kernel" 3).  A shard (smk_set_shard) renders shadows once it has this frame's light entries (smk_shadow_exports_device,
  * smk_shadow_entries_device below; without them smk_render fails) and a halo of smk_get_shadow_margin's halo_needed.  The blend order follows the light (under when
  * the slices run away from the eye, over otherwise), smk_set_blend is not consulted.  depth_out works as without shadows:
  * the view depth of the nearest sample the eye pass composites along the pixel's half-angle ray (the shadow term scales
@@ -512,6 +528,7 @@ int smk_get_brick_flags(smk_ctx *ctx, unsigned char *flags_out, int *nb_out, int
  *              bit-identical with 0 and 1); 0 = every sample is fetched and classified
  *   "shadow_march" [1] frames with shadows as two marches (light-buffer texels, then eye pixels on the ray-marchers);
  *              0 = a launch per slice
+ *   "shadow_perturb" [0] 1: a perturbed frame with shadows renders (smk_set_shadow); 0: it is refused, as before
  *   developer knobs: "tile" (slice-ring workgroup shape id), "slab_T" (band wait + 1), "slab_fly"
  *   (slices a loader keeps in flight), "slab_ns" (cap on the ring's slots), "lockstep" (bit 0 gather lockstep; bits 1..6 slice-ring
  *   diagnostics, see tools/kbench.py), "wave_w"/"blk_w" (gather tile shape), "inject_slab_status"

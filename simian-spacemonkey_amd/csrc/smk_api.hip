@@ -1006,6 +1006,7 @@ extern "C" int smk_set_option(smk_ctx *c, const char *key, int value) {
   else if (!strcmp(key, "slab_ns")) c->slab.opt_ns = value < 0 ? 0 : (value > 63 ? 63 : value);
   else if (!strcmp(key, "tile")) c->slab.opt_tile = value;
   else if (!strcmp(key, "shadow_march")) c->opt_shadow_march = value ? 1 : 0;  // (0: a launch per slice, the form of rounds 1-2)
+  else if (!strcmp(key, "shadow_perturb")) c->opt_shadow_perturb = value ? 1 : 0;  // (opt-in: perturbed fetches under shadows, smk.h smk_set_shadow)
   else if (!strcmp(key, "shadow_fused")) c->opt_lockstep = value ? (c->opt_lockstep | 256) : (c->opt_lockstep & ~256);  // (developer: all slices in one cooperative launch)
   else if (!strcmp(key, "slab_split")) c->slab.opt_split = value < 0 ? 0 : (value > 8 ? 8 : value);
   else if (!strcmp(key, "cols_shape")) c->cols.opt_shape = value & 0xff;
@@ -1191,7 +1192,8 @@ extern "C" int smk_count_samples(smk_ctx *c, double *in_volume) {
   if (smk_build_params(c, P, c->stream)) return 1;
   // a frame with shadows samples the half-angle slices in its eye box (smk_shadow_setup)
   smk_shadowcoef sc;
-  if (c->shadow_on && c->tf_mode != 0 && !P.pert_on && !c->region_on && smk_shadow_setup(c, P, sc, nullptr, nullptr)) return 1;
+  // (perturbation displaces the fetch, not the sample: it changes no count; a sub-box is in the boxes)
+  if (c->shadow_on && c->tf_mode != 0 && smk_shadow_setup(c, P, sc, nullptr, nullptr)) return 1;
   return count_on_device(c, [&](unsigned long long *d) { return smk_launch_count_inside(P, d, c->stream); }, in_volume);
 }
 

@@ -380,6 +380,7 @@ struct smk_ctx {
   size_t light_hist_cap = 0;                // texels
   const float4 *d_light_last = nullptr;     // the light buffer the last frame with shadows left (in d_light[] or the history)
   int opt_shadow_march = 1;                 // option "shadow_march": 1 = two marches (default), 0 = a launch per slice
+  int opt_shadow_perturb = 0;               // option "shadow_perturb": 1 = a perturbed frame with shadows renders (0: refused, smk.h)
   unsigned *d_shadow_barrier = nullptr;     // the fused shadow launch's grid-barrier counter
   int light_hist_n = 0;                     // buffers the last march kept (nslices + 1; 0: none)
   long long light_hist_stride = 0;          // texels between two of them

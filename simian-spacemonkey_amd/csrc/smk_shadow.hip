@@ -141,6 +141,45 @@ __device__ __forceinline__ bool shadow_brick_empty(const RenderParams &P, float 
   return !P.bricks[((size_t)(z0 >> SMK_BRICK_LOG2) * P.nbr[1] + (size_t)(y0 >> SMK_BRICK_LOG2)) * P.nbr[0] + (size_t)(x0 >> SMK_BRICK_LOG2)];
 }
 
+// ---- perturbed frames (the PERT instances; R8kVolRen3D_cpy's volShadow feeds the noise texture to both passes, so the
+// perturbed data drives the light buffer as well as the eye slices).  A sample exists, or not, by its OWN position -- box,
+// clip planes, tau, scene depth, and where the eye pass looks the light buffer up; only the data fetch is displaced.
+//
+// Every brick a displaced fetch can reach from the sample's own cell is flagged empty (the dilated set of smk_build_params,
+// the gather kernel's test): exactly transparent wherever the noise sends it, neither noise nor voxels are looked at
+__device__ __forceinline__ bool shadow_reach_empty(const RenderParams &P, float p0, float p1, float p2) {
+  if (P.bricks_dil == nullptr) return false;
+  int x0, x1, y0, y1, z0, z1;
+  float fx, fy, fz;
+  smk_lin_clamp(p0, P.N[0], x0, x1, fx);
+  smk_lin_clamp(p1, P.N[1], y0, y1, fy);
+  smk_lin_clamp(p2, P.N[2], z0, z1, fz);
+  return !P.bricks_dil[((size_t)(z0 >> SMK_BRICK_LOG2) * P.nbr[1] + (size_t)(y0 >> SMK_BRICK_LOG2)) * P.nbr[0] + (size_t)(x0 >> SMK_BRICK_LOG2)];
+}
+
+// The displaced fetch position, tc' = tc + sum w_q (noise(tc s_q) - .5) (R8kVolRen3D_cpy.cpp:1590-1595, 3462-3490): the gather
+// kernel's chain operation for operation (smk_gather.hip), so that the eye pass on that kernel, the eye pass of a launch
+// per slice and both light passes fetch at the same voxel coordinate.  Uncached lookups (smk_noise; smk_noise_cached returns
+// the same bits): a thread of the per-slice form has one sample, and a lane of the light march takes every 8th slice of its
+// texel, while the 64 samples of a wave's turn -- 8 neighbouring light rays x 8 consecutive slices -- fall into one or two
+// cells of either octave, a few cache lines per gather; a cell per lane would cost 9 registers across the whole batch.
+__device__ __forceinline__ void shadow_displace(const RenderParams &P, float &p0, float &p1, float &p2) {
+  const float t0 = (p0 + 0.5f) * P.invN[0], t1 = (p1 + 0.5f) * P.invN[1], t2 = (p2 + 0.5f) * P.invN[2];
+  float o0 = 0.f, o1 = 0.f, o2 = 0.f;
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    if (P.pw[q] == 0.0f) continue;
+    float nz[3];
+    smk_noise(P, t0 * P.ps[q], t1 * P.ps[q], t2 * P.ps[q], nz);
+    o0 = __fmaf_rn(P.pw[q], nz[0] - 0.5f, o0);
+    o1 = __fmaf_rn(P.pw[q], nz[1] - 0.5f, o1);
+    o2 = __fmaf_rn(P.pw[q], nz[2] - 0.5f, o2);
+  }
+  p0 = __fmaf_rn(t0 + o0, (float)P.N[0], -0.5f);
+  p1 = __fmaf_rn(t1 + o1, (float)P.N[1], -0.5f);
+  p2 = __fmaf_rn(t2 + o2, (float)P.N[2], -0.5f);
+}
+
 // one eye pixel of one slice: the sample on the pixel's ray in this slice, shaded under the light buffer as the previous
 // slices left it, blended into the frame
 // The fused kernel's slices meet at a barrier INSIDE one launch: what one workgroup writes of the frame and the light buffer
@@ -175,7 +214,7 @@ __device__ __forceinline__ void shadow_st1(float *p, float v) {
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <int DT, int TF, int SH, bool COH = false, bool OCC = false>
+template <int DT, int TF, int SH, bool COH = false, bool OCC = false, bool PERT = false>
 __device__ __forceinline__ void shadow_eye_pixel(const RenderParams &P, const ShadowSlice &Q, int i, int j) {
   const smk_shadowcoef &sc = Q.sc;
   if (i >= P.W || j >= P.H) return;
@@ -200,9 +239,14 @@ __device__ __forceinline__ void shadow_eye_pixel(const RenderParams &P, const Sh
   if (OCC && !(smk_plane_depth<true>(P, m, tauA, dtau) < smk_scene_depth(P, o))) return;
   float4 C = shadow_ld4<COH>(P.out + o);
   if (sc.front_to_back && C.w == 1.0f) return;  // exact: every later weight (1-A) is 0
-  if (shadow_brick_empty(P, p[0], p[1], p[2])) return;
+  float f[3] = {p[0], p[1], p[2]};  // (where the data is fetched: p itself, or displaced by the noise -- PERT)
+  if constexpr (PERT) {
+    if (shadow_reach_empty(P, p[0], p[1], p[2])) return;
+    shadow_displace(P, f[0], f[1], f[2]);
+  }
+  if (shadow_brick_empty(P, f[0], f[1], f[2])) return;
   float ch0, ch1, ch2, ch3, n0 = 0.f, n1 = 0.f, n2 = 0.f;
-  shadow_fetch<DT, TF, SH != 0>(P, p[0], p[1], p[2], ch0, ch1, ch2, ch3, n0, n1, n2);
+  shadow_fetch<DT, TF, SH != 0>(P, f[0], f[1], f[2], ch0, ch1, ch2, ch3, n0, n1, n2);
   float4 col;
   if (!shadow_maybe_visible<TF>(P, ch0, ch1)) return;
   if (!smk_classify<DT, TF>(P, ch0, ch1, ch2, ch3, col)) return;
@@ -237,7 +281,7 @@ __device__ __forceinline__ void shadow_eye_pixel(const RenderParams &P, const Sh
 }
 
 // one light-buffer texel of one slice: carried over, with the slice's sample on the texel's light ray laid over it
-template <int DT, int TF, bool COH = false>
+template <int DT, int TF, bool COH = false, bool PERT = false>
 __device__ __forceinline__ void shadow_light_texel(const RenderParams &P, const ShadowSlice &Q, int x, int y) {
   const smk_shadowcoef &sc = Q.sc;
   if (x >= sc.LB || y >= sc.LB) return;
@@ -255,6 +299,11 @@ __device__ __forceinline__ void shadow_light_texel(const RenderParams &P, const 
     in = in && p[q] >= P.sh.llo[q] && p[q] <= P.sh.lhi[q];
   }
   if (in && P.cplane_on) in = __fmaf_rn(p[0], P.cplane[0], __fmaf_rn(p[1], P.cplane[1], __fmaf_rn(p[2], P.cplane[2], P.cplane[3]))) >= 0.0f;
+  if constexpr (PERT) {
+    // (the dilated flags at the sample's own position, then the fetch displaced: the plain flags apply at the displaced cell)
+    if (in && !shadow_reach_empty(P, p[0], p[1], p[2])) shadow_displace(P, p[0], p[1], p[2]);
+    else in = false;
+  }
   if (in && !shadow_brick_empty(P, p[0], p[1], p[2])) {
     float ch0, ch1, ch2, ch3, n0, n1, n2;
     shadow_fetch<DT, TF, false>(P, p[0], p[1], p[2], ch0, ch1, ch2, ch3, n0, n1, n2);
@@ -272,16 +321,17 @@ __device__ __forceinline__ void shadow_light_texel(const RenderParams &P, const 
 }
 
 // (OCC: the frame has the host's opaque scene depth -- smk_render_occluded; its eye fragments are tested against it)
-template <int DT, int TF, int SH, bool OCC = false>
+// (PERT: the frame's fetches are displaced by the noise volume -- smk_set_perturb with option shadow_perturb)
+template <int DT, int TF, int SH, bool OCC = false, bool PERT = false>
 __global__ __launch_bounds__(256) void smk_k_shadow_slice(const RenderParams P, const ShadowSlice Q) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   // a workgroup = 16x16 pixels, each wave an 8x8 sub-tile (compact footprints in the volume)
   const int lx = (wave & 1) * 8 + (lane & 7), ly = (wave >> 1) * 8 + (lane >> 3);
   if ((int)blockIdx.x < Q.eye_blocks) {
-    shadow_eye_pixel<DT, TF, SH, false, OCC>(P, Q, ((int)blockIdx.x % Q.eye_bx) * 16 + lx, ((int)blockIdx.x / Q.eye_bx) * 16 + ly);
+    shadow_eye_pixel<DT, TF, SH, false, OCC, PERT>(P, Q, ((int)blockIdx.x % Q.eye_bx) * 16 + lx, ((int)blockIdx.x / Q.eye_bx) * 16 + ly);
   } else {
     const int b = (int)blockIdx.x - Q.eye_blocks;
-    shadow_light_texel<DT, TF>(P, Q, (b % Q.light_bx) * 16 + lx, (b / Q.light_bx) * 16 + ly);
+    shadow_light_texel<DT, TF, false, PERT>(P, Q, (b % Q.light_bx) * 16 + lx, (b / Q.light_bx) * 16 + ly);
   }
 }
 
@@ -402,7 +452,12 @@ __device__ __forceinline__ bool shadow_tile_of_block(int bid, int ntiles, int &t
 // SHARD (phase 2 of a frame with shadows on a shard, SmkShadowShard): the running value starts at E_j, the entries composed
 // in the light's BSP order, and a sample is laid over it only once the texel's ray has entered grown(j) and while it lies in
 // grown(j) + 0.25 voxels; the brick flags and voxels are the shard's stored box.
-template <int DT, int TF, bool SHARD = false>
+// PERT (perturbed frames, never on a shard): the first pass over a batch tests the DILATED flags at the samples' own
+// positions; a second one displaces the positions that survive (two octaves of noise gathers per live sample, shadow_displace)
+// and requests the plain flags of the displaced cells, which are then in flight together as the unperturbed batch's are; the
+// third is the unperturbed one, on the displaced positions.  Nothing of a light sample but its fetch needs the own position
+// after the membership tests, so the displaced one takes its registers.
+template <int DT, int TF, bool SHARD = false, bool PERT = false>
 __global__ __launch_bounds__(256) void smk_k_shadow_light_march(const RenderParams P, const ShadowSlice Q, float4 *hist, long long hstride,
                                                                 const SmkShadowShard S) {
   const smk_shadowcoef &sc = Q.sc;
@@ -460,6 +515,7 @@ __global__ __launch_bounds__(256) void smk_k_shadow_light_march(const RenderPara
   };
   auto flag_of = [&](bool in) -> unsigned char {
     if (!in) return 0;
+    if constexpr (PERT) return shadow_reach_empty(P, p[0], p[1], p[2]) ? 0 : 1;
     if (P.bricks == nullptr) return 1;
     int x0, x1, y0, y1, z0, z1;
     float fx, fy, fz;
@@ -502,6 +558,14 @@ __global__ __launch_bounds__(256) void smk_k_shadow_light_march(const RenderPara
       }
       pu[u][0] = p[0]; pu[u][1] = p[1]; pu[u][2] = p[2];
     }
+    if constexpr (PERT) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (fl[u]) {
+          shadow_displace(P, pu[u][0], pu[u][1], pu[u][2]);
+          fl[u] = shadow_brick_empty(P, pu[u][0], pu[u][1], pu[u][2]) ? 0 : 1;
+        }
+    }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int k = kb + 8 * u + sl;
@@ -536,12 +600,12 @@ __global__ __launch_bounds__(256) void smk_k_shadow_light_march(const RenderPara
     if (live && kb + sl <= sc.nslices) hist[(size_t)(kb + sl) * nl + o] = L;
 }
 
-template <int DT, int TF, bool SHARD = false>
+template <int DT, int TF, bool SHARD = false, bool PERT = false>
 static hipError_t run_march(const RenderParams &P, ShadowSlice Q, float4 *hist, long long hstride, const SmkShadowShard &S, hipStream_t s) {
   const smk_shadowcoef &sc = Q.sc;
   const int tiles = ((sc.LB + 7) / 8) * ((sc.LB + 3) / 4);
   const int lblocks = 8 * ((tiles + 7) / 8);
-  hipLaunchKernelGGL((smk_k_shadow_light_march<DT, TF, SHARD>), dim3(lblocks), dim3(256), 0, s, P, Q, hist, hstride, S);
+  hipLaunchKernelGGL((smk_k_shadow_light_march<DT, TF, SHARD, PERT>), dim3(lblocks), dim3(256), 0, s, P, Q, hist, hstride, S);
   return hipGetLastError();
 }
 
@@ -555,7 +619,7 @@ hipError_t smk_launch_shadow_march(const RenderParams &P, const smk_shadowcoef &
   SmkShadowShard S;
   memset(&S, 0, sizeof S);
 #define CASE(D, T) \
-  if (dtype == D && tf_mode == T) return run_march<D, T>(P, Q, hist, hstride, S, s);
+  if (dtype == D && tf_mode == T) return P.pert_on ? run_march<D, T, false, true>(P, Q, hist, hstride, S, s) : run_march<D, T>(P, Q, hist, hstride, S, s);
   CASE(0, 1) CASE(0, 2) CASE(1, 1) CASE(1, 2)
 #undef CASE
   return hipErrorNotSupported;
@@ -744,7 +808,7 @@ hipError_t smk_launch_shadow_count_light(const RenderParams &P, const smk_shadow
   return hipGetLastError();
 }
 
-template <int DT, int TF, int SH, bool OCC>
+template <int DT, int TF, int SH, bool OCC, bool PERT = false>
 static hipError_t run(const RenderParams &P, ShadowSlice Q, float4 *L0, float4 *L1, unsigned *barrier, hipStream_t s) {
   const smk_shadowcoef &sc = Q.sc;
   Q.eye_bx = (P.W + 15) / 16;
@@ -758,7 +822,7 @@ static hipError_t run(const RenderParams &P, ShadowSlice Q, float4 *L0, float4 *
   // walk a slice's 5120 blocks one after the other, each a chain of dependent gathers, where a launch has them all in
   // flight; many make the barrier -- every workgroup polling one word through the fabric -- cost more than the ~11 us launch
   // it replaces.  The hardware's dispatcher IS the cheaper barrier here: the fused form stays an option ("shadow_fused").
-  const bool want_fused = (P.lockstep & 256) != 0;
+  const bool want_fused = !PERT && (P.lockstep & 256) != 0;  // (no perturbed fused instances: smk_shadow_plan.hip refuses the frame)
   if (want_fused) {
     int dev = 0, coop = 0, per_cu = 0, cus = 0;
     (void)hipGetDevice(&dev);
@@ -785,7 +849,7 @@ static hipError_t run(const RenderParams &P, ShadowSlice Q, float4 *L0, float4 *
     Q.lnum = fmaf((float)k, sc.ldnum, sc.lnum0);
     Q.Lprev = (k & 1) ? L0 : L1;
     Q.Lnext = (k & 1) ? L1 : L0;
-    hipLaunchKernelGGL((smk_k_shadow_slice<DT, TF, SH, OCC>), dim3(blocks), dim3(256), 0, s, P, Q);
+    hipLaunchKernelGGL((smk_k_shadow_slice<DT, TF, SH, OCC, PERT>), dim3(blocks), dim3(256), 0, s, P, Q);
   }
   return hipGetLastError();
 }
@@ -798,7 +862,8 @@ hipError_t smk_launch_shadow(const RenderParams &P, const smk_shadowcoef &sc, in
   Q.sc = sc;
 #define CASE(D, T, S) \
   if (dtype == D && tf_mode == T && shade_kind == S) \
-    return P.zscene ? run<D, T, S, true>(P, Q, L0, L1, barrier, s) : run<D, T, S, false>(P, Q, L0, L1, barrier, s);
+    return P.pert_on ? (P.zscene ? run<D, T, S, true, true>(P, Q, L0, L1, barrier, s) : run<D, T, S, false, true>(P, Q, L0, L1, barrier, s)) \
+                     : (P.zscene ? run<D, T, S, true>(P, Q, L0, L1, barrier, s) : run<D, T, S, false>(P, Q, L0, L1, barrier, s));
   CASE(0, 1, 0) CASE(0, 1, 1) CASE(0, 2, 0) CASE(0, 2, 1)
   CASE(1, 1, 0) CASE(1, 1, 1) CASE(1, 2, 0) CASE(1, 2, 1)
 #undef CASE

@@ -289,6 +289,12 @@ int smk_shadow_setup(smk_ctx *c, RenderParams &P, smk_shadowcoef &sc, SmkShadowS
   // light buffer alone (tests/test_shadow_witness.py::test_face_coincident_last_slice).  Clip planes: both passes draw
   // the same clipped slice polygons in the reference (volShadow slices the box setupClips left; glClipPlane stays
   // enabled), so a light ray's sample must lie in the same box and on the kept side of the free plane.
+  // A sub-box (smk_set_region) is to both passes what an orthogonal clip plane's box is: smk_region_box has intersected it into
+  // the eye box (P.lo / P.hi) and, below, into the light box; its faces are outer ones, closed and widened like a clip face --
+  // the half-open upper face of an unshadowed sub-box frame is a shard's rule, and a sub-box never meets a shard here
+  // (shadow_refusals).  The slice set stays the whole volume's (compute_shadowcoef).
+  if (c->region_on && c->nranks == 1)
+    for (int a = 0; a < 3; ++a) P.top[a] = 1;
   float wlo[3], whi[3];
   int wtop[3];
   const int z0[3] = {0, 0, 0};
@@ -342,7 +348,13 @@ static int shadow_refusals(smk_ctx *c, const RenderParams &P) {
   if (c->nranks > 1 && (!c->opt_shadow_march || (c->opt_lockstep & 256)))
     FAIL(c, "smk_render: shadows need the whole volume on one GPU with option shadow_march 0 or shadow_fused (the light buffer couples every "
             "slice of every brick); a shard renders shadows with the two marches only");
-  if (P.pert_on || c->region_on) FAIL(c, "smk_render: shadows cannot be combined with perturbation or a sub-box");
+  // (perturbed fetches under shadows are opt-in, option shadow_perturb: smk.h smk_set_shadow says why)
+  if (P.pert_on && !c->opt_shadow_perturb) FAIL(c, "smk_render: shadows cannot be combined with perturbation or a sub-box");
+  if (c->nranks > 1 && (P.pert_on || c->region_on))
+    FAIL(c, "smk_render: shadows on shards cannot be combined with perturbation or a sub-box (the light exports and the grown boxes "
+            "of a shard know neither); render the whole volume on one GPU");
+  if ((c->opt_lockstep & 256) && (P.pert_on || c->region_on))
+    FAIL(c, "smk_render: option shadow_fused has no perturbed instances and no sub-box; use the two marches or shadow_march 0");
   if (c->opt_kernel == 3) FAIL(c, "smk_render: the column-stream kernel has no shadow mode");
   return 0;
 }
@@ -426,7 +438,8 @@ static int launch_per_slice(smk_ctx *c, const RenderParams &P, const smk_shadowc
 // as a launch per slice.  A shard's frame needs this frame's light entries and a halo as wide as its margin.
 int smk_shadow_frame(smk_ctx *c, RenderParams &P, void *d_rgba, void *d_depth, hipStream_t s, bool *marched) {
   const int sk = smk_shade_kind(c);
-  if (c->nranks > 1 && !c->shadow_entries_fresh && c->tf_mode != 0 && sk != 2)
+  // (a perturbed or sub-box frame on a shard is refused for what it is, entries or none: shadow_refusals)
+  if (c->nranks > 1 && !c->shadow_entries_fresh && c->tf_mode != 0 && sk != 2 && !((P.pert_on && c->opt_shadow_perturb) || c->region_on))
     FAIL(c, "smk_render: shadows need the whole volume on one GPU (the light buffer couples every slice of every brick) -- "
             "or, on a shard, this frame's light entries: smk_shadow_exports_device on every rank, then smk_shadow_entries_device "
             "(smk_shadow_exchange_local in one process)");

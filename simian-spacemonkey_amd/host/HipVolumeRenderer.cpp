@@ -23,6 +23,9 @@ HipVolumeRenderer::HipVolumeRenderer(MetaVolume *vm, int, int device)
     std::cerr << "ERROR: HipVolumeRenderer: " << smk_last_error(nullptr) << std::endl;
     failed = 1;
   }
+  // gluvv.pert.on and gluvv.light.shadow together are what the perturbing renderer this class mirrors draws
+  // (R8kVolRen3D_cpy::volShadow, :1566-1601): the C ABI's opt-in for that combination (smk.h, smk_set_shadow)
+  if (ctx) smk_set_option(ctx, "shadow_perturb", 1);
 }
 
 HipVolumeRenderer::~HipVolumeRenderer() {

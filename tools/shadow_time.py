@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Frame time of the cfg 3 frame with shadows: the two marches (default) against a launch per slice (developer tool, GPU
-box only).   python tools/shadow_time.py [volume] [light buffer px]"""
+box only).   python tools/shadow_time.py [volume] [light buffer px] [--perturb]
+--perturb: the same frame with the perturbed fetch on (option shadow_perturb; createNoiseTex's 32^3 texture, the two live
+octaves at weights (.2, .1), scales (.2, 2.1)): the eye pass is the gather kernel's -- the slice-ring kernel declines
+perturbed frames -- so the forced slice-ring line is left out."""
 import os
 import sys
 
@@ -11,8 +14,10 @@ import bench  # noqa: E402
 
 
 def main():
-    n = int(sys.argv[1]) if len(sys.argv) > 1 else 512
-    lb = int(sys.argv[2]) if len(sys.argv) > 2 else 1024
+    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    perturb = "--perturb" in sys.argv[1:]
+    n = int(args[0]) if len(args) > 0 else 512
+    lb = int(args[1]) if len(args) > 1 else 1024
     pkg = bench.load_package()
     r = pkg.Renderer(0)
     vghf, nrm = bench.make_volume(r, n)
@@ -21,11 +26,17 @@ def main():
     xform, _ = bench.configure(r, "cfg3", n, 1024, 512)
     r.set_shading("r8k", (3.0, 4.0, -3.0), bench.EYE, bench.AT, [float(v) for v in xform.T.reshape(-1)], bench.INTENS)
     r.set_shadow(1, lb, 0.5)
+    forms = [("two marches, eye pass on the slice-ring kernel", 1, 2), ("two marches, eye pass on the gather kernel", 1, 1),
+             ("a launch per slice", 0, 0), ("auto", 1, 0)]
+    if perturb:
+        r.set_option("shadow_perturb", 1)
+        r.set_perturb(bench.libc_noise_tex(32), (.2, .1, 0, 0), (.2, 2.1, 4.5, 8.7))
+        forms = forms[1:]
+        print("perturbed fetch: weights (.2, .1), scales (.2, 2.1)", flush=True)
     frame = torch.zeros((1024 * 1024, 4), dtype=torch.float32, device="cuda")
     st = torch.cuda.current_stream().cuda_stream
     keep = {}
-    for name, march, kernel in (("two marches, eye pass on the slice-ring kernel", 1, 2), ("two marches, eye pass on the gather kernel", 1, 1),
-                                ("a launch per slice", 0, 0), ("auto", 1, 0)):
+    for name, march, kernel in forms:
         r.set_option("shadow_march", march)
         r.set_option("kernel", kernel)
         for _ in range(40 if kernel != 1 else 3):
