@@ -917,12 +917,14 @@ static hipError_t dispatch_perm(const RenderParams &P, const ColParams &Q, int p
   return hipErrorInvalidValue;
 }
 
-// the modes with an instance: {voxel type, classification mode, shading}
+// the modes with an instance: {voxel type, classification mode, shading} -- every classification of 3-channel voxels under
+// every shading the other ray-marchers take (the 1-D table is unshaded, smk_launch_cols)
 hipError_t smk_cols_march(const RenderParams &P, const ColParams &Q, int dtype, int tf_mode, int shade_kind, int perm, int shape, size_t lds,
                           int njobs, hipStream_t s) {
 #define CASE(D, T, SHK) \
   if (dtype == D && tf_mode == T && shade_kind == SHK) return dispatch_perm<D, SHK, T>(P, Q, perm, shape, lds, njobs, s);
-  CASE(0, 1, 0) CASE(0, 1, 1) CASE(1, 1, 0) CASE(1, 1, 1) CASE(0, 2, 1) CASE(1, 2, 1) CASE(0, 0, 0)
+  CASE(0, 1, 0) CASE(0, 1, 1) CASE(0, 1, 2) CASE(1, 1, 0) CASE(1, 1, 1) CASE(1, 1, 2)
+  CASE(0, 2, 0) CASE(0, 2, 1) CASE(0, 2, 2) CASE(1, 2, 0) CASE(1, 2, 1) CASE(1, 2, 2) CASE(0, 0, 0)
 #undef CASE
   return hipErrorInvalidValue;
 }

@@ -19,6 +19,10 @@ struct ColPlan {
   int as, au, av;  // model axes of S (the principal axis), U and V
   int perm;        // layout: 0 S = z, 1 S = y, 2 S = x (ColsAux::lay)
   double dens;     // pixels per (u, v) cell of a slice, at the densest place
+  double side_u, side_v;  // pixels under a cell's side faces along U / along V there, weighted (cols_density)
+  double ds;       // slices a ray advances per plane, at least
+  int cells_u, cells_v;   // cells of the stored box across the view
+  double slab;     // slices the thickest slab between two slice positions spans (the volume's outermost cells: below)
   int shape;       // workgroup shape (kColShapes)
   int vb;          // bytes per voxel
   size_t fixed;    // LDS beside the ring
@@ -64,10 +68,12 @@ static const char *cols_axes(const RenderParams &P, ColParams &Q, ColPlan &L) {
   L.av = L.perm == 0 ? 1 : 2;
   const int dir = Bc[as] > 0 ? 1 : -1;
   double slope_u = 0, slope_v = 0;
+  L.ds = fabs(Bc[as]);
   for (int c = 0; c < 4; ++c) {
     double A[3], B[3];
     ray((c & 1) ? P.W : 0.0, (c & 2) ? P.H : 0.0, A, B);
     if (!(B[as] * dir > 0) || fabs(B[as]) < 1e-12) return "rays do not share a marching direction";
+    L.ds = std::min(L.ds, fabs(B[as]));
     slope_u = std::max(slope_u, fabs(B[L.au] / B[as]));
     slope_v = std::max(slope_v, fabs(B[L.av] / B[as]));
   }
@@ -122,6 +128,16 @@ static const char *cols_projection(const RenderParams &P, ColParams &Q) {
 }
 
 // ---- cell density: pixels per (u, v) cell of a slice at the volume's corners and centre (L.dens).  Every ray that is
+// inside a column at one slice position wants a lane; with samples a slice or more apart (ds >= 1) those are, on average,
+// at most the rays through the column's face, cells x rays per cell.  With samples closer than a slice every ray that
+// crosses the slab between two slices has a sample in it, also the rays that enter or leave through the column's sides: a
+// ray whose path through the slab spans p of a slice is inside with probability min(1, p / ds), p uniform on (0, 1) over
+// the pixels under a side face, which adds (1 - ds) of those pixels, (t - ds) for a slab t slices thick -- L.side_u per cell
+// along U, L.side_v along V (found
+// by the feature fuzz: a two-slice volume seen obliquely from close by, tests/test_gpu_cols.py).
+// The volume's outermost cells also take the half voxel beyond the outermost voxel centres (base cell = min((int)clamp(p,
+// 0, N - 1), N - 2) of a p in [-.5, N - .5]): a column at a face is half a cell wider, one that spans the axis a whole
+// cell, and the first and last slab are 1.5 slices thick (2 where there is one slab only).
 // inside a column at one slice position wants a lane: cells x rays per cell (largest where the volume is nearest to the
 // eye) must stay below the consumer lanes.
 static const char *cols_density(const RenderParams &P, const ColParams &Q, ColPlan &L) {
@@ -134,7 +150,7 @@ static const char *cols_density(const RenderParams &P, const ColParams &Q, ColPl
     y = (Q.My[0] * X[0] + Q.My[1] * X[1] + Q.My[2] * X[2] + Q.My[3]) / w;
     return true;
   };
-  double dens = 0;
+  double dens = 0, side_u = 0, side_v = 0;
   for (int c = 0; c < 9; ++c) {
     const double u = c == 8 ? 0.5 * P.N[L.au] : ((c & 1) ? P.N[L.au] - 0.5 : -0.5), v = c == 8 ? 0.5 * P.N[L.av] : ((c & 2) ? P.N[L.av] - 0.5 : -0.5),
                  sc = c == 8 ? 0.5 * P.N[L.as] : ((c & 4) ? P.N[L.as] - 0.5 : -0.5);
@@ -143,9 +159,17 @@ static const char *cols_density(const RenderParams &P, const ColParams &Q, ColPl
     if (!project(u, v, sc, x0, y0) || !project(u + 1, v, sc, x1, y1) || !project(u, v + 1, sc, x2, y2) || !project(u, v, sc + 1, x3, y3))
       return "volume reaches behind the eye";
     dens = std::max(dens, fabs((x1 - x0) * (y2 - y0) - (x2 - x0) * (y1 - y0)));
+    side_u = std::max(side_u, fabs((x1 - x0) * (y3 - y0) - (x3 - x0) * (y1 - y0)));
+    side_v = std::max(side_v, fabs((x2 - x0) * (y3 - y0) - (x3 - x0) * (y2 - y0)));
   }
   if (!(dens > 1e-9)) return "degenerate projection";
   L.dens = dens;
+  L.cells_u = Q.Du - 1;
+  L.cells_v = Q.Dv - 1;
+  L.slab = Q.Ds - 1 <= 1 ? 2.0 : 1.5;
+  const double under = L.slab * std::max(0.0, 1.0 - L.ds / L.slab);
+  L.side_u = under * side_u;
+  L.side_v = under * side_v;
   return nullptr;
 }
 
@@ -170,8 +194,19 @@ static size_t cols_slice_bytes(int cw, int ch, int vb) { return (((size_t)(cw + 
 // does a column of cw x ch cells fit: its rays in `fill` of the lanes at the densest place (the set-up checks every job
 // exactly and reports, see the kernel), `slots` of its slice images in LDS, two slices in flight per loader within the
 // vmcnt range
+// rays inside a column of cw x ch cells at one slice position, at the densest place (cols_density): through its face, the
+// column away from the volume's faces; and everything counted -- the outermost cells' half voxels, the side faces
+static double cols_rays(const ColPlan &L, int cw, int ch) { return (double)cw * ch * L.dens; }
+static double cols_rays_at_faces(const ColPlan &L, int cw, int ch) {
+  const double w = cw + (cw >= L.cells_u ? 1.0 : 0.5), h = ch + (ch >= L.cells_v ? 1.0 : 0.5);
+  return w * h * L.dens + w * L.side_u + h * L.side_v;
+}
+
 static bool cols_fits(const ColPlan &L, double fill, int cw, int ch, int slots) {
-  if ((double)cw * ch * L.dens > fill * (kColShapes[L.shape].nw * 64)) return false;
+  const int lanes = kColShapes[L.shape].nw * 64;
+  // (`fill` of the lanes leaves room for what the first count leaves out where columns are many cells wide and samples a
+  //  slice or more apart; the second count must fit the lanes where they are not)
+  if (cols_rays(L, cw, ch) > fill * lanes || cols_rays_at_faces(L, cw, ch) > lanes) return false;
   const size_t sb = cols_slice_bytes(cw, ch, L.vb);
   if (sb * slots + L.fixed > COL_LDS_CAP) return false;
   if ((sb + 1023) / 1024 * 2 > 63) return false;
@@ -215,7 +250,7 @@ static hipError_t cols_layout(const RenderParams &P, ColParams &Q, const ColPlan
   bool reuse = LY.d && LY.Du == Q.Du && LY.Dv == Q.Dv && LY.Ds == Q.Ds && LY.src == vox_native && LY.vb == L.vb;
   if (reuse) {
     // an existing layout is kept while its columns fit the lanes and are not wastefully small for the view
-    reuse = cols_fits(L, fill, LY.CW, LY.CH, 3) && ((double)LY.CW * LY.CH * L.dens > 0.45 * lanes || (LY.CW >= cells_u && LY.CH >= cells_v));
+    reuse = cols_fits(L, fill, LY.CW, LY.CH, 3) && (cols_rays(L, LY.CW, LY.CH) > 0.45 * lanes || (LY.CW >= cells_u && LY.CH >= cells_v));
   }
   if (!reuse) {
     int bw, bh;

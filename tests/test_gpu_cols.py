@@ -51,7 +51,11 @@ def test_every_axis_and_direction(R, pose, f32):
 
 
 @pytest.mark.parametrize("kind,shade,f32", [("cfg2", 0, True), ("cfg3", 1, True), ("cfg4", 0, True), ("cfg2", 1, False),
-                                             ("tf3d", 1, True), ("tf3d_panes", 1, True), ("tf3d_panes", 1, False), ("cfg1", 0, False)])
+                                             ("tf3d", 1, True), ("tf3d_panes", 1, True), ("tf3d_panes", 1, False), ("cfg1", 0, False),
+                                             # found by the feature fuzz (test_gpu_fuzz_features.py), pinned here: NV20 shading
+                                             # and the unshaded 3-D table had no instance of the kernel
+                                             ("cfg3", 2, True), ("cfg2", 2, False), ("cfg4", 2, False), ("tf3d", 2, True),
+                                             ("tf3d_panes", 2, False), ("tf3d", 0, True), ("tf3d_panes", 0, False)])
 def test_modes(R, kind, shade, f32):
     sc = make_scene(kind, n=32, size=64, steps=64, pose="diag", f32=f32, shade=shade)
     ref = sc.render()
@@ -66,6 +70,25 @@ def test_ragged_volume_and_window(R, pose):
     sc.width, sc.height, sc.steps = 93, 41, 70
     ref = sc.render()
     a, b = _both(R, sc)
+    assert np.abs(a - b).max() <= TOL_G and np.abs(b - ref).max() <= TOL
+
+
+@pytest.mark.parametrize("dims", [(10, 29, 2), (10, 29, 3), (2, 29, 10)])
+def test_two_slice_volume_seen_obliquely_from_close_by(R, dims):
+    """Found by the feature fuzz (test_gpu_fuzz_features.py, seed 18 case 0), pinned here: 80 planes through a volume two
+    slices thick put every ray that crosses the slab between the slices into a column's job at once, also the rays that
+    enter through the column's sides -- under this oblique close-up more than the planner's pixels-per-cell count, and the
+    kernel reported a job whose rays did not fit its lanes (status 3).  The planner counts the side faces' pixels now."""
+    from _scenes import O
+    sc = make_scene("tf3d", dims=dims, f32=True, shade=1)
+    sc.xform = O.rotation((-0.6148467751798342, 0.7092843184925239, 0.3447886269291041), 139.8967002634996)
+    sc.eye = (0.07511258429341305, 0.08257451274783939, -1.7136438023786806)
+    sc.frustum = (-0.3378498333049329, 0.3378498333049329, -0.3378498333049329, 0.3378498333049329)
+    sc.width, sc.height, sc.steps = 114, 142, 80
+    ref = sc.render()
+    assert ref[..., 3].max() > 0.05
+    a, b = _both(R, sc)
+    assert R.stat("slab_status") == 0
     assert np.abs(a - b).max() <= TOL_G and np.abs(b - ref).max() <= TOL
 
 

@@ -156,9 +156,10 @@ def test_interactive_session_in_auto_mode(gpu_renderer_factory):
 
 
 def test_random_frames_gather_only_modes(gpu_renderer_factory):
-    """The modes only the gather kernel takes -- 1-D TLUT on scalar data, dense 3-D transfer
-    function, noise-perturbed fetches, first-hit depth, bricked uploads -- on random volumes and
-    poses, against the CPU checker."""
+    """Auto-mode frames of modes that were once the gather kernel's alone -- 1-D TLUT on scalar data, dense 3-D transfer
+    function, first-hit depth, bricked uploads, all of which both ray-marchers now take, and noise-perturbed fetches, which
+    only the gather kernel does -- on random volumes and poses, against the CPU checker.  Which kernel renders a frame is
+    the library's choice here; tests/test_gpu_fuzz_features.py forces each kernel on such frames and compares them."""
     rng = np.random.default_rng(SEED + 2)
     R = gpu_renderer_factory()
     try:

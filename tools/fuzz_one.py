@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Developer tool (GPU box): re-run chosen cases of the random-frame fuzz with the slice-ring plan printed.
-    SMK_DEBUG=1 python tools/fuzz_one.py SEED CASE [CASE ...]"""
+    SMK_DEBUG=1 python tools/fuzz_one.py SEED CASE [CASE ...]
+    python tools/fuzz_one.py --features SEED CASE [CASE ...]     cases of the feature fuzz (tests/_fuzz_features.py) through
+                                                                  its three legs: the feature record, each leg's outcome and,
+                                                                  per kernel, the worst pixel against the CPU checker"""
 import os
 import sys
 
@@ -15,10 +18,47 @@ from _scenes import push_scene  # noqa: E402
 import bench  # noqa: E402
 
 
+def worst_pixel(name, img, ref):
+    d = np.abs(img - ref)
+    j, i = np.unravel_index(d.max(axis=2).argmax(), d.shape[:2])
+    print("   %s vs CPU: max %g at pixel (%d,%d): gpu %s cpu %s" % (name, d.max(), i, j, img[j, i], ref[j, i]), flush=True)
+
+
+def features(pkg, seed, cases):
+    import test_gpu_fuzz_features as FF
+    R0 = pkg.Renderer(0)
+    try:
+        for case in cases:
+            sc, ft, ref, rd = FF.case_of(seed, case)
+            print("== " + FF.F.describe(ft), flush=True)
+            print("   " + ", ".join("%s %s" % (k, ft[k]) for k in ("vol_seed", "rot", "eye", "trans", "frustum", "pert_w", "h_slider")))
+            key = (seed, case)
+            with FF.context_for(R0, pkg.Renderer, ft) as R:
+                legs = (("gather", lambda: FF.leg_gather(R, key, sc, ft, ref, rd, pkg.SmkError, "  ")),
+                        ("slice-ring", lambda: FF.leg_slice_ring(R, key, sc, ft, ref, pkg.SmkError, "  ")),
+                        ("column-stream", lambda: FF.leg_column_stream(R, key, sc, ft, ref, pkg.SmkError, "  ", again=True)))
+                for name, leg in legs:
+                    try:
+                        print("   %s -> %s" % (name, leg()), flush=True)
+                    except AssertionError as e:
+                        print("   %s FAILED %s" % (name, str(e)[-300:]), flush=True)
+                FF.push(R, sc, ft, upload=False)
+                for k, name in ((1, "gather"), (2, "slice-ring"), (3, "column-stream")):
+                    img, why = FF.forced(R, k, pkg.SmkError)
+                    if why is None:
+                        worst_pixel(name, img, ref)
+                    else:
+                        print("   %s: not applicable: %s" % (name, why))
+    finally:
+        R0.close()
+
+
 def main():
+    pkg = bench.load_package()
+    if sys.argv[1] == "--features":
+        return features(pkg, int(sys.argv[2]), [int(a) for a in sys.argv[3:]])
     seed = int(sys.argv[1])
     want = set(int(a) for a in sys.argv[2:])
-    pkg = bench.load_package()
     R = pkg.Renderer(0)
     rng = np.random.default_rng(seed)
     for case in range(max(want) + 1):
@@ -42,9 +82,7 @@ def main():
             r.set_option("kernel", k)
             try:
                 img = r.render()
-                d = np.abs(img - ref)
-                j, i = np.unravel_index(d.max(axis=2).argmax(), d.shape[:2])
-                print("   kernel %d vs CPU: max %g at pixel (%d,%d): gpu %s cpu %s" % (k, d.max(), i, j, img[j, i], ref[j, i]), flush=True)
+                worst_pixel("kernel %d" % k, img, ref)
             except Exception as e:
                 print("   kernel %d: %s" % (k, str(e)[-200:]))
         r.set_option("kernel", 0)
