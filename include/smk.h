@@ -557,7 +557,21 @@ int smk_timing_read(smk_ctx *ctx, float *avg_ms, int *nframes);
  * frame's rule chose: 0 none, 1 before the volume, 2 after it; no synchronisation); "present_ms" (the HIP-event time of the
  * conversion kernel of the last frame smk_render_present[_end] returned, or of the last smk_present_device -- then it waits for
  * that kernel), "present_bytes" (the bytes the last frame smk_render_present[_end] returned copied to the host: 4 per pixel,
- * 8 with depth). */
+ * 8 with depth).
+ * "slab_plan_<field>": the launch plan of the latest slice-ring frame, as the host derived it from camera, volume size and
+ * voxel type (host memory, no synchronisation; every field reads 0 unless smk_last_frame_info reports kernel 2).  Fields:
+ *   tw th nw nl        the workgroup's pixel tile, its consumer and its loader waves
+ *   wu wv wp           the window: 16-byte units loaded per row, rows, LDS row pitch in units
+ *   per rpg            DMA wave-instructions and rows per row group: wp / gcd(64, wp), 64 / gcd(64, wp)
+ *   groups chunks      row groups per slice = ceil(wv / rpg); DMA wave-instructions per slice = groups * per
+ *   mych               the most DMA wave-instructions ONE loader issues per slice
+ *   nslots maxfly      the ring's slots; slices a loader keeps in flight
+ *   wstep pmask        slices a wave waits for beyond its band; consumers publish progress when (turn & pmask) == 0
+ *   mask_need use_occ use_ah fast_tf   per-slice extents; occupancy bitmap / third-axis alpha table in LDS; alpha-first path
+ *   bricks             1 when the brick flags are in use (empty layers), else 0
+ *   perm dir           principal axis (0: S = z, 1: S = y, 2: S = x on the x-major copy); marching direction +1 / -1
+ *   lds_bytes          the workgroup's LDS allocation
+ *   slices_max         slices the longest tile's loaders have to stream (its positions + 1), from the host's window scan */
 int smk_get_stat(smk_ctx *ctx, const char *name, double *value);
 /* workgroup timeline of the last slice-ring frame (developer tool):
  * records of 8 x uint32 {start, end (100 MHz ticks), HW_ID, XCC_ID | tile<<8 | slices<<20, loader 0's

@@ -1148,6 +1148,7 @@ extern "C" int smk_get_stat(smk_ctx *c, const char *name, double *value) {
     return 0;
   }
   if (!strncmp(name, "cols_", 5)) return smk_cols_stat(c, name, value);  // column-stream kernel (smk_cols_plan.hip)
+  if (!strncmp(name, "slab_plan_", 10)) return smk_slab_plan_stat(c, name, value);  // the latest slice-ring launch's plan (smk_slab_plan.hip)
   if (!strcmp(name, "slab_split_tiles")) { *value = c->slab.nsplit_last; return 0; }
   if (!strcmp(name, "slab_workgroups")) { *value = c->slab.nblocks_last; return 0; }
   if (!strcmp(name, "slab_retries")) { *value = (double)c->slab_retries; return 0; }

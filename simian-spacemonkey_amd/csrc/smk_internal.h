@@ -152,6 +152,7 @@ struct SlabAux {
     std::vector<unsigned char> key;
     double v[4] = {0, 0, 0, 0};
     std::vector<int> work;
+    int slices = 0;  // load indices (npos + 1) of the longest tile
   } scan[4];
   unsigned scan_next = 0;
   std::vector<unsigned char> shape_key;  // the small-workgroup shape chosen for this view class (see the launcher's probing pass)
@@ -186,6 +187,12 @@ struct SlabAux {
   bool recut = true, cuts_engaged = false, merge_warm = false;
   unsigned *d_trace = nullptr;  // [trace_n][8] workgroup timeline of the last traced frame (option lockstep bit 32)
   int trace_cap = 0, trace_n = 0;
+  // the plan of the latest slice-ring launch, host-side (smk_get_stat "slab_plan_*", smk_slab_plan.hip): SlabParams'
+  // window, pitch, ring and flag fields, the workgroup shape and its LDS bytes, the most DMA instructions one loader
+  // issues per slice, and the slices of the longest tile (scan_slices: of the latest window scan)
+  static constexpr int PLAN_FIELDS = 25;
+  int plan_last[PLAN_FIELDS] = {0};
+  int scan_slices = 0;
 };
 
 // the column-stream kernel's side buffers (smk_cols_plan.hip), owned by the context
@@ -528,6 +535,7 @@ void smk_slab_free(SlabAux *aux);  // (smk_slab_plan.hip)
 // a ray's coefficients on the host, for planning, at a real-valued position (px, py) of the image plane (smk_slab_plan.hip)
 void host_ray_at(const RenderParams &P, double px, double py, double A[3], double B[3]);
 int smk_cols_stat(smk_ctx *c, const char *name, double *value);  // smk_get_stat "cols_*" (smk_cols_plan.hip)
+int smk_slab_plan_stat(smk_ctx *c, const char *name, double *value);  // smk_get_stat "slab_plan_*" (smk_slab_plan.hip)
 // frames with shadows (smk_shadow_plan.hip): the half-angle slices and boxes of P (S, halo_need: a shard's); the light
 // samples a context owns (smk_get_stat); and a frame's shadow stage -- the light march (*marched), else the whole frame
 // as a launch per slice

@@ -346,6 +346,7 @@ static const char *slab_scan(const RenderParams &P, const SlabParams &Q, bool sp
     const SlabAux::Scan &scan = aux->scan[slot];
     for (int k = 0; k < 4; ++k) m[k] = scan.v[k];
     work = scan.work;
+    aux->scan_slices = scan.slices;
     if (slab_clock.on) slab_clock.frame_scan += slab_now() - t0;
     return nullptr;
   }
@@ -354,7 +355,7 @@ static const char *slab_scan(const RenderParams &P, const SlabParams &Q, bool sp
   // The rows of tiles are scanned by a few host threads (a pool the context keeps): ~0.13 us of double arithmetic per
   // tile is 0.27 ms for the 2048 tiles of a 1024^2 viewport on one thread -- as much as a shard's whole kernel when the
   // camera moves every frame.  Each thread keeps its own maxima and its own refusal; rows write disjoint tiles.
-  struct Part { double eu = 0, ev = 0, du = 0, dv = 0; const char *why = nullptr; };
+  struct Part { double eu = 0, ev = 0, du = 0, dv = 0; int slices = 0; const char *why = nullptr; };
   auto scan_rows = [&](int ty0, int ty1, Part &pt) {
     for (int tyi = ty0; tyi < ty1; ++tyi)
       for (int txi = 0; txi < P.ntx; ++txi) {
@@ -380,6 +381,11 @@ static const char *slab_scan(const RenderParams &P, const SlabParams &Q, bool sp
                                      (double)std::min(tyi * th + th, P.H), as, &smin_t, &smax_t))
           continue;  // the bundle misses the region: nothing to stream
         work[(size_t)tyi * P.ntx + txi] = 16 + (int)(smax_t - smin_t);
+        {  // the load indices of the tile (the kernel's npos + 1): base slices of the bundle's two ends, and the slice behind
+          const double top = (double)(P.N[as] - 1);
+          const int b0 = std::min((int)std::min(std::max(smin_t, 0.0), top), P.N[as] - 2), b1 = std::min((int)std::min(std::max(smax_t, 0.0), top), P.N[as] - 2);
+          pt.slices = std::max(pt.slices, b1 - b0 + 2);
+        }
         // cross-section of the bundle where THIS tile streams: it is linear in s (perspective), so
         // the two ends of the tile's own slice range bound it.  A sample at s reads slices floor(s)
         // and floor(s)+1, and the window of slice j covers s in [j-1, j+1] (stretched by half a
@@ -410,8 +416,10 @@ static const char *slab_scan(const RenderParams &P, const SlabParams &Q, bool sp
   }
   if (slab_clock.on) slab_clock.frame_scan += slab_now() - t0;
   m[0] = m[1] = m[2] = m[3] = 0;
+  aux->scan_slices = 0;
   for (const Part &pt : parts) {
     if (pt.why) return pt.why;
+    aux->scan_slices = std::max(aux->scan_slices, pt.slices);
     m[0] = std::max(m[0], pt.eu); m[1] = std::max(m[1], pt.ev);
     m[2] = std::max(m[2], pt.du); m[3] = std::max(m[3], pt.dv);
   }
@@ -420,6 +428,7 @@ static const char *slab_scan(const RenderParams &P, const SlabParams &Q, bool sp
     scan.key.assign(reinterpret_cast<const unsigned char *>(&key), reinterpret_cast<const unsigned char *>(&key) + sizeof key);
     for (int k = 0; k < 4; ++k) scan.v[k] = m[k];
     scan.work = work;
+    scan.slices = aux->scan_slices;
   }
   return nullptr;
 }
@@ -1075,6 +1084,28 @@ static hipError_t slab_run(const RenderParams &P, const SlabParams &Q, SlabAux *
   return hipSuccess;
 }
 
+// ---- the plan of the latest launch, for smk_get_stat "slab_plan_<field>" (include/smk.h): host memory only, no
+// synchronisation; 0 unless the latest frame ran the slice-ring kernel
+static const char *const SLAB_PLAN_NAMES[SlabAux::PLAN_FIELDS] = {
+    "tw", "th", "nw", "nl", "wu", "wv", "wp", "per", "rpg", "groups", "chunks", "mych", "nslots", "maxfly", "wstep", "pmask", "mask_need",
+    "use_occ", "use_ah", "fast_tf", "bricks", "perm", "dir", "lds_bytes", "slices_max"};
+static void slab_keep_plan(const SlabParams &Q, SlabShape sh, size_t lds, SlabAux *aux) {
+  const int nw = slab_waves(sh), nlg = slab_loader_groups(nw, sh.nl), lpg = sh.nl / nlg;
+  const int mych = (Q.groups + lpg - 1) / lpg * Q.per;  // (slab_ring's)
+  const int v[SlabAux::PLAN_FIELDS] = {sh.tw, sh.th, nw, sh.nl, Q.wu, Q.wv, Q.wp, Q.per, Q.rpg, Q.groups, Q.chunks, mych, Q.nslots, Q.maxfly,
+                                       Q.wstep, Q.pmask, Q.mask_need, Q.use_occ, Q.use_ah, Q.fast_tf, Q.bricks ? 1 : 0, Q.perm, Q.dir, (int)lds,
+                                       aux->scan_slices};
+  memcpy(aux->plan_last, v, sizeof v);
+}
+int smk_slab_plan_stat(smk_ctx *c, const char *name, double *value) {
+  for (int k = 0; k < SlabAux::PLAN_FIELDS; ++k)
+    if (!strcmp(name + 10, SLAB_PLAN_NAMES[k])) {
+      *value = c->last_kernel == 2 ? c->slab.plan_last[k] : 0;
+      return 0;
+    }
+  FAIL(c, "smk_get_stat: unknown name '%s'", name);
+}
+
 static hipError_t slab_plan_and_launch(RenderParams &P, int dtype, int tf_mode, int shade_kind, const void *vox_native, const void *vox_xmajor,
                                        SlabAux *aux, const char **why, hipStream_t s) {
   const double t0 = slab_clock.on ? slab_now() : 0;
@@ -1117,6 +1148,7 @@ static hipError_t slab_plan_and_launch(RenderParams &P, int dtype, int tf_mode, 
   if ((e = slab_upload_order(aux, order, s)) != hipSuccess) return e;
   Q.order = aux->d_order;
   if ((e = slab_trace(P, Q, aux, nblocks, s)) != hipSuccess) return e;
+  slab_keep_plan(Q, shape, lds, aux);
   return slab_run(P, Q, aux, dtype, tf_mode, shade_kind, shape, lds, nblocks, tsig, why, s);
 }
 
