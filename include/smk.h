@@ -133,7 +133,9 @@ int smk_set_camera(smk_ctx *ctx, const double modelview[16], const float frustum
                    const float clip[2], int width, int height);
 /* replaces R8kVolRen3D::loadCubeTex (R8kVolRen3D.cpp:2620-2679) / NV20VolRen3D::setupRegComb's
  * host half (NV20VolRen3D.cpp:637-668): gluvv.light.pos, gluvv.env.eye/at, gluvv.rinfo.xform,
- * gluvv.light.intens, gluvv.light.amb (amb is only consumed by the shadow passes; stored) */
+ * gluvv.light.intens, gluvv.light.amb.  amb ("shadow strenght", gluvv.cpp:293) is consumed by frames with shadows in the NV20
+ * look (smk_set_shadow, option "shadow_look" 1: the fraction of its colour a fully shadowed sample keeps; it must then be finite
+ * and in [0, 1], or the render fails with the reason); every other frame stores it, unchecked and unused. */
 int smk_set_shading(smk_ctx *ctx, smk_shade mode, const float light_pos[3], const float eye[3],
                     const float at[3], const float xform[16], float intens, float amb);
 /* gluvv.volren.sampleRate / gamma / scaleAlphas (NV20VolRen3D.cpp:87-122).  steps > 0 fixes the
@@ -222,7 +224,7 @@ int smk_set_perturb(smk_ctx *ctx, const unsigned char *noise_rgba, int n, const 
  * nothing about membership, first-hit depth or the position the light buffer is looked up at depends on the noise; only
  * the data fetch (and, in the eye pass, the normal) is displaced, by the gather kernel's chain (smk_set_perturb above).  The
  * light-buffer recurrence is unchanged.  The eye pass of such a frame is the gather kernel's (auto mode lands there).
- * Still refused, with the reason: the 1-D table and NV20 combiners; perturbation or a sub-box with shadows on a shard
+ * Still refused, with the reason: the 1-D table and NV20 combiners (those render under option "shadow_look" 1, below); perturbation or a sub-box with shadows on a shard
  * (smk_render and smk_shadow_exports_device) and under option shadow_fused; a forced slice-ring kernel ("kernel" 2) on a
  * perturbed frame; the column-stream kernel ("kernel" 3).  A shard (smk_set_shard) renders shadows once it has this frame's light entries (smk_shadow_exports_device,
  * smk_shadow_entries_device below; without them smk_render fails) and a halo of smk_get_shadow_margin's halo_needed.  The blend order follows the light (under when
@@ -234,7 +236,29 @@ int smk_set_perturb(smk_ctx *ctx, const unsigned char *noise_rgba, int n, const 
  * ordinary frame of the ray-marchers over the half-angle slices that looks each sample's slice up -- two launches instead
  * of one per slice.  Option "shadow_march" 0 (or a history that does not fit a quarter of the free device memory) renders
  * a launch per slice as the reference draws them: the same samples, bit-identical light buffers.  The light buffers belong
- * to the context: its frames with shadows must be enqueued on ONE stream (they order themselves there). */
+ * to the context: its frames with shadows must be enqueued on ONE stream (they order themselves there).
+ *
+ * Option "shadow_look" chooses between the two shadow models of the reference.  0, the default, is all of the above: the R8k
+ * look, coloured shadows (rgb *= 1 - light buffer rgb).  1 is the NV20 look: what the GeForce3 platform draws with shadows on,
+ * through its fourth renderer NV20VolRen3D2 (gluvv.cpp:141-199 starts the renderers, :151-159 that one).  Its light pass is
+ * the R8k one -- setupPBuff (NV20VolRen3D2.cpp:959-1091) blends the premultiplied slice (col a, a), a = a_VG a_H, into the
+ * pbuffer with GL_ONE, GL_ONE_MINUS_SRC_ALPHA, the recurrence of R8kVolRen3D.cpp:3150-3165; volShadow (:1466-1585) copies the
+ * pbuffer into the shadow texture before it draws slice k; axis and blend order (:174-200) are R8k's -- so light buffer and
+ * history are bit-identical to look 0's for the same scene.  Its eye pass attenuates by the light buffer's OPACITY with an
+ * ambient floor (setupRegComb, CONSTANT_COLOR1.a = 1 - gluvv.light.amb; unshaded :866-945, shaded :724-853): with La the
+ * bilinear lookup of the light buffer's alpha where look 0 looks its colour up (zero border),
+ *     f = 1 - sat(La) * (1 - amb),    amb of smk_set_shading, 1 - amb one fp32 subtraction,
+ * SMK_SHADE_NONE gives rgb = sat(c f a) where look 0 has sat(c (1 - L.rgb) a), and SMK_SHADE_NV20_DIFF / _DSPEC give the
+ * unshadowed NV20 sample's rgb times f (f = 1: that sample, bit for bit).  Alpha is a in either case: shadows are grey, a
+ * fully shadowed sample keeps the fraction amb of its colour, and depth_out is look 0's.  Everything else is the frame
+ * with shadows described above: clip planes, sub-box, first-hit depth, time steps, the clip-plane widget's slice, brick
+ * flags, shards (the light exchange is look 0's).  Where this departs from NV20VolRen3D2 as coded -- its shaded combiners
+ * lose the ambient floor and use another Phong -- DESIGN.md section 8 lists it.  Look 1 applies to 2-D / 3-D classification
+ * with no or NV20 shading.  Refused under look 1, with the reason: R8k shading; the 1-D table; perturbation (with or
+ * without "shadow_perturb"); option shadow_fused; the column-stream kernel; an amb that is not finite or outside [0, 1].
+ * Look 0 refuses NV20 shading as before.  A frame with the host's scene depth (smk_render_occluded) under look 1 is the
+ * gather kernel's: the slice-ring kernel has no such instance, auto mode lands on the gather kernel and a forced
+ * "kernel" 2 fails with that reason.  A value other than 0 or 1 fails. */
 int smk_set_shadow(smk_ctx *ctx, int on, int buffer_px, float quality);
 /* replaces the glBlendFunc / glBlendEquationEXT state of the slice loop (VolumeRenderer.cpp:589-590,
  * NV20VolRen3D.cpp:158-163, 930; R8kVolRen3D.cpp:1436-1449).  Default: front to back.  The two
@@ -529,6 +553,8 @@ int smk_get_brick_flags(smk_ctx *ctx, unsigned char *flags_out, int *nb_out, int
  *   "shadow_march" [1] frames with shadows as two marches (light-buffer texels, then eye pixels on the ray-marchers);
  *              0 = a launch per slice
  *   "shadow_perturb" [0] 1: a perturbed frame with shadows renders (smk_set_shadow); 0: it is refused, as before
+ *   "shadow_look" [0] the shadow model of frames with shadows (smk_set_shadow): 0 the R8k look (1 - light-buffer colour),
+ *              1 the NV20 look of NV20VolRen3D2 (light-buffer opacity, ambient floor amb of smk_set_shading)
  *   developer knobs: "tile" (slice-ring workgroup shape id), "slab_T" (band wait + 1), "slab_fly"
  *   (slices a loader keeps in flight), "slab_ns" (cap on the ring's slots), "lockstep" (bit 0 gather lockstep; bits 1..6 slice-ring
  *   diagnostics, see tools/kbench.py), "wave_w"/"blk_w" (gather tile shape), "inject_slab_status"

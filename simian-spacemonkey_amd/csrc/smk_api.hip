@@ -1007,6 +1007,10 @@ extern "C" int smk_set_option(smk_ctx *c, const char *key, int value) {
   else if (!strcmp(key, "tile")) c->slab.opt_tile = value;
   else if (!strcmp(key, "shadow_march")) c->opt_shadow_march = value ? 1 : 0;  // (0: a launch per slice, the form of rounds 1-2)
   else if (!strcmp(key, "shadow_perturb")) c->opt_shadow_perturb = value ? 1 : 0;  // (opt-in: perturbed fetches under shadows, smk.h smk_set_shadow)
+  else if (!strcmp(key, "shadow_look")) {  // 0: the R8k look; 1: the NV20 look of NV20VolRen3D2 (smk.h smk_set_shadow)
+    if (value != 0 && value != 1) FAIL(c, "smk_set_option: shadow_look must be 0 (the R8k look) or 1 (the NV20 look)");
+    c->opt_shadow_look = value;
+  }
   else if (!strcmp(key, "shadow_fused")) c->opt_lockstep = value ? (c->opt_lockstep | 256) : (c->opt_lockstep & ~256);  // (developer: all slices in one cooperative launch)
   else if (!strcmp(key, "slab_split")) c->slab.opt_split = value < 0 ? 0 : (value > 8 ? 8 : value);
   else if (!strcmp(key, "cols_shape")) c->cols.opt_shape = value & 0xff;

@@ -282,8 +282,13 @@ __device__ __forceinline__ SmkPhong smk_shade_geom(const RenderParams &P, float 
   }
   return o;
 }
-template <int SH>
-__device__ __forceinline__ float4 smk_shade_apply(const RenderParams &P, float4 col, float g, SmkPhong ph, const float *shadow = nullptr) {
+// NVL: the NV20 look of a frame with shadows (option shadow_look 1; NV20VolRen3D2::setupRegComb).  `keepf` is the fraction of
+// its colour the sample keeps, 1 - sat(light-buffer OPACITY) * (1 - amb) (smk_shadow_keep): the unshaded colour is scaled by
+// it where the R8k form scales by 1 - shadow (NV20VolRen3D2.cpp:866-945), the NV20 Phong result after its last combiner
+// (:724-853, with the ambient floor its unshaded combiners have: DESIGN.md 8); alpha never.  Compile-time, as SHD is.
+template <int SH, bool NVL = false>
+__device__ __forceinline__ float4 smk_shade_apply(const RenderParams &P, float4 col, float g, SmkPhong ph, const float *shadow = nullptr,
+                                                  float keepf = 1.0f) {
   float a = col.w;
   float c[3] = {col.x, col.y, col.z};
   if (SH == 1) {
@@ -302,22 +307,29 @@ __device__ __forceinline__ float4 smk_shade_apply(const RenderParams &P, float4 
       float cc = smk_sat(__fmaf_rn(c[k] * smk_sat(ph.kd), ia, c[k] * aa));
       r[k] = smk_sat(__fmaf_rn(spec, 1.0f - cc, cc));
     }
+    if (NVL) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) r[k] *= keepf;
+    }
     o.x = r[0];
     o.y = r[1];
     o.z = r[2];
     o.w = a;
     return o;
   }
-  if (shadow) {
+  if (NVL) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) c[k] *= keepf;
+  } else if (shadow) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) c[k] *= 1.0f - shadow[k];
   }
   return make_float4(smk_sat(c[0] * a), smk_sat(c[1] * a), smk_sat(c[2] * a), a);
 }
-template <int SH>
+template <int SH, bool NVL = false>
 __device__ __forceinline__ float4 smk_shade_sample(const RenderParams &P, float4 col, float n0, float n1, float n2, float g,
-                                                   const float *shadow = nullptr) {
-  return smk_shade_apply<SH>(P, col, g, smk_shade_geom<SH>(P, n0, n1, n2), shadow);
+                                                   const float *shadow = nullptr, float keepf = 1.0f) {
+  return smk_shade_apply<SH, NVL>(P, col, g, smk_shade_geom<SH>(P, n0, n1, n2), shadow, keepf);
 }
 
 __device__ __forceinline__ float smk_nrm(uint32_t a, uint32_t b, uint32_t c, uint32_t d, uint32_t e, uint32_t f,
@@ -409,33 +421,67 @@ __device__ __forceinline__ void smk_scene_bracket(float D, float tau0, float dta
   }
 }
 
-// bilinear lookup of a light buffer; texels outside it are 0 (the rest of the pbuffer stays cleared)
-__device__ __forceinline__ void smk_light_lookup(const float4 *L, int LB, float lx, float ly, float out[3]) {
+// The four texels of a bilinear light-buffer lookup at (lx, ly) and its weights; texels outside the buffer are 0 (the rest
+// of the pbuffer stays cleared).  False where no tap can lie inside (also NaN): the lookup is 0
+__device__ __forceinline__ bool smk_light_taps(const float4 *L, int LB, float lx, float ly, float4 t[4], float &fx, float &fy) {
   const float fx0 = floorf(lx - 0.5f), fy0 = floorf(ly - 0.5f);
-  const float fx = (lx - 0.5f) - fx0, fy = (ly - 0.5f) - fy0;
-  out[0] = out[1] = out[2] = 0.0f;
-  if (!(fx0 >= -1.0f && fx0 < (float)LB && fy0 >= -1.0f && fy0 < (float)LB)) return;  // (also NaN)
+  fx = (lx - 0.5f) - fx0;
+  fy = (ly - 0.5f) - fy0;
+  if (!(fx0 >= -1.0f && fx0 < (float)LB && fy0 >= -1.0f && fy0 < (float)LB)) return false;
   const int x0 = (int)fx0, y0 = (int)fy0;
-  float4 t[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int x = x0 + (q & 1), y = y0 + (q >> 1);
     t[q] = (x >= 0 && x < LB && y >= 0 && y < LB) ? L[(size_t)y * LB + x] : make_float4(0.f, 0.f, 0.f, 0.f);
   }
+  return true;
+}
+// bilinear lookup of a light buffer's colour (lerp order: x, then y)
+__device__ __forceinline__ void smk_light_lookup(const float4 *L, int LB, float lx, float ly, float out[3]) {
+  float4 t[4];
+  float fx, fy;
+  out[0] = out[1] = out[2] = 0.0f;
+  if (!smk_light_taps(L, LB, lx, ly, t, fx, fy)) return;
   out[0] = smk_lerp(smk_lerp(t[0].x, t[1].x, fx), smk_lerp(t[2].x, t[3].x, fx), fy);
   out[1] = smk_lerp(smk_lerp(t[0].y, t[1].y, fx), smk_lerp(t[2].y, t[3].y, fx), fy);
   out[2] = smk_lerp(smk_lerp(t[0].z, t[1].z, fx), smk_lerp(t[2].z, t[3].z, fx), fy);
 }
-// the light-buffer colour over the sample of plane m at voxel coordinate p (R8kVolRen3D.cpp:1664-1676: light-buffer
-// coordinates; the buffer is the one slices < k left, k the plane's slice in the light's order)
-__device__ __forceinline__ void smk_shadow_term(const RenderParams &P, int m, float p0, float p1, float p2, float out[3]) {
-  const SmkShadowRays &sh = P.sh;
+// ... of its opacity alone (the NV20 look, NV20VolRen3D2.cpp:866-945: the shadow texture's alpha): the same taps and order
+__device__ __forceinline__ float smk_light_lookup_a(const float4 *L, int LB, float lx, float ly) {
+  float4 t[4];
+  float fx, fy;
+  if (!smk_light_taps(L, LB, lx, ly, t, fx, fy)) return 0.0f;
+  return smk_lerp(smk_lerp(t[0].w, t[1].w, fx), smk_lerp(t[2].w, t[3].w, fx), fy);
+}
+// Where the sample at voxel coordinate p looks the light buffer up (R8kVolRen3D.cpp:1664-1676: light-buffer coordinates) ...
+__device__ __forceinline__ void smk_light_xy(const SmkShadowRays &sh, float p0, float p1, float p2, float &lx, float &ly) {
   const float lw = __fmaf_rn(p0, sh.Wm[0], __fmaf_rn(p1, sh.Wm[1], __fmaf_rn(p2, sh.Wm[2], sh.Wm[3])));
   const float lxx = __fmaf_rn(p0, sh.Xm[0], __fmaf_rn(p1, sh.Xm[1], __fmaf_rn(p2, sh.Xm[2], sh.Xm[3])));
   const float lyy = __fmaf_rn(p0, sh.Ym[0], __fmaf_rn(p1, sh.Ym[1], __fmaf_rn(p2, sh.Ym[2], sh.Ym[3])));
+  lx = __fmaf_rn(__fdiv_rn(lxx, lw), sh.lscale, sh.lbias);
+  ly = __fmaf_rn(__fdiv_rn(lyy, lw), sh.lscale, sh.lbias);
+}
+// ... and in which buffer, for the sample of plane m: the one slices < k left, k the plane's slice in the light's order
+__device__ __forceinline__ const float4 *smk_light_hist(const SmkShadowRays &sh, int m) {
   const int k = sh.k0 + sh.dk * m;
-  smk_light_lookup(sh.hist + (size_t)(k - 1) * (size_t)sh.hstride, sh.LB, __fmaf_rn(__fdiv_rn(lxx, lw), sh.lscale, sh.lbias),
-                   __fmaf_rn(__fdiv_rn(lyy, lw), sh.lscale, sh.lbias), out);
+  return sh.hist + (size_t)(k - 1) * (size_t)sh.hstride;
+}
+// the light-buffer colour over the sample of plane m at voxel coordinate p (the R8k look)
+__device__ __forceinline__ void smk_shadow_term(const RenderParams &P, int m, float p0, float p1, float p2, float out[3]) {
+  const float4 *L = smk_light_hist(P.sh, m);  // (before the coordinates: the other order cost three slice-ring instances an SGPR spill)
+  float lx, ly;
+  smk_light_xy(P.sh, p0, p1, p2, lx, ly);
+  smk_light_lookup(L, P.sh.LB, lx, ly, out);
+}
+// The NV20 look's weight: the fraction of its colour a sample keeps under the light-buffer opacity La, keep = 1 - amb
+// (SmkShadowRays; NV20VolRen3D2.cpp:866-945, CONSTANT_COLOR1.a) ...
+__device__ __forceinline__ float smk_keep_weight(float La, float keep) { return 1.0f - smk_sat(La) * keep; }
+// ... of the sample of plane m at voxel coordinate p, looked up where smk_shadow_term looks
+__device__ __forceinline__ float smk_shadow_keep(const RenderParams &P, int m, float p0, float p1, float p2) {
+  const float4 *L = smk_light_hist(P.sh, m);
+  float lx, ly;
+  smk_light_xy(P.sh, p0, p1, p2, lx, ly);
+  return smk_keep_weight(smk_light_lookup_a(L, P.sh.LB, lx, ly), P.sh.keep);
 }
 
 // XCD-aware tile mapping: blocks are dealt round-robin over the 8 XCDs (bid % 8 shares an

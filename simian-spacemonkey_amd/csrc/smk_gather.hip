@@ -13,7 +13,9 @@
 // SHD: the frame's planes are the half-angle slices of a frame with shadows (SmkShadowRays): the eye pass of smk_shadow.hip
 // OCC: the frame has the host's opaque scene depth (smk_render_occluded; compile-time: as a run-time test it cost the
 // instances of frames without one up to two VGPRs)
-template <int DT, int TF, int SH, bool SHD = false, bool OCC = false>
+// NVL: the NV20 look of a frame with shadows (option shadow_look 1): the sample keeps 1 - sat(light-buffer opacity) (1 - amb) of
+// its colour (smk_shadow_keep) where the R8k look multiplies by 1 - light-buffer colour.  Compile-time as well: SHD instances only
+template <int DT, int TF, int SH, bool SHD = false, bool OCC = false, bool NVL = false>
 __global__ __launch_bounds__(256) void smk_k_gather(const RenderParams P) {
   int tx, ty;
   if (!smk_tile_of_block(P, blockIdx.x, tx, ty)) return;
@@ -101,7 +103,7 @@ __global__ __launch_bounds__(256) void smk_k_gather(const RenderParams P) {
     if (SHD && !smk_tau_ok(tauA, dtau, m)) continue;  // (half-angle slices: a sample behind the eye does not exist)
     const float q0 = p0, q1 = p1, q2 = p2;  // (the sample's own position: where its light-buffer lookup is made)
 
-    if (P.pert_on) {
+    if (!NVL && P.pert_on) {  // (the NV20 look has no perturbed frames: smk_shadow_plan.hip refuses them)
       if (TF != 0 && P.bricks_dil != nullptr) {
         // every brick the displaced fetch can reach from here is flagged empty (smk_api.hip smk_build_params): the sample is
         // exactly transparent wherever the noise sends it -- neither the noise nor the voxels are looked at
@@ -203,19 +205,21 @@ __global__ __launch_bounds__(256) void smk_k_gather(const RenderParams P) {
     // frames with shadows: the light-buffer colour over the sample, as the slices nearer the light left it (smk_shadow.hip)
     float shadow[3];
     const float *shp = nullptr;
-    if (TF != 0 && SHD) {
+    if (TF != 0 && SHD && !NVL) {
       smk_shadow_term(P, m, q0, q1, q2, shadow);
       shp = shadow;
     }
     if (TF == 0) {
       src = col;
     } else if (SH == 0) {
-      src = smk_shade_sample<0>(P, col, 0.f, 0.f, 0.f, 0.f, shp);
+      if constexpr (NVL) src = smk_shade_sample<0, true>(P, col, 0.f, 0.f, 0.f, 0.f, nullptr, smk_shadow_keep(P, m, q0, q1, q2));
+      else src = smk_shade_sample<0>(P, col, 0.f, 0.f, 0.f, 0.f, shp);
     } else {
       float n0 = smk_nrm(k000.nb, k100.nb, k010.nb, k110.nb, k001.nb, k101.nb, k011.nb, k111.nb, 0, fx, fy, fz);
       float n1 = smk_nrm(k000.nb, k100.nb, k010.nb, k110.nb, k001.nb, k101.nb, k011.nb, k111.nb, 1, fx, fy, fz);
       float n2 = smk_nrm(k000.nb, k100.nb, k010.nb, k110.nb, k001.nb, k101.nb, k011.nb, k111.nb, 2, fx, fy, fz);
-      src = smk_shade_sample<SH>(P, col, n0, n1, n2, ch1, shp);
+      if constexpr (NVL) src = smk_shade_sample<SH, true>(P, col, n0, n1, n2, ch1, nullptr, smk_shadow_keep(P, m, q0, q1, q2));
+      else src = smk_shade_sample<SH>(P, col, n0, n1, n2, ch1, shp);
     }
     if (P.blend == SMK_BLEND_FRONT_TO_BACK) {
       // C += (1-A) src   (GL_ONE_MINUS_DST_ALPHA, GL_ONE)
@@ -281,15 +285,28 @@ hipError_t smk_launch_count_inside(const RenderParams &P, unsigned long long *d_
   return hipGetLastError();
 }
 
-template <int DT, int TF, int SH, bool SHD = false>
+template <int DT, int TF, int SH, bool SHD = false, bool NVL = false>
 static hipError_t launch(const RenderParams &P, hipStream_t s) {
   dim3 grid(8 * P.tiles_per_xcd), block(256);
+  if constexpr (NVL) {
+    if (P.zscene) hipLaunchKernelGGL((smk_k_gather<DT, TF, SH, true, true, true>), grid, block, 0, s, P);
+    else hipLaunchKernelGGL((smk_k_gather<DT, TF, SH, true, false, true>), grid, block, 0, s, P);
+    return hipGetLastError();
+  }
   if (P.zscene) hipLaunchKernelGGL((smk_k_gather<DT, TF, SH, SHD, true>), grid, block, 0, s, P);
   else hipLaunchKernelGGL((smk_k_gather<DT, TF, SH, SHD>), grid, block, 0, s, P);
   return hipGetLastError();
 }
 
 hipError_t smk_launch_gather(const RenderParams &P, int dtype, int tf_mode, int shade_kind, hipStream_t s) {
+  if (P.sh.on == 2) {  // ... in the NV20 look (option shadow_look 1): 2-D / 3-D table, NV20 shading or none
+#define CASE(D, T, S) \
+  if (dtype == D && tf_mode == T && shade_kind == S) return launch<D, T, S, true, true>(P, s);
+    CASE(0, 1, 0) CASE(0, 1, 2) CASE(0, 2, 0) CASE(0, 2, 2)
+    CASE(1, 1, 0) CASE(1, 1, 2) CASE(1, 2, 0) CASE(1, 2, 2)
+#undef CASE
+    return hipErrorInvalidValue;
+  }
   if (P.sh.on) {  // the eye pass of a frame with shadows: 2-D / 3-D table, R8k shading or none
 #define CASE(D, T, S) \
   if (dtype == D && tf_mode == T && shade_kind == S) return launch<D, T, S, true>(P, s);

@@ -45,15 +45,18 @@
 // finite (a sample behind the eye does not exist).  Plane m is slice k = k0 + dk m of the light's order (k = 1..nslices away
 // from the light); its sample is shaded under the light buffer as slices < k left it: hist[k - 1].
 struct SmkShadowRays {
-  int on;  // 0: the affine coefficients of smk_raycoef
+  int on;  // 0: the affine coefficients of smk_raycoef; 1: these, the R8k look; 2: these, the NV20 look (option shadow_look 1)
   float Ec[3], Dc[3], Dx[3], Dy[3], nDc, nDx, nDy;
   float numA, dB;
   float llo[3], lhi[3];  // the box a LIGHT ray's sample must lie in (closed): the volume, or what an orthogonal clip plane leaves of it
   int k0, dk, LB;
   float Xm[4], Ym[4], Wm[4], lscale, lbias;
+  float keep;  // the NV20 look: 1 - amb, one fp32 subtraction on the host -- a fully shadowed sample keeps the fraction amb of
+               // its colour (smk_shadow_keep, smk_device.h; where the pointer's alignment left four bytes: no field moves)
   const float4 *hist;  // [nslices + 1] buffers of [LB][LB] texels, `hstride` texels apart
   long long hstride;   // (LB * LB + a pad: buffers a power of two apart would meet in the same memory channels)
 };
+static_assert(sizeof(SmkShadowRays) == 184, "keep sits in the padding before hist: the kernarg layout of every kernel stays as it was");
 
 // A frame with shadows on one shard of a sort-last split (smk_shadow.hip; DESIGN.md 4b, "Shadows on shards").  A texel's
 // light ray ENTERS grown(j) -- rank j's region widened by its margin m_j -- at its first sample (slices k0..k1 of the whole
@@ -387,6 +390,7 @@ struct smk_ctx {
   size_t light_hist_cap = 0;                // texels
   const float4 *d_light_last = nullptr;     // the light buffer the last frame with shadows left (in d_light[] or the history)
   int opt_shadow_march = 1;                 // option "shadow_march": 1 = two marches (default), 0 = a launch per slice
+  int opt_shadow_look = 0;                  // option "shadow_look": 0 the R8k look, 1 the NV20 look of NV20VolRen3D2 (smk.h smk_set_shadow)
   int opt_shadow_perturb = 0;               // option "shadow_perturb": 1 = a perturbed frame with shadows renders (0: refused, smk.h)
   unsigned *d_shadow_barrier = nullptr;     // the fused shadow launch's grid-barrier counter
   int light_hist_n = 0;                     // buffers the last march kept (nslices + 1; 0: none)

@@ -214,7 +214,9 @@ __device__ __forceinline__ void shadow_st1(float *p, float v) {
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <int DT, int TF, int SH, bool COH = false, bool OCC = false, bool PERT = false>
+// (NVL: the NV20 look, option shadow_look 1 -- the fragment keeps 1 - sat(light-buffer opacity) (1 - amb) of its colour,
+//  smk_shadow_keep's arithmetic on this slice's buffer; never fused, never perturbed)
+template <int DT, int TF, int SH, bool COH = false, bool OCC = false, bool PERT = false, bool NVL = false>
 __device__ __forceinline__ void shadow_eye_pixel(const RenderParams &P, const ShadowSlice &Q, int i, int j) {
   const smk_shadowcoef &sc = Q.sc;
   if (i >= P.W || j >= P.H) return;
@@ -256,10 +258,17 @@ __device__ __forceinline__ void shadow_eye_pixel(const RenderParams &P, const Sh
   const float lw = __fmaf_rn(p[0], sc.Wm[0], __fmaf_rn(p[1], sc.Wm[1], __fmaf_rn(p[2], sc.Wm[2], sc.Wm[3])));
   const float lxx = __fmaf_rn(p[0], sc.Xm[0], __fmaf_rn(p[1], sc.Xm[1], __fmaf_rn(p[2], sc.Xm[2], sc.Xm[3])));
   const float lyy = __fmaf_rn(p[0], sc.Ym[0], __fmaf_rn(p[1], sc.Ym[1], __fmaf_rn(p[2], sc.Ym[2], sc.Ym[3])));
-  float shadow[3];
-  shadow_lookup<COH>(Q.Lprev, sc.LB, __fmaf_rn(__fdiv_rn(lxx, lw), sc.lscale, sc.lbias),
-                     __fmaf_rn(__fdiv_rn(lyy, lw), sc.lscale, sc.lbias), shadow);
-  const float4 src = smk_shade_sample<SH>(P, col, n0, n1, n2, ch1, shadow);
+  float shadow[3], keepf = 1.0f;
+  if constexpr (NVL) {
+    static_assert(!COH && !PERT, "the NV20 look has neither fused nor perturbed instances");
+    const float La = smk_light_lookup_a(Q.Lprev, sc.LB, __fmaf_rn(__fdiv_rn(lxx, lw), sc.lscale, sc.lbias),
+                                        __fmaf_rn(__fdiv_rn(lyy, lw), sc.lscale, sc.lbias));
+    keepf = smk_keep_weight(La, P.sh.keep);
+  } else {
+    shadow_lookup<COH>(Q.Lprev, sc.LB, __fmaf_rn(__fdiv_rn(lxx, lw), sc.lscale, sc.lbias),
+                       __fmaf_rn(__fdiv_rn(lyy, lw), sc.lscale, sc.lbias), shadow);
+  }
+  const float4 src = smk_shade_sample<SH, NVL>(P, col, n0, n1, n2, ch1, NVL ? nullptr : shadow, keepf);
   // first-hit depth (the marchers' smk_plane_depth): slices running away from the viewer composite under, so the first
   // sample composited -- the one that finds the alpha still exactly 0 -- is the nearest; slices running towards the viewer
   // composite over, so every one replaces the depth and the last is the nearest.  (Buffer cleared to +inf by the launcher.)
@@ -322,13 +331,13 @@ __device__ __forceinline__ void shadow_light_texel(const RenderParams &P, const 
 
 // (OCC: the frame has the host's opaque scene depth -- smk_render_occluded; its eye fragments are tested against it)
 // (PERT: the frame's fetches are displaced by the noise volume -- smk_set_perturb with option shadow_perturb)
-template <int DT, int TF, int SH, bool OCC = false, bool PERT = false>
+template <int DT, int TF, int SH, bool OCC = false, bool PERT = false, bool NVL = false>
 __global__ __launch_bounds__(256) void smk_k_shadow_slice(const RenderParams P, const ShadowSlice Q) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   // a workgroup = 16x16 pixels, each wave an 8x8 sub-tile (compact footprints in the volume)
   const int lx = (wave & 1) * 8 + (lane & 7), ly = (wave >> 1) * 8 + (lane >> 3);
   if ((int)blockIdx.x < Q.eye_blocks) {
-    shadow_eye_pixel<DT, TF, SH, false, OCC, PERT>(P, Q, ((int)blockIdx.x % Q.eye_bx) * 16 + lx, ((int)blockIdx.x / Q.eye_bx) * 16 + ly);
+    shadow_eye_pixel<DT, TF, SH, false, OCC, PERT, NVL>(P, Q, ((int)blockIdx.x % Q.eye_bx) * 16 + lx, ((int)blockIdx.x / Q.eye_bx) * 16 + ly);
   } else {
     const int b = (int)blockIdx.x - Q.eye_blocks;
     shadow_light_texel<DT, TF, false, PERT>(P, Q, (b % Q.light_bx) * 16 + lx, (b / Q.light_bx) * 16 + ly);
@@ -808,7 +817,7 @@ hipError_t smk_launch_shadow_count_light(const RenderParams &P, const smk_shadow
   return hipGetLastError();
 }
 
-template <int DT, int TF, int SH, bool OCC, bool PERT = false>
+template <int DT, int TF, int SH, bool OCC, bool PERT = false, bool NVL = false>
 static hipError_t run(const RenderParams &P, ShadowSlice Q, float4 *L0, float4 *L1, unsigned *barrier, hipStream_t s) {
   const smk_shadowcoef &sc = Q.sc;
   Q.eye_bx = (P.W + 15) / 16;
@@ -822,25 +831,27 @@ static hipError_t run(const RenderParams &P, ShadowSlice Q, float4 *L0, float4 *
   // walk a slice's 5120 blocks one after the other, each a chain of dependent gathers, where a launch has them all in
   // flight; many make the barrier -- every workgroup polling one word through the fabric -- cost more than the ~11 us launch
   // it replaces.  The hardware's dispatcher IS the cheaper barrier here: the fused form stays an option ("shadow_fused").
-  const bool want_fused = !PERT && (P.lockstep & 256) != 0;  // (no perturbed fused instances: smk_shadow_plan.hip refuses the frame)
-  if (want_fused) {
-    int dev = 0, coop = 0, per_cu = 0, cus = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (coop && cus > 0 && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, smk_k_shadow_fused<DT, TF, SH, OCC>, 256, 0) == hipSuccess && per_cu > 0) {
-      // (a barrier costs with the number of workgroups that meet at it: four per CU hide the gathers' latency, more only wait)
-      static const int wgs_per_cu = getenv("SMK_SHADOW_WGS") ? std::max(1, atoi(getenv("SMK_SHADOW_WGS"))) : 4;  // (developer knob)
-      const int grid = std::min(blocks, cus * std::min(per_cu, wgs_per_cu));
-      RenderParams Pa = P;
-      ShadowSlice Qa = Q;
-      unsigned *bar = barrier;  // (the context's word, zeroed on the stream before every frame)
-      if (bar && hipMemsetAsync(bar, 0, 16 * 9 * 4, s) != hipSuccess) bar = nullptr;
-      void *args[] = {(void *)&Pa, (void *)&Qa, (void *)&L0, (void *)&L1, (void *)&bar};
-      if (bar) {
-      const hipError_t e = hipLaunchCooperativeKernel((const void *)smk_k_shadow_fused<DT, TF, SH, OCC>, dim3(grid), dim3(256), args, 0, s);
-      if (e == hipSuccess) return hipGetLastError();
-      (void)hipGetLastError();  // refused (resources): the per-slice launches below
+  if constexpr (!NVL) {  // (nor NV20-look ones: refused there as well)
+    const bool want_fused = !PERT && (P.lockstep & 256) != 0;  // (no perturbed fused instances: smk_shadow_plan.hip refuses the frame)
+    if (want_fused) {
+      int dev = 0, coop = 0, per_cu = 0, cus = 0;
+      (void)hipGetDevice(&dev);
+      (void)hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, dev);
+      (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+      if (coop && cus > 0 && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, smk_k_shadow_fused<DT, TF, SH, OCC>, 256, 0) == hipSuccess && per_cu > 0) {
+        // (a barrier costs with the number of workgroups that meet at it: four per CU hide the gathers' latency, more only wait)
+        static const int wgs_per_cu = getenv("SMK_SHADOW_WGS") ? std::max(1, atoi(getenv("SMK_SHADOW_WGS"))) : 4;  // (developer knob)
+        const int grid = std::min(blocks, cus * std::min(per_cu, wgs_per_cu));
+        RenderParams Pa = P;
+        ShadowSlice Qa = Q;
+        unsigned *bar = barrier;  // (the context's word, zeroed on the stream before every frame)
+        if (bar && hipMemsetAsync(bar, 0, 16 * 9 * 4, s) != hipSuccess) bar = nullptr;
+        void *args[] = {(void *)&Pa, (void *)&Qa, (void *)&L0, (void *)&L1, (void *)&bar};
+        if (bar) {
+        const hipError_t e = hipLaunchCooperativeKernel((const void *)smk_k_shadow_fused<DT, TF, SH, OCC>, dim3(grid), dim3(256), args, 0, s);
+        if (e == hipSuccess) return hipGetLastError();
+        (void)hipGetLastError();  // refused (resources): the per-slice launches below
+        }
       }
     }
   }
@@ -849,7 +860,7 @@ static hipError_t run(const RenderParams &P, ShadowSlice Q, float4 *L0, float4 *
     Q.lnum = fmaf((float)k, sc.ldnum, sc.lnum0);
     Q.Lprev = (k & 1) ? L0 : L1;
     Q.Lnext = (k & 1) ? L1 : L0;
-    hipLaunchKernelGGL((smk_k_shadow_slice<DT, TF, SH, OCC, PERT>), dim3(blocks), dim3(256), 0, s, P, Q);
+    hipLaunchKernelGGL((smk_k_shadow_slice<DT, TF, SH, OCC, PERT, NVL>), dim3(blocks), dim3(256), 0, s, P, Q);
   }
   return hipGetLastError();
 }
@@ -860,6 +871,15 @@ hipError_t smk_launch_shadow(const RenderParams &P, const smk_shadowcoef &sc, in
   ShadowSlice Q;
   memset(&Q, 0, sizeof Q);
   Q.sc = sc;
+  if (P.sh.on == 2) {  // the NV20 look (option shadow_look 1): shading none or NV20 Phong, never perturbed
+#define CASE(D, T, S) \
+  if (dtype == D && tf_mode == T && shade_kind == S && !P.pert_on) \
+    return P.zscene ? run<D, T, S, true, false, true>(P, Q, L0, L1, barrier, s) : run<D, T, S, false, false, true>(P, Q, L0, L1, barrier, s);
+    CASE(0, 1, 0) CASE(0, 1, 2) CASE(0, 2, 0) CASE(0, 2, 2)
+    CASE(1, 1, 0) CASE(1, 1, 2) CASE(1, 2, 0) CASE(1, 2, 2)
+#undef CASE
+    return hipErrorNotSupported;
+  }
 #define CASE(D, T, S) \
   if (dtype == D && tf_mode == T && shade_kind == S) \
     return P.pert_on ? (P.zscene ? run<D, T, S, true, true>(P, Q, L0, L1, barrier, s) : run<D, T, S, false, true>(P, Q, L0, L1, barrier, s)) \

@@ -263,7 +263,9 @@ int smk_shadow_setup(smk_ctx *c, RenderParams &P, smk_shadowcoef &sc, SmkShadowS
   // the eye rays over the half-angle slices, planes counted from the eye (smk_internal.h SmkShadowRays)
   SmkShadowRays &h = P.sh;
   memset(&h, 0, sizeof h);
-  h.on = 1;
+  // (option shadow_look 1, the NV20 look: on = 2, and keep = 1 - amb, the share of its colour a fully shadowed sample loses)
+  h.on = c->opt_shadow_look ? 2 : 1;
+  h.keep = c->opt_shadow_look ? 1.0f - c->amb : 0.0f;
   for (int a = 0; a < 3; ++a) { h.Ec[a] = sc.Ec[a]; h.Dc[a] = sc.Dc[a]; h.Dx[a] = sc.Dx[a]; h.Dy[a] = sc.Dy[a]; }
   h.nDc = sc.nDc; h.nDx = sc.nDx; h.nDy = sc.nDy;
   if (sc.front_to_back) { h.numA = fmaf(1.0f, sc.dnum, sc.num0); h.dB = sc.dnum; h.k0 = 1; h.dk = 1; }
@@ -343,8 +345,16 @@ int smk_shadow_setup(smk_ctx *c, RenderParams &P, smk_shadowcoef &sc, SmkShadowS
 // what a frame with shadows cannot be combined with (the same reasons as smk_render's)
 static int shadow_refusals(smk_ctx *c, const RenderParams &P) {
   const int sk = smk_shade_kind(c);
+  const bool nv20 = c->opt_shadow_look != 0;  // (option shadow_look 1: NV20VolRen3D2's look, smk.h smk_set_shadow)
+  if (c->tf_mode == 0 && nv20) FAIL(c, "smk_render: shadow_look 1 needs a 2-D or 3-D transfer function (the 1-D table renderer has no shadow mode)");
   if (c->tf_mode == 0) FAIL(c, "smk_render: shadows need a 2-D or 3-D transfer function (the 1-D table renderer has no shadow mode)");
-  if (sk == 2) FAIL(c, "smk_render: shadows are implemented for R8k shading or none (NV20 combiners: no shadow mode in NV20VolRen3D)");
+  if (sk == 2 && !nv20) FAIL(c, "smk_render: shadows are implemented for R8k shading or none (NV20 combiners: no shadow mode in NV20VolRen3D)");
+  if (sk == 1 && nv20) FAIL(c, "smk_render: shadow_look 1 is NV20VolRen3D2's: shading none or NV20");
+  if (nv20 && !(c->amb >= 0.0f && c->amb <= 1.0f))
+    FAIL(c, "smk_render: shadow_look 1 needs the ambient term of smk_set_shading finite and in [0, 1] (amb = %g)", (double)c->amb);
+  if (nv20 && P.pert_on) FAIL(c, "smk_render: shadow_look 1 has no perturbed instances (perturbation under shadows is the R8k look's, option shadow_perturb)");
+  if (nv20 && (c->opt_lockstep & 256)) FAIL(c, "smk_render: shadow_look 1 has no shadow_fused instances; use the two marches or shadow_march 0");
+  if (nv20 && c->opt_kernel == 3) FAIL(c, "smk_render: shadow_look 1: the column-stream kernel has no shadow mode");
   if (c->nranks > 1 && (!c->opt_shadow_march || (c->opt_lockstep & 256)))
     FAIL(c, "smk_render: shadows need the whole volume on one GPU with option shadow_march 0 or shadow_fused (the light buffer couples every "
             "slice of every brick); a shard renders shadows with the two marches only");
@@ -439,7 +449,7 @@ static int launch_per_slice(smk_ctx *c, const RenderParams &P, const smk_shadowc
 int smk_shadow_frame(smk_ctx *c, RenderParams &P, void *d_rgba, void *d_depth, hipStream_t s, bool *marched) {
   const int sk = smk_shade_kind(c);
   // (a perturbed or sub-box frame on a shard is refused for what it is, entries or none: shadow_refusals)
-  if (c->nranks > 1 && !c->shadow_entries_fresh && c->tf_mode != 0 && sk != 2 && !((P.pert_on && c->opt_shadow_perturb) || c->region_on))
+  if (c->nranks > 1 && !c->shadow_entries_fresh && c->tf_mode != 0 && sk != (c->opt_shadow_look ? 1 : 2) && !((P.pert_on && c->opt_shadow_perturb) || c->region_on))
     FAIL(c, "smk_render: shadows need the whole volume on one GPU (the light buffer couples every slice of every brick) -- "
             "or, on a shard, this frame's light entries: smk_shadow_exports_device on every rank, then smk_shadow_entries_device "
             "(smk_shadow_exchange_local in one process)");

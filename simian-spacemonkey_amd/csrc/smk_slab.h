@@ -74,6 +74,14 @@ hipError_t smk_slab_dispatch_f32(const RenderParams &P, const SlabParams &Q, int
 // ... and one for the eye pass of frames with shadows (SHD instances: 2-D / 3-D table, R8k shading or none, both voxel types)
 hipError_t smk_slab_dispatch_shadow(const RenderParams &P, const SlabParams &Q, int dtype, int tf_mode, int shade_kind, int nw, int nl, size_t lds,
                                     int nblocks, const char **why, hipStream_t s);
+// The NV20 look's slice-ring instances that are NOT built: float voxels, 10+2 waves, brick flags -- at the 80 VGPRs of their
+// launch bound they would spill (profiles/shadow_nv20.md).  One predicate for the dispatch, which declines such a launch, and
+// for the shape choice, which passes such a shape over (smk_slab_plan.hip)
+constexpr bool slab_nv20_left_out(int dtype, int nw, int nl, bool bricks) { return dtype == 1 && nw == 10 && nl == 2 && bricks; }
+constexpr const char *SLAB_NV20_LEFT_OUT = "option shadow_look 1 has no float-voxel 10+2-wave instances with brick flags (they would spill)";
+// ... and one for that eye pass in the NV20 look (option shadow_look 1; NVL instances: shading none or NV20 Phong)
+hipError_t smk_slab_dispatch_shadow_nv20(const RenderParams &P, const SlabParams &Q, int dtype, int tf_mode, int shade_kind, int nw, int nl,
+                                         size_t lds, int nblocks, const char **why, hipStream_t s);
 // ... and for frames with the host's opaque scene depth (OCC instances, smk_render_occluded): view-aligned planes, and the eye
 // pass of frames with shadows
 hipError_t smk_slab_dispatch_occluded(const RenderParams &P, const SlabParams &Q, int dtype, int tf_mode, int shade_kind, int nw, int nl, size_t lds,

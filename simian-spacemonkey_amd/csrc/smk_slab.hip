@@ -194,7 +194,9 @@ __device__ __forceinline__ float slab_tex_chan(const SlabTexel4 &x, int k) {
 // (OCC: the frame has the host's opaque scene depth, smk_render_occluded -- folded into each ray's plane range in the set-up.
 //  Compile-time as well: as a run-time test it cost the instances of frames without one a VGPR and a few SGPR spills; the
 //  instances live in smk_slab_occ.hip and smk_slab_occ_shadow.hip, SLAB_PART 3 and 4)
-template <int DT, int SH, int PERM, int NW, int NL, bool DIAG, int TF = 1, bool BR = true, bool SHD = false, bool OCC = false>
+// (NVL: the NV20 look of a frame with shadows, option shadow_look 1 -- the sample keeps 1 - sat(light-buffer opacity) (1 - amb)
+//  of its colour, smk_shadow_keep.  Compile-time as SHD is, SHD instances without OCC only: smk_slab_shadow_nv20.hip, SLAB_PART 5)
+template <int DT, int SH, int PERM, int NW, int NL, bool DIAG, int TF = 1, bool BR = true, bool SHD = false, bool OCC = false, bool NVL = false>
 // (second argument: waves per SIMD the register allocation must allow -- two small workgroups per CU)
 __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) == 5 || (NW + NL) == 10) ? 5 : ((NW + NL) == 11 ? 3 : (NW + NL) == 12 ? 6 : 4)) void smk_k_slab(const RenderParams P, const SlabParams Q) {
   constexpr int UPV = DT == 0 ? 2 : 1;   // voxels per 16-byte DMA unit
@@ -1329,21 +1331,25 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
             float4 src;
             // frames with shadows: the light-buffer colour over the sample, as the slices nearer the light left it
             // (smk_shadow.hip; the sample's own position: the gather kernel's fma chain)
-            float shadow[3];
+            float shadow[3], keepf = 1.0f;
             const float *shp = nullptr;
             if (TF != 0 && SHD) {
               const float mf = (float)m;
-              smk_shadow_term(P, m, __fmaf_rn(mf, B[0], A[0]), __fmaf_rn(mf, B[1], A[1]), __fmaf_rn(mf, B[2], A[2]), shadow);
-              shp = shadow;
+              if constexpr (NVL) {
+                keepf = smk_shadow_keep(P, m, __fmaf_rn(mf, B[0], A[0]), __fmaf_rn(mf, B[1], A[1]), __fmaf_rn(mf, B[2], A[2]));
+              } else {
+                smk_shadow_term(P, m, __fmaf_rn(mf, B[0], A[0]), __fmaf_rn(mf, B[1], A[1]), __fmaf_rn(mf, B[2], A[2]), shadow);
+                shp = shadow;
+              }
             }
             if (TF == 0) {
               src = col;  // the 1-D colour table's entries are premultiplied (TLUT.cpp:65-71), as in the gather kernel
             } else if (SH == 0) {
-              src = smk_shade_sample<0>(P, col, 0.f, 0.f, 0.f, 0.f, shp);
+              src = smk_shade_sample<0, NVL>(P, col, 0.f, 0.f, 0.f, 0.f, shp, keepf);
             } else {
               // (the separable table's path has the normal's share already: SHADE UNDER THE FETCH)
               if (!(TF == 1 && Q.fast_tf)) ph = phong_geom();
-              src = smk_shade_apply<SH>(P, col, ch1, ph, shp);
+              src = smk_shade_apply<SH, NVL>(P, col, ch1, ph, shp, keepf);
             }
             // first-hit depth (the gather kernel's `first`): the first sample that passes classification finds the accumulated
             // alpha still exactly 0, no later one does -- nothing is carried through the loop for it
@@ -1465,10 +1471,11 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
 
 // ------------------------------------------------------------------------------- host side
 
-// This file is compiled five times (build time: the instances are most of it): as itself -- the merge pass + the byte-voxel
+// This file is compiled six times (build time: the instances are most of it): as itself -- the merge pass + the byte-voxel
 // instances --, through smk_slab_f32.hip (SLAB_PART 1) -- the float-voxel instances alone --, through smk_slab_shadow.hip
-// (SLAB_PART 2) -- the instances of the eye pass of frames with shadows --, and through smk_slab_occ.hip (SLAB_PART 3) and
-// smk_slab_occ_shadow.hip (SLAB_PART 4) -- the instances of frames with the host's scene depth (OCC), without and with shadows.
+// (SLAB_PART 2) -- the instances of the eye pass of frames with shadows --, through smk_slab_occ.hip (SLAB_PART 3) and
+// smk_slab_occ_shadow.hip (SLAB_PART 4) -- the instances of frames with the host's scene depth (OCC), without and with shadows
+// --, and through smk_slab_shadow_nv20.hip (SLAB_PART 5) -- the eye pass of frames with shadows in the NV20 look (NVL).
 #ifndef SLAB_PART
 #define SLAB_PART 0
 #endif
@@ -1506,9 +1513,9 @@ hipError_t smk_slab_merge(const int2 *list, int n, int tw, int th, int ntx, int 
 }
 #endif  // SLAB_PART == 0
 
-template <int DT, int SH, int PERM, int NW, int NL, bool DIAG, int TF = 1, bool BR = true, bool SHD = false, bool OCC = false>
+template <int DT, int SH, int PERM, int NW, int NL, bool DIAG, int TF = 1, bool BR = true, bool SHD = false, bool OCC = false, bool NVL = false>
 static hipError_t launch_slab(const RenderParams &P, const SlabParams &Q, size_t lds, int nblocks, hipStream_t s) {
-  auto k = smk_k_slab<DT, SH, PERM, NW, NL, DIAG, TF, BR, SHD, OCC>;
+  auto k = smk_k_slab<DT, SH, PERM, NW, NL, DIAG, TF, BR, SHD, OCC, NVL>;
   static bool attr_set[64] = {};  // per device: the attribute belongs to the function ON the current device
   int dev = 0;
   (void)hipGetDevice(&dev);
@@ -1582,6 +1589,40 @@ hipError_t smk_slab_dispatch_shadow(const RenderParams &P, const SlabParams &Q, 
 #undef GO_NW
 #undef GO
   *why = "no shadow instance for this configuration";
+  return hipErrorNotSupported;
+}
+#elif SLAB_PART == 5
+// The NV20 look (option shadow_look 1): shading none or NV20 Phong, both voxel types, 2-D / 3-D table.  No scene-depth (OCC)
+// instances: such a frame is the gather kernel's (smk_slab_plan.hip slab_refusal).  Nor the float-voxel 10+2-wave instances
+// with brick flags: at the 80 VGPRs their launch bound allows they spill 1-4 VGPRs to scratch (profiles/shadow_nv20.md), and
+// no instance of this look is built with scratch -- the shape choice passes those shapes over (smk_slab_plan.hip
+// slab_shape_without_instance); one forced with option "tile" is declined with this reason
+hipError_t smk_slab_dispatch_shadow_nv20(const RenderParams &P, const SlabParams &Q, int dtype, int tf_mode, int shade_kind, int nw, int nl,
+                                         size_t lds, int nblocks, const char **why, hipStream_t s) {
+#define GO_BR(D, S, R, N, L, T)                                                                                      \
+  if (Q.bricks) {                                                                                                   \
+    if constexpr (slab_nv20_left_out(D, N, L, true)) {                                                              \
+      *why = SLAB_NV20_LEFT_OUT;                                                                                    \
+      return hipErrorNotSupported;                                                                                  \
+    } else                                                                                                          \
+      return (launch_slab<D, S, R, N, L, false, T, true, true, false, true>(P, Q, lds, nblocks, s));                \
+  }                                                                                                                 \
+  return (launch_slab<D, S, R, N, L, false, T, false, true, false, true>(P, Q, lds, nblocks, s));
+#define GO(D, S, R, N, L)                                                       \
+  if (dtype == D && shade_kind == S && Q.perm == R && nw == N && nl == L) {   \
+    if (tf_mode == 2) { GO_BR(D, S, R, N, L, 2) }                             \
+    if (tf_mode == 1) { GO_BR(D, S, R, N, L, 1) }                             \
+    *why = "shadows need a 2-D or 3-D table";                                 \
+    return hipErrorNotSupported;                                              \
+  }
+#define GO_NW(D, S, R) GO(D, S, R, 8, 2) GO(D, S, R, 10, 2) GO(D, S, R, 12, 4)
+#define GO_R(D, S) GO_NW(D, S, 0) GO_NW(D, S, 1) GO_NW(D, S, 2)
+  GO_R(0, 0) GO_R(0, 2) GO_R(1, 0) GO_R(1, 2)
+#undef GO_R
+#undef GO_NW
+#undef GO
+#undef GO_BR
+  *why = "no shadow_look 1 instance for this configuration";
   return hipErrorNotSupported;
 }
 #else

@@ -238,6 +238,8 @@ static const char *slab_refusal(const RenderParams &P, int dtype, int tf_mode, c
   if (P.N[0] < 2 || P.N[1] < 2 || P.N[2] < 2) return "volume thinner than 2 voxels";
   if (dtype == 1 && !P.n_in_w) return "4-channel f32 voxels";
   if (P.rc.nplanes <= 0) return "no planes";
+  // (the NV20 look has SHD instances without OCC only, smk_slab.hip SLAB_PART 5: the gather kernel renders the frame)
+  if (P.sh.on == 2 && P.zscene) return "option shadow_look 1 has no scene-depth instances of the slice-ring kernel";
   if (P.sh.on) {
     // frames with shadows: the component of a ray along the slice normal is affine in the pixel coordinate; where it keeps
     // its sign over the viewport's corners no ray runs parallel to the slices (the planning divides by it)
@@ -494,6 +496,12 @@ static const char *slab_size_shape(RenderParams &P, SlabParams &Q, SlabShape sh,
   return why ? why : slab_window(P, Q, dtype, slab_big(slab_waves(sh), sh.nl), m, last);
 }
 
+// A shape whose workgroup has no kernel instance for this frame (the NV20 look of a frame with shadows, option shadow_look 1:
+// slab_nv20_left_out, smk_slab.h).  The shape choice passes such a shape over.
+static bool slab_shape_without_instance(const RenderParams &P, int dtype, SlabShape sh, bool bricks) {
+  return P.sh.on == 2 && slab_nv20_left_out(dtype, slab_waves(sh), sh.nl, bricks);
+}
+
 // ---- the probing pass: the candidate small shape with the fewest DMA instructions per ray (*best, -1 if no candidate's
 // window fits), its window sized from a sparse scan.  Returns the refusal or null.
 static const char *slab_probe(RenderParams P, SlabParams Q, int dtype, SlabAux *aux, int *best) {
@@ -503,6 +511,7 @@ static const char *slab_probe(RenderParams P, SlabParams Q, int dtype, SlabAux *
   *best = -1;
   for (int ci = 0; ci < 3; ++ci) {
     const SlabShape sh = SLAB_CAND[ci];
+    if (slab_shape_without_instance(P, dtype, sh, P.bricks != nullptr)) continue;
     const char *why = slab_size_shape(P, Q, sh, dtype, true, false, aux, work);
     if (why == SLAB_NEXT) continue;
     if (why) return why;
@@ -613,8 +622,9 @@ static const char *slab_choose_shape(RenderParams &P, SlabParams &Q, int dtype, 
   // camera that moves every frame must not pay the probe -- nor flip between two shapes of nearly equal score, which
   // would throw away the measured schedule weights of the tiling each time.  The probe itself scans every fourth tile
   // row and column plus the borders (its answer only ranks the shapes; the real pass sizes the winner's window fully).
-  struct ShapeKey { int as, dir, W, H, dtype, N[3]; float lo[3], hi[3]; } skey;
+  struct ShapeKey { int as, dir, W, H, dtype, N[3]; float lo[3], hi[3]; int nv20; } skey;  // (nv20: that look's candidates differ)
   memset(&skey, 0, sizeof skey);
+  skey.nv20 = P.sh.on == 2;
   skey.as = Q.as; skey.dir = Q.dir; skey.W = P.W; skey.H = P.H; skey.dtype = dtype;
   for (int a = 0; a < 3; ++a) { skey.N[a] = P.N[a]; skey.lo[a] = P.lo[a]; skey.hi[a] = P.hi[a]; }
   const bool shape_known = choose && aux->shape_key.size() == sizeof skey && !memcmp(aux->shape_key.data(), &skey, sizeof skey) &&
@@ -651,6 +661,7 @@ static const char *slab_choose_shape(RenderParams &P, SlabParams &Q, int dtype, 
       if (!shape_known) aux->shape_chunks = Q.chunks;
     }
     if (!why) why = slab_ring(P, Q, shape, tf_mode, ds, aux, last, lds);
+    if (!why && slab_shape_without_instance(P, dtype, shape, Q.bricks != nullptr)) why = last ? SLAB_NV20_LEFT_OUT : SLAB_NEXT;
     if (why == SLAB_NEXT_BIG && alt >= 0 && ci == 0) ci = 1;  // (a stream this heavy is too heavy for the other small shape as well: the big one next)
     if (why == SLAB_NEXT || why == SLAB_NEXT_BIG) continue;
     if (why) return why;
@@ -1063,11 +1074,19 @@ static hipError_t slab_run(const RenderParams &P, const SlabParams &Q, SlabAux *
     }
     (void)hipGetLastError();
   }
-  e = P.zscene   ? (P.sh.on ? smk_slab_dispatch_occluded_shadow(P, Q, dtype, tf_mode, shade_kind, nw, sh.nl, lds, nblocks, why, s)
-                             : smk_slab_dispatch_occluded(P, Q, dtype, tf_mode, shade_kind, nw, sh.nl, lds, nblocks, why, s))
-      : P.sh.on    ? smk_slab_dispatch_shadow(P, Q, dtype, tf_mode, shade_kind, nw, sh.nl, lds, nblocks, why, s)
-      : dtype == 0 ? smk_slab_dispatch_u8(P, Q, tf_mode, shade_kind, nw, sh.nl, diag, lds, nblocks, why, s)
-                   : smk_slab_dispatch_f32(P, Q, tf_mode, shade_kind, nw, sh.nl, diag, lds, nblocks, why, s);
+  // (the look first: the NV20 look has instances of its own and none for scene depth -- slab_refusal has declined that frame)
+  if (P.sh.on == 2) {
+    if (P.zscene) {
+      *why = "option shadow_look 1 has no scene-depth instances of the slice-ring kernel";
+      return hipErrorNotSupported;
+    }
+    e = smk_slab_dispatch_shadow_nv20(P, Q, dtype, tf_mode, shade_kind, nw, sh.nl, lds, nblocks, why, s);
+  } else
+    e = P.zscene   ? (P.sh.on ? smk_slab_dispatch_occluded_shadow(P, Q, dtype, tf_mode, shade_kind, nw, sh.nl, lds, nblocks, why, s)
+                               : smk_slab_dispatch_occluded(P, Q, dtype, tf_mode, shade_kind, nw, sh.nl, lds, nblocks, why, s))
+        : P.sh.on    ? smk_slab_dispatch_shadow(P, Q, dtype, tf_mode, shade_kind, nw, sh.nl, lds, nblocks, why, s)
+        : dtype == 0 ? smk_slab_dispatch_u8(P, Q, tf_mode, shade_kind, nw, sh.nl, diag, lds, nblocks, why, s)
+                     : smk_slab_dispatch_f32(P, Q, tf_mode, shade_kind, nw, sh.nl, diag, lds, nblocks, why, s);
   if (e == hipSuccess && nsplit > 0)
     e = smk_slab_merge(aux->d_order + nblocks, nsplit, sh.tw, sh.th, P.ntx, P.W, P.H, (const float4 *)aux->d_seg, P.out,
                        P.blend == SMK_BLEND_MAX ? 1 : 0, s);

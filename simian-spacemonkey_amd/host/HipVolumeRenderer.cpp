@@ -26,6 +26,9 @@ HipVolumeRenderer::HipVolumeRenderer(MetaVolume *vm, int, int device)
   // gluvv.pert.on and gluvv.light.shadow together are what the perturbing renderer this class mirrors draws
   // (R8kVolRen3D_cpy::volShadow, :1566-1601): the C ABI's opt-in for that combination (smk.h, smk_set_shadow)
   if (ctx) smk_set_option(ctx, "shadow_perturb", 1);
+  // the GeForce3 platform draws gluvv.light.shadow with NV20VolRen3D2 (gluvv.cpp:151-159): the light buffer's opacity with
+  // the ambient floor gluvv.light.amb -- the C ABI's NV20 look (smk.h, smk_set_shadow); every other platform keeps the R8k look
+  if (ctx && gluvv.plat == GPNV20) smk_set_option(ctx, "shadow_look", 1);
 }
 
 HipVolumeRenderer::~HipVolumeRenderer() {
