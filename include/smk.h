@@ -460,6 +460,33 @@ int smk_merge_fields_device(smk_ctx *ctx, const void *d_fields_u8, int nf, int s
  * [z][y][x][nelts] is already in device memory. */
 int smk_hist2d(smk_ctx *ctx, const smk_volume_desc *bricks, int n_bricks, int nelts, unsigned char *hist);
 int smk_hist2d_device(smk_ctx *ctx, const void *d_vol_u8, int nelts, int sx, int sy, int sz, unsigned char *hist);
+/* The three entries above for FLOAT volumes [z][y][x][channels] f32: these extend the reference's byte
+ * arithmetic with the loads widened and the final quantisation dropped.  All pointers are DEVICE
+ * pointers, the work runs on the context's stream and each call synchronises before it returns.  Every step is plain
+ * fp32, one rounding per operation in the order written, so a float32 restatement gives the same bits.
+ *
+ * smk_normals_f32_device extends MetaVolume::normalsVGH = derivative3DVGH + optional blurV3D + scalebiasN
+ * (VectorMath.h:874-899, 1217-1281, 1133-1148): the gradient of channel 0, g[e] = d[o + stride_e] - d[o - stride_e] (one
+ * fp32 subtraction, 0 on the 1-voxel border); blur != 0 applies smk_normals_vgh_device's weights, 27-term order,
+ * interior-only sources and divisor; the bytes are those of smk_normals_vgh_device's scalebiasN step (nrm_store in
+ * smk_prep.hip), +1 -> 255 clamp included.  If a component of the gradient handed to that step is not finite, the voxel
+ * gets the zero vector's bytes (128, 128, 128).  d_normals is [z][y][x][3] u8, what smk_upload_volume_device /
+ * smk_upload_timestep_device take as grad.  The reference has no float pipeline. */
+int smk_normals_f32_device(smk_ctx *ctx, const void *d_f32, int nelts, int sx, int sy, int sz, int blur, void *d_normals);
+/* extends MetaVolume::mergeMV with addG (MetaVolume.cpp:1109-1268; AGradArb VectorMath.h:945-1030): nf (1..3) fields
+ * interleaved [z][y][x][nf] f32, dims >= 3, -> d_out [z][y][x][nf+1] f32.  out[..., 0:nf] are the input floats bit for
+ * bit; out[..., nf] = mag / maxm (one fp32 division), mag = sqrtf(g0*g0 + g1*g1 + g2*g2) of the SUMMED gradient (fields
+ * ascending, one add per field and axis, 0 on the border), maxm the maximum of mag over the voxels whose mag is finite.
+ * A voxel whose mag is not finite gets G = 0, and every voxel does when maxm is 0.  The optional normals [z][y][x][3] u8
+ * come from the summed gradient by smk_normals_f32_device's rule.  The reference has no float pipeline: its GMag
+ * quantises to a byte, (uchar)(mag / max * 255), which is what is dropped here. */
+int smk_merge_fields_f32_device(smk_ctx *ctx, const void *d_fields_f32, int nf, int sx, int sy, int sz, void *d_out_f32,
+                                void *d_normals_or_null);
+/* extends MetaVolume::hist2D (MetaVolume.cpp:1650-1688): a channel's bin is b(v) with t = v * 255.0f (one fp32
+ * multiply): NaN or t < 0 -> 0, t >= 255 -> 255, otherwise (int)t.  Counts go to hist[b(c1) * 256 + b(c0)] and are
+ * finished as smk_hist2d_device's (log scale, float bins that stop at 2^24); hist is 65536 bytes in HOST memory and
+ * nelts < 2 is refused as there.  d_vol_f32 needs float alignment only.  The reference has no float pipeline. */
+int smk_hist2d_f32_device(smk_ctx *ctx, const void *d_vol_f32, int nelts, int sx, int sy, int sz, unsigned char *hist);
 /* synthetic scalar test volumes generated on the GPU (u8, [z][y][x]):
  *   kind 1 = the reference's own generator: `genvol -spheres 4 -p 10 -pscale .7 -pwrap 3 3 3 -pabs -blur
  *            -bw 1 1 1 .7` with srand(seed) (genvol/main.cpp:153-165, 212-256, 334-430; perlin.c; script

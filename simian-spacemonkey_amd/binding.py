@@ -20,6 +20,7 @@ ABI_SYMBOLS = [
     "smk_set_tf2d", "smk_set_tf3d", "smk_set_camera", "smk_set_shading", "smk_set_sampling",
     "smk_set_perturb", "smk_set_blend", "smk_set_shadow", "smk_get_shadowcoef", "smk_get_light_buffer", "smk_get_brick_flags", "smk_render", "smk_render_device", "smk_composite_over_device",
     "smk_make_vgh_device", "smk_normals_vgh_device", "smk_synth_volume_device",
+    "smk_normals_f32_device", "smk_merge_fields_f32_device", "smk_hist2d_f32_device",
     "smk_get_raycoef", "smk_set_option", "smk_last_frame_info", "smk_get_stat", "smk_get_trace", "smk_get_tf2d_effective",
     "smk_timing_reset", "smk_timing_read", "smk_last_frame_id", "smk_frame_failed",
     "smk_exchange_unique_id", "smk_exchange_create", "smk_exchange_connect_local", "smk_exchange_destroy",
@@ -180,6 +181,9 @@ def load_library():
     L.smk_merge_fields_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.smk_hist2d.argtypes = [C.c_void_p, C.POINTER(VolumeDesc), C.c_int, C.c_int, C.c_void_p]
     L.smk_hist2d_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.smk_normals_f32_device.argtypes = L.smk_normals_vgh_device.argtypes
+    L.smk_merge_fields_f32_device.argtypes = L.smk_merge_fields_device.argtypes
+    L.smk_hist2d_f32_device.argtypes = L.smk_hist2d_device.argtypes
     L.smk_synth_volume_device.argtypes = [C.c_void_p, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_int,
                                           C.c_void_p]
     L.smk_get_raycoef.argtypes = [C.c_void_p, P(RayCoef)]
@@ -674,6 +678,24 @@ class Renderer:
             d.data = _ptr(sub)
         out = np.zeros((256, 256), np.uint8)
         self._ck(self.L.smk_hist2d(self.ctx, descs, len(bricks), ne, _ptr(out)))
+        return out
+
+    # -- the same for float volumes [z][y][x][channels] f32 (smk.h: smk_normals_f32_device ...)
+    def normals_f32_device(self, d_f32, nelts, dims, blur, d_normals):
+        """normal bytes [z][y][x][3] of channel 0's gradient; a gradient that is not finite gives (128, 128, 128)"""
+        sx, sy, sz = dims
+        self._ck(self.L.smk_normals_f32_device(self.ctx, d_f32, nelts, sx, sy, sz, int(blur), d_normals))
+
+    def merge_fields_f32_device(self, d_fields_f32, nf, dims, d_out_f32, d_normals=None):
+        """nf interleaved float fields -> [z][y][x][nf+1] f32 with |summed gradient| / its finite maximum as last channel"""
+        sx, sy, sz = dims
+        self._ck(self.L.smk_merge_fields_f32_device(self.ctx, d_fields_f32, nf, sx, sy, sz, d_out_f32, d_normals))
+
+    def hist2d_f32_device(self, d_vol_f32, nelts, dims):
+        """log-scaled joint (value, gradient) histogram [g][v] of a device-resident f32 volume, bins (int)(v * 255)"""
+        sx, sy, sz = dims
+        out = np.zeros((256, 256), np.uint8)
+        self._ck(self.L.smk_hist2d_f32_device(self.ctx, d_vol_f32, nelts, sx, sy, sz, _ptr(out)))
         return out
 
     def synth_volume_device(self, kind, seed, dims, d_out):

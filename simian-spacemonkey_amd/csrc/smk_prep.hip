@@ -4,6 +4,8 @@
 //   smk_normals_vgh_device   MetaVolume::normalsVGH            MetaVolume.cpp:1274-1324
 //                            = derivative3DVGH + blurV3D + scalebiasN
 //                                                              VectorMath.h:874-899, 1217-1281, 1133-1148
+//   smk_normals_f32_device, smk_merge_fields_f32_device, smk_hist2d_f32_device
+//                            normals, merge and histogram of float volumes (no reference equivalent)
 //   smk_synth_volume_device  bench/test input generator (no reference equivalent; genvol's
 //                            Perlin tables depend on libc rand(), so the GPU generator is analytic)
 //
@@ -539,6 +541,276 @@ extern "C" int smk_hist2d(smk_ctx *c, const smk_volume_desc *b, int nb, int nelt
     if (c->err.empty()) c->err = "smk_hist2d: HIP error";
     return 1;
   }
+  hist2d_finish(counts.data(), hist);
+  return 0;
+}
+
+// ------------------------------------------------------------------------------- float volumes
+// smk_normals_f32_device, smk_merge_fields_f32_device, smk_hist2d_f32_device: the three u8 entries above for
+// [z][y][x][channels] f32 volumes (the reference has no float pipeline).  The arithmetic is the u8
+// kernels' with the loads widened and the final quantisation dropped: plain fp32, one rounding per operation in
+// the order written, so a NumPy float32 restatement gives the same bits.  What float data adds is values that are
+// not finite: they never reach scalebiasN (such a voxel gets the zero vector's bytes) and never win the maximum.
+
+__device__ __forceinline__ bool finite3(const float g[3]) {
+  return __builtin_isfinite(g[0]) && __builtin_isfinite(g[1]) && __builtin_isfinite(g[2]);
+}
+
+// nrm_store behind the float rule: a gradient with a component that is not finite is stored as the zero vector
+__device__ __forceinline__ void nrm_store_f32(float g[3], unsigned char *out) {
+  if (!finite3(g)) {
+    out[0] = out[1] = out[2] = 128;
+    return;
+  }
+  nrm_store(g, out);
+}
+
+// derivative3DVGH on floats: one fp32 subtraction per axis of channel 0, 0 on the border
+__device__ __forceinline__ void nrm_grad_f32(const float *d, int ne, int sx, int sy, int sz, int i, int j, int k,
+                                             float g[3]) {
+  if (is_border(sx, sy, sz, i, j, k)) {
+    g[0] = g[1] = g[2] = 0.f;
+    return;
+  }
+  size_t sxy = (size_t)sx * sy, o = (size_t)i * sxy + (size_t)j * sx + k;
+  g[0] = d[(o + 1) * ne] - d[(o - 1) * ne];
+  g[1] = d[(o + sx) * ne] - d[(o - sx) * ne];
+  g[2] = d[(o + sxy) * ne] - d[(o - sxy) * ne];
+}
+
+// smk_k_normals with float loads: the same weights, 27-term gather order, interior-only sources and divisor
+template <int BLUR>
+__global__ __launch_bounds__(256) void smk_k_normals_f32(const float *d, int ne, int sx, int sy, int sz,
+                                                         unsigned char *out) {
+  size_t n = (size_t)sx * sy * sz;
+  for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (size_t)gridDim.x * blockDim.x) {
+    int k = (int)(t % sx), j = (int)((t / sx) % sy), i = (int)(t / ((size_t)sx * sy));
+    float g[3];
+    if (!BLUR) {
+      nrm_grad_f32(d, ne, sx, sy, sz, i, j, k, g);
+    } else {
+      const float w[4] = {1.0f, .3f, .2f, .1f};  // MetaVolume.cpp:1316
+      float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+      for (int di = -1; di <= 1; ++di)
+        for (int dj = -1; dj <= 1; ++dj)
+          for (int dk = -1; dk <= 1; ++dk) {
+            int si = i + di, sj = j + dj, sk = k + dk;
+            if (si < 1 || si > sz - 2 || sj < 1 || sj > sy - 2 || sk < 1 || sk > sx - 2) continue;
+            float s[3];
+            nrm_grad_f32(d, ne, sx, sy, sz, si, sj, sk, s);
+            float ww = w[(di != 0) + (dj != 0) + (dk != 0)];
+            a0 = a0 + ww * s[0];
+            a1 = a1 + ww * s[1];
+            a2 = a2 + ww * s[2];
+          }
+      const float div = 1.0f + 6 * .3f + 12 * .2f + 8 * .1f;
+      g[0] = a0 / div;
+      g[1] = a1 / div;
+      g[2] = a2 / div;
+    }
+    nrm_store_f32(g, out + t * 3);
+  }
+}
+
+extern "C" int smk_normals_f32_device(smk_ctx *c, const void *d, int ne, int sx, int sy, int sz, int blur, void *out) {
+  if (!c) return 1;
+  PCHK(c, hipSetDevice(c->device));
+  if (!d || !out || ne < 1 || sx < 1 || sy < 1 || sz < 1) {
+    c->err = "smk_normals_f32_device: bad arguments";
+    return 1;
+  }
+  size_t n = (size_t)sx * sy * sz;
+  unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 256 * 32);
+  if (blur)
+    hipLaunchKernelGGL(smk_k_normals_f32<1>, dim3(blocks), dim3(256), 0, c->stream, (const float *)d, ne, sx, sy, sz,
+                       (unsigned char *)out);
+  else
+    hipLaunchKernelGGL(smk_k_normals_f32<0>, dim3(blocks), dim3(256), 0, c->stream, (const float *)d, ne, sx, sy, sz,
+                       (unsigned char *)out);
+  PCHK(c, hipGetLastError());
+  PCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// merge_grad on floats: fields ascending, one add per field and axis, 0 on the border
+template <int NF>
+__device__ __forceinline__ void merge_grad_f32(const float *in, int sx, int sy, int sz, int i, int j, int k, float g[3]) {
+  g[0] = g[1] = g[2] = 0.f;
+  if (is_border(sx, sy, sz, i, j, k)) return;
+  const size_t sxy = (size_t)sx * sy, o = (size_t)i * sxy + (size_t)j * sx + k;
+#pragma unroll
+  for (int e = 0; e < NF; ++e) {
+    g[0] += in[(o + 1) * NF + e] - in[(o - 1) * NF + e];
+    g[1] += in[(o + sx) * NF + e] - in[(o - sx) * NF + e];
+    g[2] += in[(o + sxy) * NF + e] - in[(o - sxy) * NF + e];
+  }
+}
+
+// the maximum of the finite magnitudes (ordered-int atomicMax as smk_k_merge_max)
+template <int NF>
+__global__ __launch_bounds__(256) void smk_k_merge_max_f32(const float *in, int sx, int sy, int sz, int *omax) {
+  const size_t n = (size_t)sx * sy * sz;
+  int m = 0;  // f2o(0.0f): magnitudes are >= 0
+  for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (size_t)gridDim.x * blockDim.x) {
+    int k = (int)(t % sx), j = (int)((t / sx) % sy), i = (int)(t / ((size_t)sx * sy));
+    float g[3];
+    merge_grad_f32<NF>(in, sx, sy, sz, i, j, k, g);
+    const float mag = sqrtf(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
+    if (__builtin_isfinite(mag)) m = max(m, f2o(mag));
+  }
+  m = wave_max(m);
+  if ((threadIdx.x & 63) == 0) atomicMax(omax, m);
+}
+
+template <int NF>
+__global__ __launch_bounds__(256) void smk_k_merge_write_f32(const float *in, int sx, int sy, int sz, const int *omax,
+                                                             float *out, unsigned char *nrm) {
+  const size_t n = (size_t)sx * sy * sz;
+  const float maxm = o2f(*omax);
+  const int ne = NF + 1;
+  for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (size_t)gridDim.x * blockDim.x) {
+    int k = (int)(t % sx), j = (int)((t / sx) % sy), i = (int)(t / ((size_t)sx * sy));
+    float g[3];
+    merge_grad_f32<NF>(in, sx, sy, sz, i, j, k, g);
+    const float mag = sqrtf(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
+    unsigned w[NF + 1];  // the fields travel as raw words: bit for bit, NaN payloads included
+#pragma unroll
+    for (int e = 0; e < NF; ++e) w[e] = ((const unsigned *)in)[t * NF + e];
+    w[NF] = __float_as_uint((maxm > 0.f && __builtin_isfinite(mag)) ? mag / maxm : 0.f);
+#pragma unroll
+    for (int e = 0; e < ne; ++e) ((unsigned *)out)[t * ne + e] = w[e];
+    if (nrm) nrm_store_f32(g, nrm + t * 3);
+  }
+}
+
+template <int NF>
+static void merge_f32_launch(smk_ctx *c, unsigned blocks, const float *in, int sx, int sy, int sz, int *d_max, float *out,
+                             unsigned char *nrm) {
+  hipLaunchKernelGGL(smk_k_merge_max_f32<NF>, dim3(blocks), dim3(256), 0, c->stream, in, sx, sy, sz, d_max);
+  hipLaunchKernelGGL(smk_k_merge_write_f32<NF>, dim3(blocks), dim3(256), 0, c->stream, in, sx, sy, sz, (const int *)d_max, out, nrm);
+}
+
+extern "C" int smk_merge_fields_f32_device(smk_ctx *c, const void *d_fields, int nf, int sx, int sy, int sz, void *d_out,
+                                           void *d_normals) {
+  if (!c) return 1;
+  PCHK(c, hipSetDevice(c->device));
+  if (!d_fields || !d_out || nf < 1 || nf > 3 || sx < 3 || sy < 3 || sz < 3) {
+    c->err = "smk_merge_fields_f32_device: bad arguments (1..3 fields, dims >= 3)";
+    return 1;
+  }
+  int *d_max = nullptr;
+  PCHK(c, hipMalloc((void **)&d_max, sizeof(int)));
+  const size_t n = (size_t)sx * sy * sz;
+  const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 256 * 32);
+  int rc = hipMemsetAsync(d_max, 0, sizeof(int), c->stream) != hipSuccess;
+  if (!rc) {
+    const float *in = (const float *)d_fields;
+    if (nf == 1) merge_f32_launch<1>(c, blocks, in, sx, sy, sz, d_max, (float *)d_out, (unsigned char *)d_normals);
+    else if (nf == 2) merge_f32_launch<2>(c, blocks, in, sx, sy, sz, d_max, (float *)d_out, (unsigned char *)d_normals);
+    else merge_f32_launch<3>(c, blocks, in, sx, sy, sz, d_max, (float *)d_out, (unsigned char *)d_normals);
+    rc = hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess;
+  }
+  (void)hipFree(d_max);
+  if (rc) {
+    c->err = "smk_merge_fields_f32_device: HIP error";
+    return 1;
+  }
+  return 0;
+}
+
+// a float channel's histogram bin: t = v * 255 in fp32; NaN and t < 0 -> 0, t >= 255 -> 255, else (int)t
+__device__ __forceinline__ unsigned hist_bin_f32(float v) {
+  const float t = v * 255.0f;
+  if (!(t >= 0.f)) return 0;
+  if (t >= 255.f) return 255;
+  return (unsigned)(int)t;
+}
+
+// smk_k_hist2d's LDS-binned counting with the key taken from two floats
+// (pairs: nelts == 2 and the volume 8-byte aligned, so a voxel is one float2 load)
+__global__ __launch_bounds__(1024) void smk_k_hist2d_f32(const float *vol, int nelts, int pairs, size_t nvox, unsigned *bins) {
+  extern __shared__ unsigned h16[];  // 32768 words = 65536 halves
+  const size_t nchunks = (nvox + SMK_HIST_CHUNK - 1) / SMK_HIST_CHUNK;
+  for (size_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
+    for (int w = threadIdx.x; w < 32768; w += 1024) h16[w] = 0;
+    __syncthreads();
+    const size_t base = chunk * SMK_HIST_CHUNK;
+    for (int k = 0; k < SMK_HIST_CHUNK / 1024; ++k) {
+      const size_t i = base + (size_t)k * 1024 + threadIdx.x;
+      const bool ok = i < nvox;
+      unsigned key = 0;
+      if (ok) {
+        float c0, c1;
+        if (pairs) {
+          const float2 p = ((const float2 *)vol)[i];
+          c0 = p.x;
+          c1 = p.y;
+        } else {
+          const float *d = vol + i * nelts;
+          c0 = d[0];
+          c1 = d[1];
+        }
+        key = hist_bin_f32(c0) | (hist_bin_f32(c1) << 8);
+      }
+      const unsigned long long live = __ballot(ok);
+      if (!live) continue;
+      const unsigned first = __builtin_amdgcn_readfirstlane(key);  // (of the first live lane)
+      if (__ballot(ok && key == first) == live) {
+        if (ok && (int)(threadIdx.x & 63) == __builtin_ctzll(live))
+          atomicAdd(&h16[first >> 1], (unsigned)__builtin_popcountll(live) << ((first & 1) * 16));
+      } else if (ok) {
+        atomicAdd(&h16[key >> 1], 1u << ((key & 1) * 16));
+      }
+    }
+    __syncthreads();
+    for (int w = threadIdx.x; w < 32768; w += 1024) {
+      const unsigned x = h16[w];
+      if (x & 0xffffu) atomicAdd(&bins[2 * w], x & 0xffffu);
+      if (x >> 16) atomicAdd(&bins[2 * w + 1], x >> 16);
+    }
+    __syncthreads();
+  }
+}
+
+static int hist2d_count_f32(smk_ctx *c, const float *d_vol, int nelts, size_t nvox, unsigned *d_bins) {
+  static bool attr[64] = {};  // per device
+  const int dev = c->device;
+  if (dev < 0 || dev >= 64 || !attr[dev]) {
+    PCHK(c, hipFuncSetAttribute((const void *)smk_k_hist2d_f32, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+    if (dev >= 0 && dev < 64) attr[dev] = true;
+  }
+  const size_t nchunks = (nvox + SMK_HIST_CHUNK - 1) / SMK_HIST_CHUNK;
+  const unsigned blocks = (unsigned)std::min<size_t>(nchunks, 256 * 4);
+  const int pairs = nelts == 2 && ((uintptr_t)d_vol & 7) == 0;  // (a float-aligned pointer into a larger buffer takes the scalar loads)
+  hipLaunchKernelGGL(smk_k_hist2d_f32, dim3(blocks), dim3(1024), 128 * 1024, c->stream, d_vol, nelts, pairs, nvox, d_bins);
+  PCHK(c, hipGetLastError());
+  return 0;
+}
+
+extern "C" int smk_hist2d_f32_device(smk_ctx *c, const void *d_vol, int nelts, int sx, int sy, int sz, unsigned char *hist) {
+  if (!c) return 1;
+  PCHK(c, hipSetDevice(c->device));
+  if (!d_vol || !hist || sx < 1 || sy < 1 || sz < 1) {
+    c->err = "smk_hist2d_f32_device: bad arguments";
+    return 1;
+  }
+  if (nelts < 2) {
+    c->err = "smk_hist2d_f32_device: sorry this type of histogram is not implemented (needs value and gradient channels)";
+    return 1;
+  }
+  unsigned *d_bins = nullptr;
+  PCHK(c, hipMalloc((void **)&d_bins, 65536 * sizeof(unsigned)));
+  int rc = 0;
+  std::vector<unsigned> counts(65536);
+  if (hipMemsetAsync(d_bins, 0, 65536 * sizeof(unsigned), c->stream) != hipSuccess ||
+      hist2d_count_f32(c, (const float *)d_vol, nelts, (size_t)sx * sy * sz, d_bins) ||
+      hipMemcpyAsync(counts.data(), d_bins, 65536 * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+      hipStreamSynchronize(c->stream) != hipSuccess) {
+    if (c->err.empty()) c->err = "smk_hist2d_f32_device: HIP error";
+    rc = 1;
+  }
+  (void)hipFree(d_bins);
+  if (rc) return rc;
   hist2d_finish(counts.data(), hist);
   return 0;
 }
