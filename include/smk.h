@@ -119,7 +119,9 @@ int smk_shard_order(smk_ctx *ctx, int *order_out /* nranks */);
  * doing exactly as VolumeRenderable::draw does, VolumeRenderable.cpp:50); premultiplied here. */
 int smk_set_tlut1d(smk_ctx *ctx, const float *rgba, int size);
 /* replaces NV20VolRen3D::loadDepTex x2 (NV20VolRen3D.cpp:1579-1622): deptex[sg][sv][RGBA8]
- * (gluvv.volren.deptex) and the optional third-axis table deptex2 (gluvv.volren.deptex2). */
+ * (gluvv.volren.deptex) and the optional third-axis table deptex2 (gluvv.volren.deptex2).  deptex2's alpha is multiplied
+ * in only under the third-axis data modes (VGH, V1GH, V2G, V2GH, V3, V3G, V4; NV20VolRen3D.cpp:686-693) and only on a
+ * volume of nelts >= 3: it is looked up at (third channel, fourth channel), the fourth being 0 when nelts is 3. */
 int smk_set_tf2d(smk_ctx *ctx, const unsigned char *deptex, const unsigned char *deptex2_or_null,
                  int sv, int sg);
 /* replaces TFWidgetRen::loadPtex for the dense table ptex[sh][sg][sv][RGBA8]

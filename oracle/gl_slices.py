@@ -139,9 +139,11 @@ def render_quad_slice(img, vol01, fsize, mv, frustum, znear, zfar, quad, alpha):
     eye = (M[:3, :3] @ q.T).T + M[:3, 3]
     clip = (P @ np.concatenate([eye, np.ones((4, 1))], axis=1).T).T
     w = clip[:, 3]
+    edge = np.zeros((height, width), bool)
+    if np.all(w <= 0):                       # wholly behind the eye: GL clips it away before the perspective division
+        return edge                          # (which would mirror it back onto the window)
     ndc = clip[:, :2] / w[:, None]
     win = np.stack([(ndc[:, 0] * .5 + .5) * width, (ndc[:, 1] * .5 + .5) * height], axis=1)
-    edge = np.zeros((height, width), bool)
     x0, x1 = int(np.floor(win[:, 0].min())), int(np.ceil(win[:, 0].max()))
     y0, y1 = int(np.floor(win[:, 1].min())), int(np.ceil(win[:, 1].max()))
     for j in range(max(y0, 0), min(y1 + 1, height)):
