@@ -23,8 +23,24 @@ extern "C" {
 
 typedef struct smk_ctx smk_ctx;
 
-/* voxel storage handed over by the caller */
-typedef enum { SMK_U8 = 0, SMK_F32 = 1 } smk_dtype;
+/* voxel storage handed over by the caller.
+ * SMK_U16: [z][y][x][nelts] uint16_t in host byte order, nelts 1..3 (4 is refused: "4-channel u16 voxels"), for the 12 to
+ * 16-bit integer data of CT, MR and most instruments.  The reference quantises such bricks to bytes (MetaVolume.cpp:709-889,
+ * quantize<T>); here they are stored in the 8 bytes of a u8 voxel,
+ *     uint2 { c0 | c1 << 16,   n0 | n1 << 8 | n2 << 16 | q8(c2) << 24 },   q8(c) = (c * 255 + 32767) / 65535,
+ * so channels 0 and 1 -- the two axes of the 2-D table -- keep all 16 bits, and channel 2 (the second derivative / third
+ * table axis of the VGH modes) is kept at the nearest 8-bit unorm: THAT IS THE LIMIT OF THE TYPE.  A missing channel is 0,
+ * missing normals are (128, 128, 128).  A sample interpolates the raw integers as floats and scales once:
+ * ch0 = T0 / 65535, ch1 = T1 / 65535, ch2 = T2 / 255; everything after the channel values is the u8 / f32 code.  Normals are
+ * [z][y][x][3] u8 as for the other types.  Everything a u8 volume does, it does: bricked and shuffled uploads, shards, time
+ * steps (a ring is of one type: a step of another dtype is refused, as a changed geometry is), brick flags, all data modes
+ * of at most three channels, perturbation, shadows under the two marches in both looks, smk_render_slice, the clip-plane
+ * widget's slice, smk_count_samples.  The gather kernel renders every such frame; the slice-ring kernel has the plain
+ * instances and the eye pass of frames with shadows under look 0 -- bit-identical frames -- and declines, with the reason,
+ * frames with the host's scene depth, the NV20 look, and NV20 shading under the 3-D table with brick flags on its 10+2-wave
+ * shapes (those instances would need scratch): auto mode then renders on the gather kernel, a forced "kernel" 2 fails.
+ * Refused with the reason: the column-stream kernel ("kernel" 3), shadows with option "shadow_march" 0 or "shadow_fused". */
+typedef enum { SMK_U8 = 0, SMK_F32 = 1, SMK_U16 = 2 } smk_dtype;
 
 /* gluvvDataMode, same order and meaning (gluvv.h:221-235) */
 typedef enum {
@@ -55,7 +71,7 @@ typedef struct {
   float xfSize, yfSize, zfSize; /* extent in volume space                                  */
   int xiPos, yiPos, ziPos;      /* voxel origin inside the whole volume                    */
   float xfPos, yfPos, zfPos;    /* origin in volume space                                  */
-  const void *data;             /* currentData: [z][y][x][nelts], u8 or f32                */
+  const void *data;             /* currentData: [z][y][x][nelts], u8, f32 or u16           */
   const unsigned char *grad;    /* currentGrad: [z][y][x][3] scale-biased normals, or NULL */
 } smk_volume_desc;
 
@@ -441,9 +457,10 @@ int smk_exchange_frame_local_depth(smk_exchange *const *all, int nranks, int slo
 
 /* data prep on the GPU (genVGH/main.cpp:56-182, VectorMath.h:874-899,
  * 1133-1148, 1217-1281).  All pointers are DEVICE pointers.
- *   scalar  [z][y][x] u8 or f32      -> vgh_u8 [z][y][x][3] (quantised as makeVGH) and/or
+ *   scalar  [z][y][x] u8, f32 or u16 -> vgh_u8 [z][y][x][3] (quantised as makeVGH) and/or
  *                                       vgh_f32 [z][y][x][3] in [0,1] (unquantised variant)
- *   vgh_u8                           -> normals [z][y][x][3] (derivative3DVGH+[blurV3D]+scalebiasN) */
+ *   vgh_u8                           -> normals [z][y][x][3] (derivative3DVGH+[blurV3D]+scalebiasN)
+ * A SMK_U16 scalar gives, in both outputs, the bits of the SMK_F32 call on the same values converted with (float)v. */
 int smk_make_vgh_device(smk_ctx *ctx, const void *d_scalar, smk_dtype dtype, int sx, int sy,
                         int sz, int compat, void *d_vgh_u8_or_null, void *d_vgh_f32_or_null);
 int smk_normals_vgh_device(smk_ctx *ctx, const void *d_vgh_u8, int nelts, int sx, int sy, int sz,
@@ -489,6 +506,12 @@ int smk_merge_fields_f32_device(smk_ctx *ctx, const void *d_fields_f32, int nf, 
  * finished as smk_hist2d_device's (log scale, float bins that stop at 2^24); hist is 65536 bytes in HOST memory and
  * nelts < 2 is refused as there.  d_vol_f32 needs float alignment only.  The reference has no float pipeline. */
 int smk_hist2d_f32_device(smk_ctx *ctx, const void *d_vol_f32, int nelts, int sx, int sy, int sz, unsigned char *hist);
+/* the bridge from the float prep entries (smk_make_vgh_device's vgh_f32, smk_merge_fields_f32_device) to SMK_U16 voxels (no
+ * reference equivalent: the reference quantises to bytes): n_values floats -> n_values uint16_t, DEVICE pointers, on the
+ * context's stream, synchronous like its siblings.  Per value t = v * 65535.0f (one fp32 multiply): NaN or t < 0 -> 0,
+ * t >= 65535 -> 65535, otherwise (uint16_t)(int)(t + 0.5f) -- one fp32 add, then truncation.  Plain fp32 in that order, so a
+ * float32 restatement gives the same bits. */
+int smk_quantize_u16_device(smk_ctx *ctx, const void *d_f32, long long n_values, void *d_u16);
 /* synthetic scalar test volumes generated on the GPU (u8, [z][y][x]):
  *   kind 1 = the reference's own generator: `genvol -spheres 4 -p 10 -pscale .7 -pwrap 3 3 3 -pabs -blur
  *            -bw 1 1 1 .7` with srand(seed) (genvol/main.cpp:153-165, 212-256, 334-430; perlin.c; script

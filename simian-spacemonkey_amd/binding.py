@@ -20,7 +20,7 @@ ABI_SYMBOLS = [
     "smk_set_tf2d", "smk_set_tf3d", "smk_set_camera", "smk_set_shading", "smk_set_sampling",
     "smk_set_perturb", "smk_set_blend", "smk_set_shadow", "smk_get_shadowcoef", "smk_get_light_buffer", "smk_get_brick_flags", "smk_render", "smk_render_device", "smk_composite_over_device",
     "smk_make_vgh_device", "smk_normals_vgh_device", "smk_synth_volume_device",
-    "smk_normals_f32_device", "smk_merge_fields_f32_device", "smk_hist2d_f32_device",
+    "smk_normals_f32_device", "smk_merge_fields_f32_device", "smk_hist2d_f32_device", "smk_quantize_u16_device",
     "smk_get_raycoef", "smk_set_option", "smk_last_frame_info", "smk_get_stat", "smk_get_trace", "smk_get_tf2d_effective",
     "smk_timing_reset", "smk_timing_read", "smk_last_frame_id", "smk_frame_failed",
     "smk_exchange_unique_id", "smk_exchange_create", "smk_exchange_connect_local", "smk_exchange_destroy",
@@ -184,6 +184,7 @@ def load_library():
     L.smk_normals_f32_device.argtypes = L.smk_normals_vgh_device.argtypes
     L.smk_merge_fields_f32_device.argtypes = L.smk_merge_fields_device.argtypes
     L.smk_hist2d_f32_device.argtypes = L.smk_hist2d_device.argtypes
+    L.smk_quantize_u16_device.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]
     L.smk_synth_volume_device.argtypes = [C.c_void_p, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_int,
                                           C.c_void_p]
     L.smk_get_raycoef.argtypes = [C.c_void_p, P(RayCoef)]
@@ -301,7 +302,10 @@ class Renderer:
                 g = np.ascontiguousarray(grad[z0:z0 + bz, y0:y0 + by, x0:x0 + bx])
                 keep.append(g)
                 d.grad = _ptr(g)
-        dt = 0 if data.dtype == np.uint8 else 1
+        # smk_dtype: SMK_U8, SMK_F32, SMK_U16 -- any other array would be reinterpreted, so it is refused
+        dt = {np.dtype(np.uint8): 0, np.dtype(np.float32): 1, np.dtype(np.uint16): 2}.get(data.dtype)
+        if dt is None:
+            raise TypeError("volume data must be uint8, float32 or uint16, not %s" % data.dtype)
         return descs, keep, ne, dt
 
     @staticmethod
@@ -317,7 +321,7 @@ class Renderer:
         return d
 
     def upload_volume(self, data, grad=None, fsize=None, grid=(1, 1, 1), dmode="VGH"):
-        """data [nz][ny][nx][nelts] u8/f32 (numpy); split into `grid` bricks the way
+        """data [nz][ny][nx][nelts] u8/f32/u16 (numpy; any other dtype: TypeError); split into `grid` bricks the way
         MetaVolume::brick does and handed over brick by brick."""
         descs, keep, ne, dt = self._host_bricks(data, grad, fsize, grid)
         self._ck(self.L.smk_upload_volume(self.ctx, descs, len(descs), ne, dt, GDM[dmode]))
@@ -643,6 +647,7 @@ class Renderer:
 
     # -- GPU data prep
     def make_vgh_device(self, d_scalar, dtype, dims, compat, d_vgh_u8=None, d_vgh_f32=None):
+        """dtype: 0 u8, 1 f32, 2 u16 scalar [z][y][x]; a u16 scalar gives the f32 call's bits on the same values"""
         sx, sy, sz = dims
         self._ck(self.L.smk_make_vgh_device(self.ctx, d_scalar, dtype, sx, sy, sz, int(compat),
                                             d_vgh_u8, d_vgh_f32))
@@ -697,6 +702,10 @@ class Renderer:
         out = np.zeros((256, 256), np.uint8)
         self._ck(self.L.smk_hist2d_f32_device(self.ctx, d_vol_f32, nelts, sx, sy, sz, _ptr(out)))
         return out
+
+    def quantize_u16_device(self, d_f32, n_values, d_u16):
+        """n_values device floats -> uint16 voxels channels: (uint16)(int)(v * 65535 + .5), NaN and negatives 0, >= 1 65535"""
+        self._ck(self.L.smk_quantize_u16_device(self.ctx, d_f32, int(n_values), d_u16))
 
     def synth_volume_device(self, kind, seed, dims, d_out):
         sx, sy, sz = dims

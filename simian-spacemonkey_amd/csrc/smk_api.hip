@@ -205,6 +205,13 @@ __global__ void smk_k_pack(const void *src, const unsigned char *grad, int bx, i
     uint32_t d = 0;
     for (int e = 0; e < nelts; ++e) d |= (uint32_t)s[e] << (8 * e);
     ((uint2 *)dst)[o] = make_uint2(d, nb);
+  } else if (DT == 2) {
+    // SMK_U16 (smk.h): channels 0 and 1 whole, channel 2 as its nearest 8-bit unorm in the byte the normal leaves free
+    const unsigned short *s = (const unsigned short *)src + t * nelts;
+    uint32_t d = s[0];
+    if (nelts > 1) d |= (uint32_t)s[1] << 16;
+    if (nelts > 2) nb |= (((uint32_t)s[2] * 255u + 32767u) / 65535u) << 24;
+    ((uint2 *)dst)[o] = make_uint2(d, nb);
   } else {
     const float *s = (const float *)src + t * nelts;
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -241,7 +248,9 @@ int smk_volume_geometry(smk_ctx *c, const char *who, const smk_volume_desc *b, i
                         smk_datamode dmode, SmkVolGeom &g) {
   if (!b || nb <= 0) FAIL(c, "%s: no bricks", who);
   if (nelts < 1 || nelts > 4) FAIL(c, "%s: nelts %d not in 1..4", who, nelts);
-  if (dtype != SMK_U8 && dtype != SMK_F32) FAIL(c, "%s: bad dtype", who);
+  if (dtype != SMK_U8 && dtype != SMK_F32 && dtype != SMK_U16) FAIL(c, "%s: bad dtype", who);
+  if (dtype == SMK_U16 && nelts == 4)
+    FAIL(c, "%s: 4-channel u16 voxels do not fit the 8-byte packed voxel (nelts 1..3; smk.h SMK_U16)", who);
   g = SmkVolGeom();
   g.dtype = dtype;
   g.nelts = nelts;
@@ -281,7 +290,7 @@ int smk_volume_geometry(smk_ctx *c, const char *who, const smk_volume_desc *b, i
   // along both axes that can be its contiguous one (x, and y in the x-major copy) -- one more halo
   // voxel where the volume has one, else a pad column nobody samples (index N: the texel pair of a
   // clamped coordinate ends at N-1)
-  if (dtype == SMK_U8)
+  if (dtype != SMK_F32)
     for (int a = 0; a < 2; ++a)
       if (g.D[a] & 1) {
         if (g.O[a] + g.D[a] < N[a]) ++g.D[a];
@@ -289,7 +298,7 @@ int smk_volume_geometry(smk_ctx *c, const char *who, const smk_volume_desc *b, i
         else { ++g.D[a]; g.padded = true; }
       }
   const size_t nst = (size_t)g.D[0] * g.D[1] * g.D[2];
-  g.vox_bytes = nst * (dtype == SMK_U8 ? 8 : 16);
+  g.vox_bytes = nst * (dtype == SMK_F32 ? 16 : 8);
   g.nrm_bytes = dtype == SMK_F32 && nelts == 4 && any_grad ? nst * 4 : 0;
   for (int a = 0; a < 3; ++a) g.nbr[a] = (g.D[a] - 1) / (1 << SMK_BRICK_LOG2) + 1;
   g.mm_bytes = (size_t)g.nbr[0] * g.nbr[1] * g.nbr[2] * sizeof(float4);
@@ -316,7 +325,7 @@ void smk_set_geometry(smk_ctx *c, const SmkVolGeom &g) {
 
 int smk_alloc_step(smk_ctx *c, const SmkVolGeom &g, TimeStep &T) {
   if (!T.vox) {
-    HIPCHK(c, hipMalloc(&T.vox, g.vox_bytes + 16));  // (+16: the gather kernel reads u8 voxels in pairs, smk_load_pair_u8)
+    HIPCHK(c, hipMalloc(&T.vox, g.vox_bytes + 16));  // (+16: the gather kernel reads 8-byte voxels in pairs, smk_load_pair_u8 / _u16)
     if (g.padded) HIPCHK(c, hipMemset(T.vox, 0, g.vox_bytes));
   }
   if (g.nrm_bytes && !T.nrm) HIPCHK(c, hipMalloc((void **)&T.nrm, g.nrm_bytes));
@@ -330,7 +339,7 @@ int smk_alloc_step(smk_ctx *c, const SmkVolGeom &g, TimeStep &T) {
 int smk_pack_step(smk_ctx *c, const char *who, const SmkVolGeom &g, const smk_volume_desc *b, int nb, bool on_device, TimeStep &T,
                   hipStream_t s) {
   const int nelts = g.nelts;
-  const size_t esz = g.dtype == SMK_U8 ? 1 : 4;
+  const size_t esz = g.dtype == SMK_U8 ? 1 : g.dtype == SMK_U16 ? 2 : 4;
   const bool n_in_w = g.dtype == SMK_F32 && nelts <= 3;
   void *d_stage = nullptr;
   unsigned char *d_gstage = nullptr;
@@ -371,6 +380,10 @@ int smk_pack_step(smk_ctx *c, const char *who, const SmkVolGeom &g, const smk_vo
         hipLaunchKernelGGL(smk_k_pack<0>, dim3(blocks), dim3(256), 0, s, src, gsrc, k.xiSize, k.yiSize, cz, nelts,
                            k.xiPos, k.yiPos, k.ziPos + z0, g.O[0], g.O[1], g.O[2], g.D[0], g.D[1], g.D[2],
                            T.vox, T.nrm, 0);
+      else if (g.dtype == SMK_U16)
+        hipLaunchKernelGGL(smk_k_pack<2>, dim3(blocks), dim3(256), 0, s, src, gsrc, k.xiSize, k.yiSize, cz, nelts,
+                           k.xiPos, k.yiPos, k.ziPos + z0, g.O[0], g.O[1], g.O[2], g.D[0], g.D[1], g.D[2],
+                           T.vox, T.nrm, 0);
       else
         hipLaunchKernelGGL(smk_k_pack<1>, dim3(blocks), dim3(256), 0, s, src, gsrc, k.xiSize, k.yiSize, cz, nelts,
                            k.xiPos, k.yiPos, k.ziPos + z0, g.O[0], g.O[1], g.O[2], g.D[0], g.D[1], g.D[2],
@@ -382,7 +395,7 @@ int smk_pack_step(smk_ctx *c, const char *who, const SmkVolGeom &g, const smk_vo
   if (d_stage) (void)hipFree(d_stage);
   if (d_gstage) (void)hipFree(d_gstage);
   // value ranges of the 8x8x8-cell bricks (smk_bricks.hip): what the brick flags of every later table are made from
-  HIPCHK(c, smk_bricks_minmax(T.vox, g.dtype == SMK_U8 ? 0 : 1, g.D, g.nbr, T.mm, s));
+  HIPCHK(c, smk_bricks_minmax(T.vox, g.dtype, g.D, g.nbr, T.mm, s));
   if (!s) HIPCHK(c, hipDeviceSynchronize());
   T.vox_x_valid = false;
   return 0;
@@ -1396,7 +1409,7 @@ int smk_make_xmajor_copy(smk_ctx *c) {
   c->d_vox_x = T.vox_x;
   if (smk_step_wait_ready(c, c->stream)) return 1;
   dim3 grid((c->D[0] + 31) / 32, (c->D[1] + 31) / 32, c->D[2]);
-  if (c->dtype == SMK_U8)
+  if (c->dtype != SMK_F32)  // (by voxel size: u8 and u16 voxels are 8 bytes)
     hipLaunchKernelGGL(smk_k_xmajor<uint2>, grid, dim3(256), 0, c->stream, (const uint2 *)c->d_vox, (uint2 *)c->d_vox_x,
                        c->D[0], c->D[1], c->D[2]);
   else
@@ -1471,7 +1484,7 @@ __global__ __launch_bounds__(256) void smk_k_render_slice(const RenderParams P, 
   auto at = [&](int x, int y, int z) -> float { return smk_load_corner<DT>(P, ((size_t)z * Dy + y) * Dx + x).c0; };
   float I = smk_lerp(smk_lerp(smk_lerp(at(x0, y0, z0), at(x1, y0, z0), fx), smk_lerp(at(x0, y1, z0), at(x1, y1, z0), fx), fy),
                      smk_lerp(smk_lerp(at(x0, y0, z1), at(x1, y0, z1), fx), smk_lerp(at(x0, y1, z1), at(x1, y1, z1), fx), fy), fz);
-  if (DT == 0) I *= SMK_INV255;
+  if (DT != 1) I *= SmkScale<DT>::s01;
   I = smk_sat(I);
   const float sa = smk_sat(I * Q.alpha);
   float4 D = fb[(size_t)j * P.W + i];
@@ -1510,6 +1523,7 @@ extern "C" int smk_render_slice_device(smk_ctx *c, const float quad[4][3], float
   dim3 grid((c->W + 15) / 16, (c->H + 15) / 16);
   if (smk_step_wait_ready(c, s)) return 1;
   if (c->dtype == SMK_U8) hipLaunchKernelGGL(smk_k_render_slice<0>, grid, dim3(256), 0, s, P, Q, (float4 *)d_rgba);
+  else if (c->dtype == SMK_U16) hipLaunchKernelGGL(smk_k_render_slice<2>, grid, dim3(256), 0, s, P, Q, (float4 *)d_rgba);
   else hipLaunchKernelGGL(smk_k_render_slice<1>, grid, dim3(256), 0, s, P, Q, (float4 *)d_rgba);
   HIPCHK(c, hipGetLastError());
   return smk_step_mark_used(c, s);

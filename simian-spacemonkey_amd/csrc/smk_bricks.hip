@@ -46,6 +46,10 @@ __global__ __launch_bounds__(256) void smk_k_brick_minmax(const void *vox, int D
       const uint32_t d = ((const uint2 *)vox)[o].x;
       v = (float)(d & 0xffu) * SMK_INV255;
       g = (float)((d >> 8) & 0xffu) * SMK_INV255;
+    } else if (DT == 2) {  // (u16: the 16-bit first two channels, scaled as a sample scales them)
+      const uint32_t d = ((const uint2 *)vox)[o].x;
+      v = (float)(d & 0xffffu) * SMK_INV65535;
+      g = (float)(d >> 16) * SMK_INV65535;
     } else {
       const float4 f = ((const float4 *)vox)[o];
       v = f.x;
@@ -161,6 +165,7 @@ hipError_t smk_bricks_minmax(const void *vox, int dtype, const int D[3], const i
   const long long nbricks = (long long)nb[0] * nb[1] * nb[2];
   const unsigned blocks = (unsigned)((nbricks + 3) / 4);
   if (dtype == 0) hipLaunchKernelGGL(smk_k_brick_minmax<0>, dim3(blocks), dim3(256), 0, s, vox, D[0], D[1], D[2], nb[0], nb[1], nb[2], mm);
+  else if (dtype == 2) hipLaunchKernelGGL(smk_k_brick_minmax<2>, dim3(blocks), dim3(256), 0, s, vox, D[0], D[1], D[2], nb[0], nb[1], nb[2], mm);
   else hipLaunchKernelGGL(smk_k_brick_minmax<1>, dim3(blocks), dim3(256), 0, s, vox, D[0], D[1], D[2], nb[0], nb[1], nb[2], mm);
   return hipGetLastError();
 }

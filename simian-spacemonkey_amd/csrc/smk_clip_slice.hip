@@ -102,7 +102,7 @@ __global__ __launch_bounds__(256) void smk_k_clip_slice(const RenderParams P, co
   const SmkCorner k010 = smk_load_corner<DT>(P, r10 + x0), k110 = smk_load_corner<DT>(P, r10 + x1);
   const SmkCorner k001 = smk_load_corner<DT>(P, r01 + x0), k101 = smk_load_corner<DT>(P, r01 + x1);
   const SmkCorner k011 = smk_load_corner<DT>(P, r11 + x0), k111 = smk_load_corner<DT>(P, r11 + x1);
-  const float sc = DT == 0 ? SMK_INV255 : 1.0f;
+  const float sc = SmkScale<DT>::s01, sch = SmkScale<DT>::s23;
   const float c0 = smk_sat(SMK_TRI(c0) * sc);
   float4 S;
   if (LOOK == CS_NV20) {
@@ -113,7 +113,7 @@ __global__ __launch_bounds__(256) void smk_k_clip_slice(const RenderParams P, co
     float r = c0, g = 0.0f, b = c0;
     if (LOOK == CS_R8K_4B) {
       g = smk_sat(SMK_TRI(c1) * sc);
-      b = smk_sat(SMK_TRI(c2) * sc);
+      b = smk_sat(SMK_TRI(c2) * sch);
     } else if (LOOK == CS_R8K_2B) {  // GL_LUMINANCE8_ALPHA8: (L, L, L, A), green <- alpha
       g = smk_sat(SMK_TRI(c1) * sc);
     } else {  // GL_ALPHA8: (0, 0, 0, A), green <- alpha
@@ -294,6 +294,7 @@ int smk_clip_slice_stage(smk_ctx *c, const RenderParams &P, hipStream_t s) {
   Q.blend_max = blend_max ? 1 : 0;
   const dim3 grid((Q.x1 - Q.x0) / 16 + 1, (Q.y1 - Q.y0) / 16 + 1);
   if (c->dtype == SMK_U8) launch_look<0>(look, grid, s, P, Q, P.out);
+  else if (c->dtype == SMK_U16) launch_look<2>(look, grid, s, P, Q, P.out);
   else launch_look<1>(look, grid, s, P, Q, P.out);
   HIPCHK(c, hipGetLastError());
   return 0;

@@ -41,6 +41,7 @@ static const char *cols_refusal(const RenderParams &P, int dtype, int tf_mode) {
   if (P.depth) return "first-hit depth requested";
   if (P.cplane_on) return "free clip plane";
   if (dtype == 1 && !P.n_in_w) return "4-channel f32 voxels";
+  if (dtype == 2) return "u16 voxels (the column-stream kernel has no u16 instance)";
   if (P.rc.nplanes <= 0) return "no planes";
   for (int a = 0; a < 3; ++a) {
     if (P.D[a] < 2 || P.N[a] < 2) return "volume thinner than 2 voxels";

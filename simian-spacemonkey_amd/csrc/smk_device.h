@@ -16,6 +16,7 @@
 #include "smk_internal.h"
 
 #define SMK_INV255 (1.0f / 255.0f)
+#define SMK_INV65535 (1.0f / 65535.0f)
 #define SMK_RANGE_EPS 0.0078125f  // voxels; 30 x the fp32 rounding of coordinates up to 4096 (half an ulp = 2.4e-4)
 
 __device__ __forceinline__ float smk_lerp(float a, float b, float f) { return __fmaf_rn(f, b - a, a); }
@@ -47,11 +48,22 @@ __device__ __forceinline__ void smk_lin_repeat(float x, int n, int &i0, int &i1,
 
 __device__ __forceinline__ float smk_ub(uint32_t v, int k) { return (float)((v >> (8 * k)) & 0xffu); }
 
-// one voxel corner: 4 channels (raw: u8 as 0..255 floats, f32 as is) + packed normal bits
+// one voxel corner: 4 channels (raw: u8 as 0..255 floats, u16 as 0..65535 floats -- its third channel 0..255 --, f32 as
+// is) + packed normal bits
 struct SmkCorner {
   float c0, c1, c2, c3;
   uint32_t nb;
 };
+
+// u16 voxels (SMK_U16, smk.h): uint2 {c0 | c1 << 16, n0 | n1 << 8 | n2 << 16 | q8(c2) << 24}.  The normal bits sit where the
+// u8 voxel has them (smk_nrm looks at the low three bytes only), the third channel's 8 bits ride in the spare byte
+__device__ __forceinline__ void smk_decode_u16(uint2 v, SmkCorner &k) {
+  k.c0 = (float)(v.x & 0xffffu);
+  k.c1 = (float)(v.x >> 16);
+  k.c2 = (float)(v.y >> 24);
+  k.c3 = 0.0f;
+  k.nb = v.y;
+}
 
 template <int DT>
 __device__ __forceinline__ SmkCorner smk_load_corner(const RenderParams &P, size_t idx) {
@@ -63,6 +75,8 @@ __device__ __forceinline__ SmkCorner smk_load_corner(const RenderParams &P, size
     k.c2 = smk_ub(v.x, 2);
     k.c3 = smk_ub(v.x, 3);
     k.nb = v.y;
+  } else if (DT == 2) {
+    smk_decode_u16(((const uint2 *)P.vox)[idx], k);
   } else {
     float4 v = ((const float4 *)P.vox)[idx];
     k.c0 = v.x;
@@ -93,6 +107,21 @@ __device__ __forceinline__ void smk_load_pair_u8(const RenderParams &P, size_t i
   b.c0 = smk_ub(w.x, 0); b.c1 = smk_ub(w.x, 1); b.c2 = smk_ub(w.x, 2); b.c3 = smk_ub(w.x, 3);
   b.nb = w.y;
 }
+
+// ... and so are u16 voxels
+__device__ __forceinline__ void smk_load_pair_u16(const RenderParams &P, size_t i0, size_t i1, SmkCorner &a, SmkCorner &b) {
+  uint4 v;
+  __builtin_memcpy(&v, reinterpret_cast<const char *>(P.vox) + i0 * 8, 16);
+  smk_decode_u16(make_uint2(v.x, v.y), a);
+  uint2 w = make_uint2(v.z, v.w);
+  if (i1 != i0 + 1) w = ((const uint2 *)P.vox)[i1];
+  smk_decode_u16(w, b);
+}
+// what turns an interpolated raw channel into its value: channel 0 / 1, and channel 2 / 3 (u16 keeps 8 bits of those)
+template <int DT> struct SmkScale {
+  static constexpr float s01 = DT == 0 ? SMK_INV255 : DT == 2 ? SMK_INV65535 : 1.0f;
+  static constexpr float s23 = DT == 1 ? 1.0f : SMK_INV255;
+};
 
 #define SMK_TRI(field)                                                                  \
   smk_lerp(smk_lerp(smk_lerp(k000.field, k100.field, fx), smk_lerp(k010.field, k110.field, fx), fy), \

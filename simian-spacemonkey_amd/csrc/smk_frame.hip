@@ -117,7 +117,7 @@ static int frame_open(smk_ctx *c, RenderParams &P, void *d_rgba, void *d_depth) 
   P.depth = (float *)d_depth;
   // algorithmic bytes: every stored voxel once + TF + RGBA f32 frame
   size_t nst = (size_t)c->D[0] * c->D[1] * c->D[2];
-  double bv = c->dtype == SMK_U8 ? (double)c->nelts : 4.0 * c->nelts;
+  double bv = c->dtype == SMK_U8 ? (double)c->nelts : c->dtype == SMK_U16 ? 2.0 * c->nelts : 4.0 * c->nelts;
   if (smk_shade_kind(c)) bv += 3.0;
   double tfb = c->tf_mode == 0 ? 16.0 * c->tlut_size
                : c->tf_mode == 1 ? 4.0 * c->sv * c->sg * (P.third_axis ? 2 : 1)

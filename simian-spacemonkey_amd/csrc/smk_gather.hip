@@ -1,6 +1,6 @@
 // smk_gather.hip -- kernel G: the generic ray-marcher.  One lane = one ray; voxel corners,
 // transfer-function texels and noise texels are gathered straight from HBM/L2 (no staging).
-// It covers every mode of the C ABI (u8/f32, 1-/2-/3-D classification, both Phong variants,
+// It covers every mode of the C ABI (u8/f32/u16, 1-/2-/3-D classification, both Phong variants,
 // perturbation, sharded regions) and is the fallback the slab-staged kernel (smk_slab.hip)
 // defers to.  Replaces the per-slice polygon loop + fragment pipeline of
 // VolumeRenderer::render3DVA (VolumeRenderer.cpp:507-741) / NV20VolRen3D::render3DVA (:852-1083).
@@ -166,6 +166,11 @@ __global__ __launch_bounds__(256) void smk_k_gather(const RenderParams P) {
       smk_load_pair_u8(P, r10 + c0, r10 + c1, k010, k110);
       smk_load_pair_u8(P, r01 + c0, r01 + c1, k001, k101);
       smk_load_pair_u8(P, r11 + c0, r11 + c1, k011, k111);
+    } else if constexpr (DT == 2) {
+      smk_load_pair_u16(P, r00 + c0, r00 + c1, k000, k100);
+      smk_load_pair_u16(P, r10 + c0, r10 + c1, k010, k110);
+      smk_load_pair_u16(P, r01 + c0, r01 + c1, k001, k101);
+      smk_load_pair_u16(P, r11 + c0, r11 + c1, k011, k111);
     } else {
       k000 = smk_load_corner<DT>(P, r00 + c0); k100 = smk_load_corner<DT>(P, r00 + c1);
       k010 = smk_load_corner<DT>(P, r10 + c0); k110 = smk_load_corner<DT>(P, r10 + c1);
@@ -173,12 +178,12 @@ __global__ __launch_bounds__(256) void smk_k_gather(const RenderParams P) {
       k011 = smk_load_corner<DT>(P, r11 + c0); k111 = smk_load_corner<DT>(P, r11 + c1);
     }
 
-    const float sc = DT == 0 ? SMK_INV255 : 1.0f;
+    const float sc = SmkScale<DT>::s01, sch = SmkScale<DT>::s23;  // (u16: 16 bits of channels 0 / 1, 8 of channel 2)
     float ch0 = SMK_TRI(c0), ch1 = 0.f, ch2 = 0.f, ch3 = 0.f;
-    if (DT == 0) ch0 *= sc;
+    if (DT != 1) ch0 *= sc;
     if (TF != 0 || SH != 0) {
       ch1 = SMK_TRI(c1);
-      if (DT == 0) ch1 *= sc;
+      if (DT != 1) ch1 *= sc;
     }
     float4 col;
     if (TF == 2 && P.tf_occ) {
@@ -192,10 +197,10 @@ __global__ __launch_bounds__(256) void smk_k_gather(const RenderParams P) {
     }
     if (TF == 2 || (TF == 1 && P.third_axis)) {
       ch2 = SMK_TRI(c2);
-      if (DT == 0) ch2 *= sc;
+      if (DT != 1) ch2 *= sch;
       if (P.nelts == 4) {
         ch3 = SMK_TRI(c3);
-        if (DT == 0) ch3 *= sc;
+        if (DT != 1) ch3 *= sch;
       }
     }
 
@@ -304,6 +309,7 @@ hipError_t smk_launch_gather(const RenderParams &P, int dtype, int tf_mode, int 
   if (dtype == D && tf_mode == T && shade_kind == S) return launch<D, T, S, true, true>(P, s);
     CASE(0, 1, 0) CASE(0, 1, 2) CASE(0, 2, 0) CASE(0, 2, 2)
     CASE(1, 1, 0) CASE(1, 1, 2) CASE(1, 2, 0) CASE(1, 2, 2)
+    CASE(2, 1, 0) CASE(2, 1, 2) CASE(2, 2, 0) CASE(2, 2, 2)
 #undef CASE
     return hipErrorInvalidValue;
   }
@@ -312,6 +318,7 @@ hipError_t smk_launch_gather(const RenderParams &P, int dtype, int tf_mode, int 
   if (dtype == D && tf_mode == T && shade_kind == S) return launch<D, T, S, true>(P, s);
     CASE(0, 1, 0) CASE(0, 1, 1) CASE(0, 2, 0) CASE(0, 2, 1)
     CASE(1, 1, 0) CASE(1, 1, 1) CASE(1, 2, 0) CASE(1, 2, 1)
+    CASE(2, 1, 0) CASE(2, 1, 1) CASE(2, 2, 0) CASE(2, 2, 1)
 #undef CASE
     return hipErrorInvalidValue;
   }
@@ -319,6 +326,7 @@ hipError_t smk_launch_gather(const RenderParams &P, int dtype, int tf_mode, int 
   if (dtype == D && tf_mode == T && shade_kind == S) return launch<D, T, S>(P, s);
   CASE(0, 0, 0) CASE(0, 1, 0) CASE(0, 1, 1) CASE(0, 1, 2) CASE(0, 2, 0) CASE(0, 2, 1) CASE(0, 2, 2)
   CASE(1, 0, 0) CASE(1, 1, 0) CASE(1, 1, 1) CASE(1, 1, 2) CASE(1, 2, 0) CASE(1, 2, 1) CASE(1, 2, 2)
+  CASE(2, 0, 0) CASE(2, 1, 0) CASE(2, 1, 1) CASE(2, 1, 2) CASE(2, 2, 0) CASE(2, 2, 1) CASE(2, 2, 2)
 #undef CASE
   return hipErrorInvalidValue;
 }

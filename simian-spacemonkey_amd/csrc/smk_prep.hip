@@ -55,7 +55,7 @@ struct VghStats {  // ordered-int encoded
 
 template <int DT>
 __device__ __forceinline__ float ld(const void *d, size_t i) {
-  return DT == 0 ? (float)((const unsigned char *)d)[i] : ((const float *)d)[i];
+  return DT == 0 ? (float)((const unsigned char *)d)[i] : DT == 2 ? (float)((const unsigned short *)d)[i] : ((const float *)d)[i];
 }
 
 // un-normalised central differences (genVGH/main.cpp:86-88); u8 differences are exact ints
@@ -230,6 +230,7 @@ extern "C" int smk_make_vgh_device(smk_ctx *c, const void *d, smk_dtype dt, int 
   size_t n = (size_t)sx * sy * sz;
   unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 256 * 16);
   if (dt == SMK_U8) hipLaunchKernelGGL(smk_k_vgh_stats<0>, dim3(blocks), dim3(256), 0, c->stream, d, sx, sy, sz, compat, st);
+  else if (dt == SMK_U16) hipLaunchKernelGGL(smk_k_vgh_stats<2>, dim3(blocks), dim3(256), 0, c->stream, d, sx, sy, sz, compat, st);
   else hipLaunchKernelGGL(smk_k_vgh_stats<1>, dim3(blocks), dim3(256), 0, c->stream, d, sx, sy, sz, compat, st);
   PCHK(c, hipGetLastError());
   PCHK(c, hipStreamSynchronize(c->stream));
@@ -243,9 +244,43 @@ extern "C" int smk_make_vgh_device(smk_ctx *c, const void *d, smk_dtype dt, int 
   if (dt == SMK_U8)
     hipLaunchKernelGGL(smk_k_vgh_quant<0>, dim3(blocks), dim3(256), 0, c->stream, d, sx, sy, sz, compat, dmin, dmax,
                        gmin, gmax, hmin, hmax, (unsigned char *)o8, (float *)of);
+  else if (dt == SMK_U16)  // ((float)v of a 16-bit integer is exact: the f32 instance's arithmetic on the same values)
+    hipLaunchKernelGGL(smk_k_vgh_quant<2>, dim3(blocks), dim3(256), 0, c->stream, d, sx, sy, sz, compat, dmin, dmax,
+                       gmin, gmax, hmin, hmax, (unsigned char *)o8, (float *)of);
   else
     hipLaunchKernelGGL(smk_k_vgh_quant<1>, dim3(blocks), dim3(256), 0, c->stream, d, sx, sy, sz, compat, dmin, dmax,
                        gmin, gmax, hmin, hmax, (unsigned char *)o8, (float *)of);
+  PCHK(c, hipGetLastError());
+  PCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// ------------------------------------------------------------------------------- floats -> u16 voxels
+
+// smk_quantize_u16_device (smk.h): t = v * 65535 (one fp32 multiply); NaN or t < 0 -> 0, t >= 65535 -> 65535, else
+// (uint16)(int)(t + 0.5f) -- one fp32 add, then truncation
+__global__ __launch_bounds__(256) void smk_k_quantize_u16(const float *in, size_t n, unsigned short *out) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const float t = in[i] * 65535.0f;
+    unsigned short q;
+    if (!(t >= 0.0f)) q = 0;
+    else if (t >= 65535.0f) q = 65535;
+    else q = (unsigned short)(int)(t + 0.5f);
+    out[i] = q;
+  }
+}
+
+extern "C" int smk_quantize_u16_device(smk_ctx *c, const void *d_f32, long long n_values, void *d_u16) {
+  if (!c) return 1;
+  PCHK(c, hipSetDevice(c->device));
+  if (!d_f32 || !d_u16 || n_values < 0) {
+    c->err = "smk_quantize_u16_device: bad arguments (need both pointers and n_values >= 0)";
+    return 1;
+  }
+  if (n_values == 0) return 0;
+  const size_t n = (size_t)n_values;
+  const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 256 * 64);
+  hipLaunchKernelGGL(smk_k_quantize_u16, dim3(blocks), dim3(256), 0, c->stream, (const float *)d_f32, n, (unsigned short *)d_u16);
   PCHK(c, hipGetLastError());
   PCHK(c, hipStreamSynchronize(c->stream));
   return 0;

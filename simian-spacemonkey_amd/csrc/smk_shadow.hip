@@ -68,26 +68,31 @@ __device__ __forceinline__ void shadow_fetch(const RenderParams &P, float p0, fl
     smk_load_pair_u8(P, r10 + c0, r10 + c1, k010, k110);
     smk_load_pair_u8(P, r01 + c0, r01 + c1, k001, k101);
     smk_load_pair_u8(P, r11 + c0, r11 + c1, k011, k111);
+  } else if constexpr (DT == 2) {
+    smk_load_pair_u16(P, r00 + c0, r00 + c1, k000, k100);
+    smk_load_pair_u16(P, r10 + c0, r10 + c1, k010, k110);
+    smk_load_pair_u16(P, r01 + c0, r01 + c1, k001, k101);
+    smk_load_pair_u16(P, r11 + c0, r11 + c1, k011, k111);
   } else {
     k000 = smk_load_corner<DT>(P, r00 + c0); k100 = smk_load_corner<DT>(P, r00 + c1);
     k010 = smk_load_corner<DT>(P, r10 + c0); k110 = smk_load_corner<DT>(P, r10 + c1);
     k001 = smk_load_corner<DT>(P, r01 + c0); k101 = smk_load_corner<DT>(P, r01 + c1);
     k011 = smk_load_corner<DT>(P, r11 + c0); k111 = smk_load_corner<DT>(P, r11 + c1);
   }
-  const float sc = DT == 0 ? SMK_INV255 : 1.0f;
+  const float sc = SmkScale<DT>::s01, sch = SmkScale<DT>::s23;
   ch0 = SMK_TRI(c0);
   ch1 = SMK_TRI(c1);
   ch2 = ch3 = 0.f;
-  if (DT == 0) {
+  if (DT != 1) {
     ch0 *= sc;
     ch1 *= sc;
   }
   if (TF == 2 || (TF == 1 && P.third_axis)) {
     ch2 = SMK_TRI(c2);
-    if (DT == 0) ch2 *= sc;
+    if (DT != 1) ch2 *= sch;
     if (P.nelts == 4) {
       ch3 = SMK_TRI(c3);
-      if (DT == 0) ch3 *= sc;
+      if (DT != 1) ch3 *= sch;
     }
   }
   if (SHADE) {
@@ -629,7 +634,7 @@ hipError_t smk_launch_shadow_march(const RenderParams &P, const smk_shadowcoef &
   memset(&S, 0, sizeof S);
 #define CASE(D, T) \
   if (dtype == D && tf_mode == T) return P.pert_on ? run_march<D, T, false, true>(P, Q, hist, hstride, S, s) : run_march<D, T>(P, Q, hist, hstride, S, s);
-  CASE(0, 1) CASE(0, 2) CASE(1, 1) CASE(1, 2)
+  CASE(0, 1) CASE(0, 2) CASE(1, 1) CASE(1, 2) CASE(2, 1) CASE(2, 2)
 #undef CASE
   return hipErrorNotSupported;
 }
@@ -641,7 +646,7 @@ hipError_t smk_launch_shadow_march_shard(const RenderParams &P, const smk_shadow
   Q.sc = sc;
 #define CASE(D, T) \
   if (dtype == D && tf_mode == T) return run_march<D, T, true>(P, Q, hist, hstride, S, s);
-  CASE(0, 1) CASE(0, 2) CASE(1, 1) CASE(1, 2)
+  CASE(0, 1) CASE(0, 2) CASE(1, 1) CASE(1, 2) CASE(2, 1) CASE(2, 2)
 #undef CASE
   return hipErrorNotSupported;
 }
@@ -775,7 +780,7 @@ hipError_t smk_launch_shadow_exports(const RenderParams &P, const smk_shadowcoef
     hipLaunchKernelGGL((smk_k_shadow_exports<D, T>), dim3(lblocks), dim3(256), 0, s, P, Q, S);        \
     return hipGetLastError();                                                                        \
   }
-  CASE(0, 1) CASE(0, 2) CASE(1, 1) CASE(1, 2)
+  CASE(0, 1) CASE(0, 2) CASE(1, 1) CASE(1, 2) CASE(2, 1) CASE(2, 2)
 #undef CASE
   return hipErrorNotSupported;
 }

@@ -366,6 +366,8 @@ static int shadow_refusals(smk_ctx *c, const RenderParams &P) {
   if ((c->opt_lockstep & 256) && (P.pert_on || c->region_on))
     FAIL(c, "smk_render: option shadow_fused has no perturbed instances and no sub-box; use the two marches or shadow_march 0");
   if (c->opt_kernel == 3) FAIL(c, "smk_render: the column-stream kernel has no shadow mode");
+  if (c->dtype == SMK_U16 && (!c->opt_shadow_march || (c->opt_lockstep & 256)))
+    FAIL(c, "smk_render: u16 voxels render shadows with the two marches only (no shadow_march 0 or shadow_fused instances)");
   return 0;
 }
 

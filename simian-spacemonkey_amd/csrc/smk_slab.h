@@ -71,7 +71,23 @@ hipError_t smk_slab_dispatch_u8(const RenderParams &P, const SlabParams &Q, int 
                                 int nblocks, const char **why, hipStream_t s);
 hipError_t smk_slab_dispatch_f32(const RenderParams &P, const SlabParams &Q, int tf_mode, int shade_kind, int nw, int nl, bool diag, size_t lds,
                                  int nblocks, const char **why, hipStream_t s);
-// ... and one for the eye pass of frames with shadows (SHD instances: 2-D / 3-D table, R8k shading or none, both voxel types)
+// u16 voxels (SMK_U16: 8-byte voxels, staged like the u8 ones, their own corner decode): the plain instances and the eye pass
+// of frames with shadows under look 0.  Left unbuilt, and declined by slab_refusal with the reason: the instances for the
+// host's scene depth and for the NV20 look -- the gather kernel renders those frames
+hipError_t smk_slab_dispatch_u16(const RenderParams &P, const SlabParams &Q, int tf_mode, int shade_kind, int nw, int nl, bool diag, size_t lds,
+                                 int nblocks, const char **why, hipStream_t s);
+hipError_t smk_slab_dispatch_u16_shadow(const RenderParams &P, const SlabParams &Q, int tf_mode, int shade_kind, int nw, int nl, size_t lds,
+                                        int nblocks, const char **why, hipStream_t s);
+// ... and the u16 instances that are NOT built because they would need scratch: NV20 shading under the dense 3-D table, 10+2
+// waves, brick flags -- at the 80 VGPRs of their launch bound they spill 6 (the u8 counterparts, which exist, spill 1).  One
+// predicate for the dispatch and for the shape choice, as slab_nv20_left_out below
+constexpr bool slab_u16_left_out(int dtype, int shade_kind, int tf_mode, int nw, int nl, bool bricks) {
+  return dtype == 2 && shade_kind == 2 && tf_mode == 2 && nw == 10 && nl == 2 && bricks;
+}
+constexpr const char *SLAB_U16_LEFT_OUT = "u16 voxels have no 10+2-wave instances with NV20 shading, the 3-D table and brick flags (they would spill)";
+constexpr const char *SLAB_U16_NO_OCC = "u16 voxels have no scene-depth instances of the slice-ring kernel";
+constexpr const char *SLAB_U16_NO_NV20 = "u16 voxels have no shadow_look 1 instances of the slice-ring kernel";
+// ... and one for the eye pass of frames with shadows (SHD instances: 2-D / 3-D table, R8k shading or none, u8 and f32 voxels)
 hipError_t smk_slab_dispatch_shadow(const RenderParams &P, const SlabParams &Q, int dtype, int tf_mode, int shade_kind, int nw, int nl, size_t lds,
                                     int nblocks, const char **why, hipStream_t s);
 // The NV20 look's slice-ring instances that are NOT built: float voxels, 10+2 waves, brick flags -- at the 80 VGPRs of their

@@ -52,6 +52,10 @@ template <>
 struct VoxT<1> {
   typedef float4 type;
 };
+template <>
+struct VoxT<2> {  // u16 voxels (SMK_U16, smk.h): the u8 voxel's 8 bytes, staged and addressed the same way
+  typedef uint2 type;
+};
 
 typedef float v2f __attribute__((ext_vector_type(2)));
 
@@ -199,11 +203,11 @@ __device__ __forceinline__ float slab_tex_chan(const SlabTexel4 &x, int k) {
 template <int DT, int SH, int PERM, int NW, int NL, bool DIAG, int TF = 1, bool BR = true, bool SHD = false, bool OCC = false, bool NVL = false>
 // (second argument: waves per SIMD the register allocation must allow -- two small workgroups per CU)
 __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) == 5 || (NW + NL) == 10) ? 5 : ((NW + NL) == 11 ? 3 : (NW + NL) == 12 ? 6 : 4)) void smk_k_slab(const RenderParams P, const SlabParams Q) {
-  constexpr int UPV = DT == 0 ? 2 : 1;   // voxels per 16-byte DMA unit
-  constexpr int VB = DT == 0 ? 8 : 16;   // bytes per voxel
+  constexpr int UPV = DT != 1 ? 2 : 1;   // voxels per 16-byte DMA unit (by voxel size: u8 and u16 voxels are 8 bytes)
+  constexpr int VB = DT != 1 ? 8 : 16;   // bytes per voxel
   // (global_load_lds_dwordx3 does NOT compact: it writes 12 bytes per lane at a 16-byte lane stride
   //  -- tools/dma_layout_probe.hip -- so staging only {c0,c1,c2} needs a 12-byte HBM plane)
-  constexpr int VBL = DT == 0 ? 3 : 4;   // log2
+  constexpr int VBL = DT != 1 ? 3 : 4;   // log2
   constexpr int NTH = (NW + NL) * 64;
   // big workgroups (one per CU, 128 VGPRs each): read whole voxels, release ring slots early
   // (re-measured with the loaders in pairs: without the early release 4.56 vs 4.11 ms on the 1024^3 frame)
@@ -1060,7 +1064,7 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
         // ---- part A: where the sample is and its corner addresses; EARLY: the whole corner batch
         float fx = 0.f, fy = 0.f, fz = 0.f;
         unsigned a0 = 0, b0 = 0;
-        typename std::conditional<DT == 0, v2u, v4f>::type rq[EARLY ? 8 : 1];
+        typename std::conditional<DT != 1, v2u, v4f>::type rq[EARLY ? 8 : 1];
         float early_nsc = 0.f;
         int early_ni = 0;
         bool work = act && !stream_only;
@@ -1153,9 +1157,19 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
           //  per sample instead of 8 x 12)
           // (byte voxels: all four channels come in one word per corner, the interpolation alone is deferred)
           const bool lazy_h = (TF == 1 && Q.fast_tf) || (TF == 2 && Q.use_occ);
-          uint32_t q8[DT == 0 && !EARLY ? 8 : 1];  // small workgroups, byte voxels: the corners' data words
+          uint32_t q8[DT != 1 && !EARLY ? 8 : 1];  // small workgroups, 8-byte voxels: the corners' data words
           auto tri_h_early = [&]() -> float {
-            if constexpr (EARLY && DT == 0) {
+            if constexpr (EARLY && DT == 2) {  // u16 voxels: the third channel's 8 bits ride above the normal (smk_decode_u16)
+#define E2(dx, dy, dz) (float)(rq[QI(dx, dy, dz)].y >> 24)
+              return TRI(E2) * SMK_INV255;
+#undef E2
+            } else if constexpr (DT == 2) {
+              uint32_t hq[8];
+              slab_read8_nb8(a0, a0 + pitch_b, b0, b0 + pitch_b, hq);
+#define E2(dx, dy, dz) (float)(hq[QI(dx, dy, dz)] >> 24)
+              return TRI(E2) * SMK_INV255;
+#undef E2
+            } else if constexpr (EARLY && DT == 0) {
 #define E2(dx, dy, dz) smk_ub(rq[QI(dx, dy, dz)].x, 2)
               return TRI(E2) * SMK_INV255;
 #undef E2
@@ -1177,7 +1191,20 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
               return 0.f;
             }
           };
-          if constexpr (EARLY && DT == 1) {
+          if constexpr (DT == 2) {
+            // u16 voxels: both 16-bit channels in the data word, interpolated raw and scaled once (the gather kernel's
+            // operations); the third channel as tri_h_early reads it
+            if constexpr (!EARLY) slab_read8_u8(a0, a0 + pitch_b, b0, b0 + pitch_b, q8);
+#define W16(dx, dy, dz) (EARLY ? rq[EARLY ? QI(dx, dy, dz) : 0].x : q8[EARLY ? 0 : QI(dx, dy, dz)])
+#define E0(dx, dy, dz) (float)(W16(dx, dy, dz) & 0xffffu)
+#define E1(dx, dy, dz) (float)(W16(dx, dy, dz) >> 16)
+            ch0 = TRI(E0) * SMK_INV65535;
+            ch1 = TRI(E1) * SMK_INV65535;
+            if ((TF == 2 || P.third_axis) && !lazy_h) ch2 = tri_h_early();
+#undef E1
+#undef E0
+#undef W16
+          } else if constexpr (EARLY && DT == 1) {
 #define E0(dx, dy, dz) rq[QI(dx, dy, dz)].x
 #define E1(dx, dy, dz) rq[QI(dx, dy, dz)].y
             ch0 = TRI(E0);
@@ -1220,7 +1247,7 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
 #undef E0
             }
           } else {
-            uint32_t (&q)[DT == 0 && !EARLY ? 8 : 1] = q8;
+            uint32_t (&q)[DT != 1 && !EARLY ? 8 : 1] = q8;
             if constexpr (DT == 0 && !EARLY) slab_read8_u8(a0, a0 + pitch_b, b0, b0 + pitch_b, q8);
 #define E0(dx, dy, dz) smk_ub(q[QI(dx, dy, dz)], 0)
 #define E1(dx, dy, dz) smk_ub(q[QI(dx, dy, dz)], 1)
@@ -1475,7 +1502,9 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
 // instances --, through smk_slab_f32.hip (SLAB_PART 1) -- the float-voxel instances alone --, through smk_slab_shadow.hip
 // (SLAB_PART 2) -- the instances of the eye pass of frames with shadows --, through smk_slab_occ.hip (SLAB_PART 3) and
 // smk_slab_occ_shadow.hip (SLAB_PART 4) -- the instances of frames with the host's scene depth (OCC), without and with shadows
-// --, and through smk_slab_shadow_nv20.hip (SLAB_PART 5) -- the eye pass of frames with shadows in the NV20 look (NVL).
+// --, through smk_slab_shadow_nv20.hip (SLAB_PART 5) -- the eye pass of frames with shadows in the NV20 look (NVL) --, and
+// through smk_slab_u16.hip (SLAB_PART 6) and smk_slab_u16_shadow.hip (SLAB_PART 7) -- the u16-voxel instances (SMK_U16), plain
+// and the eye pass of frames with shadows under look 0.
 #ifndef SLAB_PART
 #define SLAB_PART 0
 #endif
@@ -1566,6 +1595,33 @@ hipError_t smk_slab_dispatch_occluded_shadow(const RenderParams &P, const SlabPa
   *why = "no scene-depth instance for this configuration";
   return hipErrorNotSupported;
 }
+#elif SLAB_PART == 7
+// u16 voxels, the eye pass of frames with shadows under look 0 (2-D / 3-D table, R8k shading or none).  No scene-depth and no
+// NV20-look instances: slab_refusal declines those frames, the gather kernel renders them.
+hipError_t smk_slab_dispatch_u16_shadow(const RenderParams &P, const SlabParams &Q, int tf_mode, int shade_kind, int nw, int nl, size_t lds,
+                                        int nblocks, const char **why, hipStream_t s) {
+#define GO(S, R, N, L)                                                                                     \
+  if (shade_kind == S && Q.perm == R && nw == N && nl == L) {                                              \
+    if (tf_mode == 2) {                                                                                  \
+      if (Q.bricks) return (launch_slab<2, S, R, N, L, false, 2, true, true>(P, Q, lds, nblocks, s));    \
+      return (launch_slab<2, S, R, N, L, false, 2, false, true>(P, Q, lds, nblocks, s));                 \
+    }                                                                                                    \
+    if (tf_mode == 1) {                                                                                  \
+      if (Q.bricks) return (launch_slab<2, S, R, N, L, false, 1, true, true>(P, Q, lds, nblocks, s));    \
+      return (launch_slab<2, S, R, N, L, false, 1, false, true>(P, Q, lds, nblocks, s));                 \
+    }                                                                                                    \
+    *why = "shadows need a 2-D or 3-D table";                                                            \
+    return hipErrorNotSupported;                                                                         \
+  }
+#define GO_NW(S, R) GO(S, R, 8, 2) GO(S, R, 10, 2) GO(S, R, 12, 4)
+#define GO_R(S) GO_NW(S, 0) GO_NW(S, 1) GO_NW(S, 2)
+  GO_R(0) GO_R(1)
+#undef GO_R
+#undef GO_NW
+#undef GO
+  *why = "no u16 shadow instance for this configuration";
+  return hipErrorNotSupported;
+}
 #elif SLAB_PART == 2
 hipError_t smk_slab_dispatch_shadow(const RenderParams &P, const SlabParams &Q, int dtype, int tf_mode, int shade_kind, int nw, int nl, size_t lds,
                                     int nblocks, const char **why, hipStream_t s) {
@@ -1630,6 +1686,10 @@ hipError_t smk_slab_dispatch_shadow_nv20(const RenderParams &P, const SlabParams
 hipError_t smk_slab_dispatch_u8(const RenderParams &P, const SlabParams &Q, int tf_mode, int shade_kind, int nw, int nl, bool diag, size_t lds,
                                 int nblocks, const char **why, hipStream_t s) {
   const int dtype = 0;
+#elif SLAB_PART == 6
+hipError_t smk_slab_dispatch_u16(const RenderParams &P, const SlabParams &Q, int tf_mode, int shade_kind, int nw, int nl, bool diag, size_t lds,
+                                 int nblocks, const char **why, hipStream_t s) {
+  const int dtype = 2;
 #else
 hipError_t smk_slab_dispatch_f32(const RenderParams &P, const SlabParams &Q, int tf_mode, int shade_kind, int nw, int nl, bool diag, size_t lds,
                                  int nblocks, const char **why, hipStream_t s) {
@@ -1640,7 +1700,13 @@ hipError_t smk_slab_dispatch_f32(const RenderParams &P, const SlabParams &Q, int
   if (dtype == D && shade_kind == S && Q.perm == R && nw == N && nl == L) {                          \
     if (tf_mode == 2) {                                                                              \
       if constexpr ((N == 8 && L == 2) || (N == 10 && L == 2) || (N == 12 && L == 4)) {              \
-        if (Q.bricks) return (launch_slab<D, S, R, N, L, false, 2, true>(P, Q, lds, nblocks, s));  \
+        if constexpr (slab_u16_left_out(D, S, 2, N, L, true)) {                                      \
+          if (Q.bricks) {                                                                            \
+            *why = SLAB_U16_LEFT_OUT;                                                                \
+            return hipErrorNotSupported;                                                             \
+          }                                                                                          \
+        } else if (Q.bricks)                                                                         \
+          return (launch_slab<D, S, R, N, L, false, 2, true>(P, Q, lds, nblocks, s));                \
         return (launch_slab<D, S, R, N, L, false, 2, false>(P, Q, lds, nblocks, s));     \
       }                                                                                              \
       *why = "no dense-3-D-table instance for this tile size";                                       \
@@ -1663,6 +1729,8 @@ hipError_t smk_slab_dispatch_f32(const RenderParams &P, const SlabParams &Q, int
 #define GO_R(D, S) GO_NW(D, S, 0) GO_NW(D, S, 1) GO_NW(D, S, 2)
 #if SLAB_PART == 0
   GO_R(0, 0) GO_R(0, 1) GO_R(0, 2)
+#elif SLAB_PART == 6
+  GO_R(2, 0) GO_R(2, 1) GO_R(2, 2)
 #else
   GO_R(1, 0) GO_R(1, 1) GO_R(1, 2)
 #endif
@@ -1672,4 +1740,4 @@ hipError_t smk_slab_dispatch_f32(const RenderParams &P, const SlabParams &Q, int
   *why = "no kernel instance for this tile size";
   return hipErrorNotSupported;
 }
-#endif  // SLAB_PART 0 / 1
+#endif  // SLAB_PART 0 / 1 / 6

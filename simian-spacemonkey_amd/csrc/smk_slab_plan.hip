@@ -237,6 +237,8 @@ static const char *slab_refusal(const RenderParams &P, int dtype, int tf_mode, c
   //  saturated ray may stop.  Option kernel = 1 renders them in the reference's own order.)
   if (P.N[0] < 2 || P.N[1] < 2 || P.N[2] < 2) return "volume thinner than 2 voxels";
   if (dtype == 1 && !P.n_in_w) return "4-channel f32 voxels";
+  if (dtype == 2 && P.zscene) return SLAB_U16_NO_OCC;
+  if (dtype == 2 && P.sh.on == 2) return SLAB_U16_NO_NV20;
   if (P.rc.nplanes <= 0) return "no planes";
   // (the NV20 look has SHD instances without OCC only, smk_slab.hip SLAB_PART 5: the gather kernel renders the frame)
   if (P.sh.on == 2 && P.zscene) return "option shadow_look 1 has no scene-depth instances of the slice-ring kernel";
@@ -261,8 +263,8 @@ static const char *slab_refusal(const RenderParams &P, int dtype, int tf_mode, c
   for (int a = 0; a < 3; ++a)
     if (!(P.lo[a] <= P.hin[a])) return "region is empty";
   if (Q.Ds > 4096) return "more than 4096 slices";
-  // u8 voxels are 8 B: the DMA moves 16-B units, so rows must start and end on even voxels
-  if (dtype == 0 && ((Q.Du & 1) || (Q.strideV & 1) || (Q.strideS & 1))) return "odd U extent for 8-byte voxels";
+  // u8 and u16 voxels are 8 B: the DMA moves 16-B units, so rows must start and end on even voxels
+  if (dtype != 1 && ((Q.Du & 1) || (Q.strideV & 1) || (Q.strideS & 1))) return "odd U extent for 8-byte voxels";
   return nullptr;
 }
 
@@ -438,14 +440,14 @@ static const char *slab_scan(const RenderParams &P, const SlabParams &Q, bool sp
 // ---- window and pitch of one tile shape from its scan: Wu x Wv voxels, the LDS pitch, the row groups and the DMA
 // instructions per slice.  Returns the refusal, SLAB_NEXT or null.
 static const char *slab_window(const RenderParams &P, SlabParams &Q, int dtype, bool big, const double m[4], bool last) {
-  const int upv = dtype == 0 ? 2 : 1;
+  const int upv = dtype != 1 ? 2 : 1;  // (voxels per 16-byte unit: by voxel size)
   // a window spans s in [j-1, j+1] (2 slices of drift; 2.5 at a face; 3 where slice 1 of a
   // three-slice volume touches both); a coordinate range of extent e touches at most ceil(e) + 2
   // texels (pair included); eps for the fp32 chains
   const double span = P.N[Q.as] <= 3 ? 3.0 : 2.5;
   int Wu = (int)ceil(m[0] + span * m[2] + 2 * SLAB_EPS) + 2;
   int Wv = (int)ceil(m[1] + span * m[3] + 2 * SLAB_EPS) + 2;
-  if (dtype == 0) Wu = ((Wu + 1) & ~1) + 2;  // even width, even alignment of the origin
+  if (dtype != 1) Wu = ((Wu + 1) & ~1) + 2;  // even width, even alignment of the origin
   Wu = std::min(Wu, Q.Du);
   Wv = std::min(Wv, Q.Dv);
   if (Wu < 2 || Wv < 2) return "degenerate window";
@@ -497,21 +499,23 @@ static const char *slab_size_shape(RenderParams &P, SlabParams &Q, SlabShape sh,
 }
 
 // A shape whose workgroup has no kernel instance for this frame (the NV20 look of a frame with shadows, option shadow_look 1:
-// slab_nv20_left_out, smk_slab.h).  The shape choice passes such a shape over.
-static bool slab_shape_without_instance(const RenderParams &P, int dtype, SlabShape sh, bool bricks) {
+// slab_nv20_left_out; u16 voxels with NV20 shading under the 3-D table: slab_u16_left_out; smk_slab.h).  The shape choice
+// passes such a shape over.
+static bool slab_shape_without_instance(const RenderParams &P, int dtype, int tf_mode, int shade_kind, SlabShape sh, bool bricks) {
+  if (!P.sh.on && slab_u16_left_out(dtype, shade_kind, tf_mode, slab_waves(sh), sh.nl, bricks)) return true;
   return P.sh.on == 2 && slab_nv20_left_out(dtype, slab_waves(sh), sh.nl, bricks);
 }
 
 // ---- the probing pass: the candidate small shape with the fewest DMA instructions per ray (*best, -1 if no candidate's
 // window fits), its window sized from a sparse scan.  Returns the refusal or null.
-static const char *slab_probe(RenderParams P, SlabParams Q, int dtype, SlabAux *aux, int *best) {
+static const char *slab_probe(RenderParams P, SlabParams Q, int dtype, int tf_mode, int shade_kind, SlabAux *aux, int *best) {
   double best_score = 1e300;
   int best_wu = 0;
   std::vector<int> work;
   *best = -1;
   for (int ci = 0; ci < 3; ++ci) {
     const SlabShape sh = SLAB_CAND[ci];
-    if (slab_shape_without_instance(P, dtype, sh, P.bricks != nullptr)) continue;
+    if (slab_shape_without_instance(P, dtype, tf_mode, shade_kind, sh, P.bricks != nullptr)) continue;
     const char *why = slab_size_shape(P, Q, sh, dtype, true, false, aux, work);
     if (why == SLAB_NEXT) continue;
     if (why) return why;
@@ -607,7 +611,7 @@ static const char *slab_ring(const RenderParams &P, SlabParams &Q, SlabShape sh,
 // ---- shape choice: the shape of option "tile"; or the small shape the probe ranks first (kept for the view, see
 // below), the other small one, then the big one -- the first whose window and ring fit.  Leaves P and Q planned for
 // that shape, its LDS bytes, and the tiles' weights from its scan.  Returns the refusal or null.
-static const char *slab_choose_shape(RenderParams &P, SlabParams &Q, int dtype, int tf_mode, double ds, SlabAux *aux, SlabShape &shape,
+static const char *slab_choose_shape(RenderParams &P, SlabParams &Q, int dtype, int tf_mode, int shade_kind, double ds, SlabAux *aux, SlabShape &shape,
                                      size_t *lds, std::vector<int> &work) {
   SlabShape list[3] = {{32, 16, 2}, SLAB_BIG_SHAPE, SLAB_BIG_SHAPE};
   int n = 2;
@@ -624,13 +628,13 @@ static const char *slab_choose_shape(RenderParams &P, SlabParams &Q, int dtype, 
   // row and column plus the borders (its answer only ranks the shapes; the real pass sizes the winner's window fully).
   struct ShapeKey { int as, dir, W, H, dtype, N[3]; float lo[3], hi[3]; int nv20; } skey;  // (nv20: that look's candidates differ)
   memset(&skey, 0, sizeof skey);
-  skey.nv20 = P.sh.on == 2;
+  skey.nv20 = P.sh.on == 2 ? 1 : (dtype == 2 && shade_kind == 2 && tf_mode == 2) ? 2 : 0;  // (2: slab_u16_left_out's frames)
   skey.as = Q.as; skey.dir = Q.dir; skey.W = P.W; skey.H = P.H; skey.dtype = dtype;
   for (int a = 0; a < 3; ++a) { skey.N[a] = P.N[a]; skey.lo[a] = P.lo[a]; skey.hi[a] = P.hi[a]; }
   const bool shape_known = choose && aux->shape_key.size() == sizeof skey && !memcmp(aux->shape_key.data(), &skey, sizeof skey) &&
                            aux->shape_choice >= 0 && ++aux->shape_age < 64;
   int best = shape_known ? aux->shape_choice : -1;
-  const char *why = choose && !shape_known ? slab_probe(P, Q, dtype, aux, &best) : nullptr;
+  const char *why = choose && !shape_known ? slab_probe(P, Q, dtype, tf_mode, shade_kind, aux, &best) : nullptr;
   if (why) return why;
   int alt = -1;  // the other small shape: tried before the big workgroup where the chosen one turns out not to fit
   if (best >= 0) {
@@ -661,7 +665,8 @@ static const char *slab_choose_shape(RenderParams &P, SlabParams &Q, int dtype, 
       if (!shape_known) aux->shape_chunks = Q.chunks;
     }
     if (!why) why = slab_ring(P, Q, shape, tf_mode, ds, aux, last, lds);
-    if (!why && slab_shape_without_instance(P, dtype, shape, Q.bricks != nullptr)) why = last ? SLAB_NV20_LEFT_OUT : SLAB_NEXT;
+    if (!why && slab_shape_without_instance(P, dtype, tf_mode, shade_kind, shape, Q.bricks != nullptr))
+      why = last ? (P.sh.on == 2 ? SLAB_NV20_LEFT_OUT : SLAB_U16_LEFT_OUT) : SLAB_NEXT;
     if (why == SLAB_NEXT_BIG && alt >= 0 && ci == 0) ci = 1;  // (a stream this heavy is too heavy for the other small shape as well: the big one next)
     if (why == SLAB_NEXT || why == SLAB_NEXT_BIG) continue;
     if (why) return why;
@@ -1084,8 +1089,10 @@ static hipError_t slab_run(const RenderParams &P, const SlabParams &Q, SlabAux *
   } else
     e = P.zscene   ? (P.sh.on ? smk_slab_dispatch_occluded_shadow(P, Q, dtype, tf_mode, shade_kind, nw, sh.nl, lds, nblocks, why, s)
                                : smk_slab_dispatch_occluded(P, Q, dtype, tf_mode, shade_kind, nw, sh.nl, lds, nblocks, why, s))
-        : P.sh.on    ? smk_slab_dispatch_shadow(P, Q, dtype, tf_mode, shade_kind, nw, sh.nl, lds, nblocks, why, s)
+        : P.sh.on    ? (dtype == 2 ? smk_slab_dispatch_u16_shadow(P, Q, tf_mode, shade_kind, nw, sh.nl, lds, nblocks, why, s)
+                                     : smk_slab_dispatch_shadow(P, Q, dtype, tf_mode, shade_kind, nw, sh.nl, lds, nblocks, why, s))
         : dtype == 0 ? smk_slab_dispatch_u8(P, Q, tf_mode, shade_kind, nw, sh.nl, diag, lds, nblocks, why, s)
+        : dtype == 2 ? smk_slab_dispatch_u16(P, Q, tf_mode, shade_kind, nw, sh.nl, diag, lds, nblocks, why, s)
                      : smk_slab_dispatch_f32(P, Q, tf_mode, shade_kind, nw, sh.nl, diag, lds, nblocks, why, s);
   if (e == hipSuccess && nsplit > 0)
     e = smk_slab_merge(aux->d_order + nblocks, nsplit, sh.tw, sh.th, P.ntx, P.W, P.H, (const float4 *)aux->d_seg, P.out,
@@ -1140,7 +1147,7 @@ static hipError_t slab_plan_and_launch(RenderParams &P, int dtype, int tf_mode, 
   SlabShape shape;
   size_t lds = 0;
   std::vector<int> work;
-  if ((*why = slab_choose_shape(P, Q, dtype, tf_mode, ds, aux, shape, &lds, work))) return hipErrorNotSupported;
+  if ((*why = slab_choose_shape(P, Q, dtype, tf_mode, shade_kind, ds, aux, shape, &lds, work))) return hipErrorNotSupported;
 
   const int nw = slab_waves(shape), nt = P.ntx * P.nty;
   const long long tsig = (((long long)P.ntx * 4096 + P.nty) * 64 + shape.tw) * 64 + shape.th + ((long long)(Q.perm * 2 + (Q.dir > 0)) << 48) +

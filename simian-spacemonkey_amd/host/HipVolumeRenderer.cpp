@@ -16,7 +16,7 @@ static void mul(double o[16], const double a[16], const double b[16]);
 static void translate(double m[16], double x, double y, double z);
 
 HipVolumeRenderer::HipVolumeRenderer(MetaVolume *vm, int, int device)
-    : ctx(nullptr), m_vol(vm), tlut(nullptr), pmode(HipPresentFloat), pdepth(0), pticket(0), pW(0), pH(0), fb8(nullptr), zb(nullptr), failed(0), m_bb(0), m_bbb(0) {
+    : ctx(nullptr), m_vol(vm), tlut(nullptr), pmode(HipPresentFloat), pdepth(0), pticket(0), pW(0), pH(0), fb8(nullptr), zb(nullptr), failed(0), m_bb(0), m_bbb(0), m_u16(0) {
   int err = 0;
   ctx = smk_create(device, &err);
   if (!ctx) {
@@ -53,7 +53,7 @@ static std::vector<smk_volume_desc> brick_descs(Volume *v, int n) {
 int HipVolumeRenderer::upload(Volume *v, int n) {
   if (!ctx) return 1;
   std::vector<smk_volume_desc> d = brick_descs(v, n);
-  if (smk_upload_volume(ctx, d.data(), n, m_vol->nelts, SMK_U8, (smk_datamode)gluvv.dmode)) {
+  if (smk_upload_volume(ctx, d.data(), n, m_vol->nelts, m_u16 ? SMK_U16 : SMK_U8, (smk_datamode)gluvv.dmode)) {
     std::cerr << "ERROR: HipVolumeRenderer::createVolume: " << smk_last_error(ctx) << std::endl;
     failed = 1;
     return 1;
@@ -63,6 +63,10 @@ int HipVolumeRenderer::upload(Volume *v, int n) {
 
 int HipVolumeRenderer::hist2D(unsigned char *hist) {
   if (!ctx || !m_vol || !m_vol->volumes) return 0;
+  if (m_u16) {  // (the histogram's bins are the reference's bytes: uint16_t voxels have none)
+    std::cerr << "MetaVolume::hist2D, not implemented for 16-bit voxels" << std::endl;
+    return 0;
+  }
   std::vector<smk_volume_desc> d((size_t)m_vol->numSubVols);
   for (int i = 0; i < m_vol->numSubVols; ++i) {
     const Volume &v = m_vol->volumes[i];
@@ -233,6 +237,7 @@ void HipVolumeRenderable::init() {
     return;
   }
   volren = new HipVolumeRenderer(gluvv.mv, 0, device);
+  volren->useU16(u16);
   // a series keeps MetaVolume::tstepCache steps resident (MetaVolume.cpp:894-958): they are uploaded under their time-step
   // numbers from the first one on; with one step the volume is simply replaced whenever the time step moves
   tcache = gluvv.mv->tstepCache > 1 ? gluvv.mv->tstepCache : 1;
@@ -273,7 +278,7 @@ int HipVolumeRenderable::uploadStep(int timestep) {
   smk_ctx *c = volren ? volren->context() : nullptr;
   if (!c) return 1;
   std::vector<smk_volume_desc> d = brick_descs(gluvv.mv->volumes, gluvv.mv->numSubVols);
-  if (smk_upload_timestep(c, timestep, d.data(), gluvv.mv->numSubVols, gluvv.mv->nelts, SMK_U8, (smk_datamode)gluvv.dmode)) {
+  if (smk_upload_timestep(c, timestep, d.data(), gluvv.mv->numSubVols, gluvv.mv->nelts, u16 ? SMK_U16 : SMK_U8, (smk_datamode)gluvv.dmode)) {
     std::cerr << "ERROR: HipVolumeRenderable: time step " << timestep << ": " << smk_last_error(c) << std::endl;
     return 1;
   }

@@ -61,6 +61,11 @@ class HipVolumeRenderer {
   // compile, and readable by a host that draws its own overlay
   void useBBox(int on_off) { m_bb = on_off; }
   void useBBoxBrackets(int on_off) { m_bbb = on_off; }
+  // 16-bit data (no reference equivalent: the reference quantises shorts to bytes, MetaVolume.cpp:709-889).  With the switch
+  // on -- before createVolume; off by default -- the Volumes' currentData is read as uint16_t voxels in host byte order
+  // (VolumeFiles' load_trex with keep16) and uploaded as SMK_U16 (smk.h): nelts 1..3, normals as before.
+  void useU16(int on_off) { m_u16 = on_off; }
+  int u16() const { return m_u16; }
   int bbox() const { return m_bb; }
   int bboxBrackets() const { return m_bbb; }
   // the frame of the last renderVolume: [height][width][4] premultiplied float RGBA
@@ -106,11 +111,12 @@ class HipVolumeRenderer {
   int failed;
   int m_bb;
   int m_bbb;
+  int m_u16;
 };
 
 class HipVolumeRenderable final : public gluvvPrimitive {
  public:
-  explicit HipVolumeRenderable(int device = 0) : volren(nullptr), go(0), device(device), tstep(0), tcache(1) {}
+  explicit HipVolumeRenderable(int device = 0) : volren(nullptr), go(0), device(device), tstep(0), tcache(1), u16(0) {}
   ~HipVolumeRenderable() { delete volren; }  // (gluvvPrimitive's destructor is not virtual, gluvvPrimitive.h:26: delete through this type)
   void init();  // virtual in gluvvPrimitive (gluvvPrimitive.h:29-30)
   void draw();
@@ -122,6 +128,7 @@ class HipVolumeRenderable final : public gluvvPrimitive {
   const unsigned char *framebuffer8() const { return volren ? volren->framebuffer8() : nullptr; }
   const float *depthbuffer() const { return volren ? volren->depthbuffer() : nullptr; }
   void flush() { if (volren) volren->flush(); }
+  void useU16(int on_off) { u16 = on_off; }  // before init(): gluvv.mv holds uint16_t voxels (HipVolumeRenderer::useU16)
   int running() const { return go; }
   HipVolumeRenderer *renderer() { return volren; }  // the inner interface (VolumeRenderable keeps it private; a host that
                                                     // draws sub-boxes or slice quads needs it)
@@ -136,5 +143,6 @@ class HipVolumeRenderable final : public gluvvPrimitive {
   int device;
   int tstep;   // the time step the frames show (gluvv.volren.timestep when it was uploaded or selected)
   int tcache;  // device-resident steps: gluvv.mv->tstepCache, at least 1
+  int u16;     // gluvv.mv's voxels are uint16_t and go up as SMK_U16 (useU16)
   std::vector<unsigned char> noise;  // [sz][sy][sx][4]
 };

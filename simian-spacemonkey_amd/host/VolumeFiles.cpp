@@ -104,6 +104,22 @@ void quantize_typed(const T *in, size_t n, unsigned char *out, Acc lo0, Acc hi0)
   }
 }
 
+// the same map onto 0..65535 (quantize_to_u16): the file's own min/max, double arithmetic, truncation
+template <typename T, typename Acc>
+void quantize16_typed(const T *in, size_t n, unsigned short *out, Acc lo0, Acc hi0) {
+  Acc hi = hi0, lo = lo0;
+  for (size_t i = 0; i < n; ++i) {
+    hi = hi > (Acc)in[i] ? hi : (Acc)in[i];
+    lo = lo < (Acc)in[i] ? lo : (Acc)in[i];
+  }
+  const double i0 = (double)lo, i1 = (double)hi;
+  for (size_t i = 0; i < n; ++i) {
+    if (i1 == i0) { out[i] = 0; continue; }
+    const double q = (65535.0 - 0.0) * ((double)in[i] - i0) / (i1 - i0) + 0.0;  // affine(min, x, max, 0, 65535)
+    out[i] = (unsigned short)q;
+  }
+}
+
 }  // namespace
 
 int parse_trex(const char *filename, TrexHeader *h, std::string *err) {
@@ -238,8 +254,22 @@ void quantize_to_u8(const void *native, DataType t, size_t n, unsigned char *out
   }
 }
 
+void quantize_to_u16(const void *native, DataType t, size_t n, unsigned short *out) {
+  switch (t) {
+    case T_UCHAR:  // (already 8 bits: the unorm widened, v * 257 = v / 255 * 65535 exactly)
+      for (size_t i = 0; i < n; ++i) out[i] = (unsigned short)(((const unsigned char *)native)[i] * 257u);
+      break;
+    case T_USHORT: quantize16_typed<unsigned short, unsigned short>((const unsigned short *)native, n, out, USHRT_MAX, 0); break;
+    case T_SHORT: quantize16_typed<short, short>((const short *)native, n, out, SHRT_MAX, SHRT_MIN); break;
+    case T_INT: quantize16_typed<int, int>((const int *)native, n, out, INT_MAX, INT_MIN); break;
+    case T_UINT: quantize16_typed<unsigned, unsigned>((const unsigned *)native, n, out, UINT_MAX, 0u); break;
+    case T_FLOAT: quantize16_typed<float, float>((const float *)native, n, out, 10000000000.0f, -10000000000.0f); break;
+    case T_DOUBLE: quantize16_typed<double, double>((const double *)native, n, out, 1e300, -1e300); break;
+  }
+}
+
 size_t read_brick(const TrexHeader &h, int timestep, int brick, std::vector<unsigned char> *u8,
-                  std::vector<float> *native_f32, std::string *err) {
+                  std::vector<float> *native_f32, std::string *err, std::vector<unsigned short> *u16) {
   if (brick < 0 || brick >= (int)h.bricks.size()) {
     if (err) *err = "read_brick: no such sub-volume";
     return 0;
@@ -270,6 +300,10 @@ size_t read_brick(const TrexHeader &h, int timestep, int brick, std::vector<unsi
   if (h.big_endian && type_size(h.type) > 1) swap_bytes(raw.data(), n, type_size(h.type));
   u8->resize(n);
   quantize_to_u8(raw.data(), h.type, n, u8->data());
+  if (u16) {
+    u16->resize(n);
+    quantize_to_u16(raw.data(), h.type, n, u16->data());
+  }
   if (native_f32) {
     native_f32->resize(n);
     for (size_t i = 0; i < n; ++i) {
@@ -290,7 +324,7 @@ size_t read_brick(const TrexHeader &h, int timestep, int brick, std::vector<unsi
   return got;
 }
 
-size_t load_trex(const char *filename, int timestep, LoadedVolume *out, std::string *err) {
+size_t load_trex(const char *filename, int timestep, LoadedVolume *out, std::string *err, bool keep16) {
   if (parse_trex(filename, &out->header, err) != 1) return 0;
   const TrexHeader &h = out->header;
   if (h.bricks.empty()) {
@@ -299,9 +333,10 @@ size_t load_trex(const char *filename, int timestep, LoadedVolume *out, std::str
   }
   out->vols.assign(h.bricks.size(), Volume());
   out->data.assign(h.bricks.size(), std::vector<unsigned char>());
+  out->data16.assign(keep16 ? h.bricks.size() : 0, std::vector<unsigned short>());
   size_t total = 0;
   for (size_t i = 0; i < h.bricks.size(); ++i) {
-    size_t n = read_brick(h, timestep, (int)i, &out->data[i], nullptr, err);
+    size_t n = read_brick(h, timestep, (int)i, &out->data[i], nullptr, err, keep16 ? &out->data16[i] : nullptr);
     if (!n) return 0;  // MetaVolume::readAll stops at the first failure (:891-899)
     total += n;
     Volume &v = out->vols[i];
@@ -310,7 +345,8 @@ size_t load_trex(const char *filename, int timestep, LoadedVolume *out, std::str
     v.xfSize = b.fsize[0]; v.yfSize = b.fsize[1]; v.zfSize = b.fsize[2];
     v.xiPos = b.ipos[0]; v.yiPos = b.ipos[1]; v.ziPos = b.ipos[2];
     v.xfPos = b.fpos[0]; v.yfPos = b.fpos[1]; v.zfPos = b.fpos[2];
-    v.currentData = out->data[i].data();
+    // (16-bit load: the renderers' data pointer is the u16 brick -- HipVolumeRenderer::useU16 uploads it as SMK_U16)
+    v.currentData = keep16 ? (unsigned char *)out->data16[i].data() : out->data[i].data();
     v.currentGrad = nullptr;
   }
   MetaVolume &mv = out->mv;

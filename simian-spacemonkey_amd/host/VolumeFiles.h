@@ -54,23 +54,32 @@ std::string brick_file(const TrexHeader &h, int timestep, int brick);
 // in double and truncated (VectorMath.h:70-74, 1441-1552).  A constant volume maps to 0.
 void quantize_to_u8(const void *native, DataType t, size_t n, unsigned char *out);
 
+// The same map onto 16 bits, for SMK_U16 voxels (smk.h; the reference has no such path: its textures were 8-bit):
+// (ushort) affine(min, x, max, 0, 65535) with the volume's own min/max, in quantize_to_u8's double arithmetic and
+// truncation.  A constant volume maps to 0; unsigned char data is widened, v * 257.
+void quantize_to_u16(const void *native, DataType t, size_t n, unsigned short *out);
+
 // One brick of one time step as 8-bit voxels (MetaVolume::readVol).  `native_f32`, when given,
 // receives the values before quantisation (the reference keeps them in Volume::nativeData).
-// Returns the bytes read from the file, 0 on failure.
+// `u16`, when given, receives quantize_to_u16 of the same values.  Returns the bytes read from the file, 0 on failure.
 size_t read_brick(const TrexHeader &h, int timestep, int brick, std::vector<unsigned char> *u8,
-                  std::vector<float> *native_f32, std::string *err);
+                  std::vector<float> *native_f32, std::string *err, std::vector<unsigned short> *u16 = nullptr);
 
 // Owns the voxel arrays a MetaVolume points into.
 struct LoadedVolume {
   MetaVolume mv;
   std::vector<Volume> vols;
   std::vector<std::vector<unsigned char>> data;
+  std::vector<std::vector<unsigned short>> data16;  // the 16-bit load (load_trex's keep16): what currentData then points to
   TrexHeader header;
 };
 
 // parse + readAll(timestep): every brick read and quantised, MetaVolume fields filled -- the series' tsteps, tstart, tstop and
 // tstepCache among them, currentTStep = timestep (MetaVolume.cpp:233-627, 891-899).  Returns total bytes read, 0 on failure.
-size_t load_trex(const char *filename, int timestep, LoadedVolume *out, std::string *err);
+// keep16 (off by default: the reference's 8-bit path, unchanged): the bricks are ALSO quantised to 16 bits (quantize_to_u16,
+// every file type) into data16 and the Volumes' currentData points at those -- uint16_t voxels behind the reference's
+// unsigned char pointer, for a HipVolumeRenderer with useU16(1), which uploads them as SMK_U16.
+size_t load_trex(const char *filename, int timestep, LoadedVolume *out, std::string *err, bool keep16 = false);
 
 // MetaVolume::writeAll + Volume::writeVol (:963-1000, :99-126): "<prefix>.trex" and one raw
 // 8-bit file per brick; scalar volumes only, as in the reference.  Returns bytes written.
