@@ -194,12 +194,12 @@ __device__ __forceinline__ float slab_tex_chan(const SlabTexel4 &x, int k) {
 // (BR: the instance knows about brick flags -- EMPTY LAYERS; frames without flags run instances that carry none of it:
 //  the run-time test alone, three per loop turn, cost them 12 % in scalar registers spilled)
 // (SHD: the frame's planes are the half-angle slices of a frame with shadows -- SmkShadowRays; the eye pass of smk_shadow.hip.
-//  Compile-time: the instances live in smk_slab_shadow.hip, SLAB_PART 2)
+//  Compile-time: the instances live in SLAB_PART 2 and 7)
 // (OCC: the frame has the host's opaque scene depth, smk_render_occluded -- folded into each ray's plane range in the set-up.
 //  Compile-time as well: as a run-time test it cost the instances of frames without one a VGPR and a few SGPR spills; the
-//  instances live in smk_slab_occ.hip and smk_slab_occ_shadow.hip, SLAB_PART 3 and 4)
+//  instances live in SLAB_PART 3 and 4)
 // (NVL: the NV20 look of a frame with shadows, option shadow_look 1 -- the sample keeps 1 - sat(light-buffer opacity) (1 - amb)
-//  of its colour, smk_shadow_keep.  Compile-time as SHD is, SHD instances without OCC only: smk_slab_shadow_nv20.hip, SLAB_PART 5)
+//  of its colour, smk_shadow_keep.  Compile-time as SHD is, SHD instances without OCC only: SLAB_PART 5)
 template <int DT, int SH, int PERM, int NW, int NL, bool DIAG, int TF = 1, bool BR = true, bool SHD = false, bool OCC = false, bool NVL = false>
 // (second argument: waves per SIMD the register allocation must allow -- two small workgroups per CU)
 __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) == 5 || (NW + NL) == 10) ? 5 : ((NW + NL) == 11 ? 3 : (NW + NL) == 12 ? 6 : 4)) void smk_k_slab(const RenderParams P, const SlabParams Q) {
@@ -1498,13 +1498,8 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
 
 // ------------------------------------------------------------------------------- host side
 
-// This file is compiled six times (build time: the instances are most of it): as itself -- the merge pass + the byte-voxel
-// instances --, through smk_slab_f32.hip (SLAB_PART 1) -- the float-voxel instances alone --, through smk_slab_shadow.hip
-// (SLAB_PART 2) -- the instances of the eye pass of frames with shadows --, through smk_slab_occ.hip (SLAB_PART 3) and
-// smk_slab_occ_shadow.hip (SLAB_PART 4) -- the instances of frames with the host's scene depth (OCC), without and with shadows
-// --, through smk_slab_shadow_nv20.hip (SLAB_PART 5) -- the eye pass of frames with shadows in the NV20 look (NVL) --, and
-// through smk_slab_u16.hip (SLAB_PART 6) and smk_slab_u16_shadow.hip (SLAB_PART 7) -- the u16-voxel instances (SMK_U16), plain
-// and the eye pass of frames with shadows under look 0.
+// This file is compiled eight times, -DSLAB_PART=0..7 (build time: the instances are most of it).  Each part holds the
+// instances slab_inst_part (smk_slab.h) gives it and the dispatch over them; part 0 has the merge pass and the launcher too.
 #ifndef SLAB_PART
 #define SLAB_PART 0
 #endif
@@ -1540,6 +1535,14 @@ hipError_t smk_slab_merge(const int2 *list, int n, int tw, int th, int ntx, int 
   hipLaunchKernelGGL(smk_k_slab_merge, dim3(n), dim3(256), 0, s, list, tw, th, ntx, W, H, seg_out, out, use_max);
   return hipGetLastError();
 }
+// launch the instance k names, through the part that holds it
+hipError_t smk_slab_launch_instance(const SlabInst &k, const RenderParams &P, const SlabParams &Q, size_t lds, int nblocks, const char **why,
+                                    hipStream_t s) {
+  static SlabDispatchPart *const part[8] = {smk_slab_dispatch_part0, smk_slab_dispatch_part1, smk_slab_dispatch_part2, smk_slab_dispatch_part3,
+                                            smk_slab_dispatch_part4, smk_slab_dispatch_part5, smk_slab_dispatch_part6, smk_slab_dispatch_part7};
+  if ((*why = slab_inst_missing(k))) return hipErrorNotSupported;
+  return part[slab_inst_part(k)](k, P, Q, lds, nblocks, s);
+}
 #endif  // SLAB_PART == 0
 
 template <int DT, int SH, int PERM, int NW, int NL, bool DIAG, int TF = 1, bool BR = true, bool SHD = false, bool OCC = false, bool NVL = false>
@@ -1557,187 +1560,40 @@ static hipError_t launch_slab(const RenderParams &P, const SlabParams &Q, size_t
   return hipGetLastError();
 }
 
-// ---- instance dispatch (declared in smk_slab.h)
-#if SLAB_PART == 3 || SLAB_PART == 4
-// Frames with the host's scene depth: one instance per shape, shading, axis and table kind -- with the brick-flag code (it
-// is exact with no flags as well: Q.bricks null), and none of the diagnostic ones.
-#if SLAB_PART == 3
-hipError_t smk_slab_dispatch_occluded(const RenderParams &P, const SlabParams &Q, int dtype, int tf_mode, int shade_kind, int nw, int nl, size_t lds,
-                                      int nblocks, const char **why, hipStream_t s) {
-#define GO(D, S, R, N, L)                                                                              \
-  if (dtype == D && shade_kind == S && Q.perm == R && nw == N && nl == L) {                          \
-    if (tf_mode == 2) return (launch_slab<D, S, R, N, L, false, 2, true, false, true>(P, Q, lds, nblocks, s)); \
-    if (tf_mode == 1) return (launch_slab<D, S, R, N, L, false, 1, true, false, true>(P, Q, lds, nblocks, s)); \
-    if constexpr (S == 0) return (launch_slab<D, S, R, N, L, false, 0, false, false, true>(P, Q, lds, nblocks, s)); \
-    *why = "no colour-table instance with this shading";                                               \
-    return hipErrorNotSupported;                                                                     \
+// ---- instance dispatch (declared in smk_slab.h).  Every key of the cross product is visited: slab_inst_at(I, F), F over
+// the flags, I over voxels x shading x axis x shape x table.  A key that is built and belongs to this part becomes a
+// comparison with the run-time key and a launch; any other key becomes nothing -- the discarded branch of an `if constexpr`
+// on the template's own parameters instantiates no kernel.
+constexpr bool slab_inst_here(SlabInst K) { return !slab_inst_missing(K) && slab_inst_part(K) == SLAB_PART; }
+template <int I, int F>
+static bool slab_try(const SlabInst &k, const RenderParams &P, const SlabParams &Q, size_t lds, int nblocks, hipStream_t s, hipError_t *e) {
+  constexpr SlabInst K = slab_inst_at(I, F);
+  if constexpr (slab_inst_here(K)) {
+    if (k == K) {
+      *e = launch_slab<K.dt, K.sh, K.perm, K.nw, K.nl, K.diag, K.tf, K.br, K.shd, K.occ, K.nvl>(P, Q, lds, nblocks, s);
+      return true;
+    }
   }
-#define GO_R(D, S) GO_NW(D, S, 0) GO_NW(D, S, 1) GO_NW(D, S, 2)
-#define GO_NW(D, S, R) GO(D, S, R, 8, 2) GO(D, S, R, 10, 2) GO(D, S, R, 12, 4)
-  GO_R(0, 0) GO_R(0, 1) GO_R(0, 2) GO_R(1, 0) GO_R(1, 1) GO_R(1, 2)
-#else
-hipError_t smk_slab_dispatch_occluded_shadow(const RenderParams &P, const SlabParams &Q, int dtype, int tf_mode, int shade_kind, int nw, int nl,
-                                             size_t lds, int nblocks, const char **why, hipStream_t s) {
-#define GO(D, S, R, N, L)                                                                              \
-  if (dtype == D && shade_kind == S && Q.perm == R && nw == N && nl == L) {                          \
-    if (tf_mode == 2) return (launch_slab<D, S, R, N, L, false, 2, true, true, true>(P, Q, lds, nblocks, s)); \
-    if (tf_mode == 1) return (launch_slab<D, S, R, N, L, false, 1, true, true, true>(P, Q, lds, nblocks, s)); \
-    *why = "shadows need a 2-D or 3-D table";                                                        \
-    return hipErrorNotSupported;                                                                     \
-  }
-#define GO_R(D, S) GO_NW(D, S, 0) GO_NW(D, S, 1) GO_NW(D, S, 2)
-#define GO_NW(D, S, R) GO(D, S, R, 8, 2) GO(D, S, R, 10, 2) GO(D, S, R, 12, 4)
-  GO_R(0, 0) GO_R(0, 1) GO_R(1, 0) GO_R(1, 1)
-#endif
-#undef GO_R
-#undef GO_NW
-#undef GO
-  *why = "no scene-depth instance for this configuration";
-  return hipErrorNotSupported;
+  return false;
 }
-#elif SLAB_PART == 7
-// u16 voxels, the eye pass of frames with shadows under look 0 (2-D / 3-D table, R8k shading or none).  No scene-depth and no
-// NV20-look instances: slab_refusal declines those frames, the gather kernel renders them.
-hipError_t smk_slab_dispatch_u16_shadow(const RenderParams &P, const SlabParams &Q, int tf_mode, int shade_kind, int nw, int nl, size_t lds,
-                                        int nblocks, const char **why, hipStream_t s) {
-#define GO(S, R, N, L)                                                                                     \
-  if (shade_kind == S && Q.perm == R && nw == N && nl == L) {                                              \
-    if (tf_mode == 2) {                                                                                  \
-      if (Q.bricks) return (launch_slab<2, S, R, N, L, false, 2, true, true>(P, Q, lds, nblocks, s));    \
-      return (launch_slab<2, S, R, N, L, false, 2, false, true>(P, Q, lds, nblocks, s));                 \
-    }                                                                                                    \
-    if (tf_mode == 1) {                                                                                  \
-      if (Q.bricks) return (launch_slab<2, S, R, N, L, false, 1, true, true>(P, Q, lds, nblocks, s));    \
-      return (launch_slab<2, S, R, N, L, false, 1, false, true>(P, Q, lds, nblocks, s));                 \
-    }                                                                                                    \
-    *why = "shadows need a 2-D or 3-D table";                                                            \
-    return hipErrorNotSupported;                                                                         \
-  }
-#define GO_NW(S, R) GO(S, R, 8, 2) GO(S, R, 10, 2) GO(S, R, 12, 4)
-#define GO_R(S) GO_NW(S, 0) GO_NW(S, 1) GO_NW(S, 2)
-  GO_R(0) GO_R(1)
-#undef GO_R
-#undef GO_NW
-#undef GO
-  *why = "no u16 shadow instance for this configuration";
-  return hipErrorNotSupported;
+// (two folds, one inside the other: a single fold over all the keys is deeper than the compiler nests an expression.  The
+//  flags are the outer one: most of their 32 combinations have no key in this part and are passed over whole -- build time)
+template <int F, int... I>
+static bool slab_try_kinds(std::integer_sequence<int, I...>, const SlabInst &k, const RenderParams &P, const SlabParams &Q, size_t lds, int nblocks,
+                           hipStream_t s, hipError_t *e) {
+  if constexpr ((slab_inst_here(slab_inst_at(I, F)) || ...)) return (slab_try<I, F>(k, P, Q, lds, nblocks, s, e) || ...);
+  return false;
 }
-#elif SLAB_PART == 2
-hipError_t smk_slab_dispatch_shadow(const RenderParams &P, const SlabParams &Q, int dtype, int tf_mode, int shade_kind, int nw, int nl, size_t lds,
-                                    int nblocks, const char **why, hipStream_t s) {
-#define GO(D, S, R, N, L)                                                                                  \
-  if (dtype == D && shade_kind == S && Q.perm == R && nw == N && nl == L) {                              \
-    if (tf_mode == 2) {                                                                                  \
-      if (Q.bricks) return (launch_slab<D, S, R, N, L, false, 2, true, true>(P, Q, lds, nblocks, s));    \
-      return (launch_slab<D, S, R, N, L, false, 2, false, true>(P, Q, lds, nblocks, s));                 \
-    }                                                                                                    \
-    if (tf_mode == 1) {                                                                                  \
-      if (Q.bricks) return (launch_slab<D, S, R, N, L, false, 1, true, true>(P, Q, lds, nblocks, s));    \
-      return (launch_slab<D, S, R, N, L, false, 1, false, true>(P, Q, lds, nblocks, s));                 \
-    }                                                                                                    \
-    *why = "shadows need a 2-D or 3-D table";                                                            \
-    return hipErrorNotSupported;                                                                         \
-  }
-#define GO_NW(D, S, R) GO(D, S, R, 8, 2) GO(D, S, R, 10, 2) GO(D, S, R, 12, 4)
-#define GO_R(D, S) GO_NW(D, S, 0) GO_NW(D, S, 1) GO_NW(D, S, 2)
-  GO_R(0, 0) GO_R(0, 1) GO_R(1, 0) GO_R(1, 1)
-#undef GO_R
-#undef GO_NW
-#undef GO
-  *why = "no shadow instance for this configuration";
-  return hipErrorNotSupported;
+template <int... F>
+static bool slab_try_all(std::integer_sequence<int, F...>, const SlabInst &k, const RenderParams &P, const SlabParams &Q, size_t lds, int nblocks,
+                         hipStream_t s, hipError_t *e) {
+  return (slab_try_kinds<F>(std::make_integer_sequence<int, SLAB_INST_KINDS>{}, k, P, Q, lds, nblocks, s, e) || ...);
 }
-#elif SLAB_PART == 5
-// The NV20 look (option shadow_look 1): shading none or NV20 Phong, both voxel types, 2-D / 3-D table.  No scene-depth (OCC)
-// instances: such a frame is the gather kernel's (smk_slab_plan.hip slab_refusal).  Nor the float-voxel 10+2-wave instances
-// with brick flags: at the 80 VGPRs their launch bound allows they spill 1-4 VGPRs to scratch (profiles/shadow_nv20.md), and
-// no instance of this look is built with scratch -- the shape choice passes those shapes over (smk_slab_plan.hip
-// slab_shape_without_instance); one forced with option "tile" is declined with this reason
-hipError_t smk_slab_dispatch_shadow_nv20(const RenderParams &P, const SlabParams &Q, int dtype, int tf_mode, int shade_kind, int nw, int nl,
-                                         size_t lds, int nblocks, const char **why, hipStream_t s) {
-#define GO_BR(D, S, R, N, L, T)                                                                                      \
-  if (Q.bricks) {                                                                                                   \
-    if constexpr (slab_nv20_left_out(D, N, L, true)) {                                                              \
-      *why = SLAB_NV20_LEFT_OUT;                                                                                    \
-      return hipErrorNotSupported;                                                                                  \
-    } else                                                                                                          \
-      return (launch_slab<D, S, R, N, L, false, T, true, true, false, true>(P, Q, lds, nblocks, s));                \
-  }                                                                                                                 \
-  return (launch_slab<D, S, R, N, L, false, T, false, true, false, true>(P, Q, lds, nblocks, s));
-#define GO(D, S, R, N, L)                                                       \
-  if (dtype == D && shade_kind == S && Q.perm == R && nw == N && nl == L) {   \
-    if (tf_mode == 2) { GO_BR(D, S, R, N, L, 2) }                             \
-    if (tf_mode == 1) { GO_BR(D, S, R, N, L, 1) }                             \
-    *why = "shadows need a 2-D or 3-D table";                                 \
-    return hipErrorNotSupported;                                              \
-  }
-#define GO_NW(D, S, R) GO(D, S, R, 8, 2) GO(D, S, R, 10, 2) GO(D, S, R, 12, 4)
-#define GO_R(D, S) GO_NW(D, S, 0) GO_NW(D, S, 1) GO_NW(D, S, 2)
-  GO_R(0, 0) GO_R(0, 2) GO_R(1, 0) GO_R(1, 2)
-#undef GO_R
-#undef GO_NW
-#undef GO
-#undef GO_BR
-  *why = "no shadow_look 1 instance for this configuration";
-  return hipErrorNotSupported;
+#define SLAB_PASTE_(a, b) a##b
+#define SLAB_PASTE(a, b) SLAB_PASTE_(a, b)
+hipError_t SLAB_PASTE(smk_slab_dispatch_part, SLAB_PART)(const SlabInst &k, const RenderParams &P, const SlabParams &Q, size_t lds, int nblocks,
+                                                         hipStream_t s) {
+  hipError_t e = hipErrorNotSupported;  // (a key of another part, or one that is not built: smk_slab_launch_instance sends neither)
+  slab_try_all(std::make_integer_sequence<int, SLAB_INST_FLAGS>{}, k, P, Q, lds, nblocks, s, &e);
+  return e;
 }
-#else
-#if SLAB_PART == 0
-hipError_t smk_slab_dispatch_u8(const RenderParams &P, const SlabParams &Q, int tf_mode, int shade_kind, int nw, int nl, bool diag, size_t lds,
-                                int nblocks, const char **why, hipStream_t s) {
-  const int dtype = 0;
-#elif SLAB_PART == 6
-hipError_t smk_slab_dispatch_u16(const RenderParams &P, const SlabParams &Q, int tf_mode, int shade_kind, int nw, int nl, bool diag, size_t lds,
-                                 int nblocks, const char **why, hipStream_t s) {
-  const int dtype = 2;
-#else
-hipError_t smk_slab_dispatch_f32(const RenderParams &P, const SlabParams &Q, int tf_mode, int shade_kind, int nw, int nl, bool diag, size_t lds,
-                                 int nblocks, const char **why, hipStream_t s) {
-  const int dtype = 1;
-#endif
-  (void)diag;
-#define GO(D, S, R, N, L)                                                                              \
-  if (dtype == D && shade_kind == S && Q.perm == R && nw == N && nl == L) {                          \
-    if (tf_mode == 2) {                                                                              \
-      if constexpr ((N == 8 && L == 2) || (N == 10 && L == 2) || (N == 12 && L == 4)) {              \
-        if constexpr (slab_u16_left_out(D, S, 2, N, L, true)) {                                      \
-          if (Q.bricks) {                                                                            \
-            *why = SLAB_U16_LEFT_OUT;                                                                \
-            return hipErrorNotSupported;                                                             \
-          }                                                                                          \
-        } else if (Q.bricks)                                                                         \
-          return (launch_slab<D, S, R, N, L, false, 2, true>(P, Q, lds, nblocks, s));                \
-        return (launch_slab<D, S, R, N, L, false, 2, false>(P, Q, lds, nblocks, s));     \
-      }                                                                                              \
-      *why = "no dense-3-D-table instance for this tile size";                                       \
-      return hipErrorNotSupported;                                                                   \
-    }                                                                                                \
-    if (tf_mode == 0) {                                                                              \
-      if constexpr (S == 0 && ((N == 8 && L == 2) || (N == 10 && L == 2) || (N == 12 && L == 4)))    \
-        return (launch_slab<D, S, R, N, L, false, 0, false>(P, Q, lds, nblocks, s));     \
-      *why = "no colour-table instance for this tile size";                                          \
-      return hipErrorNotSupported;                                                                   \
-    }                                                                                                \
-    if constexpr (D == 1 && S == 1) {                                                                \
-      if (diag) return (launch_slab<D, S, R, N, L, true>(P, Q, lds, nblocks, s));        \
-    }                                                                                                \
-    if (Q.bricks) return (launch_slab<D, S, R, N, L, false, 1, true>(P, Q, lds, nblocks, s));  \
-    return (launch_slab<D, S, R, N, L, false, 1, false>(P, Q, lds, nblocks, s));         \
-  }
-  // workgroup shapes: 8+2 waves (32x16 px), 10+2 (40x16 or 16x40 px), 12+4 (32x24 px and the shapes of option "tile")
-#define GO_NW(D, S, R) GO(D, S, R, 8, 2) GO(D, S, R, 10, 2) GO(D, S, R, 12, 4)
-#define GO_R(D, S) GO_NW(D, S, 0) GO_NW(D, S, 1) GO_NW(D, S, 2)
-#if SLAB_PART == 0
-  GO_R(0, 0) GO_R(0, 1) GO_R(0, 2)
-#elif SLAB_PART == 6
-  GO_R(2, 0) GO_R(2, 1) GO_R(2, 2)
-#else
-  GO_R(1, 0) GO_R(1, 1) GO_R(1, 2)
-#endif
-#undef GO_R
-#undef GO_NW
-#undef GO
-  *why = "no kernel instance for this tile size";
-  return hipErrorNotSupported;
-}
-#endif  // SLAB_PART 0 / 1 / 6

@@ -226,8 +226,34 @@ static double slab_now() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); ret
 // (SLAB_NEXT_BIG: the stream is too heavy for a small workgroup).  Any other non-null answer declines the frame.
 static const char SLAB_NEXT[] = "next shape", SLAB_NEXT_BIG[] = "next shape, a big one";
 
+// ---- the kernel instance of a frame on one workgroup shape (smk_slab.h; which keys are built: slab_inst_missing)
+struct SlabShape { int tw, th, nl; };
+static int slab_waves(SlabShape sh) { return (sh.tw / 8) * (sh.th / 8); }
+static SlabInst slab_inst_for(const RenderParams &P, const SlabParams &Q, int dtype, int tf_mode, int shade_kind, SlabShape sh) {
+  SlabInst k = {dtype, shade_kind, Q.perm, slab_waves(sh), sh.nl, tf_mode, false, false, P.sh.on != 0, P.zscene != nullptr, P.sh.on == 2};
+  // developer diagnostics (option lockstep bits 2..64) live in separate instances of the plain f32 + R8k kernels under the
+  // 2-D table only: compiled into the product kernels they cost SGPRs (spills) in every frame
+  k.diag = (P.lockstep & ~1) != 0 && dtype == 1 && shade_kind == 1 && tf_mode == 1 && !k.shd && !k.occ;
+  // the brick-flag code: where the shape has flags, always with scene depth (it is exact with no flags), never under the 1-D table
+  k.br = k.diag || (tf_mode != 0 && (k.occ || Q.bricks));
+  return k;
+}
+// A class of frames -- voxel type, scene depth, shadows and their look -- of which no shape, shading or table at all has an
+// instance: why, else null.  (The gather kernel renders such frames.)
+static const char *slab_class_missing(const RenderParams &P, int dtype) {
+  const char *why = nullptr;
+  for (int i = 0; i < SLAB_INST_KINDS / 3; ++i)
+    for (int f = 0; f < 4; ++f) {  // (diag and br)
+      SlabInst k = slab_inst_at(dtype * (SLAB_INST_KINDS / 3) + i, f);
+      k.shd = P.sh.on != 0; k.occ = P.zscene != nullptr; k.nvl = P.sh.on == 2;
+      if (!(why = slab_inst_missing(k))) return nullptr;
+    }
+  return why;
+}
+
 // ---- refusal: frames the kernel does not take, in this order (tests/test_gpu_fuzz.py tallies the reasons)
 static const char *slab_refusal(const RenderParams &P, int dtype, int tf_mode, const SlabParams &Q) {
+  const char *no_instance = slab_class_missing(P, dtype);
   if (tf_mode < 0 || tf_mode > 2) return "no classification mode";
   if (tf_mode == 0 && (!P.tlut || P.tlut_size < 1)) return "no colour table";
   if (tf_mode == 2 && (!P.tf3d || P.s3v < 1 || P.s3g < 1 || P.s3h < 1)) return "no 3-D table";
@@ -237,11 +263,9 @@ static const char *slab_refusal(const RenderParams &P, int dtype, int tf_mode, c
   //  saturated ray may stop.  Option kernel = 1 renders them in the reference's own order.)
   if (P.N[0] < 2 || P.N[1] < 2 || P.N[2] < 2) return "volume thinner than 2 voxels";
   if (dtype == 1 && !P.n_in_w) return "4-channel f32 voxels";
-  if (dtype == 2 && P.zscene) return SLAB_U16_NO_OCC;
-  if (dtype == 2 && P.sh.on == 2) return SLAB_U16_NO_NV20;
+  if (dtype == 2 && no_instance) return no_instance;  // (u16 voxels: none for scene depth, none in the NV20 look)
   if (P.rc.nplanes <= 0) return "no planes";
-  // (the NV20 look has SHD instances without OCC only, smk_slab.hip SLAB_PART 5: the gather kernel renders the frame)
-  if (P.sh.on == 2 && P.zscene) return "option shadow_look 1 has no scene-depth instances of the slice-ring kernel";
+  if (no_instance) return no_instance;  // (the NV20 look: none for scene depth)
   if (P.sh.on) {
     // frames with shadows: the component of a ray along the slice normal is affine in the pixel coordinate; where it keeps
     // its sign over the viewport's corners no ray runs parallel to the slices (the planning divides by it)
@@ -295,8 +319,6 @@ static double slab_axes(const RenderParams &P, const void *vox_native, const voi
 //   tile is narrow along U so that a window row (tile + drift + pair) fits a 32-unit LDS pitch
 // (one loader wave moves ~10 B/cycle at best, MI355X_MICROARCH.md 'ldsdma-fill'; a heavy
 //  stream needs several per CU)
-struct SlabShape { int tw, th, nl; };
-static int slab_waves(SlabShape sh) { return (sh.tw / 8) * (sh.th / 8); }
 // Small-workgroup shape: 10 + 2 waves on 16x40 or 40x16 pixels, or 8 + 2 on 32x16 -- whichever needs the fewest DMA
 // instructions per ray for THIS view (the window's width is rounded up to whole 128-byte units of LDS pitch, so the
 // answer depends on the pose: cfg 3's gives 7 / 640, 8 / 640 and 6 / 512 rays, and 1.45 / 1.57 / 1.55 ms).  Two
@@ -498,14 +520,6 @@ static const char *slab_size_shape(RenderParams &P, SlabParams &Q, SlabShape sh,
   return why ? why : slab_window(P, Q, dtype, slab_big(slab_waves(sh), sh.nl), m, last);
 }
 
-// A shape whose workgroup has no kernel instance for this frame (the NV20 look of a frame with shadows, option shadow_look 1:
-// slab_nv20_left_out; u16 voxels with NV20 shading under the 3-D table: slab_u16_left_out; smk_slab.h).  The shape choice
-// passes such a shape over.
-static bool slab_shape_without_instance(const RenderParams &P, int dtype, int tf_mode, int shade_kind, SlabShape sh, bool bricks) {
-  if (!P.sh.on && slab_u16_left_out(dtype, shade_kind, tf_mode, slab_waves(sh), sh.nl, bricks)) return true;
-  return P.sh.on == 2 && slab_nv20_left_out(dtype, slab_waves(sh), sh.nl, bricks);
-}
-
 // ---- the probing pass: the candidate small shape with the fewest DMA instructions per ray (*best, -1 if no candidate's
 // window fits), its window sized from a sparse scan.  Returns the refusal or null.
 static const char *slab_probe(RenderParams P, SlabParams Q, int dtype, int tf_mode, int shade_kind, SlabAux *aux, int *best) {
@@ -513,9 +527,11 @@ static const char *slab_probe(RenderParams P, SlabParams Q, int dtype, int tf_mo
   int best_wu = 0;
   std::vector<int> work;
   *best = -1;
+  Q.bricks = P.bricks;  // (as slab_ring will have it)
   for (int ci = 0; ci < 3; ++ci) {
     const SlabShape sh = SLAB_CAND[ci];
-    if (slab_shape_without_instance(P, dtype, tf_mode, shade_kind, sh, P.bricks != nullptr)) continue;
+    // (a shape whose workgroup has no kernel instance for this frame -- the ones left out because they would spill -- is passed over)
+    if (slab_inst_missing(slab_inst_for(P, Q, dtype, tf_mode, shade_kind, sh))) continue;
     const char *why = slab_size_shape(P, Q, sh, dtype, true, false, aux, work);
     if (why == SLAB_NEXT) continue;
     if (why) return why;
@@ -628,7 +644,7 @@ static const char *slab_choose_shape(RenderParams &P, SlabParams &Q, int dtype, 
   // row and column plus the borders (its answer only ranks the shapes; the real pass sizes the winner's window fully).
   struct ShapeKey { int as, dir, W, H, dtype, N[3]; float lo[3], hi[3]; int nv20; } skey;  // (nv20: that look's candidates differ)
   memset(&skey, 0, sizeof skey);
-  skey.nv20 = P.sh.on == 2 ? 1 : (dtype == 2 && shade_kind == 2 && tf_mode == 2) ? 2 : 0;  // (2: slab_u16_left_out's frames)
+  skey.nv20 = P.sh.on == 2 ? 1 : (dtype == 2 && shade_kind == 2 && tf_mode == 2) ? 2 : 0;  // (2: the frames of SLAB_U16_LEFT_OUT)
   skey.as = Q.as; skey.dir = Q.dir; skey.W = P.W; skey.H = P.H; skey.dtype = dtype;
   for (int a = 0; a < 3; ++a) { skey.N[a] = P.N[a]; skey.lo[a] = P.lo[a]; skey.hi[a] = P.hi[a]; }
   const bool shape_known = choose && aux->shape_key.size() == sizeof skey && !memcmp(aux->shape_key.data(), &skey, sizeof skey) &&
@@ -665,8 +681,8 @@ static const char *slab_choose_shape(RenderParams &P, SlabParams &Q, int dtype, 
       if (!shape_known) aux->shape_chunks = Q.chunks;
     }
     if (!why) why = slab_ring(P, Q, shape, tf_mode, ds, aux, last, lds);
-    if (!why && slab_shape_without_instance(P, dtype, tf_mode, shade_kind, shape, Q.bricks != nullptr))
-      why = last ? (P.sh.on == 2 ? SLAB_NV20_LEFT_OUT : SLAB_U16_LEFT_OUT) : SLAB_NEXT;
+    const char *missing = why ? nullptr : slab_inst_missing(slab_inst_for(P, Q, dtype, tf_mode, shade_kind, shape));
+    if (missing) why = last ? missing : SLAB_NEXT;  // (passed over, as in the probe)
     if (why == SLAB_NEXT_BIG && alt >= 0 && ci == 0) ci = 1;  // (a stream this heavy is too heavy for the other small shape as well: the big one next)
     if (why == SLAB_NEXT || why == SLAB_NEXT_BIG) continue;
     if (why) return why;
@@ -1057,10 +1073,7 @@ static hipError_t slab_trace(const RenderParams &P, SlabParams &Q, SlabAux *aux,
 // frames' weights)
 static hipError_t slab_run(const RenderParams &P, const SlabParams &Q, SlabAux *aux, int dtype, int tf_mode, int shade_kind, SlabShape sh,
                            size_t lds, int nblocks, long long tsig, const char **why, hipStream_t s) {
-  const int nw = slab_waves(sh), nt = Q.ntiles, nsplit = aux->nsplit_last;
-  // developer diagnostics (option lockstep bits 2..64) live in separate instances of the f32 +
-  // R8k kernels only: compiled into the product kernels they cost SGPRs (spills) in every frame
-  const bool diag = (P.lockstep & ~1) != 0 && dtype == 1 && shade_kind == 1;
+  const int nt = Q.ntiles, nsplit = aux->nsplit_last;
   hipError_t e = nsplit > 0 ? hipMemsetAsync(aux->d_ticks, 0, (size_t)nt * 20, s) : hipSuccess;  // (their tick words are sums over the pieces)
   if (e != hipSuccess) return e;
   // (the merge pass's first launch costs the host a few milliseconds of code loading, which lands between the frame's
@@ -1079,21 +1092,7 @@ static hipError_t slab_run(const RenderParams &P, const SlabParams &Q, SlabAux *
     }
     (void)hipGetLastError();
   }
-  // (the look first: the NV20 look has instances of its own and none for scene depth -- slab_refusal has declined that frame)
-  if (P.sh.on == 2) {
-    if (P.zscene) {
-      *why = "option shadow_look 1 has no scene-depth instances of the slice-ring kernel";
-      return hipErrorNotSupported;
-    }
-    e = smk_slab_dispatch_shadow_nv20(P, Q, dtype, tf_mode, shade_kind, nw, sh.nl, lds, nblocks, why, s);
-  } else
-    e = P.zscene   ? (P.sh.on ? smk_slab_dispatch_occluded_shadow(P, Q, dtype, tf_mode, shade_kind, nw, sh.nl, lds, nblocks, why, s)
-                               : smk_slab_dispatch_occluded(P, Q, dtype, tf_mode, shade_kind, nw, sh.nl, lds, nblocks, why, s))
-        : P.sh.on    ? (dtype == 2 ? smk_slab_dispatch_u16_shadow(P, Q, tf_mode, shade_kind, nw, sh.nl, lds, nblocks, why, s)
-                                     : smk_slab_dispatch_shadow(P, Q, dtype, tf_mode, shade_kind, nw, sh.nl, lds, nblocks, why, s))
-        : dtype == 0 ? smk_slab_dispatch_u8(P, Q, tf_mode, shade_kind, nw, sh.nl, diag, lds, nblocks, why, s)
-        : dtype == 2 ? smk_slab_dispatch_u16(P, Q, tf_mode, shade_kind, nw, sh.nl, diag, lds, nblocks, why, s)
-                     : smk_slab_dispatch_f32(P, Q, tf_mode, shade_kind, nw, sh.nl, diag, lds, nblocks, why, s);
+  e = smk_slab_launch_instance(slab_inst_for(P, Q, dtype, tf_mode, shade_kind, sh), P, Q, lds, nblocks, why, s);
   if (e == hipSuccess && nsplit > 0)
     e = smk_slab_merge(aux->d_order + nblocks, nsplit, sh.tw, sh.th, P.ntx, P.W, P.H, (const float4 *)aux->d_seg, P.out,
                        P.blend == SMK_BLEND_MAX ? 1 : 0, s);

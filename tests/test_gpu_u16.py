@@ -442,7 +442,7 @@ def test_count_samples(R):
 
 def test_slice_ring_instances_that_would_spill_are_left_out(R, smk):
     """NV20 shading under the dense 3-D table with brick flags on the 10+2-wave shapes (option tile 20: 40 x 16 pixels): not
-    built (smk_slab.h slab_u16_left_out); forced, the kernel says so; its own choice passes the shape over"""
+    built (smk_slab.h slab_inst_missing); forced, the kernel says so; its own choice passes the shape over"""
     from _scenes import tf3d_panes
     k = U.case(3, "3d", shade=2, view="rot", dims=U.DIMS_EVEN)
     k.sc.tf3d = tf3d_panes()
