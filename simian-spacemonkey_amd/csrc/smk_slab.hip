@@ -41,6 +41,14 @@
 
 #define SLAB_DONE 0x3fffffff
 constexpr int SLAB_POLL_SLEEP = 2;  // s_sleep of a consumer wave between two polls for its next slices
+// tools/slab_loop_isa.py --marks builds with -DSLAB_MARKS and cuts the consumer loop into its common and visible halves at
+// these comments in the assembly.  Not in the product's build: an asm statement, even an empty one, holds code motion back,
+// and on some instances that costs two or three VGPRs (profiles/r05_loop_diet.md)
+#ifdef SLAB_MARKS
+#define SLAB_MARK(what) asm volatile("; slab-mark: " what)
+#else
+#define SLAB_MARK(what) ((void)0)
+#endif
 
 template <int DT>
 struct VoxT;
@@ -67,37 +75,55 @@ typedef float v2f __attribute__((ext_vector_type(2)));
 // packed normals follow in a second batch for the samples that turn out to be visible: 16-24
 // instead of 32 VGPRs live across the batch, and less LDS traffic for the transparent majority.
 typedef float v3f __attribute__((ext_vector_type(3)));
-#define SLAB_READ8(INS, OFF)                                                                                              \
-  asm volatile(INS " %0, %8\n\t" INS " %1, %8 offset:" OFF "\n\t" INS " %2, %9\n\t" INS " %3, %9 offset:" OFF "\n\t"       \
-               INS " %4, %10\n\t" INS " %5, %10 offset:" OFF "\n\t" INS " %6, %11\n\t" INS " %7, %11 offset:" OFF "\n\t"  \
-               "s_waitcnt lgkmcnt(0)"                                                                                     \
-               : "=&v"(q[0]), "=&v"(q[1]), "=&v"(q[2]), "=&v"(q[3]), "=&v"(q[4]), "=&v"(q[5]), "=&v"(q[6]), "=&v"(q[7])   \
-               : "v"(a), "v"(ap), "v"(b), "v"(bp)                                                                         \
+#define SLAB_READ8(INS, OFF0, OFF1)                                                                                            \
+  asm volatile(INS " %0, %8 offset:" OFF0 "\n\t" INS " %1, %8 offset:" OFF1 "\n\t" INS " %2, %9 offset:" OFF0 "\n\t"             \
+               INS " %3, %9 offset:" OFF1 "\n\t" INS " %4, %10 offset:" OFF0 "\n\t" INS " %5, %10 offset:" OFF1 "\n\t"           \
+               INS " %6, %11 offset:" OFF0 "\n\t" INS " %7, %11 offset:" OFF1 "\n\t"                                            \
+               "s_waitcnt lgkmcnt(0)"                                                                                          \
+               : "=&v"(q[0]), "=&v"(q[1]), "=&v"(q[2]), "=&v"(q[3]), "=&v"(q[4]), "=&v"(q[5]), "=&v"(q[6]), "=&v"(q[7])        \
+               : "v"(a), "v"(ap), "v"(b), "v"(bp)                                                                              \
                : "memory")
 // f32 voxels {c0, c1, c2, normal bits}: first two / three channels
-__device__ __forceinline__ void slab_read8(unsigned a, unsigned ap, unsigned b, unsigned bp, v2f (&q)[8]) { SLAB_READ8("ds_read_b64", "16"); }
-__device__ __forceinline__ void slab_read8(unsigned a, unsigned ap, unsigned b, unsigned bp, v3f (&q)[8]) { SLAB_READ8("ds_read_b96", "16"); }
+__device__ __forceinline__ void slab_read8(unsigned a, unsigned ap, unsigned b, unsigned bp, v2f (&q)[8]) { SLAB_READ8("ds_read_b64", "0", "16"); }
+__device__ __forceinline__ void slab_read8(unsigned a, unsigned ap, unsigned b, unsigned bp, v3f (&q)[8]) { SLAB_READ8("ds_read_b96", "0", "16"); }
 // whole voxels (normals included) in one batch: workgroups that own a CU alone have the registers
 // for it, and can then release their ring slots before classification and shading (EARLY below)
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef unsigned v2u __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void slab_read8_full(unsigned a, unsigned ap, unsigned b, unsigned bp, v4f (&q)[8]) { SLAB_READ8("ds_read_b128", "16"); }
-__device__ __forceinline__ void slab_read8_full(unsigned a, unsigned ap, unsigned b, unsigned bp, v2u (&q)[8]) { SLAB_READ8("ds_read_b64", "8"); }
+__device__ __forceinline__ void slab_read8_full(unsigned a, unsigned ap, unsigned b, unsigned bp, v4f (&q)[8]) { SLAB_READ8("ds_read_b128", "0", "16"); }
+__device__ __forceinline__ void slab_read8_full(unsigned a, unsigned ap, unsigned b, unsigned bp, v2u (&q)[8]) { SLAB_READ8("ds_read_b64", "0", "8"); }
 // u8 voxels {4 data bytes, normal bits}: the data dword
-__device__ __forceinline__ void slab_read8_u8(unsigned a, unsigned ap, unsigned b, unsigned bp, uint32_t (&q)[8]) { SLAB_READ8("ds_read_b32", "8"); }
-// the packed normals of the same 8 corners (dword NOFF of the voxel)
+__device__ __forceinline__ void slab_read8_u8(unsigned a, unsigned ap, unsigned b, unsigned bp, uint32_t (&q)[8]) { SLAB_READ8("ds_read_b32", "0", "8"); }
+// the packed normals of the same 8 corners (dword NOFF of the voxel).  LEAN (the kernel's switch of that name): the dword's
+// place in the voxel rides in the instruction's offset field, so the four corner addresses of the first batch serve every
+// later one as they are -- four vector adds less per batch, and four addresses instead of two held across the visible path
+template <bool LEAN>
 __device__ __forceinline__ void slab_read8_nb16(unsigned a, unsigned ap, unsigned b, unsigned bp, uint32_t (&q)[8]) {
-  a += 12; ap += 12; b += 12; bp += 12;
-  SLAB_READ8("ds_read_b32", "16");
+  if constexpr (LEAN) {
+    SLAB_READ8("ds_read_b32", "12", "28");
+  } else {
+    a += 12; ap += 12; b += 12; bp += 12;
+    SLAB_READ8("ds_read_b32", "0", "16");
+  }
 }
 // the third float channel of the 8 corners (16-byte voxels), read on its own behind the (v, g) occupancy bit
+template <bool LEAN>
 __device__ __forceinline__ void slab_read8_h16(unsigned a, unsigned ap, unsigned b, unsigned bp, uint32_t (&q)[8]) {
-  a += 8; ap += 8; b += 8; bp += 8;
-  SLAB_READ8("ds_read_b32", "16");
+  if constexpr (LEAN) {
+    SLAB_READ8("ds_read_b32", "8", "24");
+  } else {
+    a += 8; ap += 8; b += 8; bp += 8;
+    SLAB_READ8("ds_read_b32", "0", "16");
+  }
 }
+template <bool LEAN>
 __device__ __forceinline__ void slab_read8_nb8(unsigned a, unsigned ap, unsigned b, unsigned bp, uint32_t (&q)[8]) {
-  a += 4; ap += 4; b += 4; bp += 4;
-  SLAB_READ8("ds_read_b32", "8");
+  if constexpr (LEAN) {
+    SLAB_READ8("ds_read_b32", "4", "12");
+  } else {
+    a += 4; ap += 4; b += 4; bp += 4;
+    SLAB_READ8("ds_read_b32", "0", "8");
+  }
 }
 #undef SLAB_READ8
 
@@ -166,11 +192,13 @@ struct SlabTexel4 {
   uint32_t a, b, c, d;
   float fs, ft;
 };
+template <bool LEAN>
 __device__ __forceinline__ SlabTexel4 slab_tex2d_fetch(const uint32_t *tex, int ss, int s0, int t0, float fs, float ft) {
   SlabTexel4 o;
   o.fs = fs;
   o.ft = ft;
-  const unsigned off = (unsigned)(t0 * ss + s0) * 4u;
+  // (LEAN: a 24-bit multiply, full rate -- a table has far fewer rows and columns; else the compiler's 64-bit multiply-add)
+  const unsigned off = LEAN ? (__umul24((unsigned)t0, (unsigned)ss) + (unsigned)s0) * 4u : (unsigned)(t0 * ss + s0) * 4u;
   const char *tb = reinterpret_cast<const char *>(tex);
   uint2 lo, hi;
   __builtin_memcpy(&lo, tb + off, 8);
@@ -213,6 +241,12 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
   // (re-measured with the loaders in pairs: without the early release 4.56 vs 4.11 ms on the 1024^3 frame)
   constexpr bool BIG = slab_big(NW, NL);
   constexpr bool EARLY = BIG;
+  // LEAN: the shorter instruction stream of a consumer's turn (*Instruction stream of a turn*) -- the
+  // slice-table entry by one multiply-add, later batches of corner reads through the first batch's addresses, the texel
+  // offset by a 24-bit multiply.  The same operations on the same values, but another register allocation: the plain frames'
+  // instances have the room, those of frames with shadows, scene depth or the NV20 look sit at the 80 VGPRs of their launch
+  // bound and would pass it or need scratch (profiles/r05_loop_diet.md), so they keep the longer form
+  constexpr bool LEAN = !SHD && !OCC && !NVL;
   // ... and their loaders skip the row groups a slice does not need, counting DMA instructions per
   // slice; small workgroups keep every slice the same number of instructions (cheaper bookkeeping:
   // measured 3 % on the 512^3 frame, where the loaders' issue slots are the consumers')
@@ -451,7 +485,9 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
   unsigned ph1 = 0, ph2 = 0, ph3 = 0;
   if (phases) ph1 = (unsigned)__builtin_amdgcn_s_memrealtime() - trace_t0;
   const int dir = Q.dir, nslots = Q.nslots;
-  const unsigned pitch_b = 16u * (unsigned)Q.wp;  // LDS row pitch in bytes
+  // LDS row pitch in bytes (LEAN: the mask says what the host guarantees -- the 24-bit multiplies of the loop then take this
+  // very register and not a masked copy of it)
+  const unsigned pitch_b = LEAN ? (16u * (unsigned)Q.wp) & 0xffffffu : 16u * (unsigned)Q.wp;
   const unsigned ring_addr = (unsigned)(size_t)(lds_cptr_t)smem;
   // positions p = 0..npos-1 in marching order: base slice b(p) = dir>0 ? smin+p : smax-p;
   // load order q = 0..npos: slice L(q) = dir>0 ? smin+q : smax+1-q; position p reads L(p), L(p+1)
@@ -998,7 +1034,10 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
       // table row of the sample's base slice: entry index = bs - Os = psgn*pb + (-psgn*poff - Os)
       const int eoff = -psgn * poff - Q.Os;
       const unsigned wtab_addr = (unsigned)(size_t)(lds_cptr_t)wtab;
+      // (LEAN: as a byte offset from the ring's start with entry 0's folded in -- one multiply-add per turn finds the entry)
+      const int tab0 = (int)(wtab_addr - ring_addr) + 8 * eoff, psgn8 = 8 * psgn;
       for (int it = 0;; ++it) {
+        SLAB_MARK("loop head");
         const bool want = pb < SLAB_DONE;
         if (!__any(want)) break;  // every ray of this wave is finished
         // progress = position of the slowest lane (DPP reduction, ~12 VALU), published every
@@ -1072,7 +1111,8 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
         if (work) {
           // the two slices' slot images (one 8-byte table entry each, adjacent): issued first,
           // the position arithmetic below covers the LDS round trip
-          const int *te = reinterpret_cast<const int *>(smem + (wtab_addr - ring_addr)) + 2 * (__mul24(psgn, pb) + eoff);  // (24-bit multiply: full rate; |pb| < 4096 on a lane that works)
+          const int *te = LEAN ? reinterpret_cast<const int *>(smem + (unsigned)(__mul24(psgn8, pb) + tab0))
+                               : reinterpret_cast<const int *>(smem + (wtab_addr - ring_addr)) + 2 * (__mul24(psgn, pb) + eoff);  // (24-bit multiply: full rate; |pb| < 4096 on a lane that works)
           base_a = te[0];
           base_b = BR ? (te[2] & ~1) : te[2];  // (bit 0: the NEXT layer's flag)
         }
@@ -1165,7 +1205,7 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
 #undef E2
             } else if constexpr (DT == 2) {
               uint32_t hq[8];
-              slab_read8_nb8(a0, a0 + pitch_b, b0, b0 + pitch_b, hq);
+              slab_read8_nb8<LEAN>(a0, a0 + pitch_b, b0, b0 + pitch_b, hq);
 #define E2(dx, dy, dz) (float)(hq[QI(dx, dy, dz)] >> 24)
               return TRI(E2) * SMK_INV255;
 #undef E2
@@ -1183,7 +1223,7 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
 #undef E2
             } else if constexpr (DT == 1) {
               uint32_t hq[8];
-              slab_read8_h16(a0, a0 + pitch_b, b0, b0 + pitch_b, hq);
+              slab_read8_h16<LEAN>(a0, a0 + pitch_b, b0, b0 + pitch_b, hq);
 #define E2(dx, dy, dz) __uint_as_float(hq[QI(dx, dy, dz)])
               return TRI(E2);
 #undef E2
@@ -1275,8 +1315,8 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
                 if constexpr (DT == 1) nb[k] = __float_as_uint(rq[k].w);
                 else nb[k] = rq[k].y;
               }
-            } else if (DT == 1) slab_read8_nb16(a0, a0 + pitch_b, b0, b0 + pitch_b, nb);
-            else slab_read8_nb8(a0, a0 + pitch_b, b0, b0 + pitch_b, nb);
+            } else if (DT == 1) slab_read8_nb16<LEAN>(a0, a0 + pitch_b, b0, b0 + pitch_b, nb);
+            else slab_read8_nb8<LEAN>(a0, a0 + pitch_b, b0, b0 + pitch_b, nb);
 #define NB(dx, dy, dz) nb[QI(dx, dy, dz)]
             float n0 = smk_nrm(NB(0, 0, 0), NB(1, 0, 0), NB(0, 1, 0), NB(1, 1, 0), NB(0, 0, 1), NB(1, 0, 1), NB(0, 1, 1), NB(1, 1, 1), 0, fx, fy, fz);
             float n1 = smk_nrm(NB(0, 0, 0), NB(1, 0, 0), NB(0, 1, 0), NB(1, 1, 0), NB(0, 0, 1), NB(1, 0, 1), NB(0, 1, 1), NB(1, 1, 1), 1, fx, fy, fz);
@@ -1299,11 +1339,12 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
             if (Q.use_occ) maybe = (occ[__mul24(t0, P.occ_roww) + (s0 >> 5)] >> (s0 & 31)) & 1u;
             col.w = 0.0f;
             if (maybe) {
+              SLAB_MARK("occupancy bit");
               if (count) {
                 d_maybe = true;
                 d_t0 = (unsigned)__builtin_amdgcn_s_memtime();
               }
-              tx4 = slab_tex2d_fetch(P.tf_vg, P.sv, s0, t0, fs, ft);
+              tx4 = slab_tex2d_fetch<LEAN>(P.tf_vg, P.sv, s0, t0, fs, ft);
               if (texwait_at_issue) {
                 const unsigned t = (unsigned)__builtin_amdgcn_s_memtime();
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1342,10 +1383,12 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
             col.w = 0.0f;
             hit = false;
             if ((occ[__mul24(t0, P.occ_roww) + (s0 >> 5)] >> (s0 & 31)) & 1u) {
+              SLAB_MARK("occupancy bit");
               ch2 = tri_h_early();  // (the third coordinate of the lookup: only now)
               hit = smk_classify<DT, TF>(P, ch0, ch1, ch2, ch3, col);
             }
           } else {
+            SLAB_MARK("occupancy bit");  // (no bitmap: every sample goes on)
             hit = smk_classify<DT, TF>(P, ch0, ch1, ch2, ch3, col);
           }
           d_hit = hit;
@@ -1397,6 +1440,7 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
               if (C3 == 1.0f) m1 = m;
             }
           }
+          SLAB_MARK("blend");
           if (count && d_maybe) d_vis = (unsigned)__builtin_amdgcn_s_memtime() - d_t0;
 #undef QI
         }
@@ -1432,6 +1476,7 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
           }
         }
         }  // rep
+        SLAB_MARK("loop tail");
       }
       if (lane == 0) lds_st(&ctl[8 + wave], SLAB_DONE);
       if (tracing && lane == 0) atomicAdd(Q.trace + 8 * (size_t)blockIdx.x + 7, (unsigned)n_it);
