@@ -118,6 +118,32 @@ int smk_upload_timestep_device(smk_ctx *ctx, int timestep, const smk_volume_desc
 /* replaces MetaVolume::swapTStep: the next frame renders that step.  A step that is not cached fails with "not cached"
  * (swapTStep's return 0): the host uploads it (smk_upload_timestep) and selects it again. */
 int smk_select_timestep(smk_ctx *ctx, int timestep);
+/* Fractional time (no reference counterpart: swapTStep swaps whole steps).  Step `step_out` becomes the blend
+ * (1 - w) a + w b of the cached steps `step_a` and `step_b`, field by field of the packed voxels, in a slot of the ring as if
+ * it had been uploaded: smk_select_timestep(step_out) shows it, smk_get_timesteps lists it, every kernel, option and shard
+ * renders it like any step.  It does not become current unless it already was.
+ * Arithmetic (the contract; plain fp32, one rounding per operation, in the order written):
+ *   u = 1.0f - w, once;  for the values x of a and y of b of every stored field:  r = (u * x) + (w * y)
+ *   -- two products and one sum, never an fma.  A float channel stores r (non-finite inputs give what this arithmetic
+ *   gives, and the brick summary flags their brick as after an upload); an integer field stores
+ *   min((int)(r + 0.5f), top), top = 255 for bytes, 65535 for 16-bit channels.  The fields: u8 -- the four channel bytes and
+ *   the three normal bytes; u16 -- channels 0 and 1 as 16-bit values, the three normal bytes and the stored 8-bit third
+ *   channel as bytes; f32 -- the float channels and the three normal bytes (in the separate normals buffer with four
+ *   channels, when there are normals).  A missing normal is (128, 128, 128) in both steps and stays so.  w == 0 reproduces
+ *   a bit for bit and w == 1 b (every integer field, every finite float); a == b is allowed and yields a copy (every integer
+ *   field exactly; a float within 2.5 * 2^-24 of itself, as u + w need not be 1).
+ * Normals are NOT normalised again: a blend in time shortens them as the trilinear fetch does in space.  G and H of a blend
+ * are the blends of G and H, not derivatives of the blended scalar: a host that wants those blends scalars and runs the
+ * data-preparation entries on the result.
+ * Refused, with the reason: no volume; step_a or step_b not cached; step_out < 0; step_out equal to step_a or step_b (there
+ * is no in-place form); w not finite or outside [0, 1]; no slot for the output.  A cached step_out is overwritten in place,
+ * as by an upload (the current step too: the next frame shows the blend); otherwise it takes a slot by smk_upload_timestep's
+ * rule that is not the current step's, a's or b's -- three slots, four when the current step is a fourth.
+ * Asynchronous, as smk_upload_timestep_device: the blend and the brick summaries are enqueued on `stream` (NULL = the
+ * context's) behind the uploads of a and b, the last frame that read the output slot and whatever still writes it; frames
+ * that render the step wait for it on their own streams, and a later upload or blend into slot a or b waits for this one's
+ * reads.  No host synchronisation. */
+int smk_blend_timesteps(smk_ctx *ctx, int step_a, int step_b, float w, int step_out, void *stream);
 /* introspection: the current step (-1: no volume), the cached ids oldest written first (min(cap, *n) of them; ids_out may
  * be NULL), their number */
 int smk_get_timesteps(smk_ctx *ctx, int *current, int *ids_out, int cap, int *n);
@@ -635,7 +661,7 @@ int smk_timing_read(smk_ctx *ctx, float *avg_ms, int *nframes);
  * frame's rule chose: 0 none, 1 before the volume, 2 after it; no synchronisation); "present_ms" (the HIP-event time of the
  * conversion kernel of the last frame smk_render_present[_end] returned, or of the last smk_present_device -- then it waits for
  * that kernel), "present_bytes" (the bytes the last frame smk_render_present[_end] returned copied to the host: 4 per pixel,
- * 8 with depth).
+ * 8 with depth); "tblend_count" (blends smk_blend_timesteps has enqueued on this context; no synchronisation).
  * "slab_plan_<field>": the launch plan of the latest slice-ring frame, as the host derived it from camera, volume size and
  * voxel type (host memory, no synchronisation; every field reads 0 unless smk_last_frame_info reports kernel 2).  Fields:
  *   tw th nw nl        the workgroup's pixel tile, its consumer and its loader waves

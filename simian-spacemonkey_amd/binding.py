@@ -30,7 +30,7 @@ ABI_SYMBOLS = [
     "smk_get_light_history", "smk_shadow_exports_device", "smk_shadow_entries_device", "smk_shadow_exchange_local",
     "smk_shard_light_order", "smk_get_shadow_margin",
     "smk_set_timestep_cache", "smk_upload_timestep", "smk_upload_timestep_device", "smk_select_timestep",
-    "smk_get_timesteps",
+    "smk_get_timesteps", "smk_blend_timesteps",
     "smk_composite_over_depth_device", "smk_exchange_partial_depth", "smk_exchange_frame_depth", "smk_exchange_frame_local_depth",
     "smk_render_occluded", "smk_render_occluded_device",
     "smk_set_clip_slice",
@@ -134,6 +134,7 @@ def load_library():
                                              C.c_void_p]
     L.smk_select_timestep.argtypes = [C.c_void_p, C.c_int]
     L.smk_get_timesteps.argtypes = [C.c_void_p, P(C.c_int), P(C.c_int), C.c_int, P(C.c_int)]
+    L.smk_blend_timesteps.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p]
     L.smk_set_shard.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.smk_set_clip.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
     L.smk_set_clip_plane.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double)]
@@ -352,6 +353,12 @@ class Renderer:
     def select_timestep(self, timestep):
         """the next frame renders that step; SmkError "... not cached ..." when it is not resident"""
         self._ck(self.L.smk_select_timestep(self.ctx, int(timestep)))
+
+    def blend_timesteps(self, a, b, w, out, stream=None):
+        """step `out` becomes (1 - w) a + w b of the cached steps a and b, field by field of the packed voxels (smk.h
+        smk_blend_timesteps: fractional time), enqueued on `stream` (a hipStream_t handle; None = the context's stream);
+        select_timestep(out) shows it"""
+        self._ck(self.L.smk_blend_timesteps(self.ctx, int(a), int(b), float(w), int(out), stream))
 
     def timesteps(self):
         """(current step or -1, the cached ids oldest written first)"""

@@ -1174,6 +1174,7 @@ extern "C" int smk_get_stat(smk_ctx *c, const char *name, double *value) {
   // smk_present_device: waits for it), and the bytes that frame's copy to the host moved
   if (!strcmp(name, "present_ms")) return smk_present_ms(c, value);
   if (!strcmp(name, "present_bytes")) { *value = c->present_bytes; return 0; }
+  if (!strcmp(name, "tblend_count")) { *value = (double)c->tblend_count; return 0; }
   FAIL(c, "smk_get_stat: unknown name '%s'", name);
 }
 

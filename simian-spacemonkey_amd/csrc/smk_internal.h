@@ -259,6 +259,8 @@ struct TimeStep {
   bool ready_pending = false;       // ... recorded and not yet seen complete
   hipEvent_t used = nullptr;        // the last frame that read the step
   bool used_valid = false;
+  hipEvent_t blended = nullptr;     // the last smk_blend_timesteps that read the step, on the stream it was enqueued on
+  bool blended_valid = false;
 };
 
 // One frame on its way to the host (smk_present.hip; DESIGN.md "Present"): everything a frame in flight needs that the
@@ -326,6 +328,7 @@ struct smk_ctx {
   int ts_cap = 1, ts_cur = -1, ts_cur_id = 0;
   long long ts_written = 0;
   bool ts_series = false;
+  long long tblend_count = 0;  // blends enqueued by smk_blend_timesteps so far (smk_get_stat "tblend_count")
 
   // sharding
   int rank = 0, nranks = 1;

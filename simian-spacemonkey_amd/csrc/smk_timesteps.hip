@@ -10,7 +10,10 @@
 // Ordering (no host synchronisation on the asynchronous path):
 //   - smk_upload_timestep_device enqueues the pack and the brick summaries on the caller's stream and records the slot's
 //     `ready` event there; every stream that reads the step (a frame's, the table refresh's) waits for it;
-//   - every frame records the slot's `used` event on its stream; an upload into the slot waits for it first.
+//   - every frame records the slot's `used` event on its stream; an upload into the slot waits for it first;
+//   - smk_blend_timesteps (fractional time, below) is an upload whose source is two other slots: it waits for their `ready`
+//     events and records their `blended` events behind its kernels; whatever overwrites a slot waits for that one too.
+#include <math.h>
 #include <string.h>
 
 #include <algorithm>
@@ -42,12 +45,14 @@ int smk_step_mark_used(smk_ctx *c, hipStream_t s) {
 static void free_step(TimeStep &T) {
   if (T.used_valid) (void)hipEventSynchronize(T.used);
   if (T.ready_pending) (void)hipEventSynchronize(T.ready);
+  if (T.blended_valid) (void)hipEventSynchronize(T.blended);
   if (T.vox) (void)hipFree(T.vox);
   if (T.nrm) (void)hipFree(T.nrm);
   if (T.mm) (void)hipFree(T.mm);
   if (T.vox_x) (void)hipFree(T.vox_x);
   if (T.ready) (void)hipEventDestroy(T.ready);
   if (T.used) (void)hipEventDestroy(T.used);
+  if (T.blended) (void)hipEventDestroy(T.blended);
   T = TimeStep();
 }
 
@@ -192,6 +197,11 @@ static int upload_step(smk_ctx *c, const char *who, int id, const smk_volume_des
     else HIPCHK(c, hipEventSynchronize(T.ready));
     T.ready_pending = false;
   }
+  if (T.blended_valid) {  // ... and a blend still reading them (smk_blend_timesteps)
+    if (s) HIPCHK(c, hipStreamWaitEvent(s, T.blended, 0));
+    else HIPCHK(c, hipEventSynchronize(T.blended));
+    T.blended_valid = false;  // (whoever writes the slot next is ordered behind this upload)
+  }
   T.id = -1;  // (until it holds the new step)
   if (smk_alloc_step(c, g, T)) return 1;
   if (smk_pack_step(c, who, g, b, nb, on_device, T, s)) return 1;
@@ -238,5 +248,183 @@ extern "C" int smk_get_timesteps(smk_ctx *c, int *current, int *ids_out, int cap
   if (n) *n = (int)held.size();
   if (ids_out)
     for (int i = 0; i < cap && i < (int)held.size(); ++i) ids_out[i] = held[(size_t)i]->id;
+  return 0;
+}
+
+// ------------------------------------------------------------------------------- fractional time (smk_blend_timesteps)
+//
+// A blended step is a step: the packed voxels of two slots blended field by field into a third, then the brick summaries
+// of the result, as after an upload.  The arithmetic is smk.h's: u = 1 - w once on the host, r = (u * x) + (w * y) in fp32
+// with one rounding per operation (two products, one sum: the build's -ffp-contract=off, restated below), a float field
+// stores r, an integer field min((int)(r + 0.5f), top).
+#pragma clang fp contract(off)
+
+namespace {
+
+// what the four words of a 16-byte unit hold
+enum { TB_BYTES = 0,  // u8 voxels (two per unit: channel bytes, normal bytes), and the separate normals buffer
+       TB_F32N = 1,   // an f32 voxel of up to three channels: three floats, the normal bytes in .w
+       TB_U16 = 2,    // u16 voxels (two per unit): channels 0 and 1 as 16-bit values, then normal + third-channel bytes
+       TB_F32C = 3 }; // a four-channel f32 voxel: four floats
+
+__device__ __forceinline__ uint32_t tb_int(uint32_t x, uint32_t y, float u, float w, int top) {
+  const float r = (u * (float)x) + (w * (float)y);
+  return (uint32_t)min((int)(r + 0.5f), top);
+}
+
+__device__ __forceinline__ uint32_t tb_bytes(uint32_t x, uint32_t y, float u, float w) {
+  uint32_t o = 0;
+#pragma unroll
+  for (int k = 0; k < 32; k += 8) o |= tb_int((x >> k) & 255u, (y >> k) & 255u, u, w, 255) << k;
+  return o;
+}
+
+__device__ __forceinline__ uint32_t tb_shorts(uint32_t x, uint32_t y, float u, float w) {
+  return tb_int(x & 65535u, y & 65535u, u, w, 65535) | (tb_int(x >> 16, y >> 16, u, w, 65535) << 16);
+}
+
+__device__ __forceinline__ uint32_t tb_float(uint32_t x, uint32_t y, float u, float w) {
+  return __float_as_uint((u * __uint_as_float(x)) + (w * __uint_as_float(y)));
+}
+
+template <int FORM>
+__device__ __forceinline__ uint4 tb_unit(const uint4 x, const uint4 y, float u, float w) {
+  uint4 o;
+  if (FORM == TB_BYTES) {
+    o.x = tb_bytes(x.x, y.x, u, w); o.y = tb_bytes(x.y, y.y, u, w); o.z = tb_bytes(x.z, y.z, u, w); o.w = tb_bytes(x.w, y.w, u, w);
+  } else if (FORM == TB_U16) {
+    o.x = tb_shorts(x.x, y.x, u, w); o.y = tb_bytes(x.y, y.y, u, w); o.z = tb_shorts(x.z, y.z, u, w); o.w = tb_bytes(x.w, y.w, u, w);
+  } else {
+    o.x = tb_float(x.x, y.x, u, w); o.y = tb_float(x.y, y.y, u, w); o.z = tb_float(x.z, y.z, u, w);
+    o.w = FORM == TB_F32N ? tb_bytes(x.w, y.w, u, w) : tb_float(x.w, y.w, u, w);
+  }
+  return o;
+}
+
+// One linear pass over `units` 16-byte units: out = (1 - w) a + w b per stored field.  A workgroup takes TB_PER runs of 256
+// consecutive units per turn (a wave's load or store instruction covers 1 KiB), and every load of a turn is issued before
+// its arithmetic: 2 * TB_PER * 16 bytes per lane in flight.  The grid is capped and strides over the rest.
+constexpr int TB_PER = 4;
+constexpr unsigned TB_MAX_BLOCKS = 2048;  // 8 workgroups for each of 256 CUs
+
+template <int FORM>
+__global__ __launch_bounds__(256) void smk_k_blend_steps(const uint4 *__restrict__ a, const uint4 *__restrict__ b, uint4 *__restrict__ out,
+                                                          size_t units, float u, float w) {
+  const size_t turn = (size_t)256 * TB_PER, stride = (size_t)gridDim.x * turn;
+  for (size_t base = (size_t)blockIdx.x * turn + threadIdx.x; base < units; base += stride) {
+    uint4 x[TB_PER], y[TB_PER];
+#pragma unroll
+    for (int j = 0; j < TB_PER; ++j) {
+      const size_t i = base + (size_t)j * 256;
+      if (i < units) {
+        x[j] = a[i];
+        y[j] = b[i];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < TB_PER; ++j) {
+      const size_t i = base + (size_t)j * 256;
+      if (i < units) out[i] = tb_unit<FORM>(x[j], y[j], u, w);
+    }
+  }
+}
+
+// the last n < 4 words of a buffer of packed normals
+__global__ __launch_bounds__(64) void smk_k_blend_words(const uint32_t *a, const uint32_t *b, uint32_t *out, int n, float u, float w) {
+  if ((int)threadIdx.x < n) out[threadIdx.x] = tb_bytes(a[threadIdx.x], b[threadIdx.x], u, w);
+}
+
+template <int FORM>
+hipError_t launch_blend(const void *a, const void *b, void *out, size_t units, float u, float w, hipStream_t s) {
+  if (!units) return hipSuccess;
+  const size_t turn = (size_t)256 * TB_PER, blocks = std::min((units + turn - 1) / turn, (size_t)TB_MAX_BLOCKS);
+  hipLaunchKernelGGL(smk_k_blend_steps<FORM>, dim3((unsigned)blocks), dim3(256), 0, s, (const uint4 *)a, (const uint4 *)b, (uint4 *)out, units, u,
+                     w);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" int smk_blend_timesteps(smk_ctx *c, int step_a, int step_b, float w, int step_out, void *stream) {
+  if (!c) return 1;
+  const char *who = "smk_blend_timesteps";
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!c->have_volume) FAIL(c, "%s: no volume uploaded", who);
+  const int ka = find_step(c, step_a), kb = find_step(c, step_b);
+  if (step_a < 0 || ka < 0) FAIL(c, "%s: time step %d (a) is not cached", who, step_a);
+  if (step_b < 0 || kb < 0) FAIL(c, "%s: time step %d (b) is not cached", who, step_b);
+  if (step_out < 0) FAIL(c, "%s: output time step %d: ids are >= 0", who, step_out);
+  if (step_out == step_a || step_out == step_b)
+    FAIL(c, "%s: output time step %d is also a source: the blend has no in-place form", who, step_out);
+  if (!(w >= 0.0f && w <= 1.0f)) FAIL(c, "%s: weight %g is not in [0, 1] (no extrapolation)", who, (double)w);
+  c->ts_series = true;
+  int k = find_step(c, step_out);
+  if (k < 0) {
+    // a slot by next_slot's rule that is neither source's: the sources, the current step and the output are 3 or 4 slots
+    // (one less where a and b are the same step)
+    const int need = 2 + (ka != kb ? 1 : 0) + (c->ts_cur != ka && c->ts_cur != kb ? 1 : 0);
+    if ((int)c->ts.size() < need)
+      FAIL(c, "%s: the cache holds %d steps: the two sources and the output need three slots, four when the current step (%d) is a fourth "
+              "(here %d); smk_set_timestep_cache sets more", who, (int)c->ts.size(), c->ts_cur_id, need);
+    k = next_slot(c);
+    while (k == ka || k == kb || k == c->ts_cur) k = (k + 1) % (int)c->ts.size();
+  }
+  TimeStep &A = c->ts[(size_t)ka], &B = c->ts[(size_t)kb], &T = c->ts[(size_t)k];
+  const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  // the sources: their uploads (or blends) come first -- the events stay pending for the frames that read the steps -- and so
+  // does the blend that read them last, on whatever stream: its event is recorded again below, behind this one's kernels
+  for (TimeStep *S : {&A, &B}) {
+    if (S->ready_pending) HIPCHK(c, hipStreamWaitEvent(s, S->ready, 0));
+    if (S->blended_valid) HIPCHK(c, hipStreamWaitEvent(s, S->blended, 0));
+  }
+  // the output slot's old contents: the frames and the blends that read them, and an upload still writing them
+  if (T.used_valid) HIPCHK(c, hipStreamWaitEvent(s, T.used, 0));
+  if (T.blended_valid) {
+    HIPCHK(c, hipStreamWaitEvent(s, T.blended, 0));
+    T.blended_valid = false;  // (whoever writes the slot next is ordered behind this blend)
+  }
+  if (T.ready_pending) {
+    HIPCHK(c, hipStreamWaitEvent(s, T.ready, 0));
+    T.ready_pending = false;
+  }
+  T.id = -1;  // (until it holds the new step)
+  const size_t nst = (size_t)c->D[0] * c->D[1] * c->D[2];
+  SmkVolGeom g;  // the series' buffers (the blend writes the pad column of a padded box itself: 0 blended with 0)
+  g.vox_bytes = c->vox_bytes;
+  g.nrm_bytes = c->dtype == SMK_F32 && c->nelts == 4 && c->have_normals ? nst * 4 : 0;
+  g.mm_bytes = (size_t)c->nbr[0] * c->nbr[1] * c->nbr[2] * sizeof(float4);
+  if (smk_alloc_step(c, g, T)) return 1;
+  // The stored box -- region + halo, D[0] D[1] D[2] voxels -- in 16-byte units: one f32 voxel, or two 8-byte voxels (D[0] is
+  // even for those types, smk_volume_geometry, so their number is even).  The 16 bytes behind the box are not touched.
+  const float u = 1.0f - w;
+  const size_t units = c->vox_bytes / 16;
+  if (c->dtype == SMK_U8) HIPCHK(c, launch_blend<TB_BYTES>(A.vox, B.vox, T.vox, units, u, w, s));
+  else if (c->dtype == SMK_U16) HIPCHK(c, launch_blend<TB_U16>(A.vox, B.vox, T.vox, units, u, w, s));
+  else if (c->nelts <= 3) HIPCHK(c, launch_blend<TB_F32N>(A.vox, B.vox, T.vox, units, u, w, s));
+  else HIPCHK(c, launch_blend<TB_F32C>(A.vox, B.vox, T.vox, units, u, w, s));
+  if (g.nrm_bytes) {
+    // the separate normals of four-channel f32, a word per voxel, in the byte form: the whole units, then the words that
+    // are left when the voxel count (odd sizes are allowed for f32) is no multiple of four
+    HIPCHK(c, launch_blend<TB_BYTES>(A.nrm, B.nrm, T.nrm, nst / 4, u, w, s));
+    if (nst % 4) {
+      const size_t done = nst / 4 * 4;
+      hipLaunchKernelGGL(smk_k_blend_words, dim3(1), dim3(64), 0, s, A.nrm + done, B.nrm + done, T.nrm + done, (int)(nst % 4), u, w);
+      HIPCHK(c, hipGetLastError());
+    }
+  }
+  HIPCHK(c, smk_bricks_minmax(T.vox, c->dtype, c->D, c->nbr, T.mm, s));
+  T.vox_x_valid = false;
+  T.id = step_out;
+  T.written = ++c->ts_written;
+  if (!T.ready) HIPCHK(c, hipEventCreateWithFlags(&T.ready, hipEventDisableTiming));
+  HIPCHK(c, hipEventRecord(T.ready, s));
+  T.ready_pending = true;
+  for (TimeStep *S : {&A, &B}) {  // whatever overwrites a source slot comes after these reads
+    if (!S->blended) HIPCHK(c, hipEventCreateWithFlags(&S->blended, hipEventDisableTiming));
+    HIPCHK(c, hipEventRecord(S->blended, s));
+    S->blended_valid = true;
+  }
+  ++c->tblend_count;
+  if (k == c->ts_cur) switch_step(c, k);  // the current step overwritten in place
   return 0;
 }

@@ -7,6 +7,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <climits>
 #include <cstdio>
 #include <iostream>
 
@@ -282,6 +283,7 @@ int HipVolumeRenderable::uploadStep(int timestep) {
     std::cerr << "ERROR: HipVolumeRenderable: time step " << timestep << ": " << smk_last_error(c) << std::endl;
     return 1;
   }
+  if (tblend_id < 0) tblend_t = -1;  // (a blend refused for want of a resident step is asked for again)
   return 0;
 }
 
@@ -290,8 +292,24 @@ int HipVolumeRenderable::uploadStep(int timestep) {
 // selected -- no voxel moves -- and any other is uploaded from gluvv.mv's current data under its number, then selected.
 int HipVolumeRenderable::showTimeStep() {
   const int t = gluvv.volren.timestep;
-  if (t == tstep) return 0;
   smk_ctx *c = volren->context();
+  if (t == tstep) {
+    if (tfrac > 0) {
+      showTimeFraction();
+      return 0;
+    }
+    if (tblend_id >= 0) {  // back from a blend to the whole step, which the ring never evicts under a blend of it
+      if (smk_select_timestep(c, t)) {
+        std::cerr << "ERROR: HipVolumeRenderable::draw: " << smk_last_error(c) << std::endl;
+        return 1;
+      }
+      tblend_id = -1;
+    }
+    tblend_t = -1;  // (the next fraction is blended afresh, one that was refused before too)
+    return 0;
+  }
+  tblend_id = -1;  // (the whole step first: it becomes current below, then the blend from it)
+  tblend_t = -1;
   if (tcache == 1) {
     const int bad = gluvv.mv->numSubVols == 1 ? volren->createVolume(VolRen3DExt, gluvv.mv->volumes)
                                               : volren->createVolume(VolRen3DExt, gluvv.mv->volumes, gluvv.mv->numSubVols);
@@ -304,7 +322,46 @@ int HipVolumeRenderable::showTimeStep() {
     }
   }
   tstep = t;
+  if (tfrac > 0) showTimeFraction();
   return 0;
+}
+
+int HipVolumeRenderable::setTimeFraction(float f) {
+  if (!(f >= 0.0f && f < 1.0f)) return 1;
+  tfrac = f;
+  return 0;
+}
+
+// The frames show (1 - tfrac) step tstep + tfrac step (tstep + 1), blended on the device into one of two ids no series uses,
+// in turn: the slot the frame before this one reads is never the one being written.  A blend the C ABI refuses -- step
+// tstep + 1 not resident -- is reported once, and the frames stay on the whole step; it is asked for again when the step or
+// the fraction moves, after a fraction of 0, or after the adapter has uploaded a step.  A series cache of one step holds the
+// volume and no steps (init(), showTimeStep): there is nothing to blend with, and the ring is not grown for it.
+void HipVolumeRenderable::showTimeFraction() {
+  if (tblend_t == tstep && tblend_f == tfrac) return;
+  smk_ctx *c = volren->context();
+  tblend_t = tstep;
+  tblend_f = tfrac;
+  if (tcache == 1) {
+    std::cerr << "ERROR: HipVolumeRenderable::setTimeFraction: time step " << tstep + 1
+              << " is not cached: the series keeps one step resident (MetaVolume::tstepCache < 2)" << std::endl;
+    return;
+  }
+  if (!tblend_grown) {
+    if (smk_set_timestep_cache(c, tcache + 2)) {
+      std::cerr << "ERROR: HipVolumeRenderable::setTimeFraction: " << smk_last_error(c) << std::endl;
+      return;
+    }
+    tblend_grown = 1;
+  }
+  const int id = INT_MAX - tblend_next;
+  if (smk_blend_timesteps(c, tstep, tstep + 1, tfrac, id, nullptr) || smk_select_timestep(c, id)) {
+    std::cerr << "ERROR: HipVolumeRenderable::setTimeFraction: " << smk_last_error(c) << std::endl;
+    if (tblend_id >= 0 && !smk_select_timestep(c, tstep)) tblend_id = -1;
+    return;
+  }
+  tblend_id = id;
+  tblend_next ^= 1;
 }
 
 void HipVolumeRenderable::draw() {

@@ -116,7 +116,9 @@ class HipVolumeRenderer {
 
 class HipVolumeRenderable final : public gluvvPrimitive {
  public:
-  explicit HipVolumeRenderable(int device = 0) : volren(nullptr), go(0), device(device), tstep(0), tcache(1), u16(0) {}
+  explicit HipVolumeRenderable(int device = 0)
+      : volren(nullptr), go(0), device(device), tstep(0), tcache(1), u16(0), tfrac(0), tblend_t(-1), tblend_f(0), tblend_id(-1), tblend_next(0),
+        tblend_grown(0) {}
   ~HipVolumeRenderable() { delete volren; }  // (gluvvPrimitive's destructor is not virtual, gluvvPrimitive.h:26: delete through this type)
   void init();  // virtual in gluvvPrimitive (gluvvPrimitive.h:29-30)
   void draw();
@@ -129,6 +131,12 @@ class HipVolumeRenderable final : public gluvvPrimitive {
   const float *depthbuffer() const { return volren ? volren->depthbuffer() : nullptr; }
   void flush() { if (volren) volren->flush(); }
   void useU16(int on_off) { u16 = on_off; }  // before init(): gluvv.mv holds uint16_t voxels (HipVolumeRenderer::useU16)
+  // fractional time (an extension, like useU16: the reference shows whole steps).  With f in (0, 1) draw() shows the blend of
+  // the steps gluvv.volren.timestep and timestep + 1 at weight f (smk_blend_timesteps), which both have to be resident; f == 0
+  // is the whole step, as before.  Returns 1 for an f outside [0, 1).  Call after init().  The series must keep at least two
+  // steps resident (gluvv.mv->tstepCache >= 2); a blend that is refused -- step timestep + 1 not resident -- is reported once
+  // on stderr and the frames stay on the whole step until the step or the fraction moves.
+  int setTimeFraction(float f);
   int running() const { return go; }
   HipVolumeRenderer *renderer() { return volren; }  // the inner interface (VolumeRenderable keeps it private; a host that
                                                     // draws sub-boxes or slice quads needs it)
@@ -144,5 +152,12 @@ class HipVolumeRenderable final : public gluvvPrimitive {
   int tstep;   // the time step the frames show (gluvv.volren.timestep when it was uploaded or selected)
   int tcache;  // device-resident steps: gluvv.mv->tstepCache, at least 1
   int u16;     // gluvv.mv's voxels are uint16_t and go up as SMK_U16 (useU16)
+  void showTimeFraction();  // the blend of (tstep, tstep + 1) at tfrac, made again only when one of the two changed
+  float tfrac;              // setTimeFraction
+  int tblend_t;             // the (time step, fraction) of the last blend asked for, made or refused (-1: none)
+  float tblend_f;
+  int tblend_id;            // the reserved id the frames show instead of tstep (-1: they show tstep)
+  int tblend_next;          // which of the two reserved ids, INT_MAX and INT_MAX - 1, the next blend goes into
+  int tblend_grown;         // the ring has the two slots more that the blends live in
   std::vector<unsigned char> noise;  // [sz][sy][sx][4]
 };

@@ -5,7 +5,13 @@
   2. a playback loop over 4 cached steps, one frame per step: all four resident (capacity 4), then capacity 2 with
      each next step uploaded (smk_upload_timestep_device) on a second stream while the current one renders.
 Frame times are HIP-event times on the render stream (median); the loop also reports wall time per frame.
-    python tools/timestep_time.py [volume edge] [loop frames]"""
+    python tools/timestep_time.py [volume edge] [loop frames]
+  3. --blend: fractional time (smk_blend_timesteps).  For f32, u8 and u16 steps: the blend alone and
+     smk_upload_timestep_device of the same step alone (HIP events round the entry's work on its stream, median of 9), the
+     bytes both move, and the blend's time against the upload's times the ratio of their bytes; then, for f32, playback
+     over the four resident steps with 4 blended frames between neighbours, each blend enqueued on a second stream beside
+     the frame before it.  Writes the note profiles/timestep_blend.md (--out PATH: elsewhere).
+    python tools/timestep_time.py --blend [--out PATH] [volume edge] [loop frames]"""
 import os
 import statistics
 import sys
@@ -28,10 +34,152 @@ def timed_frame(R, frame, st):
     return a.elapsed_time(b)
 
 
+def event_ms(stream, work):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record(stream)
+    work()
+    b.record(stream)
+    b.synchronize()
+    return a.elapsed_time(b)
+
+
+def typed_steps(R, n, dtype):
+    """four steps of config 3's volume on the device as (data, normals) tensors of that voxel type, and its smk_dtype"""
+    out = []
+    for seed in (1, 2, 3, 4):
+        vghf, nrm = bench.make_volume(R, n, seed=seed)
+        if dtype == "u8":
+            data = (vghf * 255.0 + 0.5).to(torch.uint8)
+        elif dtype == "u16":
+            data = torch.empty(vghf.shape, dtype=torch.int16, device="cuda")     # (the bits of uint16 voxels)
+            R.quantize_u16_device(vghf.data_ptr(), vghf.numel(), data.data_ptr())
+        else:
+            data = vghf
+        out.append((data, nrm))
+    torch.cuda.synchronize()
+    return out, {"u8": 0, "f32": 1, "u16": 2}[dtype]
+
+
+def blend_kernel_registers():
+    """{kernel: vgprs} of the blend kernels from the built library (tools/kernel_inventory.py), or {} where that fails"""
+    import json
+    import subprocess
+    import tempfile
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lib = os.path.join(root, "simian-spacemonkey_amd", "csrc", "libsmk_hip.so")
+    try:
+        with tempfile.TemporaryDirectory() as d:
+            subprocess.run([sys.executable, os.path.join(root, "tools", "kernel_inventory.py"), lib, "-o", os.path.join(d, "k.json")],
+                           check=True, capture_output=True, timeout=600)
+            inv = json.load(open(os.path.join(d, "k.json")))
+    except Exception:
+        return {}
+    return {k: v for k, v in inv.items() if "smk_k_blend" in k}
+
+
+def blend_leg(pkg, n, loop, out_path):
+    lines = ["# Fractional time: `smk_blend_timesteps` on one MI355X", "",
+             "Written by `tools/timestep_time.py --blend %d %d`.  Config 3's step (%d^3 VGH with normals), HIP-event times" % (n, loop, n),
+             "round the entry's work on its stream (blend or pack, then the brick summaries), median of 9 after 3 warm-up calls.",
+             "Bytes: the blend reads two stored volumes and writes one, and the summary reads the result (4 x stored); the upload",
+             "reads the caller's voxels and normals, writes the stored volume, and the summary reads it.  The yardstick is the",
+             "upload, the code that was there before: the blend should take no more than the ratio of the two kernels' bytes",
+             "(3 x stored : source + stored; 3/2 for f32, 24/14 for u8) times the upload's time, with 20 % for run-to-run spread.", "",
+             "| voxels | stored bytes | blend ms | blend TB/s | upload ms | upload TB/s | byte ratio | blend / upload | within ratio x 1.2 |",
+             "|---|---|---|---|---|---|---|---|---|"]
+    bl = torch.cuda.Stream()
+    dims = (n, n, n)
+    for dtype in ("f32", "u8", "u16"):
+        R = pkg.Renderer(0)
+        try:
+            steps, dt = typed_steps(R, n, dtype)
+            R.set_timestep_cache(6)
+            R.upload_volume_device(steps[0][0].data_ptr(), dims, 3, dt, steps[0][1].data_ptr())
+            for t in (1, 2, 3):
+                R.upload_timestep_device(t, steps[t][0].data_ptr(), dims, 3, dt, steps[t][1].data_ptr(), stream=bl.cuda_stream)
+            torch.cuda.synchronize()
+            stored = n ** 3 * (16 if dtype == "f32" else 8)
+            source = n ** 3 * (3 * {"f32": 4, "u8": 1, "u16": 2}[dtype] + 3)
+            tb = [event_ms(bl, lambda i=i: R.blend_timesteps(0, 1, 0.3, 10 + (i & 1), stream=bl.cuda_stream)) for i in range(12)][3:]
+            tu = [event_ms(bl, lambda: R.upload_timestep_device(3, steps[3][0].data_ptr(), dims, 3, dt, steps[3][1].data_ptr(),
+                                                                stream=bl.cuda_stream)) for _ in range(12)][3:]
+            b_ms, u_ms = statistics.median(tb), statistics.median(tu)
+            ratio = 3.0 * stored / (source + stored)
+            ok = b_ms <= ratio * u_ms * 1.2
+            lines.append("| %s | %.0f MiB | %.3f (min %.3f, max %.3f) | %.2f | %.3f (min %.3f, max %.3f) | %.2f | %.3f | %.3f | %s |" % (
+                dtype, stored / 2 ** 20, b_ms, min(tb), max(tb), 4.0 * stored / b_ms / 1e9, u_ms, min(tu), max(tu),
+                (source + 2.0 * stored) / u_ms / 1e9, ratio, b_ms / u_ms, "yes" if ok else "NO"))
+            print(lines[-1], flush=True)
+            if dtype == "f32":
+                play = blend_playback(R, n, loop, bl)
+        finally:
+            R.close()
+            torch.cuda.synchronize()
+    lines += ["", "## Playback", "", "Config 3's scene (f32, 1024^2 x 512 planes) over the four resident steps, every step followed by 4 blended frames",
+              "(w = 0.2 .. 0.8) towards the next one; the blend of frame i + 1 is enqueued on a second stream before frame i, into the",
+              "output id frame i does not show.  DESIGN.md 3b has 0.72 ms per frame for whole resident steps and 1.79 ms with the next",
+              "step uploaded beside the frame.", ""] + play
+    regs = blend_kernel_registers()
+    lines += ["", "## Kernels", "", "`smk_k_blend_steps<FORM>`: 256 lanes, 4 x 16-byte units of each source per lane and turn, loads before arithmetic, at most",
+              "2048 workgroups striding over the box.  No scratch, no LDS.  FORM 0: bytes (u8 voxels, the separate normals buffer), 1: f32",
+              "with the normal bytes in .w, 2: u16, 3: four-channel f32.  VGPRs from `tools/kernel_inventory.py`:", ""]
+    lines += ["- `%s`: %d VGPRs, %d bytes of scratch" % (k, v["vgprs"], v["private_segment"]) for k, v in sorted(regs.items())] or ["- (inventory not available here)"]
+    open(out_path, "w").write("\n".join(lines) + "\n")
+    print("wrote", out_path, flush=True)
+
+
+def blend_playback(R, n, loop, bl):
+    frame = torch.zeros((SIZE * SIZE, 4), dtype=torch.float32, device="cuda")
+    st = torch.cuda.Stream()
+    bench.configure(R, "cfg3", n, SIZE, PLANES)
+    for _ in range(24):
+        timed_frame(R, frame, st)
+    seq = [(t, (t + 1) % 4, j / 5.0) for t in range(4) for j in range(5)]
+
+    def prepare(i):    # what frame i shows: a whole step, or a blend enqueued now into the output the frame before does not read
+        a, b, w = seq[i % len(seq)]
+        if w == 0:
+            return a
+        R.blend_timesteps(a, b, w, 10 + (i & 1), stream=bl.cuda_stream)
+        return 10 + (i & 1)
+    out = []
+    for label, frames in (("warm-up", len(seq)), ("timed", loop)):
+        ev = []
+        R.select_timestep(prepare(0))
+        torch.cuda.synchronize()
+        w0 = time.perf_counter()
+        for i in range(frames):
+            nxt = prepare(i + 1)
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(st)
+            R.render_device(frame.data_ptr(), None, st.cuda_stream)
+            b.record(st)
+            ev.append((a, b))
+            R.select_timestep(nxt)
+        torch.cuda.synchronize()
+        wall = (time.perf_counter() - w0) * 1e3 / frames
+        ms = [a.elapsed_time(b) for a, b in ev]
+        if label == "timed":
+            out.append("- %d frames (4 of 5 blended): frame median %.3f ms, max %.3f ms, wall %.3f ms per frame, %d blends" % (
+                frames, statistics.median(ms), max(ms), wall, int(R.stat("tblend_count"))))
+            print(out[-1], flush=True)
+    assert R.stat("slab_failures") == 0
+    return out
+
+
 def main():
-    n = int(sys.argv[1]) if len(sys.argv) > 1 else 512
-    loop = int(sys.argv[2]) if len(sys.argv) > 2 else 32
+    args = sys.argv[1:]
+    blend = "--blend" in args
+    out_path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "timestep_blend.md")
+    if "--out" in args:
+        out_path = args[args.index("--out") + 1]
+        del args[args.index("--out"):args.index("--out") + 2]
+    args = [a for a in args if a != "--blend"]
+    n = int(args[0]) if len(args) > 0 else 512
+    loop = int(args[1]) if len(args) > 1 else 32
     pkg = bench.load_package()
+    if blend:
+        return blend_leg(pkg, n, loop, out_path)
     frame = torch.zeros((SIZE * SIZE, 4), dtype=torch.float32, device="cuda")
     st, up = torch.cuda.Stream(), torch.cuda.Stream()
     R = pkg.Renderer(0)
