@@ -532,6 +532,45 @@ int smk_merge_fields_f32_device(smk_ctx *ctx, const void *d_fields_f32, int nf, 
  * finished as smk_hist2d_device's (log scale, float bins that stop at 2^24); hist is 65536 bytes in HOST memory and
  * nelts < 2 is refused as there.  d_vol_f32 needs float alignment only.  The reference has no float pipeline. */
 int smk_hist2d_f32_device(smk_ctx *ctx, const void *d_vol_f32, int nelts, int sx, int sy, int sz, unsigned char *hist);
+/* ---- the histogram and the probe of a RESIDENT time step (DESIGN.md 3b "Histogram and probe of a step").  The entries above
+ * take the raw [z][y][x][nelts] array; a step that came from a device buffer (smk_upload_timestep_device), a blended step
+ * (smk_blend_timesteps), a shard's region and SMK_U16 voxels have none, so these read what the context owns: the packed
+ * voxels of a ring slot.  `timestep` is the id of a cached step, as smk_select_timestep takes it, or SMK_STEP_CURRENT; any
+ * other value fails with "not cached", as there. */
+#define SMK_STEP_CURRENT (-1)
+/* replaces MetaVolume::hist2D's counting loop (MetaVolume.cpp:1650-1688) for that step: 65536 uint32 counts into DEVICE
+ * memory, counts[b1 * 256 + b0], overwritten, not accumulated.  Every voxel of this context's region [g0, g1) of the step is
+ * counted exactly once -- never a halo voxel, never the extra voxel or the pad column that evens out 8-byte rows; on an
+ * unsharded context the region is the whole volume, and shard regions partition it (smk_set_shard), so the sum of the ranks'
+ * counts is the unsharded context's.  Bins, b0 from channel 0 and b1 from channel 1:
+ *   SMK_U8   the byte itself: smk_hist2d_device's counts on the uploaded array;
+ *   SMK_F32  smk_hist2d_f32_device's rule: t = v * 255.0f (one fp32 multiply), NaN or t < 0 -> 0, t >= 255 -> 255, else (int)t;
+ *   SMK_U16  v / 257 in integer arithmetic = floor(255 v / 65535) exactly, 65535 -> 255; no float is involved.
+ * Refused, with the reason: no volume; nelts < 2 ("needs value and gradient channels"); a step that is not cached; a NULL
+ * d_counts.  Asynchronous, as smk_blend_timesteps: everything is enqueued on `stream` (NULL = the context's) behind the
+ * step's upload or blend, and a later upload or blend INTO that slot waits for this read.  No host synchronisation. */
+int smk_hist2d_step_device(smk_ctx *ctx, int timestep, void *d_counts, void *stream);
+/* replaces MetaVolume::hist2D (MetaVolume.cpp:1650-1688; caller TFWidgetRen::loadHist, TFWidgetRen1.cpp:660-700) for that
+ * step: the same work on the context's stream, synchronous; the 65536 counts and / or smk_hist2d's log-scaled 256 x 256 bytes
+ * into HOST memory.  At least one of the two outputs must be given. */
+int smk_hist2d_step(smk_ctx *ctx, int timestep, unsigned *counts_or_null, unsigned char *hist_or_null);
+/* replaces the scaling half of MetaVolume::hist2D (MetaVolume.cpp:1672-1688), which every histogram entry above ends with:
+ * 65536 counts -> 65536 bytes, min(count, 2^24) as float (the reference's float bins stop there), log, scaled by the maximum.
+ * Host memory only, no context: a sharded host sums its ranks' counts and finishes once.  NULL arguments fail. */
+int smk_hist2d_finish(const unsigned *counts, unsigned char *hist);
+/* replaces the data fetch of TFWidgetRen::drawProbe (TFWidgetRen1.cpp:309-595; host/TransferFunctions.cpp probe_sample) for
+ * that step: the 2 x 2 x 2 corner voxels of n cells (1..65536), synchronous.  cells[n][3]: whole-volume voxel coordinates
+ * (x, y, z) of each cell's low corner; corner i * 4 + j * 2 + k is the voxel (x + k, y + j, z + i): probe_sample's order.
+ *   raw_out[n][8][4]  the STORED values as floats, nothing rescaled: SMK_U8 the bytes 0..255; SMK_U16 channels 0 and 1 as
+ *                     0..65535, channel 2 as its stored 8-bit value 0..255, channel 3 zero; SMK_F32 the floats bit for bit;
+ *                     a channel the volume lacks is 0;
+ *   nrm_out[n][8][3]  (may be NULL) the normal bytes, (128, 128, 128) when the volume has none;
+ *   ok_out[n]         1 when all eight corners lie inside the volume AND inside the box this context stores (region + halo;
+ *                     the pad column is outside the volume), else 0 and that cell's outputs are zeros: a sharded host asks
+ *                     every rank and takes whichever answers.
+ * Refused, with the reason: no volume, a step that is not cached, a missing pointer, n out of range. */
+int smk_probe_step(smk_ctx *ctx, int timestep, const int *cells, int n, float *raw_out, unsigned char *nrm_out_or_null,
+                   int *ok_out);
 /* the bridge from the float prep entries (smk_make_vgh_device's vgh_f32, smk_merge_fields_f32_device) to SMK_U16 voxels (no
  * reference equivalent: the reference quantises to bytes): n_values floats -> n_values uint16_t, DEVICE pointers, on the
  * context's stream, synchronous like its siblings.  Per value t = v * 65535.0f (one fp32 multiply): NaN or t < 0 -> 0,

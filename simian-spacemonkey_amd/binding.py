@@ -35,7 +35,9 @@ ABI_SYMBOLS = [
     "smk_render_occluded", "smk_render_occluded_device",
     "smk_set_clip_slice",
     "smk_present_device", "smk_render_present", "smk_render_present_begin", "smk_render_present_end",
+    "smk_hist2d_step_device", "smk_hist2d_step", "smk_hist2d_finish", "smk_probe_step",
 ]
+STEP_CURRENT = -1  # SMK_STEP_CURRENT: the step the frames render
 
 # gluvvDataMode order (gluvv.h:221-235)
 GDM = {n: i for i, n in enumerate(
@@ -186,6 +188,10 @@ def load_library():
     L.smk_merge_fields_f32_device.argtypes = L.smk_merge_fields_device.argtypes
     L.smk_hist2d_f32_device.argtypes = L.smk_hist2d_device.argtypes
     L.smk_quantize_u16_device.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]
+    L.smk_hist2d_step_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.smk_hist2d_step.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.smk_hist2d_finish.argtypes = [C.c_void_p, C.c_void_p]
+    L.smk_probe_step.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.smk_synth_volume_device.argtypes = [C.c_void_p, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_int,
                                           C.c_void_p]
     L.smk_get_raycoef.argtypes = [C.c_void_p, P(RayCoef)]
@@ -709,6 +715,45 @@ class Renderer:
         out = np.zeros((256, 256), np.uint8)
         self._ck(self.L.smk_hist2d_f32_device(self.ctx, d_vol_f32, nelts, sx, sy, sz, _ptr(out)))
         return out
+
+    # -- the histogram and the probe of a resident time step (smk.h: smk_hist2d_step_device ...)
+    def hist2d_step_device(self, d_counts, step=STEP_CURRENT, stream=None):
+        """the joint (value, gradient) counts of this context's region of a cached step (default: the current one), from its
+        packed voxels: 65536 uint32 into DEVICE memory, counts[b1 * 256 + b0], enqueued on `stream` (None = the context's)"""
+        self._ck(self.L.smk_hist2d_step_device(self.ctx, int(step), d_counts, stream))
+
+    def hist2d_step(self, step=STEP_CURRENT, want="counts"):
+        """the same, synchronous, to host memory: want "counts" -> [256][256] uint32, "hist" -> the log-scaled [256][256]
+        uint8 of hist2d, "both" -> (counts, hist)"""
+        if want not in ("counts", "hist", "both"):
+            raise ValueError("want must be 'counts', 'hist' or 'both', not %r" % (want,))
+        counts = np.zeros((256, 256), np.uint32) if want != "hist" else None
+        hist = np.zeros((256, 256), np.uint8) if want != "counts" else None
+        self._ck(self.L.smk_hist2d_step(self.ctx, int(step), _ptr(counts), _ptr(hist)))
+        return (counts, hist) if want == "both" else counts if want == "counts" else hist
+
+    @staticmethod
+    def hist2d_finish(counts):
+        """[256][256] counts (a shard host's summed ranks) -> the log-scaled [256][256] uint8; host only, needs no context"""
+        counts = np.ascontiguousarray(counts, np.uint32)
+        if counts.size != 65536:
+            raise ValueError("counts must hold 65536 values, not %d" % counts.size)
+        hist = np.zeros((256, 256), np.uint8)
+        if load_library().smk_hist2d_finish(_ptr(counts), _ptr(hist)) != 0:
+            raise SmkError("smk_hist2d_finish failed")
+        return hist
+
+    def probe_step(self, cells, step=STEP_CURRENT):
+        """the 2 x 2 x 2 corner voxels of cells [n][3] (x, y, z of the low corner, whole-volume voxel coordinates) of a
+        cached step: (raw [n][8][4] float32 stored values, nrm [n][8][3] uint8, ok [n] bool); corner i * 4 + j * 2 + k is
+        voxel (x + k, y + j, z + i).  Cells this context does not hold whole come back as zeros with ok False"""
+        cells = np.ascontiguousarray(cells, np.int32).reshape(-1, 3)
+        n = cells.shape[0]
+        raw = np.zeros((n, 8, 4), np.float32)
+        nrm = np.zeros((n, 8, 3), np.uint8)
+        ok = np.zeros(n, np.int32)
+        self._ck(self.L.smk_probe_step(self.ctx, int(step), _ptr(cells), n, _ptr(raw), _ptr(nrm), _ptr(ok)))
+        return raw, nrm, ok.astype(bool)
 
     def quantize_u16_device(self, d_f32, n_values, d_u16):
         """n_values device floats -> uint16 voxels channels: (uint16)(int)(v * 65535 + .5), NaN and negatives 0, >= 1 65535"""

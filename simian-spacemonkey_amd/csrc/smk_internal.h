@@ -259,7 +259,7 @@ struct TimeStep {
   bool ready_pending = false;       // ... recorded and not yet seen complete
   hipEvent_t used = nullptr;        // the last frame that read the step
   bool used_valid = false;
-  hipEvent_t blended = nullptr;     // the last smk_blend_timesteps that read the step, on the stream it was enqueued on
+  hipEvent_t blended = nullptr;     // the last smk_blend_timesteps or step histogram that read the step, on the stream it was enqueued on
   bool blended_valid = false;
 };
 
@@ -560,3 +560,8 @@ int smk_clip_slice_stage(smk_ctx *c, const RenderParams &P, hipStream_t s);
 int smk_step_wait_ready(smk_ctx *c, hipStream_t s);
 int smk_step_mark_used(smk_ctx *c, hipStream_t s);
 void smk_free_steps(smk_ctx *c);
+// the slot that holds time step `timestep` (an id, or SMK_STEP_CURRENT), or -1; and a read of slot k by a kernel on stream s
+// that is not a frame: _begin before it is enqueued, _end behind it (the slot's next writer waits for it)
+int smk_step_slot(const smk_ctx *c, int timestep);
+int smk_step_read_begin(smk_ctx *c, int k, hipStream_t s);
+int smk_step_read_end(smk_ctx *c, int k, hipStream_t s);

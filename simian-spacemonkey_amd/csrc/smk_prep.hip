@@ -511,6 +511,13 @@ static void hist2d_finish(const unsigned *counts, unsigned char *hist) {
   for (int i = 0; i < 65536; ++i) hist[i] = (!(mx > 0) || !std::isfinite(lg[i])) ? 0 : (unsigned char)(lg[i] / mx * 255);
 }
 
+// the same step for a host that holds counts of its own (the summed counts of smk_hist2d_step's ranks); no context, no device
+extern "C" int smk_hist2d_finish(const unsigned *counts, unsigned char *hist) {
+  if (!counts || !hist) return 1;
+  hist2d_finish(counts, hist);
+  return 0;
+}
+
 extern "C" int smk_hist2d_device(smk_ctx *c, const void *d_vol, int nelts, int sx, int sy, int sz, unsigned char *hist) {
   if (!c) return 1;
   PCHK(c, hipSetDevice(c->device));

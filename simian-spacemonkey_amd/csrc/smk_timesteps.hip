@@ -12,7 +12,8 @@
 //     `ready` event there; every stream that reads the step (a frame's, the table refresh's) waits for it;
 //   - every frame records the slot's `used` event on its stream; an upload into the slot waits for it first;
 //   - smk_blend_timesteps (fractional time, below) is an upload whose source is two other slots: it waits for their `ready`
-//     events and records their `blended` events behind its kernels; whatever overwrites a slot waits for that one too.
+//     events and records their `blended` events behind its kernels; whatever overwrites a slot waits for that one too;
+//   - the histogram and the probe of a step (smk_step_hist.hip) read a slot the same way: smk_step_read_begin / _end.
 #include <math.h>
 #include <string.h>
 
@@ -89,6 +90,30 @@ static int find_step(const smk_ctx *c, int id) {
   for (size_t k = 0; k < c->ts.size(); ++k)
     if (c->ts[k].id == id) return (int)k;
   return -1;
+}
+
+int smk_step_slot(const smk_ctx *c, int timestep) {
+  if (timestep == SMK_STEP_CURRENT) return c->have_volume ? c->ts_cur : -1;
+  return timestep < 0 ? -1 : find_step(c, timestep);
+}
+
+// A kernel on stream s that READS slot k and is not a frame (the step histogram and probe, smk_step_hist.hip), ordered as
+// smk_blend_timesteps orders the reads of its sources: behind the step's upload or blend -- the event stays pending for the
+// frames -- and behind the reader before it, whose `blended` event is recorded again behind this one's kernels, so that
+// whatever overwrites the slot waits for every read.
+int smk_step_read_begin(smk_ctx *c, int k, hipStream_t s) {
+  TimeStep &T = c->ts[(size_t)k];
+  if (T.ready_pending) HIPCHK(c, hipStreamWaitEvent(s, T.ready, 0));
+  if (T.blended_valid) HIPCHK(c, hipStreamWaitEvent(s, T.blended, 0));
+  return 0;
+}
+
+int smk_step_read_end(smk_ctx *c, int k, hipStream_t s) {
+  TimeStep &T = c->ts[(size_t)k];
+  if (!T.blended) HIPCHK(c, hipEventCreateWithFlags(&T.blended, hipEventDisableTiming));
+  HIPCHK(c, hipEventRecord(T.blended, s));
+  T.blended_valid = true;
+  return 0;
 }
 
 static size_t bytes_per_step(const smk_ctx *c) {

@@ -82,6 +82,37 @@ int HipVolumeRenderer::hist2D(unsigned char *hist) {
   return 1;
 }
 
+int HipVolumeRenderer::hist2DStep(unsigned char *hist) {
+  if (!ctx || !hist) return 0;
+  if (smk_hist2d_step(ctx, SMK_STEP_CURRENT, nullptr, hist)) {
+    std::cerr << "MetaVolume::hist2D, " << smk_last_error(ctx) << std::endl;
+    return 0;
+  }
+  return 1;
+}
+
+int HipVolumeRenderer::probeStep(const float vpos[3], smktf::ProbeSample *out) {
+  if (!ctx || !m_vol || !vpos || !out) return 0;
+  const int sx = m_vol->xiSize, sy = m_vol->yiSize, sz = m_vol->ziSize;
+  float raw[8][4];
+  memset(raw, 0, sizeof raw);
+  smktf::probe_sample_raw(raw, 0, sx, sy, sz, gluvv.dmode, vpos, out);  // the cell and its test
+  if (!out->inside) return 1;
+  int ok = 0;
+  if (smk_probe_step(ctx, SMK_STEP_CURRENT, out->cell, 1, &raw[0][0], nullptr, &ok)) {
+    std::cerr << "ERROR: HipVolumeRenderer::probeStep: " << smk_last_error(ctx) << std::endl;
+    return 0;
+  }
+  if (!ok) {
+    std::cerr << "HipVolumeRenderer::probeStep: cell " << out->cell[0] << " " << out->cell[1] << " " << out->cell[2]
+              << " is not held by this context" << std::endl;
+    out->inside = false;
+    return 0;
+  }
+  smktf::probe_sample_raw(raw, m_u16 ? SMK_U16 : SMK_U8, sx, sy, sz, gluvv.dmode, vpos, out);
+  return 1;
+}
+
 int HipVolumeRenderer::createVolume(int type, Volume *v) {
   if (type != VolRen3DExt) {  // VolumeRenderer.cpp:103-112: the other modes "not implemented"
     std::cerr << "texture mapping method is not implemented" << std::endl;

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/smk.h"
+#include "TransferFunctions.h"  // smktf::ProbeSample (probeStep)
 #ifdef SMK_USE_REFERENCE_HEADERS
 #include "gluvv.h"  // the reference's own: pulls in gluvvPrimitive.h, MetaVolume.h, TLUT.h
 #else
@@ -91,6 +92,15 @@ class HipVolumeRenderer {
   void loadTransferTableRGBA();  // what TLUT::loadTransferTableRGBA did with the GL color table
   // MetaVolume::hist2D (MetaVolume.cpp:1650-1688) for the TF window's background: 256x256 bytes, 1 = ok
   int hist2D(unsigned char *hist);
+  // The same histogram of the step the frames SHOW, read from the renderer's own packed voxels (smk_hist2d_step): any voxel
+  // type -- 16-bit voxels bin as floor(255 v / 65535) --, a step that was uploaded from device memory or blended in time
+  // (HipVolumeRenderable::setTimeFraction), where the host holds no bytes to hand hist2D().  1 = ok, 0 with the reason on cerr
+  int hist2DStep(unsigned char *hist);
+  // TFWidgetRen::drawProbe's data half (TFWidgetRen1.cpp:309-595) on that step: the cell under vpos (gluvv.probe.vpos, volume
+  // coordinates in [0,1]^3) fetched from the renderer (smk_probe_step) and put through smktf::probe_sample_raw -- for 8-bit
+  // voxels smktf::probe_sample's results on the host's bytes, bit for bit.  1 = *out is filled (out->inside 0 outside the
+  // volume, as probe_sample leaves it); 0 with the reason on cerr when the fetch fails or this context does not hold the cell
+  int probeStep(const float vpos[3], smktf::ProbeSample *out);
 
  private:
   int upload(Volume *v, int n);

@@ -62,6 +62,63 @@ void probe_world_to_volume(const float pos[3], const float trans[3], const float
 // TFWidgetRen::drawProbe's data half: data = [z][y][x][nelts] bytes of the (unbricked) volume
 void probe_sample(const unsigned char *data, int nelts, int sx, int sy, int sz, int dmode, const float vpos[3], ProbeSample *out);
 
+// The same for a host that does not hold the bytes: the cell's eight voxels come FETCHED, as smk_probe_step's raw_out hands
+// them over (corner i * 4 + j * 2 + k, four channels each, the STORED values as floats; dtype = smk_dtype's values: 0 u8,
+// 1 f32, 2 u16) for the cell ((int)(vpos[0] * sx), (int)(vpos[1] * sy), (int)(vpos[2] * sz)).  probe_sample's cell test,
+// corner formulas and tri-lerp on those.  For u8 the results are probe_sample's bit for bit: the same double expressions on
+// the same integers.  AN EXTENSION for the other two types (the reference has bytes only): a channel's byte-equivalent is
+// 255 * u, u its unit value -- v / 65535 for channels 0 and 1 of u16, stored-q8 / 255 for its channel 2, the float itself
+// for f32 --, evaluated in double and put through the same formulas.  (Inline: HipVolumeRenderer::probeStep uses it, and the
+// hosts that link HipVolumeRenderer.cpp do not all link TransferFunctions.cpp.)
+inline void probe_sample_raw(const float raw[8][4], int dtype, int sx, int sy, int sz, int dmode, const float vpos[3], ProbeSample *out) {
+  ProbeSample &s = *out;
+  const int px = (int)(vpos[0] * sx), py = (int)(vpos[1] * sy), pz = (int)(vpos[2] * sz);
+  const float fpos[3] = {vpos[0] * sx, vpos[1] * sy, vpos[2] * sz};
+  s.cell[0] = px; s.cell[1] = py; s.cell[2] = pz;
+  for (int i = 0; i < 8; ++i) {
+    s.corners[i][0] = s.corners[i][1] = s.corners[i][2] = 0;
+    s.hessian_pos[i] = 0;
+  }
+  s.value[0] = s.value[1] = s.value[2] = 0;
+  s.inside = !((px < 1) || (px > (sx - 2)) || (py < 1) || (py > (sy - 2)) || (pz < 1) || (pz > (sz - 2)));
+  if (!s.inside) return;
+  for (int n = 0; n < 8; ++n) {
+    double v[3];  // the byte-equivalents of the first three channels
+    for (int e = 0; e < 3; ++e)
+      v[e] = dtype == 0 ? (double)raw[n][e] : dtype == 1 ? 255.0 * (double)raw[n][e] : 255.0 * ((double)raw[n][e] / (e < 2 ? 65535.0 : 255.0));
+    float *c = s.corners[n];
+    switch (dmode) {
+      case DM_V1:
+        c[0] = (float)(v[0] / 255.0);
+        break;
+      case DM_V1G: case DM_V2: case DM_V2G:
+        c[0] = (float)(v[0] / 255.0);
+        c[1] = (float)(v[1] / 255.0);
+        break;
+      case DM_V2GH: case DM_V3: case DM_V3G: case DM_V4:
+      case DM_VGH: case DM_V1GH: case DM_VGH_VG: case DM_VGH_V: {
+        c[0] = (float)(v[0] / 255.0);
+        c[1] = (float)(v[1] / 255.0);
+        float h = (float)(v[2] / 85.0 - 1);
+        h = h > 0 ? (float)__builtin_sqrt(h) : (float)-__builtin_sqrt(-h);
+        s.hessian_pos[n] = (float)((h + 1) / 2.0);
+        c[2] = (float)(v[2] / 169.0);
+        break;
+      }
+      default: break;
+    }
+  }
+  const float fx = fpos[0] - (int)fpos[0], fy = fpos[1] - (int)fpos[1], fz = fpos[2] - (int)fpos[2];
+  for (int e = 0; e < 3; ++e) {
+    const float x1 = s.corners[0][e] + (float)(s.corners[1][e] - s.corners[0][e]) * fx;
+    const float x2 = s.corners[2][e] + (float)(s.corners[3][e] - s.corners[2][e]) * fx;
+    const float x3 = s.corners[4][e] + (float)(s.corners[5][e] - s.corners[4][e]) * fx;
+    const float x4 = s.corners[6][e] + (float)(s.corners[7][e] - s.corners[6][e]) * fx;
+    const float xy1 = x1 + (x2 - x1) * fy, xy2 = x3 + (x4 - x3) * fy;
+    s.value[e] = (xy1 + (xy2 - xy1) * fz);
+  }
+}
+
 // ... and its brush half (:497-560): where the brush widget goes for this sample; `slider` = gluvv.probe.slider
 void place_brush(LevWidgetState *brush, Brush kind, int dmode, const ProbeSample &s, float slider);
 
