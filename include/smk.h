@@ -133,8 +133,10 @@ int smk_select_timestep(smk_ctx *ctx, int timestep);
  *   a bit for bit and w == 1 b (every integer field, every finite float); a == b is allowed and yields a copy (every integer
  *   field exactly; a float within 2.5 * 2^-24 of itself, as u + w need not be 1).
  * Normals are NOT normalised again: a blend in time shortens them as the trilinear fetch does in space.  G and H of a blend
- * are the blends of G and H, not derivatives of the blended scalar: a host that wants those blends scalars and runs the
- * data-preparation entries on the result.
+ * are the blends of G and H, not derivatives of the blended scalar: a host that wants those blends scalars, reads the
+ * blended scalar back with smk_download_timestep_device, runs the data-preparation entries (smk_make_vgh_device,
+ * smk_normals_*_device, smk_merge_fields_*_device) on that array and uploads the result as another step
+ * (smk_upload_timestep_device) -- all on the device ("Derivatives of a blend").
  * Refused, with the reason: no volume; step_a or step_b not cached; step_out < 0; step_out equal to step_a or step_b (there
  * is no in-place form); w not finite or outside [0, 1]; no slot for the output.  A cached step_out is overwritten in place,
  * as by an upload (the current step too: the next frame shows the blend); otherwise it takes a slot by smk_upload_timestep's
@@ -571,6 +573,42 @@ int smk_hist2d_finish(const unsigned *counts, unsigned char *hist);
  * Refused, with the reason: no volume, a step that is not cached, a missing pointer, n out of range. */
 int smk_probe_step(smk_ctx *ctx, int timestep, const int *cells, int n, float *raw_out, unsigned char *nrm_out_or_null,
                    int *ok_out);
+/* ---- a resident time step read back: raw voxels and normals from the packed voxels of a ring slot, the inverse of the
+ * upload's pack (DESIGN.md 3b "Reading a step back").  These stand in for MetaVolume::writeAll / Volume::writeVol
+ * (MetaVolume.cpp:99-126, 963-1000), which write the host's currentData / currentGrad: a step uploaded from device memory,
+ * a blended step and a shard's region have neither, so what is read is what the context owns -- the slot's packed voxels,
+ * and the separate normals of four-channel f32; never the x-major copy.  `timestep` as for smk_hist2d_step_device. */
+/* the box smk_download_timestep* returns: this context's region [g0, g1) -- origin = g0, size = g1 - g0 in voxels (x, y, z)
+ * -- and the type of what comes back.  Unsharded: origin 0, size = the volume.  Any out pointer may be NULL.  Stands in for
+ * the sizes writeAll puts into the .trex (MetaVolume.cpp:963-1000).  Refused without a volume. */
+int smk_get_timestep_box(smk_ctx *ctx, int origin[3], int size[3], int *nelts, smk_dtype *dtype, int *has_normals);
+/* stands in for Volume::writeVol's source (MetaVolume.cpp:99-126, 963-1000) for that step, into DEVICE memory of this
+ * context's GPU.  The box is the region, exactly smk_hist2d_step_device's set of voxels: never a halo voxel, never the extra
+ * voxel or the pad column that evens out 8-byte rows; shard regions partition the volume, so the ranks' boxes placed at
+ * their origins assemble it with nothing written twice.
+ *   d_data  [sz][sy][sx][nelts] of the step's dtype -- unsigned char, float, or uint16_t in host byte order;
+ *   d_grad  (may be NULL) [sz][sy][sx][3] unsigned char;
+ * both dense, no padding; d_data needs its element's alignment only (anything less is refused), d_grad none.  EXACTLY
+ * sx * sy * sz * nelts * sizeof(element) and sx * sy * sz * 3 bytes are written: no byte before or after either buffer is
+ * touched, whatever its alignment.
+ * Values are the stored fields, nothing rescaled:
+ *   SMK_U8   the channel bytes;
+ *   SMK_F32  the floats bit for bit -- NaN payloads, infinities and -0 included;
+ *   SMK_U16  channels 0 and 1 as their 16 bits; channel 2 as 257 * q, q the stored 8-bit field.  That is the limit of the
+ *            TYPE (the packed voxel keeps 8 bits of a third channel, smk.h SMK_U16), not of the download; and since
+ *            q8(257 q) = (65535 q + 32767) / 65535 = q, uploading the result stores the same voxel again;
+ *   normals  the three normal bytes; a step without normals gives (128, 128, 128), as smk_probe_step does.
+ * So download(upload(x)) == x bit for bit for u8, f32 and the first two u16 channels, and upload(download(step)) into a
+ * fresh context packs identical voxels: frames and step histograms are bit-identical.
+ * Asynchronous, with smk_hist2d_step_device's ordering: everything is enqueued on `stream` (NULL = the context's) behind the
+ * step's upload or blend, and the slot's reader event is recorded behind it, so a later upload or blend INTO that slot
+ * waits for this read.  It neither holds up nor is held up by the frames that render the step.  No host synchronisation.
+ * Refused, with the reason: no volume; a step that is not cached; a NULL d_data. */
+int smk_download_timestep_device(smk_ctx *ctx, int timestep, void *d_data, void *d_grad_or_null, void *stream);
+/* stands in for MetaVolume::writeAll + Volume::writeVol (MetaVolume.cpp:99-126, 963-1000) for that step: the same work on
+ * the context's stream into staging device buffers of the box's size, copied out to HOST memory; synchronous.  `data` needs
+ * no alignment.  Refused as above, and -- with the bytes named -- when the staging buffers do not fit in free device memory. */
+int smk_download_timestep(smk_ctx *ctx, int timestep, void *data, unsigned char *grad_or_null);
 /* the bridge from the float prep entries (smk_make_vgh_device's vgh_f32, smk_merge_fields_f32_device) to SMK_U16 voxels (no
  * reference equivalent: the reference quantises to bytes): n_values floats -> n_values uint16_t, DEVICE pointers, on the
  * context's stream, synchronous like its siblings.  Per value t = v * 65535.0f (one fp32 multiply): NaN or t < 0 -> 0,

@@ -36,6 +36,7 @@ ABI_SYMBOLS = [
     "smk_set_clip_slice",
     "smk_present_device", "smk_render_present", "smk_render_present_begin", "smk_render_present_end",
     "smk_hist2d_step_device", "smk_hist2d_step", "smk_hist2d_finish", "smk_probe_step",
+    "smk_get_timestep_box", "smk_download_timestep_device", "smk_download_timestep",
 ]
 STEP_CURRENT = -1  # SMK_STEP_CURRENT: the step the frames render
 
@@ -192,6 +193,9 @@ def load_library():
     L.smk_hist2d_step.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     L.smk_hist2d_finish.argtypes = [C.c_void_p, C.c_void_p]
     L.smk_probe_step.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.smk_get_timestep_box.argtypes = [C.c_void_p, P(C.c_int), P(C.c_int), P(C.c_int), P(C.c_int), P(C.c_int)]
+    L.smk_download_timestep_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.smk_download_timestep.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     L.smk_synth_volume_device.argtypes = [C.c_void_p, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_int,
                                           C.c_void_p]
     L.smk_get_raycoef.argtypes = [C.c_void_p, P(RayCoef)]
@@ -754,6 +758,29 @@ class Renderer:
         ok = np.zeros(n, np.int32)
         self._ck(self.L.smk_probe_step(self.ctx, int(step), _ptr(cells), n, _ptr(raw), _ptr(nrm), _ptr(ok)))
         return raw, nrm, ok.astype(bool)
+
+    # -- a resident time step read back (smk.h: smk_get_timestep_box, smk_download_timestep_device, smk_download_timestep)
+    def timestep_box(self):
+        """(origin (x, y, z), size (sx, sy, sz), nelts, numpy dtype, has_normals) of what download_timestep returns: this
+        context's region of the volume"""
+        o, s = (C.c_int * 3)(), (C.c_int * 3)()
+        ne, dt, hn = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._ck(self.L.smk_get_timestep_box(self.ctx, o, s, C.byref(ne), C.byref(dt), C.byref(hn)))
+        return tuple(o), tuple(s), ne.value, np.dtype((np.uint8, np.float32, np.uint16)[dt.value]), bool(hn.value)
+
+    def download_timestep_device(self, d_data, d_grad=None, step=STEP_CURRENT, stream=None):
+        """the raw voxels [sz][sy][sx][nelts] (and, with d_grad, the normal bytes [sz][sy][sx][3]) of this context's region of
+        a cached step (default: the current one) into DEVICE memory, enqueued on `stream` (None = the context's)"""
+        self._ck(self.L.smk_download_timestep_device(self.ctx, int(step), d_data, d_grad, stream))
+
+    def download_timestep(self, step=STEP_CURRENT, want_grad=True):
+        """the same, synchronous, to host memory: (data [sz][sy][sx][nelts] of the step's dtype, grad [sz][sy][sx][3] uint8 or
+        None); a step without normals gives 128s"""
+        _, (sx, sy, sz), ne, dt, _ = self.timestep_box()
+        data = np.zeros((sz, sy, sx, ne), dt)
+        grad = np.zeros((sz, sy, sx, 3), np.uint8) if want_grad else None
+        self._ck(self.L.smk_download_timestep(self.ctx, int(step), _ptr(data), _ptr(grad)))
+        return data, grad
 
     def quantize_u16_device(self, d_f32, n_values, d_u16):
         """n_values device floats -> uint16 voxels channels: (uint16)(int)(v * 65535 + .5), NaN and negatives 0, >= 1 65535"""

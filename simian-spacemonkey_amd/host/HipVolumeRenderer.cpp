@@ -10,6 +10,9 @@
 #include <climits>
 #include <cstdio>
 #include <iostream>
+#include <string>
+
+#include "VolumeFiles.h"  // smkfiles::write_trex / write_nrrd (saveTimeStep)
 
 static void build_modelview(double mv[16]);  // LookAt * T(trans) * R(xform) * T(-size/2)
 static void build_world_modelview(double mv[16]);
@@ -110,6 +113,28 @@ int HipVolumeRenderer::probeStep(const float vpos[3], smktf::ProbeSample *out) {
     return 0;
   }
   smktf::probe_sample_raw(raw, m_u16 ? SMK_U16 : SMK_U8, sx, sy, sz, gluvv.dmode, vpos, out);
+  return 1;
+}
+
+int HipVolumeRenderer::downloadStep(std::vector<unsigned char> *data, std::vector<unsigned char> *grad, int origin[3], int size[3]) {
+  if (!ctx || !data) return 0;
+  int o[3], s[3], nelts = 0;
+  smk_dtype dt = SMK_U8;
+  if (smk_get_timestep_box(ctx, o, s, &nelts, &dt, nullptr)) {
+    std::cerr << "ERROR: HipVolumeRenderer::downloadStep: " << smk_last_error(ctx) << std::endl;
+    return 0;
+  }
+  const size_t nvox = (size_t)s[0] * (size_t)s[1] * (size_t)s[2];
+  data->resize(nvox * (size_t)nelts * (dt == SMK_U8 ? 1 : dt == SMK_U16 ? 2 : 4));
+  if (grad) grad->resize(nvox * 3);
+  if (smk_download_timestep(ctx, SMK_STEP_CURRENT, data->data(), grad ? grad->data() : nullptr)) {
+    std::cerr << "ERROR: HipVolumeRenderer::downloadStep: " << smk_last_error(ctx) << std::endl;
+    return 0;
+  }
+  for (int a = 0; a < 3; ++a) {
+    if (origin) origin[a] = o[a];
+    if (size) size[a] = s[a];
+  }
   return 1;
 }
 
@@ -393,6 +418,55 @@ void HipVolumeRenderable::showTimeFraction() {
   }
   tblend_id = id;
   tblend_next ^= 1;
+}
+
+int HipVolumeRenderable::saveTimeStep(const char *prefix) {
+  if (!go || !volren || !prefix) return 0;
+  if (showTimeStep()) return 0;  // (the step -- or the blend -- the next draw() shows is the one that is saved)
+  smk_dtype dt = SMK_U8;
+  int nelts = 0;
+  if (smk_get_timestep_box(volren->context(), nullptr, nullptr, &nelts, &dt, nullptr)) {
+    std::cerr << "ERROR: HipVolumeRenderable::saveTimeStep: " << smk_last_error(volren->context()) << std::endl;
+    return 0;
+  }
+  if (dt != SMK_U8) {
+    std::cerr << "ERROR: HipVolumeRenderable::saveTimeStep: no 16-bit / float writer: MetaVolume::writeAll and genVGH write 8-bit voxels "
+                 "(HipVolumeRenderer::downloadStep hands over the arrays)" << std::endl;
+    return 0;
+  }
+  std::vector<unsigned char> data;
+  int o[3], s[3];
+  if (!volren->downloadStep(&data, nullptr, o, s)) return 0;
+  // the box's extent: its share of the volume's
+  const int N[3] = {gluvv.mv->xiSize, gluvv.mv->yiSize, gluvv.mv->ziSize};
+  const float F[3] = {gluvv.mv->xfSize, gluvv.mv->yfSize, gluvv.mv->zfSize};
+  float fs[3];
+  for (int a = 0; a < 3; ++a) fs[a] = N[a] > 0 ? F[a] * (float)s[a] / (float)N[a] : F[a];
+  std::string err;
+  size_t w;
+  if (nelts == 1) {  // writeAll: the .trex and one raw brick
+    MetaVolume mv;
+    Volume v;
+    v.xiSize = mv.xiSize = s[0]; v.yiSize = mv.yiSize = s[1]; v.ziSize = mv.ziSize = s[2];
+    v.xfSize = mv.xfSize = fs[0]; v.yfSize = mv.yfSize = fs[1]; v.zfSize = mv.zfSize = fs[2];
+    v.xiPos = v.yiPos = v.ziPos = 0;
+    v.xfPos = v.yfPos = v.zfPos = 0;
+    v.currentData = data.data();
+    mv.nelts = 1;
+    mv.numSubVols = 1;
+    mv.volumes = &v;
+    w = smkfiles::write_trex(prefix, mv, true, &err);
+    mv.volumes = nullptr;  // (both objects leave scope owning nothing)
+    mv.numSubVols = 0;
+    v.currentData = nullptr;
+  } else {
+    w = smkfiles::write_nrrd((std::string(prefix) + ".nrrd").c_str(), data.data(), nelts, s, fs, nelts == 3 ? "vgh" : "v", &err);
+  }
+  if (!w) {
+    std::cerr << "ERROR: HipVolumeRenderable::saveTimeStep: " << err << std::endl;
+    return 0;
+  }
+  return 1;
 }
 
 void HipVolumeRenderable::draw() {

@@ -101,6 +101,13 @@ class HipVolumeRenderer {
   // voxels smktf::probe_sample's results on the host's bytes, bit for bit.  1 = *out is filled (out->inside 0 outside the
   // volume, as probe_sample leaves it); 0 with the reason on cerr when the fetch fails or this context does not hold the cell
   int probeStep(const float vpos[3], smktf::ProbeSample *out);
+  // The voxels of the step the frames SHOW, read back from the renderer (smk_download_timestep): what Volume::writeVol
+  // (MetaVolume.cpp:99-126) takes from currentData / currentGrad, for a step the host holds no array of -- one that was
+  // blended in time or uploaded from device memory.  data: [sz][sy][sx][nelts] of the step's type (unsigned char, or
+  // uint16_t with useU16), sized in BYTES; grad_or_null: [sz][sy][sx][3] normal bytes, 128s when the volume has none;
+  // origin / size (either may be null): the box that came back, in voxels (x, y, z) -- the whole volume unless the context is
+  // a shard.  1 = ok, 0 with the reason on cerr
+  int downloadStep(std::vector<unsigned char> *data, std::vector<unsigned char> *grad_or_null, int origin[3], int size[3]);
 
  private:
   int upload(Volume *v, int n);
@@ -147,6 +154,13 @@ class HipVolumeRenderable final : public gluvvPrimitive {
   // steps resident (gluvv.mv->tstepCache >= 2); a blend that is refused -- step timestep + 1 not resident -- is reported once
   // on stderr and the frames stay on the whole step until the step or the fraction moves.
   int setTimeFraction(float f);
+  // MetaVolume::writeAll + Volume::writeVol (MetaVolume.cpp:99-126, 963-1000) for the step draw() shows -- a blend made by
+  // setTimeFraction included --, read back from the renderer (HipVolumeRenderer::downloadStep).  A one-channel 8-bit step
+  // goes to "<prefix>.trex" plus the raw brick, one sub-volume, as writeAll writes it (smkfiles::write_trex); a
+  // multi-channel 8-bit step to "<prefix>.nrrd" (smkfiles::write_nrrd, genVGH's writer).  16-bit and float steps are
+  // refused -- no 16-bit / float writer exists --: their arrays are downloadStep's.  Call after init().  1 = written, 0 with
+  // the reason on cerr
+  int saveTimeStep(const char *prefix);
   int running() const { return go; }
   HipVolumeRenderer *renderer() { return volren; }  // the inner interface (VolumeRenderable keeps it private; a host that
                                                     // draws sub-boxes or slice quads needs it)

@@ -11,7 +11,12 @@ Frame times are HIP-event times on the render stream (median); the loop also rep
      bytes both move, and the blend's time against the upload's times the ratio of their bytes; then, for f32, playback
      over the four resident steps with 4 blended frames between neighbours, each blend enqueued on a second stream beside
      the frame before it.  Writes the note profiles/timestep_blend.md (--out PATH: elsewhere).
-    python tools/timestep_time.py --blend [--out PATH] [volume edge] [loop frames]"""
+    python tools/timestep_time.py --blend [--out PATH] [volume edge] [loop frames]
+  4. --download: reading a step back (smk_download_timestep_device).  For u8, u16 and f32 steps: the download alone and
+     smk_upload_timestep_device of the same step alone (as in 3.), the bytes both move, their ratio; then, for f32, playback
+     over the four resident steps with and without a download of the shown step on a second stream beside each frame.
+     Writes the note profiles/step_download.md (--out PATH: elsewhere).
+    python tools/timestep_time.py --download [--out PATH] [volume edge] [loop frames]"""
 import os
 import statistics
 import sys
@@ -60,8 +65,8 @@ def typed_steps(R, n, dtype):
     return out, {"u8": 0, "f32": 1, "u16": 2}[dtype]
 
 
-def blend_kernel_registers():
-    """{kernel: vgprs} of the blend kernels from the built library (tools/kernel_inventory.py), or {} where that fails"""
+def kernel_registers():
+    """{kernel: its entry} of the built library's kernels (tools/kernel_inventory.py), or {} where that fails"""
     import json
     import subprocess
     import tempfile
@@ -74,7 +79,7 @@ def blend_kernel_registers():
             inv = json.load(open(os.path.join(d, "k.json")))
     except Exception:
         return {}
-    return {k: v for k, v in inv.items() if "smk_k_blend" in k}
+    return inv
 
 
 def blend_leg(pkg, n, loop, out_path):
@@ -119,13 +124,107 @@ def blend_leg(pkg, n, loop, out_path):
               "(w = 0.2 .. 0.8) towards the next one; the blend of frame i + 1 is enqueued on a second stream before frame i, into the",
               "output id frame i does not show.  DESIGN.md 3b has 0.72 ms per frame for whole resident steps and 1.79 ms with the next",
               "step uploaded beside the frame.", ""] + play
-    regs = blend_kernel_registers()
+    regs = {k: v for k, v in kernel_registers().items() if "smk_k_blend" in k}
     lines += ["", "## Kernels", "", "`smk_k_blend_steps<FORM>`: 256 lanes, 4 x 16-byte units of each source per lane and turn, loads before arithmetic, at most",
               "2048 workgroups striding over the box.  No scratch, no LDS.  FORM 0: bytes (u8 voxels, the separate normals buffer), 1: f32",
               "with the normal bytes in .w, 2: u16, 3: four-channel f32.  VGPRs from `tools/kernel_inventory.py`:", ""]
     lines += ["- `%s`: %d VGPRs, %d bytes of scratch" % (k, v["vgprs"], v["private_segment"]) for k, v in sorted(regs.items())] or ["- (inventory not available here)"]
     open(out_path, "w").write("\n".join(lines) + "\n")
     print("wrote", out_path, flush=True)
+
+
+def download_leg(pkg, n, loop, out_path):
+    lines = ["# Reading a step back: `smk_download_timestep_device` on one MI355X", "",
+             "Written by `tools/timestep_time.py --download %d %d`.  Config 3's step (%d^3, three channels with normals), HIP-event" % (n, loop, n),
+             "times round the entry's work on its stream, median of 9 after 3 warm-up calls.  Bytes: the download reads the stored",
+             "volume and writes the caller's voxels and normals (stored + source); the upload, the yardstick measured in the same",
+             "run, reads the caller's arrays, writes the stored volume, and its brick summary reads that again (source + 2 x stored).",
+             "Nothing is gated: the expectation is the upload's time times the ratio of the bytes.", "",
+             "| voxels | stored | source | download ms | download TB/s | upload ms | upload TB/s | byte ratio | download / upload |",
+             "|---|---|---|---|---|---|---|---|---|"]
+    bl = torch.cuda.Stream()
+    dims = (n, n, n)
+    play = []
+    for dtype in ("u8", "u16", "f32"):
+        R = pkg.Renderer(0)
+        try:
+            steps, dt = typed_steps(R, n, dtype)
+            R.set_timestep_cache(4)
+            R.upload_volume_device(steps[0][0].data_ptr(), dims, 3, dt, steps[0][1].data_ptr())
+            for t in (1, 2, 3):
+                R.upload_timestep_device(t, steps[t][0].data_ptr(), dims, 3, dt, steps[t][1].data_ptr(), stream=bl.cuda_stream)
+            torch.cuda.synchronize()
+            esz = {"f32": 4, "u8": 1, "u16": 2}[dtype]
+            stored = n ** 3 * (16 if dtype == "f32" else 8)
+            source = n ** 3 * (3 * esz + 3)
+            out_d = torch.zeros(n ** 3 * 3 * esz, dtype=torch.uint8, device="cuda")
+            out_g = torch.zeros(n ** 3 * 3, dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            td = [event_ms(bl, lambda: R.download_timestep_device(out_d.data_ptr(), out_g.data_ptr(), 1, bl.cuda_stream)) for _ in range(12)][3:]
+            tu = [event_ms(bl, lambda: R.upload_timestep_device(3, steps[3][0].data_ptr(), dims, 3, dt, steps[3][1].data_ptr(),
+                                                                stream=bl.cuda_stream)) for _ in range(12)][3:]
+            # what came back is what went up (u16: the third channel to its stored 8 bits)
+            src_d = steps[1][0].contiguous().view(torch.uint8).reshape(-1)
+            if dtype == "u16":
+                a16, b16 = out_d.view(torch.int16).view(-1, 3), steps[1][0].view(-1, 3)
+                assert torch.equal(a16[:, :2], b16[:, :2]), "download differs from the uploaded step"
+            else:
+                assert torch.equal(out_d, src_d), "download differs from the uploaded step"
+            assert torch.equal(out_g, steps[1][1].contiguous().view(torch.uint8).reshape(-1)), "normals differ from the uploaded step"
+            d_ms, u_ms = statistics.median(td), statistics.median(tu)
+            ratio = (stored + source) / (source + 2.0 * stored)
+            lines.append("| %s | %.0f MiB | %.0f MiB | %.3f (min %.3f, max %.3f) | %.2f | %.3f (min %.3f, max %.3f) | %.2f | %.3f | %.3f |" % (
+                dtype, stored / 2 ** 20, source / 2 ** 20, d_ms, min(td), max(td), (stored + source) / d_ms / 1e9, u_ms, min(tu), max(tu),
+                (source + 2.0 * stored) / u_ms / 1e9, ratio, d_ms / u_ms))
+            print(lines[-1], flush=True)
+            if dtype == "f32":
+                play = download_playback(R, n, loop, bl, out_d, out_g)
+        finally:
+            R.close()
+            torch.cuda.synchronize()
+    lines += ["", "## Playback", "", "Config 3's scene (f32, 1024^2 x 512 planes) over the four resident steps, one frame per step, first alone and then",
+              "with a download of the shown step enqueued on a second stream beside each frame.", ""] + play
+    regs = {k: v for k, v in kernel_registers().items() if "smk_k_unpack" in k}
+    lines += ["", "## Kernels", "", "`smk_k_unpack_step<L>` (L 0: u8, 1: f32, 2: u16 voxels): 256 lanes, 4 x 16-byte units per lane and chunk, the next chunk's",
+              "loads issued before this chunk's bytes are staged in LDS; whole 16-byte lines of the output go out as one store each, the",
+              "ragged ends of a chunk's run byte by byte; at most 2048 workgroups striding over the chunks.  From `tools/kernel_inventory.py`:", ""]
+    lines += ["- `%s`: %d VGPRs, %d bytes of scratch" % (k, v["vgprs"], v["private_segment"]) for k, v in sorted(regs.items())] or ["- (inventory not available here)"]
+    open(out_path, "w").write("\n".join(lines) + "\n")
+    print("wrote", out_path, flush=True)
+
+
+def download_playback(R, n, loop, dl, out_d, out_g):
+    frame = torch.zeros((SIZE * SIZE, 4), dtype=torch.float32, device="cuda")
+    st = torch.cuda.Stream()
+    bench.configure(R, "cfg3", n, SIZE, PLANES)
+    for _ in range(24):
+        timed_frame(R, frame, st)
+    out = []
+    for label, with_download in (("whole resident steps", False), ("with a download of the shown step beside each frame", True)):
+        for phase, frames in (("warm-up", 8), ("timed", loop)):
+            ev = []
+            torch.cuda.synchronize()
+            w0 = time.perf_counter()
+            cur = R.timesteps()[0]
+            for _ in range(frames):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record(st)
+                R.render_device(frame.data_ptr(), None, st.cuda_stream)
+                b.record(st)
+                ev.append((a, b))
+                if with_download:
+                    R.download_timestep_device(out_d.data_ptr(), out_g.data_ptr(), stream=dl.cuda_stream)
+                cur = (cur + 1) % 4
+                R.select_timestep(cur)
+            torch.cuda.synchronize()
+            wall = (time.perf_counter() - w0) * 1e3 / frames
+            ms = [a.elapsed_time(b) for a, b in ev]
+            if phase == "timed":
+                out.append("- %s: %d frames, frame median %.3f ms, max %.3f ms, wall %.3f ms per frame" % (
+                    label, frames, statistics.median(ms), max(ms), wall))
+                print(out[-1], flush=True)
+    assert R.stat("slab_failures") == 0
+    return out
 
 
 def blend_playback(R, n, loop, bl):
@@ -169,15 +268,18 @@ def blend_playback(R, n, loop, bl):
 
 def main():
     args = sys.argv[1:]
-    blend = "--blend" in args
-    out_path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "timestep_blend.md")
+    blend, download = "--blend" in args, "--download" in args
+    out_path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                            "step_download.md" if download else "timestep_blend.md")
     if "--out" in args:
         out_path = args[args.index("--out") + 1]
         del args[args.index("--out"):args.index("--out") + 2]
-    args = [a for a in args if a != "--blend"]
+    args = [a for a in args if a not in ("--blend", "--download")]
     n = int(args[0]) if len(args) > 0 else 512
     loop = int(args[1]) if len(args) > 1 else 32
     pkg = bench.load_package()
+    if download:
+        return download_leg(pkg, n, loop, out_path)
     if blend:
         return blend_leg(pkg, n, loop, out_path)
     frame = torch.zeros((SIZE * SIZE, 4), dtype=torch.float32, device="cuda")
