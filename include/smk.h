@@ -136,7 +136,8 @@ int smk_select_timestep(smk_ctx *ctx, int timestep);
  * are the blends of G and H, not derivatives of the blended scalar: a host that wants those blends scalars, reads the
  * blended scalar back with smk_download_timestep_device, runs the data-preparation entries (smk_make_vgh_device,
  * smk_normals_*_device, smk_merge_fields_*_device) on that array and uploads the result as another step
- * (smk_upload_timestep_device) -- all on the device ("Derivatives of a blend").
+ * (smk_upload_timestep_device) -- all on the device ("Derivatives of a blend"); smk_derive_timestep
+ * below is that recipe as one asynchronous call inside the ring.
  * Refused, with the reason: no volume; step_a or step_b not cached; step_out < 0; step_out equal to step_a or step_b (there
  * is no in-place form); w not finite or outside [0, 1]; no slot for the output.  A cached step_out is overwritten in place,
  * as by an upload (the current step too: the next frame shows the blend); otherwise it takes a slot by smk_upload_timestep's
@@ -146,6 +147,38 @@ int smk_select_timestep(smk_ctx *ctx, int timestep);
  * that render the step wait for it on their own streams, and a later upload or blend into slot a or b waits for this one's
  * reads.  No host synchronisation. */
 int smk_blend_timesteps(smk_ctx *ctx, int step_a, int step_b, float w, int step_out, void *stream);
+/* Derivatives of a step (no reference counterpart: genVGH and MetaVolume::normalsVGH run on the host before the renderer
+ * starts).  Step `step_out` becomes the VGH step of channel 0 of the cached step `step_src`: with s the stored channel 0 of
+ * step_src over the whole volume (the u8 byte, the 16-bit value, or the float), the output's stored fields are exactly those
+ * that smk_upload_timestep_device packs from what the data-preparation entries make of s -- the recipe of INTEGRATION.md 5,
+ * bit for bit:
+ *   ring SMK_U8 : channels vgh_u8 = smk_make_vgh_device(s, its type, compat); normals smk_normals_vgh_device(vgh_u8, 3, blur)
+ *   ring SMK_F32: channels vgh_f32 of the same call; normals smk_normals_f32_device(vgh_f32, 3, blur)
+ *   ring SMK_U16: channels smk_quantize_u16_device(vgh_f32), the third then stored as the pack's 8-bit field; normals
+ *                 smk_normals_f32_device(vgh_f32, 3, blur), from the floats BEFORE quantisation
+ * So: channel 0 of the output is makeVGH's RESCALED V, the affine map of the step's own interior min/max onto 0..255, not a
+ * copy of the source; the 1-voxel border of the volume is 0 in all three channels; the normals' source is that output V
+ * channel, border zeros included, not the input scalar; H is NaN where the gradient vanishes, and the entries' rules apply
+ * (a NaN never wins an extreme, the byte cast gives 0, the float H is 0); non-finite gradients in the f32 normals give
+ * (128, 128, 128); a context without normals keeps (128, 128, 128).  The pad column of a padded 8-byte box holds zeros, as
+ * after an upload; the 16 bytes behind the box are not touched; the brick summaries are made for the result.
+ * Refused, with the reason: no volume; a sharded context (the stencil reaches 2 voxels beyond a voxel and the scaling needs
+ * the whole volume's extremes: neither fits region + halo); nelts != 3; a volume thinner than 3 voxels; step_src not cached;
+ * step_out < 0; step_out == step_src (the stencil has no in-place form); no slot for the output.  A refused call changes
+ * nothing.  A cached step_out is overwritten in place (the current step too); otherwise it takes a slot by
+ * smk_upload_timestep's rule that is neither the source's nor the current step's -- two slots, three when the current step
+ * is a third.
+ * Asynchronous, ordered exactly as smk_blend_timesteps: everything is enqueued on `stream` (NULL = the context's) behind the
+ * source's upload or blend and its last reader's, and behind the output slot's last frame, reader and writer; the output's
+ * readiness is recorded there, and what overwrites the source later waits for this read.  No host synchronisation, no
+ * device-to-host copy: the six extremes stay in a few device words that belong to the OUTPUT slot, seeded on the stream. */
+int smk_derive_timestep(smk_ctx *ctx, int step_src, int step_out, int compat, int blur, void *stream);
+/* The same from a dense scalar [sz][sy][sx] in DEVICE memory -- the whole volume; scalar_dtype any of SMK_U8, SMK_U16,
+ * SMK_F32, whatever the ring's type -- into step `timestep`, by smk_upload_timestep_device's slot rule.  `stream` must also
+ * order the reads of d_scalar.  Refused in addition: d_scalar NULL or below its element's alignment; a scalar_dtype outside
+ * the three; sizes that are not the series'. */
+int smk_upload_timestep_scalar_device(smk_ctx *ctx, int timestep, const void *d_scalar, smk_dtype scalar_dtype, int sx, int sy,
+                                      int sz, int compat, int blur, void *stream);
 /* introspection: the current step (-1: no volume), the cached ids oldest written first (min(cap, *n) of them; ids_out may
  * be NULL), their number */
 int smk_get_timesteps(smk_ctx *ctx, int *current, int *ids_out, int cap, int *n);

@@ -30,7 +30,7 @@ ABI_SYMBOLS = [
     "smk_get_light_history", "smk_shadow_exports_device", "smk_shadow_entries_device", "smk_shadow_exchange_local",
     "smk_shard_light_order", "smk_get_shadow_margin",
     "smk_set_timestep_cache", "smk_upload_timestep", "smk_upload_timestep_device", "smk_select_timestep",
-    "smk_get_timesteps", "smk_blend_timesteps",
+    "smk_get_timesteps", "smk_blend_timesteps", "smk_derive_timestep", "smk_upload_timestep_scalar_device",
     "smk_composite_over_depth_device", "smk_exchange_partial_depth", "smk_exchange_frame_depth", "smk_exchange_frame_local_depth",
     "smk_render_occluded", "smk_render_occluded_device",
     "smk_set_clip_slice",
@@ -138,6 +138,9 @@ def load_library():
     L.smk_select_timestep.argtypes = [C.c_void_p, C.c_int]
     L.smk_get_timesteps.argtypes = [C.c_void_p, P(C.c_int), P(C.c_int), C.c_int, P(C.c_int)]
     L.smk_blend_timesteps.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p]
+    L.smk_derive_timestep.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.smk_upload_timestep_scalar_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                    C.c_int, C.c_int, C.c_void_p]
     L.smk_set_shard.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.smk_set_clip.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
     L.smk_set_clip_plane.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double)]
@@ -369,6 +372,17 @@ class Renderer:
         smk_blend_timesteps: fractional time), enqueued on `stream` (a hipStream_t handle; None = the context's stream);
         select_timestep(out) shows it"""
         self._ck(self.L.smk_blend_timesteps(self.ctx, int(a), int(b), float(w), int(out), stream))
+
+    def derive_timestep(self, src, out, compat=1, blur=0, stream=None):
+        """step `out` becomes the VGH step of channel 0 of the cached step `src`: makeVGH's V, G and H and their normals
+        (smk.h smk_derive_timestep), enqueued on `stream` (a hipStream_t handle; None = the context's stream)"""
+        self._ck(self.L.smk_derive_timestep(self.ctx, int(src), int(out), int(compat), int(blur), stream))
+
+    def upload_timestep_scalar_device(self, timestep, dptr, scalar_dtype, dims, compat=1, blur=0, stream=None):
+        """the same from a dense scalar [sz][sy][sx] in device memory (scalar_dtype 0 u8, 1 f32, 2 u16; dims (sx, sy, sz) are
+        the series'): the caller keeps the scalar alive until the stream has passed the call"""
+        self._ck(self.L.smk_upload_timestep_scalar_device(self.ctx, int(timestep), dptr, int(scalar_dtype), int(dims[0]),
+                                                          int(dims[1]), int(dims[2]), int(compat), int(blur), stream))
 
     def timesteps(self):
         """(current step or -1, the cached ids oldest written first)"""

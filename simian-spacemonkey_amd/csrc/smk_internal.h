@@ -261,6 +261,7 @@ struct TimeStep {
   bool used_valid = false;
   hipEvent_t blended = nullptr;     // the last smk_blend_timesteps or step histogram that read the step, on the stream it was enqueued on
   bool blended_valid = false;
+  int *derive_st = nullptr;         // six ordered-int extremes between the two passes of a derive INTO this slot (smk_step_derive.hip)
 };
 
 // One frame on its way to the host (smk_present.hip; DESIGN.md "Present"): everything a frame in flight needs that the
@@ -565,3 +566,11 @@ void smk_free_steps(smk_ctx *c);
 int smk_step_slot(const smk_ctx *c, int timestep);
 int smk_step_read_begin(smk_ctx *c, int k, hipStream_t s);
 int smk_step_read_end(smk_ctx *c, int k, hipStream_t s);
+// A step written by kernels on stream s from what is on the device already (smk_blend_timesteps, smk_step_derive.hip).
+// _output_slot: the slot step `id` takes -- a cached id's own, else one by the ring's rule that is neither slot ka nor kb
+// (the sources; -1: none) nor the current step's; -1 when the ring has fewer than *need slots.  _write_begin: the kernels on s
+// are ordered behind the slot's last readers and writers, its buffers are made, it is marked empty.  _write_end: the slot
+// holds step `id`, its `ready` event is recorded on s, and a current step overwritten in place is switched to
+int smk_step_output_slot(const smk_ctx *c, int id, int ka, int kb, int *need);
+int smk_step_write_begin(smk_ctx *c, int k, hipStream_t s);
+int smk_step_write_end(smk_ctx *c, int k, int id, hipStream_t s);

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "smk_internal.h"
+#include "smk_prep_device.h"
 
 #define PCHK(ctx, call)                                                                   \
   do {                                                                                    \
@@ -33,25 +34,7 @@
 
 // ------------------------------------------------------------------------------- helpers
 
-// order-preserving float <-> int map so min/max can use integer atomics
-__device__ __forceinline__ int f2o(float f) {
-  int i = __float_as_int(f);
-  return i >= 0 ? i : i ^ 0x7fffffff;
-}
-__host__ __device__ __forceinline__ float o2f(int i) {
-  int j = i >= 0 ? i : i ^ 0x7fffffff;
-#ifdef __HIP_DEVICE_COMPILE__
-  return __int_as_float(j);
-#else
-  float f;
-  memcpy(&f, &j, 4);
-  return f;
-#endif
-}
-
-struct VghStats {  // ordered-int encoded
-  int dmin, dmax, gmin, gmax, hmin, hmax;
-};
+// (f2o / o2f, VghStats and the arithmetic shared with smk_step_derive.hip: smk_prep_device.h)
 
 template <int DT>
 __device__ __forceinline__ float ld(const void *d, size_t i) {
@@ -65,10 +48,6 @@ __device__ __forceinline__ void grad_at(const void *d, int sx, int sy, int i, in
   g[0] = ld<DT>(d, o + 1) - ld<DT>(d, o - 1);
   g[1] = ld<DT>(d, o + sx) - ld<DT>(d, o - sx);
   g[2] = ld<DT>(d, o + sxy) - ld<DT>(d, o - sxy);
-}
-
-__device__ __forceinline__ bool is_border(int sx, int sy, int sz, int i, int j, int k) {
-  return (k < 1) || (k > sx - 2) || (j < 1) || (j > sy - 2) || (i < 1) || (i > sz - 2);
 }
 
 // gradient of a neighbour: zero on the 1-voxel border (:79-84)
@@ -87,7 +66,6 @@ __device__ __forceinline__ void gh_at(const void *d, int sx, int sy, int sz, int
                                       float &gm, float &hs) {
   float g[3];
   grad_at<DT>(d, sx, sy, i, j, k, g);
-  gm = sqrtf(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
   float xp[3], xm[3], yp[3], ym[3], zp[3], zm[3];
   grad_nb<DT>(d, sx, sy, sz, i, j, k + 1, xp);
   grad_nb<DT>(d, sx, sy, sz, i, j, k - 1, xm);
@@ -95,81 +73,23 @@ __device__ __forceinline__ void gh_at(const void *d, int sx, int sy, int sz, int
   grad_nb<DT>(d, sx, sy, sz, i, j - 1, k, ym);
   grad_nb<DT>(d, sx, sy, sz, i + 1, j, k, zp);
   grad_nb<DT>(d, sx, sy, sz, i - 1, j, k, zm);
-  float h[9];
-  h[0] = xp[0] - xm[0];
-  h[1] = yp[0] - ym[0];
-  h[2] = zp[0] - zm[0];
-  h[3] = xp[1] - xm[1];
-  h[4] = yp[1] - ym[1];
-  h[5] = zp[1] - zm[1];
-  h[6] = xp[2] - xm[2];
-  h[7] = yp[2] - ym[2];
-  h[8] = zp[2] - zm[2];
-  float tg[3] = {g[0] / gm, g[1] / gm, g[2] / gm};
-  float tv0 = tg[0] * h[0] + tg[1] * h[1] + tg[2] * h[2];
-  // the reference drops h[4] here (genVGH/main.cpp:135-137); compat keeps the typo
-  float tv1 = compat ? tg[0] * h[3] + tg[1] + tg[2] * h[5] : tg[0] * h[3] + tg[1] * h[4] + tg[2] * h[5];
-  float tv2 = tg[0] * h[6] + tg[1] * h[7] + tg[2] * h[8];
-  hs = tg[0] * tv0 + tg[1] * tv1 + tg[2] * tv2;
+  gh_from_grads(g, xp, xm, yp, ym, zp, zm, compat, gm, hs);
 }
-
-__device__ __forceinline__ int wave_min(int v) {
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ int wave_max(int v) {
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
-  return v;
-}
-
-#define ORD_POS_INF 0x7f800000
-// f2o(-inf) = 0xff800000 ^ 0x7fffffff = 0x807fffff
 
 template <int DT>
 __global__ __launch_bounds__(256) void smk_k_vgh_stats(const void *d, int sx, int sy, int sz, int compat,
                                                        VghStats *st) {
   size_t n = (size_t)sx * sy * sz;
-  int dmin = ORD_POS_INF, dmax = (int)0x807fffff, gmin = ORD_POS_INF, gmax = (int)0x807fffff;
-  int hmin = ORD_POS_INF, hmax = (int)0x807fffff;
+  VghRunning run;
   for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (size_t)gridDim.x * blockDim.x) {
     int k = (int)(t % sx), j = (int)((t / sx) % sy), i = (int)(t / ((size_t)sx * sy));
     if (is_border(sx, sy, sz, i, j, k)) continue;
     float gm, hs;
     gh_at<DT>(d, sx, sy, sz, i, j, k, compat, gm, hs);
     float dv = ld<DT>(d, t);
-    dmin = min(dmin, f2o(dv));
-    dmax = max(dmax, f2o(dv));
-    gmin = min(gmin, f2o(gm));
-    gmax = max(gmax, f2o(gm));
-    if (hs == hs) {  // NaN (zero gradient) never wins the reference's MAX/MIN macros
-      hmin = min(hmin, f2o(hs));
-      hmax = max(hmax, f2o(hs));
-    }
+    run.take(dv, gm, hs);
   }
-  dmin = wave_min(dmin);
-  dmax = wave_max(dmax);
-  gmin = wave_min(gmin);
-  gmax = wave_max(gmax);
-  hmin = wave_min(hmin);
-  hmax = wave_max(hmax);
-  if ((threadIdx.x & 63) == 0) {
-    atomicMin(&st->dmin, dmin);
-    atomicMax(&st->dmax, dmax);
-    atomicMin(&st->gmin, gmin);
-    atomicMax(&st->gmax, gmax);
-    atomicMin(&st->hmin, hmin);
-    atomicMax(&st->hmax, hmax);
-  }
-}
-
-__device__ __forceinline__ double affine_d(double i, double x, double I, double o, double O) {
-  return ((O) - (o)) * ((x) - (i)) / ((I) - (i)) + (o);
-}
-
-// (unsigned char) cast as x86 does it: truncate through int32, low byte; NaN/out of range -> 0
-__device__ __forceinline__ unsigned char uc_cast(double x) {
-  if (!(x > -2147483649.0 && x < 2147483648.0)) return 0;
-  return (unsigned char)((int)x & 0xff);
+  run.publish(st);
 }
 
 template <int DT>
@@ -184,23 +104,11 @@ __global__ __launch_bounds__(256) void smk_k_vgh_quant(const void *d, int sx, in
     if (!is_border(sx, sy, sz, i, j, k)) {
       float gm, hs;
       gh_at<DT>(d, sx, sy, sz, i, j, k, compat, gm, hs);
-      // genVGH/main.cpp:164-175
-      double vq = affine_d(dmin, ld<DT>(d, t), dmax, 0, 255);
-      double gq = affine_d(gmmin, gm, gmmax, 0, 255);
-      double hq;
-      if (hs < 0) {
-        float th = (float)affine_d(hmin, hs, 0, 0, 1);
-        hq = affine_d(0, th, 1, 0, 255 / 3);
-      } else {
-        float th = (float)affine_d(0, hs, hmax, 0, 1);
-        hq = affine_d(0, th, 1, 255 / 3, 255 / 3 * 2);
-      }
-      q0 = uc_cast(vq);
-      q1 = uc_cast(gq);
-      q2 = uc_cast(hq);
-      f0 = (float)(vq / 255.0);
-      f1 = (float)(gq / 255.0);
-      f2 = (hq == hq) ? (float)(hq / 255.0) : 0.0f;
+      unsigned char q[3];
+      float f[3];
+      vgh_scale(ld<DT>(d, t), gm, hs, dmin, dmax, gmmin, gmmax, hmin, hmax, q, f);
+      q0 = q[0], q1 = q[1], q2 = q[2];
+      f0 = f[0], f1 = f[1], f2 = f[2];
     }
     if (o8) {
       o8[t * 3 + 0] = q0;
@@ -225,7 +133,7 @@ extern "C" int smk_make_vgh_device(smk_ctx *c, const void *d, smk_dtype dt, int 
   }
   VghStats *st = nullptr;
   PCHK(c, hipMalloc((void **)&st, sizeof(VghStats)));
-  VghStats init = {ORD_POS_INF, (int)0x807fffff, ORD_POS_INF, (int)0x807fffff, ORD_POS_INF, (int)0x807fffff};
+  VghStats init = {ORD_POS_INF, ORD_NEG_INF, ORD_POS_INF, ORD_NEG_INF, ORD_POS_INF, ORD_NEG_INF};
   PCHK(c, hipMemcpy(st, &init, sizeof init, hipMemcpyHostToDevice));
   size_t n = (size_t)sx * sy * sz;
   unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 256 * 16);
@@ -257,16 +165,10 @@ extern "C" int smk_make_vgh_device(smk_ctx *c, const void *d, smk_dtype dt, int 
 
 // ------------------------------------------------------------------------------- floats -> u16 voxels
 
-// smk_quantize_u16_device (smk.h): t = v * 65535 (one fp32 multiply); NaN or t < 0 -> 0, t >= 65535 -> 65535, else
-// (uint16)(int)(t + 0.5f) -- one fp32 add, then truncation
+// smk_quantize_u16_device (smk.h): quant_u16 (smk_prep_device.h) of every value
 __global__ __launch_bounds__(256) void smk_k_quantize_u16(const float *in, size_t n, unsigned short *out) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const float t = in[i] * 65535.0f;
-    unsigned short q;
-    if (!(t >= 0.0f)) q = 0;
-    else if (t >= 65535.0f) q = 65535;
-    else q = (unsigned short)(int)(t + 0.5f);
-    out[i] = q;
+    out[i] = quant_u16(in[i]);
   }
 }
 
@@ -301,53 +203,13 @@ __device__ __forceinline__ void nrm_grad(const unsigned char *d, int ne, int sx,
   g[2] = (float)((int)d[(o + sxy) * ne] - (int)d[(o - sxy) * ne]);
 }
 
-// scalebiasN (VectorMath.h:1133-1148) with the +1 -> 255 clamp
-__device__ __forceinline__ void nrm_store(float g[3], unsigned char *out) {
-  float len = sqrtf(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
-  if (len > 0) {
-    g[0] /= len;
-    g[1] /= len;
-    g[2] /= len;
-  }
-#pragma unroll
-  for (int e = 0; e < 3; ++e) {
-    float s = g[e] * 128 + 128;
-    out[e] = s >= 255.0f ? 255 : (unsigned char)((int)s & 0xff);
-  }
-}
-
 __global__ __launch_bounds__(256) void smk_k_normals(const unsigned char *d, int ne, int sx, int sy, int sz, int blur,
                                                      unsigned char *out) {
   size_t n = (size_t)sx * sy * sz;
   for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (size_t)gridDim.x * blockDim.x) {
     int k = (int)(t % sx), j = (int)((t / sx) % sy), i = (int)(t / ((size_t)sx * sy));
     float g[3];
-    if (!blur) {
-      nrm_grad(d, ne, sx, sy, sz, i, j, k, g);
-    } else {
-      // blurV3D is a scatter from every interior voxel to its 27 neighbours in raster order
-      // of the SOURCE (VectorMath.h:1232-1266).  Gathering the same terms in the same order
-      // (source raster order == ascending di,dj,dk) reproduces the float sums bit for bit.
-      const float w[4] = {1.0f, .3f, .2f, .1f};  // MetaVolume.cpp:1316
-      float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-      for (int di = -1; di <= 1; ++di)
-        for (int dj = -1; dj <= 1; ++dj)
-          for (int dk = -1; dk <= 1; ++dk) {
-            int si = i + di, sj = j + dj, sk = k + dk;
-            // only interior voxels scatter (loops run 1..n-2)
-            if (si < 1 || si > sz - 2 || sj < 1 || sj > sy - 2 || sk < 1 || sk > sx - 2) continue;
-            float s[3];
-            nrm_grad(d, ne, sx, sy, sz, si, sj, sk, s);
-            float ww = w[(di != 0) + (dj != 0) + (dk != 0)];
-            a0 = a0 + ww * s[0];
-            a1 = a1 + ww * s[1];
-            a2 = a2 + ww * s[2];
-          }
-      const float div = 1.0f + 6 * .3f + 12 * .2f + 8 * .1f;
-      g[0] = a0 / div;
-      g[1] = a1 / div;
-      g[2] = a2 / div;
-    }
+    nrm_gradient(blur, sx, sy, sz, i, j, k, g, [&](int si, int sj, int sk, float s[3]) { nrm_grad(d, ne, sx, sy, sz, si, sj, sk, s); });
     nrm_store(g, out + t * 3);
   }
 }
@@ -594,19 +456,6 @@ extern "C" int smk_hist2d(smk_ctx *c, const smk_volume_desc *b, int nb, int nelt
 // the order written, so a NumPy float32 restatement gives the same bits.  What float data adds is values that are
 // not finite: they never reach scalebiasN (such a voxel gets the zero vector's bytes) and never win the maximum.
 
-__device__ __forceinline__ bool finite3(const float g[3]) {
-  return __builtin_isfinite(g[0]) && __builtin_isfinite(g[1]) && __builtin_isfinite(g[2]);
-}
-
-// nrm_store behind the float rule: a gradient with a component that is not finite is stored as the zero vector
-__device__ __forceinline__ void nrm_store_f32(float g[3], unsigned char *out) {
-  if (!finite3(g)) {
-    out[0] = out[1] = out[2] = 128;
-    return;
-  }
-  nrm_store(g, out);
-}
-
 // derivative3DVGH on floats: one fp32 subtraction per axis of channel 0, 0 on the border
 __device__ __forceinline__ void nrm_grad_f32(const float *d, int ne, int sx, int sy, int sz, int i, int j, int k,
                                              float g[3]) {
@@ -628,28 +477,7 @@ __global__ __launch_bounds__(256) void smk_k_normals_f32(const float *d, int ne,
   for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (size_t)gridDim.x * blockDim.x) {
     int k = (int)(t % sx), j = (int)((t / sx) % sy), i = (int)(t / ((size_t)sx * sy));
     float g[3];
-    if (!BLUR) {
-      nrm_grad_f32(d, ne, sx, sy, sz, i, j, k, g);
-    } else {
-      const float w[4] = {1.0f, .3f, .2f, .1f};  // MetaVolume.cpp:1316
-      float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-      for (int di = -1; di <= 1; ++di)
-        for (int dj = -1; dj <= 1; ++dj)
-          for (int dk = -1; dk <= 1; ++dk) {
-            int si = i + di, sj = j + dj, sk = k + dk;
-            if (si < 1 || si > sz - 2 || sj < 1 || sj > sy - 2 || sk < 1 || sk > sx - 2) continue;
-            float s[3];
-            nrm_grad_f32(d, ne, sx, sy, sz, si, sj, sk, s);
-            float ww = w[(di != 0) + (dj != 0) + (dk != 0)];
-            a0 = a0 + ww * s[0];
-            a1 = a1 + ww * s[1];
-            a2 = a2 + ww * s[2];
-          }
-      const float div = 1.0f + 6 * .3f + 12 * .2f + 8 * .1f;
-      g[0] = a0 / div;
-      g[1] = a1 / div;
-      g[2] = a2 / div;
-    }
+    nrm_gradient(BLUR, sx, sy, sz, i, j, k, g, [&](int si, int sj, int sk, float s[3]) { nrm_grad_f32(d, ne, sx, sy, sz, si, sj, sk, s); });
     nrm_store_f32(g, out + t * 3);
   }
 }

@@ -1,0 +1,199 @@
+// smk_prep_device.h -- the device arithmetic of the data-preparation kernels (smk_prep.hip), shared with the kernels that
+// derive a resident time step in place (smk_step_derive.hip): one statement of every expression, so that both give the same
+// bits.  Plain fp32, doubles inside affine_d, one rounding per operation in the order written (-ffp-contract=off).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+// order-preserving float <-> int map so min/max can use integer atomics
+__device__ __forceinline__ int f2o(float f) {
+  int i = __float_as_int(f);
+  return i >= 0 ? i : i ^ 0x7fffffff;
+}
+__host__ __device__ __forceinline__ float o2f(int i) {
+  int j = i >= 0 ? i : i ^ 0x7fffffff;
+#ifdef __HIP_DEVICE_COMPILE__
+  return __int_as_float(j);
+#else
+  float f;
+  memcpy(&f, &j, 4);
+  return f;
+#endif
+}
+
+struct VghStats {  // ordered-int encoded
+  int dmin, dmax, gmin, gmax, hmin, hmax;
+};
+
+#define ORD_POS_INF 0x7f800000
+#define ORD_NEG_INF ((int)0x807fffff)  // f2o(-inf) = 0xff800000 ^ 0x7fffffff
+
+__device__ __forceinline__ bool is_border(int sx, int sy, int sz, int i, int j, int k) {
+  return (k < 1) || (k > sx - 2) || (j < 1) || (j > sy - 2) || (i < 1) || (i > sz - 2);
+}
+
+// gradient magnitude + second derivative along the gradient (genVGH/main.cpp:110-146) from the un-normalised central
+// differences g of a voxel and those of its six neighbours (zero where the neighbour lies on the 1-voxel border)
+__device__ __forceinline__ void gh_from_grads(const float g[3], const float xp[3], const float xm[3], const float yp[3],
+                                              const float ym[3], const float zp[3], const float zm[3], int compat, float &gm,
+                                              float &hs) {
+  gm = sqrtf(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
+  float h[9];
+  h[0] = xp[0] - xm[0];
+  h[1] = yp[0] - ym[0];
+  h[2] = zp[0] - zm[0];
+  h[3] = xp[1] - xm[1];
+  h[4] = yp[1] - ym[1];
+  h[5] = zp[1] - zm[1];
+  h[6] = xp[2] - xm[2];
+  h[7] = yp[2] - ym[2];
+  h[8] = zp[2] - zm[2];
+  float tg[3] = {g[0] / gm, g[1] / gm, g[2] / gm};
+  float tv0 = tg[0] * h[0] + tg[1] * h[1] + tg[2] * h[2];
+  // the reference drops h[4] here (genVGH/main.cpp:135-137); compat keeps the typo
+  float tv1 = compat ? tg[0] * h[3] + tg[1] + tg[2] * h[5] : tg[0] * h[3] + tg[1] * h[4] + tg[2] * h[5];
+  float tv2 = tg[0] * h[6] + tg[1] * h[7] + tg[2] * h[8];
+  hs = tg[0] * tv0 + tg[1] * tv1 + tg[2] * tv2;
+}
+
+__device__ __forceinline__ int wave_min(int v) {
+  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
+  return v;
+}
+__device__ __forceinline__ int wave_max(int v) {
+  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
+  return v;
+}
+
+// a thread's running extremes of the interior voxels it visits, and their way into the device words
+struct VghRunning {
+  int dmin = ORD_POS_INF, dmax = ORD_NEG_INF, gmin = ORD_POS_INF, gmax = ORD_NEG_INF, hmin = ORD_POS_INF, hmax = ORD_NEG_INF;
+  __device__ __forceinline__ void take(float dv, float gm, float hs) {
+    dmin = min(dmin, f2o(dv));
+    dmax = max(dmax, f2o(dv));
+    gmin = min(gmin, f2o(gm));
+    gmax = max(gmax, f2o(gm));
+    if (hs == hs) {  // NaN (zero gradient) never wins the reference's MAX/MIN macros
+      hmin = min(hmin, f2o(hs));
+      hmax = max(hmax, f2o(hs));
+    }
+  }
+  // wave reduction, then one ordered-int atomic per wave and extreme (every lane of the wave calls this)
+  __device__ __forceinline__ void publish(VghStats *st) {
+    dmin = wave_min(dmin);
+    dmax = wave_max(dmax);
+    gmin = wave_min(gmin);
+    gmax = wave_max(gmax);
+    hmin = wave_min(hmin);
+    hmax = wave_max(hmax);
+    if ((threadIdx.x & 63) == 0) {
+      atomicMin(&st->dmin, dmin);
+      atomicMax(&st->dmax, dmax);
+      atomicMin(&st->gmin, gmin);
+      atomicMax(&st->gmax, gmax);
+      atomicMin(&st->hmin, hmin);
+      atomicMax(&st->hmax, hmax);
+    }
+  }
+};
+
+__device__ __forceinline__ double affine_d(double i, double x, double I, double o, double O) {
+  return ((O) - (o)) * ((x) - (i)) / ((I) - (i)) + (o);
+}
+
+// (unsigned char) cast as x86 does it: truncate through int32, low byte; NaN/out of range -> 0
+__device__ __forceinline__ unsigned char uc_cast(double x) {
+  if (!(x > -2147483649.0 && x < 2147483648.0)) return 0;
+  return (unsigned char)((int)x & 0xff);
+}
+
+// makeVGH's scaling of an interior voxel (genVGH/main.cpp:164-175): the bytes q and the floats f of V, G and H
+__device__ __forceinline__ void vgh_scale(float dv, float gm, float hs, float dmin, float dmax, float gmmin, float gmmax,
+                                          float hmin, float hmax, unsigned char q[3], float f[3]) {
+  double vq = affine_d(dmin, dv, dmax, 0, 255);
+  double gq = affine_d(gmmin, gm, gmmax, 0, 255);
+  double hq;
+  if (hs < 0) {
+    float th = (float)affine_d(hmin, hs, 0, 0, 1);
+    hq = affine_d(0, th, 1, 0, 255 / 3);
+  } else {
+    float th = (float)affine_d(0, hs, hmax, 0, 1);
+    hq = affine_d(0, th, 1, 255 / 3, 255 / 3 * 2);
+  }
+  q[0] = uc_cast(vq);
+  q[1] = uc_cast(gq);
+  q[2] = uc_cast(hq);
+  f[0] = (float)(vq / 255.0);
+  f[1] = (float)(gq / 255.0);
+  f[2] = (hq == hq) ? (float)(hq / 255.0) : 0.0f;
+}
+
+// smk_quantize_u16_device (smk.h): t = v * 65535 (one fp32 multiply); NaN or t < 0 -> 0, t >= 65535 -> 65535, else
+// (uint16)(int)(t + 0.5f) -- one fp32 add, then truncation
+__device__ __forceinline__ unsigned short quant_u16(float v) {
+  const float t = v * 65535.0f;
+  if (!(t >= 0.0f)) return 0;
+  if (t >= 65535.0f) return 65535;
+  return (unsigned short)(int)(t + 0.5f);
+}
+
+// scalebiasN (VectorMath.h:1133-1148) with the +1 -> 255 clamp
+__device__ __forceinline__ void nrm_store(float g[3], unsigned char *out) {
+  float len = sqrtf(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
+  if (len > 0) {
+    g[0] /= len;
+    g[1] /= len;
+    g[2] /= len;
+  }
+#pragma unroll
+  for (int e = 0; e < 3; ++e) {
+    float s = g[e] * 128 + 128;
+    out[e] = s >= 255.0f ? 255 : (unsigned char)((int)s & 0xff);
+  }
+}
+
+__device__ __forceinline__ bool finite3(const float g[3]) {
+  return __builtin_isfinite(g[0]) && __builtin_isfinite(g[1]) && __builtin_isfinite(g[2]);
+}
+
+// nrm_store behind the float rule: a gradient with a component that is not finite is stored as the zero vector
+__device__ __forceinline__ void nrm_store_f32(float g[3], unsigned char *out) {
+  if (!finite3(g)) {
+    out[0] = out[1] = out[2] = 128;
+    return;
+  }
+  nrm_store(g, out);
+}
+
+// The normal's gradient at voxel (i, j, k) = (z, y, x) of an sx x sy x sz volume from grad(si, sj, sk, s[3]), the central
+// differences of channel 0 at an INTERIOR voxel (derivative3DVGH, VectorMath.h:874-899; 0 on the border).  Blurred: blurV3D is
+// a scatter from every interior voxel to its 27 neighbours in raster order of the SOURCE (VectorMath.h:1232-1266).  Gathering
+// the same terms in the same order (source raster order == ascending di, dj, dk) reproduces the float sums bit for bit.
+template <class Grad>
+__device__ __forceinline__ void nrm_gradient(int blur, int sx, int sy, int sz, int i, int j, int k, float g[3], Grad grad) {
+  if (!blur) {
+    if (is_border(sx, sy, sz, i, j, k)) g[0] = g[1] = g[2] = 0.f;
+    else grad(i, j, k, g);
+    return;
+  }
+  const float w[4] = {1.0f, .3f, .2f, .1f};  // MetaVolume.cpp:1316
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+  for (int di = -1; di <= 1; ++di)
+    for (int dj = -1; dj <= 1; ++dj)
+      for (int dk = -1; dk <= 1; ++dk) {
+        int si = i + di, sj = j + dj, sk = k + dk;
+        // only interior voxels scatter (loops run 1..n-2)
+        if (si < 1 || si > sz - 2 || sj < 1 || sj > sy - 2 || sk < 1 || sk > sx - 2) continue;
+        float s[3];
+        grad(si, sj, sk, s);
+        float ww = w[(di != 0) + (dj != 0) + (dk != 0)];
+        a0 = a0 + ww * s[0];
+        a1 = a1 + ww * s[1];
+        a2 = a2 + ww * s[2];
+      }
+  const float div = 1.0f + 6 * .3f + 12 * .2f + 8 * .1f;
+  g[0] = a0 / div;
+  g[1] = a1 / div;
+  g[2] = a2 / div;
+}

@@ -1,0 +1,316 @@
+// smk_step_derive.hip -- V, G, H and normals of a scalar made INSIDE the time-step ring (smk.h: smk_derive_timestep,
+// smk_upload_timestep_scalar_device; DESIGN.md 3b "Derivatives of a step").
+//
+// genVGH's makeVGH (genVGH/main.cpp:56-182) and MetaVolume::normalsVGH (MetaVolume.cpp:1274-1324) are host programs that run
+// before the renderer starts.  A step whose scalar is new on the device -- channel 0 of a blend of two resident steps, or what
+// a simulation left in device memory -- gets here what smk_make_vgh_device, smk_quantize_u16_device, smk_normals_*_device and
+// smk_upload_timestep_device would make of it, bit for bit, as two kernels on the caller's stream that write the packed
+// voxels of a ring slot: no scratch arrays, no host wait.
+//
+// Both kernels work on tiles of DV_TX x DV_TY x DV_TZ voxels of the stored box from an LDS copy of the scalar AS FLOATS with
+// a 2-voxel apron on every side: H reads the gradients of the six neighbours, each a central difference (2 voxels), and a
+// blurred normal reads the differences of the OUTPUT V channel at the 27 neighbours (2 voxels again).
+//   pass 1 (smk_k_derive_stats): gm, hs and the scalar of every interior voxel -> the six extremes, ordered-int atomics into
+//          the OUTPUT slot's words (TimeStep::derive_st), which a one-thread kernel seeded on the stream;
+//   pass 2 (smk_k_derive_write): the reference's +-1e8 seeds applied to those words, the scaled V of every tile voxel (0 on the
+//          volume's border and outside it) into a second LDS tile, then per voxel gm and hs again, the scaling, the normal
+//          from the V tile, and one 8- or 16-byte store of the packed voxel.
+// The arithmetic is smk_prep.hip's, through smk_prep_device.h.
+#include <algorithm>
+
+#include "smk_internal.h"
+#include "smk_prep_device.h"
+
+namespace {
+
+// where the scalar comes from: a dense array of the type (the values of smk_dtype), or channel 0 of a slot's packed voxels
+enum { DS_U8 = 0, DS_F32 = 1, DS_U16 = 2, DS_PK_U8 = 3, DS_PK_U16 = 4, DS_PK_F32 = 5 };
+
+constexpr int DV_TX = 32, DV_TY = 8, DV_TZ = 8, DV_AP = 2;
+constexpr int DV_LX = DV_TX + 2 * DV_AP, DV_LY = DV_TY + 2 * DV_AP, DV_LZ = DV_TZ + 2 * DV_AP;
+constexpr int DV_LN = DV_LX * DV_LY * DV_LZ;  // 5184 floats
+constexpr int DV_SY = DV_LX, DV_SZ = DV_LX * DV_LY;
+static_assert(DV_TX * DV_TY == 256 && DV_TX % 2 == 0 && DV_AP % 2 == 0, "a thread per (x, y) of the tile; tile rows start on even x");
+
+struct DeriveParams {
+  const void *src;  // the dense scalar [N2][N1][N0], or the source slot's packed voxels [D2][D1][D0]
+  void *out;        // the output slot's packed voxels
+  VghStats *st;     // the output slot's extremes
+  int N[3], D[3];   // the volume; the stored box (origin 0: an unsharded context), D >= N with a pad column or row of 8-byte voxels.
+                    // The kernels rely on D[2] == N[2], on D == N for f32 voxels and on an even D[0] otherwise: derive_refusals checks
+  int compat, blur, normals;
+};
+
+// the tile of the scalar around (x0, y0, z0), apron included; what lies outside the volume is not data: 0, and never used
+template <int SRC>
+__device__ __forceinline__ void dv_load_tile(const DeriveParams &P, int x0, int y0, int z0, float *S) {
+  if (SRC == DS_PK_U8 || SRC == DS_PK_U16) {  // two 8-byte voxels per 16-byte unit (x0 - DV_AP is even, and so is D[0])
+    constexpr int UPR = DV_LX / 2;
+    for (int u = threadIdx.x; u < UPR * DV_LY * DV_LZ; u += 256) {
+      const int cu = u % UPR, row = u / UPR, ly = row % DV_LY, lz = row / DV_LY;
+      const int X = x0 - DV_AP + 2 * cu, Y = y0 - DV_AP + ly, Z = z0 - DV_AP + lz;
+      float a = 0.f, b = 0.f;
+      if (X >= 0 && X < P.N[0] && Y >= 0 && Y < P.N[1] && Z >= 0 && Z < P.N[2]) {
+        const uint4 v = ((const uint4 *)P.src)[(((size_t)Z * P.D[1] + Y) * P.D[0] + X) >> 1];
+        const uint32_t mask = SRC == DS_PK_U8 ? 0xffu : 0xffffu;
+        a = (float)(v.x & mask);
+        if (X + 1 < P.N[0]) b = (float)(v.z & mask);
+      }
+      S[row * DV_LX + 2 * cu] = a;
+      S[row * DV_LX + 2 * cu + 1] = b;
+    }
+  } else {
+    for (int t = threadIdx.x; t < DV_LN; t += 256) {
+      const int lx = t % DV_LX, row = t / DV_LX, ly = row % DV_LY, lz = row / DV_LY;
+      const int X = x0 - DV_AP + lx, Y = y0 - DV_AP + ly, Z = z0 - DV_AP + lz;
+      float a = 0.f;
+      if (X >= 0 && X < P.N[0] && Y >= 0 && Y < P.N[1] && Z >= 0 && Z < P.N[2]) {
+        if (SRC == DS_PK_F32) {
+          a = __uint_as_float(((const uint4 *)P.src)[((size_t)Z * P.D[1] + Y) * P.D[0] + X].x);
+        } else {
+          const size_t o = ((size_t)Z * P.N[1] + Y) * P.N[0] + X;
+          a = SRC == DS_U8 ? (float)((const unsigned char *)P.src)[o] : SRC == DS_U16 ? (float)((const unsigned short *)P.src)[o] : ((const float *)P.src)[o];
+        }
+      }
+      S[t] = a;
+    }
+  }
+}
+
+// un-normalised central differences at tile index l (genVGH/main.cpp:86-88): x, then y, then z
+__device__ __forceinline__ void dv_grad(const float *S, int l, float g[3]) {
+  g[0] = S[l + 1] - S[l - 1];
+  g[1] = S[l + DV_SY] - S[l - DV_SY];
+  g[2] = S[l + DV_SZ] - S[l - DV_SZ];
+}
+
+// ... of a neighbour: zero on the volume's 1-voxel border (:79-84)
+__device__ __forceinline__ void dv_grad_nb(const DeriveParams &P, const float *S, int l, int Z, int Y, int X, float g[3]) {
+  if (is_border(P.N[0], P.N[1], P.N[2], Z, Y, X)) g[0] = g[1] = g[2] = 0.f;
+  else dv_grad(S, l, g);
+}
+
+// gm and hs of the INTERIOR voxel (Z, Y, X) at tile index l
+__device__ __forceinline__ void dv_gh(const DeriveParams &P, const float *S, int l, int Z, int Y, int X, float &gm, float &hs) {
+  float g[3], xp[3], xm[3], yp[3], ym[3], zp[3], zm[3];
+  dv_grad(S, l, g);
+  dv_grad_nb(P, S, l + 1, Z, Y, X + 1, xp);
+  dv_grad_nb(P, S, l - 1, Z, Y, X - 1, xm);
+  dv_grad_nb(P, S, l + DV_SY, Z, Y + 1, X, yp);
+  dv_grad_nb(P, S, l - DV_SY, Z, Y - 1, X, ym);
+  dv_grad_nb(P, S, l + DV_SZ, Z + 1, Y, X, zp);
+  dv_grad_nb(P, S, l - DV_SZ, Z - 1, Y, X, zm);
+  gh_from_grads(g, xp, xm, yp, ym, zp, zm, P.compat, gm, hs);
+}
+
+__global__ __launch_bounds__(64) void smk_k_derive_seed(VghStats *st) {
+  if (threadIdx.x == 0) {
+    VghStats init = {ORD_POS_INF, ORD_NEG_INF, ORD_POS_INF, ORD_NEG_INF, ORD_POS_INF, ORD_NEG_INF};
+    *st = init;
+  }
+}
+
+// A capped grid strides over the tiles, so that the extremes reach the device words as a few ten thousand atomics whatever
+// the volume's size (they all land on one cache line)
+constexpr unsigned DV_STATS_BLOCKS = 2048;  // 8 workgroups for each of 256 CUs
+
+template <int SRC>
+__global__ __launch_bounds__(256) void smk_k_derive_stats(const DeriveParams P, int gx, int gy, int ntiles) {
+  __shared__ float S[DV_LN];
+  const int tx = threadIdx.x % DV_TX, ty = threadIdx.x / DV_TX;
+  VghRunning run;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int bx = tile % gx, by = (tile / gx) % gy, bz = tile / (gx * gy);
+    const int x0 = bx * DV_TX, y0 = by * DV_TY, z0 = bz * DV_TZ;
+    dv_load_tile<SRC>(P, x0, y0, z0, S);
+    __syncthreads();
+    const int X = x0 + tx, Y = y0 + ty;
+    for (int tz = 0; tz < DV_TZ; ++tz) {
+      const int Z = z0 + tz;
+      if (is_border(P.N[0], P.N[1], P.N[2], Z, Y, X)) continue;  // (and everything outside the volume)
+      const int l = (tz + DV_AP) * DV_SZ + (ty + DV_AP) * DV_SY + tx + DV_AP;
+      float gm, hs;
+      dv_gh(P, S, l, Z, Y, X, gm, hs);
+      run.take(S[l], gm, hs);
+    }
+    __syncthreads();  // (the next tile overwrites S)
+  }
+  run.publish(P.st);
+}
+
+// std::min / std::max of <algorithm> as smk_make_vgh_device applies them to the extremes and the reference's seeds
+__device__ __forceinline__ float dv_std_min(float a, float b) { return (b < a) ? b : a; }
+__device__ __forceinline__ float dv_std_max(float a, float b) { return (a < b) ? b : a; }
+
+// OUT: the ring's dtype (smk_dtype)
+template <int SRC, int OUT>
+__global__ __launch_bounds__(256) void smk_k_derive_write(const DeriveParams P) {
+  __shared__ float S[DV_LN], V[DV_LN];
+  const int x0 = blockIdx.x * DV_TX, y0 = blockIdx.y * DV_TY, z0 = blockIdx.z * DV_TZ;
+  dv_load_tile<SRC>(P, x0, y0, z0, S);
+  // the reference seeds its running min/max with +-1e8 (genVGH/main.cpp:69-72, 104-105)
+  const float dmin = dv_std_min(o2f(P.st->dmin), 100000000.f), dmax = dv_std_max(o2f(P.st->dmax), -100000000.f);
+  const float gmin = dv_std_min(o2f(P.st->gmin), 100000000.f), gmax = dv_std_max(o2f(P.st->gmax), -100000000.f);
+  const float hmin = dv_std_min(o2f(P.st->hmin), 100000000.f), hmax = dv_std_max(o2f(P.st->hmax), -100000000.f);
+  __syncthreads();
+  // the OUTPUT's V channel as the normals' source: the byte (u8) or the float before any quantisation; 0 on the border
+  for (int t = threadIdx.x; t < DV_LN; t += 256) {
+    const int lx = t % DV_LX, row = t / DV_LX, ly = row % DV_LY, lz = row / DV_LY;
+    const int X = x0 - DV_AP + lx, Y = y0 - DV_AP + ly, Z = z0 - DV_AP + lz;
+    float v = 0.f;
+    // (plain normals read V one voxel around the tile's own voxels, blurred ones two: the outer ring is not read then)
+    const bool read = P.blur || (lx >= 1 && lx < DV_LX - 1 && ly >= 1 && ly < DV_LY - 1 && lz >= 1 && lz < DV_LZ - 1);
+    if (read && !is_border(P.N[0], P.N[1], P.N[2], Z, Y, X)) {
+      const double vq = affine_d(dmin, S[t], dmax, 0, 255);  // (vgh_scale's V)
+      v = OUT == SMK_U8 ? (float)uc_cast(vq) : (float)(vq / 255.0);
+    }
+    V[t] = v;
+  }
+  __syncthreads();
+  const int tx = threadIdx.x % DV_TX, ty = threadIdx.x / DV_TX, X = x0 + tx, Y = y0 + ty;
+  if (X >= P.D[0] || Y >= P.D[1]) return;
+  for (int tz = 0; tz < DV_TZ; ++tz) {
+    const int Z = z0 + tz;
+    if (Z >= P.D[2]) break;
+    const size_t o = ((size_t)Z * P.D[1] + Y) * P.D[0] + X;
+    if (X >= P.N[0] || Y >= P.N[1]) {  // the pad column or row of an 8-byte box: zeros, as after an upload
+      ((uint2 *)P.out)[o] = make_uint2(0u, 0u);
+      continue;
+    }
+    const int l = (tz + DV_AP) * DV_SZ + (ty + DV_AP) * DV_SY + tx + DV_AP;
+    unsigned char q[3] = {0, 0, 0};
+    float f[3] = {0.f, 0.f, 0.f};
+    if (!is_border(P.N[0], P.N[1], P.N[2], Z, Y, X)) {
+      float gm, hs;
+      dv_gh(P, S, l, Z, Y, X, gm, hs);
+      vgh_scale(S[l], gm, hs, dmin, dmax, gmin, gmax, hmin, hmax, q, f);
+    }
+    uint32_t nb = 0x00808080u;
+    if (P.normals) {
+      float g[3];
+      unsigned char n[3];
+      // (Z, Y, X) -> tile index: l moved by the offset; the differences of bytes held as floats are exact
+      nrm_gradient(P.blur, P.N[0], P.N[1], P.N[2], Z, Y, X, g, [&](int si, int sj, int sk, float s[3]) {
+        dv_grad(V, l + (si - Z) * DV_SZ + (sj - Y) * DV_SY + (sk - X), s);
+      });
+      if (OUT == SMK_U8) nrm_store(g, n);
+      else nrm_store_f32(g, n);
+      nb = (uint32_t)n[0] | ((uint32_t)n[1] << 8) | ((uint32_t)n[2] << 16);
+    }
+    if (OUT == SMK_U8) {
+      ((uint2 *)P.out)[o] = make_uint2((uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16), nb);
+    } else if (OUT == SMK_U16) {
+      // smk_quantize_u16_device of the floats, then the pack's 8-bit unorm of the third channel (smk_k_pack)
+      const uint32_t s0 = quant_u16(f[0]), s1 = quant_u16(f[1]), s2 = quant_u16(f[2]);
+      ((uint2 *)P.out)[o] = make_uint2(s0 | (s1 << 16), nb | (((s2 * 255u + 32767u) / 65535u) << 24));
+    } else {
+      ((uint4 *)P.out)[o] = make_uint4(__float_as_uint(f[0]), __float_as_uint(f[1]), __float_as_uint(f[2]), nb);
+    }
+  }
+}
+
+template <int SRC>
+hipError_t launch_derive(const DeriveParams &P, int out_dtype, hipStream_t s) {
+  const dim3 grid((unsigned)((P.D[0] + DV_TX - 1) / DV_TX), (unsigned)((P.D[1] + DV_TY - 1) / DV_TY), (unsigned)((P.D[2] + DV_TZ - 1) / DV_TZ));
+  hipLaunchKernelGGL(smk_k_derive_seed, dim3(1), dim3(64), 0, s, P.st);
+  const long long ntiles = (long long)grid.x * grid.y * grid.z;
+  if (ntiles > 0x7fffffffLL) return hipErrorInvalidValue;  // (2^31 tiles are 2^42 voxels)
+  hipLaunchKernelGGL(smk_k_derive_stats<SRC>, dim3((unsigned)std::min<long long>(ntiles, DV_STATS_BLOCKS)), dim3(256), 0, s, P, (int)grid.x, (int)grid.y,
+                     (int)ntiles);
+  if (out_dtype == SMK_U8) hipLaunchKernelGGL((smk_k_derive_write<SRC, SMK_U8>), grid, dim3(256), 0, s, P);
+  else if (out_dtype == SMK_U16) hipLaunchKernelGGL((smk_k_derive_write<SRC, SMK_U16>), grid, dim3(256), 0, s, P);
+  else hipLaunchKernelGGL((smk_k_derive_write<SRC, SMK_F32>), grid, dim3(256), 0, s, P);
+  return hipGetLastError();
+}
+
+// what both entries refuse before they look at their source
+int derive_refusals(smk_ctx *c, const char *who) {
+  if (!c->have_volume) FAIL(c, "%s: no volume uploaded", who);
+  if (c->nranks > 1)
+    FAIL(c, "%s: a sharded context (%d ranks): the stencil reaches 2 voxels beyond a voxel and the scaling needs the whole volume's "
+            "extremes; neither fits region + halo", who, c->nranks);
+  if (c->nelts != 3) FAIL(c, "%s: the series has nelts %d: V, G and H are three channels (nelts 3)", who, c->nelts);
+  // what the kernels take for granted of an unsharded context's stored box (smk_volume_geometry): it starts at voxel 0, is
+  // the volume in z, and is wider than the volume only by the pad column and row of 8-byte voxels
+  const bool wide = c->dtype == SMK_F32;
+  if (c->O[0] || c->O[1] || c->O[2] || c->D[2] != c->N[2] || c->D[0] < c->N[0] || c->D[1] < c->N[1] || c->D[0] > c->N[0] + 1 ||
+      c->D[1] > c->N[1] + 1 || (wide && (c->D[0] != c->N[0] || c->D[1] != c->N[1])) || (!wide && (c->D[0] & 1)))
+    FAIL(c, "%s: internal: the stored box %dx%dx%d at %d,%d,%d is not the volume %dx%dx%d with its pad", who, c->D[0], c->D[1], c->D[2], c->O[0],
+         c->O[1], c->O[2], c->N[0], c->N[1], c->N[2]);
+  if (c->N[0] < 3 || c->N[1] < 3 || c->N[2] < 3)
+    FAIL(c, "%s: a %dx%dx%d volume has no interior voxel (dims >= 3, as smk_make_vgh_device)", who, c->N[0], c->N[1], c->N[2]);
+  return 0;
+}
+
+// the two passes, the brick summaries and the bookkeeping of the output step; ksrc: the source slot, or -1 (a dense scalar)
+int derive_enqueue(smk_ctx *c, const char *who, int kind, const void *src, int ksrc, int step_out, int compat, int blur, hipStream_t s) {
+  int need = 0;
+  const int k = smk_step_output_slot(c, step_out, ksrc, -1, &need);
+  if (k < 0) {
+    if (ksrc >= 0)
+      FAIL(c, "%s: the cache holds %d steps: the source and the output need two slots, three when the current step (%d) is a third "
+              "(here %d); smk_set_timestep_cache sets more", who, (int)c->ts.size(), c->ts_cur_id, need);
+    FAIL(c, "%s: time step %d: the cache holds one step, the current one (%d); smk_set_timestep_cache sets more", who, step_out, c->ts_cur_id);
+  }
+  if (smk_step_write_begin(c, k, s)) return 1;
+  c->ts_series = true;
+  if (ksrc >= 0 && smk_step_read_begin(c, ksrc, s)) return 1;
+  TimeStep &T = c->ts[(size_t)k];
+  DeriveParams P;
+  P.src = ksrc >= 0 ? c->ts[(size_t)ksrc].vox : src;
+  P.out = T.vox;
+  P.st = (VghStats *)T.derive_st;
+  for (int a = 0; a < 3; ++a) {
+    P.N[a] = c->N[a];
+    P.D[a] = c->D[a];
+  }
+  P.compat = compat ? 1 : 0;
+  P.blur = blur ? 1 : 0;
+  P.normals = c->have_normals ? 1 : 0;
+  hipError_t e;
+  switch (kind) {
+    case DS_U8: e = launch_derive<DS_U8>(P, c->dtype, s); break;
+    case DS_F32: e = launch_derive<DS_F32>(P, c->dtype, s); break;
+    case DS_U16: e = launch_derive<DS_U16>(P, c->dtype, s); break;
+    case DS_PK_U8: e = launch_derive<DS_PK_U8>(P, c->dtype, s); break;
+    case DS_PK_U16: e = launch_derive<DS_PK_U16>(P, c->dtype, s); break;
+    default: e = launch_derive<DS_PK_F32>(P, c->dtype, s); break;
+  }
+  HIPCHK(c, e);
+  HIPCHK(c, smk_bricks_minmax(T.vox, c->dtype, c->D, c->nbr, T.mm, s));
+  if (smk_step_write_end(c, k, step_out, s)) return 1;
+  if (ksrc >= 0 && smk_step_read_end(c, ksrc, s)) return 1;  // whatever overwrites the source slot comes after these reads
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int smk_derive_timestep(smk_ctx *c, int step_src, int step_out, int compat, int blur, void *stream) {
+  if (!c) return 1;
+  const char *who = "smk_derive_timestep";
+  HIPCHK(c, hipSetDevice(c->device));
+  if (derive_refusals(c, who)) return 1;
+  const int ksrc = step_src < 0 ? -1 : smk_step_slot(c, step_src);
+  if (ksrc < 0) FAIL(c, "%s: time step %d (the source) is not cached", who, step_src);
+  if (step_out < 0) FAIL(c, "%s: output time step %d: ids are >= 0", who, step_out);
+  if (step_out == step_src) FAIL(c, "%s: output time step %d is also the source: the stencil has no in-place form", who, step_out);
+  const int kind = c->dtype == SMK_U8 ? DS_PK_U8 : c->dtype == SMK_U16 ? DS_PK_U16 : DS_PK_F32;
+  return derive_enqueue(c, who, kind, nullptr, ksrc, step_out, compat, blur, stream ? (hipStream_t)stream : c->stream);
+}
+
+extern "C" int smk_upload_timestep_scalar_device(smk_ctx *c, int timestep, const void *d_scalar, smk_dtype scalar_dtype, int sx, int sy,
+                                                 int sz, int compat, int blur, void *stream) {
+  if (!c) return 1;
+  const char *who = "smk_upload_timestep_scalar_device";
+  HIPCHK(c, hipSetDevice(c->device));
+  if (derive_refusals(c, who)) return 1;
+  if (timestep < 0) FAIL(c, "%s: time step %d: ids are >= 0", who, timestep);
+  if (!d_scalar) FAIL(c, "%s: d_scalar is NULL", who);
+  if (scalar_dtype != SMK_U8 && scalar_dtype != SMK_U16 && scalar_dtype != SMK_F32)
+    FAIL(c, "%s: scalar_dtype %d is none of SMK_U8, SMK_U16, SMK_F32", who, (int)scalar_dtype);
+  if (sx != c->N[0] || sy != c->N[1] || sz != c->N[2])
+    FAIL(c, "%s: time step %d: sizes %dx%dx%d differ from the series' %dx%dx%d", who, timestep, sx, sy, sz, c->N[0], c->N[1], c->N[2]);
+  const size_t eb = scalar_dtype == SMK_U8 ? 1 : scalar_dtype == SMK_U16 ? 2 : 4;
+  if ((uintptr_t)d_scalar % eb) FAIL(c, "%s: d_scalar is not aligned to its %zu-byte elements", who, eb);
+  return derive_enqueue(c, who, (int)scalar_dtype, d_scalar, -1, timestep, compat, blur, stream ? (hipStream_t)stream : c->stream);
+}

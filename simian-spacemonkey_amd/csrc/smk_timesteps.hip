@@ -13,7 +13,9 @@
 //   - every frame records the slot's `used` event on its stream; an upload into the slot waits for it first;
 //   - smk_blend_timesteps (fractional time, below) is an upload whose source is two other slots: it waits for their `ready`
 //     events and records their `blended` events behind its kernels; whatever overwrites a slot waits for that one too;
-//   - the histogram and the probe of a step (smk_step_hist.hip) read a slot the same way: smk_step_read_begin / _end.
+//   - the histogram and the probe of a step (smk_step_hist.hip) read a slot the same way: smk_step_read_begin / _end;
+//   - smk_derive_timestep (smk_step_derive.hip) reads its source that way and writes its output as a blend does:
+//     smk_step_write_begin / _end.
 #include <math.h>
 #include <string.h>
 
@@ -51,6 +53,7 @@ static void free_step(TimeStep &T) {
   if (T.nrm) (void)hipFree(T.nrm);
   if (T.mm) (void)hipFree(T.mm);
   if (T.vox_x) (void)hipFree(T.vox_x);
+  if (T.derive_st) (void)hipFree(T.derive_st);
   if (T.ready) (void)hipEventDestroy(T.ready);
   if (T.used) (void)hipEventDestroy(T.used);
   if (T.blended) (void)hipEventDestroy(T.blended);
@@ -242,6 +245,50 @@ static int upload_step(smk_ctx *c, const char *who, int id, const smk_volume_des
   return 0;
 }
 
+int smk_step_output_slot(const smk_ctx *c, int id, int ka, int kb, int *need) {
+  const int k = find_step(c, id);
+  if (k >= 0) return k;  // a cached step is overwritten in place
+  const int cur = c->ts_cur;
+  *need = 1 + (ka >= 0 ? 1 : 0) + (kb >= 0 && kb != ka ? 1 : 0) + (cur >= 0 && cur != ka && cur != kb ? 1 : 0);
+  if ((int)c->ts.size() < *need) return -1;
+  int n = next_slot(c);
+  while (n == ka || n == kb || n == cur) n = (n + 1) % (int)c->ts.size();
+  return n;
+}
+
+int smk_step_write_begin(smk_ctx *c, int k, hipStream_t s) {
+  TimeStep &T = c->ts[(size_t)k];
+  // the slot's old contents: the frames, blends and reads that use them, and an upload still writing them
+  if (T.used_valid) HIPCHK(c, hipStreamWaitEvent(s, T.used, 0));
+  if (T.blended_valid) {
+    HIPCHK(c, hipStreamWaitEvent(s, T.blended, 0));
+    T.blended_valid = false;  // (whoever writes the slot next is ordered behind this write)
+  }
+  if (T.ready_pending) {
+    HIPCHK(c, hipStreamWaitEvent(s, T.ready, 0));
+    T.ready_pending = false;
+  }
+  T.id = -1;  // (until it holds the new step)
+  const size_t nst = (size_t)c->D[0] * c->D[1] * c->D[2];
+  SmkVolGeom g;  // the series' buffers (the writer fills the pad column of a padded box itself: a blend with 0 blended with 0)
+  g.vox_bytes = c->vox_bytes;
+  g.nrm_bytes = c->dtype == SMK_F32 && c->nelts == 4 && c->have_normals ? nst * 4 : 0;
+  g.mm_bytes = (size_t)c->nbr[0] * c->nbr[1] * c->nbr[2] * sizeof(float4);
+  return smk_alloc_step(c, g, T);
+}
+
+int smk_step_write_end(smk_ctx *c, int k, int id, hipStream_t s) {
+  TimeStep &T = c->ts[(size_t)k];
+  T.vox_x_valid = false;
+  T.id = id;
+  T.written = ++c->ts_written;
+  if (!T.ready) HIPCHK(c, hipEventCreateWithFlags(&T.ready, hipEventDisableTiming));
+  HIPCHK(c, hipEventRecord(T.ready, s));
+  T.ready_pending = true;
+  if (k == c->ts_cur) switch_step(c, k);  // the current step overwritten in place
+  return 0;
+}
+
 extern "C" int smk_upload_timestep(smk_ctx *c, int timestep, const smk_volume_desc *bricks, int n_bricks, int nelts, smk_dtype dtype,
                                    smk_datamode dmode) {
   return upload_step(c, "smk_upload_timestep", timestep, bricks, n_bricks, nelts, dtype, dmode, false, nullptr);
@@ -383,17 +430,13 @@ extern "C" int smk_blend_timesteps(smk_ctx *c, int step_a, int step_b, float w, 
     FAIL(c, "%s: output time step %d is also a source: the blend has no in-place form", who, step_out);
   if (!(w >= 0.0f && w <= 1.0f)) FAIL(c, "%s: weight %g is not in [0, 1] (no extrapolation)", who, (double)w);
   c->ts_series = true;
-  int k = find_step(c, step_out);
-  if (k < 0) {
-    // a slot by next_slot's rule that is neither source's: the sources, the current step and the output are 3 or 4 slots
-    // (one less where a and b are the same step)
-    const int need = 2 + (ka != kb ? 1 : 0) + (c->ts_cur != ka && c->ts_cur != kb ? 1 : 0);
-    if ((int)c->ts.size() < need)
-      FAIL(c, "%s: the cache holds %d steps: the two sources and the output need three slots, four when the current step (%d) is a fourth "
-              "(here %d); smk_set_timestep_cache sets more", who, (int)c->ts.size(), c->ts_cur_id, need);
-    k = next_slot(c);
-    while (k == ka || k == kb || k == c->ts_cur) k = (k + 1) % (int)c->ts.size();
-  }
+  // a cached output's own slot, else one by next_slot's rule that is neither source's nor the current step's: the sources,
+  // the current step and the output are 3 or 4 slots (one less where a and b are the same step)
+  int need = 0;
+  const int k = smk_step_output_slot(c, step_out, ka, kb, &need);
+  if (k < 0)
+    FAIL(c, "%s: the cache holds %d steps: the two sources and the output need three slots, four when the current step (%d) is a fourth "
+            "(here %d); smk_set_timestep_cache sets more", who, (int)c->ts.size(), c->ts_cur_id, need);
   TimeStep &A = c->ts[(size_t)ka], &B = c->ts[(size_t)kb], &T = c->ts[(size_t)k];
   const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   // the sources: their uploads (or blends) come first -- the events stay pending for the frames that read the steps -- and so
@@ -402,23 +445,10 @@ extern "C" int smk_blend_timesteps(smk_ctx *c, int step_a, int step_b, float w, 
     if (S->ready_pending) HIPCHK(c, hipStreamWaitEvent(s, S->ready, 0));
     if (S->blended_valid) HIPCHK(c, hipStreamWaitEvent(s, S->blended, 0));
   }
-  // the output slot's old contents: the frames and the blends that read them, and an upload still writing them
-  if (T.used_valid) HIPCHK(c, hipStreamWaitEvent(s, T.used, 0));
-  if (T.blended_valid) {
-    HIPCHK(c, hipStreamWaitEvent(s, T.blended, 0));
-    T.blended_valid = false;  // (whoever writes the slot next is ordered behind this blend)
-  }
-  if (T.ready_pending) {
-    HIPCHK(c, hipStreamWaitEvent(s, T.ready, 0));
-    T.ready_pending = false;
-  }
-  T.id = -1;  // (until it holds the new step)
+  // the output slot's old contents: the frames and the blends that read them, and an upload still writing them; its buffers
+  if (smk_step_write_begin(c, k, s)) return 1;
   const size_t nst = (size_t)c->D[0] * c->D[1] * c->D[2];
-  SmkVolGeom g;  // the series' buffers (the blend writes the pad column of a padded box itself: 0 blended with 0)
-  g.vox_bytes = c->vox_bytes;
-  g.nrm_bytes = c->dtype == SMK_F32 && c->nelts == 4 && c->have_normals ? nst * 4 : 0;
-  g.mm_bytes = (size_t)c->nbr[0] * c->nbr[1] * c->nbr[2] * sizeof(float4);
-  if (smk_alloc_step(c, g, T)) return 1;
+  const size_t nrm_bytes = c->dtype == SMK_F32 && c->nelts == 4 && c->have_normals ? nst * 4 : 0;
   // The stored box -- region + halo, D[0] D[1] D[2] voxels -- in 16-byte units: one f32 voxel, or two 8-byte voxels (D[0] is
   // even for those types, smk_volume_geometry, so their number is even).  The 16 bytes behind the box are not touched.
   const float u = 1.0f - w;
@@ -427,7 +457,7 @@ extern "C" int smk_blend_timesteps(smk_ctx *c, int step_a, int step_b, float w, 
   else if (c->dtype == SMK_U16) HIPCHK(c, launch_blend<TB_U16>(A.vox, B.vox, T.vox, units, u, w, s));
   else if (c->nelts <= 3) HIPCHK(c, launch_blend<TB_F32N>(A.vox, B.vox, T.vox, units, u, w, s));
   else HIPCHK(c, launch_blend<TB_F32C>(A.vox, B.vox, T.vox, units, u, w, s));
-  if (g.nrm_bytes) {
+  if (nrm_bytes) {
     // the separate normals of four-channel f32, a word per voxel, in the byte form: the whole units, then the words that
     // are left when the voxel count (odd sizes are allowed for f32) is no multiple of four
     HIPCHK(c, launch_blend<TB_BYTES>(A.nrm, B.nrm, T.nrm, nst / 4, u, w, s));
@@ -438,18 +468,12 @@ extern "C" int smk_blend_timesteps(smk_ctx *c, int step_a, int step_b, float w, 
     }
   }
   HIPCHK(c, smk_bricks_minmax(T.vox, c->dtype, c->D, c->nbr, T.mm, s));
-  T.vox_x_valid = false;
-  T.id = step_out;
-  T.written = ++c->ts_written;
-  if (!T.ready) HIPCHK(c, hipEventCreateWithFlags(&T.ready, hipEventDisableTiming));
-  HIPCHK(c, hipEventRecord(T.ready, s));
-  T.ready_pending = true;
+  if (smk_step_write_end(c, k, step_out, s)) return 1;  // (the output's `ready`; the current step overwritten in place)
   for (TimeStep *S : {&A, &B}) {  // whatever overwrites a source slot comes after these reads
     if (!S->blended) HIPCHK(c, hipEventCreateWithFlags(&S->blended, hipEventDisableTiming));
     HIPCHK(c, hipEventRecord(S->blended, s));
     S->blended_valid = true;
   }
   ++c->tblend_count;
-  if (k == c->ts_cur) switch_step(c, k);  // the current step overwritten in place
   return 0;
 }

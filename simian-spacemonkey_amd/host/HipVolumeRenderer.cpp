@@ -403,21 +403,53 @@ void HipVolumeRenderable::showTimeFraction() {
               << " is not cached: the series keeps one step resident (MetaVolume::tstepCache < 2)" << std::endl;
     return;
   }
-  if (!tblend_grown) {
-    if (smk_set_timestep_cache(c, tcache + 2)) {
+  const int extra = tderive ? 4 : 2;
+  if (tblend_grown < extra) {
+    if (smk_set_timestep_cache(c, tcache + extra)) {
       std::cerr << "ERROR: HipVolumeRenderable::setTimeFraction: " << smk_last_error(c) << std::endl;
       return;
     }
-    tblend_grown = 1;
+    tblend_grown = extra;
   }
   const int id = INT_MAX - tblend_next;
-  if (smk_blend_timesteps(c, tstep, tstep + 1, tfrac, id, nullptr) || smk_select_timestep(c, id)) {
+  int shown = id;
+  const int bad = smk_blend_timesteps(c, tstep, tstep + 1, tfrac, id, nullptr);
+  if (!bad && tderive) {
+    // V, G, H and normals of the blended scalar, behind the blend on the same stream: no host wait.  A refusal -- a series
+    // that is not V, G, H -- is said here, once for this step and fraction as a refused blend is, and the frames show the blend
+    const int did = INT_MAX - 2 - tblend_next;
+    // A derived id that is resident is overwritten in place.  One that is not -- its first use, or evicted since by steps the
+    // series uploaded -- would take a slot by the ring's rule, which spares the derive's source and the current step but not
+    // the steps tstep and tstep + 1 the NEXT fraction blends.  smk_blend_timesteps spares exactly those, so the same blend
+    // into the derived id makes the id resident first, wherever the ring's turn stands
+    bool resident = false;
+    int n = 0;
+    if (!smk_get_timesteps(c, nullptr, nullptr, 0, &n) && n > 0) {
+      std::vector<int> ids((size_t)n);
+      if (!smk_get_timesteps(c, nullptr, ids.data(), n, &n))
+        for (int i = 0; i < n && i < (int)ids.size(); ++i) resident |= ids[(size_t)i] == did;
+    }
+    if (!resident && smk_blend_timesteps(c, tstep, tstep + 1, tfrac, did, nullptr))
+      std::cerr << "ERROR: HipVolumeRenderable::setTimeFractionDerivatives: " << smk_last_error(c) << std::endl;
+    else if (smk_derive_timestep(c, id, did, 1, 0, nullptr))
+      std::cerr << "ERROR: HipVolumeRenderable::setTimeFractionDerivatives: " << smk_last_error(c) << std::endl;
+    else
+      shown = did;
+  }
+  if (bad || smk_select_timestep(c, shown)) {
     std::cerr << "ERROR: HipVolumeRenderable::setTimeFraction: " << smk_last_error(c) << std::endl;
     if (tblend_id >= 0 && !smk_select_timestep(c, tstep)) tblend_id = -1;
     return;
   }
-  tblend_id = id;
+  tblend_id = shown;
   tblend_next ^= 1;
+}
+
+int HipVolumeRenderable::setTimeFractionDerivatives(int on_off) {
+  const int on = on_off ? 1 : 0;
+  if (on != tderive) tblend_t = -1;  // (the fraction shown now is made again, with or without its derivatives)
+  tderive = on;
+  return 0;
 }
 
 int HipVolumeRenderable::saveTimeStep(const char *prefix) {

@@ -135,7 +135,7 @@ class HipVolumeRenderable final : public gluvvPrimitive {
  public:
   explicit HipVolumeRenderable(int device = 0)
       : volren(nullptr), go(0), device(device), tstep(0), tcache(1), u16(0), tfrac(0), tblend_t(-1), tblend_f(0), tblend_id(-1), tblend_next(0),
-        tblend_grown(0) {}
+        tblend_grown(0), tderive(0) {}
   ~HipVolumeRenderable() { delete volren; }  // (gluvvPrimitive's destructor is not virtual, gluvvPrimitive.h:26: delete through this type)
   void init();  // virtual in gluvvPrimitive (gluvvPrimitive.h:29-30)
   void draw();
@@ -154,6 +154,12 @@ class HipVolumeRenderable final : public gluvvPrimitive {
   // steps resident (gluvv.mv->tstepCache >= 2); a blend that is refused -- step timestep + 1 not resident -- is reported once
   // on stderr and the frames stay on the whole step until the step or the fraction moves.
   int setTimeFraction(float f);
+  // derivatives of the blend (an extension beside setTimeFraction).  On: the frames of a fraction show not the blend -- whose G
+  // and H are the blends of G and H -- but the VGH step of the blended SCALAR, channel 0 of the blend: makeVGH's V, G, H (the
+  // reference's h[4] typo kept) and normalsVGH's plain normals, made on the device by smk_derive_timestep into a second pair
+  // of reserved ids; the ring grows by two more slots.  The series must be V, G, H (nelts 3): a derive that is refused is
+  // reported once on stderr, as a refused blend is, and the frames show the blend.  Returns 0.  Call after init().
+  int setTimeFractionDerivatives(int on_off);
   // MetaVolume::writeAll + Volume::writeVol (MetaVolume.cpp:99-126, 963-1000) for the step draw() shows -- a blend made by
   // setTimeFraction included --, read back from the renderer (HipVolumeRenderer::downloadStep).  A one-channel 8-bit step
   // goes to "<prefix>.trex" plus the raw brick, one sub-volume, as writeAll writes it (smkfiles::write_trex); a
@@ -181,7 +187,9 @@ class HipVolumeRenderable final : public gluvvPrimitive {
   int tblend_t;             // the (time step, fraction) of the last blend asked for, made or refused (-1: none)
   float tblend_f;
   int tblend_id;            // the reserved id the frames show instead of tstep (-1: they show tstep)
-  int tblend_next;          // which of the two reserved ids, INT_MAX and INT_MAX - 1, the next blend goes into
-  int tblend_grown;         // the ring has the two slots more that the blends live in
+  int tblend_next;          // which of the two reserved ids, INT_MAX and INT_MAX - 1, the next blend goes into (its derived
+                            // step: INT_MAX - 2 and INT_MAX - 3)
+  int tblend_grown;         // the slots the ring has beyond the series': 2 that the blends live in, 4 with their derived steps
+  int tderive;              // setTimeFractionDerivatives
   std::vector<unsigned char> noise;  // [sz][sy][sx][4]
 };

@@ -16,7 +16,14 @@ Frame times are HIP-event times on the render stream (median); the loop also rep
      smk_upload_timestep_device of the same step alone (as in 3.), the bytes both move, their ratio; then, for f32, playback
      over the four resident steps with and without a download of the shown step on a second stream beside each frame.
      Writes the note profiles/step_download.md (--out PATH: elsewhere).
-    python tools/timestep_time.py --download [--out PATH] [volume edge] [loop frames]"""
+    python tools/timestep_time.py --download [--out PATH] [volume edge] [loop frames]
+  5. --derive: derivatives of a step (smk_derive_timestep).  For u8, u16 and f32 rings: the blend and the derive of it (HIP
+     events round the two entries' work on their stream, median of 9) against the seven-call recipe of INTEGRATION.md 5 in
+     the same run -- blend, download, strided copy of channel 0, stream synchronise, smk_make_vgh_device,
+     smk_normals_*_device, smk_upload_timestep_device --: its device work stage by stage and its wall time, host wait
+     included; then, for f32, playback over the four resident steps with a blend and a derive on a second stream beside each
+     frame.  Writes the note profiles/step_derive.md (--out PATH: elsewhere).
+    python tools/timestep_time.py --derive [--out PATH] [volume edge] [loop frames]"""
 import os
 import statistics
 import sys
@@ -193,6 +200,159 @@ def download_leg(pkg, n, loop, out_path):
     print("wrote", out_path, flush=True)
 
 
+def wall_ms(work):
+    t0 = time.perf_counter()
+    work()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def derive_leg(pkg, n, loop, out_path):
+    lines = ["# Derivatives of a step: `smk_derive_timestep` on one MI355X", "",
+             "Written by `tools/timestep_time.py --derive %d %d`.  Config 3's step (%d^3, three channels with normals); the source is" % (n, loop, n),
+             "the 0.3 blend of two resident steps.  Median of 9 after 3 warm-up rounds.",
+             "", "- **entry**: HIP events round `smk_blend_timesteps` + `smk_derive_timestep` on one stream (and round the derive alone):",
+             "  seed, extremes pass, write pass, brick summaries.  No host wait.",
+             "- **recipe** (INTEGRATION.md 5, the definition of the contract): blend, `smk_download_timestep_device`, a strided copy of",
+             "  channel 0, a stream synchronise, `smk_make_vgh_device`, (`smk_quantize_u16_device` for a u16 ring,)",
+             "  `smk_normals_*_device`, `smk_upload_timestep_device`.  Its device work is the sum of its stages: HIP events round the",
+             "  asynchronous ones on their stream; the preparation entries run on the context's own stream and return when their",
+             "  kernels are done, so their stage is the host time of the call on an idle device (it includes their launch, their",
+             "  allocation and their device-to-host copy of the extremes, which are part of that path).  Wall: host time from the first",
+             "  call to the end of a final synchronise, the host wait in the middle included.",
+             "", "The condition of the feature: the entry's device time lies below the recipe's in the same run.", "",
+             "| ring | derive alone ms | blend + derive ms | recipe device ms (blend+download+copy / make_vgh / quantise / normals / upload) | recipe wall ms | entry / recipe device | below |",
+             "|---|---|---|---|---|---|---|"]
+    bl = torch.cuda.Stream()
+    dims = (n, n, n)
+    nv = n ** 3
+    play = []
+    for dtype in ("u8", "u16", "f32"):
+        R = pkg.Renderer(0)
+        try:
+            steps, dt = typed_steps(R, n, dtype)
+            R.set_timestep_cache(8)
+            R.upload_volume_device(steps[0][0].data_ptr(), dims, 3, dt, steps[0][1].data_ptr())
+            for t in (1, 2, 3):
+                R.upload_timestep_device(t, steps[t][0].data_ptr(), dims, 3, dt, steps[t][1].data_ptr(), stream=bl.cuda_stream)
+            torch.cuda.synchronize()
+            esz = {"f32": 4, "u8": 1, "u16": 2}[dtype]
+            tdt = {"f32": torch.float32, "u8": torch.uint8, "u16": torch.int16}[dtype]
+            out_d = torch.zeros((nv, 3), dtype=tdt, device="cuda")       # the recipe's four scratch arrays (five for u16)
+            s0 = torch.zeros(nv, dtype=tdt, device="cuda")
+            vgh8 = torch.zeros(nv * 3, dtype=torch.uint8, device="cuda")
+            vghf = torch.zeros(nv * 3, dtype=torch.float32, device="cuda") if dtype != "u8" else None
+            q16 = torch.zeros(nv * 3, dtype=torch.int16, device="cuda") if dtype == "u16" else None
+            nrm = torch.zeros(nv * 3, dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            sb = bl.cuda_stream
+            t_derive, t_entry, t_recipe, t_wall = [], [], [], []
+            for i in range(12):
+                R.blend_timesteps(0, 1, 0.3, 10, stream=sb)
+                t_derive.append(event_ms(bl, lambda: R.derive_timestep(10, 12, 1, 0, stream=sb)))
+                t_entry.append(event_ms(bl, lambda: (R.blend_timesteps(0, 1, 0.3, 10, stream=sb), R.derive_timestep(10, 12, 1, 0, stream=sb))))
+                torch.cuda.synchronize()
+                w0 = time.perf_counter()
+
+                def front():
+                    R.blend_timesteps(0, 1, 0.3, 11, stream=sb)
+                    R.download_timestep_device(out_d.data_ptr(), None, 11, sb)
+                    with torch.cuda.stream(bl):
+                        s0.copy_(out_d[:, 0])
+                st_front = event_ms(bl, front)                           # (event_ms ends with the host wait of the recipe)
+                st_vgh = wall_ms(lambda: R.make_vgh_device(s0.data_ptr(), dt, dims, 1, vgh8.data_ptr() if dtype == "u8" else None,
+                                                           vghf.data_ptr() if vghf is not None else None))
+                st_q = wall_ms(lambda: R.quantize_u16_device(vghf.data_ptr(), nv * 3, q16.data_ptr())) if dtype == "u16" else 0.0
+                if dtype == "u8":
+                    st_n = wall_ms(lambda: R.normals_vgh_device(vgh8.data_ptr(), 3, dims, 0, nrm.data_ptr()))
+                else:
+                    st_n = wall_ms(lambda: R.normals_f32_device(vghf.data_ptr(), 3, dims, 0, nrm.data_ptr()))
+                up = vgh8 if dtype == "u8" else q16 if dtype == "u16" else vghf
+                st_up = event_ms(bl, lambda: R.upload_timestep_device(13, up.data_ptr(), dims, 3, dt, nrm.data_ptr(), stream=sb))
+                torch.cuda.synchronize()
+                t_wall.append((time.perf_counter() - w0) * 1e3)
+                t_recipe.append((st_front, st_vgh, st_q, st_n, st_up))
+            # the two results are the same step
+            a_d, a_g = torch.zeros_like(out_d), torch.zeros(nv * 3, dtype=torch.uint8, device="cuda")
+            b_d, b_g = torch.zeros_like(out_d), torch.zeros(nv * 3, dtype=torch.uint8, device="cuda")
+            R.blend_timesteps(0, 1, 0.3, 11, stream=sb)
+            R.derive_timestep(11, 12, 1, 0, stream=sb)
+            R.download_timestep_device(a_d.data_ptr(), a_g.data_ptr(), 12, sb)
+            R.download_timestep_device(b_d.data_ptr(), b_g.data_ptr(), 13, sb)
+            torch.cuda.synchronize()
+            assert torch.equal(a_d.view(torch.uint8), b_d.view(torch.uint8)) and torch.equal(a_g, b_g), "the derive differs from the recipe"
+            med = statistics.median
+            d_ms, e_ms, w_ms = med(t_derive[3:]), med(t_entry[3:]), med(t_wall[3:])
+            stages = [med([r[j] for r in t_recipe[3:]]) for j in range(5)]
+            r_ms = sum(stages)
+            lines.append("| %s | %.3f (min %.3f, max %.3f) | %.3f (min %.3f, max %.3f) | %.3f (%s) | %.3f | %.3f | %s |" % (
+                dtype, d_ms, min(t_derive[3:]), max(t_derive[3:]), e_ms, min(t_entry[3:]), max(t_entry[3:]), r_ms,
+                " / ".join("%.3f" % v for v in stages), w_ms, e_ms / r_ms, "yes" if e_ms < r_ms else "NO"))
+            print(lines[-1], flush=True)
+            if dtype == "f32":
+                del out_d, s0, vgh8, vghf, nrm, a_d, a_g, b_d, b_g
+                play = derive_playback(R, n, loop, bl)
+        finally:
+            R.close()
+            torch.cuda.synchronize()
+    lines += ["", "## Playback", "", "Config 3's scene (f32, 1024^2 x 512 planes) over the four resident steps, every step followed by 4 frames of",
+              "fractional time (w = 0.2 .. 0.8) towards the next one, each showing the DERIVED step of its blend; blend and derive of",
+              "frame i + 1 are enqueued on a second stream before frame i, into the output ids frame i does not show.", ""] + play
+    regs = {k: v for k, v in kernel_registers().items() if "smk_k_derive" in k}
+    lines += ["", "## Kernels", "", "`smk_k_derive_stats<SRC>` and `smk_k_derive_write<SRC, OUT>` (SRC 0..2: a dense u8 / f32 / u16 scalar, 3..5: channel 0 of",
+              "packed u8 / u16 / f32 voxels; OUT: the ring's type): one workgroup of 256 lanes per 32 x 8 x 8 tile, the scalar as floats in",
+              "LDS with a 2-voxel apron (20 736 bytes; the write pass keeps the scaled V beside it: 41 472 bytes), a lane per (x, y)",
+              "column of 8 voxels, one 8- or 16-byte store per voxel.  From `tools/kernel_inventory.py`:", ""]
+    fam = [(name, [v for k, v in regs.items() if name in k]) for name in ("smk_k_derive_seed", "smk_k_derive_stats", "smk_k_derive_write")]
+    lines += ["- `%s`: %d instance%s, %d - %d VGPRs, at most %d bytes of scratch" % (
+        name, len(vs), "" if len(vs) == 1 else "s", min(v["vgprs"] for v in vs), max(v["vgprs"] for v in vs),
+        max(v["private_segment"] for v in vs)) for name, vs in fam if vs] or ["- (inventory not available here)"]
+    open(out_path, "w").write("\n".join(lines) + "\n")
+    print("wrote", out_path, flush=True)
+
+
+def derive_playback(R, n, loop, bl):
+    frame = torch.zeros((SIZE * SIZE, 4), dtype=torch.float32, device="cuda")
+    st = torch.cuda.Stream()
+    bench.configure(R, "cfg3", n, SIZE, PLANES)
+    for _ in range(24):
+        timed_frame(R, frame, st)
+    seq = [(t, (t + 1) % 4, j / 5.0) for t in range(4) for j in range(5)]
+
+    def prepare(i, derive):    # what frame i shows: a whole step, or a blend (and its derived step) enqueued now
+        a, b, w = seq[i % len(seq)]
+        if w == 0:
+            return a
+        R.blend_timesteps(a, b, w, 10 + (i & 1), stream=bl.cuda_stream)
+        if not derive:
+            return 10 + (i & 1)
+        R.derive_timestep(10 + (i & 1), 12 + (i & 1), 1, 0, stream=bl.cuda_stream)
+        return 12 + (i & 1)
+    out = []
+    for label, derive in (("blends alone", False), ("a blend and a derive beside each fractional frame", True)):
+        for phase, frames in (("warm-up", len(seq)), ("timed", loop)):
+            ev = []
+            R.select_timestep(prepare(0, derive))
+            torch.cuda.synchronize()
+            w0 = time.perf_counter()
+            for i in range(frames):
+                nxt = prepare(i + 1, derive)
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record(st)
+                R.render_device(frame.data_ptr(), None, st.cuda_stream)
+                b.record(st)
+                ev.append((a, b))
+                R.select_timestep(nxt)
+            torch.cuda.synchronize()
+            wall = (time.perf_counter() - w0) * 1e3 / frames
+            ms = [a.elapsed_time(b) for a, b in ev]
+            if phase == "timed":
+                out.append("- %s: %d frames (4 of 5 fractional), frame median %.3f ms, max %.3f ms, wall %.3f ms per frame" % (
+                    label, frames, statistics.median(ms), max(ms), wall))
+                print(out[-1], flush=True)
+    assert R.stat("slab_failures") == 0
+    return out
+
+
 def download_playback(R, n, loop, dl, out_d, out_g):
     frame = torch.zeros((SIZE * SIZE, 4), dtype=torch.float32, device="cuda")
     st = torch.cuda.Stream()
@@ -268,16 +428,18 @@ def blend_playback(R, n, loop, bl):
 
 def main():
     args = sys.argv[1:]
-    blend, download = "--blend" in args, "--download" in args
+    blend, download, derive = "--blend" in args, "--download" in args, "--derive" in args
     out_path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                            "step_download.md" if download else "timestep_blend.md")
+                            "step_derive.md" if derive else "step_download.md" if download else "timestep_blend.md")
     if "--out" in args:
         out_path = args[args.index("--out") + 1]
         del args[args.index("--out"):args.index("--out") + 2]
-    args = [a for a in args if a not in ("--blend", "--download")]
+    args = [a for a in args if a not in ("--blend", "--download", "--derive")]
     n = int(args[0]) if len(args) > 0 else 512
     loop = int(args[1]) if len(args) > 1 else 32
     pkg = bench.load_package()
+    if derive:
+        return derive_leg(pkg, n, loop, out_path)
     if download:
         return download_leg(pkg, n, loop, out_path)
     if blend:
