@@ -1,8 +1,12 @@
 """GPU data-prep kernels (VGH synthesis, normals) against the CPU checker: integer/byte outputs,
-so the bar is bit-exact (genVGH/main.cpp:56-182, VectorMath.h:874-899, 1133-1148, 1217-1281)."""
+so the bar is bit-exact (genVGH/main.cpp:56-182, VectorMath.h:874-899, 1133-1148, 1217-1281).  The float output of
+smk_make_vgh_device is compared as bit patterns; the scalars of those cases come from tests/_step_derive_ref.py."""
+import functools
+
 import numpy as np
 import pytest
 
+import _step_derive_ref as V
 from _scenes import scalar_volume
 
 pytestmark = pytest.mark.gpu
@@ -51,6 +55,86 @@ def test_make_vgh_f32_input_bit_exact(R, O):
     R.make_vgh_device(_dev(v).data_ptr(), 1, (22, 18, 14), 1, o8.data_ptr(), None)
     torch.cuda.synchronize()
     assert np.array_equal(o8.cpu().numpy(), ref8)
+
+
+def _make_vgh(R, s, dims, compat):
+    """(vgh_u8, vgh_f32) of smk_make_vgh_device on the scalar s [z][y][x] (u8, u16 or f32), both over a canary"""
+    import torch
+    nx, ny, nz = dims
+    d = _dev(np.array(s.view(np.int16) if s.dtype == np.uint16 else s))    # (a copy: the shared scalars are read-only)
+    o8 = torch.full((nz, ny, nx, 3), 0xa5, dtype=torch.uint8, device="cuda")
+    of = torch.full((nz, ny, nx, 3), -7.25, dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    R.make_vgh_device(d.data_ptr(), V.CODE[{np.uint8: "u8", np.uint16: "u16", np.float32: "f32"}[s.dtype.type]], dims, compat,
+                      o8.data_ptr(), of.data_ptr())
+    torch.cuda.synchronize()
+    return o8.cpu().numpy(), of.cpu().numpy()
+
+
+def _same_vgh(got, want, what):
+    """bytes equal; floats equal as their 32-bit patterns, which tell -0 from 0"""
+    for g, w, name in ((got[0], want[0], "vgh_u8"), (got[1].view(np.uint32), want[1].view(np.uint32), "vgh_f32")):
+        bad = np.argwhere(g != w)
+        assert not len(bad), "%s %s: %d of %d values differ, first at %s: got %#x, want %#x" % (
+            what, name, len(bad), g.size, tuple(bad[0]), int(g[tuple(bad[0])]), int(w[tuple(bad[0])]))
+
+
+@pytest.mark.parametrize("compat", [1, 0])
+@pytest.mark.parametrize("name", [n for n in V.SCALARS if n != "u8"])
+@pytest.mark.parametrize("dims", [V.SMALL, (5, 4, 3)], ids=lambda d: "%dx%dx%d" % d)
+def test_make_vgh_float_and_u16_scalars_bit_exact(R, O, dims, name, compat):
+    """both outputs of a u16 and of a float scalar -- in [0, 1], signed with a -0.0 voxel, wholly above the reference's seed
+    1e8 and wholly below -1e8 (tests/_step_derive_ref.py typed; qualified in tests/test_step_derive_cpu.py) -- against the
+    checker on the same values as floats.  Every scalar is finite and holds a zero-gradient voxel (NaN H)"""
+    s = V.typed(V.scalar(0, dims) if dims == V.SMALL else V.small_scalar(dims), name)
+    want = O.make_vgh(s.astype(np.float32), compat=bool(compat), f32=True)
+    assert len(np.unique(want[0])) > 10 and np.isfinite(want[1]).all()
+    _same_vgh(_make_vgh(R, s, dims, compat), want, "%s, compat %d:" % (name, compat))
+
+
+# ---- a second grid turn: more voxels than smk_make_vgh_device's 4096 x 256 threads (twice over) and than
+# smk_normals_vgh_device's 8192 x 256.  tests/_step_derive_ref.py states the caps beside the shape; here, what they are for
+assert V.VGH_THREADS == 4096 * 256 and V.NRM_THREADS == 8192 * 256
+assert V.BIG == (129, 128, 128) and 129 * 128 * 128 > V.NRM_THREADS and 129 * 128 * 128 > 2 * V.VGH_THREADS
+
+
+@functools.lru_cache(maxsize=None)
+def _big(kind):
+    s = V.as_type(V.big_scalar(), kind)
+    s.setflags(write=False)
+    return s
+
+
+@functools.lru_cache(maxsize=None)
+def _big_vgh(O, kind, compat):
+    want = O.make_vgh(_big(kind), compat=bool(compat), f32=True)
+    for a in want:
+        a.setflags(write=False)
+    return want
+
+
+@pytest.mark.parametrize("kind, compat", [("u8", 1), ("u8", 0), ("f32", 1), ("f32", 0)])
+def test_make_vgh_second_grid_turn_bit_exact(R, O, kind, compat):
+    """the interior extremes of the data, and the steepest gradient beside them, lie where only the second turn of the
+    grid-stride loops reads them; the third turn holds border voxels only, the scalar's global 0 and 255 among them
+    (tests/test_step_derive_cpu.py test_the_big_volume_needs_a_second_grid_turn)"""
+    want = _big_vgh(O, kind, compat)
+    assert want[0][V.BIG_MIN][0] == 0 and want[0][V.BIG_MAX][0] == 255 and not want[0][127].any()
+    _same_vgh(_make_vgh(R, _big(kind), V.BIG, compat), want, "%s, compat %d:" % (kind, compat))
+
+
+@pytest.mark.parametrize("blur", [0, 1])
+def test_normals_second_grid_turn_bit_exact(R, O, blur):
+    import torch
+    nx, ny, nz = V.BIG
+    vgh = _big_vgh(O, "u8", 1)[0]
+    ref = O.normals_vgh(vgh, blur=bool(blur))
+    out = torch.zeros((nz, ny, nx, 3), dtype=torch.uint8, device="cuda")
+    R.normals_vgh_device(_dev(np.array(vgh)).data_ptr(), 3, V.BIG, blur, out.data_ptr())
+    torch.cuda.synchronize()
+    got = out.cpu().numpy()
+    assert np.array_equal(got, ref), "differs in %d voxels, %d of them beyond the first grid turn" % (
+        int((got != ref).any(-1).sum()), int((got != ref).any(-1).reshape(-1)[V.NRM_THREADS:].sum()))
 
 
 @pytest.mark.parametrize("blur", [0, 1])
