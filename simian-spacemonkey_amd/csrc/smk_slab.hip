@@ -173,17 +173,34 @@ __device__ __forceinline__ void raw_lds_st_b32(void *p, int v) {
   asm volatile("ds_write_b32 %0, %1" ::"v"(a), "v"(v) : "memory");
 }
 
-// minimum over the 64 lanes of a fully active wave, on the DPP network (no LDS traffic)
-// (the compiler spends 27 instructions on it -- v_mov + s_nop + v_mov_dpp + v_min per step, four v_readlane for the row
-//  minima; written out with v_min_i32_dpp and row_bcast it is 13, bit-identical frames, and no faster on either frame)
+// minimum over the 64 lanes of a fully active wave, on the DPP network (no LDS traffic); the result is wave-uniform
+// FOLD: the identity of min as the DPP move's `old` operand.  The compiler's DPP combiner then puts the modifier on the
+// v_min_i32 itself -- with the value as `old` it cannot, and every step is v_mov + s_nop + v_mov_dpp + v_min -- and the rows
+// are combined by row_bcast:15 / row_bcast:31 and ONE v_readlane of lane 63 instead of four v_readlane, an s_min, two v_mov
+// and a v_min3: with the copy of the value that the caller goes on using, 8 vector issue slots instead of 20
+// (tools/slab_loop_isa.py shows both).  Rows whose row_mask bit is clear keep their value: min(v, identity).  The plain
+// frames' instances take it (TURN); the others keep the form their register allocation was settled with
+template <bool FOLD>
 __device__ __forceinline__ int wave_min_i32(int v) {
-  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xf, 0xf, false));   // quad_perm [1,0,3,2]
-  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x4E, 0xf, 0xf, false));   // quad_perm [2,3,0,1]
-  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x141, 0xf, 0xf, false));  // row_half_mirror
-  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x140, 0xf, 0xf, false));  // row_mirror
-  // every row of 16 lanes now holds its own minimum
-  return min(min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
-             min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
+  if constexpr (FOLD) {
+    constexpr int top = 0x7fffffff;
+    v = min(v, __builtin_amdgcn_update_dpp(top, v, 0xB1, 0xf, 0xf, false));   // quad_perm [1,0,3,2]
+    v = min(v, __builtin_amdgcn_update_dpp(top, v, 0x4E, 0xf, 0xf, false));   // quad_perm [2,3,0,1]
+    v = min(v, __builtin_amdgcn_update_dpp(top, v, 0x141, 0xf, 0xf, false));  // row_half_mirror
+    v = min(v, __builtin_amdgcn_update_dpp(top, v, 0x140, 0xf, 0xf, false));  // row_mirror
+    // every row of 16 lanes now holds its own minimum
+    v = min(v, __builtin_amdgcn_update_dpp(top, v, 0x142, 0xa, 0xf, false));  // row_bcast:15: lane 15 of a row into the next, rows 1 and 3
+    v = min(v, __builtin_amdgcn_update_dpp(top, v, 0x143, 0xc, 0xf, false));  // row_bcast:31: lane 31 into rows 2 and 3
+    return __builtin_amdgcn_readlane(v, 63);                                  // row 3 has seen all four
+  } else {
+    v = min(v, __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xf, 0xf, false));   // quad_perm [1,0,3,2]
+    v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x4E, 0xf, 0xf, false));   // quad_perm [2,3,0,1]
+    v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x141, 0xf, 0xf, false));  // row_half_mirror
+    v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x140, 0xf, 0xf, false));  // row_mirror
+    // every row of 16 lanes now holds its own minimum
+    return min(min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
+               min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
+  }
 }
 
 // bilinear RGBA8 lookup like smk_tex2d, for tables of >= 2x2 texels: the clamped texel pair is
@@ -247,6 +264,11 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
   // instances have the room, those of frames with shadows, scene depth or the NV20 look sit at the 80 VGPRs of their launch
   // bound and would pass it or need scratch (profiles/r05_loop_diet.md), so they keep the longer form
   constexpr bool LEAN = !SHD && !OCC && !NVL;
+  // TURN: the compiler's bookkeeping taken out of a turn (same section, second part) -- the wave minimum with the DPP modifier
+  // folded into v_min_i32, `work` as a lane mask, one nested visible block.  The diagnostic instances keep the older forms:
+  // with their counters and time stamps they hold more live values, and the 10+2 ones gained 4 bytes of scratch with the new
+  constexpr bool TURN = LEAN && !DIAG;
+  static_assert(VB % 8 == 0, "TURN reads the low bits of a slice-table entry as flags: bases must be multiples of 8");
   // ... and their loaders skip the row groups a slice does not need, counting DMA instructions per
   // slice; small workgroups keep every slice the same number of instructions (cheaper bookkeeping:
   // measured 3 % on the 512^3 frame, where the loaders' issue slots are the consumers')
@@ -690,7 +712,7 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
   }
   int pos = SLAB_DONE;
   if (!is_loader && npos > 0) {
-    pos = wave_min_i32(pb);
+    pos = wave_min_i32<TURN>(pb);
     if (lane == 0) ctl[8 + wave] = pos;
   }
   __syncthreads();  // table, alpha_H, control words visible; LAST workgroup barrier
@@ -1040,11 +1062,11 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
         SLAB_MARK("loop head");
         const bool want = pb < SLAB_DONE;
         if (!__any(want)) break;  // every ray of this wave is finished
-        // progress = position of the slowest lane (DPP reduction, ~12 VALU), published every
+        // progress = position of the slowest lane (DPP reduction, 8 VALU in the plain frames' instances), published every
         // iteration on a short ring and every other one where a stale value only delays slot
         // recycling by a step
         if (!EARLY && !(it & Q.pmask)) {
-          const int plo = wave_min_i32(pb);
+          const int plo = wave_min_i32<TURN>(pb);
           if (plo != pos) {  // positions below plo are done: their lower slices may be recycled
             pos = plo;       // (every slot read of earlier iterations has returned: slab_read8 waits)
             if (lane == 0) lds_st(&ctl[8 + wave], pos);
@@ -1059,7 +1081,7 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
           have = landed_all();
           if (have < need) {
             // make sure `pos` is this wave's true minimum before sleeping on it
-            const int plo = wave_min_i32(pb);
+            const int plo = wave_min_i32<TURN>(pb);
             if (plo != pos) {
               pos = plo;
               if (lane == 0) lds_st(&ctl[8 + wave], pos);
@@ -1118,12 +1140,17 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
         }
         // EMPTY LAYERS: nothing in this sample's layer can be visible for any ray of the tile -- the sample is exactly
         // transparent, and its slices may not even have been streamed
-        if (flags) work = work && !(base_a & 1);
+        // (TURN: no test of `flags` here or below.  Without brick flags nobody sets the entries' low bits, and the base
+        //  addresses are multiples of 8 -- smem is 16-byte aligned, a slot is whole KiB, a row 16 bytes, a voxel VB: the bits read 0.  As a run-time switch it was two lane masks held in scalar registers
+        //  through the loop and three v_cndmask 0, 1 per turn to apply them to `work`)
+        if constexpr (TURN) {
+          if constexpr (BR) work = work && !(base_a & 1);
+        } else if (flags) work = work && !(base_a & 1);
         // the plane of this ray's next sample: the next one, or -- from a layer that starts a run of empty ones (the
         // entry holds its length, see the set-up) -- the first plane whose base slice lies behind the run.  The planes
         // in between fall into empty layers, all of them: positions are monotone in the plane index.
         int m_next = m + 1;
-        if (flags && act && (base_a & 3) == 3) {
+        if ((TURN ? BR : flags) && act && (base_a & 3) == 3) {
           const int ptar = pb + (base_a >> 2);  // first position behind the run
           if (ptar >= npos) m_next = m1 + 1;    // nothing but empty layers to the end of the tile's range
           else {
@@ -1177,7 +1204,7 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
           early_nsc = nsc;
           early_ni = ni;
           // (every turn: on the 5-slot ring a progress word that is one turn late costs 16 % -- 4.07 vs 4.71 ms)
-          const int plo = wave_min_i32(pbn);
+          const int plo = wave_min_i32<TURN>(pbn);
           if (plo != pos && plo < SLAB_DONE) {
             pos = plo;
             if (lane == 0) lds_st(&ctl[8 + wave], pos);
@@ -1324,122 +1351,178 @@ __global__ __launch_bounds__((NW + NL) * 64, ((NW + NL) == 9) ? 6 : ((NW + NL) =
 #undef NB
             return smk_shade_geom<SH>(P, n0, n1, n2);
           };
-          SmkPhong ph = {0.f, 0.f};
-          float4 col;
-          bool hit;
-          SlabTexel4 tx4 = {0, 0, 0, 0, 0.f, 0.f};
-          if (TF == 1 && Q.fast_tf) {
-            int s0, s1, t0, t1;
-            float fs, ft;
-            smk_lin_clamp(__fmaf_rn(ch0, (float)P.sv, -0.5f), P.sv, s0, s1, fs);
-            smk_lin_clamp(__fmaf_rn(ch1, (float)P.sg, -0.5f), P.sg, t0, t1, ft);
-            // occupancy bit of the texel quad (LDS): clear => alpha is exactly 0, no fetch.  Most
-            // samples of a typical transfer function end here, without the L2 round trip.
-            bool maybe = true;
-            if (Q.use_occ) maybe = (occ[__mul24(t0, P.occ_roww) + (s0 >> 5)] >> (s0 & 31)) & 1u;
-            col.w = 0.0f;
+          // ---- classification and, for a sample that shows, everything behind it.  Two pieces of text that both arrangements
+          // below share, as macros: the same tokens give the instances that keep the older arrangement the code they had.
+          // (1) SLAB_FAST_ALPHA, the separable table's alpha from the issue of the texel loads on.
+          //     SHADE UNDER THE FETCH.  The four texels come from L2; nothing of the normal's share of the Phong term needs
+          //     them -- the second batch of LDS reads, 21 lerps, the rotation, rsqrt, two dot products and the specular power,
+          //     the larger half of a visible sample's arithmetic -- so it runs behind the issue of the loads and in front of
+          //     their first use.  (The asm statement of the LDS batch keeps the loads above it; the wait for them is the
+          //     compiler's, in front of the alpha.)  A sample that then turns out to have alpha 0 paid it for nothing.
+          //     Alpha first (all four (V,G) texels are needed for it anyway), times the third-axis alpha where that is in
+          //     use (the same products as smk_classify); colour only on a hit.
+#define SLAB_FAST_ALPHA \
+  if (count) { \
+    d_maybe = true; \
+    d_t0 = (unsigned)__builtin_amdgcn_s_memtime(); \
+  } \
+  tx4 = slab_tex2d_fetch<LEAN>(P.tf_vg, P.sv, s0, t0, fs, ft); \
+  if (texwait_at_issue) { \
+    const unsigned t = (unsigned)__builtin_amdgcn_s_memtime(); \
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); \
+    d_wait = (unsigned)__builtin_amdgcn_s_memtime() - t; \
+  } \
+  if constexpr (SH != 0) ph = phong_geom(); \
+  if (count) { \
+    const unsigned t = (unsigned)__builtin_amdgcn_s_memtime(); \
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); \
+    d_wait += (unsigned)__builtin_amdgcn_s_memtime() - t; \
+  } \
+  col.w = slab_tex_chan(tx4, 3); \
+  if (Q.use_ah) { \
+    if (lazy_h) ch2 = tri_h_early(); \
+    int h0, h1; \
+    float fh; \
+    smk_lin_clamp(__fmaf_rn(ch2, (float)P.sv, -0.5f), P.sv, h0, h1, fh); \
+    col.w *= smk_lerp(ah[h0], ah[h0 + 1], fh) * SMK_INV255; \
+  } \
+  col.w = smk_sat(col.w);
+          // (2) SLAB_SHOW, a sample whose alpha is not 0: its colour; in frames with shadows the light-buffer colour over it, as
+          //     the slices nearer the light left it (smk_shadow.hip; the sample's own position: the gather kernel's fma chain);
+          //     shading (the 1-D colour table's entries are premultiplied, TLUT.cpp:65-71, as in the gather kernel; the
+          //     separable table's path has the normal's share already); first-hit depth (the gather kernel's `first`): the
+          //     first sample that passes classification finds the accumulated alpha still exactly 0, no later one does --
+          //     nothing is carried through the loop for it; the blend.  GL_MAX (gluvvShadeMIP) has no order and no
+          //     termination; otherwise exact early termination: once A == 1.0f every later weight (1-A) is exactly 0, so no
+          //     later sample can change C or A.
+#define SLAB_SHOW \
+  if (TF == 1 && Q.fast_tf) { \
+    col.x = slab_tex_chan(tx4, 0); \
+    col.y = slab_tex_chan(tx4, 1); \
+    col.z = slab_tex_chan(tx4, 2); \
+  } \
+  float4 src; \
+  float shadow[3], keepf = 1.0f; \
+  const float *shp = nullptr; \
+  if (TF != 0 && SHD) { \
+    const float mf = (float)m; \
+    if constexpr (NVL) { \
+      keepf = smk_shadow_keep(P, m, __fmaf_rn(mf, B[0], A[0]), __fmaf_rn(mf, B[1], A[1]), __fmaf_rn(mf, B[2], A[2])); \
+    } else { \
+      smk_shadow_term(P, m, __fmaf_rn(mf, B[0], A[0]), __fmaf_rn(mf, B[1], A[1]), __fmaf_rn(mf, B[2], A[2]), shadow); \
+      shp = shadow; \
+    } \
+  } \
+  if (TF == 0) { \
+    src = col; \
+  } else if (SH == 0) { \
+    src = smk_shade_sample<0, NVL>(P, col, 0.f, 0.f, 0.f, 0.f, shp, keepf); \
+  } else { \
+    if (!(TF == 1 && Q.fast_tf)) ph = phong_geom(); \
+    src = smk_shade_apply<SH, NVL>(P, col, ch1, ph, shp, keepf); \
+  } \
+  if (P.depth != nullptr && C3 == 0.0f) P.depth[(size_t)j * P.W + i] = smk_plane_depth_px<SHD>(P, m, px, py); \
+  if (P.blend == SMK_BLEND_MAX) { \
+    C0 = fmaxf(C0, src.x); \
+    C1 = fmaxf(C1, src.y); \
+    C2 = fmaxf(C2, src.z); \
+    C3 = fmaxf(C3, src.w); \
+  } else { \
+    float w = 1.0f - C3; \
+    C0 = __fmaf_rn(w, src.x, C0); \
+    C1 = __fmaf_rn(w, src.y, C1); \
+    C2 = __fmaf_rn(w, src.z, C2); \
+    C3 = __fmaf_rn(w, src.w, C3); \
+    if (C3 == 1.0f) m1 = m; \
+  }
+          if constexpr (TURN) {
+            // ONE block behind the occupancy bit.  The bit of the sample's texel quad decides whether anything of a visible
+            // sample runs at all: clear => alpha is exactly 0, and most samples of a typical transfer function end there,
+            // without the L2 round trip.  Fetch, normal, alpha, colour, shading, first-hit depth and blend are nested inside
+            // that one test, and what they hand on to each other (the texels, the Phong term, the colour) is declared inside
+            // it.  Declared in front of it and used in a second block behind it -- the other arrangement -- every one of them
+            // costs every turn of the loop a `v_mov 0` for the lanes that skip both blocks: nine in the separable table's turn
+            // (*Instruction stream of a turn*).  The same operations in the same order.
+            const bool fast = TF == 1 && Q.fast_tf;  // separable table: bilinear (V,G) lookup x optional third-axis alpha
+            const bool occ3 = TF == 2 && Q.use_occ;  // dense 3-D table, its (v, g) bitmap folded over the sheets (smk_set_tf3d)
+            int s0 = 0, s1, t0 = 0, t1;
+            float fs = 0.f, ft = 0.f;
+            bool maybe = true;  // (no bitmap: every sample goes on)
+            if (fast) {
+              smk_lin_clamp(__fmaf_rn(ch0, (float)P.sv, -0.5f), P.sv, s0, s1, fs);
+              smk_lin_clamp(__fmaf_rn(ch1, (float)P.sg, -0.5f), P.sg, t0, t1, ft);
+              if (Q.use_occ) maybe = (occ[__mul24(t0, P.occ_roww) + (s0 >> 5)] >> (s0 & 31)) & 1u;
+            } else if (occ3) {
+              smk_lin_clamp(__fmaf_rn(ch0, (float)P.s3v, -0.5f), P.s3v, s0, s1, fs);
+              smk_lin_clamp(__fmaf_rn(ch1, (float)P.s3g, -0.5f), P.s3g, t0, t1, ft);
+              maybe = (occ[__mul24(t0, P.occ_roww) + (s0 >> 5)] >> (s0 & 31)) & 1u;
+            }
+            (void)s1; (void)t1;
             if (maybe) {
               SLAB_MARK("occupancy bit");
-              if (count) {
-                d_maybe = true;
-                d_t0 = (unsigned)__builtin_amdgcn_s_memtime();
+              SmkPhong ph = {0.f, 0.f};
+              float4 col;
+              bool hit;
+              SlabTexel4 tx4 = {0, 0, 0, 0, 0.f, 0.f};
+              if (!fast) {
+                if (occ3) ch2 = tri_h_early();  // (the third coordinate of the lookup: only behind the bit)
+                hit = smk_classify<DT, TF>(P, ch0, ch1, ch2, ch3, col);
+              } else {
+                SLAB_FAST_ALPHA
+                hit = col.w != 0.0f;
               }
-              tx4 = slab_tex2d_fetch<LEAN>(P.tf_vg, P.sv, s0, t0, fs, ft);
-              if (texwait_at_issue) {
-                const unsigned t = (unsigned)__builtin_amdgcn_s_memtime();
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                d_wait = (unsigned)__builtin_amdgcn_s_memtime() - t;
+              d_hit = hit;
+              if (hit) {
+                SLAB_SHOW
               }
-              // SHADE UNDER THE FETCH.  The four texels come from L2; nothing of the normal's share of the Phong term needs
-              // them -- the second batch of LDS reads, 21 lerps, the rotation, rsqrt, two dot products and the specular power,
-              // the larger half of a visible sample's arithmetic -- so it runs here, behind the issue of the loads and in front
-              // of their first use.  (The asm statement of the LDS batch keeps the loads above it; the wait for them is the
-              // compiler's, in front of the alpha below.)  A sample that then turns out to have alpha 0 paid it for nothing.
-              if constexpr (SH != 0) ph = phong_geom();
-              if (count) {
-                const unsigned t = (unsigned)__builtin_amdgcn_s_memtime();
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                d_wait += (unsigned)__builtin_amdgcn_s_memtime() - t;
-              }
-              // alpha first (all four (V,G) texels are needed for it anyway); colour only on a hit
-              col.w = slab_tex_chan(tx4, 3);
-              if (Q.use_ah) {  // third-axis alpha (the same products as smk_classify)
-                if (lazy_h) ch2 = tri_h_early();
-                int h0, h1;
-                float fh;
-                smk_lin_clamp(__fmaf_rn(ch2, (float)P.sv, -0.5f), P.sv, h0, h1, fh);
-                col.w *= smk_lerp(ah[h0], ah[h0 + 1], fh) * SMK_INV255;
-              }
-              col.w = smk_sat(col.w);
-            }
-            hit = col.w != 0.0f;
-          } else if (TF == 2 && Q.use_occ) {
-            // dense 3-D table: the (v, g) base texel's occupancy bit, folded over the sheets (smk_set_tf3d), decides
-            // whether the eight-texel gather can return anything but alpha == 0
-            int s0, s1, t0, t1;
-            float fs, ft;
-            smk_lin_clamp(__fmaf_rn(ch0, (float)P.s3v, -0.5f), P.s3v, s0, s1, fs);
-            smk_lin_clamp(__fmaf_rn(ch1, (float)P.s3g, -0.5f), P.s3g, t0, t1, ft);
-            col.w = 0.0f;
-            hit = false;
-            if ((occ[__mul24(t0, P.occ_roww) + (s0 >> 5)] >> (s0 & 31)) & 1u) {
-              SLAB_MARK("occupancy bit");
-              ch2 = tri_h_early();  // (the third coordinate of the lookup: only now)
-              hit = smk_classify<DT, TF>(P, ch0, ch1, ch2, ch3, col);
             }
           } else {
-            SLAB_MARK("occupancy bit");  // (no bitmap: every sample goes on)
-            hit = smk_classify<DT, TF>(P, ch0, ch1, ch2, ch3, col);
-          }
-          d_hit = hit;
-          if (hit) {
+            // (frames with shadows, scene depth or the NV20 look, and the diagnostic instances: two blocks, the carriers declared in front of both -- nested,
+            //  instances that sit at the 80 VGPRs of their launch bound pass it: profiles/r06_turn_diet.md)
+            SmkPhong ph = {0.f, 0.f};
+            float4 col;
+            bool hit;
+            SlabTexel4 tx4 = {0, 0, 0, 0, 0.f, 0.f};
             if (TF == 1 && Q.fast_tf) {
-              col.x = slab_tex_chan(tx4, 0);
-              col.y = slab_tex_chan(tx4, 1);
-              col.z = slab_tex_chan(tx4, 2);
-            }
-            float4 src;
-            // frames with shadows: the light-buffer colour over the sample, as the slices nearer the light left it
-            // (smk_shadow.hip; the sample's own position: the gather kernel's fma chain)
-            float shadow[3], keepf = 1.0f;
-            const float *shp = nullptr;
-            if (TF != 0 && SHD) {
-              const float mf = (float)m;
-              if constexpr (NVL) {
-                keepf = smk_shadow_keep(P, m, __fmaf_rn(mf, B[0], A[0]), __fmaf_rn(mf, B[1], A[1]), __fmaf_rn(mf, B[2], A[2]));
-              } else {
-                smk_shadow_term(P, m, __fmaf_rn(mf, B[0], A[0]), __fmaf_rn(mf, B[1], A[1]), __fmaf_rn(mf, B[2], A[2]), shadow);
-                shp = shadow;
+              int s0, s1, t0, t1;
+              float fs, ft;
+              smk_lin_clamp(__fmaf_rn(ch0, (float)P.sv, -0.5f), P.sv, s0, s1, fs);
+              smk_lin_clamp(__fmaf_rn(ch1, (float)P.sg, -0.5f), P.sg, t0, t1, ft);
+              // occupancy bit of the texel quad (LDS): clear => alpha is exactly 0, no fetch.  Most
+              // samples of a typical transfer function end here, without the L2 round trip.
+              bool maybe = true;
+              if (Q.use_occ) maybe = (occ[__mul24(t0, P.occ_roww) + (s0 >> 5)] >> (s0 & 31)) & 1u;
+              col.w = 0.0f;
+              if (maybe) {
+                SLAB_MARK("occupancy bit");
+                SLAB_FAST_ALPHA
               }
-            }
-            if (TF == 0) {
-              src = col;  // the 1-D colour table's entries are premultiplied (TLUT.cpp:65-71), as in the gather kernel
-            } else if (SH == 0) {
-              src = smk_shade_sample<0, NVL>(P, col, 0.f, 0.f, 0.f, 0.f, shp, keepf);
+              hit = col.w != 0.0f;
+            } else if (TF == 2 && Q.use_occ) {
+              // dense 3-D table: the (v, g) base texel's occupancy bit, folded over the sheets (smk_set_tf3d), decides
+              // whether the eight-texel gather can return anything but alpha == 0
+              int s0, s1, t0, t1;
+              float fs, ft;
+              smk_lin_clamp(__fmaf_rn(ch0, (float)P.s3v, -0.5f), P.s3v, s0, s1, fs);
+              smk_lin_clamp(__fmaf_rn(ch1, (float)P.s3g, -0.5f), P.s3g, t0, t1, ft);
+              col.w = 0.0f;
+              hit = false;
+              if ((occ[__mul24(t0, P.occ_roww) + (s0 >> 5)] >> (s0 & 31)) & 1u) {
+                SLAB_MARK("occupancy bit");
+                ch2 = tri_h_early();  // (the third coordinate of the lookup: only now)
+                hit = smk_classify<DT, TF>(P, ch0, ch1, ch2, ch3, col);
+              }
             } else {
-              // (the separable table's path has the normal's share already: SHADE UNDER THE FETCH)
-              if (!(TF == 1 && Q.fast_tf)) ph = phong_geom();
-              src = smk_shade_apply<SH, NVL>(P, col, ch1, ph, shp, keepf);
+              SLAB_MARK("occupancy bit");  // (no bitmap: every sample goes on)
+              hit = smk_classify<DT, TF>(P, ch0, ch1, ch2, ch3, col);
             }
-            // first-hit depth (the gather kernel's `first`): the first sample that passes classification finds the accumulated
-            // alpha still exactly 0, no later one does -- nothing is carried through the loop for it
-            if (P.depth != nullptr && C3 == 0.0f) P.depth[(size_t)j * P.W + i] = smk_plane_depth_px<SHD>(P, m, px, py);
-            if (P.blend == SMK_BLEND_MAX) {  // GL_MAX (gluvvShadeMIP): no order, no termination
-              C0 = fmaxf(C0, src.x);
-              C1 = fmaxf(C1, src.y);
-              C2 = fmaxf(C2, src.z);
-              C3 = fmaxf(C3, src.w);
-            } else {
-              float w = 1.0f - C3;
-              C0 = __fmaf_rn(w, src.x, C0);
-              C1 = __fmaf_rn(w, src.y, C1);
-              C2 = __fmaf_rn(w, src.z, C2);
-              C3 = __fmaf_rn(w, src.w, C3);
-              // exact early termination: once A == 1.0f every later weight (1-A) is exactly 0,
-              // so no later sample can change C or A
-              if (C3 == 1.0f) m1 = m;
+            d_hit = hit;
+            if (hit) {
+              SLAB_SHOW
             }
           }
+#undef SLAB_SHOW
+#undef SLAB_FAST_ALPHA
           SLAB_MARK("blend");
           if (count && d_maybe) d_vis = (unsigned)__builtin_amdgcn_s_memtime() - d_t0;
 #undef QI

@@ -555,7 +555,7 @@ static const char *slab_ring(const RenderParams &P, SlabParams &Q, SlabShape sh,
                              size_t *lds) {
   const int nw = slab_waves(sh), nl = sh.nl;
   const bool big = slab_big(nw, nl);
-  Q.slot_bytes = Q.chunks * 1024;
+  Q.slot_bytes = Q.chunks * 1024;  // (whole KiB: the kernel's slice-table entries keep their low three bits free for flags)
   // per-slice extents (and with them the table-occupancy bitmap) from four chunks per slice up:
   // re-measured with two slices in flight, 512^3 f32 1.66 -> 1.58 ms, 512^3 u8 1.72 -> 1.68,
   // 256^3 at 1024^2 1.72 -> 1.55 (the first threshold, 12 chunks, dated from five slices in flight)
