@@ -2,7 +2,15 @@
 """bench.py -- headline benchmark of the volume ray-march hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W            (N>1 without a launcher: starts its own N ranks)
+    python bench.py --gpus N --steps K --warmup W --full     (the same, then every secondary measurement and check)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what the headline figure needs and no more: it sets up, settles, warms up, times the K
+steps, writes the last frame if --dump-outputs is given and prints the JSON line (the headline fields, the
+configuration, and the figures that fall out of the timed steps themselves: their HIP-event kernel time as
+`roofline` / `roofline_valu`, the workgroup load, the failure counters).  Everything that takes frames, volumes or
+CPU time of its own -- listed below -- runs only with --full, after the timed steps and the dump, so the timed
+region and the dumped frame are the same with and without it.
 
 Metric (BASELINE.json): Msamples/s (+ fps) of one frame of the 512^3 VGH volume at
 1024^2 x 512 planes: config 3 -- f32 VGH, 2-D LevWidget transfer function, gradient Phong.
@@ -12,11 +20,16 @@ ray-marches the full viewport against its shard and the frames are merged by one
 all-to-all + ordered "over" + gather; that merge is inside the timed region.
 
 Extra objects on the JSON line:
-  roofline      dominant kernel (the ray-marcher) vs the HBM roofline, HIP-event timed in here
+  roofline      dominant kernel (the ray-marcher) vs the HBM roofline, HIP-event timed in the timed steps
+With --full (--no-cpu, --no-north-star and --no-extra drop parts of it again):
+  samples       nominal / in-volume / taken sample counts of the frame (N=1 only)
+  without_brick_flags  the same frame with empty-space skipping off, compared bit for bit (N=1 only)
+  sortlast_check  the merged frame against the same frame ray-marched unsharded (N>1 only)
   cpu_baseline  the CPU checker (oracle/, kind "port") timed on this box's host cores on a
                 bounded band of rows of the same frame (rank 0, N=1 only)
   north_star    same kernel on the 1024^3 f32 VGH volume (config 4's single-GPU case), the
                 case BASELINE.json's >= 60 % HBM-roofline target is quoted on (N=1 only)
+  extra         dense and opaque tables, shadows, u8 and round-1 inputs at 1024^3, config 5 (N=1 only)
 """
 import argparse
 import importlib.util
@@ -610,9 +623,13 @@ def main():
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--planes", type=int, default=512)
     ap.add_argument("--kernel", type=int, default=0, help="0 auto, 1 gather, 2 slab-staged")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-north-star", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary timings (dense / opaque tables, config 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every secondary measurement and check: sample counts, the frame with "
+                         "empty-space skipping off, the CPU baseline, the north star, the secondary legs, the sort-last check")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU checker (cpu_baseline, north-star parity)")
+    ap.add_argument("--no-north-star", action="store_true", help="with --full: skip the 1024^3 north star and what hangs off it")
+    ap.add_argument("--no-extra", action="store_true",
+                    help="with --full: skip the secondary timings (flags off, dense / opaque tables, config 5)")
     ap.add_argument("--north-star-volume", type=int, default=1024)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the frame the timed steps computed in their last step to DIR/*.npy (float32; rank 0)")
@@ -732,7 +749,7 @@ def main():
         "value": samples / (t / a.steps) / 1e6, "unit": "Msamples/s", "fps": a.steps / t,
         "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": ms,
         "higher_is_better": True, "scaling": "strong" if world > 1 else "weak",
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": bool(a.full),
         "config": {"workload": "cfg3: %d^3 f32 VGH + u8 normals, 2-D LevWidget TF, R8k Phong (diff+spec), "
                                "%dx%d viewport x %d planes, pose 30deg about (1,1,0)" % (n, size, size, planes),
                    "volume": n, "viewport": size, "planes": planes,
@@ -742,7 +759,7 @@ def main():
                    "kernel": {1: "gather", 2: "slab-staged"}.get(kernel, str(kernel)),
                    # what the frame does NOT do, said on the line itself: bricks of 8x8x8 cells in which no sample can be
                    # visible under the table are neither streamed nor sampled.  Every sample that is dropped
-                   # is exactly transparent -- the frame is compared bit for bit with the flags-off one in this very run
+                   # is exactly transparent -- a --full run compares the frame bit for bit with the flags-off one
                    # (`without_brick_flags`, which is also the leg to read for the streaming kernel's own roofline).  The
                    # flags are made per volume upload (value ranges) and per table refresh (two launches, ~0.1 ms of stream
                    # time); volume and table are static here, so neither falls into the timed steps.
@@ -756,10 +773,10 @@ def main():
         out["roofline"]["kernel_frames_timed"] = kn
         if default_workload and world == 1:
             out["roofline_valu"] = roofline_valu(kms, "cfg3")
-        if world == 1:
+        if world == 1 and a.full:
             out["samples"] = sample_counts(r, frame, size, planes)
         out["workgroups"] = workgroup_load(r)
-        if world == 1 and not a.no_extra and flags_on:
+        if world == 1 and a.full and not a.no_extra and flags_on:
             out["without_brick_flags"] = no_flags_leg(r, work, frame, size, planes, a.steps)
     if dumped is not None:
         out["dump_outputs"] = dumped
@@ -786,7 +803,7 @@ def main():
     out["slab_failures"] = failures       # slice-ring frames flagged invalid during the run, all ranks (must be 0)
     if rehearse:
         out["data"] = "synthetic; REHEARSAL (all ranks on cuda:0, gloo through host memory): not a benchmark number"
-    if world > 1:
+    if world > 1 and a.full:
         # outside the timed region: the merged frame against the same frame ray-marched unsharded
         dist.barrier()
         if rank == 0:
@@ -801,12 +818,12 @@ def main():
             out["sortlast_check"] = {"max_abs_err_vs_unsharded_frame": float((merged - frame).abs().max().item()),
                                      "alpha_mean": float(merged[:, 3].mean().item()), "tolerance": 2e-5}
         dist.barrier()
-    if rank == 0 and world == 1 and not a.no_cpu:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu:
         torch.cuda.synchronize()
         gpu_frame = frame.view(size, size, 4).cpu().numpy()
         tf_eff, _ = r.tf2d_effective(256, 256)
         out["cpu_baseline"] = cpu_baseline(vghf, nrm, tf_eff, size, planes, xform, mv, gpu_frame)
-    if rank == 0 and world == 1 and not a.no_north_star:
+    if rank == 0 and world == 1 and a.full and not a.no_north_star:
         del vghf, nrm
         torch.cuda.empty_cache()
         nn_ = a.north_star_volume

@@ -86,10 +86,10 @@ def test_bench_multi_rank_plumbing_rehearsal():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    # plain `python bench.py --gpus 2`, as the driver runs it: bench.py starts its own two ranks and, on a
-    # box with one GPU, labels the run a rehearsal
+    # `python bench.py --gpus 2 --full` without a launcher: bench.py starts its own two ranks and, on a
+    # box with one GPU, labels the run a rehearsal; --full makes it render the unsharded frame and compare
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "SMK_BENCH_REHEARSE")}
-    cmd = [sys.executable, os.path.join(root, "bench.py"),
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full",
            "--gpus", "2", "--steps", "3", "--warmup", "1", "--volume", "96", "--size", "192", "--planes", "96"]
     p = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-3000:]

@@ -58,7 +58,7 @@ def main():
     fetch, write = pmc(fd, "FETCH_SIZE"), pmc(wd, "WRITE_SIZE")
     traffic = {}
     with open(os.path.join(prof, tag + "_pmc.txt"), "w") as fo:
-        fo.write("# rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes) around `python3 bench.py --steps 5 --warmup 1 --no-cpu`\n")
+        fo.write("# rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes) around `python3 bench.py --full --steps 5 --warmup 1 --no-cpu --no-extra`\n")
         fo.write("# per-dispatch values in KiB as reported; HBM bytes = (2*FETCH_SIZE + WRITE_SIZE)*1024 on gfx950\n")
         fo.write("# (FETCH_SIZE tallies 128-B requests at 64 B; calibrated on smk_k_pack<1>: known 16.11 GB read <-> 8.05 GB reported)\n")
         for k in sorted(set(fetch) | set(write)):
@@ -75,7 +75,7 @@ def main():
             res[k] = {"hbm_bytes_per_launch": (2 * sum(f_) / len(f_) + sum(w_) / len(w_)) * 1024,
                       "fetch_size_kib_mean": sum(f_) / len(f_), "write_size_kib_mean": sum(w_) / len(w_),
                       "launches": len(f_)}
-    # the default bench.py run marches two volumes: the smaller traffic belongs to the headline
+    # a bench.py --full run marches two volumes: the smaller traffic belongs to the headline
     # workload (512^3), the larger to the north-star one (1024^3)
     # (auto mode times the gather kernel once per configuration: those trial launches are not the workload)
     # (the run also launches diagnostic instances once -- the sample counts -- and, with the secondary legs, other tables:
