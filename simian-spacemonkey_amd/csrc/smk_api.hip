@@ -198,32 +198,16 @@ __global__ void smk_k_pack(const void *src, const unsigned char *grad, int bx, i
   int X = gx0 + x - Ox, Y = gy0 + y - Oy, Z = gz0 + z - Oz;
   if (X < 0 || X >= Dx || Y < 0 || Y >= Dy || Z < 0 || Z >= Dz) return;
   size_t o = ((size_t)Z * Dy + Y) * Dx + X;
-  uint32_t nb = 0x00808080u;
-  if (grad) nb = (uint32_t)grad[t * 3] | ((uint32_t)grad[t * 3 + 1] << 8) | ((uint32_t)grad[t * 3 + 2] << 16);
-  if (DT == 0) {
-    const unsigned char *s = (const unsigned char *)src + t * nelts;
-    uint32_t d = 0;
-    for (int e = 0; e < nelts; ++e) d |= (uint32_t)s[e] << (8 * e);
-    ((uint2 *)dst)[o] = make_uint2(d, nb);
-  } else if (DT == 2) {
-    // SMK_U16 (smk.h): channels 0 and 1 whole, channel 2 as its nearest 8-bit unorm in the byte the normal leaves free
-    const unsigned short *s = (const unsigned short *)src + t * nelts;
-    uint32_t d = s[0];
-    if (nelts > 1) d |= (uint32_t)s[1] << 16;
-    if (nelts > 2) nb |= (((uint32_t)s[2] * 255u + 32767u) / 65535u) << 24;
-    ((uint2 *)dst)[o] = make_uint2(d, nb);
+  uint32_t nb = SMK_NRM_NONE;
+  if (grad) nb = smk_nrm_word(grad[t * 3], grad[t * 3 + 1], grad[t * 3 + 2]);
+  if (DT == SMK_U8) {
+    ((uint2 *)dst)[o] = smk_pack_u8((const unsigned char *)src + t * nelts, nelts, nb);
+  } else if (DT == SMK_U16) {
+    ((uint2 *)dst)[o] = smk_pack_u16((const unsigned short *)src + t * nelts, nelts, nb);
   } else {
-    const float *s = (const float *)src + t * nelts;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    v.x = s[0];
-    if (nelts > 1) v.y = s[1];
-    if (nelts > 2) v.z = s[2];
-    if (n_in_w) v.w = __uint_as_float(nb);
-    else {
-      v.w = s[3];
-      if (nrm) nrm[o] = nb;
-    }
-    ((float4 *)dst)[o] = v;
+    const uint4 v = smk_pack_f32((const float *)src + t * nelts, nelts, nb, n_in_w);
+    if (!n_in_w && nrm) nrm[o] = nb;
+    ((uint4 *)dst)[o] = v;
   }
 }
 

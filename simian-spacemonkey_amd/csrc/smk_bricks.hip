@@ -42,14 +42,10 @@ __global__ __launch_bounds__(256) void smk_k_brick_minmax(const void *vox, int D
     const int x = i % ex, y = (i / ex) % ey, z = i / (ex * ey);
     const size_t o = ((size_t)(z0 + z) * Dy + (y0 + y)) * Dx + (x0 + x);
     float v, g;
-    if (DT == 0) {
+    if (DT != SMK_F32) {  // (u16: the 16-bit first two channels, scaled as a sample scales them)
       const uint32_t d = ((const uint2 *)vox)[o].x;
-      v = (float)(d & 0xffu) * SMK_INV255;
-      g = (float)((d >> 8) & 0xffu) * SMK_INV255;
-    } else if (DT == 2) {  // (u16: the 16-bit first two channels, scaled as a sample scales them)
-      const uint32_t d = ((const uint2 *)vox)[o].x;
-      v = (float)(d & 0xffffu) * SMK_INV65535;
-      g = (float)(d >> 16) * SMK_INV65535;
+      v = (float)smk_vox8_c0<DT>(d) * (DT == SMK_U8 ? SMK_INV255 : SMK_INV65535);
+      g = (float)smk_vox8_c1<DT>(d) * (DT == SMK_U8 ? SMK_INV255 : SMK_INV65535);
     } else {
       const float4 f = ((const float4 *)vox)[o];
       v = f.x;

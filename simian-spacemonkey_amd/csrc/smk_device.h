@@ -14,6 +14,7 @@
 //   front-to-back blend ................. R8kVolRen3D.cpp:1441-1449
 #pragma once
 #include "smk_internal.h"
+#include "smk_packed.h"
 
 #define SMK_INV255 (1.0f / 255.0f)
 #define SMK_INV65535 (1.0f / 65535.0f)
@@ -48,23 +49,7 @@ __device__ __forceinline__ void smk_lin_repeat(float x, int n, int &i0, int &i1,
 
 __device__ __forceinline__ float smk_ub(uint32_t v, int k) { return (float)((v >> (8 * k)) & 0xffu); }
 
-// one voxel corner: 4 channels (raw: u8 as 0..255 floats, u16 as 0..65535 floats -- its third channel 0..255 --, f32 as
-// is) + packed normal bits
-struct SmkCorner {
-  float c0, c1, c2, c3;
-  uint32_t nb;
-};
-
-// u16 voxels (SMK_U16, smk.h): uint2 {c0 | c1 << 16, n0 | n1 << 8 | n2 << 16 | q8(c2) << 24}.  The normal bits sit where the
-// u8 voxel has them (smk_nrm looks at the low three bytes only), the third channel's 8 bits ride in the spare byte
-__device__ __forceinline__ void smk_decode_u16(uint2 v, SmkCorner &k) {
-  k.c0 = (float)(v.x & 0xffffu);
-  k.c1 = (float)(v.x >> 16);
-  k.c2 = (float)(v.y >> 24);
-  k.c3 = 0.0f;
-  k.nb = v.y;
-}
-
+// (SmkCorner, one voxel corner as the fetches below hand it on, and smk_decode_u16: smk_packed.h)
 template <int DT>
 __device__ __forceinline__ SmkCorner smk_load_corner(const RenderParams &P, size_t idx) {
   SmkCorner k;
@@ -87,7 +72,7 @@ __device__ __forceinline__ SmkCorner smk_load_corner(const RenderParams &P, size
       k.nb = __float_as_uint(v.w);
     } else {
       k.c3 = v.w;
-      k.nb = P.nrm ? P.nrm[idx] : 0x808080u;
+      k.nb = P.nrm ? P.nrm[idx] : SMK_NRM_NONE;
     }
   }
   return k;

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/smk.h"
+#include "smk_packed.h"
 
 #define SMK_MAX_RANKS 8
 #define SMK_TIMING_RING 64
@@ -566,6 +567,14 @@ void smk_free_steps(smk_ctx *c);
 int smk_step_slot(const smk_ctx *c, int timestep);
 int smk_step_read_begin(smk_ctx *c, int k, hipStream_t s);
 int smk_step_read_end(smk_ctx *c, int k, hipStream_t s);
+// the slot of `timestep` for entry `who`, with the refusals that the histogram, the probe and the read-back of a step share
+__attribute__((visibility("hidden"))) int step_slot(smk_ctx *c, const char *who, int timestep, int *k);
+// a step of this context keeps its normals in a buffer of their own, TimeStep::nrm (smk_packed.h: four-channel f32)
+inline bool smk_step_separate_normals(const smk_ctx *c) { return c->dtype == SMK_F32 && c->nelts == 4 && c->have_normals; }
+// the bytes of that buffer: a word per voxel of the stored box, or 0
+inline size_t smk_step_nrm_bytes(const smk_ctx *c) { return smk_step_separate_normals(c) ? (size_t)c->D[0] * c->D[1] * c->D[2] * 4 : 0; }
+// the rows of this context's region in its stored box (smk_packed.h)
+inline StepRows smk_step_rows(const smk_ctx *c) { return step_rows(c->g0, c->g1, c->O, c->D, c->dtype == SMK_F32); }
 // A step written by kernels on stream s from what is on the device already (smk_blend_timesteps, smk_step_derive.hip).
 // _output_slot: the slot step `id` takes -- a cached id's own, else one by the ring's rule that is neither slot ka nor kb
 // (the sources; -1: none) nor the current step's; -1 when the ring has fewer than *need slots.  _write_begin: the kernels on s

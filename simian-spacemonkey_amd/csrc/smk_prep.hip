@@ -305,20 +305,16 @@ extern "C" int smk_merge_fields_device(smk_ctx *c, const void *d_fields, int nf,
 }
 
 // ------------------------------------------------------------------------------- 2-D histogram
-// MetaVolume::hist2D (MetaVolume.cpp:1650-1688): counts of (value, gradient) byte pairs.  HBM-bound
-// byte work: every workgroup keeps ALL 65536 bins in LDS as 16-bit counters (128 KB) and flushes
-// them to the global 32-bit bins after at most 61440 voxels, so no counter can overflow; a wave
-// whose 64 voxels fall into one bin (air, the common case) adds once instead of 64 times.
-#define SMK_HIST_CHUNK 61440  // voxels per flush (< 65536), a multiple of the block size
+// MetaVolume::hist2D (MetaVolume.cpp:1650-1688): counts of (value, gradient) byte pairs.  HBM-bound byte work, binned in
+// LDS (hist_lds_*, smk_prep_device.h)
 
 __global__ __launch_bounds__(1024) void smk_k_hist2d(const unsigned char *vol, int nelts, size_t nvox, unsigned *bins) {
   extern __shared__ unsigned h16[];  // 32768 words = 65536 halves
-  const size_t nchunks = (nvox + SMK_HIST_CHUNK - 1) / SMK_HIST_CHUNK;
+  const size_t nchunks = (nvox + HIST_CHUNK - 1) / HIST_CHUNK;
   for (size_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
-    for (int w = threadIdx.x; w < 32768; w += 1024) h16[w] = 0;
-    __syncthreads();
-    const size_t base = chunk * SMK_HIST_CHUNK;
-    for (int k = 0; k < SMK_HIST_CHUNK / 1024; ++k) {
+    hist_lds_zero(h16);
+    const size_t base = chunk * HIST_CHUNK;
+    for (int k = 0; k < HIST_CHUNK / 1024; ++k) {
       const size_t i = base + (size_t)k * 1024 + threadIdx.x;
       const bool ok = i < nvox;
       unsigned key = 0;
@@ -326,36 +322,18 @@ __global__ __launch_bounds__(1024) void smk_k_hist2d(const unsigned char *vol, i
         const unsigned char *d = vol + i * nelts;
         key = (unsigned)d[0] | ((unsigned)d[1] << 8);
       }
-      const unsigned long long live = __ballot(ok);
-      if (!live) continue;
-      const unsigned first = __builtin_amdgcn_readfirstlane(key);  // (of the first live lane)
-      if (__ballot(ok && key == first) == live) {
-        if (ok && (int)(threadIdx.x & 63) == __builtin_ctzll(live))
-          atomicAdd(&h16[first >> 1], (unsigned)__builtin_popcountll(live) << ((first & 1) * 16));
-      } else if (ok) {
-        atomicAdd(&h16[key >> 1], 1u << ((key & 1) * 16));
-      }
+      hist_lds_count(h16, ok, key);
     }
-    __syncthreads();
-    for (int w = threadIdx.x; w < 32768; w += 1024) {
-      const unsigned x = h16[w];
-      if (x & 0xffffu) atomicAdd(&bins[2 * w], x & 0xffffu);
-      if (x >> 16) atomicAdd(&bins[2 * w + 1], x >> 16);
-    }
-    __syncthreads();
+    hist_lds_flush(h16, bins);
   }
 }
 
 static int hist2d_count(smk_ctx *c, const unsigned char *d_vol, int nelts, size_t nvox, unsigned *d_bins) {
   static bool attr[64] = {};  // per device
-  const int dev = c->device;
-  if (dev < 0 || dev >= 64 || !attr[dev]) {
-    PCHK(c, hipFuncSetAttribute((const void *)smk_k_hist2d, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-    if (dev >= 0 && dev < 64) attr[dev] = true;
-  }
-  const size_t nchunks = (nvox + SMK_HIST_CHUNK - 1) / SMK_HIST_CHUNK;
+  PCHK(c, hist_lds_allow((const void *)smk_k_hist2d, c->device, attr));
+  const size_t nchunks = (nvox + HIST_CHUNK - 1) / HIST_CHUNK;
   const unsigned blocks = (unsigned)std::min<size_t>(nchunks, 256 * 4);
-  hipLaunchKernelGGL(smk_k_hist2d, dim3(blocks), dim3(1024), 128 * 1024, c->stream, d_vol, nelts, nvox, d_bins);
+  hipLaunchKernelGGL(smk_k_hist2d, dim3(blocks), dim3(1024), HIST_LDS_BYTES, c->stream, d_vol, nelts, nvox, d_bins);
   PCHK(c, hipGetLastError());
   return 0;
 }
@@ -588,24 +566,15 @@ extern "C" int smk_merge_fields_f32_device(smk_ctx *c, const void *d_fields, int
   return 0;
 }
 
-// a float channel's histogram bin: t = v * 255 in fp32; NaN and t < 0 -> 0, t >= 255 -> 255, else (int)t
-__device__ __forceinline__ unsigned hist_bin_f32(float v) {
-  const float t = v * 255.0f;
-  if (!(t >= 0.f)) return 0;
-  if (t >= 255.f) return 255;
-  return (unsigned)(int)t;
-}
-
-// smk_k_hist2d's LDS-binned counting with the key taken from two floats
+// smk_k_hist2d's LDS-binned counting with the key taken from two floats (hist_bin_f32, smk_prep_device.h)
 // (pairs: nelts == 2 and the volume 8-byte aligned, so a voxel is one float2 load)
 __global__ __launch_bounds__(1024) void smk_k_hist2d_f32(const float *vol, int nelts, int pairs, size_t nvox, unsigned *bins) {
   extern __shared__ unsigned h16[];  // 32768 words = 65536 halves
-  const size_t nchunks = (nvox + SMK_HIST_CHUNK - 1) / SMK_HIST_CHUNK;
+  const size_t nchunks = (nvox + HIST_CHUNK - 1) / HIST_CHUNK;
   for (size_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
-    for (int w = threadIdx.x; w < 32768; w += 1024) h16[w] = 0;
-    __syncthreads();
-    const size_t base = chunk * SMK_HIST_CHUNK;
-    for (int k = 0; k < SMK_HIST_CHUNK / 1024; ++k) {
+    hist_lds_zero(h16);
+    const size_t base = chunk * HIST_CHUNK;
+    for (int k = 0; k < HIST_CHUNK / 1024; ++k) {
       const size_t i = base + (size_t)k * 1024 + threadIdx.x;
       const bool ok = i < nvox;
       unsigned key = 0;
@@ -622,37 +591,19 @@ __global__ __launch_bounds__(1024) void smk_k_hist2d_f32(const float *vol, int n
         }
         key = hist_bin_f32(c0) | (hist_bin_f32(c1) << 8);
       }
-      const unsigned long long live = __ballot(ok);
-      if (!live) continue;
-      const unsigned first = __builtin_amdgcn_readfirstlane(key);  // (of the first live lane)
-      if (__ballot(ok && key == first) == live) {
-        if (ok && (int)(threadIdx.x & 63) == __builtin_ctzll(live))
-          atomicAdd(&h16[first >> 1], (unsigned)__builtin_popcountll(live) << ((first & 1) * 16));
-      } else if (ok) {
-        atomicAdd(&h16[key >> 1], 1u << ((key & 1) * 16));
-      }
+      hist_lds_count(h16, ok, key);
     }
-    __syncthreads();
-    for (int w = threadIdx.x; w < 32768; w += 1024) {
-      const unsigned x = h16[w];
-      if (x & 0xffffu) atomicAdd(&bins[2 * w], x & 0xffffu);
-      if (x >> 16) atomicAdd(&bins[2 * w + 1], x >> 16);
-    }
-    __syncthreads();
+    hist_lds_flush(h16, bins);
   }
 }
 
 static int hist2d_count_f32(smk_ctx *c, const float *d_vol, int nelts, size_t nvox, unsigned *d_bins) {
   static bool attr[64] = {};  // per device
-  const int dev = c->device;
-  if (dev < 0 || dev >= 64 || !attr[dev]) {
-    PCHK(c, hipFuncSetAttribute((const void *)smk_k_hist2d_f32, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-    if (dev >= 0 && dev < 64) attr[dev] = true;
-  }
-  const size_t nchunks = (nvox + SMK_HIST_CHUNK - 1) / SMK_HIST_CHUNK;
+  PCHK(c, hist_lds_allow((const void *)smk_k_hist2d_f32, c->device, attr));
+  const size_t nchunks = (nvox + HIST_CHUNK - 1) / HIST_CHUNK;
   const unsigned blocks = (unsigned)std::min<size_t>(nchunks, 256 * 4);
   const int pairs = nelts == 2 && ((uintptr_t)d_vol & 7) == 0;  // (a float-aligned pointer into a larger buffer takes the scalar loads)
-  hipLaunchKernelGGL(smk_k_hist2d_f32, dim3(blocks), dim3(1024), 128 * 1024, c->stream, d_vol, nelts, pairs, nvox, d_bins);
+  hipLaunchKernelGGL(smk_k_hist2d_f32, dim3(blocks), dim3(1024), HIST_LDS_BYTES, c->stream, d_vol, nelts, pairs, nvox, d_bins);
   PCHK(c, hipGetLastError());
   return 0;
 }

@@ -197,3 +197,52 @@ __device__ __forceinline__ void nrm_gradient(int blur, int sx, int sy, int sz, i
   g[1] = a1 / div;
   g[2] = a2 / div;
 }
+
+// a float channel's histogram bin: t = v * 255 in fp32; NaN and t < 0 -> 0, t >= 255 -> 255, else (int)t
+__device__ __forceinline__ unsigned hist_bin_f32(float v) {
+  const float t = v * 255.0f;
+  if (!(t >= 0.f)) return 0;
+  if (t >= 255.f) return 255;
+  return (unsigned)(int)t;
+}
+
+// Every workgroup (1024 lanes) keeps ALL 65536 bins as 16-bit counters in 128 KB of dynamic LDS (h16: 32768 words) and flushes
+// them to the global 32-bit bins after fewer than 65536 voxels, so no counter can overflow
+constexpr int HIST_LDS_BYTES = 128 * 1024;
+constexpr int HIST_CHUNK = 61440;  // voxels per flush: below 65536, a multiple of the workgroup size
+
+__device__ __forceinline__ void hist_lds_zero(unsigned *h16) {
+  for (int w = threadIdx.x; w < 32768; w += 1024) h16[w] = 0;
+  __syncthreads();
+}
+
+// every lane of a wave calls this (ok: it has a voxel, key: its bin b1 * 256 + b0): live lanes that all share a key add once
+__device__ __forceinline__ void hist_lds_count(unsigned *h16, bool ok, unsigned key) {
+  const unsigned long long live = __ballot(ok);
+  if (!live) return;
+  const unsigned first = __builtin_amdgcn_readlane(key, __builtin_ctzll(live));  // (of the first live lane)
+  if (__ballot(ok && key == first) == live) {
+    if (ok && (int)(threadIdx.x & 63) == __builtin_ctzll(live))
+      atomicAdd(&h16[first >> 1], (unsigned)__builtin_popcountll(live) << ((first & 1) * 16));
+  } else if (ok) {
+    atomicAdd(&h16[key >> 1], 1u << ((key & 1) * 16));
+  }
+}
+
+__device__ __forceinline__ void hist_lds_flush(const unsigned *h16, unsigned *bins) {
+  __syncthreads();
+  for (int w = threadIdx.x; w < 32768; w += 1024) {
+    const unsigned v = h16[w];
+    if (v & 0xffffu) atomicAdd(&bins[2 * w], v & 0xffffu);
+    if (v >> 16) atomicAdd(&bins[2 * w + 1], v >> 16);
+  }
+  __syncthreads();
+}
+
+// the kernel's dynamic LDS raised to HIST_LDS_BYTES, once per device: `done` is that kernel's own flags, one per device
+inline hipError_t hist_lds_allow(const void *kernel, int device, bool (&done)[64]) {
+  if (device >= 0 && device < 64 && done[device]) return hipSuccess;
+  const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, HIST_LDS_BYTES);
+  if (e == hipSuccess && device >= 0 && device < 64) done[device] = true;
+  return e;
+}

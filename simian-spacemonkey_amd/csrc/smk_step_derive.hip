@@ -15,7 +15,7 @@
 //   pass 2 (smk_k_derive_write): the reference's +-1e8 seeds applied to those words, the scaled V of every tile voxel (0 on the
 //          volume's border and outside it) into a second LDS tile, then per voxel gm and hs again, the scaling, the normal
 //          from the V tile, and one 8- or 16-byte store of the packed voxel.
-// The arithmetic is smk_prep.hip's, through smk_prep_device.h.
+// The arithmetic is smk_prep.hip's, through smk_prep_device.h; the packed voxel is smk_packed.h's.
 #include <algorithm>
 
 #include "smk_internal.h"
@@ -23,8 +23,8 @@
 
 namespace {
 
-// where the scalar comes from: a dense array of the type (the values of smk_dtype), or channel 0 of a slot's packed voxels
-enum { DS_U8 = 0, DS_F32 = 1, DS_U16 = 2, DS_PK_U8 = 3, DS_PK_U16 = 4, DS_PK_F32 = 5 };
+// where the scalar comes from: a dense array of a type (SRC is its smk_dtype), or channel 0 of a slot's packed voxels
+enum { DS_PK_U8 = 3, DS_PK_U16 = 4, DS_PK_F32 = 5 };
 
 constexpr int DV_TX = 32, DV_TY = 8, DV_TZ = 8, DV_AP = 2;
 constexpr int DV_LX = DV_TX + 2 * DV_AP, DV_LY = DV_TY + 2 * DV_AP, DV_LZ = DV_TZ + 2 * DV_AP;
@@ -52,9 +52,9 @@ __device__ __forceinline__ void dv_load_tile(const DeriveParams &P, int x0, int 
       float a = 0.f, b = 0.f;
       if (X >= 0 && X < P.N[0] && Y >= 0 && Y < P.N[1] && Z >= 0 && Z < P.N[2]) {
         const uint4 v = ((const uint4 *)P.src)[(((size_t)Z * P.D[1] + Y) * P.D[0] + X) >> 1];
-        const uint32_t mask = SRC == DS_PK_U8 ? 0xffu : 0xffffu;
-        a = (float)(v.x & mask);
-        if (X + 1 < P.N[0]) b = (float)(v.z & mask);
+        constexpr int DT = SRC == DS_PK_U8 ? SMK_U8 : SMK_U16;
+        a = (float)smk_vox8_c0<DT>(v.x);
+        if (X + 1 < P.N[0]) b = (float)smk_vox8_c0<DT>(v.z);
       }
       S[row * DV_LX + 2 * cu] = a;
       S[row * DV_LX + 2 * cu + 1] = b;
@@ -69,7 +69,7 @@ __device__ __forceinline__ void dv_load_tile(const DeriveParams &P, int x0, int 
           a = __uint_as_float(((const uint4 *)P.src)[((size_t)Z * P.D[1] + Y) * P.D[0] + X].x);
         } else {
           const size_t o = ((size_t)Z * P.N[1] + Y) * P.N[0] + X;
-          a = SRC == DS_U8 ? (float)((const unsigned char *)P.src)[o] : SRC == DS_U16 ? (float)((const unsigned short *)P.src)[o] : ((const float *)P.src)[o];
+          a = SRC == SMK_U8 ? (float)((const unsigned char *)P.src)[o] : SRC == SMK_U16 ? (float)((const unsigned short *)P.src)[o] : ((const float *)P.src)[o];
         }
       }
       S[t] = a;
@@ -185,7 +185,7 @@ __global__ __launch_bounds__(256) void smk_k_derive_write(const DeriveParams P) 
       dv_gh(P, S, l, Z, Y, X, gm, hs);
       vgh_scale(S[l], gm, hs, dmin, dmax, gmin, gmax, hmin, hmax, q, f);
     }
-    uint32_t nb = 0x00808080u;
+    uint32_t nb = SMK_NRM_NONE;
     if (P.normals) {
       float g[3];
       unsigned char n[3];
@@ -195,16 +195,16 @@ __global__ __launch_bounds__(256) void smk_k_derive_write(const DeriveParams P) 
       });
       if (OUT == SMK_U8) nrm_store(g, n);
       else nrm_store_f32(g, n);
-      nb = (uint32_t)n[0] | ((uint32_t)n[1] << 8) | ((uint32_t)n[2] << 16);
+      nb = smk_nrm_word(n[0], n[1], n[2]);
     }
     if (OUT == SMK_U8) {
-      ((uint2 *)P.out)[o] = make_uint2((uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16), nb);
+      ((uint2 *)P.out)[o] = smk_pack_u8(q, 3, nb);
     } else if (OUT == SMK_U16) {
-      // smk_quantize_u16_device of the floats, then the pack's 8-bit unorm of the third channel (smk_k_pack)
-      const uint32_t s0 = quant_u16(f[0]), s1 = quant_u16(f[1]), s2 = quant_u16(f[2]);
-      ((uint2 *)P.out)[o] = make_uint2(s0 | (s1 << 16), nb | (((s2 * 255u + 32767u) / 65535u) << 24));
+      // smk_quantize_u16_device of the floats, then the pack's 8-bit unorm of the third channel
+      const unsigned short s[3] = {quant_u16(f[0]), quant_u16(f[1]), quant_u16(f[2])};
+      ((uint2 *)P.out)[o] = smk_pack_u16(s, 3, nb);
     } else {
-      ((uint4 *)P.out)[o] = make_uint4(__float_as_uint(f[0]), __float_as_uint(f[1]), __float_as_uint(f[2]), nb);
+      ((uint4 *)P.out)[o] = smk_pack_f32(f, 3, nb, 1);
     }
   }
 }
@@ -269,9 +269,9 @@ int derive_enqueue(smk_ctx *c, const char *who, int kind, const void *src, int k
   P.normals = c->have_normals ? 1 : 0;
   hipError_t e;
   switch (kind) {
-    case DS_U8: e = launch_derive<DS_U8>(P, c->dtype, s); break;
-    case DS_F32: e = launch_derive<DS_F32>(P, c->dtype, s); break;
-    case DS_U16: e = launch_derive<DS_U16>(P, c->dtype, s); break;
+    case SMK_U8: e = launch_derive<SMK_U8>(P, c->dtype, s); break;
+    case SMK_F32: e = launch_derive<SMK_F32>(P, c->dtype, s); break;
+    case SMK_U16: e = launch_derive<SMK_U16>(P, c->dtype, s); break;
     case DS_PK_U8: e = launch_derive<DS_PK_U8>(P, c->dtype, s); break;
     case DS_PK_U16: e = launch_derive<DS_PK_U16>(P, c->dtype, s); break;
     default: e = launch_derive<DS_PK_F32>(P, c->dtype, s); break;
@@ -310,7 +310,7 @@ extern "C" int smk_upload_timestep_scalar_device(smk_ctx *c, int timestep, const
     FAIL(c, "%s: scalar_dtype %d is none of SMK_U8, SMK_U16, SMK_F32", who, (int)scalar_dtype);
   if (sx != c->N[0] || sy != c->N[1] || sz != c->N[2])
     FAIL(c, "%s: time step %d: sizes %dx%dx%d differ from the series' %dx%dx%d", who, timestep, sx, sy, sz, c->N[0], c->N[1], c->N[2]);
-  const size_t eb = scalar_dtype == SMK_U8 ? 1 : scalar_dtype == SMK_U16 ? 2 : 4;
+  const size_t eb = smk_elem_bytes(scalar_dtype);
   if ((uintptr_t)d_scalar % eb) FAIL(c, "%s: d_scalar is not aligned to its %zu-byte elements", who, eb);
   return derive_enqueue(c, who, (int)scalar_dtype, d_scalar, -1, timestep, compat, blur, stream ? (hipStream_t)stream : c->stream);
 }

@@ -5,137 +5,73 @@
 // the host's [z][y][x][nelts] array.  A step that came from a device buffer, a blended step, a shard's region and 16-bit
 // voxels have no such array: what the context owns is the packed voxels of a ring slot (TimeStep::vox), so these entries
 // read those.  smk_prep.hip's histogram kernels stay what they are for raw arrays; this file holds the packed-layout family.
-//
-// Region and stored box.  The slot stores D[0] x D[1] x D[2] voxels from O (region + halo, rows of 8-byte voxels made even
-// by one more voxel or a pad column); the histogram counts the region [g0, g1) alone: ny * nz rows, each a contiguous run of
-// nx = g1x - g0x voxels that starts g0 - O into the box.  A row is read in whole 16-byte units -- one f32 voxel, or two
-// 8-byte voxels -- so the run of an 8-byte layout is widened to even voxel offsets: the first unit's low voxel is masked
-// when g0x - Ox is odd, the last unit's high voxel when the run ends on an odd offset.  D[0] is even for those layouts, so
-// both masked voxels lie inside the row (nothing is read outside the stored box).
+// The packed layouts, the stored box and the region's rows: smk_packed.h.  The histogram counts the region [g0, g1) alone.
 #include <string.h>
 
 #include <algorithm>
 #include <vector>
 
 #include "smk_internal.h"
+#include "smk_prep_device.h"
 
 namespace {
 
-// voxels per flush of the 16-bit LDS counters, smk_k_hist2d's: below 65536, a multiple of the workgroup size
-constexpr unsigned SH_CHUNK = 61440;
 constexpr int SH_PER = 4;  // units a lane loads before it bins them (a chunk's last turn is a partial one)
 
-enum { SH_U8 = 0, SH_F32 = 1, SH_U16 = 2 };  // smk_dtype's values: the packed layout of an instance
-
-// floor(n / d) of 32-bit numbers by a multiplication and two shifts (Granlund and Montgomery 1994, figure 4.1): exact for
-// every n < 2^32 and d >= 1.  A lane finds its row and column with two of these in place of two integer divisions
-struct StepDiv {
-  unsigned m, sh1, sh2;
-};
-
-StepDiv step_div(unsigned d) {
-  unsigned l = 0;
-  while ((1ull << l) < d) ++l;  // ceil(log2 d)
-  StepDiv k;
-  k.m = (unsigned)((((1ull << l) - d) << 32) / d + 1);
-  k.sh1 = l < 1 ? l : 1;
-  k.sh2 = l > 1 ? l - 1 : 0;
-  return k;
-}
-
-__device__ __forceinline__ unsigned sh_div(unsigned n, const StepDiv k) {
-  const unsigned t = __umulhi(k.m, n);
-  return (t + ((n - t) >> k.sh1)) >> k.sh2;
-}
-
 struct StepHistParams {
-  const uint4 *vox;            // the slot's packed voxels
-  unsigned *bins;              // [65536] global counts
-  unsigned long long units;    // rows * upr
-  unsigned upr;                // 16-byte units per row
-  unsigned ny;                 // rows per z
-  unsigned long long pitch;    // units per stored row: D[0], or D[0] / 2
-  unsigned D1;                 // stored rows per z
-  unsigned ox, oy, oz;         // the first unit's offset in its stored row; g0 - O in y and z
-  unsigned head, tail;         // 8-byte layouts: the first unit's low / the last unit's high voxel lies outside the run
-  StepDiv by_upr, by_ny;
+  const uint4 *vox;  // the slot's packed voxels
+  unsigned *bins;    // [65536] global counts
+  StepRows R;
 };
-
-// smk_prep.hip's hist_bin_f32, as smk.h states it
-__device__ __forceinline__ unsigned sh_bin_f32(float v) {
-  const float t = v * 255.0f;
-  if (!(t >= 0.f)) return 0;
-  if (t >= 255.f) return 255;
-  return (unsigned)(int)t;
-}
 
 // the key b1 * 256 + b0 of an 8-byte voxel's first word
 template <int L>
 __device__ __forceinline__ unsigned sh_key8(unsigned w) {
-  if (L == SH_U8) return w & 0xffffu;                     // the two bytes are the bins
-  return (w & 0xffffu) / 257u | ((w >> 16) / 257u) << 8;  // u16: floor(255 v / 65535) in integers
+  if (L == SMK_U8) return w & 0xffffu;  // the two bytes are the bins
+  return smk_u16_bin(smk_vox8_c0<SMK_U16>(w)) | smk_u16_bin(smk_vox8_c1<SMK_U16>(w)) << 8;
 }
 
-// smk_k_hist2d's counting step: a wave whose live lanes share a key adds their number once
-__device__ __forceinline__ void sh_count(unsigned *h16, bool ok, unsigned key) {
-  const unsigned long long live = __ballot(ok);
-  if (!live) return;
-  const unsigned first = __builtin_amdgcn_readlane(key, __builtin_ctzll(live));  // (of the first live lane)
-  if (__ballot(ok && key == first) == live) {
-    if (ok && (int)(threadIdx.x & 63) == __builtin_ctzll(live))
-      atomicAdd(&h16[first >> 1], (unsigned)__builtin_popcountll(live) << ((first & 1) * 16));
-  } else if (ok) {
-    atomicAdd(&h16[key >> 1], 1u << ((key & 1) * 16));
-  }
-}
-
-// a lane's SH_PER units of the turn that starts at unit k of a chunk (u0, y0, z0: the chunk's first unit), and their columns
-__device__ __forceinline__ void sh_load(const StepHistParams &P, unsigned k, unsigned lim, unsigned u0, unsigned y0, unsigned long long z0,
-                                        uint4 (&x)[SH_PER], unsigned (&col)[SH_PER]) {
+// a lane's SH_PER units of the turn that starts at unit k of the chunk that starts at C, and their columns
+__device__ __forceinline__ void sh_load(const StepHistParams &P, unsigned k, unsigned lim, const StepOrigin &C, uint4 (&x)[SH_PER],
+                                        unsigned (&col)[SH_PER]) {
 #pragma unroll
   for (int j = 0; j < SH_PER; ++j) {
     const unsigned i = k + (unsigned)j * 1024 + threadIdx.x;
     col[j] = 0;
     x[j] = make_uint4(0, 0, 0, 0);
     if (i < lim) {
-      const unsigned t = u0 + i, q = sh_div(t, P.by_upr), ry = y0 + q, zq = sh_div(ry, P.by_ny);
-      col[j] = t - q * P.upr;
-      const unsigned long long z = z0 + zq + P.oz, y = (unsigned long long)(ry - zq * P.ny) + P.oy;
-      x[j] = P.vox[(z * P.D1 + y) * P.pitch + P.ox + col[j]];
+      unsigned q;
+      x[j] = P.vox[step_unit(P.R, C, i, col[j], q)];
     }
   }
 }
 
-// All 65536 bins as 16-bit LDS counters, flushed to the global bins after a chunk of at most SH_CHUNK voxels.  A chunk is a
+// All 65536 bins as 16-bit LDS counters, flushed to the global bins after a chunk of at most HIST_CHUNK voxels.  A chunk is a
 // run of consecutive units of the region's rows; its first unit's row and column are found once per chunk, a lane's from there.
 template <int L>
 __global__ __launch_bounds__(1024) void smk_k_step_hist(const StepHistParams P) {
   extern __shared__ unsigned h16[];  // 32768 words = 65536 halves
-  constexpr unsigned CH = L == SH_F32 ? SH_CHUNK : SH_CHUNK / 2;  // units per chunk
-  const unsigned long long nchunks = (P.units + CH - 1) / CH;
+  constexpr unsigned CH = L == SMK_F32 ? HIST_CHUNK : HIST_CHUNK / 2;  // units per chunk
+  const unsigned long long nchunks = (P.R.units + CH - 1) / CH;
   for (unsigned long long chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
-    for (int w = threadIdx.x; w < 32768; w += 1024) h16[w] = 0;
-    __syncthreads();
+    hist_lds_zero(h16);
     const unsigned long long base = chunk * CH;
-    const unsigned lim = P.units - base < CH ? (unsigned)(P.units - base) : CH;
-    const unsigned long long row0 = base / P.upr;
-    const unsigned u0 = (unsigned)(base - row0 * P.upr);
-    const unsigned long long z0 = row0 / P.ny;
-    const unsigned y0 = (unsigned)(row0 - z0 * P.ny);
+    const unsigned lim = P.R.units - base < CH ? (unsigned)(P.R.units - base) : CH;
+    const StepOrigin C = step_chunk_origin(P.R, base);
     // a turn = SH_PER units per lane; the next turn's loads are issued before this turn's units are binned
     uint4 x[SH_PER], xn[SH_PER];
     unsigned col[SH_PER], coln[SH_PER];
-    sh_load(P, 0, lim, u0, y0, z0, x, col);
+    sh_load(P, 0, lim, C, x, col);
     for (unsigned k = 0; k < lim; k += 1024 * SH_PER) {
-      if (k + 1024 * SH_PER < lim) sh_load(P, k + 1024 * SH_PER, lim, u0, y0, z0, xn, coln);
+      if (k + 1024 * SH_PER < lim) sh_load(P, k + 1024 * SH_PER, lim, C, xn, coln);
 #pragma unroll
       for (int j = 0; j < SH_PER; ++j) {
         const bool ok = k + (unsigned)j * 1024 + threadIdx.x < lim;
-        if (L == SH_F32) {
-          sh_count(h16, ok, ok ? sh_bin_f32(__uint_as_float(x[j].x)) | sh_bin_f32(__uint_as_float(x[j].y)) << 8 : 0u);
+        if (L == SMK_F32) {
+          hist_lds_count(h16, ok, ok ? hist_bin_f32(__uint_as_float(x[j].x)) | hist_bin_f32(__uint_as_float(x[j].y)) << 8 : 0u);
         } else {
-          sh_count(h16, ok && !(P.head && col[j] == 0), ok ? sh_key8<L>(x[j].x) : 0u);
-          sh_count(h16, ok && !(P.tail && col[j] == P.upr - 1), ok ? sh_key8<L>(x[j].z) : 0u);
+          hist_lds_count(h16, ok && !step_low_masked(P.R, col[j]), ok ? sh_key8<L>(x[j].x) : 0u);
+          hist_lds_count(h16, ok && !step_high_masked(P.R, col[j]), ok ? sh_key8<L>(x[j].z) : 0u);
         }
       }
 #pragma unroll
@@ -144,27 +80,17 @@ __global__ __launch_bounds__(1024) void smk_k_step_hist(const StepHistParams P) 
         col[j] = coln[j];
       }
     }
-    __syncthreads();
-    for (int w = threadIdx.x; w < 32768; w += 1024) {
-      const unsigned v = h16[w];
-      if (v & 0xffffu) atomicAdd(&P.bins[2 * w], v & 0xffffu);
-      if (v >> 16) atomicAdd(&P.bins[2 * w + 1], v >> 16);
-    }
-    __syncthreads();
+    hist_lds_flush(h16, P.bins);
   }
 }
 
 template <int L>
 hipError_t launch_step_hist(const StepHistParams &P, int device, hipStream_t s) {
   static bool attr[64] = {};  // per device
-  if (device < 0 || device >= 64 || !attr[device]) {
-    const hipError_t e = hipFuncSetAttribute((const void *)smk_k_step_hist<L>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    if (e != hipSuccess) return e;
-    if (device >= 0 && device < 64) attr[device] = true;
-  }
-  const unsigned long long ch = L == SH_F32 ? SH_CHUNK : SH_CHUNK / 2, nchunks = (P.units + ch - 1) / ch;
+  if (const hipError_t e = hist_lds_allow((const void *)smk_k_step_hist<L>, device, attr); e != hipSuccess) return e;
+  const unsigned long long ch = L == SMK_F32 ? HIST_CHUNK : HIST_CHUNK / 2, nchunks = (P.R.units + ch - 1) / ch;
   const unsigned blocks = (unsigned)std::min<unsigned long long>(nchunks, 256);  // one workgroup per CU is resident (its LDS): they stride
-  hipLaunchKernelGGL(smk_k_step_hist<L>, dim3(blocks), dim3(1024), 128 * 1024, s, P);
+  hipLaunchKernelGGL(smk_k_step_hist<L>, dim3(blocks), dim3(1024), HIST_LDS_BYTES, s, P);
   return hipGetLastError();
 }
 
@@ -201,21 +127,17 @@ __global__ __launch_bounds__(256) void smk_k_step_probe(const StepProbeParams P)
     if (P.dtype == SMK_F32) {
       const uint4 v = ((const uint4 *)P.vox)[o];
       r[0] = v.x; r[1] = v.y; r[2] = v.z;
-      if (P.nelts == 4) {
-        r[3] = v.w;
-        nb = P.nrm ? P.nrm[o] & 0xffffffu : 0x808080u;
-      } else {
-        nb = v.w & 0xffffffu;
-      }
+      if (P.nelts == 4) r[3] = v.w;
+      nb = smk_nrm_bits(smk_f32_nrm_word(v, P.nelts, P.nrm ? P.nrm[o] : SMK_NRM_NONE));
     } else {
       const uint2 v = ((const uint2 *)P.vox)[o];
-      nb = v.y & 0xffffffu;
+      nb = smk_nrm_bits(v.y);
       if (P.dtype == SMK_U8) {
-        for (int e = 0; e < 4; ++e) r[e] = __float_as_uint((float)((v.x >> (8 * e)) & 255u));
+        for (int e = 0; e < 4; ++e) r[e] = __float_as_uint((float)smk_u8_ch(v.x, e));
       } else {
-        r[0] = __float_as_uint((float)(v.x & 65535u));
-        r[1] = __float_as_uint((float)(v.x >> 16));
-        r[2] = __float_as_uint((float)(v.y >> 24));
+        r[0] = __float_as_uint((float)smk_vox8_c0<SMK_U16>(v.x));
+        r[1] = __float_as_uint((float)smk_vox8_c1<SMK_U16>(v.x));
+        r[2] = __float_as_uint((float)smk_u16_q2(v.y));
         r[3] = __float_as_uint(0.f);
       }
     }
@@ -225,45 +147,24 @@ __global__ __launch_bounds__(256) void smk_k_step_probe(const StepProbeParams P)
   if (corner == 0) P.ok[cell] = ok ? 1 : 0;
 }
 
-// the slot of `timestep` for entry `who`, with the refusals every entry here shares
-int step_slot(smk_ctx *c, const char *who, int timestep, int *k) {
-  if (!c->have_volume) FAIL(c, "%s: no volume uploaded", who);
-  *k = smk_step_slot(c, timestep);
-  if (*k < 0) FAIL(c, "%s: time step %d is not cached (upload it with smk_upload_timestep)", who, timestep);
-  return 0;
-}
-
 int hist_enqueue(smk_ctx *c, const char *who, int timestep, void *d_counts, hipStream_t s) {
   int k = -1;
   if (step_slot(c, who, timestep, &k)) return 1;
   if (c->nelts < 2) FAIL(c, "%s: sorry this type of histogram is not implemented (needs value and gradient channels)", who);
   if (!d_counts) FAIL(c, "%s: d_counts is NULL", who);
   TimeStep &T = c->ts[(size_t)k];
-  const bool wide = c->dtype == SMK_F32;  // a unit is one voxel
-  const unsigned nx = (unsigned)(c->g1[0] - c->g0[0]), ox = (unsigned)(c->g0[0] - c->O[0]);
   StepHistParams P;
   P.vox = (const uint4 *)T.vox;
   P.bins = (unsigned *)d_counts;
-  P.head = wide ? 0 : ox & 1;
-  P.tail = wide ? 0 : (ox + nx) & 1;
-  P.upr = wide ? nx : (P.head + nx + 1) / 2;
-  P.ny = (unsigned)(c->g1[1] - c->g0[1]);
-  P.units = (unsigned long long)P.upr * P.ny * (unsigned long long)(c->g1[2] - c->g0[2]);
-  P.pitch = wide ? (unsigned long long)c->D[0] : (unsigned long long)c->D[0] / 2;
-  P.D1 = (unsigned)c->D[1];
-  P.ox = wide ? ox : ox / 2;
-  P.oy = (unsigned)(c->g0[1] - c->O[1]);
-  P.oz = (unsigned)(c->g0[2] - c->O[2]);
-  if (!P.units) FAIL(c, "%s: this context's region is empty", who);
-  P.by_upr = step_div(P.upr);
-  P.by_ny = step_div(P.ny);
-  if ((unsigned long long)P.upr + SH_CHUNK > 0xffffffffull) FAIL(c, "%s: rows of %u voxels are too long", who, nx);
+  P.R = smk_step_rows(c);
+  if (!P.R.units) FAIL(c, "%s: this context's region is empty", who);
+  if ((unsigned long long)P.R.upr + HIST_CHUNK > 0xffffffffull) FAIL(c, "%s: rows of %u voxels are too long", who, P.R.nx);
   // behind the step's upload or blend; what overwrites the slot later waits for this read (smk_timesteps.hip)
   if (smk_step_read_begin(c, k, s)) return 1;
   HIPCHK(c, hipMemsetAsync(d_counts, 0, 65536 * sizeof(unsigned), s));
-  if (c->dtype == SMK_U8) HIPCHK(c, launch_step_hist<SH_U8>(P, c->device, s));
-  else if (c->dtype == SMK_U16) HIPCHK(c, launch_step_hist<SH_U16>(P, c->device, s));
-  else HIPCHK(c, launch_step_hist<SH_F32>(P, c->device, s));
+  if (c->dtype == SMK_U8) HIPCHK(c, launch_step_hist<SMK_U8>(P, c->device, s));
+  else if (c->dtype == SMK_U16) HIPCHK(c, launch_step_hist<SMK_U16>(P, c->device, s));
+  else HIPCHK(c, launch_step_hist<SMK_F32>(P, c->device, s));
   return smk_step_read_end(c, k, s);
 }
 
@@ -318,7 +219,7 @@ extern "C" int smk_probe_step(smk_ctx *c, int timestep, const int *cells, int n,
   HIPCHK(c, hipMalloc((void **)&d, o_ok + b_ok));
   StepProbeParams P;
   P.vox = T.vox;
-  P.nrm = c->dtype == SMK_F32 && c->nelts == 4 && c->have_normals ? T.nrm : nullptr;
+  P.nrm = smk_step_separate_normals(c) ? T.nrm : nullptr;
   for (int a = 0; a < 3; ++a) {
     P.N[a] = c->N[a];
     P.O[a] = c->O[a];

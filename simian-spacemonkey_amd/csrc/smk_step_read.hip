@@ -6,10 +6,7 @@
 // step that came from a device buffer, a blended step and a shard's region have neither: what the context owns is the slot's
 // packed voxels (TimeStep::vox, and TimeStep::nrm for four-channel f32), so these entries read those.
 //
-// Reads are smk_step_hist.hip's: the region [g0, g1) is ny * nz rows, each a run of nx voxels that starts g0 - O into the
-// stored box, read in whole 16-byte units (one f32 voxel, or two 8-byte voxels: the run widened to even voxel offsets, the
-// first unit's low and the last unit's high voxel masked; D[0] is even there, so nothing is read outside the stored box).
-//
+// Reads: the region's rows in whole 16-byte units (smk_packed.h, with the packed layouts and the stored box).
 // Writes.  The output is dense, so the region's voxels in row order ARE the output in address order: a chunk of consecutive
 // units is one run of output bytes, which starts and ends on any byte (9 voxels x 3 bytes are a 27-byte row).  A workgroup
 // puts its chunk's bytes into LDS at the phase the run has in its 16-byte line of the OUTPUT, then writes whole lines as
@@ -20,78 +17,37 @@
 
 namespace {
 
-enum { SR_U8 = 0, SR_F32 = 1, SR_U16 = 2 };  // smk_dtype's values: the packed layout of an instance
-
 constexpr int SR_PER = 4;                          // units a lane loads per chunk
 constexpr unsigned SR_LANES = 256;
 constexpr unsigned SR_CHUNK = SR_LANES * SR_PER;   // units per chunk: a wave's load instruction covers 1 KiB
 constexpr unsigned SR_MAX_BLOCKS = 2048;           // 8 workgroups for each of 256 CUs: they stride over the chunks
 
-// smk_step_hist.hip's exact division (Granlund and Montgomery 1994, figure 4.1): floor(n / d) for every n < 2^32, d >= 1
-struct StepDiv {
-  unsigned m, sh1, sh2;
-};
-
-StepDiv step_div(unsigned d) {
-  unsigned l = 0;
-  while ((1ull << l) < d) ++l;  // ceil(log2 d)
-  StepDiv k;
-  k.m = (unsigned)((((1ull << l) - d) << 32) / d + 1);
-  k.sh1 = l < 1 ? l : 1;
-  k.sh2 = l > 1 ? l - 1 : 0;
-  return k;
-}
-
-__device__ __forceinline__ unsigned sr_div(unsigned n, const StepDiv k) {
-  const unsigned t = __umulhi(k.m, n);
-  return (t + ((n - t) >> k.sh1)) >> k.sh2;
-}
-
 struct StepReadParams {
-  const uint4 *vox;            // the slot's packed voxels
-  const uint32_t *nrm;         // the separate normals of four-channel f32, or null
-  unsigned char *data;         // [nvox][nelts] elements of the step's type
-  unsigned char *grad;         // [nvox][3] bytes, or null
-  unsigned long long units;    // rows * upr
-  unsigned long long nvox;     // voxels of the region
-  unsigned upr;                // 16-byte units per row
-  unsigned nx, ny;             // voxels per row, rows per z
-  unsigned long long pitch;    // units per stored row: D[0], or D[0] / 2
-  unsigned D1;                 // stored rows per z
-  unsigned ox, oy, oz;         // the first unit's offset in its stored row; g0 - O in y and z
-  unsigned head, tail;         // 8-byte layouts: the first unit's low / the last unit's high voxel lies outside the run
+  const uint4 *vox;     // the slot's packed voxels
+  const uint32_t *nrm;  // the separate normals of four-channel f32, or null
+  unsigned char *data;  // [nvox][nelts] elements of the step's type
+  unsigned char *grad;  // [nvox][3] bytes, or null
+  StepRows R;
   unsigned nelts;
-  StepDiv by_upr, by_ny;
 };
 
-// a chunk of consecutive units of the region's rows: its first unit's column, row and slice, its length, and the output
-// voxel its first unit starts (the end of the output for a chunk past the last)
+// a chunk of consecutive units of the region's rows: where it starts, its length (0 past the last chunk), the first voxel x0
+// of the run it starts in its row, and the output voxel that is (the end of the output for a chunk past the last)
 struct SrChunk {
-  unsigned u0, y0, lim, x0;
-  unsigned long long z0, v0;
+  StepOrigin o;
+  unsigned lim, x0;
+  unsigned long long v0;
 };
 
 template <int L>
 __device__ __forceinline__ SrChunk sr_chunk(const StepReadParams &P, unsigned long long chunk) {
-  SrChunk C;
   const unsigned long long base = chunk * SR_CHUNK;
-  C.u0 = C.y0 = C.lim = C.x0 = 0;
-  C.z0 = 0;
-  C.v0 = P.nvox;
-  if (base >= P.units) return C;
-  C.lim = P.units - base < SR_CHUNK ? (unsigned)(P.units - base) : SR_CHUNK;
-  unsigned long long row0;
-  if (P.units <= 0xffffffffull) {  // (every step that fits a device but the very largest: no 64-bit division)
-    row0 = sr_div((unsigned)base, P.by_upr);
-    C.z0 = sr_div((unsigned)row0, P.by_ny);
-  } else {
-    row0 = base / P.upr;
-    C.z0 = row0 / P.ny;
-  }
-  C.u0 = (unsigned)(base - row0 * P.upr);
-  C.y0 = (unsigned)(row0 - C.z0 * P.ny);
-  C.x0 = L == SR_F32 ? C.u0 : (C.u0 ? 2 * C.u0 - P.head : 0);  // the first voxel of the run the chunk starts in its row
-  C.v0 = row0 * P.nx + C.x0;
+  SrChunk C = {{0, 0, 0, 0}, 0, 0, P.R.nvox};
+  if (base >= P.R.units) return C;
+  C.lim = P.R.units - base < SR_CHUNK ? (unsigned)(P.R.units - base) : SR_CHUNK;
+  C.o = step_chunk_origin(P.R, base);
+  C.x0 = L == SMK_F32 ? C.o.u0 : (C.o.u0 ? 2 * C.o.u0 - P.R.head : 0);
+  C.v0 = C.o.row0 * P.R.nx + C.x0;
   return C;
 }
 
@@ -104,20 +60,18 @@ __device__ __forceinline__ void sr_load(const StepReadParams &P, const SrChunk &
   for (int j = 0; j < SR_PER; ++j) {
     const unsigned i = (unsigned)j * SR_LANES + threadIdx.x;
     x[j] = make_uint4(0, 0, 0, 0);
-    n[j] = 0x00808080u;
+    n[j] = SMK_NRM_NONE;
     col[j] = 0;
     lv[j] = 0;
     if (i < C.lim) {
-      const unsigned t = C.u0 + i, q = sr_div(t, P.by_upr), ry = C.y0 + q, zq = sr_div(ry, P.by_ny);
-      col[j] = t - q * P.upr;
-      const unsigned long long z = C.z0 + zq + P.oz, y = (unsigned long long)(ry - zq * P.ny) + P.oy;
-      const unsigned long long o = (z * P.D1 + y) * P.pitch + P.ox + col[j];
+      unsigned q;
+      const unsigned long long o = step_unit(P.R, C.o, i, col[j], q);
       x[j] = P.vox[o];
-      if (L == SR_F32) {
+      if (L == SMK_F32) {
         if (P.nrm) n[j] = P.nrm[o];  // (a unit is a voxel: the same index)
-        lv[j] = (int)(q * P.nx + col[j] - C.x0);
+        lv[j] = (int)(q * P.R.nx + col[j] - C.x0);
       } else {
-        lv[j] = (int)(q * P.nx + 2 * col[j] - C.x0) - (int)P.head;
+        lv[j] = (int)(q * P.R.nx + 2 * col[j] - C.x0) - (int)P.R.head;
       }
     }
   }
@@ -130,21 +84,17 @@ typedef uint4 __attribute__((may_alias)) sr_u128;
 // one 8-byte voxel {w0, w1} into the staged run: its channels at d, its three normal bytes at g (null: none wanted)
 template <int L>
 __device__ __forceinline__ void sr_put8(unsigned char *d, unsigned char *g, uint32_t w0, uint32_t w1, unsigned nelts) {
-  if (L == SR_U8) {
+  if (L == SMK_U8) {
 #pragma unroll
     for (unsigned e = 0; e < 4; ++e)
-      if (e < nelts) d[e] = (unsigned char)(w0 >> (8 * e));
+      if (e < nelts) d[e] = (unsigned char)smk_u8_ch(w0, (int)e);
   } else {
     sr_u16 *h = (sr_u16 *)d;  // (the run's phase is even: d_data has the element's alignment)
-    h[0] = (unsigned short)(w0 & 0xffffu);
-    if (nelts > 1) h[1] = (unsigned short)(w0 >> 16);
-    if (nelts > 2) h[2] = (unsigned short)(257u * (w1 >> 24));  // the stored 8-bit field q as the 16-bit value 257 q
+    h[0] = (unsigned short)smk_vox8_c0<SMK_U16>(w0);
+    if (nelts > 1) h[1] = (unsigned short)smk_vox8_c1<SMK_U16>(w0);
+    if (nelts > 2) h[2] = (unsigned short)smk_q8_expand(smk_u16_q2(w1));  // the stored 8-bit field q as the 16-bit value 257 q
   }
-  if (g) {
-    g[0] = (unsigned char)w1;
-    g[1] = (unsigned char)(w1 >> 8);
-    g[2] = (unsigned char)(w1 >> 16);
-  }
+  if (g) smk_nrm_bytes(w1, g);
 }
 
 // the staged run lds[ph, ph + nb) to out[0, nb): LDS byte k is output byte k - ph, and out - ph is 16-byte aligned, so
@@ -166,8 +116,8 @@ __device__ __forceinline__ void sr_flush(unsigned char *out, const unsigned char
 // voxels a chunk can hold, and the bytes of its two staged runs (+ 16: the run's phase in its first line)
 template <int L>
 struct SrLds {
-  static constexpr unsigned VOX = L == SR_F32 ? SR_CHUNK : 2 * SR_CHUNK;
-  static constexpr unsigned DATA = VOX * (L == SR_F32 ? 16 : L == SR_U16 ? 6 : 4) + 16;
+  static constexpr unsigned VOX = L == SMK_F32 ? SR_CHUNK : 2 * SR_CHUNK;
+  static constexpr unsigned DATA = VOX * (L == SMK_U16 ? 3 : 4) * (unsigned)smk_elem_bytes(L) + 16;  // (u16 has up to 3 channels)
   static constexpr unsigned GRAD = VOX * 3 + 16;
 };
 
@@ -177,8 +127,8 @@ template <int L>
 __global__ __launch_bounds__(256) void smk_k_unpack_step(const StepReadParams P) {
   __shared__ uint4 s_data[SrLds<L>::DATA / 16], s_grad[SrLds<L>::GRAD / 16];
   unsigned char *sd = (unsigned char *)s_data, *sg = (unsigned char *)s_grad;
-  const unsigned vb = P.nelts * (L == SR_U8 ? 1u : L == SR_U16 ? 2u : 4u);  // bytes of an output voxel
-  const unsigned long long nchunks = (P.units + SR_CHUNK - 1) / SR_CHUNK;
+  const unsigned vb = P.nelts * (unsigned)smk_elem_bytes(L);  // bytes of an output voxel
+  const unsigned long long nchunks = (P.R.units + SR_CHUNK - 1) / SR_CHUNK;
   unsigned long long chunk = blockIdx.x;
   if (chunk >= nchunks) return;
   SrChunk C = sr_chunk<L>(P, chunk);
@@ -197,23 +147,19 @@ __global__ __launch_bounds__(256) void smk_k_unpack_step(const StepReadParams P)
 #pragma unroll
     for (int j = 0; j < SR_PER; ++j) {
       if ((unsigned)j * SR_LANES + threadIdx.x >= C.lim) continue;
-      if (L == SR_F32) {
+      if (L == SMK_F32) {
         sr_u32 *d = (sr_u32 *)(sd + phd + (unsigned)lv[j] * vb);  // (phd is a multiple of 4: d_data is float-aligned)
         d[0] = x[j].x;
         if (P.nelts > 1) d[1] = x[j].y;
         if (P.nelts > 2) d[2] = x[j].z;
         if (P.nelts > 3) d[3] = x[j].w;
         if (og) {
-          const uint32_t w = P.nelts > 3 ? n[j] : x[j].w;
-          unsigned char *g = sg + phg + (unsigned)lv[j] * 3;
-          g[0] = (unsigned char)w;
-          g[1] = (unsigned char)(w >> 8);
-          g[2] = (unsigned char)(w >> 16);
+          smk_nrm_bytes(smk_f32_nrm_word(x[j], (int)P.nelts, n[j]), sg + phg + (unsigned)lv[j] * 3);
         }
       } else {
-        if (!(P.head && col[j] == 0))
+        if (!step_low_masked(P.R, col[j]))
           sr_put8<L>(sd + phd + (unsigned)lv[j] * vb, og ? sg + phg + (unsigned)lv[j] * 3 : nullptr, x[j].x, x[j].y, P.nelts);
-        if (!(P.tail && col[j] == P.upr - 1))
+        if (!step_high_masked(P.R, col[j]))
           sr_put8<L>(sd + phd + (unsigned)(lv[j] + 1) * vb, og ? sg + phg + (unsigned)(lv[j] + 1) * 3 : nullptr, x[j].z, x[j].w, P.nelts);
       }
     }
@@ -234,53 +180,29 @@ __global__ __launch_bounds__(256) void smk_k_unpack_step(const StepReadParams P)
 
 template <int L>
 hipError_t launch_unpack(const StepReadParams &P, hipStream_t s) {
-  const unsigned long long nchunks = (P.units + SR_CHUNK - 1) / SR_CHUNK;
+  const unsigned long long nchunks = (P.R.units + SR_CHUNK - 1) / SR_CHUNK;
   const unsigned blocks = (unsigned)std::min<unsigned long long>(nchunks, SR_MAX_BLOCKS);
   hipLaunchKernelGGL(smk_k_unpack_step<L>, dim3(blocks), dim3(SR_LANES), 0, s, P);
   return hipGetLastError();
 }
 
-size_t elem_bytes(const smk_ctx *c) { return c->dtype == SMK_U8 ? 1 : c->dtype == SMK_U16 ? 2 : 4; }
-
-// the slot of `timestep` for entry `who`, with the refusals the step histogram's entries make
-int step_slot(smk_ctx *c, const char *who, int timestep, int *k) {
-  if (!c->have_volume) FAIL(c, "%s: no volume uploaded", who);
-  *k = smk_step_slot(c, timestep);
-  if (*k < 0) FAIL(c, "%s: time step %d is not cached (upload it with smk_upload_timestep)", who, timestep);
-  return 0;
-}
-
 int read_enqueue(smk_ctx *c, const char *who, int k, void *d_data, void *d_grad, hipStream_t s) {
   TimeStep &T = c->ts[(size_t)k];
-  const bool wide = c->dtype == SMK_F32;  // a unit is one voxel
-  const unsigned nx = (unsigned)(c->g1[0] - c->g0[0]), ox = (unsigned)(c->g0[0] - c->O[0]);
-  if ((uintptr_t)d_data % elem_bytes(c)) FAIL(c, "%s: d_data is not aligned to its %zu-byte elements", who, elem_bytes(c));
+  const size_t eb = smk_elem_bytes(c->dtype);
+  if ((uintptr_t)d_data % eb) FAIL(c, "%s: d_data is not aligned to its %zu-byte elements", who, eb);
   StepReadParams P;
   P.vox = (const uint4 *)T.vox;
-  P.nrm = wide && c->nelts == 4 && c->have_normals ? T.nrm : nullptr;
+  P.nrm = smk_step_separate_normals(c) ? T.nrm : nullptr;
   P.data = (unsigned char *)d_data;
   P.grad = (unsigned char *)d_grad;
-  P.head = wide ? 0 : ox & 1;
-  P.tail = wide ? 0 : (ox + nx) & 1;
-  P.upr = wide ? nx : (P.head + nx + 1) / 2;
-  P.nx = nx;
-  P.ny = (unsigned)(c->g1[1] - c->g0[1]);
-  P.units = (unsigned long long)P.upr * P.ny * (unsigned long long)(c->g1[2] - c->g0[2]);
-  P.nvox = (unsigned long long)nx * P.ny * (unsigned long long)(c->g1[2] - c->g0[2]);
-  P.pitch = wide ? (unsigned long long)c->D[0] : (unsigned long long)c->D[0] / 2;
-  P.D1 = (unsigned)c->D[1];
-  P.ox = wide ? ox : ox / 2;
-  P.oy = (unsigned)(c->g0[1] - c->O[1]);
-  P.oz = (unsigned)(c->g0[2] - c->O[2]);
+  P.R = smk_step_rows(c);
   P.nelts = (unsigned)c->nelts;
-  if (!P.units) FAIL(c, "%s: this context's region is empty", who);
-  P.by_upr = step_div(P.upr);
-  P.by_ny = step_div(P.ny);
+  if (!P.R.units) FAIL(c, "%s: this context's region is empty", who);
   // behind the step's upload or blend; what overwrites the slot later waits for this read (smk_timesteps.hip)
   if (smk_step_read_begin(c, k, s)) return 1;
-  if (c->dtype == SMK_U8) HIPCHK(c, launch_unpack<SR_U8>(P, s));
-  else if (c->dtype == SMK_U16) HIPCHK(c, launch_unpack<SR_U16>(P, s));
-  else HIPCHK(c, launch_unpack<SR_F32>(P, s));
+  if (c->dtype == SMK_U8) HIPCHK(c, launch_unpack<SMK_U8>(P, s));
+  else if (c->dtype == SMK_U16) HIPCHK(c, launch_unpack<SMK_U16>(P, s));
+  else HIPCHK(c, launch_unpack<SMK_F32>(P, s));
   return smk_step_read_end(c, k, s);
 }
 
@@ -318,7 +240,7 @@ extern "C" int smk_download_timestep(smk_ctx *c, int timestep, void *data, unsig
   if (!data) FAIL(c, "%s: data is NULL", who);
   // one staging buffer of the box's size: the voxels, then (from a 16-byte boundary) the normals
   const size_t nvox = (size_t)(c->g1[0] - c->g0[0]) * (size_t)(c->g1[1] - c->g0[1]) * (size_t)(c->g1[2] - c->g0[2]);
-  const size_t b_data = nvox * (size_t)c->nelts * elem_bytes(c), b_grad = grad ? nvox * 3 : 0, o_grad = (b_data + 15) / 16 * 16;
+  const size_t b_data = nvox * (size_t)c->nelts * smk_elem_bytes(c->dtype), b_grad = grad ? nvox * 3 : 0, o_grad = (b_data + 15) / 16 * 16;
   const size_t need = o_grad + b_grad;
   if (!need) FAIL(c, "%s: this context's region is empty", who);
   size_t fr = 0, tot = 0;

@@ -11,11 +11,10 @@
 //   - smk_upload_timestep_device enqueues the pack and the brick summaries on the caller's stream and records the slot's
 //     `ready` event there; every stream that reads the step (a frame's, the table refresh's) waits for it;
 //   - every frame records the slot's `used` event on its stream; an upload into the slot waits for it first;
-//   - smk_blend_timesteps (fractional time, below) is an upload whose source is two other slots: it waits for their `ready`
-//     events and records their `blended` events behind its kernels; whatever overwrites a slot waits for that one too;
-//   - the histogram and the probe of a step (smk_step_hist.hip) read a slot the same way: smk_step_read_begin / _end;
-//   - smk_derive_timestep (smk_step_derive.hip) reads its source that way and writes its output as a blend does:
-//     smk_step_write_begin / _end.
+//   - a kernel that reads a slot and is no frame's (a blend's and a derive's sources, the histogram, the probe, the read-back)
+//     waits for the slot's `ready` event and records its `blended` event behind itself: smk_step_read_begin / _end; whatever
+//     overwrites a slot waits for that one too;
+//   - a blend and a derive write their output slot as an upload does: smk_step_write_begin / _end.
 #include <math.h>
 #include <string.h>
 
@@ -100,10 +99,9 @@ int smk_step_slot(const smk_ctx *c, int timestep) {
   return timestep < 0 ? -1 : find_step(c, timestep);
 }
 
-// A kernel on stream s that READS slot k and is not a frame (the step histogram and probe, smk_step_hist.hip), ordered as
-// smk_blend_timesteps orders the reads of its sources: behind the step's upload or blend -- the event stays pending for the
-// frames -- and behind the reader before it, whose `blended` event is recorded again behind this one's kernels, so that
-// whatever overwrites the slot waits for every read.
+// A kernel on stream s that READS slot k and is not a frame: behind the step's upload or blend -- the event stays pending for
+// the frames -- and behind the reader before it, on whatever stream, whose `blended` event is recorded again behind this one's
+// kernels, so that whatever overwrites the slot waits for every read.
 int smk_step_read_begin(smk_ctx *c, int k, hipStream_t s) {
   TimeStep &T = c->ts[(size_t)k];
   if (T.ready_pending) HIPCHK(c, hipStreamWaitEvent(s, T.ready, 0));
@@ -119,10 +117,15 @@ int smk_step_read_end(smk_ctx *c, int k, hipStream_t s) {
   return 0;
 }
 
+int step_slot(smk_ctx *c, const char *who, int timestep, int *k) {
+  if (!c->have_volume) FAIL(c, "%s: no volume uploaded", who);
+  *k = smk_step_slot(c, timestep);
+  if (*k < 0) FAIL(c, "%s: time step %d is not cached (upload it with smk_upload_timestep)", who, timestep);
+  return 0;
+}
+
 static size_t bytes_per_step(const smk_ctx *c) {
-  const size_t nst = (size_t)c->D[0] * c->D[1] * c->D[2];
-  const size_t nrm = c->dtype == SMK_F32 && c->nelts == 4 && c->have_normals ? nst * 4 : 0;
-  return c->vox_bytes + 16 + nrm + (size_t)c->nbr[0] * c->nbr[1] * c->nbr[2] * sizeof(float4);
+  return c->vox_bytes + 16 + smk_step_nrm_bytes(c) + (size_t)c->nbr[0] * c->nbr[1] * c->nbr[2] * sizeof(float4);
 }
 
 extern "C" int smk_set_timestep_cache(smk_ctx *c, int nsteps) {
@@ -269,10 +272,9 @@ int smk_step_write_begin(smk_ctx *c, int k, hipStream_t s) {
     T.ready_pending = false;
   }
   T.id = -1;  // (until it holds the new step)
-  const size_t nst = (size_t)c->D[0] * c->D[1] * c->D[2];
   SmkVolGeom g;  // the series' buffers (the writer fills the pad column of a padded box itself: a blend with 0 blended with 0)
   g.vox_bytes = c->vox_bytes;
-  g.nrm_bytes = c->dtype == SMK_F32 && c->nelts == 4 && c->have_normals ? nst * 4 : 0;
+  g.nrm_bytes = smk_step_nrm_bytes(c);
   g.mm_bytes = (size_t)c->nbr[0] * c->nbr[1] * c->nbr[2] * sizeof(float4);
   return smk_alloc_step(c, g, T);
 }
@@ -333,11 +335,10 @@ extern "C" int smk_get_timesteps(smk_ctx *c, int *current, int *ids_out, int cap
 
 namespace {
 
-// what the four words of a 16-byte unit hold
-enum { TB_BYTES = 0,  // u8 voxels (two per unit: channel bytes, normal bytes), and the separate normals buffer
-       TB_F32N = 1,   // an f32 voxel of up to three channels: three floats, the normal bytes in .w
-       TB_U16 = 2,    // u16 voxels (two per unit): channels 0 and 1 as 16-bit values, then normal + third-channel bytes
-       TB_F32C = 3 }; // a four-channel f32 voxel: four floats
+// What the four words of a 16-byte unit hold (smk_packed.h): FORM is the voxels' smk_dtype -- SMK_U8, all bytes, is also the
+// form of the separate normals buffer; SMK_U16 is two 16-bit channels, then bytes -- with f32 split by what .w holds:
+enum { TB_F32N = SMK_F32,  // an f32 voxel of up to three channels: three floats, the normal bytes in .w
+       TB_F32C = 3 };      // a four-channel f32 voxel: four floats
 
 __device__ __forceinline__ uint32_t tb_int(uint32_t x, uint32_t y, float u, float w, int top) {
   const float r = (u * (float)x) + (w * (float)y);
@@ -362,9 +363,9 @@ __device__ __forceinline__ uint32_t tb_float(uint32_t x, uint32_t y, float u, fl
 template <int FORM>
 __device__ __forceinline__ uint4 tb_unit(const uint4 x, const uint4 y, float u, float w) {
   uint4 o;
-  if (FORM == TB_BYTES) {
+  if (FORM == SMK_U8) {
     o.x = tb_bytes(x.x, y.x, u, w); o.y = tb_bytes(x.y, y.y, u, w); o.z = tb_bytes(x.z, y.z, u, w); o.w = tb_bytes(x.w, y.w, u, w);
-  } else if (FORM == TB_U16) {
+  } else if (FORM == SMK_U16) {
     o.x = tb_shorts(x.x, y.x, u, w); o.y = tb_bytes(x.y, y.y, u, w); o.z = tb_shorts(x.z, y.z, u, w); o.w = tb_bytes(x.w, y.w, u, w);
   } else {
     o.x = tb_float(x.x, y.x, u, w); o.y = tb_float(x.y, y.y, u, w); o.z = tb_float(x.z, y.z, u, w);
@@ -439,28 +440,22 @@ extern "C" int smk_blend_timesteps(smk_ctx *c, int step_a, int step_b, float w, 
             "(here %d); smk_set_timestep_cache sets more", who, (int)c->ts.size(), c->ts_cur_id, need);
   TimeStep &A = c->ts[(size_t)ka], &B = c->ts[(size_t)kb], &T = c->ts[(size_t)k];
   const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-  // the sources: their uploads (or blends) come first -- the events stay pending for the frames that read the steps -- and so
-  // does the blend that read them last, on whatever stream: its event is recorded again below, behind this one's kernels
-  for (TimeStep *S : {&A, &B}) {
-    if (S->ready_pending) HIPCHK(c, hipStreamWaitEvent(s, S->ready, 0));
-    if (S->blended_valid) HIPCHK(c, hipStreamWaitEvent(s, S->blended, 0));
-  }
+  // the sources: behind their uploads (or blends) and their last reader; their `blended` events are recorded again below
+  if (smk_step_read_begin(c, ka, s) || smk_step_read_begin(c, kb, s)) return 1;
   // the output slot's old contents: the frames and the blends that read them, and an upload still writing them; its buffers
   if (smk_step_write_begin(c, k, s)) return 1;
   const size_t nst = (size_t)c->D[0] * c->D[1] * c->D[2];
-  const size_t nrm_bytes = c->dtype == SMK_F32 && c->nelts == 4 && c->have_normals ? nst * 4 : 0;
-  // The stored box -- region + halo, D[0] D[1] D[2] voxels -- in 16-byte units: one f32 voxel, or two 8-byte voxels (D[0] is
-  // even for those types, smk_volume_geometry, so their number is even).  The 16 bytes behind the box are not touched.
+  // the stored box in 16-byte units (a whole number of them: smk_packed.h); the 16 bytes behind the box are not touched
   const float u = 1.0f - w;
   const size_t units = c->vox_bytes / 16;
-  if (c->dtype == SMK_U8) HIPCHK(c, launch_blend<TB_BYTES>(A.vox, B.vox, T.vox, units, u, w, s));
-  else if (c->dtype == SMK_U16) HIPCHK(c, launch_blend<TB_U16>(A.vox, B.vox, T.vox, units, u, w, s));
+  if (c->dtype == SMK_U8) HIPCHK(c, launch_blend<SMK_U8>(A.vox, B.vox, T.vox, units, u, w, s));
+  else if (c->dtype == SMK_U16) HIPCHK(c, launch_blend<SMK_U16>(A.vox, B.vox, T.vox, units, u, w, s));
   else if (c->nelts <= 3) HIPCHK(c, launch_blend<TB_F32N>(A.vox, B.vox, T.vox, units, u, w, s));
   else HIPCHK(c, launch_blend<TB_F32C>(A.vox, B.vox, T.vox, units, u, w, s));
-  if (nrm_bytes) {
+  if (smk_step_nrm_bytes(c)) {
     // the separate normals of four-channel f32, a word per voxel, in the byte form: the whole units, then the words that
     // are left when the voxel count (odd sizes are allowed for f32) is no multiple of four
-    HIPCHK(c, launch_blend<TB_BYTES>(A.nrm, B.nrm, T.nrm, nst / 4, u, w, s));
+    HIPCHK(c, launch_blend<SMK_U8>(A.nrm, B.nrm, T.nrm, nst / 4, u, w, s));
     if (nst % 4) {
       const size_t done = nst / 4 * 4;
       hipLaunchKernelGGL(smk_k_blend_words, dim3(1), dim3(64), 0, s, A.nrm + done, B.nrm + done, T.nrm + done, (int)(nst % 4), u, w);
@@ -469,11 +464,7 @@ extern "C" int smk_blend_timesteps(smk_ctx *c, int step_a, int step_b, float w, 
   }
   HIPCHK(c, smk_bricks_minmax(T.vox, c->dtype, c->D, c->nbr, T.mm, s));
   if (smk_step_write_end(c, k, step_out, s)) return 1;  // (the output's `ready`; the current step overwritten in place)
-  for (TimeStep *S : {&A, &B}) {  // whatever overwrites a source slot comes after these reads
-    if (!S->blended) HIPCHK(c, hipEventCreateWithFlags(&S->blended, hipEventDisableTiming));
-    HIPCHK(c, hipEventRecord(S->blended, s));
-    S->blended_valid = true;
-  }
+  if (smk_step_read_end(c, ka, s) || smk_step_read_end(c, kb, s)) return 1;  // whatever overwrites a source slot comes after these reads
   ++c->tblend_count;
   return 0;
 }
