@@ -179,6 +179,41 @@ int smk_derive_timestep(smk_ctx *ctx, int step_src, int step_out, int compat, in
  * the three; sizes that are not the series'. */
 int smk_upload_timestep_scalar_device(smk_ctx *ctx, int timestep, const void *d_scalar, smk_dtype scalar_dtype, int sx, int sy,
                                       int sz, int compat, int blur, void *stream);
+/* Merged fields of a step (MetaVolume::mergeMV with addG, MetaVolume.cpp:1109-1268, which the host runs before the renderer
+ * starts: the data modes SMK_GDM_V1G, _V2G, _V3G).  With nf = nelts - 1, step `step_out` becomes the multi-field step of the
+ * first nf stored channels of the cached step `step_src`: its stored fields are exactly those that smk_upload_timestep_device
+ * packs from what the existing merge entries make of the fields, bit for bit:
+ *   ring SMK_U8 : smk_merge_fields_device(fields, nf).  Channels 0..nf-1 are the fields' bytes; channel nf is GMag's byte,
+ *                 (uchar)(mag / max * 255.0) with a float quotient and a double product, 0 where the cast is out of range or
+ *                 the quotient is NaN (everywhere when the maximum is 0); the normals are that entry's.
+ *   ring SMK_F32: smk_merge_fields_f32_device(fields, nf).  The fields travel as raw words, NaN payloads and -0 included;
+ *                 channel nf is mag / maxm, 0 where mag is not finite or maxm is 0; maxm is taken over finite magnitudes only;
+ *                 a non-finite gradient gives the normal (128, 128, 128).  With nelts == 4 the normals go to the slot's
+ *                 separate normals buffer.
+ *   ring SMK_U16: (no merge entry exists for u16; this defines the result.)  The fields keep their stored 16-bit values.  With
+ *                 F = (float)v of each field value, unscaled, smk_merge_fields_f32_device(F, nf) gives G as a float in [0, 1]
+ *                 and the normals; channel nf is smk_quantize_u16_device of that G, with nf == 2 then stored as the pack's
+ *                 8-bit field; the normals are the float entry's, made from the floats before any quantisation.
+ * The summed gradient is g[axis] = 0.f; g[axis] += (plus - minus), fields ascending: one fp32 subtraction and one add per
+ * field and axis; it is 0 on the volume's 1-voxel border.  The fields on the border are COPIED, not zeroed (smk_derive_timestep
+ * zeroes them).  A context without normals keeps (128, 128, 128).  The pad column and row of a padded 8-byte box hold zeros,
+ * as after an upload; the 16 bytes behind the box are not touched; the brick summaries are made for the result.  The series'
+ * data mode is not looked at: the caller says whether a three-channel step is V, G, H (smk_derive_timestep) or two fields and
+ * G (this entry).
+ * Refused, with the reason, changing nothing: no volume; a sharded context (the stencil reaches 1 voxel beyond region + halo,
+ * and the maximum is the whole volume's); nelts < 2; a volume thinner than 3 voxels; step_src not cached; step_out < 0;
+ * step_out == step_src; no slot for the output.  Slots and ordering are smk_derive_timestep's: a cached step_out is
+ * overwritten in place (the current step too), otherwise the output takes a slot that is neither the source's nor the current
+ * step's; everything is enqueued on `stream` (NULL = the context's); no host synchronisation, no device-to-host copy, no
+ * allocation: the maximum stays in a device word that belongs to the OUTPUT slot, seeded on the stream. */
+int smk_merge_timestep(smk_ctx *ctx, int step_src, int step_out, void *stream);
+/* The same from nf dense scalars [sz][sy][sx] in DEVICE memory, one array per field as a simulation holds them: d_fields is a
+ * HOST array of nf device pointers, read before the call returns.  The fields' type is the ring's.  Into step `timestep`, by
+ * smk_upload_timestep_device's slot rule; `stream` must also order the reads of the fields.  Refused in addition: d_fields
+ * NULL, or any of its pointers NULL or below its element's alignment; nf != nelts - 1; field_dtype not the ring's type; sizes
+ * that are not the series'. */
+int smk_upload_timestep_fields_device(smk_ctx *ctx, int timestep, const void *const *d_fields, int nf, smk_dtype field_dtype,
+                                      int sx, int sy, int sz, void *stream);
 /* introspection: the current step (-1: no volume), the cached ids oldest written first (min(cap, *n) of them; ids_out may
  * be NULL), their number */
 int smk_get_timesteps(smk_ctx *ctx, int *current, int *ids_out, int cap, int *n);

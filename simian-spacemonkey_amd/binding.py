@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "smk_shard_light_order", "smk_get_shadow_margin",
     "smk_set_timestep_cache", "smk_upload_timestep", "smk_upload_timestep_device", "smk_select_timestep",
     "smk_get_timesteps", "smk_blend_timesteps", "smk_derive_timestep", "smk_upload_timestep_scalar_device",
+    "smk_merge_timestep", "smk_upload_timestep_fields_device",
     "smk_composite_over_depth_device", "smk_exchange_partial_depth", "smk_exchange_frame_depth", "smk_exchange_frame_local_depth",
     "smk_render_occluded", "smk_render_occluded_device",
     "smk_set_clip_slice",
@@ -141,6 +142,9 @@ def load_library():
     L.smk_derive_timestep.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
     L.smk_upload_timestep_scalar_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                                     C.c_int, C.c_int, C.c_void_p]
+    L.smk_merge_timestep.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.smk_upload_timestep_fields_device.argtypes = [C.c_void_p, C.c_int, P(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int,
+                                                    C.c_int, C.c_void_p]
     L.smk_set_shard.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.smk_set_clip.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
     L.smk_set_clip_plane.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double)]
@@ -383,6 +387,20 @@ class Renderer:
         the series'): the caller keeps the scalar alive until the stream has passed the call"""
         self._ck(self.L.smk_upload_timestep_scalar_device(self.ctx, int(timestep), dptr, int(scalar_dtype), int(dims[0]),
                                                           int(dims[1]), int(dims[2]), int(compat), int(blur), stream))
+
+    def merge_timestep(self, src, out, stream=None):
+        """step `out` becomes the multi-field step of the first nelts - 1 channels of the cached step `src`: the fields, G of
+        their summed gradient and its normals (smk.h smk_merge_timestep), enqueued on `stream` (a hipStream_t handle; None =
+        the context's stream)"""
+        self._ck(self.L.smk_merge_timestep(self.ctx, int(src), int(out), stream))
+
+    def upload_timestep_fields_device(self, timestep, ptrs, dtype, dims, stream=None):
+        """the same from dense scalars [sz][sy][sx] in device memory, one per field: `ptrs` is a sequence of device addresses
+        (None passes d_fields NULL), dtype the ring's (0 u8, 1 f32, 2 u16), dims (sx, sy, sz) the series'; the caller keeps the
+        fields alive until the stream has passed the call"""
+        arr = None if ptrs is None else (C.c_void_p * max(len(ptrs), 1))(*ptrs)
+        self._ck(self.L.smk_upload_timestep_fields_device(self.ctx, int(timestep), arr, 0 if ptrs is None else len(ptrs), int(dtype),
+                                                          int(dims[0]), int(dims[1]), int(dims[2]), stream))
 
     def timesteps(self):
         """(current step or -1, the cached ids oldest written first)"""

@@ -237,24 +237,22 @@ extern "C" int smk_normals_vgh_device(smk_ctx *c, const void *d, int ne, int sx,
 // (AGradArb, VectorMath.h:945-1004; 0 on the 1-voxel border) scaled by the volume's maximum to
 // 0..255 (GMag, :1010-1030), and the normal bytes of that summed gradient (scalebiasN).
 __device__ __forceinline__ void merge_grad(const unsigned char *in, int nf, int sx, int sy, int sz, int i, int j, int k, float g[3]) {
-  g[0] = g[1] = g[2] = 0.f;
+  merge_grad_zero(g);
   if (is_border(sx, sy, sz, i, j, k)) return;
   const size_t sxy = (size_t)sx * sy, o = (size_t)i * sxy + (size_t)j * sx + k;
-  for (int e = 0; e < nf; ++e) {  // byte differences and their sums are exact in float
-    g[0] += (float)in[(o + 1) * nf + e] - (float)in[(o - 1) * nf + e];
-    g[1] += (float)in[(o + sx) * nf + e] - (float)in[(o - sx) * nf + e];
-    g[2] += (float)in[(o + sxy) * nf + e] - (float)in[(o - sxy) * nf + e];
-  }
+  for (int e = 0; e < nf; ++e)  // byte differences and their sums are exact in float
+    merge_grad_add(g, (float)in[(o + 1) * nf + e], (float)in[(o - 1) * nf + e], (float)in[(o + sx) * nf + e], (float)in[(o - sx) * nf + e],
+                   (float)in[(o + sxy) * nf + e], (float)in[(o - sxy) * nf + e]);
 }
 
 __global__ __launch_bounds__(256) void smk_k_merge_max(const unsigned char *in, int nf, int sx, int sy, int sz, int *omax) {
   const size_t n = (size_t)sx * sy * sz;
-  int m = 0;  // f2o(0.0f): magnitudes are >= 0
+  int m = MERGE_MAX_SEED;
   for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (size_t)gridDim.x * blockDim.x) {
     int k = (int)(t % sx), j = (int)((t / sx) % sy), i = (int)(t / ((size_t)sx * sy));
     float g[3];
     merge_grad(in, nf, sx, sy, sz, i, j, k, g);
-    m = max(m, f2o(sqrtf(g[0] * g[0] + g[1] * g[1] + g[2] * g[2])));
+    m = merge_max_take(m, merge_mag(g));
   }
   m = wave_max(m);
   if ((threadIdx.x & 63) == 0) atomicMax(omax, m);
@@ -270,9 +268,7 @@ __global__ __launch_bounds__(256) void smk_k_merge_write(const unsigned char *in
     float g[3];
     merge_grad(in, nf, sx, sy, sz, i, j, k, g);
     for (int e = 0; e < nf; ++e) out[t * ne + e] = in[t * nf + e];
-    const float mag = sqrtf(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
-    const double q = (double)(mag / maxm) * 255.0;  // (uchar)(mag/max*255.0): float quotient, double product
-    out[t * ne + nf] = (q > -2147483649.0 && q < 2147483648.0) ? (unsigned char)((int)q & 0xff) : 0;
+    out[t * ne + nf] = merge_gmag_u8(merge_mag(g), maxm);
     if (nrm) nrm_store(g, nrm + t * 3);
   }
 }
@@ -483,28 +479,25 @@ extern "C" int smk_normals_f32_device(smk_ctx *c, const void *d, int ne, int sx,
 // merge_grad on floats: fields ascending, one add per field and axis, 0 on the border
 template <int NF>
 __device__ __forceinline__ void merge_grad_f32(const float *in, int sx, int sy, int sz, int i, int j, int k, float g[3]) {
-  g[0] = g[1] = g[2] = 0.f;
+  merge_grad_zero(g);
   if (is_border(sx, sy, sz, i, j, k)) return;
   const size_t sxy = (size_t)sx * sy, o = (size_t)i * sxy + (size_t)j * sx + k;
 #pragma unroll
-  for (int e = 0; e < NF; ++e) {
-    g[0] += in[(o + 1) * NF + e] - in[(o - 1) * NF + e];
-    g[1] += in[(o + sx) * NF + e] - in[(o - sx) * NF + e];
-    g[2] += in[(o + sxy) * NF + e] - in[(o - sxy) * NF + e];
-  }
+  for (int e = 0; e < NF; ++e)
+    merge_grad_add(g, in[(o + 1) * NF + e], in[(o - 1) * NF + e], in[(o + sx) * NF + e], in[(o - sx) * NF + e], in[(o + sxy) * NF + e],
+                   in[(o - sxy) * NF + e]);
 }
 
 // the maximum of the finite magnitudes (ordered-int atomicMax as smk_k_merge_max)
 template <int NF>
 __global__ __launch_bounds__(256) void smk_k_merge_max_f32(const float *in, int sx, int sy, int sz, int *omax) {
   const size_t n = (size_t)sx * sy * sz;
-  int m = 0;  // f2o(0.0f): magnitudes are >= 0
+  int m = MERGE_MAX_SEED;
   for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (size_t)gridDim.x * blockDim.x) {
     int k = (int)(t % sx), j = (int)((t / sx) % sy), i = (int)(t / ((size_t)sx * sy));
     float g[3];
     merge_grad_f32<NF>(in, sx, sy, sz, i, j, k, g);
-    const float mag = sqrtf(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
-    if (__builtin_isfinite(mag)) m = max(m, f2o(mag));
+    m = merge_max_take_f32(m, merge_mag(g));
   }
   m = wave_max(m);
   if ((threadIdx.x & 63) == 0) atomicMax(omax, m);
@@ -520,11 +513,11 @@ __global__ __launch_bounds__(256) void smk_k_merge_write_f32(const float *in, in
     int k = (int)(t % sx), j = (int)((t / sx) % sy), i = (int)(t / ((size_t)sx * sy));
     float g[3];
     merge_grad_f32<NF>(in, sx, sy, sz, i, j, k, g);
-    const float mag = sqrtf(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
+    const float mag = merge_mag(g);
     unsigned w[NF + 1];  // the fields travel as raw words: bit for bit, NaN payloads included
 #pragma unroll
     for (int e = 0; e < NF; ++e) w[e] = ((const unsigned *)in)[t * NF + e];
-    w[NF] = __float_as_uint((maxm > 0.f && __builtin_isfinite(mag)) ? mag / maxm : 0.f);
+    w[NF] = __float_as_uint(merge_g_f32(mag, maxm));
 #pragma unroll
     for (int e = 0; e < ne; ++e) ((unsigned *)out)[t * ne + e] = w[e];
     if (nrm) nrm_store_f32(g, nrm + t * 3);

@@ -1,6 +1,6 @@
 // smk_prep_device.h -- the device arithmetic of the data-preparation kernels (smk_prep.hip), shared with the kernels that
-// derive a resident time step in place (smk_step_derive.hip): one statement of every expression, so that both give the same
-// bits.  Plain fp32, doubles inside affine_d, one rounding per operation in the order written (-ffp-contract=off).
+// derive or merge a resident time step inside the ring (smk_step_derive.hip, smk_step_merge.hip): one statement of every
+// expression, so that all give the same bits.  Plain fp32, doubles inside affine_d, one rounding per operation in the order written (-ffp-contract=off).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -165,6 +165,29 @@ __device__ __forceinline__ void nrm_store_f32(float g[3], unsigned char *out) {
   }
   nrm_store(g, out);
 }
+
+// The multi-field merge (MetaVolume::mergeMV with addG; smk_prep.hip "multi-field merge", smk_step_merge.hip).  The summed
+// gradient starts at merge_grad_zero and takes merge_grad_add once per field, fields ascending: one fp32 subtraction and one
+// add per field and axis (byte and 16-bit differences and their sums are exact in float).  It stays zero on the 1-voxel border
+__device__ __forceinline__ void merge_grad_zero(float g[3]) { g[0] = g[1] = g[2] = 0.f; }
+__device__ __forceinline__ void merge_grad_add(float g[3], float xp, float xm, float yp, float ym, float zp, float zm) {
+  g[0] += xp - xm;
+  g[1] += yp - ym;
+  g[2] += zp - zm;
+}
+__device__ __forceinline__ float merge_mag(const float g[3]) { return sqrtf(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]); }
+
+// a thread's running maximum of the magnitudes starts at MERGE_MAX_SEED = f2o(0.0f): magnitudes are >= 0.  The u8 merge
+// counts every magnitude, the float merge the finite ones
+constexpr int MERGE_MAX_SEED = 0;
+__device__ __forceinline__ int merge_max_take(int m, float mag) { return max(m, f2o(mag)); }
+__device__ __forceinline__ int merge_max_take_f32(int m, float mag) { return __builtin_isfinite(mag) ? max(m, f2o(mag)) : m; }
+
+// GMag's byte (VectorMath.h:1010-1030), (uchar)(mag/max*255.0): float quotient, double product, the cast as uc_cast
+__device__ __forceinline__ unsigned char merge_gmag_u8(float mag, float maxm) { return uc_cast((double)(mag / maxm) * 255.0); }
+
+// the float merge's G: 0 where the magnitude is not finite or the maximum is 0
+__device__ __forceinline__ float merge_g_f32(float mag, float maxm) { return (maxm > 0.f && __builtin_isfinite(mag)) ? mag / maxm : 0.f; }
 
 // The normal's gradient at voxel (i, j, k) = (z, y, x) of an sx x sy x sz volume from grad(si, sj, sk, s[3]), the central
 // differences of channel 0 at an INTERIOR voxel (derivative3DVGH, VectorMath.h:874-899; 0 on the border).  Blurred: blurV3D is

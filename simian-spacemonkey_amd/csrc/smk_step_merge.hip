@@ -1,0 +1,368 @@
+// smk_step_merge.hip -- the multi-field step (fields + G, normals of the summed gradient) made INSIDE the time-step ring
+// (smk.h: smk_merge_timestep, smk_upload_timestep_fields_device; DESIGN.md 3b "Merged fields of a step").
+//
+// MetaVolume::mergeMV with addG (MetaVolume.cpp:1109-1268) is a host program that runs before the renderer starts.  A step
+// whose fields are new on the device -- the first nelts - 1 channels of a blend of two resident steps, or what a simulation
+// left in device memory, one array per field -- gets here what smk_merge_fields_device / smk_merge_fields_f32_device (and, in
+// a u16 ring, smk_quantize_u16_device) and smk_upload_timestep_device would make of them, bit for bit, as two kernels on the
+// caller's stream that write the packed voxels of a ring slot: no scratch arrays, no host wait.
+//
+// The stencil is the six face neighbours of every field, one difference per field and axis.  Both kernels read straight
+// through the caches, no LDS tile: a lane owns one 16-byte unit of the stored box (one f32 voxel, or two 8-byte voxels) and
+// marches through the slices of its tile, a workgroup MG_UX units of MG_TY rows of MG_TZ slices (mg_march).  A packed source
+// is read in whole units.
+//   pass 1 (smk_k_merge_max):   the magnitude of the summed gradient of every interior voxel -> its maximum (u8: of all, float
+//          rings: of the finite ones), one ordered-int atomicMax per wave into the OUTPUT slot's word (TimeStep::derive_st),
+//          which a one-lane kernel seeded on the stream; a capped grid strides over the tiles;
+//   pass 2 (smk_k_merge_write): the gradient again, G and the normal, and one 16-byte store of the unit (and the normal word of
+//          a four-channel f32 voxel).
+// The arithmetic is smk_prep.hip's, through smk_prep_device.h; the packed voxel is smk_packed.h's.
+#include <algorithm>
+
+#include "smk_internal.h"
+#include "smk_prep_device.h"
+
+namespace {
+
+// where the fields come from: dense arrays of a type (SRC is their smk_dtype), or the channels of a slot's packed voxels
+enum { MS_PK_U8 = 3, MS_PK_U16 = 4, MS_PK_F32 = 5 };
+
+constexpr int MG_UX = 64, MG_TY = 4, MG_TZ = 4;  // a workgroup's tile: units in x (a wave per row), rows, slices
+static_assert(MG_UX * MG_TY == 256, "a lane per unit of a slice of the tile");
+constexpr unsigned MG_MAX_BLOCKS = 2048;  // pass 1's grid: 8 workgroups for each of 256 CUs (its atomics land on one cache line)
+
+struct MergeParams {
+  const void *src;    // the source slot's packed voxels [D2][D1][D0] ...
+  const void *f[3];   // ... or the dense fields [N2][N1][N0], one array each
+  void *out;          // the output slot's packed voxels
+  uint32_t *nrm;      // its separate normal words (four-channel f32 with normals), else null
+  int *mx;            // the output slot's word: the maximum magnitude, ordered-int
+  int N[3], D[3];     // the volume; the stored box (origin 0: an unsharded context), D >= N with a pad column or row of 8-byte
+                      // voxels.  The kernels rely on D[2] == N[2], on D == N for f32 voxels and on an even D[0] otherwise
+  int normals;
+  int ux, uy, ntiles;  // tiles per row of tiles, per slice of tiles, in all
+};
+
+constexpr int mg_ring(int SRC) { return SRC == MS_PK_U8 ? SMK_U8 : SRC == MS_PK_U16 ? SMK_U16 : SRC == MS_PK_F32 ? SMK_F32 : SRC; }
+constexpr int mg_vpu(int SRC) { return mg_ring(SRC) == SMK_F32 ? 1 : 2;  }  // voxels per 16-byte unit
+
+// The fields of the voxels of unit U of row Y of slice Z as they are stored -- a byte, a 16-bit value or a float's word each --:
+// r[c][e], voxel c of the unit, field e.  A unit outside the stored box (and a dense voxel outside the volume) is zeros and is
+// never read: no interior voxel has such a neighbour
+template <int SRC, int NF>
+__device__ __forceinline__ void mg_cell(const MergeParams &P, int U, int Y, int Z, uint32_t r[][NF]) {
+  constexpr int VPU = mg_vpu(SRC);
+#pragma unroll
+  for (int c = 0; c < VPU; ++c)
+#pragma unroll
+    for (int e = 0; e < NF; ++e) r[c][e] = 0u;
+  if (U < 0 || U * VPU >= P.D[0] || Y < 0 || Y >= P.D[1] || Z < 0 || Z >= P.D[2]) return;
+  if (SRC == MS_PK_F32) {
+    const uint4 v = ((const uint4 *)P.src)[((size_t)Z * P.D[1] + Y) * P.D[0] + U];
+#pragma unroll
+    for (int e = 0; e < NF; ++e) r[0][e] = e == 0 ? v.x : e == 1 ? v.y : v.z;
+  } else if (SRC == MS_PK_U8 || SRC == MS_PK_U16) {  // two voxels (D[0] is even): their first words are .x and .z
+    const uint4 v = ((const uint4 *)P.src)[((size_t)Z * P.D[1] + Y) * (size_t)(P.D[0] >> 1) + U];
+#pragma unroll
+    for (int c = 0; c < VPU; ++c) {
+      const uint32_t w0 = c ? v.z : v.x;
+#pragma unroll
+      for (int e = 0; e < NF; ++e)
+        r[c][e] = SRC == MS_PK_U8 ? smk_u8_ch(w0, e) : e == 0 ? smk_vox8_c0<SMK_U16>(w0) : smk_vox8_c1<SMK_U16>(w0);
+    }
+  } else {  // dense fields, read at their element size
+    if (Y >= P.N[1]) return;
+#pragma unroll
+    for (int c = 0; c < VPU; ++c) {
+      const int X = U * VPU + c;
+      if (X >= P.N[0]) continue;
+      const size_t o = ((size_t)Z * P.N[1] + Y) * P.N[0] + X;
+#pragma unroll
+      for (int e = 0; e < NF; ++e)
+        r[c][e] = SRC == SMK_U8 ? (uint32_t)((const unsigned char *)P.f[e])[o]
+                : SRC == SMK_U16 ? (uint32_t)((const unsigned short *)P.f[e])[o] : ((const uint32_t *)P.f[e])[o];
+    }
+  }
+}
+
+// ... as the float the gradient is taken of: (float)v of an integer, unscaled (differences and their sums are exact)
+template <int SRC>
+__device__ __forceinline__ float mg_val(uint32_t r) {
+  return mg_ring(SRC) == SMK_F32 ? __uint_as_float(r) : (float)r;
+}
+
+// A lane's march through the MG_TZ slices of its tile at unit U of row Y: per slice visit(Z, g, r) with the summed gradients
+// g[c] of the unit's voxels (0 on the volume's 1-voxel border and outside the volume) and their fields r[c].  The units before
+// and behind come along in registers from slice to slice; the neighbours in the row are the neighbouring lanes' units (a wave
+// is a row of the tile: every lane of it must be here), which only the wave's first and last lane have to load; the units
+// above and below are loaded.  That makes three loads of a unit per unit where a plain stencil makes seven
+template <int SRC, int NF, class Visit>
+__device__ __forceinline__ void mg_march(const MergeParams &P, int U, int Y, int z0, Visit visit) {
+  constexpr int VPU = mg_vpu(SRC);
+  const int lane = threadIdx.x & 63;
+  uint32_t zm[VPU][NF], c0[VPU][NF], zp[VPU][NF];
+  mg_cell<SRC, NF>(P, U, Y, z0 - 1, zm);
+  mg_cell<SRC, NF>(P, U, Y, z0, c0);
+  for (int tz = 0; tz < MG_TZ; ++tz) {
+    const int Z = z0 + tz;
+    if (Z >= P.D[2]) break;  // (the whole workgroup)
+    uint32_t ym[VPU][NF], yp[VPU][NF], xl[NF], xr[NF];
+    mg_cell<SRC, NF>(P, U, Y, Z + 1, zp);
+    mg_cell<SRC, NF>(P, U, Y - 1, Z, ym);
+    mg_cell<SRC, NF>(P, U, Y + 1, Z, yp);
+#pragma unroll
+    for (int e = 0; e < NF; ++e) {
+      xl[e] = (uint32_t)__shfl_up((int)c0[VPU - 1][e], 1);
+      xr[e] = (uint32_t)__shfl_down((int)c0[0][e], 1);
+    }
+    if (lane == 0 || lane == 63) {
+      uint32_t t[VPU][NF];
+      mg_cell<SRC, NF>(P, lane ? U + 1 : U - 1, Y, Z, t);
+#pragma unroll
+      for (int e = 0; e < NF; ++e) {
+        if (lane) xr[e] = t[0][e];
+        else xl[e] = t[VPU - 1][e];
+      }
+    }
+    float g[VPU][3];
+#pragma unroll
+    for (int c = 0; c < VPU; ++c) {
+      merge_grad_zero(g[c]);
+      if (is_border(P.N[0], P.N[1], P.N[2], Z, Y, U * VPU + c)) continue;
+#pragma unroll
+      for (int e = 0; e < NF; ++e)
+        merge_grad_add(g[c], mg_val<SRC>(c == VPU - 1 ? xr[e] : c0[(c + 1) % VPU][e]), mg_val<SRC>(c == 0 ? xl[e] : c0[(c + VPU - 1) % VPU][e]),
+                       mg_val<SRC>(yp[c][e]), mg_val<SRC>(ym[c][e]), mg_val<SRC>(zp[c][e]), mg_val<SRC>(zm[c][e]));
+    }
+    visit(Z, g, c0);
+#pragma unroll
+    for (int c = 0; c < VPU; ++c)
+#pragma unroll
+      for (int e = 0; e < NF; ++e) {
+        zm[c][e] = c0[c][e];
+        c0[c][e] = zp[c][e];
+      }
+  }
+}
+
+// tile -> its first unit, row and slice
+__device__ __forceinline__ void mg_tile(const MergeParams &P, int tile, int &u0, int &y0, int &z0) {
+  const int bz = tile / P.uy, r = tile - bz * P.uy, by = r / P.ux;
+  u0 = (r - by * P.ux) * MG_UX;
+  y0 = by * MG_TY;
+  z0 = bz * MG_TZ;
+}
+
+__global__ __launch_bounds__(64) void smk_k_merge_seed(int *mx) {
+  if (threadIdx.x == 0) *mx = MERGE_MAX_SEED;
+}
+
+template <int SRC, int NF>
+__global__ __launch_bounds__(256) void smk_k_merge_max(const MergeParams P) {
+  constexpr int VPU = mg_vpu(SRC);
+  const int tu = threadIdx.x % MG_UX, ty = threadIdx.x / MG_UX;
+  int m = MERGE_MAX_SEED;
+  for (int tile = blockIdx.x; tile < P.ntiles; tile += gridDim.x) {
+    int u0, y0, z0;
+    mg_tile(P, tile, u0, y0, z0);
+    const int U = u0 + tu, Y = y0 + ty;
+    mg_march<SRC, NF>(P, U, Y, z0, [&](int Z, const float g[][3], const uint32_t r[][NF]) {
+#pragma unroll
+      for (int c = 0; c < VPU; ++c) {
+        if (is_border(P.N[0], P.N[1], P.N[2], Z, Y, U * VPU + c)) continue;  // (and everything outside the volume)
+        const float mag = merge_mag(g[c]);
+        m = mg_ring(SRC) == SMK_U8 ? merge_max_take(m, mag) : merge_max_take_f32(m, mag);
+      }
+    });
+  }
+  m = wave_max(m);
+  if ((threadIdx.x & 63) == 0) atomicMax(P.mx, m);
+}
+
+// the packed voxel of the output at column X of row Y from its summed gradient g and its fields r: w[0..1] of an 8-byte ring,
+// w[0..3] of f32; nw: the normal word
+template <int SRC, int NF>
+__device__ __forceinline__ void mg_voxel(const MergeParams &P, int X, int Y, const float gin[3], const uint32_t r[NF], float maxm, uint32_t w[4],
+                                         uint32_t &nw) {
+  constexpr int RING = mg_ring(SRC);
+  nw = SMK_NRM_NONE;
+  if (X >= P.N[0] || Y >= P.N[1]) {  // the pad column or row of an 8-byte box: zeros, as after an upload
+    w[0] = w[1] = w[2] = w[3] = 0u;
+    return;
+  }
+  float g[3] = {gin[0], gin[1], gin[2]};
+  const float mag = merge_mag(g);
+  if (P.normals) {
+    unsigned char n[3];
+    if (RING == SMK_U8) nrm_store(g, n);
+    else nrm_store_f32(g, n);  // (u16: the float entry's normals, made from the floats before any quantisation)
+    nw = smk_nrm_word(n[0], n[1], n[2]);
+  }
+  if (RING == SMK_U8) {  // (the fields are copied, on the border too)
+    unsigned char q[NF + 1];
+#pragma unroll
+    for (int e = 0; e < NF; ++e) q[e] = (unsigned char)r[e];
+    q[NF] = merge_gmag_u8(mag, maxm);
+    const uint2 v = smk_pack_u8(q, NF + 1, nw);
+    w[0] = v.x, w[1] = v.y;
+  } else if (RING == SMK_U16) {
+    unsigned short s[NF + 1];
+#pragma unroll
+    for (int e = 0; e < NF; ++e) s[e] = (unsigned short)r[e];
+    s[NF] = quant_u16(merge_g_f32(mag, maxm));  // smk_quantize_u16_device of the float G
+    const uint2 v = smk_pack_u16(s, NF + 1, nw);
+    w[0] = v.x, w[1] = v.y;
+  } else {
+    float f[NF + 1];
+#pragma unroll
+    for (int e = 0; e < NF; ++e) f[e] = __uint_as_float(r[e]);  // raw words: NaN payloads and -0 travel
+    f[NF] = merge_g_f32(mag, maxm);
+    const uint4 v = smk_pack_f32(f, NF + 1, nw, NF + 1 <= 3);
+    w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
+  }
+}
+
+template <int SRC, int NF>
+__global__ __launch_bounds__(256) void smk_k_merge_write(const MergeParams P) {
+  constexpr int VPU = mg_vpu(SRC);
+  const float maxm = o2f(*P.mx);
+  int u0, y0, z0;
+  mg_tile(P, blockIdx.x, u0, y0, z0);
+  const int U = u0 + threadIdx.x % MG_UX, Y = y0 + threadIdx.x / MG_UX;
+  const bool stored = U * VPU < P.D[0] && Y < P.D[1];  // (a lane outside the box stays for its neighbours' sake)
+  mg_march<SRC, NF>(P, U, Y, z0, [&](int Z, const float g[][3], const uint32_t r[][NF]) {
+    if (!stored) return;
+    const size_t o = ((size_t)Z * P.D[1] + Y) * (size_t)(P.D[0] / VPU) + U;  // the unit
+    uint32_t w[4], nw;
+    if (VPU == 1) {
+      mg_voxel<SRC, NF>(P, U, Y, g[0], r[0], maxm, w, nw);
+      if (NF == 3 && P.nrm) P.nrm[o] = nw;
+    } else {
+      uint32_t hi[4];
+      mg_voxel<SRC, NF>(P, 2 * U, Y, g[0], r[0], maxm, w, nw);
+      mg_voxel<SRC, NF>(P, 2 * U + 1, Y, g[VPU - 1], r[VPU - 1], maxm, hi, nw);
+      w[2] = hi[0], w[3] = hi[1];
+    }
+    ((uint4 *)P.out)[o] = make_uint4(w[0], w[1], w[2], w[3]);
+  });
+}
+
+template <int SRC, int NF>
+hipError_t launch_merge(const MergeParams &P, hipStream_t s) {
+  hipLaunchKernelGGL(smk_k_merge_seed, dim3(1), dim3(64), 0, s, P.mx);
+  hipLaunchKernelGGL((smk_k_merge_max<SRC, NF>), dim3(std::min<unsigned>((unsigned)P.ntiles, MG_MAX_BLOCKS)), dim3(256), 0, s, P);
+  hipLaunchKernelGGL((smk_k_merge_write<SRC, NF>), dim3((unsigned)P.ntiles), dim3(256), 0, s, P);
+  return hipGetLastError();
+}
+
+template <int SRC>
+hipError_t launch_merge_nf(const MergeParams &P, int nf, hipStream_t s) {
+  if (nf == 1) return launch_merge<SRC, 1>(P, s);
+  if (nf == 2) return launch_merge<SRC, 2>(P, s);
+  if constexpr (mg_ring(SRC) != SMK_U16) {  // (a u16 voxel holds three channels: merge_refusals)
+    if (nf == 3) return launch_merge<SRC, 3>(P, s);
+  }
+  return hipErrorInvalidValue;
+}
+
+// what both entries refuse before they look at their source
+int merge_refusals(smk_ctx *c, const char *who) {
+  if (!c->have_volume) FAIL(c, "%s: no volume uploaded", who);
+  if (c->nranks > 1)
+    FAIL(c, "%s: a sharded context (%d ranks): the stencil reaches 1 voxel beyond region + halo, and G is scaled by the whole "
+            "volume's maximum", who, c->nranks);
+  if (c->nelts < 2) FAIL(c, "%s: the series has nelts %d: a multi-field step is at least one field and G (nelts >= 2)", who, c->nelts);
+  const int top = c->dtype == SMK_U16 ? 3 : 4;
+  if (c->nelts > top) FAIL(c, "%s: internal: nelts %d of a voxel type that holds %d channels", who, c->nelts, top);
+  // what the kernels take for granted of an unsharded context's stored box (smk_volume_geometry): it starts at voxel 0, is
+  // the volume in z, and is wider than the volume only by the pad column and row of 8-byte voxels
+  const bool wide = c->dtype == SMK_F32;
+  if (c->O[0] || c->O[1] || c->O[2] || c->D[2] != c->N[2] || c->D[0] < c->N[0] || c->D[1] < c->N[1] || c->D[0] > c->N[0] + 1 ||
+      c->D[1] > c->N[1] + 1 || (wide && (c->D[0] != c->N[0] || c->D[1] != c->N[1])) || (!wide && (c->D[0] & 1)))
+    FAIL(c, "%s: internal: the stored box %dx%dx%d at %d,%d,%d is not the volume %dx%dx%d with its pad", who, c->D[0], c->D[1], c->D[2], c->O[0],
+         c->O[1], c->O[2], c->N[0], c->N[1], c->N[2]);
+  if (c->N[0] < 3 || c->N[1] < 3 || c->N[2] < 3)
+    FAIL(c, "%s: a %dx%dx%d volume has no interior voxel (dims >= 3, as smk_merge_fields_device)", who, c->N[0], c->N[1], c->N[2]);
+  return 0;
+}
+
+// the two passes, the brick summaries and the bookkeeping of the output step; ksrc: the source slot, or -1 (dense fields)
+int merge_enqueue(smk_ctx *c, const char *who, const void *const *fields, int ksrc, int step_out, hipStream_t s) {
+  int need = 0;
+  const int k = smk_step_output_slot(c, step_out, ksrc, -1, &need);
+  if (k < 0) {
+    if (ksrc >= 0)
+      FAIL(c, "%s: the cache holds %d steps: the source and the output need two slots, three when the current step (%d) is a third "
+              "(here %d); smk_set_timestep_cache sets more", who, (int)c->ts.size(), c->ts_cur_id, need);
+    FAIL(c, "%s: time step %d: the cache holds one step, the current one (%d); smk_set_timestep_cache sets more", who, step_out, c->ts_cur_id);
+  }
+  const int VPU = c->dtype == SMK_F32 ? 1 : 2, nf = c->nelts - 1;
+  const long long ux = (c->D[0] / VPU + MG_UX - 1) / MG_UX, uy = (c->D[1] + MG_TY - 1) / MG_TY, uz = (c->D[2] + MG_TZ - 1) / MG_TZ;
+  if (ux * uy * uz > 0x7fffffffLL) FAIL(c, "%s: a %dx%dx%d volume has more than 2^31 tiles", who, c->N[0], c->N[1], c->N[2]);
+  if (smk_step_write_begin(c, k, s)) return 1;
+  c->ts_series = true;
+  if (ksrc >= 0 && smk_step_read_begin(c, ksrc, s)) return 1;
+  TimeStep &T = c->ts[(size_t)k];
+  MergeParams P;
+  P.src = ksrc >= 0 ? c->ts[(size_t)ksrc].vox : nullptr;
+  for (int e = 0; e < 3; ++e) P.f[e] = fields && e < nf ? fields[e] : nullptr;
+  P.out = T.vox;
+  P.nrm = smk_step_separate_normals(c) ? T.nrm : nullptr;
+  P.mx = T.derive_st;
+  for (int a = 0; a < 3; ++a) {
+    P.N[a] = c->N[a];
+    P.D[a] = c->D[a];
+  }
+  P.normals = c->have_normals ? 1 : 0;
+  P.ux = (int)ux;
+  P.uy = (int)(ux * uy);
+  P.ntiles = (int)(ux * uy * uz);
+  hipError_t e;
+  if (ksrc >= 0) {
+    e = c->dtype == SMK_U8 ? launch_merge_nf<MS_PK_U8>(P, nf, s) : c->dtype == SMK_U16 ? launch_merge_nf<MS_PK_U16>(P, nf, s)
+                                                                                          : launch_merge_nf<MS_PK_F32>(P, nf, s);
+  } else {
+    e = c->dtype == SMK_U8 ? launch_merge_nf<SMK_U8>(P, nf, s) : c->dtype == SMK_U16 ? launch_merge_nf<SMK_U16>(P, nf, s)
+                                                                                        : launch_merge_nf<SMK_F32>(P, nf, s);
+  }
+  HIPCHK(c, e);
+  HIPCHK(c, smk_bricks_minmax(T.vox, c->dtype, c->D, c->nbr, T.mm, s));
+  if (smk_step_write_end(c, k, step_out, s)) return 1;
+  if (ksrc >= 0 && smk_step_read_end(c, ksrc, s)) return 1;  // whatever overwrites the source slot comes after these reads
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int smk_merge_timestep(smk_ctx *c, int step_src, int step_out, void *stream) {
+  if (!c) return 1;
+  const char *who = "smk_merge_timestep";
+  HIPCHK(c, hipSetDevice(c->device));
+  if (merge_refusals(c, who)) return 1;
+  const int ksrc = step_src < 0 ? -1 : smk_step_slot(c, step_src);
+  if (ksrc < 0) FAIL(c, "%s: time step %d (the source) is not cached", who, step_src);
+  if (step_out < 0) FAIL(c, "%s: output time step %d: ids are >= 0", who, step_out);
+  if (step_out == step_src) FAIL(c, "%s: output time step %d is also the source: the stencil has no in-place form", who, step_out);
+  return merge_enqueue(c, who, nullptr, ksrc, step_out, stream ? (hipStream_t)stream : c->stream);
+}
+
+extern "C" int smk_upload_timestep_fields_device(smk_ctx *c, int timestep, const void *const *d_fields, int nf, smk_dtype field_dtype,
+                                                 int sx, int sy, int sz, void *stream) {
+  if (!c) return 1;
+  const char *who = "smk_upload_timestep_fields_device";
+  HIPCHK(c, hipSetDevice(c->device));
+  if (merge_refusals(c, who)) return 1;
+  if (timestep < 0) FAIL(c, "%s: time step %d: ids are >= 0", who, timestep);
+  if (!d_fields) FAIL(c, "%s: d_fields is NULL", who);
+  if (nf != c->nelts - 1) FAIL(c, "%s: %d fields for a series of nelts %d: the fields are nelts - 1 = %d", who, nf, c->nelts, c->nelts - 1);
+  if ((int)field_dtype != c->dtype)
+    FAIL(c, "%s: field_dtype %d is not the ring's type (%d): the fields are stored as they come", who, (int)field_dtype, c->dtype);
+  if (sx != c->N[0] || sy != c->N[1] || sz != c->N[2])
+    FAIL(c, "%s: time step %d: sizes %dx%dx%d differ from the series' %dx%dx%d", who, timestep, sx, sy, sz, c->N[0], c->N[1], c->N[2]);
+  const size_t eb = smk_elem_bytes(field_dtype);
+  for (int e = 0; e < nf; ++e) {
+    if (!d_fields[e]) FAIL(c, "%s: d_fields[%d] is NULL", who, e);
+    if ((uintptr_t)d_fields[e] % eb) FAIL(c, "%s: d_fields[%d] is not aligned to its %zu-byte elements", who, e, eb);
+  }
+  return merge_enqueue(c, who, d_fields, -1, timestep, stream ? (hipStream_t)stream : c->stream);
+}

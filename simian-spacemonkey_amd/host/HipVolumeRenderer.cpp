@@ -415,8 +415,11 @@ void HipVolumeRenderable::showTimeFraction() {
   int shown = id;
   const int bad = smk_blend_timesteps(c, tstep, tstep + 1, tfrac, id, nullptr);
   if (!bad && tderive) {
-    // V, G, H and normals of the blended scalar, behind the blend on the same stream: no host wait.  A refusal -- a series
-    // that is not V, G, H -- is said here, once for this step and fraction as a refused blend is, and the frames show the blend
+    // V, G, H and normals of the blended scalar -- or, for a multi-field series (gluvv.dmode GDM_V1G, GDM_V2G, GDM_V3G: what
+    // mergeMV with -addG made), the blended fields with G and the normals of their summed gradient -- behind the blend on the
+    // same stream: no host wait.  A refusal -- a series that is neither -- is said here, once for this step and fraction as a
+    // refused blend is, and the frames show the blend
+    const bool merged = gluvv.dmode == GDM_V1G || gluvv.dmode == GDM_V2G || gluvv.dmode == GDM_V3G;
     const int did = INT_MAX - 2 - tblend_next;
     // A derived id that is resident is overwritten in place.  One that is not -- its first use, or evicted since by steps the
     // series uploaded -- would take a slot by the ring's rule, which spares the derive's source and the current step but not
@@ -431,7 +434,7 @@ void HipVolumeRenderable::showTimeFraction() {
     }
     if (!resident && smk_blend_timesteps(c, tstep, tstep + 1, tfrac, did, nullptr))
       std::cerr << "ERROR: HipVolumeRenderable::setTimeFractionDerivatives: " << smk_last_error(c) << std::endl;
-    else if (smk_derive_timestep(c, id, did, 1, 0, nullptr))
+    else if (merged ? smk_merge_timestep(c, id, did, nullptr) : smk_derive_timestep(c, id, did, 1, 0, nullptr))
       std::cerr << "ERROR: HipVolumeRenderable::setTimeFractionDerivatives: " << smk_last_error(c) << std::endl;
     else
       shown = did;

@@ -157,8 +157,11 @@ class HipVolumeRenderable final : public gluvvPrimitive {
   // derivatives of the blend (an extension beside setTimeFraction).  On: the frames of a fraction show not the blend -- whose G
   // and H are the blends of G and H -- but the VGH step of the blended SCALAR, channel 0 of the blend: makeVGH's V, G, H (the
   // reference's h[4] typo kept) and normalsVGH's plain normals, made on the device by smk_derive_timestep into a second pair
-  // of reserved ids; the ring grows by two more slots.  The series must be V, G, H (nelts 3): a derive that is refused is
-  // reported once on stderr, as a refused blend is, and the frames show the blend.  Returns 0.  Call after init().
+  // of reserved ids; the ring grows by two more slots.  A multi-field series -- gluvv.dmode GDM_V1G, GDM_V2G or GDM_V3G, what
+  // MetaVolume::mergeMV with -addG made of one to three fields -- shows the merged step of the blended FIELDS instead: the fields
+  // as blended, G of their summed gradient and its normals (smk_merge_timestep), by the same ids and rules.  Every other series
+  // must be V, G, H (nelts 3): a derive that is refused is reported once on stderr, as a refused blend is, and the frames show
+  // the blend.  Returns 0.  Call after init().
   int setTimeFractionDerivatives(int on_off);
   // MetaVolume::writeAll + Volume::writeVol (MetaVolume.cpp:99-126, 963-1000) for the step draw() shows -- a blend made by
   // setTimeFraction included --, read back from the renderer (HipVolumeRenderer::downloadStep).  A one-channel 8-bit step

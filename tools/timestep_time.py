@@ -23,7 +23,13 @@ Frame times are HIP-event times on the render stream (median); the loop also rep
      smk_normals_*_device, smk_upload_timestep_device --: its device work stage by stage and its wall time, host wait
      included; then, for f32, playback over the four resident steps with a blend and a derive on a second stream beside each
      frame.  Writes the note profiles/step_derive.md (--out PATH: elsewhere).
-    python tools/timestep_time.py --derive [--out PATH] [volume edge] [loop frames]"""
+    python tools/timestep_time.py --derive [--out PATH] [volume edge] [loop frames]
+  6. --merge: merged fields of a step (smk_merge_timestep).  The same two comparisons for a multi-field series -- config 3's
+     step read as two fields and G --: the blend and the merge of it against the recipe -- blend, download, strided copy of
+     the fields, stream synchronise, smk_merge_fields_device / smk_merge_fields_f32_device (for a u16 ring: the fields as
+     floats, the float merge, smk_quantize_u16_device of G, the voxels put together), smk_upload_timestep_device --; then,
+     for f32, playback with a blend and a merge on a second stream beside each frame.  Writes profiles/step_merge.md.
+    python tools/timestep_time.py --merge [--out PATH] [volume edge] [loop frames]"""
 import os
 import statistics
 import sys
@@ -310,7 +316,127 @@ def derive_leg(pkg, n, loop, out_path):
     print("wrote", out_path, flush=True)
 
 
-def derive_playback(R, n, loop, bl):
+def merge_leg(pkg, n, loop, out_path):
+    lines = ["# Merged fields of a step: `smk_merge_timestep` on one MI355X", "",
+             "Written by `tools/timestep_time.py --merge %d %d`.  Config 3's step (%d^3, three channels with normals) read as a" % (n, loop, n),
+             "multi-field step: two fields and G.  The source is the 0.3 blend of two resident steps.  Median of 9 after 3 warm-up rounds.",
+             "", "- **entry**: HIP events round `smk_blend_timesteps` + `smk_merge_timestep` on one stream (and round the merge alone):",
+             "  seed, maximum pass, write pass, brick summaries.  No host wait.  Bytes counted for the merge alone: the two passes read",
+             "  the stored source, the write pass writes the stored output, the summaries read it: 4 x stored.",
+             "- **recipe** (INTEGRATION.md 5, the definition of the contract): blend, `smk_download_timestep_device`, a strided copy of",
+             "  the two fields, a stream synchronise, the merge entry (`smk_merge_fields_device` for u8, `smk_merge_fields_f32_device`",
+             "  for f32; for a u16 ring the fields as floats, the float merge, `smk_quantize_u16_device` of G and the voxels put together),",
+             "  `smk_upload_timestep_device`.  Its device work is the sum of its stages: HIP events round the asynchronous ones on",
+             "  their stream; the merge and quantise entries run on the context's own stream and return when their kernels are done,",
+             "  so their stage is the host time of the call on an idle device (it includes their launch and their allocation, which",
+             "  are part of that path).  Wall: host time from the first call to the end of a final synchronise.",
+             "", "The condition of the feature: the entry's device time does not exceed the recipe's in the same run, on any ring type.", "",
+             "| ring | merge alone ms | merge GB/s | blend + merge ms | recipe device ms (blend+download+copy / merge / quantise+compose / upload) | recipe wall ms | entry / recipe device | not above |",
+             "|---|---|---|---|---|---|---|---|"]
+    bl = torch.cuda.Stream()
+    dims = (n, n, n)
+    nv = n ** 3
+    play = []
+    for dtype in ("u8", "u16", "f32"):
+        R = pkg.Renderer(0)
+        try:
+            steps, dt = typed_steps(R, n, dtype)
+            R.set_timestep_cache(8)
+            R.upload_volume_device(steps[0][0].data_ptr(), dims, 3, dt, steps[0][1].data_ptr(), dmode="V2G")
+            for t in (1, 2, 3):
+                R.upload_timestep_device(t, steps[t][0].data_ptr(), dims, 3, dt, steps[t][1].data_ptr(), dmode="V2G", stream=bl.cuda_stream)
+            torch.cuda.synchronize()
+            tdt = {"f32": torch.float32, "u8": torch.uint8, "u16": torch.int16}[dtype]
+            mdt = torch.uint8 if dtype == "u8" else torch.float32
+            out_d = torch.zeros((nv, 3), dtype=tdt, device="cuda")       # the recipe's scratch arrays
+            f2 = torch.zeros((nv, 2), dtype=mdt, device="cuda")
+            mg = torch.zeros((nv, 3), dtype=mdt, device="cuda")
+            g1 = torch.zeros(nv, dtype=torch.float32, device="cuda") if dtype == "u16" else None
+            q1 = torch.zeros(nv, dtype=torch.int16, device="cuda") if dtype == "u16" else None
+            v16 = torch.zeros((nv, 3), dtype=torch.int16, device="cuda") if dtype == "u16" else None
+            nrm = torch.zeros(nv * 3, dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            sb = bl.cuda_stream
+            t_merge, t_entry, t_recipe, t_wall = [], [], [], []
+            for i in range(12):
+                R.blend_timesteps(0, 1, 0.3, 10, stream=sb)
+                t_merge.append(event_ms(bl, lambda: R.merge_timestep(10, 12, stream=sb)))
+                t_entry.append(event_ms(bl, lambda: (R.blend_timesteps(0, 1, 0.3, 10, stream=sb), R.merge_timestep(10, 12, stream=sb))))
+                torch.cuda.synchronize()
+                w0 = time.perf_counter()
+
+                def front():
+                    R.blend_timesteps(0, 1, 0.3, 11, stream=sb)
+                    R.download_timestep_device(out_d.data_ptr(), None, 11, sb)
+                    with torch.cuda.stream(bl):
+                        if dtype == "u16":                               # F = (float)v of the 16-bit values, unscaled
+                            f2.copy_(out_d[:, :2].to(torch.int32) & 0xffff)
+                        else:
+                            f2.copy_(out_d[:, :2])
+                st_front = event_ms(bl, front)                           # (event_ms ends with the host wait of the recipe)
+                if dtype == "u8":
+                    st_m = wall_ms(lambda: R.merge_fields_device(f2.data_ptr(), 2, dims, mg.data_ptr(), nrm.data_ptr()))
+                else:
+                    st_m = wall_ms(lambda: R.merge_fields_f32_device(f2.data_ptr(), 2, dims, mg.data_ptr(), nrm.data_ptr()))
+                st_q = 0.0
+                if dtype == "u16":
+                    def gcopy():
+                        with torch.cuda.stream(bl):
+                            g1.copy_(mg[:, 2])
+                    st_q = event_ms(bl, gcopy)
+                    st_q += wall_ms(lambda: R.quantize_u16_device(g1.data_ptr(), nv, q1.data_ptr()))
+
+                    def compose():
+                        with torch.cuda.stream(bl):
+                            v16[:, :2].copy_(out_d[:, :2])
+                            v16[:, 2].copy_(q1)
+                    st_q += event_ms(bl, compose)
+                up = v16 if dtype == "u16" else mg
+                st_up = event_ms(bl, lambda: R.upload_timestep_device(13, up.data_ptr(), dims, 3, dt, nrm.data_ptr(), dmode="V2G", stream=sb))
+                torch.cuda.synchronize()
+                t_wall.append((time.perf_counter() - w0) * 1e3)
+                t_recipe.append((st_front, st_m, st_q, st_up))
+            # the two results are the same step
+            a_d, a_g = torch.zeros_like(out_d), torch.zeros(nv * 3, dtype=torch.uint8, device="cuda")
+            b_d, b_g = torch.zeros_like(out_d), torch.zeros(nv * 3, dtype=torch.uint8, device="cuda")
+            R.blend_timesteps(0, 1, 0.3, 11, stream=sb)
+            R.merge_timestep(11, 12, stream=sb)
+            R.download_timestep_device(a_d.data_ptr(), a_g.data_ptr(), 12, sb)
+            R.download_timestep_device(b_d.data_ptr(), b_g.data_ptr(), 13, sb)
+            torch.cuda.synchronize()
+            assert torch.equal(a_d.view(torch.uint8), b_d.view(torch.uint8)) and torch.equal(a_g, b_g), "the merge differs from the recipe"
+            med = statistics.median
+            m_ms, e_ms, w_ms = med(t_merge[3:]), med(t_entry[3:]), med(t_wall[3:])
+            stages = [med([r[j] for r in t_recipe[3:]]) for j in range(4)]
+            r_ms = sum(stages)
+            stored = nv * (16 if dtype == "f32" else 8)
+            lines.append("| %s | %.3f (min %.3f, max %.3f) | %.0f | %.3f (min %.3f, max %.3f) | %.3f (%s) | %.3f | %.3f | %s |" % (
+                dtype, m_ms, min(t_merge[3:]), max(t_merge[3:]), 4 * stored / m_ms / 1e6, e_ms, min(t_entry[3:]), max(t_entry[3:]), r_ms,
+                " / ".join("%.3f" % v for v in stages), w_ms, e_ms / r_ms, "yes" if e_ms <= r_ms else "NO"))
+            print(lines[-1], flush=True)
+            if dtype == "f32":
+                del out_d, f2, mg, nrm, a_d, a_g, b_d, b_g
+                play = derive_playback(R, n, loop, bl, make=lambda src, out: R.merge_timestep(src, out, stream=bl.cuda_stream), what="merge")
+        finally:
+            R.close()
+            torch.cuda.synchronize()
+    lines += ["", "## Playback", "", "Config 3's scene (f32, 1024^2 x 512 planes) over the four resident steps, every step followed by 4 frames of",
+              "fractional time (w = 0.2 .. 0.8) towards the next one, each showing the MERGED step of its blend; blend and merge of",
+              "frame i + 1 are enqueued on a second stream before frame i, into the output ids frame i does not show.", ""] + play
+    regs = {k: v for k, v in kernel_registers().items() if "smk_k_merge_seed" in k or "MergeParams" in k}
+    lines += ["", "## Kernels", "", "`smk_k_merge_max<SRC, NF>` and `smk_k_merge_write<SRC, NF>` (SRC 0..2: dense u8 / f32 / u16 fields, 3..5: the channels of",
+              "packed u8 / u16 / f32 voxels; NF: the number of fields): one workgroup of 256 lanes per tile of 64 units x 4 rows x 4 slices,",
+              "a lane per 16-byte unit (two 8-byte voxels, or one f32 voxel) that marches through the tile's slices: the units before and",
+              "behind stay in registers, the row's neighbours come from the neighbouring lanes, the units above and below are loaded",
+              "straight through the caches; no LDS; one 16-byte store per unit.  From `tools/kernel_inventory.py`:", "",
+              "| kernel | VGPRs | SGPRs | LDS bytes | scratch bytes |", "|---|---|---|---|---|"]
+    lines += ["| `%s` | %d | %d | %d | %d |" % (k, v["vgprs"], v["sgprs"], v["group_segment"], v["private_segment"]) for k, v in sorted(regs.items())] \
+        or ["| (inventory not available here) | | | | |"]
+    open(out_path, "w").write("\n".join(lines) + "\n")
+    print("wrote", out_path, flush=True)
+
+
+def derive_playback(R, n, loop, bl, make=None, what="derive"):
     frame = torch.zeros((SIZE * SIZE, 4), dtype=torch.float32, device="cuda")
     st = torch.cuda.Stream()
     bench.configure(R, "cfg3", n, SIZE, PLANES)
@@ -325,10 +451,13 @@ def derive_playback(R, n, loop, bl):
         R.blend_timesteps(a, b, w, 10 + (i & 1), stream=bl.cuda_stream)
         if not derive:
             return 10 + (i & 1)
-        R.derive_timestep(10 + (i & 1), 12 + (i & 1), 1, 0, stream=bl.cuda_stream)
+        if make:
+            make(10 + (i & 1), 12 + (i & 1))
+        else:
+            R.derive_timestep(10 + (i & 1), 12 + (i & 1), 1, 0, stream=bl.cuda_stream)
         return 12 + (i & 1)
     out = []
-    for label, derive in (("blends alone", False), ("a blend and a derive beside each fractional frame", True)):
+    for label, derive in (("blends alone", False), ("a blend and a %s beside each fractional frame" % what, True)):
         for phase, frames in (("warm-up", len(seq)), ("timed", loop)):
             ev = []
             R.select_timestep(prepare(0, derive))
@@ -428,16 +557,18 @@ def blend_playback(R, n, loop, bl):
 
 def main():
     args = sys.argv[1:]
-    blend, download, derive = "--blend" in args, "--download" in args, "--derive" in args
+    blend, download, derive, merge = "--blend" in args, "--download" in args, "--derive" in args, "--merge" in args
     out_path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                            "step_derive.md" if derive else "step_download.md" if download else "timestep_blend.md")
+                            "step_merge.md" if merge else "step_derive.md" if derive else "step_download.md" if download else "timestep_blend.md")
     if "--out" in args:
         out_path = args[args.index("--out") + 1]
         del args[args.index("--out"):args.index("--out") + 2]
-    args = [a for a in args if a not in ("--blend", "--download", "--derive")]
+    args = [a for a in args if a not in ("--blend", "--download", "--derive", "--merge")]
     n = int(args[0]) if len(args) > 0 else 512
     loop = int(args[1]) if len(args) > 1 else 32
     pkg = bench.load_package()
+    if merge:
+        return merge_leg(pkg, n, loop, out_path)
     if derive:
         return derive_leg(pkg, n, loop, out_path)
     if download:
