@@ -314,7 +314,7 @@ int smk_alloc_step(smk_ctx *c, const SmkVolGeom &g, TimeStep &T) {
   }
   if (g.nrm_bytes && !T.nrm) HIPCHK(c, hipMalloc((void **)&T.nrm, g.nrm_bytes));
   if (!T.mm) HIPCHK(c, hipMalloc((void **)&T.mm, g.mm_bytes));
-  if (!T.derive_st) HIPCHK(c, hipMalloc((void **)&T.derive_st, 8 * sizeof(int)));  // (with the slot: a derive allocates nothing)
+  if (!T.pass1_words) HIPCHK(c, hipMalloc((void **)&T.pass1_words, 8 * sizeof(int)));  // (with the slot: a producer allocates nothing)
   return 0;
 }
 

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <functional>
 #include <map>
 #include <string>
 #include <vector>
@@ -260,9 +261,9 @@ struct TimeStep {
   bool ready_pending = false;       // ... recorded and not yet seen complete
   hipEvent_t used = nullptr;        // the last frame that read the step
   bool used_valid = false;
-  hipEvent_t blended = nullptr;     // the last smk_blend_timesteps or step histogram that read the step, on the stream it was enqueued on
-  bool blended_valid = false;
-  int *derive_st = nullptr;         // six ordered-int extremes between the two passes of a derive INTO this slot (smk_step_derive.hip)
+  hipEvent_t nonframe_read = nullptr;  // the last reader of the step that is no frame (a producer's source, the histogram, the read-back)
+  bool nonframe_read_valid = false;
+  int *pass1_words = nullptr;       // eight ints the first pass of a producer INTO this slot reduces into (a derive's six extremes, a merge's maximum)
 };
 
 // One frame on its way to the host (smk_present.hip; DESIGN.md "Present"): everything a frame in flight needs that the
@@ -562,11 +563,8 @@ int smk_clip_slice_stage(smk_ctx *c, const RenderParams &P, hipStream_t s);
 int smk_step_wait_ready(smk_ctx *c, hipStream_t s);
 int smk_step_mark_used(smk_ctx *c, hipStream_t s);
 void smk_free_steps(smk_ctx *c);
-// the slot that holds time step `timestep` (an id, or SMK_STEP_CURRENT), or -1; and a read of slot k by a kernel on stream s
-// that is not a frame: _begin before it is enqueued, _end behind it (the slot's next writer waits for it)
+// the slot that holds time step `timestep` (an id, or SMK_STEP_CURRENT), or -1
 int smk_step_slot(const smk_ctx *c, int timestep);
-int smk_step_read_begin(smk_ctx *c, int k, hipStream_t s);
-int smk_step_read_end(smk_ctx *c, int k, hipStream_t s);
 // the slot of `timestep` for entry `who`, with the refusals that the histogram, the probe and the read-back of a step share
 __attribute__((visibility("hidden"))) int step_slot(smk_ctx *c, const char *who, int timestep, int *k);
 // a step of this context keeps its normals in a buffer of their own, TimeStep::nrm (smk_packed.h: four-channel f32)
@@ -575,11 +573,29 @@ inline bool smk_step_separate_normals(const smk_ctx *c) { return c->dtype == SMK
 inline size_t smk_step_nrm_bytes(const smk_ctx *c) { return smk_step_separate_normals(c) ? (size_t)c->D[0] * c->D[1] * c->D[2] * 4 : 0; }
 // the rows of this context's region in its stored box (smk_packed.h)
 inline StepRows smk_step_rows(const smk_ctx *c) { return step_rows(c->g0, c->g1, c->O, c->D, c->dtype == SMK_F32); }
-// A step written by kernels on stream s from what is on the device already (smk_blend_timesteps, smk_step_derive.hip).
-// _output_slot: the slot step `id` takes -- a cached id's own, else one by the ring's rule that is neither slot ka nor kb
-// (the sources; -1: none) nor the current step's; -1 when the ring has fewer than *need slots.  _write_begin: the kernels on s
-// are ordered behind the slot's last readers and writers, its buffers are made, it is marked empty.  _write_end: the slot
-// holds step `id`, its `ready` event is recorded on s, and a current step overwritten in place is switched to
-int smk_step_output_slot(const smk_ctx *c, int id, int ka, int kb, int *need);
-int smk_step_write_begin(smk_ctx *c, int k, hipStream_t s);
-int smk_step_write_end(smk_ctx *c, int k, int id, hipStream_t s);
+// Kernels on stream s that read or make resident steps and are no frame's: one bracket for all (smk_timesteps.hip, "Ordering").
+// _read_begin: s is ordered behind the writer of slot k and behind its last reader that is no frame.
+// _read: `launches` enqueues kernels that READ slots ka and kb (-1: none) behind their _read_begin; whatever it returns, the
+//   slots' read events are then recorded on s -- the one place where that is done --, so a slot's next writer waits for them.
+// _produce: entry `who` makes step `id` from slots ka and kb (the sources; -1: none), as a _read of them.  The output takes a
+//   cached id's own slot, else one by the ring's rule that is neither a source's nor the current step's: a ring of fewer slots
+//   than 1 + the distinct slots among the sources and the current step refuses the call.  s is ordered behind the output slot's
+//   old readers and writers, the slot is emptied and its buffers are made; `launches(out, a, b)` enqueues the kernels that fill
+//   `out` from the sources' slots (null: none); then the brick summaries are made, the slot holds step `id`, its `ready` event
+//   is recorded on s and a current step overwritten in place is switched to.  After a failed launch the slot stays empty.
+int smk_step_read_begin(smk_ctx *c, int k, hipStream_t s);
+#pragma GCC visibility push(hidden)
+int smk_step_read(smk_ctx *c, int ka, int kb, hipStream_t s, const std::function<int()> &launches);
+using StepLaunches = std::function<int(TimeStep &out, const TimeStep *a, const TimeStep *b)>;
+int smk_step_produce(smk_ctx *c, const char *who, int id, int ka, int kb, hipStream_t s, const StepLaunches &launches);
+// What the stencil producers (smk_step_derive.hip, smk_step_merge.hip) refuse before they look at their data, in this order:
+// no volume; a sharded context (sharded_why: the entry's reason); the series' nelts (nelts_why: the entry's refusal behind
+// "who: ", empty when they suit); a stored box that is not what the kernels take for granted; a volume without an interior
+// voxel (as prep_entry); then, with step_src (null: dense arrays), a source that is not cached (*ksrc: its slot), and the ids
+struct StencilEntry {
+  const char *who, *sharded_why;
+  std::string nelts_why;
+  const char *prep_entry;
+};
+int smk_step_stencil_refusals(smk_ctx *c, const StencilEntry &E, int step_out, const int *step_src, int *ksrc);
+#pragma GCC visibility pop

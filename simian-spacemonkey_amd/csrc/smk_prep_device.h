@@ -26,6 +26,10 @@ struct VghStats {  // ordered-int encoded
   int dmin, dmax, gmin, gmax, hmin, hmax;
 };
 
+// Where a kernel that makes a step inside the ring reads from, as its SRC template argument: dense arrays of a type (their
+// smk_dtype, 0..2), or the packed voxels of a slot of that type
+enum { SRC_PK_U8 = 3, SRC_PK_U16 = 4, SRC_PK_F32 = 5 };
+
 #define ORD_POS_INF 0x7f800000
 #define ORD_NEG_INF ((int)0x807fffff)  // f2o(-inf) = 0xff800000 ^ 0x7fffffff
 

@@ -11,7 +11,7 @@
 // a 2-voxel apron on every side: H reads the gradients of the six neighbours, each a central difference (2 voxels), and a
 // blurred normal reads the differences of the OUTPUT V channel at the 27 neighbours (2 voxels again).
 //   pass 1 (smk_k_derive_stats): gm, hs and the scalar of every interior voxel -> the six extremes, ordered-int atomics into
-//          the OUTPUT slot's words (TimeStep::derive_st), which a one-thread kernel seeded on the stream;
+//          the OUTPUT slot's words (TimeStep::pass1_words), which a one-thread kernel seeded on the stream;
 //   pass 2 (smk_k_derive_write): the reference's +-1e8 seeds applied to those words, the scaled V of every tile voxel (0 on the
 //          volume's border and outside it) into a second LDS tile, then per voxel gm and hs again, the scaling, the normal
 //          from the V tile, and one 8- or 16-byte store of the packed voxel.
@@ -23,8 +23,7 @@
 
 namespace {
 
-// where the scalar comes from: a dense array of a type (SRC is its smk_dtype), or channel 0 of a slot's packed voxels
-enum { DS_PK_U8 = 3, DS_PK_U16 = 4, DS_PK_F32 = 5 };
+// where the scalar comes from: a dense array of a type (SRC is its smk_dtype), or channel 0 of a slot's packed voxels (SRC_PK_*)
 
 constexpr int DV_TX = 32, DV_TY = 8, DV_TZ = 8, DV_AP = 2;
 constexpr int DV_LX = DV_TX + 2 * DV_AP, DV_LY = DV_TY + 2 * DV_AP, DV_LZ = DV_TZ + 2 * DV_AP;
@@ -37,14 +36,14 @@ struct DeriveParams {
   void *out;        // the output slot's packed voxels
   VghStats *st;     // the output slot's extremes
   int N[3], D[3];   // the volume; the stored box (origin 0: an unsharded context), D >= N with a pad column or row of 8-byte voxels.
-                    // The kernels rely on D[2] == N[2], on D == N for f32 voxels and on an even D[0] otherwise: derive_refusals checks
+                    // The kernels rely on D[2] == N[2], on D == N for f32 voxels and on an even D[0] otherwise: smk_step_stencil_refusals checks
   int compat, blur, normals;
 };
 
 // the tile of the scalar around (x0, y0, z0), apron included; what lies outside the volume is not data: 0, and never used
 template <int SRC>
 __device__ __forceinline__ void dv_load_tile(const DeriveParams &P, int x0, int y0, int z0, float *S) {
-  if (SRC == DS_PK_U8 || SRC == DS_PK_U16) {  // two 8-byte voxels per 16-byte unit (x0 - DV_AP is even, and so is D[0])
+  if (SRC == SRC_PK_U8 || SRC == SRC_PK_U16) {  // two 8-byte voxels per 16-byte unit (x0 - DV_AP is even, and so is D[0])
     constexpr int UPR = DV_LX / 2;
     for (int u = threadIdx.x; u < UPR * DV_LY * DV_LZ; u += 256) {
       const int cu = u % UPR, row = u / UPR, ly = row % DV_LY, lz = row / DV_LY;
@@ -52,7 +51,7 @@ __device__ __forceinline__ void dv_load_tile(const DeriveParams &P, int x0, int 
       float a = 0.f, b = 0.f;
       if (X >= 0 && X < P.N[0] && Y >= 0 && Y < P.N[1] && Z >= 0 && Z < P.N[2]) {
         const uint4 v = ((const uint4 *)P.src)[(((size_t)Z * P.D[1] + Y) * P.D[0] + X) >> 1];
-        constexpr int DT = SRC == DS_PK_U8 ? SMK_U8 : SMK_U16;
+        constexpr int DT = SRC == SRC_PK_U8 ? SMK_U8 : SMK_U16;
         a = (float)smk_vox8_c0<DT>(v.x);
         if (X + 1 < P.N[0]) b = (float)smk_vox8_c0<DT>(v.z);
       }
@@ -65,7 +64,7 @@ __device__ __forceinline__ void dv_load_tile(const DeriveParams &P, int x0, int 
       const int X = x0 - DV_AP + lx, Y = y0 - DV_AP + ly, Z = z0 - DV_AP + lz;
       float a = 0.f;
       if (X >= 0 && X < P.N[0] && Y >= 0 && Y < P.N[1] && Z >= 0 && Z < P.N[2]) {
-        if (SRC == DS_PK_F32) {
+        if (SRC == SRC_PK_F32) {
           a = __uint_as_float(((const uint4 *)P.src)[((size_t)Z * P.D[1] + Y) * P.D[0] + X].x);
         } else {
           const size_t o = ((size_t)Z * P.N[1] + Y) * P.N[0] + X;
@@ -223,64 +222,40 @@ hipError_t launch_derive(const DeriveParams &P, int out_dtype, hipStream_t s) {
   return hipGetLastError();
 }
 
-// what both entries refuse before they look at their source
-int derive_refusals(smk_ctx *c, const char *who) {
-  if (!c->have_volume) FAIL(c, "%s: no volume uploaded", who);
-  if (c->nranks > 1)
-    FAIL(c, "%s: a sharded context (%d ranks): the stencil reaches 2 voxels beyond a voxel and the scaling needs the whole volume's "
-            "extremes; neither fits region + halo", who, c->nranks);
-  if (c->nelts != 3) FAIL(c, "%s: the series has nelts %d: V, G and H are three channels (nelts 3)", who, c->nelts);
-  // what the kernels take for granted of an unsharded context's stored box (smk_volume_geometry): it starts at voxel 0, is
-  // the volume in z, and is wider than the volume only by the pad column and row of 8-byte voxels
-  const bool wide = c->dtype == SMK_F32;
-  if (c->O[0] || c->O[1] || c->O[2] || c->D[2] != c->N[2] || c->D[0] < c->N[0] || c->D[1] < c->N[1] || c->D[0] > c->N[0] + 1 ||
-      c->D[1] > c->N[1] + 1 || (wide && (c->D[0] != c->N[0] || c->D[1] != c->N[1])) || (!wide && (c->D[0] & 1)))
-    FAIL(c, "%s: internal: the stored box %dx%dx%d at %d,%d,%d is not the volume %dx%dx%d with its pad", who, c->D[0], c->D[1], c->D[2], c->O[0],
-         c->O[1], c->O[2], c->N[0], c->N[1], c->N[2]);
-  if (c->N[0] < 3 || c->N[1] < 3 || c->N[2] < 3)
-    FAIL(c, "%s: a %dx%dx%d volume has no interior voxel (dims >= 3, as smk_make_vgh_device)", who, c->N[0], c->N[1], c->N[2]);
-  return 0;
+// what both entries refuse before they look at their data (smk_step_stencil_refusals)
+StencilEntry derive_entry(const smk_ctx *c, const char *who) {
+  char nelts_why[96] = "";
+  if (c->nelts != 3) snprintf(nelts_why, sizeof nelts_why, "the series has nelts %d: V, G and H are three channels (nelts 3)", c->nelts);
+  return {who, "the stencil reaches 2 voxels beyond a voxel and the scaling needs the whole volume's extremes; neither fits region + halo",
+          nelts_why, "smk_make_vgh_device"};
 }
 
-// the two passes, the brick summaries and the bookkeeping of the output step; ksrc: the source slot, or -1 (a dense scalar)
+// the two passes inside the producer frame; ksrc: the source slot, or -1 (a dense scalar)
 int derive_enqueue(smk_ctx *c, const char *who, int kind, const void *src, int ksrc, int step_out, int compat, int blur, hipStream_t s) {
-  int need = 0;
-  const int k = smk_step_output_slot(c, step_out, ksrc, -1, &need);
-  if (k < 0) {
-    if (ksrc >= 0)
-      FAIL(c, "%s: the cache holds %d steps: the source and the output need two slots, three when the current step (%d) is a third "
-              "(here %d); smk_set_timestep_cache sets more", who, (int)c->ts.size(), c->ts_cur_id, need);
-    FAIL(c, "%s: time step %d: the cache holds one step, the current one (%d); smk_set_timestep_cache sets more", who, step_out, c->ts_cur_id);
-  }
-  if (smk_step_write_begin(c, k, s)) return 1;
-  c->ts_series = true;
-  if (ksrc >= 0 && smk_step_read_begin(c, ksrc, s)) return 1;
-  TimeStep &T = c->ts[(size_t)k];
-  DeriveParams P;
-  P.src = ksrc >= 0 ? c->ts[(size_t)ksrc].vox : src;
-  P.out = T.vox;
-  P.st = (VghStats *)T.derive_st;
-  for (int a = 0; a < 3; ++a) {
-    P.N[a] = c->N[a];
-    P.D[a] = c->D[a];
-  }
-  P.compat = compat ? 1 : 0;
-  P.blur = blur ? 1 : 0;
-  P.normals = c->have_normals ? 1 : 0;
-  hipError_t e;
-  switch (kind) {
-    case SMK_U8: e = launch_derive<SMK_U8>(P, c->dtype, s); break;
-    case SMK_F32: e = launch_derive<SMK_F32>(P, c->dtype, s); break;
-    case SMK_U16: e = launch_derive<SMK_U16>(P, c->dtype, s); break;
-    case DS_PK_U8: e = launch_derive<DS_PK_U8>(P, c->dtype, s); break;
-    case DS_PK_U16: e = launch_derive<DS_PK_U16>(P, c->dtype, s); break;
-    default: e = launch_derive<DS_PK_F32>(P, c->dtype, s); break;
-  }
-  HIPCHK(c, e);
-  HIPCHK(c, smk_bricks_minmax(T.vox, c->dtype, c->D, c->nbr, T.mm, s));
-  if (smk_step_write_end(c, k, step_out, s)) return 1;
-  if (ksrc >= 0 && smk_step_read_end(c, ksrc, s)) return 1;  // whatever overwrites the source slot comes after these reads
-  return 0;
+  return smk_step_produce(c, who, step_out, ksrc, -1, s, [&](TimeStep &T, const TimeStep *S, const TimeStep *) -> int {
+    DeriveParams P;
+    P.src = S ? S->vox : src;
+    P.out = T.vox;
+    P.st = (VghStats *)T.pass1_words;
+    for (int a = 0; a < 3; ++a) {
+      P.N[a] = c->N[a];
+      P.D[a] = c->D[a];
+    }
+    P.compat = compat ? 1 : 0;
+    P.blur = blur ? 1 : 0;
+    P.normals = c->have_normals ? 1 : 0;
+    hipError_t e;
+    switch (kind) {
+      case SMK_U8: e = launch_derive<SMK_U8>(P, c->dtype, s); break;
+      case SMK_F32: e = launch_derive<SMK_F32>(P, c->dtype, s); break;
+      case SMK_U16: e = launch_derive<SMK_U16>(P, c->dtype, s); break;
+      case SRC_PK_U8: e = launch_derive<SRC_PK_U8>(P, c->dtype, s); break;
+      case SRC_PK_U16: e = launch_derive<SRC_PK_U16>(P, c->dtype, s); break;
+      default: e = launch_derive<SRC_PK_F32>(P, c->dtype, s); break;
+    }
+    HIPCHK(c, e);
+    return 0;
+  });
 }
 
 }  // namespace
@@ -289,12 +264,9 @@ extern "C" int smk_derive_timestep(smk_ctx *c, int step_src, int step_out, int c
   if (!c) return 1;
   const char *who = "smk_derive_timestep";
   HIPCHK(c, hipSetDevice(c->device));
-  if (derive_refusals(c, who)) return 1;
-  const int ksrc = step_src < 0 ? -1 : smk_step_slot(c, step_src);
-  if (ksrc < 0) FAIL(c, "%s: time step %d (the source) is not cached", who, step_src);
-  if (step_out < 0) FAIL(c, "%s: output time step %d: ids are >= 0", who, step_out);
-  if (step_out == step_src) FAIL(c, "%s: output time step %d is also the source: the stencil has no in-place form", who, step_out);
-  const int kind = c->dtype == SMK_U8 ? DS_PK_U8 : c->dtype == SMK_U16 ? DS_PK_U16 : DS_PK_F32;
+  int ksrc = -1;
+  if (smk_step_stencil_refusals(c, derive_entry(c, who), step_out, &step_src, &ksrc)) return 1;
+  const int kind = c->dtype == SMK_U8 ? SRC_PK_U8 : c->dtype == SMK_U16 ? SRC_PK_U16 : SRC_PK_F32;
   return derive_enqueue(c, who, kind, nullptr, ksrc, step_out, compat, blur, stream ? (hipStream_t)stream : c->stream);
 }
 
@@ -303,8 +275,7 @@ extern "C" int smk_upload_timestep_scalar_device(smk_ctx *c, int timestep, const
   if (!c) return 1;
   const char *who = "smk_upload_timestep_scalar_device";
   HIPCHK(c, hipSetDevice(c->device));
-  if (derive_refusals(c, who)) return 1;
-  if (timestep < 0) FAIL(c, "%s: time step %d: ids are >= 0", who, timestep);
+  if (smk_step_stencil_refusals(c, derive_entry(c, who), timestep, nullptr, nullptr)) return 1;
   if (!d_scalar) FAIL(c, "%s: d_scalar is NULL", who);
   if (scalar_dtype != SMK_U8 && scalar_dtype != SMK_U16 && scalar_dtype != SMK_F32)
     FAIL(c, "%s: scalar_dtype %d is none of SMK_U8, SMK_U16, SMK_F32", who, (int)scalar_dtype);

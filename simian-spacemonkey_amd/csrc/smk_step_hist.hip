@@ -159,13 +159,13 @@ int hist_enqueue(smk_ctx *c, const char *who, int timestep, void *d_counts, hipS
   P.R = smk_step_rows(c);
   if (!P.R.units) FAIL(c, "%s: this context's region is empty", who);
   if ((unsigned long long)P.R.upr + HIST_CHUNK > 0xffffffffull) FAIL(c, "%s: rows of %u voxels are too long", who, P.R.nx);
-  // behind the step's upload or blend; what overwrites the slot later waits for this read (smk_timesteps.hip)
-  if (smk_step_read_begin(c, k, s)) return 1;
-  HIPCHK(c, hipMemsetAsync(d_counts, 0, 65536 * sizeof(unsigned), s));
-  if (c->dtype == SMK_U8) HIPCHK(c, launch_step_hist<SMK_U8>(P, c->device, s));
-  else if (c->dtype == SMK_U16) HIPCHK(c, launch_step_hist<SMK_U16>(P, c->device, s));
-  else HIPCHK(c, launch_step_hist<SMK_F32>(P, c->device, s));
-  return smk_step_read_end(c, k, s);
+  // behind the step's writer; what overwrites the slot later waits for this read (smk_timesteps.hip)
+  return smk_step_read(c, k, -1, s, [&]() -> int {
+    HIPCHK(c, hipMemsetAsync(d_counts, 0, 65536 * sizeof(unsigned), s));
+    HIPCHK(c, c->dtype == SMK_U8    ? launch_step_hist<SMK_U8>(P, c->device, s)
+              : c->dtype == SMK_U16 ? launch_step_hist<SMK_U16>(P, c->device, s) : launch_step_hist<SMK_F32>(P, c->device, s));
+    return 0;
+  });
 }
 
 }  // namespace

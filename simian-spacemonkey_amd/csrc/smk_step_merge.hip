@@ -12,7 +12,7 @@
 // marches through the slices of its tile, a workgroup MG_UX units of MG_TY rows of MG_TZ slices (mg_march).  A packed source
 // is read in whole units.
 //   pass 1 (smk_k_merge_max):   the magnitude of the summed gradient of every interior voxel -> its maximum (u8: of all, float
-//          rings: of the finite ones), one ordered-int atomicMax per wave into the OUTPUT slot's word (TimeStep::derive_st),
+//          rings: of the finite ones), one ordered-int atomicMax per wave into the OUTPUT slot's word (TimeStep::pass1_words),
 //          which a one-lane kernel seeded on the stream; a capped grid strides over the tiles;
 //   pass 2 (smk_k_merge_write): the gradient again, G and the normal, and one 16-byte store of the unit (and the normal word of
 //          a four-channel f32 voxel).
@@ -24,8 +24,7 @@
 
 namespace {
 
-// where the fields come from: dense arrays of a type (SRC is their smk_dtype), or the channels of a slot's packed voxels
-enum { MS_PK_U8 = 3, MS_PK_U16 = 4, MS_PK_F32 = 5 };
+// where the fields come from: dense arrays of a type (SRC is their smk_dtype), or the channels of a slot's packed voxels (SRC_PK_*)
 
 constexpr int MG_UX = 64, MG_TY = 4, MG_TZ = 4;  // a workgroup's tile: units in x (a wave per row), rows, slices
 static_assert(MG_UX * MG_TY == 256, "a lane per unit of a slice of the tile");
@@ -43,7 +42,7 @@ struct MergeParams {
   int ux, uy, ntiles;  // tiles per row of tiles, per slice of tiles, in all
 };
 
-constexpr int mg_ring(int SRC) { return SRC == MS_PK_U8 ? SMK_U8 : SRC == MS_PK_U16 ? SMK_U16 : SRC == MS_PK_F32 ? SMK_F32 : SRC; }
+constexpr int mg_ring(int SRC) { return SRC == SRC_PK_U8 ? SMK_U8 : SRC == SRC_PK_U16 ? SMK_U16 : SRC == SRC_PK_F32 ? SMK_F32 : SRC; }
 constexpr int mg_vpu(int SRC) { return mg_ring(SRC) == SMK_F32 ? 1 : 2;  }  // voxels per 16-byte unit
 
 // The fields of the voxels of unit U of row Y of slice Z as they are stored -- a byte, a 16-bit value or a float's word each --:
@@ -57,18 +56,18 @@ __device__ __forceinline__ void mg_cell(const MergeParams &P, int U, int Y, int 
 #pragma unroll
     for (int e = 0; e < NF; ++e) r[c][e] = 0u;
   if (U < 0 || U * VPU >= P.D[0] || Y < 0 || Y >= P.D[1] || Z < 0 || Z >= P.D[2]) return;
-  if (SRC == MS_PK_F32) {
+  if (SRC == SRC_PK_F32) {
     const uint4 v = ((const uint4 *)P.src)[((size_t)Z * P.D[1] + Y) * P.D[0] + U];
 #pragma unroll
     for (int e = 0; e < NF; ++e) r[0][e] = e == 0 ? v.x : e == 1 ? v.y : v.z;
-  } else if (SRC == MS_PK_U8 || SRC == MS_PK_U16) {  // two voxels (D[0] is even): their first words are .x and .z
+  } else if (SRC == SRC_PK_U8 || SRC == SRC_PK_U16) {  // two voxels (D[0] is even): their first words are .x and .z
     const uint4 v = ((const uint4 *)P.src)[((size_t)Z * P.D[1] + Y) * (size_t)(P.D[0] >> 1) + U];
 #pragma unroll
     for (int c = 0; c < VPU; ++c) {
       const uint32_t w0 = c ? v.z : v.x;
 #pragma unroll
       for (int e = 0; e < NF; ++e)
-        r[c][e] = SRC == MS_PK_U8 ? smk_u8_ch(w0, e) : e == 0 ? smk_vox8_c0<SMK_U16>(w0) : smk_vox8_c1<SMK_U16>(w0);
+        r[c][e] = SRC == SRC_PK_U8 ? smk_u8_ch(w0, e) : e == 0 ? smk_vox8_c0<SMK_U16>(w0) : smk_vox8_c1<SMK_U16>(w0);
     }
   } else {  // dense fields, read at their element size
     if (Y >= P.N[1]) return;
@@ -259,77 +258,54 @@ template <int SRC>
 hipError_t launch_merge_nf(const MergeParams &P, int nf, hipStream_t s) {
   if (nf == 1) return launch_merge<SRC, 1>(P, s);
   if (nf == 2) return launch_merge<SRC, 2>(P, s);
-  if constexpr (mg_ring(SRC) != SMK_U16) {  // (a u16 voxel holds three channels: merge_refusals)
+  if constexpr (mg_ring(SRC) != SMK_U16) {  // (a u16 voxel holds three channels: merge_entry)
     if (nf == 3) return launch_merge<SRC, 3>(P, s);
   }
   return hipErrorInvalidValue;
 }
 
-// what both entries refuse before they look at their source
-int merge_refusals(smk_ctx *c, const char *who) {
-  if (!c->have_volume) FAIL(c, "%s: no volume uploaded", who);
-  if (c->nranks > 1)
-    FAIL(c, "%s: a sharded context (%d ranks): the stencil reaches 1 voxel beyond region + halo, and G is scaled by the whole "
-            "volume's maximum", who, c->nranks);
-  if (c->nelts < 2) FAIL(c, "%s: the series has nelts %d: a multi-field step is at least one field and G (nelts >= 2)", who, c->nelts);
+// what both entries refuse before they look at their data (smk_step_stencil_refusals)
+StencilEntry merge_entry(const smk_ctx *c, const char *who) {
+  char nelts_why[112] = "";
   const int top = c->dtype == SMK_U16 ? 3 : 4;
-  if (c->nelts > top) FAIL(c, "%s: internal: nelts %d of a voxel type that holds %d channels", who, c->nelts, top);
-  // what the kernels take for granted of an unsharded context's stored box (smk_volume_geometry): it starts at voxel 0, is
-  // the volume in z, and is wider than the volume only by the pad column and row of 8-byte voxels
-  const bool wide = c->dtype == SMK_F32;
-  if (c->O[0] || c->O[1] || c->O[2] || c->D[2] != c->N[2] || c->D[0] < c->N[0] || c->D[1] < c->N[1] || c->D[0] > c->N[0] + 1 ||
-      c->D[1] > c->N[1] + 1 || (wide && (c->D[0] != c->N[0] || c->D[1] != c->N[1])) || (!wide && (c->D[0] & 1)))
-    FAIL(c, "%s: internal: the stored box %dx%dx%d at %d,%d,%d is not the volume %dx%dx%d with its pad", who, c->D[0], c->D[1], c->D[2], c->O[0],
-         c->O[1], c->O[2], c->N[0], c->N[1], c->N[2]);
-  if (c->N[0] < 3 || c->N[1] < 3 || c->N[2] < 3)
-    FAIL(c, "%s: a %dx%dx%d volume has no interior voxel (dims >= 3, as smk_merge_fields_device)", who, c->N[0], c->N[1], c->N[2]);
-  return 0;
+  if (c->nelts < 2) snprintf(nelts_why, sizeof nelts_why, "the series has nelts %d: a multi-field step is at least one field and G (nelts >= 2)", c->nelts);
+  else if (c->nelts > top) snprintf(nelts_why, sizeof nelts_why, "internal: nelts %d of a voxel type that holds %d channels", c->nelts, top);
+  return {who, "the stencil reaches 1 voxel beyond region + halo, and G is scaled by the whole volume's maximum", nelts_why,
+          "smk_merge_fields_device"};
 }
 
-// the two passes, the brick summaries and the bookkeeping of the output step; ksrc: the source slot, or -1 (dense fields)
+// the two passes inside the producer frame; ksrc: the source slot, or -1 (dense fields)
 int merge_enqueue(smk_ctx *c, const char *who, const void *const *fields, int ksrc, int step_out, hipStream_t s) {
-  int need = 0;
-  const int k = smk_step_output_slot(c, step_out, ksrc, -1, &need);
-  if (k < 0) {
-    if (ksrc >= 0)
-      FAIL(c, "%s: the cache holds %d steps: the source and the output need two slots, three when the current step (%d) is a third "
-              "(here %d); smk_set_timestep_cache sets more", who, (int)c->ts.size(), c->ts_cur_id, need);
-    FAIL(c, "%s: time step %d: the cache holds one step, the current one (%d); smk_set_timestep_cache sets more", who, step_out, c->ts_cur_id);
-  }
   const int VPU = c->dtype == SMK_F32 ? 1 : 2, nf = c->nelts - 1;
   const long long ux = (c->D[0] / VPU + MG_UX - 1) / MG_UX, uy = (c->D[1] + MG_TY - 1) / MG_TY, uz = (c->D[2] + MG_TZ - 1) / MG_TZ;
-  if (ux * uy * uz > 0x7fffffffLL) FAIL(c, "%s: a %dx%dx%d volume has more than 2^31 tiles", who, c->N[0], c->N[1], c->N[2]);
-  if (smk_step_write_begin(c, k, s)) return 1;
-  c->ts_series = true;
-  if (ksrc >= 0 && smk_step_read_begin(c, ksrc, s)) return 1;
-  TimeStep &T = c->ts[(size_t)k];
-  MergeParams P;
-  P.src = ksrc >= 0 ? c->ts[(size_t)ksrc].vox : nullptr;
-  for (int e = 0; e < 3; ++e) P.f[e] = fields && e < nf ? fields[e] : nullptr;
-  P.out = T.vox;
-  P.nrm = smk_step_separate_normals(c) ? T.nrm : nullptr;
-  P.mx = T.derive_st;
-  for (int a = 0; a < 3; ++a) {
-    P.N[a] = c->N[a];
-    P.D[a] = c->D[a];
-  }
-  P.normals = c->have_normals ? 1 : 0;
-  P.ux = (int)ux;
-  P.uy = (int)(ux * uy);
-  P.ntiles = (int)(ux * uy * uz);
-  hipError_t e;
-  if (ksrc >= 0) {
-    e = c->dtype == SMK_U8 ? launch_merge_nf<MS_PK_U8>(P, nf, s) : c->dtype == SMK_U16 ? launch_merge_nf<MS_PK_U16>(P, nf, s)
-                                                                                          : launch_merge_nf<MS_PK_F32>(P, nf, s);
-  } else {
-    e = c->dtype == SMK_U8 ? launch_merge_nf<SMK_U8>(P, nf, s) : c->dtype == SMK_U16 ? launch_merge_nf<SMK_U16>(P, nf, s)
-                                                                                        : launch_merge_nf<SMK_F32>(P, nf, s);
-  }
-  HIPCHK(c, e);
-  HIPCHK(c, smk_bricks_minmax(T.vox, c->dtype, c->D, c->nbr, T.mm, s));
-  if (smk_step_write_end(c, k, step_out, s)) return 1;
-  if (ksrc >= 0 && smk_step_read_end(c, ksrc, s)) return 1;  // whatever overwrites the source slot comes after these reads
-  return 0;
+  if (ux * uy * uz > 0x7fffffffLL)  // (2^42 voxels: no ring holds such a step, so its place before the frame's refusal is moot)
+    FAIL(c, "%s: a %dx%dx%d volume has more than 2^31 tiles", who, c->N[0], c->N[1], c->N[2]);
+  return smk_step_produce(c, who, step_out, ksrc, -1, s, [&](TimeStep &T, const TimeStep *S, const TimeStep *) -> int {
+    MergeParams P;
+    P.src = S ? S->vox : nullptr;
+    for (int e = 0; e < 3; ++e) P.f[e] = fields && e < nf ? fields[e] : nullptr;
+    P.out = T.vox;
+    P.nrm = smk_step_separate_normals(c) ? T.nrm : nullptr;
+    P.mx = T.pass1_words;
+    for (int a = 0; a < 3; ++a) {
+      P.N[a] = c->N[a];
+      P.D[a] = c->D[a];
+    }
+    P.normals = c->have_normals ? 1 : 0;
+    P.ux = (int)ux;
+    P.uy = (int)(ux * uy);
+    P.ntiles = (int)(ux * uy * uz);
+    hipError_t e;
+    if (S) {
+      e = c->dtype == SMK_U8 ? launch_merge_nf<SRC_PK_U8>(P, nf, s) : c->dtype == SMK_U16 ? launch_merge_nf<SRC_PK_U16>(P, nf, s)
+                                                                                             : launch_merge_nf<SRC_PK_F32>(P, nf, s);
+    } else {
+      e = c->dtype == SMK_U8 ? launch_merge_nf<SMK_U8>(P, nf, s) : c->dtype == SMK_U16 ? launch_merge_nf<SMK_U16>(P, nf, s)
+                                                                                          : launch_merge_nf<SMK_F32>(P, nf, s);
+    }
+    HIPCHK(c, e);
+    return 0;
+  });
 }
 
 }  // namespace
@@ -338,11 +314,8 @@ extern "C" int smk_merge_timestep(smk_ctx *c, int step_src, int step_out, void *
   if (!c) return 1;
   const char *who = "smk_merge_timestep";
   HIPCHK(c, hipSetDevice(c->device));
-  if (merge_refusals(c, who)) return 1;
-  const int ksrc = step_src < 0 ? -1 : smk_step_slot(c, step_src);
-  if (ksrc < 0) FAIL(c, "%s: time step %d (the source) is not cached", who, step_src);
-  if (step_out < 0) FAIL(c, "%s: output time step %d: ids are >= 0", who, step_out);
-  if (step_out == step_src) FAIL(c, "%s: output time step %d is also the source: the stencil has no in-place form", who, step_out);
+  int ksrc = -1;
+  if (smk_step_stencil_refusals(c, merge_entry(c, who), step_out, &step_src, &ksrc)) return 1;
   return merge_enqueue(c, who, nullptr, ksrc, step_out, stream ? (hipStream_t)stream : c->stream);
 }
 
@@ -351,8 +324,7 @@ extern "C" int smk_upload_timestep_fields_device(smk_ctx *c, int timestep, const
   if (!c) return 1;
   const char *who = "smk_upload_timestep_fields_device";
   HIPCHK(c, hipSetDevice(c->device));
-  if (merge_refusals(c, who)) return 1;
-  if (timestep < 0) FAIL(c, "%s: time step %d: ids are >= 0", who, timestep);
+  if (smk_step_stencil_refusals(c, merge_entry(c, who), timestep, nullptr, nullptr)) return 1;
   if (!d_fields) FAIL(c, "%s: d_fields is NULL", who);
   if (nf != c->nelts - 1) FAIL(c, "%s: %d fields for a series of nelts %d: the fields are nelts - 1 = %d", who, nf, c->nelts, c->nelts - 1);
   if ((int)field_dtype != c->dtype)

@@ -198,12 +198,11 @@ int read_enqueue(smk_ctx *c, const char *who, int k, void *d_data, void *d_grad,
   P.R = smk_step_rows(c);
   P.nelts = (unsigned)c->nelts;
   if (!P.R.units) FAIL(c, "%s: this context's region is empty", who);
-  // behind the step's upload or blend; what overwrites the slot later waits for this read (smk_timesteps.hip)
-  if (smk_step_read_begin(c, k, s)) return 1;
-  if (c->dtype == SMK_U8) HIPCHK(c, launch_unpack<SMK_U8>(P, s));
-  else if (c->dtype == SMK_U16) HIPCHK(c, launch_unpack<SMK_U16>(P, s));
-  else HIPCHK(c, launch_unpack<SMK_F32>(P, s));
-  return smk_step_read_end(c, k, s);
+  // behind the step's writer; what overwrites the slot later waits for this read (smk_timesteps.hip)
+  return smk_step_read(c, k, -1, s, [&]() -> int {
+    HIPCHK(c, c->dtype == SMK_U8 ? launch_unpack<SMK_U8>(P, s) : c->dtype == SMK_U16 ? launch_unpack<SMK_U16>(P, s) : launch_unpack<SMK_F32>(P, s));
+    return 0;
+  });
 }
 
 }  // namespace
