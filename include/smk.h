@@ -214,6 +214,60 @@ int smk_merge_timestep(smk_ctx *ctx, int step_src, int step_out, void *stream);
  * that are not the series'. */
 int smk_upload_timestep_fields_device(smk_ctx *ctx, int timestep, const void *const *d_fields, int nf, smk_dtype field_dtype,
                                       int sx, int sy, int sz, void *stream);
+/* The two stencil producers on a SHARDED context (smk_set_shard), in two calls with one exchange of eight integers between
+ * them; no voxel moves between ranks.  smk_derive_timestep and smk_merge_timestep above refuse a sharded context for two
+ * reasons, and both go:
+ *   - the extremes the result is scaled by are minima and maxima, which decompose exactly over the ranks' regions: every rank
+ *     EXPORTS those of its region (smk_step_extremes_device), the host combines the ranks' words by elementwise integer
+ *     maximum -- in-process ranks directly, a multi-process host with one integer MAX all-reduce of 8 words on its own
+ *     transport --, and every rank runs the write pass with the combined words (smk_*_timestep_shard);
+ *   - the stencil reaches r voxels (r = 2 for the derive, blurred or not; r = 1 for the merge), and option "halo" lets a
+ *     context keep that many and more.
+ * THE WORDS.  Eight int32 in device memory.  A float x travels as its ordered int ord(x) = bits >= 0 ? bits : bits ^ 0x7fffffff
+ * (ascending with x), and every MINIMUM as the bitwise complement of that, so that all eight words combine by maximum:
+ *   SMK_EXTREMES_DERIVE  {~ord(min V), ord(max V), ~ord(min G), ord(max G), ~ord(min H), ord(max H), INT_MIN, INT_MIN}
+ *                        over the region's interior voxels of the volume (V the source's channel 0, G and H the unscaled
+ *                        gradient magnitude and second derivative; a NaN H is skipped), before the reference's +-1e8 seeds;
+ *                        a region without an interior voxel exports the seeds {~ord(+inf), ord(-inf)} x 3
+ *   SMK_EXTREMES_MERGE   {ord(max magnitude), INT_MIN x 7}: of the summed gradient over the region's interior voxels (a u8
+ *                        ring: of all magnitudes; u16 and f32: of the finite ones); the seed is ord(0.0f) = 0
+ * The maximum over the ranks' words equals, bit for bit, the words an unsharded context exports for the same step.
+ * THE VALID BOX.  The result is exact on the stored box cut at the volume and then shrunk by r at every face that is not a
+ * face of the volume (a face is the volume's when the stored box starts at voxel 0 or ends at or beyond the volume's last):
+ * there every stored field and normal byte is what smk_derive_timestep / smk_merge_timestep store at that voxel on an
+ * unsharded context -- the 1-voxel border (decided on the volume's coordinates) and the pad column and row included.  The
+ * other stored voxels, the RIM, are written as zeros with the normal (128, 128, 128); zeros can only widen a brick's summary
+ * range, so empty-space skipping stays conservative.  A source that has a rim itself (a second stencil) shrinks from its own
+ * valid box.
+ * THE VALID HALO.  Every cached step carries the number of halo voxels round the region that are exact: option "halo" after
+ * an upload, the smaller of the sources' after a blend, the source's less r after these entries (on every rank of a
+ * sharded series alike; unchanged on an unsharded context, which has no halo to lose).  smk_get_timestep_halo reads it.
+ * A frame with perturbation or shadows on a shard compares its need with the SHOWN step's valid halo, and smk_probe_step
+ * answers cells inside the step's valid box only.
+ *
+ * smk_step_extremes_device: pass 1 of the derive (`compat` as smk_derive_timestep's) or of the merge (`compat` ignored) over
+ * this context's REGION of the cached step `step_src`, into the eight words at `d_words` (device memory, 4-byte aligned,
+ * overwritten).  A reader of the step, ordered as smk_hist2d_step_device: enqueued on `stream` (NULL = the context's) behind
+ * the step's writer; what overwrites the step later waits for it.  No host synchronisation, no allocation.  Refused, with the
+ * reason: an unknown kind; d_words NULL or misaligned; no volume; the series' nelts (3 for the derive, >= 2 for the merge);
+ * a volume thinner than 3 voxels; step_src not cached; a source whose valid halo is below r + 1 on a sharded context (the
+ * message names both numbers). */
+enum { SMK_EXTREMES_DERIVE = 0, SMK_EXTREMES_MERGE = 1 };
+int smk_step_extremes_device(smk_ctx *ctx, int kind, int step_src, int compat, void *d_words, void *stream);
+/* The write pass alone: step `step_out` becomes the VGH step (derive) or the multi-field step (merge) of the cached step
+ * `step_src`, scaled by the extremes in the eight words at `d_words` (device memory, read by the kernels on `stream`: the
+ * caller orders its combine before them).  The words are NOT validated: words that are not the combined exports of this
+ * step give a step scaled by whatever they say.  Producers like the one-call entries: the same slot rule (a cached step_out
+ * is overwritten in place, otherwise a slot that is neither the source's nor the current step's), the same ordering on
+ * `stream`, brick summaries for the result, no host synchronisation, no allocation.  They run on an unsharded context too:
+ * there export + _shard stores the bits of smk_derive_timestep / smk_merge_timestep.  Refused, with the reason, changing
+ * nothing: what smk_step_extremes_device refuses for the step; step_out < 0; step_out == step_src; no slot for the output
+ * (the message names the slots needed).  The valid halo must be r + 1 because the result has to keep one halo voxel for a
+ * frame's trilinear fetch. */
+int smk_derive_timestep_shard(smk_ctx *ctx, int step_src, int step_out, int compat, int blur, const void *d_words, void *stream);
+int smk_merge_timestep_shard(smk_ctx *ctx, int step_src, int step_out, const void *d_words, void *stream);
+/* the valid halo of cached step `timestep` (an id, or SMK_STEP_CURRENT) */
+int smk_get_timestep_halo(smk_ctx *ctx, int timestep, int *valid_halo);
 /* introspection: the current step (-1: no volume), the cached ids oldest written first (min(cap, *n) of them; ids_out may
  * be NULL), their number */
 int smk_get_timesteps(smk_ctx *ctx, int *current, int *ids_out, int cap, int *n);

@@ -32,6 +32,7 @@ ABI_SYMBOLS = [
     "smk_set_timestep_cache", "smk_upload_timestep", "smk_upload_timestep_device", "smk_select_timestep",
     "smk_get_timesteps", "smk_blend_timesteps", "smk_derive_timestep", "smk_upload_timestep_scalar_device",
     "smk_merge_timestep", "smk_upload_timestep_fields_device",
+    "smk_step_extremes_device", "smk_derive_timestep_shard", "smk_merge_timestep_shard", "smk_get_timestep_halo",
     "smk_composite_over_depth_device", "smk_exchange_partial_depth", "smk_exchange_frame_depth", "smk_exchange_frame_local_depth",
     "smk_render_occluded", "smk_render_occluded_device",
     "smk_set_clip_slice",
@@ -40,6 +41,7 @@ ABI_SYMBOLS = [
     "smk_get_timestep_box", "smk_download_timestep_device", "smk_download_timestep",
 ]
 STEP_CURRENT = -1  # SMK_STEP_CURRENT: the step the frames render
+EXTREMES_DERIVE, EXTREMES_MERGE = 0, 1  # SMK_EXTREMES_*: the kind of smk_step_extremes_device
 
 # gluvvDataMode order (gluvv.h:221-235)
 GDM = {n: i for i, n in enumerate(
@@ -143,6 +145,10 @@ def load_library():
     L.smk_upload_timestep_scalar_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                                     C.c_int, C.c_int, C.c_void_p]
     L.smk_merge_timestep.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.smk_step_extremes_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.smk_derive_timestep_shard.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.smk_merge_timestep_shard.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.smk_get_timestep_halo.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     L.smk_upload_timestep_fields_device.argtypes = [C.c_void_p, C.c_int, P(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int,
                                                     C.c_int, C.c_void_p]
     L.smk_set_shard.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -401,6 +407,29 @@ class Renderer:
         arr = None if ptrs is None else (C.c_void_p * max(len(ptrs), 1))(*ptrs)
         self._ck(self.L.smk_upload_timestep_fields_device(self.ctx, int(timestep), arr, 0 if ptrs is None else len(ptrs), int(dtype),
                                                           int(dims[0]), int(dims[1]), int(dims[2]), stream))
+
+    # -- the stencil producers on a shard (smk.h: smk_step_extremes_device ...): export, combine by integer maximum, write
+    def step_extremes_device(self, kind, src, d_words, compat=1, stream=None):
+        """the extremes of this context's region of the cached step `src` (kind EXTREMES_DERIVE or EXTREMES_MERGE) into the
+        eight int32 words at device address `d_words`, every minimum complemented so that ranks combine by elementwise maximum;
+        enqueued on `stream` (a hipStream_t handle; None = the context's stream)"""
+        self._ck(self.L.smk_step_extremes_device(self.ctx, int(kind), int(src), int(compat), d_words, stream))
+
+    def derive_timestep_shard(self, src, out, d_words, compat=1, blur=0, stream=None):
+        """derive_timestep's write pass with the combined extremes read from the eight words at device address `d_words`
+        (smk.h smk_derive_timestep_shard); exact on the step's valid box, zeros on its rim"""
+        self._ck(self.L.smk_derive_timestep_shard(self.ctx, int(src), int(out), int(compat), int(blur), d_words, stream))
+
+    def merge_timestep_shard(self, src, out, d_words, stream=None):
+        """merge_timestep's write pass with the combined maximum read from the eight words at device address `d_words`
+        (smk.h smk_merge_timestep_shard); exact on the step's valid box, zeros on its rim"""
+        self._ck(self.L.smk_merge_timestep_shard(self.ctx, int(src), int(out), d_words, stream))
+
+    def timestep_halo(self, step=STEP_CURRENT):
+        """the valid halo of a cached step: the halo voxels round the region that are exact (smk.h smk_get_timestep_halo)"""
+        h = C.c_int(0)
+        self._ck(self.L.smk_get_timestep_halo(self.ctx, int(step), C.byref(h)))
+        return h.value
 
     def timesteps(self):
         """(current step or -1, the cached ids oldest written first)"""

@@ -383,6 +383,12 @@ int smk_pack_step(smk_ctx *c, const char *who, const SmkVolGeom &g, const smk_vo
   HIPCHK(c, smk_bricks_minmax(T.vox, g.dtype, g.D, g.nbr, T.mm, s));
   if (!s) HIPCHK(c, hipDeviceSynchronize());
   T.vox_x_valid = false;
+  // an upload fills the stored box: all of it that lies in the volume is valid
+  T.valid_halo = c->halo;
+  for (int a = 0; a < 3; ++a) {
+    T.vlo[a] = g.O[a];
+    T.vhi[a] = std::min(g.O[a] + g.D[a], g.N[a]);
+  }
   return 0;
 }
 
@@ -1325,11 +1331,17 @@ int smk_build_params(smk_ctx *c, RenderParams &P, hipStream_t s) {
   P.ps[1] = c->ps[1];
   P.pert_on = (c->d_noise && (c->pw[0] != 0 || c->pw[1] != 0)) ? 1 : 0;
   if (P.pert_on && c->nranks > 1) {
-    // a displaced fetch must stay inside region + halo
+    // a displaced fetch must stay inside region + halo: the halo voxels of the SHOWN step that are exact (a sharded stencil
+    // producer leaves fewer than it found)
+    const int have = smk_step_shown_halo(c);
     for (int a = 0; a < 3; ++a) {
       int need = 1 + (int)ceil(0.5 * (fabs(c->pw[0]) + fabs(c->pw[1])) * c->N[a]);
-      if (c->halo < need && c->D[a] < c->N[a])
+      if (have < need && c->D[a] < c->N[a]) {
+        if (have != c->halo)
+          FAIL(c, "smk_render: perturbation needs halo >= %d voxels on a sharded volume (time step %d has a valid halo of %d, of option halo %d: "
+                  "smk_get_timestep_halo); set option 'halo' before upload", need, c->ts_cur_id, have, c->halo);
         FAIL(c, "smk_render: perturbation needs halo >= %d voxels on a sharded volume (have %d); set option 'halo' before upload", need, c->halo);
+      }
     }
   }
   // a perturbed fetch lands within 0.5 (|w0| + |w1|) N voxels of the undisplaced position on every axis: when that is a

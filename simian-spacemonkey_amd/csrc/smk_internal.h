@@ -264,6 +264,10 @@ struct TimeStep {
   hipEvent_t nonframe_read = nullptr;  // the last reader of the step that is no frame (a producer's source, the histogram, the read-back)
   bool nonframe_read_valid = false;
   int *pass1_words = nullptr;       // eight ints the first pass of a producer INTO this slot reduces into (a derive's six extremes, a merge's maximum)
+  // what of the stored box holds the step's real voxels (DESIGN.md 3b "Stencil producers on a shard"): an upload fills the
+  // stored box, a sharded stencil producer leaves a rim of zeros at every face that is no face of the volume
+  int valid_halo = 1;               // halo voxels round the region that are exact: `halo` after an upload
+  int vlo[3] = {0, 0, 0}, vhi[3] = {0, 0, 0};  // the valid box [vlo, vhi), global voxels
 };
 
 // One frame on its way to the host (smk_present.hip; DESIGN.md "Present"): everything a frame in flight needs that the
@@ -598,4 +602,20 @@ struct StencilEntry {
   const char *prep_entry;
 };
 int smk_step_stencil_refusals(smk_ctx *c, const StencilEntry &E, int step_out, const int *step_src, int *ksrc);
+// The stencil producers' shard entries (smk_*_timestep_shard, smk_step_extremes_device): a stored box anywhere in the volume.
+// _shard_refusals: no volume; the series' nelts; a stored box that is not what the shard kernels take for granted; a volume
+// without an interior voxel; a source that is not cached (*ksrc: its slot); with step_out (null: the export, a reader) the ids;
+// a source whose valid halo is below reach + 1.  SmkShardBox: what the kernels get of the geometry, in LOCAL voxels of the
+// stored box -- the region, and with `out` the valid box of the result, which _shard_done then writes into the output slot
+struct SmkShardBox {
+  int O[3], r0[3], r1[3], v0[3], v1[3];
+};
+int smk_step_shard_refusals(smk_ctx *c, const StencilEntry &E, int reach, int step_src, const int *step_out, int *ksrc);
+void smk_step_shard_box(const smk_ctx *c, const TimeStep &src, int reach, SmkShardBox &B);
+void smk_step_shard_done(const smk_ctx *c, const TimeStep &src, int reach, const SmkShardBox &B, TimeStep &out);
+// smk_step_extremes_device's two kinds: pass 1 of the shard instances over the region, into the caller's eight words
+int smk_derive_extremes_enqueue(smk_ctx *c, const char *who, int step_src, int compat, void *d_words, hipStream_t s);  // (smk_step_derive.hip)
+int smk_merge_extremes_enqueue(smk_ctx *c, const char *who, int step_src, void *d_words, hipStream_t s);               // (smk_step_merge.hip)
+// the valid halo of the step frames render, for the frame path's comparisons with a need
+int smk_step_shown_halo(const smk_ctx *c);
 #pragma GCC visibility pop

@@ -373,10 +373,15 @@ static int shadow_refusals(smk_ctx *c, const RenderParams &P) {
 
 // a shard's halo against the margin of its frame with shadows
 static int shadow_halo_check(smk_ctx *c, int need) {
+  const int have = smk_step_shown_halo(c);  // (of the SHOWN step: a sharded stencil producer leaves fewer exact halo voxels than it found)
   for (int a = 0; a < 3; ++a)
-    if (c->halo < need && c->D[a] < c->N[a])
+    if (have < need && c->D[a] < c->N[a]) {
+      if (have != c->halo)
+        FAIL(c, "smk_render: shadows on a shard need halo >= %d voxels (time step %d has a valid halo of %d, of option halo %d: "
+                "smk_get_timestep_halo; margin %d, smk_get_shadow_margin); set option 'halo' before upload", need, c->ts_cur_id, have, c->halo, need - 1);
       FAIL(c, "smk_render: shadows on a shard need halo >= %d voxels (have %d; margin %d, smk_get_shadow_margin); set option 'halo' before upload",
            need, c->halo, need - 1);
+    }
   return 0;
 }
 

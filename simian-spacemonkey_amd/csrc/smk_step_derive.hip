@@ -16,7 +16,10 @@
 //          volume's border and outside it) into a second LDS tile, then per voxel gm and hs again, the scaling, the normal
 //          from the V tile, and one 8- or 16-byte store of the packed voxel.
 // The arithmetic is smk_prep.hip's, through smk_prep_device.h; the packed voxel is smk_packed.h's.
+#include <limits.h>
+
 #include <algorithm>
+#include <type_traits>
 
 #include "smk_internal.h"
 #include "smk_prep_device.h"
@@ -40,20 +43,51 @@ struct DeriveParams {
   int compat, blur, normals;
 };
 
+// The SHARD instances (smk.h: smk_step_extremes_device, smk_derive_timestep_shard): the stored box lies anywhere in the volume.
+// Tiles and every index into S, V and the slots stay LOCAL to the stored box, so a 16-byte unit of two 8-byte voxels starts
+// on an even local x whatever the parity of O[0]; the border of the volume, its interior and its pad are decided on GLOBAL
+// voxels O + local.  Pass 1 takes the region's voxels alone and leaves its extremes in the caller's eight words, every
+// minimum complemented; pass 2 reads the combined words, and writes zeros (normal 128) outside the valid box: what lies
+// within `reach` of a face of the stored box that is no face of the volume was made from voxels this context does not hold.
+// A parameter TYPE of its own: the unsharded instances' code is what it was.
+struct DeriveShardParams : DeriveParams {
+  SmkShardBox B;
+  int *words_out;       // pass 1: the export
+  const int *words_in;  // pass 2: the combined extremes
+};
+template <class PT>
+constexpr bool dv_shard = std::is_same<PT, DeriveShardParams>::value;
+
+// local voxel l of axis a as a voxel of the volume
+template <class PT>
+__device__ __forceinline__ int dv_glob(const PT &P, int a, int l) {
+  if constexpr (dv_shard<PT>) return P.B.O[a] + l;
+  else return l;
+}
+
+// local voxel (X, Y, Z) is a voxel of the volume that the stored box holds
+template <class PT>
+__device__ __forceinline__ bool dv_held(const PT &P, int X, int Y, int Z) {
+  if constexpr (dv_shard<PT>)
+    return X >= 0 && X < P.D[0] && P.B.O[0] + X < P.N[0] && Y >= 0 && Y < P.D[1] && P.B.O[1] + Y < P.N[1] && Z >= 0 && Z < P.D[2] &&
+           P.B.O[2] + Z < P.N[2];
+  else return X >= 0 && X < P.N[0] && Y >= 0 && Y < P.N[1] && Z >= 0 && Z < P.N[2];
+}
+
 // the tile of the scalar around (x0, y0, z0), apron included; what lies outside the volume is not data: 0, and never used
-template <int SRC>
-__device__ __forceinline__ void dv_load_tile(const DeriveParams &P, int x0, int y0, int z0, float *S) {
+template <int SRC, class PT>
+__device__ __forceinline__ void dv_load_tile(const PT &P, int x0, int y0, int z0, float *S) {
   if (SRC == SRC_PK_U8 || SRC == SRC_PK_U16) {  // two 8-byte voxels per 16-byte unit (x0 - DV_AP is even, and so is D[0])
     constexpr int UPR = DV_LX / 2;
     for (int u = threadIdx.x; u < UPR * DV_LY * DV_LZ; u += 256) {
       const int cu = u % UPR, row = u / UPR, ly = row % DV_LY, lz = row / DV_LY;
       const int X = x0 - DV_AP + 2 * cu, Y = y0 - DV_AP + ly, Z = z0 - DV_AP + lz;
       float a = 0.f, b = 0.f;
-      if (X >= 0 && X < P.N[0] && Y >= 0 && Y < P.N[1] && Z >= 0 && Z < P.N[2]) {
+      if (dv_held(P, X, Y, Z)) {
         const uint4 v = ((const uint4 *)P.src)[(((size_t)Z * P.D[1] + Y) * P.D[0] + X) >> 1];
         constexpr int DT = SRC == SRC_PK_U8 ? SMK_U8 : SMK_U16;
         a = (float)smk_vox8_c0<DT>(v.x);
-        if (X + 1 < P.N[0]) b = (float)smk_vox8_c0<DT>(v.z);
+        if (dv_glob(P, 0, X) + 1 < P.N[0]) b = (float)smk_vox8_c0<DT>(v.z);
       }
       S[row * DV_LX + 2 * cu] = a;
       S[row * DV_LX + 2 * cu + 1] = b;
@@ -63,7 +97,7 @@ __device__ __forceinline__ void dv_load_tile(const DeriveParams &P, int x0, int 
       const int lx = t % DV_LX, row = t / DV_LX, ly = row % DV_LY, lz = row / DV_LY;
       const int X = x0 - DV_AP + lx, Y = y0 - DV_AP + ly, Z = z0 - DV_AP + lz;
       float a = 0.f;
-      if (X >= 0 && X < P.N[0] && Y >= 0 && Y < P.N[1] && Z >= 0 && Z < P.N[2]) {
+      if (dv_held(P, X, Y, Z)) {
         if (SRC == SRC_PK_F32) {
           a = __uint_as_float(((const uint4 *)P.src)[((size_t)Z * P.D[1] + Y) * P.D[0] + X].x);
         } else {
@@ -83,14 +117,16 @@ __device__ __forceinline__ void dv_grad(const float *S, int l, float g[3]) {
   g[2] = S[l + DV_SZ] - S[l - DV_SZ];
 }
 
-// ... of a neighbour: zero on the volume's 1-voxel border (:79-84)
-__device__ __forceinline__ void dv_grad_nb(const DeriveParams &P, const float *S, int l, int Z, int Y, int X, float g[3]) {
+// ... of a neighbour, the voxel (Z, Y, X) of the VOLUME: zero on the volume's 1-voxel border (:79-84)
+template <class PT>
+__device__ __forceinline__ void dv_grad_nb(const PT &P, const float *S, int l, int Z, int Y, int X, float g[3]) {
   if (is_border(P.N[0], P.N[1], P.N[2], Z, Y, X)) g[0] = g[1] = g[2] = 0.f;
   else dv_grad(S, l, g);
 }
 
-// gm and hs of the INTERIOR voxel (Z, Y, X) at tile index l
-__device__ __forceinline__ void dv_gh(const DeriveParams &P, const float *S, int l, int Z, int Y, int X, float &gm, float &hs) {
+// gm and hs of the INTERIOR voxel (Z, Y, X) of the volume at tile index l
+template <class PT>
+__device__ __forceinline__ void dv_gh(const PT &P, const float *S, int l, int Z, int Y, int X, float &gm, float &hs) {
   float g[3], xp[3], xm[3], yp[3], ym[3], zp[3], zm[3];
   dv_grad(S, l, g);
   dv_grad_nb(P, S, l + 1, Z, Y, X + 1, xp);
@@ -113,28 +149,57 @@ __global__ __launch_bounds__(64) void smk_k_derive_seed(VghStats *st) {
 // the volume's size (they all land on one cache line)
 constexpr unsigned DV_STATS_BLOCKS = 2048;  // 8 workgroups for each of 256 CUs
 
-template <int SRC>
-__global__ __launch_bounds__(256) void smk_k_derive_stats(const DeriveParams P, int gx, int gy, int ntiles) {
+// the eight words of an export (smk.h, smk_step_extremes_device): every minimum complemented, so that all combine by maximum
+__global__ __launch_bounds__(64) void smk_k_derive_seed_words(int *w) {
+  if (threadIdx.x < 8) w[threadIdx.x] = threadIdx.x >= 6 ? INT_MIN : (threadIdx.x & 1) ? ORD_NEG_INF : ~ORD_POS_INF;
+}
+
+// ... a wave's running extremes into them (every lane of the wave calls this)
+__device__ __forceinline__ void dv_publish_words(VghRunning &run, int *w) {
+  const int dmin = wave_min(run.dmin), dmax = wave_max(run.dmax), gmin = wave_min(run.gmin), gmax = wave_max(run.gmax), hmin = wave_min(run.hmin),
+            hmax = wave_max(run.hmax);
+  if ((threadIdx.x & 63) == 0) {
+    atomicMax(&w[0], ~dmin);
+    atomicMax(&w[1], dmax);
+    atomicMax(&w[2], ~gmin);
+    atomicMax(&w[3], gmax);
+    atomicMax(&w[4], ~hmin);
+    atomicMax(&w[5], hmax);
+  }
+}
+
+template <int SRC, class PT = DeriveParams>
+__global__ __launch_bounds__(256) void smk_k_derive_stats(const PT P, int gx, int gy, int ntiles) {
   __shared__ float S[DV_LN];
   const int tx = threadIdx.x % DV_TX, ty = threadIdx.x / DV_TX;
   VghRunning run;
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int bx = tile % gx, by = (tile / gx) % gy, bz = tile / (gx * gy);
     const int x0 = bx * DV_TX, y0 = by * DV_TY, z0 = bz * DV_TZ;
+    if constexpr (dv_shard<PT>) {  // a tile of halo voxels alone has nothing to add (the whole workgroup skips it)
+      if (x0 >= P.B.r1[0] || x0 + DV_TX <= P.B.r0[0] || y0 >= P.B.r1[1] || y0 + DV_TY <= P.B.r0[1] || z0 >= P.B.r1[2] || z0 + DV_TZ <= P.B.r0[2])
+        continue;
+    }
     dv_load_tile<SRC>(P, x0, y0, z0, S);
     __syncthreads();
-    const int X = x0 + tx, Y = y0 + ty;
+    const int X = x0 + tx, Y = y0 + ty, GX = dv_glob(P, 0, X), GY = dv_glob(P, 1, Y);
+    bool mine = true;
+    if constexpr (dv_shard<PT>) mine = X >= P.B.r0[0] && X < P.B.r1[0] && Y >= P.B.r0[1] && Y < P.B.r1[1];  // the region's voxels alone
     for (int tz = 0; tz < DV_TZ; ++tz) {
-      const int Z = z0 + tz;
-      if (is_border(P.N[0], P.N[1], P.N[2], Z, Y, X)) continue;  // (and everything outside the volume)
+      const int Z = z0 + tz, GZ = dv_glob(P, 2, Z);
+      if constexpr (dv_shard<PT>) {
+        if (!mine || Z < P.B.r0[2] || Z >= P.B.r1[2]) continue;
+      }
+      if (is_border(P.N[0], P.N[1], P.N[2], GZ, GY, GX)) continue;  // (and everything outside the volume)
       const int l = (tz + DV_AP) * DV_SZ + (ty + DV_AP) * DV_SY + tx + DV_AP;
       float gm, hs;
-      dv_gh(P, S, l, Z, Y, X, gm, hs);
+      dv_gh(P, S, l, GZ, GY, GX, gm, hs);
       run.take(S[l], gm, hs);
     }
     __syncthreads();  // (the next tile overwrites S)
   }
-  run.publish(P.st);
+  if constexpr (dv_shard<PT>) dv_publish_words(run, P.words_out);
+  else run.publish(P.st);
 }
 
 // std::min / std::max of <algorithm> as smk_make_vgh_device applies them to the extremes and the reference's seeds
@@ -142,15 +207,18 @@ __device__ __forceinline__ float dv_std_min(float a, float b) { return (b < a) ?
 __device__ __forceinline__ float dv_std_max(float a, float b) { return (a < b) ? b : a; }
 
 // OUT: the ring's dtype (smk_dtype)
-template <int SRC, int OUT>
-__global__ __launch_bounds__(256) void smk_k_derive_write(const DeriveParams P) {
+template <int SRC, int OUT, class PT = DeriveParams>
+__global__ __launch_bounds__(256) void smk_k_derive_write(const PT P) {
   __shared__ float S[DV_LN], V[DV_LN];
   const int x0 = blockIdx.x * DV_TX, y0 = blockIdx.y * DV_TY, z0 = blockIdx.z * DV_TZ;
   dv_load_tile<SRC>(P, x0, y0, z0, S);
+  VghStats st;  // (a shard's come combined from the caller's words, the minima complemented)
+  if constexpr (dv_shard<PT>) st = {~P.words_in[0], P.words_in[1], ~P.words_in[2], P.words_in[3], ~P.words_in[4], P.words_in[5]};
+  else st = *P.st;
   // the reference seeds its running min/max with +-1e8 (genVGH/main.cpp:69-72, 104-105)
-  const float dmin = dv_std_min(o2f(P.st->dmin), 100000000.f), dmax = dv_std_max(o2f(P.st->dmax), -100000000.f);
-  const float gmin = dv_std_min(o2f(P.st->gmin), 100000000.f), gmax = dv_std_max(o2f(P.st->gmax), -100000000.f);
-  const float hmin = dv_std_min(o2f(P.st->hmin), 100000000.f), hmax = dv_std_max(o2f(P.st->hmax), -100000000.f);
+  const float dmin = dv_std_min(o2f(st.dmin), 100000000.f), dmax = dv_std_max(o2f(st.dmax), -100000000.f);
+  const float gmin = dv_std_min(o2f(st.gmin), 100000000.f), gmax = dv_std_max(o2f(st.gmax), -100000000.f);
+  const float hmin = dv_std_min(o2f(st.hmin), 100000000.f), hmax = dv_std_max(o2f(st.hmax), -100000000.f);
   __syncthreads();
   // the OUTPUT's V channel as the normals' source: the byte (u8) or the float before any quantisation; 0 on the border
   for (int t = threadIdx.x; t < DV_LN; t += 256) {
@@ -159,7 +227,7 @@ __global__ __launch_bounds__(256) void smk_k_derive_write(const DeriveParams P) 
     float v = 0.f;
     // (plain normals read V one voxel around the tile's own voxels, blurred ones two: the outer ring is not read then)
     const bool read = P.blur || (lx >= 1 && lx < DV_LX - 1 && ly >= 1 && ly < DV_LY - 1 && lz >= 1 && lz < DV_LZ - 1);
-    if (read && !is_border(P.N[0], P.N[1], P.N[2], Z, Y, X)) {
+    if (read && !is_border(P.N[0], P.N[1], P.N[2], dv_glob(P, 2, Z), dv_glob(P, 1, Y), dv_glob(P, 0, X))) {
       const double vq = affine_d(dmin, S[t], dmax, 0, 255);  // (vgh_scale's V)
       v = OUT == SMK_U8 ? (float)uc_cast(vq) : (float)(vq / 255.0);
     }
@@ -168,20 +236,28 @@ __global__ __launch_bounds__(256) void smk_k_derive_write(const DeriveParams P) 
   __syncthreads();
   const int tx = threadIdx.x % DV_TX, ty = threadIdx.x / DV_TX, X = x0 + tx, Y = y0 + ty;
   if (X >= P.D[0] || Y >= P.D[1]) return;
+  const int GX = dv_glob(P, 0, X), GY = dv_glob(P, 1, Y);
   for (int tz = 0; tz < DV_TZ; ++tz) {
-    const int Z = z0 + tz;
+    const int Z = z0 + tz, GZ = dv_glob(P, 2, Z);
     if (Z >= P.D[2]) break;
     const size_t o = ((size_t)Z * P.D[1] + Y) * P.D[0] + X;
-    if (X >= P.N[0] || Y >= P.N[1]) {  // the pad column or row of an 8-byte box: zeros, as after an upload
+    if (GX >= P.N[0] || GY >= P.N[1]) {  // the pad column or row of an 8-byte box: zeros, as after an upload
       ((uint2 *)P.out)[o] = make_uint2(0u, 0u);
       continue;
+    }
+    if constexpr (dv_shard<PT>) {  // the rim: zeros that carry no normal
+      if (X < P.B.v0[0] || X >= P.B.v1[0] || Y < P.B.v0[1] || Y >= P.B.v1[1] || Z < P.B.v0[2] || Z >= P.B.v1[2]) {
+        if (OUT == SMK_F32) ((uint4 *)P.out)[o] = make_uint4(0u, 0u, 0u, SMK_NRM_NONE);
+        else ((uint2 *)P.out)[o] = make_uint2(0u, SMK_NRM_NONE);
+        continue;
+      }
     }
     const int l = (tz + DV_AP) * DV_SZ + (ty + DV_AP) * DV_SY + tx + DV_AP;
     unsigned char q[3] = {0, 0, 0};
     float f[3] = {0.f, 0.f, 0.f};
-    if (!is_border(P.N[0], P.N[1], P.N[2], Z, Y, X)) {
+    if (!is_border(P.N[0], P.N[1], P.N[2], GZ, GY, GX)) {
       float gm, hs;
-      dv_gh(P, S, l, Z, Y, X, gm, hs);
+      dv_gh(P, S, l, GZ, GY, GX, gm, hs);
       vgh_scale(S[l], gm, hs, dmin, dmax, gmin, gmax, hmin, hmax, q, f);
     }
     uint32_t nb = SMK_NRM_NONE;
@@ -189,8 +265,8 @@ __global__ __launch_bounds__(256) void smk_k_derive_write(const DeriveParams P) 
       float g[3];
       unsigned char n[3];
       // (Z, Y, X) -> tile index: l moved by the offset; the differences of bytes held as floats are exact
-      nrm_gradient(P.blur, P.N[0], P.N[1], P.N[2], Z, Y, X, g, [&](int si, int sj, int sk, float s[3]) {
-        dv_grad(V, l + (si - Z) * DV_SZ + (sj - Y) * DV_SY + (sk - X), s);
+      nrm_gradient(P.blur, P.N[0], P.N[1], P.N[2], GZ, GY, GX, g, [&](int si, int sj, int sk, float s[3]) {
+        dv_grad(V, l + (si - GZ) * DV_SZ + (sj - GY) * DV_SY + (sk - GX), s);
       });
       if (OUT == SMK_U8) nrm_store(g, n);
       else nrm_store_f32(g, n);
@@ -258,7 +334,105 @@ int derive_enqueue(smk_ctx *c, const char *who, int kind, const void *src, int k
   });
 }
 
+// ---------------------------------------------------------------------------------------------- the shard entries
+
+constexpr int DV_REACH = 2;  // H reads the gradients of the neighbours, a blurred normal the differences of theirs: DV_AP
+
+StencilEntry derive_shard_entry(const smk_ctx *c, const char *who) {
+  StencilEntry E = derive_entry(c, who);
+  E.sharded_why = "";
+  return E;
+}
+
+DeriveShardParams derive_shard_params(const smk_ctx *c, const TimeStep &S, int compat, int blur) {
+  DeriveShardParams P;
+  P.src = S.vox;
+  P.out = nullptr;
+  P.st = nullptr;
+  for (int a = 0; a < 3; ++a) {
+    P.N[a] = c->N[a];
+    P.D[a] = c->D[a];
+  }
+  P.compat = compat ? 1 : 0;
+  P.blur = blur ? 1 : 0;
+  P.normals = c->have_normals ? 1 : 0;
+  smk_step_shard_box(c, S, DV_REACH, P.B);
+  P.words_out = nullptr;
+  P.words_in = nullptr;
+  return P;
+}
+
+dim3 derive_grid(const DeriveParams &P) {
+  return dim3((unsigned)((P.D[0] + DV_TX - 1) / DV_TX), (unsigned)((P.D[1] + DV_TY - 1) / DV_TY), (unsigned)((P.D[2] + DV_TZ - 1) / DV_TZ));
+}
+
+template <int SRC>
+hipError_t launch_derive_export(const DeriveShardParams &P, hipStream_t s) {
+  const dim3 grid = derive_grid(P);
+  const long long ntiles = (long long)grid.x * grid.y * grid.z;
+  if (ntiles > 0x7fffffffLL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(smk_k_derive_seed_words, dim3(1), dim3(64), 0, s, P.words_out);
+  hipLaunchKernelGGL((smk_k_derive_stats<SRC, DeriveShardParams>), dim3((unsigned)std::min<long long>(ntiles, DV_STATS_BLOCKS)), dim3(256), 0, s, P,
+                     (int)grid.x, (int)grid.y, (int)ntiles);
+  return hipGetLastError();
+}
+
+template <int SRC, int OUT>
+hipError_t launch_derive_write_shard(const DeriveShardParams &P, hipStream_t s) {
+  hipLaunchKernelGGL((smk_k_derive_write<SRC, OUT, DeriveShardParams>), derive_grid(P), dim3(256), 0, s, P);
+  return hipGetLastError();
+}
+
 }  // namespace
+
+int smk_derive_extremes_enqueue(smk_ctx *c, const char *who, int step_src, int compat, void *d_words, hipStream_t s) {
+  int ksrc = -1;
+  if (smk_step_shard_refusals(c, derive_shard_entry(c, who), DV_REACH, step_src, nullptr, &ksrc)) return 1;
+  return smk_step_read(c, ksrc, -1, s, [&]() -> int {
+    DeriveShardParams P = derive_shard_params(c, c->ts[(size_t)ksrc], compat, 0);
+    P.words_out = (int *)d_words;
+    HIPCHK(c, c->dtype == SMK_U8    ? launch_derive_export<SRC_PK_U8>(P, s)
+              : c->dtype == SMK_U16 ? launch_derive_export<SRC_PK_U16>(P, s) : launch_derive_export<SRC_PK_F32>(P, s));
+    return 0;
+  });
+}
+
+extern "C" int smk_step_extremes_device(smk_ctx *c, int kind, int step_src, int compat, void *d_words, void *stream) {
+  if (!c) return 1;
+  const char *who = "smk_step_extremes_device";
+  HIPCHK(c, hipSetDevice(c->device));
+  if (kind != SMK_EXTREMES_DERIVE && kind != SMK_EXTREMES_MERGE)
+    FAIL(c, "%s: kind %d is neither SMK_EXTREMES_DERIVE (%d) nor SMK_EXTREMES_MERGE (%d)", who, kind, (int)SMK_EXTREMES_DERIVE,
+         (int)SMK_EXTREMES_MERGE);
+  if (!d_words) FAIL(c, "%s: d_words is NULL", who);
+  if ((uintptr_t)d_words % sizeof(int)) FAIL(c, "%s: d_words is not aligned to its 4-byte words", who);
+  const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  return kind == SMK_EXTREMES_DERIVE ? smk_derive_extremes_enqueue(c, who, step_src, compat, d_words, s)
+                                     : smk_merge_extremes_enqueue(c, who, step_src, d_words, s);
+}
+
+extern "C" int smk_derive_timestep_shard(smk_ctx *c, int step_src, int step_out, int compat, int blur, const void *d_words, void *stream) {
+  if (!c) return 1;
+  const char *who = "smk_derive_timestep_shard";
+  HIPCHK(c, hipSetDevice(c->device));
+  int ksrc = -1;
+  if (smk_step_shard_refusals(c, derive_shard_entry(c, who), DV_REACH, step_src, &step_out, &ksrc)) return 1;
+  if (!d_words) FAIL(c, "%s: d_words is NULL", who);
+  if ((uintptr_t)d_words % sizeof(int)) FAIL(c, "%s: d_words is not aligned to its 4-byte words", who);
+  const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  return smk_step_produce(c, who, step_out, ksrc, -1, s, [&](TimeStep &T, const TimeStep *S, const TimeStep *) -> int {
+    DeriveShardParams P = derive_shard_params(c, *S, compat, blur);
+    P.out = T.vox;
+    P.words_in = (const int *)d_words;
+    hipError_t e;
+    if (c->dtype == SMK_U8) e = launch_derive_write_shard<SRC_PK_U8, SMK_U8>(P, s);
+    else if (c->dtype == SMK_U16) e = launch_derive_write_shard<SRC_PK_U16, SMK_U16>(P, s);
+    else e = launch_derive_write_shard<SRC_PK_F32, SMK_F32>(P, s);
+    HIPCHK(c, e);
+    smk_step_shard_done(c, *S, DV_REACH, P.B, T);
+    return 0;
+  });
+}
 
 extern "C" int smk_derive_timestep(smk_ctx *c, int step_src, int step_out, int compat, int blur, void *stream) {
   if (!c) return 1;

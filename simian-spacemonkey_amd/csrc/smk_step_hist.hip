@@ -99,7 +99,8 @@ hipError_t launch_step_hist(const StepHistParams &P, int device, hipStream_t s) 
 struct StepProbeParams {
   const void *vox;
   const uint32_t *nrm;  // the separate normals of four-channel f32, or null
-  int N[3], O[3], D[3];
+  int O[3], D[3];
+  int vlo[3], vhi[3];   // the step's valid box, global voxels: the stored box cut at the volume, less the rim a sharded stencil producer left
   int dtype, nelts;
   const int *cells;     // [n][3]
   int n;
@@ -109,7 +110,8 @@ struct StepProbeParams {
 };
 
 // One lane per corner (i * 4 + j * 2 + k: i along z, j along y, k along x).  A cell is answered when its eight corners lie
-// in the volume and in the stored box (whose pad column is outside the volume); otherwise its outputs are zeros.
+// in the step's valid box (TimeStep::vlo, vhi: inside the volume and the stored box, whose pad column is outside the volume,
+// and off the rim of a sharded stencil producer's result); otherwise its outputs are zeros.
 __global__ __launch_bounds__(256) void smk_k_step_probe(const StepProbeParams P) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (size_t)P.n * 8) return;
@@ -118,8 +120,8 @@ __global__ __launch_bounds__(256) void smk_k_step_probe(const StepProbeParams P)
   bool ok = true;
   size_t o = 0;
   for (int a = 2; a >= 0; --a) {
-    const int lo = P.cells[cell * 3 + a], top = min(P.O[a] + P.D[a], P.N[a]);
-    ok = ok && lo >= P.O[a] && lo >= 0 && lo < top - 1;  // (lo + 1 <= top - 1, without the overflow of lo + 1)
+    const int lo = P.cells[cell * 3 + a];
+    ok = ok && lo >= P.vlo[a] && lo < P.vhi[a] - 1;  // (lo + 1 <= vhi - 1, without the overflow of lo + 1)
     o = o * (size_t)P.D[a] + (size_t)(ok ? lo + d[a] - P.O[a] : 0);
   }
   uint32_t r[4] = {0, 0, 0, 0}, nb = 0;
@@ -221,9 +223,10 @@ extern "C" int smk_probe_step(smk_ctx *c, int timestep, const int *cells, int n,
   P.vox = T.vox;
   P.nrm = smk_step_separate_normals(c) ? T.nrm : nullptr;
   for (int a = 0; a < 3; ++a) {
-    P.N[a] = c->N[a];
     P.O[a] = c->O[a];
     P.D[a] = c->D[a];
+    P.vlo[a] = T.vlo[a];
+    P.vhi[a] = T.vhi[a];
   }
   P.dtype = c->dtype;
   P.nelts = c->nelts;

@@ -17,7 +17,10 @@
 //   pass 2 (smk_k_merge_write): the gradient again, G and the normal, and one 16-byte store of the unit (and the normal word of
 //          a four-channel f32 voxel).
 // The arithmetic is smk_prep.hip's, through smk_prep_device.h; the packed voxel is smk_packed.h's.
+#include <limits.h>
+
 #include <algorithm>
+#include <type_traits>
 
 #include "smk_internal.h"
 #include "smk_prep_device.h"
@@ -41,6 +44,27 @@ struct MergeParams {
   int normals;
   int ux, uy, ntiles;  // tiles per row of tiles, per slice of tiles, in all
 };
+
+// The SHARD instances (smk.h: smk_step_extremes_device, smk_merge_timestep_shard): the stored box lies anywhere in the volume.
+// Units, tiles and every index into the slots stay LOCAL to the stored box (a unit of two 8-byte voxels starts on an even
+// local x whatever the parity of O[0]); the border of the volume and its pad are decided on GLOBAL voxels O + local.  Pass 1
+// takes the region's voxels alone and leaves its maximum in the caller's eight words; pass 2 reads the combined word, and
+// writes zeros (normal 128) outside the valid box: a voxel on a face of the stored box that is no face of the volume has a
+// neighbour this context does not hold.  A parameter TYPE of its own: the unsharded instances' code is what it was.
+struct MergeShardParams : MergeParams {
+  SmkShardBox B;
+  int *words_out;       // pass 1: the export
+  const int *words_in;  // pass 2: the combined maximum
+};
+template <class PT>
+constexpr bool mg_shard = std::is_same<PT, MergeShardParams>::value;
+
+// local voxel l of axis a as a voxel of the volume
+template <class PT>
+__device__ __forceinline__ int mg_glob(const PT &P, int a, int l) {
+  if constexpr (mg_shard<PT>) return P.B.O[a] + l;
+  else return l;
+}
 
 constexpr int mg_ring(int SRC) { return SRC == SRC_PK_U8 ? SMK_U8 : SRC == SRC_PK_U16 ? SMK_U16 : SRC == SRC_PK_F32 ? SMK_F32 : SRC; }
 constexpr int mg_vpu(int SRC) { return mg_ring(SRC) == SMK_F32 ? 1 : 2;  }  // voxels per 16-byte unit
@@ -95,8 +119,8 @@ __device__ __forceinline__ float mg_val(uint32_t r) {
 // and behind come along in registers from slice to slice; the neighbours in the row are the neighbouring lanes' units (a wave
 // is a row of the tile: every lane of it must be here), which only the wave's first and last lane have to load; the units
 // above and below are loaded.  That makes three loads of a unit per unit where a plain stencil makes seven
-template <int SRC, int NF, class Visit>
-__device__ __forceinline__ void mg_march(const MergeParams &P, int U, int Y, int z0, Visit visit) {
+template <int SRC, int NF, class PT, class Visit>
+__device__ __forceinline__ void mg_march(const PT &P, int U, int Y, int z0, Visit visit) {
   constexpr int VPU = mg_vpu(SRC);
   const int lane = threadIdx.x & 63;
   uint32_t zm[VPU][NF], c0[VPU][NF], zp[VPU][NF];
@@ -127,7 +151,7 @@ __device__ __forceinline__ void mg_march(const MergeParams &P, int U, int Y, int
 #pragma unroll
     for (int c = 0; c < VPU; ++c) {
       merge_grad_zero(g[c]);
-      if (is_border(P.N[0], P.N[1], P.N[2], Z, Y, U * VPU + c)) continue;
+      if (is_border(P.N[0], P.N[1], P.N[2], mg_glob(P, 2, Z), mg_glob(P, 1, Y), mg_glob(P, 0, U * VPU + c))) continue;
 #pragma unroll
       for (int e = 0; e < NF; ++e)
         merge_grad_add(g[c], mg_val<SRC>(c == VPU - 1 ? xr[e] : c0[(c + 1) % VPU][e]), mg_val<SRC>(c == 0 ? xl[e] : c0[(c + VPU - 1) % VPU][e]),
@@ -156,38 +180,64 @@ __global__ __launch_bounds__(64) void smk_k_merge_seed(int *mx) {
   if (threadIdx.x == 0) *mx = MERGE_MAX_SEED;
 }
 
-template <int SRC, int NF>
-__global__ __launch_bounds__(256) void smk_k_merge_max(const MergeParams P) {
+// the eight words of an export (smk.h, smk_step_extremes_device): the maximum, then seven unused words
+__global__ __launch_bounds__(64) void smk_k_merge_seed_words(int *w) {
+  if (threadIdx.x < 8) w[threadIdx.x] = threadIdx.x ? INT_MIN : MERGE_MAX_SEED;
+}
+
+template <int SRC, int NF, class PT = MergeParams>
+__global__ __launch_bounds__(256) void smk_k_merge_max(const PT P) {
   constexpr int VPU = mg_vpu(SRC);
   const int tu = threadIdx.x % MG_UX, ty = threadIdx.x / MG_UX;
   int m = MERGE_MAX_SEED;
   for (int tile = blockIdx.x; tile < P.ntiles; tile += gridDim.x) {
     int u0, y0, z0;
     mg_tile(P, tile, u0, y0, z0);
+    if constexpr (mg_shard<PT>) {  // a tile of halo voxels alone has nothing to add (the whole workgroup skips it)
+      if (u0 * VPU >= P.B.r1[0] || (u0 + MG_UX) * VPU <= P.B.r0[0] || y0 >= P.B.r1[1] || y0 + MG_TY <= P.B.r0[1] || z0 >= P.B.r1[2] ||
+          z0 + MG_TZ <= P.B.r0[2])
+        continue;
+    }
     const int U = u0 + tu, Y = y0 + ty;
     mg_march<SRC, NF>(P, U, Y, z0, [&](int Z, const float g[][3], const uint32_t r[][NF]) {
 #pragma unroll
       for (int c = 0; c < VPU; ++c) {
-        if (is_border(P.N[0], P.N[1], P.N[2], Z, Y, U * VPU + c)) continue;  // (and everything outside the volume)
+        const int X = U * VPU + c;
+        if constexpr (mg_shard<PT>) {  // the region's voxels alone
+          if (X < P.B.r0[0] || X >= P.B.r1[0] || Y < P.B.r0[1] || Y >= P.B.r1[1] || Z < P.B.r0[2] || Z >= P.B.r1[2]) continue;
+        }
+        if (is_border(P.N[0], P.N[1], P.N[2], mg_glob(P, 2, Z), mg_glob(P, 1, Y), mg_glob(P, 0, X))) continue;  // (and everything outside the volume)
         const float mag = merge_mag(g[c]);
         m = mg_ring(SRC) == SMK_U8 ? merge_max_take(m, mag) : merge_max_take_f32(m, mag);
       }
     });
   }
   m = wave_max(m);
-  if ((threadIdx.x & 63) == 0) atomicMax(P.mx, m);
+  if constexpr (mg_shard<PT>) {
+    if ((threadIdx.x & 63) == 0) atomicMax(P.words_out, m);
+  } else {
+    if ((threadIdx.x & 63) == 0) atomicMax(P.mx, m);
+  }
 }
 
 // the packed voxel of the output at column X of row Y from its summed gradient g and its fields r: w[0..1] of an 8-byte ring,
 // w[0..3] of f32; nw: the normal word
-template <int SRC, int NF>
-__device__ __forceinline__ void mg_voxel(const MergeParams &P, int X, int Y, const float gin[3], const uint32_t r[NF], float maxm, uint32_t w[4],
+template <int SRC, int NF, class PT>
+__device__ __forceinline__ void mg_voxel(const PT &P, int X, int Y, int Z, const float gin[3], const uint32_t r[NF], float maxm, uint32_t w[4],
                                          uint32_t &nw) {
   constexpr int RING = mg_ring(SRC);
   nw = SMK_NRM_NONE;
-  if (X >= P.N[0] || Y >= P.N[1]) {  // the pad column or row of an 8-byte box: zeros, as after an upload
+  if (mg_glob(P, 0, X) >= P.N[0] || mg_glob(P, 1, Y) >= P.N[1]) {  // the pad column or row of an 8-byte box: zeros, as after an upload
     w[0] = w[1] = w[2] = w[3] = 0u;
     return;
+  }
+  if constexpr (mg_shard<PT>) {  // the rim: zeros that carry no normal (a four-channel f32 voxel's goes to the separate buffer)
+    if (X < P.B.v0[0] || X >= P.B.v1[0] || Y < P.B.v0[1] || Y >= P.B.v1[1] || Z < P.B.v0[2] || Z >= P.B.v1[2]) {
+      w[0] = w[1] = w[2] = w[3] = 0u;
+      if (RING != SMK_F32) w[1] = SMK_NRM_NONE;
+      else if (NF + 1 <= 3) w[3] = SMK_NRM_NONE;
+      return;
+    }
   }
   float g[3] = {gin[0], gin[1], gin[2]};
   const float mag = merge_mag(g);
@@ -221,10 +271,12 @@ __device__ __forceinline__ void mg_voxel(const MergeParams &P, int X, int Y, con
   }
 }
 
-template <int SRC, int NF>
-__global__ __launch_bounds__(256) void smk_k_merge_write(const MergeParams P) {
+template <int SRC, int NF, class PT = MergeParams>
+__global__ __launch_bounds__(256) void smk_k_merge_write(const PT P) {
   constexpr int VPU = mg_vpu(SRC);
-  const float maxm = o2f(*P.mx);
+  float maxm;  // (a shard's comes combined from the caller's words)
+  if constexpr (mg_shard<PT>) maxm = o2f(P.words_in[0]);
+  else maxm = o2f(*P.mx);
   int u0, y0, z0;
   mg_tile(P, blockIdx.x, u0, y0, z0);
   const int U = u0 + threadIdx.x % MG_UX, Y = y0 + threadIdx.x / MG_UX;
@@ -234,12 +286,12 @@ __global__ __launch_bounds__(256) void smk_k_merge_write(const MergeParams P) {
     const size_t o = ((size_t)Z * P.D[1] + Y) * (size_t)(P.D[0] / VPU) + U;  // the unit
     uint32_t w[4], nw;
     if (VPU == 1) {
-      mg_voxel<SRC, NF>(P, U, Y, g[0], r[0], maxm, w, nw);
+      mg_voxel<SRC, NF>(P, U, Y, Z, g[0], r[0], maxm, w, nw);
       if (NF == 3 && P.nrm) P.nrm[o] = nw;
     } else {
       uint32_t hi[4];
-      mg_voxel<SRC, NF>(P, 2 * U, Y, g[0], r[0], maxm, w, nw);
-      mg_voxel<SRC, NF>(P, 2 * U + 1, Y, g[VPU - 1], r[VPU - 1], maxm, hi, nw);
+      mg_voxel<SRC, NF>(P, 2 * U, Y, Z, g[0], r[0], maxm, w, nw);
+      mg_voxel<SRC, NF>(P, 2 * U + 1, Y, Z, g[VPU - 1], r[VPU - 1], maxm, hi, nw);
       w[2] = hi[0], w[3] = hi[1];
     }
     ((uint4 *)P.out)[o] = make_uint4(w[0], w[1], w[2], w[3]);
@@ -308,7 +360,101 @@ int merge_enqueue(smk_ctx *c, const char *who, const void *const *fields, int ks
   });
 }
 
+// ---------------------------------------------------------------------------------------------- the shard entries
+
+constexpr int MG_REACH = 1;  // the six face neighbours
+
+StencilEntry merge_shard_entry(const smk_ctx *c, const char *who) {
+  StencilEntry E = merge_entry(c, who);
+  E.sharded_why = "";
+  return E;
+}
+
+// false: more than 2^31 tiles
+bool merge_shard_params(const smk_ctx *c, const TimeStep &S, MergeShardParams &P) {
+  const int VPU = c->dtype == SMK_F32 ? 1 : 2;
+  const long long ux = (c->D[0] / VPU + MG_UX - 1) / MG_UX, uy = (c->D[1] + MG_TY - 1) / MG_TY, uz = (c->D[2] + MG_TZ - 1) / MG_TZ;
+  if (ux * uy * uz > 0x7fffffffLL) return false;
+  P.src = S.vox;
+  for (int e = 0; e < 3; ++e) P.f[e] = nullptr;
+  P.out = nullptr;
+  P.nrm = nullptr;
+  P.mx = nullptr;
+  for (int a = 0; a < 3; ++a) {
+    P.N[a] = c->N[a];
+    P.D[a] = c->D[a];
+  }
+  P.normals = c->have_normals ? 1 : 0;
+  P.ux = (int)ux;
+  P.uy = (int)(ux * uy);
+  P.ntiles = (int)(ux * uy * uz);
+  smk_step_shard_box(c, S, MG_REACH, P.B);
+  P.words_out = nullptr;
+  P.words_in = nullptr;
+  return true;
+}
+
+template <int SRC, int NF>
+hipError_t launch_merge_shard(const MergeShardParams &P, bool write, hipStream_t s) {
+  if (write) {
+    hipLaunchKernelGGL((smk_k_merge_write<SRC, NF, MergeShardParams>), dim3((unsigned)P.ntiles), dim3(256), 0, s, P);
+  } else {
+    hipLaunchKernelGGL(smk_k_merge_seed_words, dim3(1), dim3(64), 0, s, P.words_out);
+    hipLaunchKernelGGL((smk_k_merge_max<SRC, NF, MergeShardParams>), dim3(std::min<unsigned>((unsigned)P.ntiles, MG_MAX_BLOCKS)), dim3(256), 0, s, P);
+  }
+  return hipGetLastError();
+}
+
+template <int SRC>
+hipError_t launch_merge_shard_nf(const MergeShardParams &P, int nf, bool write, hipStream_t s) {
+  if (nf == 1) return launch_merge_shard<SRC, 1>(P, write, s);
+  if (nf == 2) return launch_merge_shard<SRC, 2>(P, write, s);
+  if constexpr (mg_ring(SRC) != SMK_U16) {
+    if (nf == 3) return launch_merge_shard<SRC, 3>(P, write, s);
+  }
+  return hipErrorInvalidValue;
+}
+
+hipError_t launch_merge_shard_dtype(const smk_ctx *c, const MergeShardParams &P, bool write, hipStream_t s) {
+  const int nf = c->nelts - 1;
+  return c->dtype == SMK_U8    ? launch_merge_shard_nf<SRC_PK_U8>(P, nf, write, s)
+         : c->dtype == SMK_U16 ? launch_merge_shard_nf<SRC_PK_U16>(P, nf, write, s) : launch_merge_shard_nf<SRC_PK_F32>(P, nf, write, s);
+}
+
 }  // namespace
+
+int smk_merge_extremes_enqueue(smk_ctx *c, const char *who, int step_src, void *d_words, hipStream_t s) {
+  int ksrc = -1;
+  if (smk_step_shard_refusals(c, merge_shard_entry(c, who), MG_REACH, step_src, nullptr, &ksrc)) return 1;
+  MergeShardParams P;
+  if (!merge_shard_params(c, c->ts[(size_t)ksrc], P)) FAIL(c, "%s: a %dx%dx%d stored box has more than 2^31 tiles", who, c->D[0], c->D[1], c->D[2]);
+  P.words_out = (int *)d_words;
+  return smk_step_read(c, ksrc, -1, s, [&]() -> int {
+    HIPCHK(c, launch_merge_shard_dtype(c, P, false, s));
+    return 0;
+  });
+}
+
+extern "C" int smk_merge_timestep_shard(smk_ctx *c, int step_src, int step_out, const void *d_words, void *stream) {
+  if (!c) return 1;
+  const char *who = "smk_merge_timestep_shard";
+  HIPCHK(c, hipSetDevice(c->device));
+  int ksrc = -1;
+  if (smk_step_shard_refusals(c, merge_shard_entry(c, who), MG_REACH, step_src, &step_out, &ksrc)) return 1;
+  if (!d_words) FAIL(c, "%s: d_words is NULL", who);
+  if ((uintptr_t)d_words % sizeof(int)) FAIL(c, "%s: d_words is not aligned to its 4-byte words", who);
+  MergeShardParams P;
+  if (!merge_shard_params(c, c->ts[(size_t)ksrc], P)) FAIL(c, "%s: a %dx%dx%d stored box has more than 2^31 tiles", who, c->D[0], c->D[1], c->D[2]);
+  const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  return smk_step_produce(c, who, step_out, ksrc, -1, s, [&](TimeStep &T, const TimeStep *S, const TimeStep *) -> int {
+    P.out = T.vox;
+    P.nrm = smk_step_separate_normals(c) ? T.nrm : nullptr;
+    P.words_in = (const int *)d_words;
+    HIPCHK(c, launch_merge_shard_dtype(c, P, true, s));
+    smk_step_shard_done(c, *S, MG_REACH, P.B, T);
+    return 0;
+  });
+}
 
 extern "C" int smk_merge_timestep(smk_ctx *c, int step_src, int step_out, void *stream) {
   if (!c) return 1;

@@ -302,6 +302,22 @@ int smk_step_produce(smk_ctx *c, const char *who, int id, int ka, int kb, hipStr
     g.nrm_bytes = smk_step_nrm_bytes(c);
     g.mm_bytes = (size_t)c->nbr[0] * c->nbr[1] * c->nbr[2] * sizeof(float4);
     if (smk_alloc_step(c, g, T)) return 1;
+    // what is valid of the result: what is valid of every source (a blend), all of the stored box without one (dense
+    // arrays); a sharded stencil producer narrows it in its `launches` (smk_step_shard_done)
+    T.valid_halo = c->halo;
+    for (int a = 0; a < 3; ++a) {
+      T.vlo[a] = c->O[a];
+      T.vhi[a] = std::min(c->O[a] + c->D[a], c->N[a]);
+    }
+    for (const int ks : {ka, kb}) {
+      if (ks < 0) continue;
+      const TimeStep &S = c->ts[(size_t)ks];
+      T.valid_halo = std::min(T.valid_halo, S.valid_halo);
+      for (int a = 0; a < 3; ++a) {
+        T.vlo[a] = std::max(T.vlo[a], S.vlo[a]);
+        T.vhi[a] = std::min(T.vhi[a], S.vhi[a]);
+      }
+    }
     if (launches(T, ka >= 0 ? &c->ts[(size_t)ka] : nullptr, kb >= 0 ? &c->ts[(size_t)kb] : nullptr)) return 1;
     HIPCHK(c, smk_bricks_minmax(T.vox, c->dtype, c->D, c->nbr, T.mm, s));
     T.vox_x_valid = false;
@@ -329,6 +345,74 @@ int smk_step_stencil_refusals(smk_ctx *c, const StencilEntry &E, int step_out, c
   if (*ksrc < 0) FAIL(c, "%s: time step %d (the source) is not cached", who, *step_src);
   if (step_out < 0) FAIL(c, "%s: output time step %d: ids are >= 0", who, step_out);
   if (step_out == *step_src) FAIL(c, "%s: output time step %d is also the source: the stencil has no in-place form", who, step_out);
+  return 0;
+}
+
+// ---------------------------------------------------------------------- the stencil producers on a shard: what is valid
+
+// a face of the stored box that is a face of the volume loses nothing to a stencil: beyond it lies no voxel
+static bool volume_face(const smk_ctx *c, int a, int hi) { return hi ? c->O[a] + c->D[a] >= c->N[a] : c->O[a] == 0; }
+
+int smk_step_shown_halo(const smk_ctx *c) { return c->ts_cur >= 0 ? c->ts[(size_t)c->ts_cur].valid_halo : c->halo; }
+
+int smk_step_shard_refusals(smk_ctx *c, const StencilEntry &E, int reach, int step_src, const int *step_out, int *ksrc) {
+  const char *who = E.who;
+  if (!c->have_volume) FAIL(c, "%s: no volume uploaded", who);
+  if (!E.nelts_why.empty()) FAIL(c, "%s: %s", who, E.nelts_why.c_str());
+  // what the shard kernels take for granted of a stored box (smk_volume_geometry): it lies in the volume but for the pad
+  // column and row of 8-byte voxels, which exist only behind the volume's last voxel, it has an even D[0] then, and it holds
+  // the region
+  const bool wide = c->dtype == SMK_F32;
+  bool fits = wide || !(c->D[0] & 1);
+  for (int a = 0; a < 3; ++a) {
+    const int pad = !wide && a < 2 ? 1 : 0;
+    fits = fits && c->O[a] >= 0 && c->D[a] >= 1 && c->O[a] + c->D[a] <= c->N[a] + pad && c->g0[a] >= c->O[a] && c->g1[a] >= c->g0[a] &&
+           c->g1[a] <= std::min(c->O[a] + c->D[a], c->N[a]);
+  }
+  if (!fits)
+    FAIL(c, "%s: internal: the stored box %dx%dx%d at %d,%d,%d does not hold its region inside the volume %dx%dx%d", who, c->D[0], c->D[1], c->D[2],
+         c->O[0], c->O[1], c->O[2], c->N[0], c->N[1], c->N[2]);
+  if (c->N[0] < 3 || c->N[1] < 3 || c->N[2] < 3)
+    FAIL(c, "%s: a %dx%dx%d volume has no interior voxel (dims >= 3, as %s)", who, c->N[0], c->N[1], c->N[2], E.prep_entry);
+  *ksrc = step_src < 0 ? -1 : smk_step_slot(c, step_src);
+  if (*ksrc < 0) FAIL(c, "%s: time step %d (the source) is not cached", who, step_src);
+  if (step_out) {
+    if (*step_out < 0) FAIL(c, "%s: output time step %d: ids are >= 0", who, *step_out);
+    if (*step_out == step_src) FAIL(c, "%s: output time step %d is also the source: the stencil has no in-place form", who, *step_out);
+  }
+  const int have = c->ts[(size_t)*ksrc].valid_halo;
+  if (c->nranks > 1 && have < reach + 1)  // (every rank of a sharded series alike, whatever its own box is cut by)
+    FAIL(c, "%s: time step %d (the source) has a valid halo of %d voxels, the stencil reaches %d and the result keeps one for a frame: a valid "
+            "halo >= %d is needed (option 'halo', set before upload, less the reach of every stencil the step went through)", who, step_src, have,
+         reach, reach + 1);
+  return 0;
+}
+
+void smk_step_shard_box(const smk_ctx *c, const TimeStep &src, int reach, SmkShardBox &B) {
+  for (int a = 0; a < 3; ++a) {
+    B.O[a] = c->O[a];
+    B.r0[a] = c->g0[a] - c->O[a];
+    B.r1[a] = c->g1[a] - c->O[a];
+    B.v0[a] = (volume_face(c, a, 0) ? src.vlo[a] : src.vlo[a] + reach) - c->O[a];
+    B.v1[a] = (volume_face(c, a, 1) ? src.vhi[a] : src.vhi[a] - reach) - c->O[a];
+  }
+}
+
+void smk_step_shard_done(const smk_ctx *c, const TimeStep &src, int reach, const SmkShardBox &B, TimeStep &out) {
+  out.valid_halo = c->nranks > 1 ? src.valid_halo - reach : src.valid_halo;
+  for (int a = 0; a < 3; ++a) {
+    out.vlo[a] = B.v0[a] + c->O[a];
+    out.vhi[a] = B.v1[a] + c->O[a];
+  }
+}
+
+extern "C" int smk_get_timestep_halo(smk_ctx *c, int timestep, int *valid_halo) {
+  if (!c) return 1;
+  const char *who = "smk_get_timestep_halo";
+  int k = -1;
+  if (step_slot(c, who, timestep, &k)) return 1;
+  if (!valid_halo) FAIL(c, "%s: valid_halo is NULL", who);
+  *valid_halo = c->ts[(size_t)k].valid_halo;
   return 0;
 }
 

@@ -321,3 +321,44 @@ def render_shadow_frame_local(renderers, depth=False, scene_depth=None, scene_de
         renderers[0].composite_over_device(layers.data_ptr(), nranks, order, npix, out.data_ptr())
     torch.cuda.synchronize(dev)
     return (out.view(h, w, 4), dout.view(h, w)) if depth else out.view(h, w, 4)
+
+
+def stencil_timestep_local(renderers, kind, src, out, compat=1, blur=0, stream=None, words=None):
+    """Step `out` becomes the derived (kind "derive") or merged (kind "merge") step of the cached step `src` on P shard contexts
+    of this process that share one device, ranks in order (smk.h, "The two stencil producers on a SHARDED context"): every rank
+    exports the extremes of its region (smk_step_extremes_device), the eight words combine by elementwise integer maximum, and
+    every rank runs the write pass with the combined words (smk_derive_timestep_shard / smk_merge_timestep_shard).  No voxel
+    moves between ranks.  A multi-process host does the same with one integer MAX all-reduce of 8 words in place of the
+    maximum taken here.
+    stream: a hipStream_t handle for every rank's kernels (an int or a ctypes.c_void_p).  Exports, the maximum and the write
+    passes are then all enqueued on it and the host waits for nothing.  None: each context's own stream; the host then waits
+    once for the ranks' exports and once for the combined words, both waits the combine's; the write passes are enqueued and
+    not waited for.
+    words: a [P + 1][8] int32 tensor on the device to work in (rows 0..P-1 the ranks' exports, row P the combined words), or
+    None to have one made.  It is returned, and must stay alive until the streams have passed the write passes."""
+    from .binding import EXTREMES_DERIVE, EXTREMES_MERGE
+    if kind not in ("derive", "merge"):
+        raise ValueError("kind must be 'derive' or 'merge', got %r" % (kind,))
+    nranks = len(renderers)
+    dev = torch.device("cuda", renderers[0].device)
+    if words is None:
+        words = torch.empty((nranks + 1, 8), dtype=torch.int32, device=dev)
+    if tuple(words.shape) != (nranks + 1, 8) or words.dtype != torch.int32 or not words.is_contiguous():
+        raise ValueError("words must be a contiguous [%d][8] int32 tensor" % (nranks + 1))
+    k = EXTREMES_DERIVE if kind == "derive" else EXTREMES_MERGE
+    for r, R in enumerate(renderers):
+        R.step_extremes_device(k, src, words[r].data_ptr(), compat=compat, stream=stream)
+    if stream is None:
+        torch.cuda.synchronize(dev)  # the combine's wait: every rank's export, each on its context's stream, is in memory
+        words[nranks].copy_(words[:nranks].amax(0))
+        torch.cuda.current_stream(dev).synchronize()  # ... and the combined words, before the contexts' streams read them
+    else:
+        handle = stream.value if hasattr(stream, "value") else int(stream)
+        with torch.cuda.stream(torch.cuda.ExternalStream(handle, device=dev)):  # behind the exports, before the write passes
+            words[nranks].copy_(words[:nranks].amax(0))
+    for R in renderers:
+        if kind == "derive":
+            R.derive_timestep_shard(src, out, words[nranks].data_ptr(), compat=compat, blur=blur, stream=stream)
+        else:
+            R.merge_timestep_shard(src, out, words[nranks].data_ptr(), stream=stream)
+    return words

@@ -29,7 +29,15 @@ Frame times are HIP-event times on the render stream (median); the loop also rep
      the fields, stream synchronise, smk_merge_fields_device / smk_merge_fields_f32_device (for a u16 ring: the fields as
      floats, the float merge, smk_quantize_u16_device of G, the voxels put together), smk_upload_timestep_device --; then,
      for f32, playback with a blend and a merge on a second stream beside each frame.  Writes profiles/step_merge.md.
-    python tools/timestep_time.py --merge [--out PATH] [volume edge] [loop frames]"""
+    python tools/timestep_time.py --merge [--out PATH] [volume edge] [loop frames]
+  7. --shards: the stencil producers on a shard (smk_step_extremes_device + smk_derive_timestep_shard / smk_merge_timestep_shard).
+     Rank 0 of an 8-way shard of a series of twice the edge (edge 512: a 1024^3 series, a stored box of about 512^3), halo 4:
+     blend + export + write pass on one stream for u8, u16 and f32 rings, HIP events, no host wait (the rank's own words
+     stand in for the combined ones: the device work is the same); beside it, in the same run, the unsharded one-call
+     entries alone on a step of edge^3, `repeats` times over so that their run-to-run spread shows; the shard rank as a ratio
+     to the unsharded entry per voxel written.  Replaces the section "## Times on one MI355X" of profiles/step_shard.md (what
+     stands before it, the kernels' resource table, stays; --out PATH: another file, treated alike).
+    python tools/timestep_time.py --shards [--out PATH] [volume edge] [repeats]"""
 import os
 import statistics
 import sys
@@ -555,18 +563,127 @@ def blend_playback(R, n, loop, bl):
     return out
 
 
+def alone_ms(R, kind, stream, rounds=12, warm=3):
+    """the one-call entry alone on the blend 10 of a context's steps 0 and 1: (median, min, max) ms of HIP events"""
+    sb = stream.cuda_stream
+    t = []
+    for i in range(rounds):
+        R.blend_timesteps(0, 1, 0.3, 10, stream=sb)
+        if kind == "derive":
+            t.append(event_ms(stream, lambda: R.derive_timestep(10, 12, 1, 0, stream=sb)))
+        else:
+            t.append(event_ms(stream, lambda: R.merge_timestep(10, 12, stream=sb)))
+    t = t[warm:]
+    return statistics.median(t), min(t), max(t)
+
+
+def shards_leg(pkg, n, repeats, out_path):
+    N, halo = 2 * n, 4
+    lines = ["## Times on one MI355X", "",
+             "Written by `tools/timestep_time.py --shards %d %d`.  Rank 0 of an 8-way shard of a %d^3 series (three channels with" % (n, repeats, N),
+             "normals, halo %d: a stored box of %d^3 voxels of 8 bytes, %d^3 of f32) against an unsharded context that holds a %d^3" % (
+                 halo, n + halo + (n + halo) % 2, n + halo, n),
+             "step.  HIP events on one stream, median of 9 after 3 warm-up rounds (min - max); the source is the 0.3 blend of two resident",
+             "steps.  The shard's write pass reads the rank's own exported words: the combine is a host's 8-word MAX all-reduce and no",
+             "device work.  *Per voxel written*: (export + write) / stored voxels over the one-call entry / its stored voxels.", "",
+             "| ring | entry | shard: blend + export + write ms | export ms | write ms | unsharded one-call entry alone ms, %d repeats (median, min - max) | shard / unsharded per voxel written |" % repeats,
+             "|---|---|---|---|---|---|---|"]
+    st = torch.cuda.Stream()
+    sb = st.cuda_stream
+    med = statistics.median
+    for dtype in ("u8", "u16", "f32"):
+        # the unsharded yardstick first: edge^3
+        R = pkg.Renderer(0)
+        un = {}
+        try:
+            steps, dt = typed_steps(R, n, dtype)
+            R.set_timestep_cache(8)
+            R.upload_volume_device(steps[0][0].data_ptr(), (n, n, n), 3, dt, steps[0][1].data_ptr())
+            R.upload_timestep_device(1, steps[1][0].data_ptr(), (n, n, n), 3, dt, steps[1][1].data_ptr(), stream=sb)
+            torch.cuda.synchronize()
+            del steps
+            for kind in ("derive", "merge"):
+                un[kind] = [alone_ms(R, kind, st) for _ in range(repeats)]
+            unvox = (n + (n % 2 if dtype != "f32" else 0)) ** 2 * n     # the stored box of the unsharded step
+        finally:
+            R.close()
+            torch.cuda.synchronize()
+        dt = {"u8": 0, "f32": 1, "u16": 2}[dtype]            # smk_dtype
+        R = pkg.Renderer(0)
+        try:
+            R.set_shard(0, 8)
+            R.set_option("halo", halo)
+            R.set_timestep_cache(6)
+            for t in (0, 1):                                 # one step of the series at a time is on the device beside the ring
+                vghf, nrm = bench.make_volume(R, N, seed=t + 1)
+                if dtype == "u8":
+                    data = (vghf * 255.0 + 0.5).to(torch.uint8)
+                elif dtype == "u16":
+                    data = torch.empty(vghf.shape, dtype=torch.int16, device="cuda")
+                    R.quantize_u16_device(vghf.data_ptr(), vghf.numel(), data.data_ptr())
+                else:
+                    data = vghf
+                torch.cuda.synchronize()
+                if t == 0:
+                    R.upload_volume_device(data.data_ptr(), (N, N, N), 3, dt, nrm.data_ptr())
+                else:
+                    R.upload_timestep_device(1, data.data_ptr(), (N, N, N), 3, dt, nrm.data_ptr(), stream=sb)
+                torch.cuda.synchronize()
+                del vghf, nrm, data
+                torch.cuda.empty_cache()
+            edge = n + halo + ((n + halo) % 2 if dtype != "f32" else 0)
+            shvox = edge * edge * (n + halo)
+            words = torch.zeros(8, dtype=torch.int32, device="cuda")
+            torch.cuda.synchronize()
+            wp = words.data_ptr()
+            for kind, code in (("derive", 0), ("merge", 1)):
+                def write():
+                    if kind == "derive":
+                        R.derive_timestep_shard(10, 12, wp, 1, 0, stream=sb)
+                    else:
+                        R.merge_timestep_shard(10, 12, wp, stream=sb)
+                t_all, t_ex, t_wr = [], [], []
+                for i in range(12):
+                    t_all.append(event_ms(st, lambda: (R.blend_timesteps(0, 1, 0.3, 10, stream=sb), R.step_extremes_device(code, 10, wp, stream=sb), write())))
+                    t_ex.append(event_ms(st, lambda: R.step_extremes_device(code, 10, wp, stream=sb)))
+                    t_wr.append(event_ms(st, write))
+                assert R.timestep_halo(12) == halo - (2 if kind == "derive" else 1)
+                a, e, w = t_all[3:], t_ex[3:], t_wr[3:]
+                u = un[kind]
+                umed = med([x[0] for x in u])
+                ratio = ((med(e) + med(w)) / shvox) / (umed / unvox)
+                lines.append("| %s | %s | %.3f (%.3f - %.3f) | %.3f (%.3f - %.3f) | %.3f (%.3f - %.3f) | %s | %.2f |" % (
+                    dtype, kind, med(a), min(a), max(a), med(e), min(e), max(e), med(w), min(w), max(w),
+                    "; ".join("%.3f (%.3f - %.3f)" % x for x in u), ratio))
+                print(lines[-1], flush=True)
+        finally:
+            R.close()
+            torch.cuda.synchronize()
+    # the section replaces the one the file has; what stands before it stays
+    head = open(out_path).read() if os.path.exists(out_path) else ""
+    if lines[0] in head:
+        head = head[:head.index(lines[0])]
+    if head and not head.endswith("\n\n"):
+        head = head.rstrip("\n") + "\n\n"
+    open(out_path, "w").write(head + "\n".join(lines) + "\n")
+    print("wrote", out_path, flush=True)
+
+
 def main():
     args = sys.argv[1:]
     blend, download, derive, merge = "--blend" in args, "--download" in args, "--derive" in args, "--merge" in args
+    shards = "--shards" in args
     out_path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                            "step_merge.md" if merge else "step_derive.md" if derive else "step_download.md" if download else "timestep_blend.md")
+                            "step_shard.md" if shards else "step_merge.md" if merge else "step_derive.md" if derive else "step_download.md" if download else "timestep_blend.md")
     if "--out" in args:
         out_path = args[args.index("--out") + 1]
         del args[args.index("--out"):args.index("--out") + 2]
-    args = [a for a in args if a not in ("--blend", "--download", "--derive", "--merge")]
+    args = [a for a in args if a not in ("--blend", "--download", "--derive", "--merge", "--shards")]
     n = int(args[0]) if len(args) > 0 else 512
     loop = int(args[1]) if len(args) > 1 else 32
     pkg = bench.load_package()
+    if shards:
+        return shards_leg(pkg, n, int(args[1]) if len(args) > 1 else 3, out_path)
     if merge:
         return merge_leg(pkg, n, loop, out_path)
     if derive:
