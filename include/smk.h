@@ -268,6 +268,68 @@ int smk_derive_timestep_shard(smk_ctx *ctx, int step_src, int step_out, int comp
 int smk_merge_timestep_shard(smk_ctx *ctx, int step_src, int step_out, const void *d_words, void *stream);
 /* the valid halo of cached step `timestep` (an id, or SMK_STEP_CURRENT) */
 int smk_get_timestep_halo(smk_ctx *ctx, int timestep, int *valid_halo);
+/* ---- Blocks of a decomposed simulation: time steps from a rank's OWN dense block of the volume ("Blocks of a
+ * decomposed simulation"; INTEGRATION.md 5, the in-situ recipe).  A simulation on P GPUs holds its sub-domain with ghost cells
+ * on each GPU; the three device upload entries above have a BLOCK FORM that reads that array where it lies, wherever it lies
+ * in the volume, so that no rank describes or assembles arrays it does not hold.
+ * smk_block: `origin` is the global voxel of element [0][0][0] of the array handed over, `size` its voxels (x, y, z); the
+ * pitches are the distances of two rows and of two slices in ELEMENTS (an element is one voxel of the array: a scalar, or the
+ * nelts values of an interleaved voxel and the 3 bytes of its normal), 0 = contiguous: size[0] and size[0] * size[1].  The
+ * block must lie inside the volume: a simulation whose array carries ghost cells outside the volume, or wider ghosts than it
+ * wants to hand over, passes a VIEW -- the address of the view's first element, and the array's pitches.  Elements of the array
+ * outside the view are never read.
+ * THE VALID BOX OF A BLOCK, one rule for all three forms.  C = block ∩ stored box ∩ volume.  C must contain the context's
+ * region [g0, g1), else the call is refused, naming the axis and both intervals.  The source's VALID HALO is the smallest
+ * number of voxels C extends beyond the region, over the region's faces that are no faces of the volume, capped at option
+ * "halo" (a side where C ends on the volume's own face gives all a halo can: no voxel lies beyond it); on an unsharded
+ * context it is "halo", unchanged.  Stored voxels of the volume outside the result's valid box are
+ * the RIM, zeros with the normal (128, 128, 128), as after smk_*_timestep_shard; the slot's valid halo and valid box are set
+ * accordingly, and the frame path, smk_probe_step and every later producer respect them.
+ * Refused by all block entries, changing nothing: a NULL block; a size <= 0; a pitch below the size (pitch_y < size[0],
+ * pitch_z < pitch_y * size[1]); a block that leaves the volume; a block whose C does not contain the region. */
+typedef struct {
+  int origin[3];
+  int size[3];
+  long long pitch_y, pitch_z;
+} smk_block;
+/* The series' geometry WITHOUT data: leaves the context exactly as smk_upload_volume leaves it for a volume of zeros of
+ * dims[3] voxels and extent[3] (volume space) with `normals` != 0 saying whether the series carries normals -- cached steps
+ * dropped, the volume stored as the current step (id 0 on a new context, else the current id), packed zero voxels with the
+ * normal (128, 128, 128), the pad, brick summaries, the shard's stored box (smk_set_shard and option "halo" before this
+ * call), valid halo = "halo".  Refuses what smk_upload_volume refuses of such a volume, with the same words.  The only way
+ * to give a sharded in-situ context its geometry; the block entries below need a volume, declared or uploaded.  Synchronous. */
+int smk_declare_volume(smk_ctx *ctx, const int dims[3], const float extent[3], int nelts, smk_dtype dtype, smk_datamode dmode,
+                       int normals);
+/* The packed form: what smk_upload_timestep_device does with ONE brick at block->origin, pitched, without the requirement
+ * that bricks tile the volume.  d_data is [z][y][x][nelts] of the series' dtype, d_grad_or_null [z][y][x][3] (present exactly
+ * when the series has normals), both DEVICE memory read through the block's pitches.  The valid box is C, the valid halo the
+ * source's; refused when that is below 1 on a sharded context (a frame's trilinear fetch needs one).  On an unsharded
+ * context a block that is the whole volume stores smk_upload_timestep_device's bits.  Slot rule, ordering and refusals
+ * otherwise as that entry's (no volume; timestep < 0; no slot); `stream` must also order the reads of the block. */
+int smk_upload_timestep_block_device(smk_ctx *ctx, int timestep, const void *d_data, const unsigned char *d_grad_or_null,
+                                     const smk_block *block, void *stream);
+/* The stencil forms: smk_upload_timestep_scalar_device and smk_upload_timestep_fields_device from blocks, as two calls with
+ * the eight-word exchange of smk_step_extremes_device between them.
+ * Pass 1, smk_block_extremes_device: `kind` SMK_EXTREMES_DERIVE -- nf == 1, d_fields[0] the scalar, dtype any of SMK_U8,
+ * SMK_U16, SMK_F32 whatever the ring's --, or SMK_EXTREMES_MERGE -- nf == nelts - 1 fields of the ring's dtype; d_fields is a
+ * HOST array of nf device pointers read before the call returns, every array laid out by the one block.  The extremes of
+ * the region's interior voxels go to the eight words at d_words, words and seeds as smk_step_extremes_device's: the maximum
+ * over the ranks' words equals, bit for bit, what an unsharded context exports for the same scalar held as floats.
+ * Pass 2, smk_upload_timestep_scalar_block_device / smk_upload_timestep_fields_block_device: the write pass with the
+ * combined words, a producer into step `timestep` by smk_upload_timestep_device's slot rule.  The result's valid box is C
+ * shrunk by the reach r (2 derive, 1 merge) at every face of C that is no face of the volume; its valid halo is the source's
+ * less r on a sharded series.  A source valid halo below r + 1 on a sharded context is refused with both numbers.  Inside
+ * the valid box every stored field and normal byte is what the unsharded entry stores at that voxel from the whole arrays:
+ * the volume's 1-voxel border decided on global voxels, the pad column and row, u16's definition.
+ * Refused, changing nothing: what the unsharded twins refuse (no volume; the series' nelts; a NULL or misaligned array; a
+ * dtype that does not fit; nf; timestep < 0; no slot; d_words NULL or misaligned; an unknown kind) and what every block entry
+ * refuses.  No host synchronisation, no allocation; `stream` (NULL = the context's) also orders the reads of the block. */
+int smk_block_extremes_device(smk_ctx *ctx, int kind, const void *const *d_fields, int nf, smk_dtype dtype, const smk_block *block,
+                              int compat, void *d_words, void *stream);
+int smk_upload_timestep_scalar_block_device(smk_ctx *ctx, int timestep, const void *d_scalar, smk_dtype scalar_dtype,
+                                            const smk_block *block, int compat, int blur, const void *d_words, void *stream);
+int smk_upload_timestep_fields_block_device(smk_ctx *ctx, int timestep, const void *const *d_fields, int nf, smk_dtype field_dtype,
+                                            const smk_block *block, const void *d_words, void *stream);
 /* introspection: the current step (-1: no volume), the cached ids oldest written first (min(cap, *n) of them; ids_out may
  * be NULL), their number */
 int smk_get_timesteps(smk_ctx *ctx, int *current, int *ids_out, int cap, int *n);

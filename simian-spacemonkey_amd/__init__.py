@@ -7,4 +7,4 @@ __graft_entry__.build().
 """
 from . import binding  # noqa: F401
 from .binding import (SmkError, Renderer, Exchange, exchange_unique_id, build_library, library_path,  # noqa: F401
-                      load_library, ABI_SYMBOLS)
+                      load_library, ABI_SYMBOLS, smk_block)

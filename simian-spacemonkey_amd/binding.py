@@ -39,6 +39,8 @@ ABI_SYMBOLS = [
     "smk_present_device", "smk_render_present", "smk_render_present_begin", "smk_render_present_end",
     "smk_hist2d_step_device", "smk_hist2d_step", "smk_hist2d_finish", "smk_probe_step",
     "smk_get_timestep_box", "smk_download_timestep_device", "smk_download_timestep",
+    "smk_declare_volume", "smk_upload_timestep_block_device", "smk_block_extremes_device",
+    "smk_upload_timestep_scalar_block_device", "smk_upload_timestep_fields_block_device",
 ]
 STEP_CURRENT = -1  # SMK_STEP_CURRENT: the step the frames render
 EXTREMES_DERIVE, EXTREMES_MERGE = 0, 1  # SMK_EXTREMES_*: the kind of smk_step_extremes_device
@@ -63,6 +65,18 @@ class VolumeDesc(C.Structure):
                 ("xiPos", C.c_int), ("yiPos", C.c_int), ("ziPos", C.c_int),
                 ("xfPos", C.c_float), ("yfPos", C.c_float), ("zfPos", C.c_float),
                 ("data", C.c_void_p), ("grad", C.c_void_p)]
+
+
+class Block(C.Structure):
+    """smk_block: a rank's own dense block of the volume"""
+    _fields_ = [("origin", C.c_int * 3), ("size", C.c_int * 3), ("pitch_y", C.c_longlong), ("pitch_z", C.c_longlong)]
+
+
+def smk_block(origin, size, pitch_y=0, pitch_z=0):
+    """the smk_block of an array whose element [0][0][0] is global voxel `origin` (x, y, z) and that holds `size` (x, y, z)
+    voxels; pitches in elements between two rows and two slices, 0 = contiguous.  A view of a larger array: the address of the
+    view's first element goes to the entry, the array's pitches here"""
+    return Block((C.c_int * 3)(*map(int, origin)), (C.c_int * 3)(*map(int, size)), int(pitch_y), int(pitch_z))
 
 
 class RayCoef(C.Structure):
@@ -149,6 +163,14 @@ def load_library():
     L.smk_derive_timestep_shard.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.smk_merge_timestep_shard.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.smk_get_timestep_halo.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.smk_declare_volume.argtypes = [C.c_void_p, P(C.c_int), P(C.c_float), C.c_int, C.c_int, C.c_int, C.c_int]
+    L.smk_upload_timestep_block_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, P(Block), C.c_void_p]
+    L.smk_block_extremes_device.argtypes = [C.c_void_p, C.c_int, P(C.c_void_p), C.c_int, C.c_int, P(Block), C.c_int, C.c_void_p,
+                                            C.c_void_p]
+    L.smk_upload_timestep_scalar_block_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, P(Block), C.c_int, C.c_int,
+                                                          C.c_void_p, C.c_void_p]
+    L.smk_upload_timestep_fields_block_device.argtypes = [C.c_void_p, C.c_int, P(C.c_void_p), C.c_int, C.c_int, P(Block),
+                                                          C.c_void_p, C.c_void_p]
     L.smk_upload_timestep_fields_device.argtypes = [C.c_void_p, C.c_int, P(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int,
                                                     C.c_int, C.c_void_p]
     L.smk_set_shard.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -424,6 +446,48 @@ class Renderer:
         """merge_timestep's write pass with the combined maximum read from the eight words at device address `d_words`
         (smk.h smk_merge_timestep_shard); exact on the step's valid box, zeros on its rim"""
         self._ck(self.L.smk_merge_timestep_shard(self.ctx, int(src), int(out), d_words, stream))
+
+    # -- blocks of a decomposed simulation (smk.h: smk_block ...): a rank's own dense block of the volume, wherever it lies
+    def declare_volume(self, dims, nelts, dtype, fsize=None, dmode="VGH", normals=True):
+        """the series' geometry without data: the context as upload_volume leaves it for a volume of zeros of dims (x, y, z)
+        voxels (smk.h smk_declare_volume); dtype 0 u8, 1 f32, 2 u16"""
+        m = float(max(dims))
+        fsize = fsize or tuple(n / m for n in dims)
+        self._ck(self.L.smk_declare_volume(self.ctx, (C.c_int * 3)(*map(int, dims)), (C.c_float * 3)(*fsize), int(nelts), int(dtype),
+                                           GDM[dmode], 1 if normals else 0))
+
+    @staticmethod
+    def _block_arg(block):
+        """the `block` argument of the block entries as ctypes takes it: an smk_block(), or None, which passes a NULL block"""
+        return None if block is None else C.byref(block)
+
+    @staticmethod
+    def _ptr_array(ptrs):
+        return None if ptrs is None else (C.c_void_p * max(len(ptrs), 1))(*ptrs)
+
+    def upload_timestep_block_device(self, timestep, dptr, block, grad_dptr=None, stream=None):
+        """step `timestep` from the interleaved voxels [z][y][x][nelts] (and normals [z][y][x][3]) of `block` (an smk_block()),
+        device memory read through the block's pitches (smk.h smk_upload_timestep_block_device)"""
+        self._ck(self.L.smk_upload_timestep_block_device(self.ctx, int(timestep), dptr, grad_dptr, self._block_arg(block), stream))
+
+    def block_extremes_device(self, kind, ptrs, dtype, block, d_words, compat=1, stream=None):
+        """pass 1 of the derive (kind EXTREMES_DERIVE: ptrs holds the one scalar, any dtype) or of the merge (EXTREMES_MERGE:
+        nelts - 1 fields of the ring's dtype) over this context's region, read from the dense array(s) of `block`, into the
+        eight int32 words at device address `d_words` (smk.h smk_block_extremes_device)"""
+        self._ck(self.L.smk_block_extremes_device(self.ctx, int(kind), self._ptr_array(ptrs), 0 if ptrs is None else len(ptrs), int(dtype),
+                                                  self._block_arg(block), int(compat), d_words, stream))
+
+    def upload_timestep_scalar_block_device(self, timestep, dptr, scalar_dtype, block, d_words, compat=1, blur=0, stream=None):
+        """the derive's write pass from the scalar of `block` with the combined words at `d_words`: step `timestep` becomes the
+        VGH step of the scalar, exact on the block's valid box (smk.h smk_upload_timestep_scalar_block_device)"""
+        self._ck(self.L.smk_upload_timestep_scalar_block_device(self.ctx, int(timestep), dptr, int(scalar_dtype), self._block_arg(block),
+                                                                int(compat), int(blur), d_words, stream))
+
+    def upload_timestep_fields_block_device(self, timestep, ptrs, dtype, block, d_words, stream=None):
+        """the merge's write pass from the fields of `block`, one device address each, with the combined words at `d_words`
+        (smk.h smk_upload_timestep_fields_block_device)"""
+        self._ck(self.L.smk_upload_timestep_fields_block_device(self.ctx, int(timestep), self._ptr_array(ptrs), 0 if ptrs is None else len(ptrs),
+                                                                int(dtype), self._block_arg(block), d_words, stream))
 
     def timestep_halo(self, step=STEP_CURRENT):
         """the valid halo of a cached step: the halo voxels round the region that are exact (smk.h smk_get_timestep_halo)"""

@@ -422,6 +422,42 @@ extern "C" int smk_upload_volume_device(smk_ctx *c, const smk_volume_desc *b, in
   return upload_impl(c, b, nb, nelts, dt, dm, true);
 }
 
+// The geometry of a series without data (smk.h): upload_impl for a volume of zeros that nobody holds.  The geometry and its
+// refusals are smk_volume_geometry's own, asked about ONE brick that is the whole volume; its data pointer only has to be
+// non-null there, and nothing reads it: smk_pack_block without a source fills the stored box
+extern "C" int smk_declare_volume(smk_ctx *c, const int dims[3], const float extent[3], int nelts, smk_dtype dtype, smk_datamode dmode,
+                                  int normals) {
+  if (!c) return 1;
+  const char *who = "smk_declare_volume";
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!dims || !extent) FAIL(c, "%s: dims or extent is NULL", who);
+  static const unsigned char nobody = 0;
+  smk_volume_desc b = {dims[0], dims[1], dims[2], extent[0], extent[1], extent[2], 0, 0, 0, 0.f, 0.f, 0.f, &nobody, normals ? &nobody : nullptr};
+  SmkVolGeom g;
+  if (smk_volume_geometry(c, who, &b, 1, nelts, dtype, dmode, g)) return 1;
+  free_volume(c);
+  smk_set_geometry(c, g);
+  c->ts.assign((size_t)c->ts_cap, TimeStep());
+  TimeStep &T = c->ts[0];
+  if (smk_alloc_step(c, g, T)) return 1;
+  T.id = c->ts_cur_id;
+  T.written = ++c->ts_written;
+  const int none[3] = {0, 0, 0};
+  HIPCHK(c, smk_pack_block(c, nullptr, nullptr, none, none, none, 0, 0, T, nullptr));
+  HIPCHK(c, smk_bricks_minmax(T.vox, g.dtype, g.D, g.nbr, T.mm, nullptr));
+  HIPCHK(c, hipDeviceSynchronize());
+  T.vox_x_valid = false;
+  T.valid_halo = c->halo;
+  for (int a = 0; a < 3; ++a) {
+    T.vlo[a] = g.O[a];
+    T.vhi[a] = std::min(g.O[a] + g.D[a], g.N[a]);
+  }
+  smk_use_step(c, 0);
+  c->tune_choice.clear();
+  c->tune_sig = 0;
+  return 0;
+}
+
 extern "C" int smk_set_clip(smk_ctx *c, int on, int oaxis, const float *vpos) {
   if (!c) return 1;
   if (!on) {

@@ -616,6 +616,32 @@ void smk_step_shard_done(const smk_ctx *c, const TimeStep &src, int reach, const
 // smk_step_extremes_device's two kinds: pass 1 of the shard instances over the region, into the caller's eight words
 int smk_derive_extremes_enqueue(smk_ctx *c, const char *who, int step_src, int compat, void *d_words, hipStream_t s);  // (smk_step_derive.hip)
 int smk_merge_extremes_enqueue(smk_ctx *c, const char *who, int step_src, void *d_words, hipStream_t s);               // (smk_step_merge.hip)
+// The block entries (smk.h: smk_block; smk_step_block.hip, and the block instances of the two stencil producers): a rank's own
+// dense block of the volume.  SmkBlockView: what the entries make of a block against this context's stored box -- C = block ∩
+// stored box ∩ volume in GLOBAL voxels, the source's valid halo, and the pitches with their zeros resolved.
+// smk_block_view: the refusals every block entry shares (a NULL block, sizes, pitches, a block outside the volume, a C that
+//   does not contain the region) and the view.
+// smk_step_block_refusals: a stencil form's, in the twins' order -- no volume; the series' nelts; the stored box; a volume
+//   without an interior voxel; with step_out (null: the export) the id --, then smk_block_view's, then on a sharded context a
+//   source valid halo below reach + 1.
+// _block_box / _block_done: smk_step_shard_box / _done with C in the place of the source slot's valid box.
+struct SmkBlockView {
+  int c0[3], c1[3];
+  int halo;
+  long long py, pz;
+};
+int smk_block_view(smk_ctx *c, const char *who, const smk_block *b, SmkBlockView &V);
+int smk_step_block_refusals(smk_ctx *c, const StencilEntry &E, int reach, const int *step_out, const smk_block *b, SmkBlockView &V);
+void smk_step_block_box(const smk_ctx *c, const SmkBlockView &V, int reach, SmkShardBox &B);
+void smk_step_block_done(const smk_ctx *c, const SmkBlockView &V, int reach, const SmkShardBox &B, TimeStep &out);
+// smk_block_extremes_device's merge kind (smk_step_merge.hip); the derive kind lives beside the entry (smk_step_derive.hip)
+int smk_merge_block_extremes_enqueue(smk_ctx *c, const char *who, const void *const *d_fields, int nf, smk_dtype dtype, const smk_block *b,
+                                     void *d_words, hipStream_t s);
+// The packed voxels of a whole stored box in one pass (smk_step_block.hip): inside the box [c0, c1) (LOCAL voxels of the stored
+// box; empty: nowhere) the voxels of the block whose element [0][0][0] is local voxel bo, read through its pitches; elsewhere in
+// the volume zeros with the normal (128, 128, 128); zeros in the pad column and row.  src null: zeros everywhere (smk_declare_volume)
+hipError_t smk_pack_block(const smk_ctx *c, const void *src, const unsigned char *grad, const int bo[3], const int c0[3], const int c1[3],
+                          long long py, long long pz, TimeStep &T, hipStream_t s);
 // the valid halo of the step frames render, for the frame path's comparisons with a need
 int smk_step_shown_halo(const smk_ctx *c);
 #pragma GCC visibility pop

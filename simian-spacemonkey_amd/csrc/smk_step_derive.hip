@@ -16,6 +16,9 @@
 //          volume's border and outside it) into a second LDS tile, then per voxel gm and hs again, the scaling, the normal
 //          from the V tile, and one 8- or 16-byte store of the packed voxel.
 // The arithmetic is smk_prep.hip's, through smk_prep_device.h; the packed voxel is smk_packed.h's.
+// Instances of the two kernels over parameter types of their own serve sharded contexts (DeriveShardParams: a packed step of
+// the ring) and a decomposed simulation's own dense block of the volume (DeriveBlockParams: smk_block_extremes_device,
+// smk_upload_timestep_scalar_block_device).
 #include <limits.h>
 
 #include <algorithm>
@@ -55,8 +58,19 @@ struct DeriveShardParams : DeriveParams {
   int *words_out;       // pass 1: the export
   const int *words_in;  // pass 2: the combined extremes
 };
+// The BLOCK instances (smk.h: smk_block_extremes_device, smk_upload_timestep_scalar_block_device): shard instances whose scalar
+// is a rank's own dense block of the volume, lying anywhere.  Tiles, the region, the valid box and every index into S, V and the
+// slot are the shard's; only the SOURCE differs: a voxel is held when it lies inside C = block ∩ stored box ∩ volume, and it is
+// read at (local - bo) through the block's pitches.  Again a parameter type of its own
+struct DeriveBlockParams : DeriveShardParams {
+  int bo[3];          // the block's element [0][0][0] in LOCAL voxels of the stored box (negative: the block starts before the box)
+  int c0[3], c1[3];   // C, local voxels: what of the block's extent this context takes
+  long long py, pz;   // elements between two rows, two slices of the block
+};
 template <class PT>
-constexpr bool dv_shard = std::is_same<PT, DeriveShardParams>::value;
+constexpr bool dv_shard = std::is_base_of<DeriveShardParams, PT>::value;
+template <class PT>
+constexpr bool dv_block = std::is_same<PT, DeriveBlockParams>::value;
 
 // local voxel l of axis a as a voxel of the volume
 template <class PT>
@@ -68,7 +82,9 @@ __device__ __forceinline__ int dv_glob(const PT &P, int a, int l) {
 // local voxel (X, Y, Z) is a voxel of the volume that the stored box holds
 template <class PT>
 __device__ __forceinline__ bool dv_held(const PT &P, int X, int Y, int Z) {
-  if constexpr (dv_shard<PT>)
+  if constexpr (dv_block<PT>)
+    return X >= P.c0[0] && X < P.c1[0] && Y >= P.c0[1] && Y < P.c1[1] && Z >= P.c0[2] && Z < P.c1[2];
+  else if constexpr (dv_shard<PT>)
     return X >= 0 && X < P.D[0] && P.B.O[0] + X < P.N[0] && Y >= 0 && Y < P.D[1] && P.B.O[1] + Y < P.N[1] && Z >= 0 && Z < P.D[2] &&
            P.B.O[2] + Z < P.N[2];
   else return X >= 0 && X < P.N[0] && Y >= 0 && Y < P.N[1] && Z >= 0 && Z < P.N[2];
@@ -101,7 +117,9 @@ __device__ __forceinline__ void dv_load_tile(const PT &P, int x0, int y0, int z0
         if (SRC == SRC_PK_F32) {
           a = __uint_as_float(((const uint4 *)P.src)[((size_t)Z * P.D[1] + Y) * P.D[0] + X].x);
         } else {
-          const size_t o = ((size_t)Z * P.N[1] + Y) * P.N[0] + X;
+          size_t o;
+          if constexpr (dv_block<PT>) o = (size_t)(Z - P.bo[2]) * (size_t)P.pz + (size_t)(Y - P.bo[1]) * (size_t)P.py + (size_t)(X - P.bo[0]);
+          else o = ((size_t)Z * P.N[1] + Y) * P.N[0] + X;
           a = SRC == SMK_U8 ? (float)((const unsigned char *)P.src)[o] : SRC == SMK_U16 ? (float)((const unsigned short *)P.src)[o] : ((const float *)P.src)[o];
         }
       }
@@ -366,21 +384,63 @@ dim3 derive_grid(const DeriveParams &P) {
   return dim3((unsigned)((P.D[0] + DV_TX - 1) / DV_TX), (unsigned)((P.D[1] + DV_TY - 1) / DV_TY), (unsigned)((P.D[2] + DV_TZ - 1) / DV_TZ));
 }
 
-template <int SRC>
-hipError_t launch_derive_export(const DeriveShardParams &P, hipStream_t s) {
+template <int SRC, class PT>
+hipError_t launch_derive_export(const PT &P, hipStream_t s) {
   const dim3 grid = derive_grid(P);
   const long long ntiles = (long long)grid.x * grid.y * grid.z;
   if (ntiles > 0x7fffffffLL) return hipErrorInvalidValue;
   hipLaunchKernelGGL(smk_k_derive_seed_words, dim3(1), dim3(64), 0, s, P.words_out);
-  hipLaunchKernelGGL((smk_k_derive_stats<SRC, DeriveShardParams>), dim3((unsigned)std::min<long long>(ntiles, DV_STATS_BLOCKS)), dim3(256), 0, s, P,
+  hipLaunchKernelGGL((smk_k_derive_stats<SRC, PT>), dim3((unsigned)std::min<long long>(ntiles, DV_STATS_BLOCKS)), dim3(256), 0, s, P,
                      (int)grid.x, (int)grid.y, (int)ntiles);
   return hipGetLastError();
 }
 
-template <int SRC, int OUT>
-hipError_t launch_derive_write_shard(const DeriveShardParams &P, hipStream_t s) {
-  hipLaunchKernelGGL((smk_k_derive_write<SRC, OUT, DeriveShardParams>), derive_grid(P), dim3(256), 0, s, P);
+template <int SRC, int OUT, class PT>
+hipError_t launch_derive_write_shard(const PT &P, hipStream_t s) {
+  hipLaunchKernelGGL((smk_k_derive_write<SRC, OUT, PT>), derive_grid(P), dim3(256), 0, s, P);
   return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------- the block entries
+
+// the shard's parameters with the block as the source.  B: the region, and C shrunk by the reach as the result's valid box
+DeriveBlockParams derive_block_params(const smk_ctx *c, const void *src, const smk_block *b, const SmkBlockView &V, int compat, int blur) {
+  DeriveBlockParams P;
+  P.src = src;
+  P.out = nullptr;
+  P.st = nullptr;
+  for (int a = 0; a < 3; ++a) {
+    P.N[a] = c->N[a];
+    P.D[a] = c->D[a];
+    P.bo[a] = b->origin[a] - c->O[a];
+    P.c0[a] = V.c0[a] - c->O[a];
+    P.c1[a] = V.c1[a] - c->O[a];
+  }
+  P.py = V.py;
+  P.pz = V.pz;
+  P.compat = compat ? 1 : 0;
+  P.blur = blur ? 1 : 0;
+  P.normals = c->have_normals ? 1 : 0;
+  smk_step_block_box(c, V, DV_REACH, P.B);
+  P.words_out = nullptr;
+  P.words_in = nullptr;
+  return P;
+}
+
+template <int SRC>
+hipError_t launch_derive_write_block(const DeriveBlockParams &P, int out_dtype, hipStream_t s) {
+  if (out_dtype == SMK_U8) return launch_derive_write_shard<SRC, SMK_U8>(P, s);
+  if (out_dtype == SMK_U16) return launch_derive_write_shard<SRC, SMK_U16>(P, s);
+  return launch_derive_write_shard<SRC, SMK_F32>(P, s);
+}
+
+// what both block entries refuse of the scalar
+int derive_block_scalar_refusals(smk_ctx *c, const char *who, const void *d_scalar, smk_dtype dt) {
+  if (!d_scalar) FAIL(c, "%s: d_scalar is NULL", who);
+  if (dt != SMK_U8 && dt != SMK_U16 && dt != SMK_F32) FAIL(c, "%s: scalar_dtype %d is none of SMK_U8, SMK_U16, SMK_F32", who, (int)dt);
+  const size_t eb = smk_elem_bytes(dt);
+  if ((uintptr_t)d_scalar % eb) FAIL(c, "%s: d_scalar is not aligned to its %zu-byte elements", who, eb);
+  return 0;
 }
 
 }  // namespace
@@ -409,6 +469,52 @@ extern "C" int smk_step_extremes_device(smk_ctx *c, int kind, int step_src, int 
   const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   return kind == SMK_EXTREMES_DERIVE ? smk_derive_extremes_enqueue(c, who, step_src, compat, d_words, s)
                                      : smk_merge_extremes_enqueue(c, who, step_src, d_words, s);
+}
+
+extern "C" int smk_block_extremes_device(smk_ctx *c, int kind, const void *const *d_fields, int nf, smk_dtype dtype, const smk_block *b,
+                                         int compat, void *d_words, void *stream) {
+  if (!c) return 1;
+  const char *who = "smk_block_extremes_device";
+  HIPCHK(c, hipSetDevice(c->device));
+  if (kind != SMK_EXTREMES_DERIVE && kind != SMK_EXTREMES_MERGE)
+    FAIL(c, "%s: kind %d is neither SMK_EXTREMES_DERIVE (%d) nor SMK_EXTREMES_MERGE (%d)", who, kind, (int)SMK_EXTREMES_DERIVE,
+         (int)SMK_EXTREMES_MERGE);
+  if (!d_words) FAIL(c, "%s: d_words is NULL", who);
+  if ((uintptr_t)d_words % sizeof(int)) FAIL(c, "%s: d_words is not aligned to its 4-byte words", who);
+  const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  if (kind == SMK_EXTREMES_MERGE) return smk_merge_block_extremes_enqueue(c, who, d_fields, nf, dtype, b, d_words, s);
+  SmkBlockView V;
+  if (smk_step_block_refusals(c, derive_shard_entry(c, who), DV_REACH, nullptr, b, V)) return 1;
+  if (!d_fields) FAIL(c, "%s: d_fields is NULL", who);
+  if (nf != 1) FAIL(c, "%s: %d fields: the derive takes one scalar (nf 1)", who, nf);
+  if (derive_block_scalar_refusals(c, who, d_fields[0], dtype)) return 1;
+  DeriveBlockParams P = derive_block_params(c, d_fields[0], b, V, compat, 0);
+  P.words_out = (int *)d_words;
+  HIPCHK(c, dtype == SMK_U8 ? launch_derive_export<SMK_U8>(P, s) : dtype == SMK_U16 ? launch_derive_export<SMK_U16>(P, s)
+                                                                                     : launch_derive_export<SMK_F32>(P, s));
+  return 0;
+}
+
+extern "C" int smk_upload_timestep_scalar_block_device(smk_ctx *c, int timestep, const void *d_scalar, smk_dtype scalar_dtype,
+                                                       const smk_block *b, int compat, int blur, const void *d_words, void *stream) {
+  if (!c) return 1;
+  const char *who = "smk_upload_timestep_scalar_block_device";
+  HIPCHK(c, hipSetDevice(c->device));
+  SmkBlockView V;
+  if (smk_step_block_refusals(c, derive_shard_entry(c, who), DV_REACH, &timestep, b, V)) return 1;
+  if (derive_block_scalar_refusals(c, who, d_scalar, scalar_dtype)) return 1;
+  if (!d_words) FAIL(c, "%s: d_words is NULL", who);
+  if ((uintptr_t)d_words % sizeof(int)) FAIL(c, "%s: d_words is not aligned to its 4-byte words", who);
+  const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  return smk_step_produce(c, who, timestep, -1, -1, s, [&](TimeStep &T, const TimeStep *, const TimeStep *) -> int {
+    DeriveBlockParams P = derive_block_params(c, d_scalar, b, V, compat, blur);
+    P.out = T.vox;
+    P.words_in = (const int *)d_words;
+    HIPCHK(c, scalar_dtype == SMK_U8    ? launch_derive_write_block<SMK_U8>(P, c->dtype, s)
+              : scalar_dtype == SMK_U16 ? launch_derive_write_block<SMK_U16>(P, c->dtype, s) : launch_derive_write_block<SMK_F32>(P, c->dtype, s));
+    smk_step_block_done(c, V, DV_REACH, P.B, T);
+    return 0;
+  });
 }
 
 extern "C" int smk_derive_timestep_shard(smk_ctx *c, int step_src, int step_out, int compat, int blur, const void *d_words, void *stream) {

@@ -17,6 +17,9 @@
 //   pass 2 (smk_k_merge_write): the gradient again, G and the normal, and one 16-byte store of the unit (and the normal word of
 //          a four-channel f32 voxel).
 // The arithmetic is smk_prep.hip's, through smk_prep_device.h; the packed voxel is smk_packed.h's.
+// Instances of the two kernels over parameter types of their own serve sharded contexts (MergeShardParams: a packed step of
+// the ring) and a decomposed simulation's own dense blocks of the volume (MergeBlockParams: smk_block_extremes_device,
+// smk_upload_timestep_fields_block_device).
 #include <limits.h>
 
 #include <algorithm>
@@ -56,8 +59,19 @@ struct MergeShardParams : MergeParams {
   int *words_out;       // pass 1: the export
   const int *words_in;  // pass 2: the combined maximum
 };
+// The BLOCK instances (smk.h: smk_block_extremes_device, smk_upload_timestep_fields_block_device): shard instances whose fields
+// are a rank's own dense blocks of the volume, all laid out by one smk_block that lies anywhere.  Units, tiles, the region, the
+// valid box and every index into the slot are the shard's; only the SOURCE differs: a voxel is read when it lies inside
+// C = block ∩ stored box ∩ volume, at (local - bo) through the block's pitches.  Again a parameter type of its own
+struct MergeBlockParams : MergeShardParams {
+  int bo[3];          // the block's element [0][0][0] in LOCAL voxels of the stored box (negative: the block starts before the box)
+  int c0[3], c1[3];   // C, local voxels: what of the block's extent this context takes
+  long long py, pz;   // elements between two rows, two slices of the block
+};
 template <class PT>
-constexpr bool mg_shard = std::is_same<PT, MergeShardParams>::value;
+constexpr bool mg_shard = std::is_base_of<MergeShardParams, PT>::value;
+template <class PT>
+constexpr bool mg_block = std::is_same<PT, MergeBlockParams>::value;
 
 // local voxel l of axis a as a voxel of the volume
 template <class PT>
@@ -72,8 +86,8 @@ constexpr int mg_vpu(int SRC) { return mg_ring(SRC) == SMK_F32 ? 1 : 2;  }  // v
 // The fields of the voxels of unit U of row Y of slice Z as they are stored -- a byte, a 16-bit value or a float's word each --:
 // r[c][e], voxel c of the unit, field e.  A unit outside the stored box (and a dense voxel outside the volume) is zeros and is
 // never read: no interior voxel has such a neighbour
-template <int SRC, int NF>
-__device__ __forceinline__ void mg_cell(const MergeParams &P, int U, int Y, int Z, uint32_t r[][NF]) {
+template <int SRC, int NF, class PT>
+__device__ __forceinline__ void mg_cell(const PT &P, int U, int Y, int Z, uint32_t r[][NF]) {
   constexpr int VPU = mg_vpu(SRC);
 #pragma unroll
   for (int c = 0; c < VPU; ++c)
@@ -92,6 +106,19 @@ __device__ __forceinline__ void mg_cell(const MergeParams &P, int U, int Y, int 
 #pragma unroll
       for (int e = 0; e < NF; ++e)
         r[c][e] = SRC == SRC_PK_U8 ? smk_u8_ch(w0, e) : e == 0 ? smk_vox8_c0<SMK_U16>(w0) : smk_vox8_c1<SMK_U16>(w0);
+    }
+  } else if constexpr (mg_block<PT>) {  // dense fields of a block: the voxels inside C, through the pitches
+    if (Y < P.c0[1] || Y >= P.c1[1] || Z < P.c0[2] || Z >= P.c1[2]) return;
+    const size_t row = (size_t)(Z - P.bo[2]) * (size_t)P.pz + (size_t)(Y - P.bo[1]) * (size_t)P.py;
+#pragma unroll
+    for (int c = 0; c < VPU; ++c) {
+      const int X = U * VPU + c;
+      if (X < P.c0[0] || X >= P.c1[0]) continue;
+      const size_t o = row + (size_t)(X - P.bo[0]);
+#pragma unroll
+      for (int e = 0; e < NF; ++e)
+        r[c][e] = SRC == SMK_U8 ? (uint32_t)((const unsigned char *)P.f[e])[o]
+                : SRC == SMK_U16 ? (uint32_t)((const unsigned short *)P.f[e])[o] : ((const uint32_t *)P.f[e])[o];
     }
   } else {  // dense fields, read at their element size
     if (Y >= P.N[1]) return;
@@ -394,19 +421,19 @@ bool merge_shard_params(const smk_ctx *c, const TimeStep &S, MergeShardParams &P
   return true;
 }
 
-template <int SRC, int NF>
-hipError_t launch_merge_shard(const MergeShardParams &P, bool write, hipStream_t s) {
+template <int SRC, int NF, class PT>
+hipError_t launch_merge_shard(const PT &P, bool write, hipStream_t s) {
   if (write) {
-    hipLaunchKernelGGL((smk_k_merge_write<SRC, NF, MergeShardParams>), dim3((unsigned)P.ntiles), dim3(256), 0, s, P);
+    hipLaunchKernelGGL((smk_k_merge_write<SRC, NF, PT>), dim3((unsigned)P.ntiles), dim3(256), 0, s, P);
   } else {
     hipLaunchKernelGGL(smk_k_merge_seed_words, dim3(1), dim3(64), 0, s, P.words_out);
-    hipLaunchKernelGGL((smk_k_merge_max<SRC, NF, MergeShardParams>), dim3(std::min<unsigned>((unsigned)P.ntiles, MG_MAX_BLOCKS)), dim3(256), 0, s, P);
+    hipLaunchKernelGGL((smk_k_merge_max<SRC, NF, PT>), dim3(std::min<unsigned>((unsigned)P.ntiles, MG_MAX_BLOCKS)), dim3(256), 0, s, P);
   }
   return hipGetLastError();
 }
 
-template <int SRC>
-hipError_t launch_merge_shard_nf(const MergeShardParams &P, int nf, bool write, hipStream_t s) {
+template <int SRC, class PT>
+hipError_t launch_merge_shard_nf(const PT &P, int nf, bool write, hipStream_t s) {
   if (nf == 1) return launch_merge_shard<SRC, 1>(P, write, s);
   if (nf == 2) return launch_merge_shard<SRC, 2>(P, write, s);
   if constexpr (mg_ring(SRC) != SMK_U16) {
@@ -421,7 +448,86 @@ hipError_t launch_merge_shard_dtype(const smk_ctx *c, const MergeShardParams &P,
          : c->dtype == SMK_U16 ? launch_merge_shard_nf<SRC_PK_U16>(P, nf, write, s) : launch_merge_shard_nf<SRC_PK_F32>(P, nf, write, s);
 }
 
+// ---------------------------------------------------------------------------------------------- the block entries
+
+// What both block entries refuse, and the shard's parameters with the block's fields as the source (B: the region, and C shrunk
+// by the reach as the result's valid box).  step_out: null for the export
+int merge_block_params(smk_ctx *c, const char *who, const int *step_out, const void *const *d_fields, int nf, smk_dtype dt, const smk_block *b,
+                       SmkBlockView &V, MergeBlockParams &P) {
+  if (smk_step_block_refusals(c, merge_shard_entry(c, who), MG_REACH, step_out, b, V)) return 1;
+  if (!d_fields) FAIL(c, "%s: d_fields is NULL", who);
+  if (nf != c->nelts - 1) FAIL(c, "%s: %d fields for a series of nelts %d: the fields are nelts - 1 = %d", who, nf, c->nelts, c->nelts - 1);
+  if ((int)dt != c->dtype) FAIL(c, "%s: field_dtype %d is not the ring's type (%d): the fields are stored as they come", who, (int)dt, c->dtype);
+  const size_t eb = smk_elem_bytes(dt);
+  for (int e = 0; e < nf; ++e) {
+    if (!d_fields[e]) FAIL(c, "%s: d_fields[%d] is NULL", who, e);
+    if ((uintptr_t)d_fields[e] % eb) FAIL(c, "%s: d_fields[%d] is not aligned to its %zu-byte elements", who, e, eb);
+  }
+  const int VPU = c->dtype == SMK_F32 ? 1 : 2;
+  const long long ux = (c->D[0] / VPU + MG_UX - 1) / MG_UX, uy = (c->D[1] + MG_TY - 1) / MG_TY, uz = (c->D[2] + MG_TZ - 1) / MG_TZ;
+  if (ux * uy * uz > 0x7fffffffLL) FAIL(c, "%s: a %dx%dx%d stored box has more than 2^31 tiles", who, c->D[0], c->D[1], c->D[2]);
+  P.src = nullptr;
+  for (int e = 0; e < 3; ++e) P.f[e] = e < nf ? d_fields[e] : nullptr;
+  P.out = nullptr;
+  P.nrm = nullptr;
+  P.mx = nullptr;
+  for (int a = 0; a < 3; ++a) {
+    P.N[a] = c->N[a];
+    P.D[a] = c->D[a];
+    P.bo[a] = b->origin[a] - c->O[a];
+    P.c0[a] = V.c0[a] - c->O[a];
+    P.c1[a] = V.c1[a] - c->O[a];
+  }
+  P.py = V.py;
+  P.pz = V.pz;
+  P.normals = c->have_normals ? 1 : 0;
+  P.ux = (int)ux;
+  P.uy = (int)(ux * uy);
+  P.ntiles = (int)(ux * uy * uz);
+  smk_step_block_box(c, V, MG_REACH, P.B);
+  P.words_out = nullptr;
+  P.words_in = nullptr;
+  return 0;
+}
+
+hipError_t launch_merge_block_dtype(const smk_ctx *c, const MergeBlockParams &P, bool write, hipStream_t s) {
+  const int nf = c->nelts - 1;
+  return c->dtype == SMK_U8    ? launch_merge_shard_nf<SMK_U8>(P, nf, write, s)
+         : c->dtype == SMK_U16 ? launch_merge_shard_nf<SMK_U16>(P, nf, write, s) : launch_merge_shard_nf<SMK_F32>(P, nf, write, s);
+}
+
 }  // namespace
+
+int smk_merge_block_extremes_enqueue(smk_ctx *c, const char *who, const void *const *d_fields, int nf, smk_dtype dtype, const smk_block *b,
+                                     void *d_words, hipStream_t s) {
+  SmkBlockView V;
+  MergeBlockParams P;
+  if (merge_block_params(c, who, nullptr, d_fields, nf, dtype, b, V, P)) return 1;
+  P.words_out = (int *)d_words;
+  HIPCHK(c, launch_merge_block_dtype(c, P, false, s));
+  return 0;
+}
+
+extern "C" int smk_upload_timestep_fields_block_device(smk_ctx *c, int timestep, const void *const *d_fields, int nf, smk_dtype field_dtype,
+                                                       const smk_block *b, const void *d_words, void *stream) {
+  if (!c) return 1;
+  const char *who = "smk_upload_timestep_fields_block_device";
+  HIPCHK(c, hipSetDevice(c->device));
+  SmkBlockView V;
+  MergeBlockParams P;
+  if (merge_block_params(c, who, &timestep, d_fields, nf, field_dtype, b, V, P)) return 1;
+  if (!d_words) FAIL(c, "%s: d_words is NULL", who);
+  if ((uintptr_t)d_words % sizeof(int)) FAIL(c, "%s: d_words is not aligned to its 4-byte words", who);
+  const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  return smk_step_produce(c, who, timestep, -1, -1, s, [&](TimeStep &T, const TimeStep *, const TimeStep *) -> int {
+    P.out = T.vox;
+    P.nrm = smk_step_separate_normals(c) ? T.nrm : nullptr;
+    P.words_in = (const int *)d_words;
+    HIPCHK(c, launch_merge_block_dtype(c, P, true, s));
+    smk_step_block_done(c, V, MG_REACH, P.B, T);
+    return 0;
+  });
+}
 
 int smk_merge_extremes_enqueue(smk_ctx *c, const char *who, int step_src, void *d_words, hipStream_t s) {
   int ksrc = -1;

@@ -18,6 +18,8 @@
 //   - a producer (blend, derive, merge: kernels that make a step from what is on the device) runs inside smk_step_produce,
 //     which is all of the above once: the output slot by the ring's rule, the sources' and the output slot's waits, the
 //     producer's kernels, the brick summaries, `ready`, the sources' read events.
+#include <limits.h>
+
 #include <algorithm>
 
 #include "smk_internal.h"
@@ -355,7 +357,8 @@ static bool volume_face(const smk_ctx *c, int a, int hi) { return hi ? c->O[a] +
 
 int smk_step_shown_halo(const smk_ctx *c) { return c->ts_cur >= 0 ? c->ts[(size_t)c->ts_cur].valid_halo : c->halo; }
 
-int smk_step_shard_refusals(smk_ctx *c, const StencilEntry &E, int reach, int step_src, const int *step_out, int *ksrc) {
+// what the shard and the block entries refuse of the context before they look at a source
+static int shard_context_refusals(smk_ctx *c, const StencilEntry &E) {
   const char *who = E.who;
   if (!c->have_volume) FAIL(c, "%s: no volume uploaded", who);
   if (!E.nelts_why.empty()) FAIL(c, "%s: %s", who, E.nelts_why.c_str());
@@ -374,6 +377,12 @@ int smk_step_shard_refusals(smk_ctx *c, const StencilEntry &E, int reach, int st
          c->O[0], c->O[1], c->O[2], c->N[0], c->N[1], c->N[2]);
   if (c->N[0] < 3 || c->N[1] < 3 || c->N[2] < 3)
     FAIL(c, "%s: a %dx%dx%d volume has no interior voxel (dims >= 3, as %s)", who, c->N[0], c->N[1], c->N[2], E.prep_entry);
+  return 0;
+}
+
+int smk_step_shard_refusals(smk_ctx *c, const StencilEntry &E, int reach, int step_src, const int *step_out, int *ksrc) {
+  const char *who = E.who;
+  if (shard_context_refusals(c, E)) return 1;
   *ksrc = step_src < 0 ? -1 : smk_step_slot(c, step_src);
   if (*ksrc < 0) FAIL(c, "%s: time step %d (the source) is not cached", who, step_src);
   if (step_out) {
@@ -400,6 +409,69 @@ void smk_step_shard_box(const smk_ctx *c, const TimeStep &src, int reach, SmkSha
 
 void smk_step_shard_done(const smk_ctx *c, const TimeStep &src, int reach, const SmkShardBox &B, TimeStep &out) {
   out.valid_halo = c->nranks > 1 ? src.valid_halo - reach : src.valid_halo;
+  for (int a = 0; a < 3; ++a) {
+    out.vlo[a] = B.v0[a] + c->O[a];
+    out.vhi[a] = B.v1[a] + c->O[a];
+  }
+}
+
+// ---------------------------------------------------------------------- blocks of a decomposed simulation: what is valid
+
+int smk_block_view(smk_ctx *c, const char *who, const smk_block *b, SmkBlockView &V) {
+  if (!b) FAIL(c, "%s: block is NULL", who);
+  for (int a = 0; a < 3; ++a)
+    if (b->size[a] <= 0) FAIL(c, "%s: block size %dx%dx%d: sizes are > 0", who, b->size[0], b->size[1], b->size[2]);
+  V.py = b->pitch_y ? b->pitch_y : (long long)b->size[0];
+  if (V.py < b->size[0]) FAIL(c, "%s: pitch_y %lld is below the block's %d voxels per row", who, b->pitch_y, b->size[0]);
+  // (by division: py * size[1] <= pz exactly when py <= pz / size[1], and no product of a caller's numbers can overflow)
+  if (V.py > LLONG_MAX / b->size[1] / b->size[2])
+    FAIL(c, "%s: pitch_y %lld: a block of %d rows and %d slices of that pitch is beyond any address", who, b->pitch_y, b->size[1], b->size[2]);
+  V.pz = b->pitch_z ? b->pitch_z : V.py * b->size[1];
+  if (V.py > V.pz / b->size[1])
+    FAIL(c, "%s: pitch_z %lld is below the block's %d rows of pitch %lld", who, b->pitch_z, b->size[1], V.py);
+  if (V.pz > LLONG_MAX / b->size[2])
+    FAIL(c, "%s: pitch_z %lld: a block of %d slices of that pitch is beyond any address", who, b->pitch_z, b->size[2]);
+  for (int a = 0; a < 3; ++a)
+    if (b->origin[a] < 0 || b->origin[a] > c->N[a] - b->size[a])
+      FAIL(c, "%s: the block [%d, %d) of axis %c lies outside the volume %dx%dx%d (pass a view of the array that lies inside)", who, b->origin[a],
+           b->origin[a] + b->size[a], "xyz"[a], c->N[0], c->N[1], c->N[2]);
+  V.halo = c->halo;
+  for (int a = 0; a < 3; ++a) {
+    V.c0[a] = std::max(b->origin[a], c->O[a]);
+    V.c1[a] = std::min(b->origin[a] + b->size[a], std::min(c->O[a] + c->D[a], c->N[a]));
+    if (V.c0[a] > c->g0[a] || V.c1[a] < c->g1[a])
+      FAIL(c, "%s: the block holds voxels [%d, %d) of axis %c inside this context's stored box, its region is [%d, %d): the block must contain "
+              "the region", who, V.c0[a], std::max(V.c1[a], V.c0[a]), "xyz"[a], c->g0[a], c->g1[a]);
+    // (beyond a face of C that is the volume's lies no voxel: that side gives all a halo can)
+    if (c->g0[a] > 0 && V.c0[a] > 0) V.halo = std::min(V.halo, c->g0[a] - V.c0[a]);
+    if (c->g1[a] < c->N[a] && V.c1[a] < c->N[a]) V.halo = std::min(V.halo, V.c1[a] - c->g1[a]);
+  }
+  return 0;
+}
+
+int smk_step_block_refusals(smk_ctx *c, const StencilEntry &E, int reach, const int *step_out, const smk_block *b, SmkBlockView &V) {
+  const char *who = E.who;
+  if (shard_context_refusals(c, E)) return 1;
+  if (step_out && *step_out < 0) FAIL(c, "%s: time step %d: ids are >= 0", who, *step_out);
+  if (smk_block_view(c, who, b, V)) return 1;
+  if (c->nranks > 1 && V.halo < reach + 1)
+    FAIL(c, "%s: the block gives a valid halo of %d voxels, the stencil reaches %d and the result keeps one for a frame: a valid halo >= %d is "
+            "needed (ghost cells handed over, and option 'halo', set before the volume)", who, V.halo, reach, reach + 1);
+  return 0;
+}
+
+void smk_step_block_box(const smk_ctx *c, const SmkBlockView &V, int reach, SmkShardBox &B) {
+  for (int a = 0; a < 3; ++a) {
+    B.O[a] = c->O[a];
+    B.r0[a] = c->g0[a] - c->O[a];
+    B.r1[a] = c->g1[a] - c->O[a];
+    B.v0[a] = (V.c0[a] == 0 ? V.c0[a] : V.c0[a] + reach) - c->O[a];
+    B.v1[a] = (V.c1[a] >= c->N[a] ? V.c1[a] : V.c1[a] - reach) - c->O[a];
+  }
+}
+
+void smk_step_block_done(const smk_ctx *c, const SmkBlockView &V, int reach, const SmkShardBox &B, TimeStep &out) {
+  out.valid_halo = c->nranks > 1 ? V.halo - reach : V.halo;
   for (int a = 0; a < 3; ++a) {
     out.vlo[a] = B.v0[a] + c->O[a];
     out.vhi[a] = B.v1[a] + c->O[a];

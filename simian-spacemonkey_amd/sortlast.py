@@ -362,3 +362,43 @@ def stencil_timestep_local(renderers, kind, src, out, compat=1, blur=0, stream=N
         else:
             R.merge_timestep_shard(src, out, words[nranks].data_ptr(), stream=stream)
     return words
+
+
+def stencil_block_local(renderers, kind, blocks, out, compat=1, blur=0, stream=None, words=None):
+    """stencil_timestep_local from the ranks' OWN dense blocks of the volume in place of a cached step (smk.h, "Blocks of a
+    decomposed simulation"): step `out` becomes the derived (kind "derive") or merged (kind "merge") step of the scalar or the
+    fields every rank holds for its sub-domain, ghost cells included.  blocks: per rank (ptrs, dtype, block) -- the device
+    addresses of the dense arrays (one scalar for the derive, nelts - 1 fields for the merge), their dtype code and the
+    smk_block() that lays all of them out.  Every rank exports the extremes of its region (smk_block_extremes_device), the
+    eight words combine by elementwise integer maximum, and every rank runs the write pass with the combined words
+    (smk_upload_timestep_scalar_block_device / smk_upload_timestep_fields_block_device).  No voxel moves between ranks, and no
+    rank sees an array it does not hold.  A multi-process host does the same with one integer MAX all-reduce of 8 words.
+    stream, words and the return value: as stencil_timestep_local; `stream` also orders the reads of the blocks."""
+    from .binding import EXTREMES_DERIVE, EXTREMES_MERGE
+    if kind not in ("derive", "merge"):
+        raise ValueError("kind must be 'derive' or 'merge', got %r" % (kind,))
+    nranks = len(renderers)
+    if len(blocks) != nranks:
+        raise ValueError("%d blocks for %d ranks" % (len(blocks), nranks))
+    dev = torch.device("cuda", renderers[0].device)
+    if words is None:
+        words = torch.empty((nranks + 1, 8), dtype=torch.int32, device=dev)
+    if tuple(words.shape) != (nranks + 1, 8) or words.dtype != torch.int32 or not words.is_contiguous():
+        raise ValueError("words must be a contiguous [%d][8] int32 tensor" % (nranks + 1))
+    k = EXTREMES_DERIVE if kind == "derive" else EXTREMES_MERGE
+    for r, (R, (ptrs, dtype, block)) in enumerate(zip(renderers, blocks)):
+        R.block_extremes_device(k, ptrs, dtype, block, words[r].data_ptr(), compat=compat, stream=stream)
+    if stream is None:
+        torch.cuda.synchronize(dev)  # the combine's wait: every rank's export, each on its context's stream, is in memory
+        words[nranks].copy_(words[:nranks].amax(0))
+        torch.cuda.current_stream(dev).synchronize()  # ... and the combined words, before the contexts' streams read them
+    else:
+        handle = stream.value if hasattr(stream, "value") else int(stream)
+        with torch.cuda.stream(torch.cuda.ExternalStream(handle, device=dev)):  # behind the exports, before the write passes
+            words[nranks].copy_(words[:nranks].amax(0))
+    for R, (ptrs, dtype, block) in zip(renderers, blocks):
+        if kind == "derive":
+            R.upload_timestep_scalar_block_device(out, ptrs[0], dtype, block, words[nranks].data_ptr(), compat=compat, blur=blur, stream=stream)
+        else:
+            R.upload_timestep_fields_block_device(out, ptrs, dtype, block, words[nranks].data_ptr(), stream=stream)
+    return words

@@ -37,7 +37,14 @@ Frame times are HIP-event times on the render stream (median); the loop also rep
      entries alone on a step of edge^3, `repeats` times over so that their run-to-run spread shows; the shard rank as a ratio
      to the unsharded entry per voxel written.  Replaces the section "## Times on one MI355X" of profiles/step_shard.md (what
      stands before it, the kernels' resource table, stays; --out PATH: another file, treated alike).
-    python tools/timestep_time.py --shards [--out PATH] [volume edge] [repeats]"""
+    python tools/timestep_time.py --shards [--out PATH] [volume edge] [repeats]
+  8. --blocks: time steps from a rank's own dense block (smk_block_extremes_device + smk_upload_timestep_scalar_block_device /
+     smk_upload_timestep_fields_block_device).  Rank 0 of an 8-way shard of a series of that edge, declared without data, halo
+     4: the block route's export + write for u8, u16 and f32 rings, HIP events, `repeats` rounds after warm-up; in the same
+     run the packed route, the only one before: smk_upload_timestep_device of the whole volume's interleaved array, then
+     smk_step_extremes_device, then smk_*_timestep_shard.  Replaces the section "## Times on one MI355X" of
+     profiles/step_block.md (what stands before it, the kernels' resource table, stays).
+    python tools/timestep_time.py --blocks [--out PATH] [volume edge] [repeats]"""
 import os
 import statistics
 import sys
@@ -669,19 +676,113 @@ def shards_leg(pkg, n, repeats, out_path):
     print("wrote", out_path, flush=True)
 
 
+def blocks_leg(pkg, n, repeats, out_path):
+    """rank 0 of an 8-way shard of an n^3 series: the block route against the packed route, per ring and producer"""
+    halo, warm = 4, 3
+    e = n // 2 + halo                                        # rank 0's block: its region and `halo` ghost cells, from voxel 0
+    lines = ["## Times on one MI355X", "",
+             "Written by `tools/timestep_time.py --blocks %d %d`.  Rank 0 of an 8-way shard of a %d^3 series (three channels, no" % (n, repeats, n),
+             "normals, halo %d), declared with `smk_declare_volume`; the rank's block is its region plus %d ghost cells, %d^3 elements" % (halo, halo, e),
+             "from voxel 0.  HIP events on one stream, median of %d after %d warm-up rounds (min - max).  *Block route*:" % (repeats, warm),
+             "`smk_block_extremes_device` + the block write pass, straight from the dense arrays.  *Packed route*, the only one before",
+             "the block entries: `smk_upload_timestep_device` of the WHOLE volume's interleaved `(s, 0, 0)` or `(f0, f1, 0)` array (which",
+             "a rank of a decomposed simulation does not hold), then `smk_step_extremes_device`, then `smk_*_timestep_shard`.  Both write",
+             "passes read the rank's own exported words: the combine is a host's 8-word MAX all-reduce and no device work.", "",
+             "| ring | entry | block route ms | its export ms | its write ms | packed route ms | its pack ms | its export ms | its write ms | block / packed |",
+             "|---|---|---|---|---|---|---|---|---|---|"]
+    st = torch.cuda.Stream()
+    sb = st.cuda_stream
+    med = statistics.median
+    tdt = {"u8": torch.uint8, "u16": torch.int16, "f32": torch.float32}
+    for dtype in ("u8", "u16", "f32"):
+        dt = {"u8": 0, "f32": 1, "u16": 2}[dtype]
+        R = pkg.Renderer(0)
+        try:
+            R.set_shard(0, 8)
+            R.set_option("halo", halo)
+            R.set_timestep_cache(4)
+            R.declare_volume((n, n, n), 3, dt, normals=False)
+            g = torch.Generator(device="cuda").manual_seed(7)
+            whole = torch.zeros((n, n, n, 3), dtype=tdt[dtype], device="cuda")       # the packed route's array: the whole volume
+            for ch in (0, 1):
+                f = torch.rand((n, n, n), generator=g, device="cuda")
+                whole[..., ch] = f if dtype == "f32" else (f * (255 if dtype == "u8" else 32767)).to(tdt[dtype])
+            del f
+            fields = [whole[:e, :e, :e, ch].contiguous() for ch in (0, 1)]           # the block route's: the rank's own dense arrays
+            blk = pkg.smk_block((0, 0, 0), (e, e, e))
+            words = torch.zeros(8, dtype=torch.int32, device="cuda")
+            torch.cuda.synchronize()
+            wp = words.data_ptr()
+            for kind, code in (("derive", 0), ("merge", 1)):
+                ptrs = [f.data_ptr() for f in (fields[:1] if kind == "derive" else fields)]
+                if kind == "derive":
+                    whole[..., 1] = 0                        # (s, 0, 0); the second field comes back for the merge below
+                    torch.cuda.synchronize()
+
+                def bex():
+                    R.block_extremes_device(code, ptrs, dt, blk, wp, stream=sb)
+
+                def bwr():
+                    if kind == "derive":
+                        R.upload_timestep_scalar_block_device(12, ptrs[0], dt, blk, wp, 1, 0, stream=sb)
+                    else:
+                        R.upload_timestep_fields_block_device(12, ptrs, dt, blk, wp, stream=sb)
+
+                def pack():
+                    R.upload_timestep_device(10, whole.data_ptr(), (n, n, n), 3, dt, None, stream=sb)
+
+                def pex():
+                    R.step_extremes_device(code, 10, wp, stream=sb)
+
+                def pwr():
+                    if kind == "derive":
+                        R.derive_timestep_shard(10, 13, wp, 1, 0, stream=sb)
+                    else:
+                        R.merge_timestep_shard(10, 13, wp, stream=sb)
+                t = {k: [] for k in ("b", "bex", "bwr", "p", "pack", "pex", "pwr")}
+                for i in range(warm + repeats):
+                    t["b"].append(event_ms(st, lambda: (bex(), bwr())))
+                    t["p"].append(event_ms(st, lambda: (pack(), pex(), pwr())))
+                    for k, f in (("bex", bex), ("bwr", bwr), ("pack", pack), ("pex", pex), ("pwr", pwr)):
+                        t[k].append(event_ms(st, f))
+                assert R.timestep_halo(12) == R.timestep_halo(13) == halo - (2 if kind == "derive" else 1)
+                t = {k: v[warm:] for k, v in t.items()}
+                lines.append("| %s | %s | %s | %.2f |" % (dtype, kind, " | ".join(
+                    "%.3f (%.3f - %.3f)" % (med(t[k]), min(t[k]), max(t[k])) for k in ("b", "bex", "bwr", "p", "pack", "pex", "pwr")),
+                    med(t["b"]) / med(t["p"])))
+                print(lines[-1], flush=True)
+                if kind == "derive":                         # the second field again, for the merge
+                    whole[:e, :e, :e, 1] = fields[1]
+                    torch.cuda.synchronize()
+        finally:
+            R.close()
+            del whole, fields
+            torch.cuda.empty_cache()
+            torch.cuda.synchronize()
+    head = open(out_path).read() if os.path.exists(out_path) else ""
+    if lines[0] in head:
+        head = head[:head.index(lines[0])]
+    if head and not head.endswith("\n\n"):
+        head = head.rstrip("\n") + "\n\n"
+    open(out_path, "w").write(head + "\n".join(lines) + "\n")
+    print("wrote", out_path, flush=True)
+
+
 def main():
     args = sys.argv[1:]
     blend, download, derive, merge = "--blend" in args, "--download" in args, "--derive" in args, "--merge" in args
-    shards = "--shards" in args
+    shards, blocks = "--shards" in args, "--blocks" in args
     out_path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                            "step_shard.md" if shards else "step_merge.md" if merge else "step_derive.md" if derive else "step_download.md" if download else "timestep_blend.md")
+                            "step_block.md" if blocks else "step_shard.md" if shards else "step_merge.md" if merge else "step_derive.md" if derive else "step_download.md" if download else "timestep_blend.md")
     if "--out" in args:
         out_path = args[args.index("--out") + 1]
         del args[args.index("--out"):args.index("--out") + 2]
-    args = [a for a in args if a not in ("--blend", "--download", "--derive", "--merge", "--shards")]
+    args = [a for a in args if a not in ("--blend", "--download", "--derive", "--merge", "--shards", "--blocks")]
     n = int(args[0]) if len(args) > 0 else 512
     loop = int(args[1]) if len(args) > 1 else 32
     pkg = bench.load_package()
+    if blocks:
+        return blocks_leg(pkg, n, int(args[1]) if len(args) > 1 else 5, out_path)
     if shards:
         return shards_leg(pkg, n, int(args[1]) if len(args) > 1 else 3, out_path)
     if merge:
