@@ -232,8 +232,10 @@ int smk_upload_timestep_fields_device(smk_ctx *ctx, int timestep, const void *co
  *   SMK_EXTREMES_MERGE   {ord(max magnitude), INT_MIN x 7}: of the summed gradient over the region's interior voxels (a u8
  *                        ring: of all magnitudes; u16 and f32: of the finite ones); the seed is ord(0.0f) = 0
  * The maximum over the ranks' words equals, bit for bit, the words an unsharded context exports for the same step.
- * THE VALID BOX.  The result is exact on the stored box cut at the volume and then shrunk by r at every face that is not a
- * face of the volume (a face is the volume's when the stored box starts at voxel 0 or ends at or beyond the volume's last):
+ * THE VALID BOX.  The result is exact on the SOURCE's valid box shrunk by r at every face of it that is not a face of the
+ * volume (a face is the volume's when the source's valid box starts at voxel 0 or ends at the volume's last voxel; an
+ * uploaded source is valid on the stored box cut at the volume, a block step on its C, which may end inside a stored box
+ * that reaches the volume's face):
  * there every stored field and normal byte is what smk_derive_timestep / smk_merge_timestep store at that voxel on an
  * unsharded context -- the 1-voxel border (decided on the volume's coordinates) and the pad column and row included.  The
  * other stored voxels, the RIM, are written as zeros with the normal (128, 128, 128); zeros can only widen a brick's summary

@@ -352,8 +352,9 @@ int smk_step_stencil_refusals(smk_ctx *c, const StencilEntry &E, int step_out, c
 
 // ---------------------------------------------------------------------- the stencil producers on a shard: what is valid
 
-// a face of the stored box that is a face of the volume loses nothing to a stencil: beyond it lies no voxel
-static bool volume_face(const smk_ctx *c, int a, int hi) { return hi ? c->O[a] + c->D[a] >= c->N[a] : c->O[a] == 0; }
+// a face of the SOURCE's valid box that is a face of the volume loses nothing to a stencil: beyond it lies no voxel.  (Not
+// a face of the stored box: a block step with ghosts narrower than option "halo" is valid from voxel 2 of a box stored from 0.)
+static bool volume_face(const smk_ctx *c, const TimeStep &src, int a, int hi) { return hi ? src.vhi[a] >= c->N[a] : src.vlo[a] == 0; }
 
 int smk_step_shown_halo(const smk_ctx *c) { return c->ts_cur >= 0 ? c->ts[(size_t)c->ts_cur].valid_halo : c->halo; }
 
@@ -402,8 +403,8 @@ void smk_step_shard_box(const smk_ctx *c, const TimeStep &src, int reach, SmkSha
     B.O[a] = c->O[a];
     B.r0[a] = c->g0[a] - c->O[a];
     B.r1[a] = c->g1[a] - c->O[a];
-    B.v0[a] = (volume_face(c, a, 0) ? src.vlo[a] : src.vlo[a] + reach) - c->O[a];
-    B.v1[a] = (volume_face(c, a, 1) ? src.vhi[a] : src.vhi[a] - reach) - c->O[a];
+    B.v0[a] = (volume_face(c, src, a, 0) ? src.vlo[a] : src.vlo[a] + reach) - c->O[a];
+    B.v1[a] = (volume_face(c, src, a, 1) ? src.vhi[a] : src.vhi[a] - reach) - c->O[a];
   }
 }
 

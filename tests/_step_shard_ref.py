@@ -50,10 +50,11 @@ def uploaded_valid(dims, O, D):
 
 def valid_box(dims, O, D, reach, src=None):
     """the valid box (lo, hi), global voxels, of a stencil of `reach` over a source whose valid box is `src` (None: an
-    upload's): shrunk by `reach` at every face of the stored box that is not a face of the volume"""
+    upload's): the source's shrunk by `reach` at every face of it that is not a face of the volume.  An upload's valid box is
+    the stored box cut at the volume, so for an upload these are the faces of the stored box"""
     slo, shi = src or uploaded_valid(dims, O, D)
-    lo = tuple(slo[a] if O[a] == 0 else slo[a] + reach for a in range(3))
-    hi = tuple(shi[a] if O[a] + D[a] >= dims[a] else shi[a] - reach for a in range(3))
+    lo = tuple(slo[a] if slo[a] == 0 else slo[a] + reach for a in range(3))
+    hi = tuple(shi[a] if shi[a] >= dims[a] else shi[a] - reach for a in range(3))
     return lo, hi
 
 
