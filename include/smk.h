@@ -214,6 +214,24 @@ int smk_merge_timestep(smk_ctx *ctx, int step_src, int step_out, void *stream);
  * that are not the series'. */
 int smk_upload_timestep_fields_device(smk_ctx *ctx, int timestep, const void *const *d_fields, int nf, smk_dtype field_dtype,
                                       int sx, int sy, int sz, void *stream);
+/* Merged fields of a step WITH H and blurred normals (MetaVolume::mergeMV with addG, addH and blurnorms: gluvv's -addH and
+ * -blurNormals; the data modes SMK_GDM_V1GH, _V2GH).  smk_merge_timestep with three flags: with nf = nelts - 1 - add_h, step
+ * `step_out` becomes the step that smk_upload_timestep_device packs from what smk_merge_fields_h_device (ring SMK_U8) or
+ * smk_merge_fields_h_f32_device (SMK_F32; SMK_U16 as in smk_merge_timestep: F = (float)v, G and H each through
+ * smk_quantize_u16_device, H then stored as the pack's 8-bit field, the normals from the floats) make of the first nf stored
+ * channels of `step_src`, bit for bit; the contract of the arithmetic stands at those entries below.  Channels: the nf fields,
+ * G, and with add_h H.  With add_h = 0 and blur = 0 the stored bits are smk_merge_timestep's.
+ * Two kernels on `stream`: pass 1 leaves {maximum magnitude, min H, max H} as ordered integers in three device words of the
+ * OUTPUT slot, seeded on the stream; pass 2 writes the packed voxels, zeros in the pad column and row, and the brick summaries
+ * follow.  No host wait, no allocation, no scratch arrays.  Slots, the in-place overwrite of a cached step_out, ordering and
+ * refusals are smk_merge_timestep's.  Refused in addition, changing nothing: add_h or blur outside 0 / 1; nelts - 1 - add_h < 1;
+ * add_h on a SMK_U16 ring with nelts != 3; a sharded context (the stencil reaches 2 voxels beyond region + halo and the scaling
+ * needs the whole volume's three extremes: the shard and block forms do not exist yet). */
+int smk_merge_timestep_h(smk_ctx *ctx, int step_src, int step_out, int add_h, int compat, int blur, void *stream);
+/* The same from nf = nelts - 1 - add_h dense scalars in DEVICE memory, as smk_upload_timestep_fields_device takes them, with
+ * that entry's additional refusals. */
+int smk_upload_timestep_fields_h_device(smk_ctx *ctx, int timestep, const void *const *d_fields, int nf, smk_dtype field_dtype,
+                                        int sx, int sy, int sz, int add_h, int compat, int blur, void *stream);
 /* The two stencil producers on a SHARDED context (smk_set_shard), in two calls with one exchange of eight integers between
  * them; no voxel moves between ranks.  smk_derive_timestep and smk_merge_timestep above refuse a sharded context for two
  * reasons, and both go:
@@ -715,6 +733,32 @@ int smk_normals_f32_device(smk_ctx *ctx, const void *d_f32, int nelts, int sx, i
  * quantises to a byte, (uchar)(mag / max * 255), which is what is dropped here. */
 int smk_merge_fields_f32_device(smk_ctx *ctx, const void *d_fields_f32, int nf, int sx, int sy, int sz, void *d_out_f32,
                                 void *d_normals_or_null);
+/* MetaVolume::mergeMV with addG, addH and blurnorms (MetaVolume.cpp:1109-1268; gluvv.cpp's -addH and -blurNormals): the two
+ * merge entries above with H and blurred normals.  d_fields is [z][y][x][nf], d_out [z][y][x][nf + 1 + add_h], bytes (_h_device)
+ * or floats (_h_f32_device); nf is 1..3, and 1..2 with add_h; dims >= 3; add_h and blur are 0 or 1; synchronous, as their twins.
+ * With add_h = 0 and blur = 0 they store the bits of smk_merge_fields_device / smk_merge_fields_f32_device.  The contract, with
+ * S the summed gradient exactly as there (fields ascending, one fp32 subtraction and one add per field and axis, 0 on the
+ * volume's 1-voxel border):
+ *   G.  Unchanged: (uchar)(|S| / max * 255.0), or |S| / maxm in floats.  G and H come from the UNBLURRED S, as mergeMV
+ *       computes them before blurV3D (MetaVolume.cpp:1217-1256).
+ *   H.  GMagHess (VectorMath.h:1032-1113) is a copy of makeVGH's second-derivative block (genVGH/main.cpp:103-175) in which
+ *       three reads name the output array `hess`, never yet written, where the copy's source names the computed value
+ *       (:1086-1087, :1099): as coded it reads uninitialised memory and has no defined result.  Built here: those three reads
+ *       take `tmph`, i.e. makeVGH's lines.  An interior voxel has hs = the second derivative along the gradient from S and S at
+ *       its six neighbours (smk_make_vgh_device's expression; compat != 0 keeps the `tg[1] +` typo of :1078, 0 uses h[4]).  A
+ *       border voxel has hs = 0 -- NOT makeVGH's zeroed border: 0 takes the `else` branch of the scaling and quantises to 85
+ *       (floats: (float)(85.0 / 255.0)) wherever max H is not 0.  hmin and hmax run over the interior voxels from the seeds
+ *       +1e8 and -1e8; a NaN (zero gradient) never wins.  The byte / float is makeVGH's scaling of hs with those extremes
+ *       (255 / 3 and 255 / 3 * 2 are the integers 85 and 170); the byte of a NaN is 0.
+ *       Floats: hmin and hmax run over FINITE hs only, and a voxel whose hs is not finite gets H = 0 (the rule maxm follows).
+ *   Blurred normals.  blur != 0: the normal's gradient is blurV3D of S -- smk_normals_vgh_device's weights, 27-term
+ *       source-raster order, interior-only sources and divisor -- then the twins' byte rule.  blur == 0: S itself.
+ *   Fields.  Copied as by the twins, border included.
+ * The float entry refuses pointers below float alignment. */
+int smk_merge_fields_h_device(smk_ctx *ctx, const void *d_fields_u8, int nf, int sx, int sy, int sz, int add_h, int compat,
+                              int blur, void *d_out, void *d_normals_or_null);
+int smk_merge_fields_h_f32_device(smk_ctx *ctx, const void *d_fields_f32, int nf, int sx, int sy, int sz, int add_h, int compat,
+                                  int blur, void *d_out_f32, void *d_normals_or_null);
 /* extends MetaVolume::hist2D (MetaVolume.cpp:1650-1688): a channel's bin is b(v) with t = v * 255.0f (one fp32
  * multiply): NaN or t < 0 -> 0, t >= 255 -> 255, otherwise (int)t.  Counts go to hist[b(c1) * 256 + b(c0)] and are
  * finished as smk_hist2d_device's (log scale, float bins that stop at 2^24); hist is 65536 bytes in HOST memory and

@@ -41,6 +41,7 @@ ABI_SYMBOLS = [
     "smk_get_timestep_box", "smk_download_timestep_device", "smk_download_timestep",
     "smk_declare_volume", "smk_upload_timestep_block_device", "smk_block_extremes_device",
     "smk_upload_timestep_scalar_block_device", "smk_upload_timestep_fields_block_device",
+    "smk_merge_fields_h_device", "smk_merge_fields_h_f32_device", "smk_merge_timestep_h", "smk_upload_timestep_fields_h_device",
 ]
 STEP_CURRENT = -1  # SMK_STEP_CURRENT: the step the frames render
 EXTREMES_DERIVE, EXTREMES_MERGE = 0, 1  # SMK_EXTREMES_*: the kind of smk_step_extremes_device
@@ -173,6 +174,12 @@ def load_library():
                                                           C.c_void_p, C.c_void_p]
     L.smk_upload_timestep_fields_device.argtypes = [C.c_void_p, C.c_int, P(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int,
                                                     C.c_int, C.c_void_p]
+    L.smk_merge_timestep_h.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.smk_upload_timestep_fields_h_device.argtypes = [C.c_void_p, C.c_int, P(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int,
+                                                      C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.smk_merge_fields_h_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                            C.c_void_p, C.c_void_p]
+    L.smk_merge_fields_h_f32_device.argtypes = L.smk_merge_fields_h_device.argtypes
     L.smk_set_shard.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.smk_set_clip.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
     L.smk_set_clip_plane.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double)]
@@ -429,6 +436,18 @@ class Renderer:
         arr = None if ptrs is None else (C.c_void_p * max(len(ptrs), 1))(*ptrs)
         self._ck(self.L.smk_upload_timestep_fields_device(self.ctx, int(timestep), arr, 0 if ptrs is None else len(ptrs), int(dtype),
                                                           int(dims[0]), int(dims[1]), int(dims[2]), stream))
+
+    def merge_timestep_h(self, src, out, add_h=1, compat=1, blur=0, stream=None):
+        """merge_timestep with H of the summed gradient (add_h) and blurred normals (blur): the first nelts - 1 - add_h channels
+        of the cached step `src` with G, H and the normals (smk.h smk_merge_timestep_h)"""
+        self._ck(self.L.smk_merge_timestep_h(self.ctx, int(src), int(out), int(add_h), int(compat), int(blur), stream))
+
+    def upload_timestep_fields_h_device(self, timestep, ptrs, dtype, dims, add_h=1, compat=1, blur=0, stream=None):
+        """the same from dense scalars in device memory, one per field, as upload_timestep_fields_device takes them"""
+        arr = None if ptrs is None else (C.c_void_p * max(len(ptrs), 1))(*ptrs)
+        self._ck(self.L.smk_upload_timestep_fields_h_device(self.ctx, int(timestep), arr, 0 if ptrs is None else len(ptrs), int(dtype),
+                                                            int(dims[0]), int(dims[1]), int(dims[2]), int(add_h), int(compat),
+                                                            int(blur), stream))
 
     # -- the stencil producers on a shard (smk.h: smk_step_extremes_device ...): export, combine by integer maximum, write
     def step_extremes_device(self, kind, src, d_words, compat=1, stream=None):
@@ -837,6 +856,18 @@ class Renderer:
         """nf interleaved float fields -> [z][y][x][nf+1] f32 with |summed gradient| / its finite maximum as last channel"""
         sx, sy, sz = dims
         self._ck(self.L.smk_merge_fields_f32_device(self.ctx, d_fields_f32, nf, sx, sy, sz, d_out_f32, d_normals))
+
+    # -- the two merges with H of the summed gradient and blurred normals (smk.h: smk_merge_fields_h_device ...)
+    def merge_fields_h_device(self, d_fields, nf, dims, d_out, d_normals=None, add_h=1, compat=1, blur=0):
+        """nf interleaved byte fields -> [z][y][x][nf + 1 + add_h] bytes: the fields, G and, with add_h, H"""
+        sx, sy, sz = dims
+        self._ck(self.L.smk_merge_fields_h_device(self.ctx, d_fields, nf, sx, sy, sz, int(add_h), int(compat), int(blur), d_out, d_normals))
+
+    def merge_fields_h_f32_device(self, d_fields_f32, nf, dims, d_out_f32, d_normals=None, add_h=1, compat=1, blur=0):
+        """the same in floats"""
+        sx, sy, sz = dims
+        self._ck(self.L.smk_merge_fields_h_f32_device(self.ctx, d_fields_f32, nf, sx, sy, sz, int(add_h), int(compat), int(blur), d_out_f32,
+                                                      d_normals))
 
     def hist2d_f32_device(self, d_vol_f32, nelts, dims):
         """log-scaled joint (value, gradient) histogram [g][v] of a device-resident f32 volume, bins (int)(v * 255)"""

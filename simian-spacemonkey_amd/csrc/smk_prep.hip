@@ -6,6 +6,8 @@
 //                                                              VectorMath.h:874-899, 1217-1281, 1133-1148
 //   smk_normals_f32_device, smk_merge_fields_f32_device, smk_hist2d_f32_device
 //                            normals, merge and histogram of float volumes (no reference equivalent)
+//   smk_merge_fields_h_device, smk_merge_fields_h_f32_device
+//                            MetaVolume::mergeMV with addH and blurnorms   MetaVolume.cpp:1109-1268
 //   smk_synth_volume_device  bench/test input generator (no reference equivalent; genvol's
 //                            Perlin tables depend on libc rand(), so the GPU generator is analytic)
 //
@@ -18,6 +20,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 #include "smk_internal.h"
@@ -557,6 +560,161 @@ extern "C" int smk_merge_fields_f32_device(smk_ctx *c, const void *d_fields, int
     return 1;
   }
   return 0;
+}
+
+// ------------------------------------------------------------------------------- multi-field merge with H, blurred normals
+// smk_merge_fields_h_device, smk_merge_fields_h_f32_device: mergeMV with addH and blurnorms (MetaVolume.cpp:1109-1268; the
+// contract is smk.h's).  T: the fields' element (unsigned char or float); one pair of kernels serves both pipelines
+
+// merge_grad / merge_grad_f32 of fields of either type: the summed gradient, 0 on the border
+template <class T, int NF>
+__device__ __forceinline__ void mh_grad(const T *in, int sx, int sy, int sz, int i, int j, int k, float g[3]) {
+  merge_grad_zero(g);
+  if (is_border(sx, sy, sz, i, j, k)) return;
+  const size_t sxy = (size_t)sx * sy, o = (size_t)i * sxy + (size_t)j * sx + k;
+#pragma unroll
+  for (int e = 0; e < NF; ++e)
+    merge_grad_add(g, (float)in[(o + 1) * NF + e], (float)in[(o - 1) * NF + e], (float)in[(o + sx) * NF + e], (float)in[(o - sx) * NF + e],
+                   (float)in[(o + sxy) * NF + e], (float)in[(o - sxy) * NF + e]);
+}
+
+// hs of the INTERIOR voxel (i, j, k) whose summed gradient is g
+template <class T, int NF>
+__device__ __forceinline__ float mh_hs(const T *in, int sx, int sy, int sz, int i, int j, int k, int compat, const float g[3]) {
+  float xp[3], xm[3], yp[3], ym[3], zp[3], zm[3], gm, hs;
+  mh_grad<T, NF>(in, sx, sy, sz, i, j, k + 1, xp);
+  mh_grad<T, NF>(in, sx, sy, sz, i, j, k - 1, xm);
+  mh_grad<T, NF>(in, sx, sy, sz, i, j + 1, k, yp);
+  mh_grad<T, NF>(in, sx, sy, sz, i, j - 1, k, ym);
+  mh_grad<T, NF>(in, sx, sy, sz, i + 1, j, k, zp);
+  mh_grad<T, NF>(in, sx, sy, sz, i - 1, j, k, zm);
+  gh_from_grads(g, xp, xm, yp, ym, zp, zm, compat, gm, hs);
+  return hs;
+}
+
+// w: {the maximum magnitude, min H, max H}, ordered-int, seeded {MERGE_MAX_SEED, ORD_POS_INF, ORD_NEG_INF}
+template <class T, int NF>
+__global__ __launch_bounds__(256) void smk_k_merge_h_extremes(const T *in, int sx, int sy, int sz, int add_h, int compat, int *w) {
+  constexpr bool FLT = std::is_same<T, float>::value;
+  const size_t n = (size_t)sx * sy * sz;
+  int m = MERGE_MAX_SEED, hmin = ORD_POS_INF, hmax = ORD_NEG_INF;
+  for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (size_t)gridDim.x * blockDim.x) {
+    int k = (int)(t % sx), j = (int)((t / sx) % sy), i = (int)(t / ((size_t)sx * sy));
+    if (is_border(sx, sy, sz, i, j, k)) continue;
+    float g[3];
+    mh_grad<T, NF>(in, sx, sy, sz, i, j, k, g);
+    const float mag = merge_mag(g);
+    m = FLT ? merge_max_take_f32(m, mag) : merge_max_take(m, mag);
+    if (add_h) {
+      const float hs = mh_hs<T, NF>(in, sx, sy, sz, i, j, k, compat, g);
+      if (merge_h_counts(FLT, hs)) {
+        hmin = min(hmin, f2o(hs));
+        hmax = max(hmax, f2o(hs));
+      }
+    }
+  }
+  m = wave_max(m);
+  hmin = wave_min(hmin);
+  hmax = wave_max(hmax);
+  if ((threadIdx.x & 63) == 0) {
+    atomicMax(&w[0], m);
+    if (add_h) {
+      atomicMin(&w[1], hmin);
+      atomicMax(&w[2], hmax);
+    }
+  }
+}
+
+__global__ __launch_bounds__(64) void smk_k_merge_h_seed(int *w) {
+  if (threadIdx.x < 3) w[threadIdx.x] = threadIdx.x == 0 ? MERGE_MAX_SEED : threadIdx.x == 1 ? ORD_POS_INF : ORD_NEG_INF;
+}
+
+template <class T, int NF>
+__global__ __launch_bounds__(256) void smk_k_merge_h_write(const T *in, int sx, int sy, int sz, int add_h, int compat, int blur, const int *w,
+                                                           T *out, unsigned char *nrm) {
+  constexpr bool FLT = std::is_same<T, float>::value;
+  const size_t n = (size_t)sx * sy * sz;
+  const float maxm = o2f(w[0]);
+  float hmin, hmax;
+  merge_h_extremes(w[1], w[2], hmin, hmax);
+  const int ne = NF + 1 + add_h;
+  for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (size_t)gridDim.x * blockDim.x) {
+    int k = (int)(t % sx), j = (int)((t / sx) % sy), i = (int)(t / ((size_t)sx * sy));
+    float g[3];
+    mh_grad<T, NF>(in, sx, sy, sz, i, j, k, g);
+    const float mag = merge_mag(g);
+    float hs = 0.f;  // (the border's)
+    if (add_h && !is_border(sx, sy, sz, i, j, k)) hs = mh_hs<T, NF>(in, sx, sy, sz, i, j, k, compat, g);
+    if constexpr (FLT) {  // the fields travel as raw words: bit for bit, NaN payloads included
+#pragma unroll
+      for (int e = 0; e < NF; ++e) ((unsigned *)out)[t * ne + e] = ((const unsigned *)in)[t * NF + e];
+      out[t * ne + NF] = merge_g_f32(mag, maxm);
+      if (add_h) out[t * ne + NF + 1] = merge_h_f32(hs, hmin, hmax);
+    } else {
+#pragma unroll
+      for (int e = 0; e < NF; ++e) out[t * ne + e] = in[t * NF + e];
+      out[t * ne + NF] = merge_gmag_u8(mag, maxm);
+      if (add_h) out[t * ne + NF + 1] = merge_h_u8(hs, hmin, hmax);
+    }
+    if (nrm) {
+      float gn[3];
+      nrm_gradient(blur, sx, sy, sz, i, j, k, gn, [&](int si, int sj, int sk, float s[3]) { mh_grad<T, NF>(in, sx, sy, sz, si, sj, sk, s); });
+      if (FLT) nrm_store_f32(gn, nrm + t * 3);
+      else nrm_store(gn, nrm + t * 3);
+    }
+  }
+}
+
+template <class T, int NF>
+static void merge_h_launch(smk_ctx *c, unsigned blocks, const T *in, int sx, int sy, int sz, int add_h, int compat, int blur, int *d_w, T *out,
+                           unsigned char *nrm) {
+  hipLaunchKernelGGL(smk_k_merge_h_seed, dim3(1), dim3(64), 0, c->stream, d_w);
+  hipLaunchKernelGGL((smk_k_merge_h_extremes<T, NF>), dim3(blocks), dim3(256), 0, c->stream, in, sx, sy, sz, add_h, compat, d_w);
+  hipLaunchKernelGGL((smk_k_merge_h_write<T, NF>), dim3(blocks), dim3(256), 0, c->stream, in, sx, sy, sz, add_h, compat, blur, (const int *)d_w, out,
+                     nrm);
+}
+
+template <class T>
+static int merge_h_entry(smk_ctx *c, const char *bad, const char *hip, const void *d_fields, int nf, int sx, int sy, int sz,
+                         int add_h, int compat, int blur, void *d_out, void *d_normals) {
+  if (!c) return 1;
+  PCHK(c, hipSetDevice(c->device));
+  if (!d_fields || !d_out || nf < 1 || nf > (add_h ? 2 : 3) || sx < 3 || sy < 3 || sz < 3 || (add_h != 0 && add_h != 1) || (blur != 0 && blur != 1) ||
+      (uintptr_t)d_fields % sizeof(T) || (uintptr_t)d_out % sizeof(T)) {
+    c->err = bad;
+    return 1;
+  }
+  int *d_w = nullptr;
+  PCHK(c, hipMalloc((void **)&d_w, 3 * sizeof(int)));
+  const size_t n = (size_t)sx * sy * sz;
+  const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 256 * 32);
+  const T *in = (const T *)d_fields;
+  compat = compat ? 1 : 0;
+  if (nf == 1) merge_h_launch<T, 1>(c, blocks, in, sx, sy, sz, add_h, compat, blur, d_w, (T *)d_out, (unsigned char *)d_normals);
+  else if (nf == 2) merge_h_launch<T, 2>(c, blocks, in, sx, sy, sz, add_h, compat, blur, d_w, (T *)d_out, (unsigned char *)d_normals);
+  else merge_h_launch<T, 3>(c, blocks, in, sx, sy, sz, add_h, compat, blur, d_w, (T *)d_out, (unsigned char *)d_normals);
+  const int rc = hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess;
+  (void)hipFree(d_w);
+  if (rc) {
+    c->err = hip;
+    return 1;
+  }
+  return 0;
+}
+
+extern "C" int smk_merge_fields_h_device(smk_ctx *c, const void *d_fields, int nf, int sx, int sy, int sz, int add_h, int compat, int blur,
+                                         void *d_out, void *d_normals) {
+  return merge_h_entry<unsigned char>(c,
+                                      "smk_merge_fields_h_device: bad arguments (1..3 fields, 1..2 with add_h; dims >= 3; add_h and blur 0 or 1)",
+                                      "smk_merge_fields_h_device: HIP error", d_fields, nf, sx, sy, sz, add_h, compat, blur, d_out, d_normals);
+}
+
+extern "C" int smk_merge_fields_h_f32_device(smk_ctx *c, const void *d_fields, int nf, int sx, int sy, int sz, int add_h, int compat, int blur,
+                                             void *d_out, void *d_normals) {
+  return merge_h_entry<float>(c,
+                              "smk_merge_fields_h_f32_device: bad arguments (1..3 fields, 1..2 with add_h; dims >= 3; add_h and blur 0 or 1; "
+                              "float alignment)",
+                              "smk_merge_fields_h_f32_device: HIP error", d_fields, nf, sx, sy, sz, add_h, compat, blur, d_out, d_normals);
 }
 
 // smk_k_hist2d's LDS-binned counting with the key taken from two floats (hist_bin_f32, smk_prep_device.h)

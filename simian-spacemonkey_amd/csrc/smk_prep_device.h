@@ -193,6 +193,42 @@ __device__ __forceinline__ unsigned char merge_gmag_u8(float mag, float maxm) { 
 // the float merge's G: 0 where the magnitude is not finite or the maximum is 0
 __device__ __forceinline__ float merge_g_f32(float mag, float maxm) { return (maxm > 0.f && __builtin_isfinite(mag)) ? mag / maxm : 0.f; }
 
+// The merge with H and blurred normals (mergeMV with addH: GMagHess, VectorMath.h:1032-1113, read as makeVGH's
+// second-derivative block; smk.h smk_merge_fields_h_device).  hs of an interior voxel is gh_from_grads of the summed gradient
+// and the summed gradients of its six neighbours; a border voxel has hs = 0.  The extremes run over the interior voxels: a NaN
+// never wins, and in the float pipeline (FLT) nothing that is not finite does
+__device__ __forceinline__ bool merge_h_counts(bool flt, float hs) { return flt ? __builtin_isfinite(hs) : hs == hs; }
+
+// the running extremes' words {min H, max H} (ordered-int; seeds ORD_POS_INF, ORD_NEG_INF) behind the reference's +-1e8 seeds,
+// taken as std::min / std::max take them
+__device__ __forceinline__ void merge_h_extremes(int omin, int omax, float &hmin, float &hmax) {
+  const float a = o2f(omin), b = o2f(omax);
+  hmin = (100000000.f < a) ? 100000000.f : a;
+  hmax = (b < -100000000.f) ? -100000000.f : b;
+}
+
+// the H byte and the H float of hs: vgh_scale's third output (the data and the magnitude are not looked at)
+__device__ __forceinline__ void merge_h_scale(float hs, float hmin, float hmax, unsigned char &q, float &f) {
+  unsigned char q3[3];
+  float f3[3];
+  vgh_scale(0.f, 0.f, hs, 0.f, 1.f, 0.f, 1.f, hmin, hmax, q3, f3);
+  q = q3[2];
+  f = f3[2];
+}
+__device__ __forceinline__ unsigned char merge_h_u8(float hs, float hmin, float hmax) {
+  unsigned char q;
+  float f;
+  merge_h_scale(hs, hmin, hmax, q, f);
+  return q;
+}
+// ... the float pipeline's: 0 where hs is not finite
+__device__ __forceinline__ float merge_h_f32(float hs, float hmin, float hmax) {
+  unsigned char q;
+  float f;
+  merge_h_scale(hs, hmin, hmax, q, f);
+  return __builtin_isfinite(hs) ? f : 0.f;
+}
+
 // The normal's gradient at voxel (i, j, k) = (z, y, x) of an sx x sy x sz volume from grad(si, sj, sk, s[3]), the central
 // differences of channel 0 at an INTERIOR voxel (derivative3DVGH, VectorMath.h:874-899; 0 on the border).  Blurred: blurV3D is
 // a scatter from every interior voxel to its 27 neighbours in raster order of the SOURCE (VectorMath.h:1232-1266).  Gathering

@@ -1,0 +1,381 @@
+// smk_step_merge_h.hip -- the multi-field step WITH H and blurred normals (fields + G, H, normals of the summed gradient) made
+// INSIDE the time-step ring (smk.h: smk_merge_timestep_h, smk_upload_timestep_fields_h_device; DESIGN.md 3b "Merged fields
+// with H").
+//
+// MetaVolume::mergeMV with addG, addH and blurnorms (MetaVolume.cpp:1109-1268; gluvv.cpp's -addH and -blurNormals: the data
+// modes V1GH, V2GH) is a host program that runs before the renderer starts.  A step whose fields are new on the device gets here
+// what smk_merge_fields_h_device / smk_merge_fields_h_f32_device (and, in a u16 ring, smk_quantize_u16_device) and
+// smk_upload_timestep_device would make of them, bit for bit, as two kernels on the caller's stream that write the packed
+// voxels of a ring slot: no scratch arrays, no host wait.
+//
+// H reads the summed gradient S of the six neighbours and a blurred normal that of the 26, each a central difference of every
+// field: the stencil reaches 2 voxels, which smk_step_merge.hip's register march (reach 1) does not hold.  Both kernels here
+// work on tiles of MH_TX x MH_TY x MH_TZ voxels of the stored box, as smk_step_derive.hip's do:
+//   F  the fields of the tile with a 2-voxel apron, one 32-bit word per voxel: the channel word of an 8-byte voxel (all fields
+//      of a u8 or u16 ring at once), or ONE float field of an f32 ring, which then takes a turn per field;
+//   S  the summed gradient (three floats, one plane each) of the tile with a 1-voxel apron, made from F: 0 on the volume's
+//      border and outside it, merge_grad_add once per field, fields ascending.
+// 20 736 + 40 800 bytes of LDS: two workgroups fit a CU.  Tile rows start on even x, so two 8-byte voxels load as one 16-byte unit.
+//   pass 1 (smk_k_merge_h_stats): |S| and, with add_h, hs of every interior voxel -> {max magnitude, min H, max H}, ordered-int
+//          atomics per wave into the OUTPUT slot's words (TimeStep::pass1_words), which a one-wave kernel seeded on the stream;
+//          a capped grid strides over the tiles;
+//   pass 2 (smk_k_merge_h_write): S again, G, H and the normal, and one 8- or 16-byte store of the packed voxel (and the
+//          normal word of a four-channel f32 voxel).
+// The arithmetic is smk_prep.hip's, through smk_prep_device.h; the packed voxel is smk_packed.h's.  Unsharded contexts only.
+#include <algorithm>
+
+#include "smk_internal.h"
+#include "smk_prep_device.h"
+
+namespace {
+
+constexpr int MH_TX = 32, MH_TY = 8, MH_TZ = 8;
+constexpr int MH_FX = MH_TX + 4, MH_FY = MH_TY + 4, MH_FZ = MH_TZ + 4, MH_FN = MH_FX * MH_FY * MH_FZ;  // 5184 words
+constexpr int MH_SX = MH_TX + 2, MH_SY = MH_TY + 2, MH_SZ = MH_TZ + 2, MH_SN = MH_SX * MH_SY * MH_SZ;  // 3400 floats, three times
+constexpr int MH_FSY = MH_FX, MH_FSZ = MH_FX * MH_FY, MH_SSY = MH_SX, MH_SSZ = MH_SX * MH_SY;
+static_assert(MH_TX * MH_TY == 256 && MH_TX % 2 == 0, "a thread per (x, y) of the tile; tile rows start on even x");
+static_assert((MH_FN + 3 * MH_SN) * 4 <= 64 * 1024, "two workgroups per CU");
+constexpr unsigned MH_STATS_BLOCKS = 2048;  // pass 1's grid: 8 workgroups for each of 256 CUs (its atomics land on one cache line)
+
+struct MergeHParams {
+  const void *src;    // the source slot's packed voxels [D2][D1][D0] ...
+  const void *f[3];   // ... or the dense fields [N2][N1][N0], one array each
+  void *out;          // the output slot's packed voxels
+  uint32_t *nrm;      // its separate normal words (four-channel f32 with normals), else null
+  int *w;             // the output slot's words {max magnitude, min H, max H}, ordered-int
+  int N[3], D[3];     // the volume; the stored box (origin 0), D >= N with a pad column or row of 8-byte voxels.  The kernels rely
+                      // on D[2] == N[2], on D == N for f32 voxels and on an even D[0] otherwise: smk_step_stencil_refusals checks
+  int add_h, compat, blur, normals;
+  int gx, gy, ntiles;  // tiles per row of tiles, rows of tiles per slice of tiles, tiles in all
+};
+
+constexpr int mh_ring(int SRC) { return SRC == SRC_PK_U8 ? SMK_U8 : SRC == SRC_PK_U16 ? SMK_U16 : SRC == SRC_PK_F32 ? SMK_F32 : SRC; }
+// the turns F takes: one per field of an f32 ring, one for all fields of an 8-byte voxel
+constexpr int mh_turns(int SRC, int NF) { return mh_ring(SRC) == SMK_F32 ? NF : 1; }
+
+// field e of a word of F as the float the gradient is taken of: (float)v of an integer, unscaled
+template <int SRC>
+__device__ __forceinline__ float mh_val(uint32_t w, int e) {
+  constexpr int RING = mh_ring(SRC);
+  if (RING == SMK_F32) return __uint_as_float(w);
+  if (RING == SMK_U8) return (float)smk_u8_ch(w, e);
+  return (float)(e ? smk_vox8_c1<SMK_U16>(w) : smk_vox8_c0<SMK_U16>(w));
+}
+
+// F of the tile at (x0, y0, z0) for turn p; what lies outside the volume is 0 and is never used
+template <int SRC, int NF>
+__device__ __forceinline__ void mh_load(const MergeHParams &P, int x0, int y0, int z0, int p, uint32_t *F) {
+  constexpr int RING = mh_ring(SRC);
+  if (SRC == SRC_PK_U8 || SRC == SRC_PK_U16) {  // two voxels per 16-byte unit (x0 - 2 is even, and so is D[0]): their channel words are .x and .z
+    constexpr int UPR = MH_FX / 2;
+    for (int u = threadIdx.x; u < UPR * MH_FY * MH_FZ; u += 256) {
+      const int cu = u % UPR, row = u / UPR, ly = row % MH_FY, lz = row / MH_FY;
+      const int X = x0 - 2 + 2 * cu, Y = y0 - 2 + ly, Z = z0 - 2 + lz;
+      uint32_t a = 0u, b = 0u;
+      if (X >= 0 && X < P.N[0] && Y >= 0 && Y < P.N[1] && Z >= 0 && Z < P.N[2]) {
+        const uint4 v = ((const uint4 *)P.src)[(((size_t)Z * P.D[1] + Y) * P.D[0] + X) >> 1];
+        a = v.x;
+        if (X + 1 < P.N[0]) b = v.z;
+      }
+      F[row * MH_FX + 2 * cu] = a;
+      F[row * MH_FX + 2 * cu + 1] = b;
+    }
+  } else {
+    for (int t = threadIdx.x; t < MH_FN; t += 256) {
+      const int lx = t % MH_FX, row = t / MH_FX, ly = row % MH_FY, lz = row / MH_FY;
+      const int X = x0 - 2 + lx, Y = y0 - 2 + ly, Z = z0 - 2 + lz;
+      uint32_t a = 0u;
+      if (X >= 0 && X < P.N[0] && Y >= 0 && Y < P.N[1] && Z >= 0 && Z < P.N[2]) {
+        if (SRC == SRC_PK_F32) {
+          const uint4 v = ((const uint4 *)P.src)[((size_t)Z * P.D[1] + Y) * P.D[0] + X];
+          a = p == 0 ? v.x : p == 1 ? v.y : v.z;
+        } else {
+          const size_t o = ((size_t)Z * P.N[1] + Y) * P.N[0] + X;
+          if (RING == SMK_F32) {
+            a = ((const uint32_t *)P.f[p])[o];
+          } else {  // the channel word an 8-byte voxel would hold
+#pragma unroll
+            for (int e = 0; e < NF; ++e)
+              a |= RING == SMK_U8 ? (uint32_t)((const unsigned char *)P.f[e])[o] << (8 * e) : (uint32_t)((const unsigned short *)P.f[e])[o] << (16 * e);
+          }
+        }
+      }
+      F[t] = a;
+    }
+  }
+}
+
+// S of the tile with its 1-voxel apron, and own[p][tz]: the words of this thread's voxels (their fields, as stored).  Every
+// thread of the workgroup calls this; S is whole behind it
+template <int SRC, int NF>
+__device__ __forceinline__ void mh_tile(const MergeHParams &P, int x0, int y0, int z0, uint32_t *F, float *S, uint32_t own[][MH_TZ]) {
+  constexpr int TURNS = mh_turns(SRC, NF);
+  const int tx = threadIdx.x % MH_TX, ty = threadIdx.x / MH_TX;
+#pragma unroll
+  for (int p = 0; p < TURNS; ++p) {
+    mh_load<SRC, NF>(P, x0, y0, z0, p, F);
+    __syncthreads();
+#pragma unroll
+    for (int tz = 0; tz < MH_TZ; ++tz) own[p][tz] = F[(tz + 2) * MH_FSZ + (ty + 2) * MH_FSY + tx + 2];
+    for (int t = threadIdx.x; t < MH_SN; t += 256) {
+      const int lx = t % MH_SX, row = t / MH_SX, ly = row % MH_SY, lz = row / MH_SY;
+      const int X = x0 - 1 + lx, Y = y0 - 1 + ly, Z = z0 - 1 + lz;
+      float g[3];
+      if (p == 0) merge_grad_zero(g);
+      else g[0] = S[t], g[1] = S[MH_SN + t], g[2] = S[2 * MH_SN + t];
+      if (!is_border(P.N[0], P.N[1], P.N[2], Z, Y, X)) {  // (the border, and everything outside the volume, stays 0)
+        const int l = (lz + 1) * MH_FSZ + (ly + 1) * MH_FSY + lx + 1;
+#pragma unroll
+        for (int e = 0; e < (TURNS == 1 ? NF : 1); ++e) {
+          const int fe = TURNS == 1 ? e : p;
+          merge_grad_add(g, mh_val<SRC>(F[l + 1], fe), mh_val<SRC>(F[l - 1], fe), mh_val<SRC>(F[l + MH_FSY], fe), mh_val<SRC>(F[l - MH_FSY], fe),
+                         mh_val<SRC>(F[l + MH_FSZ], fe), mh_val<SRC>(F[l - MH_FSZ], fe));
+        }
+      }
+      S[t] = g[0], S[MH_SN + t] = g[1], S[2 * MH_SN + t] = g[2];
+    }
+    __syncthreads();  // (the next turn overwrites F; S is read behind the last)
+  }
+}
+
+__device__ __forceinline__ void mh_s(const float *S, int l, float g[3]) { g[0] = S[l], g[1] = S[MH_SN + l], g[2] = S[2 * MH_SN + l]; }
+
+// hs of the INTERIOR voxel at index l of S whose summed gradient is g (the neighbours on the border hold 0)
+__device__ __forceinline__ float mh_hs(const float *S, int l, const float g[3], int compat) {
+  float xp[3], xm[3], yp[3], ym[3], zp[3], zm[3], gm, hs;
+  mh_s(S, l + 1, xp);
+  mh_s(S, l - 1, xm);
+  mh_s(S, l + MH_SSY, yp);
+  mh_s(S, l - MH_SSY, ym);
+  mh_s(S, l + MH_SSZ, zp);
+  mh_s(S, l - MH_SSZ, zm);
+  gh_from_grads(g, xp, xm, yp, ym, zp, zm, compat, gm, hs);
+  return hs;
+}
+
+__global__ __launch_bounds__(64) void smk_k_merge_h_seed_words(int *w) {
+  if (threadIdx.x < 3) w[threadIdx.x] = threadIdx.x == 0 ? MERGE_MAX_SEED : threadIdx.x == 1 ? ORD_POS_INF : ORD_NEG_INF;
+}
+
+template <int SRC, int NF>
+__global__ __launch_bounds__(256) void smk_k_merge_h_stats(const MergeHParams P) {
+  __shared__ uint32_t F[MH_FN];
+  __shared__ float S[3 * MH_SN];
+  constexpr bool FLT = mh_ring(SRC) != SMK_U8;  // (a u16 ring's G and H are the float entry's)
+  const int tx = threadIdx.x % MH_TX, ty = threadIdx.x / MH_TX;
+  int m = MERGE_MAX_SEED, hmin = ORD_POS_INF, hmax = ORD_NEG_INF;
+  for (int tile = blockIdx.x; tile < P.ntiles; tile += gridDim.x) {
+    const int bx = tile % P.gx, by = (tile / P.gx) % P.gy, bz = tile / (P.gx * P.gy);
+    const int x0 = bx * MH_TX, y0 = by * MH_TY, z0 = bz * MH_TZ;
+    uint32_t own[mh_turns(SRC, NF)][MH_TZ];
+    mh_tile<SRC, NF>(P, x0, y0, z0, F, S, own);
+    const int X = x0 + tx, Y = y0 + ty;
+    for (int tz = 0; tz < MH_TZ; ++tz) {
+      const int Z = z0 + tz;
+      if (is_border(P.N[0], P.N[1], P.N[2], Z, Y, X)) continue;  // (and everything outside the volume)
+      const int l = (tz + 1) * MH_SSZ + (ty + 1) * MH_SSY + tx + 1;
+      float g[3];
+      mh_s(S, l, g);
+      const float mag = merge_mag(g);
+      m = FLT ? merge_max_take_f32(m, mag) : merge_max_take(m, mag);
+      if (P.add_h) {
+        const float hs = mh_hs(S, l, g, P.compat);
+        if (merge_h_counts(FLT, hs)) {
+          hmin = min(hmin, f2o(hs));
+          hmax = max(hmax, f2o(hs));
+        }
+      }
+    }
+    // (the next tile writes S behind its first barrier, which every thread reaches behind these reads)
+  }
+  m = wave_max(m);
+  hmin = wave_min(hmin);
+  hmax = wave_max(hmax);
+  if ((threadIdx.x & 63) == 0) {
+    atomicMax(&P.w[0], m);
+    if (P.add_h) {
+      atomicMin(&P.w[1], hmin);
+      atomicMax(&P.w[2], hmax);
+    }
+  }
+}
+
+template <int SRC, int NF>
+__global__ __launch_bounds__(256) void smk_k_merge_h_write(const MergeHParams P) {
+  __shared__ uint32_t F[MH_FN];
+  __shared__ float S[3 * MH_SN];
+  constexpr int RING = mh_ring(SRC), TURNS = mh_turns(SRC, NF);
+  const int x0 = blockIdx.x * MH_TX, y0 = blockIdx.y * MH_TY, z0 = blockIdx.z * MH_TZ;
+  uint32_t own[TURNS][MH_TZ];
+  mh_tile<SRC, NF>(P, x0, y0, z0, F, S, own);
+  const float maxm = o2f(P.w[0]);
+  float hmin, hmax;
+  merge_h_extremes(P.w[1], P.w[2], hmin, hmax);
+  const int tx = threadIdx.x % MH_TX, ty = threadIdx.x / MH_TX, X = x0 + tx, Y = y0 + ty;
+  if (X >= P.D[0] || Y >= P.D[1]) return;
+  const int ne = NF + 1 + P.add_h;
+#pragma unroll
+  for (int tz = 0; tz < MH_TZ; ++tz) {
+    const int Z = z0 + tz;
+    if (Z >= P.D[2]) break;
+    const size_t o = ((size_t)Z * P.D[1] + Y) * P.D[0] + X;
+    if (X >= P.N[0] || Y >= P.N[1]) {  // the pad column or row of an 8-byte box: zeros, as after an upload
+      ((uint2 *)P.out)[o] = make_uint2(0u, 0u);
+      continue;
+    }
+    const int l = (tz + 1) * MH_SSZ + (ty + 1) * MH_SSY + tx + 1;
+    float g[3];
+    mh_s(S, l, g);
+    const float mag = merge_mag(g);
+    float hs = 0.f;  // (the border's)
+    if (P.add_h && !is_border(P.N[0], P.N[1], P.N[2], Z, Y, X)) hs = mh_hs(S, l, g, P.compat);
+    uint32_t nw = SMK_NRM_NONE;
+    if (P.normals) {
+      float gn[3];
+      unsigned char n[3];
+      // (Z, Y, X) -> index of S: l moved by the offset; only interior voxels are asked for, all inside the apron
+      nrm_gradient(P.blur, P.N[0], P.N[1], P.N[2], Z, Y, X, gn,
+                   [&](int si, int sj, int sk, float s[3]) { mh_s(S, l + (si - Z) * MH_SSZ + (sj - Y) * MH_SSY + (sk - X), s); });
+      if (RING == SMK_U8) nrm_store(gn, n);
+      else nrm_store_f32(gn, n);  // (u16: the float entry's normals, made from the floats before any quantisation)
+      nw = smk_nrm_word(n[0], n[1], n[2]);
+    }
+    if (RING == SMK_U8) {  // (the fields are copied, on the border too)
+      unsigned char q[4] = {0, 0, 0, 0};
+#pragma unroll
+      for (int e = 0; e < NF; ++e) q[e] = (unsigned char)smk_u8_ch(own[0][tz], e);
+      q[NF] = merge_gmag_u8(mag, maxm);
+      if (P.add_h) q[(NF + 1) & 3] = merge_h_u8(hs, hmin, hmax);
+      ((uint2 *)P.out)[o] = smk_pack_u8(q, ne, nw);
+    } else if (RING == SMK_U16) {
+      unsigned short s[4] = {0, 0, 0, 0};
+      s[0] = (unsigned short)smk_vox8_c0<SMK_U16>(own[0][tz]);
+      if (NF > 1) s[1] = (unsigned short)smk_vox8_c1<SMK_U16>(own[0][tz]);
+      s[NF] = quant_u16(merge_g_f32(mag, maxm));  // smk_quantize_u16_device of the float G, and of the float H
+      if (P.add_h) s[(NF + 1) & 3] = quant_u16(merge_h_f32(hs, hmin, hmax));
+      ((uint2 *)P.out)[o] = smk_pack_u16(s, ne, nw);
+    } else {
+      float f[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int e = 0; e < NF; ++e) f[e] = __uint_as_float(own[e % TURNS][tz]);  // raw words: NaN payloads and -0 travel
+      f[NF] = merge_g_f32(mag, maxm);
+      if (P.add_h) f[(NF + 1) & 3] = merge_h_f32(hs, hmin, hmax);
+      ((uint4 *)P.out)[o] = smk_pack_f32(f, ne, nw, ne <= 3);
+      if (ne == 4 && P.nrm) P.nrm[o] = nw;
+    }
+  }
+}
+
+template <int SRC, int NF>
+hipError_t launch_merge_h(const MergeHParams &P, hipStream_t s) {
+  const dim3 grid((unsigned)P.gx, (unsigned)P.gy, (unsigned)(P.ntiles / (P.gx * P.gy)));
+  hipLaunchKernelGGL(smk_k_merge_h_seed_words, dim3(1), dim3(64), 0, s, P.w);
+  hipLaunchKernelGGL((smk_k_merge_h_stats<SRC, NF>), dim3(std::min<unsigned>((unsigned)P.ntiles, MH_STATS_BLOCKS)), dim3(256), 0, s, P);
+  hipLaunchKernelGGL((smk_k_merge_h_write<SRC, NF>), grid, dim3(256), 0, s, P);
+  return hipGetLastError();
+}
+
+template <int SRC>
+hipError_t launch_merge_h_nf(const MergeHParams &P, int nf, hipStream_t s) {
+  if (nf == 1) return launch_merge_h<SRC, 1>(P, s);
+  if (nf == 2) return launch_merge_h<SRC, 2>(P, s);
+  if constexpr (mh_ring(SRC) != SMK_U16) {  // (a u16 voxel holds three channels: merge_h_entry)
+    if (nf == 3) return launch_merge_h<SRC, 3>(P, s);
+  }
+  return hipErrorInvalidValue;
+}
+
+// what both entries refuse before they look at their data (smk_step_stencil_refusals); add_h is 0 or 1
+StencilEntry merge_h_entry(const smk_ctx *c, const char *who, int add_h) {
+  char nelts_why[160] = "";
+  const int top = c->dtype == SMK_U16 ? 3 : 4;
+  if (add_h && c->dtype == SMK_U16 && c->nelts != 3)
+    snprintf(nelts_why, sizeof nelts_why, "add_h on a 16-bit ring of nelts %d: a u16 voxel holds three channels, one field, G and H (nelts 3)", c->nelts);
+  else if (c->nelts - 1 - add_h < 1)
+    snprintf(nelts_why, sizeof nelts_why, "the series has nelts %d: with add_h %d a multi-field step is at least one field, G%s (nelts >= %d)", c->nelts,
+             add_h, add_h ? " and H" : "", 2 + add_h);
+  else if (c->nelts > top) snprintf(nelts_why, sizeof nelts_why, "internal: nelts %d of a voxel type that holds %d channels", c->nelts, top);
+  return {who,
+          "the stencil reaches 2 voxels beyond region + halo, and G and H are scaled by the whole volume's three extremes (maximum magnitude, "
+          "min H, max H); the shard and block forms do not exist yet",
+          nelts_why, "smk_merge_fields_h_device"};
+}
+
+// the flags both entries take: 0 or 1
+int merge_h_flags(smk_ctx *c, const char *who, int add_h, int blur) {
+  if (add_h != 0 && add_h != 1) FAIL(c, "%s: add_h %d is neither 0 nor 1", who, add_h);
+  if (blur != 0 && blur != 1) FAIL(c, "%s: blur %d is neither 0 nor 1", who, blur);
+  return 0;
+}
+
+// the two passes inside the producer frame; ksrc: the source slot, or -1 (dense fields)
+int merge_h_enqueue(smk_ctx *c, const char *who, const void *const *fields, int ksrc, int step_out, int add_h, int compat, int blur, hipStream_t s) {
+  const int nf = c->nelts - 1 - add_h;
+  const long long gx = (c->D[0] + MH_TX - 1) / MH_TX, gy = (c->D[1] + MH_TY - 1) / MH_TY, gz = (c->D[2] + MH_TZ - 1) / MH_TZ;
+  if (gx * gy * gz > 0x7fffffffLL || gy > 65535 || gz > 65535)  // (2^42 voxels, or 2^19 rows or slices: no ring holds such a step)
+    FAIL(c, "%s: a %dx%dx%d volume has more tiles than a grid holds", who, c->N[0], c->N[1], c->N[2]);
+  return smk_step_produce(c, who, step_out, ksrc, -1, s, [&](TimeStep &T, const TimeStep *S, const TimeStep *) -> int {
+    MergeHParams P;
+    P.src = S ? S->vox : nullptr;
+    for (int e = 0; e < 3; ++e) P.f[e] = fields && e < nf ? fields[e] : nullptr;
+    P.out = T.vox;
+    P.nrm = smk_step_separate_normals(c) ? T.nrm : nullptr;
+    P.w = T.pass1_words;
+    for (int a = 0; a < 3; ++a) {
+      P.N[a] = c->N[a];
+      P.D[a] = c->D[a];
+    }
+    P.add_h = add_h;
+    P.compat = compat ? 1 : 0;
+    P.blur = blur;
+    P.normals = c->have_normals ? 1 : 0;
+    P.gx = (int)gx;
+    P.gy = (int)gy;
+    P.ntiles = (int)(gx * gy * gz);
+    hipError_t e;
+    if (S) {
+      e = c->dtype == SMK_U8 ? launch_merge_h_nf<SRC_PK_U8>(P, nf, s) : c->dtype == SMK_U16 ? launch_merge_h_nf<SRC_PK_U16>(P, nf, s)
+                                                                                             : launch_merge_h_nf<SRC_PK_F32>(P, nf, s);
+    } else {
+      e = c->dtype == SMK_U8 ? launch_merge_h_nf<SMK_U8>(P, nf, s) : c->dtype == SMK_U16 ? launch_merge_h_nf<SMK_U16>(P, nf, s)
+                                                                                          : launch_merge_h_nf<SMK_F32>(P, nf, s);
+    }
+    HIPCHK(c, e);
+    return 0;
+  });
+}
+
+}  // namespace
+
+extern "C" int smk_merge_timestep_h(smk_ctx *c, int step_src, int step_out, int add_h, int compat, int blur, void *stream) {
+  if (!c) return 1;
+  const char *who = "smk_merge_timestep_h";
+  HIPCHK(c, hipSetDevice(c->device));
+  if (merge_h_flags(c, who, add_h, blur)) return 1;
+  int ksrc = -1;
+  if (smk_step_stencil_refusals(c, merge_h_entry(c, who, add_h), step_out, &step_src, &ksrc)) return 1;
+  return merge_h_enqueue(c, who, nullptr, ksrc, step_out, add_h, compat, blur, stream ? (hipStream_t)stream : c->stream);
+}
+
+extern "C" int smk_upload_timestep_fields_h_device(smk_ctx *c, int timestep, const void *const *d_fields, int nf, smk_dtype field_dtype, int sx,
+                                                   int sy, int sz, int add_h, int compat, int blur, void *stream) {
+  if (!c) return 1;
+  const char *who = "smk_upload_timestep_fields_h_device";
+  HIPCHK(c, hipSetDevice(c->device));
+  if (merge_h_flags(c, who, add_h, blur)) return 1;
+  if (smk_step_stencil_refusals(c, merge_h_entry(c, who, add_h), timestep, nullptr, nullptr)) return 1;
+  if (!d_fields) FAIL(c, "%s: d_fields is NULL", who);
+  if (nf != c->nelts - 1 - add_h)
+    FAIL(c, "%s: %d fields for a series of nelts %d with add_h %d: the fields are nelts - 1 - add_h = %d", who, nf, c->nelts, add_h,
+         c->nelts - 1 - add_h);
+  if ((int)field_dtype != c->dtype)
+    FAIL(c, "%s: field_dtype %d is not the ring's type (%d): the fields are stored as they come", who, (int)field_dtype, c->dtype);
+  if (sx != c->N[0] || sy != c->N[1] || sz != c->N[2])
+    FAIL(c, "%s: time step %d: sizes %dx%dx%d differ from the series' %dx%dx%d", who, timestep, sx, sy, sz, c->N[0], c->N[1], c->N[2]);
+  const size_t eb = smk_elem_bytes(field_dtype);
+  for (int e = 0; e < nf; ++e) {
+    if (!d_fields[e]) FAIL(c, "%s: d_fields[%d] is NULL", who, e);
+    if ((uintptr_t)d_fields[e] % eb) FAIL(c, "%s: d_fields[%d] is not aligned to its %zu-byte elements", who, e, eb);
+  }
+  return merge_h_enqueue(c, who, d_fields, -1, timestep, add_h, compat, blur, stream ? (hipStream_t)stream : c->stream);
+}

@@ -420,6 +420,9 @@ void HipVolumeRenderable::showTimeFraction() {
     // same stream: no host wait.  A refusal -- a series that is neither -- is said here, once for this step and fraction as a
     // refused blend is, and the frames show the blend
     const bool merged = gluvv.dmode == GDM_V1G || gluvv.dmode == GDM_V2G || gluvv.dmode == GDM_V3G;
+    // ... and for GDM_V1GH, GDM_V2GH (mergeMV with -addH) with H of the summed gradient too, the reference's typo kept; blurred
+    // normals (setBlurNormals) go to the derive and to either merge
+    const bool merged_h = gluvv.dmode == GDM_V1GH || gluvv.dmode == GDM_V2GH;
     const int did = INT_MAX - 2 - tblend_next;
     // A derived id that is resident is overwritten in place.  One that is not -- its first use, or evicted since by steps the
     // series uploaded -- would take a slot by the ring's rule, which spares the derive's source and the current step but not
@@ -434,7 +437,9 @@ void HipVolumeRenderable::showTimeFraction() {
     }
     if (!resident && smk_blend_timesteps(c, tstep, tstep + 1, tfrac, did, nullptr))
       std::cerr << "ERROR: HipVolumeRenderable::setTimeFractionDerivatives: " << smk_last_error(c) << std::endl;
-    else if (merged ? smk_merge_timestep(c, id, did, nullptr) : smk_derive_timestep(c, id, did, 1, 0, nullptr))
+    else if (merged_h || (merged && tblur) ? smk_merge_timestep_h(c, id, did, merged_h ? 1 : 0, 1, tblur, nullptr)
+             : merged                      ? smk_merge_timestep(c, id, did, nullptr)
+                                           : smk_derive_timestep(c, id, did, 1, tblur, nullptr))
       std::cerr << "ERROR: HipVolumeRenderable::setTimeFractionDerivatives: " << smk_last_error(c) << std::endl;
     else
       shown = did;
@@ -452,6 +457,13 @@ int HipVolumeRenderable::setTimeFractionDerivatives(int on_off) {
   const int on = on_off ? 1 : 0;
   if (on != tderive) tblend_t = -1;  // (the fraction shown now is made again, with or without its derivatives)
   tderive = on;
+  return 0;
+}
+
+int HipVolumeRenderable::setBlurNormals(int on_off) {
+  const int on = on_off ? 1 : 0;
+  if (on != tblur && tderive) tblend_t = -1;  // (the fraction shown now is made again with the other normals)
+  tblur = on;
   return 0;
 }
 

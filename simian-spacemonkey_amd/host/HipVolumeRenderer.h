@@ -135,7 +135,7 @@ class HipVolumeRenderable final : public gluvvPrimitive {
  public:
   explicit HipVolumeRenderable(int device = 0)
       : volren(nullptr), go(0), device(device), tstep(0), tcache(1), u16(0), tfrac(0), tblend_t(-1), tblend_f(0), tblend_id(-1), tblend_next(0),
-        tblend_grown(0), tderive(0) {}
+        tblend_grown(0), tderive(0), tblur(0) {}
   ~HipVolumeRenderable() { delete volren; }  // (gluvvPrimitive's destructor is not virtual, gluvvPrimitive.h:26: delete through this type)
   void init();  // virtual in gluvvPrimitive (gluvvPrimitive.h:29-30)
   void draw();
@@ -163,6 +163,12 @@ class HipVolumeRenderable final : public gluvvPrimitive {
   // must be V, G, H (nelts 3): a derive that is refused is reported once on stderr, as a refused blend is, and the frames show
   // the blend.  Returns 0.  Call after init().
   int setTimeFractionDerivatives(int on_off);
+  // gluvv.cpp's file-scope `blurnorms` (-blurNormals, gluvv.cpp:1457), which initData() hands to normalsVGH and mergeMV.
+  // Default 0.  On: the derivatives of a blend carry blurred normals, in the derive and in the merge.  A series of data mode
+  // GDM_V1GH or GDM_V2GH -- what mergeMV with -addH made of one or two fields -- shows under setTimeFractionDerivatives the
+  // blended fields with G AND H of their summed gradient (smk_merge_timestep_h, add_h 1, the reference's typo kept).  With
+  // this unset and the other data modes the calls are those described above.  Returns 0.  Call after init().
+  int setBlurNormals(int on_off);
   // MetaVolume::writeAll + Volume::writeVol (MetaVolume.cpp:99-126, 963-1000) for the step draw() shows -- a blend made by
   // setTimeFraction included --, read back from the renderer (HipVolumeRenderer::downloadStep).  A one-channel 8-bit step
   // goes to "<prefix>.trex" plus the raw brick, one sub-volume, as writeAll writes it (smkfiles::write_trex); a
@@ -194,5 +200,6 @@ class HipVolumeRenderable final : public gluvvPrimitive {
                             // step: INT_MAX - 2 and INT_MAX - 3)
   int tblend_grown;         // the slots the ring has beyond the series': 2 that the blends live in, 4 with their derived steps
   int tderive;              // setTimeFractionDerivatives
+  int tblur;                // setBlurNormals
   std::vector<unsigned char> noise;  // [sz][sy][sx][4]
 };
