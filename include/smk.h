@@ -982,7 +982,25 @@ int smk_timing_read(smk_ctx *ctx, float *avg_ms, int *nframes);
  *   bricks             1 when the brick flags are in use (empty layers), else 0
  *   perm dir           principal axis (0: S = z, 1: S = y, 2: S = x on the x-major copy); marching direction +1 / -1
  *   lds_bytes          the workgroup's LDS allocation
- *   slices_max         slices the longest tile's loaders have to stream (its positions + 1), from the host's window scan */
+ *   slices_max         slices the longest tile's loaders have to stream (its positions + 1), from the host's window scan
+ * The column-stream kernel (option "kernel" 3) of the latest frame: "cols_builds" (column layouts built so far),
+ * "cols_config" (cw | ch << 8 | nslots << 16 | shape << 24), "cols_jobs", "cols_stream_bytes" (host memory); "cols_job_ms_max",
+ * "cols_job_ms_sum", "cols_setup_ms_sum", "cols_rays" (over the jobs' workgroups; synchronise); with option "cols_counts" on
+ * "cols_samples", "cols_visible", "cols_slices", "cols_segments", "cols_iters", "cols_active_lanes", "cols_switch_iters",
+ * "cols_switch_lanes" (synchronise).
+ * "cols_plan_<field>": the launch plan of the latest column-stream frame (host memory, no synchronisation; every field reads
+ * 0 unless smk_last_frame_info reports kernel 4).  Fields:
+ *   cw ch ncu ncv      cells per column along U and V; columns (the pad voxel of a box of 8-byte voxels is no cell)
+ *   slice_bytes        a column's slice image: (cw + 1)(ch + 1) voxels, rounded up to 16 bytes
+ *   n_ch last_units    DMA wave-instructions per slice = ceil(slice_bytes / 1024); lanes (16-byte units) of the last one, 1..64
+ *   nslots maxfly      the ring's slots (option "cols_ns" caps them); slices one loader keeps in flight ("cols_fly")
+ *   wstep              slices a wave waits for beyond the two it reads ("cols_wstep" - 1), at most nslots - 2
+ *   take_min take_wait a wave takes new rays when this many lanes are free, or after this many turns ("cols_take_min",
+ *                      "cols_take_wait" - 1)
+ *   cl nck             slice positions per chunk ("cols_chunk" caps them, 4..256); chunks
+ *   nkeys mask_words   segment keys = ncu + ncv + nck - 2; 64-bit mask words per pixel, at most 8
+ *   shape              workgroup shape: 0 = 15 consumer waves + 1 loader, 1 = 14 + 2 ("cols_shape" - 1)
+ *   perm dir           principal axis (0: S = z, 1: S = y, 2: S = x); marching direction +1 / -1 */
 int smk_get_stat(smk_ctx *ctx, const char *name, double *value);
 /* workgroup timeline of the last slice-ring frame (developer tool):
  * records of 8 x uint32 {start, end (100 MHz ticks), HW_ID, XCC_ID | tile<<8 | slices<<20, loader 0's

@@ -21,7 +21,8 @@ struct ColPlan {
   double dens;     // pixels per (u, v) cell of a slice, at the densest place
   double side_u, side_v;  // pixels under a cell's side faces along U / along V there, weighted (cols_density)
   double ds;       // slices a ray advances per plane, at least
-  int cells_u, cells_v;   // cells of the stored box across the view
+  int cells_u, cells_v;   // cells of the stored box across the view (cols_cells: a pad column is no cell)
+  int npos;               // slice positions along S to chunk (cols_cells)
   double slab;     // slices the thickest slab between two slice positions spans (the volume's outermost cells: below)
   int shape;       // workgroup shape (kColShapes)
   int vb;          // bytes per voxel
@@ -83,6 +84,21 @@ static const char *cols_axes(const RenderParams &P, ColParams &Q, ColPlan &L) {
   Q.Ou = P.O[L.au]; Q.Ov = P.O[L.av]; Q.Os = P.O[as];
   Q.Du = P.D[L.au]; Q.Dv = P.D[L.av]; Q.Ds = P.D[as];
   return nullptr;
+}
+
+// ---- cells: what the columns and the chunks divide.  A box of 8-byte voxels has even x and y extents; where the volume's
+// own extent is odd the box ends in a pad voxel (index N, never sampled: the base cell of a clamped coordinate is at most
+// N - 2).  The pad is no cell: a column, or a chunk, that held the pad's cell alone would have the volume's face as its
+// whole box -- [N - 1, N - 1/2], whose samples have their base cell in the column (chunk) before it, which takes them as
+// well -- every such sample twice, and fetched from one cell outside the column (found by the plan sweep,
+// tests/test_gpu_cols_plans.py; counted in, the 129 cells of a box of 130 voxels in columns of 16 are eight columns and the
+// pad).  Along U and V the pad cell is left out;
+// along S it can only be left out where it is the LAST position, marching towards it (the kernel counts positions from the
+// near end); marching away from it it is the first position of the first chunk, which has at least two.
+static void cols_cells(const RenderParams &P, const ColParams &Q, ColPlan &L) {
+  L.cells_u = std::max(std::min(Q.Du, P.N[L.au] - Q.Ou) - 1, 1);
+  L.cells_v = std::max(std::min(Q.Dv, P.N[L.av] - Q.Ov) - 1, 1);
+  L.npos = std::max((Q.dir > 0 ? std::min(Q.Ds, P.N[L.as] - Q.Os) : Q.Ds) - 1, 1);
 }
 
 static bool inv3(const double m[9], double o[9]) {
@@ -165,8 +181,6 @@ static const char *cols_density(const RenderParams &P, const ColParams &Q, ColPl
   }
   if (!(dens > 1e-9)) return "degenerate projection";
   L.dens = dens;
-  L.cells_u = Q.Du - 1;
-  L.cells_v = Q.Dv - 1;
   L.slab = Q.Ds - 1 <= 1 ? 2.0 : 1.5;
   const double under = L.slab * std::max(0.0, 1.0 - L.ds / L.slab);
   L.side_u = under * side_u;
@@ -246,7 +260,7 @@ static hipError_t cols_layout(const RenderParams &P, ColParams &Q, const ColPlan
                               const char **why, hipStream_t s) {
   ColLayout &LY = aux->lay[L.perm];
   const int lanes = kColShapes[L.shape].nw * 64;
-  const int cells_u = Q.Du - 1, cells_v = Q.Dv - 1;
+  const int cells_u = L.cells_u, cells_v = L.cells_v;
   const double fill = (aux->opt_fill > 0 ? aux->opt_fill : 92) * 0.01;  // of the lanes, at the densest place
   bool reuse = LY.d && LY.Du == Q.Du && LY.Dv == Q.Dv && LY.Ds == Q.Ds && LY.src == vox_native && LY.vb == L.vb;
   if (reuse) {
@@ -290,7 +304,11 @@ static hipError_t cols_layout(const RenderParams &P, ColParams &Q, const ColPlan
 }
 
 // ---- ring: the DMA instructions per slice, the slots in LDS (option cols_ns caps them), slices in flight per loader
-// (cols_fly), the band wait (cols_wstep) and when a wave takes new rays (cols_take_min, cols_take_wait)
+// (cols_fly), the band wait (cols_wstep) and when a wave takes new rays (cols_take_min, cols_take_wait).
+// The band wait is bounded by the ring: a consumer at position p waits for min(p + 2 + wstep, npos + 1) landed slices, the
+// last of them load p + 1 + wstep, and a loader issues load r only while r - nslots < the slowest consumer's position <= p
+// -- so that load is issued only where wstep <= nslots - 2.  A larger request (cols_wstep up to 7, whatever cols_ns says)
+// would wait for a slice the ring cannot hold until the bounded spin gives up (status 1): it is clamped.
 static const char *cols_ring(const ColsAux *aux, const ColPlan &L, ColParams &Q) {
   Q.n_ch = (Q.slice_bytes + 1023) / 1024;
   const int last_units = Q.slice_bytes / 16 - 64 * (Q.n_ch - 1);
@@ -303,16 +321,16 @@ static const char *cols_ring(const ColsAux *aux, const ColPlan &L, ColParams &Q)
   Q.maxfly = std::max(1, std::min(aux->opt_fly > 0 ? aux->opt_fly : 2, (nslots - 2) / kColShapes[L.shape].nl));
   while (Q.maxfly > 1 && Q.n_ch * Q.maxfly > 63) --Q.maxfly;  // (the counted vmcnt wait takes an immediate < 64)
   if (Q.n_ch > 63) return "column slice needs more than 63 DMA instructions";
-  Q.wstep = aux->opt_wstep ? aux->opt_wstep - 1 : (nslots >= 7 ? 2 : nslots >= 5 ? 1 : 0);
+  Q.wstep = std::min(aux->opt_wstep ? aux->opt_wstep - 1 : (nslots >= 7 ? 2 : nslots >= 5 ? 1 : 0), nslots - 2);
   Q.take_min = aux->opt_take_min > 0 ? aux->opt_take_min : 16;
   Q.take_wait = aux->opt_take_wait > 0 ? aux->opt_take_wait - 1 : 3;
   return nullptr;
 }
 
-// ---- chunks and keys: the Ds - 1 slice positions in equal chunks of at most 128 (option cols_chunk, 4..COL_MAX_CL); a
-// segment key per column index along U and V and per chunk
+// ---- chunks and keys: the slice positions (cols_cells) in equal chunks of at most 128 (option cols_chunk, 4..COL_MAX_CL);
+// a segment key per column index along U and V and per chunk
 static const char *cols_chunks(const ColsAux *aux, ColParams &Q, ColPlan &L) {
-  const int npos_total = Q.Ds - 1;
+  const int npos_total = L.npos;
   int clmax = aux->opt_chunk ? std::min(aux->opt_chunk, COL_MAX_CL) : 128;
   clmax = std::max(clmax, 4);
   Q.nck = (npos_total + clmax - 1) / clmax;
@@ -374,6 +392,10 @@ static hipError_t cols_run(const RenderParams &P, ColParams &Q, const ColPlan &L
   aux->njobs_last = L.njobs;
   aux->cw_last = Q.CW; aux->ch_last = Q.CH; aux->nslots_last = Q.nslots; aux->shape_last = L.shape;
   aux->last_stream_bytes = (double)L.njobs / Q.nck * ((double)(Q.Ds - 1) + Q.nck) * Q.slice_bytes;
+  const int plan[ColsAux::PLAN_FIELDS] = {Q.CW, Q.CH, Q.ncu, Q.ncv, Q.slice_bytes, Q.n_ch, (int)__builtin_popcountll(Q.last_mask),
+                                          Q.nslots, Q.maxfly, Q.wstep, Q.take_min, Q.take_wait, Q.CL, Q.nck, Q.nkeys, Q.mask_words,
+                                          L.shape, L.perm, Q.dir};
+  memcpy(aux->plan_last, plan, sizeof plan);
   Q.ring_bytes = (int)std::max((size_t)Q.nslots * Q.slice_bytes, (size_t)COL_MAX_RAYS * 16);  // (set-up scratch: the unsorted rays)
   const size_t lds = (size_t)Q.ring_bytes + L.fixed;
   if (lds > COL_LDS_CAP) { *why = "column job does not fit LDS"; return hipErrorNotSupported; }
@@ -399,7 +421,9 @@ hipError_t smk_launch_cols(RenderParams P, int dtype, int tf_mode, int shade_kin
   ColPlan L = {};
   if ((*why = cols_refusal(P, dtype, tf_mode))) return hipErrorNotSupported;
   if (tf_mode == 0) shade_kind = 0;
-  if ((*why = cols_axes(P, Q, L)) || (*why = cols_projection(P, Q)) || (*why = cols_density(P, Q, L)) ||
+  if ((*why = cols_axes(P, Q, L))) return hipErrorNotSupported;
+  cols_cells(P, Q, L);
+  if ((*why = cols_projection(P, Q)) || (*why = cols_density(P, Q, L)) ||
       (*why = cols_lds_budget(P, dtype, tf_mode, aux, Q, L)))
     return hipErrorNotSupported;
   hipError_t e = cols_layout(P, Q, L, dtype, vox_native, aux, why, s);
@@ -422,10 +446,24 @@ void smk_cols_drop_layouts(ColsAux *aux) {
   for (int k = 0; k < 3; ++k) cols_free_layout(aux->lay[k]);
 }
 
-// ---- statistics of the latest frame (smk_get_stat "cols_*"); these synchronise
+// the fields of "cols_plan_<field>" in the order cols_run records them (ColsAux::plan_last; last_units: the lanes of the
+// last DMA instruction's mask as the kernel gets it)
+static const char *const kColsPlanFields[ColsAux::PLAN_FIELDS] = {"cw", "ch", "ncu", "ncv", "slice_bytes", "n_ch", "last_units", "nslots", "maxfly",
+                                                                  "wstep", "take_min", "take_wait", "cl", "nck", "nkeys", "mask_words", "shape",
+                                                                  "perm", "dir"};
+
+// ---- statistics of the latest frame (smk_get_stat "cols_*"); these synchronise (the plan's fields do not)
 int smk_cols_stat(smk_ctx *c, const char *name, double *value) {
   const ColsAux &A = c->cols;
   *value = 0.0;
+  if (!strncmp(name, "cols_plan_", 10)) {  // host memory; 0 unless the latest frame was this kernel's
+    for (int k = 0; k < ColsAux::PLAN_FIELDS; ++k)
+      if (!strcmp(name + 10, kColsPlanFields[k])) {
+        if (c->last_kernel == 4) *value = A.plan_last[k];
+        return 0;
+      }
+    FAIL(c, "smk_get_stat: unknown name '%s'", name);
+  }
   if (!strcmp(name, "cols_builds")) { *value = A.builds; return 0; }
   if (!strcmp(name, "cols_config")) { *value = A.cw_last | (A.ch_last << 8) | (A.nslots_last << 16) | (A.shape_last << 24); return 0; }
   if (!strcmp(name, "cols_jobs")) { *value = A.njobs_last; return 0; }

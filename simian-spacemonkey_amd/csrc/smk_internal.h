@@ -226,6 +226,10 @@ struct ColsAux {
   int builds = 0;               // layouts built so far
   int cw_last = 0, ch_last = 0, nslots_last = 0, shape_last = 0;  // columns, ring slots and workgroup shape of the latest launch
   double last_stream_bytes = 0; // bytes the loaders of the latest launch had to stream
+  // the launch plan of the latest launch (smk_get_stat "cols_plan_<field>", smk.h; the order of kColsPlanFields in
+  // smk_cols_plan.hip)
+  static constexpr int PLAN_FIELDS = 19;
+  int plan_last[PLAN_FIELDS] = {0};
   hipEvent_t frame_ev0 = nullptr;
   int status_tag = 0;           // the frame's id << 8 (written with a status word)
 };
