@@ -226,7 +226,8 @@ int smk_upload_timestep_fields_device(smk_ctx *ctx, int timestep, const void *co
  * follow.  No host wait, no allocation, no scratch arrays.  Slots, the in-place overwrite of a cached step_out, ordering and
  * refusals are smk_merge_timestep's.  Refused in addition, changing nothing: add_h or blur outside 0 / 1; nelts - 1 - add_h < 1;
  * add_h on a SMK_U16 ring with nelts != 3; a sharded context (the stencil reaches 2 voxels beyond region + halo and the scaling
- * needs the whole volume's three extremes: the shard and block forms do not exist yet). */
+ * needs the whole volume's three extremes: smk_step_extremes_h_device + smk_merge_timestep_h_shard below are the two-call
+ * form, smk_block_extremes_h_device + smk_upload_timestep_fields_h_block_device the one from blocks). */
 int smk_merge_timestep_h(smk_ctx *ctx, int step_src, int step_out, int add_h, int compat, int blur, void *stream);
 /* The same from nf = nelts - 1 - add_h dense scalars in DEVICE memory, as smk_upload_timestep_fields_device takes them, with
  * that entry's additional refusals. */
@@ -239,8 +240,8 @@ int smk_upload_timestep_fields_h_device(smk_ctx *ctx, int timestep, const void *
  *     EXPORTS those of its region (smk_step_extremes_device), the host combines the ranks' words by elementwise integer
  *     maximum -- in-process ranks directly, a multi-process host with one integer MAX all-reduce of 8 words on its own
  *     transport --, and every rank runs the write pass with the combined words (smk_*_timestep_shard);
- *   - the stencil reaches r voxels (r = 2 for the derive, blurred or not; r = 1 for the merge), and option "halo" lets a
- *     context keep that many and more.
+ *   - the stencil reaches r voxels (r = 2 for the derive, blurred or not; r = 1 for the merge; r = 2 for the merge with H,
+ *     smk_merge_timestep_h_shard further below), and option "halo" lets a context keep that many and more.
  * THE WORDS.  Eight int32 in device memory.  A float x travels as its ordered int ord(x) = bits >= 0 ? bits : bits ^ 0x7fffffff
  * (ascending with x), and every MINIMUM as the bitwise complement of that, so that all eight words combine by maximum:
  *   SMK_EXTREMES_DERIVE  {~ord(min V), ord(max V), ~ord(min G), ord(max G), ~ord(min H), ord(max H), INT_MIN, INT_MIN}
@@ -272,7 +273,7 @@ int smk_upload_timestep_fields_h_device(smk_ctx *ctx, int timestep, const void *
  * reason: an unknown kind; d_words NULL or misaligned; no volume; the series' nelts (3 for the derive, >= 2 for the merge);
  * a volume thinner than 3 voxels; step_src not cached; a source whose valid halo is below r + 1 on a sharded context (the
  * message names both numbers). */
-enum { SMK_EXTREMES_DERIVE = 0, SMK_EXTREMES_MERGE = 1 };
+enum { SMK_EXTREMES_DERIVE = 0, SMK_EXTREMES_MERGE = 1, SMK_EXTREMES_MERGE_H = 2 /* a word layout, not a kind: smk_step_extremes_h_device */ };
 int smk_step_extremes_device(smk_ctx *ctx, int kind, int step_src, int compat, void *d_words, void *stream);
 /* The write pass alone: step `step_out` becomes the VGH step (derive) or the multi-field step (merge) of the cached step
  * `step_src`, scaled by the extremes in the eight words at `d_words` (device memory, read by the kernels on `stream`: the
@@ -350,6 +351,46 @@ int smk_upload_timestep_scalar_block_device(smk_ctx *ctx, int timestep, const vo
                                             const smk_block *block, int compat, int blur, const void *d_words, void *stream);
 int smk_upload_timestep_fields_block_device(smk_ctx *ctx, int timestep, const void *const *d_fields, int nf, smk_dtype field_dtype,
                                             const smk_block *block, const void *d_words, void *stream);
+/* ---- Merged fields WITH H and blurred normals on a SHARDED context and from blocks: smk_merge_timestep_h and
+ * smk_upload_timestep_fields_h_device as the same two calls with the same exchange of eight integers between them.  Entries
+ * of their own because add_h decides which channels are fields (nf = nelts - 1 - add_h), which smk_step_extremes_device's
+ * signature has no place for; SMK_EXTREMES_MERGE_H names their word layout and is no kind of that entry.
+ * THE WORDS.  Eight int32, all combined by maximum as above:
+ *   SMK_EXTREMES_MERGE_H  {ord(max magnitude), ~ord(min H), ord(max H), INT_MIN x 5}
+ * over the REGION's interior voxels of the volume, the border decided on global voxels: the magnitude of the summed gradient
+ * and, with add_h, its second derivative H, counted as pass 1 of smk_merge_timestep_h counts them (a u8 ring: every magnitude
+ * and every H that is not NaN; u16 and f32: the finite ones).  The seeds are {0, ~ord(+inf), ord(-inf)}: with add_h == 0 words
+ * 1 and 2 keep them, and a region without an interior voxel exports all three.  The write pass undoes the complement and then
+ * applies the reference's +-1e8 seeds to min H and max H exactly as smk_merge_timestep_h does.  The maximum over the ranks'
+ * words equals, bit for bit, the words an unsharded context exports for the same step.
+ * THE REACH.  r = 2 for every combination of the flags: H reads the summed gradient of the six neighbours, a blurred normal that
+ * of the 26, and each of those the fields one voxel further.  (A caller who wants reach 1 with no H and no blur has
+ * smk_merge_timestep_shard.)  So a source valid halo below 3 on a sharded context is refused with both numbers; the result's
+ * valid box is the source's (a block: C) shrunk by 2 at every face that is no face of the volume; its valid halo is the
+ * source's less 2 on a sharded series, unchanged on an unsharded context; the rim is zeros with the normal (128, 128, 128);
+ * the pad column and row are zeros.
+ * THE CONTRACT.  Inside the valid box every stored field and normal byte is what smk_merge_timestep_h /
+ * smk_upload_timestep_fields_h_device store at that voxel on an unsharded context from the whole volume.  On an unsharded
+ * context, export followed by the write entry stores the one-call entry's bits.
+ * smk_step_extremes_h_device: pass 1 over this context's region of the cached step `step_src` into the eight words at d_words
+ * (device memory, 4-byte aligned, overwritten).  A reader of the step, ordered as smk_step_extremes_device.
+ * smk_merge_timestep_h_shard: the write pass with the combined words; a producer like smk_merge_timestep_shard (slot rule,
+ * in-place overwrite of a cached step_out, ordering on `stream`, brick summaries).  The words are not validated.
+ * smk_block_extremes_h_device, smk_upload_timestep_fields_h_block_device: the same from nf = nelts - 1 - add_h dense fields of
+ * the ring's dtype, every array laid out by the one block; F is taken as 0 outside C.  Reads no slot / a producer into step
+ * `timestep`, as smk_block_extremes_device / smk_upload_timestep_fields_block_device.
+ * No host synchronisation, no allocation in any of the four.  Refused, with the reason, changing nothing: add_h or blur outside
+ * 0 / 1; nelts - 1 - add_h < 1; add_h on a SMK_U16 ring with nelts != 3; d_words NULL or misaligned; what
+ * smk_step_extremes_device and smk_merge_timestep_shard (blocks: the block entries above) refuse, with reach 2; for blocks
+ * d_fields NULL, a NULL or misaligned array, nf != nelts - 1 - add_h, a dtype that is not the ring's. */
+int smk_step_extremes_h_device(smk_ctx *ctx, int step_src, int add_h, int compat, void *d_words, void *stream);
+int smk_merge_timestep_h_shard(smk_ctx *ctx, int step_src, int step_out, int add_h, int compat, int blur, const void *d_words,
+                               void *stream);
+int smk_block_extremes_h_device(smk_ctx *ctx, const void *const *d_fields, int nf, smk_dtype dtype, const smk_block *block, int add_h,
+                                int compat, void *d_words, void *stream);
+int smk_upload_timestep_fields_h_block_device(smk_ctx *ctx, int timestep, const void *const *d_fields, int nf, smk_dtype field_dtype,
+                                              const smk_block *block, int add_h, int compat, int blur, const void *d_words,
+                                              void *stream);
 /* introspection: the current step (-1: no volume), the cached ids oldest written first (min(cap, *n) of them; ids_out may
  * be NULL), their number */
 int smk_get_timesteps(smk_ctx *ctx, int *current, int *ids_out, int cap, int *n);

@@ -42,9 +42,12 @@ ABI_SYMBOLS = [
     "smk_declare_volume", "smk_upload_timestep_block_device", "smk_block_extremes_device",
     "smk_upload_timestep_scalar_block_device", "smk_upload_timestep_fields_block_device",
     "smk_merge_fields_h_device", "smk_merge_fields_h_f32_device", "smk_merge_timestep_h", "smk_upload_timestep_fields_h_device",
+    "smk_step_extremes_h_device", "smk_merge_timestep_h_shard", "smk_block_extremes_h_device",
+    "smk_upload_timestep_fields_h_block_device",
 ]
 STEP_CURRENT = -1  # SMK_STEP_CURRENT: the step the frames render
 EXTREMES_DERIVE, EXTREMES_MERGE = 0, 1  # SMK_EXTREMES_*: the kind of smk_step_extremes_device
+EXTREMES_MERGE_H = 2  # SMK_EXTREMES_MERGE_H: the word layout of smk_step_extremes_h_device and smk_block_extremes_h_device
 
 # gluvvDataMode order (gluvv.h:221-235)
 GDM = {n: i for i, n in enumerate(
@@ -177,6 +180,12 @@ def load_library():
     L.smk_merge_timestep_h.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
     L.smk_upload_timestep_fields_h_device.argtypes = [C.c_void_p, C.c_int, P(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int,
                                                       C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.smk_step_extremes_h_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.smk_merge_timestep_h_shard.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.smk_block_extremes_h_device.argtypes = [C.c_void_p, P(C.c_void_p), C.c_int, C.c_int, P(Block), C.c_int, C.c_int, C.c_void_p,
+                                              C.c_void_p]
+    L.smk_upload_timestep_fields_h_block_device.argtypes = [C.c_void_p, C.c_int, P(C.c_void_p), C.c_int, C.c_int, P(Block), C.c_int,
+                                                            C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.smk_merge_fields_h_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                             C.c_void_p, C.c_void_p]
     L.smk_merge_fields_h_f32_device.argtypes = L.smk_merge_fields_h_device.argtypes
@@ -466,6 +475,17 @@ class Renderer:
         (smk.h smk_merge_timestep_shard); exact on the step's valid box, zeros on its rim"""
         self._ck(self.L.smk_merge_timestep_shard(self.ctx, int(src), int(out), d_words, stream))
 
+    def step_extremes_h_device(self, src, d_words, add_h=1, compat=1, stream=None):
+        """pass 1 of merge_timestep_h over this context's region of the cached step `src`: {max magnitude, ~min H, max H} and
+        five unused words (layout EXTREMES_MERGE_H) into the eight int32 words at device address `d_words`; without add_h the H
+        words keep their seeds (smk.h smk_step_extremes_h_device)"""
+        self._ck(self.L.smk_step_extremes_h_device(self.ctx, int(src), int(add_h), int(compat), d_words, stream))
+
+    def merge_timestep_h_shard(self, src, out, d_words, add_h=1, compat=1, blur=0, stream=None):
+        """merge_timestep_h's write pass with the combined extremes read from the eight words at device address `d_words`
+        (smk.h smk_merge_timestep_h_shard); the stencil reaches 2 voxels: exact on the step's valid box, zeros on its rim"""
+        self._ck(self.L.smk_merge_timestep_h_shard(self.ctx, int(src), int(out), int(add_h), int(compat), int(blur), d_words, stream))
+
     # -- blocks of a decomposed simulation (smk.h: smk_block ...): a rank's own dense block of the volume, wherever it lies
     def declare_volume(self, dims, nelts, dtype, fsize=None, dmode="VGH", normals=True):
         """the series' geometry without data: the context as upload_volume leaves it for a volume of zeros of dims (x, y, z)
@@ -507,6 +527,20 @@ class Renderer:
         (smk.h smk_upload_timestep_fields_block_device)"""
         self._ck(self.L.smk_upload_timestep_fields_block_device(self.ctx, int(timestep), self._ptr_array(ptrs), 0 if ptrs is None else len(ptrs),
                                                                 int(dtype), self._block_arg(block), d_words, stream))
+
+    def block_extremes_h_device(self, ptrs, dtype, block, d_words, add_h=1, compat=1, stream=None):
+        """pass 1 of the merge with H over this context's region, read from the nelts - 1 - add_h dense fields of `block` (the
+        ring's dtype), into the eight int32 words at device address `d_words`, layout EXTREMES_MERGE_H (smk.h
+        smk_block_extremes_h_device)"""
+        self._ck(self.L.smk_block_extremes_h_device(self.ctx, self._ptr_array(ptrs), 0 if ptrs is None else len(ptrs), int(dtype),
+                                                    self._block_arg(block), int(add_h), int(compat), d_words, stream))
+
+    def upload_timestep_fields_h_block_device(self, timestep, ptrs, dtype, block, d_words, add_h=1, compat=1, blur=0, stream=None):
+        """the write pass of the merge with H from the fields of `block`, one device address each, with the combined words at
+        `d_words` (smk.h smk_upload_timestep_fields_h_block_device); the stencil reaches 2 voxels"""
+        self._ck(self.L.smk_upload_timestep_fields_h_block_device(self.ctx, int(timestep), self._ptr_array(ptrs),
+                                                                  0 if ptrs is None else len(ptrs), int(dtype), self._block_arg(block),
+                                                                  int(add_h), int(compat), int(blur), d_words, stream))
 
     def timestep_halo(self, step=STEP_CURRENT):
         """the valid halo of a cached step: the halo voxels round the region that are exact (smk.h smk_get_timestep_halo)"""

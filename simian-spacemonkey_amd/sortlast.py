@@ -323,13 +323,18 @@ def render_shadow_frame_local(renderers, depth=False, scene_depth=None, scene_de
     return (out.view(h, w, 4), dout.view(h, w)) if depth else out.view(h, w, 4)
 
 
-def stencil_timestep_local(renderers, kind, src, out, compat=1, blur=0, stream=None, words=None):
-    """Step `out` becomes the derived (kind "derive") or merged (kind "merge") step of the cached step `src` on P shard contexts
-    of this process that share one device, ranks in order (smk.h, "The two stencil producers on a SHARDED context"): every rank
-    exports the extremes of its region (smk_step_extremes_device), the eight words combine by elementwise integer maximum, and
-    every rank runs the write pass with the combined words (smk_derive_timestep_shard / smk_merge_timestep_shard).  No voxel
+def stencil_timestep_local(renderers, kind, src, out, compat=1, blur=0, stream=None, words=None, add_h=1):
+    """Step `out` becomes the derived (kind "derive"), merged (kind "merge") or merged-with-H (kind "merge_h") step of the cached
+    step `src` on P shard contexts of this process that share one device, ranks in order (smk.h, "The two stencil producers on a
+    SHARDED context"): every rank exports the extremes of its region (smk_step_extremes_device; "merge_h":
+    smk_step_extremes_h_device), the eight words combine by elementwise integer maximum, and every rank runs the write pass
+    with the combined words (smk_derive_timestep_shard / smk_merge_timestep_shard / smk_merge_timestep_h_shard).  No voxel
     moves between ranks.  A multi-process host does the same with one integer MAX all-reduce of 8 words in place of the
     maximum taken here.
+    The stencil reaches 2 voxels for "derive" and for "merge_h" (whatever add_h and blur are), 1 voxel for "merge": the source
+    needs a valid halo of the reach + 1, and the result's is the source's less the reach.
+    add_h: "merge_h" alone -- 1: the channel behind G is H of the summed gradient; 0: no H (blur then gives smoothed normals
+    to a merge without H).  compat and blur: "derive" and "merge_h"; "merge" has neither.
     stream: a hipStream_t handle for every rank's kernels (an int or a ctypes.c_void_p).  Exports, the maximum and the write
     passes are then all enqueued on it and the host waits for nothing.  None: each context's own stream; the host then waits
     once for the ranks' exports and once for the combined words, both waits the combine's; the write passes are enqueued and
@@ -337,8 +342,8 @@ def stencil_timestep_local(renderers, kind, src, out, compat=1, blur=0, stream=N
     words: a [P + 1][8] int32 tensor on the device to work in (rows 0..P-1 the ranks' exports, row P the combined words), or
     None to have one made.  It is returned, and must stay alive until the streams have passed the write passes."""
     from .binding import EXTREMES_DERIVE, EXTREMES_MERGE
-    if kind not in ("derive", "merge"):
-        raise ValueError("kind must be 'derive' or 'merge', got %r" % (kind,))
+    if kind not in ("derive", "merge", "merge_h"):
+        raise ValueError("kind must be 'derive', 'merge' or 'merge_h', got %r" % (kind,))
     nranks = len(renderers)
     dev = torch.device("cuda", renderers[0].device)
     if words is None:
@@ -347,7 +352,10 @@ def stencil_timestep_local(renderers, kind, src, out, compat=1, blur=0, stream=N
         raise ValueError("words must be a contiguous [%d][8] int32 tensor" % (nranks + 1))
     k = EXTREMES_DERIVE if kind == "derive" else EXTREMES_MERGE
     for r, R in enumerate(renderers):
-        R.step_extremes_device(k, src, words[r].data_ptr(), compat=compat, stream=stream)
+        if kind == "merge_h":
+            R.step_extremes_h_device(src, words[r].data_ptr(), add_h=add_h, compat=compat, stream=stream)
+        else:
+            R.step_extremes_device(k, src, words[r].data_ptr(), compat=compat, stream=stream)
     if stream is None:
         torch.cuda.synchronize(dev)  # the combine's wait: every rank's export, each on its context's stream, is in memory
         words[nranks].copy_(words[:nranks].amax(0))
@@ -359,24 +367,30 @@ def stencil_timestep_local(renderers, kind, src, out, compat=1, blur=0, stream=N
     for R in renderers:
         if kind == "derive":
             R.derive_timestep_shard(src, out, words[nranks].data_ptr(), compat=compat, blur=blur, stream=stream)
+        elif kind == "merge_h":
+            R.merge_timestep_h_shard(src, out, words[nranks].data_ptr(), add_h=add_h, compat=compat, blur=blur, stream=stream)
         else:
             R.merge_timestep_shard(src, out, words[nranks].data_ptr(), stream=stream)
     return words
 
 
-def stencil_block_local(renderers, kind, blocks, out, compat=1, blur=0, stream=None, words=None):
+def stencil_block_local(renderers, kind, blocks, out, compat=1, blur=0, stream=None, words=None, add_h=1):
     """stencil_timestep_local from the ranks' OWN dense blocks of the volume in place of a cached step (smk.h, "Blocks of a
-    decomposed simulation"): step `out` becomes the derived (kind "derive") or merged (kind "merge") step of the scalar or the
-    fields every rank holds for its sub-domain, ghost cells included.  blocks: per rank (ptrs, dtype, block) -- the device
-    addresses of the dense arrays (one scalar for the derive, nelts - 1 fields for the merge), their dtype code and the
-    smk_block() that lays all of them out.  Every rank exports the extremes of its region (smk_block_extremes_device), the
-    eight words combine by elementwise integer maximum, and every rank runs the write pass with the combined words
-    (smk_upload_timestep_scalar_block_device / smk_upload_timestep_fields_block_device).  No voxel moves between ranks, and no
-    rank sees an array it does not hold.  A multi-process host does the same with one integer MAX all-reduce of 8 words.
+    decomposed simulation"): step `out` becomes the derived (kind "derive"), merged (kind "merge") or merged-with-H (kind
+    "merge_h") step of the scalar or the fields every rank holds for its sub-domain, ghost cells included.  blocks: per rank
+    (ptrs, dtype, block) -- the device addresses of the dense arrays (one scalar for the derive, nelts - 1 fields for the merge,
+    nelts - 1 - add_h for the merge with H), their dtype code and the smk_block() that lays all of them out.  Every rank
+    exports the extremes of its region (smk_block_extremes_device; "merge_h": smk_block_extremes_h_device), the eight words
+    combine by elementwise integer maximum, and every rank runs the write pass with the combined words
+    (smk_upload_timestep_scalar_block_device / smk_upload_timestep_fields_block_device /
+    smk_upload_timestep_fields_h_block_device).  No voxel moves between ranks, and no rank sees an array it does not hold.  A
+    multi-process host does the same with one integer MAX all-reduce of 8 words.
+    The reach is stencil_timestep_local's: 2 voxels for "derive" and "merge_h", 1 for "merge"; the blocks' ghost cells must give
+    a valid halo of the reach + 1.  add_h: as there.
     stream, words and the return value: as stencil_timestep_local; `stream` also orders the reads of the blocks."""
     from .binding import EXTREMES_DERIVE, EXTREMES_MERGE
-    if kind not in ("derive", "merge"):
-        raise ValueError("kind must be 'derive' or 'merge', got %r" % (kind,))
+    if kind not in ("derive", "merge", "merge_h"):
+        raise ValueError("kind must be 'derive', 'merge' or 'merge_h', got %r" % (kind,))
     nranks = len(renderers)
     if len(blocks) != nranks:
         raise ValueError("%d blocks for %d ranks" % (len(blocks), nranks))
@@ -387,7 +401,10 @@ def stencil_block_local(renderers, kind, blocks, out, compat=1, blur=0, stream=N
         raise ValueError("words must be a contiguous [%d][8] int32 tensor" % (nranks + 1))
     k = EXTREMES_DERIVE if kind == "derive" else EXTREMES_MERGE
     for r, (R, (ptrs, dtype, block)) in enumerate(zip(renderers, blocks)):
-        R.block_extremes_device(k, ptrs, dtype, block, words[r].data_ptr(), compat=compat, stream=stream)
+        if kind == "merge_h":
+            R.block_extremes_h_device(ptrs, dtype, block, words[r].data_ptr(), add_h=add_h, compat=compat, stream=stream)
+        else:
+            R.block_extremes_device(k, ptrs, dtype, block, words[r].data_ptr(), compat=compat, stream=stream)
     if stream is None:
         torch.cuda.synchronize(dev)  # the combine's wait: every rank's export, each on its context's stream, is in memory
         words[nranks].copy_(words[:nranks].amax(0))
@@ -399,6 +416,9 @@ def stencil_block_local(renderers, kind, blocks, out, compat=1, blur=0, stream=N
     for R, (ptrs, dtype, block) in zip(renderers, blocks):
         if kind == "derive":
             R.upload_timestep_scalar_block_device(out, ptrs[0], dtype, block, words[nranks].data_ptr(), compat=compat, blur=blur, stream=stream)
+        elif kind == "merge_h":
+            R.upload_timestep_fields_h_block_device(out, ptrs, dtype, block, words[nranks].data_ptr(), add_h=add_h, compat=compat, blur=blur,
+                                                    stream=stream)
         else:
             R.upload_timestep_fields_block_device(out, ptrs, dtype, block, words[nranks].data_ptr(), stream=stream)
     return words
