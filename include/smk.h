@@ -391,6 +391,59 @@ int smk_block_extremes_h_device(smk_ctx *ctx, const void *const *d_fields, int n
 int smk_upload_timestep_fields_h_block_device(smk_ctx *ctx, int timestep, const void *const *d_fields, int nf, smk_dtype field_dtype,
                                               const smk_block *block, int add_h, int compat, int blur, const void *d_words,
                                               void *stream);
+/* ---- Halo refill: a cached step's stored halo copied, bit for bit, from the ranks that own those voxels ("Halo
+ * refill"; INTEGRATION.md 5, the in-situ recipe).  The stencil producers above move no voxel between ranks and pay with the
+ * valid halo; this is the one operation that moves voxels, and it is optional: a host that needs no more halo than survives
+ * never calls it, and without a call every step, refusal and frame is what it is without these entries.  The regions
+ * partition the volume and a sharded producer's result is exact on its region, so every voxel a rank lacks is held exactly by
+ * exactly one other rank.  After the refill the step is the unsharded step's voxels on the whole stored box: valid box = the
+ * stored box cut at the volume, valid halo = option "halo", no rim; frames, smk_probe_step and later producers treat it as
+ * an uploaded step.  The shape is the light exchange's (smk_shadow_exports_device, _entries_device, _exchange_local).
+ * `timestep` is a cached id or SMK_STEP_CURRENT.
+ * GEOMETRY.  Rank r owns its region [g0_r, g1_r) (smk_set_shard's split).  Rank j stores S_j = [O_j, min(O_j + D_j, N)): the
+ * region plus option "halo" voxels, cut at the volume, with the rule that evens the rows of 8-byte voxels in x and y -- one
+ * more halo voxel where the volume has one, else the origin moved by one, else a pad column or row, which lies outside the
+ * volume and is never touched.  Every rank computes every peer's box from the series' dims, dtype, nranks and the "halo" its
+ * own stored box was made with: all ranks of a series must have the same.  Segment r->j (j != r) is the box region_r ∩ S_j; it
+ * may be empty.  For every j, region_j and the segments i->j tile S_j exactly once.
+ * SEGMENT FORMAT.  VB = 16 for SMK_F32 and 8 otherwise; NB = 4 where the slot has the separate normals buffer (4-channel f32
+ * with normals), else 0.  A segment of n voxels is roundup16(n VB) bytes of packed voxels as stored, in z, y, x order with x
+ * fastest, followed by roundup16(n NB) bytes of normal words in the same order.  The bytes a roundup adds are not written.
+ * smk_step_halo_layout: send_bytes[j] = the length of segment r->j, recv_bytes[i] = that of segment i->r (index r: 0), and
+ * their sums; any output may be NULL.  d_exports holds the segments to ranks 0..P-1 in rank order, back to back; d_entries
+ * the segments from ranks 0..P-1 in rank order, back to back.  send_bytes of r to j equals recv_bytes of j from r, so a
+ * multi-process host moves them with one all-to-all-v (grouped ncclSend / ncclRecv, or MPI_Alltoallv) whose counts and
+ * displacements are these arrays and their prefix sums.  Needs a volume (uploaded or declared) and no step.
+ * smk_step_halo_exports_device: a READER of the step, ordered as smk_hist2d_step_device: enqueued on `stream` (NULL = the
+ * context's) behind the step's writer; what overwrites the step later waits for it.  Copies the voxels of this context's
+ * region that lie in the peers' stored boxes into d_exports.
+ * smk_step_halo_entries_device: an in-place WRITER of the cached step, which may be the current one.  On `stream` it comes
+ * behind the frames and readers of the slot and behind its writer; the step keeps its id and its place in the ring.  It
+ * scatters the segments into the stored halo (the region's own voxels are not written), makes the brick summaries again for
+ * the whole stored box, drops the x-major copy, sets the valid box to S_j and the valid halo to "halo", records the slot's
+ * readiness, and a current step is switched to as after an in-place upload.  The segments are NOT validated: entries that
+ * are not the peers' exports of that step give a halo of whatever they hold.
+ * smk_step_halo_exchange_local: both for the contexts of one process, ranks in order.  On one device every owner's slot is
+ * copied straight into the receivers' slots -- exports read only regions and entries write only outside regions, so the
+ * two never touch the same voxel and nothing is staged --, ordered per slot as a reader of the owner and a writer of the
+ * receiver.  With a `stream` everything is enqueued on it and the host waits for nothing.  With NULL every receiver's copy
+ * runs on its own context's stream and the host waits for all of them, before and after, as smk_shadow_exchange_local does.
+ * Contexts on several devices take stream NULL and go through the two entries above with staging buffers the contexts keep and
+ * peer copies between them.
+ * One launch moves all of a rank's segments (at most nranks - 1 boxes, the table by value in the kernel's arguments); lanes
+ * run along x, then y, then z of a box and move 16 bytes each.  No host synchronisation and no allocation in the two
+ * _device entries.  On an unsharded context all byte counts are 0 and the entries return 0 and do nothing.  They are
+ * idempotent: on a step whose halo is whole they store the same bits again.
+ * Refused, with the reason, changing nothing: no volume; a step that is not cached; a NULL buffer where bytes are due; a
+ * buffer below 16-byte alignment; in the local form: nranks outside 1..8 or different from the contexts' own, a context whose
+ * rank is not its index, a context without a volume or without the step, contexts that differ from rank 0 in dims, dtype,
+ * nelts, normals or "halo" (the message names the first rank that differs and the field), a `stream` with contexts on
+ * several devices. */
+int smk_step_halo_layout(smk_ctx *ctx, long long *send_bytes /*[nranks]*/, long long *recv_bytes /*[nranks]*/, long long *total_send,
+                         long long *total_recv);
+int smk_step_halo_exports_device(smk_ctx *ctx, int timestep, void *d_exports, void *stream);
+int smk_step_halo_entries_device(smk_ctx *ctx, int timestep, const void *d_entries, void *stream);
+int smk_step_halo_exchange_local(smk_ctx *const *all, int nranks, int timestep, void *stream);
 /* introspection: the current step (-1: no volume), the cached ids oldest written first (min(cap, *n) of them; ids_out may
  * be NULL), their number */
 int smk_get_timesteps(smk_ctx *ctx, int *current, int *ids_out, int cap, int *n);

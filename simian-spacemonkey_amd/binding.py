@@ -44,6 +44,7 @@ ABI_SYMBOLS = [
     "smk_merge_fields_h_device", "smk_merge_fields_h_f32_device", "smk_merge_timestep_h", "smk_upload_timestep_fields_h_device",
     "smk_step_extremes_h_device", "smk_merge_timestep_h_shard", "smk_block_extremes_h_device",
     "smk_upload_timestep_fields_h_block_device",
+    "smk_step_halo_layout", "smk_step_halo_exports_device", "smk_step_halo_entries_device", "smk_step_halo_exchange_local",
 ]
 STEP_CURRENT = -1  # SMK_STEP_CURRENT: the step the frames render
 EXTREMES_DERIVE, EXTREMES_MERGE = 0, 1  # SMK_EXTREMES_*: the kind of smk_step_extremes_device
@@ -214,6 +215,10 @@ def load_library():
     L.smk_shadow_exports_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.smk_shadow_entries_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.smk_shadow_exchange_local.argtypes = [P(C.c_void_p), C.c_int]
+    L.smk_step_halo_layout.argtypes = [C.c_void_p, P(C.c_longlong), P(C.c_longlong), P(C.c_longlong), P(C.c_longlong)]
+    L.smk_step_halo_exports_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.smk_step_halo_entries_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.smk_step_halo_exchange_local.argtypes = [P(C.c_void_p), C.c_int, C.c_int, C.c_void_p]
     L.smk_shard_light_order.argtypes = [C.c_void_p, P(C.c_int)]
     L.smk_get_shadow_margin.argtypes = [C.c_void_p, P(C.c_int), P(C.c_int)]
     L.smk_get_brick_flags.argtypes = [C.c_void_p, C.c_void_p, P(C.c_int), P(C.c_int)]
@@ -547,6 +552,25 @@ class Renderer:
         h = C.c_int(0)
         self._ck(self.L.smk_get_timestep_halo(self.ctx, int(step), C.byref(h)))
         return h.value
+
+    # -- halo refill (smk.h: smk_step_halo_layout ...)
+    def step_halo_layout(self, nranks):
+        """(send_bytes [nranks], recv_bytes [nranks], total_send, total_recv) of this rank's halo segments: the counts of the
+        all-to-all-v that moves them, their prefix sums its displacements"""
+        send, recv = (C.c_longlong * nranks)(), (C.c_longlong * nranks)()
+        ts, tr = C.c_longlong(0), C.c_longlong(0)
+        self._ck(self.L.smk_step_halo_layout(self.ctx, send, recv, C.byref(ts), C.byref(tr)))
+        return list(send), list(recv), ts.value, tr.value
+
+    def step_halo_exports_device(self, d_exports, step=STEP_CURRENT, stream=None):
+        """the voxels of this context's region that lie in the peers' stored boxes, packed into total_send bytes of DEVICE
+        memory; a reader of the step, enqueued on `stream` (None = the context's)"""
+        self._ck(self.L.smk_step_halo_exports_device(self.ctx, int(step), d_exports, stream))
+
+    def step_halo_entries_device(self, d_entries, step=STEP_CURRENT, stream=None):
+        """the peers' segments (total_recv bytes of DEVICE memory) scattered into the cached step's stored halo, in place: the
+        step's valid halo is option "halo" again"""
+        self._ck(self.L.smk_step_halo_entries_device(self.ctx, int(step), d_entries, stream))
 
     def timesteps(self):
         """(current step or -1, the cached ids oldest written first)"""
@@ -988,6 +1012,16 @@ def shadow_exchange_local(renderers):
     if rc != 0:
         msgs = [r.L.smk_last_error(r.ctx).decode() for r in renderers]
         raise SmkError(next((m for m in msgs if m), "smk_shadow_exchange_local failed"))
+
+
+def step_halo_exchange_local(renderers, step=STEP_CURRENT, stream=None):
+    """the halo refill of a cached step for shard contexts of this process, in rank order (smk.h
+    smk_step_halo_exchange_local)"""
+    arr = (C.c_void_p * len(renderers))(*[r.ctx for r in renderers])
+    rc = renderers[0].L.smk_step_halo_exchange_local(arr, len(renderers), int(step), stream)
+    if rc != 0:
+        msgs = [r.L.smk_last_error(r.ctx).decode() for r in renderers]
+        raise SmkError(next((m for m in msgs if m), "smk_step_halo_exchange_local failed"))
 
 
 def exchange_unique_id():

@@ -169,7 +169,7 @@ extern "C" void smk_destroy(smk_ctx *c) {
   free_brick_set(c->br3);
   smk_cols_free(&c->cols);
   smk_present_free(c);  // (the slots' device and pinned buffers, the copy stream)
-  void *ptrs[] = {c->d_light_hist, c->d_shadow_entries, c->d_shadow_exports, c->d_shadow_barrier, c->d_tf_raw, c->d_tlut, c->d_tf_h, c->d_tf3d, c->d_tf3d_occ, c->d_noise, c->d_out, c->d_depth, c->d_zscene, c->d_light[0], c->d_light[1]};
+  void *ptrs[] = {c->d_light_hist, c->d_shadow_entries, c->d_shadow_exports, c->d_halo_stage[0], c->d_halo_stage[1], c->d_shadow_barrier, c->d_tf_raw, c->d_tlut, c->d_tf_h, c->d_tf3d, c->d_tf3d_occ, c->d_noise, c->d_out, c->d_depth, c->d_zscene, c->d_light[0], c->d_light[1]};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   smk_slab_free(&c->slab);
@@ -227,6 +227,34 @@ static void shard_box(const int N[3], int rank, int nranks, int g0[3], int g1[3]
 
 void smk_shard_region(const smk_ctx *c, int rank, int g0[3], int g1[3]) { shard_box(c->N, rank, c->nranks, g0, g1); }
 
+// the region of shard `rank` and the box it stores: the region plus `halo` voxels, cut at the volume; true when the box has a
+// pad column or row.
+// 8-byte voxels travel to LDS in 16-byte units: the slice-ring kernel wants even row lengths
+// along both axes that can be its contiguous one (x, and y in the x-major copy) -- one more halo
+// voxel where the volume has one, else a pad column nobody samples (index N: the texel pair of a
+// clamped coordinate ends at N-1)
+static bool stored_box(const int N[3], int dtype, int halo, int rank, int nranks, int g0[3], int g1[3], int O[3], int D[3]) {
+  bool padded = false;
+  shard_box(N, rank, nranks, g0, g1);
+  for (int a = 0; a < 3; ++a) {
+    int lo = std::max(g0[a] - halo, 0), hi = std::min(g1[a] + halo, N[a]);
+    O[a] = lo;
+    D[a] = hi - lo;
+  }
+  if (dtype != SMK_F32)
+    for (int a = 0; a < 2; ++a)
+      if (D[a] & 1) {
+        if (O[a] + D[a] < N[a]) ++D[a];
+        else if (O[a] > 0) { --O[a]; ++D[a]; }
+        else { ++D[a]; padded = true; }
+      }
+  return padded;
+}
+
+void smk_shard_stored_box(const smk_ctx *c, int rank, int g0[3], int g1[3], int O[3], int D[3]) {
+  (void)stored_box(c->N, c->dtype, c->halo, rank, c->nranks, g0, g1, O, D);
+}
+
 // whole-volume dims and extent from the brick list (MetaVolume::brick keeps iPos/fPos), and the box this context stores
 int smk_volume_geometry(smk_ctx *c, const char *who, const smk_volume_desc *b, int nb, int nelts, smk_dtype dtype,
                         smk_datamode dmode, SmkVolGeom &g) {
@@ -264,23 +292,7 @@ int smk_volume_geometry(smk_ctx *c, const char *who, const smk_volume_desc *b, i
     for (int a = 0; a < 3; ++a)
       if (N[a] < 2) FAIL(c, "%s: volume too thin to shard", who);
   g.grad = any_grad;
-  shard_box(N, c->rank, c->nranks, g.g0, g.g1);
-  for (int a = 0; a < 3; ++a) {
-    int lo = std::max(g.g0[a] - c->halo, 0), hi = std::min(g.g1[a] + c->halo, N[a]);
-    g.O[a] = lo;
-    g.D[a] = hi - lo;
-  }
-  // 8-byte voxels travel to LDS in 16-byte units: the slice-ring kernel wants even row lengths
-  // along both axes that can be its contiguous one (x, and y in the x-major copy) -- one more halo
-  // voxel where the volume has one, else a pad column nobody samples (index N: the texel pair of a
-  // clamped coordinate ends at N-1)
-  if (dtype != SMK_F32)
-    for (int a = 0; a < 2; ++a)
-      if (g.D[a] & 1) {
-        if (g.O[a] + g.D[a] < N[a]) ++g.D[a];
-        else if (g.O[a] > 0) { --g.O[a]; ++g.D[a]; }
-        else { ++g.D[a]; g.padded = true; }
-      }
+  g.padded = stored_box(N, dtype, c->halo, c->rank, c->nranks, g.g0, g.g1, g.O, g.D);
   const size_t nst = (size_t)g.D[0] * g.D[1] * g.D[2];
   g.vox_bytes = nst * (dtype == SMK_F32 ? 16 : 8);
   g.nrm_bytes = dtype == SMK_F32 && nelts == 4 && any_grad ? nst * 4 : 0;

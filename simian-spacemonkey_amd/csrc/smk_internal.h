@@ -416,6 +416,9 @@ struct smk_ctx {
   smk_shadowcoef shadow_entries_sc;         // the slice set they were made for
   float4 *d_shadow_exports = nullptr;       // phase 1's output of smk_shadow_exchange_local
   size_t shadow_exports_cap = 0;            // texels
+  // halo refill between devices (smk_step_halo_exchange_local): this rank's exports [0] and entries [1], staged
+  void *d_halo_stage[2] = {nullptr, nullptr};
+  size_t halo_stage_cap[2] = {0, 0};        // bytes
 
   // perturbation
   uint32_t *d_noise = nullptr;
@@ -537,6 +540,9 @@ int smk_build_params(smk_ctx *c, RenderParams &P, hipStream_t s);  // a frame's 
 int smk_shade_kind(const smk_ctx *c);  // 0 none, 1 R8k, 2 NV20
 void smk_region_box(const smk_ctx *c, const int g0[3], const int g1[3], float lo[3], float hi[3], int top[3]);
 void smk_shard_region(const smk_ctx *c, int rank, int g0[3], int g1[3]);
+// the region of shard `rank` of this context's series and the box of D voxels from O that rank stores, pad included
+// (smk_volume_geometry's rule, from the series' dims and dtype and this context's option "halo")
+void smk_shard_stored_box(const smk_ctx *c, int rank, int g0[3], int g1[3], int O[3], int D[3]);
 void smk_bsp_order(const smk_ctx *c, const double pos[3], int *order);
 void smk_inverse_affine(double inv[16], const double m[16]);
 int smk_make_xmajor_copy(smk_ctx *c);
@@ -596,6 +602,12 @@ int smk_step_read_begin(smk_ctx *c, int k, hipStream_t s);
 int smk_step_read(smk_ctx *c, int ka, int kb, hipStream_t s, const std::function<int()> &launches);
 using StepLaunches = std::function<int(TimeStep &out, const TimeStep *a, const TimeStep *b)>;
 int smk_step_produce(smk_ctx *c, const char *who, int id, int ka, int kb, hipStream_t s, const StepLaunches &launches);
+// _rewrite: `launches` enqueues kernels that WRITE voxels of the cached step in slot k in place (the halo refill,
+//   smk_step_halo.hip).  s is ordered behind the slot's frames, readers and writer, as for any writer, but the slot keeps its
+//   id and its place in the ring's order; then the brick summaries are made again for the stored voxels, the x-major copy is
+//   dropped, the slot's `ready` event is recorded on s -- also after a failed launch: every later reader waits for whatever
+//   was enqueued -- and a current step is switched to, as after an in-place upload.  `launches` sets what is valid of the step.
+int smk_step_rewrite(smk_ctx *c, int k, hipStream_t s, const std::function<int(TimeStep &)> &launches);
 // What the stencil producers (smk_step_derive.hip, smk_step_merge.hip) refuse before they look at their data, in this order:
 // no volume; a sharded context (sharded_why: the entry's reason); the series' nelts (nelts_why: the entry's refusal behind
 // "who: ", empty when they suit); a stored box that is not what the kernels take for granted; a volume without an interior

@@ -327,6 +327,31 @@ int smk_step_produce(smk_ctx *c, const char *who, int id, int ka, int kb, hipStr
   });
 }
 
+int smk_step_rewrite(smk_ctx *c, int k, hipStream_t s, const std::function<int(TimeStep &)> &launches) {
+  c->ts_series = true;
+  TimeStep &T = c->ts[(size_t)k];
+  const int id = T.id;
+  const int waited = wait_old_contents(c, T, s);
+  T.id = id;  // (the slot is not emptied: the step stays what it was, with more of it valid)
+  if (waited) return 1;
+  T.vox_x_valid = false;
+  int rc = launches(T);
+  if (!rc) {
+    const hipError_t e = smk_bricks_minmax(T.vox, c->dtype, c->D, c->nbr, T.mm, s);
+    if (e != hipSuccess) {
+      c->err = std::string("smk_bricks_minmax failed: ") + hipGetErrorString(e);
+      rc = 1;
+    }
+  }
+  const std::string why = c->err;
+  if (!T.ready) HIPCHK(c, hipEventCreateWithFlags(&T.ready, hipEventDisableTiming));
+  HIPCHK(c, hipEventRecord(T.ready, s));
+  T.ready_pending = true;
+  if (k == c->ts_cur) switch_step(c, k);
+  if (rc) c->err = why;
+  return rc;
+}
+
 int smk_step_stencil_refusals(smk_ctx *c, const StencilEntry &E, int step_out, const int *step_src, int *ksrc) {
   const char *who = E.who;
   if (!c->have_volume) FAIL(c, "%s: no volume uploaded", who);

@@ -422,3 +422,16 @@ def stencil_block_local(renderers, kind, blocks, out, compat=1, blur=0, stream=N
         else:
             R.upload_timestep_fields_block_device(out, ptrs, dtype, block, words[nranks].data_ptr(), stream=stream)
     return words
+
+
+def refill_halo_local(renderers, step, stream=None):
+    """The stored halo of cached step `step` (an id, or binding.STEP_CURRENT) on P shard contexts of this process, ranks in
+    order, copied bit for bit from the ranks that own those voxels (smk.h, "Halo refill"; smk_step_halo_exchange_local).  After
+    stencil_timestep_local or stencil_block_local a step's valid halo is the source's less the reach and the stored voxels
+    beyond it are a rim of zeros; after this call the step is the unsharded step's voxels on the whole stored box, with valid
+    halo = option "halo": frames with shadows or perturbation, the probe and later producers treat it as an uploaded step.
+    stream: a hipStream_t handle (an int or a ctypes.c_void_p) on which everything is enqueued, the host waiting for
+    nothing; None: every context's own stream, and the host waits for all of them.  A multi-process host does the same with
+    Renderer.step_halo_layout, step_halo_exports_device, one all-to-all-v of the segments, and step_halo_entries_device."""
+    from .binding import step_halo_exchange_local
+    step_halo_exchange_local(renderers, step, stream)
