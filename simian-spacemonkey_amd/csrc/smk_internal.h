@@ -608,7 +608,8 @@ int smk_step_produce(smk_ctx *c, const char *who, int id, int ka, int kb, hipStr
 //   dropped, the slot's `ready` event is recorded on s -- also after a failed launch: every later reader waits for whatever
 //   was enqueued -- and a current step is switched to, as after an in-place upload.  `launches` sets what is valid of the step.
 int smk_step_rewrite(smk_ctx *c, int k, hipStream_t s, const std::function<int(TimeStep &)> &launches);
-// What the stencil producers (smk_step_derive.hip, smk_step_merge.hip) refuse before they look at their data, in this order:
+// What the stencil producers (smk_step_derive.hip, smk_step_merge.hip, smk_step_merge_h.hip; what their host sides say alike:
+// smk_step_stencil.h) refuse before they look at their data, in this order:
 // no volume; a sharded context (sharded_why: the entry's reason); the series' nelts (nelts_why: the entry's refusal behind
 // "who: ", empty when they suit); a stored box that is not what the kernels take for granted; a volume without an interior
 // voxel (as prep_entry); then, with step_src (null: dense arrays), a source that is not cached (*ksrc: its slot), and the ids
@@ -632,7 +633,7 @@ void smk_step_shard_done(const smk_ctx *c, const TimeStep &src, int reach, const
 // smk_step_extremes_device's two kinds: pass 1 of the shard instances over the region, into the caller's eight words
 int smk_derive_extremes_enqueue(smk_ctx *c, const char *who, int step_src, int compat, void *d_words, hipStream_t s);  // (smk_step_derive.hip)
 int smk_merge_extremes_enqueue(smk_ctx *c, const char *who, int step_src, void *d_words, hipStream_t s);               // (smk_step_merge.hip)
-// The block entries (smk.h: smk_block; smk_step_block.hip, and the block instances of the two stencil producers): a rank's own
+// The block entries (smk.h: smk_block; smk_step_block.hip, and the block instances of the three stencil producers): a rank's own
 // dense block of the volume.  SmkBlockView: what the entries make of a block against this context's stored box -- C = block ∩
 // stored box ∩ volume in GLOBAL voxels, the source's valid halo, and the pitches with their zeros resolved.
 // smk_block_view: the refusals every block entry shares (a NULL block, sizes, pitches, a block outside the volume, a C that

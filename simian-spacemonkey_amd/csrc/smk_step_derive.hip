@@ -22,10 +22,8 @@
 #include <limits.h>
 
 #include <algorithm>
-#include <type_traits>
 
-#include "smk_internal.h"
-#include "smk_prep_device.h"
+#include "smk_step_stencil.h"
 
 namespace {
 
@@ -61,34 +59,8 @@ struct DeriveShardParams : DeriveParams {
 // The BLOCK instances (smk.h: smk_block_extremes_device, smk_upload_timestep_scalar_block_device): shard instances whose scalar
 // is a rank's own dense block of the volume, lying anywhere.  Tiles, the region, the valid box and every index into S, V and the
 // slot are the shard's; only the SOURCE differs: a voxel is held when it lies inside C = block ∩ stored box ∩ volume, and it is
-// read at (local - bo) through the block's pitches.  Again a parameter type of its own
-struct DeriveBlockParams : DeriveShardParams {
-  int bo[3];          // the block's element [0][0][0] in LOCAL voxels of the stored box (negative: the block starts before the box)
-  int c0[3], c1[3];   // C, local voxels: what of the block's extent this context takes
-  long long py, pz;   // elements between two rows, two slices of the block
-};
-template <class PT>
-constexpr bool dv_shard = std::is_base_of<DeriveShardParams, PT>::value;
-template <class PT>
-constexpr bool dv_block = std::is_same<PT, DeriveBlockParams>::value;
-
-// local voxel l of axis a as a voxel of the volume
-template <class PT>
-__device__ __forceinline__ int dv_glob(const PT &P, int a, int l) {
-  if constexpr (dv_shard<PT>) return P.B.O[a] + l;
-  else return l;
-}
-
-// local voxel (X, Y, Z) is a voxel of the volume that the stored box holds
-template <class PT>
-__device__ __forceinline__ bool dv_held(const PT &P, int X, int Y, int Z) {
-  if constexpr (dv_block<PT>)
-    return X >= P.c0[0] && X < P.c1[0] && Y >= P.c0[1] && Y < P.c1[1] && Z >= P.c0[2] && Z < P.c1[2];
-  else if constexpr (dv_shard<PT>)
-    return X >= 0 && X < P.D[0] && P.B.O[0] + X < P.N[0] && Y >= 0 && Y < P.D[1] && P.B.O[1] + Y < P.N[1] && Z >= 0 && Z < P.D[2] &&
-           P.B.O[2] + Z < P.N[2];
-  else return X >= 0 && X < P.N[0] && Y >= 0 && Y < P.N[1] && Z >= 0 && Z < P.N[2];
-}
+// read at (local - bo) through the block's pitches (StencilBlockSrc: bo, c0, c1, py, pz).  Again a parameter type of its own
+struct DeriveBlockParams : DeriveShardParams, StencilBlockSrc {};
 
 // the tile of the scalar around (x0, y0, z0), apron included; what lies outside the volume is not data: 0, and never used
 template <int SRC, class PT>
@@ -99,11 +71,11 @@ __device__ __forceinline__ void dv_load_tile(const PT &P, int x0, int y0, int z0
       const int cu = u % UPR, row = u / UPR, ly = row % DV_LY, lz = row / DV_LY;
       const int X = x0 - DV_AP + 2 * cu, Y = y0 - DV_AP + ly, Z = z0 - DV_AP + lz;
       float a = 0.f, b = 0.f;
-      if (dv_held(P, X, Y, Z)) {
+      if (stencil_held(P, X, Y, Z)) {
         const uint4 v = ((const uint4 *)P.src)[(((size_t)Z * P.D[1] + Y) * P.D[0] + X) >> 1];
         constexpr int DT = SRC == SRC_PK_U8 ? SMK_U8 : SMK_U16;
         a = (float)smk_vox8_c0<DT>(v.x);
-        if (dv_glob(P, 0, X) + 1 < P.N[0]) b = (float)smk_vox8_c0<DT>(v.z);
+        if (stencil_glob(P, 0, X) + 1 < P.N[0]) b = (float)smk_vox8_c0<DT>(v.z);
       }
       S[row * DV_LX + 2 * cu] = a;
       S[row * DV_LX + 2 * cu + 1] = b;
@@ -113,12 +85,12 @@ __device__ __forceinline__ void dv_load_tile(const PT &P, int x0, int y0, int z0
       const int lx = t % DV_LX, row = t / DV_LX, ly = row % DV_LY, lz = row / DV_LY;
       const int X = x0 - DV_AP + lx, Y = y0 - DV_AP + ly, Z = z0 - DV_AP + lz;
       float a = 0.f;
-      if (dv_held(P, X, Y, Z)) {
+      if (stencil_held(P, X, Y, Z)) {
         if (SRC == SRC_PK_F32) {
           a = __uint_as_float(((const uint4 *)P.src)[((size_t)Z * P.D[1] + Y) * P.D[0] + X].x);
         } else {
           size_t o;
-          if constexpr (dv_block<PT>) o = (size_t)(Z - P.bo[2]) * (size_t)P.pz + (size_t)(Y - P.bo[1]) * (size_t)P.py + (size_t)(X - P.bo[0]);
+          if constexpr (stencil_block<PT>) o = (size_t)(Z - P.bo[2]) * (size_t)P.pz + (size_t)(Y - P.bo[1]) * (size_t)P.py + (size_t)(X - P.bo[0]);
           else o = ((size_t)Z * P.N[1] + Y) * P.N[0] + X;
           a = SRC == SMK_U8 ? (float)((const unsigned char *)P.src)[o] : SRC == SMK_U16 ? (float)((const unsigned short *)P.src)[o] : ((const float *)P.src)[o];
         }
@@ -194,18 +166,18 @@ __global__ __launch_bounds__(256) void smk_k_derive_stats(const PT P, int gx, in
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int bx = tile % gx, by = (tile / gx) % gy, bz = tile / (gx * gy);
     const int x0 = bx * DV_TX, y0 = by * DV_TY, z0 = bz * DV_TZ;
-    if constexpr (dv_shard<PT>) {  // a tile of halo voxels alone has nothing to add (the whole workgroup skips it)
+    if constexpr (stencil_shard<PT>) {  // a tile of halo voxels alone has nothing to add (the whole workgroup skips it)
       if (x0 >= P.B.r1[0] || x0 + DV_TX <= P.B.r0[0] || y0 >= P.B.r1[1] || y0 + DV_TY <= P.B.r0[1] || z0 >= P.B.r1[2] || z0 + DV_TZ <= P.B.r0[2])
         continue;
     }
     dv_load_tile<SRC>(P, x0, y0, z0, S);
     __syncthreads();
-    const int X = x0 + tx, Y = y0 + ty, GX = dv_glob(P, 0, X), GY = dv_glob(P, 1, Y);
+    const int X = x0 + tx, Y = y0 + ty, GX = stencil_glob(P, 0, X), GY = stencil_glob(P, 1, Y);
     bool mine = true;
-    if constexpr (dv_shard<PT>) mine = X >= P.B.r0[0] && X < P.B.r1[0] && Y >= P.B.r0[1] && Y < P.B.r1[1];  // the region's voxels alone
+    if constexpr (stencil_shard<PT>) mine = X >= P.B.r0[0] && X < P.B.r1[0] && Y >= P.B.r0[1] && Y < P.B.r1[1];  // the region's voxels alone
     for (int tz = 0; tz < DV_TZ; ++tz) {
-      const int Z = z0 + tz, GZ = dv_glob(P, 2, Z);
-      if constexpr (dv_shard<PT>) {
+      const int Z = z0 + tz, GZ = stencil_glob(P, 2, Z);
+      if constexpr (stencil_shard<PT>) {
         if (!mine || Z < P.B.r0[2] || Z >= P.B.r1[2]) continue;
       }
       if (is_border(P.N[0], P.N[1], P.N[2], GZ, GY, GX)) continue;  // (and everything outside the volume)
@@ -216,7 +188,7 @@ __global__ __launch_bounds__(256) void smk_k_derive_stats(const PT P, int gx, in
     }
     __syncthreads();  // (the next tile overwrites S)
   }
-  if constexpr (dv_shard<PT>) dv_publish_words(run, P.words_out);
+  if constexpr (stencil_shard<PT>) dv_publish_words(run, P.words_out);
   else run.publish(P.st);
 }
 
@@ -231,7 +203,7 @@ __global__ __launch_bounds__(256) void smk_k_derive_write(const PT P) {
   const int x0 = blockIdx.x * DV_TX, y0 = blockIdx.y * DV_TY, z0 = blockIdx.z * DV_TZ;
   dv_load_tile<SRC>(P, x0, y0, z0, S);
   VghStats st;  // (a shard's come combined from the caller's words, the minima complemented)
-  if constexpr (dv_shard<PT>) st = {~P.words_in[0], P.words_in[1], ~P.words_in[2], P.words_in[3], ~P.words_in[4], P.words_in[5]};
+  if constexpr (stencil_shard<PT>) st = {~P.words_in[0], P.words_in[1], ~P.words_in[2], P.words_in[3], ~P.words_in[4], P.words_in[5]};
   else st = *P.st;
   // the reference seeds its running min/max with +-1e8 (genVGH/main.cpp:69-72, 104-105)
   const float dmin = dv_std_min(o2f(st.dmin), 100000000.f), dmax = dv_std_max(o2f(st.dmax), -100000000.f);
@@ -245,7 +217,7 @@ __global__ __launch_bounds__(256) void smk_k_derive_write(const PT P) {
     float v = 0.f;
     // (plain normals read V one voxel around the tile's own voxels, blurred ones two: the outer ring is not read then)
     const bool read = P.blur || (lx >= 1 && lx < DV_LX - 1 && ly >= 1 && ly < DV_LY - 1 && lz >= 1 && lz < DV_LZ - 1);
-    if (read && !is_border(P.N[0], P.N[1], P.N[2], dv_glob(P, 2, Z), dv_glob(P, 1, Y), dv_glob(P, 0, X))) {
+    if (read && !is_border(P.N[0], P.N[1], P.N[2], stencil_glob(P, 2, Z), stencil_glob(P, 1, Y), stencil_glob(P, 0, X))) {
       const double vq = affine_d(dmin, S[t], dmax, 0, 255);  // (vgh_scale's V)
       v = OUT == SMK_U8 ? (float)uc_cast(vq) : (float)(vq / 255.0);
     }
@@ -254,16 +226,16 @@ __global__ __launch_bounds__(256) void smk_k_derive_write(const PT P) {
   __syncthreads();
   const int tx = threadIdx.x % DV_TX, ty = threadIdx.x / DV_TX, X = x0 + tx, Y = y0 + ty;
   if (X >= P.D[0] || Y >= P.D[1]) return;
-  const int GX = dv_glob(P, 0, X), GY = dv_glob(P, 1, Y);
+  const int GX = stencil_glob(P, 0, X), GY = stencil_glob(P, 1, Y);
   for (int tz = 0; tz < DV_TZ; ++tz) {
-    const int Z = z0 + tz, GZ = dv_glob(P, 2, Z);
+    const int Z = z0 + tz, GZ = stencil_glob(P, 2, Z);
     if (Z >= P.D[2]) break;
     const size_t o = ((size_t)Z * P.D[1] + Y) * P.D[0] + X;
     if (GX >= P.N[0] || GY >= P.N[1]) {  // the pad column or row of an 8-byte box: zeros, as after an upload
       ((uint2 *)P.out)[o] = make_uint2(0u, 0u);
       continue;
     }
-    if constexpr (dv_shard<PT>) {  // the rim: zeros that carry no normal
+    if constexpr (stencil_shard<PT>) {  // the rim: zeros that carry no normal
       if (X < P.B.v0[0] || X >= P.B.v1[0] || Y < P.B.v0[1] || Y >= P.B.v1[1] || Z < P.B.v0[2] || Z >= P.B.v1[2]) {
         if (OUT == SMK_F32) ((uint4 *)P.out)[o] = make_uint4(0u, 0u, 0u, SMK_NRM_NONE);
         else ((uint2 *)P.out)[o] = make_uint2(0u, SMK_NRM_NONE);
@@ -302,18 +274,34 @@ __global__ __launch_bounds__(256) void smk_k_derive_write(const PT P) {
   }
 }
 
-template <int SRC>
-hipError_t launch_derive(const DeriveParams &P, int out_dtype, hipStream_t s) {
+// The seed and pass 1 (PASS_1: into the slot's extremes, a shard's and a block's into the caller's words), pass 2, or both
+template <int SRC, int OUT, class PT>
+hipError_t launch_derive(const PT &P, int passes, hipStream_t s) {
   const dim3 grid((unsigned)((P.D[0] + DV_TX - 1) / DV_TX), (unsigned)((P.D[1] + DV_TY - 1) / DV_TY), (unsigned)((P.D[2] + DV_TZ - 1) / DV_TZ));
-  hipLaunchKernelGGL(smk_k_derive_seed, dim3(1), dim3(64), 0, s, P.st);
-  const long long ntiles = (long long)grid.x * grid.y * grid.z;
-  if (ntiles > 0x7fffffffLL) return hipErrorInvalidValue;  // (2^31 tiles are 2^42 voxels)
-  hipLaunchKernelGGL(smk_k_derive_stats<SRC>, dim3((unsigned)std::min<long long>(ntiles, DV_STATS_BLOCKS)), dim3(256), 0, s, P, (int)grid.x, (int)grid.y,
-                     (int)ntiles);
-  if (out_dtype == SMK_U8) hipLaunchKernelGGL((smk_k_derive_write<SRC, SMK_U8>), grid, dim3(256), 0, s, P);
-  else if (out_dtype == SMK_U16) hipLaunchKernelGGL((smk_k_derive_write<SRC, SMK_U16>), grid, dim3(256), 0, s, P);
-  else hipLaunchKernelGGL((smk_k_derive_write<SRC, SMK_F32>), grid, dim3(256), 0, s, P);
+  if (passes & PASS_1) {
+    const long long ntiles = (long long)grid.x * grid.y * grid.z;
+    if (ntiles > 0x7fffffffLL) return hipErrorInvalidValue;  // (2^31 tiles are 2^42 voxels)
+    if constexpr (stencil_shard<PT>) hipLaunchKernelGGL(smk_k_derive_seed_words, dim3(1), dim3(64), 0, s, P.words_out);
+    else hipLaunchKernelGGL(smk_k_derive_seed, dim3(1), dim3(64), 0, s, P.st);
+    hipLaunchKernelGGL((smk_k_derive_stats<SRC, PT>), dim3((unsigned)std::min<long long>(ntiles, DV_STATS_BLOCKS)), dim3(256), 0, s, P, (int)grid.x,
+                       (int)grid.y, (int)ntiles);
+  }
+  if (passes & PASS_2) hipLaunchKernelGGL((smk_k_derive_write<SRC, OUT, PT>), grid, dim3(256), 0, s, P);
   return hipGetLastError();
+}
+
+// ... of the instance that reads a source of type dt -- a packed step of the ring (PACKED) or a dense scalar -- and writes the
+// ring's voxels.  A shard's source IS a step of the ring: its kernels have the instances of equal types alone
+template <bool PACKED, class PT>
+hipError_t launch_derive_src(const smk_ctx *c, const PT &P, int dt, int passes, hipStream_t s) {
+  return stencil_dispatch_src<PACKED>(dt, [&](auto src) -> hipError_t {
+    constexpr int SRC = decltype(src)::value;
+    if constexpr (PACKED && stencil_shard<PT>) {
+      return launch_derive<SRC, stencil_ring(SRC)>(P, passes, s);
+    } else {
+      return stencil_dispatch_src<false>(c->dtype, [&](auto out) { return launch_derive<SRC, decltype(out)::value>(P, passes, s); });
+    }
+  });
 }
 
 // what both entries refuse before they look at their data (smk_step_stencil_refusals)
@@ -324,30 +312,28 @@ StencilEntry derive_entry(const smk_ctx *c, const char *who) {
           nelts_why, "smk_make_vgh_device"};
 }
 
-// the two passes inside the producer frame; ksrc: the source slot, or -1 (a dense scalar)
-int derive_enqueue(smk_ctx *c, const char *who, int kind, const void *src, int ksrc, int step_out, int compat, int blur, hipStream_t s) {
+// what every instance takes of the context: the volume, the stored box, the flags; no output yet
+void derive_common(const smk_ctx *c, const void *src, int compat, int blur, DeriveParams &P) {
+  P.src = src;
+  P.out = nullptr;
+  P.st = nullptr;
+  for (int a = 0; a < 3; ++a) {
+    P.N[a] = c->N[a];
+    P.D[a] = c->D[a];
+  }
+  P.compat = compat ? 1 : 0;
+  P.blur = blur ? 1 : 0;
+  P.normals = c->have_normals ? 1 : 0;
+}
+
+// the two passes inside the producer frame; ksrc: the source slot, or -1 (the dense scalar src of type dt)
+int derive_enqueue(smk_ctx *c, const char *who, const void *src, int dt, int ksrc, int step_out, int compat, int blur, hipStream_t s) {
   return smk_step_produce(c, who, step_out, ksrc, -1, s, [&](TimeStep &T, const TimeStep *S, const TimeStep *) -> int {
     DeriveParams P;
-    P.src = S ? S->vox : src;
+    derive_common(c, S ? S->vox : src, compat, blur, P);
     P.out = T.vox;
     P.st = (VghStats *)T.pass1_words;
-    for (int a = 0; a < 3; ++a) {
-      P.N[a] = c->N[a];
-      P.D[a] = c->D[a];
-    }
-    P.compat = compat ? 1 : 0;
-    P.blur = blur ? 1 : 0;
-    P.normals = c->have_normals ? 1 : 0;
-    hipError_t e;
-    switch (kind) {
-      case SMK_U8: e = launch_derive<SMK_U8>(P, c->dtype, s); break;
-      case SMK_F32: e = launch_derive<SMK_F32>(P, c->dtype, s); break;
-      case SMK_U16: e = launch_derive<SMK_U16>(P, c->dtype, s); break;
-      case SRC_PK_U8: e = launch_derive<SRC_PK_U8>(P, c->dtype, s); break;
-      case SRC_PK_U16: e = launch_derive<SRC_PK_U16>(P, c->dtype, s); break;
-      default: e = launch_derive<SRC_PK_F32>(P, c->dtype, s); break;
-    }
-    HIPCHK(c, e);
+    HIPCHK(c, S ? launch_derive_src<true>(c, P, c->dtype, PASS_1 | PASS_2, s) : launch_derive_src<false>(c, P, dt, PASS_1 | PASS_2, s));
     return 0;
   });
 }
@@ -364,41 +350,11 @@ StencilEntry derive_shard_entry(const smk_ctx *c, const char *who) {
 
 DeriveShardParams derive_shard_params(const smk_ctx *c, const TimeStep &S, int compat, int blur) {
   DeriveShardParams P;
-  P.src = S.vox;
-  P.out = nullptr;
-  P.st = nullptr;
-  for (int a = 0; a < 3; ++a) {
-    P.N[a] = c->N[a];
-    P.D[a] = c->D[a];
-  }
-  P.compat = compat ? 1 : 0;
-  P.blur = blur ? 1 : 0;
-  P.normals = c->have_normals ? 1 : 0;
+  derive_common(c, S.vox, compat, blur, P);
   smk_step_shard_box(c, S, DV_REACH, P.B);
   P.words_out = nullptr;
   P.words_in = nullptr;
   return P;
-}
-
-dim3 derive_grid(const DeriveParams &P) {
-  return dim3((unsigned)((P.D[0] + DV_TX - 1) / DV_TX), (unsigned)((P.D[1] + DV_TY - 1) / DV_TY), (unsigned)((P.D[2] + DV_TZ - 1) / DV_TZ));
-}
-
-template <int SRC, class PT>
-hipError_t launch_derive_export(const PT &P, hipStream_t s) {
-  const dim3 grid = derive_grid(P);
-  const long long ntiles = (long long)grid.x * grid.y * grid.z;
-  if (ntiles > 0x7fffffffLL) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(smk_k_derive_seed_words, dim3(1), dim3(64), 0, s, P.words_out);
-  hipLaunchKernelGGL((smk_k_derive_stats<SRC, PT>), dim3((unsigned)std::min<long long>(ntiles, DV_STATS_BLOCKS)), dim3(256), 0, s, P,
-                     (int)grid.x, (int)grid.y, (int)ntiles);
-  return hipGetLastError();
-}
-
-template <int SRC, int OUT, class PT>
-hipError_t launch_derive_write_shard(const PT &P, hipStream_t s) {
-  hipLaunchKernelGGL((smk_k_derive_write<SRC, OUT, PT>), derive_grid(P), dim3(256), 0, s, P);
-  return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------------- the block entries
@@ -406,41 +362,12 @@ hipError_t launch_derive_write_shard(const PT &P, hipStream_t s) {
 // the shard's parameters with the block as the source.  B: the region, and C shrunk by the reach as the result's valid box
 DeriveBlockParams derive_block_params(const smk_ctx *c, const void *src, const smk_block *b, const SmkBlockView &V, int compat, int blur) {
   DeriveBlockParams P;
-  P.src = src;
-  P.out = nullptr;
-  P.st = nullptr;
-  for (int a = 0; a < 3; ++a) {
-    P.N[a] = c->N[a];
-    P.D[a] = c->D[a];
-    P.bo[a] = b->origin[a] - c->O[a];
-    P.c0[a] = V.c0[a] - c->O[a];
-    P.c1[a] = V.c1[a] - c->O[a];
-  }
-  P.py = V.py;
-  P.pz = V.pz;
-  P.compat = compat ? 1 : 0;
-  P.blur = blur ? 1 : 0;
-  P.normals = c->have_normals ? 1 : 0;
+  derive_common(c, src, compat, blur, P);
+  stencil_block_src(c, b, V, P);
   smk_step_block_box(c, V, DV_REACH, P.B);
   P.words_out = nullptr;
   P.words_in = nullptr;
   return P;
-}
-
-template <int SRC>
-hipError_t launch_derive_write_block(const DeriveBlockParams &P, int out_dtype, hipStream_t s) {
-  if (out_dtype == SMK_U8) return launch_derive_write_shard<SRC, SMK_U8>(P, s);
-  if (out_dtype == SMK_U16) return launch_derive_write_shard<SRC, SMK_U16>(P, s);
-  return launch_derive_write_shard<SRC, SMK_F32>(P, s);
-}
-
-// what both block entries refuse of the scalar
-int derive_block_scalar_refusals(smk_ctx *c, const char *who, const void *d_scalar, smk_dtype dt) {
-  if (!d_scalar) FAIL(c, "%s: d_scalar is NULL", who);
-  if (dt != SMK_U8 && dt != SMK_U16 && dt != SMK_F32) FAIL(c, "%s: scalar_dtype %d is none of SMK_U8, SMK_U16, SMK_F32", who, (int)dt);
-  const size_t eb = smk_elem_bytes(dt);
-  if ((uintptr_t)d_scalar % eb) FAIL(c, "%s: d_scalar is not aligned to its %zu-byte elements", who, eb);
-  return 0;
 }
 
 }  // namespace
@@ -451,8 +378,7 @@ int smk_derive_extremes_enqueue(smk_ctx *c, const char *who, int step_src, int c
   return smk_step_read(c, ksrc, -1, s, [&]() -> int {
     DeriveShardParams P = derive_shard_params(c, c->ts[(size_t)ksrc], compat, 0);
     P.words_out = (int *)d_words;
-    HIPCHK(c, c->dtype == SMK_U8    ? launch_derive_export<SRC_PK_U8>(P, s)
-              : c->dtype == SMK_U16 ? launch_derive_export<SRC_PK_U16>(P, s) : launch_derive_export<SRC_PK_F32>(P, s));
+    HIPCHK(c, launch_derive_src<true>(c, P, c->dtype, PASS_1, s));
     return 0;
   });
 }
@@ -461,11 +387,7 @@ extern "C" int smk_step_extremes_device(smk_ctx *c, int kind, int step_src, int 
   if (!c) return 1;
   const char *who = "smk_step_extremes_device";
   HIPCHK(c, hipSetDevice(c->device));
-  if (kind != SMK_EXTREMES_DERIVE && kind != SMK_EXTREMES_MERGE)
-    FAIL(c, "%s: kind %d is neither SMK_EXTREMES_DERIVE (%d) nor SMK_EXTREMES_MERGE (%d)", who, kind, (int)SMK_EXTREMES_DERIVE,
-         (int)SMK_EXTREMES_MERGE);
-  if (!d_words) FAIL(c, "%s: d_words is NULL", who);
-  if ((uintptr_t)d_words % sizeof(int)) FAIL(c, "%s: d_words is not aligned to its 4-byte words", who);
+  if (stencil_kind_refusals(c, who, kind) || stencil_words_refusals(c, who, d_words)) return 1;
   const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   return kind == SMK_EXTREMES_DERIVE ? smk_derive_extremes_enqueue(c, who, step_src, compat, d_words, s)
                                      : smk_merge_extremes_enqueue(c, who, step_src, d_words, s);
@@ -476,22 +398,17 @@ extern "C" int smk_block_extremes_device(smk_ctx *c, int kind, const void *const
   if (!c) return 1;
   const char *who = "smk_block_extremes_device";
   HIPCHK(c, hipSetDevice(c->device));
-  if (kind != SMK_EXTREMES_DERIVE && kind != SMK_EXTREMES_MERGE)
-    FAIL(c, "%s: kind %d is neither SMK_EXTREMES_DERIVE (%d) nor SMK_EXTREMES_MERGE (%d)", who, kind, (int)SMK_EXTREMES_DERIVE,
-         (int)SMK_EXTREMES_MERGE);
-  if (!d_words) FAIL(c, "%s: d_words is NULL", who);
-  if ((uintptr_t)d_words % sizeof(int)) FAIL(c, "%s: d_words is not aligned to its 4-byte words", who);
+  if (stencil_kind_refusals(c, who, kind) || stencil_words_refusals(c, who, d_words)) return 1;
   const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   if (kind == SMK_EXTREMES_MERGE) return smk_merge_block_extremes_enqueue(c, who, d_fields, nf, dtype, b, d_words, s);
   SmkBlockView V;
   if (smk_step_block_refusals(c, derive_shard_entry(c, who), DV_REACH, nullptr, b, V)) return 1;
   if (!d_fields) FAIL(c, "%s: d_fields is NULL", who);
   if (nf != 1) FAIL(c, "%s: %d fields: the derive takes one scalar (nf 1)", who, nf);
-  if (derive_block_scalar_refusals(c, who, d_fields[0], dtype)) return 1;
+  if (stencil_scalar_refusals(c, who, d_fields[0], dtype, -1, nullptr)) return 1;
   DeriveBlockParams P = derive_block_params(c, d_fields[0], b, V, compat, 0);
   P.words_out = (int *)d_words;
-  HIPCHK(c, dtype == SMK_U8 ? launch_derive_export<SMK_U8>(P, s) : dtype == SMK_U16 ? launch_derive_export<SMK_U16>(P, s)
-                                                                                     : launch_derive_export<SMK_F32>(P, s));
+  HIPCHK(c, launch_derive_src<false>(c, P, dtype, PASS_1, s));
   return 0;
 }
 
@@ -502,16 +419,13 @@ extern "C" int smk_upload_timestep_scalar_block_device(smk_ctx *c, int timestep,
   HIPCHK(c, hipSetDevice(c->device));
   SmkBlockView V;
   if (smk_step_block_refusals(c, derive_shard_entry(c, who), DV_REACH, &timestep, b, V)) return 1;
-  if (derive_block_scalar_refusals(c, who, d_scalar, scalar_dtype)) return 1;
-  if (!d_words) FAIL(c, "%s: d_words is NULL", who);
-  if ((uintptr_t)d_words % sizeof(int)) FAIL(c, "%s: d_words is not aligned to its 4-byte words", who);
+  if (stencil_scalar_refusals(c, who, d_scalar, scalar_dtype, timestep, nullptr) || stencil_words_refusals(c, who, d_words)) return 1;
   const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   return smk_step_produce(c, who, timestep, -1, -1, s, [&](TimeStep &T, const TimeStep *, const TimeStep *) -> int {
     DeriveBlockParams P = derive_block_params(c, d_scalar, b, V, compat, blur);
     P.out = T.vox;
     P.words_in = (const int *)d_words;
-    HIPCHK(c, scalar_dtype == SMK_U8    ? launch_derive_write_block<SMK_U8>(P, c->dtype, s)
-              : scalar_dtype == SMK_U16 ? launch_derive_write_block<SMK_U16>(P, c->dtype, s) : launch_derive_write_block<SMK_F32>(P, c->dtype, s));
+    HIPCHK(c, launch_derive_src<false>(c, P, scalar_dtype, PASS_2, s));
     smk_step_block_done(c, V, DV_REACH, P.B, T);
     return 0;
   });
@@ -523,18 +437,13 @@ extern "C" int smk_derive_timestep_shard(smk_ctx *c, int step_src, int step_out,
   HIPCHK(c, hipSetDevice(c->device));
   int ksrc = -1;
   if (smk_step_shard_refusals(c, derive_shard_entry(c, who), DV_REACH, step_src, &step_out, &ksrc)) return 1;
-  if (!d_words) FAIL(c, "%s: d_words is NULL", who);
-  if ((uintptr_t)d_words % sizeof(int)) FAIL(c, "%s: d_words is not aligned to its 4-byte words", who);
+  if (stencil_words_refusals(c, who, d_words)) return 1;
   const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   return smk_step_produce(c, who, step_out, ksrc, -1, s, [&](TimeStep &T, const TimeStep *S, const TimeStep *) -> int {
     DeriveShardParams P = derive_shard_params(c, *S, compat, blur);
     P.out = T.vox;
     P.words_in = (const int *)d_words;
-    hipError_t e;
-    if (c->dtype == SMK_U8) e = launch_derive_write_shard<SRC_PK_U8, SMK_U8>(P, s);
-    else if (c->dtype == SMK_U16) e = launch_derive_write_shard<SRC_PK_U16, SMK_U16>(P, s);
-    else e = launch_derive_write_shard<SRC_PK_F32, SMK_F32>(P, s);
-    HIPCHK(c, e);
+    HIPCHK(c, launch_derive_src<true>(c, P, c->dtype, PASS_2, s));
     smk_step_shard_done(c, *S, DV_REACH, P.B, T);
     return 0;
   });
@@ -546,8 +455,7 @@ extern "C" int smk_derive_timestep(smk_ctx *c, int step_src, int step_out, int c
   HIPCHK(c, hipSetDevice(c->device));
   int ksrc = -1;
   if (smk_step_stencil_refusals(c, derive_entry(c, who), step_out, &step_src, &ksrc)) return 1;
-  const int kind = c->dtype == SMK_U8 ? SRC_PK_U8 : c->dtype == SMK_U16 ? SRC_PK_U16 : SRC_PK_F32;
-  return derive_enqueue(c, who, kind, nullptr, ksrc, step_out, compat, blur, stream ? (hipStream_t)stream : c->stream);
+  return derive_enqueue(c, who, nullptr, c->dtype, ksrc, step_out, compat, blur, stream ? (hipStream_t)stream : c->stream);
 }
 
 extern "C" int smk_upload_timestep_scalar_device(smk_ctx *c, int timestep, const void *d_scalar, smk_dtype scalar_dtype, int sx, int sy,
@@ -556,12 +464,7 @@ extern "C" int smk_upload_timestep_scalar_device(smk_ctx *c, int timestep, const
   const char *who = "smk_upload_timestep_scalar_device";
   HIPCHK(c, hipSetDevice(c->device));
   if (smk_step_stencil_refusals(c, derive_entry(c, who), timestep, nullptr, nullptr)) return 1;
-  if (!d_scalar) FAIL(c, "%s: d_scalar is NULL", who);
-  if (scalar_dtype != SMK_U8 && scalar_dtype != SMK_U16 && scalar_dtype != SMK_F32)
-    FAIL(c, "%s: scalar_dtype %d is none of SMK_U8, SMK_U16, SMK_F32", who, (int)scalar_dtype);
-  if (sx != c->N[0] || sy != c->N[1] || sz != c->N[2])
-    FAIL(c, "%s: time step %d: sizes %dx%dx%d differ from the series' %dx%dx%d", who, timestep, sx, sy, sz, c->N[0], c->N[1], c->N[2]);
-  const size_t eb = smk_elem_bytes(scalar_dtype);
-  if ((uintptr_t)d_scalar % eb) FAIL(c, "%s: d_scalar is not aligned to its %zu-byte elements", who, eb);
-  return derive_enqueue(c, who, (int)scalar_dtype, d_scalar, -1, timestep, compat, blur, stream ? (hipStream_t)stream : c->stream);
+  const int sizes[3] = {sx, sy, sz};
+  if (stencil_scalar_refusals(c, who, d_scalar, scalar_dtype, timestep, sizes)) return 1;
+  return derive_enqueue(c, who, d_scalar, (int)scalar_dtype, -1, timestep, compat, blur, stream ? (hipStream_t)stream : c->stream);
 }

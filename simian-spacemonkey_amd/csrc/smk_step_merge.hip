@@ -23,10 +23,8 @@
 #include <limits.h>
 
 #include <algorithm>
-#include <type_traits>
 
-#include "smk_internal.h"
-#include "smk_prep_device.h"
+#include "smk_step_stencil.h"
 
 namespace {
 
@@ -62,26 +60,11 @@ struct MergeShardParams : MergeParams {
 // The BLOCK instances (smk.h: smk_block_extremes_device, smk_upload_timestep_fields_block_device): shard instances whose fields
 // are a rank's own dense blocks of the volume, all laid out by one smk_block that lies anywhere.  Units, tiles, the region, the
 // valid box and every index into the slot are the shard's; only the SOURCE differs: a voxel is read when it lies inside
-// C = block ∩ stored box ∩ volume, at (local - bo) through the block's pitches.  Again a parameter type of its own
-struct MergeBlockParams : MergeShardParams {
-  int bo[3];          // the block's element [0][0][0] in LOCAL voxels of the stored box (negative: the block starts before the box)
-  int c0[3], c1[3];   // C, local voxels: what of the block's extent this context takes
-  long long py, pz;   // elements between two rows, two slices of the block
-};
-template <class PT>
-constexpr bool mg_shard = std::is_base_of<MergeShardParams, PT>::value;
-template <class PT>
-constexpr bool mg_block = std::is_same<PT, MergeBlockParams>::value;
+// C = block ∩ stored box ∩ volume, at (local - bo) through the block's pitches (StencilBlockSrc: bo, c0, c1, py, pz).  Again a
+// parameter type of its own
+struct MergeBlockParams : MergeShardParams, StencilBlockSrc {};
 
-// local voxel l of axis a as a voxel of the volume
-template <class PT>
-__device__ __forceinline__ int mg_glob(const PT &P, int a, int l) {
-  if constexpr (mg_shard<PT>) return P.B.O[a] + l;
-  else return l;
-}
-
-constexpr int mg_ring(int SRC) { return SRC == SRC_PK_U8 ? SMK_U8 : SRC == SRC_PK_U16 ? SMK_U16 : SRC == SRC_PK_F32 ? SMK_F32 : SRC; }
-constexpr int mg_vpu(int SRC) { return mg_ring(SRC) == SMK_F32 ? 1 : 2;  }  // voxels per 16-byte unit
+constexpr int mg_vpu(int SRC) { return stencil_ring(SRC) == SMK_F32 ? 1 : 2;  }  // voxels per 16-byte unit
 
 // The fields of the voxels of unit U of row Y of slice Z as they are stored -- a byte, a 16-bit value or a float's word each --:
 // r[c][e], voxel c of the unit, field e.  A unit outside the stored box (and a dense voxel outside the volume) is zeros and is
@@ -107,7 +90,7 @@ __device__ __forceinline__ void mg_cell(const PT &P, int U, int Y, int Z, uint32
       for (int e = 0; e < NF; ++e)
         r[c][e] = SRC == SRC_PK_U8 ? smk_u8_ch(w0, e) : e == 0 ? smk_vox8_c0<SMK_U16>(w0) : smk_vox8_c1<SMK_U16>(w0);
     }
-  } else if constexpr (mg_block<PT>) {  // dense fields of a block: the voxels inside C, through the pitches
+  } else if constexpr (stencil_block<PT>) {  // dense fields of a block: the voxels inside C, through the pitches
     if (Y < P.c0[1] || Y >= P.c1[1] || Z < P.c0[2] || Z >= P.c1[2]) return;
     const size_t row = (size_t)(Z - P.bo[2]) * (size_t)P.pz + (size_t)(Y - P.bo[1]) * (size_t)P.py;
 #pragma unroll
@@ -138,7 +121,7 @@ __device__ __forceinline__ void mg_cell(const PT &P, int U, int Y, int Z, uint32
 // ... as the float the gradient is taken of: (float)v of an integer, unscaled (differences and their sums are exact)
 template <int SRC>
 __device__ __forceinline__ float mg_val(uint32_t r) {
-  return mg_ring(SRC) == SMK_F32 ? __uint_as_float(r) : (float)r;
+  return stencil_ring(SRC) == SMK_F32 ? __uint_as_float(r) : (float)r;
 }
 
 // A lane's march through the MG_TZ slices of its tile at unit U of row Y: per slice visit(Z, g, r) with the summed gradients
@@ -178,7 +161,7 @@ __device__ __forceinline__ void mg_march(const PT &P, int U, int Y, int z0, Visi
 #pragma unroll
     for (int c = 0; c < VPU; ++c) {
       merge_grad_zero(g[c]);
-      if (is_border(P.N[0], P.N[1], P.N[2], mg_glob(P, 2, Z), mg_glob(P, 1, Y), mg_glob(P, 0, U * VPU + c))) continue;
+      if (is_border(P.N[0], P.N[1], P.N[2], stencil_glob(P, 2, Z), stencil_glob(P, 1, Y), stencil_glob(P, 0, U * VPU + c))) continue;
 #pragma unroll
       for (int e = 0; e < NF; ++e)
         merge_grad_add(g[c], mg_val<SRC>(c == VPU - 1 ? xr[e] : c0[(c + 1) % VPU][e]), mg_val<SRC>(c == 0 ? xl[e] : c0[(c + VPU - 1) % VPU][e]),
@@ -220,7 +203,7 @@ __global__ __launch_bounds__(256) void smk_k_merge_max(const PT P) {
   for (int tile = blockIdx.x; tile < P.ntiles; tile += gridDim.x) {
     int u0, y0, z0;
     mg_tile(P, tile, u0, y0, z0);
-    if constexpr (mg_shard<PT>) {  // a tile of halo voxels alone has nothing to add (the whole workgroup skips it)
+    if constexpr (stencil_shard<PT>) {  // a tile of halo voxels alone has nothing to add (the whole workgroup skips it)
       if (u0 * VPU >= P.B.r1[0] || (u0 + MG_UX) * VPU <= P.B.r0[0] || y0 >= P.B.r1[1] || y0 + MG_TY <= P.B.r0[1] || z0 >= P.B.r1[2] ||
           z0 + MG_TZ <= P.B.r0[2])
         continue;
@@ -230,17 +213,17 @@ __global__ __launch_bounds__(256) void smk_k_merge_max(const PT P) {
 #pragma unroll
       for (int c = 0; c < VPU; ++c) {
         const int X = U * VPU + c;
-        if constexpr (mg_shard<PT>) {  // the region's voxels alone
+        if constexpr (stencil_shard<PT>) {  // the region's voxels alone
           if (X < P.B.r0[0] || X >= P.B.r1[0] || Y < P.B.r0[1] || Y >= P.B.r1[1] || Z < P.B.r0[2] || Z >= P.B.r1[2]) continue;
         }
-        if (is_border(P.N[0], P.N[1], P.N[2], mg_glob(P, 2, Z), mg_glob(P, 1, Y), mg_glob(P, 0, X))) continue;  // (and everything outside the volume)
+        if (is_border(P.N[0], P.N[1], P.N[2], stencil_glob(P, 2, Z), stencil_glob(P, 1, Y), stencil_glob(P, 0, X))) continue;  // (and everything outside the volume)
         const float mag = merge_mag(g[c]);
-        m = mg_ring(SRC) == SMK_U8 ? merge_max_take(m, mag) : merge_max_take_f32(m, mag);
+        m = stencil_ring(SRC) == SMK_U8 ? merge_max_take(m, mag) : merge_max_take_f32(m, mag);
       }
     });
   }
   m = wave_max(m);
-  if constexpr (mg_shard<PT>) {
+  if constexpr (stencil_shard<PT>) {
     if ((threadIdx.x & 63) == 0) atomicMax(P.words_out, m);
   } else {
     if ((threadIdx.x & 63) == 0) atomicMax(P.mx, m);
@@ -252,13 +235,13 @@ __global__ __launch_bounds__(256) void smk_k_merge_max(const PT P) {
 template <int SRC, int NF, class PT>
 __device__ __forceinline__ void mg_voxel(const PT &P, int X, int Y, int Z, const float gin[3], const uint32_t r[NF], float maxm, uint32_t w[4],
                                          uint32_t &nw) {
-  constexpr int RING = mg_ring(SRC);
+  constexpr int RING = stencil_ring(SRC);
   nw = SMK_NRM_NONE;
-  if (mg_glob(P, 0, X) >= P.N[0] || mg_glob(P, 1, Y) >= P.N[1]) {  // the pad column or row of an 8-byte box: zeros, as after an upload
+  if (stencil_glob(P, 0, X) >= P.N[0] || stencil_glob(P, 1, Y) >= P.N[1]) {  // the pad column or row of an 8-byte box: zeros, as after an upload
     w[0] = w[1] = w[2] = w[3] = 0u;
     return;
   }
-  if constexpr (mg_shard<PT>) {  // the rim: zeros that carry no normal (a four-channel f32 voxel's goes to the separate buffer)
+  if constexpr (stencil_shard<PT>) {  // the rim: zeros that carry no normal (a four-channel f32 voxel's goes to the separate buffer)
     if (X < P.B.v0[0] || X >= P.B.v1[0] || Y < P.B.v0[1] || Y >= P.B.v1[1] || Z < P.B.v0[2] || Z >= P.B.v1[2]) {
       w[0] = w[1] = w[2] = w[3] = 0u;
       if (RING != SMK_F32) w[1] = SMK_NRM_NONE;
@@ -302,7 +285,7 @@ template <int SRC, int NF, class PT = MergeParams>
 __global__ __launch_bounds__(256) void smk_k_merge_write(const PT P) {
   constexpr int VPU = mg_vpu(SRC);
   float maxm;  // (a shard's comes combined from the caller's words)
-  if constexpr (mg_shard<PT>) maxm = o2f(P.words_in[0]);
+  if constexpr (stencil_shard<PT>) maxm = o2f(P.words_in[0]);
   else maxm = o2f(*P.mx);
   int u0, y0, z0;
   mg_tile(P, blockIdx.x, u0, y0, z0);
@@ -325,22 +308,20 @@ __global__ __launch_bounds__(256) void smk_k_merge_write(const PT P) {
   });
 }
 
-template <int SRC, int NF>
-hipError_t launch_merge(const MergeParams &P, hipStream_t s) {
-  hipLaunchKernelGGL(smk_k_merge_seed, dim3(1), dim3(64), 0, s, P.mx);
-  hipLaunchKernelGGL((smk_k_merge_max<SRC, NF>), dim3(std::min<unsigned>((unsigned)P.ntiles, MG_MAX_BLOCKS)), dim3(256), 0, s, P);
-  hipLaunchKernelGGL((smk_k_merge_write<SRC, NF>), dim3((unsigned)P.ntiles), dim3(256), 0, s, P);
-  return hipGetLastError();
-}
-
-template <int SRC>
-hipError_t launch_merge_nf(const MergeParams &P, int nf, hipStream_t s) {
-  if (nf == 1) return launch_merge<SRC, 1>(P, s);
-  if (nf == 2) return launch_merge<SRC, 2>(P, s);
-  if constexpr (mg_ring(SRC) != SMK_U16) {  // (a u16 voxel holds three channels: merge_entry)
-    if (nf == 3) return launch_merge<SRC, 3>(P, s);
-  }
-  return hipErrorInvalidValue;
+// The seed and pass 1 (PASS_1: into the slot's word, a shard's and a block's into the caller's words), pass 2, or both, of the
+// instance that reads the ring's type -- a packed step of the ring (PACKED) or dense fields -- with the series' fields
+template <bool PACKED, class PT>
+hipError_t launch_merge(const smk_ctx *c, const PT &P, int passes, hipStream_t s) {
+  return stencil_dispatch<PACKED>(c->dtype, c->nelts - 1, [&](auto src, auto nf) {
+    constexpr int SRC = decltype(src)::value, NF = decltype(nf)::value;
+    if (passes & PASS_1) {
+      if constexpr (stencil_shard<PT>) hipLaunchKernelGGL(smk_k_merge_seed_words, dim3(1), dim3(64), 0, s, P.words_out);
+      else hipLaunchKernelGGL(smk_k_merge_seed, dim3(1), dim3(64), 0, s, P.mx);
+      hipLaunchKernelGGL((smk_k_merge_max<SRC, NF, PT>), dim3(std::min<unsigned>((unsigned)P.ntiles, MG_MAX_BLOCKS)), dim3(256), 0, s, P);
+    }
+    if (passes & PASS_2) hipLaunchKernelGGL((smk_k_merge_write<SRC, NF, PT>), dim3((unsigned)P.ntiles), dim3(256), 0, s, P);
+    return hipGetLastError();
+  });
 }
 
 // what both entries refuse before they look at their data (smk_step_stencil_refusals)
@@ -353,36 +334,43 @@ StencilEntry merge_entry(const smk_ctx *c, const char *who) {
           "smk_merge_fields_device"};
 }
 
-// the two passes inside the producer frame; ksrc: the source slot, or -1 (dense fields)
-int merge_enqueue(smk_ctx *c, const char *who, const void *const *fields, int ksrc, int step_out, hipStream_t s) {
+// What every instance takes of the context: the volume, the stored box and its tiles, and with `fields` the series' dense
+// fields; no packed source and no output yet.  More than 2^31 tiles (2^42 voxels: no ring holds such a step, so the place of
+// this refusal before the frame's is moot) are refused in the words of the entries of the whole volume (`whole`), or of the
+// shard and block entries
+int merge_common(smk_ctx *c, const char *who, bool whole, const void *const *fields, MergeParams &P) {
   const int VPU = c->dtype == SMK_F32 ? 1 : 2, nf = c->nelts - 1;
   const long long ux = (c->D[0] / VPU + MG_UX - 1) / MG_UX, uy = (c->D[1] + MG_TY - 1) / MG_TY, uz = (c->D[2] + MG_TZ - 1) / MG_TZ;
-  if (ux * uy * uz > 0x7fffffffLL)  // (2^42 voxels: no ring holds such a step, so its place before the frame's refusal is moot)
-    FAIL(c, "%s: a %dx%dx%d volume has more than 2^31 tiles", who, c->N[0], c->N[1], c->N[2]);
+  if (ux * uy * uz > 0x7fffffffLL) {
+    if (whole) FAIL(c, "%s: a %dx%dx%d volume has more than 2^31 tiles", who, c->N[0], c->N[1], c->N[2]);
+    FAIL(c, "%s: a %dx%dx%d stored box has more than 2^31 tiles", who, c->D[0], c->D[1], c->D[2]);
+  }
+  P.src = nullptr;
+  for (int e = 0; e < 3; ++e) P.f[e] = fields && e < nf ? fields[e] : nullptr;
+  P.out = nullptr;
+  P.nrm = nullptr;
+  P.mx = nullptr;
+  for (int a = 0; a < 3; ++a) {
+    P.N[a] = c->N[a];
+    P.D[a] = c->D[a];
+  }
+  P.normals = c->have_normals ? 1 : 0;
+  P.ux = (int)ux;
+  P.uy = (int)(ux * uy);
+  P.ntiles = (int)(ux * uy * uz);
+  return 0;
+}
+
+// the two passes inside the producer frame; ksrc: the source slot, or -1 (dense fields)
+int merge_enqueue(smk_ctx *c, const char *who, const void *const *fields, int ksrc, int step_out, hipStream_t s) {
+  MergeParams P;
+  if (merge_common(c, who, true, fields, P)) return 1;
   return smk_step_produce(c, who, step_out, ksrc, -1, s, [&](TimeStep &T, const TimeStep *S, const TimeStep *) -> int {
-    MergeParams P;
     P.src = S ? S->vox : nullptr;
-    for (int e = 0; e < 3; ++e) P.f[e] = fields && e < nf ? fields[e] : nullptr;
     P.out = T.vox;
     P.nrm = smk_step_separate_normals(c) ? T.nrm : nullptr;
     P.mx = T.pass1_words;
-    for (int a = 0; a < 3; ++a) {
-      P.N[a] = c->N[a];
-      P.D[a] = c->D[a];
-    }
-    P.normals = c->have_normals ? 1 : 0;
-    P.ux = (int)ux;
-    P.uy = (int)(ux * uy);
-    P.ntiles = (int)(ux * uy * uz);
-    hipError_t e;
-    if (S) {
-      e = c->dtype == SMK_U8 ? launch_merge_nf<SRC_PK_U8>(P, nf, s) : c->dtype == SMK_U16 ? launch_merge_nf<SRC_PK_U16>(P, nf, s)
-                                                                                             : launch_merge_nf<SRC_PK_F32>(P, nf, s);
-    } else {
-      e = c->dtype == SMK_U8 ? launch_merge_nf<SMK_U8>(P, nf, s) : c->dtype == SMK_U16 ? launch_merge_nf<SMK_U16>(P, nf, s)
-                                                                                          : launch_merge_nf<SMK_F32>(P, nf, s);
-    }
-    HIPCHK(c, e);
+    HIPCHK(c, S ? launch_merge<true>(c, P, PASS_1 | PASS_2, s) : launch_merge<false>(c, P, PASS_1 | PASS_2, s));
     return 0;
   });
 }
@@ -397,55 +385,14 @@ StencilEntry merge_shard_entry(const smk_ctx *c, const char *who) {
   return E;
 }
 
-// false: more than 2^31 tiles
-bool merge_shard_params(const smk_ctx *c, const TimeStep &S, MergeShardParams &P) {
-  const int VPU = c->dtype == SMK_F32 ? 1 : 2;
-  const long long ux = (c->D[0] / VPU + MG_UX - 1) / MG_UX, uy = (c->D[1] + MG_TY - 1) / MG_TY, uz = (c->D[2] + MG_TZ - 1) / MG_TZ;
-  if (ux * uy * uz > 0x7fffffffLL) return false;
+// the shard's parameters with the packed step S as the source (B: the region, and the result's valid box)
+int merge_shard_params(smk_ctx *c, const char *who, const TimeStep &S, MergeShardParams &P) {
+  if (merge_common(c, who, false, nullptr, P)) return 1;
   P.src = S.vox;
-  for (int e = 0; e < 3; ++e) P.f[e] = nullptr;
-  P.out = nullptr;
-  P.nrm = nullptr;
-  P.mx = nullptr;
-  for (int a = 0; a < 3; ++a) {
-    P.N[a] = c->N[a];
-    P.D[a] = c->D[a];
-  }
-  P.normals = c->have_normals ? 1 : 0;
-  P.ux = (int)ux;
-  P.uy = (int)(ux * uy);
-  P.ntiles = (int)(ux * uy * uz);
   smk_step_shard_box(c, S, MG_REACH, P.B);
   P.words_out = nullptr;
   P.words_in = nullptr;
-  return true;
-}
-
-template <int SRC, int NF, class PT>
-hipError_t launch_merge_shard(const PT &P, bool write, hipStream_t s) {
-  if (write) {
-    hipLaunchKernelGGL((smk_k_merge_write<SRC, NF, PT>), dim3((unsigned)P.ntiles), dim3(256), 0, s, P);
-  } else {
-    hipLaunchKernelGGL(smk_k_merge_seed_words, dim3(1), dim3(64), 0, s, P.words_out);
-    hipLaunchKernelGGL((smk_k_merge_max<SRC, NF, PT>), dim3(std::min<unsigned>((unsigned)P.ntiles, MG_MAX_BLOCKS)), dim3(256), 0, s, P);
-  }
-  return hipGetLastError();
-}
-
-template <int SRC, class PT>
-hipError_t launch_merge_shard_nf(const PT &P, int nf, bool write, hipStream_t s) {
-  if (nf == 1) return launch_merge_shard<SRC, 1>(P, write, s);
-  if (nf == 2) return launch_merge_shard<SRC, 2>(P, write, s);
-  if constexpr (mg_ring(SRC) != SMK_U16) {
-    if (nf == 3) return launch_merge_shard<SRC, 3>(P, write, s);
-  }
-  return hipErrorInvalidValue;
-}
-
-hipError_t launch_merge_shard_dtype(const smk_ctx *c, const MergeShardParams &P, bool write, hipStream_t s) {
-  const int nf = c->nelts - 1;
-  return c->dtype == SMK_U8    ? launch_merge_shard_nf<SRC_PK_U8>(P, nf, write, s)
-         : c->dtype == SMK_U16 ? launch_merge_shard_nf<SRC_PK_U16>(P, nf, write, s) : launch_merge_shard_nf<SRC_PK_F32>(P, nf, write, s);
+  return 0;
 }
 
 // ---------------------------------------------------------------------------------------------- the block entries
@@ -455,45 +402,13 @@ hipError_t launch_merge_shard_dtype(const smk_ctx *c, const MergeShardParams &P,
 int merge_block_params(smk_ctx *c, const char *who, const int *step_out, const void *const *d_fields, int nf, smk_dtype dt, const smk_block *b,
                        SmkBlockView &V, MergeBlockParams &P) {
   if (smk_step_block_refusals(c, merge_shard_entry(c, who), MG_REACH, step_out, b, V)) return 1;
-  if (!d_fields) FAIL(c, "%s: d_fields is NULL", who);
-  if (nf != c->nelts - 1) FAIL(c, "%s: %d fields for a series of nelts %d: the fields are nelts - 1 = %d", who, nf, c->nelts, c->nelts - 1);
-  if ((int)dt != c->dtype) FAIL(c, "%s: field_dtype %d is not the ring's type (%d): the fields are stored as they come", who, (int)dt, c->dtype);
-  const size_t eb = smk_elem_bytes(dt);
-  for (int e = 0; e < nf; ++e) {
-    if (!d_fields[e]) FAIL(c, "%s: d_fields[%d] is NULL", who, e);
-    if ((uintptr_t)d_fields[e] % eb) FAIL(c, "%s: d_fields[%d] is not aligned to its %zu-byte elements", who, e, eb);
-  }
-  const int VPU = c->dtype == SMK_F32 ? 1 : 2;
-  const long long ux = (c->D[0] / VPU + MG_UX - 1) / MG_UX, uy = (c->D[1] + MG_TY - 1) / MG_TY, uz = (c->D[2] + MG_TZ - 1) / MG_TZ;
-  if (ux * uy * uz > 0x7fffffffLL) FAIL(c, "%s: a %dx%dx%d stored box has more than 2^31 tiles", who, c->D[0], c->D[1], c->D[2]);
-  P.src = nullptr;
-  for (int e = 0; e < 3; ++e) P.f[e] = e < nf ? d_fields[e] : nullptr;
-  P.out = nullptr;
-  P.nrm = nullptr;
-  P.mx = nullptr;
-  for (int a = 0; a < 3; ++a) {
-    P.N[a] = c->N[a];
-    P.D[a] = c->D[a];
-    P.bo[a] = b->origin[a] - c->O[a];
-    P.c0[a] = V.c0[a] - c->O[a];
-    P.c1[a] = V.c1[a] - c->O[a];
-  }
-  P.py = V.py;
-  P.pz = V.pz;
-  P.normals = c->have_normals ? 1 : 0;
-  P.ux = (int)ux;
-  P.uy = (int)(ux * uy);
-  P.ntiles = (int)(ux * uy * uz);
+  if (stencil_fields_refusals(c, who, d_fields, nf, dt, nullptr, -1, nullptr)) return 1;
+  if (merge_common(c, who, false, d_fields, P)) return 1;
+  stencil_block_src(c, b, V, P);
   smk_step_block_box(c, V, MG_REACH, P.B);
   P.words_out = nullptr;
   P.words_in = nullptr;
   return 0;
-}
-
-hipError_t launch_merge_block_dtype(const smk_ctx *c, const MergeBlockParams &P, bool write, hipStream_t s) {
-  const int nf = c->nelts - 1;
-  return c->dtype == SMK_U8    ? launch_merge_shard_nf<SMK_U8>(P, nf, write, s)
-         : c->dtype == SMK_U16 ? launch_merge_shard_nf<SMK_U16>(P, nf, write, s) : launch_merge_shard_nf<SMK_F32>(P, nf, write, s);
 }
 
 }  // namespace
@@ -504,7 +419,7 @@ int smk_merge_block_extremes_enqueue(smk_ctx *c, const char *who, const void *co
   MergeBlockParams P;
   if (merge_block_params(c, who, nullptr, d_fields, nf, dtype, b, V, P)) return 1;
   P.words_out = (int *)d_words;
-  HIPCHK(c, launch_merge_block_dtype(c, P, false, s));
+  HIPCHK(c, launch_merge<false>(c, P, PASS_1, s));
   return 0;
 }
 
@@ -515,15 +430,13 @@ extern "C" int smk_upload_timestep_fields_block_device(smk_ctx *c, int timestep,
   HIPCHK(c, hipSetDevice(c->device));
   SmkBlockView V;
   MergeBlockParams P;
-  if (merge_block_params(c, who, &timestep, d_fields, nf, field_dtype, b, V, P)) return 1;
-  if (!d_words) FAIL(c, "%s: d_words is NULL", who);
-  if ((uintptr_t)d_words % sizeof(int)) FAIL(c, "%s: d_words is not aligned to its 4-byte words", who);
+  if (merge_block_params(c, who, &timestep, d_fields, nf, field_dtype, b, V, P) || stencil_words_refusals(c, who, d_words)) return 1;
   const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   return smk_step_produce(c, who, timestep, -1, -1, s, [&](TimeStep &T, const TimeStep *, const TimeStep *) -> int {
     P.out = T.vox;
     P.nrm = smk_step_separate_normals(c) ? T.nrm : nullptr;
     P.words_in = (const int *)d_words;
-    HIPCHK(c, launch_merge_block_dtype(c, P, true, s));
+    HIPCHK(c, launch_merge<false>(c, P, PASS_2, s));
     smk_step_block_done(c, V, MG_REACH, P.B, T);
     return 0;
   });
@@ -533,10 +446,10 @@ int smk_merge_extremes_enqueue(smk_ctx *c, const char *who, int step_src, void *
   int ksrc = -1;
   if (smk_step_shard_refusals(c, merge_shard_entry(c, who), MG_REACH, step_src, nullptr, &ksrc)) return 1;
   MergeShardParams P;
-  if (!merge_shard_params(c, c->ts[(size_t)ksrc], P)) FAIL(c, "%s: a %dx%dx%d stored box has more than 2^31 tiles", who, c->D[0], c->D[1], c->D[2]);
+  if (merge_shard_params(c, who, c->ts[(size_t)ksrc], P)) return 1;
   P.words_out = (int *)d_words;
   return smk_step_read(c, ksrc, -1, s, [&]() -> int {
-    HIPCHK(c, launch_merge_shard_dtype(c, P, false, s));
+    HIPCHK(c, launch_merge<true>(c, P, PASS_1, s));
     return 0;
   });
 }
@@ -547,16 +460,14 @@ extern "C" int smk_merge_timestep_shard(smk_ctx *c, int step_src, int step_out, 
   HIPCHK(c, hipSetDevice(c->device));
   int ksrc = -1;
   if (smk_step_shard_refusals(c, merge_shard_entry(c, who), MG_REACH, step_src, &step_out, &ksrc)) return 1;
-  if (!d_words) FAIL(c, "%s: d_words is NULL", who);
-  if ((uintptr_t)d_words % sizeof(int)) FAIL(c, "%s: d_words is not aligned to its 4-byte words", who);
   MergeShardParams P;
-  if (!merge_shard_params(c, c->ts[(size_t)ksrc], P)) FAIL(c, "%s: a %dx%dx%d stored box has more than 2^31 tiles", who, c->D[0], c->D[1], c->D[2]);
+  if (stencil_words_refusals(c, who, d_words) || merge_shard_params(c, who, c->ts[(size_t)ksrc], P)) return 1;
   const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   return smk_step_produce(c, who, step_out, ksrc, -1, s, [&](TimeStep &T, const TimeStep *S, const TimeStep *) -> int {
     P.out = T.vox;
     P.nrm = smk_step_separate_normals(c) ? T.nrm : nullptr;
     P.words_in = (const int *)d_words;
-    HIPCHK(c, launch_merge_shard_dtype(c, P, true, s));
+    HIPCHK(c, launch_merge<true>(c, P, PASS_2, s));
     smk_step_shard_done(c, *S, MG_REACH, P.B, T);
     return 0;
   });
@@ -577,16 +488,7 @@ extern "C" int smk_upload_timestep_fields_device(smk_ctx *c, int timestep, const
   const char *who = "smk_upload_timestep_fields_device";
   HIPCHK(c, hipSetDevice(c->device));
   if (smk_step_stencil_refusals(c, merge_entry(c, who), timestep, nullptr, nullptr)) return 1;
-  if (!d_fields) FAIL(c, "%s: d_fields is NULL", who);
-  if (nf != c->nelts - 1) FAIL(c, "%s: %d fields for a series of nelts %d: the fields are nelts - 1 = %d", who, nf, c->nelts, c->nelts - 1);
-  if ((int)field_dtype != c->dtype)
-    FAIL(c, "%s: field_dtype %d is not the ring's type (%d): the fields are stored as they come", who, (int)field_dtype, c->dtype);
-  if (sx != c->N[0] || sy != c->N[1] || sz != c->N[2])
-    FAIL(c, "%s: time step %d: sizes %dx%dx%d differ from the series' %dx%dx%d", who, timestep, sx, sy, sz, c->N[0], c->N[1], c->N[2]);
-  const size_t eb = smk_elem_bytes(field_dtype);
-  for (int e = 0; e < nf; ++e) {
-    if (!d_fields[e]) FAIL(c, "%s: d_fields[%d] is NULL", who, e);
-    if ((uintptr_t)d_fields[e] % eb) FAIL(c, "%s: d_fields[%d] is not aligned to its %zu-byte elements", who, e, eb);
-  }
+  const int sizes[3] = {sx, sy, sz};
+  if (stencil_fields_refusals(c, who, d_fields, nf, field_dtype, nullptr, timestep, sizes)) return 1;
   return merge_enqueue(c, who, d_fields, -1, timestep, stream ? (hipStream_t)stream : c->stream);
 }

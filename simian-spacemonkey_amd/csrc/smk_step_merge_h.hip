@@ -28,10 +28,8 @@
 #include <limits.h>
 
 #include <algorithm>
-#include <type_traits>
 
-#include "smk_internal.h"
-#include "smk_prep_device.h"
+#include "smk_step_stencil.h"
 
 namespace {
 
@@ -70,49 +68,22 @@ struct MergeHShardParams : MergeHParams {
 // The BLOCK instances (smk.h: smk_block_extremes_h_device, smk_upload_timestep_fields_h_block_device): shard instances whose
 // fields are a rank's own dense blocks of the volume, all laid out by one smk_block that lies anywhere.  Only the SOURCE
 // differs: a voxel is read when it lies inside C = block ∩ stored box ∩ volume, at (local - bo) through the block's pitches,
-// and F is 0 outside C.  Again a parameter type of its own
-struct MergeHBlockParams : MergeHShardParams {
-  int bo[3];          // the block's element [0][0][0] in LOCAL voxels of the stored box (negative: the block starts before the box)
-  int c0[3], c1[3];   // C, local voxels: what of the block's extent this context takes
-  long long py, pz;   // elements between two rows, two slices of the block
-};
-template <class PT>
-constexpr bool mh_shard = std::is_base_of<MergeHShardParams, PT>::value;
-template <class PT>
-constexpr bool mh_block = std::is_same<PT, MergeHBlockParams>::value;
-
-// local voxel l of axis a as a voxel of the volume
-template <class PT>
-__device__ __forceinline__ int mh_glob(const PT &P, int a, int l) {
-  if constexpr (mh_shard<PT>) return P.B.O[a] + l;
-  else return l;
-}
-
-// local voxel (X, Y, Z) is a voxel of the volume that the source holds
-template <class PT>
-__device__ __forceinline__ bool mh_held(const PT &P, int X, int Y, int Z) {
-  if constexpr (mh_block<PT>)
-    return X >= P.c0[0] && X < P.c1[0] && Y >= P.c0[1] && Y < P.c1[1] && Z >= P.c0[2] && Z < P.c1[2];
-  else if constexpr (mh_shard<PT>)
-    return X >= 0 && X < P.D[0] && P.B.O[0] + X < P.N[0] && Y >= 0 && Y < P.D[1] && P.B.O[1] + Y < P.N[1] && Z >= 0 && Z < P.D[2] &&
-           P.B.O[2] + Z < P.N[2];
-  else return X >= 0 && X < P.N[0] && Y >= 0 && Y < P.N[1] && Z >= 0 && Z < P.N[2];
-}
+// (StencilBlockSrc: bo, c0, c1, py, pz), and F is 0 outside C.  Again a parameter type of its own
+struct MergeHBlockParams : MergeHShardParams, StencilBlockSrc {};
 
 // the volume's 1-voxel border (and everything outside the volume) at local voxel (X, Y, Z)
 template <class PT>
 __device__ __forceinline__ bool mh_border(const PT &P, int X, int Y, int Z) {
-  return is_border(P.N[0], P.N[1], P.N[2], mh_glob(P, 2, Z), mh_glob(P, 1, Y), mh_glob(P, 0, X));
+  return is_border(P.N[0], P.N[1], P.N[2], stencil_glob(P, 2, Z), stencil_glob(P, 1, Y), stencil_glob(P, 0, X));
 }
 
-constexpr int mh_ring(int SRC) { return SRC == SRC_PK_U8 ? SMK_U8 : SRC == SRC_PK_U16 ? SMK_U16 : SRC == SRC_PK_F32 ? SMK_F32 : SRC; }
 // the turns F takes: one per field of an f32 ring, one for all fields of an 8-byte voxel
-constexpr int mh_turns(int SRC, int NF) { return mh_ring(SRC) == SMK_F32 ? NF : 1; }
+constexpr int mh_turns(int SRC, int NF) { return stencil_ring(SRC) == SMK_F32 ? NF : 1; }
 
 // field e of a word of F as the float the gradient is taken of: (float)v of an integer, unscaled
 template <int SRC>
 __device__ __forceinline__ float mh_val(uint32_t w, int e) {
-  constexpr int RING = mh_ring(SRC);
+  constexpr int RING = stencil_ring(SRC);
   if (RING == SMK_F32) return __uint_as_float(w);
   if (RING == SMK_U8) return (float)smk_u8_ch(w, e);
   return (float)(e ? smk_vox8_c1<SMK_U16>(w) : smk_vox8_c0<SMK_U16>(w));
@@ -122,18 +93,18 @@ __device__ __forceinline__ float mh_val(uint32_t w, int e) {
 // source does not hold is 0 too, and is used by the voxels of the rim alone)
 template <int SRC, int NF, class PT>
 __device__ __forceinline__ void mh_load(const PT &P, int x0, int y0, int z0, int p, uint32_t *F) {
-  constexpr int RING = mh_ring(SRC);
+  constexpr int RING = stencil_ring(SRC);
   if (SRC == SRC_PK_U8 || SRC == SRC_PK_U16) {  // two voxels per 16-byte unit (x0 - 2 is even, and so is D[0]): their channel words are .x and .z
     constexpr int UPR = MH_FX / 2;
     for (int u = threadIdx.x; u < UPR * MH_FY * MH_FZ; u += 256) {
       const int cu = u % UPR, row = u / UPR, ly = row % MH_FY, lz = row / MH_FY;
       const int X = x0 - 2 + 2 * cu, Y = y0 - 2 + ly, Z = z0 - 2 + lz;
       uint32_t a = 0u, b = 0u;
-      // (the unsharded test spelled out here: through mh_held the compiler lays these instances' branches out differently)
-      if (mh_shard<PT> ? mh_held(P, X, Y, Z) : (X >= 0 && X < P.N[0] && Y >= 0 && Y < P.N[1] && Z >= 0 && Z < P.N[2])) {
+      // (the unsharded test spelled out here: through stencil_held the compiler lays these instances' branches out differently)
+      if (stencil_shard<PT> ? stencil_held(P, X, Y, Z) : (X >= 0 && X < P.N[0] && Y >= 0 && Y < P.N[1] && Z >= 0 && Z < P.N[2])) {
         const uint4 v = ((const uint4 *)P.src)[(((size_t)Z * P.D[1] + Y) * P.D[0] + X) >> 1];
         a = v.x;
-        if (mh_shard<PT> ? mh_glob(P, 0, X) + 1 < P.N[0] : X + 1 < P.N[0]) b = v.z;
+        if (stencil_shard<PT> ? stencil_glob(P, 0, X) + 1 < P.N[0] : X + 1 < P.N[0]) b = v.z;
       }
       F[row * MH_FX + 2 * cu] = a;
       F[row * MH_FX + 2 * cu + 1] = b;
@@ -143,13 +114,13 @@ __device__ __forceinline__ void mh_load(const PT &P, int x0, int y0, int z0, int
       const int lx = t % MH_FX, row = t / MH_FX, ly = row % MH_FY, lz = row / MH_FY;
       const int X = x0 - 2 + lx, Y = y0 - 2 + ly, Z = z0 - 2 + lz;
       uint32_t a = 0u;
-      if (mh_held(P, X, Y, Z)) {
+      if (stencil_held(P, X, Y, Z)) {
         if (SRC == SRC_PK_F32) {
           const uint4 v = ((const uint4 *)P.src)[((size_t)Z * P.D[1] + Y) * P.D[0] + X];
           a = p == 0 ? v.x : p == 1 ? v.y : v.z;
         } else {
           size_t o;
-          if constexpr (mh_block<PT>) o = (size_t)(Z - P.bo[2]) * (size_t)P.pz + (size_t)(Y - P.bo[1]) * (size_t)P.py + (size_t)(X - P.bo[0]);
+          if constexpr (stencil_block<PT>) o = (size_t)(Z - P.bo[2]) * (size_t)P.pz + (size_t)(Y - P.bo[1]) * (size_t)P.py + (size_t)(X - P.bo[0]);
           else o = ((size_t)Z * P.N[1] + Y) * P.N[0] + X;
           if (RING == SMK_F32) {
             a = ((const uint32_t *)P.f[p])[o];
@@ -228,13 +199,13 @@ __global__ __launch_bounds__(256) void smk_k_merge_h_stats(const PT P) {
   __shared__ uint32_t F[MH_FN];
   __shared__ float S[3 * MH_SN];
   static_assert(sizeof(uint32_t) * MH_FN + sizeof(float) * 3 * MH_SN == 61536, "the shard and block instances add nothing to the LDS: two workgroups per CU");
-  constexpr bool FLT = mh_ring(SRC) != SMK_U8;  // (a u16 ring's G and H are the float entry's)
+  constexpr bool FLT = stencil_ring(SRC) != SMK_U8;  // (a u16 ring's G and H are the float entry's)
   const int tx = threadIdx.x % MH_TX, ty = threadIdx.x / MH_TX;
   int m = MERGE_MAX_SEED, hmin = ORD_POS_INF, hmax = ORD_NEG_INF;
   for (int tile = blockIdx.x; tile < P.ntiles; tile += gridDim.x) {
     const int bx = tile % P.gx, by = (tile / P.gx) % P.gy, bz = tile / (P.gx * P.gy);
     const int x0 = bx * MH_TX, y0 = by * MH_TY, z0 = bz * MH_TZ;
-    if constexpr (mh_shard<PT>) {  // a tile of halo voxels alone has nothing to add (the whole workgroup skips it)
+    if constexpr (stencil_shard<PT>) {  // a tile of halo voxels alone has nothing to add (the whole workgroup skips it)
       if (x0 >= P.B.r1[0] || x0 + MH_TX <= P.B.r0[0] || y0 >= P.B.r1[1] || y0 + MH_TY <= P.B.r0[1] || z0 >= P.B.r1[2] || z0 + MH_TZ <= P.B.r0[2])
         continue;
     }
@@ -242,10 +213,10 @@ __global__ __launch_bounds__(256) void smk_k_merge_h_stats(const PT P) {
     mh_tile<SRC, NF>(P, x0, y0, z0, F, S, own);
     const int X = x0 + tx, Y = y0 + ty;
     bool mine = true;
-    if constexpr (mh_shard<PT>) mine = X >= P.B.r0[0] && X < P.B.r1[0] && Y >= P.B.r0[1] && Y < P.B.r1[1];  // the region's voxels alone
+    if constexpr (stencil_shard<PT>) mine = X >= P.B.r0[0] && X < P.B.r1[0] && Y >= P.B.r0[1] && Y < P.B.r1[1];  // the region's voxels alone
     for (int tz = 0; tz < MH_TZ; ++tz) {
       const int Z = z0 + tz;
-      if constexpr (mh_shard<PT>) {
+      if constexpr (stencil_shard<PT>) {
         if (!mine || Z < P.B.r0[2] || Z >= P.B.r1[2]) continue;
       }
       if (mh_border(P, X, Y, Z)) continue;  // (and everything outside the volume)
@@ -268,7 +239,7 @@ __global__ __launch_bounds__(256) void smk_k_merge_h_stats(const PT P) {
   hmin = wave_min(hmin);
   hmax = wave_max(hmax);
   if ((threadIdx.x & 63) == 0) {
-    if constexpr (mh_shard<PT>) {
+    if constexpr (stencil_shard<PT>) {
       atomicMax(&P.words_out[0], m);
       if (P.add_h) {
         atomicMax(&P.words_out[1], ~hmin);
@@ -288,12 +259,12 @@ template <int SRC, int NF, class PT = MergeHParams>
 __global__ __launch_bounds__(256) void smk_k_merge_h_write(const PT P) {
   __shared__ uint32_t F[MH_FN];
   __shared__ float S[3 * MH_SN];
-  constexpr int RING = mh_ring(SRC), TURNS = mh_turns(SRC, NF);
+  constexpr int RING = stencil_ring(SRC), TURNS = mh_turns(SRC, NF);
   const int x0 = blockIdx.x * MH_TX, y0 = blockIdx.y * MH_TY, z0 = blockIdx.z * MH_TZ;
   uint32_t own[TURNS][MH_TZ];
   mh_tile<SRC, NF>(P, x0, y0, z0, F, S, own);
   float maxm, hmin, hmax;  // (a shard's come combined from the caller's words, min H complemented)
-  if constexpr (mh_shard<PT>) {
+  if constexpr (stencil_shard<PT>) {
     maxm = o2f(P.words_in[0]);
     merge_h_extremes(~P.words_in[1], P.words_in[2], hmin, hmax);
   } else {
@@ -302,18 +273,18 @@ __global__ __launch_bounds__(256) void smk_k_merge_h_write(const PT P) {
   }
   const int tx = threadIdx.x % MH_TX, ty = threadIdx.x / MH_TX, X = x0 + tx, Y = y0 + ty;
   if (X >= P.D[0] || Y >= P.D[1]) return;
-  const int GX = mh_glob(P, 0, X), GY = mh_glob(P, 1, Y);
+  const int GX = stencil_glob(P, 0, X), GY = stencil_glob(P, 1, Y);
   const int ne = NF + 1 + P.add_h;
 #pragma unroll
   for (int tz = 0; tz < MH_TZ; ++tz) {
-    const int Z = z0 + tz, GZ = mh_glob(P, 2, Z);
+    const int Z = z0 + tz, GZ = stencil_glob(P, 2, Z);
     if (Z >= P.D[2]) break;
     const size_t o = ((size_t)Z * P.D[1] + Y) * P.D[0] + X;
     if (GX >= P.N[0] || GY >= P.N[1]) {  // the pad column or row of an 8-byte box: zeros, as after an upload
       ((uint2 *)P.out)[o] = make_uint2(0u, 0u);
       continue;
     }
-    if constexpr (mh_shard<PT>) {  // the rim: zeros that carry no normal (a four-channel f32 voxel's goes to the separate buffer)
+    if constexpr (stencil_shard<PT>) {  // the rim: zeros that carry no normal (a four-channel f32 voxel's goes to the separate buffer)
       if (X < P.B.v0[0] || X >= P.B.v1[0] || Y < P.B.v0[1] || Y >= P.B.v1[1] || Z < P.B.v0[2] || Z >= P.B.v1[2]) {
         if (RING != SMK_F32) {
           ((uint2 *)P.out)[o] = make_uint2(0u, SMK_NRM_NONE);
@@ -367,23 +338,23 @@ __global__ __launch_bounds__(256) void smk_k_merge_h_write(const PT P) {
   }
 }
 
-template <int SRC, int NF>
-hipError_t launch_merge_h(const MergeHParams &P, hipStream_t s) {
-  const dim3 grid((unsigned)P.gx, (unsigned)P.gy, (unsigned)(P.ntiles / (P.gx * P.gy)));
-  hipLaunchKernelGGL(smk_k_merge_h_seed_words, dim3(1), dim3(64), 0, s, P.w);
-  hipLaunchKernelGGL((smk_k_merge_h_stats<SRC, NF>), dim3(std::min<unsigned>((unsigned)P.ntiles, MH_STATS_BLOCKS)), dim3(256), 0, s, P);
-  hipLaunchKernelGGL((smk_k_merge_h_write<SRC, NF>), grid, dim3(256), 0, s, P);
-  return hipGetLastError();
-}
-
-template <int SRC>
-hipError_t launch_merge_h_nf(const MergeHParams &P, int nf, hipStream_t s) {
-  if (nf == 1) return launch_merge_h<SRC, 1>(P, s);
-  if (nf == 2) return launch_merge_h<SRC, 2>(P, s);
-  if constexpr (mh_ring(SRC) != SMK_U16) {  // (a u16 voxel holds three channels: merge_h_entry)
-    if (nf == 3) return launch_merge_h<SRC, 3>(P, s);
-  }
-  return hipErrorInvalidValue;
+// The seed and pass 1 (PASS_1: into the slot's words, a shard's and a block's into the caller's words), pass 2, or both, of the
+// instance that reads the ring's type -- a packed step of the ring (PACKED) or dense fields -- with the series' fields
+template <bool PACKED, class PT>
+hipError_t launch_merge_h(const smk_ctx *c, const PT &P, int passes, hipStream_t s) {
+  return stencil_dispatch<PACKED>(c->dtype, c->nelts - 1 - P.add_h, [&](auto src, auto nf) {
+    constexpr int SRC = decltype(src)::value, NF = decltype(nf)::value;
+    if (passes & PASS_1) {
+      if constexpr (stencil_shard<PT>) hipLaunchKernelGGL(smk_k_merge_h_seed_export, dim3(1), dim3(64), 0, s, P.words_out);
+      else hipLaunchKernelGGL(smk_k_merge_h_seed_words, dim3(1), dim3(64), 0, s, P.w);
+      hipLaunchKernelGGL((smk_k_merge_h_stats<SRC, NF, PT>), dim3(std::min<unsigned>((unsigned)P.ntiles, MH_STATS_BLOCKS)), dim3(256), 0, s, P);
+    }
+    if (passes & PASS_2) {
+      const dim3 grid((unsigned)P.gx, (unsigned)P.gy, (unsigned)(P.ntiles / (P.gx * P.gy)));
+      hipLaunchKernelGGL((smk_k_merge_h_write<SRC, NF, PT>), grid, dim3(256), 0, s, P);
+    }
+    return hipGetLastError();
+  });
 }
 
 // what both entries refuse before they look at their data (smk_step_stencil_refusals); add_h is 0 or 1
@@ -410,65 +381,17 @@ int merge_h_flags(smk_ctx *c, const char *who, int add_h, int blur) {
   return 0;
 }
 
-// the two passes inside the producer frame; ksrc: the source slot, or -1 (dense fields)
-int merge_h_enqueue(smk_ctx *c, const char *who, const void *const *fields, int ksrc, int step_out, int add_h, int compat, int blur, hipStream_t s) {
-  const int nf = c->nelts - 1 - add_h;
+// What every instance takes of the context: the volume, the stored box, its tiles, the flags, and with `fields` the series'
+// dense fields; no packed source and no output yet.  More tiles than a grid holds (2^42 voxels, or 2^19 rows or slices: no ring
+// holds such a step) are refused in the words of the entries of the whole volume (`whole`), or of the shard and block entries
+int merge_h_common(smk_ctx *c, const char *who, bool whole, const void *const *fields, int add_h, int compat, int blur, MergeHParams &P) {
   const long long gx = (c->D[0] + MH_TX - 1) / MH_TX, gy = (c->D[1] + MH_TY - 1) / MH_TY, gz = (c->D[2] + MH_TZ - 1) / MH_TZ;
-  if (gx * gy * gz > 0x7fffffffLL || gy > 65535 || gz > 65535)  // (2^42 voxels, or 2^19 rows or slices: no ring holds such a step)
-    FAIL(c, "%s: a %dx%dx%d volume has more tiles than a grid holds", who, c->N[0], c->N[1], c->N[2]);
-  return smk_step_produce(c, who, step_out, ksrc, -1, s, [&](TimeStep &T, const TimeStep *S, const TimeStep *) -> int {
-    MergeHParams P;
-    P.src = S ? S->vox : nullptr;
-    for (int e = 0; e < 3; ++e) P.f[e] = fields && e < nf ? fields[e] : nullptr;
-    P.out = T.vox;
-    P.nrm = smk_step_separate_normals(c) ? T.nrm : nullptr;
-    P.w = T.pass1_words;
-    for (int a = 0; a < 3; ++a) {
-      P.N[a] = c->N[a];
-      P.D[a] = c->D[a];
-    }
-    P.add_h = add_h;
-    P.compat = compat ? 1 : 0;
-    P.blur = blur;
-    P.normals = c->have_normals ? 1 : 0;
-    P.gx = (int)gx;
-    P.gy = (int)gy;
-    P.ntiles = (int)(gx * gy * gz);
-    hipError_t e;
-    if (S) {
-      e = c->dtype == SMK_U8 ? launch_merge_h_nf<SRC_PK_U8>(P, nf, s) : c->dtype == SMK_U16 ? launch_merge_h_nf<SRC_PK_U16>(P, nf, s)
-                                                                                             : launch_merge_h_nf<SRC_PK_F32>(P, nf, s);
-    } else {
-      e = c->dtype == SMK_U8 ? launch_merge_h_nf<SMK_U8>(P, nf, s) : c->dtype == SMK_U16 ? launch_merge_h_nf<SMK_U16>(P, nf, s)
-                                                                                          : launch_merge_h_nf<SMK_F32>(P, nf, s);
-    }
-    HIPCHK(c, e);
-    return 0;
-  });
-}
-
-// ---------------------------------------------------------------------------------------------- the shard entries
-
-constexpr int MH_REACH = 2;  // H reads S of the six neighbours, a blurred normal that of the 26, and S the fields' of theirs: the apron of F
-
-StencilEntry merge_h_shard_entry(const smk_ctx *c, const char *who, int add_h) {
-  StencilEntry E = merge_h_entry(c, who, add_h);
-  E.sharded_why = "";
-  return E;
-}
-
-int merge_h_words_refusals(smk_ctx *c, const char *who, const void *d_words) {
-  if (!d_words) FAIL(c, "%s: d_words is NULL", who);
-  if ((uintptr_t)d_words % sizeof(int)) FAIL(c, "%s: d_words is not aligned to its 4-byte words", who);
-  return 0;
-}
-
-// what every instance takes of the context: the volume, the stored box, its tiles, the flags.  False: more tiles than a grid holds
-bool merge_h_common(const smk_ctx *c, int add_h, int compat, int blur, MergeHParams &P) {
-  const long long gx = (c->D[0] + MH_TX - 1) / MH_TX, gy = (c->D[1] + MH_TY - 1) / MH_TY, gz = (c->D[2] + MH_TZ - 1) / MH_TZ;
-  if (gx * gy * gz > 0x7fffffffLL || gy > 65535 || gz > 65535) return false;
+  if (gx * gy * gz > 0x7fffffffLL || gy > 65535 || gz > 65535) {
+    if (whole) FAIL(c, "%s: a %dx%dx%d volume has more tiles than a grid holds", who, c->N[0], c->N[1], c->N[2]);
+    FAIL(c, "%s: a %dx%dx%d stored box has more tiles than a grid holds", who, c->D[0], c->D[1], c->D[2]);
+  }
   P.src = nullptr;
-  for (int e = 0; e < 3; ++e) P.f[e] = nullptr;
+  for (int e = 0; e < 3; ++e) P.f[e] = fields && e < c->nelts - 1 - add_h ? fields[e] : nullptr;
   P.out = nullptr;
   P.nrm = nullptr;
   P.w = nullptr;
@@ -483,46 +406,42 @@ bool merge_h_common(const smk_ctx *c, int add_h, int compat, int blur, MergeHPar
   P.gx = (int)gx;
   P.gy = (int)gy;
   P.ntiles = (int)(gx * gy * gz);
-  return true;
+  return 0;
 }
 
-template <int SRC, int NF, class PT>
-hipError_t launch_merge_h_shard(const PT &P, bool write, hipStream_t s) {
-  if (write) {
-    const dim3 grid((unsigned)P.gx, (unsigned)P.gy, (unsigned)(P.ntiles / (P.gx * P.gy)));
-    hipLaunchKernelGGL((smk_k_merge_h_write<SRC, NF, PT>), grid, dim3(256), 0, s, P);
-  } else {
-    hipLaunchKernelGGL(smk_k_merge_h_seed_export, dim3(1), dim3(64), 0, s, P.words_out);
-    hipLaunchKernelGGL((smk_k_merge_h_stats<SRC, NF, PT>), dim3(std::min<unsigned>((unsigned)P.ntiles, MH_STATS_BLOCKS)), dim3(256), 0, s, P);
-  }
-  return hipGetLastError();
+// the two passes inside the producer frame; ksrc: the source slot, or -1 (dense fields)
+int merge_h_enqueue(smk_ctx *c, const char *who, const void *const *fields, int ksrc, int step_out, int add_h, int compat, int blur, hipStream_t s) {
+  MergeHParams P;
+  if (merge_h_common(c, who, true, fields, add_h, compat, blur, P)) return 1;
+  return smk_step_produce(c, who, step_out, ksrc, -1, s, [&](TimeStep &T, const TimeStep *S, const TimeStep *) -> int {
+    P.src = S ? S->vox : nullptr;
+    P.out = T.vox;
+    P.nrm = smk_step_separate_normals(c) ? T.nrm : nullptr;
+    P.w = T.pass1_words;
+    HIPCHK(c, S ? launch_merge_h<true>(c, P, PASS_1 | PASS_2, s) : launch_merge_h<false>(c, P, PASS_1 | PASS_2, s));
+    return 0;
+  });
 }
 
-template <int SRC, class PT>
-hipError_t launch_merge_h_shard_nf(const PT &P, int nf, bool write, hipStream_t s) {
-  if (nf == 1) return launch_merge_h_shard<SRC, 1>(P, write, s);
-  if (nf == 2) return launch_merge_h_shard<SRC, 2>(P, write, s);
-  if constexpr (mh_ring(SRC) != SMK_U16) {
-    if (nf == 3) return launch_merge_h_shard<SRC, 3>(P, write, s);
-  }
-  return hipErrorInvalidValue;
+// ---------------------------------------------------------------------------------------------- the shard entries
+
+constexpr int MH_REACH = 2;  // H reads S of the six neighbours, a blurred normal that of the 26, and S the fields' of theirs: the apron of F
+
+StencilEntry merge_h_shard_entry(const smk_ctx *c, const char *who, int add_h) {
+  StencilEntry E = merge_h_entry(c, who, add_h);
+  E.sharded_why = "";
+  return E;
 }
 
-// a packed step of the ring as the source
-hipError_t launch_merge_h_shard_dtype(const smk_ctx *c, const MergeHShardParams &P, bool write, hipStream_t s) {
-  const int nf = c->nelts - 1 - P.add_h;
-  return c->dtype == SMK_U8    ? launch_merge_h_shard_nf<SRC_PK_U8>(P, nf, write, s)
-         : c->dtype == SMK_U16 ? launch_merge_h_shard_nf<SRC_PK_U16>(P, nf, write, s) : launch_merge_h_shard_nf<SRC_PK_F32>(P, nf, write, s);
+// the shard's parameters without the source's: the export finds its slot before the frame, the write pass inside it
+int merge_h_shard_params(smk_ctx *c, const char *who, int add_h, int compat, int blur, MergeHShardParams &P) {
+  if (merge_h_common(c, who, false, nullptr, add_h, compat, blur, P)) return 1;
+  P.words_out = nullptr;
+  P.words_in = nullptr;
+  return 0;
 }
 
 // ---------------------------------------------------------------------------------------------- the block entries
-
-// dense fields of the ring's type as the source
-hipError_t launch_merge_h_block_dtype(const smk_ctx *c, const MergeHBlockParams &P, bool write, hipStream_t s) {
-  const int nf = c->nelts - 1 - P.add_h;
-  return c->dtype == SMK_U8    ? launch_merge_h_shard_nf<SMK_U8>(P, nf, write, s)
-         : c->dtype == SMK_U16 ? launch_merge_h_shard_nf<SMK_U16>(P, nf, write, s) : launch_merge_h_shard_nf<SMK_F32>(P, nf, write, s);
-}
 
 // What both block entries refuse, and the shard's parameters with the block's fields as the source (B: the region, and C shrunk
 // by the reach as the result's valid box).  step_out: null for the export
@@ -530,26 +449,9 @@ int merge_h_block_params(smk_ctx *c, const char *who, const int *step_out, const
                          int add_h, int compat, int blur, SmkBlockView &V, MergeHBlockParams &P) {
   if (merge_h_flags(c, who, add_h, blur)) return 1;
   if (smk_step_block_refusals(c, merge_h_shard_entry(c, who, add_h), MH_REACH, step_out, b, V)) return 1;
-  if (!d_fields) FAIL(c, "%s: d_fields is NULL", who);
-  if (nf != c->nelts - 1 - add_h)
-    FAIL(c, "%s: %d fields for a series of nelts %d with add_h %d: the fields are nelts - 1 - add_h = %d", who, nf, c->nelts, add_h,
-         c->nelts - 1 - add_h);
-  if ((int)dt != c->dtype) FAIL(c, "%s: field_dtype %d is not the ring's type (%d): the fields are stored as they come", who, (int)dt, c->dtype);
-  const size_t eb = smk_elem_bytes(dt);
-  for (int e = 0; e < nf; ++e) {
-    if (!d_fields[e]) FAIL(c, "%s: d_fields[%d] is NULL", who, e);
-    if ((uintptr_t)d_fields[e] % eb) FAIL(c, "%s: d_fields[%d] is not aligned to its %zu-byte elements", who, e, eb);
-  }
-  if (!merge_h_common(c, add_h, compat, blur, P))
-    FAIL(c, "%s: a %dx%dx%d stored box has more tiles than a grid holds", who, c->D[0], c->D[1], c->D[2]);
-  for (int e = 0; e < nf; ++e) P.f[e] = d_fields[e];
-  for (int a = 0; a < 3; ++a) {
-    P.bo[a] = b->origin[a] - c->O[a];
-    P.c0[a] = V.c0[a] - c->O[a];
-    P.c1[a] = V.c1[a] - c->O[a];
-  }
-  P.py = V.py;
-  P.pz = V.pz;
+  if (stencil_fields_refusals(c, who, d_fields, nf, dt, &add_h, -1, nullptr)) return 1;
+  if (merge_h_common(c, who, false, d_fields, add_h, compat, blur, P)) return 1;
+  stencil_block_src(c, b, V, P);
   smk_step_block_box(c, V, MH_REACH, P.B);
   P.words_out = nullptr;
   P.words_in = nullptr;
@@ -562,20 +464,18 @@ extern "C" int smk_step_extremes_h_device(smk_ctx *c, int step_src, int add_h, i
   if (!c) return 1;
   const char *who = "smk_step_extremes_h_device";
   HIPCHK(c, hipSetDevice(c->device));
-  if (merge_h_flags(c, who, add_h, 0)) return 1;
-  if (merge_h_words_refusals(c, who, d_words)) return 1;
+  if (merge_h_flags(c, who, add_h, 0) || stencil_words_refusals(c, who, d_words)) return 1;
   int ksrc = -1;
   if (smk_step_shard_refusals(c, merge_h_shard_entry(c, who, add_h), MH_REACH, step_src, nullptr, &ksrc)) return 1;
   MergeHShardParams P;
-  if (!merge_h_common(c, add_h, compat, 0, P)) FAIL(c, "%s: a %dx%dx%d stored box has more tiles than a grid holds", who, c->D[0], c->D[1], c->D[2]);
+  if (merge_h_shard_params(c, who, add_h, compat, 0, P)) return 1;
   const TimeStep &S = c->ts[(size_t)ksrc];
   P.src = S.vox;
   smk_step_shard_box(c, S, MH_REACH, P.B);
   P.words_out = (int *)d_words;
-  P.words_in = nullptr;
   const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   return smk_step_read(c, ksrc, -1, s, [&]() -> int {
-    HIPCHK(c, launch_merge_h_shard_dtype(c, P, false, s));
+    HIPCHK(c, launch_merge_h<true>(c, P, PASS_1, s));
     return 0;
   });
 }
@@ -588,18 +488,16 @@ extern "C" int smk_merge_timestep_h_shard(smk_ctx *c, int step_src, int step_out
   if (merge_h_flags(c, who, add_h, blur)) return 1;
   int ksrc = -1;
   if (smk_step_shard_refusals(c, merge_h_shard_entry(c, who, add_h), MH_REACH, step_src, &step_out, &ksrc)) return 1;
-  if (merge_h_words_refusals(c, who, d_words)) return 1;
   MergeHShardParams P;
-  if (!merge_h_common(c, add_h, compat, blur, P)) FAIL(c, "%s: a %dx%dx%d stored box has more tiles than a grid holds", who, c->D[0], c->D[1], c->D[2]);
+  if (stencil_words_refusals(c, who, d_words) || merge_h_shard_params(c, who, add_h, compat, blur, P)) return 1;
   const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   return smk_step_produce(c, who, step_out, ksrc, -1, s, [&](TimeStep &T, const TimeStep *S, const TimeStep *) -> int {
     P.src = S->vox;
     P.out = T.vox;
     P.nrm = smk_step_separate_normals(c) ? T.nrm : nullptr;
     smk_step_shard_box(c, *S, MH_REACH, P.B);
-    P.words_out = nullptr;
     P.words_in = (const int *)d_words;
-    HIPCHK(c, launch_merge_h_shard_dtype(c, P, true, s));
+    HIPCHK(c, launch_merge_h<true>(c, P, PASS_2, s));
     smk_step_shard_done(c, *S, MH_REACH, P.B, T);
     return 0;
   });
@@ -610,12 +508,11 @@ extern "C" int smk_block_extremes_h_device(smk_ctx *c, const void *const *d_fiel
   if (!c) return 1;
   const char *who = "smk_block_extremes_h_device";
   HIPCHK(c, hipSetDevice(c->device));
-  if (merge_h_words_refusals(c, who, d_words)) return 1;
   SmkBlockView V;
   MergeHBlockParams P;
-  if (merge_h_block_params(c, who, nullptr, d_fields, nf, dtype, b, add_h, compat, 0, V, P)) return 1;
+  if (stencil_words_refusals(c, who, d_words) || merge_h_block_params(c, who, nullptr, d_fields, nf, dtype, b, add_h, compat, 0, V, P)) return 1;
   P.words_out = (int *)d_words;
-  HIPCHK(c, launch_merge_h_block_dtype(c, P, false, stream ? (hipStream_t)stream : c->stream));
+  HIPCHK(c, launch_merge_h<false>(c, P, PASS_1, stream ? (hipStream_t)stream : c->stream));
   return 0;
 }
 
@@ -627,14 +524,14 @@ extern "C" int smk_upload_timestep_fields_h_block_device(smk_ctx *c, int timeste
   HIPCHK(c, hipSetDevice(c->device));
   SmkBlockView V;
   MergeHBlockParams P;
-  if (merge_h_block_params(c, who, &timestep, d_fields, nf, field_dtype, b, add_h, compat, blur, V, P)) return 1;
-  if (merge_h_words_refusals(c, who, d_words)) return 1;
+  if (merge_h_block_params(c, who, &timestep, d_fields, nf, field_dtype, b, add_h, compat, blur, V, P) || stencil_words_refusals(c, who, d_words))
+    return 1;
   const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   return smk_step_produce(c, who, timestep, -1, -1, s, [&](TimeStep &T, const TimeStep *, const TimeStep *) -> int {
     P.out = T.vox;
     P.nrm = smk_step_separate_normals(c) ? T.nrm : nullptr;
     P.words_in = (const int *)d_words;
-    HIPCHK(c, launch_merge_h_block_dtype(c, P, true, s));
+    HIPCHK(c, launch_merge_h<false>(c, P, PASS_2, s));
     smk_step_block_done(c, V, MH_REACH, P.B, T);
     return 0;
   });
@@ -657,18 +554,7 @@ extern "C" int smk_upload_timestep_fields_h_device(smk_ctx *c, int timestep, con
   HIPCHK(c, hipSetDevice(c->device));
   if (merge_h_flags(c, who, add_h, blur)) return 1;
   if (smk_step_stencil_refusals(c, merge_h_entry(c, who, add_h), timestep, nullptr, nullptr)) return 1;
-  if (!d_fields) FAIL(c, "%s: d_fields is NULL", who);
-  if (nf != c->nelts - 1 - add_h)
-    FAIL(c, "%s: %d fields for a series of nelts %d with add_h %d: the fields are nelts - 1 - add_h = %d", who, nf, c->nelts, add_h,
-         c->nelts - 1 - add_h);
-  if ((int)field_dtype != c->dtype)
-    FAIL(c, "%s: field_dtype %d is not the ring's type (%d): the fields are stored as they come", who, (int)field_dtype, c->dtype);
-  if (sx != c->N[0] || sy != c->N[1] || sz != c->N[2])
-    FAIL(c, "%s: time step %d: sizes %dx%dx%d differ from the series' %dx%dx%d", who, timestep, sx, sy, sz, c->N[0], c->N[1], c->N[2]);
-  const size_t eb = smk_elem_bytes(field_dtype);
-  for (int e = 0; e < nf; ++e) {
-    if (!d_fields[e]) FAIL(c, "%s: d_fields[%d] is NULL", who, e);
-    if ((uintptr_t)d_fields[e] % eb) FAIL(c, "%s: d_fields[%d] is not aligned to its %zu-byte elements", who, e, eb);
-  }
+  const int sizes[3] = {sx, sy, sz};
+  if (stencil_fields_refusals(c, who, d_fields, nf, field_dtype, &add_h, timestep, sizes)) return 1;
   return merge_h_enqueue(c, who, d_fields, -1, timestep, add_h, compat, blur, stream ? (hipStream_t)stream : c->stream);
 }
