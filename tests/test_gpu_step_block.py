@@ -13,75 +13,15 @@ import pytest
 import _step_block_ref as B
 import _step_shard_ref as S
 import _tblend_ref as T
-import test_gpu_step_shard as G
-from test_gpu_step_shard import same, fsz, close, words_buf, Undisturbed
+import _step_gpu as G
+from _gpu_mem import dev_ptr as dev, fetch_layers, layer_buffer, merged, words_buf
+from _step_gpu import (RAN, UndisturbedHalos as Undisturbed, arrays, close, declared, dmode, flags_of, fsz, hand_over, params, probe_at,
+                       rank_context, ranks_declared, ranks_of, reference_of_arrays as reference, rim_tables, run_cut, same_bits as same,
+                       uploaded_zeros)
 
 pytestmark = pytest.mark.gpu
 CODE = B.M.CODE
 NP = B.M.NP
-
-
-def dev(a):
-    """(device address, the torch tensor that owns it) of the array's bytes"""
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
-    torch.cuda.synchronize()
-    return t.data_ptr(), t
-
-
-def declared(factory, dims, ring, nelts, dmode, rank=0, nranks=1, halo=1, normals=True, cap=4, opts=()):
-    """a context (one rank of `nranks`, or unsharded) that was given the series' geometry and no data"""
-    R = factory()
-    try:
-        if nranks > 1:
-            R.set_shard(rank, nranks)
-            R.set_option("halo", halo)
-        for k, v in opts:
-            R.set_option(k, v)
-        R.set_timestep_cache(cap)
-        R.declare_volume(dims, nelts, CODE[ring], fsize=fsz(dims), dmode=dmode, normals=normals)
-    except Exception:
-        R.close()
-        raise
-    return R
-
-
-def uploaded_zeros(factory, dims, ring, nelts, dmode, rank=0, nranks=1, halo=1, normals=True, cap=4, opts=()):
-    """... that UPLOADED a volume of zeros: existing entries alone"""
-    nx, ny, nz = dims
-    R = factory()
-    try:
-        if nranks > 1:
-            R.set_shard(rank, nranks)
-            R.set_option("halo", halo)
-        for k, v in opts:
-            R.set_option(k, v)
-        R.set_timestep_cache(cap)
-        R.upload_volume(np.zeros((nz, ny, nx, nelts), NP[ring]), np.full((nz, ny, nx, 3), 128, np.uint8) if normals else None, fsize=fsz(dims),
-                        dmode=dmode)
-    except Exception:
-        R.close()
-        raise
-    return R
-
-
-def hand_over(smk, c, whole, ring):
-    """(device address of the block's first element, what keeps it alive, the smk_block) of cut c of `whole` [z][y][x](...)"""
-    a, off, py, pz = c.take(whole, B.POISON[ring])
-    p, keep = dev(a)
-    per = a.itemsize * int(np.prod(a.shape[3:], dtype=np.int64))
-    return p + off * per, keep, smk.smk_block(c.origin, c.size, py, pz)
-
-
-def ranks_declared(factory, kind, dims, ring, nelts, cuts, normals=True, cap=4, opts=()):
-    rs = []
-    try:
-        for c in cuts:
-            rs.append(declared(factory, dims, ring, nelts, G.dmode(kind, nelts), c.rank, c.nranks, c.option_halo, normals, cap, opts))
-    except Exception:
-        close(rs)
-        raise
-    return rs
 
 
 # ---- 1. the data-free geometry
@@ -166,14 +106,14 @@ PACKED = [pytest.param(i, ring, id="%s-%s" % (B.CASE_IDS[i], ring)) for i in ran
 def test_the_ranks_packed_blocks_assemble_to_the_uploaded_volume(gpu_renderer_factory, smk, case, ring, which):
     kind, dims, nranks, halo = B.CASES[case]
     data, grad = S.source(kind, ring, dims)
-    U = G.context(gpu_renderer_factory, kind, dims, data, grad)
+    U = rank_context(gpu_renderer_factory, dims, data, grad, dmode(kind, data.shape[-1]))
     try:
         wdata, wgrad = U.download_timestep(0)
         wprobe = U.probe_step(S.cells_of((0, 0, 0), dims), 0)
     finally:
         U.close()
     cuts = B.cuts_of(case, ring, which, reach=0)
-    rs = ranks_declared(gpu_renderer_factory, kind, dims, ring, data.shape[-1], cuts)
+    rs = ranks_declared(gpu_renderer_factory, dims, ring, data.shape[-1], dmode(kind, data.shape[-1]), cuts)
     parts, gparts, keep = [], [], []
     try:
         for R, c in zip(rs, cuts):
@@ -190,7 +130,7 @@ def test_the_ranks_packed_blocks_assemble_to_the_uploaded_volume(gpu_renderer_fa
             raw, nrm, ok = R.probe_step(cells, 1)
             inside = np.all((cells >= np.array(c.lo)) & (cells + 1 < np.array(c.hi)), -1)
             assert np.array_equal(ok, inside), "rank %d: %d cells answered, %d lie in C" % (c.rank, ok.sum(), inside.sum())
-            wraw, wnrm = G.probe_at(wprobe, dims, cells[inside])
+            wraw, wnrm = probe_at(wprobe, dims, cells[inside])
             same(raw[inside], wraw, "rank %d: C's voxels" % c.rank)
             same(nrm[inside], wnrm, "rank %d: C's normals" % c.rank)
             # (an unanswered cell comes back as zeros from the host: that says nothing of the rim, which
@@ -204,66 +144,6 @@ def test_the_ranks_packed_blocks_assemble_to_the_uploaded_volume(gpu_renderer_fa
 
 
 # ---- 3. the words, 4. the voxels
-
-_REF = {}
-
-
-def arrays(kind, ring, dims, sd, nf):
-    """the whole dense arrays [z][y][x] a simulation holds: one scalar of type sd (derive), nf fields of the ring's (merge)"""
-    if kind == "derive":
-        return [B.scalar(sd, dims)]
-    F = B.M.fields(ring, nf, dims)
-    return [np.ascontiguousarray(F[..., e]) for e in range(nf)]
-
-
-def reference(factory, kind, ring, dims, sd=None, nf=2, compat=1, blur=0, normals=True):
-    """what the unsharded one-call entry makes of the whole arrays, made once and shared: (the arrays, result data, result
-    normals, probe(cells) of the result, the words an unsharded f32-ring context exports for the same arrays held as floats)"""
-    sd = sd or ring
-    key = (kind, ring, dims, sd, nf, compat, blur, normals)
-    if key not in _REF:
-        arr = arrays(kind, ring, dims, sd, nf)
-        nelts = 3 if kind == "derive" else nf + 1
-        held = [dev(a) for a in arr]
-        U = uploaded_zeros(factory, dims, ring, nelts, G.dmode(kind, nelts), normals=normals)
-        try:
-            if kind == "derive":
-                U.upload_timestep_scalar_device(1, held[0][0], CODE[sd], dims, compat, blur)
-            else:
-                U.upload_timestep_fields_device(1, [h[0] for h in held], CODE[ring], dims)
-            got = U.download_timestep(1)
-            probe = U.probe_step(S.cells_of((0, 0, 0), dims), 1)
-            assert probe[2].all() and got[0].any()
-        finally:
-            U.close()
-        wkey = (kind, dims, sd if kind == "derive" else ring, nf, compat)
-        if wkey not in _REF:                                # the same values as floats in an f32 ring: exact for u8 and u16
-            fl = np.stack([a.astype(np.float32) for a in arr] + [np.zeros(dims[::-1], np.float32)] * (nelts - len(arr)), -1)
-            W = G.context(factory, kind, dims, np.ascontiguousarray(fl), None)
-            try:
-                _REF[wkey] = G.export(W, kind, 0, compat)
-            finally:
-                W.close()
-        for a in list(got) + list(probe[:2]) + arr:
-            a.setflags(write=False)
-        _REF[key] = (arr, got[0], got[1], probe, _REF[wkey])
-    return _REF[key]
-
-
-def run_cut(smk, rs, cuts, kind, ring, sd, arr, out, compat, blur, stream=None):
-    """every rank's block of cut `cuts` handed over: the two passes, then what keeps the blocks alive and the words"""
-    from simian_spacemonkey_amd import sortlast
-    keep, blocks = [], []
-    for c in cuts:
-        ptrs = []
-        for a in arr:
-            p, k, blk = hand_over(smk, c, a, sd)
-            ptrs.append(p)
-            keep.append(k)
-        blocks.append((ptrs, CODE[sd], blk))
-    words = sortlast.stencil_block_local(rs, kind, blocks, out, compat=compat, blur=blur, stream=stream)
-    return keep, words
-
 
 def check_cut(rs, cuts, kind, dims, out, words, ref):
     arr, wdata, wgrad, wprobe, wwords = ref
@@ -288,7 +168,7 @@ def check_cut(rs, cuts, kind, dims, out, words, ref):
         inside = np.all((cells >= np.array(c.vlo)) & (cells + 1 < np.array(c.vhi)), -1)
         assert np.array_equal(ok, inside), "cut %s rank %d: %d cells answered, %d lie in the valid box" % (c.which, c.rank, ok.sum(), inside.sum())
         assert (S.straddles(cells, c.g0, c.g1) & inside).any()
-        wraw, wnrm = G.probe_at(wprobe, dims, cells[inside])
+        wraw, wnrm = probe_at(wprobe, dims, cells[inside])
         same(raw[inside], wraw, "cut %s rank %d: the valid box's voxels" % (c.which, c.rank))
         same(nrm[inside], wnrm, "cut %s rank %d: the valid box's normals" % (c.which, c.rank))
         assert not raw[~inside].any() and not nrm[~inside].any()     # (unanswered cells are zeroed on the host; the rim: section 4b)
@@ -306,7 +186,7 @@ def check_case(factory, smk, kind, ring, case, sd=None, nf=2, compat=1, blur=0, 
         if not group:
             continue
         cuts = [B.cuts_of(case, ring, wc) for wc in group]
-        rs = ranks_declared(factory, kind, dims, ring, nelts, cuts[0], normals)
+        rs = ranks_declared(factory, dims, ring, nelts, dmode(kind, nelts), cuts[0], normals)
         try:
             for out, cs in enumerate(cuts, 1):
                 keep, words = run_cut(smk, rs, cs, kind, ring, sd, ref[0], out, compat, blur)
@@ -324,13 +204,13 @@ CASES = [pytest.param(i, ring, id="%s-%s" % (B.CASE_IDS[i], ring)) for i in rang
 @pytest.mark.parametrize("case, ring", CASES)
 def test_the_ranks_blocks_give_the_unsharded_step(gpu_renderer_factory, smk, case, ring):
     kind = B.CASES[case][0]
-    compat, blur = G.params(kind, case)
+    compat, blur = params(kind, case)
     check_case(gpu_renderer_factory, smk, kind, ring, case, compat=compat, blur=blur)
 
 
 @pytest.mark.parametrize("n, sd, ring", [(n, sd, ring) for n, (sd, ring) in enumerate((sd, ring) for sd in B.RINGS for ring in B.RINGS) if sd != ring])
 def test_a_scalar_of_any_type_into_a_ring_of_any_type(gpu_renderer_factory, smk, n, sd, ring):
-    compat, blur = G.params("derive", n)
+    compat, blur = params("derive", n)
     check_case(gpu_renderer_factory, smk, "derive", ring, 0, sd=sd, compat=compat, blur=blur)
 
 
@@ -347,17 +227,15 @@ def test_a_context_without_normals(gpu_renderer_factory, smk, kind, ring, nf, ca
 @pytest.mark.parametrize("kind, ring, sd, nf", [("derive", "u8", "u8", 2), ("derive", "u16", "f32", 2), ("derive", "f32", "u16", 2), ("merge", "u8", "u8", 3),
                                                  ("merge", "u16", "u16", 2), ("merge", "f32", "f32", 3)])
 def test_extremes_and_write_on_an_unsharded_context_is_the_one_call_entry(gpu_renderer_factory, smk, kind, ring, sd, nf):
-    import torch
     dims = (37, 13, 11)
     arr, wdata, wgrad, _, wwords = reference(gpu_renderer_factory, kind, ring, dims, sd, nf, 1, 1)
     nelts = 3 if kind == "derive" else nf + 1
     held = [dev(a) for a in arr]
     ptrs = [h[0] for h in held]
     blk = smk.smk_block((0, 0, 0), dims)
-    R = declared(gpu_renderer_factory, dims, ring, nelts, G.dmode(kind, nelts))
+    R = declared(gpu_renderer_factory, dims, ring, nelts, dmode(kind, nelts))
     try:
         w = words_buf()
-        torch.cuda.synchronize()
         R.block_extremes_device(0 if kind == "derive" else 1, ptrs, CODE[sd], blk, w.data_ptr())
         if kind == "derive":
             R.upload_timestep_scalar_block_device(1, ptrs[0], CODE[sd], blk, w.data_ptr(), 1, 1)
@@ -376,29 +254,6 @@ def test_extremes_and_write_on_an_unsharded_context_is_the_one_call_entry(gpu_re
 # a table that is transparent at the lowest few values alone a brick of rim voxels is flagged when one of them is not near zero, and
 # under a table that is opaque at the top values alone every brick that touches a rim of stale top values is flagged.
 
-def table(opaque):
-    t = np.zeros((256, 256, 4), np.uint8)
-    if opaque == "all but zero":
-        t[...] = 255
-        t[:6, :6, 3] = 0                                    # (the bilinear lookup of value 0 reaches texels 0 and 1, and a brick's range is taken
-                                                            # with a margin: the lowest few values are transparent)
-    else:
-        t[250:, 250:] = 255                                 # "the top alone"
-    return t
-
-
-def flags_of(R, sc, step):
-    """the brick flags of `step` under both tables"""
-    from _scenes import push_scene
-    push_scene(R, sc, upload=False)
-    R.select_timestep(step)
-    out = []
-    for opaque in ("all but zero", "the top alone"):
-        R.set_tf2d(table(opaque), None)
-        out.append(R.brick_flags()[0].copy())               # (made for every table; a frame uses them when few bricks are flagged)
-    return out
-
-
 @pytest.mark.parametrize("form", ["packed", "derive", "merge"])
 def test_the_rim_is_zeros_over_what_the_slot_held(gpu_renderer_factory, smk, form):
     """A step of top values everywhere goes up through an existing entry; the same id is overwritten in place by a block form
@@ -415,7 +270,7 @@ def test_the_rim_is_zeros_over_what_the_slot_held(gpu_renderer_factory, smk, for
         arr, wdata, wgrad, _, words = reference(gpu_renderer_factory, kind, ring, dims)
         cuts = [B.Cut(kind, dims, r, nranks, halo, ring, "a") for r in range(nranks)]
         words = torch.tensor(words, dtype=torch.int32, device="cuda")
-        torch.cuda.synchronize()
+        torch.cuda.synchronize()                            # the words are on the device before a context's stream reads them
     nz, ny, nx = dims[::-1]
     stale = np.full((nz, ny, nx, 3), 255, np.uint8)
     sgrad = np.full((nz, ny, nx, 3), 7, np.uint8)
@@ -429,15 +284,15 @@ def test_the_rim_is_zeros_over_what_the_slot_held(gpu_renderer_factory, smk, for
         for fill, gfill in ((0, 128), (255, 7)):            # the result with its rim zeroed; with the stale step left on it
             d, g = wdata.copy(), wgrad.copy()
             d[outside], g[outside] = fill, gfill
-            U = G.context(gpu_renderer_factory, kind, dims, d, g, c.rank, nranks, c.option_halo, opts=opts)
+            U = rank_context(gpu_renderer_factory, dims, d, g, dmode(kind, d.shape[-1]), c.rank, nranks, c.option_halo, opts=opts)
             try:
-                want.append(flags_of(U, sc, 0))
+                want.append(flags_of(U, sc, 0, rim_tables()))
             finally:
                 U.close()
-        R = G.context(gpu_renderer_factory, kind, dims, stale, sgrad, c.rank, nranks, c.option_halo, cap=3, opts=opts)
+        R = rank_context(gpu_renderer_factory, dims, stale, sgrad, dmode(kind, stale.shape[-1]), c.rank, nranks, c.option_halo, cap=3, opts=opts)
         try:
-            R.upload_timestep(1, stale, sgrad, fsize=fsz(dims), dmode=G.dmode(kind, 3))
-            before = flags_of(R, sc, 1)
+            R.upload_timestep(1, stale, sgrad, fsize=fsz(dims), dmode=dmode(kind, 3))
+            before = flags_of(R, sc, 1, rim_tables())
             if form == "packed":
                 pd, k0, blk = hand_over(smk, c, wdata, ring)
                 pg, k1, _ = hand_over(smk, c, wgrad, "u8")
@@ -450,7 +305,7 @@ def test_the_rim_is_zeros_over_what_the_slot_held(gpu_renderer_factory, smk, for
                 else:
                     R.upload_timestep_fields_block_device(1, ptrs, CODE[ring], blk, words.data_ptr())
             assert R.timesteps() == (1, [0, 1]) and R.timestep_halo(1) == c.halo      # (the shown step, overwritten in place)
-            got = flags_of(R, sc, 1)
+            got = flags_of(R, sc, 1, rim_tables())
         finally:
             R.close()
         assert before[0].all() and before[1].all(), "the stale step flags every brick under both tables"
@@ -469,7 +324,6 @@ def test_the_rim_is_zeros_over_what_the_slot_held(gpu_renderer_factory, smk, for
 @pytest.mark.parametrize("kind, ring, case, which", [("derive", "u8", 0, "a"), ("derive", "f32", 0, "c"), ("merge", "u16", 7, "b")])
 def test_frames_of_the_produced_step(gpu_renderer_factory, smk, kind, ring, case, which, kernel, bricks):
     from _scenes import push_scene
-    from test_gpu_tblend import RAN
     _, dims, nranks, halo = B.CASES[case]
     if nranks > 2:
         nranks = 2
@@ -481,21 +335,21 @@ def test_frames_of_the_produced_step(gpu_renderer_factory, smk, kind, ring, case
     def frames(rs):
         for R in rs:
             push_scene(R, sc, upload=False)
-        lay, out = G.merged(rs, sc)
+        lay, out = merged(rs, sc)
         assert all(R.last_frame_info()[0] == RAN[kernel] for R in rs) and all(R.stat("slab_failures") == 0 for R in rs)
         return lay, out
-    up = G.ranks_of(gpu_renderer_factory, kind, dims, wdata, wgrad, nranks, cuts[0].option_halo, opts=opts)     # ... that UPLOADED the unsharded result
+    up = ranks_of(gpu_renderer_factory, dims, wdata, wgrad, dmode(kind, wdata.shape[-1]), nranks, cuts[0].option_halo, opts=opts)     # ... that UPLOADED the unsharded result
     try:
         want_layers, want = frames(up)
     finally:
         close(up)
-    U = G.context(gpu_renderer_factory, kind, dims, wdata, wgrad, opts=opts)
+    U = rank_context(gpu_renderer_factory, dims, wdata, wgrad, dmode(kind, wdata.shape[-1]), opts=opts)
     try:
         push_scene(U, sc, upload=False)
         whole = U.render()
     finally:
         U.close()
-    rs = ranks_declared(gpu_renderer_factory, kind, dims, ring, 3, cuts, opts=opts)
+    rs = ranks_declared(gpu_renderer_factory, dims, ring, 3, dmode(kind, 3), cuts, opts=opts)
     try:
         frames(rs)                                          # (the declared zeros rendered first: flags and plans of another step exist)
         keep = run_cut(smk, rs, cuts, kind, ring, ring, arr, 1, 1, 0)
@@ -517,7 +371,6 @@ def test_frames_of_the_produced_step(gpu_renderer_factory, smk, kind, ring, case
 
 @pytest.mark.parametrize("kind", ["derive", "merge"])
 def test_refusals_leave_the_ring_unchanged(gpu_renderer_factory, smk, kind):
-    import torch
     from _scenes import push_scene
     dims, nranks = (37, 13, 11), 2
     reach = B.REACH[kind]
@@ -532,7 +385,6 @@ def test_refusals_leave_the_ring_unchanged(gpu_renderer_factory, smk, kind):
     pd, k0 = dev(data)
     pg, k1 = dev(grad)
     w = words_buf()
-    torch.cuda.synchronize()
     p = w.data_ptr()
     whole = smk.smk_block((0, 0, 0), dims)
 
@@ -551,10 +403,10 @@ def test_refusals_leave_the_ring_unchanged(gpu_renderer_factory, smk, kind):
         R.close()
     halo = reach + 1
     g0, g1, O, D, pad = S.stored_box(dims, 0, nranks, halo, ring)           # rank 0: x [0, 18), stored to 18 + halo (evened)
-    R = G.context(gpu_renderer_factory, kind, dims, data, grad, 0, nranks, halo, cap=2, opts=(("kernel", 1),))
+    R = rank_context(gpu_renderer_factory, dims, data, grad, dmode(kind, data.shape[-1]), 0, nranks, halo, cap=2, opts=(("kernel", 1),))
     try:
         push_scene(R, sc, upload=False)
-        R.upload_timestep(1, data, grad, fsize=fsz(dims), dmode=G.dmode(kind, 3))
+        R.upload_timestep(1, data, grad, fsize=fsz(dims), dmode=dmode(kind, 3))
         blk = lambda o, s, py=0, pz=0: smk.smk_block(o, s, py, pz)      # noqa: E731
         ok = blk((0, 0, 0), dims)
         short = blk((0, 0, 0), (g1[0] + reach, dims[1], dims[2]))          # a valid halo of `reach`
@@ -598,7 +450,7 @@ def test_refusals_leave_the_ring_unchanged(gpu_renderer_factory, smk, kind):
     finally:
         R.close()
     # no slot: a ring of one step, the current one
-    one = declared(gpu_renderer_factory, dims, ring, 3, G.dmode(kind, 3), cap=1)
+    one = declared(gpu_renderer_factory, dims, ring, 3, dmode(kind, 3), cap=1)
     try:
         for call, who in ((lambda: write(one, 5, ptrs, 0, whole, p), entry), (lambda: one.upload_timestep_block_device(5, pd, whole, pg), "smk_upload_timestep_block_device")):
             with pytest.raises(smk.SmkError, match=who + r": time step 5: the cache holds one step, the current one \(0\)"):
@@ -607,7 +459,7 @@ def test_refusals_leave_the_ring_unchanged(gpu_renderer_factory, smk, kind):
     finally:
         one.close()
     # a misaligned array, and the nelts rules
-    f32 = declared(gpu_renderer_factory, dims, "f32", 3, G.dmode(kind, 3), cap=3)
+    f32 = declared(gpu_renderer_factory, dims, "f32", 3, dmode(kind, 3), cap=3)
     try:
         with pytest.raises(smk.SmkError, match="is not aligned to its 4-byte elements"):
             write(f32, 1, [q + 2 for q in ptrs], 1, whole, p)
@@ -640,24 +492,22 @@ def test_on_a_stream_of_the_callers(gpu_renderer_factory, smk, kind):
     cuts = B.cuts_of(case, ring, "b")
     arr, wdata, wgrad, _, _ = reference(gpu_renderer_factory, kind, ring, dims)
     sc = T.scene(wdata, wgrad)
-    npix = sc.width * sc.height
 
     def run(side):
         st = None if side is None else ctypes.c_void_p(side.cuda_stream)
-        rs = ranks_declared(gpu_renderer_factory, kind, dims, ring, 3, cuts, opts=(("kernel", 1),))
+        rs = ranks_declared(gpu_renderer_factory, dims, ring, 3, dmode(kind, 3), cuts, opts=(("kernel", 1),))
         try:
             for R in rs:
                 push_scene(R, sc, upload=False)
-            layers = torch.zeros((nranks, npix, 4), dtype=torch.float32, device="cuda")
-            torch.cuda.synchronize()
+            layers = layer_buffer(rs, sc)
             keep = run_cut(smk, rs, cuts, kind, ring, ring, arr, 1, 1, 0, stream=st)
             for r, R in enumerate(rs):
                 R.select_timestep(1)
                 R.render_device(layers[r].data_ptr(), None, st)
-            torch.cuda.synchronize()
+            lay = fetch_layers(layers, sc)
             downs = [R.download_timestep(1) for R in rs]
             del keep
-            return layers.cpu().numpy(), downs
+            return lay, downs
         finally:
             close(rs)
     want = run(None)

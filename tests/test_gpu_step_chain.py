@@ -19,10 +19,10 @@ import _step_chain_ref as C
 import _step_read_ref as D
 import _step_shard_ref as S
 import _tblend_ref as T
-import test_gpu_step_block as GB
-import test_gpu_step_shard as G
-from test_gpu_step_block import dev
-from test_gpu_step_shard import same, fsz, close, words_buf, Undisturbed
+import _step_gpu as G
+from _gpu_mem import dev_ptr as dev, merged, words_buf
+from _step_gpu import (RAN, UndisturbedHalos as Undisturbed, close, declared, dmode, export, flags_of, fsz, one_call, probe_at, rank_context,
+                       ranks_declared, ranks_of, rim_tables, same_bits as same, write_shard)
 
 pytestmark = pytest.mark.gpu
 CODE = B.M.CODE
@@ -46,7 +46,7 @@ def dense(kind, ring, dims, fields):
 
 
 def dmode_of(links):
-    return G.dmode(C.final_kind(links), 3)
+    return dmode(C.final_kind(links), 3)
 
 
 # ---- the unsharded chain
@@ -76,7 +76,7 @@ def unsharded_link(U, link, src, fields, dims, ring, dm, compat, blur, keep):
     elif what == "blend":
         U.blend_timesteps(link[2], link[3], link[4], out)
     else:
-        G.one_call(U, link[2], link[3], out, compat, blur)
+        one_call(U, link[2], link[3], out, compat, blur)
 
 
 def reference_of(factory, cid, dims, links, ring, compat, blur):
@@ -87,11 +87,11 @@ def reference_of(factory, cid, dims, links, ring, compat, blur):
         ref = Ref()
         ref.steps, ref.probe, ref.words, keep = {}, {}, {}, []
         cells = S.cells_of((0, 0, 0), dims)
-        U = GB.declared(factory, dims, ring, 3, dm, cap=CAP)
+        U = declared(factory, dims, ring, 3, dm, cap=CAP)
         try:
             for link in links:
                 if link[0] == "stencil":
-                    ref.words[link[1]] = G.export(U, link[2], link[3], compat)
+                    ref.words[link[1]] = export(U, link[2], link[3], compat)
                 unsharded_link(U, link, src, fields, dims, ring, dm, compat, blur, keep)
                 ref.steps[link[1]] = U.download_timestep(link[1])
                 ref.probe[link[1]] = U.probe_step(cells, link[1])
@@ -127,14 +127,7 @@ def exact(got, want, cells, what):
 # ---- the chain on the ranks
 
 def declared_ranks(factory, ranks, dm, opts=(), cap=CAP):
-    rs = []
-    try:
-        for K in ranks:
-            rs.append(GB.declared(factory, K.dims, K.ring, 3, dm, K.rank, K.nranks, K.option_halo, cap=cap, opts=opts))
-    except Exception:
-        close(rs)
-        raise
-    return rs
+    return ranks_declared(factory, ranks[0].dims, ranks[0].ring, 3, dm, ranks, cap=cap, opts=opts)
 
 
 def sharded_link(smk, rs, ranks, link, src, fields, dm, compat, blur, keep):
@@ -216,14 +209,14 @@ def test_every_step_of_the_chain_is_the_unsharded_chains(gpu_renderer_factory, s
                 inside = np.all((cells >= np.array(lo)) & (cells + 1 < np.array(hi)), -1)
                 assert inside.any()
                 # what is answered is exact (a voxel computed from the source's rim is not) ...
-                araw, anrm = G.probe_at(ref.probe[out], dims, cells[ok])
+                araw, anrm = probe_at(ref.probe[out], dims, cells[ok])
                 exact(raw[ok], araw, cells[ok], who + ": the answered cells' voxels")
                 exact(nrm[ok], anrm, cells[ok], who + ": the answered cells' normals")
                 # ... and the answered cells are those of the model's box
                 bad = np.argwhere(ok != inside)
                 assert not len(bad), "%s: %d cells answered, %d lie in the model's box %s..%s; first other cell %s (answered: %s)" % (
                     who, ok.sum(), inside.sum(), lo, hi, tuple(cells[bad[0][0]]), bool(ok[bad[0][0]]))
-                wraw, wnrm = G.probe_at(ref.probe[out], dims, cells[inside])
+                wraw, wnrm = probe_at(ref.probe[out], dims, cells[inside])
                 same(raw[inside], wraw, who + ": the valid box's voxels")
                 same(nrm[inside], wnrm, who + ": the valid box's normals")
                 assert not raw[~inside].any() and not nrm[~inside].any(), who + ": an unanswered cell is zeros"
@@ -274,9 +267,9 @@ def test_the_rim_of_the_last_stencil_is_zeros_over_what_the_slot_held(gpu_render
         for fill, gfill in ((0, 128), (255, 7)):            # the result with its rim zeroed; with the stale step left on it
             d, g = wdata.copy(), wgrad.copy()
             d[~st.mask], g[~st.mask] = fill, gfill
-            U = G.context(gpu_renderer_factory, kind, dims, d, g, K.rank, nranks, halo, opts=opts)
+            U = rank_context(gpu_renderer_factory, dims, d, g, dmode(kind, d.shape[-1]), K.rank, nranks, halo, opts=opts)
             try:
-                both.append(GB.flags_of(U, sc, 0))
+                both.append(flags_of(U, sc, 0, rim_tables()))
             finally:
                 U.close()
         want.append(both)
@@ -285,9 +278,9 @@ def test_the_rim_of_the_last_stencil_is_zeros_over_what_the_slot_held(gpu_render
         before = []
         for R in rs:
             R.upload_timestep(final, stale, sgrad, fsize=fsz(dims), dmode=dm)
-            before.append(GB.flags_of(R, sc, final))
+            before.append(flags_of(R, sc, final, rim_tables()))
         words, keep = run_chain(smk, rs, ranks, links, ring, compat, blur)
-        got = [GB.flags_of(R, sc, final) for R in rs]
+        got = [flags_of(R, sc, final, rim_tables()) for R in rs]
         assert all(R.timesteps()[0] == final for R in rs)      # (the shown step, overwritten in place)
         del words, keep
     finally:
@@ -326,17 +319,16 @@ def test_a_rim_fed_voxel_differs_from_the_exact_one(gpu_renderer_factory, case, 
             zd, zg = data.copy(), grad.copy()
             zd[~st.src], zg[~st.src] = 0, 128               # what the rank holds of the source: zeros on its rim
             assert zd[st.src].any() and data[~st.src].any()
-            W = GB.declared(gpu_renderer_factory, dims, ring, 3, dm, cap=4)
+            W = declared(gpu_renderer_factory, dims, ring, 3, dm, cap=4)
             try:
                 W.upload_timestep(1, data, grad, fsize=fsz(dims), dmode=dm)
                 W.upload_timestep(2, zd, zg, fsize=fsz(dims), dmode=dm)
                 same(W.download_timestep(1)[0], data, "the source, read back and uploaded again")
                 w = words_buf()
-                torch.cuda.synchronize()
                 W.step_extremes_device(0 if kind == "derive" else 1, 1, w.data_ptr(), compat=compat)
-                torch.cuda.synchronize()
+                torch.cuda.synchronize()                    # the export ran on the context's stream: read-back
                 assert np.array_equal(w.cpu().numpy()[0], ref.words[out])
-                G.write_shard(W, kind, 2, 3, w.data_ptr(), compat, blur)
+                write_shard(W, kind, 2, 3, w.data_ptr(), compat, blur)
                 got = W.download_timestep(3)
             finally:
                 W.close()
@@ -364,7 +356,6 @@ FRAMES = [("B-derive-12x9x13-r2-h6", "u8"), ("C-derive-12x9x13-r2-h6", "f32"), (
 @pytest.mark.parametrize("cid, ring", FRAMES)
 def test_frames_of_the_chains_final_step(gpu_renderer_factory, smk, cid, ring, kernel, bricks):
     from _scenes import push_scene
-    from test_gpu_tblend import RAN
     case = C.CASE_IDS.index(cid)
     _, dims, nranks, halo, links = C.CASES[case]
     compat, blur = params(case)
@@ -377,15 +368,15 @@ def test_frames_of_the_chains_final_step(gpu_renderer_factory, smk, cid, ring, k
     def frames(rs):
         for R in rs:
             push_scene(R, sc, upload=False)
-        lay, out = G.merged(rs, sc)
+        lay, out = merged(rs, sc)
         assert all(R.last_frame_info()[0] == RAN[kernel] for R in rs) and all(R.stat("slab_failures") == 0 for R in rs)
         return lay, out
-    up = G.ranks_of(gpu_renderer_factory, kind, dims, wdata, wgrad, nranks, halo, opts=opts)     # ... that UPLOADED the unsharded result
+    up = ranks_of(gpu_renderer_factory, dims, wdata, wgrad, dmode(kind, wdata.shape[-1]), nranks, halo, opts=opts)     # ... that UPLOADED the unsharded result
     try:
         want_layers, want = frames(up)
     finally:
         close(up)
-    U = G.context(gpu_renderer_factory, kind, dims, wdata, wgrad, opts=opts)
+    U = rank_context(gpu_renderer_factory, dims, wdata, wgrad, dmode(kind, wdata.shape[-1]), opts=opts)
     try:
         push_scene(U, sc, upload=False)
         whole = U.render()
@@ -414,12 +405,11 @@ def test_frames_of_the_chains_final_step(gpu_renderer_factory, smk, cid, ring, k
 
 @pytest.mark.parametrize("n", range(len(C.REFUSED)), ids=C.REFUSED_IDS)
 def test_a_chain_whose_halo_runs_out_is_refused(gpu_renderer_factory, smk, n):
-    import torch
     from _scenes import push_scene
     cid, dims, nranks, halo, links, refused, (have, reach) = C.REFUSED[n]
     ring = "u8"
     _, out, kind, src_id = refused
-    dm = G.dmode(kind, 3)
+    dm = dmode(kind, 3)
     src, fields = sources(ring, dims)
     sc = T.scene(*src[0])
     ranks = [C.Rank(dims, r, nranks, halo, ring) for r in range(nranks)]
@@ -427,7 +417,6 @@ def test_a_chain_whose_halo_runs_out_is_refused(gpu_renderer_factory, smk, n):
         with pytest.raises(C.Refused):
             C.run(K, links + (refused,))
     w = words_buf()
-    torch.cuda.synchronize()
     p = w.data_ptr()
     why = r"smk_%s: time step %d \(the source\) has a valid halo of %d voxels, the stencil reaches %d .*a valid halo >= %d is needed"
     rs = declared_ranks(gpu_renderer_factory, ranks, dm, opts=(("kernel", 1),))
@@ -442,7 +431,7 @@ def test_a_chain_whose_halo_runs_out_is_refused(gpu_renderer_factory, smk, n):
                 with pytest.raises(smk.SmkError, match=why % ("step_extremes_device", src_id, have, reach, reach + 1)):
                     R.step_extremes_device(0 if kind == "derive" else 1, src_id, p)
                 with pytest.raises(smk.SmkError, match=why % (kind + "_timestep_shard", src_id, have, reach, reach + 1)):
-                    G.write_shard(R, kind, src_id, out, p)
+                    write_shard(R, kind, src_id, out, p)
         del keep
     finally:
         close(rs)

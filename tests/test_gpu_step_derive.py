@@ -5,7 +5,6 @@ test -- voxels and normals as smk_download_timestep returns them, frames on the 
 histogram.  Where the scalar is finite the arrays are also the CPU checker's (tests/_step_derive_ref.py, qualified by
 tests/test_step_derive_cpu.py; more of that in tests/test_gpu_step_derive_shapes.py).  Volumes are 37 x 13 x 11 and
 70 x 21 x 19 voxels and smaller."""
-import ctypes
 import os
 import subprocess
 
@@ -13,92 +12,14 @@ import numpy as np
 import pytest
 
 import _step_derive_ref as V
-import _step_read_ref as D
 import _tblend_ref as T
+from _gpu_mem import dev_ptr as dev, out_buffer, stream_arg
+from _step_gpu import RAN, Undisturbed, recipe, recipe_download, same_bits as same, scene_context, series
+from _trex_series import write_series
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IDS = dict(ids=lambda d: "x".join(map(str, d)) if isinstance(d, tuple) else None)
-
-
-def same(got, want, what=""):
-    got, want = D.bits(got), D.bits(want)
-    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.dtype, want.dtype, got.shape, want.shape)
-    bad = np.argwhere(got != want)
-    assert not len(bad), "%s: %d of %d values differ, first at %s: got %#x, want %#x" % (
-        what, len(bad), got.size, tuple(bad[0]), int(got[tuple(bad[0])]), int(want[tuple(bad[0])]))
-
-
-def dev(a, shift=0):
-    """(device address, the torch tensor that owns it) of the array's bytes, `shift` bytes behind the allocation's start"""
-    import torch
-    b = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
-    t = torch.zeros(b.size + shift, dtype=torch.uint8, device="cuda")
-    t[shift:] = torch.from_numpy(b.copy()).cuda()
-    torch.cuda.synchronize()
-    return t.data_ptr() + shift, t
-
-
-def stream_arg(s):
-    return ctypes.c_void_p(s.cuda_stream)
-
-
-def series(factory, steps, cap=4):
-    """a context whose step 0 (current) and step 1 are `steps` = ((data, grad), (data, grad)); grad None: no normals"""
-    R = factory()
-    try:
-        R.set_timestep_cache(cap)
-        R.upload_volume(steps[0][0], steps[0][1], dmode="VGH")
-        if len(steps) > 1:
-            R.upload_timestep(1, steps[1][0], steps[1][1], dmode="VGH")
-    except Exception:
-        R.close()
-        raise
-    return R
-
-
-def recipe(R, s, ring, compat, blur):
-    """what the recipe's device entries make of the scalar s [z][y][x] (u8, u16 or f32) for a ring of type `ring`:
-    (data, normals) as host arrays, made on the device through context R"""
-    import torch
-    nz, ny, nx = s.shape
-    dims, n = (nx, ny, nz), nx * ny * nz
-    ps, keep = dev(s)
-    v8 = torch.zeros(n * 3, dtype=torch.uint8, device="cuda")
-    vf = torch.zeros(n * 3, dtype=torch.float32, device="cuda")
-    nrm = torch.zeros(n * 3, dtype=torch.uint8, device="cuda")
-    q = torch.zeros(n * 3 * 2, dtype=torch.uint8, device="cuda")
-    torch.cuda.synchronize()                                # (the entries run on the context's stream and wait for it)
-    R.make_vgh_device(ps, V.CODE[{np.uint8: "u8", np.uint16: "u16", np.float32: "f32"}[s.dtype.type]], dims, compat, v8.data_ptr(), vf.data_ptr())
-    if ring == "u8":
-        R.normals_vgh_device(v8.data_ptr(), 3, dims, blur, nrm.data_ptr())
-        data = v8.cpu().numpy()
-    else:
-        R.normals_f32_device(vf.data_ptr(), 3, dims, blur, nrm.data_ptr())
-        if ring == "u16":
-            R.quantize_u16_device(vf.data_ptr(), n * 3, q.data_ptr())
-            data = q.cpu().numpy().view(np.uint16)
-        else:
-            data = vf.cpu().numpy()
-    return data.reshape(nz, ny, nx, 3), nrm.cpu().numpy().reshape(nz, ny, nx, 3)
-
-
-def fresh_download(factory, data, nrm, normals=True):
-    """the download of a fresh context that uploaded (data, nrm) from device memory"""
-    nz, ny, nx, _ = data.shape
-    F = factory()
-    try:
-        pd, k0 = dev(data)
-        pn, k1 = dev(nrm)
-        F.upload_volume_device(pd, (nx, ny, nz), 3, V.CODE[{np.uint8: "u8", np.uint16: "u16", np.float32: "f32"}[data.dtype.type]],
-                               pn if normals else None, dmode="VGH")
-        return F.download_timestep()
-    finally:
-        F.close()
-
-
-def recipe_download(factory, R, s, ring, compat, blur, normals=True):
-    return fresh_download(factory, *recipe(R, s, ring, compat, blur), normals=normals)
 
 
 # ---- 1. equals the recipe
@@ -152,7 +73,6 @@ def high_g_scene(data, grad):
 @pytest.mark.parametrize("ring", V.RINGS)
 def test_a_derived_step_renders_and_counts_like_the_recipes_upload(gpu_renderer_factory, O, ring, kernel):
     from _scenes import push_scene
-    from test_gpu_tblend import RAN
     dims = V.DIMS[0]
     a, b, _ = V.blended(O, dims, ring)
     opts = (("kernel", kernel), ("bricks", 1))
@@ -300,7 +220,7 @@ def test_derive_on_a_second_stream_behind_a_blend_and_a_source_overwritten(gpu_r
         R.set_timestep_cache(4)
         push_scene(R, sca)
         R.upload_timestep(1, b[0], b[1], fsize=tuple(float(f) for f in sca.fsize), dmode="VGH")
-        torch.cuda.synchronize()
+        torch.cuda.synchronize()                            # nothing is in flight when the four streams start
         outs = []
 
         def frames(n, t):
@@ -317,7 +237,7 @@ def test_derive_on_a_second_stream_behind_a_blend_and_a_source_overwritten(gpu_r
         frames(3, 3)
         R.derive_timestep(2, 3, 1, 0, stream=stream_arg(dv))               # into the slot those three read: it waits for them
         R.derive_timestep(1, 3, 1, 1, stream=stream_arg(bl))               # ... and again, on another stream
-        torch.cuda.synchronize()
+        torch.cuda.synchronize()                            # all four streams: read-back
         for i, (o, t) in enumerate(outs):
             assert np.array_equal(o.cpu().numpy(), want3 if t == 3 else want0), "frame %d (step %d)" % (i, t)
         same(R.download_timestep(2)[0], c[0], "the new step 2")
@@ -348,12 +268,12 @@ def test_async_results_equal_the_synchronous_ones(gpu_renderer_factory, O):
     bl, dv, up, dn = (torch.cuda.Stream() for _ in range(4))
     pc, kc = dev(c[0])
     pg, kg = dev(c[1])
-    out_d = torch.zeros(nx * ny * nz * 3, dtype=torch.float32, device="cuda")
-    out_g = torch.zeros(nx * ny * nz * 3, dtype=torch.uint8, device="cuda")
-    work = torch.zeros(1 << 22, dtype=torch.float32, device="cuda")
+    out_d = out_buffer(nx * ny * nz * 3, np.float32)
+    out_g = out_buffer(nx * ny * nz * 3, np.uint8)
+    work = out_buffer(1 << 22, np.float32)
     R = series(gpu_renderer_factory, (a, b))
     try:
-        torch.cuda.synchronize()
+        torch.cuda.synchronize()                            # nothing is in flight when the four streams start
         with torch.cuda.stream(bl):                         # work in front of the blend: nothing behind it has started yet
             for _ in range(24):
                 work.add_(1)
@@ -361,7 +281,7 @@ def test_async_results_equal_the_synchronous_ones(gpu_renderer_factory, O):
         R.derive_timestep(2, 3, 0, 1, stream=stream_arg(dv))
         R.upload_timestep_device(2, pc, dims, 3, 1, pg, dmode="VGH", stream=stream_arg(up))
         R.download_timestep_device(out_d.data_ptr(), out_g.data_ptr(), 3, stream_arg(dn))
-        torch.cuda.synchronize()
+        torch.cuda.synchronize()                            # all four streams: read-back
         same(out_d.cpu().numpy().reshape(nz, ny, nx, 3), want[0], "data")
         same(out_g.cpu().numpy().reshape(nz, ny, nx, 3), want[1], "normals")
         same(R.download_timestep(2)[0], c[0], "the new step 2")
@@ -371,57 +291,11 @@ def test_async_results_equal_the_synchronous_ones(gpu_renderer_factory, O):
 
 # ---- 6. ring and refusals
 
-def scene_context(factory, sc, cap=None, shard=None):
-    """a context that can render: scene sc pushed (its volume is step 0, current)"""
-    from _scenes import push_scene
-    R = factory()
-    try:
-        if shard:
-            R.set_shard(*shard)
-        if cap:
-            R.set_timestep_cache(cap)
-        push_scene(R, sc)
-    except Exception:
-        R.close()
-        raise
-    return R
-
-
-class Undisturbed:
-    """the refusals inside the block change nothing: the context renders, flags its bricks, lists and downloads its steps as before"""
-
-    def __init__(self, R, visible=True):
-        self.R, self.visible = R, visible
-
-    def state(self):
-        R = self.R
-        frame = R.render()
-        return frame, R.brick_flags()[0], R.timesteps(), [R.download_timestep(t) for t in R.timesteps()[1]], R.stat("tblend_count")
-
-    def __enter__(self):
-        self.before = self.state()
-        assert not self.visible or self.before[0][..., 3].max() > 0.05
-        return self
-
-    def __exit__(self, et, ev, tb):
-        if et is not None:
-            return False
-        after = self.state()
-        assert np.array_equal(after[0], self.before[0]), "the frame after the refusals"
-        assert np.array_equal(after[1], self.before[1]), "the brick flags after the refusals"
-        assert after[2] == self.before[2] and after[4] == self.before[4]
-        for (d0, g0), (d1, g1) in zip(self.before[3], after[3]):
-            same(d1, d0, "a step after the refusals")
-            same(g1, g0, "its normals after the refusals")
-        return False
-
-
 def test_ring_and_refusals(gpu_renderer_factory, smk, O):
-    import torch
     dims, ring = V.SMALL, "u8"
     nx, ny, nz = dims
     a, b, _ = V.blended(O, dims, ring)
-    buf = torch.zeros(nx * ny * nz * 4 + 64, dtype=torch.uint8, device="cuda")
+    buf = out_buffer(nx * ny * nz * 4 + 64, np.uint8)
     R = gpu_renderer_factory()
     try:
         with pytest.raises(smk.SmkError, match="smk_derive_timestep: no volume"):
@@ -540,7 +414,6 @@ def test_host_adapter_shows_the_derivatives_of_a_blend(tmp_path, O):
     """tests/host/derive_main drives HipVolumeRenderable::setTimeFraction + setTimeFractionDerivatives over a 3-step u8
     series: with derivatives on the step a fractional frame shows is the checker's VGH and normals of the blended scalar;
     with them off its frames are tblend_main's"""
-    from test_timesteps_cpu import write_series
     exe = os.path.join(ROOT, "tests", "host", "derive_main")
     tblend = os.path.join(ROOT, "tests", "host", "tblend_main")
     for e in (exe, tblend):

@@ -11,7 +11,8 @@ import numpy as np
 import pytest
 
 import _step_derive_ref as V
-from test_gpu_step_derive import dev, recipe_download, same, series
+from _gpu_mem import dev_ptr as dev
+from _step_gpu import recipe_download, same_bits as same, series
 
 pytestmark = pytest.mark.gpu
 IDS = dict(ids=lambda d: "x".join(map(str, d)) if isinstance(d, tuple) else None)

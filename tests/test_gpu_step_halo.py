@@ -12,11 +12,10 @@ import _step_halo_ref as HR
 import _step_merge_h_ref as H
 import _step_shard_ref as S
 import _tblend_ref as T
-import test_gpu_step_block as BK
-import test_gpu_step_merge_h_shard as MH
-import test_gpu_step_shard as G
-from test_gpu_step_block import dev
-from test_gpu_step_shard import same, fsz, close
+import _step_gpu as G
+from _gpu_mem import dev_ptr as dev, enqueue_layers, fetch_layers, layer_buffer, layers_of, out_buffer
+from _step_gpu import (MODE, UndisturbedHalos, close, declared, dmode, flags_of, fsz, pert_scene, probe_at, rank_context,
+                       ranks_declared, ranks_of, reference_of_arrays, reference_of_source, run_cut, same_bits as same)
 
 pytestmark = pytest.mark.gpu
 CODE = H.CODE
@@ -24,32 +23,12 @@ CODE = H.CODE
 
 # ---- contexts, producers and twins
 
-def sharded(factory, dims, data, grad, dm, nranks, halo, cap=4, opts=()):
-    """the ranks of a series whose step 0 is the UPLOADED (data, grad)"""
-    rs = []
-    try:
-        for r in range(nranks):
-            R = factory()
-            rs.append(R)
-            if nranks > 1:
-                R.set_shard(r, nranks)
-                R.set_option("halo", halo)
-            for k, v in opts:
-                R.set_option(k, v)
-            R.set_timestep_cache(cap)
-            R.upload_volume(data, grad, fsize=fsz(dims), dmode=dm)
-    except Exception:
-        close(rs)
-        raise
-    return rs
-
-
 def declared_ranks(factory, dims, cls, nranks, halo):
     ring, nelts, normals = HR.CLASSES[cls]
     rs = []
     try:
         for r in range(nranks):
-            rs.append(BK.declared(factory, dims, ring, nelts, "VGH" if nelts == 3 else "V4", r, nranks, halo, normals))
+            rs.append(declared(factory, dims, ring, nelts, "VGH" if nelts == 3 else "V4", r, nranks, halo, normals))
     except Exception:
         close(rs)
         raise
@@ -69,25 +48,25 @@ def recipe(factory, smk, prod, cls, dims):
         return _RECIPE[key]
     ring, nelts, normals = HR.CLASSES[cls]
     if prod == "derive":
-        data, grad, wdata, wgrad = G.reference(factory, "derive", ring, dims, compat=1, blur=1)[:4]
+        data, grad, wdata, wgrad = reference_of_source(factory, "derive", ring, dims, compat=1, blur=1)[:4]
         dm = "VGH"
 
         def make(nranks, halo, cap=4, opts=()):
-            rs = G.ranks_of(factory, "derive", dims, data, grad, nranks, halo, cap, opts)
+            rs = ranks_of(factory, dims, data, grad, "VGH", nranks, halo, cap, opts)
             return rs, sortlast.stencil_timestep_local(rs, "derive", 0, 1, compat=1, blur=1)
     elif prod == "merge":
-        data, grad, wdata, wgrad = G.reference(factory, "merge", ring, dims, nf=nelts - 1, normals=normals)[:4]
-        dm = G.MODE[nelts]
+        data, grad, wdata, wgrad = reference_of_source(factory, "merge", ring, dims, nf=nelts - 1, normals=normals)[:4]
+        dm = MODE[nelts]
 
         def make(nranks, halo, cap=4, opts=()):
-            rs = G.ranks_of(factory, "merge", dims, data, grad, nranks, halo, cap, opts)
+            rs = ranks_of(factory, dims, data, grad, dm, nranks, halo, cap, opts)
             return rs, sortlast.stencil_timestep_local(rs, "merge", 0, 1)
     elif prod == "merge_h":
         nf = nelts - 2
         data, grad = H.source_step(H.fields(ring, nf, dims, 0), 1)
         grad = grad if normals else None
         dm = H.MODE[(nf, 1)]
-        U = MH.context(factory, dims, data, grad, 1)
+        U = rank_context(factory, dims, data, grad, dm)
         try:
             U.merge_timestep_h(0, 1, 1, 1, 1)
             wdata, wgrad = U.download_timestep(1)
@@ -95,21 +74,21 @@ def recipe(factory, smk, prod, cls, dims):
             U.close()
 
         def make(nranks, halo, cap=4, opts=()):
-            rs = MH.ranks_of(factory, dims, data, grad, 1, nranks, halo, cap, opts)
+            rs = ranks_of(factory, dims, data, grad, dm, nranks, halo, cap, opts)
             return rs, sortlast.stencil_timestep_local(rs, "merge_h", 0, 1, compat=1, blur=1, add_h=1)
     elif prod in ("block_derive", "block_merge"):
         kind = prod[6:]
         nf = 2 if kind == "derive" else nelts - 1
         blur = 1 if kind == "derive" else 0
-        arr, wdata, wgrad = BK.reference(factory, kind, ring, dims, ring, nf, 1, blur, normals)[:3]
-        dm = G.dmode(kind, nelts)
+        arr, wdata, wgrad = reference_of_arrays(factory, kind, ring, dims, ring, nf, 1, blur, normals)[:3]
+        dm = dmode(kind, nelts)
 
         def make(nranks, halo, cap=4, opts=()):
             cuts = [B.Cut(kind, dims, r, nranks, halo - B.WIDER, ring, "c") for r in range(nranks)]
             assert all(c.option_halo == halo for c in cuts)
-            rs = BK.ranks_declared(factory, kind, dims, ring, nelts, cuts, normals, cap, opts)
+            rs = ranks_declared(factory, dims, ring, nelts, dm, cuts, normals, cap, opts)
             try:
-                return rs, BK.run_cut(smk, rs, cuts, kind, ring, ring, arr, 1, 1, blur)
+                return rs, run_cut(smk, rs, cuts, kind, ring, ring, arr, 1, 1, blur)
             except Exception:
                 close(rs)
                 raise
@@ -119,7 +98,7 @@ def recipe(factory, smk, prod, cls, dims):
         arr = [np.ascontiguousarray(F[..., e]) for e in range(nf)]
         dm = H.MODE[(nf, 1)]
         held = [dev(a) for a in arr]
-        U = MH.declared(factory, dims, ring, nelts, 1, normals=normals)
+        U = declared(factory, dims, ring, nelts, dm, normals=normals)
         try:
             U.upload_timestep_fields_h_device(1, [h[0] for h in held], CODE[ring], dims, 1, 1, 1)
             wdata, wgrad = U.download_timestep(1)
@@ -129,11 +108,9 @@ def recipe(factory, smk, prod, cls, dims):
 
         def make(nranks, halo, cap=4, opts=()):
             cuts = [B.Cut("derive", dims, r, nranks, halo - B.WIDER, ring, "c", reach=2) for r in range(nranks)]
-            rs = []
+            rs = ranks_declared(factory, dims, ring, nelts, dm, cuts, normals, cap, opts)
             try:
-                for c in cuts:
-                    rs.append(MH.declared(factory, dims, ring, nelts, 1, c.rank, nranks, c.option_halo, normals, cap, opts))
-                return rs, MH.run_cut(smk, rs, cuts, ring, arr, 1, 1, 1, 1)
+                return rs, run_cut(smk, rs, cuts, "merge_h", ring, ring, arr, 1, 1, 1, add_h=1)
             except Exception:
                 close(rs)
                 raise
@@ -159,7 +136,7 @@ def twin_probes(factory, key, dims, wdata, wgrad, dm, nranks, halo, ring):
     """probe(every cell of S_r) of every rank of the twin, made once and shared"""
     k = (key, dims, nranks, halo)
     if k not in _TWIN:
-        tw = sharded(factory, dims, wdata, wgrad, dm, nranks, halo)
+        tw = ranks_of(factory, dims, wdata, wgrad, dm, nranks, halo)
         try:
             assert all(R.timestep_halo(0) == halo for R in tw)
             _TWIN[k] = probes(tw, dims, halo, ring, 0)
@@ -176,31 +153,6 @@ def check_whole(rs, want, dims, halo, ring, step, what=""):
         same(raw, wraw, "%s rank %d: voxels of the stored box" % (what, r))
         same(nrm, wnrm, "%s rank %d: normals of the stored box" % (what, r))
         assert R.timestep_halo(step) == halo
-
-
-def layer_buffer(rs, sc):
-    import torch
-    layers = torch.zeros((len(rs), sc.width * sc.height, 4), dtype=torch.float32, device="cuda")
-    torch.cuda.synchronize()
-    return layers
-
-
-def enqueue_layers(rs, layers, stream=None):
-    for r, R in enumerate(rs):
-        R.render_device(layers[r].data_ptr(), None, stream)
-
-
-def fetch_layers(layers, sc):
-    import torch
-    torch.cuda.synchronize()
-    return layers.cpu().numpy().reshape(layers.shape[0], sc.height, sc.width, 4)
-
-
-def layers_of(rs, sc, stream=None):
-    """every rank's layer of the scene, [P][H][W][4]"""
-    layers = layer_buffer(rs, sc)
-    enqueue_layers(rs, layers, stream)
-    return fetch_layers(layers, sc)
 
 
 def push(rs, sc):
@@ -263,12 +215,11 @@ def all_to_all_v(rs, step, stream=None):
     import torch
     n = len(rs)
     lay = [R.step_halo_layout(n) for R in rs]
-    exp = [torch.full((max(l[2], 16),), 0x5a, dtype=torch.uint8, device="cuda") for l in lay]
-    ent = [torch.full((max(l[3], 16),), 0xa5, dtype=torch.uint8, device="cuda") for l in lay]
-    torch.cuda.synchronize()
+    exp = [out_buffer(max(l[2], 16), np.uint8, 0x5a) for l in lay]
+    ent = [out_buffer(max(l[3], 16), np.uint8, 0xa5) for l in lay]
     for R, e in zip(rs, exp):
         R.step_halo_exports_device(e.data_ptr(), step, stream)
-    torch.cuda.synchronize()
+    torch.cuda.synchronize()                                # the exports ran on the contexts' streams; torch's copies do not wait for them
     for r in range(n):
         so = HR.offsets(lay[r][0])
         for j in range(n):
@@ -276,10 +227,10 @@ def all_to_all_v(rs, step, stream=None):
             nb = lay[r][0][j]
             assert nb == lay[j][1][r]
             ent[j][ro[r]:ro[r] + nb].copy_(exp[r][so[j]:so[j] + nb])
-    torch.cuda.synchronize()
+    torch.cuda.synchronize()                                # ... and the contexts' streams do not wait for torch's copies
     for R, e in zip(rs, ent):
         R.step_halo_entries_device(e.data_ptr(), step, stream)
-    torch.cuda.synchronize()
+    torch.cuda.synchronize()                                # the entries are stored before the caller looks
     return exp, ent
 
 
@@ -290,7 +241,7 @@ def test_the_two_call_form_stores_the_local_forms_bits(gpu_renderer_factory, smk
     ring = HR.CLASSES[cls][0]
     dm, wdata, wgrad, make = recipe(gpu_renderer_factory, smk, prod, cls, dims)
     want = twin_probes(gpu_renderer_factory, (prod, cls), dims, wdata, wgrad, dm, nranks, halo, ring)
-    sc = G.pert_scene(np.ascontiguousarray(wdata[..., :3]), wgrad)
+    sc = pert_scene(np.ascontiguousarray(wdata[..., :3]), wgrad)
     opts = (("kernel", 1),)
     out = []
     for form in ("local", "buffers"):
@@ -322,7 +273,7 @@ def test_the_brick_summaries_are_made_again(gpu_renderer_factory):
     rng = np.random.default_rng(11)
     data = rng.integers(100, 256, dims[::-1] + (3,)).astype(np.uint8)
     grad = rng.integers(0, 256, dims[::-1] + (3,)).astype(np.uint8)
-    U = G.context(gpu_renderer_factory, "merge", dims, data, grad)
+    U = rank_context(gpu_renderer_factory, dims, data, grad, "V2G")
     try:
         U.merge_timestep(0, 1)
         wdata, wgrad = U.download_timestep(1)
@@ -333,17 +284,17 @@ def test_the_brick_summaries_are_made_again(gpu_renderer_factory):
     table = np.zeros((256, 256, 4), np.uint8)
     table[:, :8] = 255                                      # ([sg][sv]: opaque where the first channel is below 8, whatever the second)
     opts = (("kernel", 1),)
-    tw = sharded(gpu_renderer_factory, dims, wdata, wgrad, "V2G", nranks, halo, opts=opts)
+    tw = ranks_of(gpu_renderer_factory, dims, wdata, wgrad, "V2G", nranks, halo, opts=opts)
     try:
-        want = [MH.flags_of(R, sc, 0, table) for R in tw]
+        want = [flags_of(R, sc, 0, [table])[0] for R in tw]
     finally:
         close(tw)
-    rs = G.ranks_of(gpu_renderer_factory, "merge", dims, data, grad, nranks, halo, opts=opts)
+    rs = ranks_of(gpu_renderer_factory, dims, data, grad, "V2G", nranks, halo, opts=opts)
     try:
         keep = sortlast.stencil_timestep_local(rs, "merge", 0, 1)
-        before = [MH.flags_of(R, sc, 1, table) for R in rs]
+        before = [flags_of(R, sc, 1, [table])[0] for R in rs]
         sortlast.refill_halo_local(rs, 1)
-        after = [MH.flags_of(R, sc, 1, table) for R in rs]
+        after = [flags_of(R, sc, 1, [table])[0] for R in rs]
         del keep
     finally:
         close(rs)
@@ -368,8 +319,8 @@ def test_the_refused_frames_render_after_the_refill(gpu_renderer_factory, smk, n
     the twin's, layer by layer, after it"""
     from simian_spacemonkey_amd import sortlast
     dims, halo = (21, 13, 11), 3
-    data, grad, wdata, wgrad, _, _ = G.reference(gpu_renderer_factory, "derive", "u8", dims)
-    sc = G.pert_scene(wdata, wgrad)
+    data, grad, wdata, wgrad, _, _ = reference_of_source(gpu_renderer_factory, "derive", "u8", dims)
+    sc = pert_scene(wdata, wgrad)
     assert G.pert_need(dims, sc.pert_w)[0] == 2
     opts = (("kernel", 1),)
     shadows = nranks == 2
@@ -385,12 +336,12 @@ def test_the_refused_frames_render_after_the_refill(gpu_renderer_factory, smk, n
             assert 1 < min(need) and max(need) <= halo, need
             out.append(shadow_layers(rs, sc))
         return out
-    tw = sharded(gpu_renderer_factory, dims, wdata, wgrad, "VGH", nranks, halo, opts=opts)
+    tw = ranks_of(gpu_renderer_factory, dims, wdata, wgrad, "VGH", nranks, halo, opts=opts)
     try:
         want = both(tw)
     finally:
         close(tw)
-    rs = G.ranks_of(gpu_renderer_factory, "derive", dims, data, grad, nranks, halo, opts=opts)
+    rs = ranks_of(gpu_renderer_factory, dims, data, grad, "VGH", nranks, halo, opts=opts)
     try:
         push(rs, sc)
         keep = sortlast.stencil_timestep_local(rs, "derive", 0, 1)
@@ -425,14 +376,14 @@ def test_a_second_stencil_on_the_refilled_step(gpu_renderer_factory, smk, ring):
     dims, nranks, halo = (22, 13, 11), 4, 4
     data, grad = S.source("derive", ring, dims)
     cells = S.cells_of((0, 0, 0), dims)
-    U = G.context(gpu_renderer_factory, "derive", dims, data, grad)
+    U = rank_context(gpu_renderer_factory, dims, data, grad, "VGH")
     try:
         U.derive_timestep(0, 1, 1, 1)
         U.derive_timestep(1, 2, 1, 0)
         want = U.probe_step(cells, 2)
     finally:
         U.close()
-    rs = G.ranks_of(gpu_renderer_factory, "derive", dims, data, grad, nranks, halo)
+    rs = ranks_of(gpu_renderer_factory, dims, data, grad, "VGH", nranks, halo)
     try:
         keep = [sortlast.stencil_timestep_local(rs, "derive", 0, 1, compat=1, blur=1)]
         with pytest.raises(smk.SmkError, match=r"time step 1 \(the source\) has a valid halo of 2 voxels, the stencil reaches 2"):
@@ -447,7 +398,7 @@ def test_a_second_stencil_on_the_refilled_step(gpu_renderer_factory, smk, ring):
             raw, nrm, ok = R.probe_step(cs, 2)
             inside = np.all((cs >= np.array(lo)) & (cs + 1 < np.array(hi)), -1)
             assert np.array_equal(ok, inside) and (S.straddles(cs, g0, g1) & inside).any()
-            wraw, wnrm = G.probe_at(want, dims, cs[inside])
+            wraw, wnrm = probe_at(want, dims, cs[inside])
             same(raw[inside], wraw, "rank %d: the chain's voxels" % r)
             same(nrm[inside], wnrm, "rank %d: the chain's normals" % r)
         del keep
@@ -464,11 +415,11 @@ def test_refill_and_frames_on_one_stream_without_a_host_wait(gpu_renderer_factor
     from simian_spacemonkey_amd import sortlast
     from simian_spacemonkey_amd.binding import STEP_CURRENT
     dims, nranks, halo, ring = (21, 13, 11), 2, 3, "u8"
-    data, grad, wdata, wgrad, _, _ = G.reference(gpu_renderer_factory, "derive", ring, dims)
+    data, grad, wdata, wgrad, _, _ = reference_of_source(gpu_renderer_factory, "derive", ring, dims)
     data2, grad2 = S.source("derive", ring, dims, seed=1)
-    plain, pert = T.scene(wdata, wgrad), G.pert_scene(wdata, wgrad)
+    plain, pert = T.scene(wdata, wgrad), pert_scene(wdata, wgrad)
     opts = (("kernel", 1),)
-    tw = sharded(gpu_renderer_factory, dims, wdata, wgrad, "VGH", nranks, halo, opts=opts)
+    tw = ranks_of(gpu_renderer_factory, dims, wdata, wgrad, "VGH", nranks, halo, opts=opts)
     try:
         push(tw, plain)
         want_plain = layers_of(tw, plain)
@@ -480,7 +431,7 @@ def test_refill_and_frames_on_one_stream_without_a_host_wait(gpu_renderer_factor
     side, other = torch.cuda.Stream(), torch.cuda.Stream()
     st, ot = ctypes.c_void_p(side.cuda_stream), ctypes.c_void_p(other.cuda_stream)
     # (a) one stream, no host wait between the write pass, the refill and the frames
-    rs = G.ranks_of(gpu_renderer_factory, "derive", dims, data, grad, nranks, halo, opts=opts)
+    rs = ranks_of(gpu_renderer_factory, dims, data, grad, "VGH", nranks, halo, opts=opts)
     try:
         push(rs, pert)
         layers = layer_buffer(rs, pert)
@@ -493,16 +444,15 @@ def test_refill_and_frames_on_one_stream_without_a_host_wait(gpu_renderer_factor
         assert np.array_equal(got, want_pert)
         # (c) an export, and right behind it an upload into the slot on another stream: the export holds the old step's voxels
         lay = rs[0].step_halo_layout(nranks)
-        calm = torch.zeros((lay[2],), dtype=torch.uint8, device="cuda")
-        busy = torch.zeros((lay[2],), dtype=torch.uint8, device="cuda")
+        calm = out_buffer(lay[2], np.uint8)
+        busy = out_buffer(lay[2], np.uint8)
         pd, k0 = dev(data2)
         pg, k1 = dev(grad2)
-        torch.cuda.synchronize()
         rs[0].step_halo_exports_device(calm.data_ptr(), 1)
-        torch.cuda.synchronize()
+        torch.cuda.synchronize()                            # the calm export has ended before the busy one and the upload start
         rs[0].step_halo_exports_device(busy.data_ptr(), 1, st)
         rs[0].upload_timestep_device(1, pd, dims, 3, CODE[ring], pg, fsize=fsz(dims), dmode="VGH", stream=ot)
-        torch.cuda.synchronize()
+        torch.cuda.synchronize()                            # both streams: read-back
         assert calm.any() and torch.equal(calm, busy)
         g0, g1 = S.stored_box(dims, 0, nranks, halo, ring)[:2]
         same(rs[0].download_timestep(1)[0], data2[g0[2]:g1[2], g0[1]:g1[1], g0[0]:g1[0]], "the upload behind the export")
@@ -510,7 +460,7 @@ def test_refill_and_frames_on_one_stream_without_a_host_wait(gpu_renderer_factor
     finally:
         close(rs)
     # (b) the CURRENT step refilled between two frames
-    rs = G.ranks_of(gpu_renderer_factory, "derive", dims, data, grad, nranks, halo, opts=opts)
+    rs = ranks_of(gpu_renderer_factory, dims, data, grad, "VGH", nranks, halo, opts=opts)
     try:
         push(rs, plain)
         l1, l2 = layer_buffer(rs, plain), layer_buffer(rs, pert)
@@ -538,8 +488,8 @@ def test_idempotent_on_an_uploaded_step(gpu_renderer_factory, cls):
     dims, nranks, halo = HR.CASES[3]
     ring, nelts, normals = HR.CLASSES[cls]
     data, grad = S.source("merge", ring, dims, nf=nelts - 1)
-    sc = G.pert_scene(np.ascontiguousarray(data[..., :3]), grad)
-    rs = sharded(gpu_renderer_factory, dims, data, grad, G.MODE[nelts], nranks, halo, opts=(("kernel", 1),))
+    sc = pert_scene(np.ascontiguousarray(data[..., :3]), grad)
+    rs = ranks_of(gpu_renderer_factory, dims, data, grad, MODE[nelts], nranks, halo, opts=(("kernel", 1),))
     try:
         push(rs, sc)
         p0 = probes(rs, dims, halo, ring, 0)
@@ -561,7 +511,7 @@ def test_an_unsharded_context_has_nothing_to_refill(gpu_renderer_factory):
     dims = (21, 13, 11)
     data, grad = S.source("derive", "u8", dims)
     sc = T.scene(data, grad)
-    U = G.context(gpu_renderer_factory, "derive", dims, data, grad)
+    U = rank_context(gpu_renderer_factory, dims, data, grad, "VGH")
     try:
         push([U], sc)
         f0, d0 = U.render(), U.download_timestep(0)
@@ -584,8 +534,7 @@ def test_refusals_change_nothing(gpu_renderer_factory, smk):
     dims, nranks, halo = (21, 13, 11), 2, 3
     data, grad = S.source("derive", "u8", dims)
     sc = T.scene(data, grad)
-    buf = torch.full((1 << 16,), 0x5a, dtype=torch.uint8, device="cuda")
-    torch.cuda.synchronize()
+    buf = out_buffer(1 << 16, np.uint8, 0x5a)
     p = buf.data_ptr()
     E = smk.SmkError
     C = gpu_renderer_factory()
@@ -598,7 +547,7 @@ def test_refusals_change_nothing(gpu_renderer_factory, smk):
     finally:
         C.close()
     opts = (("kernel", 1),)
-    rs = G.ranks_of(gpu_renderer_factory, "derive", dims, data, grad, nranks, halo, opts=opts)
+    rs = ranks_of(gpu_renderer_factory, dims, data, grad, "VGH", nranks, halo, opts=opts)
     odd = []
     try:
         push(rs, sc)
@@ -615,7 +564,7 @@ def test_refusals_change_nothing(gpu_renderer_factory, smk):
             R.set_timestep_cache(4)
             R.upload_volume(np.ascontiguousarray(gg), dg, fsize=fsz(dd), dmode=dm)
             R.upload_timestep(1, np.ascontiguousarray(gg), dg, fsize=fsz(dd), dmode=dm)
-        with MH.Unchanged(rs[0]), MH.Unchanged(rs[1]):
+        with UndisturbedHalos(rs[0], downloads=False), UndisturbedHalos(rs[1], downloads=False):
             before = probes(rs, dims, halo, "u8", 1)
             for call, why in (
                     (lambda: rs[0].step_halo_exports_device(p, 99), "smk_step_halo_exports_device: time step 99 is not cached"),
@@ -634,7 +583,7 @@ def test_refusals_change_nothing(gpu_renderer_factory, smk):
                     (lambda: sortlast.refill_halo_local([rs[0], odd[4]], 1), "rank 1 differs from rank 0 in halo: 4, not 3")):
                 with pytest.raises(E, match=why):
                     call()
-            torch.cuda.synchronize()
+            torch.cuda.synchronize()                        # the contexts' streams: read-back
             assert (buf.cpu().numpy() == 0x5a).all(), "a refused export writes no byte"
             after = probes(rs, dims, halo, "u8", 1)
             for (r0, n0, k0), (r1, n1, k1) in zip(before, after):

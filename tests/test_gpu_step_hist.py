@@ -3,14 +3,14 @@ voxels: raw COUNTS, exactly, against the NumPy restatement of the header's contr
 tests/test_step_hist_cpu.py) -- for every packed layout, bricked uploads, every shard, steps that are not current, uploaded
 from device memory on another stream or blended in time -- and, where the older entries apply (u8, f32), their bytes.  The
 volume is 41 x 37 x 45 (tests/_step_hist_ref.DIMS): all odd, more than one flush chunk."""
-import ctypes
-
 import numpy as np
 import pytest
 
 import _step_hist_ref as S
 import _tblend_ref as T
+from _gpu_mem import busy, dev_tensor as dev, out_buffer, stream_arg
 from _layouts import shuffled
+from _step_gpu import bricked, context, ring, same_bins as same
 
 pytestmark = pytest.mark.gpu
 DMODE = {1: "V1", 2: "V1G", 3: "VGH", 4: "V2GH"}
@@ -18,68 +18,6 @@ DT = {"u8": 0, "f32": 1, "u16": 2}
 NX, NY, NZ = S.DIMS
 NVOX = NX * NY * NZ
 LAYOUTS = [("u8", 2), ("u8", 3), ("u8", 4), ("f32", 2), ("f32", 3), ("f32", 4), ("u16", 2), ("u16", 3)]
-
-
-def same(got, want, what=""):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    bad = np.argwhere(got != want)
-    assert not len(bad), "%s: %d bins differ, first %s: got %d, want %d; totals %d / %d" % (
-        what, len(bad), tuple(bad[0]), got[tuple(bad[0])], want[tuple(bad[0])], int(got.astype(np.int64).sum()), int(want.astype(np.int64).sum()))
-
-
-def context(factory, data, grad, cap=1, shard=None, halo=None):
-    R = factory()
-    try:
-        if shard:
-            R.set_shard(*shard)
-        if halo is not None:
-            R.set_option("halo", halo)
-        if cap > 1:
-            R.set_timestep_cache(cap)
-        R.upload_volume(data, grad, dmode=DMODE[data.shape[-1]])
-    except Exception:
-        R.close()
-        raise
-    return R
-
-
-def bricked(smk, data, grad, order):
-    """(smk_volume_desc array, keep-alive list) of the volume cut at its midpoints into 2 x 2 x 2 unequal bricks, handed over
-    in `order`"""
-    nz, ny, nx, _ = data.shape
-    dims, m = (nx, ny, nz), float(max(nx, ny, nz))
-    cuts = [(0, n // 2, n) for n in dims]
-    boxes = [[(cuts[a][i[a]], cuts[a][i[a] + 1]) for a in range(3)] for i in np.ndindex(2, 2, 2)]
-    descs, keep = (smk.binding.VolumeDesc * 8)(), []
-    for d, k in zip(descs, order):
-        (x0, x1), (y0, y1), (z0, z1) = boxes[k]
-        d.xiSize, d.yiSize, d.ziSize = x1 - x0, y1 - y0, z1 - z0
-        d.xfSize, d.yfSize, d.zfSize = (x1 - x0) / m, (y1 - y0) / m, (z1 - z0) / m
-        d.xiPos, d.yiPos, d.ziPos = x0, y0, z0
-        d.xfPos, d.yfPos, d.zfPos = x0 / m, y0 / m, z0 / m
-        sub = [np.ascontiguousarray(a[z0:z1, y0:y1, x0:x1]) for a in (data, grad)]
-        keep += sub
-        d.data, d.grad = sub[0].ctypes.data, sub[1].ctypes.data
-    return descs, keep
-
-
-def dev(a):
-    """the array's bytes in device memory (a torch tensor that owns them)"""
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
-
-
-def stream_arg(s):
-    return ctypes.c_void_p(s.cuda_stream)
-
-
-def busy(s, work):
-    """a few milliseconds of work on stream s, so that what is enqueued behind it has not started when the next call is made"""
-    import torch
-    with torch.cuda.stream(s):
-        for _ in range(24):
-            work.add_(1)
 
 
 # ---- 1. layouts
@@ -217,21 +155,9 @@ def test_shards(gpu_renderer_factory, smk, dtype, nranks, halo):
 
 # ---- 6. steps
 
-def ring(factory, dtype, nelts=3, cap=4):
-    """a context with step 0 = seed 1 (current) and step 1 = seed 2 resident"""
-    a, b = S.volume(dtype, nelts, 1), S.volume(dtype, nelts, 2)
-    R = context(factory, a[0], a[1], cap=cap)
-    try:
-        R.upload_timestep(1, b[0], b[1], dmode=DMODE[nelts])
-    except Exception:
-        R.close()
-        raise
-    return R, a, b
-
-
 @pytest.mark.parametrize("dtype", ["u8", "f32", "u16"])
 def test_steps_by_id_current_and_blended(gpu_renderer_factory, dtype):
-    R, a, b = ring(gpu_renderer_factory, dtype)
+    R, a, b = ring(gpu_renderer_factory, S.volume(dtype, 3, 1), S.volume(dtype, 3, 2))
     ca, cb = S.counts(a[0]), S.counts(b[0])
     assert not np.array_equal(ca, cb)
     try:
@@ -257,18 +183,18 @@ def test_device_upload_on_one_stream_histogram_on_another(gpu_renderer_factory):
     import torch
     a, b = S.volume("u8", 3, 1), S.volume("u8", 3, 2)
     up, hs = torch.cuda.Stream(), torch.cuda.Stream()
-    work = torch.zeros(1 << 28, dtype=torch.uint8, device="cuda")
+    work = out_buffer(1 << 28, np.uint8)
     d, g = dev(b[0]), dev(b[1])
-    cnt = torch.full((65536,), -1, dtype=torch.int32, device="cuda")
+    cnt = out_buffer(65536, np.int32, -1)
     R = context(gpu_renderer_factory, a[0], a[1], cap=2)
     try:
-        torch.cuda.synchronize()
+        torch.cuda.synchronize()                            # nothing is in flight when the two streams start
         busy(up, work)
         R.upload_timestep_device(5, d.data_ptr(), S.DIMS, 3, 0, g.data_ptr(), dmode="VGH", stream=stream_arg(up))
         R.hist2d_step_device(cnt.data_ptr(), 5, stream_arg(hs))        # no host wait in between
-        hs.synchronize()
+        hs.synchronize()                                    # the histogram's stream alone: it waited for the upload on the device
         same(cnt.cpu().numpy().view(np.uint32).reshape(256, 256), S.counts(b[0]))
-        torch.cuda.synchronize()
+        torch.cuda.synchronize()                            # stream `up` has ended before its work buffer goes
     finally:
         R.close()
 
@@ -277,17 +203,17 @@ def test_an_upload_into_the_slot_waits_for_the_histogram(gpu_renderer_factory):
     import torch
     a, b, c = (S.volume("f32", 2, s) for s in (1, 2, 3))
     hs, up = torch.cuda.Stream(), torch.cuda.Stream()
-    work = torch.zeros(1 << 28, dtype=torch.uint8, device="cuda")
+    work = out_buffer(1 << 28, np.uint8)
     d, g = dev(c[0]), dev(c[1])
-    cnt = torch.full((65536,), -1, dtype=torch.int32, device="cuda")
+    cnt = out_buffer(65536, np.int32, -1)
     R = context(gpu_renderer_factory, a[0], a[1], cap=2)
     try:
         R.upload_timestep(5, b[0], b[1], dmode="V1G")
-        torch.cuda.synchronize()
+        torch.cuda.synchronize()                            # nothing is in flight when the two streams start
         busy(hs, work)
         R.hist2d_step_device(cnt.data_ptr(), 5, stream_arg(hs))
         R.upload_timestep_device(5, d.data_ptr(), S.DIMS, 2, 1, g.data_ptr(), dmode="V1G", stream=stream_arg(up))
-        torch.cuda.synchronize()
+        torch.cuda.synchronize()                            # both streams: read-back
         same(cnt.cpu().numpy().view(np.uint32).reshape(256, 256), S.counts(b[0]), "the step the histogram was asked of")
         same(R.hist2d_step(5), S.counts(c[0]), "the step that replaced it")
     finally:
@@ -300,12 +226,12 @@ def test_device_counts_are_overwritten(gpu_renderer_factory):
     import torch
     data, grad = S.volume("u16", 2)
     want = S.counts(data)
-    cnt = torch.full((65536,), 0x5a5a5a5a, dtype=torch.int32, device="cuda")
+    cnt = out_buffer(65536, np.int32, 0x5a5a5a5a)
     R = context(gpu_renderer_factory, data, grad)
     try:
         for turn in range(2):
             R.hist2d_step_device(cnt.data_ptr())
-            torch.cuda.synchronize()
+            torch.cuda.synchronize()                        # the context's stream: read-back
             same(cnt.cpu().numpy().view(np.uint32).reshape(256, 256), want, "call %d" % turn)
     finally:
         R.close()
@@ -314,8 +240,7 @@ def test_device_counts_are_overwritten(gpu_renderer_factory):
 # ---- 8. refusals
 
 def test_refusals(gpu_renderer_factory, smk):
-    import torch
-    cnt = torch.zeros(65536, dtype=torch.int32, device="cuda")
+    cnt = out_buffer(65536, np.int32)
     R = gpu_renderer_factory()
     try:
         with pytest.raises(smk.SmkError, match="smk_hist2d_step: no volume"):

@@ -5,7 +5,6 @@ smk_quantize_u16_device) in the same test -- voxels and normals as smk_download_
 and the slice-ring kernel, the step histogram.  Where the fields are finite and their summed gradient is not zero everywhere
 the arrays are also the restatement's (tests/_step_merge_ref.py, qualified by tests/test_step_merge_cpu.py).  Volumes are
 37 x 13 x 11 and 70 x 21 x 19 voxels, the kernels' tile sizes and a thin 5 x 190 x 175."""
-import ctypes
 import os
 import subprocess
 
@@ -13,107 +12,43 @@ import numpy as np
 import pytest
 
 import _step_merge_ref as M
-import _step_read_ref as D
 import _tblend_ref as T
+from _gpu_mem import dev_ptr as dev, field_ptrs, out_buffer, stream_arg
+from _step_gpu import MODE, RAN, Undisturbed, fresh_download, same_bits as same, scene_context, series
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MODE = {2: "V1G", 3: "V2G", 4: "V3G"}  # the data mode mergeMV -addG gives nelts channels
 W = 0.37
-
-
-def same(got, want, what=""):
-    got, want = D.bits(got), D.bits(want)
-    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.dtype, want.dtype, got.shape, want.shape)
-    bad = np.argwhere(got != want)
-    assert not len(bad), "%s: %d of %d values differ, first at %s: got %#x, want %#x" % (
-        what, len(bad), got.size, tuple(bad[0]), int(got[tuple(bad[0])]), int(want[tuple(bad[0])]))
-
-
-def dev(a, shift=0):
-    """(device address, the torch tensor that owns it) of the array's bytes, `shift` bytes behind the allocation's start"""
-    import torch
-    b = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
-    t = torch.zeros(b.size + shift, dtype=torch.uint8, device="cuda")
-    t[shift:] = torch.from_numpy(b.copy()).cuda()
-    torch.cuda.synchronize()
-    return t.data_ptr() + shift, t
-
-
-def stream_arg(s):
-    return ctypes.c_void_p(s.cuda_stream)
-
-
-def series(factory, steps, cap=4):
-    """a context whose step 0 (current), 1, ... are `steps` = ((data, grad), ...); grad None: no normals"""
-    R = factory()
-    try:
-        R.set_timestep_cache(cap)
-        ne = steps[0][0].shape[-1]
-        R.upload_volume(steps[0][0], steps[0][1], dmode=MODE[ne])
-        for t, (data, grad) in enumerate(steps[1:], 1):
-            R.upload_timestep(t, data, grad, dmode=MODE[ne])
-    except Exception:
-        R.close()
-        raise
-    return R
 
 
 def recipe(R, F):
     """what the recipe's device entries make of the fields F [z][y][x][nf] (u8, u16 or f32) for a ring of F's type:
     (data [z][y][x][nf + 1], normals) as host arrays, made on the device through context R"""
-    import torch
     F = np.ascontiguousarray(F)
     nz, ny, nx, nf = F.shape
     dims, n = (nx, ny, nz), nx * ny * nz
-    nrm = torch.zeros(n * 3, dtype=torch.uint8, device="cuda")
+    nrm = out_buffer(n * 3, np.uint8)                       # (the entries run on the context's stream)
     if F.dtype == np.uint8:
         pf, keep = dev(F)
-        out = torch.zeros(n * (nf + 1), dtype=torch.uint8, device="cuda")
-        torch.cuda.synchronize()                            # (the entries run on the context's stream and wait for it)
+        out = out_buffer(n * (nf + 1), np.uint8)
         R.merge_fields_device(pf, nf, dims, out.data_ptr(), nrm.data_ptr())
         data = out.cpu().numpy().reshape(nz, ny, nx, nf + 1)
     else:
         pf, keep = dev(F.astype(np.float32))                # u16: F = (float)v, unscaled
-        out = torch.zeros(n * (nf + 1), dtype=torch.float32, device="cuda")
-        torch.cuda.synchronize()
+        out = out_buffer(n * (nf + 1), np.float32)
         R.merge_fields_f32_device(pf, nf, dims, out.data_ptr(), nrm.data_ptr())
         data = out.cpu().numpy().reshape(nz, ny, nx, nf + 1)
         if F.dtype == np.uint16:
             g = out.view(n, nf + 1)[:, nf].contiguous()     # G, a strided device copy
-            q = torch.zeros(n * 2, dtype=torch.uint8, device="cuda")
-            torch.cuda.synchronize()
+            q = out_buffer(n * 2, np.uint8)                 # (it waits for that copy too)
             R.quantize_u16_device(g.data_ptr(), n, q.data_ptr())
             gq = q.cpu().numpy().view(np.uint16).reshape(nz, ny, nx, 1)
             data = np.ascontiguousarray(np.concatenate([F, gq], -1))
     return data, nrm.cpu().numpy().reshape(nz, ny, nx, 3)
 
 
-def fresh_download(factory, data, nrm, normals=True):
-    """the download of a fresh context that uploaded (data, nrm) from device memory"""
-    nz, ny, nx, ne = data.shape
-    F = factory()
-    try:
-        pd, k0 = dev(data)
-        pn, k1 = dev(nrm)
-        F.upload_volume_device(pd, (nx, ny, nz), ne, M.CODE[M.RING_OF[data.dtype]], pn if normals else None, dmode=MODE[ne])
-        return F.download_timestep()
-    finally:
-        F.close()
-
-
 def recipe_download(factory, R, F, normals=True):
-    return fresh_download(factory, *recipe(R, F), normals=normals)
-
-
-def field_ptrs(F, shift=0):
-    """(device addresses, owners) of the fields of F as separate dense arrays, as a simulation holds them"""
-    ptrs, keep = [], []
-    for e in range(F.shape[-1]):
-        p, k = dev(np.ascontiguousarray(F[..., e]), shift)
-        ptrs.append(p)
-        keep.append(k)
-    return ptrs, keep
+    return fresh_download(factory, *recipe(R, F), MODE, normals=normals)
 
 
 def both_forms(factory, F, normals=True, cap=3):
@@ -122,7 +57,7 @@ def both_forms(factory, F, normals=True, cap=3):
     nz, ny, nx, nf = F.shape
     sdata, snrm = M.source_step(F)
     src = M.downloaded(sdata, snrm, normals)
-    R = series(factory, ((sdata, snrm if normals else None),), cap=cap)
+    R = series(factory, ((sdata, snrm if normals else None),), cap=cap, dm=MODE)
     try:
         R.merge_timestep(0, 1)
         assert R.timesteps() == (0, [0, 1])                 # (a merged step does not become current)
@@ -228,7 +163,6 @@ FRAMES = (("u8", 2, 1), ("u8", 2, 2), ("u16", 2, 1), ("f32", 2, 1), ("f32", 3, 1
 @pytest.mark.parametrize("ring, nf, kernel", FRAMES, ids=["%s-nf%d-%s" % (r, n, {1: "gather", 2: "slice-ring"}[k]) for r, n, k in FRAMES])
 def test_a_merged_step_renders_and_counts_like_the_recipes_upload(gpu_renderer_factory, ring, nf, kernel):
     from _scenes import push_scene
-    from test_gpu_tblend import RAN
     dims = M.DIMS[1]
     F = M.fields(ring, nf, dims)
     sdata, snrm = M.source_step(F)
@@ -274,7 +208,7 @@ def test_in_place_overwrite_of_a_cached_output_that_is_current(gpu_renderer_fact
     Fa, Fb = M.fields("u8", 2, dims, 0), M.fields("u8", 2, dims, 1)
     a, b = M.source_step(Fa), M.source_step(Fb, 6)
     wa, wb = M.downloaded(*M.merge(O, Fa)), M.downloaded(*M.merge(O, Fb))
-    R = series(gpu_renderer_factory, (a, b), cap=3)
+    R = series(gpu_renderer_factory, (a, b), cap=3, dm=MODE)
     try:
         R.merge_timestep(1, 5)
         assert R.timesteps() == (0, [0, 1, 5])
@@ -307,10 +241,10 @@ def test_merge_on_a_side_stream_behind_a_blend_and_a_source_overwritten(gpu_rend
         side, up = torch.cuda.Stream(), torch.cuda.Stream()
         pc, kc = dev(c[0])
         pg, kg = dev(c[1])
-        work = torch.zeros(1 << 22, dtype=torch.float32, device="cuda")
-        R = series(gpu_renderer_factory, (a, b), cap=4)
+        work = out_buffer(1 << 22, np.float32)
+        R = series(gpu_renderer_factory, (a, b), cap=4, dm=MODE)
         try:
-            torch.cuda.synchronize()
+            torch.cuda.synchronize()                        # nothing is in flight when the two streams start
             with torch.cuda.stream(side):                   # work in front of the blend: nothing behind it has started yet
                 for _ in range(24):
                     work.add_(1)
@@ -318,7 +252,7 @@ def test_merge_on_a_side_stream_behind_a_blend_and_a_source_overwritten(gpu_rend
             R.merge_timestep(2, 3, stream=stream_arg(side))  # directly behind the blend, no host wait
             R.upload_timestep_device(2, pc, dims, nf + 1, M.CODE[ring], pg, dmode=MODE[nf + 1],
                                      stream=stream_arg(up))  # the source slot overwritten: behind the merge's reads
-            torch.cuda.synchronize()
+            torch.cuda.synchronize()                        # both streams have ended: the host forms below read their results
             got = R.download_timestep(3)
             same(R.download_timestep(2)[0], M.downloaded(*c)[0], "the new step 2")
             R.blend_timesteps(0, 1, W, 2)                   # the synchronous results: the blend again, and the recipe of its fields
@@ -333,14 +267,12 @@ def test_merge_on_a_side_stream_behind_a_blend_and_a_source_overwritten(gpu_rend
 
 
 def test_refusals(gpu_renderer_factory, smk, O):
-    import torch
-    from test_gpu_step_derive import Undisturbed, scene_context
     dims = M.SMALL
     nx, ny, nz = dims
     F = M.fields("u8", 2, dims)
     a = M.source_step(F)
     b = M.source_step(M.fields("u8", 2, dims, 1), 6)
-    buf = torch.zeros(nx * ny * nz * 4 + 64, dtype=torch.uint8, device="cuda")
+    buf = out_buffer(nx * ny * nz * 4 + 64, np.uint8)
     p0, p1 = buf.data_ptr(), buf.data_ptr() + nx * ny * nz
     R = gpu_renderer_factory()
     try:

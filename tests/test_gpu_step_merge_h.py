@@ -13,7 +13,8 @@ import pytest
 import _step_merge_h_ref as H
 import _step_merge_ref as M
 import _tblend_ref as T
-from test_gpu_step_merge import dev, field_ptrs, same, stream_arg
+from _gpu_mem import dev_ptr as dev, field_ptrs, out_buffer, stream_arg
+from _step_gpu import RAN, Undisturbed, context, same_bits as same, scene_context
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -22,44 +23,33 @@ WITH_H = (("u8", 1), ("u8", 2), ("u16", 1), ("f32", 1), ("f32", 2))       # ever
 BLUR_ONLY = (("u8", 3), ("u16", 2), ("f32", 3))                           # a voxel has no room for H: add_h 0
 
 
-def context(factory, data, grad, add_h, cap=4):
-    """a context whose step 0 (current) is (data, grad); grad None: no normals"""
-    R = factory()
-    try:
-        R.set_timestep_cache(cap)
-        R.upload_volume(data, grad, dmode=H.MODE[(data.shape[-1] - 1 - add_h, add_h)])
-    except Exception:
-        R.close()
-        raise
-    return R
+def mode(data, add_h):
+    """the data mode of a step of fields, G and (add_h) H"""
+    return H.MODE[(data.shape[-1] - 1 - add_h, add_h)]
 
 
 def recipe(R, F, add_h, compat, blur):
     """what the preparation entries make of the fields F [z][y][x][nf] (u8, u16 or f32) for a ring of F's type:
     (data [z][y][x][nf + 1 + add_h], normals) as host arrays, made on the device through context R"""
-    import torch
     F = np.ascontiguousarray(F)
     nz, ny, nx, nf = F.shape
     dims, n, ne = (nx, ny, nz), nx * ny * nz, nf + 1 + add_h
-    nrm = torch.zeros(n * 3, dtype=torch.uint8, device="cuda")
+    nrm = out_buffer(n * 3, np.uint8)                       # (the entries run on the context's stream)
     if F.dtype == np.uint8:
         pf, keep = dev(F)
-        out = torch.zeros(n * ne, dtype=torch.uint8, device="cuda")
-        torch.cuda.synchronize()                            # (the entries run on the context's stream and wait for it)
+        out = out_buffer(n * ne, np.uint8)
         R.merge_fields_h_device(pf, nf, dims, out.data_ptr(), nrm.data_ptr(), add_h, compat, blur)
         data = out.cpu().numpy().reshape(nz, ny, nx, ne)
     else:
         pf, keep = dev(F.astype(np.float32))                # u16: F = (float)v, unscaled
-        out = torch.zeros(n * ne, dtype=torch.float32, device="cuda")
-        torch.cuda.synchronize()
+        out = out_buffer(n * ne, np.float32)
         R.merge_fields_h_f32_device(pf, nf, dims, out.data_ptr(), nrm.data_ptr(), add_h, compat, blur)
         data = out.cpu().numpy().reshape(nz, ny, nx, ne)
         if F.dtype == np.uint16:
             chans = [F]
             for k in range(nf, ne):                         # G, then H: strided device copies, quantised
                 g = out.view(n, ne)[:, k].contiguous()
-                q = torch.zeros(n * 2, dtype=torch.uint8, device="cuda")
-                torch.cuda.synchronize()
+                q = out_buffer(n * 2, np.uint8)             # (it waits for that copy too)
                 R.quantize_u16_device(g.data_ptr(), n, q.data_ptr())
                 chans.append(q.cpu().numpy().view(np.uint16).reshape(nz, ny, nx, 1))
             data = np.ascontiguousarray(np.concatenate(chans, -1))
@@ -83,7 +73,7 @@ def both_forms(factory, F, add_h, compat, blur, normals=True):
     nz, ny, nx, nf = F.shape
     sdata, snrm = H.source_step(F, add_h)
     src = M.downloaded(sdata, snrm, normals)
-    R = context(factory, sdata, snrm if normals else None, add_h)
+    R = context(factory, sdata, snrm if normals else None, cap=4, dm=mode(sdata, add_h))
     try:
         R.merge_timestep_h(0, 1, add_h, compat, blur)
         assert R.timesteps() == (0, [0, 1])                 # (a merged step does not become current)
@@ -144,12 +134,11 @@ def test_every_shape_with_h_and_blur(gpu_renderer_factory, ring):
 
 @pytest.mark.parametrize("ring, nf", (("u8", 3), ("u16", 2), ("f32", 3), ("f32", 1)))
 def test_without_h_and_blur_the_old_entries_bits(gpu_renderer_factory, ring, nf):
-    import torch
     dims = H.SHAPES[1]
     nx, ny, nz = dims
     F = H.fields(ring, nf, dims)
     sdata, snrm = H.source_step(F, 0)
-    R = context(gpu_renderer_factory, sdata, snrm, 0, cap=5)
+    R = context(gpu_renderer_factory, sdata, snrm, cap=5, dm=mode(sdata, 0))
     try:
         R.merge_timestep(0, 1)
         R.merge_timestep_h(0, 2, 0, 1, 0)
@@ -164,11 +153,9 @@ def test_without_h_and_blur_the_old_entries_bits(gpu_renderer_factory, ring, nf)
         if ring != "u16":                                   # the preparation entries, array for array
             n = nx * ny * nz
             Fd = F if ring == "u8" else F.astype(np.float32)
-            tdt = torch.uint8 if ring == "u8" else torch.float32
             pf, k0 = dev(Fd)
-            outs = [torch.zeros(n * (nf + 1), dtype=tdt, device="cuda") for _ in range(2)]
-            nrms = [torch.zeros(n * 3, dtype=torch.uint8, device="cuda") for _ in range(2)]
-            torch.cuda.synchronize()
+            outs = [out_buffer(n * (nf + 1), Fd.dtype) for _ in range(2)]
+            nrms = [out_buffer(n * 3, np.uint8) for _ in range(2)]
             old, new = (R.merge_fields_device, R.merge_fields_h_device) if ring == "u8" else (R.merge_fields_f32_device, R.merge_fields_h_f32_device)
             old(pf, nf, dims, outs[0].data_ptr(), nrms[0].data_ptr())
             new(pf, nf, dims, outs[1].data_ptr(), nrms[1].data_ptr(), 0, 1, 0)
@@ -236,7 +223,6 @@ FRAMES = (("u8", 2, 1), ("u8", 2, 2), ("u16", 1, 1), ("f32", 2, 1))
 @pytest.mark.parametrize("ring, nf, kernel", FRAMES, ids=["%s-nf%d-%s" % (r, n, {1: "gather", 2: "slice-ring"}[k]) for r, n, k in FRAMES])
 def test_a_merged_step_renders_and_counts_like_the_recipes_upload(gpu_renderer_factory, ring, nf, kernel):
     from _scenes import push_scene
-    from test_gpu_tblend import RAN
     dims = H.MAIN
     F = H.fields(ring, nf, dims)
     sdata, snrm = H.source_step(F, 1)
@@ -282,7 +268,7 @@ def test_in_place_overwrite_of_a_cached_output_that_is_current(gpu_renderer_fact
     Fa, Fb = H.fields("u8", 2, dims, 0), H.fields("u8", 2, dims, 1)
     a, b = H.source_step(Fa, 1), H.source_step(Fb, 1, 6)
     wa, wb = H.downloaded(*H.merge_h(Fa, 1, 1, 1)), H.downloaded(*H.merge_h(Fb, 1, 1, 1))
-    R = context(gpu_renderer_factory, a[0], a[1], 1, cap=3)
+    R = context(gpu_renderer_factory, a[0], a[1], cap=3, dm=mode(a[0], 1))
     try:
         R.upload_timestep(1, b[0], b[1], dmode="V2GH")
         R.merge_timestep_h(1, 5, 1, 1, 1)
@@ -316,11 +302,11 @@ def test_merge_on_a_side_stream_behind_a_blend_and_a_source_overwritten(gpu_rend
         side, up = torch.cuda.Stream(), torch.cuda.Stream()
         pc, kc = dev(c[0])
         pg, kg = dev(c[1])
-        work = torch.zeros(1 << 22, dtype=torch.float32, device="cuda")
-        R = context(gpu_renderer_factory, a[0], a[1], 1, cap=5)
+        work = out_buffer(1 << 22, np.float32)
+        R = context(gpu_renderer_factory, a[0], a[1], cap=5, dm=mode(a[0], 1))
         try:
             R.upload_timestep(1, b[0], b[1], dmode="V2GH")
-            torch.cuda.synchronize()
+            torch.cuda.synchronize()                        # nothing is in flight when the two streams start
             with torch.cuda.stream(side):                   # work in front of the blend: nothing behind it has started yet
                 for _ in range(24):
                     work.add_(1)
@@ -328,7 +314,7 @@ def test_merge_on_a_side_stream_behind_a_blend_and_a_source_overwritten(gpu_rend
             R.merge_timestep_h(2, 3, 1, 1, 1, stream=stream_arg(side))   # directly behind the blend, no host wait
             R.upload_timestep_device(2, pc, dims, nf + 2, H.CODE[ring], pg, dmode="V2GH",
                                      stream=stream_arg(up))  # the source slot overwritten: behind the merge's reads
-            torch.cuda.synchronize()
+            torch.cuda.synchronize()                        # both streams have ended: the host forms below read their results
             got = R.download_timestep(3)
             same(R.download_timestep(2)[0], M.downloaded(*c)[0], "the new step 2")
             R.blend_timesteps(0, 1, W, 2)                   # the synchronous results: the blend again, and the recipe of its fields
@@ -346,14 +332,12 @@ def test_merge_on_a_side_stream_behind_a_blend_and_a_source_overwritten(gpu_rend
 
 
 def test_refusals(gpu_renderer_factory, smk):
-    import torch
-    from test_gpu_step_derive import Undisturbed, scene_context
     dims = M.SMALL
     nx, ny, nz = dims
     F = H.fields("u8", 2, dims)
     a = H.source_step(F, 1)
     b = H.source_step(H.fields("u8", 2, dims, 1), 1, 6)
-    buf = torch.zeros(nx * ny * nz * 4 + 64, dtype=torch.uint8, device="cuda")
+    buf = out_buffer(nx * ny * nz * 4 + 64, np.uint8)
     p0, p1 = buf.data_ptr(), buf.data_ptr() + nx * ny * nz
     mt, up = "smk_merge_timestep_h: ", "smk_upload_timestep_fields_h_device: "
     R = gpu_renderer_factory()

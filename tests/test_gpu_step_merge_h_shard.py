@@ -12,12 +12,11 @@ import pytest
 import _step_block_ref as B
 import _step_merge_h_ref as H
 import _step_merge_h_shard_ref as R
-import _step_read_ref as D
 import _step_shard_ref as S
 import _tblend_ref as T
-import test_gpu_step_shard as G
-from test_gpu_step_block import dev, hand_over
-from test_gpu_step_shard import same, fsz, close, words_buf, SORT_LAST_TOL
+from _gpu_mem import dev_ptr as dev, merged, words_buf
+from _step_gpu import (RAN, SORT_LAST_TOL, UndisturbedHalos, close, declared, flags_of, fsz, probe_at, rank_context, ranks_declared,
+                       ranks_of, run_cut, same_bits as same)
 
 pytestmark = pytest.mark.gpu
 CODE = H.CODE
@@ -28,56 +27,11 @@ def mode(nelts, add_h):
     return H.MODE[(nelts - 1 - add_h, add_h)]
 
 
-def context(factory, dims, data, grad, add_h, rank=0, nranks=1, halo=1, cap=4, opts=()):
-    """a context (one rank of `nranks`, or unsharded) whose step 0 is (data, grad); grad None: a context without normals"""
-    C = factory()
-    try:
-        if nranks > 1:
-            C.set_shard(rank, nranks)
-            C.set_option("halo", halo)
-        for k, v in opts:
-            C.set_option(k, v)
-        C.set_timestep_cache(cap)
-        C.upload_volume(data, grad, fsize=fsz(dims), dmode=mode(data.shape[-1], add_h))
-    except Exception:
-        C.close()
-        raise
-    return C
-
-
-def ranks_of(factory, dims, data, grad, add_h, nranks, halo, cap=4, opts=()):
-    rs = []
-    try:
-        for r in range(nranks):
-            rs.append(context(factory, dims, data, grad, add_h, r, nranks, halo, cap, opts))
-    except Exception:
-        close(rs)
-        raise
-    return rs
-
-
-def declared(factory, dims, ring, nelts, add_h, rank=0, nranks=1, halo=1, normals=True, cap=4, opts=()):
-    C = factory()
-    try:
-        if nranks > 1:
-            C.set_shard(rank, nranks)
-            C.set_option("halo", halo)
-        for k, v in opts:
-            C.set_option(k, v)
-        C.set_timestep_cache(cap)
-        C.declare_volume(dims, nelts, CODE[ring], fsize=fsz(dims), dmode=mode(nelts, add_h), normals=normals)
-    except Exception:
-        C.close()
-        raise
-    return C
-
-
 def export(C, src, add_h, compat, stream=None):
     import torch
     w = words_buf()
-    torch.cuda.synchronize()
     C.step_extremes_h_device(src, w.data_ptr(), add_h=add_h, compat=compat, stream=stream)
-    torch.cuda.synchronize()
+    torch.cuda.synchronize()                                # the export ran on the context's stream, or the caller's: read-back
     return w.cpu().numpy()[0]
 
 
@@ -92,7 +46,7 @@ def reference(factory, case, ring, nf, add_h, blur, compat, normals=True):
         dims = R.CASES[case][0]
         data, grad = R.source(case, ring, nf, add_h)
         grad = grad if normals else None
-        U = context(factory, dims, data, grad, add_h)
+        U = rank_context(factory, dims, data, grad, mode(data.shape[-1], add_h))
         try:
             U.merge_timestep_h(0, 1, add_h, compat, blur)
             got = U.download_timestep(1)
@@ -121,12 +75,12 @@ def test_the_ranks_words_combine_to_the_unsharded_words(gpu_renderer_factory, ca
             continue
         seen.add((nf, add_h, compat))
         data, grad = R.source(case, ring, nf, add_h)
-        U = context(gpu_renderer_factory, dims, data, grad, add_h)
+        U = rank_context(gpu_renderer_factory, dims, data, grad, mode(data.shape[-1], add_h))
         try:
             want = export(U, 0, add_h, compat)
         finally:
             U.close()
-        rs = ranks_of(gpu_renderer_factory, dims, data, grad, add_h, nranks, halo)
+        rs = ranks_of(gpu_renderer_factory, dims, data, grad, mode(data.shape[-1], add_h), nranks, halo)
         try:
             words = [export(C, 0, add_h, compat) for C in rs]
         finally:
@@ -154,20 +108,18 @@ def test_export_and_write_on_an_unsharded_context_is_the_one_call_entry(gpu_rend
     """both source forms: a resident step, and dense fields handed over as a whole-volume block"""
     import torch
     from _scenes import push_scene
-    from test_gpu_tblend import RAN
     dims = (37, 13, 11)                                     # (odd x and y: a pad column and row of 8-byte voxels)
     F = H.fields(ring, nf, dims, 0)
     data, grad = H.source_step(F, add_h)
     sc = T.scene(np.ascontiguousarray(data[..., :3]), grad)
     held = [dev(np.ascontiguousarray(F[..., e])) for e in range(nf)]
     ptrs = [h[0] for h in held]
-    C = context(gpu_renderer_factory, dims, data, grad, add_h, cap=6, opts=(("kernel", kernel),))
+    C = rank_context(gpu_renderer_factory, dims, data, grad, mode(data.shape[-1], add_h), cap=6, opts=(("kernel", kernel),))
     try:
         push_scene(C, sc, upload=False)
         C.merge_timestep_h(0, 1, add_h, 1, 1)
         C.upload_timestep_fields_h_device(4, ptrs, CODE[ring], dims, add_h, 1, 1)
         w = words_buf(2)
-        torch.cuda.synchronize()
         C.step_extremes_h_device(0, w[0].data_ptr(), add_h=add_h)
         C.merge_timestep_h_shard(0, 2, w[0].data_ptr(), add_h=add_h, blur=1)
         blk = smk.smk_block((0, 0, 0), dims)
@@ -204,7 +156,7 @@ def check_ranks(factory, case, ring, nf, add_h, blur, compat, normals=True):
     dims, nranks, halo = R.CASES[case]
     data, grad, wdata, wgrad, wprobe, whist = reference(factory, case, ring, nf, add_h, blur, compat, normals)
     what = "nf %d add_h %d blur %d compat %d" % (nf, add_h, blur, compat)
-    rs = ranks_of(factory, dims, data, grad, add_h, nranks, halo)
+    rs = ranks_of(factory, dims, data, grad, mode(data.shape[-1], add_h), nranks, halo)
     try:
         sortlast.stencil_timestep_local(rs, "merge_h", 0, 1, compat=compat, blur=blur, add_h=add_h)
         parts, gparts, hist, rim_seen = [], [], np.zeros((256, 256), np.int64), False
@@ -227,7 +179,7 @@ def check_ranks(factory, case, ring, nf, add_h, blur, compat, normals=True):
             inside = np.all((cells >= np.array(lo)) & (cells + 1 < np.array(hi)), -1)
             assert np.array_equal(ok, inside), "%s rank %d: %d cells answered, %d lie in the valid box" % (what, r, ok.sum(), inside.sum())
             assert (S.straddles(cells, g0, g1) & inside).any(), "a cell with a corner in the halo"
-            wraw, wnrm = G.probe_at(wprobe, dims, cells[inside])
+            wraw, wnrm = probe_at(wprobe, dims, cells[inside])
             same(raw[inside], wraw, "%s rank %d: the valid box's voxels" % (what, r))
             same(nrm[inside], wnrm, "%s rank %d: the valid box's normals" % (what, r))
             assert not raw[~inside].any() and not nrm[~inside].any()
@@ -245,14 +197,6 @@ def check_ranks(factory, case, ring, nf, add_h, blur, compat, normals=True):
 def test_the_ranks_regions_and_halos_are_the_unsharded_step(gpu_renderer_factory, case, ring):
     for nf, add_h, blur, compat in R.layouts(case, ring):
         check_ranks(gpu_renderer_factory, case, ring, nf, add_h, blur, compat)
-
-
-def flags_of(C, sc, step, table):
-    from _scenes import push_scene
-    push_scene(C, sc, upload=False)
-    C.select_timestep(step)
-    C.set_tf2d(table, None)
-    return C.brick_flags()[0].copy()
 
 
 @pytest.mark.parametrize("ring, nf, add_h", [("u8", 2, 1), ("u16", 1, 1), ("f32", 2, 1), ("f32", 2, 0)])
@@ -281,23 +225,23 @@ def test_the_rim_is_zeros_with_normal_128(gpu_renderer_factory, ring, nf, add_h)
         for fill, gfill in ((0, 128), (top, 7)):
             d, g = wdata.copy(), wgrad.copy()
             d[outside], g[outside] = fill, gfill
-            U = context(gpu_renderer_factory, dims, d, g, add_h, r, nranks, halo, opts=opts)
+            U = rank_context(gpu_renderer_factory, dims, d, g, mode(d.shape[-1], add_h), r, nranks, halo, opts=opts)
             try:
-                want.append(flags_of(U, sc, 0, table))
+                want.append(flags_of(U, sc, 0, [table])[0])
             finally:
                 U.close()
-        C = context(gpu_renderer_factory, dims, data, grad, add_h, r, nranks, halo, cap=3, opts=opts)
+        C = rank_context(gpu_renderer_factory, dims, data, grad, mode(ne, add_h), r, nranks, halo, cap=3, opts=opts)
         try:
             import torch
             C.upload_timestep(1, stale, sgrad, fsize=fsz(dims), dmode=mode(ne, add_h))
-            before = flags_of(C, sc, 1, table)
+            before = flags_of(C, sc, 1, [table])[0]
             w = words_buf()
             wu = export_unsharded(gpu_renderer_factory, case, ring, nf, add_h, compat)
             w[0] = torch.tensor(wu, dtype=torch.int32)
-            torch.cuda.synchronize()
+            torch.cuda.synchronize()                        # the words are on the device before the context's stream reads them
             C.merge_timestep_h_shard(0, 1, w.data_ptr(), add_h=add_h, compat=compat, blur=blur)
             assert C.timesteps() == (1, [0, 1]) and C.timestep_halo(1) == halo - REACH     # (the shown step, overwritten in place)
-            got = flags_of(C, sc, 1, table)
+            got = flags_of(C, sc, 1, [table])[0]
         finally:
             C.close()
         assert before.all(), "the stale step flags every brick"
@@ -313,7 +257,7 @@ def export_unsharded(factory, case, ring, nf, add_h, compat):
     key = (case, ring, nf, add_h, compat)
     if key not in _WORDS:
         data, grad = R.source(case, ring, nf, add_h)
-        U = context(factory, R.CASES[case][0], data, grad, add_h)
+        U = rank_context(factory, R.CASES[case][0], data, grad, mode(data.shape[-1], add_h))
         try:
             _WORDS[key] = export(U, 0, add_h, compat)
         finally:
@@ -332,7 +276,7 @@ def block_reference(factory, case, ring, nf, add_h, blur, compat, normals=True):
         F = R.fields(case, ring, nf)
         arr = [np.ascontiguousarray(F[..., e]) for e in range(nf)]
         held = [dev(a) for a in arr]
-        U = declared(factory, dims, ring, nf + 1 + add_h, add_h, normals=normals)
+        U = declared(factory, dims, ring, nf + 1 + add_h, mode(nf + 1 + add_h, add_h), normals=normals)
         try:
             U.upload_timestep_fields_h_device(1, [h[0] for h in held], CODE[ring], dims, add_h, compat, blur)
             got = U.download_timestep(1)
@@ -343,20 +287,6 @@ def block_reference(factory, case, ring, nf, add_h, blur, compat, normals=True):
         del held
         _REF[key] = (arr, got[0], got[1], probe)
     return _REF[key]
-
-
-def run_cut(smk, rs, cuts, ring, arr, out, add_h, compat, blur, stream=None):
-    from simian_spacemonkey_amd import sortlast
-    keep, blocks = [], []
-    for c in cuts:
-        ptrs = []
-        for a in arr:
-            p, k, blk = hand_over(smk, c, a, ring)          # (a view: everything outside it is poison)
-            ptrs.append(p)
-            keep.append(k)
-        blocks.append((ptrs, CODE[ring], blk))
-    words = sortlast.stencil_block_local(rs, "merge_h", blocks, out, compat=compat, blur=blur, stream=stream, add_h=add_h)
-    return keep, words
 
 
 def cuts_of(case, ring, which):
@@ -374,12 +304,10 @@ def check_blocks(factory, smk, case, ring, nf, add_h, blur, compat, normals=True
         if not group:
             continue
         all_cuts = [cuts_of(case, ring, wc) for wc in group]
-        rs = []
+        rs = ranks_declared(factory, dims, ring, nf + 1 + add_h, mode(nf + 1 + add_h, add_h), all_cuts[0], normals)
         try:
-            for c in all_cuts[0]:
-                rs.append(declared(factory, dims, ring, nf + 1 + add_h, add_h, c.rank, nranks, c.option_halo, normals))
             for out, cuts in enumerate(all_cuts, 1):
-                keep, words = run_cut(smk, rs, cuts, ring, arr, out, add_h, compat, blur)
+                keep, words = run_cut(smk, rs, cuts, "merge_h", ring, ring, arr, out, compat, blur, add_h=add_h)
                 w = words.cpu().numpy()
                 assert np.array_equal(w[nranks], wwords), (w, wwords)
                 parts, gparts = [], []
@@ -397,7 +325,7 @@ def check_blocks(factory, smk, case, ring, nf, add_h, blur, compat, normals=True
                     inside = np.all((cells >= np.array(c.vlo)) & (cells + 1 < np.array(c.vhi)), -1)
                     assert np.array_equal(ok, inside), "%s: %d cells answered, %d lie in the valid box" % (what, ok.sum(), inside.sum())
                     assert (S.straddles(cells, c.g0, c.g1) & inside).any()
-                    wraw, wnrm = G.probe_at(wprobe, dims, cells[inside])
+                    wraw, wnrm = probe_at(wprobe, dims, cells[inside])
                     same(raw[inside], wraw, what + ": the valid box's voxels")
                     same(nrm[inside], wnrm, what + ": the valid box's normals")
                 same(S.place(dims, wdata.shape[-1], wdata.dtype, parts), wdata, "data")
@@ -432,7 +360,6 @@ def test_a_context_without_normals(gpu_renderer_factory, smk, ring, nf, add_h):
 def test_frames_of_the_produced_step(gpu_renderer_factory, case, ring, nf, add_h, kernel):
     from _scenes import push_scene
     from simian_spacemonkey_amd import sortlast
-    from test_gpu_tblend import RAN
     dims, nranks, halo = R.CASES[case]
     data, grad, wdata, wgrad, _, _ = reference(gpu_renderer_factory, case, ring, nf, add_h, 1, 1)
     opts = (("kernel", kernel), ("slab_split", 1))
@@ -441,16 +368,16 @@ def test_frames_of_the_produced_step(gpu_renderer_factory, case, ring, nf, add_h
     def frames(rs):
         for C in rs:
             push_scene(C, sc, upload=False)
-        lay, out = G.merged(rs, sc)
+        lay, out = merged(rs, sc)
         assert all(C.last_frame_info()[0] == RAN[kernel] for C in rs) and all(C.stat("slab_failures") == 0 for C in rs)
         return lay, out
-    U = context(gpu_renderer_factory, dims, wdata, wgrad, add_h, opts=opts)
+    U = rank_context(gpu_renderer_factory, dims, wdata, wgrad, mode(wdata.shape[-1], add_h), opts=opts)
     try:
         push_scene(U, sc, upload=False)
         whole = U.render()
     finally:
         U.close()
-    rs = ranks_of(gpu_renderer_factory, dims, data, grad, add_h, nranks, halo, opts=opts)
+    rs = ranks_of(gpu_renderer_factory, dims, data, grad, mode(data.shape[-1], add_h), nranks, halo, opts=opts)
     try:
         frames(rs)                                          # (the source rendered first: flags and plans of another step exist)
         keep = sortlast.stencil_timestep_local(rs, "merge_h", 0, 1, compat=1, blur=1, add_h=add_h)
@@ -478,7 +405,7 @@ def test_a_chain_of_stencils(gpu_renderer_factory, smk, ring, nranks):
     F0, F1 = H.fields(ring, 1, dims, 0), H.fields(ring, 1, dims, 1)
     (d0, g0), (d1, g1) = H.source_step(F0, 1), H.source_step(F1, 1, seed=6)
     cells = S.cells_of((0, 0, 0), dims)
-    U = context(gpu_renderer_factory, dims, d0, g0, 1, cap=6)
+    U = rank_context(gpu_renderer_factory, dims, d0, g0, "V1GH", cap=6)
     try:
         U.upload_timestep(1, d1, g1, fsize=fsz(dims), dmode="V1GH")
         U.merge_timestep_h(0, 2, 1, 1, 1)
@@ -488,7 +415,7 @@ def test_a_chain_of_stencils(gpu_renderer_factory, smk, ring, nranks):
         want = {t: U.probe_step(cells, t) for t in (2, 3, 4, 5)}
     finally:
         U.close()
-    rs = ranks_of(gpu_renderer_factory, dims, d0, g0, 1, nranks, halo, cap=6)
+    rs = ranks_of(gpu_renderer_factory, dims, d0, g0, "V1GH", nranks, halo, cap=6)
     try:
         for C in rs:
             C.upload_timestep(1, d1, g1, fsize=fsz(dims), dmode="V1GH")
@@ -508,7 +435,7 @@ def test_a_chain_of_stencils(gpu_renderer_factory, smk, ring, nranks):
                 raw, nrm, ok = C.probe_step(cs, t)
                 inside = np.all((cs >= np.array(lo)) & (cs + 1 < np.array(hi)), -1)
                 assert np.array_equal(ok, inside), "rank %d step %d: %d cells answered, %d lie in the valid box" % (r, t, ok.sum(), inside.sum())
-                wraw, wnrm = G.probe_at(want[t], dims, cs[inside])
+                wraw, wnrm = probe_at(want[t], dims, cs[inside])
                 same(raw[inside], wraw, "rank %d step %d: voxels" % (r, t))
                 same(nrm[inside], wnrm, "rank %d step %d: normals" % (r, t))
             before = C.timesteps()
@@ -538,7 +465,7 @@ def test_on_a_stream_of_the_callers_and_in_place(gpu_renderer_factory):
     sc = T.scene(np.ascontiguousarray(wdata[..., :3]), wgrad)
 
     def run(side, other):
-        rs = ranks_of(gpu_renderer_factory, dims, data, grad, add_h, nranks, halo, opts=(("kernel", 1),))
+        rs = ranks_of(gpu_renderer_factory, dims, data, grad, mode(data.shape[-1], add_h), nranks, halo, opts=(("kernel", 1),))
         try:
             for C in rs:
                 push_scene(C, sc, upload=False)
@@ -550,12 +477,12 @@ def test_on_a_stream_of_the_callers_and_in_place(gpu_renderer_factory):
                 C.upload_timestep_device(0, pd, dims, data2.shape[-1], CODE[ring], pg, fsize=fsz(dims), dmode=mode(data2.shape[-1], add_h),
                                          stream=None if other is None else ctypes.c_void_p(other.cuda_stream))
                 C.select_timestep(1)
-            lay, out = G.merged(rs, sc)
+            lay, out = merged(rs, sc)
             downs = [C.download_timestep(1) for C in rs]
             # in place: step 1 is current and cached; made again from the new step 0, it stays current
             keep.append(sortlast.stencil_timestep_local(rs, "merge_h", 0, 1, compat=1, blur=1, stream=st, add_h=add_h))
             assert all(C.timesteps() == (1, [0, 1]) for C in rs)
-            lay2, out2 = G.merged(rs, sc)
+            lay2, out2 = merged(rs, sc)
             downs += [C.download_timestep(1) for C in rs]
             del keep, k0, k1
             return lay, out, downs, out2
@@ -570,7 +497,7 @@ def test_on_a_stream_of_the_callers_and_in_place(gpu_renderer_factory):
         same(d, b, "its normals")
     g0r, g1r = R.stored_box(dims, 0, nranks, halo, ring)[:2]
     same(got[2][0][0], wdata[g0r[2]:g1r[2], g0r[1]:g1r[1], g0r[0]:g1r[0]], "rank 0's region")
-    U = context(gpu_renderer_factory, dims, data2, grad2, add_h)
+    U = rank_context(gpu_renderer_factory, dims, data2, grad2, mode(data2.shape[-1], add_h))
     try:
         U.merge_timestep_h(0, 1, add_h, 1, 1)
         again = U.download_timestep(1)[0]
@@ -581,29 +508,7 @@ def test_on_a_stream_of_the_callers_and_in_place(gpu_renderer_factory):
 
 # ---- 9. refusals
 
-class Unchanged:
-    """the refusals inside the block change nothing: smk_get_timesteps, the steps' valid halos and the frame"""
-
-    def __init__(self, C):
-        self.C = C
-
-    def state(self):
-        ids = self.C.timesteps()
-        return self.C.render(), ids, [self.C.timestep_halo(t) for t in ids[1]]
-
-    def __enter__(self):
-        self.before = self.state()
-        return self
-
-    def __exit__(self, et, ev, tb):
-        if et is None:
-            after = self.state()
-            assert np.array_equal(after[0], self.before[0]) and after[1:] == self.before[1:]
-        return False
-
-
 def test_refusals_leave_the_ring_unchanged(gpu_renderer_factory, smk):
-    import torch
     from _scenes import push_scene
     dims, nranks, ring = (37, 13, 11), 2, "u8"
     F = H.fields(ring, 2, dims, 0)
@@ -612,7 +517,6 @@ def test_refusals_leave_the_ring_unchanged(gpu_renderer_factory, smk):
     held = [dev(np.ascontiguousarray(F[..., e])) for e in range(2)]
     ptrs = [h[0] for h in held]
     w = words_buf()
-    torch.cuda.synchronize()
     p = w.data_ptr()
     whole = smk.smk_block((0, 0, 0), dims)
     entries = ("smk_step_extremes_h_device", "smk_merge_timestep_h_shard", "smk_block_extremes_h_device", "smk_upload_timestep_fields_h_block_device")
@@ -627,13 +531,13 @@ def test_refusals_leave_the_ring_unchanged(gpu_renderer_factory, smk):
         C.close()
     # a ring of two slots, both held: the source and the current step leave no slot for the output
     g0, g1, O, Dd, pad = R.stored_box(dims, 0, nranks, REACH + 1, ring)
-    C = context(gpu_renderer_factory, dims, data, grad, 1, 0, nranks, REACH + 1, cap=2, opts=(("kernel", 1),))
+    C = rank_context(gpu_renderer_factory, dims, data, grad, "V2GH", 0, nranks, REACH + 1, cap=2, opts=(("kernel", 1),))
     try:
         push_scene(C, sc, upload=False)
         C.upload_timestep(1, data, grad, fsize=fsz(dims), dmode="V2GH")
         short = smk.smk_block((0, 0, 0), (g1[0] + REACH, dims[1], dims[2]))        # a valid halo of 2
         miss = smk.smk_block((0, 0, 0), (g1[0] - 1, dims[1], dims[2]))             # C misses the region's last column
-        with Unchanged(C):
+        with UndisturbedHalos(C, downloads=False):
             for call, why in (
                     (lambda: C.step_extremes_h_device(0, p, add_h=2), "smk_step_extremes_h_device: add_h 2 is neither 0 nor 1"),
                     (lambda: C.merge_timestep_h_shard(1, 5, p, add_h=-1), "smk_merge_timestep_h_shard: add_h -1 is neither 0 nor 1"),
@@ -669,10 +573,10 @@ def test_refusals_leave_the_ring_unchanged(gpu_renderer_factory, smk):
     finally:
         C.close()
     # the source's valid halo below reach + 1: the message names 2 and 3
-    C = context(gpu_renderer_factory, dims, data, grad, 1, 0, nranks, 2, cap=3, opts=(("kernel", 1),))
+    C = rank_context(gpu_renderer_factory, dims, data, grad, "V2GH", 0, nranks, 2, cap=3, opts=(("kernel", 1),))
     try:
         push_scene(C, sc, upload=False)
-        with Unchanged(C):
+        with UndisturbedHalos(C, downloads=False):
             for call in (lambda: C.merge_timestep_h_shard(0, 1, p), lambda: C.step_extremes_h_device(0, p),
                          lambda: C.merge_timestep_h_shard(0, 1, p, add_h=1, blur=0)):
                 with pytest.raises(smk.SmkError, match=r"time step 0 \(the source\) has a valid halo of 2 voxels, the stencil reaches 2 .*>= 3 is needed"):
@@ -700,7 +604,7 @@ def test_refusals_leave_the_ring_unchanged(gpu_renderer_factory, smk):
         finally:
             C.close()
     # no slot: a ring of one step, the current one
-    one = declared(gpu_renderer_factory, dims, ring, 4, 1, cap=1)
+    one = declared(gpu_renderer_factory, dims, ring, 4, "V2GH", cap=1)
     try:
         with pytest.raises(smk.SmkError, match=r"smk_upload_timestep_fields_h_block_device: time step 5: the cache holds one step, the current one \(0\)"):
             one.upload_timestep_fields_h_block_device(5, ptrs, 0, whole, p)
@@ -708,7 +612,7 @@ def test_refusals_leave_the_ring_unchanged(gpu_renderer_factory, smk):
     finally:
         one.close()
     # a sharded context still refuses the one-call entries, now naming the two-call forms
-    C = context(gpu_renderer_factory, dims, data, grad, 1, 0, nranks, 3, cap=3)
+    C = rank_context(gpu_renderer_factory, dims, data, grad, "V2GH", 0, nranks, 3, cap=3)
     try:
         with pytest.raises(smk.SmkError, match=r"a sharded context.*reaches 2 voxels beyond region \+ halo.*three extremes.*smk_step_extremes_h_device \+ "
                                                  r"smk_merge_timestep_h_shard.*smk_block_extremes_h_device \+ smk_upload_timestep_fields_h_block_device"):

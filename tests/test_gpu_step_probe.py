@@ -12,7 +12,7 @@ import pytest
 import _step_hist_ref as S
 import _tblend_ref as T
 from _layouts import stored_box
-from test_gpu_step_hist import DMODE, context, ring
+from _step_gpu import context, ring
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -119,7 +119,7 @@ def test_shards(gpu_renderer_factory, dtype, nranks, halo):
 
 @pytest.mark.parametrize("dtype, nelts", [("u8", 3), ("f32", 3), ("u16", 3), ("f32", 4)])
 def test_steps(gpu_renderer_factory, dtype, nelts):
-    R, a, b = ring(gpu_renderer_factory, dtype, nelts)
+    R, a, b = ring(gpu_renderer_factory, S.volume(dtype, nelts, 1), S.volume(dtype, nelts, 2))
     cs = cells()
     try:
         same(R.probe_step(cs, step=1), S.probe(b[0], b[1], cs), "a cached step that is not current")

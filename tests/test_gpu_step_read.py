@@ -5,94 +5,42 @@ steps that are not current, uploaded from device memory on another stream, overw
 and the two things the entry exists for: a step that goes into a fresh context and renders the same frame, and the
 derivatives of a blended scalar made on the device.  Volumes are per-voxel noise; f32 voxels are compared as their 32-bit
 patterns.  Every output buffer of a _device call lies between 64 guard bytes of 0xA5 that must not change."""
-import ctypes
-
 import numpy as np
 import pytest
 
 import _step_hist_ref as S
 import _step_read_ref as D
 import _tblend_ref as T
+from _gpu_mem import Guarded, busy, dev_tensor as dev, out_buffer, stream_arg
 from _layouts import shuffled
+from _step_gpu import bricked, context, ring, same_bits as same
 
 pytestmark = pytest.mark.gpu
 BIG = S.DIMS                                                # 41 x 37 x 45
 
 
-def same(got, want, what=""):
-    got, want = D.bits(got), D.bits(want)
-    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.dtype, want.dtype, got.shape, want.shape)
-    bad = np.argwhere(got != want)
-    assert not len(bad), "%s: %d of %d values differ, first at %s: got %#x, want %#x" % (
-        what, len(bad), got.size, tuple(bad[0]), int(got[tuple(bad[0])]), int(want[tuple(bad[0])]))
-
-
-def context(factory, data, grad, cap=1, shard=None, halo=None):
-    R = factory()
-    try:
-        if shard:
-            R.set_shard(*shard)
-        if halo is not None:
-            R.set_option("halo", halo)
-        if cap > 1:
-            R.set_timestep_cache(cap)
-        R.upload_volume(data, grad, dmode=D.DMODE[data.shape[-1]])
-    except Exception:
-        R.close()
-        raise
-    return R
-
-
-def dev(a):
-    """the array's bytes in device memory (a torch tensor that owns them)"""
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
-
-
-def stream_arg(s):
-    return ctypes.c_void_p(s.cuda_stream)
-
-
-def busy(s, work):
-    """a few milliseconds of work on stream s, so that what is enqueued behind it has not started when the next call is made"""
-    import torch
-    with torch.cuda.stream(s):
-        for _ in range(24):
-            work.add_(1)
-
-
-class Guarded:
-    """nbytes of device memory between guard bytes; `shift` more bytes in front move the buffer off the allocation's
-    alignment (a multiple of the element size)"""
-
-    def __init__(self, nbytes, shift=0):
-        import torch
-        self.n, self.off = int(nbytes), D.GUARD + shift
-        self.t = torch.full((self.off + self.n + D.GUARD,), 0xA5, dtype=torch.uint8, device="cuda")
-        self.ptr = self.t.data_ptr() + self.off
-
-    def take(self, dtype, shape, what=""):
-        h = self.t.cpu().numpy()
-        assert (h[:self.off] == 0xA5).all(), "%s: bytes in front of the buffer were written" % what
-        assert (h[self.off + self.n:] == 0xA5).all(), "%s: bytes behind the buffer were written" % what
-        return h[self.off:self.off + self.n].copy().view(dtype).reshape(shape)
-
-
-def download_device(R, step=-1, stream=None, want_grad=True, shift=0, sync=True):
-    """download_timestep_device into guarded buffers -> (data, grad or None); sync False: (the buffers, a function that
-    reads them)"""
-    import torch
+def guarded_buffers(R, want_grad=True, shift=0):
+    """the guarded buffers a download of a step of R's series takes: (data's, normals' or None, a function that reads them).
+    Making them waits for the device (Guarded), so a test that lets no host wait between two calls makes them first"""
     _, (sx, sy, sz), ne, dt, _ = R.timestep_box()
     nv = sx * sy * sz
     gd = Guarded(nv * ne * dt.itemsize, shift * dt.itemsize)
     gg = Guarded(nv * 3, shift) if want_grad else None
-    R.download_timestep_device(gd.ptr, gg.ptr if gg else None, step, stream)
 
     def read():
         return gd.take(dt, (sz, sy, sx, ne), "data"), (gg.take(np.uint8, (sz, sy, sx, 3), "grad") if gg else None)
+    return gd, gg, read
+
+
+def download_device(R, step=-1, stream=None, want_grad=True, shift=0, sync=True, bufs=None):
+    """download_timestep_device into guarded buffers (bufs, or new ones) -> (data, grad or None); sync False: (the buffers, a
+    function that reads them), and with bufs given the call enqueues the download and waits for nothing"""
+    import torch
+    gd, gg, read = bufs or guarded_buffers(R, want_grad, shift)
+    R.download_timestep_device(gd.ptr, gg.ptr if gg else None, step, stream)
     if not sync:
         return (gd, gg), read
-    torch.cuda.synchronize()
+    torch.cuda.synchronize()                                # the download ran on the context's stream, or the caller's: read-back
     return read()
 
 
@@ -144,26 +92,6 @@ def test_rows_longer_than_a_workgroups_run(gpu_renderer_factory, dtype, dims):
 
 # ---- 2. bricked and shuffled uploads
 
-def bricked(smk, data, grad, order):
-    """(smk_volume_desc array, keep-alive list) of the volume cut at its midpoints into 2 x 2 x 2 unequal bricks, handed over
-    in `order`"""
-    nz, ny, nx, _ = data.shape
-    dims, m = (nx, ny, nz), float(max(nx, ny, nz))
-    cuts = [(0, n // 2, n) for n in dims]
-    boxes = [[(cuts[a][i[a]], cuts[a][i[a] + 1]) for a in range(3)] for i in np.ndindex(2, 2, 2)]
-    descs, keep = (smk.binding.VolumeDesc * 8)(), []
-    for d, k in zip(descs, order):
-        (x0, x1), (y0, y1), (z0, z1) = boxes[k]
-        d.xiSize, d.yiSize, d.ziSize = x1 - x0, y1 - y0, z1 - z0
-        d.xfSize, d.yfSize, d.zfSize = (x1 - x0) / m, (y1 - y0) / m, (z1 - z0) / m
-        d.xiPos, d.yiPos, d.ziPos = x0, y0, z0
-        d.xfPos, d.yfPos, d.zfPos = x0 / m, y0 / m, z0 / m
-        sub = [np.ascontiguousarray(a[z0:z1, y0:y1, x0:x1]) for a in (data, grad)]
-        keep += sub
-        d.data, d.grad = sub[0].ctypes.data, sub[1].ctypes.data
-    return descs, keep
-
-
 @pytest.mark.parametrize("dtype, nelts", [("u8", 3), ("f32", 4), ("u16", 3)])
 def test_bricked_and_shuffled_upload(gpu_renderer_factory, smk, dtype, nelts):
     data, grad = D.volume(dtype, nelts, BIG)
@@ -210,21 +138,9 @@ def test_shards(gpu_renderer_factory, dtype, nelts, nranks):
 
 # ---- 4. the ring
 
-def ring(factory, dtype, nelts=3, cap=4, dims=D.SMALL):
-    """a context with step 0 = seed 1 (current) and step 1 = seed 2 resident"""
-    a, b = D.volume(dtype, nelts, dims, 1), D.volume(dtype, nelts, dims, 2)
-    R = context(factory, a[0], a[1], cap=cap)
-    try:
-        R.upload_timestep(1, b[0], b[1], dmode=D.DMODE[nelts])
-    except Exception:
-        R.close()
-        raise
-    return R, a, b
-
-
 @pytest.mark.parametrize("dtype", ["u8", "f32", "u16"])
 def test_steps_by_id_and_current(gpu_renderer_factory, dtype):
-    R, a, b = ring(gpu_renderer_factory, dtype)
+    R, a, b = ring(gpu_renderer_factory, D.volume(dtype, 3, D.SMALL, 1), D.volume(dtype, 3, D.SMALL, 2))
     ea, eb = D.expected(*a), D.expected(*b)
     assert not np.array_equal(D.bits(ea[0]), D.bits(eb[0]))
     try:
@@ -242,19 +158,20 @@ def test_device_upload_on_one_stream_download_on_another(gpu_renderer_factory):
     import torch
     a, b = D.volume("u8", 3, BIG, 1), D.volume("u8", 3, BIG, 2)
     up, ds = torch.cuda.Stream(), torch.cuda.Stream()
-    work = torch.zeros(1 << 28, dtype=torch.uint8, device="cuda")
+    work = out_buffer(1 << 28, np.uint8)
     d, g = dev(b[0]), dev(b[1])
     R = context(gpu_renderer_factory, a[0], a[1], cap=2)
     try:
-        torch.cuda.synchronize()
+        bufs = guarded_buffers(R)                           # (made before the streams start: making them waits for the device)
+        torch.cuda.synchronize()                            # nothing is in flight when the two streams start
         busy(up, work)
         R.upload_timestep_device(5, d.data_ptr(), BIG, 3, 0, g.data_ptr(), dmode="VGH", stream=stream_arg(up))
-        _, read = download_device(R, 5, stream_arg(ds), sync=False)        # no host wait in between
-        ds.synchronize()
+        _, read = download_device(R, 5, stream_arg(ds), sync=False, bufs=bufs)     # no host wait in between
+        ds.synchronize()                                    # the download's stream alone: it waited for the upload on the device
         data, grad = read()
         same(data, b[0], "the step uploaded on the other stream")
         same(grad, b[1], "... its normals")
-        torch.cuda.synchronize()
+        torch.cuda.synchronize()                            # stream `up` has ended before its work buffer goes
     finally:
         R.close()
 
@@ -263,16 +180,17 @@ def test_an_upload_into_the_slot_waits_for_the_download(gpu_renderer_factory):
     import torch
     a, b, c = (D.volume("f32", 2, BIG, s) for s in (1, 2, 3))
     s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
-    work = torch.zeros(1 << 28, dtype=torch.uint8, device="cuda")
+    work = out_buffer(1 << 28, np.uint8)
     d, g = dev(c[0]), dev(c[1])
     R = context(gpu_renderer_factory, a[0], a[1], cap=2)
     try:
         R.upload_timestep(5, b[0], b[1], dmode="V1G")
-        torch.cuda.synchronize()
+        bufs = guarded_buffers(R)                           # (made before the streams start: making them waits for the device)
+        torch.cuda.synchronize()                            # nothing is in flight when the two streams start
         busy(s1, work)
-        _, read = download_device(R, 5, stream_arg(s1), sync=False)
+        _, read = download_device(R, 5, stream_arg(s1), sync=False, bufs=bufs)     # behind the busy work, no host wait
         R.upload_timestep_device(5, d.data_ptr(), BIG, 2, 1, g.data_ptr(), dmode="V1G", stream=stream_arg(s2))
-        torch.cuda.synchronize()
+        torch.cuda.synchronize()                            # both streams: read-back
         data, grad = read()
         same(data, b[0], "the step the download was asked of")
         same(grad, b[1], "... its normals")
@@ -368,9 +286,8 @@ def test_derivatives_of_a_blend_on_the_device(gpu_renderer_factory, O):
         R.download_timestep_device(gd.ptr, None, 2)         # (on the context's stream, as the prep entries below)
         torch.cuda.synchronize()                            # torch's stream is not the context's: wait on both sides of its copy
         s0 = gd.t[gd.off:gd.off + nv * 3].view(nz, ny, nx, 3)[..., 0].contiguous()         # channel 0, a strided device copy
-        vgh = torch.zeros((nz, ny, nx, 3), dtype=torch.uint8, device="cuda")
-        nrm = torch.zeros((nz, ny, nx, 3), dtype=torch.uint8, device="cuda")
-        torch.cuda.synchronize()
+        vgh = out_buffer((nz, ny, nx, 3), np.uint8)
+        nrm = out_buffer((nz, ny, nx, 3), np.uint8)           # (these wait for s0's copy too)
         R.make_vgh_device(s0.data_ptr(), 0, dims, 1, vgh.data_ptr(), None)
         R.normals_vgh_device(vgh.data_ptr(), 3, dims, 0, nrm.data_ptr())
         R.upload_timestep_device(3, vgh.data_ptr(), dims, 3, 0, nrm.data_ptr(), dmode="VGH")
@@ -385,8 +302,7 @@ def test_derivatives_of_a_blend_on_the_device(gpu_renderer_factory, O):
 # ---- 8. refusals
 
 def test_refusals(gpu_renderer_factory, smk):
-    import torch
-    buf = torch.zeros(1 << 16, dtype=torch.uint8, device="cuda")
+    buf = out_buffer(1 << 16, np.uint8)
     R = gpu_renderer_factory()
     try:
         host = np.zeros(16, np.uint8)

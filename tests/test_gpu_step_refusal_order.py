@@ -27,9 +27,8 @@ import pytest
 
 import _step_merge_h_ref as H
 import _tblend_ref as T
-from test_gpu_step_block import dev
-from test_gpu_step_merge_h_shard import Unchanged, context
-from test_gpu_step_shard import words_buf
+from _gpu_mem import dev_ptr as dev, words_buf
+from _step_gpu import UndisturbedHalos, rank_context
 
 pytestmark = pytest.mark.gpu
 DIMS, NRANKS, HALO, RING = (37, 13, 11), 2, 3, 3
@@ -43,7 +42,6 @@ def refused(calls, smk):
 
 
 def test_the_earlier_refusal_speaks(gpu_renderer_factory, smk):
-    import torch
     from _scenes import push_scene
     F = H.fields("u8", 3, DIMS, 0)
     data4, grad = H.source_step(F[..., :2], 1)                      # two fields, G and H
@@ -52,7 +50,6 @@ def test_the_earlier_refusal_speaks(gpu_renderer_factory, smk):
     ptrs = [h[0] for h in held[:3]]                                 # (byte fields: any address is aligned)
     flt = held[3][0]                                                # a float scalar: flt + 2 is not aligned
     w = words_buf()
-    torch.cuda.synchronize()
     p = w.data_ptr()
     whole = smk.smk_block((0, 0, 0), DIMS)
     bad = (DIMS[0] + 1, DIMS[1], DIMS[2])
@@ -60,14 +57,14 @@ def test_the_earlier_refusal_speaks(gpu_renderer_factory, smk):
     count_h = "1 fields for a series of nelts 4 with add_h 1: the fields are nelts - 1 - add_h = 2"
 
     def made(data, nranks):
-        C = context(gpu_renderer_factory, DIMS, data, grad, 1, 0, nranks, HALO, cap=RING, opts=(("kernel", 1),))
+        C = rank_context(gpu_renderer_factory, DIMS, data, grad, H.MODE[(data.shape[-1] - 2, 1)], 0, nranks, HALO, cap=RING, opts=(("kernel", 1),))
         push_scene(C, T.scene(np.ascontiguousarray(data[..., :3]), grad), upload=False)
         return C
 
     # ---- rank 0 of 2, nelts 4: the merge and the merge with H, from a step and from blocks
     C = made(data4, NRANKS)
     try:
-        with Unchanged(C):
+        with UndisturbedHalos(C, downloads=False):
             refused((
                 # smk_step_extremes_device, the merge's kind
                 (lambda: C.step_extremes_device(7, 99, None), "smk_step_extremes_device: kind 7 is neither"),
@@ -116,7 +113,7 @@ def test_the_earlier_refusal_speaks(gpu_renderer_factory, smk):
     # ---- rank 0 of 2, nelts 3: the derive, from a step and from a block
     C = made(data3, NRANKS)
     try:
-        with Unchanged(C):
+        with UndisturbedHalos(C, downloads=False):
             refused((
                 (lambda: C.step_extremes_device(DERIVE, 99, None), "smk_step_extremes_device: d_words is NULL"),
                 (lambda: C.block_extremes_device(DERIVE, ptrs[:1], 0, None, None), "smk_block_extremes_device: d_words is NULL"),
@@ -138,7 +135,7 @@ def test_the_earlier_refusal_speaks(gpu_renderer_factory, smk):
     # ---- the unsharded context, nelts 4: the merges of dense fields of the whole volume
     C = made(data4, 1)
     try:
-        with Unchanged(C):
+        with UndisturbedHalos(C, downloads=False):
             refused((
                 (lambda: C.upload_timestep_fields_device(1, None, 1, bad), "smk_upload_timestep_fields_device: d_fields is NULL"),
                 (lambda: C.upload_timestep_fields_device(1, ptrs[:2], 1, bad), "2 fields for a series of nelts 4: the fields are nelts - 1 = 3"),
@@ -155,7 +152,7 @@ def test_the_earlier_refusal_speaks(gpu_renderer_factory, smk):
     # ---- the unsharded context, nelts 3: the derive of a dense scalar of the whole volume
     C = made(data3, 1)
     try:
-        with Unchanged(C):
+        with UndisturbedHalos(C, downloads=False):
             refused((
                 (lambda: C.upload_timestep_scalar_device(1, None, 7, bad), "smk_upload_timestep_scalar_device: d_scalar is NULL"),
                 (lambda: C.upload_timestep_scalar_device(1, flt + 2, 7, bad), "scalar_dtype 7 is none of"),

@@ -55,7 +55,7 @@ def steps():
     host = {i: (rng.integers(0, 256, (nz, ny, nx, 3), dtype=np.uint8), rng.integers(0, 256, (nz, ny, nx, 3), dtype=np.uint8))
             for i in (A, B, THIRD, OUT)}
     dense = [torch.from_numpy(rng.integers(0, 256, (nz, ny, nx), dtype=np.uint8)).cuda() for _ in range(2)]
-    torch.cuda.synchronize()
+    torch.cuda.synchronize()                                      # the dense arrays are on the device before a context reads them
     return host, dense
 
 

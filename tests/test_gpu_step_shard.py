@@ -8,135 +8,13 @@ import ctypes
 import numpy as np
 import pytest
 
-import _step_read_ref as D
 import _step_shard_ref as S
 import _tblend_ref as T
+from _gpu_mem import dev_ptr as dev, merged, words_buf
+from _step_gpu import (RAN, SORT_LAST_TOL, UndisturbedHalos as Undisturbed, close, dmode, export, fsz, one_call, params, pert_need, pert_scene,
+                       probe_at, rank_context, ranks_of, reference_of_source as reference, same_bits as same, write_shard)
 
 pytestmark = pytest.mark.gpu
-MODE = {2: "V1G", 3: "V2G", 4: "V3G"}
-# A merged sharded frame against the unsharded frame.  The sharded time-step test, tests/test_gpu_timesteps.py::
-# test_shards_switch_and_merge, compares merged shards with merged FRESH shards, exactly, and has no tolerance against the
-# unsharded frame to take; that exact comparison is made below too.  Against the unsharded frame this is the sort-last
-# tolerance of tests/test_gpu_shadow_shards.py (TOL), the tightest one the suite uses for that comparison
-SORT_LAST_TOL = 2e-5
-
-
-def same(got, want, what=""):
-    got, want = D.bits(got), D.bits(want)
-    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.dtype, want.dtype, got.shape, want.shape)
-    bad = np.argwhere(got != want)
-    assert not len(bad), "%s: %d of %d values differ, first at %s: got %#x, want %#x" % (
-        what, len(bad), got.size, tuple(bad[0]), int(got[tuple(bad[0])]), int(want[tuple(bad[0])]))
-
-
-def fsz(dims):
-    m = float(max(dims))
-    return tuple(float(np.float32(n / m)) for n in dims)
-
-
-def dmode(kind, nelts):
-    return "VGH" if kind == "derive" else MODE[nelts]
-
-
-def context(factory, kind, dims, data, grad, rank=0, nranks=1, halo=1, cap=4, opts=()):
-    """a context (one rank of `nranks`, or unsharded) whose step 0 is (data, grad)"""
-    R = factory()
-    try:
-        if nranks > 1:
-            R.set_shard(rank, nranks)
-            R.set_option("halo", halo)
-        for k, v in opts:
-            R.set_option(k, v)
-        R.set_timestep_cache(cap)
-        R.upload_volume(data, grad, fsize=fsz(dims), dmode=dmode(kind, data.shape[-1]))
-    except Exception:
-        R.close()
-        raise
-    return R
-
-
-def ranks_of(factory, kind, dims, data, grad, nranks, halo, cap=4, opts=()):
-    rs = []
-    try:
-        for r in range(nranks):
-            rs.append(context(factory, kind, dims, data, grad, r, nranks, halo, cap, opts))
-    except Exception:
-        close(rs)
-        raise
-    return rs
-
-
-def close(rs):
-    for R in rs:
-        R.close()
-
-
-def words_buf(n=1):
-    import torch
-    return torch.full((n, 8), 0x5a5a5a5a, dtype=torch.int32, device="cuda")
-
-
-def export(R, kind, src, compat=1, stream=None):
-    import torch
-    w = words_buf()
-    torch.cuda.synchronize()
-    R.step_extremes_device(0 if kind == "derive" else 1, src, w.data_ptr(), compat=compat, stream=stream)
-    torch.cuda.synchronize()
-    return w.cpu().numpy()[0]
-
-
-def one_call(R, kind, src, out, compat=1, blur=0, stream=None):
-    if kind == "derive":
-        R.derive_timestep(src, out, compat, blur, stream=stream)
-    else:
-        R.merge_timestep(src, out, stream=stream)
-
-
-def write_shard(R, kind, src, out, d_words, compat=1, blur=0, stream=None):
-    if kind == "derive":
-        R.derive_timestep_shard(src, out, d_words, compat, blur, stream=stream)
-    else:
-        R.merge_timestep_shard(src, out, d_words, stream=stream)
-
-
-_REF = {}
-
-
-def reference(factory, kind, ring, dims, nf=2, compat=1, blur=0, normals=True):
-    """what the one-call entry makes of the case's source on an unsharded context, made once and shared:
-    (source data, source normals, result data, result normals, the unsharded export's words, probe(cells) of the result)"""
-    key = (kind, ring, dims, nf, compat, blur, normals)
-    if key not in _REF:
-        data, grad = S.source(kind, ring, dims, nf)
-        grad = grad if normals else None
-        U = context(factory, kind, dims, data, grad)
-        try:
-            one_call(U, kind, 0, 1, compat, blur)
-            got = U.download_timestep(1)
-            words = export(U, kind, 0, compat)
-            cells = S.cells_of((0, 0, 0), dims)
-            probe = U.probe_step(cells, 1)
-            assert probe[2].all()
-        finally:
-            U.close()
-        for a in got + probe[:2]:
-            a.setflags(write=False)
-        _REF[key] = (data, grad, got[0], got[1], words, probe)
-    return _REF[key]
-
-
-def probe_at(ref_probe, dims, cells):
-    """the rows of the unsharded probe of every cell of the volume that belong to `cells`"""
-    nx, ny, nz = dims
-    idx = (cells[:, 0] * (ny - 1) + cells[:, 1]) * (nz - 1) + cells[:, 2]      # (cells_of's order: x slowest)
-    return ref_probe[0][idx], ref_probe[1][idx]
-
-
-def params(kind, i):
-    """(compat, blur) of case i: every derive flag takes both values over the case list"""
-    return ((1, 0), (0, 1), (1, 1), (0, 0))[i % 4] if kind == "derive" else (1, 0)
-
-
 CASES = [pytest.param(i, ring, id="%s-%s" % (S.CASE_IDS[i], ring)) for i in range(len(S.CASES)) for ring in S.RINGS]
 
 
@@ -147,7 +25,7 @@ def test_the_ranks_words_combine_to_the_unsharded_words(gpu_renderer_factory, ca
     kind, dims, nranks, halo = S.CASES[case]
     compat, _ = params(kind, case)
     data, grad, _, _, want, _ = reference(gpu_renderer_factory, kind, ring, dims, compat=compat, blur=params(kind, case)[1])
-    rs = ranks_of(gpu_renderer_factory, kind, dims, data, grad, nranks, halo)
+    rs = ranks_of(gpu_renderer_factory, dims, data, grad, dmode(kind, data.shape[-1]), nranks, halo)
     try:
         words = [export(R, kind, 0, compat) for R in rs]
     finally:
@@ -171,18 +49,15 @@ TWO_CALL.append(("merge", "f32", 3, 1))                     # (four-channel f32 
 
 @pytest.mark.parametrize("kind, ring, nf, kernel", TWO_CALL)
 def test_export_and_write_on_an_unsharded_context_is_the_one_call_entry(gpu_renderer_factory, kind, ring, nf, kernel):
-    import torch
     from _scenes import push_scene
-    from test_gpu_tblend import RAN
     dims = (37, 13, 11)                                     # (odd x and y: a pad column and row of 8-byte voxels)
     data, grad = S.source(kind, ring, dims, nf)
     sc = T.scene(np.ascontiguousarray(data[..., :3]), grad)
-    R = context(gpu_renderer_factory, kind, dims, data, grad, opts=(("kernel", kernel),))
+    R = rank_context(gpu_renderer_factory, dims, data, grad, dmode(kind, data.shape[-1]), opts=(("kernel", kernel),))
     try:
         push_scene(R, sc, upload=False)
         one_call(R, kind, 0, 1, 1, 1)
         w = words_buf()
-        torch.cuda.synchronize()
         R.step_extremes_device(0 if kind == "derive" else 1, 0, w.data_ptr())
         write_shard(R, kind, 0, 2, w.data_ptr(), 1, 1)
         assert R.timestep_halo(1) == R.timestep_halo(2) == R.timestep_halo(0) == 1
@@ -208,7 +83,7 @@ def check_ranks(factory, kind, ring, dims, nranks, halo, nf=2, compat=1, blur=0,
     from simian_spacemonkey_amd import sortlast
     data, grad, wdata, wgrad, wwords, wprobe = reference(factory, kind, ring, dims, nf, compat, blur, normals)
     reach = S.REACH[kind]
-    rs = ranks_of(factory, kind, dims, data, grad, nranks, halo)
+    rs = ranks_of(factory, dims, data, grad, dmode(kind, data.shape[-1]), nranks, halo)
     try:
         words = sortlast.stencil_timestep_local(rs, kind, 0, 1, compat=compat, blur=blur)
         assert np.array_equal(words.cpu().numpy()[nranks], wwords)
@@ -264,27 +139,12 @@ def test_a_context_without_normals(gpu_renderer_factory, kind, ring, nf):
 
 # ---- 5. frames
 
-def merged(rs, sc):
-    import torch
-    npix = sc.width * sc.height
-    layers = torch.zeros((len(rs), npix, 4), dtype=torch.float32, device="cuda")
-    out = torch.zeros((npix, 4), dtype=torch.float32, device="cuda")
-    torch.cuda.synchronize()
-    for r, R in enumerate(rs):
-        R.render_device(layers[r].data_ptr(), None, None)
-    torch.cuda.synchronize()
-    rs[0].composite_over_device(layers.data_ptr(), len(rs), rs[0].shard_order(len(rs)), npix, out.data_ptr(), None)
-    torch.cuda.synchronize()
-    return layers.cpu().numpy().reshape(len(rs), sc.height, sc.width, 4), out.cpu().numpy().reshape(sc.height, sc.width, 4)
-
-
 @pytest.mark.parametrize("bricks", [0, 1])
 @pytest.mark.parametrize("kernel", [1, 2], ids=["gather", "slice-ring"])
 @pytest.mark.parametrize("kind, ring, halo", [("derive", "u8", 3), ("derive", "f32", 4), ("merge", "u16", 2)])
 def test_frames_of_the_produced_step(gpu_renderer_factory, kind, ring, halo, kernel, bricks):
     from _scenes import push_scene
     from simian_spacemonkey_amd import sortlast
-    from test_gpu_tblend import RAN
     dims, nranks = (75, 21, 19), 2
     data, grad, wdata, wgrad, _, _ = reference(gpu_renderer_factory, kind, ring, dims)
     opts = (("kernel", kernel), ("bricks", bricks), ("slab_split", 1))
@@ -296,18 +156,18 @@ def test_frames_of_the_produced_step(gpu_renderer_factory, kind, ring, halo, ker
         lay, out = merged(rs, sc)
         assert all(R.last_frame_info()[0] == RAN[kernel] for R in rs) and all(R.stat("slab_failures") == 0 for R in rs)
         return lay, out
-    up = ranks_of(gpu_renderer_factory, kind, dims, wdata, wgrad, nranks, halo, opts=opts)      # ... that UPLOADED the unsharded result
+    up = ranks_of(gpu_renderer_factory, dims, wdata, wgrad, dmode(kind, wdata.shape[-1]), nranks, halo, opts=opts)      # ... that UPLOADED the unsharded result
     try:
         want_layers, want = frames(up)
     finally:
         close(up)
-    U = context(gpu_renderer_factory, kind, dims, wdata, wgrad, opts=opts)
+    U = rank_context(gpu_renderer_factory, dims, wdata, wgrad, dmode(kind, wdata.shape[-1]), opts=opts)
     try:
         push_scene(U, sc, upload=False)
         whole = U.render()
     finally:
         U.close()
-    rs = ranks_of(gpu_renderer_factory, kind, dims, data, grad, nranks, halo, opts=opts)
+    rs = ranks_of(gpu_renderer_factory, dims, data, grad, dmode(kind, data.shape[-1]), nranks, halo, opts=opts)
     try:
         frames(rs)                                          # (the source rendered first: flags and plans of another step exist)
         keep = sortlast.stencil_timestep_local(rs, kind, 0, 1)
@@ -327,28 +187,16 @@ def test_frames_of_the_produced_step(gpu_renderer_factory, kind, ring, halo, ker
 
 # ---- 6. the valid halo
 
-def pert_scene(data, grad):
-    sc = T.scene(data, grad, pert=True)
-    sc.pert_w = (.04, .02, 0, 0)
-    return sc
-
-
-def pert_need(dims, w):
-    return [1 + int(np.ceil(0.5 * (abs(w[0]) + abs(w[1])) * n)) for n in dims]
-
-
 def test_the_valid_halo_follows_uploads_blends_and_stencils(gpu_renderer_factory, smk):
-    import torch
     dims, nranks, halo = (75, 21, 19), 2, 3
     data, grad = S.source("derive", "u8", dims)
     data2, grad2 = S.source("derive", "u8", dims, seed=1)
-    R = context(gpu_renderer_factory, "derive", dims, data, grad, 1, nranks, halo, cap=6)
+    R = rank_context(gpu_renderer_factory, dims, data, grad, "VGH", 1, nranks, halo, cap=6)
     try:
         R.upload_timestep(1, data2, grad2, fsize=fsz(dims), dmode="VGH")
         R.blend_timesteps(0, 1, 0.4, 2)
         assert [R.timestep_halo(t) for t in (0, 1, 2)] == [3, 3, 3] and R.timestep_halo() == 3
         w = words_buf()
-        torch.cuda.synchronize()
         R.step_extremes_device(1, 2, w.data_ptr())          # (a lone rank: its own words are all it combines)
         R.merge_timestep_shard(2, 3, w.data_ptr())
         assert R.timestep_halo(3) == 2
@@ -382,7 +230,7 @@ def test_a_frame_compares_its_need_with_the_shown_steps_valid_halo(gpu_renderer_
     need = pert_need(dims, sc.pert_w)
     assert need[0] == 2                                     # x is the split axis: halo 3 - reach 2 < 2 <= halo 4 - reach 2
     opts = (("kernel", 1),)
-    rs = ranks_of(gpu_renderer_factory, "derive", dims, data, grad, nranks, halo, opts=opts)
+    rs = ranks_of(gpu_renderer_factory, dims, data, grad, "VGH", nranks, halo, opts=opts)
     try:
         for R in rs:
             push_scene(R, sc, upload=False)
@@ -411,7 +259,7 @@ def test_a_frame_compares_its_need_with_the_shown_steps_valid_halo(gpu_renderer_
         del keep
     finally:
         close(rs)
-    up = ranks_of(gpu_renderer_factory, "derive", dims, wdata, wgrad, nranks, halo, opts=opts)
+    up = ranks_of(gpu_renderer_factory, dims, wdata, wgrad, "VGH", nranks, halo, opts=opts)
     try:
         for R in up:
             push_scene(R, sc, upload=False)
@@ -424,36 +272,8 @@ def test_a_frame_compares_its_need_with_the_shown_steps_valid_halo(gpu_renderer_
 
 # ---- 7. refusals and the ring's rule
 
-class Undisturbed:
-    """the refusals inside the block change nothing: the context renders, lists and downloads its steps and reports their valid
-    halos as before"""
-
-    def __init__(self, R):
-        self.R = R
-
-    def state(self):
-        R = self.R
-        ids = R.timesteps()
-        return R.render(), ids, [R.download_timestep(t) for t in ids[1]], [R.timestep_halo(t) for t in ids[1]]
-
-    def __enter__(self):
-        self.before = self.state()
-        return self
-
-    def __exit__(self, et, ev, tb):
-        if et is not None:
-            return False
-        after = self.state()
-        assert np.array_equal(after[0], self.before[0]) and after[1] == self.before[1] and after[3] == self.before[3]
-        for (d0, g0), (d1, g1) in zip(self.before[2], after[2]):
-            same(d1, d0, "a step after the refusals")
-            same(g1, g0, "its normals after the refusals")
-        return False
-
-
 @pytest.mark.parametrize("kind", ["derive", "merge"])
 def test_refusals_leave_the_ring_unchanged(gpu_renderer_factory, smk, kind):
-    import torch
     from _scenes import push_scene
     dims, nranks = (37, 13, 11), 2
     reach = S.REACH[kind]
@@ -463,7 +283,6 @@ def test_refusals_leave_the_ring_unchanged(gpu_renderer_factory, smk, kind):
     data2, grad2 = S.source(kind, "u8", dims, seed=1)
     sc = T.scene(data, grad)
     w = words_buf()
-    torch.cuda.synchronize()
     p = w.data_ptr()
     R = gpu_renderer_factory()
     try:
@@ -474,7 +293,7 @@ def test_refusals_leave_the_ring_unchanged(gpu_renderer_factory, smk, kind):
     finally:
         R.close()
     # a ring of two slots, both held: the source and the current step leave no slot for the output
-    R = context(gpu_renderer_factory, kind, dims, data, grad, 0, nranks, reach + 1, cap=2, opts=(("kernel", 1),))
+    R = rank_context(gpu_renderer_factory, dims, data, grad, dmode(kind, data.shape[-1]), 0, nranks, reach + 1, cap=2, opts=(("kernel", 1),))
     try:
         push_scene(R, sc, upload=False)
         R.upload_timestep(1, data2, grad2, fsize=fsz(dims), dmode=dmode(kind, 3))
@@ -496,7 +315,7 @@ def test_refusals_leave_the_ring_unchanged(gpu_renderer_factory, smk, kind):
     finally:
         R.close()
     # the source's valid halo below reach + 1
-    R = context(gpu_renderer_factory, kind, dims, data, grad, 0, nranks, reach, cap=3, opts=(("kernel", 1),))
+    R = rank_context(gpu_renderer_factory, dims, data, grad, dmode(kind, data.shape[-1]), 0, nranks, reach, cap=3, opts=(("kernel", 1),))
     try:
         push_scene(R, sc, upload=False)
         with Undisturbed(R):
@@ -539,7 +358,7 @@ def test_on_a_stream_of_the_callers(gpu_renderer_factory, kind):
     opts = (("kernel", 1),)
 
     def run(side, other):
-        rs = ranks_of(gpu_renderer_factory, kind, dims, data, grad, nranks, halo, opts=opts)
+        rs = ranks_of(gpu_renderer_factory, dims, data, grad, dmode(kind, data.shape[-1]), nranks, halo, opts=opts)
         try:
             for R in rs:
                 push_scene(R, sc, upload=False)
@@ -567,10 +386,3 @@ def test_on_a_stream_of_the_callers(gpu_renderer_factory, kind):
     same(got[2][0][0], wdata[g0r[2]:g1r[2], g0r[1]:g1r[1], g0r[0]:g1r[0]], "rank 0's region")
     same(got[2][nranks][0], data2[g0r[2]:g1r[2], g0r[1]:g1r[1], g0r[0]:g1r[0]], "the new step 0")
 
-
-def dev(a):
-    """(device address, the torch tensor that owns it) of the array's bytes"""
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
-    torch.cuda.synchronize()
-    return t.data_ptr(), t

@@ -11,12 +11,12 @@ import numpy as np
 import pytest
 
 import _tblend_ref as T
-from test_gpu_timesteps import _merged, fresh_frame
+from _step_gpu import RAN, fresh_frame, merged_frame as _merged
+from _trex_series import write_series
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DMODE = {1: "V1", 2: "V1G", 3: "VGH", 4: "V2GH"}
-RAN = {1: 1, 2: 2, 3: 4}               # option "kernel" -> what smk_last_frame_info reports
 GATHER = (("kernel", 1),)
 
 
@@ -241,7 +241,7 @@ def test_blend_on_a_second_stream_beside_frames_in_flight(gpu_renderer_factory):
     rend, bl = torch.cuda.Stream(), torch.cuda.Stream()
     R = ring(gpu_renderer_factory, sa, sb)
     try:
-        torch.cuda.synchronize()
+        torch.cuda.synchronize()                    # nothing is in flight when the streams start
         outs = []
 
         def frames(n, t):
@@ -261,7 +261,7 @@ def test_blend_on_a_second_stream_beside_frames_in_flight(gpu_renderer_factory):
         frames(2, 11)
         R.select_timestep(0)
         frames(1, 0)
-        torch.cuda.synchronize()
+        torch.cuda.synchronize()                    # both streams: read-back
         for i, (o, t) in enumerate(outs):
             same(o.cpu().numpy(), want[10 if (t == 11 and i >= 28) else t], "frame %d (step %d)" % (i, t))
         assert R.stat("slab_failures") == 0
@@ -279,7 +279,7 @@ def test_a_source_overwritten_right_after_the_blend_was_enqueued(gpu_renderer_fa
     rend, bl, up = torch.cuda.Stream(), torch.cuda.Stream(), torch.cuda.Stream()
     R = ring(gpu_renderer_factory, sa, sb)
     try:
-        torch.cuda.synchronize()
+        torch.cuda.synchronize()                    # nothing is in flight when the streams start
         outs = [torch.empty((sa.height, sa.width, 4), dtype=torch.float32, device="cuda") for _ in range(2)]
         R.blend_timesteps(0, 1, 0.3, 10, stream=ctypes.c_void_p(bl.cuda_stream))
         R.upload_timestep_device(0, dev[0].data_ptr(), sc.dims, 3, 1, dev[1].data_ptr(), fsize=tuple(float(f) for f in sc.fsize),
@@ -288,7 +288,7 @@ def test_a_source_overwritten_right_after_the_blend_was_enqueued(gpu_renderer_fa
         R.render_device(outs[0].data_ptr(), None, ctypes.c_void_p(rend.cuda_stream))
         R.select_timestep(0)
         R.render_device(outs[1].data_ptr(), None, ctypes.c_void_p(rend.cuda_stream))
-        torch.cuda.synchronize()
+        torch.cuda.synchronize()                    # the three streams: read-back
         same(outs[0].cpu().numpy(), want_mid, "the blend of the old step 0")
         same(outs[1].cpu().numpy(), want_c, "the new step 0")
     finally:
@@ -373,7 +373,6 @@ def _frames(prefix, n):
 def test_host_adapter_shows_fractional_time(tmp_path):
     """tests/host/tblend_main drives HipVolumeRenderable::setTimeFraction over a 3-step series; its frames are the ones the C
     ABI gives when the blend is made behind the adapter's back, and the ones of the restated blends drawn alone"""
-    from test_timesteps_cpu import write_series
     exe = os.path.join(ROOT, "tests", "host", "tblend_main")
     alone = os.path.join(ROOT, "tests", "host", "timestep_main")
     for e in (exe, alone):

@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 
 from _scenes import make_scene, push_scene, vgh_volume
+from _step_gpu import fresh_frame, merged_frame as _merged
+from _trex_series import write_series
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,21 +25,6 @@ def step_scene(seed, f32=True, kind="cfg3", **kw):
     vgh8, vghf, nrm = vgh_volume(32, seed)
     sc.data, sc.grad = (vghf if f32 else vgh8), nrm
     return sc
-
-
-def fresh_frame(factory, sc, opts=(), render=None):
-    R = factory()
-    try:
-        push_scene(R, sc)
-        for k, v in opts:
-            R.set_option(k, v)
-        if render:
-            return render(R)
-        out = R.render()
-        assert R.stat("slab_failures") == 0
-        return out
-    finally:
-        R.close()
 
 
 def upload_step(R, t, sc):
@@ -171,7 +158,7 @@ def test_asynchronous_upload_beside_frames_in_flight(gpu_renderer_factory):
     try:
         R.set_timestep_cache(2)
         push_scene(R, scs[0])
-        torch.cuda.synchronize()
+        torch.cuda.synchronize()                    # nothing is in flight when the two streams start
         outs, want = [], []
 
         def frame(t):
@@ -196,7 +183,7 @@ def test_asynchronous_upload_beside_frames_in_flight(gpu_renderer_factory):
             frame(2)
         R.select_timestep(1)
         frame(1)
-        torch.cuda.synchronize()
+        torch.cuda.synchronize()                    # both streams: read-back
         for i, (o, t) in enumerate(zip(outs, want)):
             got = o.cpu().numpy()
             assert np.array_equal(got, fresh[t]), "frame %d (step %d): max diff %g" % (i, t, np.abs(got - fresh[t]).max())
@@ -223,22 +210,6 @@ def test_shadows_and_perturbation_after_a_switch(gpu_renderer_factory, mode):
         assert np.array_equal(got, want), np.abs(got - want).max()
     finally:
         R.close()
-
-
-def _merged(rs, sc, shadow):
-    import torch
-    from simian_spacemonkey_amd import sortlast
-    if shadow:
-        return sortlast.render_shadow_frame_local(rs).cpu().numpy()
-    npix = sc.width * sc.height
-    layers = torch.zeros((len(rs), npix, 4), dtype=torch.float32, device="cuda")
-    out = torch.zeros((npix, 4), dtype=torch.float32, device="cuda")
-    for r, R in enumerate(rs):
-        R.render_device(layers[r].data_ptr(), None, None)
-    torch.cuda.synchronize()
-    rs[0].composite_over_device(layers.data_ptr(), len(rs), rs[0].shard_order(len(rs)), npix, out.data_ptr(), None)
-    torch.cuda.synchronize()
-    return out.cpu().numpy().reshape(sc.height, sc.width, 4)
 
 
 @pytest.mark.parametrize("shadow", [False, True])
@@ -291,7 +262,6 @@ def test_shards_switch_and_merge(gpu_renderer_factory, shadow):
 def test_host_adapter_follows_the_time_step(tmp_path):
     """tests/host/timestep_main drives HipVolumeRenderable through a 3-step .trex series as the key handler does; every
     draw() shows the step gluvv.volren.timestep names (before this, every step rendered the one uploaded first)"""
-    from test_timesteps_cpu import write_series
     exe = os.path.join(ROOT, "tests", "host", "timestep_main")
     assert os.path.exists(exe), "tests/host/timestep_main is not built: __graft_entry__.build() builds it"
     steps = [np.ascontiguousarray(vgh_volume(32, s)[0][..., 0]) for s in SEEDS]

@@ -7,6 +7,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from _trex_series import write_series
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "tests", "host")
 NEW = ["smk_set_timestep_cache", "smk_upload_timestep", "smk_upload_timestep_device", "smk_select_timestep",
@@ -39,26 +41,6 @@ def test_new_declarations_parse_as_c():
     p = subprocess.run(["cc", "-std=c99", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), "-x", "c", "-"],
                        input=probe, capture_output=True, text=True)
     assert p.returncode == 0, p.stderr
-
-
-def write_series(d, steps, shape=(16, 12, 10), tstart=3, cache=2, bricks=2):
-    """a .trex series as MetaVolume::writeAll would lay it out with time steps: <files>.<TTTT>.<BB> per brick (bricks
-    split along z), `steps` = list of [z][y][x] u8 volumes for tstart, tstart + 1, ..."""
-    nx, ny, nz = shape
-    bz = nz // bricks
-    name = os.path.join(d, "series")
-    lines = ["Data Set Name: series", "Data Set Files: %s" % name,
-             "Number of Time Steps: %d, %d, %d" % (len(steps), tstart, tstart + len(steps) - 1),
-             "Time Step Cache: %d" % cache, "Volume Size int: %d, %d, %d" % shape,
-             "Volume Size float: 1, %f, %f" % (ny / nx, nz / nx), "Number of Sub Volumes: %d" % bricks]
-    for b in range(bricks):
-        lines += ["SubVolume {", "Size int: %d, %d, %d" % (nx, ny, bz), "Size float: 1, %f, %f" % (ny / nx, bz / nx),
-                  "Pos int: 0, 0, %d" % (b * bz), "Pos float: 0, 0, %f" % (b * bz / nx), "}"]
-    open(name + ".trex", "w").write("\n".join(lines) + "\n")
-    for k, v in enumerate(steps):
-        for b in range(bricks):
-            np.ascontiguousarray(v[b * bz:(b + 1) * bz]).tofile("%s.%04d.%02d" % (name, tstart + k, b))
-    return name + ".trex"
 
 
 def test_trex_series_fields_round_trip(tmp_path):
